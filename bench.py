@@ -77,6 +77,8 @@ def parse():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL)")
     ap.add_argument("--same-device", action="store_true",
                     help="rehearsal only: every rank uses cuda:0 (needs --backend gloo; RCCL refuses duplicate devices)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="launch / rendezvous / collect path only: every rank joins the group, all-reduces a one and rank 0 "
                          "prints a line — no GPU is touched (CPU test of the self-launch; use with --backend gloo)")
@@ -221,6 +223,52 @@ def measured_traffic(cfg_name, kernel, n_local):
     return float(rec["hbm_bytes_per_launch"]), rec.get("issue"), rec.get("source", "")
 
 
+DUMP_BUDGET = 64 << 20   # bytes, all files of all ranks together
+
+
+def dump_outputs(d, f, r, world, rank):
+    """What the timed path handed its caller in its last step, as DIR/<name>.npy: the rendered class images, the raw and
+    normalised weights, the weight statistics {argmax, sum, mean, bottom_stddev}, the resample indices and the resampled
+    states (7 x particles, the filter's SoA rows).  Every value written is finite: a raw weight of NaN ("too much unknown",
+    include/tdr.h) is written as 0 with 0 in raw_weights_known (1 for a scored particle).
+    With several ranks, rank 0 writes the arrays every rank holds alike (the scan it rendered, the global weights and their
+    statistics) and every rank writes its own shard of the others as <name>_rank<r>.  A rank's files stay within its share
+    of DUMP_BUDGET: over it, the per-particle arrays are cut to a fixed, seeded sample whose indices go to
+    <name>_sample.npy."""
+    import numpy as np
+    import torch
+
+    torch.cuda.synchronize()
+    shard = f"_rank{rank}" if world > 1 else ""   # file-name suffix of this rank's own shard
+    arrays = {}   # name -> (array, particle axis or None, suffix)
+    if rank == 0:
+        info = f.info[:4].cpu()
+        arrays["scan"] = (r.last_images().float().cpu().numpy(), None, "")
+        stats = [info[:1].view(torch.int32).item()] + info[1:4].tolist()   # argmax is stored as int bits
+        arrays["weight_stats"] = (np.array(stats, np.float64), None, "")
+        arrays["weights"] = (f.weights().astype(np.float32), 0, "")
+    raw = f.raw_weights()
+    known = ~np.isnan(raw)
+    arrays["raw_weights"] = (np.where(known, raw, 0).astype(np.float32), 0, shard)
+    arrays["raw_weights_known"] = (known.astype(np.float32), 0, shard)
+    arrays["resample_idx"] = (f.resample_indices().astype(np.float64), 0, shard)
+    arrays["states"] = (f.st[:, :f.n_local].cpu().numpy().astype(np.float32), 1, shard)
+
+    budget = DUMP_BUDGET // world
+    total = sum(a.nbytes for a, _, _ in arrays.values())
+    fixed = sum(a.nbytes for a, ax, _ in arrays.values() if ax is None) + 4096   # + the files' headers
+    cut = sum(a.nbytes + 8 * a.shape[ax] for a, ax, _ in arrays.values() if ax is not None)   # + float64 sample indices
+    keep = 1.0 if total + 4096 <= budget else max(0.0, (budget - fixed) / cut)
+    os.makedirs(d, exist_ok=True)
+    for name, (a, ax, sfx) in arrays.items():
+        if ax is not None and keep < 1.0:
+            n = a.shape[ax]
+            sel = np.sort(np.random.default_rng(n).choice(n, int(n * keep), replace=False))
+            a = np.take(a, sel, axis=ax)
+            np.save(os.path.join(d, f"{name}_sample{sfx}.npy"), sel.astype(np.float64))
+        np.save(os.path.join(d, f"{name}{sfx}.npy"), np.ascontiguousarray(a))
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -348,6 +396,8 @@ def main():
         step()
     barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, f, r, world, rank)   # before the steps below reuse the filter
     trials_timed = (f.score_ctx.trial_calls() - trials0) if cfg.polar else 0
     tot_ms, launches = C.c_double(0), C.c_int64(0)
     k.lib.tdr_profile_score_ms(C.byref(tot_ms), C.byref(launches))
