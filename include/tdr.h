@@ -610,6 +610,51 @@ int tdr_map_save_rasters(tdr_map* m, const char* dir);
 int tdr_png_read_gray8_host(const char* path, uint8_t* px_out, int64_t capacity, int* w, int* h);
 int tdr_png_write_gray8_host(const char* path, const uint8_t* px, int w, int h);
 int tdr_map_load_rasters(tdr_map* m, const char* dir, int num_classes, float resolution, int center_x, int center_y);
+/* The static vector map: TopDownMap::loadSvg + getRasterMap + getClasses (src/top_down_map.cpp:22-31,
+ * 66-110, 328-365, 391-408), then the constructor's geometric layers and computeDists (:48-58) through the same device
+ * ingest as tdr_map_load_rasters.
+ *
+ * tdr_svg_parse_host (host only, no device needed): reads an SVG like the reference's nanosvg call
+ * (nsvgParseFromFile(path, "px", 96)) and returns what loadSvg keeps of it: size_out = the image's float width / height
+ * (after units and viewBox; H_f), and per subpath of every shape one polygon — its fill key (nanosvg's 0xBBGGRR colour
+ * & 0xFFFFFF; 0 for fill="none" and for an absent fill; TDR_SVG_NO_KEY for a gradient), the vertex range
+ * [offsets_out[p], offsets_out[p+1]) and vertices_out[v] = {x, H_f - y}: the start point and every segment's end point
+ * but the last (so a closed subpath loses the copy of its start, an open one its real last point).  Polygons come in
+ * document order (the reference reverses the subpaths of a shape; the fill does not depend on the order).
+ * Two calls: with keys_out == offsets_out == verts_out == NULL only the counts are written to *n_poly / *n_vert; then
+ * with arrays of at least those sizes (*n_poly / *n_vert = their capacities; offsets_out holds n_poly + 1 entries).
+ * Supported: svg (width / height in px pt pc mm cm in %, viewBox, preserveAspectRatio), g, path (all commands),
+ * rect (rx / ry), circle, ellipse, line, polyline, polygon, transform (matrix translate scale rotate skewX skewY),
+ * fill / style= / inheritance from g, defs (skipped), gradients.  Not: strokes, <style> sheets, <use>, text.  A file
+ * without a usable size, a non-finite coordinate or more than 2^27 path points: TDR_ERR_ARG. */
+#define TDR_SVG_NO_KEY 0xFFFFFFFFu
+int tdr_svg_parse_host(const char* path, float size_out[2], int64_t* n_poly, int64_t* n_vert, uint32_t* keys_out,
+                       int64_t* offsets_out, float* verts_out);
+/* getRasterMap + getClasses for polygons from anywhere, then the ingest (handle layer, HOST arrays): polygon p has the
+ * vertices verts[offsets[p] .. offsets[p+1]) ({x, y} pairs, offsets non-decreasing from 0) and the flattened class
+ * poly_class[p] (polygons of a class outside [0, num_classes) are skipped).  The map is int(height / resolution) x
+ * int(width / resolution) cells sampled at samplePts(center = (width / 2, height / 2), rot 0) (top_down_map.cpp:391-408);
+ * a cell is inside a polygon when the even-odd test of :336-347 says so, bit for bit (f32, no FMA, IEEE division).
+ * exclusive[n_excl] = params_.exclusive_classes (ids in [0, num_classes)): where a listed class c lies, every listed
+ * class u < c is cleared (:356-365).  planes_out: NULL, or HOST [num_classes][rows * cols] u8, column-major, the class
+ * planes before the distance transform (0 inside the class, 1 elsewhere).  center = map_center_.  Every argument is
+ * checked before any device work.  The fill relies on both sample tables rising (LinSpaced over a symmetric range always
+ * does); the host checks it and returns TDR_ERR_ARG if one ever decreased, instead of falling back to a linear count. */
+int tdr_map_load_polygons(tdr_map* m, const float* verts, const int64_t* poly_offsets, const int32_t* poly_class,
+                          int64_t n_poly, int width, int height, int num_classes, const int32_t* exclusive, int n_excl,
+                          float resolution, int center_x, int center_y, uint8_t* planes_out);
+/* The fill alone, for callers that ingest the planes themselves: the same arguments and checks, planes_out required
+ * (HOST [num_classes][rows * cols], column-major, 0 inside / 1 elsewhere); needs a device, no handle. */
+int tdr_polygon_planes(const float* verts, const int64_t* poly_offsets, const int32_t* poly_class, int64_t n_poly,
+                       int width, int height, int num_classes, const int32_t* exclusive, int n_excl, float resolution,
+                       uint8_t* planes_out);
+/* The constructor's SVG branch (:22-31): parse (tdr_svg_parse_host), class assignment like loadSvg (:77-103: LUT index
+ * cls collects the polygons whose key is fill_keys[cls] = c[0] << 16 | c[1] << 8 | c[2] of
+ * SemanticColorLut::unpackColor(ind2Color(cls)), into flattened class flatten_lut[cls]; entries outside
+ * [0, num_classes) are skipped), then tdr_map_load_polygons with width / height = int of the image's float size.  A file
+ * that does not parse leaves the handle as it was. */
+int tdr_map_load_svg(tdr_map* m, const char* path, const uint32_t* fill_keys, const int32_t* flatten_lut, int lut_size,
+                     int num_classes, const int32_t* exclusive, int n_excl, float resolution, int center_x, int center_y);
 
 int tdr_renderer_create(const int32_t* flatten_lut256, tdr_renderer** out);              /* scan_renderer.cpp:3-5 */
 void tdr_renderer_destroy(tdr_renderer* r);

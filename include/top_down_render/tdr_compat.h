@@ -147,13 +147,30 @@ class Mat {
 }  // namespace cv
 #endif
 
-// TopDownMap::Params::color_lut (top_down_map.h:56) is a semantics_manager type used only by the static-map loader
-// (SVG / colour PNG -> class image), which is outside the per-scan path.  The member exists so that
-// `params.color_lut = class_params.color_lut` (src/top_down_render.cpp:173) compiles unchanged.
+// TopDownMap::Params::color_lut (top_down_map.h:56) is a semantics_manager type: `params.color_lut =
+// class_params.color_lut` (src/top_down_render.cpp:173) compiles unchanged, and the SVG loader reads a class's fill
+// colour through it exactly like the reference (src/top_down_map.cpp:80-84): unpackColor(ind2Color(cls)).  Without
+// semantics_manager this stand-in carries a settable table: ind2Color(i) = the packed colour of LUT index i (0 outside
+// the table), unpackColor(packed) = its three bytes {bits 16-23, 8-15, 0-7}.  The SVG key of index i is then
+// packed & 0xFFFFFF; nanosvg stores #RRGGBB as 0xBBGGRR, so the red of an SVG (#ff0000) is the packed value 0x0000ff.
 #ifdef TDR_HAVE_SEMANTICS_MANAGER
 #include <semantics_manager/semantic_color_lut.h>
 #else
-class SemanticColorLut {};
+#include <array>
+#include <utility>
+class SemanticColorLut {
+ public:
+  SemanticColorLut() = default;
+  explicit SemanticColorLut(std::vector<uint32_t> packed) : packed_(std::move(packed)) {}
+  void setColors(std::vector<uint32_t> packed) { packed_ = std::move(packed); }
+  uint32_t ind2Color(int ind) const { return ind >= 0 && (size_t)ind < packed_.size() ? packed_[(size_t)ind] : 0u; }
+  static std::array<uint8_t, 3> unpackColor(uint32_t packed) {
+    return {(uint8_t)(packed >> 16), (uint8_t)(packed >> 8), (uint8_t)packed};
+  }
+
+ private:
+  std::vector<uint32_t> packed_;
+};
 #endif
 
 static_assert(sizeof(pcl::PointXYZI) == 32, "pcl::PointXYZI is 32 bytes (x,y,z,pad,intensity,pad,pad,pad)");

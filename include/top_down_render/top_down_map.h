@@ -1,8 +1,9 @@
 // TopDownMap — reference surface: include/top_down_render/top_down_map.h:52-102.  Holds the per-class truncated
 // distance maps + unknown mask on the GPU (tdr_map, include/tdr.h).  The reference builds these at load time from an
-// SVG / PNG / cache file (src/top_down_map.cpp:9-64, OpenCV + nanosvg): that ingest is outside the per-scan path
-// (SURVEY §8f N1), so here the distance maps are handed over with setDistanceMaps() in the same layout as the
-// reference's class_maps_ / class_mask_ members.
+// SVG / PNG / cache file (src/top_down_map.cpp:9-64, OpenCV + nanosvg).  Here the constructor reads the reference's map
+// cache, an SVG vector map (parsed on the host, filled and distance-transformed on the GPU) or a raster-cache
+// directory; colour PNG / JPG maps are not decoded.  Distance maps computed elsewhere are handed over with
+// setDistanceMaps() in the layout of the reference's class_maps_ / class_mask_ members.
 #ifndef TOP_DOWN_MAP_H_
 #define TOP_DOWN_MAP_H_
 
@@ -17,7 +18,7 @@ class TopDownMap {
  public:
   struct Params {  // top_down_map.h:54-62, member for member
     std::string map_path = "";
-    SemanticColorLut color_lut;   // static-map loader only (outside the per-scan path); carried, never read
+    SemanticColorLut color_lut;   // the SVG loader's class colours (unpackColor(ind2Color(cls)), :80-84)
     std::vector<int> flatten_lut;
     int num_classes = 0;
     std::vector<int> exclusive_classes;
@@ -27,8 +28,10 @@ class TopDownMap {
   // src/top_down_map.cpp:9-64.  An empty map_path is the dynamic-map case (the map arrives through updateMap).  A static
   // map is taken from the reference's own cache — ~/.ros/xview_cache, written by the reference or by saveCachedMaps() —
   // when its (map_path, num_classes, resolution) match (:18-20, :226-261), else from a raster-cache directory of class<i>.png
-  // (:42-46).  Parsing SVG / decoding colour images (nanosvg, OpenCV: load-time work outside the per-scan path) is not done
-  // here: without either the map stays empty until setDistanceMaps() / updateMap() provide it.
+  // (:42-46), else — a .svg map_path — from the vector map (:22-31): parse, class fill on the GPU, the raster cache
+  // <stem>_raster_cache/class<i>.png, geometric layers and distance maps, then the map cache (:61).  A file that does not
+  // parse leaves the map empty (haveMap() == false, the reason in tdr_last_error()) and writes nothing.  Colour PNG / JPG
+  // maps (cv::imread + color2Ind) are not decoded: such a map stays empty until setDistanceMaps() / updateMap().
   explicit TopDownMap(const Params& params, const char* cache_dir = nullptr) : params_(params) {
     if (tdr_map_create(&m_) != TDR_OK) throw std::runtime_error(std::string("TopDownMap: ") + tdr_last_error());
     if (!params_.map_path.empty() && params_.num_classes > 0) {
@@ -46,6 +49,10 @@ class TopDownMap {
       if (!loaded && ext != ".svg" && ext != ".png" && ext != ".jpg" &&
           tdr_map_load_rasters(m_, mp.c_str(), params_.num_classes, params_.resolution, 0, 0) == TDR_OK)
         (void)tdr_map_save_cache(m_, cache_dir, mp.c_str());
+      if (!loaded && ext == ".svg" && load_svg(mp)) {
+        (void)tdr_map_save_rasters(m_, (mp.substr(0, mp.size() - 4) + "_raster_cache").c_str());   // :31
+        (void)tdr_map_save_cache(m_, cache_dir, mp.c_str());                                       // :61
+      }
     }
   }
   // saveRasterizedMaps / loadRasterizedMaps (:197-224): a directory of class<i>.png (8-bit grey, 0 inside the class,
@@ -169,6 +176,19 @@ class TopDownMap {
     if (tdr_map_local_geo_map(m_, polar, center[0], center[1], scale_or_rot, res, rows, cols, d.data()) != TDR_OK)
       throw std::runtime_error(std::string("getLocalGeoMap: ") + tdr_last_error());
     for (size_t c = 0; c < dists.size() && c < 2; c++) std::memcpy(dists[c].data(), d.data() + P * c, P * sizeof(float));
+  }
+  // loadSvg + getRasterMap (:22-31): the key of LUT index cls is the reference's own expression (:80-84), so this
+  // compiles unchanged against semantics_manager's SemanticColorLut
+  bool load_svg(const std::string& path) {
+    std::vector<uint32_t> keys;
+    std::vector<int32_t> lut(params_.flatten_lut.begin(), params_.flatten_lut.end());
+    for (size_t cls = 0; cls < params_.flatten_lut.size(); cls++) {
+      auto color = SemanticColorLut::unpackColor(params_.color_lut.ind2Color(cls));
+      keys.push_back((uint32_t)color[0] << 16 | (uint32_t)color[1] << 8 | (uint32_t)color[2]);
+    }
+    std::vector<int32_t> excl(params_.exclusive_classes.begin(), params_.exclusive_classes.end());
+    return tdr_map_load_svg(m_, path.c_str(), keys.data(), lut.data(), (int)lut.size(), params_.num_classes,
+                            excl.data(), (int)excl.size(), params_.resolution, 0, 0) == TDR_OK;
   }
   Params params_;
   Eigen::Vector2i map_center_;

@@ -8,6 +8,7 @@ SO_PATH = os.environ.get("TDR_LIB_PATH") or os.path.join(_PKG, "libtdr_hip.so") 
 
 TDR_ST_FIELDS = 7
 TDR_MAX_CLASSES = 15
+TDR_SVG_NO_KEY = 0xFFFFFFFF
 
 
 class FilterParamsC(C.Structure):
@@ -74,6 +75,10 @@ SIGNATURES = {
     "tdr_png_read_gray8_host": (_i, [C.c_char_p, _vp, _i64, _vp, _vp]),
     "tdr_png_write_gray8_host": (_i, [C.c_char_p, _vp, _i, _i]),
     "tdr_map_load_rasters": (_i, [_vp, C.c_char_p, _i, _f, _i, _i]),
+    "tdr_svg_parse_host": (_i, [C.c_char_p, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _vp]),
+    "tdr_map_load_polygons": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _f, _i, _i, _vp]),
+    "tdr_map_load_svg": (_i, [_vp, C.c_char_p, _vp, _vp, _i, _i, _vp, _i, _f, _i, _i]),
+    "tdr_polygon_planes": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _f, _vp]),
     "tdr_k_unpack_map": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "tdr_polar_table_host": (_i, [_i, _i, _f, _f, _vp]),
     "tdr_raster_workspace_bytes": (_i64, [_i64]),

@@ -565,6 +565,8 @@ int tdr_map_save_rasters(tdr_map* m, const char* dir) {
 // TopDownMap::loadRasterizedMaps (:213-224) followed by what the constructor does with the rasters (:48-58): the geometric
 // layers derived from them and computeDists on both — on the device (tdr_k_map_from_rasters).
 static int map_load_rasters(tdr_map* m, const char* dir, int num_classes, float resolution, int center_x, int center_y);
+static int map_set_from_rasters(tdr_map* m, const uint8_t* d_planes, int num_classes, int rows, int cols,
+                                float resolution, int center_x, int center_y);
 int tdr_map_load_rasters(tdr_map* m, const char* dir, int num_classes, float resolution, int center_x, int center_y) {
   try {   // (no exception crosses the C ABI: a file that makes an allocation fail is an error code)
     return map_load_rasters(m, dir, num_classes, resolution, center_x, center_y);
@@ -586,14 +588,20 @@ static int map_load_rasters(tdr_map* m, const char* dir, int num_classes, float 
     planes.insert(planes.end(), one.begin(), one.end());
   }
   const int rows = h, cols = w;
-  const size_t ncell = (size_t)rows * cols;
-  DevBuf<uint8_t> d_planes, d_ws, d_mask;
-  DevBuf<float> d_maps;
+  DevBuf<uint8_t> d_planes;
   TTRY(d_planes.resize(planes.size()));
-  TTRY(d_ws.resize(tdr_map_ingest_workspace_bytes(num_classes, rows, cols)));
   HTRY(hipMemcpy(d_planes.p, planes.data(), planes.size(), hipMemcpyHostToDevice));
+  return map_set_from_rasters(m, d_planes.p, num_classes, rows, cols, resolution, center_x, center_y);
+}
+// what the constructor does with the class rasters of a static map (:48-58), from DEVICE planes in the class<i>.png layout
+static int map_set_from_rasters(tdr_map* m, const uint8_t* d_planes, int num_classes, int rows, int cols,
+                                float resolution, int center_x, int center_y) {
+  const size_t ncell = (size_t)rows * cols;
+  DevBuf<uint8_t> d_ws, d_mask;
+  DevBuf<float> d_maps;
+  TTRY(d_ws.resize(tdr_map_ingest_workspace_bytes(num_classes, rows, cols)));
   TTRY(m->rec.resize(tdr_map_rec_floats_total(num_classes, rows, cols)));
-  TTRY(tdr_k_map_from_rasters(d_planes.p, num_classes, rows, cols, resolution, m->rec.p, d_ws.p, nullptr));
+  TTRY(tdr_k_map_from_rasters(d_planes, num_classes, rows, cols, resolution, m->rec.p, d_ws.p, nullptr));
   TTRY(d_maps.resize(ncell * num_classes));
   TTRY(d_mask.resize(ncell));
   TTRY(tdr_k_unpack_map(m->rec.p, num_classes, rows, cols, d_maps.p, d_mask.p, nullptr));
@@ -614,6 +622,142 @@ static int map_load_rasters(tdr_map* m, const char* dir, int num_classes, float 
   m->have_map = true;             // :63
   if (m->nb > 0) return tdr_map_sample_pts_polar(m, m->nb, m->nr, m->ang_res);
   return TDR_OK;
+}
+
+// ---- the static vector map (src/top_down_map.cpp:22-31, 66-110, 328-365, 391-408) -------------------------------------
+// the fill runs on the device (csrc/tdr_poly.hip), the planes then take the raster cache's path into the map
+}  // extern "C"
+int tdr_poly_grid(int width, int height, float resolution, int* rows, int* cols);                  // tdr_poly.hip
+int tdr_poly_fill(const float* verts, const int64_t* offs, const int32_t* cls, int64_t n_poly, int width, int height,
+                  float resolution, int ncls, const uint32_t* excl_above, uint8_t* planes_cm, uint8_t* raster,
+                  hipStream_t s);
+int tdr_svg_parse_internal(const char* path, float* w, float* h, std::vector<uint32_t>& keys, std::vector<int64_t>& offs,
+                           std::vector<float>& verts);                                               // tdr_svg.cpp
+
+// the checks every polygon entry makes before it touches the device; excl_above[u] = the exclusive classes c > u that
+// clear u (u itself listed).  With binary planes the reference's loop (:356-365: plane[u] += 1 - plane[c] for listed
+// u < c, then min(., 1)) clears u exactly where any listed c > u is inside: a plane changed earlier in the loop only
+// lost cells some still higher listed class covers, so the union over c > u is the same, and repeats change nothing.
+static int poly_check(int num_classes, const int32_t* exclusive, int n_excl, float resolution, uint32_t* excl_above,
+                      const char* who) {
+  if (num_classes < 1 || num_classes > TDR_MAX_CLASSES)
+    return failh(TDR_ERR_ARG, "%s: num_classes %d outside [1, %d]", who, num_classes, TDR_MAX_CLASSES);
+  if (n_excl < 0 || (n_excl > 0 && !exclusive)) return failh(TDR_ERR_ARG, "%s: null exclusive list", who);
+  if (!(resolution > 0.f) || !std::isfinite(resolution)) return failh(TDR_ERR_ARG, "%s: resolution must be > 0", who);
+  if ((int)std::ceil(50.0 / (double)resolution) > 250)
+    return failh(TDR_ERR_ARG, "%s: resolution %g needs a distance window over 250 cells", who, (double)resolution);
+  for (int k = 0; k < TDR_MAX_CLASSES; k++) excl_above[k] = 0;
+  uint32_t listed = 0;
+  for (int k = 0; k < n_excl; k++) {
+    if (exclusive[k] < 0 || exclusive[k] >= num_classes)
+      return failh(TDR_ERR_ARG, "%s: exclusive class %d outside [0, %d)", who, exclusive[k], num_classes);
+    listed |= 1u << exclusive[k];
+  }
+  for (int u = 0; u < num_classes; u++)
+    if (listed & (1u << u)) excl_above[u] = listed & ~((2u << u) - 1u);
+  return TDR_OK;
+}
+
+static int map_load_polygons(tdr_map* m, const float* verts, const int64_t* offs, const int32_t* cls, int64_t n_poly,
+                             int width, int height, int num_classes, const uint32_t* excl_above, float resolution,
+                             int center_x, int center_y, uint8_t* planes_out) {
+  int rows = 0, cols = 0;
+  TTRY(tdr_poly_grid(width, height, resolution, &rows, &cols));
+  const size_t ncell = (size_t)rows * cols;
+  DevBuf<uint8_t> d_planes, d_raster;
+  TTRY(d_planes.resize(ncell * num_classes));
+  TTRY(d_raster.resize(ncell * num_classes));
+  TTRY(tdr_poly_fill(verts, offs, cls, n_poly, width, height, resolution, num_classes, excl_above, d_planes.p, d_raster.p,
+                     nullptr));
+  if (planes_out) HTRY(hipMemcpy(planes_out, d_planes.p, ncell * num_classes, hipMemcpyDeviceToHost));
+  d_planes.release();
+  return map_set_from_rasters(m, d_raster.p, num_classes, rows, cols, resolution, center_x, center_y);
+}
+
+extern "C" {
+int tdr_map_load_polygons(tdr_map* m, const float* verts, const int64_t* poly_offsets, const int32_t* poly_class,
+                          int64_t n_poly, int width, int height, int num_classes, const int32_t* exclusive, int n_excl,
+                          float resolution, int center_x, int center_y, uint8_t* planes_out) {
+  const char* who = "map_load_polygons";
+  if (n_poly < 0 || (n_poly > 0 && (!verts || !poly_offsets || !poly_class)))
+    return failh(TDR_ERR_ARG, "%s: null polygon arrays", who);
+  uint32_t above[TDR_MAX_CLASSES];
+  TTRY(poly_check(num_classes, exclusive, n_excl, resolution, above, who));
+  int rows = 0, cols = 0;
+  TTRY(tdr_poly_grid(width, height, resolution, &rows, &cols));
+  if (n_poly > 0 && poly_offsets[0] < 0) return failh(TDR_ERR_ARG, "%s: negative vertex offset", who);
+  for (int64_t p = 0; p < n_poly; p++)
+    if (poly_offsets[p + 1] < poly_offsets[p]) return failh(TDR_ERR_ARG, "%s: vertex offsets decrease at %lld", who, (long long)p);
+  if (!m) return failh(TDR_ERR_ARG, "%s: null map", who);
+  try {
+    return map_load_polygons(m, verts, poly_offsets, poly_class, n_poly, width, height, num_classes, above, resolution,
+                             center_x, center_y, planes_out);
+  } catch (const std::exception& e) {
+    return failh(TDR_ERR_NOMEM, "%s: %s", who, e.what());
+  }
+}
+
+int tdr_polygon_planes(const float* verts, const int64_t* poly_offsets, const int32_t* poly_class, int64_t n_poly,
+                       int width, int height, int num_classes, const int32_t* exclusive, int n_excl, float resolution,
+                       uint8_t* planes_out) {
+  const char* who = "polygon_planes";
+  if (n_poly < 0 || (n_poly > 0 && (!verts || !poly_offsets || !poly_class)))
+    return failh(TDR_ERR_ARG, "%s: null polygon arrays", who);
+  uint32_t above[TDR_MAX_CLASSES];
+  TTRY(poly_check(num_classes, exclusive, n_excl, resolution, above, who));
+  int rows = 0, cols = 0;
+  TTRY(tdr_poly_grid(width, height, resolution, &rows, &cols));
+  if (n_poly > 0 && poly_offsets[0] < 0) return failh(TDR_ERR_ARG, "%s: negative vertex offset", who);
+  for (int64_t p = 0; p < n_poly; p++)
+    if (poly_offsets[p + 1] < poly_offsets[p]) return failh(TDR_ERR_ARG, "%s: vertex offsets decrease at %lld", who, (long long)p);
+  if (!planes_out) return failh(TDR_ERR_ARG, "%s: null planes_out", who);
+  if (tdr_device_count() < 1) return failh(TDR_ERR_HIP, "%s: no HIP device (there is no CPU fallback)", who);
+  try {
+    const size_t ncell = (size_t)rows * cols;
+    DevBuf<uint8_t> d_planes;
+    TTRY(d_planes.resize(ncell * num_classes));
+    TTRY(tdr_poly_fill(verts, poly_offsets, poly_class, n_poly, width, height, resolution, num_classes, above, d_planes.p,
+                       nullptr, nullptr));
+    HTRY(hipMemcpy(planes_out, d_planes.p, ncell * num_classes, hipMemcpyDeviceToHost));
+    return TDR_OK;
+  } catch (const std::exception& e) {
+    return failh(TDR_ERR_NOMEM, "%s: %s", who, e.what());
+  }
+}
+
+int tdr_map_load_svg(tdr_map* m, const char* path, const uint32_t* fill_keys, const int32_t* flatten_lut, int lut_size,
+                     int num_classes, const int32_t* exclusive, int n_excl, float resolution, int center_x, int center_y) {
+  const char* who = "map_load_svg";
+  if (!path || lut_size < 0 || (lut_size > 0 && (!fill_keys || !flatten_lut)))
+    return failh(TDR_ERR_ARG, "%s: null path / lookup tables", who);
+  uint32_t above[TDR_MAX_CLASSES];
+  TTRY(poly_check(num_classes, exclusive, n_excl, resolution, above, who));
+  if (!m) return failh(TDR_ERR_ARG, "%s: null map", who);
+  try {
+    float w = 0, h = 0;
+    std::vector<uint32_t> keys;
+    std::vector<int64_t> offs;
+    std::vector<float> verts;
+    TTRY(tdr_svg_parse_internal(path, &w, &h, keys, offs, verts));
+    // loadSvg :77-103: per LUT index, the polygons of every shape of its colour, into its flattened class
+    std::vector<float> cv;
+    std::vector<int64_t> co(1, 0);
+    std::vector<int32_t> cc;
+    for (int l = 0; l < lut_size; l++) {
+      if (flatten_lut[l] < 0 || flatten_lut[l] >= num_classes) continue;
+      for (size_t p = 0; p < keys.size(); p++) {
+        if (keys[p] == TDR_SVG_NO_KEY || keys[p] != (fill_keys[l] & 0xFFFFFFu)) continue;
+        cv.insert(cv.end(), verts.begin() + 2 * offs[p], verts.begin() + 2 * offs[p + 1]);
+        co.push_back((int64_t)(cv.size() / 2));
+        cc.push_back(flatten_lut[l]);
+      }
+    }
+    const int W = (int)w, H = (int)h;   // Eigen::Vector2i map_size{width, height} (:107)
+    return map_load_polygons(m, cv.data(), co.data(), cc.data(), (int64_t)cc.size(), W, H, num_classes, above, resolution,
+                             center_x, center_y, nullptr);
+  } catch (const std::exception& e) {
+    return failh(TDR_ERR_NOMEM, "%s: %s", who, e.what());
+  }
 }
 
 // TopDownMap::getClassesAtPoint(Vector2i) (top_down_map.cpp:159-170): bit c set = class c present (< 1 px away)

@@ -150,6 +150,24 @@ class DeviceMap:
         return bool(self.desc.cwords)
 
 
+def svg_parse(path):
+    """tdr_svg_parse_host (host only, no GPU): the polygons TopDownMap::loadSvg keeps of an SVG.  Returns
+    (size float32[2] = the image's float width / height, keys uint32[P] (_lib.TDR_SVG_NO_KEY: gradient),
+    offs int64[P + 1], verts float32[V, 2] = (x, height - y))."""
+    lib = _lib.load()
+    size = np.zeros(2, np.float32)
+    n_poly, n_vert = C.c_int64(0), C.c_int64(0)
+    check(lib.tdr_svg_parse_host(str(path).encode(), size.ctypes.data_as(C.c_void_p), C.byref(n_poly), C.byref(n_vert),
+                                 None, None, None))
+    keys = np.zeros(max(n_poly.value, 1), np.uint32)
+    offs = np.zeros(n_poly.value + 1, np.int64)
+    verts = np.zeros((max(n_vert.value, 1), 2), np.float32)
+    check(lib.tdr_svg_parse_host(str(path).encode(), size.ctypes.data_as(C.c_void_p), C.byref(n_poly), C.byref(n_vert),
+                                 keys.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
+                                 verts.ctypes.data_as(C.c_void_p)))
+    return size, keys[:n_poly.value], offs, verts[:n_vert.value]
+
+
 class HipKernels:
     name = "hip"
 
@@ -237,6 +255,47 @@ class HipKernels:
         m = DeviceMap(rec, ncls, rows, cols, resolution)
         m.compact(self)
         return m
+
+    def map_load_polygons(self, handle, verts, offs, cls, width, height, ncls, exclusive, resolution, center=(0, 0),
+                          want_planes=True):
+        """tdr_map_load_polygons on a tdr_map handle: getRasterMap + getClasses of the polygons (vertex (x, y) pairs
+        verts[offs[p]:offs[p+1]], class cls[p]) on the device, then the ingest.  Returns the class planes before the
+        distance transform, (ncls, cols, rows) uint8 column-major (0 inside, 1 elsewhere), or None."""
+        verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 2)
+        offs = np.ascontiguousarray(offs, np.int64)
+        cls = np.ascontiguousarray(cls, np.int32)
+        excl = np.ascontiguousarray(exclusive, np.int32)
+        rows, cols = int(np.float32(height) / np.float32(resolution)), int(np.float32(width) / np.float32(resolution))
+        planes = np.empty((ncls, cols, rows), np.uint8) if want_planes else None
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        check(self.lib.tdr_map_load_polygons(handle, vp(verts), offs.ctypes.data_as(C.c_void_p), vp(cls), len(cls),
+                                             int(width), int(height), int(ncls), vp(excl), len(excl),
+                                             C.c_float(resolution), int(center[0]), int(center[1]), vp(planes)))
+        return planes
+
+    def polygon_planes(self, verts, offs, cls, width, height, ncls, exclusive, resolution):
+        """tdr_polygon_planes: the fill alone (getRasterMap + getClasses on the device, no ingest).  Returns the class
+        planes (ncls, cols, rows) uint8 column-major (0 inside, 1 elsewhere)."""
+        verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 2)
+        offs = np.ascontiguousarray(offs, np.int64)
+        cls = np.ascontiguousarray(cls, np.int32)
+        excl = np.ascontiguousarray(exclusive, np.int32)
+        rows, cols = int(np.float32(height) / np.float32(resolution)), int(np.float32(width) / np.float32(resolution))
+        planes = np.empty((ncls, max(cols, 0), max(rows, 0)), np.uint8)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        check(self.lib.tdr_polygon_planes(vp(verts), offs.ctypes.data_as(C.c_void_p), vp(cls), len(cls), int(width),
+                                          int(height), int(ncls), vp(excl), len(excl), C.c_float(resolution),
+                                          planes.ctypes.data_as(C.c_void_p)))
+        return planes
+
+    def map_load_svg(self, handle, path, fill_keys, flatten_lut, ncls, exclusive, resolution, center=(0, 0)):
+        """tdr_map_load_svg: the reference constructor's SVG branch on a tdr_map handle."""
+        keys = np.ascontiguousarray(fill_keys, np.uint32)
+        lut = np.ascontiguousarray(flatten_lut, np.int32)
+        excl = np.ascontiguousarray(exclusive, np.int32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        check(self.lib.tdr_map_load_svg(handle, str(path).encode(), vp(keys), vp(lut), len(lut), int(ncls), vp(excl),
+                                        len(excl), C.c_float(resolution), int(center[0]), int(center[1])))
 
     def png_read_gray8(self, path):
         w, h = C.c_int(0), C.c_int(0)

@@ -2,13 +2,31 @@
 top_down_map_polar.h:6-22) holding the map on the device for the HIP kernels.
 
 Map content is taken in the form the reference's load-time code produces (src/top_down_map.cpp:289-326): per-class
-truncated distance maps + unknown mask.  Loading SVG/PNG maps and the on-disk caches is load-time work outside the
-per-scan path.
+truncated distance maps + unknown mask, or built on the GPU from a label image, a raster cache or an SVG vector map
+(loadVectorMap; parse_svg returns the polygons the reference's loadSvg keeps).
 """
 from dataclasses import dataclass, field
 
 import numpy as np
 import torch
+
+
+def parse_svg(path):
+    """The polygons TopDownMap::loadSvg (src/top_down_map.cpp:66-110) keeps of an SVG file (host only, no GPU):
+    (size, polygons) with size = (width, height) as floats and polygons a list of (fill_key, (n, 2) float32 vertices
+    (x, height - y)).  fill_key = the shape's 0xBBGGRR fill colour (0 for fill="none" / no fill), None for a gradient."""
+    from . import _lib
+    from .kernels import svg_parse
+    size, keys, offs, verts = svg_parse(path)
+    polys = [(None if int(k) == _lib.TDR_SVG_NO_KEY else int(k), verts[offs[p]:offs[p + 1]].copy())
+             for p, k in enumerate(keys)]
+    return (float(size[0]), float(size[1])), polys
+
+
+def svg_fill_key(rgb):
+    """The key loadSvg compares a shape's fill with (:82-84) for an (r, g, b) colour: c[0] << 16 | c[1] << 8 | c[2]."""
+    r, g, b = (int(x) & 0xFF for x in rgb[:3])
+    return (r << 16) | (g << 8) | b
 
 
 @dataclass
@@ -106,6 +124,47 @@ class TopDownMap:
         self.rows, self.cols = self.dev.rows, self.dev.cols
         maps_cm, _ = self.k.unpack_map(self.dev)
         self.maps_cm_host = maps_cm
+        self.map_center_ = (int(map_center[0]), int(map_center[1]))
+        self.have_map_ = True                                                # :63
+        if old is not None and getattr(old, "nb", 0):
+            self.k.set_polar_table(self.dev, old.nb, old.nr, old.ang_res)
+
+    # top_down_map.cpp:22-31 + 48-58: the static vector map
+    def loadVectorMap(self, svg_path, fill_keys, map_center=(0, 0)):
+        """Parses svg_path like loadSvg (host), fills the class planes like getRasterMap + getClasses on the GPU
+        (tdr_map_load_polygons) and builds the distance maps from them like the constructor (:48-58).  fill_keys[cls]:
+        the key of LUT index cls (svg_fill_key(unpackColor(ind2Color(cls)))); params_.flatten_lut / num_classes /
+        exclusive_classes / resolution as the reference reads them.  The class planes before the distance transform
+        are kept in self.class_planes_ ((ncls, cols, rows) column-major, 0 inside)."""
+        import os
+        p = self.params_
+        if not p.num_classes or not len(p.flatten_lut):
+            raise ValueError("Params.num_classes and Params.flatten_lut are needed to load a vector map")
+        if len(fill_keys) < len(p.flatten_lut):
+            raise ValueError("one fill key per flatten_lut entry is needed")
+        if not os.path.exists(svg_path):
+            raise FileNotFoundError(svg_path)
+        (w, h), polys = parse_svg(svg_path)
+        verts, offs, cls = [], [0], []
+        for lut_i, flat in enumerate(p.flatten_lut):          # loadSvg :77-103
+            if not 0 <= flat < p.num_classes:
+                continue
+            for key, v in polys:
+                if key is not None and key == (int(fill_keys[lut_i]) & 0xFFFFFF):
+                    verts.append(v)
+                    offs.append(offs[-1] + len(v))
+                    cls.append(flat)
+        verts = np.concatenate(verts) if verts else np.zeros((0, 2), np.float32)
+        planes = self.k.polygon_planes(verts, np.asarray(offs, np.int64), np.asarray(cls, np.int32), int(w), int(h),
+                                       p.num_classes, list(p.exclusive_classes), p.resolution)
+        # the planes as the raster cache stores them (0 inside, 255 elsewhere, flipped) -> the ingest of loadRasterizedMaps
+        raster = np.where(np.transpose(planes, (0, 2, 1)) == 0, 0, 255).astype(np.uint8)[:, ::-1]
+        old = self.dev
+        self.geo_constant_one_ = False
+        self.dev = self.k.make_map_from_rasters(raster, p.resolution)
+        self.rows, self.cols = self.dev.rows, self.dev.cols
+        self.maps_cm_host, _ = self.k.unpack_map(self.dev)
+        self.class_planes_ = planes
         self.map_center_ = (int(map_center[0]), int(map_center[1]))
         self.have_map_ = True                                                # :63
         if old is not None and getattr(old, "nb", 0):
