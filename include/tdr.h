@@ -155,6 +155,21 @@ int tdr_k_map_from_rasters(const uint8_t* planes, int ncls, int rows, int cols, 
                            void* workspace, void* stream);
 int tdr_k_map_from_labels(const uint8_t* label_img, int img_h, int img_w, const int32_t* flatten_lut, int lut_size,
                           int ncls, float resolution, float* rec_out, void* workspace, void* stream);
+/* The colour-image form (the constructor's .png / .jpg branch, src/top_down_map.cpp:32-42: cv::imread ->
+ * SemanticColorLut::color2Ind -> loadCompressedRasterMap): bgr = DEVICE image, img_h x img_w pixels of 3 bytes B, G, R
+ * (cv::imread's layout, rows packed, row 0 = top).  A pixel's key is B << 16 | G << 8 | R; fill_keys / flatten_lut are
+ * HOST arrays of lut_size <= 256 entries: LUT index i has the key fill_keys[i] & 0xFFFFFF (the key tdr_map_load_svg takes)
+ * and the flattened class flatten_lut[i].  color2Ind is taken as the exact inverse of ind2Color over the LUT: the
+ * smallest index whose key matches; a pixel that matches no key, or whose index flattens outside [0, ncls), is unknown.
+ * Exclusive classes are not applied (loadCompressedRasterMap does not).  Sampling, rec_out and workspace as for
+ * tdr_k_map_from_labels. */
+int tdr_k_map_from_color(const uint8_t* bgr, int img_h, int img_w, const uint32_t* fill_keys, const int32_t* flatten_lut,
+                         int lut_size, int ncls, float resolution, float* rec_out, void* workspace, void* stream);
+/* color2Ind over a whole image: index_out = DEVICE img_h x img_w u8 (CV_8UC1): the LUT index of each pixel of the DEVICE
+ * BGR image, 255 where no key matches (so index 255 of a 256-key table cannot be told from no match).  fill_keys: HOST,
+ * 1 <= n_keys <= 256, keys as above. */
+int tdr_k_color_index(const uint8_t* bgr, int img_h, int img_w, const uint32_t* fill_keys, int n_keys, uint8_t* index_out,
+                      void* stream);
 /* geo_maps_ (top_down_map.h:79) as a 2-class record map {d_without, d_with, 1, 1}, derived from the class records
  * (getGeoRasterMap top_down_map.cpp:410-427 + computeDists :58; exact distance transform), or — constant_one != 0 — the
  * constant 1 of the dynamic-map path (:126-133).  geo_rec_out: tdr_map_rec_floats_total(2, rows, cols) floats;
@@ -655,6 +670,28 @@ int tdr_polygon_planes(const float* verts, const int64_t* poly_offsets, const in
  * that does not parse leaves the handle as it was. */
 int tdr_map_load_svg(tdr_map* m, const char* path, const uint32_t* fill_keys, const int32_t* flatten_lut, int lut_size,
                      int num_classes, const int32_t* exclusive, int n_excl, float resolution, int center_x, int center_y);
+/* The static colour raster map: the constructor's branch for a .png / .jpg map_path
+ * (src/top_down_map.cpp:32-42, then :48-63): cv::imread, color2Ind, loadCompressedRasterMap, then the geometric layers
+ * derived from the classes and computeDists on both, have_map = true even for a map without road (:63; unlike
+ * tdr_map_set_labels).  The map is int(h / resolution) x int(w / resolution) cells.
+ *
+ * tdr_png_read_color_host (host only, no device needed): the BGR8 image cv::imread(path) gives for a PNG: every colour
+ * type, bit depth and interlace method; palette expanded (tRNS ignored), grey below 8 bits scaled to 8 bits and copied into
+ * three channels, alpha dropped, 16-bit samples cut to their high byte, no gamma or colour-space conversion; row 0 = top.
+ * bgr_out holds `capacity` bytes (3 * w * h needed); *w / *h are set even when the image does not fit (then TDR_ERR_ARG),
+ * so bgr_out = NULL is a size query.  Bad CRCs, truncation, a missing or misplaced PLTE, unknown critical chunks and
+ * headers announcing more pixels than the data can hold are refused.  eXIf is ignored (cv::imread may rotate by it).
+ *
+ * tdr_map_load_color_image: from a HOST BGR image (e.g. a caller's own cv::imread, which also covers .jpg maps);
+ * fill_keys / flatten_lut as for tdr_k_map_from_color (HOST, lut_size <= 256), resolution >= 0.2 (the distance window).
+ * tdr_map_load_color_png: tdr_png_read_color_host, then the same.  Every argument is checked and the file read before any
+ * device work: a failed read or a refused argument leaves the handle as it was. */
+int tdr_png_read_color_host(const char* path, uint8_t* bgr_out, int64_t capacity, int* w, int* h);
+int tdr_map_load_color_image(tdr_map* m, const uint8_t* bgr, int img_h, int img_w, const uint32_t* fill_keys,
+                             const int32_t* flatten_lut, int lut_size, int num_classes, float resolution, int center_x,
+                             int center_y);
+int tdr_map_load_color_png(tdr_map* m, const char* path, const uint32_t* fill_keys, const int32_t* flatten_lut,
+                           int lut_size, int num_classes, float resolution, int center_x, int center_y);
 
 int tdr_renderer_create(const int32_t* flatten_lut256, tdr_renderer** out);              /* scan_renderer.cpp:3-5 */
 void tdr_renderer_destroy(tdr_renderer* r);

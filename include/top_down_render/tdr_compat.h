@@ -125,21 +125,32 @@ class PointCloud {
 };
 }  // namespace pcl
 #endif
-// cv::Mat appears in two signatures of the reference's surface (updateMap, visualize).  Without OpenCV a minimal
-// stand-in carries what those methods need: an 8-bit single-channel image (rows x cols, row 0 = top, `step` bytes per row).
+// cv::Mat appears in two signatures of the reference's surface (updateMap, visualize) and in TopDownMap's colour-map
+// loader.  Without OpenCV a minimal stand-in carries what those methods need: an 8-bit image of one channel or of three
+// (B, G, R, as cv::imread gives; constructed with CV_8UC3), rows x cols, row 0 = top, `step` bytes per row.
 #ifdef TDR_HAVE_OPENCV
 #include <opencv2/core.hpp>
 #include <opencv2/imgproc.hpp>
 #else
+#ifndef CV_8UC1
+#define CV_8UC1 0
+#define CV_8UC3 16
+#endif
 namespace cv {
 class Mat {
  public:
   Mat() {}
   Mat(int r, int c, uint8_t* d, size_t row_bytes = 0) : rows(r), cols(c), data(d), step(row_bytes ? row_bytes : (size_t)c) {}
+  Mat(int r, int c, int type, void* d, size_t row_bytes = 0)   // type: CV_8UC1 or CV_8UC3
+      : rows(r), cols(c), data(static_cast<uint8_t*>(d)), nch(type == CV_8UC3 ? 3 : 1),
+        step(row_bytes ? row_bytes : (size_t)c * (type == CV_8UC3 ? 3 : 1)) {}
   int rows = 0, cols = 0;
   uint8_t* data = nullptr;
+  int nch = 1;
   size_t step = 0;
-  bool isContinuous() const { return step == (size_t)cols; }
+  int channels() const { return nch; }
+  size_t elemSize() const { return (size_t)nch; }
+  bool isContinuous() const { return step == (size_t)cols * nch; }
   bool empty() const { return !data || rows < 1 || cols < 1; }
   template <class T> T* ptr(int r = 0) { return reinterpret_cast<T*>(data + (size_t)r * step); }
   template <class T> const T* ptr(int r = 0) const { return reinterpret_cast<const T*>(data + (size_t)r * step); }

@@ -1,9 +1,10 @@
 // TopDownMap — reference surface: include/top_down_render/top_down_map.h:52-102.  Holds the per-class truncated
 // distance maps + unknown mask on the GPU (tdr_map, include/tdr.h).  The reference builds these at load time from an
 // SVG / PNG / cache file (src/top_down_map.cpp:9-64, OpenCV + nanosvg).  Here the constructor reads the reference's map
-// cache, an SVG vector map (parsed on the host, filled and distance-transformed on the GPU) or a raster-cache
-// directory; colour PNG / JPG maps are not decoded.  Distance maps computed elsewhere are handed over with
-// setDistanceMaps() in the layout of the reference's class_maps_ / class_mask_ members.
+// cache, an SVG vector map (parsed on the host, filled and distance-transformed on the GPU), a colour PNG map (decoded
+// on the host, colour lookup and distance transforms on the GPU) or a raster-cache directory.  JPEG maps are not
+// decoded: decode them elsewhere and hand the BGR pixels to loadColorRasterMap().  Distance maps computed elsewhere are
+// handed over with setDistanceMaps() in the layout of the reference's class_maps_ / class_mask_ members.
 #ifndef TOP_DOWN_MAP_H_
 #define TOP_DOWN_MAP_H_
 
@@ -29,9 +30,12 @@ class TopDownMap {
   // map is taken from the reference's own cache — ~/.ros/xview_cache, written by the reference or by saveCachedMaps() —
   // when its (map_path, num_classes, resolution) match (:18-20, :226-261), else from a raster-cache directory of class<i>.png
   // (:42-46), else — a .svg map_path — from the vector map (:22-31): parse, class fill on the GPU, the raster cache
-  // <stem>_raster_cache/class<i>.png, geometric layers and distance maps, then the map cache (:61).  A file that does not
-  // parse leaves the map empty (haveMap() == false, the reason in tdr_last_error()) and writes nothing.  Colour PNG / JPG
-  // maps (cv::imread + color2Ind) are not decoded: such a map stays empty until setDistanceMaps() / updateMap().
+  // <stem>_raster_cache/class<i>.png, geometric layers and distance maps, then the map cache (:61); else — a .png
+  // map_path — from the colour raster map (:32-42): cv::imread's BGR image, color2Ind against the keys of
+  // params_.color_lut (the SVG loader's keys), loadCompressedRasterMap, geometric layers and distance maps, then the map
+  // cache (:61; no raster cache on this branch).  A file that does not parse or decode leaves the map empty
+  // (haveMap() == false, the reason in tdr_last_error()) and writes nothing.  A .jpg map is not decoded: it stays empty
+  // (tdr_last_error() says so) until loadColorRasterMap(), setDistanceMaps() or updateMap() provide the map.
   explicit TopDownMap(const Params& params, const char* cache_dir = nullptr) : params_(params) {
     if (tdr_map_create(&m_) != TDR_OK) throw std::runtime_error(std::string("TopDownMap: ") + tdr_last_error());
     if (!params_.map_path.empty() && params_.num_classes > 0) {
@@ -53,6 +57,10 @@ class TopDownMap {
         (void)tdr_map_save_rasters(m_, (mp.substr(0, mp.size() - 4) + "_raster_cache").c_str());   // :31
         (void)tdr_map_save_cache(m_, cache_dir, mp.c_str());                                       // :61
       }
+      if (!loaded && ext == ".png" && load_color_png(mp)) (void)tdr_map_save_cache(m_, cache_dir, mp.c_str());   // :61
+      if (!loaded && ext == ".jpg")
+        tdr_set_error(TDR_ERR_ARG, "TopDownMap: JPEG maps are not decoded here; decode the map (e.g. cv::imread) and hand "
+                                   "its BGR pixels to loadColorRasterMap() / tdr_map_load_color_image()");
     }
   }
   // saveRasterizedMaps / loadRasterizedMaps (:197-224): a directory of class<i>.png (8-bit grey, 0 inside the class,
@@ -105,6 +113,29 @@ class TopDownMap {
     std::vector<uint8_t> packed((size_t)map.rows * map.cols);   // a view with row padding: pack the rows
     for (int r = 0; r < map.rows; r++) std::memcpy(packed.data() + (size_t)r * map.cols, map.ptr<uint8_t>(r), (size_t)map.cols);
     updateMap(packed.data(), map.rows, map.cols, map_center);
+  }
+  // The constructor's colour-map branch (:32-42, 48-63) for a BGR image the caller decoded (cv::imread's layout: 3 bytes
+  // B, G, R per pixel, row 0 = top), e.g. a .jpg map: color2Ind against params_.color_lut, loadCompressedRasterMap,
+  // geometric layers and distance maps on the GPU; haveMap() turns true even without road (:63).
+  void loadColorRasterMap(const uint8_t* bgr, int img_h, int img_w,
+                          const Eigen::Vector2i& map_center = Eigen::Vector2i(0, 0)) {
+    std::vector<uint32_t> keys = color_keys();
+    std::vector<int32_t> lut(params_.flatten_lut.begin(), params_.flatten_lut.end());
+    if (lut.empty() || params_.num_classes < 1)
+      throw std::invalid_argument("loadColorRasterMap: Params::flatten_lut / num_classes not set");
+    if (tdr_map_load_color_image(m_, bgr, img_h, img_w, keys.data(), lut.data(), (int)lut.size(), params_.num_classes,
+                                 params_.resolution, map_center[0], map_center[1]) != TDR_OK)
+      throw std::runtime_error(std::string("TopDownMap::loadColorRasterMap: ") + tdr_last_error());
+    map_center_ = map_center;
+  }
+  template <class MatT = cv::Mat>   // a cv::Mat of CV_8UC3 (a template: only instantiated where it is called)
+  void loadColorRasterMap(const MatT& bgr, const Eigen::Vector2i& map_center = Eigen::Vector2i(0, 0)) {
+    if (bgr.empty() || bgr.elemSize() != 3) throw std::invalid_argument("loadColorRasterMap: needs an 8-bit BGR image");
+    if (bgr.isContinuous()) return loadColorRasterMap(bgr.template ptr<uint8_t>(), bgr.rows, bgr.cols, map_center);
+    std::vector<uint8_t> packed((size_t)bgr.rows * bgr.cols * 3);   // a view with row padding: pack the rows
+    for (int r = 0; r < bgr.rows; r++)
+      std::memcpy(packed.data() + (size_t)r * bgr.cols * 3, bgr.template ptr<uint8_t>(r), (size_t)bgr.cols * 3);
+    loadColorRasterMap(packed.data(), bgr.rows, bgr.cols, map_center);
   }
   const Params& params() const { return params_; }
   void getClassesAtPoint(const Eigen::Vector2i& center_ind, std::vector<int>& classes) {  // top_down_map.cpp:159-170
@@ -177,18 +208,32 @@ class TopDownMap {
       throw std::runtime_error(std::string("getLocalGeoMap: ") + tdr_last_error());
     for (size_t c = 0; c < dists.size() && c < 2; c++) std::memcpy(dists[c].data(), d.data() + P * c, P * sizeof(float));
   }
-  // loadSvg + getRasterMap (:22-31): the key of LUT index cls is the reference's own expression (:80-84), so this
-  // compiles unchanged against semantics_manager's SemanticColorLut
-  bool load_svg(const std::string& path) {
+  // the key of LUT index cls: the reference's own expression (:80-84), so this compiles unchanged against
+  // semantics_manager's SemanticColorLut.  unpackColor gives B, G, R, so the key of a cv::imread pixel px is
+  // px[0] << 16 | px[1] << 8 | px[2]: the SVG fill #ff0000 and the PNG pixel RGB (255, 0, 0) both have the key 0x0000ff.
+  std::vector<uint32_t> color_keys() const {
     std::vector<uint32_t> keys;
-    std::vector<int32_t> lut(params_.flatten_lut.begin(), params_.flatten_lut.end());
     for (size_t cls = 0; cls < params_.flatten_lut.size(); cls++) {
       auto color = SemanticColorLut::unpackColor(params_.color_lut.ind2Color(cls));
       keys.push_back((uint32_t)color[0] << 16 | (uint32_t)color[1] << 8 | (uint32_t)color[2]);
     }
+    return keys;
+  }
+  // loadSvg + getRasterMap (:22-31)
+  bool load_svg(const std::string& path) {
+    std::vector<uint32_t> keys = color_keys();
+    std::vector<int32_t> lut(params_.flatten_lut.begin(), params_.flatten_lut.end());
     std::vector<int32_t> excl(params_.exclusive_classes.begin(), params_.exclusive_classes.end());
     return tdr_map_load_svg(m_, path.c_str(), keys.data(), lut.data(), (int)lut.size(), params_.num_classes,
                             excl.data(), (int)excl.size(), params_.resolution, 0, 0) == TDR_OK;
+  }
+  // cv::imread + color2Ind + loadCompressedRasterMap (:32-42)
+  bool load_color_png(const std::string& path) {
+    std::vector<uint32_t> keys = color_keys();
+    std::vector<int32_t> lut(params_.flatten_lut.begin(), params_.flatten_lut.end());
+    if (lut.empty()) return tdr_set_error(TDR_ERR_ARG, "TopDownMap: Params::flatten_lut is empty"), false;
+    return tdr_map_load_color_png(m_, path.c_str(), keys.data(), lut.data(), (int)lut.size(), params_.num_classes,
+                                  params_.resolution, 0, 0) == TDR_OK;
   }
   Params params_;
   Eigen::Vector2i map_center_;

@@ -78,6 +78,11 @@ SIGNATURES = {
     "tdr_svg_parse_host": (_i, [C.c_char_p, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _vp]),
     "tdr_map_load_polygons": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _f, _i, _i, _vp]),
     "tdr_map_load_svg": (_i, [_vp, C.c_char_p, _vp, _vp, _i, _i, _vp, _i, _f, _i, _i]),
+    "tdr_k_map_from_color": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
+    "tdr_k_color_index": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    "tdr_png_read_color_host": (_i, [C.c_char_p, _vp, _i64, _vp, _vp]),
+    "tdr_map_load_color_image": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _i, _i]),
+    "tdr_map_load_color_png": (_i, [_vp, C.c_char_p, _vp, _vp, _i, _i, _f, _i, _i]),
     "tdr_polygon_planes": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _f, _vp]),
     "tdr_k_unpack_map": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "tdr_polar_table_host": (_i, [_i, _i, _f, _f, _vp]),

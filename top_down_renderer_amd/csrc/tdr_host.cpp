@@ -158,6 +158,7 @@ static std::string cache_dir_or_default(const char* cache_dir) {
 }
 int tdr_png_read_gray8(const char* path, std::vector<uint8_t>& px, int& w, int& h);   // tdr_png.cpp
 int tdr_png_write_gray8(const char* path, const uint8_t* px, int w, int h);
+int tdr_png_read_bgr8(const char* path, std::vector<uint8_t>& bgr, int& w, int& h);
 
 template <class T>
 static int read_eig(const std::string& path, std::vector<T>& out, int64_t& rows, int64_t& cols) {
@@ -567,6 +568,7 @@ int tdr_map_save_rasters(tdr_map* m, const char* dir) {
 static int map_load_rasters(tdr_map* m, const char* dir, int num_classes, float resolution, int center_x, int center_y);
 static int map_set_from_rasters(tdr_map* m, const uint8_t* d_planes, int num_classes, int rows, int cols,
                                 float resolution, int center_x, int center_y);
+static int map_adopt_static(tdr_map* m, int num_classes, int rows, int cols, float resolution, int center_x, int center_y);
 int tdr_map_load_rasters(tdr_map* m, const char* dir, int num_classes, float resolution, int center_x, int center_y) {
   try {   // (no exception crosses the C ABI: a file that makes an allocation fail is an error code)
     return map_load_rasters(m, dir, num_classes, resolution, center_x, center_y);
@@ -596,12 +598,18 @@ static int map_load_rasters(tdr_map* m, const char* dir, int num_classes, float 
 // what the constructor does with the class rasters of a static map (:48-58), from DEVICE planes in the class<i>.png layout
 static int map_set_from_rasters(tdr_map* m, const uint8_t* d_planes, int num_classes, int rows, int cols,
                                 float resolution, int center_x, int center_y) {
-  const size_t ncell = (size_t)rows * cols;
-  DevBuf<uint8_t> d_ws, d_mask;
-  DevBuf<float> d_maps;
+  DevBuf<uint8_t> d_ws;
   TTRY(d_ws.resize(tdr_map_ingest_workspace_bytes(num_classes, rows, cols)));
   TTRY(m->rec.resize(tdr_map_rec_floats_total(num_classes, rows, cols)));
   TTRY(tdr_k_map_from_rasters(d_planes, num_classes, rows, cols, resolution, m->rec.p, d_ws.p, nullptr));
+  return map_adopt_static(m, num_classes, rows, cols, resolution, center_x, center_y);
+}
+// the rest of the constructor for a static map whose cell records m->rec now hold (:48-63): host copies of class_maps_ /
+// class_mask_, compact records, geometric layers derived from the classes, have_map_ = true
+static int map_adopt_static(tdr_map* m, int num_classes, int rows, int cols, float resolution, int center_x, int center_y) {
+  const size_t ncell = (size_t)rows * cols;
+  DevBuf<uint8_t> d_mask;
+  DevBuf<float> d_maps;
   TTRY(d_maps.resize(ncell * num_classes));
   TTRY(d_mask.resize(ncell));
   TTRY(tdr_k_unpack_map(m->rec.p, num_classes, rows, cols, d_maps.p, d_mask.p, nullptr));
@@ -755,6 +763,85 @@ int tdr_map_load_svg(tdr_map* m, const char* path, const uint32_t* fill_keys, co
     const int W = (int)w, H = (int)h;   // Eigen::Vector2i map_size{width, height} (:107)
     return map_load_polygons(m, cv.data(), co.data(), cc.data(), (int64_t)cc.size(), W, H, num_classes, above, resolution,
                              center_x, center_y, nullptr);
+  } catch (const std::exception& e) {
+    return failh(TDR_ERR_NOMEM, "%s: %s", who, e.what());
+  }
+}
+
+// ---- the static colour raster map (src/top_down_map.cpp:32-42, then :48-63) -----------------------------------------
+// cv::imread (csrc/tdr_png.cpp for PNG), color2Ind + loadCompressedRasterMap + computeDists on the device
+// (tdr_k_map_from_color), then what the constructor does with every static map.  Geometric layers: on this branch
+// loadCompressedRasterMap leaves two constant-1 geo_maps_ (:126-133) and the constructor appends two more (:48-52), so
+// getGeoRasterMap (:410-427) and computeDists (:58) see four layers.  getGeoRasterMap zeroes all four, fills layer 1,
+// re-binarises all four (layers 2 and 3 become all 1) and sets layer 0 = 1 - layer 1; computeDists transforms each layer
+// on its own, and its mask (:294-299: a cell is masked where the four binary values sum past 4 - 1 = 3) is never set,
+// since layers 0 + 1 always sum to 1 and layers 2 + 3 to 2 — as with two layers (sum 1, never past 1).  So layers 0 and
+// 1 are those of the other static branches.  Layers 2 and 3 are not kept: the cache holds two (:252-256, :277-280) and
+// only getLocalGeoMap, which the node does not call, could reach them.
+static int color_check(const uint32_t* fill_keys, const int32_t* flatten_lut, int lut_size, int num_classes,
+                       float resolution, const char* who) {
+  if (!fill_keys || !flatten_lut) return failh(TDR_ERR_ARG, "%s: null lookup tables", who);
+  if (lut_size < 1 || lut_size > 256) return failh(TDR_ERR_ARG, "%s: lut_size %d outside [1, 256]", who, lut_size);
+  if (num_classes < 1 || num_classes > TDR_MAX_CLASSES)
+    return failh(TDR_ERR_ARG, "%s: num_classes %d outside [1, %d]", who, num_classes, TDR_MAX_CLASSES);
+  if (!(resolution > 0.f) || !std::isfinite(resolution)) return failh(TDR_ERR_ARG, "%s: resolution must be > 0", who);
+  if ((int)std::ceil(50.0 / (double)resolution) > 250)
+    return failh(TDR_ERR_ARG, "%s: resolution %g needs a distance window over 250 cells", who, (double)resolution);
+  return TDR_OK;
+}
+static int color_shape(int img_h, int img_w, float resolution, const char* who) {
+  if (img_h < 1 || img_w < 1 || img_h > (1 << 24) || img_w > (1 << 24))
+    return failh(TDR_ERR_ARG, "%s: image size %d x %d outside [1, 2^24]", who, img_w, img_h);
+  int rows = 0, cols = 0;
+  TTRY(tdr_map_ingest_shape(img_h, img_w, resolution, &rows, &cols));
+  if (rows < 1 || cols < 1) return failh(TDR_ERR_ARG, "%s: image size %d x %d gives an empty map", who, img_w, img_h);
+  return TDR_OK;
+}
+static int map_load_color(tdr_map* m, const uint8_t* bgr, int img_h, int img_w, const uint32_t* fill_keys,
+                          const int32_t* flatten_lut, int lut_size, int num_classes, float resolution, int center_x,
+                          int center_y) {
+  int rows = 0, cols = 0;
+  TTRY(tdr_map_ingest_shape(img_h, img_w, resolution, &rows, &cols));
+  const size_t nbytes = (size_t)img_h * img_w * 3;
+  DevBuf<uint8_t> d_img, d_ws;
+  TTRY(d_img.resize(nbytes));
+  TTRY(d_ws.resize(tdr_map_ingest_workspace_bytes(num_classes, rows, cols)));
+  HTRY(hipMemcpy(d_img.p, bgr, nbytes, hipMemcpyHostToDevice));
+  TTRY(m->rec.resize(tdr_map_rec_floats_total(num_classes, rows, cols)));
+  TTRY(tdr_k_map_from_color(d_img.p, img_h, img_w, fill_keys, flatten_lut, lut_size, num_classes, resolution, m->rec.p,
+                            d_ws.p, nullptr));
+  return map_adopt_static(m, num_classes, rows, cols, resolution, center_x, center_y);
+}
+
+int tdr_map_load_color_image(tdr_map* m, const uint8_t* bgr, int img_h, int img_w, const uint32_t* fill_keys,
+                             const int32_t* flatten_lut, int lut_size, int num_classes, float resolution, int center_x,
+                             int center_y) {
+  const char* who = "map_load_color_image";
+  if (!bgr) return failh(TDR_ERR_ARG, "%s: null image", who);
+  TTRY(color_check(fill_keys, flatten_lut, lut_size, num_classes, resolution, who));
+  TTRY(color_shape(img_h, img_w, resolution, who));
+  if (!m) return failh(TDR_ERR_ARG, "%s: null map", who);
+  try {
+    return map_load_color(m, bgr, img_h, img_w, fill_keys, flatten_lut, lut_size, num_classes, resolution, center_x,
+                          center_y);
+  } catch (const std::exception& e) {
+    return failh(TDR_ERR_NOMEM, "%s: %s", who, e.what());
+  }
+}
+
+int tdr_map_load_color_png(tdr_map* m, const char* path, const uint32_t* fill_keys, const int32_t* flatten_lut,
+                           int lut_size, int num_classes, float resolution, int center_x, int center_y) {
+  const char* who = "map_load_color_png";
+  if (!path) return failh(TDR_ERR_ARG, "%s: null path", who);
+  TTRY(color_check(fill_keys, flatten_lut, lut_size, num_classes, resolution, who));
+  if (!m) return failh(TDR_ERR_ARG, "%s: null map", who);
+  try {
+    std::vector<uint8_t> bgr;
+    int w = 0, h = 0;
+    TTRY(tdr_png_read_bgr8(path, bgr, w, h));   // cv::imread (:35)
+    TTRY(color_shape(h, w, resolution, who));
+    return map_load_color(m, bgr.data(), h, w, fill_keys, flatten_lut, lut_size, num_classes, resolution, center_x,
+                          center_y);
   } catch (const std::exception& e) {
     return failh(TDR_ERR_NOMEM, "%s: %s", who, e.what());
   }

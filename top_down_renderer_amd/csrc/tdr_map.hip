@@ -1,5 +1,7 @@
-// tdr_map.hip — map cell records (pack / unpack), map ingest from a label image, the polar sample table.
+// tdr_map.hip — map cell records (pack / unpack), map ingest from a label or colour image, the polar sample table.
 #include "tdr_common.h"
+
+#include <algorithm>
 
 // ------------------------------------------------------------------------------------------------------------------
 // K0: map packing.  Output is row-major over a GUARDED grid of (rows+2) x (cols+2) cell records: one ring of
@@ -54,18 +56,21 @@ extern "C" int tdr_k_pack_map(const float* class_maps, const uint8_t* class_mask
 // A label image gives one bit per cell; the per-class rasters of the raster cache may overlap.
 #define INGEST_MAXC 16
 #define INGEST_UNKNOWN 0x80000000u
+// the image pixel cell (yi, xi) reads (:137-138) — row 0 of the map is the bottom row of the image
+__device__ inline int64_t ingest_pixel(int yi, int xi, int img_h, int img_w, float resolution) {
+  int iy = (int)((float)img_h - (float)yi * resolution - 1.f);
+  iy = iy > 0 ? iy : 0;
+  int ix = (int)((float)xi * resolution);
+  ix = ix < img_w - 1 ? ix : img_w - 1;
+  return (int64_t)iy * img_w + ix;
+}
 __global__ void ingest_labels_kernel(const uint8_t* __restrict__ img, int img_h, int img_w,
                                      const int32_t* __restrict__ lut, int lut_size, int ncls, int rows, int cols,
                                      float resolution, uint32_t* __restrict__ cls_map) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)rows * cols) return;
   const int yi = (int)(idx / cols), xi = (int)(idx % cols);
-  // :137-138 — row 0 of the map is the bottom row of the image
-  int iy = (int)((float)img_h - (float)yi * resolution - 1.f);
-  iy = iy > 0 ? iy : 0;
-  int ix = (int)((float)xi * resolution);
-  ix = ix < img_w - 1 ? ix : img_w - 1;
-  const int label = img[(int64_t)iy * img_w + ix];
+  const int label = img[ingest_pixel(yi, xi, img_h, img_w, resolution)];
   int c = label < lut_size ? lut[label] : -1;
   if (c < 0 || c >= ncls) c = -1;  // :139
   cls_map[idx] = c < 0 ? INGEST_UNKNOWN : (1u << c);
@@ -219,6 +224,171 @@ extern "C" int tdr_k_map_from_rasters(const uint8_t* planes, int ncls, int rows,
   hipLaunchKernelGGL(ingest_rowmin_kernel, dim3((unsigned)cdiv(ncell, 256)), dim3(256), 0, s, (const uint32_t*)cls_map,
                      (const uint8_t*)g, ncls, rows, cols, R, resolution, rf, rec_out);
   LAUNCH_CHECK("map_from_rasters");
+  return TDR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// N1, colour maps: the TopDownMap constructor's branch for a colour raster image (src/top_down_map.cpp:32-42):
+// cv::imread -> SemanticColorLut::color2Ind -> loadCompressedRasterMap, with color2Ind on the device and fused into the
+// ingest's sampling step.  The image is cv::imread's BGR8 layout (B, G, R bytes per pixel, row 0 = top, rows packed).
+// A pixel's key is b << 16 | g << 8 | r — the key loadSvg builds for LUT index cls from unpackColor(ind2Color(cls))
+// (:80-84; unpackColor returns B, G, R), so one key array serves the SVG and the colour map (fill_keys).
+// color2Ind itself (semantics_manager) was not available to check against.  It is taken as the exact inverse of
+// ind2Color over the LUT: a pixel whose key is fill_keys[i] gets index i, the smallest such i when a colour appears under
+// several indices, and a pixel that matches no key gets no class (255 in the index image, unknown in the map).
+// The table is resolved on the host — at most 256 keys, sorted, each with its value (LUT index or flattened class) —
+// passed by value as a kernel argument and copied into LDS by every workgroup; a pixel costs one 8-step binary search.
+#define COLOR_TABLE_N 256
+#define COLOR_NONE 0xFFu
+struct ColorTable {
+  uint32_t key[COLOR_TABLE_N];   // ascending; padded with 0xFFFFFFFF, which no 24-bit key equals
+  uint8_t val[COLOR_TABLE_N];    // LUT index / flattened class of key[i]; COLOR_NONE: no class
+};
+// keys[n] (masked to 24 bits like the SVG loader masks fill colours) -> table; flatten_lut == NULL: values are the LUT
+// indices (color2Ind), else the flattened class flatten_lut[i] when it lies in [0, ncls) and COLOR_NONE otherwise
+static void color_table(const uint32_t* keys, const int32_t* flatten_lut, int n, int ncls, ColorTable& t) {
+  std::vector<std::pair<uint32_t, int>> kv;
+  for (int i = 0; i < n; i++) kv.emplace_back(keys[i] & 0xFFFFFFu, i);
+  std::sort(kv.begin(), kv.end());   // by key, then by index: the first of equal keys is the smallest index
+  int m = 0;
+  for (size_t j = 0; j < kv.size(); j++) {
+    if (m > 0 && t.key[m - 1] == kv[j].first) continue;
+    const int i = kv[j].second;
+    t.key[m] = kv[j].first;
+    t.val[m] = !flatten_lut ? (uint8_t)i
+                            : (flatten_lut[i] >= 0 && flatten_lut[i] < ncls ? (uint8_t)flatten_lut[i] : (uint8_t)COLOR_NONE);
+    m++;
+  }
+  for (; m < COLOR_TABLE_N; m++) { t.key[m] = 0xFFFFFFFFu; t.val[m] = COLOR_NONE; }
+}
+__device__ inline void color_table_to_lds(const ColorTable& t, uint32_t* skey, uint8_t* sval) {
+  for (int i = threadIdx.x; i < COLOR_TABLE_N; i += blockDim.x) { skey[i] = t.key[i]; sval[i] = t.val[i]; }
+  __syncthreads();
+}
+__device__ inline uint32_t color_lookup(const uint32_t* skey, const uint8_t* sval, uint32_t key) {
+  int lo = 0;   // lower bound: the number of table keys below `key`
+#pragma unroll
+  for (int s = COLOR_TABLE_N / 2; s > 0; s >>= 1) lo += skey[lo + s - 1] < key ? s : 0;
+  return (lo < COLOR_TABLE_N && skey[lo & (COLOR_TABLE_N - 1)] == key) ? sval[lo & (COLOR_TABLE_N - 1)] : COLOR_NONE;
+}
+__device__ inline uint32_t color_key(const uint8_t* px) { return (uint32_t)px[0] << 16 | (uint32_t)px[1] << 8 | px[2]; }
+// byte k of 16 bytes held as four little-endian words
+__device__ inline uint32_t byte_of(const uint4* v, int k) {
+  const uint32_t w[4] = {v[k >> 4].x, v[k >> 4].y, v[k >> 4].z, v[k >> 4].w};
+  return (w[(k >> 2) & 3] >> (8 * (k & 3))) & 0xFFu;
+}
+// 16 consecutive pixels = 48 bytes = three 16-byte loads (p must be 16-byte aligned); keys[j] = key of pixel j
+__device__ inline void color_keys16(const uint8_t* p, uint32_t* keys) {
+  uint4 v[3];
+  v[0] = reinterpret_cast<const uint4*>(p)[0];
+  v[1] = reinterpret_cast<const uint4*>(p)[1];
+  v[2] = reinterpret_cast<const uint4*>(p)[2];
+#pragma unroll
+  for (int j = 0; j < 16; j++) keys[j] = byte_of(v, 3 * j) << 16 | byte_of(v, 3 * j + 1) << 8 | byte_of(v, 3 * j + 2);
+}
+
+// color2Ind over the whole image: index_out[p] = LUT index of pixel p (CV_8UC1, 255 where nothing matches).  A thread
+// takes 16 pixels; with 16-byte aligned pointers it reads them with three 16-byte loads and writes one.
+__global__ void __launch_bounds__(256) color_index_kernel(const uint8_t* __restrict__ bgr, int64_t npix, int vec,
+                                                          ColorTable tab, uint8_t* __restrict__ index_out) {
+  __shared__ uint32_t skey[COLOR_TABLE_N];
+  __shared__ uint8_t sval[COLOR_TABLE_N];
+  color_table_to_lds(tab, skey, sval);
+  const int64_t p0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
+  if (p0 >= npix) return;
+  if (vec && p0 + 16 <= npix) {
+    uint32_t keys[16];
+    color_keys16(bgr + 3 * p0, keys);
+    uint32_t o[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 16; j++) o[j >> 2] |= color_lookup(skey, sval, keys[j]) << (8 * (j & 3));
+    *reinterpret_cast<uint4*>(index_out + p0) = make_uint4(o[0], o[1], o[2], o[3]);
+    return;
+  }
+  const int64_t p1 = p0 + 16 < npix ? p0 + 16 : npix;
+  for (int64_t p = p0; p < p1; p++) index_out[p] = (uint8_t)color_lookup(skey, sval, color_key(bgr + 3 * p));
+}
+
+// the ingest's first step for a colour image: ingest_labels_kernel with the label replaced by the looked-up class.  A
+// thread takes 16 cells of one map row.  At resolution 1 (cell (yi, xi) reads pixel (img_h - 1 - yi, xi)) with rows of a
+// multiple of 16 pixels and aligned pointers (vec != 0) the 16 pixels are contiguous and read with three 16-byte loads;
+// otherwise every cell reads its own pixel.
+__device__ inline uint32_t class_word(uint32_t c, int ncls) { return c < (uint32_t)ncls ? 1u << c : INGEST_UNKNOWN; }
+__global__ void __launch_bounds__(256) ingest_color_kernel(const uint8_t* __restrict__ bgr, int img_h, int img_w,
+                                                           ColorTable tab, int ncls, int rows, int cols, float resolution,
+                                                           int vec, uint32_t* __restrict__ cls_map) {
+  __shared__ uint32_t skey[COLOR_TABLE_N];
+  __shared__ uint8_t sval[COLOR_TABLE_N];
+  color_table_to_lds(tab, skey, sval);
+  const int64_t ncell = (int64_t)rows * cols;
+  const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
+  if (i0 >= ncell) return;
+  if (vec) {   // cols % 16 == 0: the 16 cells lie in one row
+    const int yi = (int)(i0 / cols), xi = (int)(i0 % cols);
+    uint32_t keys[16];
+    color_keys16(bgr + 3 * ingest_pixel(yi, xi, img_h, img_w, resolution), keys);
+    uint32_t o[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) o[j] = class_word(color_lookup(skey, sval, keys[j]), ncls);
+    uint4* dst = reinterpret_cast<uint4*>(cls_map + i0);
+#pragma unroll
+    for (int q = 0; q < 4; q++) dst[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+    return;
+  }
+  const int64_t i1 = i0 + 16 < ncell ? i0 + 16 : ncell;
+  for (int64_t idx = i0; idx < i1; idx++) {
+    const int yi = (int)(idx / cols), xi = (int)(idx % cols);
+    cls_map[idx] = class_word(color_lookup(skey, sval, color_key(bgr + 3 * ingest_pixel(yi, xi, img_h, img_w, resolution))), ncls);
+  }
+}
+
+extern "C" int tdr_k_color_index(const uint8_t* bgr, int img_h, int img_w, const uint32_t* fill_keys, int n_keys,
+                                 uint8_t* index_out, void* stream) {
+  if (!bgr || !fill_keys || !index_out) return fail(TDR_ERR_ARG, "color_index: null pointer");
+  if (n_keys < 1 || n_keys > COLOR_TABLE_N) return fail(TDR_ERR_ARG, "color_index: %d keys outside [1, 256]", n_keys);
+  if (img_h < 1 || img_w < 1) return fail(TDR_ERR_ARG, "color_index: bad image size %d x %d", img_w, img_h);
+  ColorTable tab;
+  color_table(fill_keys, nullptr, n_keys, 0, tab);
+  const int64_t npix = (int64_t)img_h * img_w;
+  const int vec = ((uintptr_t)bgr % 16 == 0 && (uintptr_t)index_out % 16 == 0) ? 1 : 0;
+  hipLaunchKernelGGL(color_index_kernel, dim3((unsigned)cdiv(cdiv(npix, 16), 256)), dim3(256), 0, (hipStream_t)stream,
+                     bgr, npix, vec, tab, index_out);
+  LAUNCH_CHECK("color_index");
+  return TDR_OK;
+}
+
+// loadCompressedRasterMap + computeDists for a colour image: as tdr_k_map_from_labels, with color2Ind and flatten_lut
+// applied by one table lookup per cell; then the same distance passes.  Exclusive classes are not applied (:116-144).
+extern "C" int tdr_k_map_from_color(const uint8_t* bgr, int img_h, int img_w, const uint32_t* fill_keys,
+                                    const int32_t* flatten_lut, int lut_size, int ncls, float resolution, float* rec_out,
+                                    void* workspace, void* stream) {
+  if (!bgr || !fill_keys || !flatten_lut || !rec_out || !workspace) return fail(TDR_ERR_ARG, "map_from_color: null pointer");
+  if (ncls < 1 || ncls > TDR_MAX_CLASSES || lut_size < 1 || lut_size > COLOR_TABLE_N)
+    return fail(TDR_ERR_ARG, "map_from_color: bad class count / lut size");
+  int rows, cols;
+  int rc = tdr_map_ingest_shape(img_h, img_w, resolution, &rows, &cols);
+  if (rc) return rc;
+  if (rows < 1 || cols < 1) return fail(TDR_ERR_ARG, "map_from_color: empty map");
+  const int R = (int)std::ceil(50.0 / (double)resolution);
+  if (R > 250) return fail(TDR_ERR_ARG, "map_from_color: resolution %g needs a %d-cell window (max 250)", resolution, R);
+  ColorTable tab;
+  color_table(fill_keys, flatten_lut, lut_size, ncls, tab);
+  const int rf = tdr_rec_floats(ncls);
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t* cls_map = reinterpret_cast<uint32_t*>(workspace);
+  uint8_t* g = reinterpret_cast<uint8_t*>(workspace) + (((size_t)rows * cols * 4 + 255) & ~(size_t)255);
+  const int64_t ncell = (int64_t)rows * cols;
+  const int64_t nrec = (int64_t)tdr_map_rec_floats_total(ncls, rows, cols);
+  const int vec = (resolution == 1.f && img_w % 16 == 0 && cols == img_w && (uintptr_t)bgr % 16 == 0 &&
+                   (uintptr_t)workspace % 16 == 0) ? 1 : 0;
+  hipLaunchKernelGGL(zero_floats_kernel, dim3((unsigned)cdiv(nrec, 256)), dim3(256), 0, s, rec_out, nrec);  // guard ring
+  hipLaunchKernelGGL(ingest_color_kernel, dim3((unsigned)cdiv(cdiv(ncell, 16), 256)), dim3(256), 0, s, bgr, img_h, img_w,
+                     tab, ncls, rows, cols, resolution, vec, cls_map);
+  hipLaunchKernelGGL(ingest_coldist_kernel, dim3((unsigned)cdiv(ncell, 256)), dim3(256), 0, s, (const uint32_t*)cls_map,
+                     ncls, rows, cols, R, g);
+  hipLaunchKernelGGL(ingest_rowmin_kernel, dim3((unsigned)cdiv(ncell, 256)), dim3(256), 0, s, (const uint32_t*)cls_map,
+                     (const uint8_t*)g, ncls, rows, cols, R, resolution, rf, rec_out);
+  LAUNCH_CHECK("map_from_color");
   return TDR_OK;
 }
 

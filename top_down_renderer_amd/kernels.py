@@ -168,6 +168,20 @@ def svg_parse(path):
     return size, keys[:n_poly.value], offs, verts[:n_vert.value]
 
 
+def png_read_color(path):
+    """tdr_png_read_color_host (host only, no GPU): the BGR8 image cv::imread(path) gives for a PNG, (H, W, 3) uint8,
+    row 0 = top, channels B, G, R."""
+    lib = _lib.load()
+    w, h = C.c_int(0), C.c_int(0)
+    rc = lib.tdr_png_read_color_host(str(path).encode(), None, 0, C.byref(w), C.byref(h))   # size query
+    if w.value < 1 or h.value < 1:
+        check(rc)
+    out = np.empty((h.value, w.value, 3), np.uint8)
+    check(lib.tdr_png_read_color_host(str(path).encode(), out.ctypes.data_as(C.c_void_p), out.size, C.byref(w),
+                                      C.byref(h)))
+    return out
+
+
 class HipKernels:
     name = "hip"
 
@@ -255,6 +269,62 @@ class HipKernels:
         m = DeviceMap(rec, ncls, rows, cols, resolution)
         m.compact(self)
         return m
+
+    def make_map_from_color(self, bgr, fill_keys, flatten_lut, ncls, resolution):
+        """bgr: (img_h, img_w, 3) uint8 image in cv::imread's layout.  Runs color2Ind + loadCompressedRasterMap +
+        computeDists on the device (tdr_k_map_from_color); fill_keys[i] = the key of LUT index i."""
+        bgr = np.ascontiguousarray(bgr, np.uint8)
+        img_h, img_w = bgr.shape[:2]
+        rows, cols = C.c_int(0), C.c_int(0)
+        check(self.lib.tdr_map_ingest_shape(img_h, img_w, C.c_float(resolution), C.byref(rows), C.byref(cols)))
+        rows, cols = rows.value, cols.value
+        keys = np.ascontiguousarray(fill_keys, np.uint32).ravel()
+        lut = np.ascontiguousarray(flatten_lut, np.int32).ravel()
+        if len(keys) < len(lut):
+            raise ValueError("one fill key per flatten_lut entry is needed")
+        img_d = self.to_device(bgr)
+        rec = self.empty((int(self.lib.tdr_map_rec_floats_total(ncls, rows, cols)),))
+        ws = self.empty((int(self.lib.tdr_map_ingest_workspace_bytes(ncls, rows, cols)),), torch.uint8)
+        check(self.lib.tdr_k_map_from_color(_ptr(img_d), img_h, img_w, keys.ctypes.data_as(C.c_void_p),
+                                            lut.ctypes.data_as(C.c_void_p), len(lut), ncls, C.c_float(resolution),
+                                            _ptr(rec), _ptr(ws), self.stream()))
+        self.synchronize()
+        m = DeviceMap(rec, ncls, rows, cols, resolution)
+        m.compact(self)
+        return m
+
+    def color_index(self, bgr, fill_keys):
+        """color2Ind on the device (tdr_k_color_index): (H, W, 3) uint8 BGR -> (H, W) uint8 LUT indices, 255 where no
+        key matches.  bgr may be a numpy array or a cuda uint8 tensor; a tensor gives a tensor."""
+        keys = np.ascontiguousarray(fill_keys, np.uint32).ravel()
+        on_dev = isinstance(bgr, torch.Tensor)
+        img_d = bgr.contiguous() if on_dev else self.to_device(np.ascontiguousarray(bgr, np.uint8))
+        if img_d.dtype != torch.uint8 or img_d.dim() != 3 or img_d.shape[2] != 3:
+            raise ValueError("color_index needs an (H, W, 3) uint8 image")
+        out = self.empty(tuple(img_d.shape[:2]), torch.uint8)
+        check(self.lib.tdr_k_color_index(_ptr(img_d), img_d.shape[0], img_d.shape[1], keys.ctypes.data_as(C.c_void_p),
+                                         len(keys), _ptr(out), self.stream()))
+        if on_dev:
+            return out
+        return out.cpu().numpy()
+
+    def map_load_color_image(self, handle, bgr, fill_keys, flatten_lut, ncls, resolution, center=(0, 0)):
+        """tdr_map_load_color_image: the reference constructor's colour-map branch on a tdr_map handle, from a host
+        (H, W, 3) uint8 BGR image."""
+        bgr = np.ascontiguousarray(bgr, np.uint8)
+        keys = np.ascontiguousarray(fill_keys, np.uint32)
+        lut = np.ascontiguousarray(flatten_lut, np.int32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        check(self.lib.tdr_map_load_color_image(handle, vp(bgr), bgr.shape[0], bgr.shape[1], vp(keys), vp(lut), len(lut),
+                                                int(ncls), C.c_float(resolution), int(center[0]), int(center[1])))
+
+    def map_load_color_png(self, handle, path, fill_keys, flatten_lut, ncls, resolution, center=(0, 0)):
+        """tdr_map_load_color_png: read the PNG (host), then tdr_map_load_color_image's path."""
+        keys = np.ascontiguousarray(fill_keys, np.uint32)
+        lut = np.ascontiguousarray(flatten_lut, np.int32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        check(self.lib.tdr_map_load_color_png(handle, str(path).encode(), vp(keys), vp(lut), len(lut), int(ncls),
+                                              C.c_float(resolution), int(center[0]), int(center[1])))
 
     def map_load_polygons(self, handle, verts, offs, cls, width, height, ncls, exclusive, resolution, center=(0, 0),
                           want_planes=True):

@@ -2,8 +2,9 @@
 top_down_map_polar.h:6-22) holding the map on the device for the HIP kernels.
 
 Map content is taken in the form the reference's load-time code produces (src/top_down_map.cpp:289-326): per-class
-truncated distance maps + unknown mask, or built on the GPU from a label image, a raster cache or an SVG vector map
-(loadVectorMap; parse_svg returns the polygons the reference's loadSvg keeps).
+truncated distance maps + unknown mask, or built on the GPU from a label image, a raster cache, an SVG vector map
+(loadVectorMap; parse_svg returns the polygons the reference's loadSvg keeps) or a colour raster map (loadColorRasterMap;
+png_read_color returns the BGR image cv::imread gives, color_index is color2Ind on the GPU).
 """
 from dataclasses import dataclass, field
 
@@ -27,6 +28,33 @@ def svg_fill_key(rgb):
     """The key loadSvg compares a shape's fill with (:82-84) for an (r, g, b) colour: c[0] << 16 | c[1] << 8 | c[2]."""
     r, g, b = (int(x) & 0xFF for x in rgb[:3])
     return (r << 16) | (g << 8) | b
+
+
+def color_key(bgr):
+    """The key of a BGR pixel (cv::imread's channel order) as the colour map's lookup compares it: b << 16 | g << 8 | r,
+    which is svg_fill_key of the same colour's unpackColor bytes — an SVG fill #ff0000 and a PNG pixel RGB (255, 0, 0)
+    have the same key 0x0000ff.  bgr: one (b, g, r) triple -> int, or an (..., 3) array -> uint32 array of keys."""
+    a = np.asarray(bgr)
+    if a.ndim == 1:
+        b, g, r = (int(x) & 0xFF for x in a[:3])
+        return (b << 16) | (g << 8) | r
+    a = a.astype(np.uint32)
+    return (a[..., 0] << 16) | (a[..., 1] << 8) | a[..., 2]
+
+
+def png_read_color(path):
+    """The BGR8 image cv::imread(path) gives for a PNG file (host only, no GPU): (H, W, 3) uint8, row 0 = top."""
+    from .kernels import png_read_color as read
+    return read(path)
+
+
+def color_index(bgr, fill_keys, kernels=None):
+    """SemanticColorLut::color2Ind on the GPU, taken as the exact inverse of ind2Color over the LUT: (H, W, 3) uint8
+    BGR -> (H, W) uint8, the smallest LUT index i with color_key(pixel) == fill_keys[i], 255 where none matches."""
+    if kernels is None:
+        from .kernels import HipKernels
+        kernels = HipKernels()
+    return kernels.color_index(bgr, fill_keys)
 
 
 @dataclass
@@ -165,6 +193,37 @@ class TopDownMap:
         self.rows, self.cols = self.dev.rows, self.dev.cols
         self.maps_cm_host, _ = self.k.unpack_map(self.dev)
         self.class_planes_ = planes
+        self.map_center_ = (int(map_center[0]), int(map_center[1]))
+        self.have_map_ = True                                                # :63
+        if old is not None and getattr(old, "nb", 0):
+            self.k.set_polar_table(self.dev, old.nb, old.nr, old.ang_res)
+
+    # top_down_map.cpp:32-42 + 48-63: the static colour raster map
+    def loadColorRasterMap(self, path_or_bgr, fill_keys, map_center=(0, 0)):
+        """The constructor's branch for a colour image: cv::imread (png_read_color for a path; an (H, W, 3) uint8 BGR
+        array is taken as decoded), color2Ind against fill_keys (fill_keys[i] = the key of LUT index i,
+        svg_fill_key(unpackColor(ind2Color(i)))) and loadCompressedRasterMap + computeDists on the GPU, geometric layers
+        derived from the classes like the constructor (:48-58).  have_map_ turns true even without road (:63)."""
+        import os
+        p = self.params_
+        if not p.num_classes or not len(p.flatten_lut):
+            raise ValueError("Params.num_classes and Params.flatten_lut are needed to load a colour map")
+        if len(fill_keys) < len(p.flatten_lut):
+            raise ValueError("one fill key per flatten_lut entry is needed")
+        if isinstance(path_or_bgr, (str, bytes, os.PathLike)):
+            if not os.path.exists(path_or_bgr):
+                raise FileNotFoundError(path_or_bgr)
+            bgr = png_read_color(path_or_bgr)
+        else:
+            bgr = np.ascontiguousarray(path_or_bgr, np.uint8)
+            if bgr.ndim != 3 or bgr.shape[2] != 3:
+                raise ValueError("loadColorRasterMap needs an (H, W, 3) BGR image")
+        old = self.dev
+        self.geo_constant_one_ = False
+        self.dev = self.k.make_map_from_color(bgr, list(fill_keys)[:len(p.flatten_lut)], p.flatten_lut, p.num_classes,
+                                              p.resolution)
+        self.rows, self.cols = self.dev.rows, self.dev.cols
+        self.maps_cm_host, _ = self.k.unpack_map(self.dev)
         self.map_center_ = (int(map_center[0]), int(map_center[1]))
         self.have_map_ = True                                                # :63
         if old is not None and getattr(old, "nb", 0):
