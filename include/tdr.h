@@ -807,6 +807,31 @@ int tdr_filter_compute_gmm(tdr_filter* f);
 int tdr_filter_get_gmm(tdr_filter* f, int max_k, int* k_out, float* means, float* covs);
 int64_t tdr_filter_adaptive_count(tdr_filter* f);
 
+/* ---- batched filters: many filters on one map stepped together (csrc/tdr_batch.hip) ------------------------------------
+ * tdr_batch_step = for every filter k: tdr_filter_propagate(filters[k], in[k].tx, in[k].ty, in[k].omega) followed by
+ * tdr_filter_update(filters[k], in[k].scan_imgs, in[k].renderer, in[k].res, in[k].n_target) — every filter ends BIT FOR BIT
+ * where those calls leave it (states, raw and normalised weights, statistics, resample indices, max-likelihood state, the
+ * generator's position in its stream).  Filters that qualify run on `stream` (a hipStream_t, NULL = the default stream),
+ * one launch per stage for the whole batch — propagate, scoring, statistics, running sum, resample — when
+ * they are not sharded, draw from the device generator in parity mode
+ * (a seeded filter whose generator is its own), have at most 32 768 particles, no particle still without a heading (the
+ * 40-rotation search of the first update) and a scoring launch of the float form (small windows and filters, see
+ * tdr_config_shift_uniform).  Every other filter runs its standalone calls inside the same tdr_batch_step, so a batch is
+ * always correct.  Each filter's own stream and generator streams are ordered against `stream` with events.
+ * Refused with TDR_ERR_ARG before any device work (no filter changes): k < 1, a null array or filter, a filter twice,
+ * filters on different maps, a map without samplePtsPolar, an input without a scan, a render whose shape is not the map's.
+ * scan_imgs: HOST [ncls][nb*nr] images as for tdr_filter_update, or NULL with `renderer` (its last render, on the device).
+ * tdr_batch_last_stats: how many filters of this thread's last tdr_batch_step took the batched path / their standalone calls. */
+typedef struct tdr_batch_input {
+  const float* scan_imgs;
+  const tdr_renderer* renderer;
+  float res;
+  float tx, ty, omega;
+  int64_t n_target;
+} tdr_batch_input;
+int tdr_batch_step(tdr_filter* const* filters, int k, const tdr_batch_input* in, void* stream);
+int tdr_batch_last_stats(int* batched, int* standalone);
+
 /* internal: lets tdr_host.cpp report through tdr_last_error() */
 int tdr_set_error(int code, const char* msg);
 

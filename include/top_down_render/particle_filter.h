@@ -103,6 +103,10 @@ class ParticleFilter {
   void update(const ScanRenderer& renderer, float res) {
     check(tdr_filter_update(f_, nullptr, renderer.handle(), res, next_count()), "update");
   }
+  // Extension: the handle and the particle count the next update asks for (ParticleFilterBatch, particle_filter_batch.h).
+  tdr_filter* handle() const { return f_; }
+  TopDownMapPolar* map() const { return map_; }
+  int64_t nextCount() { return next_count(); }
   // getGMM (:238-243) / computeGMM (:252-318)
   void computeGMM() { check(tdr_filter_compute_gmm(f_), "computeGMM"); }
   void getGMM(std::vector<Eigen::Vector3f>& means, std::vector<Eigen::Matrix3f>& covs) {

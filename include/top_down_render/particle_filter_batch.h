@@ -1,0 +1,72 @@
+// particle_filter_batch.h — many ParticleFilters that share one TopDownMapPolar stepped together (extension; the reference
+// steps one filter per node).  step() = propagate(priors[k]) + update(scans[k], res[k]) of every filter, through
+// tdr_batch_step (include/tdr.h): one launch per stage for the filters that qualify, their standalone calls for the
+// others, every filter ending bit for bit where those two calls would leave it.
+#pragma once
+
+#include <cstring>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "top_down_render/particle_filter.h"
+
+struct MotionPrior {   // the arguments of ParticleFilter::propagate
+  float tx = 0.f, ty = 0.f, omega = 0.f;
+};
+
+class ParticleFilterBatch {
+ public:
+  // scans[k]: the filter's per-class images (the shape given to samplePtsPolar), or empty with renderers[k] set.  res: one
+  // value per filter.  stream: a hipStream_t (nullptr = the default stream).  Throws on a refused batch.
+  void step(const std::vector<ParticleFilter*>& filters, const std::vector<std::vector<Eigen::ArrayXXf>>& scans,
+            const std::vector<float>& res, const std::vector<MotionPrior>& priors,
+            const std::vector<const ScanRenderer*>& renderers = {}, void* stream = nullptr) {
+    const size_t k = filters.size();
+    if (scans.size() != k || res.size() != k || priors.size() != k || (!renderers.empty() && renderers.size() != k))
+      throw std::invalid_argument("ParticleFilterBatch::step: one scan, res and prior per filter");
+    std::vector<tdr_filter*> handles(k, nullptr);
+    std::vector<tdr_batch_input> in(k);
+    std::vector<std::vector<float>> bufs(k);
+    for (size_t i = 0; i < k; i++) {
+      if (!filters[i]) throw std::invalid_argument("ParticleFilterBatch::step: null filter");
+      handles[i] = filters[i]->handle();
+      in[i] = tdr_batch_input{};
+      in[i].res = res[i];
+      in[i].tx = priors[i].tx;
+      in[i].ty = priors[i].ty;
+      in[i].omega = priors[i].omega;
+      in[i].n_target = filters[i]->nextCount();
+      if (!scans[i].empty()) {
+        // the images must have the map's class count and samplePtsPolar's shape (tdr_batch_step reads ncls * nb * nr
+        // floats): like ParticleFilter::update, but a batch refuses instead of skipping one filter
+        const TopDownMapPolar* m = filters[i]->map();
+        const int ncls = m->numClasses();
+        const Eigen::Vector2i shape = m->polarShape();
+        if ((int)scans[i].size() < ncls)
+          throw std::invalid_argument("ParticleFilterBatch::step: scan " + std::to_string(i) + " has " +
+                                      std::to_string(scans[i].size()) + " images, the map " + std::to_string(ncls) + " classes");
+        const size_t P = (size_t)shape[0] * shape[1];
+        for (int c = 0; c < ncls; c++)
+          if (scans[i][c].rows() != shape[0] || scans[i][c].cols() != shape[1])
+            throw std::invalid_argument("ParticleFilterBatch::step: scan " + std::to_string(i) + " image " + std::to_string(c) +
+                                        " is " + std::to_string(scans[i][c].rows()) + "x" + std::to_string(scans[i][c].cols()) +
+                                        ", samplePtsPolar was given " + std::to_string(shape[0]) + "x" + std::to_string(shape[1]));
+        bufs[i].resize(P * ncls);
+        for (int c = 0; c < ncls; c++) std::memcpy(bufs[i].data() + P * c, scans[i][c].data(), P * sizeof(float));
+        in[i].scan_imgs = bufs[i].data();
+      } else if (!renderers.empty() && renderers[i]) {
+        in[i].renderer = renderers[i]->handle();
+      }
+    }
+    if (tdr_batch_step(handles.data(), (int)k, in.data(), stream) != TDR_OK)
+      throw std::runtime_error(std::string("ParticleFilterBatch::step: ") + tdr_last_error());
+    tdr_batch_last_stats(&batched_, &standalone_);
+  }
+  // filters of the last step that took the batched path / their standalone calls
+  int lastBatched() const { return batched_; }
+  int lastStandalone() const { return standalone_; }
+
+ private:
+  int batched_ = 0, standalone_ = 0;
+};

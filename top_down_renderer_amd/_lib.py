@@ -31,6 +31,12 @@ class MapDescC(C.Structure):
                 ("rec16", C.c_void_p)]
 
 
+class BatchInputC(C.Structure):
+    """tdr_batch_input: one filter's share of a tdr_batch_step."""
+    _fields_ = [("scan_imgs", C.c_void_p), ("renderer", C.c_void_p), ("res", C.c_float), ("tx", C.c_float),
+                ("ty", C.c_float), ("omega", C.c_float), ("n_target", C.c_int64)]
+
+
 # name -> (restype, argtypes); every symbol include/tdr.h declares
 _vp, _i, _i64, _f, _u64, _u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_uint32
 SIGNATURES = {
@@ -218,6 +224,8 @@ SIGNATURES = {
     "tdr_filter_scale": (_f, [_vp]),
     "tdr_filter_num_particles": (_i64, [_vp]),
     "tdr_filter_update_map": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _i]),
+    "tdr_batch_step": (_i, [_vp, _i, _vp, _vp]),
+    "tdr_batch_last_stats": (_i, [_vp, _vp]),
     "tdr_set_error": (_i, [_i, C.c_char_p]),
     "tdr_locality_tmp_ints": (C.c_size_t, [_i64, _i, _i]),
     "tdr_locality_pose_tmp_ints": (C.c_size_t, [_i64]),

@@ -1,0 +1,172 @@
+"""Batched filters over the handle layer (include/tdr.h: tdr_batch_step): many filters that share one map stepped
+together — propagate + update of every filter, one launch per stage for those that qualify, the standalone calls for the
+others.  Each filter ends bit for bit where tdr_filter_propagate + tdr_filter_update would leave it.
+
+    m = MapHandle(class_maps, class_mask, resolution=1.0); m.sample_pts_polar(100, 25, ang_res)
+    fs = [FilterHandle(m, 20000, params, seed=s) for s in seeds]   # set_states / initialize_particles
+    step_batch(fs, scans, res, priors)                              # scans[k]: (ncls, nb, nr) array, or a Renderer
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import BatchInputC, FilterParamsC, check
+
+_vp = C.c_void_p
+STATE_DTYPE = np.dtype([("init_x_px", "<f4"), ("init_y_px", "<f4"), ("dx_m", "<f4"), ("dy_m", "<f4"), ("theta", "<f4"),
+                        ("scale", "<f4"), ("have_init", "u1"), ("pad", "u1", 3)])
+
+
+def _ptr(a):
+    return a.ctypes.data_as(_vp)
+
+
+class MapHandle:
+    """tdr_map: class_maps (ncls, rows, cols) distance maps, class_mask (rows, cols) with 1 = unknown."""
+
+    def __init__(self, class_maps, class_mask, resolution=1.0, center=(0, 0)):
+        self.L = _lib.load()
+        self.h = _vp()
+        check(self.L.tdr_map_create(C.byref(self.h)))
+        ncls, rows, cols = class_maps.shape
+        maps_cm = np.ascontiguousarray(np.transpose(class_maps, (0, 2, 1)), np.float32)
+        mask_cm = np.ascontiguousarray(np.asarray(class_mask).T, np.uint8)
+        check(self.L.tdr_map_set(self.h, _ptr(maps_cm), _ptr(mask_cm), ncls, rows, cols, C.c_float(resolution),
+                                 int(center[0]), int(center[1])))
+        self.ncls = ncls
+
+    def sample_pts_polar(self, nb, nr, ang_res):
+        check(self.L.tdr_map_sample_pts_polar(self.h, nb, nr, C.c_float(ang_res)))
+        self.shape = (nb, nr)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.tdr_map_destroy(self.h)
+            self.h = None
+
+
+class Renderer:
+    """tdr_renderer whose last render stays on the device (a batch input that needs no host images)."""
+
+    def __init__(self, lut256):
+        self.L = _lib.load()
+        self.h = _vp()
+        self._lut = np.ascontiguousarray(lut256, np.int32)
+        check(self.L.tdr_renderer_create(_ptr(self._lut), C.byref(self.h)))
+
+    def render_polar(self, pts, stride, ioff, res, ang_res, ncls, nb, nr):
+        """pts: points of `stride` floats, x y z at 0..2, the label at float `ioff`."""
+        pts = np.ascontiguousarray(pts, np.float32)
+        check(self.L.tdr_renderer_render(self.h, 1, _ptr(pts), stride, ioff, pts.size // stride, C.c_float(res),
+                                         C.c_float(ang_res), ncls, nb, nr, None))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.tdr_renderer_destroy(self.h)
+            self.h = None
+
+
+class FilterHandle:
+    """tdr_filter on a MapHandle; seed != 0 is the reference-ordered generator (parity mode)."""
+
+    def __init__(self, map_handle, n_max, params, seed=0):
+        self.L = _lib.load()
+        self.map = map_handle
+        self.h = _vp()
+        fp = params if isinstance(params, FilterParamsC) else params.to_c(map_handle.ncls)
+        check(self.L.tdr_filter_create(map_handle.h, int(n_max), C.byref(fp), int(seed), C.byref(self.h)))
+
+    def configure(self, parity_rng, locality_every=1):
+        check(self.L.tdr_filter_configure(self.h, int(parity_rng), int(locality_every)))
+
+    def set_states(self, states):
+        states = np.ascontiguousarray(states, STATE_DTYPE)
+        check(self.L.tdr_filter_set_states(self.h, _ptr(states), len(states)))
+
+    def num_particles(self):
+        return int(self.L.tdr_filter_num_particles(self.h))
+
+    def states(self):
+        out = np.zeros(self.num_particles(), STATE_DTYPE)
+        check(self.L.tdr_filter_get_states(self.h, _ptr(out), len(out)))
+        return out
+
+    def _floats(self, fn, n):
+        out = np.zeros(n, np.float32)
+        check(fn(self.h, _ptr(out), n))
+        return out
+
+    def weights(self):
+        return self._floats(self.L.tdr_filter_get_weights, self.num_particles())
+
+    def raw_weights(self, n):
+        return self._floats(self.L.tdr_filter_get_raw_weights, n)
+
+    def resample_indices(self):
+        out = np.zeros(self.num_particles(), np.int32)
+        check(self.L.tdr_filter_get_resample_indices(self.h, _ptr(out), len(out)))
+        return out
+
+    def mean_cov(self, about_max=False):
+        st, cov = np.zeros(4, np.float32), np.zeros(16, np.float32)
+        check(self.L.tdr_filter_mean_cov(self.h, int(bool(about_max)), _ptr(st), _ptr(cov)))
+        return st, cov.reshape(4, 4)
+
+    def propagate(self, tx, ty, omega):
+        check(self.L.tdr_filter_propagate(self.h, C.c_float(tx), C.c_float(ty), C.c_float(omega)))
+
+    def update(self, scan, res, n_target=-1):
+        if isinstance(scan, Renderer):
+            check(self.L.tdr_filter_update(self.h, None, scan.h, C.c_float(res), int(n_target)))
+        else:
+            imgs = _scan_images(scan, self.map)
+            check(self.L.tdr_filter_update(self.h, _ptr(imgs), None, C.c_float(res), int(n_target)))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.tdr_filter_destroy(self.h)
+            self.h = None
+
+
+def _scan_images(scan, map_handle):
+    """(ncls, nb, nr) images -> the column-major [ncls][nb*nr] layout tdr_filter_update reads; the shape is checked."""
+    a = np.asarray(scan, np.float32)
+    want = (map_handle.ncls,) + tuple(map_handle.shape)
+    if a.shape != want:
+        raise ValueError(f"scan of shape {a.shape}, the map expects {want}")
+    return np.ascontiguousarray(np.transpose(a, (0, 2, 1)))
+
+
+def step_batch(filters, scans, res, priors, n_targets=None, stream=None):
+    """propagate(priors[k]) + update(scans[k], res[k], n_targets[k]) of every filter in one tdr_batch_step.
+    priors[k] = (tx, ty, omega); res: a float or one per filter; scans[k]: (ncls, nb, nr) images or a Renderer.
+    stream: a hipStream_t as an int (None = the default stream).  Returns (batched, standalone) filter counts."""
+    L = _lib.load()
+    k = len(filters)
+    if len(scans) != k or len(priors) != k:
+        raise ValueError("step_batch: one scan and one prior per filter")
+    resv = list(res) if np.ndim(res) else [float(res)] * k
+    nts = [-1] * k if n_targets is None else [int(t) for t in n_targets]
+    arr = (_vp * max(k, 1))(*[f.h for f in filters])
+    ins = (BatchInputC * max(k, 1))()
+    keep = []
+    for i, (f, sc, pr) in enumerate(zip(filters, scans, priors)):
+        if isinstance(sc, Renderer):
+            ins[i].renderer = sc.h
+        else:
+            imgs = _scan_images(sc, f.map)
+            keep.append(imgs)
+            ins[i].scan_imgs = imgs.ctypes.data
+        ins[i].res, ins[i].n_target = resv[i], nts[i]
+        ins[i].tx, ins[i].ty, ins[i].omega = (float(v) for v in pr)
+    check(L.tdr_batch_step(arr, k, ins, _vp(stream) if stream else None))
+    return last_stats()
+
+
+def last_stats():
+    """(batched, standalone): how the filters of this thread's last step_batch were stepped."""
+    L = _lib.load()
+    a, b = C.c_int(), C.c_int()
+    check(L.tdr_batch_last_stats(C.byref(a), C.byref(b)))
+    return a.value, b.value

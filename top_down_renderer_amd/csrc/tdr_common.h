@@ -71,6 +71,8 @@ int tdr_chain_total(const float* raw, const float* mean_dev, int kind, int64_t n
                     hipStream_t st);
 // tdr_prefix.hip: particle_filter.cpp:107-147 for n <= 32768 in one launch, both serial chains exact
 int tdr_uw_small(const float* raw, const float* last_dist, int64_t n, float* w, float* info, hipStream_t st);
+// tdr_score.hip: whether tdr_k_score_polar_ctx scores a filter of these shapes with the float kernel (not the integer form)
+bool tdr_score_polar_float_form(const tdr_map_desc* map, int nb, int nr, int64_t n, int64_t n_total);
 // a record with a spare slot (ncls + 2 <= rf) carries `known` twice: slot rf-2 pairs with a constant 1 of the scan record
 __host__ __device__ inline bool tdr_has_kslot(int ncls, int rf) { return ncls + 2 <= rf; }
 // diagnostics: 16 device counters while tdr_profile_enable(1) is in force, else NULL (tdr_score.hip, tdr_profile_variants)

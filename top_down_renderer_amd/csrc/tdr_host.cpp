@@ -21,6 +21,9 @@
 #include <vector>
 
 #include "tdr.h"
+#include "tdr_batch.h"
+
+bool tdr_score_polar_float_form(const tdr_map_desc* map, int nb, int nr, int64_t n, int64_t n_total);   // tdr_score.hip
 
 extern "C" int tdr_set_error(int code, const char* msg);  // tdr_core.hip
 
@@ -1479,6 +1482,185 @@ int tdr_filter_update_map(tdr_filter* f, const float* class_maps, const uint8_t*
   return tdr_filter_initialize_particles(f);  // :337-340
 }
 
+
+// ---- batched filters (tdr_batch_step): many filters on one map, one launch per stage -------------------------------------
+// Each filter keeps what is its own: its generator pipe draws its normals and its uniform (per-filter mt19937 streams) and
+// its scan is packed into its own buffer.  The stages of the step are then one launch each over a table of the filters:
+// propagate and resample (csrc/tdr_batch.hip), the float scoring launch (tdr_score.hip), the statistics and the running
+// sum (tdr_prefix.hip).  The locality order is left out: it never changes results (tdr.h).
+namespace {
+thread_local int g_batch_stats[2] = {0, 0};   // filters of this thread's last batch: batched, standalone
+struct BatchCtx {   // per thread: the tables, staged in pinned host memory and copied to the device, reused from call to call
+  char* host = nullptr;
+  DevBuf<char> dev;
+  size_t cap = 0;
+  hipEvent_t uploaded = nullptr;   // the last call's copy has read `host`
+  hipEvent_t done = nullptr;       // the last call's kernels have read `dev`
+  ~BatchCtx() {
+    if (uploaded) { (void)hipEventSynchronize(uploaded); (void)hipEventDestroy(uploaded); }
+    if (done) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+    if (host) (void)hipHostFree(host);
+  }
+};
+thread_local BatchCtx g_batch;
+}  // namespace
+
+extern "C" {
+int tdr_batch_last_stats(int* batched, int* standalone) {
+  if (batched) *batched = g_batch_stats[0];
+  if (standalone) *standalone = g_batch_stats[1];
+  return TDR_OK;
+}
+
+static bool batch_eligible(const tdr_filter* f) {
+  const tdr_map* m = f->map;
+  return !f->comm && rng_device_capable(f) && !f->maybe_uninit && f->n >= 1 && f->n <= 32768 &&
+         tdr_score_polar_float_form(&m->desc, m->nb, m->nr, f->n, f->n);
+}
+
+int tdr_batch_step(tdr_filter* const* filters, int k, const tdr_batch_input* in, void* stream) {
+  g_batch_stats[0] = g_batch_stats[1] = 0;
+  if (k < 1) return failh(TDR_ERR_ARG, "batch_step: k = %d, at least one filter is needed", k);
+  if (!filters || !in) return failh(TDR_ERR_ARG, "batch_step: null %s array", !filters ? "filter" : "input");
+  for (int i = 0; i < k; i++)
+    if (!filters[i]) return failh(TDR_ERR_ARG, "batch_step: filter %d is null", i);
+  {
+    std::vector<const tdr_filter*> seen(filters, filters + k);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+      return failh(TDR_ERR_ARG, "batch_step: a filter appears twice in the batch");
+  }
+  tdr_map* m = filters[0]->map;
+  for (int i = 0; i < k; i++)
+    if (filters[i]->map != m) return failh(TDR_ERR_ARG, "batch_step: filter %d is on another map than filter 0", i);
+  if (!m || !m->have_map) return failh(TDR_ERR_ARG, "batch_step: the filters' map holds no map");
+  if (m->nb < 1 || !m->tab.p) return failh(TDR_ERR_ARG, "batch_step: samplePtsPolar was never called on the map");
+  const int ncls = m->desc.ncls, nb = m->nb, nr = m->nr;
+  for (int i = 0; i < k; i++) {
+    const tdr_renderer* r = in[i].renderer;
+    if (!in[i].scan_imgs && !r) return failh(TDR_ERR_ARG, "batch_step: input %d has no scan", i);
+    if (!in[i].scan_imgs && !r->have_scan) return failh(TDR_ERR_ARG, "batch_step: input %d: the renderer has no render", i);
+    if (!in[i].scan_imgs && (r->ncls != ncls || r->rows != nb || r->cols != nr))
+      return failh(TDR_ERR_ARG, "batch_step: input %d: render shape %dx%dx%d does not match the map's %dx%dx%d", i, r->ncls,
+                   r->rows, r->cols, ncls, nb, nr);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> fast;
+  for (int i = 0; i < k; i++) {
+    tdr_filter* f = filters[i];
+    if (batch_eligible(f)) { fast.push_back(i); continue; }
+    TTRY(tdr_filter_propagate(f, in[i].tx, in[i].ty, in[i].omega));
+    TTRY(tdr_filter_update(f, in[i].scan_imgs, in[i].renderer, in[i].res, in[i].n_target));
+    g_batch_stats[1]++;
+  }
+  const int kf = (int)fast.size();
+  if (kf == 0) return TDR_OK;
+
+  BatchCtx& B = g_batch;
+  // one staging area: [kf] TdrBatchEntry, then the scoring launch's tables (tdr_batch_score_stage_bytes)
+  const size_t ent_bytes = (sizeof(TdrBatchEntry) * (size_t)kf + 63) / 64 * 64;
+  const size_t stage = ent_bytes + tdr_batch_score_stage_bytes(kf);
+  if (!B.uploaded) HTRY(hipEventCreateWithFlags(&B.uploaded, hipEventDisableTiming));
+  if (!B.done) HTRY(hipEventCreateWithFlags(&B.done, hipEventDisableTiming));
+  HTRY(hipEventSynchronize(B.uploaded));   // (the previous call's copy has left the pinned buffer)
+  if (B.cap < stage) {
+    HTRY(hipEventSynchronize(B.done));     // (and its kernels the device buffer that is replaced)
+    if (B.host) HTRY(hipHostFree(B.host));
+    B.host = nullptr;
+    B.cap = 0;
+    HTRY(hipHostMalloc((void**)&B.host, stage));
+    B.cap = stage;
+  }
+  TTRY(B.dev.resize(stage));
+  TdrBatchEntry* const tab = reinterpret_cast<TdrBatchEntry*>(B.host);
+  TdrBatchEntry* const tab_dev = reinterpret_cast<TdrBatchEntry*>(B.dev.p);
+
+  // the batch stream continues after everything already queued on the filters' own streams, and after the previous
+  // batch's kernels have read the device tables this call overwrites
+  std::vector<hipEvent_t> evs((size_t)kf, nullptr);
+  auto destroy_events = [&]() { for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e); };
+  int rc = TDR_OK;
+  if (hipStreamWaitEvent(s, B.done, 0) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: stream wait");
+  for (int j = 0; j < kf && rc == TDR_OK; j++) {
+    tdr_filter* f = filters[fast[j]];
+    rc = rng_to_device(f);
+    if (rc == TDR_OK && hipEventCreateWithFlags(&evs[j], hipEventDisableTiming) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: event");
+    if (rc == TDR_OK && hipEventRecord(evs[j], f->stream) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: event record");
+    if (rc == TDR_OK && hipStreamWaitEvent(s, evs[j], 0) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: stream wait");
+  }
+  if (rc != TDR_OK) { destroy_events(); return rc; }
+
+  // per filter: its generator's normals and uniform (the pipe orders its own side stream against `s`; the draws keep the
+  // standalone order), its scan packed into its own buffer, and its table entries
+  const size_t P = (size_t)nb * nr, pk_floats = P * tdr_rec_floats(ncls);
+  std::vector<TdrBatchScoreIn> sin((size_t)kf);
+  int blocks_prop = 0, blocks_res = 0;
+  int64_t n_big = 1;
+  for (int j = 0; j < kf && rc == TDR_OK; j++) {
+    tdr_filter* f = filters[fast[j]];
+    const tdr_batch_input& x = in[fast[j]];
+    TdrBatchEntry& e = tab[j];
+    e = TdrBatchEntry{};
+    f->states_changed();
+    f->fp.num_classes = ncls;
+    rc = tdr_rng_pipe_normals(f->pipe, f->n, 0, f->n, f->scale_frozen ? 1 : 0, &e.z4, s);
+    f->prop_calls++;
+    if (rc == TDR_OK) rc = tdr_rng_pipe_uniform(f->pipe, &e.shift, s);
+    if (rc == TDR_OK) rc = f->ml_dev.resize(12);
+    const float* pk = nullptr;
+    if (rc == TDR_OK && x.scan_imgs) {
+      rc = f->scan_img.resize(P * ncls);
+      if (rc == TDR_OK) rc = f->scan_pk.resize(pk_floats);
+      if (rc == TDR_OK && hipMemcpyAsync(f->scan_img.p, x.scan_imgs, P * ncls * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)
+        rc = failh(TDR_ERR_HIP, "batch_step: scan upload");
+      if (rc == TDR_OK) rc = tdr_k_pack_scan(f->scan_img.p, ncls, nb, nr, f->scan_pk.p, s);
+      pk = f->scan_pk.p;
+    } else {
+      pk = x.renderer->pk.p;
+    }
+    if (rc == TDR_OK) rc = f->ws.resize(tdr_score_workspace_floats(ncls, nb, nr, f->n, f->n));
+    int64_t n_new = f->n;
+    if (x.n_target >= 0) n_new = std::max<int64_t>(1, std::min<int64_t>(x.n_target, f->n_max));
+    e.st = f->st.p; e.st_new = f->st_new.p; e.last_dist = f->last_dist.p; e.cap = f->cap; e.n = f->n; e.n_new = n_new;
+    e.tx = x.tx; e.ty = x.ty; e.omega = x.omega; e.pos_cov = f->fp.pos_cov; e.theta_cov = f->fp.theta_cov;
+    e.scale_freeze = f->scale_frozen ? 1 : 0;
+    e.raw_w = f->raw_w.p; e.w_out = f->w.p; e.info_out = f->info.p; e.runmax_out = f->runmax.p;
+    e.runmax = f->runmax.p; e.info = f->info.p; e.idx = f->idx.p; e.ml = f->ml_dev.p;
+    e.blk_prop = blocks_prop;
+    blocks_prop += (int)((f->n + TDR_BATCH_THREADS - 1) / TDR_BATCH_THREADS);
+    e.blk_res = blocks_res;
+    blocks_res += (int)((n_new + TDR_BATCH_THREADS - 1) / TDR_BATCH_THREADS);
+    n_big = std::max(n_big, f->n);
+    sin[j] = TdrBatchScoreIn{pk, x.res, &f->fp, f->st.p, f->cap, f->n, f->uniform_scale, f->raw_w.p, f->ws.p};
+  }
+  if (rc == TDR_OK) rc = tdr_batch_score_build(&m->desc, m->tab.p, nb, nr, kf, sin.data(), B.host + ent_bytes);
+  if (rc == TDR_OK && hipMemcpyAsync(B.dev.p, B.host, stage, hipMemcpyHostToDevice, s) != hipSuccess)
+    rc = failh(TDR_ERR_HIP, "batch_step: table upload");
+  if (rc == TDR_OK && hipEventRecord(B.uploaded, s) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: event record");
+  // one launch per stage over the whole batch (the scoring launch: utab, score, finalize)
+  if (rc == TDR_OK) rc = tdr_batch_propagate(tab_dev, kf, blocks_prop, s);
+  if (rc == TDR_OK) rc = tdr_batch_score_launch(&m->desc, m->tab.p, nb, nr, kf, B.host + ent_bytes, B.dev.p + ent_bytes, s);
+  if (rc == TDR_OK) rc = tdr_batch_update_weights(tab_dev, kf, n_big, s);
+  if (rc == TDR_OK) rc = tdr_batch_prefix(tab_dev, kf, n_big, s);
+  if (rc == TDR_OK) rc = tdr_batch_resample(tab_dev, kf, blocks_res, s);
+  if (rc == TDR_OK && hipEventRecord(B.done, s) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: event record");
+  if (rc != TDR_OK) { destroy_events(); return rc; }
+  for (int j = 0; j < kf; j++) {
+    tdr_filter* f = filters[fast[j]];
+    f->have_ml = true;
+    f->states_changed();
+    std::swap(f->st.p, f->st_new.p);   // particle_filter.cpp:187
+    f->n = tab[j].n_new;
+    f->step++;
+  }
+  // the filters' own streams continue after the batch
+  for (int j = 0; j < kf && rc == TDR_OK; j++)
+    if (hipStreamWaitEvent(filters[fast[j]]->stream, B.done, 0) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: stream wait");
+  destroy_events();
+  g_batch_stats[0] = kf;
+  return rc;
+}
+}  // extern "C"
 
 // ---- device self-test of the scoring kernels -------------------------------------------------------------------------------
 // The integer-form kernels run hand-scheduled, generated assembly (tdr_score_su_asm.h, tdr_score_cart_asm.h): a toolchain

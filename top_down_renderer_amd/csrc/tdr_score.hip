@@ -2,6 +2,7 @@
 #include <type_traits>
 
 #include "tdr_common.h"
+#include "tdr_batch.h"
 #include "tdr_sincosf.h"
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -336,6 +337,282 @@ __global__ __launch_bounds__(256, COMPACT ? (WIDE ? 3 : 5) : 1) void score_polar
   __syncthreads();
   if (threadIdx.x == 0 && tl_id < TDR_TL_MAX) g_timeline[2 * tl_id + 1] = wall_clock64();
 #endif
+}
+
+// score_polar_kernel's body for workgroup (bx, by), for score_polar_batch_kernel (one grid over many filters).  A copy
+// rather than a shared function: the existing kernel keeps its own text, so it compiles to the same code as before.
+template <int NV4, int U, bool KSLOT, bool USCALE, bool COMPACT, bool WIDE = false, bool SKIP = false>
+__device__ __forceinline__ void score_polar_body(const ScoreArgs& a, const unsigned bx, const unsigned by) {
+  constexpr int RF = 4 * NV4;
+  static_assert(!WIDE || (COMPACT && NV4 == 2), "wide compact records: 8-float dense records only");
+  static_assert(!SKIP || (COMPACT && !WIDE), "SKIP: narrow compact records only");
+  constexpr int CW = WIDE ? 4 : CmapShape<RF, KSLOT>::CW, LC = WIDE ? 1 : CmapShape<RF, KSLOT>::LC;
+  constexpr int NDICT = WIDE ? TDR_CMAP_WIDE_MAX_DICT : TDR_CMAP_MAX_DICT;
+#ifdef TDR_SCORE_TIMELINE
+  const unsigned tl_id = blockIdx.y * gridDim.x + blockIdx.x;
+  if (threadIdx.x == 0 && tl_id < TDR_TL_MAX) g_timeline[2 * tl_id] = wall_clock64();
+#endif
+  extern __shared__ float4 ring[];  // [nb rows][rs]: a row's (ring, plane) records side by side, rs = group * NV4 | 1
+  __shared__ float ldict[COMPACT ? NDICT : 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t slot = ((int64_t)bx * 4 + wave) * 64 + lane;
+  if (a.run_if && !int_form_off(a.run_if)) return;  // (uniform)
+  const int64_t nact = a.count ? (int64_t)*a.count : a.n;
+  if ((int64_t)bx * 256 >= nact) return;  // whole workgroup idle (uniform)
+  const bool valid = slot < nact;
+  const int64_t sbase = a.slot_base ? (int64_t)*a.slot_base : 0;
+  const int64_t p = a.order ? (int64_t)a.order[sbase + (valid ? slot : 0)] : (valid ? slot : 0);
+  if (a.only_uninit && !__syncthreads_or(valid && a.st[TDR_ST_HAVE_INIT * a.cap + p] == 0.f)) return;
+  const float scale = a.st[TDR_ST_SCALE * a.cap + p];
+  const float cx = a.st[TDR_ST_DX * a.cap + p] * scale + a.st[TDR_ST_INIT_X * a.cap + p];  // state_particle.cpp:161
+  const float cy = a.st[TDR_ST_DY * a.cap + p] * scale + a.st[TDR_ST_INIT_Y * a.cap + p];  // :162
+  const float off0 = cy / a.resolution;  // top_down_map_polar.cpp:29
+  const float off1 = cx / a.resolution;  // :30
+  const float theta = a.use_theta_override ? a.theta_override : a.st[TDR_ST_THETA * a.cap + p];
+  const int shift = rot_shift_dev(theta, a.nb);  // scan row paired with window row i is (i + shift) mod nb
+
+  const int j0 = by * a.group, gn = min(a.nr - j0, a.group);   // this workgroup's rings: [j0, j0 + gn)
+  const int rowstride = (a.cols + 2) * (RF * 4);            // bytes per guarded map row
+  const int kbase = (a.cols + 3) * (RF * 4);                // byte offset of cell (0,0)
+  const float rmaxf = (float)a.rows, cmaxf = (float)a.cols;
+  const char* __restrict__ recb = reinterpret_cast<const char*>(a.rec);
+  const char* __restrict__ crecb = reinterpret_cast<const char*>(a.crec);
+  const int ckcol = a.ctiles_r * 128 - 16 * CW, ckconst = a.ctiles_r * 128 + 128;   // cmap_offset
+  // The sample table is read-only for the whole launch and every lane of a wave reads the same entry: it is addressed
+  // through the CONSTANT address space so that these are scalar loads whatever else the kernel contains.  (Left to its
+  // own no-clobber analysis the compiler gives up in the compact kernel — the dictionary staging is one store too many —
+  // and emits vector loads with a full wait in front of every address computation.)
+  typedef const float __attribute__((address_space(4))) * tdr_const_f;
+  const tdr_const_f tabc = (tdr_const_f)(USCALE ? a.utab : a.tab);
+  auto tab_at = [&](int64_t k) { return make_float2(tabc[2 * k], tabc[2 * k + 1]); };
+  const float4* __restrict__ scan4 = reinterpret_cast<const float4*>(a.scan_pk);
+  const int nb = a.nb;
+
+  // stage the group's scan rows and (compact) the dictionary
+  bool dict_bad = false;   // a non-finite dictionary value: 0 x inf must stay NaN, nothing may be skipped
+  if constexpr (COMPACT)
+    for (int t = threadIdx.x; t < a.dict_n; t += 256) {
+      const float v = a.dict[t];
+      ldict[t] = v;
+      if constexpr (SKIP) dict_bad |= !(fabsf(v) <= 3.402823466e+38f);
+    }
+  // One row of the LDS image = the scan records (ring, plane) of one direction, 16 bytes each, side by side: a step
+  // reads them with ONE address per lane and immediate offsets.  The row stride is an ODD number of 16-byte slots, so
+  // lanes on different rows (different headings) fall on different banks.
+  const int rs = (a.group * NV4) | 1;
+  for (int jj = 0; jj < gn; jj++)
+    for (int t = threadIdx.x; t < nb * NV4; t += 256) {
+      const float4 v = scan4[(int64_t)(j0 + jj) * nb * NV4 + t];
+      const int row = t / NV4, pl = t - row * NV4;
+      ring[row * rs + jj * NV4 + pl] = v;
+    }
+  bool skip_ok = false;
+  if constexpr (SKIP) skip_ok = !__syncthreads_or(dict_bad);
+  else __syncthreads();
+
+  // USCALE: every particle has the same scale, so (tab*scale)*res was evaluated once per step into a.utab and is
+  // wave-uniform here; otherwise it is evaluated per lane.  Identical float operations either way.
+  // Returns the byte offset of the sample's record (dense: guarded row-major grid; compact: tiled).
+  typedef float tdr_v2f __attribute__((ext_vector_type(2)));   // both coordinates in one v_pk_add_f32 / v_pk_mul_f32
+  const tdr_v2f offv = {off0, off1};
+  unsigned moff[SKIP ? U : 1];   // SKIP: byte offset (from crec) of the known-mask word of sample u's cell ...
+  int mbit[SKIP ? U : 1];        // ... and the cell's column (its low 5 bits: the bit in that word)
+  const int mconst = (int)a.kmask_off + a.kmask_row + 128;   // kmask_offset
+  auto cell_offset = [&](float2 t, int u) -> unsigned {
+    tdr_v2f pv = {t.x, t.y};
+    if constexpr (!USCALE) pv = (pv * scale) * a.res;  // top_down_map_polar.cpp:28
+    pv = pv + offv;                                     // :29-30
+    // clamp into the guard ring, then round like `pts.round().cast<int>()` (:31): roundf(x) == floor(fl(x + (0.5 - 2^-25)))
+    // on [-1, 2^23] (round_half_away_clamped), the addition done for both coordinates at once
+    tdr_v2f qv = {__builtin_amdgcn_fmed3f(pv.x, -1.f, rmaxf), __builtin_amdgcn_fmed3f(pv.y, -1.f, cmaxf)};
+    qv = qv + 0.49999997f;
+    int ri, ci;
+    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ri) : "v"(qv.x));
+    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ci) : "v"(qv.y));
+    if constexpr (SKIP) {
+      moff[u] = kmask_offset(ri, ci, a.kmask_row, mconst);
+      mbit[u] = ci;
+    }
+    if constexpr (COMPACT) {
+      // cells of the guard ring are zero records in their own right (distance 0, unknown): no select needed
+      return cmap_offset<CW, LC>(ri, ci, ckcol, ckconst);
+    } else {
+#if TDR_OOB_ALIAS
+      // every out-of-bounds sample reads the SAME guard record (always cache-resident) instead of a distinct one
+      const bool inb = (unsigned)ri < (unsigned)a.rows && (unsigned)ci < (unsigned)a.cols;
+      return inb ? (unsigned)(__mul24(ri, rowstride) + (ci * (RF * 4) + kbase)) : 0u;
+#else
+      return (unsigned)(__mul24(ri, rowstride) + (ci * (RF * 4) + kbase));  // v_mad_i32_i24 + v_lshl_add
+#endif
+    }
+  };
+  // the record at `off` as the RF operands of the product sums (compact: decoded, bit-identical to the dense record)
+  struct Raw { uint32_t w[COMPACT ? CW : 1]; float4 q[COMPACT ? 1 : NV4]; };
+  auto load_raw = [&](unsigned off, Raw& r) {
+    if constexpr (COMPACT) cmap_load<CW>(crecb, off, r.w);
+    else {
+#pragma unroll
+      for (int v = 0; v < NV4; v++) r.q[v] = *reinterpret_cast<const float4*>(recb + off + 16 * v);
+    }
+  };
+  auto operands = [&](const Raw& r, float (&m)[RF]) {
+    if constexpr (WIDE) cmap_decode_wide<RF, KSLOT>(r.w, ldict, m);
+    else if constexpr (COMPACT) cmap_decode<RF, KSLOT>(r.w, ldict, m);
+    else {
+#pragma unroll
+      for (int v = 0; v < NV4; v++) { m[4 * v] = r.q[v].x; m[4 * v + 1] = r.q[v].y; m[4 * v + 2] = r.q[v].z; m[4 * v + 3] = r.q[v].w; }
+    }
+  };
+
+  float acc[RF];
+#pragma unroll
+  for (int k = 0; k < RF; k++) acc[k] = 0.f;
+  float known = 0.f;
+  // U samples per step: all addresses first, then all loads (map records + LDS scan records) in flight together, then
+  // the FMAs.  The order of the FMAs — direction i ascending, ring ascending within it — is the same in every
+  // instantiation and independent of U and of the launch: results are a pure function of the inputs.
+  auto step = [&](auto full_step, const unsigned (&boff)[U], const float4* const (&sp)[U], int cnt) {
+    constexpr bool FULL = decltype(full_step)::value;   // all U samples are real: no per-sample predicate
+    Raw raw[U];
+    float4 s[U][NV4];
+    if constexpr (SKIP) {
+      // the scan records first: a lane whose bin is empty in every class asks for the mask word instead of the record
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (FULL || u < cnt) {
+#pragma unroll
+          for (int v = 0; v < NV4; v++) s[u][v] = sp[u][v];
+        }
+      bool empty[U];
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (FULL || u < cnt) {
+          constexpr int ND = CmapShape<RF, KSLOT>::ND;
+          uint32_t any = 0;
+#pragma unroll
+          for (int k = 0; k < ND; k++) {
+            const float4 q = s[u][k / 4];
+            any |= __float_as_uint(k % 4 == 0 ? q.x : (k % 4 == 1 ? q.y : (k % 4 == 2 ? q.z : q.w)));
+          }
+          empty[u] = skip_ok && any == 0;
+          load_raw(empty[u] ? moff[u] : boff[u], raw[u]);
+        }
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (FULL || u < cnt) {
+          // an empty bin's "record": dictionary entry 0 for every distance, the known bit from the mask
+          const uint32_t kb = (raw[u].w[0] >> (mbit[u] & 31)) & 1u;
+#pragma unroll
+          for (int d = 0; d < CW; d++) raw[u].w[d] = empty[u] ? kb : raw[u].w[d];
+        }
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (FULL || u < cnt) load_raw(boff[u], raw[u]);
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (FULL || u < cnt) {
+#pragma unroll
+          for (int v = 0; v < NV4; v++) s[u][v] = sp[u][v];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++)
+      if (FULL || u < cnt) {
+        float m[RF];
+        operands(raw[u], m);
+#pragma unroll
+        for (int v = 0; v < NV4; v++) {
+          acc[4 * v + 0] = __builtin_fmaf(s[u][v].x, m[4 * v + 0], acc[4 * v + 0]);
+          acc[4 * v + 1] = __builtin_fmaf(s[u][v].y, m[4 * v + 1], acc[4 * v + 1]);
+          acc[4 * v + 2] = __builtin_fmaf(s[u][v].z, m[4 * v + 2], acc[4 * v + 2]);
+          acc[4 * v + 3] = __builtin_fmaf(s[u][v].w, m[4 * v + 3], acc[4 * v + 3]);
+        }
+        if (!KSLOT) known += m[RF - 1];
+      }
+  };
+  if (gn >= U) {
+    // ray-major: consecutive samples of a lane are consecutive cells along one ray
+    const int gfull = gn - gn % U;
+    for (int i = 0; i < nb; i++) {
+      int row = i + shift;
+      row -= row >= nb ? nb : 0;
+      const float4* const rl = ring + __mul24(row, rs);
+      for (int jj = 0; jj < gfull; jj += U) {
+        unsigned boff[U];
+        const float4* sp[U];
+        const float4* const rj = rl + jj * NV4;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          boff[u] = cell_offset(tab_at((int64_t)(j0 + jj + u) * nb + i), u);
+          sp[u] = rj + u * NV4;
+        }
+        step(std::true_type{}, boff, sp, U);
+      }
+    }
+    if (gfull < gn) {   // the group's last rings when gn is not a multiple of U: a pass of their own over the directions
+      for (int i = 0; i < nb; i++) {
+        int row = i + shift;
+        row -= row >= nb ? nb : 0;
+        const float4* const rl = ring + __mul24(row, rs);
+        unsigned boff[U];
+        const float4* sp[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          const int jc = min(gfull + u, gn - 1);
+          boff[u] = cell_offset(tab_at((int64_t)(j0 + jc) * nb + i), u);
+          sp[u] = rl + jc * NV4;
+        }
+        step(std::false_type{}, boff, sp, gn - gfull);
+      }
+    }
+  } else {
+    // fewer rings than loads to keep in flight (very long rows): U consecutive directions of one ring at a time
+    for (int jj = 0; jj < gn; jj++) {
+      const float4* const rj = ring + jj * NV4;
+      for (int i = 0; i < nb; i += U) {
+        unsigned boff[U];
+        const float4* sp[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          const int ic = min(i + u, nb - 1);
+          int row = ic + shift;
+          row -= row >= nb ? nb : 0;
+          boff[u] = cell_offset(tab_at((int64_t)(j0 + jj) * nb + ic), u);
+          sp[u] = rj + __mul24(row, rs);
+        }
+        step(std::false_type{}, boff, sp, min(U, nb - i));
+      }
+    }
+  }
+  if (sbase + slot < a.npad) {
+    float* o = a.part + (int64_t)by * (RF + 1) * a.npad + sbase + slot;
+#pragma unroll
+    for (int k = 0; k < RF; k++) o[(int64_t)k * a.npad] = acc[k];
+    o[(int64_t)RF * a.npad] = KSLOT ? acc[RF - 2] : known;
+  }
+#ifdef TDR_SCORE_TIMELINE
+  __syncthreads();
+  if (threadIdx.x == 0 && tl_id < TDR_TL_MAX) g_timeline[2 * tl_id + 1] = wall_clock64();
+#endif
+}
+// batched filters (tdr_batch_step): filter e owns the blocks [blk[e], blk[e + 1]) of grid.x and grid.y rows
+// [0, its nchunks); its ScoreArgs are args[e].  Filters whose USCALE differs from the instantiation's are another launch.
+__device__ __forceinline__ int batch_find(const int32_t* __restrict__ blk, int k, int b) {
+  int lo = 0, hi = k - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (blk[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+template <int NV4, int U, bool KSLOT, bool USCALE, bool COMPACT, bool WIDE = false>
+__global__ __launch_bounds__(256, COMPACT ? (WIDE ? 3 : 5) : 1) void score_polar_batch_kernel(const ScoreArgs* __restrict__ args,
+                                                                                              const int32_t* __restrict__ blk, int k) {
+  const int e = batch_find(blk, k, (int)blockIdx.x);
+  const ScoreArgs a = args[e];
+  if ((int)blockIdx.y >= a.nchunks || (a.utab != nullptr) != USCALE) return;   // (uniform)
+  score_polar_body<NV4, U, KSLOT, USCALE, COMPACT, WIDE, false>(a, blockIdx.x - (unsigned)blk[e], blockIdx.y);
 }
 
 // K2c: Cartesian scoring (BASELINE config 4).  The reference's StateParticle never reaches the Cartesian
@@ -702,6 +979,107 @@ __global__ __launch_bounds__(256) void score_finalize_kernel(FinalizeArgs a) {
     a.best_cost[slot] = best;
     a.best_theta[slot] = bt;
   }
+}
+// score_finalize_kernel's body for thread gid, for score_finalize_batch_kernel (a copy, like score_polar_body)
+__device__ __forceinline__ void score_finalize_body(const FinalizeArgs& a, const int64_t gid) {
+  const int T = 1 << a.tlog, t = (int)(gid & (T - 1));
+  const int64_t slot = gid >> a.tlog;
+  if (a.run_if && !int_form_off(a.run_if)) return;
+  const int64_t nact = a.count ? (int64_t)*a.count : a.n;
+  if (slot >= nact) return;
+  const int64_t p = a.order ? (int64_t)a.order[slot] : slot;
+  if (p < 0) return;   // a padding slot of the shift-uniform order (tdr_score_su.h)
+  const float scale = a.st[TDR_ST_SCALE * a.cap + p];
+  const float cx = a.st[TDR_ST_DX * a.cap + p] * scale + a.st[TDR_ST_INIT_X * a.cap + p];
+  const float cy = a.st[TDR_ST_DY * a.cap + p] * scale + a.st[TDR_ST_INIT_Y * a.cap + p];
+  if (a.mode == 0 && particle_gated(a.gate, cx, cy, scale)) {
+    a.raw_w[p] = 0.f;
+    return;
+  }
+  if (a.mode == 1 && a.only_uninit && a.st[TDR_ST_HAVE_INIT * a.cap + p] != 0.f) return;
+  // Per-chunk partial sums -> double totals, chunk order ascending.  The loads of FIN_B chunks x all slots are issued
+  // together (independent addresses, coalesced over the particles) before the dependent additions.  A small particle
+  // set has many chunks and few slots — 128 x 1000 at the reference's test size — and one lane per slot would wait for
+  // memory 32 times in a row: there 2^tlog neighbouring lanes take a contiguous share of a slot's chunks each and
+  // their double totals are added up in a fixed butterfly.
+  constexpr int FIN_B = 4, FIN_S = TDR_MAX_CLASSES + 2;   // slots: ncls class dots, normalisation, known count
+  double tot[FIN_S];
+#pragma unroll
+  for (int k = 0; k < FIN_S; k++) tot[k] = 0;
+  const int64_t cstride = (int64_t)(a.rf + 1) * a.npad;
+  auto slot_row = [&](int k) { return k < a.ncls ? k : (k == a.ncls ? a.rf - 1 : a.rf); };
+  const int share = (a.nchunks + T - 1) >> a.tlog, cend = min(a.nchunks, (t + 1) * share);
+  int c0 = t * share;
+  for (; c0 + FIN_B <= cend; c0 += FIN_B) {
+    float v[FIN_B][FIN_S];
+#pragma unroll
+    for (int b = 0; b < FIN_B; b++)
+#pragma unroll
+      for (int k = 0; k < FIN_S; k++)
+        if (k < a.ncls + 2) v[b][k] = a.part[(int64_t)(c0 + b) * cstride + (int64_t)slot_row(k) * a.npad + slot];
+#pragma unroll
+    for (int b = 0; b < FIN_B; b++)
+#pragma unroll
+      for (int k = 0; k < FIN_S; k++)
+        if (k < a.ncls + 2) tot[k] += (double)v[b][k];
+  }
+  for (; c0 < cend; c0++) {
+#pragma unroll
+    for (int k = 0; k < FIN_S; k++)
+      if (k < a.ncls + 2) tot[k] += (double)a.part[(int64_t)c0 * cstride + (int64_t)slot_row(k) * a.npad + slot];
+  }
+  if (T > 1) {   // (the lanes of a slot left or stayed together above)
+    for (int sft = T >> 1; sft >= 1; sft >>= 1)
+#pragma unroll
+      for (int k = 0; k < FIN_S; k++)
+        if (k < a.ncls + 2) tot[k] += __shfl_xor(tot[k], sft, 64);
+    if (t != 0) return;
+  }
+  double known = 0, norm = 0;
+#pragma unroll
+  for (int k = 0; k < FIN_S; k++) {
+    if (k == a.ncls) norm = tot[k];
+    if (k == a.ncls + 1) known = tot[k];
+  }
+  // known fraction gate (state_particle.cpp:117-120); counts are exact integers in float
+  float cost;
+  if ((float)known / (float)a.P < 0.5) {
+    cost = __builtin_nanf("");
+  } else {
+    cost = 0.f;
+#pragma unroll
+    for (int k = 0; k < TDR_MAX_CLASSES; k++)
+      if (k < a.ncls) cost = (float)((double)cost + (double)(float)tot[k] * 0.01 * (double)a.fp.class_weights[k]);  // :136-139
+    float normf = (float)norm;
+    if (a.gpart) {   // :145-152: cost += (geo_i . geo_cls_i) * 0.01; normalization += geo_i.sum()
+      double g[2] = {0, 0};
+      const int64_t gstride = (int64_t)5 * a.npad;
+      for (int c0g = 0; c0g < a.gnchunks; c0g++) {
+        g[0] += (double)a.gpart[(int64_t)c0g * gstride + slot];
+        g[1] += (double)a.gpart[(int64_t)c0g * gstride + a.npad + slot];
+      }
+      cost = (float)((double)cost + (double)(float)g[0] * 0.01);
+      normf = normf + a.gsum0;
+      cost = (float)((double)cost + (double)(float)g[1] * 0.01);
+      normf = normf + a.gsum1;
+    }
+    cost = cost / normf;  // :154
+  }
+  if (a.mode == 0) {
+    a.raw_w[p] = (float)(1. / (double)(cost + a.fp.regularization));  // :212
+  } else {
+    float best = a.first ? 3.402823466e+38f : a.best_cost[slot];
+    float bt = a.first ? 0.f : a.best_theta[slot];
+    if (cost < best) { best = cost; bt = a.theta_override; }  // :200-203 (NaN never wins)
+    a.best_cost[slot] = best;
+    a.best_theta[slot] = bt;
+  }
+}
+__global__ __launch_bounds__(256) void score_finalize_batch_kernel(const FinalizeArgs* __restrict__ args,
+                                                                   const int32_t* __restrict__ blk, int k) {
+  const int e = batch_find(blk, k, (int)blockIdx.x);
+  const FinalizeArgs a = args[e];
+  score_finalize_body(a, (int64_t)(blockIdx.x - (unsigned)blk[e]) * blockDim.x + threadIdx.x);
 }
 
 // The integer form of a launch (tdr_score_su.hip, tdr_score_ray.hip): a slot's chunk rows hold, per class, the 64-bit
@@ -2041,6 +2419,160 @@ struct TunerScope {
   }
 };
 
+// The launch's choice between the integer form (tdr_score_su.h) and the float kernel, taken on the host: one place for
+// tdr_k_score_polar_ctx and for the callers that must know which form a filter's launch takes (tdr_batch_step).
+static bool int_form_applies(const ScoreWs& W, const tdr_map_desc* map, int rf) {
+  return W.su && map_has_compact(map, rf) && !map_is_wide(map, rf) && tdr_ray_map_ok(map);
+}
+bool tdr_score_polar_float_form(const tdr_map_desc* map, int nb, int nr, int64_t n, int64_t n_total) {
+  const int rf = tdr_rec_floats(map->ncls);
+  return !int_form_applies(score_ws(map->ncls, nb, nr, n, n_total), map, rf);
+}
+// ---- batched filters (tdr_batch_step, tdr_batch.h): the float form of k filters' scoring launches as ONE grid ----------
+// Per filter exactly the ScoreArgs / FinalizeArgs tdr_k_score_polar_ctx builds for its float launch (same workspace
+// layout, ring groups from its own particle count, its own scan, res and sample offsets); the grid's x blocks are the
+// filters' particle blocks side by side, grid.y the largest chunk count.  No locality order (results never depend on it).
+namespace {
+struct BatchScoreHdr {
+  int32_t blocks, max_chunks, fin_blocks, n_uscale;
+  size_t lds;
+};
+struct UtabEntry {
+  float scale, res;
+  float* out;   // NULL: the filter reads each particle's own scale
+};
+struct BatchScoreLayout {
+  size_t args, fargs, blk, fblk, utab, total;
+};
+BatchScoreLayout batch_layout(int k) {
+  auto up = [](size_t x) { return (x + 63) / 64 * 64; };
+  BatchScoreLayout L;
+  L.args = up(sizeof(BatchScoreHdr));
+  L.fargs = L.args + up(sizeof(ScoreArgs) * k);
+  L.blk = L.fargs + up(sizeof(FinalizeArgs) * k);
+  L.fblk = L.blk + up(sizeof(int32_t) * k);
+  L.utab = L.fblk + up(sizeof(int32_t) * k);
+  L.total = L.utab + up(sizeof(UtabEntry) * k);
+  return L;
+}
+}  // namespace
+__global__ void utab_batch_kernel(const float* __restrict__ tab, int64_t n2, const UtabEntry* __restrict__ ut) {
+  const UtabEntry e = ut[blockIdx.y];
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e.out && k < n2) e.out[k] = (tab[k] * e.scale) * e.res;  // utab_kernel's expression
+}
+size_t tdr_batch_score_stage_bytes(int k) { return k < 1 ? 0 : batch_layout(k).total; }
+int tdr_batch_score_build(const tdr_map_desc* map, const float* tab, int nb, int nr, int k, const TdrBatchScoreIn* in,
+                          void* host_stage) {
+  if (!map || !tab || !in || !host_stage || k < 1 || nb < 1 || nr < 1) return fail(TDR_ERR_ARG, "batch_score: bad arguments");
+  const int rf = tdr_rec_floats(map->ncls);
+  if (map->rec_floats != rf) return fail(TDR_ERR_ARG, "batch_score: map record size %d != %d", map->rec_floats, rf);
+  if ((size_t)2 * nb * rf * 4 > 64 * 1024) return fail(TDR_ERR_ARG, "batch_score: nb too large for the LDS scan ring");
+  if (int rc0 = check_map_addressing(map, rf, "batch_score")) return rc0;
+  const BatchScoreLayout Lo = batch_layout(k);
+  char* base = static_cast<char*>(host_stage);
+  BatchScoreHdr& h = *reinterpret_cast<BatchScoreHdr*>(base);
+  ScoreArgs* args = reinterpret_cast<ScoreArgs*>(base + Lo.args);
+  FinalizeArgs* fargs = reinterpret_cast<FinalizeArgs*>(base + Lo.fargs);
+  int32_t* blk = reinterpret_cast<int32_t*>(base + Lo.blk);
+  int32_t* fblk = reinterpret_cast<int32_t*>(base + Lo.fblk);
+  UtabEntry* ut = reinterpret_cast<UtabEntry*>(base + Lo.utab);
+  const bool cm = map_has_compact(map, rf), wide = cm && map_is_wide(map, rf);
+  const int lc = map->cwords == 1 ? 3 : (map->cwords == 2 ? 2 : 1);
+  h = BatchScoreHdr{};
+  for (int i = 0; i < k; i++) {
+    const TdrBatchScoreIn& x = in[i];
+    if (x.n < 1 || x.cap < x.n || !x.fp || x.fp->num_classes != map->ncls) return fail(TDR_ERR_ARG, "batch_score: filter %d", i);
+    const ScoreWs W = score_ws(map->ncls, nb, nr, x.n, x.n);
+    if (int_form_applies(W, map, rf)) return fail(TDR_ERR_ARG, "batch_score: filter %d takes the integer form", i);
+    ScoreArgs a{};
+    a.rec = map->rec; a.rows = map->rows; a.cols = map->cols; a.resolution = map->resolution;
+    a.tab = tab; a.scan_pk = x.scan_pk; a.nb = nb; a.nr = nr; a.res = x.res;
+    a.st = x.st; a.cap = x.cap; a.n = x.n; a.order = nullptr; a.count = nullptr; a.slot_base = nullptr; a.kmask_off = 0;
+    a.kmask_row = 0; a.use_theta_override = 0; a.theta_override = 0.f; a.only_uninit = 0;
+    a.group = W.group; a.nchunks = W.nchunks; a.npad = W.npad; a.part = x.ws; a.run_if = nullptr;
+    a.utab = x.uniform_scale > 0.f ? x.ws + W.off_utab : nullptr;   // fill_utab's place
+    ut[i] = UtabEntry{x.uniform_scale, x.res, const_cast<float*>(a.utab)};
+    a.crec = nullptr; a.dict = nullptr; a.dict_n = 0; a.ctiles_r = 0;
+    if (cm) { a.crec = map->crec; a.dict = map->dict; a.dict_n = map->dict_n; a.ctiles_r = (map->rows >> lc) + 2; }
+    args[i] = a;
+    const size_t lds = wide ? (size_t)nb * ((a.group * 2) | 1) * 16 : (size_t)nb * ((a.group * (rf / 4)) | 1) * 16;
+    h.lds = std::max(h.lds, lds);
+    blk[i] = h.blocks;
+    h.blocks += (int32_t)cdiv(x.n, 256);
+    h.max_chunks = std::max(h.max_chunks, a.nchunks);
+    h.n_uscale += a.utab ? 1 : 0;
+    FinalizeArgs f{};
+    f.part = a.part; f.rf = rf; f.nchunks = a.nchunks; f.npad = a.npad; f.n = x.n; f.cap = x.cap;
+    f.order = nullptr; f.count = nullptr; f.st = x.st; f.fp = *x.fp;
+    f.gate = make_gate(x.fp, map);
+    f.P = (int64_t)nb * nr; f.ncls = map->ncls; f.mode = 0; f.first = 0; f.theta_override = 0.f;
+    f.raw_w = x.raw_w; f.best_cost = nullptr; f.best_theta = nullptr;
+    f.gpart = nullptr; f.gnchunks = 0; f.gsum0 = f.gsum1 = 0.f; f.only_uninit = 0; f.run_if = nullptr;
+    int tl = 0;   // launch_finalize's choice for this filter
+    while (tl < 4 && (f.nchunks >> (tl + 1)) >= 4 && (x.n << (tl + 1)) <= 131072) tl++;
+    f.tlog = tl;
+    fargs[i] = f;
+    fblk[i] = h.fin_blocks;
+    h.fin_blocks += (int32_t)cdiv(x.n << tl, 256);
+  }
+  return TDR_OK;
+}
+template <int NV4, bool KS, bool US, bool CM, bool WIDE>
+static void launch_batch_score(dim3 grid, size_t lds, hipStream_t s, const ScoreArgs* args, const int32_t* blk, int k) {
+  auto kfn = score_polar_batch_kernel<NV4, TDR_SCORE_U, KS, US, CM, WIDE>;
+  if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kfn, grid, dim3(256), lds, s, args, blk, k);
+}
+template <bool US>
+static int launch_batch_score_form(const tdr_map_desc* map, int rf, dim3 grid, size_t lds, hipStream_t s,
+                                   const ScoreArgs* args, const int32_t* blk, int k) {
+  const bool ks = tdr_has_kslot(map->ncls, rf), cm = map_has_compact(map, rf);
+  if (cm && map_is_wide(map, rf)) {
+    if (ks) launch_batch_score<2, true, US, true, true>(grid, lds, s, args, blk, k);
+    else launch_batch_score<2, false, US, true, true>(grid, lds, s, args, blk, k);
+    return TDR_OK;
+  }
+#define TDR_BATCH_SCORE(NV4, CM)                                                   \
+  if (ks) launch_batch_score<NV4, true, US, CM, false>(grid, lds, s, args, blk, k); \
+  else launch_batch_score<NV4, false, US, CM, false>(grid, lds, s, args, blk, k);
+  switch (rf / 4) {
+    case 1: if (cm) { TDR_BATCH_SCORE(1, true) } else { TDR_BATCH_SCORE(1, false) } break;
+    case 2: if (cm) { TDR_BATCH_SCORE(2, true) } else { TDR_BATCH_SCORE(2, false) } break;
+    case 3: if (cm) { TDR_BATCH_SCORE(3, true) } else { TDR_BATCH_SCORE(3, false) } break;
+    case 4: TDR_BATCH_SCORE(4, false) break;   // 12-15 classes have no compact form
+    default: return fail(TDR_ERR_ARG, "batch_score: unsupported record size %d", rf);
+  }
+#undef TDR_BATCH_SCORE
+  return TDR_OK;
+}
+int tdr_batch_score_launch(const tdr_map_desc* map, const float* tab, int nb, int nr, int k, const void* host_stage,
+                           const void* dev_stage, hipStream_t s) {
+  if (!map || !tab || !host_stage || !dev_stage || k < 1) return fail(TDR_ERR_ARG, "batch_score: bad arguments");
+  const BatchScoreLayout Lo = batch_layout(k);
+  const BatchScoreHdr& h = *static_cast<const BatchScoreHdr*>(host_stage);
+  const char* d = static_cast<const char*>(dev_stage);
+  const ScoreArgs* args = reinterpret_cast<const ScoreArgs*>(d + Lo.args);
+  const FinalizeArgs* fargs = reinterpret_cast<const FinalizeArgs*>(d + Lo.fargs);
+  const int32_t* blk = reinterpret_cast<const int32_t*>(d + Lo.blk);
+  const int32_t* fblk = reinterpret_cast<const int32_t*>(d + Lo.fblk);
+  const UtabEntry* ut = reinterpret_cast<const UtabEntry*>(d + Lo.utab);
+  const int rf = tdr_rec_floats(map->ncls);
+  if (h.n_uscale > 0) {
+    const int64_t n2 = 2 * (int64_t)nb * nr;
+    hipLaunchKernelGGL(utab_batch_kernel, dim3((unsigned)cdiv(n2, 256), (unsigned)k), dim3(256), 0, s, tab, n2, ut);
+    LAUNCH_CHECK("batch_utab");
+  }
+  const dim3 grid((unsigned)h.blocks, (unsigned)h.max_chunks);
+  if (h.n_uscale > 0)
+    if (int rc = launch_batch_score_form<true>(map, rf, grid, h.lds, s, args, blk, k)) return rc;
+  if (h.n_uscale < k)
+    if (int rc = launch_batch_score_form<false>(map, rf, grid, h.lds, s, args, blk, k)) return rc;
+  LAUNCH_CHECK("batch_score_polar");
+  hipLaunchKernelGGL(score_finalize_batch_kernel, dim3((unsigned)h.fin_blocks), dim3(256), 0, s, fargs, fblk, k);
+  LAUNCH_CHECK("batch_score_finalize");
+  return TDR_OK;
+}
 extern "C" int tdr_k_score_polar(const tdr_map_desc* map, const float* tab, const float* scan_pk, int nb, int nr,
                                  float res, const tdr_filter_params* fp, float* st, int64_t cap, int64_t n,
                                  int64_t n_total, const int32_t* perm, float uniform_scale, int init_search,
@@ -2188,7 +2720,7 @@ extern "C" int tdr_k_score_polar_ctx(const tdr_map_desc* map, const float* tab, 
   f.P = (int64_t)nb * nr; f.ncls = map->ncls; f.mode = 0; f.first = 0; f.theta_override = 0.f;
   f.raw_w = raw_w; f.best_cost = nullptr; f.best_theta = nullptr;
   f.gpart = nullptr; f.gnchunks = 0; f.gsum0 = f.gsum1 = 0.f; f.only_uninit = 0;
-  if (W.su && map_has_compact(map, rf) && !map_is_wide(map, rf) && tdr_ray_map_ok(map)) {
+  if (int_form_applies(W, map, rf)) {
     // The INTEGER form of the launch (tdr_score_su.h): dense particles by heading bin through the shift-uniform kernel,
     // scattered ones — behind the bins in the same slot list — one wave each through the ray-mapped kernel; both form exact
     // integer sums, so a particle's weight does not depend on which of the two scored it.  A scan or a map without
