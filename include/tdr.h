@@ -832,6 +832,39 @@ typedef struct tdr_batch_input {
 int tdr_batch_step(tdr_filter* const* filters, int k, const tdr_batch_input* in, void* stream);
 int tdr_batch_last_stats(int* batched, int* standalone);
 
+/* ---- batched node loop: the render and the pose statistics of many robots at once (csrc/tdr_batch_loop.hip) ------------
+ * tdr_batch_render_polar = for every i: tdr_renderer_render(r[i], 1, clouds[i].pts, clouds[i].stride, clouds[i].ioff,
+ * clouds[i].n, clouds[i].res, ang_res, ncls, nb, nr, NULL) — each renderer ends holding the same bits on the device
+ * (have_scan, shape), ready as a tdr_batch_step / tdr_filter_update input — with one upload of all clouds (staged in a
+ * per-thread pinned buffer) and one keys launch + one raster launch on `stream` (shapes the standalone raster bins
+ * without keys take its launch per renderer).  No host wait: readers of a renderer's previous render and readers of this
+ * one are ordered with events.  Refused with TDR_ERR_ARG before any device work: k < 1, a null array or renderer, a
+ * renderer twice, a cloud with n < 0 or n > 0 and null pts, stride < 3, ioff outside [0, stride), res <= 0, ang_res <= 0,
+ * a shape outside 1..TDR_MAX_CLASSES x >= 1 x >= 1, ncls * nb * 4 > 152 KB.  pts: HOST.
+ * tdr_renderer_get_render: HOST copies of the last render ([ncls][rows*cols] column-major images and the packed records,
+ * [rows*cols][tdr_rec_floats(ncls)]); either pointer may be NULL; TDR_ERR_ARG without a render.
+ * tdr_batch_pose = for every i: tdr_filter_mean_cov(f[i], 0, mean, cov) and tdr_filter_scale(f[i]), bit for bit, with one
+ * launch set for all filters on `stream` (after each filter's own stream), one device-to-host copy and one wait; it
+ * fills each filter's mean / covariance cache, so a following tdr_filter_mean_cov(f, 0, ...) / tdr_filter_scale does no
+ * device work.  n = 0 gives zeros; sharded filters make their standalone calls inside.  Refused with TDR_ERR_ARG before
+ * any device work: k < 1, a null array or filter, a filter twice, filters on different maps. */
+typedef struct tdr_batch_cloud {
+  const float* pts;
+  int stride, ioff;
+  int64_t n;
+  float res;
+} tdr_batch_cloud;
+int tdr_batch_render_polar(tdr_renderer* const* r, int k, const tdr_batch_cloud* clouds, float ang_res, int ncls, int nb,
+                           int nr, void* stream);
+int tdr_renderer_get_render(const tdr_renderer* r, float* imgs_out, float* pk_out);
+typedef struct tdr_pose_stats {
+  float mean[4];
+  float cov[16];
+  float scale;
+  int64_t n;
+} tdr_pose_stats;
+int tdr_batch_pose(tdr_filter* const* f, int k, tdr_pose_stats* out, void* stream);
+
 /* internal: lets tdr_host.cpp report through tdr_last_error() */
 int tdr_set_error(int code, const char* msg);
 

@@ -37,6 +37,7 @@ class ScanRenderer {
     render_geo(0, cloud, res, 1.f, imgs);
   }
   const tdr_renderer* handle() const { return r_; }  // device-resident last render, for ParticleFilter::update
+  tdr_renderer* handle() { return r_; }              // ... and the target of a batched render (tdr_batch_render_polar)
 
  protected:
   void render(int polar, const pcl::PointCloud<pcl::PointXYZI>::ConstPtr& cloud, float res, float ang_res,

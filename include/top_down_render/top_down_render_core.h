@@ -139,6 +139,7 @@ class TopDownRenderCore {
   void setDeviceScan(bool on) { device_scan_ = on; }
 
  private:
+  friend class TopDownRenderCoreBatch;   // steps many cores at once (top_down_render_core_batch.h)
   void finishInit(FilterParams& filter_params, const Eigen::VectorXi& flatten_lut) {
     map_->samplePtsPolar(Eigen::Vector2i(cfg_.theta_bins, cfg_.range_bins), (float)(2 * M_PI / cfg_.theta_bins));   // :115
     filter_ = new ParticleFilter(cfg_.particle_count, map_, filter_params, cfg_.seed);                              // :116

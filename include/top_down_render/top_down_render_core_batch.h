@@ -1,0 +1,97 @@
+// top_down_render_core_batch.h — the node's per-scan loop (TopDownRenderCore::takeStep, top_down_render_core.h) for many
+// robots on one map at once (extension; the reference runs one loop per node):
+//
+//   1. render every core's cloud at that core's current_range_scale_ into the core's own renderer: tdr_batch_render_polar
+//   2. ParticleFilterBatch::step with the renders as inputs and the priors {trans, yaw}: tdr_batch_step
+//   3. the pose statistics of all filters, one read-back: tdr_batch_pose (fills every filter's mean / covariance / scale
+//      cache)
+//   4. every core's own publishPoseEst() — it reads the cache, so it makes no device call except in the step in which a
+//      filter's scale freezes
+//
+// Every core ends where cores[i]->takeStep(...) with setDeviceScan(true) leaves it: filter states, weights and generator
+// position, PoseEst, currentRangeScale, lastRes, isConverged.  One difference: the host topDown() images are not filled
+// (the renders stay on the device; ScanRenderer::handle + tdr_renderer_get_render reads them).
+#pragma once
+
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "top_down_render/particle_filter_batch.h"
+#include "top_down_render/top_down_render_core.h"
+
+class TopDownRenderCoreBatch {
+ public:
+  // cores: on one map, with one (theta_bins, range_bins); clouds / trans / yaw: one per core.  stream: a hipStream_t
+  // (nullptr = the default stream).  Returns false when the map holds no map yet (nothing moves, like takeStep); throws
+  // before anything moves on a batch that does not fit, and on a refused call.
+  bool takeStep(const std::vector<TopDownRenderCore*>& cores, const std::vector<pcl::PointCloud<PointType>::ConstPtr>& clouds,
+                const std::vector<Eigen::Vector2f>& trans, const std::vector<float>& yaw,
+                std::vector<TopDownRenderCore::PoseEst>* ests = nullptr, void* stream = nullptr) {
+    const size_t k = cores.size();
+    if (k < 1) throw std::invalid_argument("TopDownRenderCoreBatch::takeStep: no core");
+    if (clouds.size() != k || trans.size() != k || yaw.size() != k)
+      throw std::invalid_argument("TopDownRenderCoreBatch::takeStep: one cloud, translation and yaw per core");
+    for (size_t i = 0; i < k; i++) {
+      const TopDownRenderCore* c = cores[i];
+      if (!c || !c->map_ || !c->filter_ || !c->renderer_)
+        throw std::invalid_argument("TopDownRenderCoreBatch::takeStep: core " + std::to_string(i) + " is null or not initialised");
+      if (c->cfg_.theta_bins != cores[0]->cfg_.theta_bins || c->cfg_.range_bins != cores[0]->cfg_.range_bins)
+        throw std::invalid_argument("TopDownRenderCoreBatch::takeStep: core " + std::to_string(i) + " has " +
+                                    std::to_string(c->cfg_.theta_bins) + " x " + std::to_string(c->cfg_.range_bins) +
+                                    " bins, core 0 " + std::to_string(cores[0]->cfg_.theta_bins) + " x " +
+                                    std::to_string(cores[0]->cfg_.range_bins));
+      if (c->map_ != cores[0]->map_)
+        throw std::invalid_argument("TopDownRenderCoreBatch::takeStep: core " + std::to_string(i) + " is on another map than core 0");
+    }
+    TopDownMapPolar* map = cores[0]->map_;
+    if (!map->haveMap()) return false;                                                      // :508-511
+    const int nb = cores[0]->cfg_.theta_bins, nr = cores[0]->cfg_.range_bins;
+    const float ang_res = (float)(2 * M_PI / nb);
+
+    std::vector<tdr_renderer*> rs(k);
+    std::vector<tdr_batch_cloud> cl(k);
+    std::vector<ParticleFilter*> filters(k);
+    std::vector<const ScanRenderer*> renderers(k);
+    std::vector<float> res(k);
+    std::vector<MotionPrior> priors(k);
+    for (size_t i = 0; i < k; i++) {
+      TopDownRenderCore* c = cores[i];
+      const pcl::PointCloud<PointType>::ConstPtr& cloud = clouds[i];
+      rs[i] = c->renderer_->handle();
+      cl[i] = tdr_batch_cloud{};
+      cl[i].pts = cloud && !cloud->points.empty() ? reinterpret_cast<const float*>(cloud->points.data()) : nullptr;
+      cl[i].n = cloud ? (int64_t)cloud->points.size() : 0;
+      cl[i].stride = 8;   // pcl::PointXYZI: x y z pad intensity pad pad pad (as ScanRenderer::render)
+      cl[i].ioff = 4;
+      cl[i].res = c->current_range_scale_;                                                  // :539
+      filters[i] = c->filter_;
+      renderers[i] = c->renderer_;
+      res[i] = c->current_range_scale_;
+      priors[i].tx = trans[i][0];
+      priors[i].ty = trans[i][1];
+      priors[i].omega = yaw[i];
+    }
+    if (tdr_batch_render_polar(rs.data(), (int)k, cl.data(), ang_res, map->numClasses(), nb, nr, stream) != TDR_OK)
+      throw std::runtime_error(std::string("TopDownRenderCoreBatch::takeStep: ") + tdr_last_error());
+    batch_.step(filters, std::vector<std::vector<Eigen::ArrayXXf>>(k), res, priors, renderers, stream);   // :559
+    std::vector<tdr_filter*> handles(k);
+    for (size_t i = 0; i < k; i++) handles[i] = filters[i]->handle();
+    std::vector<tdr_pose_stats> stats(k);
+    if (tdr_batch_pose(handles.data(), (int)k, stats.data(), stream) != TDR_OK)
+      throw std::runtime_error(std::string("TopDownRenderCoreBatch::takeStep: ") + tdr_last_error());
+    if (ests) ests->resize(k);
+    for (size_t i = 0; i < k; i++) {
+      cores[i]->last_res_ = res[i];
+      TopDownRenderCore::PoseEst e = cores[i]->publishPoseEst();                           // :560
+      if (ests) (*ests)[i] = e;
+    }
+    return true;
+  }
+  // filters of the last step that took the batched path / their standalone calls (ParticleFilterBatch)
+  int lastBatched() const { return batch_.lastBatched(); }
+  int lastStandalone() const { return batch_.lastStandalone(); }
+
+ private:
+  ParticleFilterBatch batch_;
+};

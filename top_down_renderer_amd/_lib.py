@@ -37,6 +37,16 @@ class BatchInputC(C.Structure):
                 ("ty", C.c_float), ("omega", C.c_float), ("n_target", C.c_int64)]
 
 
+class BatchCloudC(C.Structure):
+    """tdr_batch_cloud: one renderer's cloud in a tdr_batch_render_polar."""
+    _fields_ = [("pts", C.c_void_p), ("stride", C.c_int), ("ioff", C.c_int), ("n", C.c_int64), ("res", C.c_float)]
+
+
+class PoseStatsC(C.Structure):
+    """tdr_pose_stats: one filter's result of a tdr_batch_pose."""
+    _fields_ = [("mean", C.c_float * 4), ("cov", C.c_float * 16), ("scale", C.c_float), ("n", C.c_int64)]
+
+
 # name -> (restype, argtypes); every symbol include/tdr.h declares
 _vp, _i, _i64, _f, _u64, _u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_uint32
 SIGNATURES = {
@@ -226,6 +236,9 @@ SIGNATURES = {
     "tdr_filter_update_map": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _i]),
     "tdr_batch_step": (_i, [_vp, _i, _vp, _vp]),
     "tdr_batch_last_stats": (_i, [_vp, _vp]),
+    "tdr_batch_render_polar": (_i, [_vp, _i, _vp, _f, _i, _i, _i, _vp]),
+    "tdr_renderer_get_render": (_i, [_vp, _vp, _vp]),
+    "tdr_batch_pose": (_i, [_vp, _i, _vp, _vp]),
     "tdr_set_error": (_i, [_i, C.c_char_p]),
     "tdr_locality_tmp_ints": (C.c_size_t, [_i64, _i, _i]),
     "tdr_locality_pose_tmp_ints": (C.c_size_t, [_i64]),

@@ -5,13 +5,18 @@ others.  Each filter ends bit for bit where tdr_filter_propagate + tdr_filter_up
     m = MapHandle(class_maps, class_mask, resolution=1.0); m.sample_pts_polar(100, 25, ang_res)
     fs = [FilterHandle(m, 20000, params, seed=s) for s in seeds]   # set_states / initialize_particles
     step_batch(fs, scans, res, priors)                              # scans[k]: (ncls, nb, nr) array, or a Renderer
+
+The node loop of many robots (tdr_batch_render_polar + tdr_batch_step + tdr_batch_pose):
+
+    loop = LoopBatch(filters, renderers, cfgs, ang_res, ncls, nb, nr)
+    ests = loop.take_step(clouds, priors)       # one PoseEst per robot, as TopDownRenderCore.takeStep returns it
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from ._lib import BatchInputC, FilterParamsC, check
+from ._lib import BatchCloudC, BatchInputC, FilterParamsC, PoseStatsC, check
 
 _vp = C.c_void_p
 STATE_DTYPE = np.dtype([("init_x_px", "<f4"), ("init_y_px", "<f4"), ("dx_m", "<f4"), ("dy_m", "<f4"), ("theta", "<f4"),
@@ -54,12 +59,26 @@ class Renderer:
         self.h = _vp()
         self._lut = np.ascontiguousarray(lut256, np.int32)
         check(self.L.tdr_renderer_create(_ptr(self._lut), C.byref(self.h)))
+        self._shape = None
 
     def render_polar(self, pts, stride, ioff, res, ang_res, ncls, nb, nr):
         """pts: points of `stride` floats, x y z at 0..2, the label at float `ioff`."""
         pts = np.ascontiguousarray(pts, np.float32)
+        self._shape = (ncls, nb, nr)
         check(self.L.tdr_renderer_render(self.h, 1, _ptr(pts), stride, ioff, pts.size // stride, C.c_float(res),
                                          C.c_float(ang_res), ncls, nb, nr, None))
+
+    def get_render(self):
+        """(img, pk) of the last render: img (ncls, rows, cols) as renderSemanticTopDown fills it, pk (rows * cols, rf) the
+        packed records the scoring reads (record t = row + rows * col)."""
+        shape = self._shape
+        if shape is None:
+            raise _lib.TdrError("get_render: the renderer has no render")
+        ncls, nb, nr = shape
+        img = np.zeros((ncls, nr, nb), np.float32)
+        pk = np.zeros((nb * nr, self.L.tdr_rec_floats(ncls)), np.float32)
+        check(self.L.tdr_renderer_get_render(self.h, _ptr(img), _ptr(pk)))
+        return np.ascontiguousarray(np.transpose(img, (0, 2, 1))), pk
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -112,6 +131,15 @@ class FilterHandle:
         st, cov = np.zeros(4, np.float32), np.zeros(16, np.float32)
         check(self.L.tdr_filter_mean_cov(self.h, int(bool(about_max)), _ptr(st), _ptr(cov)))
         return st, cov.reshape(4, 4)
+
+    def freeze_scale(self):
+        check(self.L.tdr_filter_freeze_scale(self.h))
+
+    def is_scale_frozen(self):
+        return bool(self.L.tdr_filter_is_scale_frozen(self.h))
+
+    def scale(self):
+        return float(self.L.tdr_filter_scale(self.h))
 
     def propagate(self, tx, ty, omega):
         check(self.L.tdr_filter_propagate(self.h, C.c_float(tx), C.c_float(ty), C.c_float(omega)))
@@ -170,3 +198,106 @@ def last_stats():
     a, b = C.c_int(), C.c_int()
     check(L.tdr_batch_last_stats(C.byref(a), C.byref(b)))
     return a.value, b.value
+
+
+def render_batch(renderers, clouds, res, ang_res, ncls, nb, nr, stream=None):
+    """Renderer.render_polar of every renderer in one tdr_batch_render_polar: clouds[k] = (pts, stride, ioff) with pts an
+    (n, stride) float32 array (n may be 0); res: a float or one per renderer.  The renders stay on the device."""
+    L = _lib.load()
+    k = len(renderers)
+    if len(clouds) != k:
+        raise ValueError("render_batch: one cloud per renderer")
+    resv = list(res) if np.ndim(res) else [float(res)] * k
+    arr = (_vp * max(k, 1))(*[r.h for r in renderers])
+    cs = (BatchCloudC * max(k, 1))()
+    keep = []
+    for i, (pts, stride, ioff) in enumerate(clouds):
+        pts = np.ascontiguousarray(pts, np.float32)
+        keep.append(pts)
+        cs[i].pts = pts.ctypes.data if pts.size else None
+        cs[i].stride, cs[i].ioff, cs[i].n, cs[i].res = int(stride), int(ioff), pts.size // int(stride), float(resv[i])
+    check(L.tdr_batch_render_polar(arr, k, cs, C.c_float(ang_res), int(ncls), int(nb), int(nr),
+                                   _vp(stream) if stream else None))
+    for r in renderers:
+        r._shape = (int(ncls), int(nb), int(nr))
+
+
+def pose_batch(filters, stream=None):
+    """FilterHandle.mean_cov() + scale() of every filter in one tdr_batch_pose: (mean[k, 4], cov[k, 4, 4], scale[k], n[k])."""
+    L = _lib.load()
+    k = len(filters)
+    arr = (_vp * max(k, 1))(*[f.h for f in filters])
+    out = (PoseStatsC * max(k, 1))()
+    check(L.tdr_batch_pose(arr, k, out, _vp(stream) if stream else None))
+    mean = np.array([list(o.mean) for o in out[:k]], np.float32).reshape(k, 4)
+    cov = np.array([list(o.cov) for o in out[:k]], np.float32).reshape(k, 4, 4)
+    return mean, cov, np.array([o.scale for o in out[:k]], np.float32), np.array([o.n for o in out[:k]], np.int64)
+
+
+class _PoseView:
+    """What TopDownRenderCore.publishPoseEst asks of its filter, answered from one robot's share of a pose_batch; a
+    freezeScale goes to the filter, and the scale is read from it again afterwards (the freeze changes it)."""
+
+    def __init__(self, handle, mean, cov, scale, n):
+        self.h, self.mean, self.cov, self.scale_, self.n, self.froze = handle, mean, cov, scale, n, False
+
+    def computeMeanCov(self):
+        return self.cov
+
+    def meanLikelihood(self):
+        return self.mean
+
+    def scale(self):
+        return self.h.scale() if self.froze else self.scale_
+
+    def numParticles(self):
+        return int(self.n)
+
+    def isScaleFrozen(self):
+        return self.h.is_scale_frozen()
+
+    def freezeScale(self):
+        self.h.freeze_scale()
+        self.froze = True
+
+
+class HandleView(_PoseView):
+    """The same questions asked of a FilterHandle directly (the standalone form of one robot's loop)."""
+
+    def __init__(self, handle):
+        st, cov = handle.mean_cov()
+        super().__init__(handle, st, cov, handle.scale(), handle.num_particles())
+
+
+class LoopBatch:
+    """The node's per-scan loop (TopDownRenderCore.takeStep: render at the robot's range scale, propagate + update,
+    publishPoseEst) for many robots on one map: tdr_batch_render_polar, tdr_batch_step, tdr_batch_pose, then each robot's
+    own TopDownRenderCore.publishPoseEst over the read-back statistics — the range-scale, freeze and convergence rules
+    are that method's.  filters: FilterHandles on one map; renderers: one Renderer per robot; cfgs: one CoreConfig per
+    robot (or one for all)."""
+
+    def __init__(self, filters, renderers, cfgs, ang_res, ncls, nb, nr):
+        from .top_down_render_core import CoreConfig, TopDownRenderCore
+        k = len(filters)
+        if len(renderers) != k:
+            raise ValueError("LoopBatch: one renderer per filter")
+        cfgs = list(cfgs) if isinstance(cfgs, (list, tuple)) else [cfgs or CoreConfig()] * k
+        self.filters, self.renderers = list(filters), list(renderers)
+        self.cores = [TopDownRenderCore(c) for c in cfgs]
+        self.ang_res, self.ncls, self.nb, self.nr = float(ang_res), int(ncls), int(nb), int(nr)
+        self.stats = (0, 0)
+
+    def take_step(self, clouds, priors, n_targets=None, stream=None):
+        """clouds[k] = (pts, stride, ioff); priors[k] = (tx, ty, yaw).  Returns one PoseEst per robot."""
+        res = [np.float32(c.current_range_scale_) for c in self.cores]
+        for c, r in zip(self.cores, res):
+            c.last_res_ = r
+        render_batch(self.renderers, clouds, [float(r) for r in res], self.ang_res, self.ncls, self.nb, self.nr, stream)
+        self.stats = step_batch(self.filters, self.renderers, [float(r) for r in res], priors, n_targets, stream)
+        mean, cov, scale, n = pose_batch(self.filters, stream)
+        out = []
+        for i, (c, f) in enumerate(zip(self.cores, self.filters)):
+            c.filter_ = _PoseView(f, mean[i], cov[i], float(scale[i]), n[i])
+            out.append(c.publishPoseEst())
+            c.filter_ = None
+        return out

@@ -61,4 +61,38 @@ int tdr_batch_score_build(const tdr_map_desc* map, const float* tab, int nb, int
 int tdr_batch_score_launch(const tdr_map_desc* map, const float* tab, int nb, int nr, int k, const void* host_stage,
                            const void* dev_stage, hipStream_t s);
 
+// ---- the two ends of a batched node loop (tdr_batch_loop.hip): tdr_batch_render_polar and tdr_batch_pose ---------------
+// raster: one entry per cloud; entry k owns the blocks [blk_keys, next entry's blk_keys) of the keys launch and row
+// blockIdx.y == k of the raster launch.  pts / keys live in the batch's own device buffer, img / pk are the renderer's.
+struct TdrBatchRasterEntry {
+  const float* pts;
+  const int32_t* lut;     // the renderer's LUT (256 entries)
+  uint32_t* keys;         // [n] bin keys
+  float* img;             // [ncls][rows*cols]
+  float* pk;              // [rows*cols][rf]
+  int64_t n;
+  float res;
+  int32_t stride, ioff;
+  int32_t blk_keys;
+};
+struct TdrBatchRasterShape { float ang_res; int ncls, rows, cols, rf, cpt; };
+#define TDR_BATCH_RASTER_KEY_MAX_COLS 4095    // RASTER_KEY_MAX_COLS (tdr_raster.hip)
+#define TDR_BATCH_RASTER_KEY_MAX_ROWS 65535   // RASTER_KEY_MAX_ROWS
+bool tdr_batch_raster_shape(int ncls, int rows, int cols, float ang_res, TdrBatchRasterShape* out);
+int tdr_batch_raster(const TdrBatchRasterEntry* tab, int k, int blocks_keys, const TdrBatchRasterShape& a, hipStream_t s);
+
+// pose statistics: one entry per filter with n >= 1; `out` is the filter's TDR_BATCH_POSE_FLOATS-float result record
+// ([0, 24) as tdr_k_mean_cov writes them, [24] the scale of particle 0), `scratch` the filter's stats buffer + 24 (the
+// partial sums of the multi-workgroup form).  small: n <= TDR_BATCH_MC_SINGLE_MAX_N (one workgroup each), big: the rest.
+struct TdrBatchPoseEntry {
+  const float* st;
+  int64_t cap, n;
+  float* out;
+  float* scratch;
+};
+#define TDR_BATCH_POSE_FLOATS 32
+#define TDR_BATCH_MC_SINGLE_MAX_N 4096        // MC_SINGLE_MAX_N (tdr_filter.hip)
+int tdr_batch_pose_launch(const TdrBatchPoseEntry* small, int k_small, const TdrBatchPoseEntry* big, int k_big,
+                          hipStream_t s);
+
 #endif  // TDR_BATCH_H_

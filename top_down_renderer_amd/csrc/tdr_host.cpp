@@ -107,6 +107,17 @@ struct tdr_renderer {
   DevBuf<uint8_t> geo_ws;  // sort keys / scratch of the geometric render
   int ncls = 0, rows = 0, cols = 0;  // shape of the last render
   bool have_scan = false;
+  // tdr_batch_render_polar renders on the caller's stream without a host wait: `rendered` marks the end of that render
+  // (render_async), and every stream that has since read img / pk leaves an event in `readers` for the next batched
+  // render to wait on (one per stream: a later record on the same stream covers the earlier reads)
+  hipEvent_t rendered = nullptr;
+  bool render_async = false;
+  mutable std::vector<std::pair<hipStream_t, hipEvent_t>> readers;
+  mutable size_t n_readers = 0;
+  ~tdr_renderer() {
+    if (rendered) { (void)hipEventSynchronize(rendered); (void)hipEventDestroy(rendered); }
+    for (auto& e : readers) { (void)hipEventSynchronize(e.second); (void)hipEventDestroy(e.second); }
+  }
 };
 
 struct tdr_filter {
@@ -134,7 +145,10 @@ struct tdr_filter {
   // clears the flag (states_changed).
   float mean_cov_host[24] = {0};
   bool mean_cov_valid = false;
-  void states_changed() { mean_cov_valid = false; }
+  // scale() of a frozen filter as tdr_batch_pose read it back (cleared with the mean / covariance)
+  float scale_host = -1.f;
+  bool scale_valid = false;
+  void states_changed() { mean_cov_valid = false; scale_valid = false; }
   hipStream_t stream = nullptr;
   tdr_score_ctx* score_ctx = nullptr;   // this filter's own span tuner (and the table's factors) for its scoring launches (tdr.h)
   // The reference's generator in parity mode: the host std::mt19937 `rng` and its continuation on the device, a
@@ -152,6 +166,27 @@ struct tdr_filter {
   DevBuf<float> geo_pk;   // packed geometric scan (tdr_filter_update_geo)
   int64_t nl() const { return n / world; }
 };
+
+// a stream that reads a renderer's render continues after its batched render / notes the read for the next one
+static int renderer_wait_render(const tdr_renderer* r, hipStream_t s) {
+  if (r->render_async) HTRY(hipStreamWaitEvent(s, r->rendered, 0));
+  return TDR_OK;
+}
+static int renderer_note_read(const tdr_renderer* r, hipStream_t s) {
+  size_t i = 0;
+  while (i < r->n_readers && r->readers[i].first != s) i++;
+  if (i == r->n_readers) {
+    if (i == r->readers.size()) {
+      hipEvent_t e = nullptr;
+      HTRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      r->readers.emplace_back(s, e);
+    }
+    r->readers[i].first = s;
+    r->n_readers++;
+  }
+  HTRY(hipEventRecord(r->readers[i].second, s));
+  return TDR_OK;
+}
 
 // .eig files of the reference's map cache (top_down_map.h:29-50)
 static std::string cache_dir_or_default(const char* cache_dir) {
@@ -889,6 +924,10 @@ int tdr_renderer_render(tdr_renderer* r, int polar, const float* pts, int stride
   if (n < 0 || (n > 0 && !pts)) return failh(TDR_ERR_ARG, "render: null points");
   if (ncls < 1 || rows < 1 || cols < 1) return TDR_OK;  // `if (imgs.size() < 1) return;` (:85)
   const size_t P = (size_t)rows * cols;
+  if (r->render_async) {   // (a tdr_batch_render_polar still writing img / pk)
+    HTRY(hipEventSynchronize(r->rendered));
+    r->render_async = false;
+  }
   TTRY(r->pts.resize((size_t)std::max<int64_t>(n, 1) * stride));
   TTRY(r->img.resize(P * ncls));
   TTRY(r->pk.resize(P * tdr_rec_floats(ncls)));
@@ -1246,6 +1285,7 @@ static int filter_score(tdr_filter* f, const float* scan_imgs, const tdr_rendere
       return failh(TDR_ERR_ARG, "filter_update: render shape %dx%dx%d does not match the map's %dx%dx%d",
                    renderer->ncls, renderer->rows, renderer->cols, ncls, nb, nr);
     pk = renderer->pk.p;
+    TTRY(renderer_wait_render(renderer, f->stream));
   } else if (!(f->comm && f->rank != 0)) {
     return failh(TDR_ERR_ARG, "filter_update: no scan");
   }
@@ -1277,6 +1317,7 @@ static int filter_score(tdr_filter* f, const float* scan_imgs, const tdr_rendere
   TTRY(tdr_score_ctx_set_polar_factors(f->score_ctx, m->fac.p, nb, nr));
   TTRY(tdr_k_score_polar_ctx(&m->desc, m->tab.p, pk, nb, nr, res, &f->fp, f->st.p, f->cap, n, f->n, perm, f->uniform_scale,
                              f->maybe_uninit ? 1 : 0, f->raw_w.p, f->ws.p, f->score_ctx, f->stream));
+  if (renderer && !scan_imgs) TTRY(renderer_note_read(renderer, f->stream));
   // the search initialises every un-gated particle; only gated ones (state_particle.cpp:163-176) can stay un-initialised
   if (f->maybe_uninit && !(f->fp.force_on_map || f->fp.fixed_scale < 0)) f->maybe_uninit = false;
   return TDR_OK;
@@ -1406,6 +1447,7 @@ float tdr_filter_scale(tdr_filter* f) {
   if (!f) return -1.f;
   if (f->fp.fixed_scale > 0) return f->fp.fixed_scale;
   if (f->scale_frozen && f->n > 0) {
+    if (f->scale_valid) return f->scale_host;
     float s = -1.f;
     if (hipMemcpy(&s, f->st.p + (size_t)TDR_ST_SCALE * f->cap, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
     return s;
@@ -1575,8 +1617,10 @@ int tdr_batch_step(tdr_filter* const* filters, int k, const tdr_batch_input* in,
   TdrBatchEntry* const tab = reinterpret_cast<TdrBatchEntry*>(B.host);
   TdrBatchEntry* const tab_dev = reinterpret_cast<TdrBatchEntry*>(B.dev.p);
 
-  // the batch stream continues after everything already queued on the filters' own streams, and after the previous
-  // batch's kernels have read the device tables this call overwrites
+  // the batch stream continues after the batched renders it reads, everything already queued on the filters' own
+  // streams, and after the previous batch's kernels have read the device tables this call overwrites
+  for (int j = 0; j < kf; j++)
+    if (!in[fast[j]].scan_imgs) TTRY(renderer_wait_render(in[fast[j]].renderer, s));
   std::vector<hipEvent_t> evs((size_t)kf, nullptr);
   auto destroy_events = [&]() { for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e); };
   int rc = TDR_OK;
@@ -1644,6 +1688,8 @@ int tdr_batch_step(tdr_filter* const* filters, int k, const tdr_batch_input* in,
   if (rc == TDR_OK) rc = tdr_batch_prefix(tab_dev, kf, n_big, s);
   if (rc == TDR_OK) rc = tdr_batch_resample(tab_dev, kf, blocks_res, s);
   if (rc == TDR_OK && hipEventRecord(B.done, s) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: event record");
+  for (int j = 0; j < kf && rc == TDR_OK; j++)
+    if (!in[fast[j]].scan_imgs) rc = renderer_note_read(in[fast[j]].renderer, s);
   if (rc != TDR_OK) { destroy_events(); return rc; }
   for (int j = 0; j < kf; j++) {
     tdr_filter* f = filters[fast[j]];
@@ -1659,6 +1705,238 @@ int tdr_batch_step(tdr_filter* const* filters, int k, const tdr_batch_input* in,
   destroy_events();
   g_batch_stats[0] = kf;
   return rc;
+}
+}  // extern "C"
+
+// ---- the two ends of a batched node loop: tdr_batch_render_polar, tdr_batch_pose (csrc/tdr_batch_loop.hip) ---------------
+namespace {
+struct StageCtx {   // per thread and call kind: pinned staging, its device copy, the events that order their reuse
+  char* host = nullptr;
+  size_t cap = 0;
+  DevBuf<char> dev;
+  hipEvent_t uploaded = nullptr;   // the last call's copies have read / written `host`
+  hipEvent_t done = nullptr;       // the last call's kernels have read `dev`
+  ~StageCtx() {
+    if (uploaded) { (void)hipEventSynchronize(uploaded); (void)hipEventDestroy(uploaded); }
+    if (done) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+    if (host) (void)hipHostFree(host);
+  }
+  // host >= host_bytes, dev >= dev_bytes; `s` continues after the previous call's kernels
+  int reserve(size_t host_bytes, size_t dev_bytes, hipStream_t s) {
+    if (!uploaded) HTRY(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
+    if (!done) HTRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    HTRY(hipEventSynchronize(uploaded));
+    if (cap < host_bytes) {
+      if (host) HTRY(hipHostFree(host));
+      host = nullptr;
+      cap = 0;
+      HTRY(hipHostMalloc((void**)&host, host_bytes));
+      cap = host_bytes;
+    }
+    if (dev.n < dev_bytes) {
+      HTRY(hipEventSynchronize(done));
+      TTRY(dev.resize(dev_bytes));
+    }
+    HTRY(hipStreamWaitEvent(s, done, 0));
+    return TDR_OK;
+  }
+};
+thread_local StageCtx g_render_stage, g_pose_stage;
+size_t align64(size_t b) { return (b + 63) / 64 * 64; }
+}  // namespace
+
+extern "C" {
+int tdr_batch_render_polar(tdr_renderer* const* r, int k, const tdr_batch_cloud* clouds, float ang_res, int ncls, int nb,
+                           int nr, void* stream) {
+  if (k < 1) return failh(TDR_ERR_ARG, "batch_render: k = %d, at least one renderer is needed", k);
+  if (!r || !clouds) return failh(TDR_ERR_ARG, "batch_render: null %s array", !r ? "renderer" : "cloud");
+  for (int i = 0; i < k; i++)
+    if (!r[i]) return failh(TDR_ERR_ARG, "batch_render: renderer %d is null", i);
+  {
+    std::vector<const tdr_renderer*> seen(r, r + k);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+      return failh(TDR_ERR_ARG, "batch_render: a renderer appears twice in the batch");
+  }
+  for (int i = 0; i < k; i++) {
+    const tdr_batch_cloud& c = clouds[i];
+    if (c.n < 0 || (c.n > 0 && !c.pts)) return failh(TDR_ERR_ARG, "batch_render: cloud %d: null points", i);
+    if (c.stride < 3 || c.ioff < 0 || c.ioff >= c.stride)
+      return failh(TDR_ERR_ARG, "batch_render: cloud %d: bad point stride / offset %d / %d", i, c.stride, c.ioff);
+    if (!(c.res > 0.f)) return failh(TDR_ERR_ARG, "batch_render: cloud %d: resolution must be > 0", i);
+  }
+  if (!(ang_res > 0.f)) return failh(TDR_ERR_ARG, "batch_render: angular resolution must be > 0");
+  if (ncls < 1 || ncls > TDR_MAX_CLASSES || nb < 1 || nr < 1)
+    return failh(TDR_ERR_ARG, "batch_render: bad image shape %dx%dx%d", ncls, nb, nr);
+  if ((int64_t)ncls * nb * 4 > 152 * 1024) return failh(TDR_ERR_ARG, "batch_render: ncls*rows too large for one LDS tile (152 KB)");
+  TdrBatchRasterShape shape{};
+  const bool keyed = tdr_batch_raster_shape(ncls, nb, nr, ang_res, &shape);
+  hipStream_t s = (hipStream_t)stream;
+
+  // one staging area: [k] entries, then every cloud's points (64-byte aligned); on the device, the keys follow
+  const size_t ent_bytes = align64(sizeof(TdrBatchRasterEntry) * (size_t)k);
+  std::vector<size_t> pts_off((size_t)k), key_off((size_t)k);
+  size_t stage = ent_bytes;
+  for (int i = 0; i < k; i++) {
+    pts_off[i] = stage;
+    stage += align64((size_t)clouds[i].n * clouds[i].stride * sizeof(float));
+  }
+  size_t dev_bytes = stage;
+  for (int i = 0; i < k; i++) {
+    key_off[i] = dev_bytes;
+    dev_bytes += align64((size_t)clouds[i].n * sizeof(uint32_t));
+  }
+  StageCtx& B = g_render_stage;
+  TTRY(B.reserve(stage, std::max<size_t>(dev_bytes, 64), s));
+  const size_t P = (size_t)nb * nr, rf = (size_t)tdr_rec_floats(ncls);
+  for (int i = 0; i < k; i++) {
+    tdr_renderer* q = r[i];
+    TTRY(q->img.resize(P * ncls));
+    TTRY(q->pk.resize(P * rf));
+    // img / pk are rewritten: after their readers and the renderer's previous batched render
+    for (size_t j = 0; j < q->n_readers; j++) HTRY(hipStreamWaitEvent(s, q->readers[j].second, 0));
+    TTRY(renderer_wait_render(q, s));
+    if (!q->rendered) HTRY(hipEventCreateWithFlags(&q->rendered, hipEventDisableTiming));
+  }
+  TdrBatchRasterEntry* tab = reinterpret_cast<TdrBatchRasterEntry*>(B.host);
+  int blocks_keys = 0;
+  for (int i = 0; i < k; i++) {
+    const tdr_batch_cloud& c = clouds[i];
+    if (c.n > 0) std::memcpy(B.host + pts_off[i], c.pts, (size_t)c.n * c.stride * sizeof(float));
+    TdrBatchRasterEntry& e = tab[i];
+    e = TdrBatchRasterEntry{};
+    e.pts = reinterpret_cast<const float*>(B.dev.p + pts_off[i]);
+    e.lut = r[i]->lut.p;
+    e.keys = reinterpret_cast<uint32_t*>(B.dev.p + key_off[i]);
+    e.img = r[i]->img.p;
+    e.pk = r[i]->pk.p;
+    e.n = c.n;
+    e.res = c.res;
+    e.stride = c.stride;
+    e.ioff = c.ioff;
+    e.blk_keys = blocks_keys;
+    blocks_keys += (int)((c.n + 255) / 256);
+  }
+  HTRY(hipMemcpyAsync(B.dev.p, B.host, stage, hipMemcpyHostToDevice, s));
+  HTRY(hipEventRecord(B.uploaded, s));
+  if (keyed) {
+    TTRY(tdr_batch_raster(reinterpret_cast<const TdrBatchRasterEntry*>(B.dev.p), k, blocks_keys, shape, s));
+  } else {   // shapes the standalone raster scores without keys: its own launch per renderer
+    for (int i = 0; i < k; i++)
+      TTRY(tdr_k_raster_polar(tab[i].pts, clouds[i].stride, clouds[i].ioff, clouds[i].n, clouds[i].res, ang_res, r[i]->lut.p,
+                              ncls, nb, nr, r[i]->img.p, r[i]->pk.p, tab[i].keys, s));
+  }
+  HTRY(hipEventRecord(B.done, s));
+  for (int i = 0; i < k; i++) {
+    tdr_renderer* q = r[i];
+    HTRY(hipEventRecord(q->rendered, s));
+    q->render_async = true;
+    q->n_readers = 0;
+    q->ncls = ncls;
+    q->rows = nb;
+    q->cols = nr;
+    q->have_scan = true;
+  }
+  return TDR_OK;
+}
+
+int tdr_renderer_get_render(const tdr_renderer* r, float* imgs_out, float* pk_out) {
+  if (!r) return failh(TDR_ERR_ARG, "renderer_get_render: null renderer");
+  if (!r->have_scan) return failh(TDR_ERR_ARG, "renderer_get_render: the renderer has no render");
+  const size_t P = (size_t)r->rows * r->cols;
+  if (r->render_async) HTRY(hipEventSynchronize(r->rendered));
+  if (imgs_out) HTRY(hipMemcpy(imgs_out, r->img.p, P * r->ncls * sizeof(float), hipMemcpyDeviceToHost));
+  if (pk_out) HTRY(hipMemcpy(pk_out, r->pk.p, P * tdr_rec_floats(r->ncls) * sizeof(float), hipMemcpyDeviceToHost));
+  return TDR_OK;
+}
+
+int tdr_batch_pose(tdr_filter* const* f, int k, tdr_pose_stats* out, void* stream) {
+  if (k < 1) return failh(TDR_ERR_ARG, "batch_pose: k = %d, at least one filter is needed", k);
+  if (!f || !out) return failh(TDR_ERR_ARG, "batch_pose: null %s array", !f ? "filter" : "output");
+  for (int i = 0; i < k; i++)
+    if (!f[i]) return failh(TDR_ERR_ARG, "batch_pose: filter %d is null", i);
+  {
+    std::vector<const tdr_filter*> seen(f, f + k);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+      return failh(TDR_ERR_ARG, "batch_pose: a filter appears twice in the batch");
+  }
+  for (int i = 0; i < k; i++)
+    if (f[i]->map != f[0]->map) return failh(TDR_ERR_ARG, "batch_pose: filter %d is on another map than filter 0", i);
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> small, big;
+  for (int i = 0; i < k; i++) {
+    tdr_filter* g = f[i];
+    tdr_pose_stats& o = out[i];
+    o = tdr_pose_stats{};
+    o.n = g->n;
+    if (g->comm) {   // the all-gather inside is collective: the standalone calls
+      TTRY(tdr_filter_mean_cov(g, 0, o.mean, o.cov));
+      o.scale = tdr_filter_scale(g);
+      continue;
+    }
+    if (g->n < 1) { o.scale = tdr_filter_scale(g); continue; }   // (zeros, no device work)
+    (g->n <= TDR_BATCH_MC_SINGLE_MAX_N ? small : big).push_back(i);
+  }
+  const int ks = (int)small.size(), kb = (int)big.size(), kd = ks + kb;
+  if (kd == 0) return TDR_OK;
+  // staging: [kd] entries (small ones first), then the [kd] result records the kernels write and the copy brings back
+  const size_t ent_bytes = align64(sizeof(TdrBatchPoseEntry) * (size_t)kd);
+  const size_t res_bytes = sizeof(float) * TDR_BATCH_POSE_FLOATS * (size_t)kd;
+  StageCtx& B = g_pose_stage;
+  TTRY(B.reserve(ent_bytes + res_bytes, ent_bytes + res_bytes, s));
+  // after every filter's last step, on whichever stream it ran (tdr_batch_step leaves the filters' streams after it)
+  {
+    std::vector<hipStream_t> streams;
+    for (int i : small) streams.push_back(f[i]->stream);
+    for (int i : big) streams.push_back(f[i]->stream);
+    std::sort(streams.begin(), streams.end());
+    streams.erase(std::unique(streams.begin(), streams.end()), streams.end());
+    for (hipStream_t fs : streams) {
+      if (fs == s) continue;
+      hipEvent_t e = nullptr;
+      HTRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      int rc = TDR_OK;
+      if (hipEventRecord(e, fs) != hipSuccess || hipStreamWaitEvent(s, e, 0) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_pose: stream order");
+      (void)hipEventDestroy(e);
+      if (rc != TDR_OK) return rc;
+    }
+  }
+  TdrBatchPoseEntry* tab = reinterpret_cast<TdrBatchPoseEntry*>(B.host);
+  float* res_dev = reinterpret_cast<float*>(B.dev.p + ent_bytes);
+  float* res_host = reinterpret_cast<float*>(B.host + ent_bytes);
+  std::vector<int> order(small);
+  order.insert(order.end(), big.begin(), big.end());
+  for (int j = 0; j < kd; j++) {
+    tdr_filter* g = f[order[j]];
+    tab[j] = TdrBatchPoseEntry{g->st.p, g->cap, g->n, res_dev + (size_t)TDR_BATCH_POSE_FLOATS * j, g->stats.p + 24};
+  }
+  const TdrBatchPoseEntry* tab_dev = reinterpret_cast<const TdrBatchPoseEntry*>(B.dev.p);
+  HTRY(hipMemcpyAsync(B.dev.p, B.host, ent_bytes, hipMemcpyHostToDevice, s));
+  TTRY(tdr_batch_pose_launch(tab_dev, ks, tab_dev + ks, kb, s));
+  HTRY(hipMemcpyAsync(res_host, res_dev, res_bytes, hipMemcpyDeviceToHost, s));
+  HTRY(hipEventRecord(B.done, s));
+  HTRY(hipEventRecord(B.uploaded, s));
+  HTRY(hipEventSynchronize(B.done));   // the one wait of the call
+  for (int j = 0; j < kd; j++) {
+    tdr_filter* g = f[order[j]];
+    const float* rec = res_host + (size_t)TDR_BATCH_POSE_FLOATS * j;
+    tdr_pose_stats& o = out[order[j]];
+    std::memcpy(g->mean_cov_host, rec, sizeof(g->mean_cov_host));   // the cache tdr_filter_mean_cov(f, 0, ...) reads
+    g->mean_cov_valid = true;
+    std::memcpy(o.mean, rec, sizeof(o.mean));
+    std::memcpy(o.cov, rec + 4, sizeof(o.cov));
+    if (g->fp.fixed_scale > 0) {           // tdr_filter_scale
+      o.scale = g->fp.fixed_scale;
+    } else if (g->scale_frozen) {
+      o.scale = rec[24];
+      g->scale_host = rec[24];
+      g->scale_valid = true;
+    } else {
+      o.scale = -1.f;
+    }
+  }
+  return TDR_OK;
 }
 }  // extern "C"
 
