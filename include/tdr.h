@@ -347,6 +347,23 @@ int tdr_init_particle_host(void* rng, const float* class_maps, int ncls, int row
                            const tdr_filter_params* fp, tdr_state* out);
 int tdr_init_particles_host(void* rng, const float* class_maps, int ncls, int rows, int cols, float resolution,
                             const tdr_filter_params* fp, int max_num, tdr_state* out, int64_t* n_out);
+/* The same particle loop on the DEVICE (csrc/tdr_init.hip): for the same generator state and map it writes the same
+ * states as tdr_init_particles_host and leaves the generator at the same word.  rng_state_dev: TDR_RNG_STATE_WORDS device
+ * words (tdr_k_rng_propagate_normals); the on-road test reads the class-1 slot of map->rec.  Particles [lo, hi) of the
+ * n_out = tdr_init_particles_count(fp, max_num) the loop keeps go to the SoA planes st (stride cap) at index i - lo;
+ * dx_m = dy_m = 0.  Every rank of a sharded filter runs the whole chain and writes its own slice.  The stream is read in
+ * windows of tdr_config_tuning("init_window_words") words; workspace: tdr_init_workspace_bytes() bytes of device memory,
+ * fixed by the window, not by max_num.  Synchronises `stream` once per window.  Errors as the host loop's: fewer than 2
+ * classes, a map without a road cell (TDR_ERR_ARG, no word drawn); unknown scale with max_num < 10 keeps 0 particles
+ * and draws nothing.  tdr_rng_pipe_init_particles runs it on a pipe's state (the pipe must be on the device): what the
+ * pipe drew ahead is dropped and the stream stays on the device. */
+int64_t tdr_init_particles_count(const tdr_filter_params* fp, int max_num);
+size_t tdr_init_workspace_bytes(void);
+int tdr_k_init_particles(uint32_t* rng_state_dev, const tdr_map_desc* map, const tdr_filter_params* fp, int max_num,
+                         int64_t lo, int64_t hi, float* st, int64_t cap, int64_t* n_out, void* workspace, void* stream);
+int tdr_rng_pipe_init_particles(tdr_rng_pipe* p, const tdr_map_desc* map, const tdr_filter_params* fp, int max_num,
+                                int64_t lo, int64_t hi, float* st, int64_t cap, int64_t* n_out, void* workspace,
+                                void* stream);
 
 /* ---- ParticleFilter::update, weight statistics (src/particle_filter.cpp:107-147) ---------------------------- */
 /* raw_w, last_dist: [n] -> w_out [n] final normalised weights; info_out (device, TDR_UW_INFO_FLOATS floats: the first 8
@@ -523,7 +540,11 @@ int tdr_profile_variants(int64_t out[16]);
  *   "cart_seg_rows"    window rows per segment of score_cart_su_kernel (a multiple of 4; 0: the Cartesian integer form's dense
  *                      share goes through the plain kernel instead — same bits)
  *   "su_lds_pad"       bytes of dynamic LDS added to a workgroup of score_polar_su_kernel: fewer workgroups fit a CU — an
- *                      occupancy sweep without touching the code object (0, the default; same bits) */
+ *                      occupancy sweep without touching the code object (0, the default; same bits)
+ *   "init_device"      0: tdr_filter_initialize_particles keeps the serial host loop; 1 (default): a filter that owns its
+ *                      generator in parity mode initialises on the device (tdr_k_init_particles — the same states)
+ *   "init_window_words" words of the generator's stream per window of tdr_k_init_particles (a multiple of 2048, 2048 to
+ *                      2^22; default 2^21; same states) */
 int64_t tdr_config_tuning(const char* name, int64_t value);
 /* Device self-test of the scoring kernels: a tiny fixed problem (160 x 160 map, 6 classes, 512 particles) scored by every
  * kernel the library has for it.  The integer-form kernels run generated, hand-scheduled assembly; their sums are exact, so
@@ -749,7 +770,12 @@ void tdr_filter_destroy(tdr_filter* f);
 /* parity_rng: propagate consumes host std::mt19937 normals in the reference's order; 0 = device RNG.
  * locality_every: > 0 processes particles in Morton order of their map position (default 1; results unchanged). */
 int tdr_filter_configure(tdr_filter* f, int parity_rng, int locality_every);
-int tdr_filter_initialize_particles(tdr_filter* f);                                      /* particle_filter.cpp:19-84 */
+/* particle_filter.cpp:19-84.  The loop keeps tdr_init_particles_count(fp, n_max) particles; a filter sharded over W ranks
+ * then keeps n - n % W of them (the first ones), so every rank holds the same count.  A filter that owns its generator in
+ * parity mode (seed != 0, no tdr_filter_share_rng) draws on the device (tdr_rng_pipe_init_particles): the generator stays
+ * there, each rank runs the whole chain and keeps its own slice.  A generator shared with the caller, and
+ * tdr_config_tuning("init_device", 0), keep the host loop.  Same states either way. */
+int tdr_filter_initialize_particles(tdr_filter* f);
 int tdr_filter_set_states(tdr_filter* f, const tdr_state* states, int64_t n);
 int tdr_filter_get_states(tdr_filter* f, tdr_state* out, int64_t n);
 int tdr_filter_propagate(tdr_filter* f, float tx, float ty, float omega);                /* particle_filter.cpp:86-92 */

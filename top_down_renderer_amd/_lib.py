@@ -158,6 +158,12 @@ SIGNATURES = {
     "tdr_k_resample": (_i, [_vp, _i64, _i64, _f, _i64, _i64, _vp, _vp]),
     "tdr_k_gather_states": (_i, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "tdr_init_particles_host": (_i, [_vp, _vp, _i, _i, _i, _f, C.POINTER(FilterParamsC), _i, _vp, C.POINTER(C.c_int64)]),
+    "tdr_init_particles_count": (_i64, [C.POINTER(FilterParamsC), _i]),
+    "tdr_init_workspace_bytes": (C.c_size_t, []),
+    "tdr_k_init_particles": (_i, [_vp, C.POINTER(MapDescC), C.POINTER(FilterParamsC), _i, _i64, _i64, _vp, _i64,
+                                  C.POINTER(C.c_int64), _vp, _vp]),
+    "tdr_rng_pipe_init_particles": (_i, [_vp, C.POINTER(MapDescC), C.POINTER(FilterParamsC), _i, _i64, _i64, _vp, _i64,
+                                         C.POINTER(C.c_int64), _vp, _vp]),
     "tdr_k_mean_cov": (_i, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "tdr_k_sample_ml_states": (_i, [_vp, _i64, _i64, _i, _vp, _vp]),
     "tdr_gmm_fit_host": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

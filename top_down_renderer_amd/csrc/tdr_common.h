@@ -71,6 +71,9 @@ int tdr_chain_total(const float* raw, const float* mean_dev, int kind, int64_t n
                     hipStream_t st);
 // tdr_prefix.hip: particle_filter.cpp:107-147 for n <= 32768 in one launch, both serial chains exact
 int tdr_uw_small(const float* raw, const float* last_dist, int64_t n, float* w, float* info, hipStream_t st);
+// tdr_rng.hip: the generator's raw stream of `nblocks` state blocks behind `state`, and the state behind *consumed words of it
+int tdr_mt_raw_stream(const uint32_t* state, int64_t nblocks, uint32_t* raw, hipStream_t s);
+int tdr_mt_advance(const uint32_t* raw, int64_t nblocks, const uint32_t* consumed, uint32_t* state, hipStream_t s);
 // tdr_score.hip: whether tdr_k_score_polar_ctx scores a filter of these shapes with the float kernel (not the integer form)
 bool tdr_score_polar_float_form(const tdr_map_desc* map, int nb, int nr, int64_t n, int64_t n_total);
 // a record with a spare slot (ncls + 2 <= rf) carries `known` twice: slot rf-2 pairs with a constant 1 of the scan record

@@ -1085,6 +1085,33 @@ int tdr_filter_get_states(tdr_filter* f, tdr_state* out, int64_t n) {
   return TDR_OK;
 }
 
+// The particle loop of initializeParticles on the device, on the filter's own generator (which stays there): every rank
+// runs the whole chain and writes its slice; the bookkeeping is tdr_filter_set_states' for the states the loop makes
+// (one heading rule and one scale rule for all of them).
+static int rng_to_device(tdr_filter* f);
+static bool rng_device_capable(const tdr_filter* f);
+static int initialize_on_device(tdr_filter* f) {
+  tdr_map* m = f->map;
+  const tdr_filter_params& p = f->fp;
+  int64_t n = std::min<int64_t>(tdr_init_particles_count(&p, (int)f->n_max), f->n_max);
+  n -= n % f->world;
+  const int64_t nl = n / f->world;
+  TTRY(rng_to_device(f));
+  DevBuf<uint8_t> ws;
+  TTRY(ws.resize(tdr_init_workspace_bytes()));
+  int64_t made = 0;
+  TTRY(tdr_rng_pipe_init_particles(f->pipe, &m->desc, &p, (int)f->n_max, (int64_t)f->rank * nl, (int64_t)(f->rank + 1) * nl,
+                                   f->st.p, f->cap, &made, ws.p, f->stream));
+  HTRY(hipStreamSynchronize(f->stream));
+  f->n = n;
+  f->states_changed();
+  f->maybe_uninit = n > 0 && p.init_pos_deg_theta == std::numeric_limits<float>::infinity();
+  if (p.fixed_scale > 0) f->scale_frozen = true;
+  // note_uniform_scale: a fixed scale is every particle's; the unknown-scale groups hold ten different scales
+  f->uniform_scale = (f->scale_frozen && n > 0 && p.fixed_scale > 0) ? p.fixed_scale : 0.f;
+  return TDR_OK;
+}
+
 // ParticleFilter::initializeParticles (particle_filter.cpp:19-84)
 int tdr_filter_initialize_particles(tdr_filter* f) {
   if (!f || !f->map || !f->map->have_map) return failh(TDR_ERR_ARG, "initialize_particles: no map");
@@ -1107,6 +1134,7 @@ int tdr_filter_initialize_particles(tdr_filter* f) {
       }
     if (!good) return TDR_OK;  // "No road in map at init location"
   }
+  if (rng_device_capable(f) && tdr_config_tuning("init_device", -1) != 0) return initialize_on_device(f);
   std::vector<tdr_state> states((size_t)f->n_max + 16);
   int64_t n = 0;
   TTRY(rng_to_host(f));

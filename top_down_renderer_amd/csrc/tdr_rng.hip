@@ -262,6 +262,30 @@ extern "C" int tdr_config_mt_stretches(int on) {   // < 0: query only
   if (on >= 0) g_mt_stretches = on ? 1 : 0;
   return g_mt_stretches;
 }
+// The raw stream [nblocks][624] behind `state` (mt_fill_kernel's layout): one wave walks it, or — a long call — stretches of
+// MT_JUMP_STRIDE blocks side by side, their first blocks reached by jumping ahead in rounds of doubling (round m: the 2^m
+// stretch starts there are, each 2^m stretches further).  Also the windows of the particle initialisation (tdr_init.hip).
+int tdr_mt_raw_stream(const uint32_t* state, int64_t nblocks, uint32_t* raw, hipStream_t s) {
+  const int64_t nstretch = cdiv(nblocks, (int64_t)MT_JUMP_STRIDE);
+  if (g_mt_stretches && nstretch > 1 && nstretch <= ((int64_t)1 << MT_JUMP_LEVELS)) {
+    for (int m = 0; ((int64_t)1 << m) < nstretch; m++) {
+      const int64_t have = (int64_t)1 << m, jumps = std::min(have, nstretch - have);
+      hipLaunchKernelGGL(mt_jump_kernel, dim3((unsigned)jumps), dim3(1024), 0, s, state, raw, m);
+      LAUNCH_CHECK("mt_jump");
+    }
+    hipLaunchKernelGGL(mt_fill_kernel, dim3((unsigned)nstretch), dim3(64), 0, s, state, (int)nblocks, MT_JUMP_STRIDE, raw);
+  } else {
+    hipLaunchKernelGGL(mt_fill_kernel, dim3(1), dim3(64), 0, s, state, (int)nblocks, (int)nblocks, raw);
+  }
+  LAUNCH_CHECK("mt_fill");
+  return TDR_OK;
+}
+// `state` moves behind the *consumed (device) words of the raw stream of `nblocks` blocks that was filled from it
+int tdr_mt_advance(const uint32_t* raw, int64_t nblocks, const uint32_t* consumed, uint32_t* state, hipStream_t s) {
+  hipLaunchKernelGGL(mt_advance_kernel, dim3(1), dim3(64), 0, s, raw, (int)nblocks, consumed, state);
+  LAUNCH_CHECK("mt_advance");
+  return TDR_OK;
+}
 // attempts a call may look at: the expected 3.82 per particle-normal... (acceptance pi / 4) plus 5 % and ten standard
 // deviations: running out has probability ~1e-23 (and is reported, never silent)
 static int64_t mt_attempt_budget(int64_t need) {
@@ -312,21 +336,7 @@ extern "C" int tdr_k_rng_propagate_normals(uint32_t* state, int64_t n, int64_t l
   uint32_t* rank = reinterpret_cast<uint32_t*>(base + W.off_rank);
   uint32_t* consumed = reinterpret_cast<uint32_t*>(base + W.off_consumed);
   HIP_TRY(hipMemsetAsync(consumed, 0xFF, 4, s));
-  // the raw stream: one wave walks it, or — a long call — stretches of MT_JUMP_STRIDE blocks side by side, their first blocks
-  // reached by jumping ahead in rounds of doubling (round m: the 2^m stretch starts there are, each 2^m stretches further)
-  const int64_t nstretch = cdiv(W.nblocks, (int64_t)MT_JUMP_STRIDE);
-  if (g_mt_stretches && nstretch > 1 && nstretch <= ((int64_t)1 << MT_JUMP_LEVELS)) {
-    for (int m = 0; ((int64_t)1 << m) < nstretch; m++) {
-      const int64_t have = (int64_t)1 << m, jumps = std::min(have, nstretch - have);
-      hipLaunchKernelGGL(mt_jump_kernel, dim3((unsigned)jumps), dim3(1024), 0, s, (const uint32_t*)state, raw, m);
-      LAUNCH_CHECK("mt_jump");
-    }
-    hipLaunchKernelGGL(mt_fill_kernel, dim3((unsigned)nstretch), dim3(64), 0, s, (const uint32_t*)state, (int)W.nblocks,
-                       MT_JUMP_STRIDE, raw);
-  } else {
-    hipLaunchKernelGGL(mt_fill_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)state, (int)W.nblocks, (int)W.nblocks, raw);
-  }
-  LAUNCH_CHECK("mt_fill");
+  if (int rc = tdr_mt_raw_stream(state, W.nblocks, raw, s)) return rc;
   const unsigned blocks = (unsigned)cdiv(W.nattempts, 256);
   hipLaunchKernelGGL(mt_attempt_kernel, dim3(blocks), dim3(256), 0, s, (const uint32_t*)raw, (const uint32_t*)state,
                      W.nattempts, flags);
@@ -337,10 +347,7 @@ extern "C" int tdr_k_rng_propagate_normals(uint32_t* state, int64_t n, int64_t l
   hipLaunchKernelGGL(mt_normal_kernel, dim3(blocks), dim3(256), 0, s, (const uint32_t*)raw, (const uint32_t*)state,
                      (const uint32_t*)flags, (const uint32_t*)rank, W.nattempts, n, per, lo, hi, z4_out, consumed);
   LAUNCH_CHECK("mt_normal");
-  hipLaunchKernelGGL(mt_advance_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)raw, (int)W.nblocks,
-                     (const uint32_t*)consumed, state);
-  LAUNCH_CHECK("mt_advance");
-  return TDR_OK;
+  return tdr_mt_advance(raw, W.nblocks, consumed, state, s);
 }
 extern "C" int tdr_k_rng_uniform(uint32_t* state, float* out, void* stream) {
   if (!state || !out) return fail(TDR_ERR_ARG, "rng_uniform: null pointer");
@@ -560,6 +567,20 @@ extern "C" int tdr_rng_pipe_normals(tdr_rng_pipe* p, int64_t n, int64_t lo, int6
   }
   *z4_out = p->z[p->cur];
   return pipe_draw_ahead(p, n, lo, hi, fr, s);
+}
+// ParticleFilter::initializeParticles on the pipe's state (tdr_k_init_particles): what was drawn ahead is dropped — the
+// stream position moves by a data-dependent count of words — and the stream stays on the device.  Ordered on `stream`
+// (the call itself waits for each window's end).
+extern "C" int tdr_rng_pipe_init_particles(tdr_rng_pipe* p, const tdr_map_desc* map, const tdr_filter_params* fp, int max_num,
+                                           int64_t lo, int64_t hi, float* st, int64_t cap, int64_t* n_out, void* workspace,
+                                           void* stream) {
+  if (!p) return fail(TDR_ERR_ARG, "rng_pipe_init_particles: null pointer");
+  if (!p->on_device) return fail(TDR_ERR_ARG, "rng_pipe_init_particles: the stream is on the host (tdr_rng_pipe_from_host)");
+  if (int rc = pipe_check(p, "rng_pipe_init_particles")) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = pipe_drop(p, s)) return rc;
+  p->misses = 0;
+  return tdr_k_init_particles(p->state, map, fp, max_num, lo, hi, st, cap, n_out, workspace, stream);
 }
 // The uniform draw of the resample: *shift_out = device float, valid until the next call of this function.
 extern "C" int tdr_rng_pipe_uniform(tdr_rng_pipe* p, const float** shift_out, void* stream) {

@@ -74,6 +74,15 @@ class RngPipe:
         check(self.lib.tdr_rng_pipe_uniform(self.handle, C.byref(u), self.k.stream()))
         return DevPtr(u.value)
 
+    def init_particles(self, dmap, fp, max_num, lo, hi, st):
+        """initializeParticles' particle loop on the pipe's state (tdr_rng_pipe_init_particles): particles [lo, hi) into
+        the SoA planes st; returns the count the loop keeps."""
+        n = C.c_int64(0)
+        ws = self.k.empty((int(self.lib.tdr_init_workspace_bytes()),), torch.uint8)
+        check(self.lib.tdr_rng_pipe_init_particles(self.handle, C.byref(dmap.desc), C.byref(fp), max_num, lo, hi, _ptr(st),
+                                                   st.shape[1], C.byref(n), _ptr(ws), self.k.stream()))
+        return n.value
+
     def __del__(self):
         try:
             if self.handle:
@@ -587,6 +596,10 @@ class HipKernels:
         check(self.lib.tdr_k_states_soa_to_aos(_ptr(st), st.shape[1], n, _ptr(raw), self.stream()))
         return raw.cpu().numpy().view(dtype).reshape(-1).copy()
 
+    def tuning(self, name, value=-1):
+        """tdr_config_tuning (include/tdr.h): value < 0 queries; returns the value in force, -1 for an unknown name."""
+        return int(self.lib.tdr_config_tuning(name.encode(), value))
+
     # ---- host RNG (the reference's shared std::mt19937) -------------------------------------------------------
     def rng_create(self, seed):
         return C.c_void_p(self.lib.tdr_rng_create(C.c_uint32(seed & 0xFFFFFFFF)))
@@ -632,6 +645,19 @@ class HipKernels:
                                                C.c_float(resolution), C.byref(fp), max_num,
                                                out.ctypes.data_as(C.c_void_p), C.byref(n)))
         return out[: min(n.value, max_num + 16)].copy()
+
+    def init_particles_count(self, fp, max_num):
+        """Particles initializeParticles' loop keeps (tdr_init_particles_count)."""
+        return int(self.lib.tdr_init_particles_count(C.byref(fp), max_num))
+
+    def init_particles_dev(self, state_dev, dmap, fp, max_num, lo, hi, st):
+        """The same loop on a device generator state (tdr_k_init_particles): particles [lo, hi) into st; returns the
+        count the loop keeps."""
+        n = C.c_int64(0)
+        ws = self.empty((int(self.lib.tdr_init_workspace_bytes()),), torch.uint8)
+        check(self.lib.tdr_k_init_particles(_ptr(state_dev), C.byref(dmap.desc), C.byref(fp), max_num, lo, hi, _ptr(st),
+                                            st.shape[1], C.byref(n), _ptr(ws), self.stream()))
+        return n.value
 
     def propagate_normals(self, rng, n, scale_freeze):
         z = np.empty((n, 4), np.float32)

@@ -214,6 +214,22 @@ class ParticleFilter:
             if not good:
                 return  # "No road in map at init location" :49-52
         self.fp_c = p.to_c(m.numClasses())
+        if self.parity_rng and getattr(self.k, "device_rng", False) and self.k.tuning("init_device") != 0:
+            # the reference's serial loop, run on the device from where the generator stands; it stays there
+            self._rng_to_device()
+            n = min(self.k.init_particles_count(self.fp_c, self.max_num_particles_), self.max_num_particles_)
+            n -= n % self.comm.world
+            nl = n // self.comm.world
+            self._pipe.init_particles(m.dev, self.fp_c, self.max_num_particles_, self.comm.rank * nl,
+                                      (self.comm.rank + 1) * nl, self.st)
+            # set_states' bookkeeping for the states the loop makes: one heading rule and one scale rule for all of them
+            self.num_particles_ = n
+            self._maybe_uninit = n > 0 and self.fp_c.init_pos_deg_theta == float("inf")
+            self.scale_frozen_ = self.scale_frozen_ or p.fixed_scale > 0
+            fs = self.fp_c.fixed_scale   # (every particle's scale when it is fixed; ten different ones per group if not)
+            self._uniform_scale = fs if (self.scale_frozen_ and n > 0 and fs > 0) else 0.0
+            self.perm = None
+            return
         self._rng_to_host()
         states = self.k.init_particles(self.gen_, m.maps_cm_host, m.numClasses(), m.rows, m.cols, m.resolution(),
                                        self.fp_c, self.max_num_particles_, STATE_DTYPE)
