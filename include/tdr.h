@@ -147,6 +147,41 @@ int tdr_k_unpack_compact_map(const tdr_map_desc* map, float* rec_out, void* stre
  * (tdr_map_rec_floats_total floats).  The Euclidean distance transform is exact. */
 size_t tdr_map_ingest_workspace_bytes(int ncls, int rows, int cols);
 int tdr_map_ingest_shape(int img_h, int img_w, float resolution, int* rows, int* cols);
+/* Incremental ingest of a label image into a map built by tdr_k_map_from_labels (csrc/tdr_map_incr.hip): the same
+ * records (and compact form) tdr_k_map_from_labels (+ tdr_k_compact_map) would build from label_img, reached by
+ * rebuilding only the cells within R = ceil(50 / resolution) of a cell whose class changed.  Distances are truncated
+ * at 50, so every other cell keeps its record bit for bit.  Work is done on TDR_MAP_INCR_TILE^2-cell tiles.
+ *   label_img / flatten_lut: DEVICE, as for tdr_k_map_from_labels; same image shape, LUT and class count as the last
+ *     ingest of `map` (the caller checks: only the shape is checked here).
+ *   map: rec (updated in place), ncls / rows / cols / resolution, and its compact form if any (crec updated in place;
+ *     the dictionary is left as it is).
+ *   ingest_ws: the workspace of the last tdr_k_map_from_labels / tdr_k_map_update_labels of this map; it holds the class
+ *     words and column distances of the map and is updated.
+ *   dict_counts: DEVICE int32 [TDR_CMAP_WIDE_MAX_DICT], the dictionary's occurrence counts (tdr_k_map_dict_counts),
+ *     updated; needed when map->cwords != 0, NULL otherwise.
+ *   max_cells: when the affected tiles hold more cells than this (< 0: no limit), nothing is done and *n_tiles = -1:
+ *     a full ingest is cheaper then.
+ *   workspace: DEVICE tdr_map_incr_workspace_bytes(rows, cols) bytes.  tiles_out: HOST int32 [tdr_map_incr_tiles]: the
+ *     affected tiles (t = ty * ceil(cols / TILE) + tx), *n_tiles of them: the cells whose records may have changed.
+ *   *changed_cells: cells whose class word changed.  *compact_ok = 1: the compact form is current (or the class count
+ *     has none); 0: the dictionary changed (a value it lacks, or an entry no cell holds any more) or the map had no
+ *     compact form: rebuild it with tdr_k_compact_map (and tdr_k_map_dict_counts after it).
+ * Load-time work: synchronises with `stream` twice (the tile lists are formed on the host). */
+#define TDR_MAP_INCR_TILE 32
+#define TDR_MAP_INCR_MAX_FRACTION 0.5   /* tdr_map_update_labels_incremental: above this share of the map, the full path */
+int tdr_map_incr_tiles(int rows, int cols);
+size_t tdr_map_incr_workspace_bytes(int rows, int cols);
+int tdr_k_map_update_labels(const uint8_t* label_img, int img_h, int img_w, const int32_t* flatten_lut, int lut_size,
+                            tdr_map_desc* map, void* ingest_ws, int32_t* dict_counts, int64_t max_cells, void* workspace,
+                            int32_t* tiles_out, int* n_tiles, int64_t* changed_cells, int* compact_ok, void* stream);
+/* The occurrence count of every dictionary entry over the (cell, class) values of the guarded grid: counts = DEVICE int32
+ * [TDR_CMAP_WIDE_MAX_DICT], entries [0, dict_n) written.  Needs map->cwords != 0. */
+int tdr_k_map_dict_counts(const tdr_map_desc* map, int32_t* counts, void* stream);
+/* The cells of n_tiles listed tiles (DEVICE int32, as tiles_out above) in class_maps_' column-major order per tile:
+ * maps_out [n][ncls][TILE * TILE] (cell (r, c) of the tile at c * TILE + r), mask_out [n][TILE * TILE] (1 = unknown).
+ * Cells outside the map are not written. */
+int tdr_k_map_gather_tiles(const float* rec, int ncls, int rows, int cols, const int32_t* tiles, int n_tiles,
+                           float* maps_out, uint8_t* mask_out, void* stream);
 /* The same from the per-class rasters of the raster cache: planes [ncls][rows][cols] device bytes = the class<i>.png
  * images as stored (8-bit grey, row 0 = top; src/top_down_map.cpp:213-224 flips and scales them, computeDists :289-326
  * binarises: p <= 127 = inside the class, a cell is unknown where every class holds 255).  Classes may overlap.  The map
@@ -607,6 +642,21 @@ int tdr_map_set(tdr_map* m, const float* class_maps, const uint8_t* class_mask, 
  * haveMap() turns true only if the map contains road (class 1), like :150-154. */
 int tdr_map_set_labels(tdr_map* m, const uint8_t* label_img, int img_h, int img_w, const int32_t* flatten_lut,
                        int lut_size, int ncls, float resolution, int center_x, int center_y);
+/* tdr_map_set_labels' end state, byte for byte, reached by rebuilding only what the new image changes (tdr_k_map_update_labels;
+ * the host copies change in the affected tiles only).  Takes the full path (tdr_map_set_labels) itself and reports
+ * *changed_cells = -1 when the map was not last set from a label image (tdr_map_set_labels or these entries), when the
+ * image shape, resolution, class count or LUT differ, or when the affected tiles exceed TDR_MAP_INCR_MAX_FRACTION of
+ * the map; else *changed_cells = the cells whose class changed.  A host can call it for every map message. */
+int tdr_map_update_labels_incremental(tdr_map* m, const uint8_t* label_img, int img_h, int img_w,
+                                      const int32_t* flatten_lut, int lut_size, int ncls, float resolution, int center_x,
+                                      int center_y, int64_t* changed_cells);
+/* The same for the previous label image with the rectangle [y0, y0 + h) x [x0, x0 + w) of IMAGE pixels (row 0 = top)
+ * overwritten by `patch` (HOST, h x w u8, rows packed): only the rectangle is uploaded.  Needs a map last set from a
+ * label image (TDR_ERR_ARG otherwise); never takes the full path. */
+int tdr_map_patch_labels(tdr_map* m, const uint8_t* patch, int y0, int x0, int h, int w, int center_x, int center_y,
+                         int64_t* changed_cells);
+/* the map's descriptor as the scoring kernels see it (device pointers owned by the map; read-only) */
+int tdr_map_get_desc(const tdr_map* m, tdr_map_desc* out);
 int tdr_map_sample_pts_polar(tdr_map* m, int nb, int nr, float ang_res);                 /* top_down_map_polar.cpp:7-19 */
 int tdr_map_polar_shape(const tdr_map* m, int* nb, int* nr);   /* the shape of the last samplePtsPolar (0, 0 before) */
 int tdr_map_info(const tdr_map* m, int* ncls, int* rows, int* cols, float* resolution, int* have_map);
@@ -812,6 +862,14 @@ int tdr_filter_update_map(tdr_filter* f, const float* class_maps, const uint8_t*
 int tdr_filter_update_map_labels(tdr_filter* f, const uint8_t* label_img, int img_h, int img_w,
                                  const int32_t* flatten_lut, int lut_size, int ncls, float resolution, int center_x,
                                  int center_y);                                          /* :320-341, cv::Mat form */
+/* tdr_filter_update_map_labels through tdr_map_update_labels_incremental / tdr_map_patch_labels: the map is rebuilt
+ * where it changed, then the particles shift by the centre's move (or are initialised) exactly as there.  Filters that
+ * share the map may each call it: only the first call changes the map, the others find 0 changed cells. */
+int tdr_filter_update_map_labels_incremental(tdr_filter* f, const uint8_t* label_img, int img_h, int img_w,
+                                             const int32_t* flatten_lut, int lut_size, int ncls, float resolution,
+                                             int center_x, int center_y, int64_t* changed_cells);
+int tdr_filter_patch_map_labels(tdr_filter* f, const uint8_t* patch, int y0, int x0, int h, int w, int center_x,
+                                int center_y, int64_t* changed_cells);
 /* ---- adaptive particle count from a Gaussian mixture (src/particle_filter.cpp:151-157, 245-318) ---- */
 /* out (device, [num][3] floats): mlState().head<3>() = {x, y, theta} of particle min(n-1, i*n/num) (:262-266). */
 int tdr_k_sample_ml_states(const float* st, int64_t cap, int64_t n, int num, float* out, void* stream);

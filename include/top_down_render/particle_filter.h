@@ -161,6 +161,32 @@ class ParticleFilter {
     for (int r = 0; r < map.rows; r++) std::memcpy(packed.data() + (size_t)r * map.cols, map.ptr<uint8_t>(r), (size_t)map.cols);
     updateMap(packed.data(), map.rows, map.cols, lut, map_center);
   }
+  // updateMap with the map rebuilt only where the image changed (tdr_filter_update_map_labels_incremental); the
+  // particles move with the centre as in updateMap.  Returns the changed-cell count, -1 after the full path.
+  int64_t updateMapIncremental(const uint8_t* label_img, int img_h, int img_w, const std::vector<int>& flatten_lut,
+                               const Eigen::Vector2i& map_center) {
+    std::vector<int32_t> lut(flatten_lut.begin(), flatten_lut.end());
+    int64_t changed = -1;
+    check(tdr_filter_update_map_labels_incremental(f_, label_img, img_h, img_w, lut.data(), (int)lut.size(),
+                                                   map_->numClasses(), map_->resolution(), map_center[0], map_center[1],
+                                                   &changed), "updateMapIncremental");
+    return changed;
+  }
+  int64_t updateMapIncremental(const cv::Mat& map, const Eigen::Vector2i& map_center) {
+    if (map.empty()) throw std::invalid_argument("updateMapIncremental: empty image");
+    const std::vector<int>& lut = map_->params().flatten_lut;
+    if (lut.empty()) throw std::invalid_argument("updateMapIncremental: the map's Params::flatten_lut is not set");
+    if (map.isContinuous()) return updateMapIncremental(map.ptr<uint8_t>(), map.rows, map.cols, lut, map_center);
+    std::vector<uint8_t> packed((size_t)map.rows * map.cols);
+    for (int r = 0; r < map.rows; r++) std::memcpy(packed.data() + (size_t)r * map.cols, map.ptr<uint8_t>(r), (size_t)map.cols);
+    return updateMapIncremental(packed.data(), map.rows, map.cols, lut, map_center);
+  }
+  // ... for a host that knows which image rectangle changed (tdr_filter_patch_map_labels)
+  int64_t patchMap(const uint8_t* patch, int y0, int x0, int h, int w, const Eigen::Vector2i& map_center) {
+    int64_t changed = -1;
+    check(tdr_filter_patch_map_labels(f_, patch, y0, x0, h, w, map_center[0], map_center[1], &changed), "patchMap");
+    return changed;
+  }
   // visualize (call site src/top_down_render.cpp:431).  Drawing is out of scope here and this library
   // links no image library: the call hands the host a copy of the particle states, the mixture of the last computeGMM
   // and the max-likelihood state through the hook set with setVisualizer(), and does nothing when none is set.

@@ -114,6 +114,36 @@ class TopDownMap {
     for (int r = 0; r < map.rows; r++) std::memcpy(packed.data() + (size_t)r * map.cols, map.ptr<uint8_t>(r), (size_t)map.cols);
     updateMap(packed.data(), map.rows, map.cols, map_center);
   }
+  // updateMap's end state, byte for byte, reached by rebuilding only the cells a changed class can reach
+  // (tdr_map_update_labels_incremental).  Returns the number of cells whose class changed, or -1 when it took the full
+  // path (no previous label-image map, another shape / resolution / LUT, or a change over half the map).
+  int64_t updateMapIncremental(const uint8_t* label_img, int img_h, int img_w, const Eigen::Vector2i& map_center) {
+    std::vector<int32_t> lut(params_.flatten_lut.begin(), params_.flatten_lut.end());
+    if (lut.empty() || params_.num_classes < 1)
+      throw std::invalid_argument("updateMapIncremental: Params::flatten_lut / num_classes not set");
+    int64_t changed = -1;
+    if (tdr_map_update_labels_incremental(m_, label_img, img_h, img_w, lut.data(), (int)lut.size(), params_.num_classes,
+                                          params_.resolution, map_center[0], map_center[1], &changed) != TDR_OK)
+      throw std::runtime_error(std::string("TopDownMap::updateMapIncremental: ") + tdr_last_error());
+    map_center_ = map_center;
+    return changed;
+  }
+  int64_t updateMapIncremental(const cv::Mat& map, const Eigen::Vector2i& map_center) {
+    if (map.empty()) throw std::invalid_argument("updateMapIncremental: empty image");
+    if (map.isContinuous()) return updateMapIncremental(map.ptr<uint8_t>(), map.rows, map.cols, map_center);
+    std::vector<uint8_t> packed((size_t)map.rows * map.cols);
+    for (int r = 0; r < map.rows; r++) std::memcpy(packed.data() + (size_t)r * map.cols, map.ptr<uint8_t>(r), (size_t)map.cols);
+    return updateMapIncremental(packed.data(), map.rows, map.cols, map_center);
+  }
+  // The last label image with the image rectangle [y0, y0 + h) x [x0, x0 + w) (row 0 = top) overwritten by `patch`
+  // (h x w, rows packed), for a host that knows what changed (tdr_map_patch_labels).  Returns the changed-cell count.
+  int64_t patchMap(const uint8_t* patch, int y0, int x0, int h, int w, const Eigen::Vector2i& map_center) {
+    int64_t changed = -1;
+    if (tdr_map_patch_labels(m_, patch, y0, x0, h, w, map_center[0], map_center[1], &changed) != TDR_OK)
+      throw std::runtime_error(std::string("TopDownMap::patchMap: ") + tdr_last_error());
+    map_center_ = map_center;
+    return changed;
+  }
   // The constructor's colour-map branch (:32-42, 48-63) for a BGR image the caller decoded (cv::imread's layout: 3 bytes
   // B, G, R per pixel, row 0 = top), e.g. a .jpg map: color2Ind against params_.color_lut, loadCompressedRasterMap,
   // geometric layers and distance maps on the GPU; haveMap() turns true even without road (:63).

@@ -121,6 +121,11 @@ class TopDownRenderCore {
   }
   // aerialMapCallback's effect on the hot-path classes (:574-593)
   void aerialMap(const cv::Mat& map_img, const Eigen::Vector2i& map_center) { filter_->updateMap(map_img, map_center); }
+  // ... with the map rebuilt only where the new message differs from the last (ParticleFilter::updateMapIncremental): the
+  // same end state; returns the changed-cell count, -1 after the full path
+  int64_t aerialMapIncremental(const cv::Mat& map_img, const Eigen::Vector2i& map_center) {
+    return filter_->updateMapIncremental(map_img, map_center);
+  }
 
   // the plane projection of a 3-D motion prior (updateFilter, :418-420): R row-major 3 x 3, t the translation
   static void projectPrior(const float R[9], const float t[3], Eigen::Vector2f& trans, float& yaw) {

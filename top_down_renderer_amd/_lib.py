@@ -87,6 +87,12 @@ SIGNATURES = {
     "tdr_map_ingest_shape": (_i, [_i, _i, _f, C.POINTER(_i), C.POINTER(_i)]),
     "tdr_k_map_from_labels": (_i, [_vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp]),
     "tdr_k_map_from_rasters": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "tdr_map_incr_tiles": (_i, [_i, _i]),
+    "tdr_map_incr_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "tdr_k_map_update_labels": (_i, [_vp, _i, _i, _vp, _i, C.POINTER(MapDescC), _vp, _vp, _i64, _vp, _vp,
+                                     C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i), _vp]),
+    "tdr_k_map_dict_counts": (_i, [C.POINTER(MapDescC), _vp, _vp]),
+    "tdr_k_map_gather_tiles": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "tdr_map_save_rasters": (_i, [_vp, C.c_char_p]),
     "tdr_png_read_gray8_host": (_i, [C.c_char_p, _vp, _i64, _vp, _vp]),
     "tdr_png_write_gray8_host": (_i, [C.c_char_p, _vp, _i, _i]),
@@ -199,6 +205,11 @@ SIGNATURES = {
     "tdr_map_set": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _i]),
     "tdr_map_set_labels": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _i, _i]),
     "tdr_filter_update_map_labels": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _i, _i]),
+    "tdr_map_update_labels_incremental": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _i, _i, C.POINTER(_i64)]),
+    "tdr_map_patch_labels": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i64)]),
+    "tdr_map_get_desc": (_i, [_vp, C.POINTER(MapDescC)]),
+    "tdr_filter_update_map_labels_incremental": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _i, _i, C.POINTER(_i64)]),
+    "tdr_filter_patch_map_labels": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i64)]),
     "tdr_map_sample_pts_polar": (_i, [_vp, _i, _i, _f]),
     "tdr_map_polar_shape": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "tdr_map_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_f), C.POINTER(_i)]),

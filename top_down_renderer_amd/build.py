@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 SRC = [os.path.join(PKG, "csrc", f) for f in
        ("tdr_core.hip", "tdr_map.hip", "tdr_raster.hip", "tdr_score.hip", "tdr_score_su.hip", "tdr_score_ray.hip", "tdr_score_cart.hip", "tdr_filter.hip", "tdr_rng.hip", "tdr_prefix.hip",
-        "tdr_geo.hip", "tdr_cmap.hip", "tdr_active.hip", "tdr_poly.hip", "tdr_batch.hip", "tdr_batch_loop.hip", "tdr_init.hip", "tdr_host.cpp", "tdr_comm.cpp", "tdr_gmm.cpp", "tdr_png.cpp",
+        "tdr_geo.hip", "tdr_cmap.hip", "tdr_active.hip", "tdr_poly.hip", "tdr_batch.hip", "tdr_batch_loop.hip", "tdr_init.hip", "tdr_map_incr.hip", "tdr_host.cpp", "tdr_comm.cpp", "tdr_gmm.cpp", "tdr_png.cpp",
         "tdr_svg.cpp")]
 HDR = [os.path.join(ROOT, "include", "tdr.h")] + \
       [os.path.join(PKG, "csrc", f) for f in ("tdr_common.h", "tdr_sincosf.h", "tdr_atan2f.h", "tdr_score_su.h", "tdr_score_dev.h", "tdr_score_su_asm.h", "tdr_score_cart.h", "tdr_score_cart_asm.h", "tdr_logf.h", "tdr_mt_jump.h", "tdr_batch.h")]

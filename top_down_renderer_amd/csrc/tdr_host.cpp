@@ -98,6 +98,19 @@ struct tdr_map {
   DevBuf<uint8_t> ing_img, ing_ws, ing_mask;
   DevBuf<int32_t> ing_lut;
   DevBuf<float> ing_maps;
+  // incremental updates (tdr_map_update_labels_incremental, csrc/tdr_map_incr.hip).  inc_valid: the map was last set from
+  // a label image (tdr_map_set_labels or an incremental update) and ing_img / ing_lut / ing_ws still hold that image, its
+  // LUT (inc_lut) and the ingest's class words and column distances.  inc_counts: the dictionary's occurrence counts
+  // (tdr_k_map_dict_counts), current while inc_counts_ok; every full compaction clears it.
+  bool inc_valid = false, inc_counts_ok = false;
+  int inc_img_h = 0, inc_img_w = 0;
+  std::vector<int32_t> inc_lut;
+  DevBuf<uint8_t> inc_ws, inc_mstage;
+  DevBuf<int32_t> inc_counts, inc_dtiles;
+  DevBuf<float> inc_stage;
+  std::vector<int32_t> inc_tiles;
+  std::vector<float> inc_hstage;
+  std::vector<uint8_t> inc_hmstage;
 };
 
 struct tdr_renderer {
@@ -262,6 +275,7 @@ static int map_ensure_geo(tdr_map* m) {
 
 // the compact records of a freshly packed map (desc.rec etc. already set)
 static int map_compact(tdr_map* m) {
+  m->inc_counts_ok = false;   // the dictionary is built anew
   m->desc.crec = nullptr; m->desc.dict = nullptr; m->desc.dict_n = 0; m->desc.cwords = 0;
   m->desc.rec16 = nullptr;   // sized for the previous grid: the next large init search allocates it again
   const size_t nw = tdr_cmap_words_total(m->desc.ncls, m->desc.rows, m->desc.cols);
@@ -297,6 +311,7 @@ int tdr_map_set(tdr_map* m, const float* class_maps, const uint8_t* class_mask, 
   if (!m || !class_maps || !class_mask) return failh(TDR_ERR_ARG, "map_set: null pointer");
   if (ncls < 1 || ncls > TDR_MAX_CLASSES || rows < 1 || cols < 1 || !(resolution > 0))
     return failh(TDR_ERR_ARG, "map_set: bad shape / resolution");
+  m->inc_valid = false;
   const size_t ncell = (size_t)rows * cols;
   DevBuf<float> d_maps;
   DevBuf<uint8_t> d_mask;
@@ -332,6 +347,7 @@ int tdr_map_set_labels(tdr_map* m, const uint8_t* label_img, int img_h, int img_
   int rows = 0, cols = 0;
   TTRY(tdr_map_ingest_shape(img_h, img_w, resolution, &rows, &cols));
   if (ncls < 1 || ncls > TDR_MAX_CLASSES || rows < 1 || cols < 1) return failh(TDR_ERR_ARG, "map_set_labels: bad shape");
+  m->inc_valid = false;
   DevBuf<uint8_t>&d_img = m->ing_img, &d_ws = m->ing_ws, &d_mask = m->ing_mask;
   DevBuf<int32_t>& d_lut = m->ing_lut;
   DevBuf<float>& d_maps = m->ing_maps;
@@ -366,7 +382,120 @@ int tdr_map_set_labels(tdr_map* m, const uint8_t* label_img, int img_h, int img_
   if (ncls > 1)
     for (size_t k = 0; k < ncell && !road; k++) road = m->maps_host[ncell + k] != 0.f;
   if (road) m->have_map = true;
+  m->inc_valid = true;   // ing_img / ing_lut / ing_ws now describe this map (tdr_map_update_labels_incremental)
+  m->inc_img_h = img_h;
+  m->inc_img_w = img_w;
+  m->inc_lut.assign(flatten_lut, flatten_lut + lut_size);
   if (m->nb > 0 && m->have_map) return tdr_map_sample_pts_polar(m, m->nb, m->nr, m->ang_res);
+  return TDR_OK;
+}
+
+// The incremental update of a map whose ing_img now holds the new image (same shape, resolution, classes and LUT as the
+// label image the map was last set from): tdr_k_map_update_labels rebuilds the cells within R of a changed cell, the host
+// copies change in the affected tiles only.  *too_large: more than max_cells cells would be rebuilt (max_cells < 0: no
+// limit); nothing has changed then and the caller takes the full path.
+static int map_apply_incremental(tdr_map* m, int center_x, int center_y, int64_t max_cells, int64_t* changed,
+                                 bool* too_large) {
+  const int ncls = m->desc.ncls, rows = m->desc.rows, cols = m->desc.cols;
+  const size_t ncell = (size_t)rows * cols;
+  *too_large = false;
+  TTRY(m->inc_ws.resize(tdr_map_incr_workspace_bytes(rows, cols)));
+  m->inc_tiles.resize((size_t)tdr_map_incr_tiles(rows, cols));
+  if (m->desc.cwords && !m->inc_counts_ok) {
+    TTRY(m->inc_counts.resize(TDR_CMAP_WIDE_MAX_DICT));
+    TTRY(tdr_k_map_dict_counts(&m->desc, m->inc_counts.p, nullptr));
+    m->inc_counts_ok = true;
+  }
+  m->inc_valid = false;   // until the update is through
+  int n_tiles = 0, compact_ok = 0;
+  TTRY(tdr_k_map_update_labels(m->ing_img.p, m->inc_img_h, m->inc_img_w, m->ing_lut.p, (int)m->inc_lut.size(), &m->desc,
+                               m->ing_ws.p, m->desc.cwords ? m->inc_counts.p : nullptr, max_cells, m->inc_ws.p,
+                               m->inc_tiles.data(), &n_tiles, changed, &compact_ok, nullptr));
+  if (n_tiles < 0) {
+    *too_large = true;
+    return TDR_OK;
+  }
+  if (!compact_ok) TTRY(map_compact(m));   // the dictionary changes (or the map may gain a compact form): build it whole
+  else m->desc.rec16 = nullptr;            // as map_compact drops it
+  // host copies of the affected tiles; `have_map` (sticky, tdr_map_set_labels): while false, class 1 of the previous map
+  // was zero everywhere, so only the affected cells can hold road now
+  bool road = false;
+  if (n_tiles > 0) {
+    const size_t tc = (size_t)TDR_MAP_INCR_TILE * TDR_MAP_INCR_TILE;
+    TTRY(m->inc_dtiles.resize((size_t)n_tiles));
+    TTRY(m->inc_stage.resize((size_t)n_tiles * ncls * tc));
+    TTRY(m->inc_mstage.resize((size_t)n_tiles * tc));
+    HTRY(hipMemcpy(m->inc_dtiles.p, m->inc_tiles.data(), (size_t)n_tiles * sizeof(int32_t), hipMemcpyHostToDevice));
+    TTRY(tdr_k_map_gather_tiles(m->rec.p, ncls, rows, cols, m->inc_dtiles.p, n_tiles, m->inc_stage.p, m->inc_mstage.p,
+                                nullptr));
+    m->inc_hstage.resize((size_t)n_tiles * ncls * tc);
+    m->inc_hmstage.resize((size_t)n_tiles * tc);
+    HTRY(hipMemcpy(m->inc_hstage.data(), m->inc_stage.p, m->inc_hstage.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HTRY(hipMemcpy(m->inc_hmstage.data(), m->inc_mstage.p, m->inc_hmstage.size(), hipMemcpyDeviceToHost));
+    const int T = TDR_MAP_INCR_TILE, tx_n = (cols + T - 1) / T;
+    for (int b = 0; b < n_tiles; b++) {
+      const int t = m->inc_tiles[(size_t)b], ty = t / tx_n, tx = t - ty * tx_n;
+      const int r0 = ty * T, nr = std::min(T, rows - r0);
+      for (int cl = 0; cl < T && tx * T + cl < cols; cl++) {
+        const size_t dst = (size_t)(tx * T + cl) * rows + r0;   // column-major: the tile's column is nr floats in a row
+        for (int k = 0; k < ncls; k++)
+          std::memcpy(m->maps_host.data() + (size_t)k * ncell + dst, m->inc_hstage.data() + ((size_t)b * ncls + k) * tc + (size_t)cl * T,
+                      (size_t)nr * sizeof(float));
+        std::memcpy(m->mask_host.data() + dst, m->inc_hmstage.data() + (size_t)b * tc + (size_t)cl * T, (size_t)nr);
+        if (!m->have_map && ncls > 1)
+          for (int r = 0; r < nr && !road; r++) road = m->maps_host[ncell + dst + r] != 0.f;
+      }
+    }
+  }
+  const bool had_map = m->have_map;
+  if (road) m->have_map = true;
+  m->center_x = center_x;
+  m->center_y = center_y;
+  m->inc_valid = true;
+  // the polar table depends on the shape and the resolution alone: built already unless this update brought the first map
+  if (m->nb > 0 && m->have_map && !had_map) return tdr_map_sample_pts_polar(m, m->nb, m->nr, m->ang_res);
+  return TDR_OK;
+}
+
+// tdr_map_set_labels' end state, reached by rebuilding only what the new image changes (tdr_map_incr.hip)
+int tdr_map_update_labels_incremental(tdr_map* m, const uint8_t* label_img, int img_h, int img_w,
+                                      const int32_t* flatten_lut, int lut_size, int ncls, float resolution, int center_x,
+                                      int center_y, int64_t* changed_cells) {
+  if (!m || !label_img || !flatten_lut || !changed_cells)
+    return failh(TDR_ERR_ARG, "map_update_labels_incremental: null pointer");
+  *changed_cells = -1;
+  const bool same = m->inc_valid && img_h == m->inc_img_h && img_w == m->inc_img_w && ncls == m->desc.ncls &&
+                    resolution == m->desc.resolution && lut_size == (int)m->inc_lut.size() &&
+                    std::equal(m->inc_lut.begin(), m->inc_lut.end(), flatten_lut);
+  if (!same) return tdr_map_set_labels(m, label_img, img_h, img_w, flatten_lut, lut_size, ncls, resolution, center_x, center_y);
+  HTRY(hipMemcpy(m->ing_img.p, label_img, (size_t)img_h * img_w, hipMemcpyHostToDevice));
+  int64_t changed = 0;
+  bool too_large = false;
+  TTRY(map_apply_incremental(m, center_x, center_y, (int64_t)((double)m->desc.rows * m->desc.cols * TDR_MAP_INCR_MAX_FRACTION),
+                             &changed, &too_large));
+  if (too_large) return tdr_map_set_labels(m, label_img, img_h, img_w, flatten_lut, lut_size, ncls, resolution, center_x, center_y);
+  *changed_cells = changed;
+  return TDR_OK;
+}
+
+// the image of the last label-image map with one rectangle overwritten: only the rectangle is uploaded
+int tdr_map_patch_labels(tdr_map* m, const uint8_t* patch, int y0, int x0, int h, int w, int center_x, int center_y,
+                         int64_t* changed_cells) {
+  if (!m || !patch || !changed_cells) return failh(TDR_ERR_ARG, "map_patch_labels: null pointer");
+  if (!m->inc_valid)
+    return failh(TDR_ERR_ARG, "map_patch_labels: the map was not last set from a label image (tdr_map_set_labels)");
+  if (h < 1 || w < 1 || y0 < 0 || x0 < 0 || (int64_t)y0 + h > m->inc_img_h || (int64_t)x0 + w > m->inc_img_w)
+    return failh(TDR_ERR_ARG, "map_patch_labels: rectangle (%d, %d) + %d x %d lies outside the %d x %d image", x0, y0, w, h,
+                 m->inc_img_w, m->inc_img_h);
+  HTRY(hipMemcpy2D(m->ing_img.p + (size_t)y0 * m->inc_img_w + x0, (size_t)m->inc_img_w, patch, (size_t)w, (size_t)w,
+                   (size_t)h, hipMemcpyHostToDevice));
+  bool too_large = false;
+  return map_apply_incremental(m, center_x, center_y, -1, changed_cells, &too_large);
+}
+
+int tdr_map_get_desc(const tdr_map* m, tdr_map_desc* out) {
+  if (!m || !out) return failh(TDR_ERR_ARG, "map_get_desc: null pointer");
+  *out = m->desc;
   return TDR_OK;
 }
 
@@ -636,6 +765,7 @@ static int map_load_rasters(tdr_map* m, const char* dir, int num_classes, float 
 // what the constructor does with the class rasters of a static map (:48-58), from DEVICE planes in the class<i>.png layout
 static int map_set_from_rasters(tdr_map* m, const uint8_t* d_planes, int num_classes, int rows, int cols,
                                 float resolution, int center_x, int center_y) {
+  m->inc_valid = false;
   DevBuf<uint8_t> d_ws;
   TTRY(d_ws.resize(tdr_map_ingest_workspace_bytes(num_classes, rows, cols)));
   TTRY(m->rec.resize(tdr_map_rec_floats_total(num_classes, rows, cols)));
@@ -645,6 +775,7 @@ static int map_set_from_rasters(tdr_map* m, const uint8_t* d_planes, int num_cla
 // the rest of the constructor for a static map whose cell records m->rec now hold (:48-63): host copies of class_maps_ /
 // class_mask_, compact records, geometric layers derived from the classes, have_map_ = true
 static int map_adopt_static(tdr_map* m, int num_classes, int rows, int cols, float resolution, int center_x, int center_y) {
+  m->inc_valid = false;
   const size_t ncell = (size_t)rows * cols;
   DevBuf<uint8_t> d_mask;
   DevBuf<float> d_maps;
@@ -839,6 +970,7 @@ static int map_load_color(tdr_map* m, const uint8_t* bgr, int img_h, int img_w, 
                           const int32_t* flatten_lut, int lut_size, int num_classes, float resolution, int center_x,
                           int center_y) {
   int rows = 0, cols = 0;
+  m->inc_valid = false;
   TTRY(tdr_map_ingest_shape(img_h, img_w, resolution, &rows, &cols));
   const size_t nbytes = (size_t)img_h * img_w * 3;
   DevBuf<uint8_t> d_img, d_ws;
@@ -1535,6 +1667,31 @@ int tdr_filter_update_map_labels(tdr_filter* f, const uint8_t* label_img, int im
   if (!f || !f->map) return failh(TDR_ERR_ARG, "filter_update_map_labels: null filter");
   const int ox = f->map->center_x, oy = f->map->center_y;
   TTRY(tdr_map_set_labels(f->map, label_img, img_h, img_w, flatten_lut, lut_size, ncls, resolution, center_x, center_y));
+  f->states_changed();
+  if (f->n > 0) return tdr_k_shift_init(f->st.p, f->cap, f->nl(), (float)(center_x - ox), (float)(center_y - oy), f->stream);
+  if (f->map->have_map) return tdr_filter_initialize_particles(f);  // :337-340
+  return TDR_OK;
+}
+
+// tdr_filter_update_map_labels through the incremental map update (tdr_map_update_labels_incremental)
+int tdr_filter_update_map_labels_incremental(tdr_filter* f, const uint8_t* label_img, int img_h, int img_w,
+                                             const int32_t* flatten_lut, int lut_size, int ncls, float resolution,
+                                             int center_x, int center_y, int64_t* changed_cells) {
+  if (!f || !f->map) return failh(TDR_ERR_ARG, "filter_update_map_labels_incremental: null filter");
+  const int ox = f->map->center_x, oy = f->map->center_y;
+  TTRY(tdr_map_update_labels_incremental(f->map, label_img, img_h, img_w, flatten_lut, lut_size, ncls, resolution, center_x,
+                                         center_y, changed_cells));
+  f->states_changed();
+  if (f->n > 0) return tdr_k_shift_init(f->st.p, f->cap, f->nl(), (float)(center_x - ox), (float)(center_y - oy), f->stream);
+  if (f->map->have_map) return tdr_filter_initialize_particles(f);  // :337-340
+  return TDR_OK;
+}
+// ... and through tdr_map_patch_labels
+int tdr_filter_patch_map_labels(tdr_filter* f, const uint8_t* patch, int y0, int x0, int h, int w, int center_x,
+                                int center_y, int64_t* changed_cells) {
+  if (!f || !f->map) return failh(TDR_ERR_ARG, "filter_patch_map_labels: null filter");
+  const int ox = f->map->center_x, oy = f->map->center_y;
+  TTRY(tdr_map_patch_labels(f->map, patch, y0, x0, h, w, center_x, center_y, changed_cells));
   f->states_changed();
   if (f->n > 0) return tdr_k_shift_init(f->st.p, f->cap, f->nl(), (float)(center_x - ox), (float)(center_y - oy), f->stream);
   if (f->map->have_map) return tdr_filter_initialize_particles(f);  // :337-340

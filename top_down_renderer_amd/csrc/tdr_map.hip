@@ -1,5 +1,6 @@
 // tdr_map.hip — map cell records (pack / unpack), map ingest from a label or colour image, the polar sample table.
 #include "tdr_common.h"
+#include "tdr_ingest_dev.h"
 
 #include <algorithm>
 
@@ -52,28 +53,15 @@ extern "C" int tdr_k_pack_map(const float* class_maps, const uint8_t* class_mask
 // DIST_MASK_PRECISE): squared Euclidean distances are integers, minimised exactly; because distances are truncated at
 // 50 (:315) only cells within R = ceil(50/resolution) matter, so both separable passes are windowed brute force —
 // every cell independent, integer arithmetic, one correctly rounded sqrtf at the end.
-// Per cell the ingest keeps a word of class bits: bit c = the cell lies inside class c; bit 31 = no known class (mask = 1).
-// A label image gives one bit per cell; the per-class rasters of the raster cache may overlap.
-#define INGEST_MAXC 16
-#define INGEST_UNKNOWN 0x80000000u
-// the image pixel cell (yi, xi) reads (:137-138) — row 0 of the map is the bottom row of the image
-__device__ inline int64_t ingest_pixel(int yi, int xi, int img_h, int img_w, float resolution) {
-  int iy = (int)((float)img_h - (float)yi * resolution - 1.f);
-  iy = iy > 0 ? iy : 0;
-  int ix = (int)((float)xi * resolution);
-  ix = ix < img_w - 1 ? ix : img_w - 1;
-  return (int64_t)iy * img_w + ix;
-}
+// The per-cell bodies (class word, column pass, row pass) live in tdr_ingest_dev.h, shared with the incremental update
+// (tdr_map_incr.hip).
 __global__ void ingest_labels_kernel(const uint8_t* __restrict__ img, int img_h, int img_w,
                                      const int32_t* __restrict__ lut, int lut_size, int ncls, int rows, int cols,
                                      float resolution, uint32_t* __restrict__ cls_map) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)rows * cols) return;
   const int yi = (int)(idx / cols), xi = (int)(idx % cols);
-  const int label = img[ingest_pixel(yi, xi, img_h, img_w, resolution)];
-  int c = label < lut_size ? lut[label] : -1;
-  if (c < 0 || c >= ncls) c = -1;  // :139
-  cls_map[idx] = c < 0 ? INGEST_UNKNOWN : (1u << c);
+  cls_map[idx] = ingest_label_word(img, img_h, img_w, lut, lut_size, ncls, yi, xi, resolution);
 }
 // TopDownMap::loadRasterizedMaps (src/top_down_map.cpp:213-224) + the first lines of computeDists (:293-305): planes
 // [ncls][h][w] are the class<i>.png images as stored (8-bit grey, row 0 = top); the loader flips them back (:217), scales by
@@ -100,22 +88,7 @@ __global__ void ingest_coldist_kernel(const uint32_t* __restrict__ cls_map, int 
                                       uint8_t* __restrict__ g /* [rows*cols][INGEST_MAXC] */) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)rows * cols) return;
-  const int y = (int)(idx / cols), x = (int)(idx % cols);
-  int gd[INGEST_MAXC];
-#pragma unroll
-  for (int c = 0; c < INGEST_MAXC; c++) gd[c] = 255;
-  for (int d = 0; d <= R; d++) {
-    const int ya = y - d, yb = y + d;
-    const uint32_t ca = ya >= 0 ? cls_map[(int64_t)ya * cols + x] : 0u;
-    const uint32_t cb = yb < rows ? cls_map[(int64_t)yb * cols + x] : 0u;
-    const uint32_t either = ca | cb;
-#pragma unroll
-    for (int c = 0; c < INGEST_MAXC; c++)
-      if (((either >> c) & 1u) && gd[c] == 255) gd[c] = d;
-  }
-  uint8_t* o = g + idx * INGEST_MAXC;
-#pragma unroll
-  for (int c = 0; c < INGEST_MAXC; c++) o[c] = (uint8_t)gd[c];
+  ingest_coldist_cell(cls_map, rows, cols, R, (int)(idx / cols), (int)(idx % cols), g);
   (void)ncls;
 }
 
@@ -125,33 +98,12 @@ __global__ void ingest_rowmin_kernel(const uint32_t* __restrict__ cls_map, const
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)rows * cols) return;
   const int y = (int)(idx / cols), x = (int)(idx % cols);
-  int best[INGEST_MAXC];
-#pragma unroll
-  for (int c = 0; c < INGEST_MAXC; c++) best[c] = 0x7fffffff;
-  const int x0 = x - R > 0 ? x - R : 0, x1 = x + R < cols - 1 ? x + R : cols - 1;
-  for (int xx = x0; xx <= x1; xx++) {
-    const int dx2 = (xx - x) * (xx - x);
-    const uint4 gv = *reinterpret_cast<const uint4*>(g + ((int64_t)y * cols + xx) * INGEST_MAXC);
-    const unsigned wv[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-    for (int c = 0; c < INGEST_MAXC; c++) {
-      const int gd = (int)((wv[c >> 2] >> (8 * (c & 3))) & 0xFF);
-      const int cand = gd == 255 ? 0x7fffffff : dx2 + gd * gd;
-      best[c] = cand < best[c] ? cand : best[c];
-    }
-  }
-  const bool unknown = (cls_map[idx] & INGEST_UNKNOWN) != 0;  // no class at this cell (:294-299): mask = 1, distances zeroed (:317)
+  float d[INGEST_MAXC];
+  const float known = ingest_rowmin_cell(cls_map, g, ncls, cols, R, resolution, y, x, d);
   float* o = rec + ((int64_t)(y + 1) * (cols + 2) + (x + 1)) * rf;
 #pragma unroll
-  for (int c = 0; c < INGEST_MAXC; c++) {
-    if (c < ncls) {
-      float d = best[c] == 0x7fffffff ? 3.0e38f : sqrtf((float)best[c]);  // cv::distanceTransform, precise L2
-      d = d * resolution;                                                   // :314
-      d = d > 50.f ? 50.f : d;                                              // :315 THRESH_TRUNC
-      o[c] = unknown ? 0.f : d;
-    }
-  }
-  const float known = unknown ? 0.f : 1.f;
+  for (int c = 0; c < INGEST_MAXC; c++)
+    if (c < ncls) o[c] = d[c];
   o[rf - 1] = known;
   if (tdr_has_kslot(ncls, rf)) o[rf - 2] = known;
 }

@@ -92,6 +92,15 @@ class RngPipe:
             pass
 
 
+class IngestState:
+    """What make_map_from_labels(keep_ingest=True) keeps for incremental updates: the device image and LUT, the host LUT,
+    the ingest workspace (class words + column distances), the image shape, the class count and the resolution."""
+
+    def __init__(self, img, lut_d, lut, ws, shape, ncls, resolution):
+        self.img, self.lut_d, self.lut, self.ws = img, lut_d, lut, ws
+        self.shape, self.ncls, self.resolution = tuple(shape), int(ncls), float(resolution)
+
+
 class DeviceMap:
     """Device-resident interleaved map (tdr_map_desc) + the polar sampling table."""
 
@@ -107,6 +116,10 @@ class DeviceMap:
         self.crec = self.dict = None   # compact form of the records (tdr_k_compact_map), when the map has one
         self.rec16 = None              # scratch of the 40-rotation search (tdr_map_desc.rec16), allocated on first use
         self.use_rec16 = True          # False: the search splits the f32 records on the fly (A/B, tests)
+        self.ingest = None             # IngestState of a label-image map kept for incremental updates
+        self.counts = None             # the dictionary's occurrence counts (tdr_k_map_dict_counts), current if counts_ok
+        self.counts_ok = False
+        self.incr_ws = None
 
     def init_scratch(self, kernels):
         """Gives the descriptor the scratch the matrix-core init search writes its pre-split f16 records to."""
@@ -245,9 +258,10 @@ class HipKernels:
         m.compact(self)
         return m
 
-    def make_map_from_labels(self, label_img, flatten_lut, ncls, resolution):
+    def make_map_from_labels(self, label_img, flatten_lut, ncls, resolution, keep_ingest=False):
         """label_img: (img_h, img_w) uint8 class-index image (cv::Mat layout, row 0 = top).  Runs
-        loadCompressedRasterMap + computeDists on the device (tdr_k_map_from_labels)."""
+        loadCompressedRasterMap + computeDists on the device (tdr_k_map_from_labels).  keep_ingest: the map keeps the
+        image, the LUT and the ingest workspace (class words, column distances) for update_map_from_labels."""
         label_img = np.ascontiguousarray(label_img, np.uint8)
         img_h, img_w = label_img.shape
         rows, cols = C.c_int(0), C.c_int(0)
@@ -262,7 +276,53 @@ class HipKernels:
         self.synchronize()
         m = DeviceMap(rec, ncls, rows, cols, resolution)
         m.compact(self)
+        if keep_ingest:
+            m.ingest = IngestState(img_d, lut_d, lut, ws, (img_h, img_w), ncls, float(resolution))
         return m
+
+    def update_map_from_labels(self, m, label_img, max_cells=-1):
+        """The incremental ingest (tdr_k_map_update_labels) of a new label image into a DeviceMap built by
+        make_map_from_labels(keep_ingest=True) from an image of the same shape, LUT and class count: only the cells
+        within R = ceil(50 / resolution) of a changed cell are rebuilt; the compact form is refreshed in place, or built
+        anew when its dictionary changes.  Returns (changed_cells, affected tiles) — None, with nothing changed, when the
+        affected tiles hold more than max_cells cells (>= 0)."""
+        ing, lib = m.ingest, self.lib
+        label_img = np.ascontiguousarray(label_img, np.uint8)
+        if label_img.shape != ing.shape:
+            raise ValueError("update_map_from_labels: the image shape differs from the map's last image")
+        ing.img.copy_(torch.from_numpy(label_img))
+        if m.desc.cwords and not m.counts_ok:
+            if m.counts is None:
+                m.counts = self.empty((4096,), torch.int32)   # TDR_CMAP_WIDE_MAX_DICT
+            check(lib.tdr_k_map_dict_counts(C.byref(m.desc), _ptr(m.counts), self.stream()))
+            m.counts_ok = True
+        if m.incr_ws is None:
+            m.incr_ws = self.empty((int(lib.tdr_map_incr_workspace_bytes(m.rows, m.cols)),), torch.uint8)
+        tiles = np.zeros(max(1, int(lib.tdr_map_incr_tiles(m.rows, m.cols))), np.int32)
+        n_tiles, changed, compact_ok = C.c_int(0), C.c_int64(0), C.c_int(0)
+        check(lib.tdr_k_map_update_labels(_ptr(ing.img), ing.shape[0], ing.shape[1], _ptr(ing.lut_d), len(ing.lut),
+                                          C.byref(m.desc), _ptr(ing.ws), _ptr(m.counts) if m.desc.cwords else None,
+                                          int(max_cells), _ptr(m.incr_ws), tiles.ctypes.data_as(C.c_void_p),
+                                          C.byref(n_tiles), C.byref(changed), C.byref(compact_ok), self.stream()))
+        if n_tiles.value < 0:
+            return None
+        if not compact_ok.value:
+            m.counts_ok = False
+            m.compact(self)
+        return changed.value, tiles[:n_tiles.value].copy()
+
+    def gather_tiles(self, m, tiles):
+        """The cells of the listed tiles (tdr_k_map_gather_tiles): (n, ncls, T, T) float32 indexed [tile, class, column,
+        row] like class_maps_, and (n, T, T) uint8 masks (1 = unknown), T = TDR_MAP_INCR_TILE."""
+        T = 32
+        n = len(tiles)
+        maps = self.zeros((max(n, 1), m.ncls, T, T))
+        mask = self.zeros((max(n, 1), T, T), torch.uint8)
+        if n:
+            t_d = self.to_device(np.ascontiguousarray(tiles, np.int32))
+            check(self.lib.tdr_k_map_gather_tiles(_ptr(m.rec), m.ncls, m.rows, m.cols, _ptr(t_d), n, _ptr(maps), _ptr(mask),
+                                                  self.stream()))
+        return maps[:n].cpu().numpy(), mask[:n].cpu().numpy()
 
     def make_map_from_rasters(self, planes, resolution):
         """planes: (ncls, rows, cols) uint8, the class<i>.png images of a raster cache as stored (row 0 = top).  Runs

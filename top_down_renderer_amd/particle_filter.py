@@ -478,6 +478,19 @@ class ParticleFilter:
     def numParticles(self):
         return self.num_particles_
 
+    def updateMapIncremental(self, label_img, map_center=(0, 0)):
+        """updateMap(label_img, map_center) with the map rebuilt only where the image changed
+        (TopDownMap.updateMapIncremental); the particles move with the centre as in updateMap.  Returns the changed-cell
+        count, -1 after the full path."""
+        old = self.map_.mapCenter()
+        changed = self.map_.updateMapIncremental(label_img, map_center)
+        self.fp_c = self.params_.to_c(self.map_.numClasses())
+        if self.num_particles_ > 0:
+            self.k.shift_init(self.st, self.n_local, float(map_center[0] - old[0]), float(map_center[1] - old[1]))
+        else:
+            self.initializeParticles()
+        return changed
+
     def updateMap(self, class_maps, class_mask=None, map_center=(0, 0)):
         """particle_filter.cpp:320-341.  updateMap(label_img, map_center) like the reference (class-index image, the
         distance transform runs on the GPU), or updateMap(class_maps, class_mask, map_center) with ready distance maps."""

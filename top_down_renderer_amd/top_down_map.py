@@ -132,6 +132,50 @@ class TopDownMap:
         if old is not None and getattr(old, "nb", 0):
             self.k.set_polar_table(self.dev, old.nb, old.nr, old.ang_res)
 
+    def updateMapIncremental(self, label_img, map_center=(0, 0)):
+        """loadCompressedRasterMap's end state, reached by rebuilding only what changed since the last image
+        (kernels.update_map_from_labels, csrc/tdr_map_incr.hip).  Returns the number of cells whose class changed, or -1
+        when it took the full path: no label image kept from an earlier call, a different shape / LUT / class count /
+        resolution, or a change over more than half the map."""
+        p = self.params_
+        if not p.num_classes or not len(p.flatten_lut):
+            raise ValueError("Params.num_classes and Params.flatten_lut are needed to ingest a label image")
+        label_img = np.ascontiguousarray(label_img, np.uint8)
+        lut = np.ascontiguousarray(p.flatten_lut, np.int32).ravel()
+        dev = self.dev
+        ing = getattr(dev, "ingest", None)
+        res = None
+        if (ing is not None and ing.shape == label_img.shape and ing.ncls == p.num_classes
+                and ing.resolution == float(p.resolution) and np.array_equal(ing.lut, lut)):
+            res = self.k.update_map_from_labels(dev, label_img, max_cells=int(dev.rows * dev.cols * 0.5))
+        if res is None:   # the full path, keeping what the next call needs
+            old = self.dev
+            self.geo_constant_one_ = True
+            self.dev = self.k.make_map_from_labels(label_img, p.flatten_lut, p.num_classes, p.resolution,
+                                                   keep_ingest=True)
+            self.rows, self.cols = self.dev.rows, self.dev.cols
+            maps_cm, _ = self.k.unpack_map(self.dev)
+            self.maps_cm_host = maps_cm
+            self.map_center_ = (int(map_center[0]), int(map_center[1]))
+            if p.num_classes > 1 and bool((self.maps_cm_host[1] != 0).any()):
+                self.have_map_ = True
+            if old is not None and getattr(old, "nb", 0):
+                self.k.set_polar_table(self.dev, old.nb, old.nr, old.ang_res)
+            return -1
+        changed, tiles = res
+        if len(tiles):   # the host copy changes in the affected tiles only
+            maps_t, _ = self.k.gather_tiles(dev, tiles)
+            tx_n = (dev.cols + 31) // 32
+            for b, t in enumerate(tiles):
+                ty, tx = divmod(int(t), tx_n)
+                r0, c0 = ty * 32, tx * 32
+                nr, nc = min(32, dev.rows - r0), min(32, dev.cols - c0)
+                self.maps_cm_host[:, c0:c0 + nc, r0:r0 + nr] = maps_t[b, :, :nc, :nr]
+                if not self.have_map_ and p.num_classes > 1 and bool((maps_t[b, 1, :nc, :nr] != 0).any()):
+                    self.have_map_ = True
+        self.map_center_ = (int(map_center[0]), int(map_center[1]))
+        return changed
+
     # top_down_map.cpp:197-224 — the raster cache: a directory of class<i>.png (8-bit grey, 0 inside the class, flipped)
     def saveRasterizedMaps(self, path):
         import os
