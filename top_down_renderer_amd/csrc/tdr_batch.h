@@ -33,6 +33,17 @@ struct TdrBatchEntry {
   int32_t blk_prop, blk_res;   // first block of this filter in the propagate / resample launch
 };
 
+// the entry whose block range holds block b: the largest e < k with first(e) <= b (ranges are non-empty and ascending)
+template <class First>
+__device__ __forceinline__ int batch_find(int k, int b, First first) {
+  int lo = 0, hi = k - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (first(mid) <= b) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
 // tdr_batch.hip.  tab: device copy of the k entries; blocks_prop / blocks_res: total blocks of the two launches.
 int tdr_batch_propagate(const TdrBatchEntry* tab, int k, int blocks_prop, hipStream_t s);
 int tdr_batch_resample(const TdrBatchEntry* tab, int k, int blocks_res, hipStream_t s);
@@ -76,8 +87,6 @@ struct TdrBatchRasterEntry {
   int32_t blk_keys;
 };
 struct TdrBatchRasterShape { float ang_res; int ncls, rows, cols, rf, cpt; };
-#define TDR_BATCH_RASTER_KEY_MAX_COLS 4095    // RASTER_KEY_MAX_COLS (tdr_raster.hip)
-#define TDR_BATCH_RASTER_KEY_MAX_ROWS 65535   // RASTER_KEY_MAX_ROWS
 bool tdr_batch_raster_shape(int ncls, int rows, int cols, float ang_res, TdrBatchRasterShape* out);
 int tdr_batch_raster(const TdrBatchRasterEntry* tab, int k, int blocks_keys, const TdrBatchRasterShape& a, hipStream_t s);
 
@@ -91,7 +100,7 @@ struct TdrBatchPoseEntry {
   float* scratch;
 };
 #define TDR_BATCH_POSE_FLOATS 32
-#define TDR_BATCH_MC_SINGLE_MAX_N 4096        // MC_SINGLE_MAX_N (tdr_filter.hip)
+#define TDR_BATCH_MC_SINGLE_MAX_N 4096        // MC_SINGLE_MAX_N (tdr_filter_dev.h; tdr_batch_loop.hip asserts they agree)
 int tdr_batch_pose_launch(const TdrBatchPoseEntry* small, int k_small, const TdrBatchPoseEntry* big, int k_big,
                           hipStream_t s);
 

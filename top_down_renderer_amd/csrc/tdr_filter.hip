@@ -7,11 +7,10 @@
 using TdrSortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::merge_sort_config<512, 512, 4>, rocprim::default_config>;
 
 #include "tdr_common.h"
-#include "tdr_sincosf.h"
+#include "tdr_filter_dev.h"
 
 // ------------------------------------------------------------------------------------------------------------------
-// K3: propagate (state_particle.cpp:57-78).  z*sigma+mu spelled without contraction like libstdc++'s
-// normal_distribution (`__ret * stddev + mean`).
+// K3: propagate (state_particle.cpp:57-78); the particle's step itself is propagate_particle (tdr_filter_dev.h).
 __device__ __forceinline__ uint32_t mulhi32(uint32_t a, uint32_t b) { return __umulhi(a, b); }
 __device__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
 #pragma unroll
@@ -44,32 +43,7 @@ __global__ void propagate_kernel(float* __restrict__ st, int64_t cap, int64_t n,
     z[0] = r0 * cosf(6.283185307f * u1); z[1] = r0 * sinf(6.283185307f * u1);
     z[2] = r1 * cosf(6.283185307f * u3); z[3] = r1 * sinf(6.283185307f * u3);
   }
-  float theta = st[TDR_ST_THETA * cap + p];
-  float dx = st[TDR_ST_DX * cap + p], dy = st[TDR_ST_DY * cap + p];
-  // Rotation2D<float>(theta) * trans (:58): std::cos / std::sin of a float = the host libm's cosf / sinf, restated
-  // bit for bit (tdr_sincosf.h)
-  const float c = tdr_libm::cosf_v(theta, libm_fma), s = tdr_libm::sinf_v(theta, libm_fma);
-  const float gx = c * tx + (-s) * ty;
-  const float gy = s * tx + c * ty;
-  const float lx = dx, ly = dy;
-  dx += gx;
-  dy += gy;
-  const float dist = sqrtf(gx * gx + gy * gy);
-  const float sd_pos = pos_cov * dist, sd_th = theta_cov * dist;
-  theta += (z[0] * sd_th + 0.f) + omega;
-  dx += z[1] * sd_pos + 0.f;
-  dy += z[2] * sd_pos + 0.f;
-  if (!scale_freeze) {
-    const float sd_s = (float)fmin(2. / (double)dist, 0.02);
-    float scale = st[TDR_ST_SCALE * cap + p];
-    scale *= z[3] * sd_s + 1.f;
-    st[TDR_ST_SCALE * cap + p] = scale;
-  }
-  st[TDR_ST_THETA * cap + p] = theta;
-  st[TDR_ST_DX * cap + p] = dx;
-  st[TDR_ST_DY * cap + p] = dy;
-  const float mx = lx - dx, my = ly - dy;
-  last_dist[p] = sqrtf(mx * mx + my * my);
+  propagate_particle(st, cap, p, last_dist, z, tx, ty, omega, scale_freeze, pos_cov, theta_cov, libm_fma);
 }
 
 extern "C" int tdr_k_propagate(float* st, int64_t cap, int64_t n, float* last_dist, float tx, float ty, float omega,
@@ -195,17 +169,6 @@ extern "C" int tdr_init_particles_host(void* rng, const float* class_maps, int n
 // taken in double with a fixed order, the reference's two serial float chains (`sum`, `bottom_stddev`) exactly, so the
 // result depends only on (raw_w, last_dist, n) — identical on every rank that holds the all-gathered weights.  Up to
 // 32768 particles everything is one launch of one workgroup (uw_small_kernel, tdr_prefix.hip); above, the passes below.
-__device__ double block_sum_d(double v, double* sh) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double t = 0;
-  const int nw = blockDim.x >> 6;
-  for (int w = 0; w < nw; w++) t += sh[w];
-  return t;
-}
 __device__ long long block_sum_ll(long long v, long long* sh) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -427,13 +390,7 @@ __global__ void resample_kernel(const float* __restrict__ runmax, int64_t n, int
                                 int64_t i_begin, int64_t i_end, int32_t* __restrict__ idx) {
   const int64_t i = i_begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= i_end) return;
-  const float sample = ((float)i + shift) / (float)n_new;  // particle_filter.cpp:176
-  int64_t lo = 0, hi = n - 1;
-  while (lo < hi) {
-    int64_t mid = (lo + hi) >> 1;
-    if (runmax[mid] > sample) hi = mid; else lo = mid + 1;
-  }
-  idx[i - i_begin] = (int32_t)lo;
+  idx[i - i_begin] = (int32_t)resample_pick(runmax, n, n_new, i, shift);
 }
 
 extern "C" int tdr_k_resample(const float* runmax, int64_t n, int64_t n_new, float shift, int64_t i_begin,
@@ -452,13 +409,7 @@ __global__ void resample_dev_kernel(const float* __restrict__ runmax, int64_t n,
                                     int64_t i_begin, int64_t i_end, int32_t* __restrict__ idx) {
   const int64_t i = i_begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= i_end) return;
-  const float sample = ((float)i + *shift_dev) / (float)n_new;  // particle_filter.cpp:176
-  int64_t lo = 0, hi = n - 1;
-  while (lo < hi) {
-    int64_t mid = (lo + hi) >> 1;
-    if (runmax[mid] > sample) hi = mid; else lo = mid + 1;
-  }
-  idx[i - i_begin] = (int32_t)lo;
+  idx[i - i_begin] = (int32_t)resample_pick(runmax, n, n_new, i, *shift_dev);
 }
 extern "C" int tdr_k_resample_dev(const float* runmax, int64_t n, int64_t n_new, const float* shift_dev, int64_t i_begin,
                                   int64_t i_end, int32_t* idx_out, void* stream) {
@@ -483,8 +434,7 @@ __global__ void gather_states_kernel(const float* __restrict__ src, int64_t src_
 #pragma unroll
     for (int f = 0; f < TDR_ST_FIELDS; f++) dst[f * dst_cap + i] = src[(r * TDR_ST_FIELDS + f) * src_shard + l];
   } else {
-#pragma unroll
-    for (int f = 0; f < TDR_ST_FIELDS; f++) dst[f * dst_cap + i] = src[f * src_cap + j];
+    gather_particle(src, src_cap, j, dst, dst_cap, i);
   }
 }
 
@@ -500,176 +450,25 @@ extern "C" int tdr_k_gather_states(const float* src, int64_t src_cap, int64_t sr
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// K6: pose statistics (particle_filter.cpp:191-236) + geometric-mean scale (:343-357).  Double accumulation.
+// K6: pose statistics (particle_filter.cpp:191-236) + geometric-mean scale (:343-357): the bodies are in tdr_filter_dev.h;
+// the partial sums of the multi-workgroup form go to the scratch part of `out`.
+__device__ __forceinline__ McScratch* mc_scratch(float* out) { return reinterpret_cast<McScratch*>(out + 24); }
 __global__ __launch_bounds__(1024) void mean_cov_kernel(const float* __restrict__ st, int64_t cap, int64_t n,
                                                        const float* __restrict__ about, float* __restrict__ out,
                                                        int libm_fma) {
-  __shared__ double shd[16];
-  __shared__ float ref[4];
-  const int tid = threadIdx.x, nt = blockDim.x;
-  double acc[7] = {0, 0, 0, 0, 0, 0, 0};
-  for (int64_t p = tid; p < n; p += nt) {
-    const float sc = st[TDR_ST_SCALE * cap + p];
-    const float x = st[TDR_ST_DX * cap + p] * sc + st[TDR_ST_INIT_X * cap + p];  // mlState, state_particle.cpp:98-102
-    const float y = st[TDR_ST_DY * cap + p] * sc + st[TDR_ST_INIT_Y * cap + p];
-    const float th = st[TDR_ST_THETA * cap + p];
-    acc[0] += x; acc[1] += y; acc[2] += th; acc[3] += sc;
-    acc[4] += (double)tdr_libm::cosf_v(th, libm_fma); acc[5] += (double)tdr_libm::sinf_v(th, libm_fma);   // :198-199
-    acc[6] += log((double)sc);
-  }
-  double tot[7];
-  for (int k = 0; k < 7; k++) tot[k] = block_sum_d(acc[k], shd);
-  if (tid == 0) {
-    const float fn = (float)n;
-    float mean[4];
-    mean[0] = (float)tot[0] / fn; mean[1] = (float)tot[1] / fn; mean[3] = (float)tot[3] / fn;
-    mean[2] = atan2f((float)tot[5] / fn, (float)tot[4] / fn);  // :202
-    for (int k = 0; k < 4; k++) out[k] = mean[k];
-    out[20] = (float)exp(tot[6] / (double)n);  // freezeScale geo-mean
-    out[21] = out[22] = out[23] = 0.f;
-    if (about) {  // computeCov: about the max-likelihood particle's mlState (particle_filter.cpp:226-236)
-      for (int k = 0; k < 4; k++) ref[k] = about[k];
-    } else {
-      for (int k = 0; k < 4; k++) ref[k] = mean[k];
-    }
-  }
-  __syncthreads();
-  double c[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int64_t p = tid; p < n; p += nt) {
-    const float sc = st[TDR_ST_SCALE * cap + p];
-    float d[4];
-    d[0] = (st[TDR_ST_DX * cap + p] * sc + st[TDR_ST_INIT_X * cap + p]) - ref[0];
-    d[1] = (st[TDR_ST_DY * cap + p] * sc + st[TDR_ST_INIT_Y * cap + p]) - ref[1];
-    d[2] = st[TDR_ST_THETA * cap + p] - ref[2];
-    d[3] = sc - ref[3];
-    while (d[2] > M_PI) d[2] = (float)((double)d[2] - 2 * M_PI);    // :215
-    while (d[2] < -M_PI) d[2] = (float)((double)d[2] + 2 * M_PI);   // :216
-    int k = 0;
-    for (int a = 0; a < 4; a++)
-      for (int b = a; b < 4; b++) c[k++] += (double)(d[a] * d[b]);
-  }
-  double ct[10];
-  for (int k = 0; k < 10; k++) ct[k] = block_sum_d(c[k], shd);
-  if (tid == 0) {
-    int k = 0;
-    for (int a = 0; a < 4; a++)
-      for (int b = a; b < 4; b++) {
-        float v = (float)ct[k++] / (float)(n - 1);  // :219
-        out[4 + 4 * a + b] = v;
-        out[4 + 4 * b + a] = v;
-      }
-  }
+  mean_cov_body(st, cap, n, about, out, libm_fma);
 }
-
-// Larger particle sets: the same two reductions over MC_WGS workgroups.  Per-workgroup partial sums (double) go to the
-// scratch part of `out`; they are combined in workgroup order, so the result is a pure function of the inputs.
-//   mc_sums_kernel (MC_WGS)  -> partial sums of {x, y, theta, scale, cos, sin, log scale}
-//   mc_cov_kernel  (MC_WGS)  -> every workgroup combines the partial sums (mean / reference), then its share of the
-//                               10 second moments about it
-//   mc_final_kernel (1)      -> combines both, writes the 24 result floats
-#define MC_WGS 128
-#define MC_THREADS 256
-#define MC_SINGLE_MAX_N 4096   // up to here one workgroup does everything in one launch
-struct McScratch {
-  double sums[MC_WGS][8];
-  double mom[MC_WGS][10];
-};
-static_assert(24 * 4 + sizeof(McScratch) <= TDR_MEAN_COV_FLOATS * 4, "TDR_MEAN_COV_FLOATS too small");
-__device__ __forceinline__ McScratch* mc_scratch(float* out) { return reinterpret_cast<McScratch*>(out + 24); }
-
 __global__ __launch_bounds__(MC_THREADS) void mc_sums_kernel(const float* __restrict__ st, int64_t cap, int64_t n,
                                                              float* __restrict__ out, int libm_fma) {
-  __shared__ double shd[16];
-  double acc[7] = {0, 0, 0, 0, 0, 0, 0};
-  for (int64_t p = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x; p < n; p += (int64_t)MC_WGS * MC_THREADS) {
-    const float sc = st[TDR_ST_SCALE * cap + p];
-    const float x = st[TDR_ST_DX * cap + p] * sc + st[TDR_ST_INIT_X * cap + p];  // mlState, state_particle.cpp:98-102
-    const float y = st[TDR_ST_DY * cap + p] * sc + st[TDR_ST_INIT_Y * cap + p];
-    const float th = st[TDR_ST_THETA * cap + p];
-    acc[0] += x; acc[1] += y; acc[2] += th; acc[3] += sc;
-    acc[4] += (double)tdr_libm::cosf_v(th, libm_fma); acc[5] += (double)tdr_libm::sinf_v(th, libm_fma);   // :198-199
-    acc[6] += log((double)sc);
-  }
-  McScratch* sc = mc_scratch(out);
-  for (int k = 0; k < 7; k++) {
-    const double t = block_sum_d(acc[k], shd);
-    if (threadIdx.x == 0) sc->sums[blockIdx.x][k] = t;
-  }
-}
-// mean / reference point from the partial sums, identically in every caller (workgroup order); `stage` = MC_WGS*8 doubles
-__device__ __forceinline__ void mc_means(const McScratch* sc, int64_t n, const float* about, double* stage,
-                                         double* sh /*[8]*/, float mean[4], float ref[4], float& geo) {
-  __syncthreads();
-  for (int t = threadIdx.x; t < MC_WGS * 8; t += MC_THREADS) stage[t] = (&sc->sums[0][0])[t];   // coalesced
-  __syncthreads();
-  if (threadIdx.x < 7) {
-    double t = 0;
-    for (int g = 0; g < MC_WGS; g++) t += stage[g * 8 + threadIdx.x];
-    sh[threadIdx.x] = t;
-  }
-  __syncthreads();
-  const float fn = (float)n;
-  mean[0] = (float)sh[0] / fn; mean[1] = (float)sh[1] / fn; mean[3] = (float)sh[3] / fn;
-  mean[2] = atan2f((float)sh[5] / fn, (float)sh[4] / fn);  // :202
-  geo = (float)exp(sh[6] / (double)n);                      // freezeScale geo-mean
-  for (int k = 0; k < 4; k++) ref[k] = about ? about[k] : mean[k];
+  mc_sums_body(st, cap, n, mc_scratch(out), libm_fma);
 }
 __global__ __launch_bounds__(MC_THREADS) void mc_cov_kernel(const float* __restrict__ st, int64_t cap, int64_t n,
                                                             const float* __restrict__ about, float* __restrict__ out) {
-  __shared__ double shd[16];
-  __shared__ double shm[8];
-  __shared__ double stage[MC_WGS * 10];
-  McScratch* sc = mc_scratch(out);
-  float mean[4], ref[4], geo;
-  mc_means(sc, n, about, stage, shm, mean, ref, geo);
-  double c[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int64_t p = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x; p < n; p += (int64_t)MC_WGS * MC_THREADS) {
-    const float s = st[TDR_ST_SCALE * cap + p];
-    float d[4];
-    d[0] = (st[TDR_ST_DX * cap + p] * s + st[TDR_ST_INIT_X * cap + p]) - ref[0];
-    d[1] = (st[TDR_ST_DY * cap + p] * s + st[TDR_ST_INIT_Y * cap + p]) - ref[1];
-    d[2] = st[TDR_ST_THETA * cap + p] - ref[2];
-    d[3] = s - ref[3];
-    while (d[2] > M_PI) d[2] = (float)((double)d[2] - 2 * M_PI);    // :215
-    while (d[2] < -M_PI) d[2] = (float)((double)d[2] + 2 * M_PI);   // :216
-    int k = 0;
-    for (int a = 0; a < 4; a++)
-      for (int b = a; b < 4; b++) c[k++] += (double)(d[a] * d[b]);
-  }
-  for (int k = 0; k < 10; k++) {
-    const double t = block_sum_d(c[k], shd);
-    if (threadIdx.x == 0) sc->mom[blockIdx.x][k] = t;
-  }
+  mc_cov_body(st, cap, n, about, mc_scratch(out));
 }
 __global__ __launch_bounds__(MC_THREADS) void mc_final_kernel(int64_t n, const float* __restrict__ about,
                                                               float* __restrict__ out) {
-  __shared__ double shm[8];
-  __shared__ double shc[10];
-  __shared__ double stage[MC_WGS * 10];
-  const McScratch* sc = mc_scratch(out);
-  float mean[4], ref[4], geo;
-  mc_means(sc, n, about, stage, shm, mean, ref, geo);
-  __syncthreads();
-  for (int t = threadIdx.x; t < MC_WGS * 10; t += MC_THREADS) stage[t] = (&sc->mom[0][0])[t];
-  __syncthreads();
-  if (threadIdx.x < 10) {
-    double t = 0;
-    for (int g = 0; g < MC_WGS; g++) t += stage[g * 10 + threadIdx.x];
-    shc[threadIdx.x] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int k = 0; k < 4; k++) out[k] = mean[k];
-    out[20] = geo;
-    out[21] = out[22] = out[23] = 0.f;
-    int k = 0;
-    for (int a = 0; a < 4; a++)
-      for (int b = a; b < 4; b++) {
-        const float v = (float)shc[k++] / (float)(n - 1);  // :219
-        out[4 + 4 * a + b] = v;
-        out[4 + 4 * b + a] = v;
-      }
-  }
+  mc_final_body(n, about, mc_scratch(out), out);
 }
 
 extern "C" int tdr_k_mean_cov(const float* st, int64_t cap, int64_t n, const float* about, float* out, void* stream) {
@@ -720,22 +519,17 @@ extern "C" int tdr_k_shift_init(float* st, int64_t cap, int64_t n, float dx, flo
 __global__ void save_ml_state_kernel(const float* __restrict__ info, const float* __restrict__ st, int64_t cap,
                                      int64_t src_shard, int64_t n, float* __restrict__ out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  int64_t best = (int64_t)__float_as_int(info[0]);
-  if (best < 0 || best >= n) best = 0;
+  const int64_t best = ml_index(info, n);
   float f[TDR_ST_FIELDS];
   if (src_shard > 0) {   // all-gathered source [rank][field][src_shard], `best` is a global particle index
     const int64_t r = best / src_shard, l = best - r * src_shard;
 #pragma unroll
-    for (int k = 0; k < TDR_ST_FIELDS; k++) { f[k] = st[(r * TDR_ST_FIELDS + k) * src_shard + l]; out[k] = f[k]; }
+    for (int k = 0; k < TDR_ST_FIELDS; k++) f[k] = st[(r * TDR_ST_FIELDS + k) * src_shard + l];
   } else {
 #pragma unroll
-    for (int k = 0; k < TDR_ST_FIELDS; k++) { f[k] = st[(int64_t)k * cap + best]; out[k] = f[k]; }
+    for (int k = 0; k < TDR_ST_FIELDS; k++) f[k] = st[(int64_t)k * cap + best];
   }
-  out[7] = 0.f;
-  out[8] = f[TDR_ST_DX] * f[TDR_ST_SCALE] + f[TDR_ST_INIT_X];
-  out[9] = f[TDR_ST_DY] * f[TDR_ST_SCALE] + f[TDR_ST_INIT_Y];
-  out[10] = f[TDR_ST_THETA];
-  out[11] = f[TDR_ST_SCALE];
+  ml_record(f, out);
 }
 extern "C" int tdr_k_save_ml_state(const float* info, const float* st, int64_t cap, int64_t src_shard, int64_t n,
                                    float* out12, void* stream) {

@@ -28,7 +28,7 @@
 // whose rejection loop outlasts a window carries its phase and position into the next one.  The host waits for each
 // window's "done" flag.
 #include "tdr_common.h"
-#include "tdr_logf.h"
+#include "tdr_mt_dev.h"
 
 #define INI_MT_N 624
 #define INI_TILE 2048                 // stream positions per workgroup of ini_flags_kernel (1024 per parity)
@@ -46,19 +46,6 @@ extern "C" int64_t tdr_config_init_window_words(int64_t w) {   // < 0: query onl
 extern "C" int tdr_config_init_device(int on) {   // < 0: query only
   if (on >= 0) g_init_device = on ? 1 : 0;
   return g_init_device;
-}
-
-// (copies of tdr_rng.hip's mt_temper / mt_canonical / mt_attempt: that file's kernels keep their code objects)
-__device__ __forceinline__ uint32_t ini_temper(uint32_t y) {
-  y ^= (y >> 11);
-  y ^= (y << 7) & 0x9d2c5680u;
-  y ^= (y << 15) & 0xefc60000u;
-  y ^= (y >> 18);
-  return y;
-}
-__device__ __forceinline__ float ini_canonical(uint32_t u) {   // generate_canonical<float, 24>: one word
-  float c = (float)u * 0x1p-32f;
-  return c >= 1.f ? 0x1.fffffep-1f : c;
 }
 
 struct IniParams {
@@ -105,13 +92,12 @@ struct IniTry {
 // the two words at w[i], w[i + 1]: a uniform try, or a Marsaglia attempt (a normal try / the theta draw)
 __device__ IniTry ini_try(const IniParams& q, const uint32_t* __restrict__ w, int64_t i, bool need_value) {
   IniTry t;
-  const float c0 = ini_canonical(ini_temper(w[i])), c1 = ini_canonical(ini_temper(w[i + 1]));
-  const float ax = (float)((double)(2.0f * c0) - 1.0), ay = (float)((double)(2.0f * c1) - 1.0);
-  const float r2 = ax * ax + ay * ay;
-  t.accepted = !((double)r2 > 1.0 || (double)r2 == 0.0);
+  const MtAttempt at = mt_attempt(w, i);
+  const float c0 = at.c0, c1 = at.c1, ax = at.x, ay = at.y, r2 = at.r2;
+  t.accepted = at.ok;
   t.z = 0.f;
   if (t.accepted && (q.normal || need_value)) {
-    const float mult = sqrtf(-2.f * tdr_libm::logf_t<true>(r2) / r2);
+    const float mult = mt_attempt_mult(r2);
     t.z = ay * mult * 1.f + 0.f;
     if (q.normal) {
       const float vx = ax * mult * 1.f + 0.f;

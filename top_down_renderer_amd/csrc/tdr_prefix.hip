@@ -1567,186 +1567,7 @@ __device__ __forceinline__ double uws_sum_d(double v, double* sh) {   // block s
   for (int w = 0; w < NT / 64; w++) t += sh[w];
   return t;
 }
-template <bool WAVES>
-__global__ __launch_bounds__(WAVES ? UWS_THREADS : PFXW_THREADS) void uw_small_kernel(const float* __restrict__ raw,
-                                                                const float* __restrict__ last_dist, int n,
-                                                                float* __restrict__ w, float* __restrict__ info) {
-  extern __shared__ float uws_lraw[];   // [uws_idx(n)]: the raw weights, later the weights being normalised
-  float* const lraw = uws_lraw;
-  constexpr int nt = WAVES ? UWS_THREADS : PFXW_THREADS;
-  __shared__ UwsShared ush;
-  double* const shd = ush.shd;
-  __shared__ float sh_best[nt / 64];
-  __shared__ int sh_besti[nt / 64];
-  const int tid = threadIdx.x;
-#ifdef TDR_UW_TIMELINE
-  if (tid == 0) { for (int k = 10; k < 16; k++) g_uw_tl[k] = 0; }
-#endif
-  UW_STAMP(0);
-  float sum = 0.f, mean = 0.f, bsum = 0.f;
-  long long num_valid = 0, num_under = 0;
-  double valid_sum = 0.0;   // WAVES: the valid weights summed in double (the sum of the wave-chunks' sums)
-  if constexpr (WAVES) {
-    // chain 0: stage the weights and count the valid ones (:108-116), `sum`; chain 1: count the weights below the mean,
-    // `bottom_stddev` (:118-126).  Either pass works wave-chunk by wave-chunk and leaves the chunks' double sums behind
-    // for the chain's predictions.  (Unrolled: `kind` is a constant in each copy — 47 us against 53 with one copy.)
-    const int lane = tid & 63, nwc = (n + UWS_WC - 1) / UWS_WC;
-#pragma unroll
-    for (int kind = 0; kind < 2; kind++) {
-      int cnt = 0;
-      for (int c = tid >> 6; c < nwc; c += nt / 64) {
-        const int base = c * UWS_WC + lane;
-        float v[CHAIN_K];
-        if (kind == 0) {   // (eight loads of 64 consecutive weights in flight per wave)
-#pragma unroll
-          for (int m = 0; m < CHAIN_K; m++) v[m] = base + 64 * m < n ? raw[base + 64 * m] : __uint_as_float(0x7FC00000u);
-#pragma unroll
-          for (int m = 0; m < CHAIN_K; m++)
-            if (base + 64 * m < n) lraw[uws_idx(base + 64 * m)] = v[m];
-        } else {
-#pragma unroll
-          for (int m = 0; m < CHAIN_K; m++) {
-            const float x = lraw[uws_idx(min(base + 64 * m, n - 1))];
-            v[m] = base + 64 * m < n ? x : __uint_as_float(0x7FC00000u);
-          }
-        }
-        double acc = 0;
-#pragma unroll
-        for (int m = 0; m < CHAIN_K; m++) {
-          const bool take = kind == 0 ? v[m] == v[m] : (v[m] == v[m] && v[m] < mean);
-          double x = (double)(kind == 0 ? v[m] : v[m] - mean);
-          if (kind) x = x * x;
-          cnt += take ? 1 : 0;
-          acc += take ? x : 0.0;
-        }
-        acc = uws_wave_scan_d(acc);
-        if (lane == 63) ush.csum[c] = acc;
-      }
-      const long long count = (long long)uws_sum_d<nt>((double)cnt, shd);   // (its barriers also publish the staged weights)
-      if (kind == 0) valid_sum = uws_readlane_d(uws_wave_scan_d(lane < nwc ? ush.csum[lane] : 0.0), 63);
-      UW_STAMP(kind ? 4 : 1);
-      const float total = uws_chain_total_waves(kind, n, mean, ush);   // serial float chain, exact
-      UW_STAMP(kind ? 6 : 3);
-      if (kind == 0) {
-        sum = total; num_valid = count;
-        mean = sum / (float)num_valid;  // :117 (0/0 -> NaN like the reference)
-      } else {
-        bsum = total; num_under = count;
-      }
-    }
-  } else {
-    // stage (four loads in flight per thread), count the valid weights on the way (:108-116)
-    double cnt = 0;
-    int i = tid;
-    for (; i + 3 * nt < n; i += 4 * nt) {
-      const float v0 = raw[i], v1 = raw[i + nt], v2 = raw[i + 2 * nt], v3 = raw[i + 3 * nt];
-      lraw[uws_idx(i)] = v0; lraw[uws_idx(i + nt)] = v1; lraw[uws_idx(i + 2 * nt)] = v2; lraw[uws_idx(i + 3 * nt)] = v3;
-      cnt += (v0 == v0 ? 1.0 : 0.0) + (v1 == v1 ? 1.0 : 0.0) + (v2 == v2 ? 1.0 : 0.0) + (v3 == v3 ? 1.0 : 0.0);
-    }
-    for (; i < n; i += nt) {
-      const float v = raw[i];
-      lraw[uws_idx(i)] = v;
-      cnt += (v == v) ? 1.0 : 0.0;
-    }
-    num_valid = (long long)uws_sum_d<nt>(cnt, shd);   // (its barriers also publish the staged weights)
-    UW_STAMP(1);
-    sum = uws_chain_total(0, n, 0.f);   // serial float chain, exact
-    UW_STAMP(3);
-    mean = sum / (float)num_valid;  // :117 (0/0 -> NaN like the reference)
-    // :118-126  bottom_stddev (serial float chain with double addends, exact) and the count below the mean
-    double cu = 0;
-    for (int i = tid; i < n; i += nt) {
-      const float v = lraw[uws_idx(i)];
-      cu += (v == v && v < mean) ? 1.0 : 0.0;
-    }
-    num_under = (long long)uws_sum_d<nt>(cu, shd);
-    UW_STAMP(4);
-    bsum = uws_chain_total(1, n, mean);
-    UW_STAMP(6);
-  }
-  const float bottom = sqrtf(bsum / (float)num_under);
-  const bool fallback = (sum == 0.f || num_under < 1);  // :129
-  const float fill = mean - bottom;                      // :133
-  const float fn = (float)n;
-  float fs1;
-  double s2 = 0;
-  if constexpr (WAVES) {
-    // :130-135 without a pass of its own: the filled weights sum to the valid ones plus `fill` for every NaN (all ones in
-    // the fallback); the fill itself happens where the weight is read next.  The last travel distances are requested
-    // sixteen per thread at a time, ahead of the divisions.
-    fs1 = (float)(fallback ? (double)n : valid_sum + (double)(n - num_valid) * (double)fill);
-    UW_STAMP(7);
-    for (int i0 = tid; i0 < n; i0 += 16 * nt) {
-      float ld[16];
-#pragma unroll
-      for (int j = 0; j < 16; j++) ld[j] = i0 + j * nt < n ? last_dist[i0 + j * nt] : 0.f;
-#pragma unroll
-      for (int j = 0; j < 16; j++) {
-        const int i = i0 + j * nt;
-        if (i < n) {   // :135, :138-141
-          float v = lraw[uws_idx(i)];
-          v = (fallback ? 1.f : (v != v ? fill : v)) / fs1;
-          const float d = fminf(ld[j] * 5.f, 1.f);
-          v = d * v + (1.f - d) / fn;
-          lraw[uws_idx(i)] = v;
-          s2 += (double)v;
-        }
-      }
-    }
-  } else {
-    pfx_sync();                                            // every thread is done reading the raw weights
-    double s1a = 0;
-    for (int i = tid; i < n; i += nt) {
-      float v = lraw[uws_idx(i)];
-      v = fallback ? 1.f : (v != v ? fill : v);
-      lraw[uws_idx(i)] = v;
-      s1a += (double)v;
-    }
-    fs1 = (float)uws_sum_d<nt>(s1a, shd);
-    UW_STAMP(7);
-    auto one = [&](int i, float ld) {   // :135, :138-141
-      float v = lraw[uws_idx(i)] / fs1;
-      const float d = fminf(ld * 5.f, 1.f);
-      v = d * v + (1.f - d) / fn;
-      lraw[uws_idx(i)] = v;
-      s2 += (double)v;
-    };
-    int i = tid;
-    for (; i + 3 * nt < n; i += 4 * nt) {
-      const float l0 = last_dist[i], l1 = last_dist[i + nt], l2 = last_dist[i + 2 * nt], l3 = last_dist[i + 3 * nt];
-      one(i, l0); one(i + nt, l1); one(i + 2 * nt, l2); one(i + 3 * nt, l3);   // same order as one by one
-    }
-    for (; i < n; i += nt) one(i, last_dist[i]);
-  }
-  const float fs2 = (float)uws_sum_d<nt>(s2, shd);
-  UW_STAMP(8);
-  float best = -INFINITY;
-  int besti = 0x7fffffff;
-  for (int i = tid; i < n; i += nt) {  // :142, :145-147 (first maximum)
-    const float v = lraw[uws_idx(i)] / fs2;
-    w[i] = v;
-    if (v > best || (v == best && i < besti)) { best = v; besti = i; }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_down(best, o, 64);
-    const int oi = __shfl_down(besti, o, 64);
-    if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
-  }
-  pfx_sync();
-  if ((tid & 63) == 0) { sh_best[tid >> 6] = best; sh_besti[tid >> 6] = besti; }
-  pfx_sync();
-  if (tid == 0) {
-    for (int k = 1; k < nt / 64; k++)
-      if (sh_best[k] > best || (sh_best[k] == best && sh_besti[k] < besti)) { best = sh_best[k]; besti = sh_besti[k]; }
-    if (besti == 0x7fffffff) besti = 0;
-    info[0] = __int_as_float(besti);
-    info[1] = sum; info[2] = mean; info[3] = bottom; info[4] = fallback ? 1.f : 0.f;
-    info[5] = (float)num_valid; info[6] = (float)num_under; info[7] = 0.f;
-  }
-  UW_STAMP(9);
-}
-// uw_small_kernel's body, for uw_small_batch_kernel (one workgroup per filter).  A copy rather than a shared function: the
-// existing kernel keeps its own text, so it compiles to the same code as before.
+// the one-workgroup weight statistics: the body of uw_small_kernel and of uw_small_batch_kernel
 template <bool WAVES>
 __device__ __forceinline__ void uw_small_body(const float* __restrict__ raw, const float* __restrict__ last_dist, int n,
                                               float* __restrict__ w, float* __restrict__ info) {
@@ -1924,6 +1745,12 @@ __device__ __forceinline__ void uw_small_body(const float* __restrict__ raw, con
   }
   UW_STAMP(9);
 }
+template <bool WAVES>
+__global__ __launch_bounds__(WAVES ? UWS_THREADS : PFXW_THREADS) void uw_small_kernel(const float* __restrict__ raw,
+                                                                const float* __restrict__ last_dist, int n,
+                                                                float* __restrict__ w, float* __restrict__ info) {
+  uw_small_body<WAVES>(raw, last_dist, n, w, info);
+}
 // batched filters (tdr_batch_step): workgroup k = filter k of the table
 template <bool WAVES>
 __global__ __launch_bounds__(WAVES ? UWS_THREADS : PFXW_THREADS) void uw_small_batch_kernel(const TdrBatchEntry* __restrict__ tab) {
@@ -2067,87 +1894,7 @@ __device__ __forceinline__ void pfs_wave_fill(int lo, int cnt, float r) {
   for (int k = 0; k < CHAIN_K; k++)
     if (t0 + k < cnt) uws_lraw[uws_idx(lo + t0 + k)] = pv[k];
 }
-__global__ __launch_bounds__(UWS_THREADS) void pfx_small_kernel(const float* __restrict__ w, int n,
-                                                                float* __restrict__ runmax, float* __restrict__ prefix_opt,
-                                                                float* __restrict__ tail) {   // tail (optional): sum, maximum
-  extern __shared__ float uws_lraw[];
-  float* const lraw = uws_lraw;
-  __shared__ PfsShared sh;
-  constexpr int nt = UWS_THREADS, NW = UWS_THREADS / 64;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nwc = (n + UWS_WC - 1) / UWS_WC;
-  if (tid == 0) sh.irregular = 0;
-  pfx_sync();
-  // stage wave-chunk by wave-chunk; their double sums for the predictions
-  bool irr = false;
-  for (int c = wave; c < nwc; c += NW) {
-    const int base = c * UWS_WC + lane;
-    float v[CHAIN_K];
-#pragma unroll
-    for (int m = 0; m < CHAIN_K; m++) v[m] = base + 64 * m < n ? w[base + 64 * m] : 0.f;
-    double acc = 0;
-#pragma unroll
-    for (int m = 0; m < CHAIN_K; m++) {
-      if (base + 64 * m < n) lraw[uws_idx(base + 64 * m)] = v[m];
-      irr |= !(v[m] >= 0.f);
-      acc += (double)v[m];
-    }
-    acc = uws_wave_scan_d(acc);
-    if (lane == 63) sh.u.csum[c] = acc;
-  }
-  if (__ballot(irr) != 0ull && lane == 0) atomicOr(&sh.irregular, 1);
-  pfx_sync();
-  const float total = uws_chain_total_waves(2, n, 0.f, sh.u, sh.rin);   // (ends in a barrier)
-  // every chunk again from its exact starting sum (the first one was filled by the head)
-  for (int c = 1 + wave; c < nwc; c += NW) pfs_wave_fill(c * UWS_WC, min(UWS_WC, n - c * UWS_WC), sh.rin[c]);
-  pfx_sync();
-  if (sh.irregular == 0) {   // the running sum never falls: it is its own running maximum
-    if (tail && tid == 0) { tail[0] = total; tail[1] = total; }
-    for (int i = tid; i < n; i += nt) {
-      const float v = lraw[uws_idx(i)];
-      runmax[i] = v;
-      if (prefix_opt) prefix_opt[i] = v;
-    }
-    return;
-  }
-  const int t0 = lane * CHAIN_K;
-  for (int c = wave; c < nwc; c += NW) {
-    const int lo = c * UWS_WC, cnt = min(UWS_WC, n - lo);
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < CHAIN_K; k++) {
-      const float v = lraw[uws_idx(lo + t0 + k)];
-      if (t0 + k < cnt && v == v) m = fmaxf(m, v);
-    }
-    m = pfs_wave_scan_max(m);
-    if (lane == 63) sh.cmax[c] = m;
-  }
-  pfx_sync();
-  const float before = pfs_wave_scan_max(lane < nwc ? sh.cmax[lane] : -INFINITY);   // lane c: maximum up to chunk c's end
-  if (tail && tid == 63) { tail[0] = total; tail[1] = before; }
-  for (int c = wave; c < nwc; c += NW) {
-    const int lo = c * UWS_WC, cnt = min(UWS_WC, n - lo);
-    const float carry = c > 0 ? __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(before), c - 1)) : -INFINITY;
-    float pv[CHAIN_K], lm[CHAIN_K];
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < CHAIN_K; k++) {
-      pv[k] = lraw[uws_idx(lo + t0 + k)];
-      if (t0 + k < cnt && pv[k] == pv[k]) m = fmaxf(m, pv[k]);
-      lm[k] = m;
-    }
-    const float incl = pfs_wave_scan_max(m);
-    float ex = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp((int)0xFF800000u, (int)__float_as_uint(incl), 0x138, 0xF, 0xF, false));
-    ex = fmaxf(ex, carry);
-#pragma unroll
-    for (int k = 0; k < CHAIN_K; k++)
-      if (t0 + k < cnt) {
-        runmax[lo + t0 + k] = fmaxf(lm[k], ex);
-        if (prefix_opt) prefix_opt[lo + t0 + k] = pv[k];
-      }
-  }
-}
-// pfx_small_kernel's body, for pfx_small_batch_kernel (one workgroup per filter; a copy, like uw_small_body)
+// the one-workgroup running sum / running maximum: the body of pfx_small_kernel and of pfx_small_batch_kernel
 __device__ __forceinline__ void pfx_small_body(const float* __restrict__ w, int n, float* __restrict__ runmax,
                                                float* __restrict__ prefix_opt,
                                                float* __restrict__ tail) {   // tail (optional): sum, maximum
@@ -2228,6 +1975,12 @@ __device__ __forceinline__ void pfx_small_body(const float* __restrict__ w, int 
       }
   }
 }
+__global__ __launch_bounds__(UWS_THREADS) void pfx_small_kernel(const float* __restrict__ w, int n,
+                                                                float* __restrict__ runmax, float* __restrict__ prefix_opt,
+                                                                float* __restrict__ tail) {
+  pfx_small_body(w, n, runmax, prefix_opt, tail);
+}
+// batched filters (tdr_batch_step): workgroup k = filter k of the table
 __global__ __launch_bounds__(UWS_THREADS) void pfx_small_batch_kernel(const TdrBatchEntry* __restrict__ tab) {
   const TdrBatchEntry& e = tab[blockIdx.x];
   pfx_small_body(e.w_out, (int)e.n, e.runmax_out, nullptr, nullptr);

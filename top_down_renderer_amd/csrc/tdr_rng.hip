@@ -35,24 +35,12 @@
 #include <sstream>
 
 #include "tdr_common.h"
-#include "tdr_logf.h"
+#include "tdr_mt_dev.h"
 #include "tdr_mt_jump.h"
 
 #define MT_N 624
 #define MT_M 397
 
-__device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
-  y ^= (y >> 11);                    // (d = 0xffffffff)
-  y ^= (y << 7) & 0x9d2c5680u;
-  y ^= (y << 15) & 0xefc60000u;
-  y ^= (y >> 18);
-  return y;
-}
-// generate_canonical<float, 24>(mt19937) (bits/random.tcc): one word, float(u) / 2^32, clamped below 1
-__device__ __forceinline__ float mt_canonical(uint32_t u) {
-  float c = (float)u * 0x1p-32f;     // u32 -> float rounds to nearest; the scaling is exact
-  return c >= 1.f ? 0x1.fffffep-1f : c;
-}
 // One twist of the state in LDS (mersenne_twister_engine::_M_gen_rand), by ONE wave: elements in ascending order, 192 at
 // a time — element k needs the OLD x[k], x[k + 1] and, from 227 on, the NEW x[k - 227], written at least one batch earlier;
 // element 623 reads the NEW x[0] (it is the last of the engine's loop), long written when its batch comes.  So a batch is
@@ -171,19 +159,6 @@ __global__ __launch_bounds__(1024) void mt_jump_kernel(const uint32_t* __restric
   for (int p = lane; p < MT_N; p += 64) dst[p] = xs[p];
 }
 
-struct MtAttempt {
-  float x, y, r2;
-  bool ok;
-};
-__device__ __forceinline__ MtAttempt mt_attempt(const uint32_t* __restrict__ raw, int64_t g) {
-  MtAttempt a;
-  const float c0 = mt_canonical(mt_temper(raw[g])), c1 = mt_canonical(mt_temper(raw[g + 1]));
-  a.x = (float)((double)(2.0f * c0) - 1.0);   // result_type(2.0) * aurng() - 1.0: float product, double difference
-  a.y = (float)((double)(2.0f * c1) - 1.0);
-  a.r2 = a.x * a.x + a.y * a.y;               // (compiled with -ffp-contract=off: two roundings, like the host's)
-  a.ok = !((double)a.r2 > 1.0 || (double)a.r2 == 0.0);
-  return a;
-}
 // attempt t uses words p0 + 2t, p0 + 2t + 1 of the raw stream
 __global__ __launch_bounds__(256) void mt_attempt_kernel(const uint32_t* __restrict__ raw, const uint32_t* __restrict__ state,
                                                          int64_t nattempts, uint32_t* __restrict__ flags) {
@@ -205,8 +180,7 @@ __global__ __launch_bounds__(256) void mt_normal_kernel(const uint32_t* __restri
   const int slot = (int)(a - p * per);
   if (p < lo || p >= hi) return;
   const MtAttempt at = mt_attempt(raw, (int64_t)state[MT_N] + 2 * t);
-  // std::sqrt(-2 * std::log(r2) / r2): the float overloads (glibc logf, IEEE division and square root)
-  const float mult = sqrtf(-2.f * tdr_libm::logf_t<true>(at.r2) / at.r2);
+  const float mult = mt_attempt_mult(at.r2);
   float* z = z4 + 4 * (p - lo);
   const float vy = at.y * mult * 1.f + 0.f, vx = at.x * mult * 1.f + 0.f;   // ret * stddev + mean of the {0, 1} objects
   if (slot == 0) z[0] = vy;                       // theta: a fresh object's first value; its saved one is dropped

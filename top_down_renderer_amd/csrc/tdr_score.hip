@@ -74,273 +74,8 @@ extern "C" int tdr_debug_read_timeline(unsigned long long* out, int n) {
 // by the lines they pull through the fabric; the empty bins of a LiDAR scan are mostly its outer rings, where a window
 // touches the most lines: half of a scattered particle's lines are never requested.  The FMAs of such a
 // sample are still executed, with a zero scan operand against the dictionary's entry 0: the sums are bit-identical.
-template <int NV4, int U, bool KSLOT, bool USCALE, bool COMPACT, bool WIDE = false, bool SKIP = false>
-__global__ __launch_bounds__(256, COMPACT ? (WIDE ? 3 : 5) : 1) void score_polar_kernel(ScoreArgs a) {
-  constexpr int RF = 4 * NV4;
-  static_assert(!WIDE || (COMPACT && NV4 == 2), "wide compact records: 8-float dense records only");
-  static_assert(!SKIP || (COMPACT && !WIDE), "SKIP: narrow compact records only");
-  constexpr int CW = WIDE ? 4 : CmapShape<RF, KSLOT>::CW, LC = WIDE ? 1 : CmapShape<RF, KSLOT>::LC;
-  constexpr int NDICT = WIDE ? TDR_CMAP_WIDE_MAX_DICT : TDR_CMAP_MAX_DICT;
-#ifdef TDR_SCORE_TIMELINE
-  const unsigned tl_id = blockIdx.y * gridDim.x + blockIdx.x;
-  if (threadIdx.x == 0 && tl_id < TDR_TL_MAX) g_timeline[2 * tl_id] = wall_clock64();
-#endif
-  extern __shared__ float4 ring[];  // [nb rows][rs]: a row's (ring, plane) records side by side, rs = group * NV4 | 1
-  __shared__ float ldict[COMPACT ? NDICT : 1];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#if TDR_XCD_SWIZZLE
-  // Workgroups are dealt round-robin over the 8 XCDs; remap so that each XCD (its own L2) gets a contiguous run of
-  // particle batches (Morton neighbours) instead of every 8th one.  Speed only: any mapping gives the same results.
-  const unsigned nbx = gridDim.x, per = (nbx + 7) / 8;
-  unsigned bx = (blockIdx.x % 8) * per + blockIdx.x / 8;
-  if (nbx % 8 != 0) bx = blockIdx.x;  // keep it a bijection
-#else
-  const unsigned bx = blockIdx.x;
-#endif
-  const int64_t slot = ((int64_t)bx * 4 + wave) * 64 + lane;
-  if (a.run_if && !int_form_off(a.run_if)) return;  // (uniform)
-  const int64_t nact = a.count ? (int64_t)*a.count : a.n;
-  if ((int64_t)bx * 256 >= nact) return;  // whole workgroup idle (uniform)
-  const bool valid = slot < nact;
-  const int64_t sbase = a.slot_base ? (int64_t)*a.slot_base : 0;
-  const int64_t p = a.order ? (int64_t)a.order[sbase + (valid ? slot : 0)] : (valid ? slot : 0);
-  if (a.only_uninit && !__syncthreads_or(valid && a.st[TDR_ST_HAVE_INIT * a.cap + p] == 0.f)) return;
-  const float scale = a.st[TDR_ST_SCALE * a.cap + p];
-  const float cx = a.st[TDR_ST_DX * a.cap + p] * scale + a.st[TDR_ST_INIT_X * a.cap + p];  // state_particle.cpp:161
-  const float cy = a.st[TDR_ST_DY * a.cap + p] * scale + a.st[TDR_ST_INIT_Y * a.cap + p];  // :162
-  const float off0 = cy / a.resolution;  // top_down_map_polar.cpp:29
-  const float off1 = cx / a.resolution;  // :30
-  const float theta = a.use_theta_override ? a.theta_override : a.st[TDR_ST_THETA * a.cap + p];
-  const int shift = rot_shift_dev(theta, a.nb);  // scan row paired with window row i is (i + shift) mod nb
-
-  const int j0 = blockIdx.y * a.group, gn = min(a.nr - j0, a.group);   // this workgroup's rings: [j0, j0 + gn)
-  const int rowstride = (a.cols + 2) * (RF * 4);            // bytes per guarded map row
-  const int kbase = (a.cols + 3) * (RF * 4);                // byte offset of cell (0,0)
-  const float rmaxf = (float)a.rows, cmaxf = (float)a.cols;
-  const char* __restrict__ recb = reinterpret_cast<const char*>(a.rec);
-  const char* __restrict__ crecb = reinterpret_cast<const char*>(a.crec);
-  const int ckcol = a.ctiles_r * 128 - 16 * CW, ckconst = a.ctiles_r * 128 + 128;   // cmap_offset
-  // The sample table is read-only for the whole launch and every lane of a wave reads the same entry: it is addressed
-  // through the CONSTANT address space so that these are scalar loads whatever else the kernel contains.  (Left to its
-  // own no-clobber analysis the compiler gives up in the compact kernel — the dictionary staging is one store too many —
-  // and emits vector loads with a full wait in front of every address computation.)
-  typedef const float __attribute__((address_space(4))) * tdr_const_f;
-  const tdr_const_f tabc = (tdr_const_f)(USCALE ? a.utab : a.tab);
-  auto tab_at = [&](int64_t k) { return make_float2(tabc[2 * k], tabc[2 * k + 1]); };
-  const float4* __restrict__ scan4 = reinterpret_cast<const float4*>(a.scan_pk);
-  const int nb = a.nb;
-
-  // stage the group's scan rows and (compact) the dictionary
-  bool dict_bad = false;   // a non-finite dictionary value: 0 x inf must stay NaN, nothing may be skipped
-  if constexpr (COMPACT)
-    for (int t = threadIdx.x; t < a.dict_n; t += 256) {
-      const float v = a.dict[t];
-      ldict[t] = v;
-      if constexpr (SKIP) dict_bad |= !(fabsf(v) <= 3.402823466e+38f);
-    }
-  // One row of the LDS image = the scan records (ring, plane) of one direction, 16 bytes each, side by side: a step
-  // reads them with ONE address per lane and immediate offsets.  The row stride is an ODD number of 16-byte slots, so
-  // lanes on different rows (different headings) fall on different banks.
-  const int rs = (a.group * NV4) | 1;
-  for (int jj = 0; jj < gn; jj++)
-    for (int t = threadIdx.x; t < nb * NV4; t += 256) {
-      const float4 v = scan4[(int64_t)(j0 + jj) * nb * NV4 + t];
-      const int row = t / NV4, pl = t - row * NV4;
-      ring[row * rs + jj * NV4 + pl] = v;
-    }
-  bool skip_ok = false;
-  if constexpr (SKIP) skip_ok = !__syncthreads_or(dict_bad);
-  else __syncthreads();
-
-  // USCALE: every particle has the same scale, so (tab*scale)*res was evaluated once per step into a.utab and is
-  // wave-uniform here; otherwise it is evaluated per lane.  Identical float operations either way.
-  // Returns the byte offset of the sample's record (dense: guarded row-major grid; compact: tiled).
-  typedef float tdr_v2f __attribute__((ext_vector_type(2)));   // both coordinates in one v_pk_add_f32 / v_pk_mul_f32
-  const tdr_v2f offv = {off0, off1};
-  unsigned moff[SKIP ? U : 1];   // SKIP: byte offset (from crec) of the known-mask word of sample u's cell ...
-  int mbit[SKIP ? U : 1];        // ... and the cell's column (its low 5 bits: the bit in that word)
-  const int mconst = (int)a.kmask_off + a.kmask_row + 128;   // kmask_offset
-  auto cell_offset = [&](float2 t, int u) -> unsigned {
-    tdr_v2f pv = {t.x, t.y};
-    if constexpr (!USCALE) pv = (pv * scale) * a.res;  // top_down_map_polar.cpp:28
-    pv = pv + offv;                                     // :29-30
-    // clamp into the guard ring, then round like `pts.round().cast<int>()` (:31): roundf(x) == floor(fl(x + (0.5 - 2^-25)))
-    // on [-1, 2^23] (round_half_away_clamped), the addition done for both coordinates at once
-    tdr_v2f qv = {__builtin_amdgcn_fmed3f(pv.x, -1.f, rmaxf), __builtin_amdgcn_fmed3f(pv.y, -1.f, cmaxf)};
-    qv = qv + 0.49999997f;
-    int ri, ci;
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ri) : "v"(qv.x));
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ci) : "v"(qv.y));
-    if constexpr (SKIP) {
-      moff[u] = kmask_offset(ri, ci, a.kmask_row, mconst);
-      mbit[u] = ci;
-    }
-    if constexpr (COMPACT) {
-      // cells of the guard ring are zero records in their own right (distance 0, unknown): no select needed
-      return cmap_offset<CW, LC>(ri, ci, ckcol, ckconst);
-    } else {
-#if TDR_OOB_ALIAS
-      // every out-of-bounds sample reads the SAME guard record (always cache-resident) instead of a distinct one
-      const bool inb = (unsigned)ri < (unsigned)a.rows && (unsigned)ci < (unsigned)a.cols;
-      return inb ? (unsigned)(__mul24(ri, rowstride) + (ci * (RF * 4) + kbase)) : 0u;
-#else
-      return (unsigned)(__mul24(ri, rowstride) + (ci * (RF * 4) + kbase));  // v_mad_i32_i24 + v_lshl_add
-#endif
-    }
-  };
-  // the record at `off` as the RF operands of the product sums (compact: decoded, bit-identical to the dense record)
-  struct Raw { uint32_t w[COMPACT ? CW : 1]; float4 q[COMPACT ? 1 : NV4]; };
-  auto load_raw = [&](unsigned off, Raw& r) {
-    if constexpr (COMPACT) cmap_load<CW>(crecb, off, r.w);
-    else {
-#pragma unroll
-      for (int v = 0; v < NV4; v++) r.q[v] = *reinterpret_cast<const float4*>(recb + off + 16 * v);
-    }
-  };
-  auto operands = [&](const Raw& r, float (&m)[RF]) {
-    if constexpr (WIDE) cmap_decode_wide<RF, KSLOT>(r.w, ldict, m);
-    else if constexpr (COMPACT) cmap_decode<RF, KSLOT>(r.w, ldict, m);
-    else {
-#pragma unroll
-      for (int v = 0; v < NV4; v++) { m[4 * v] = r.q[v].x; m[4 * v + 1] = r.q[v].y; m[4 * v + 2] = r.q[v].z; m[4 * v + 3] = r.q[v].w; }
-    }
-  };
-
-  float acc[RF];
-#pragma unroll
-  for (int k = 0; k < RF; k++) acc[k] = 0.f;
-  float known = 0.f;
-  // U samples per step: all addresses first, then all loads (map records + LDS scan records) in flight together, then
-  // the FMAs.  The order of the FMAs — direction i ascending, ring ascending within it — is the same in every
-  // instantiation and independent of U and of the launch: results are a pure function of the inputs.
-  auto step = [&](auto full_step, const unsigned (&boff)[U], const float4* const (&sp)[U], int cnt) {
-    constexpr bool FULL = decltype(full_step)::value;   // all U samples are real: no per-sample predicate
-    Raw raw[U];
-    float4 s[U][NV4];
-    if constexpr (SKIP) {
-      // the scan records first: a lane whose bin is empty in every class asks for the mask word instead of the record
-#pragma unroll
-      for (int u = 0; u < U; u++)
-        if (FULL || u < cnt) {
-#pragma unroll
-          for (int v = 0; v < NV4; v++) s[u][v] = sp[u][v];
-        }
-      bool empty[U];
-#pragma unroll
-      for (int u = 0; u < U; u++)
-        if (FULL || u < cnt) {
-          constexpr int ND = CmapShape<RF, KSLOT>::ND;
-          uint32_t any = 0;
-#pragma unroll
-          for (int k = 0; k < ND; k++) {
-            const float4 q = s[u][k / 4];
-            any |= __float_as_uint(k % 4 == 0 ? q.x : (k % 4 == 1 ? q.y : (k % 4 == 2 ? q.z : q.w)));
-          }
-          empty[u] = skip_ok && any == 0;
-          load_raw(empty[u] ? moff[u] : boff[u], raw[u]);
-        }
-#pragma unroll
-      for (int u = 0; u < U; u++)
-        if (FULL || u < cnt) {
-          // an empty bin's "record": dictionary entry 0 for every distance, the known bit from the mask
-          const uint32_t kb = (raw[u].w[0] >> (mbit[u] & 31)) & 1u;
-#pragma unroll
-          for (int d = 0; d < CW; d++) raw[u].w[d] = empty[u] ? kb : raw[u].w[d];
-        }
-    } else {
-#pragma unroll
-      for (int u = 0; u < U; u++)
-        if (FULL || u < cnt) load_raw(boff[u], raw[u]);
-#pragma unroll
-      for (int u = 0; u < U; u++)
-        if (FULL || u < cnt) {
-#pragma unroll
-          for (int v = 0; v < NV4; v++) s[u][v] = sp[u][v];
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      if (FULL || u < cnt) {
-        float m[RF];
-        operands(raw[u], m);
-#pragma unroll
-        for (int v = 0; v < NV4; v++) {
-          acc[4 * v + 0] = __builtin_fmaf(s[u][v].x, m[4 * v + 0], acc[4 * v + 0]);
-          acc[4 * v + 1] = __builtin_fmaf(s[u][v].y, m[4 * v + 1], acc[4 * v + 1]);
-          acc[4 * v + 2] = __builtin_fmaf(s[u][v].z, m[4 * v + 2], acc[4 * v + 2]);
-          acc[4 * v + 3] = __builtin_fmaf(s[u][v].w, m[4 * v + 3], acc[4 * v + 3]);
-        }
-        if (!KSLOT) known += m[RF - 1];
-      }
-  };
-  if (gn >= U) {
-    // ray-major: consecutive samples of a lane are consecutive cells along one ray
-    const int gfull = gn - gn % U;
-    for (int i = 0; i < nb; i++) {
-      int row = i + shift;
-      row -= row >= nb ? nb : 0;
-      const float4* const rl = ring + __mul24(row, rs);
-      for (int jj = 0; jj < gfull; jj += U) {
-        unsigned boff[U];
-        const float4* sp[U];
-        const float4* const rj = rl + jj * NV4;
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-          boff[u] = cell_offset(tab_at((int64_t)(j0 + jj + u) * nb + i), u);
-          sp[u] = rj + u * NV4;
-        }
-        step(std::true_type{}, boff, sp, U);
-      }
-    }
-    if (gfull < gn) {   // the group's last rings when gn is not a multiple of U: a pass of their own over the directions
-      for (int i = 0; i < nb; i++) {
-        int row = i + shift;
-        row -= row >= nb ? nb : 0;
-        const float4* const rl = ring + __mul24(row, rs);
-        unsigned boff[U];
-        const float4* sp[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-          const int jc = min(gfull + u, gn - 1);
-          boff[u] = cell_offset(tab_at((int64_t)(j0 + jc) * nb + i), u);
-          sp[u] = rl + jc * NV4;
-        }
-        step(std::false_type{}, boff, sp, gn - gfull);
-      }
-    }
-  } else {
-    // fewer rings than loads to keep in flight (very long rows): U consecutive directions of one ring at a time
-    for (int jj = 0; jj < gn; jj++) {
-      const float4* const rj = ring + jj * NV4;
-      for (int i = 0; i < nb; i += U) {
-        unsigned boff[U];
-        const float4* sp[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-          const int ic = min(i + u, nb - 1);
-          int row = ic + shift;
-          row -= row >= nb ? nb : 0;
-          boff[u] = cell_offset(tab_at((int64_t)(j0 + jj) * nb + ic), u);
-          sp[u] = rj + __mul24(row, rs);
-        }
-        step(std::false_type{}, boff, sp, min(U, nb - i));
-      }
-    }
-  }
-  if (sbase + slot < a.npad) {
-    float* o = a.part + (int64_t)blockIdx.y * (RF + 1) * a.npad + sbase + slot;
-#pragma unroll
-    for (int k = 0; k < RF; k++) o[(int64_t)k * a.npad] = acc[k];
-    o[(int64_t)RF * a.npad] = KSLOT ? acc[RF - 2] : known;
-  }
-#ifdef TDR_SCORE_TIMELINE
-  __syncthreads();
-  if (threadIdx.x == 0 && tl_id < TDR_TL_MAX) g_timeline[2 * tl_id + 1] = wall_clock64();
-#endif
-}
-
-// score_polar_kernel's body for workgroup (bx, by), for score_polar_batch_kernel (one grid over many filters).  A copy
-// rather than a shared function: the existing kernel keeps its own text, so it compiles to the same code as before.
+// The body for workgroup (bx, by) of the launch: score_polar_kernel and score_polar_batch_kernel (one grid over many
+// filters) both call it.
 template <int NV4, int U, bool KSLOT, bool USCALE, bool COMPACT, bool WIDE = false, bool SKIP = false>
 __device__ __forceinline__ void score_polar_body(const ScoreArgs& a, const unsigned bx, const unsigned by) {
   constexpr int RF = 4 * NV4;
@@ -596,20 +331,25 @@ __device__ __forceinline__ void score_polar_body(const ScoreArgs& a, const unsig
   if (threadIdx.x == 0 && tl_id < TDR_TL_MAX) g_timeline[2 * tl_id + 1] = wall_clock64();
 #endif
 }
+template <int NV4, int U, bool KSLOT, bool USCALE, bool COMPACT, bool WIDE = false, bool SKIP = false>
+__global__ __launch_bounds__(256, COMPACT ? (WIDE ? 3 : 5) : 1) void score_polar_kernel(ScoreArgs a) {
+#if TDR_XCD_SWIZZLE
+  // Workgroups are dealt round-robin over the 8 XCDs; remap so that each XCD (its own L2) gets a contiguous run of
+  // particle batches (Morton neighbours) instead of every 8th one.  Speed only: any mapping gives the same results.
+  const unsigned nbx = gridDim.x, per = (nbx + 7) / 8;
+  unsigned bx = (blockIdx.x % 8) * per + blockIdx.x / 8;
+  if (nbx % 8 != 0) bx = blockIdx.x;  // keep it a bijection
+#else
+  const unsigned bx = blockIdx.x;
+#endif
+  score_polar_body<NV4, U, KSLOT, USCALE, COMPACT, WIDE, SKIP>(a, bx, blockIdx.y);
+}
 // batched filters (tdr_batch_step): filter e owns the blocks [blk[e], blk[e + 1]) of grid.x and grid.y rows
 // [0, its nchunks); its ScoreArgs are args[e].  Filters whose USCALE differs from the instantiation's are another launch.
-__device__ __forceinline__ int batch_find(const int32_t* __restrict__ blk, int k, int b) {
-  int lo = 0, hi = k - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (blk[mid] <= b) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 template <int NV4, int U, bool KSLOT, bool USCALE, bool COMPACT, bool WIDE = false>
 __global__ __launch_bounds__(256, COMPACT ? (WIDE ? 3 : 5) : 1) void score_polar_batch_kernel(const ScoreArgs* __restrict__ args,
                                                                                               const int32_t* __restrict__ blk, int k) {
-  const int e = batch_find(blk, k, (int)blockIdx.x);
+  const int e = batch_find(k, (int)blockIdx.x, [&](int i) { return blk[i]; });
   const ScoreArgs a = args[e];
   if ((int)blockIdx.y >= a.nchunks || (a.utab != nullptr) != USCALE) return;   // (uniform)
   score_polar_body<NV4, U, KSLOT, USCALE, COMPACT, WIDE, false>(a, blockIdx.x - (unsigned)blk[e], blockIdx.y);
@@ -885,102 +625,7 @@ struct FinalizeArgs {
   int ray_split = 1;
 };
 
-__global__ __launch_bounds__(256) void score_finalize_kernel(FinalizeArgs a) {
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int T = 1 << a.tlog, t = (int)(gid & (T - 1));
-  const int64_t slot = gid >> a.tlog;
-  if (a.run_if && !int_form_off(a.run_if)) return;
-  const int64_t nact = a.count ? (int64_t)*a.count : a.n;
-  if (slot >= nact) return;
-  const int64_t p = a.order ? (int64_t)a.order[slot] : slot;
-  if (p < 0) return;   // a padding slot of the shift-uniform order (tdr_score_su.h)
-  const float scale = a.st[TDR_ST_SCALE * a.cap + p];
-  const float cx = a.st[TDR_ST_DX * a.cap + p] * scale + a.st[TDR_ST_INIT_X * a.cap + p];
-  const float cy = a.st[TDR_ST_DY * a.cap + p] * scale + a.st[TDR_ST_INIT_Y * a.cap + p];
-  if (a.mode == 0 && particle_gated(a.gate, cx, cy, scale)) {
-    a.raw_w[p] = 0.f;
-    return;
-  }
-  if (a.mode == 1 && a.only_uninit && a.st[TDR_ST_HAVE_INIT * a.cap + p] != 0.f) return;
-  // Per-chunk partial sums -> double totals, chunk order ascending.  The loads of FIN_B chunks x all slots are issued
-  // together (independent addresses, coalesced over the particles) before the dependent additions.  A small particle
-  // set has many chunks and few slots — 128 x 1000 at the reference's test size — and one lane per slot would wait for
-  // memory 32 times in a row: there 2^tlog neighbouring lanes take a contiguous share of a slot's chunks each and
-  // their double totals are added up in a fixed butterfly.
-  constexpr int FIN_B = 4, FIN_S = TDR_MAX_CLASSES + 2;   // slots: ncls class dots, normalisation, known count
-  double tot[FIN_S];
-#pragma unroll
-  for (int k = 0; k < FIN_S; k++) tot[k] = 0;
-  const int64_t cstride = (int64_t)(a.rf + 1) * a.npad;
-  auto slot_row = [&](int k) { return k < a.ncls ? k : (k == a.ncls ? a.rf - 1 : a.rf); };
-  const int share = (a.nchunks + T - 1) >> a.tlog, cend = min(a.nchunks, (t + 1) * share);
-  int c0 = t * share;
-  for (; c0 + FIN_B <= cend; c0 += FIN_B) {
-    float v[FIN_B][FIN_S];
-#pragma unroll
-    for (int b = 0; b < FIN_B; b++)
-#pragma unroll
-      for (int k = 0; k < FIN_S; k++)
-        if (k < a.ncls + 2) v[b][k] = a.part[(int64_t)(c0 + b) * cstride + (int64_t)slot_row(k) * a.npad + slot];
-#pragma unroll
-    for (int b = 0; b < FIN_B; b++)
-#pragma unroll
-      for (int k = 0; k < FIN_S; k++)
-        if (k < a.ncls + 2) tot[k] += (double)v[b][k];
-  }
-  for (; c0 < cend; c0++) {
-#pragma unroll
-    for (int k = 0; k < FIN_S; k++)
-      if (k < a.ncls + 2) tot[k] += (double)a.part[(int64_t)c0 * cstride + (int64_t)slot_row(k) * a.npad + slot];
-  }
-  if (T > 1) {   // (the lanes of a slot left or stayed together above)
-    for (int sft = T >> 1; sft >= 1; sft >>= 1)
-#pragma unroll
-      for (int k = 0; k < FIN_S; k++)
-        if (k < a.ncls + 2) tot[k] += __shfl_xor(tot[k], sft, 64);
-    if (t != 0) return;
-  }
-  double known = 0, norm = 0;
-#pragma unroll
-  for (int k = 0; k < FIN_S; k++) {
-    if (k == a.ncls) norm = tot[k];
-    if (k == a.ncls + 1) known = tot[k];
-  }
-  // known fraction gate (state_particle.cpp:117-120); counts are exact integers in float
-  float cost;
-  if ((float)known / (float)a.P < 0.5) {
-    cost = __builtin_nanf("");
-  } else {
-    cost = 0.f;
-#pragma unroll
-    for (int k = 0; k < TDR_MAX_CLASSES; k++)
-      if (k < a.ncls) cost = (float)((double)cost + (double)(float)tot[k] * 0.01 * (double)a.fp.class_weights[k]);  // :136-139
-    float normf = (float)norm;
-    if (a.gpart) {   // :145-152: cost += (geo_i . geo_cls_i) * 0.01; normalization += geo_i.sum()
-      double g[2] = {0, 0};
-      const int64_t gstride = (int64_t)5 * a.npad;
-      for (int c0g = 0; c0g < a.gnchunks; c0g++) {
-        g[0] += (double)a.gpart[(int64_t)c0g * gstride + slot];
-        g[1] += (double)a.gpart[(int64_t)c0g * gstride + a.npad + slot];
-      }
-      cost = (float)((double)cost + (double)(float)g[0] * 0.01);
-      normf = normf + a.gsum0;
-      cost = (float)((double)cost + (double)(float)g[1] * 0.01);
-      normf = normf + a.gsum1;
-    }
-    cost = cost / normf;  // :154
-  }
-  if (a.mode == 0) {
-    a.raw_w[p] = (float)(1. / (double)(cost + a.fp.regularization));  // :212
-  } else {
-    float best = a.first ? 3.402823466e+38f : a.best_cost[slot];
-    float bt = a.first ? 0.f : a.best_theta[slot];
-    if (cost < best) { best = cost; bt = a.theta_override; }  // :200-203 (NaN never wins)
-    a.best_cost[slot] = best;
-    a.best_theta[slot] = bt;
-  }
-}
-// score_finalize_kernel's body for thread gid, for score_finalize_batch_kernel (a copy, like score_polar_body)
+// the body of score_finalize_kernel and of score_finalize_batch_kernel, for thread gid of the launch
 __device__ __forceinline__ void score_finalize_body(const FinalizeArgs& a, const int64_t gid) {
   const int T = 1 << a.tlog, t = (int)(gid & (T - 1));
   const int64_t slot = gid >> a.tlog;
@@ -1075,9 +720,12 @@ __device__ __forceinline__ void score_finalize_body(const FinalizeArgs& a, const
     a.best_theta[slot] = bt;
   }
 }
+__global__ __launch_bounds__(256) void score_finalize_kernel(FinalizeArgs a) {
+  score_finalize_body(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
 __global__ __launch_bounds__(256) void score_finalize_batch_kernel(const FinalizeArgs* __restrict__ args,
                                                                    const int32_t* __restrict__ blk, int k) {
-  const int e = batch_find(blk, k, (int)blockIdx.x);
+  const int e = batch_find(k, (int)blockIdx.x, [&](int i) { return blk[i]; });
   const FinalizeArgs a = args[e];
   score_finalize_body(a, (int64_t)(blockIdx.x - (unsigned)blk[e]) * blockDim.x + threadIdx.x);
 }
