@@ -1,26 +1,44 @@
-// tdr_prefix.hip — the serial float32 running sum of the resampling step, reproduced bit-exactly in parallel.
+// tdr_prefix.hip — the serial float32 chains of the filter step, reproduced bit-exactly in parallel: the running sum of
+// the resample (particle_filter.cpp:179, every prefix is written) and the two statistics chains of the update (`sum`,
+// `bottom_stddev`, :108-126, only the totals are used).
 #include "tdr_common.h"
 #include "tdr_batch.h"
 
-// ------------------------------------------------------------------------------------------------------------------
-// K5: resample.  The running sum of particle_filter.cpp:179 is a serial float32 chain,
-//     prefix_j = fl(prefix_{j-1} + w_j),
-// and "bit-exact resample indices" needs exactly these values.  Two kernels produce them:
+// Map of the file: entry point -> kernels, by n, and the switch that reaches each path.
 //
-//  * prefix_serial_kernel — one wave, lane 0 performs the additions in index order (weights staged through LDS).
-//    Simple, ~10 ns per element; kept as the reference implementation and for small n.
-//  * prefix_exact_kernel — the same values computed in parallel.  While the running sum r stays inside one binade
-//    [2^e, 2^(e+1)) it is an integer multiple R*u of u = 2^(e-23) and fl(r + w) = (R + q)*u, where q is w/u rounded
-//    to nearest — a pure integer increment that depends on r only when w/u ends in exactly .5 (tie to even: the parity
-//    of R + floor(w/u)).  So per tile of 4096 weights the workgroup (i) classifies every weight into an integer
-//    increment / tie / "needs a real float add" (NaN, inf, larger than the binade), (ii) prefix-sums the increments,
-//    (iii) resolves the (rare) ties in order on one thread, (iv) prefix-sums the tie corrections, (v) finds the first
-//    element at which the sum leaves the binade or a real add is needed, commits everything before it, performs that
-//    one addition in float arithmetic and restarts behind it in the new binade.  A running sum of 1 crosses ~24
-//    binades, so a million weights take a few hundred workgroup passes instead of a million dependent additions.
-//    tests/test_gpu_parity.py compares both kernels with the CPU chain bit for bit on random and adversarial inputs.
+//  tdr_k_prefix (running sum + running maximum; tdr_k_prefix_mode forces a path)
+//    256 <= n <= 32 768                   pfx_small_kernel: one launch, one workgroup, weights in LDS          mode 3
+//    n >= 6144 with a workspace           prefix_multi: pfx_chunk_sum_kernel -> pfx_chunk_summary_kernel ->    mode 2
+//                                         [pfx_small_kernel over the first 32 768 weights when n >= 32 768] ->
+//                                         pfx_walk_kernel -> pfx_chunk_fill_kernel
+//    n < 24 576 otherwise                 prefix_serial_kernel: one wave, lane 0 adds in index order           mode 0
+//    else                                 prefix_exact_kernel: one workgroup, the older tie-list algorithm     mode 1
+//    tdr_config_prefix_small(0): no pfx_small_kernel (and no chain_head_kernel): the chunk walks start at the first addend
+//    tdr_config_prefix_head(n): addends pfx_walk_kernel hands to the serial head of pfx_exact_range at the very start
+//  tdr_uw_small (the update's statistics, n <= 32 768)
+//    uw_small_kernel<true>: the chains wave by wave (default); <false>: chunk by chunk on the whole workgroup
+//    (tdr_config_uw_waves(0))
+//  tdr_chain_total (one statistics chain, n > 32 768; called from tdr_filter.hip)
+//    chain_sum_kernel -> chain_summary_kernel -> [chain_head_kernel<kind> over the first 32 768 addends] -> chain_walk_kernel
+//  tdr_batch_update_weights / tdr_batch_prefix: uw_small_batch_kernel / pfx_small_batch_kernel, one workgroup per filter
 //
-// The running maximum makes "first j with prefix_j > sample" searchable even when weights are negative (NaN fill, :133).
+// Order of the file: the one-wave serial kernel; the one-workgroup tie-list kernel; the parity-pair chain step and
+// what it is made of (written once, used by every kernel behind it); the multi-workgroup kernels; the one-workgroup
+// kernels; dispatch.  tests/test_gpu_parity.py compares every path with the CPU chains bit for bit.
+//
+// ---- one wave, serially --------------------------------------------------------------------------------------------------
+// prefix_serial_kernel: lane 0 performs the additions in index order (weights staged through LDS).  Simple, ~10 ns per
+// element; kept as the reference implementation and for small n.  The running maximum makes "first j with prefix_j >
+// sample" searchable even when weights are negative (NaN fill, :133).
+//
+// prefix_exact_kernel (below it): while the running sum r stays inside one binade [2^e, 2^(e+1)) it is an integer
+// multiple R*u of u = 2^(e-23) and fl(r + w) = (R + q)*u, where q is w/u rounded to nearest — a pure integer increment
+// that depends on r only when w/u ends in exactly .5 (tie to even: the parity of R + floor(w/u)).  Per tile of 8192
+// weights the workgroup (i) classifies every weight into an integer increment / tie / "needs a real float add" (NaN,
+// inf, larger than the binade), (ii) prefix-sums the increments, (iii) resolves the (rare) ties in order on one thread,
+// (iv) prefix-sums the tie corrections, (v) finds the first element at which the sum leaves the binade or a real add
+// is needed, commits everything before it, performs that one addition in float arithmetic and restarts behind it in
+// the new binade.  It handles every running sum (negative, subnormal, inf, NaN) and weights of either sign.
 #define TDR_PFX_BLOCK 4096  // elements staged in LDS per pass (64 per lane)
 __global__ __launch_bounds__(64) void prefix_serial_kernel(const float* __restrict__ w, int64_t n,
                                                            float* __restrict__ runmax) {
@@ -80,7 +98,7 @@ __global__ __launch_bounds__(64) void prefix_serial_kernel(const float* __restri
   }
 }
 
-// ---- exact parallel prefix -------------------------------------------------------------------------------------------
+// ---- exact parallel prefix in one workgroup: the tie-list algorithm (mode 1; the chunk walk's general fallback) -------------------------------------------------------------------------------------------
 #define PFX_THREADS 1024
 #define PFX_K 8
 #define PFX_TILE (PFX_THREADS * PFX_K)
@@ -418,22 +436,19 @@ __global__ __launch_bounds__(PFX_THREADS) void prefix_exact_kernel(const float* 
   pfx_exact_range<PFX_THREADS>(w, 0, n, runmax, prefix_opt, r, carry);
 }
 
-// ---- exact parallel prefix over many workgroups ---------------------------------------------------------------------
-// Inside one binade (ulp u) the chain r <- fl(r + w) with w >= 0 is R <- R + a(R & 1): the increment of one element is
-// an integer that depends on the running mantissa only through its PARITY (round-half-even ties).  A run of elements is
+// ==== exact chains over parity pairs ===================================================================================
+// Inside one binade (ulp u) the chain r <- fl(r + x) with x >= 0 is R <- R + a(R & 1): the increment of one addend is
+// an integer that depends on the running mantissa only through its PARITY (round-half-even ties).  A run of addends is
 // therefore summarised by two integers (D0, D1) — its total increment entered with an even / odd mantissa — and
-// summaries compose associatively: (A then B)_p = A_p + B_{(p + A_p) & 1}.  That turns the chain into a scan:
-//   1. pfx_chunk_sum_kernel      — per chunk of PFXM_CHUNK weights: the sum in double
-//   2. pfx_chunk_summary_kernel  — per chunk: binade predicted from the double sum of everything before it; (D0, D1) in
-//                                  that binade, or "irregular" (NaN / inf / negative / weight above the binade)
-//   3. pfx_walk_kernel           — ONE workgroup walks the chunks in order with the exact running sum: a chunk whose
-//                                  prediction holds (same binade, R + D_p stays below 2^24) is a single integer add;
-//                                  any other chunk (the ~log2(n) binade crossings, irregular weights, the head) is
-//                                  processed on the spot by pfx_exact_range
-//   4. pfx_chunk_fill_kernel     — per accepted chunk: the same scan again, now with the exact starting mantissa,
-//                                  writes every element's running sum / running maximum
-// Every value written is the serial float32 chain's, whatever the prediction was: a wrong prediction only sends the
-// chunk down the slower path.
+// summaries compose associatively: (A then B)_p = A_p + B_{(p + A_p) & 1}.  That turns a chain into a scan plus one real
+// addition at every binade crossing.  Everything below is built from four pieces, each written once:
+//   ChainAddend   what a chain adds: value type, where element i comes from, its classification in a binade, the real add
+//   chain_step    one stretch inside a binade: classify, compose and scan the pairs, rebuild every mantissa, find the first
+//                 addend that needs a real addition
+//   chain_walk    a chunk: steps, what lies before each stop committed to a sink, the real additions in between
+//   chain_head_*  the leading addends one by one (the sum starts at zero and doubles every few addends)
+// Every value produced is the serial float32 chain's, whatever a prediction was: a wrong one only sends a chunk down the
+// slower path.
 #define PFXM_THREADS 256
 #define PFXM_K 16
 #define PFXM_CHUNK (PFXM_THREADS * PFXM_K)
@@ -446,7 +461,28 @@ struct PfxChunk {     // 32 bytes per chunk in the caller's workspace
   int accepted;       // 3: 1 = pfx_chunk_fill_kernel writes this chunk's outputs
 };
 static_assert(sizeof(PfxChunk) == 32, "PfxChunk");
+#ifndef PFXW_THREADS
+#define PFXW_THREADS 512   // the walking workgroup: PFXW_THREADS x PFXW_K = one chunk (two waves per SIMD: the dependent
+#endif                     // instruction chains of one wave hide behind the other's)
+#define PFXW_K (PFXM_CHUNK / PFXW_THREADS)
+#define CHAIN_K PFXW_K            // addends per lane of a walking wave
+#define UWS_WC (64 * CHAIN_K)     // addends per wave-chunk
+#define PFXM_RE_MIN 24            // binades (biased exponent, sign bit included) a step works in: positive normal sums
+#define PFXM_RE_MAX 254           // whose ulp's reciprocal 2^(150 - re) is a normal float
 
+#ifdef TDR_UW_TIMELINE   // diagnostic build: 100 MHz time stamps at the phase boundaries of uw_small_kernel
+__device__ unsigned long long g_uw_tl[16];
+extern "C" int tdr_debug_read_uw_timeline(unsigned long long* out) {
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_uw_tl), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : -1;
+}
+#define UW_STAMP(k) do { __syncthreads(); if (threadIdx.x == 0) g_uw_tl[k] = wall_clock64(); } while (0)
+#define UW_COUNT(k) do { if (threadIdx.x == 0) g_uw_tl[k]++; } while (0)
+#else
+#define UW_STAMP(k) do { } while (0)
+#define UW_COUNT(k) do { } while (0)
+#endif
+
+// ---- parity pairs and their scans ---------------------------------------------------------------------------------------
 struct PfxPair { unsigned a0, a1; };
 __device__ __forceinline__ unsigned pfx_sat(unsigned x) { return x > PFXM_SAT ? PFXM_SAT : x; }
 // first A, then B
@@ -456,31 +492,20 @@ __device__ __forceinline__ PfxPair pfx_compose(PfxPair A, PfxPair B) {
   c.a1 = pfx_sat(A.a1 + ((A.a1 & 1u) ? B.a0 : B.a1));   // entered odd: the parity after A is (1 + A.a1) & 1
   return c;
 }
-// One weight against the binade of a running sum with biased exponent `re` (PFXM_RE_MIN <= re <= PFXM_RE_MAX), ulp
-// u = 2^(re-150): f = round-half-down(w/u), tie = the remainder is exactly one half, bad = cannot be an integer increment
-// (NaN, inf, negative, or at least twice the binade's lower end).  w * 2^(150-re) is exact (a power-of-two scaling
-// inside the normal range; a product that underflows is far below one half anyway), and so are floor and the
-// remainder, so this is the integer classification of pfx_exact_range in a handful of float operations.
-#define PFXM_RE_MIN 24
-#define PFXM_RE_MAX 254
-__device__ __forceinline__ void pfx_classify(float wv, unsigned re, unsigned& f, bool& tie, bool& bad) {
-  const float scale = __uint_as_float((277u - re) << 23);   // 2^(150 - re) = 1/u
-  const float t = wv * scale;
-  bad = !(wv >= 0.f) || !(t < 16777216.f);
-  const float fl = floorf(t);
-  const float fr = t - fl;
-  tie = fr == 0.5f;
-  f = (unsigned)fl + (fr > 0.5f ? 1u : 0u);
-  if (bad) { f = 0; tie = false; }
-}
 __device__ __forceinline__ PfxPair pfx_element_pair(unsigned f, bool tie) {
   PfxPair p;
   p.a0 = f + (tie ? (f & 1u) : 0u);         // even mantissa + f + 1/2 -> the even neighbour
   p.a1 = f + (tie ? ((f & 1u) ^ 1u) : 0u);
   return p;
 }
-// inclusive scan of per-thread pairs over a workgroup of NT threads; returns the EXCLUSIVE pair of this thread and the
-// workgroup total.  `sh` holds one slot per wave; safe to call repeatedly (leading barrier).
+// the pair of one lane's K consecutive addends (increments f, bit k of tiebits: addend k is a rounding tie)
+template <int K>
+__device__ __forceinline__ PfxPair chain_lane_pair(const unsigned (&f)[K], unsigned tiebits) {
+  PfxPair mine = {0u, 0u};
+#pragma unroll
+  for (int k = 0; k < K; k++) mine = pfx_compose(mine, pfx_element_pair(f[k], ((tiebits >> k) & 1u) != 0u));
+  return mine;
+}
 // Inclusive wave scan of pairs with data-parallel-primitive moves instead of LDS permutes (each __shfl_up is a
 // ds_bpermute: ~100 clocks of latency, twelve of them in a row per scan).  Lanes without a source lane receive the
 // identity pair {0, 0} (compose({0,0}, v) == v), so no lane predicate is needed.  Steps: shift right by 1, 2, 4, 8
@@ -501,6 +526,8 @@ __device__ __forceinline__ PfxPair pfx_pair_wave_scan(PfxPair v) {
   v = pfx_compose(pfx_pair_dpp<0x143, 0xC>(v), v);   // row_bcast:31 into rows 2 and 3
   return v;
 }
+// inclusive scan of per-thread pairs over a workgroup of NT threads; returns the EXCLUSIVE pair of this thread and the
+// workgroup total.  `sh` holds one slot per wave; safe to call repeatedly (leading barrier).
 template <int NT>
 __device__ __forceinline__ PfxPair pfx_pair_scan(PfxPair v, PfxPair* sh, PfxPair& total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -520,674 +547,7 @@ __device__ __forceinline__ PfxPair pfx_pair_scan(PfxPair v, PfxPair* sh, PfxPair
   PfxPair ex = pfx_pair_dpp<0x138, 0xF>(v);
   return pfx_compose(pre, ex);
 }
-template <int K>
-__device__ __forceinline__ void pfx_load_chunk(const float* __restrict__ w, long long lo, int cnt, float (&wv)[K]) {
-  const int t0 = threadIdx.x * K;
-  if (t0 + K <= cnt && ((lo & 3) == 0)) {
-    const float4* p = reinterpret_cast<const float4*>(w + lo + t0);
-#pragma unroll
-    for (int k = 0; k < K / 4; k++) {
-      const float4 v = p[k];
-      wv[4 * k] = v.x; wv[4 * k + 1] = v.y; wv[4 * k + 2] = v.z; wv[4 * k + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < K; k++) wv[k] = (t0 + k < cnt) ? w[lo + t0 + k] : 0.f;
-  }
-}
-
-__global__ __launch_bounds__(PFXM_THREADS) void pfx_chunk_sum_kernel(const float* __restrict__ w, int64_t n,
-                                                                     PfxChunk* __restrict__ ch) {
-  __shared__ double shd[PFXM_THREADS / 64];
-  const long long lo = (long long)blockIdx.x * PFXM_CHUNK;
-  const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
-  float wv[PFXM_K];
-  pfx_load_chunk(w, lo, cnt, wv);
-  double acc = 0.0;
-#pragma unroll
-  for (int k = 0; k < PFXM_K; k++) acc += (double)wv[k];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) shd[threadIdx.x >> 6] = acc;
-  pfx_sync();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int k = 0; k < PFXM_THREADS / 64; k++) t += shd[k];
-    ch[blockIdx.x].sum = t;
-  }
-}
-
-__global__ __launch_bounds__(PFXM_THREADS) void pfx_chunk_summary_kernel(const float* __restrict__ w, int64_t n,
-                                                                         PfxChunk* __restrict__ ch, int c_first) {
-  __shared__ double shd[PFXM_THREADS / 64];
-  __shared__ PfxPair shp[PFXM_THREADS / 64];
-  __shared__ int s_bad;
-  const int c = blockIdx.x + c_first;   // (the chunks before c_first are not walked, see prefix_multi)
-  const long long lo = (long long)c * PFXM_CHUNK;
-  const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
-  // predicted running sum before the chunk: the double sums of the chunks before it, in chunk order per thread
-  double acc = 0.0;
-  for (int j = threadIdx.x; j < c; j += PFXM_THREADS) acc += ch[j].sum;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) shd[threadIdx.x >> 6] = acc;
-  if (threadIdx.x == 0) s_bad = 0;
-  pfx_sync();
-  double before = 0.0;
-  for (int k = 0; k < PFXM_THREADS / 64; k++) before += shd[k];
-  const float r_pred = (float)before, r_end = (float)(before + ch[c].sum);
-  const unsigned pb = __float_as_uint(r_pred), eb = __float_as_uint(r_end);
-  const int re = (pb >> 23) & 0xFF;
-  // a chunk that is predicted to start and end in one binade of a positive normal sum; everything else is irregular
-  const bool plausible = (pb >> 31) == 0 && re >= PFXM_RE_MIN && re <= PFXM_RE_MAX && (int)((eb >> 23) & 0xFF) == re && (eb >> 31) == 0;
-  if (!plausible) {   // uniform across the workgroup
-    if (threadIdx.x == 0) { ch[c].re = -1; ch[c].d0 = 0u; ch[c].d1 = 0u; }
-    return;
-  }
-  float wv[PFXM_K];
-  pfx_load_chunk(w, lo, cnt, wv);
-  PfxPair mine = {0u, 0u};
-  bool anybad = false;
-#pragma unroll
-  for (int k = 0; k < PFXM_K; k++) {
-    unsigned f; bool tie, bad;
-    pfx_classify(wv[k], (unsigned)re, f, tie, bad);
-    anybad |= bad;
-    mine = pfx_compose(mine, pfx_element_pair(f, tie));
-  }
-  if (anybad) s_bad = 1;   // benign race: every writer stores 1; ordered by the barrier inside the scan
-  PfxPair total;
-  (void)pfx_pair_scan<PFXM_THREADS>(mine, shp, total);
-  if (threadIdx.x == 0) {
-    const bool ok = s_bad == 0 && total.a0 < (1u << 24) && total.a1 < (1u << 24);
-    ch[c].re = ok ? re : -1;
-    ch[c].d0 = total.a0;
-    ch[c].d1 = total.a1;
-  }
-}
-
-// A chunk the walk cannot take as one integer add (it holds a binade crossing or an irregular weight, or was
-// mispredicted), carried through in order by the walking workgroup: one scan per stretch between two real float
-// additions.  The walking workgroup has PFXW_THREADS threads holding PFXW_K weights each (two waves per SIMD: the
-// dependent instruction chains of one wave hide behind the other's).  Anything that is not a positive normal running sum goes to
-// pfx_exact_range.
-#ifndef PFXW_THREADS
-#define PFXW_THREADS 512   // the walking workgroup: PFXW_THREADS x PFXW_K = one chunk
-#endif
-#define PFXW_K (PFXM_CHUNK / PFXW_THREADS)
-#define PFXW_HEAD 64   // leading elements the walk adds one by one (tunable: tdr_config_tuning("prefix_head", n))
-static int g_pfx_head = PFXW_HEAD;
-extern "C" int tdr_config_prefix_head(int n) {   // < 0: query only
-  if (n >= 0) g_pfx_head = n < 1 ? 1 : (n > PFX_HEAD ? PFX_HEAD : n);
-  return g_pfx_head;
-}
-__device__ __forceinline__ void pfx_walk_chunk(const float* __restrict__ w, long long lo, int cnt,
-                                               float* __restrict__ runmax, float* __restrict__ prefix_opt,
-                                               float& r, float& carry, int head_len) {
-  __shared__ PfxPair shp[PFXW_THREADS / 64];
-  __shared__ int s_bad, s_cross;
-  __shared__ float s_last, s_wstop;
-  const int tid = threadIdx.x, t0 = tid * PFXW_K;
-  float wv[PFXW_K];
-  pfx_load_chunk(w, lo, cnt, wv);
-  int pos = 0;   // workgroup-uniform: elements before pos are done
-  while (pos < cnt) {
-    const unsigned rb = __float_as_uint(r);
-    const unsigned re = rb >> 23;   // sign included
-    if (!(re >= PFXM_RE_MIN && re <= PFXM_RE_MAX)) {
-      // zero / tiny / huge / negative / inf / NaN running sum: the general path (with its serial head at the very start)
-      const long long a = lo + pos;
-      const long long b = a == 0 ? min((long long)head_len, (long long)cnt) : lo + cnt;
-      pfx_exact_range<PFXW_THREADS>(w, a, b, runmax, prefix_opt, r, carry, head_len);
-      pos = (int)(b - lo);
-      continue;
-    }
-    const unsigned R = (rb & 0x7FFFFFu) | 0x800000u;
-    pfx_sync();
-    if (tid == 0) { s_bad = cnt; s_cross = cnt; s_last = r; s_wstop = 0.f; }
-    pfx_sync();
-    unsigned f[PFXW_K];
-    unsigned tiebits = 0u;
-    PfxPair mine = {0u, 0u};
-    {
-#pragma unroll
-      for (int k = 0; k < PFXW_K; k++) {
-        const int li = t0 + k;
-        bool bad, tie;
-        pfx_classify(wv[k], re, f[k], tie, bad);
-        if (li < pos || li >= cnt) { f[k] = 0u; tie = false; bad = false; }
-        if (bad) atomicMin(&s_bad, li);
-        tiebits |= tie ? (1u << k) : 0u;
-        mine = pfx_compose(mine, pfx_element_pair(f[k], tie));
-      }
-    }
-    PfxPair total;
-    const PfxPair ex = pfx_pair_scan<PFXW_THREADS>(mine, shp, total);
-    unsigned st[PFXW_K];
-    {
-      unsigned state = R + ((R & 1u) ? ex.a1 : ex.a0);
-      int first = cnt;
-#pragma unroll
-      for (int k = 0; k < PFXW_K; k++) {
-        state += f[k] + (((tiebits >> k) & 1u) ? ((state + f[k]) & 1u) : 0u);
-        st[k] = state;
-        const int li = t0 + k;
-        if (li >= pos && li < cnt && state >= (1u << 24)) first = min(first, li);
-      }
-      if (first < cnt) atomicMin(&s_cross, first);
-    }
-    pfx_sync();
-    const int stop = min(s_bad, s_cross);   // first element that needs a real float addition (or cnt)
-    {
-#pragma unroll
-      for (int k = 0; k < PFXW_K; k++) {
-        const int li = t0 + k;
-        if (li >= pos && li < stop) {
-          const float val = __uint_as_float((re << 23) | (st[k] & 0x7FFFFFu));
-          runmax[lo + li] = fmaxf(carry, val);
-          if (prefix_opt) prefix_opt[lo + li] = val;
-          if (li == stop - 1) s_last = val;
-        }
-        if (li == stop) s_wstop = wv[k];
-      }
-    }
-    pfx_sync();
-    r = s_last;                  // the sum after element stop-1 (unchanged when nothing was committed)
-    carry = fmaxf(carry, r);     // increments are non-negative: the last committed value is the largest
-    if (stop < cnt) {
-      const float nr = r + s_wstop;   // particle_filter.cpp:179, one real addition
-      if (nr == nr) carry = fmaxf(carry, nr);
-      if (tid == 0) {
-        runmax[lo + stop] = carry;
-        if (prefix_opt) prefix_opt[lo + stop] = nr;
-      }
-      r = nr;
-      pos = stop + 1;
-    } else {
-      pos = cnt;
-    }
-  }
-}
-
-#define PFXW_BLOCK 512   // chunk summaries / headers staged in LDS at a time
-__global__ __launch_bounds__(PFXW_THREADS) void pfx_walk_kernel(const float* __restrict__ w, int64_t n,
-                                                               PfxChunk* __restrict__ ch, int nch,
-                                                               float* __restrict__ runmax,
-                                                               float* __restrict__ prefix_opt, int head_len,
-                                                               int c_first, const float* __restrict__ tail) {
-  __shared__ int sm_re[PFXW_BLOCK], sm_acc[PFXW_BLOCK];
-  __shared__ unsigned sm_d0[PFXW_BLOCK], sm_d1[PFXW_BLOCK];
-  __shared__ float sm_r0[PFXW_BLOCK], sm_c0[PFXW_BLOCK];
-  // workgroup-uniform; chunks [0, c_first) were done by pfx_small_kernel, which left the sum and the maximum behind them
-  float r = c_first > 0 ? tail[0] : 0.f, carry = c_first > 0 ? tail[1] : -INFINITY;
-  for (int cb = 0; cb < nch; cb += PFXW_BLOCK) {
-    pfx_sync();
-    for (int t = threadIdx.x; t < PFXW_BLOCK && cb + t < nch; t += PFXW_THREADS) {
-      const PfxChunk x = ch[cb + t];
-      sm_re[t] = x.re; sm_d0[t] = x.d0; sm_d1[t] = x.d1;
-    }
-    pfx_sync();
-    const int ce = min(nch, cb + PFXW_BLOCK);
-    for (int c = cb; c < ce; c++) {
-      if (c < c_first) { sm_acc[c - cb] = 0; continue; }
-      const unsigned rb = __float_as_uint(r);
-      const int re = (int)(rb >> 23);                   // sign bit included: a negative sum never matches
-      const unsigned R = (rb & 0x7FFFFFu) | 0x800000u;
-      const unsigned D = (R & 1u) ? sm_d1[c - cb] : sm_d0[c - cb];
-      const bool fast = sm_re[c - cb] == re && R + D < (1u << 24);   // sm_re is in [PFXM_RE_MIN, PFXM_RE_MAX] or -1
-      // the waves run through this loop unsynchronised and all store the same words
-      if (fast) {
-        sm_r0[c - cb] = r; sm_c0[c - cb] = carry; sm_acc[c - cb] = 1;
-        r = __uint_as_float(((unsigned)re << 23) | ((R + D) & 0x7FFFFFu));
-        carry = fmaxf(carry, r);
-      } else {
-        sm_acc[c - cb] = 0;
-        const long long lo = (long long)c * PFXM_CHUNK;
-        const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
-        pfx_walk_chunk(w, lo, cnt, runmax, prefix_opt, r, carry, head_len);
-      }
-#ifdef TDR_PFX_TIMING   // diagnostic build: time stamp (100 MHz) after every chunk in the header's dead `sum` slot
-      if (threadIdx.x == 0) *reinterpret_cast<long long*>(&ch[c].sum) = (long long)wall_clock64();
-#endif
-    }
-    pfx_sync();
-    for (int t = threadIdx.x; t < PFXW_BLOCK && cb + t < nch; t += PFXW_THREADS) {   // for pfx_chunk_fill_kernel
-      PfxChunk* o = ch + cb + t;
-      o->r0 = sm_r0[t];
-      o->carry0 = sm_c0[t];
-      o->accepted = sm_acc[t];
-    }
-  }
-}
-
-__global__ __launch_bounds__(PFXM_THREADS) void pfx_chunk_fill_kernel(const float* __restrict__ w, int64_t n,
-                                                                      const PfxChunk* __restrict__ ch,
-                                                                      float* __restrict__ runmax,
-                                                                      float* __restrict__ prefix_opt) {
-  __shared__ PfxPair shp[PFXM_THREADS / 64];
-  const int c = blockIdx.x;
-  const PfxChunk hdr = ch[c];
-  if (!hdr.accepted) return;   // written by the walk
-  const long long lo = (long long)c * PFXM_CHUNK;
-  const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
-  const unsigned rb = __float_as_uint(hdr.r0);
-  const unsigned re = rb >> 23;
-  const unsigned R = (rb & 0x7FFFFFu) | 0x800000u;
-  float wv[PFXM_K];
-  pfx_load_chunk(w, lo, cnt, wv);
-  unsigned f[PFXM_K];
-  bool tie[PFXM_K];
-  PfxPair mine = {0u, 0u};
-#pragma unroll
-  for (int k = 0; k < PFXM_K; k++) {
-    bool bad;
-    pfx_classify(wv[k], re, f[k], tie[k], bad);
-    mine = pfx_compose(mine, pfx_element_pair(f[k], tie[k]));
-  }
-  PfxPair total;
-  const PfxPair ex = pfx_pair_scan<PFXM_THREADS>(mine, shp, total);
-  unsigned state = R + ((R & 1u) ? ex.a1 : ex.a0);   // the exact mantissa before this thread's first element
-  const int t0 = threadIdx.x * PFXM_K;
-  float val[PFXM_K];
-#pragma unroll
-  for (int k = 0; k < PFXM_K; k++) {
-    state += f[k] + (tie[k] ? ((state + f[k]) & 1u) : 0u);
-    val[k] = __uint_as_float((re << 23) | (state & 0x7FFFFFu));
-  }
-  const float carry = hdr.carry0;
-  if (t0 + PFXM_K <= cnt && ((lo & 3) == 0)) {
-    float4* o = reinterpret_cast<float4*>(runmax + lo + t0);
-#pragma unroll
-    for (int k = 0; k < PFXM_K / 4; k++)
-      o[k] = make_float4(fmaxf(carry, val[4 * k]), fmaxf(carry, val[4 * k + 1]), fmaxf(carry, val[4 * k + 2]),
-                         fmaxf(carry, val[4 * k + 3]));
-    if (prefix_opt) {
-      float4* q = reinterpret_cast<float4*>(prefix_opt + lo + t0);
-#pragma unroll
-      for (int k = 0; k < PFXM_K / 4; k++) q[k] = make_float4(val[4 * k], val[4 * k + 1], val[4 * k + 2], val[4 * k + 3]);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < PFXM_K; k++)
-      if (t0 + k < cnt) {
-        runmax[lo + t0 + k] = fmaxf(carry, val[k]);
-        if (prefix_opt) prefix_opt[lo + t0 + k] = val[k];
-      }
-  }
-}
-
-// ---- totals of serial float32 chains with double addends ---------------------------------------------------------------
-// ParticleFilter::update's statistics are serial chains too (src/particle_filter.cpp:108-126):
-//     sum           : float += float            over the valid (non-NaN) raw weights
-//     bottom_stddev : float += pow(w - mean, 2)  = (float)((double)acc + x), x an exact double, over the weights below the mean
-// Only their FINAL values are used.  Both are evaluated by the scan of this file with the addend as a double made on the
-// fly from (raw, mean): for a float chain r <- (float)((double)r + x) the step is x first rounded to the double grid of
-// the sum's binade — 2^-29 ulp(r), and because R is an integer that rounding does not depend on R — and then to the
-// float grid with the parity rule of pfx_classify.  (A float addend lies on the double grid or is far below half an
-// ulp, so the `sum` chain is the plain float chain.)  Chunks as above: double sum -> predicted binade + parity summary
-// -> one walking workgroup; no fill pass.
-struct ChainSrc {
-  const float* raw;    // raw weights
-  const float* mean;   // device scalar (kind 1)
-  int kind;            // 0: valid raw weights; 1: squared deviations of the weights below the mean
-};
-__device__ __forceinline__ double chain_addend(const ChainSrc& s, long long i, float mean) {
-  const float v = s.raw[i];
-  if (s.kind == 0) return (v != v) ? 0.0 : (double)v;                       // :111-115
-  if (v != v || !(v < mean)) return 0.0;                                    // :120
-  const double d = (double)(v - mean);                                      // float subtraction, then pow(double, 2)
-  return d * d;
-}
-__device__ __forceinline__ void chain_classify(double x, unsigned re, unsigned& f, bool& tie, bool& bad) {
-  const double scale = __longlong_as_double((long long)(1023 + 150 - (int)re) << 52);   // 2^(150 - re) = 1/u
-  const double t = x * scale;
-  bad = !(x >= 0.0) || !(t < 4194304.0);                 // negative / NaN / inf, or not small against the sum: real add
-  const double tg = (t + 8388608.0) - 8388608.0;         // t on the double grid of [2^23, 2^24): multiples of 2^-29
-  const double fl = floor(tg);
-  const double fr = tg - fl;
-  tie = fr == 0.5;
-  f = (unsigned)fl + (fr > 0.5 ? 1u : 0u);
-  if (bad) { f = 0; tie = false; }
-}
-#define CHAIN_K (PFXM_CHUNK / PFXW_THREADS)
-#ifndef CHAIN_HEAD
-#define CHAIN_HEAD 1024   // leading addends added one by one (<= PFXM_CHUNK)
-#endif
-__device__ __forceinline__ void chain_load(const ChainSrc& s, long long lo, int cnt, float mean, double (&xv)[CHAIN_K]) {
-  const int t0 = threadIdx.x * CHAIN_K;
-#pragma unroll
-  for (int k = 0; k < CHAIN_K; k++) xv[k] = (t0 + k < cnt) ? chain_addend(s, lo + t0 + k, mean) : 0.0;
-}
-__global__ __launch_bounds__(PFXW_THREADS) void chain_sum_kernel(ChainSrc s, int64_t n, PfxChunk* __restrict__ ch) {
-  __shared__ double shd[PFXW_THREADS / 64];
-  const long long lo = (long long)blockIdx.x * PFXM_CHUNK;
-  const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
-  const float mean = s.kind ? *s.mean : 0.f;
-  double xv[CHAIN_K];
-  chain_load(s, lo, cnt, mean, xv);
-  double acc = 0.0;
-#pragma unroll
-  for (int k = 0; k < CHAIN_K; k++) acc += xv[k];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) shd[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int k = 0; k < PFXW_THREADS / 64; k++) t += shd[k];
-    ch[blockIdx.x].sum = t;
-  }
-}
-__global__ __launch_bounds__(PFXW_THREADS) void chain_summary_kernel(ChainSrc s, int64_t n, PfxChunk* __restrict__ ch,
-                                                                    int c_first) {
-  __shared__ double shd[PFXW_THREADS / 64];
-  __shared__ PfxPair shp[PFXW_THREADS / 64];
-  __shared__ int s_bad;
-  const int c = blockIdx.x + c_first;   // (the chunks before c_first are not walked, see tdr_chain_total)
-  const long long lo = (long long)c * PFXM_CHUNK;
-  const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
-  double acc = 0.0;
-  for (int j = threadIdx.x; j < c; j += PFXW_THREADS) acc += ch[j].sum;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) shd[threadIdx.x >> 6] = acc;
-  if (threadIdx.x == 0) s_bad = 0;
-  __syncthreads();
-  double before = 0.0;
-  for (int k = 0; k < PFXW_THREADS / 64; k++) before += shd[k];
-  const float r_pred = (float)before, r_end = (float)(before + ch[c].sum);
-  const unsigned pb = __float_as_uint(r_pred), eb = __float_as_uint(r_end);
-  const int re = (pb >> 23) & 0xFF;
-  const bool plausible = (pb >> 31) == 0 && re >= PFXM_RE_MIN && re <= PFXM_RE_MAX && (int)((eb >> 23) & 0xFF) == re && (eb >> 31) == 0;
-  if (!plausible) {
-    if (threadIdx.x == 0) { ch[c].re = -1; ch[c].d0 = 0u; ch[c].d1 = 0u; }
-    return;
-  }
-  const float mean = s.kind ? *s.mean : 0.f;
-  double xv[CHAIN_K];
-  chain_load(s, lo, cnt, mean, xv);
-  PfxPair mine = {0u, 0u};
-  bool anybad = false;
-#pragma unroll
-  for (int k = 0; k < CHAIN_K; k++) {
-    unsigned f; bool tie, bad;
-    chain_classify(xv[k], (unsigned)re, f, tie, bad);
-    anybad |= bad;
-    mine = pfx_compose(mine, pfx_element_pair(f, tie));
-  }
-  if (anybad) s_bad = 1;
-  PfxPair total;
-  (void)pfx_pair_scan<PFXW_THREADS>(mine, shp, total);
-  if (threadIdx.x == 0) {
-    const bool ok = s_bad == 0 && total.a0 < (1u << 24) && total.a1 < (1u << 24);
-    ch[c].re = ok ? re : -1;
-    ch[c].d0 = total.a0;
-    ch[c].d1 = total.a1;
-  }
-}
-// one chunk on the spot: like pfx_walk_chunk, without outputs and with the real additions done in double
-#ifdef TDR_UW_TIMELINE   // diagnostic build: 100 MHz time stamps at the phase boundaries of uw_small_kernel
-__device__ unsigned long long g_uw_tl[16];
-extern "C" int tdr_debug_read_uw_timeline(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_uw_tl), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : -1;
-}
-#define UW_STAMP(k) do { __syncthreads(); if (threadIdx.x == 0) g_uw_tl[k] = wall_clock64(); } while (0)
-#define UW_COUNT(k) do { if (threadIdx.x == 0) g_uw_tl[k]++; } while (0)
-#else
-#define UW_STAMP(k) do { } while (0)
-#define UW_COUNT(k) do { } while (0)
-#endif
-// FROM_LDS: the raw weights sit in the kernel's dynamic LDS array (uw_small_kernel) instead of global memory
-__device__ __forceinline__ int uws_idx(int e) { return e + (e >> 5); }   // one pad word per 32: bank spread for strided runs
-__device__ __forceinline__ double uws_addend(int kind, int e, float mean) {
-  extern __shared__ float uws_lraw[];
-  const float v = uws_lraw[uws_idx(e)];
-  if (kind == 2) return (double)v;                                          // :179 (the running sum of the resample)
-  if (kind == 0) return (v != v) ? 0.0 : (double)v;                         // :111-115
-  if (v != v || !(v < mean)) return 0.0;                                    // :120
-  const double d = (double)(v - mean);                                      // float subtraction, then pow(double, 2)
-  return d * d;
-}
-template <bool FROM_LDS = false>
-__device__ __forceinline__ void chain_walk_chunk(const ChainSrc& s, long long lo, int cnt, float mean, float& r,
-                                                 int pos_start) {
-  __shared__ PfxPair shp[PFXW_THREADS / 64];
-  __shared__ int s_bad, s_cross, s_nz;
-  __shared__ unsigned s_state;
-  __shared__ double s_xstop;
-  const int tid = threadIdx.x, t0 = tid * CHAIN_K;
-  double xv[CHAIN_K];
-  if constexpr (FROM_LDS) {
-#pragma unroll
-    for (int k = 0; k < CHAIN_K; k++) xv[k] = (t0 + k < cnt) ? uws_addend(s.kind, (int)lo + t0 + k, mean) : 0.0;
-  } else {
-    chain_load(s, lo, cnt, mean, xv);
-  }
-  int pos = pos_start;
-  while (pos < cnt) {
-#ifdef TDR_UW_TIMELINE
-    if (FROM_LDS && tid == 0) g_uw_tl[10 + s.kind]++;
-#endif
-    const unsigned rb = __float_as_uint(r);
-    const unsigned re = rb >> 23;   // sign included
-    pfx_sync();
-    if (tid == 0) { s_bad = cnt; s_cross = cnt; s_nz = cnt; s_xstop = 0.0; s_state = 0u; }
-    pfx_sync();
-
-    if (!(re >= PFXM_RE_MIN && re <= PFXM_RE_MAX)) {
-      // zero / tiny / huge / inf / NaN running sum: zero addends change nothing, the next other one is really added
-      int first = cnt;
-#pragma unroll
-      for (int k = 0; k < CHAIN_K; k++) {
-        const int li = t0 + k;
-        if (li >= pos && li < cnt && xv[k] != 0.0) first = min(first, li);
-      }
-      if (first < cnt) atomicMin(&s_nz, first);
-      pfx_sync();
-      const int stop = s_nz;
-#pragma unroll
-      for (int k = 0; k < CHAIN_K; k++)
-        if (t0 + k == stop) s_xstop = xv[k];
-      pfx_sync();
-      if (stop < cnt) r = (float)((double)r + s_xstop);
-      pos = stop < cnt ? stop + 1 : cnt;
-      continue;
-    }
-    const unsigned R = (rb & 0x7FFFFFu) | 0x800000u;
-    unsigned f[CHAIN_K];
-    unsigned tiebits = 0u;
-    PfxPair mine = {0u, 0u};
-#pragma unroll
-    for (int k = 0; k < CHAIN_K; k++) {
-      const int li = t0 + k;
-      bool bad, tie;
-      chain_classify(xv[k], re, f[k], tie, bad);
-      if (li < pos || li >= cnt) { f[k] = 0u; tie = false; bad = false; }
-      if (bad) atomicMin(&s_bad, li);
-      tiebits |= tie ? (1u << k) : 0u;
-      mine = pfx_compose(mine, pfx_element_pair(f[k], tie));
-    }
-
-    PfxPair total;
-    const PfxPair ex = pfx_pair_scan<PFXW_THREADS>(mine, shp, total);
-    unsigned st[CHAIN_K];
-    {
-      unsigned state = R + ((R & 1u) ? ex.a1 : ex.a0);
-      int first = cnt;
-#pragma unroll
-      for (int k = 0; k < CHAIN_K; k++) {
-        state += f[k] + (((tiebits >> k) & 1u) ? ((state + f[k]) & 1u) : 0u);
-        st[k] = state;
-        const int li = t0 + k;
-        if (li >= pos && li < cnt && state >= (1u << 24)) first = min(first, li);
-      }
-      if (first < cnt) atomicMin(&s_cross, first);
-    }
-    pfx_sync();
-    const int stop = min(s_bad, s_cross);
-#pragma unroll
-    for (int k = 0; k < CHAIN_K; k++) {
-      const int li = t0 + k;
-      if (li >= pos && li == stop - 1) s_state = st[k];
-      if (li == stop) s_xstop = xv[k];
-    }
-    pfx_sync();
-
-    if (stop > pos) r = __uint_as_float((re << 23) | (s_state & 0x7FFFFFu));
-    if (stop < cnt) {
-      r = (float)((double)r + s_xstop);   // one real addition, in the reference's types
-      pos = stop + 1;
-    } else {
-      pos = cnt;
-    }
-  }
-}
-__global__ __launch_bounds__(PFXW_THREADS) void chain_walk_kernel(ChainSrc s, int64_t n, const PfxChunk* __restrict__ ch,
-                                                                 int nch, float* __restrict__ total_out, int c_first,
-                                                                 const float* __restrict__ r_first) {
-  __shared__ int sm_re[PFXW_BLOCK];
-  __shared__ unsigned sm_d0[PFXW_BLOCK], sm_d1[PFXW_BLOCK];
-  const float mean = s.kind ? *s.mean : 0.f;
-  // head: the sum of unnormalised weights crosses a binade every time it doubles — about ten times within the first
-  // thousand addends — so those are added one by one by a single thread out of LDS
-  __shared__ double head[CHAIN_HEAD];
-  __shared__ float s_head_r;
-  // (c_first > 0: chunks [0, c_first) were summed by chain_head_kernel, which left the sum behind them in *r_first)
-  const int hn = c_first > 0 ? 0 : (int)min((long long)CHAIN_HEAD, (long long)n);
-  for (int t = threadIdx.x; t < hn; t += PFXW_THREADS) head[t] = chain_addend(s, t, mean);
-  pfx_sync();
-  if (threadIdx.x == 0) {
-    float run = c_first > 0 ? *r_first : 0.f;
-    for (int t = 0; t < hn; t++) run = (float)((double)run + head[t]);
-    s_head_r = run;
-  }
-  pfx_sync();
-  float r = s_head_r;   // workgroup-uniform
-  for (int cb = (c_first / PFXW_BLOCK) * PFXW_BLOCK; cb < nch; cb += PFXW_BLOCK) {
-    pfx_sync();
-    for (int t = threadIdx.x; t < PFXW_BLOCK && cb + t < nch; t += PFXW_THREADS) {
-      const PfxChunk x = ch[cb + t];
-      sm_re[t] = x.re; sm_d0[t] = x.d0; sm_d1[t] = x.d1;
-    }
-    pfx_sync();
-    const int ce = min(nch, cb + PFXW_BLOCK);
-    for (int c = max(cb, c_first); c < ce; c++) {
-      const unsigned rb = __float_as_uint(r);
-      const int re = (int)(rb >> 23);
-      const unsigned R = (rb & 0x7FFFFFu) | 0x800000u;
-      const unsigned D = (R & 1u) ? sm_d1[c - cb] : sm_d0[c - cb];
-      if (c > 0 && sm_re[c - cb] == re && R + D < (1u << 24)) {
-        r = __uint_as_float(((unsigned)re << 23) | ((R + D) & 0x7FFFFFu));
-      } else {
-        const long long lo = (long long)c * PFXM_CHUNK;
-        chain_walk_chunk(s, lo, (int)min((long long)PFXM_CHUNK, (long long)n - lo), mean, r, c == 0 ? hn : 0);
-      }
-    }
-  }
-  if (threadIdx.x == 0) *total_out = r;
-}
-static int g_pfx_small = 1;   // 0 = without the one-launch kernel (A/B and debugging)
-extern "C" int tdr_config_prefix_small(int on) {   // < 0: query only
-  if (on >= 0) g_pfx_small = on ? 1 : 0;
-  return g_pfx_small;
-}
-#define CHAIN_HEAD_N 32768
-// whole chunks at the start that the one-workgroup machinery takes (0: none; tdr_config_prefix_small(0) switches it off
-// for the running sum AND the statistics chains: the chunk walk from the first addend on, for A/B and debugging)
-static int chain_head_chunks(int64_t n) { return (g_pfx_small && n >= CHAIN_HEAD_N) ? CHAIN_HEAD_N / PFXM_CHUNK : 0; }
-static int chain_head_launch(const float* raw, const float* mean_dev, int kind, int n_head, float* r_out, hipStream_t st);
-// raw: [n] raw weights; kind 0: total = serial float sum of the non-NaN weights; kind 1: total = serial
-// float-accumulated sum of pow(w - *mean_dev, 2) over the non-NaN weights below *mean_dev.  workspace: chunk headers,
-// tdr_prefix_workspace_bytes(n).  total_out: one device float.
-int tdr_chain_total(const float* raw, const float* mean_dev, int kind, int64_t n, float* total_out, void* workspace,
-                    hipStream_t st) {
-  const int64_t nch64 = cdiv(n, (int64_t)PFXM_CHUNK);
-  if (nch64 > (1 << 24)) return fail(TDR_ERR_ARG, "chain_total: n too large");
-  const int nch = (int)nch64;
-  PfxChunk* ch = reinterpret_cast<PfxChunk*>(workspace);
-  ChainSrc s{raw, mean_dev, kind};
-  // The first 32 768 addends — where the sum crosses most of its binades — go through the one-workgroup machinery of
-  // uw_small_kernel (chain_head_kernel, below); the chunk walk starts behind them.
-  const int c_first = chain_head_chunks(n);
-  hipLaunchKernelGGL(chain_sum_kernel, dim3(nch), dim3(PFXW_THREADS), 0, st, s, n, ch);
-  if (nch > c_first)
-    hipLaunchKernelGGL(chain_summary_kernel, dim3(nch - c_first), dim3(PFXW_THREADS), 0, st, s, n, ch, c_first);
-  float* r_first = reinterpret_cast<float*>(&ch[0].r0);   // (a header slot the chains do not use)
-  if (c_first > 0) {
-    const int rc = chain_head_launch(raw, mean_dev, kind, c_first * PFXM_CHUNK, r_first, st);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(chain_walk_kernel, dim3(1), dim3(PFXW_THREADS), 0, st, s, n, (const PfxChunk*)ch, nch, total_out,
-                     c_first, (const float*)r_first);
-  return TDR_OK;
-}
-
-// ---- ParticleFilter::update's statistics for small particle sets, in ONE launch ------------------------------------
-// src/particle_filter.cpp:107-147 for n <= TDR_UW_SMALL_MAX_N — the reference's own operating point (20 000 particles,
-// src/top_down_render.cpp:53).  One workgroup; the raw weights are staged into LDS once (n floats, at most 128 KB) and
-// every pass — the two exact serial chains, the counts, fill / normalise / argmax — runs out of LDS; the weights are
-// written to memory once, at the end.  Same results as the multi-workgroup path of tdr_filter.hip, bit for bit in
-// `sum`, `mean`, `bottom_stddev` (tests/test_gpu_parity.py::test_update_weights_serial_chains_bit_exact).
-//
-// The chains: head one by one, then chunk by chunk with chain_walk_chunk (no prediction pass: at most 8 chunks).  (One
-// stretch over the whole array instead of chunks re-classifies every remaining addend at each binade crossing: 80 us
-// against 48 at 20 000 weights.)
-__device__ __forceinline__ float uws_chain_total(int kind, int n, float mean) {
-  __shared__ double head[CHAIN_HEAD];
-  __shared__ float s_head_r;
-  const int hn = min(CHAIN_HEAD, n);
-  pfx_sync();
-  for (int t = threadIdx.x; t < hn; t += PFXW_THREADS) head[t] = uws_addend(kind, t, mean);
-  pfx_sync();
-  if (threadIdx.x == 0) {
-    float run = 0.f;
-    if (kind == 0) {
-      // float + float: (float)((double)a + (double)b) == a + b for every pair of floats (53 >= 2 * 24 + 2 bits: the
-      // double sum rounds to the same float), and a float add is a third of the dependent latency
-      for (int t = 0; t < hn; t++) run += (float)head[t];
-    } else {
-      for (int t = 0; t < hn; t++) run = (float)((double)run + head[t]);
-    }
-    s_head_r = run;
-  }
-  pfx_sync();
-  UW_STAMP(kind ? 5 : 2);
-  float r = s_head_r;   // workgroup-uniform
-  const ChainSrc s{nullptr, nullptr, kind};
-  const int nch = (n + PFXM_CHUNK - 1) / PFXM_CHUNK;
-  for (int c = 0; c < nch; c++) {
-    const int lo = c * PFXM_CHUNK;
-    const int cnt = min((int)PFXM_CHUNK, n - lo);
-    if (c == 0 && hn >= cnt) continue;
-    chain_walk_chunk<true>(s, lo, cnt, mean, r, c == 0 ? hn : 0);
-  }
-  return r;
-}
-// ---- the same chains, wave by wave (default) --------------------------------------------------------------------------
-// The weights are cut into wave-chunks of 512 (one wave, 8 consecutive addends a lane).  The pass before the chain (the
-// count of valid weights / of weights below the mean) leaves the double sum of every wave-chunk's addends behind; from the
-// sums before a chunk every wave predicts the binade the chain is in when it enters and leaves it.  Then, side by side:
-//   * wave 0 adds the first wave-chunk one by one (the sum starts at zero and doubles every few addends);
-//   * the other waves summarise their chunks: a chunk predicted to stay in one binade as its parity pair (D0, D1) there;
-//     a chunk predicted to cross into the next binade as the parity pairs of every LANE (8 addends) in both binades.
-// One barrier later wave 0 walks the chunk list with the exact running sum, with register-level moves only — no workgroup
-// barrier inside the serial part: a one-binade chunk whose prediction holds is one integer add; in a crossing chunk a
-// scan of the lane pairs of the first binade finds the lane the sum crosses in, that lane's 8 addends are really added,
-// and a scan of the lane pairs of the second binade carries the sum to the chunk's end.  Whatever fits neither (a wrong
-// prediction, irregular addends, two crossings in one chunk) is carried through element by element by uws_wave_walk.
-// The bits are the serial chain's whatever was predicted, as in the multi-workgroup path.
-#define UWS_WC (64 * CHAIN_K)   // addends per wave-chunk
-#define UWS_THREADS 1024
-#define UWS_DUAL_SLOTS 8        // crossing chunks summarised lane by lane (the sum doubles log2(n / 512) times behind the head)
-#define UWS_DUAL_FLAG 0x100
-struct UwsShared {
-  double csum[64];                       // double sum of every wave-chunk's addends
-  int code[64];                          // -1: carried through; binade; binade | UWS_DUAL_FLAG | slot << 16
-  unsigned d0[64], d1[64];               // parity pair of a one-binade chunk
-  uint4 dual[UWS_DUAL_SLOTS][64];        // crossing chunks: scans of the lane pairs in the binade entered (x, y) / the next (z, w)
-  double shd[UWS_THREADS / 64];
-  float total;
-};
+// the same six moves for a minimum, a double sum, an unsigned sum and a float maximum
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ int uws_min_dpp(int v) {
   return min(v, __builtin_amdgcn_update_dpp(0x7FFFFFFF, v, CTRL, ROW_MASK, 0xF, false));
@@ -1229,108 +589,392 @@ __device__ __forceinline__ unsigned uws_wave_scan_u(unsigned v) {
   v = uws_addu_dpp<0x143, 0xC>(v);
   return v;
 }
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float pfs_max_dpp(float v) {
+  return fmaxf(v, __uint_as_float((unsigned)__builtin_amdgcn_update_dpp((int)0xFF800000u, (int)__float_as_uint(v), CTRL,
+                                                                        ROW_MASK, 0xF, false)));
+}
+__device__ __forceinline__ float pfs_wave_scan_max(float v) {   // inclusive maximum over the lanes before and this one
+  v = pfs_max_dpp<0x111, 0xF>(v);
+  v = pfs_max_dpp<0x112, 0xF>(v);
+  v = pfs_max_dpp<0x114, 0xF>(v);
+  v = pfs_max_dpp<0x118, 0xF>(v);
+  v = pfs_max_dpp<0x142, 0xA>(v);
+  v = pfs_max_dpp<0x143, 0xC>(v);
+  return v;
+}
 __device__ __forceinline__ double uws_readlane_d(double v, int lane) {   // lane: wave-uniform
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane),
                           __builtin_amdgcn_readlane(__double2loint(v), lane));
 }
-// addend e of the chain if `take`, else 0.0 — the LDS read is unconditional (n: number of weights staged)
-// (the staged array ends in UWS_PAD unused words, so a read up to that far behind the last weight stays inside it)
+__device__ __forceinline__ double chain_readlane(double v, int lane) { return uws_readlane_d(v, lane); }
+__device__ __forceinline__ float chain_readlane(float v, int lane) {
+  return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(v), lane));
+}
+// Workgroup sum of one double per thread: a __shfl_xor tree inside every wave, then the waves in order.  The order of
+// the additions is fixed — these sums feed the binade predictions, and a launch stays a pure function of its inputs.
+// (uws_sum_d below adds in another order, a DPP scan inside the wave, and is therefore a function of its own: a
+// different double sum can flip a prediction — harmless for the bits, but it moves chunks between the fast and the
+// slow path.)  Values written to LDS before the call are visible to every thread behind it.
+template <int NT>
+__device__ __forceinline__ double chain_wg_sum(double acc, double* shd) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) shd[threadIdx.x >> 6] = acc;
+  pfx_sync();
+  double t = 0.0;
+  for (int k = 0; k < NT / 64; k++) t += shd[k];
+  return t;
+}
+
+// ---- what a chain adds ---------------------------------------------------------------------------------------------------
+// The three chains (src/particle_filter.cpp):
+//   CHAIN_SUM     :108-116  sum += w             float addends, NaN weights skipped
+//   CHAIN_BOTTOM  :118-126  acc += pow(w - mean, 2) over the weights below the mean: (float)((double)acc + x), x a double
+//   CHAIN_RUNSUM  :179      running_sum += w     float addends, NaN weights added like any other
+enum { CHAIN_SUM = 0, CHAIN_BOTTOM = 1, CHAIN_RUNSUM = 2 };
+// where element i comes from: an array in memory (nothing is read where `take` is false) ...
+struct ChainGlobal {
+  const float* p;
+  static constexpr bool lds = false;
+  __device__ __forceinline__ float read(long long i, bool take) const { return take ? p[i] : 0.f; }
+};
+// ... or the image of the weights the one-workgroup kernels keep in their dynamic LDS array.  GUARD = false reads
+// unconditionally, ahead of the test (the image ends in UWS_PAD unused words behind the last weight).
+__device__ __forceinline__ int uws_idx(int e) { return e + (e >> 5); }   // one pad word per 32: bank spread for strided runs
 #define UWS_PAD 16
-__device__ __forceinline__ double uws_addend_if(int kind, int e, bool take, float mean) {
-  const double x = uws_addend(kind, e, mean);
-  return take ? x : 0.0;
-}
-// the `sum` chain's addends are floats: pfx_classify's float arithmetic (exact, see there) with chain_classify's bound
-__device__ __forceinline__ float uws_addend_f(int kind, int e, bool take) {
-  extern __shared__ float uws_lraw[];
-  const float v = uws_lraw[uws_idx(e)];
-  return (take && (kind == 2 || v == v)) ? v : 0.f;   // :111-115 (`sum` skips NaN weights; the running sum, kind 2, does not)
-}
-__device__ __forceinline__ void uws_classify_f(float wv, unsigned re, unsigned& f, bool& tie, bool& bad) {
-  const float t = wv * __uint_as_float((277u - re) << 23);   // w / u, u = 2^(re - 150)
-  bad = !(wv >= 0.f) || !(t < 4194304.f);
+template <bool GUARD>
+struct ChainLds {
+  static constexpr bool lds = true;
+  __device__ __forceinline__ float read(long long i, bool take) const {
+    extern __shared__ float uws_lraw[];
+    if (GUARD) return take ? uws_lraw[uws_idx((int)i)] : 0.f;
+    return uws_lraw[uws_idx((int)i)];
+  }
+};
+// The real addition, in the reference's types.  float + float equals the double form for every pair of floats —
+// (float)((double)a + (double)b) == a + b: 53 >= 2 * 24 + 2 bits, the double sum rounds to the same float — and is a
+// third of the dependent latency; so the float chains may be carried in either type, and each use keeps the one its
+// timing was measured with.
+__device__ __forceinline__ float chain_add(float r, float x) { return r + x; }
+__device__ __forceinline__ float chain_add(float r, double x) { return (float)((double)r + x); }
+__device__ __forceinline__ bool chain_finite(float x) { return fabsf(x) < INFINITY; }
+__device__ __forceinline__ bool chain_finite(double x) { return fabs(x) < INFINITY; }
+// One addend x against the binade of a running sum with biased exponent `re` (PFXM_RE_MIN <= re <= PFXM_RE_MAX), ulp
+// u = 2^(re-150): f = round-half-down(x/u), tie = the remainder is exactly one half, bad = cannot be an integer
+// increment (NaN, inf, negative, or x/u >= bound).  x * 2^(150-re) is exact (a power-of-two scaling inside the normal
+// range; a product that underflows is far below one half anyway), and so are floor and the remainder.
+//
+// The bound.  Anything up to 2^24 keeps the arithmetic right: f < 2^24 and R < 2^24 stay far from the pairs' saturation
+// (PFXM_SAT) and a mantissa that reaches 2^24 stops the step, so a large addend only ends a stretch where a smaller bound
+// would have ended it one element earlier with the same real addition.  CHAIN_BOUND_24 is what the multi-workgroup running
+// sum takes (summary, walk and fill must agree with each other: a chunk accepted by the summary is refilled without a
+// stop search).  CHAIN_BOUND_22 serves two needs: the double classifier rounds x/u to the double grid of [2^23, 2^24)
+// by adding 2^23, which needs x/u < 2^23; and the wave-level summaries add the f of a whole wave-chunk as plain unsigned
+// numbers when no tie occurs (8 per lane < 2^25, 64 lanes < 2^31).  Reading the code, 2^22 would serve every caller with
+// the same bits (the bound only moves an element between "scan" and "real addition", which give the same float); the
+// bounds are nevertheless kept per use as they were measured.
+#define CHAIN_BOUND_24 24
+#define CHAIN_BOUND_22 22
+template <int LOG2_BOUND>
+__device__ __forceinline__ void chain_classify(float x, unsigned re, unsigned& f, bool& tie, bool& bad) {
+  const float t = x * __uint_as_float((277u - re) << 23);   // x / u: 2^(150 - re) = 1/u
+  bad = !(x >= 0.f) || !(t < (float)(1 << LOG2_BOUND));
   const float fl = floorf(t);
   const float fr = t - fl;
   tie = fr == 0.5f;
   f = (unsigned)fl + (fr > 0.5f ? 1u : 0u);
   if (bad) { f = 0; tie = false; }
 }
-// an addend of chain `kind` (a compile-time constant where it matters): a float in the `sum` chain, else a double
-struct UwsX { float f; double d; };
-__device__ __forceinline__ UwsX uws_load_x(int kind, int e, bool take, float mean) {
-  UwsX x;
-  x.f = 0.f; x.d = 0.0;
-  if (kind != 1) x.f = uws_addend_f(kind, e, take); else x.d = uws_addend_if(kind, e, take, mean);
-  return x;
+// A double addend: for a float chain r <- (float)((double)r + x) the step is x first rounded to the double grid of the
+// sum's binade — 2^-29 ulp(r), and because R is an integer that rounding does not depend on R — and then to the float
+// grid with the parity rule.  (A float addend lies on the double grid or is far below half an ulp, so a float chain
+// classified here gives what the float classifier gives.)
+template <int LOG2_BOUND>
+__device__ __forceinline__ void chain_classify(double x, unsigned re, unsigned& f, bool& tie, bool& bad) {
+  const double scale = __longlong_as_double((long long)(1023 + 150 - (int)re) << 52);   // 2^(150 - re) = 1/u
+  const double t = x * scale;
+  bad = !(x >= 0.0) || !(t < (double)(1 << LOG2_BOUND));   // negative / NaN / inf, or not small against the sum: real add
+  const double tg = (t + 8388608.0) - 8388608.0;           // t on the double grid of [2^23, 2^24): multiples of 2^-29
+  const double fl = floor(tg);
+  const double fr = tg - fl;
+  tie = fr == 0.5;
+  f = (unsigned)fl + (fr > 0.5 ? 1u : 0u);
+  if (bad) { f = 0; tie = false; }
 }
-__device__ __forceinline__ void uws_classify_x(int kind, const UwsX& x, unsigned re, unsigned& f, bool& tie, bool& bad) {
-  if (kind != 1) uws_classify_f(x.f, re, f, tie, bad); else chain_classify(x.d, re, f, tie, bad);
-}
-__device__ __forceinline__ float uws_mant(unsigned re, unsigned state) { return __uint_as_float((re << 23) | (state & 0x7FFFFFu)); }
-// wave-chunk [lo, lo + cnt) carried through by the calling wave from its element `pos` on, entered with the running sum r
-// (wave-uniform): chain_walk_chunk on one wave
-__device__ __forceinline__ float uws_wave_walk(int kind, int lo, int cnt, float mean, float r, int pos) {
-  const int t0 = (threadIdx.x & 63) * CHAIN_K;
-  double xv[CHAIN_K];
+// X: the type the addends are carried in (double for CHAIN_BOTTOM; float or double for the two float chains, see
+// chain_add); SRC: ChainGlobal / ChainLds; LOG2B: the classifier's bound.  `kind` is a compile-time constant wherever
+// it matters (everything here is inlined); the kernels that serve both statistics chains pass it at run time.
+template <class X, class SRC, int LOG2B>
+struct ChainAddend {
+  using value_t = X;
+  using src_t = SRC;
+  SRC src;
+  int kind;     // CHAIN_*
+  float mean;   // CHAIN_BOTTOM
+  __device__ __forceinline__ X value(float v) const {
+    if (kind == CHAIN_RUNSUM) return (X)v;
+    if (kind == CHAIN_SUM) return (v != v) ? X(0) : (X)v;       // :111-115
+    if (v != v || !(v < mean)) return X(0);                     // :120
+    const double d = (double)(v - mean);                        // float subtraction, then pow(double, 2)
+    return (X)(d * d);
+  }
+  __device__ __forceinline__ X load(long long i, bool take) const {   // addend i if `take`, else zero (x + 0 == x)
+    const X x = value(src.read(i, take));
+    return take ? x : X(0);
+  }
+  // the K consecutive addends of the calling lane, from its element t0 of the chunk [lo, lo + cnt)
+  template <int K>
+  __device__ __forceinline__ void load_items(long long lo, int cnt, int t0, X (&xv)[K]) const {
+    if constexpr (!SRC::lds && sizeof(X) == sizeof(float)) {
+      if (t0 + K <= cnt && ((lo & 3) == 0)) {
+        const float4* p = reinterpret_cast<const float4*>(src.p + lo + t0);
 #pragma unroll
-  for (int k = 0; k < CHAIN_K; k++) xv[k] = uws_addend_if(kind, lo + t0 + k, t0 + k < cnt, mean);
+        for (int k = 0; k < K / 4; k++) {
+          const float4 v = p[k];
+          xv[4 * k] = value(v.x); xv[4 * k + 1] = value(v.y); xv[4 * k + 2] = value(v.z); xv[4 * k + 3] = value(v.w);
+        }
+        return;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K; k++) xv[k] = load(lo + t0 + k, t0 + k < cnt);
+  }
+  static __device__ __forceinline__ void classify(X x, unsigned re, unsigned& f, bool& tie, bool& bad) {
+    chain_classify<LOG2B>(x, re, f, tie, bad);
+  }
+  __device__ __forceinline__ ChainAddend<double, SRC, CHAIN_BOUND_22> as_double() const { return {src, kind, mean}; }
+};
+using PfxRunSum = ChainAddend<float, ChainGlobal, CHAIN_BOUND_24>;     // the multi-workgroup running sum (kind CHAIN_RUNSUM)
+using ChainStat = ChainAddend<double, ChainGlobal, CHAIN_BOUND_22>;    // the multi-workgroup statistics chains
+using UwsAddF = ChainAddend<float, ChainLds<false>, CHAIN_BOUND_22>;   // wave level, out of LDS: the float chains ...
+using UwsAddD = ChainAddend<double, ChainLds<false>, CHAIN_BOUND_22>;  // ... and CHAIN_BOTTOM / the element-by-element walker
+using UwsWgAdd = ChainAddend<double, ChainLds<true>, CHAIN_BOUND_22>;  // workgroup level, out of LDS (tdr_config_uw_waves(0))
+__device__ __forceinline__ float chain_mant(unsigned re, unsigned state) { return __uint_as_float((re << 23) | (state & 0x7FFFFFu)); }
+
+// ---- scope: who carries a stretch ------------------------------------------------------------------------------------------
+// a workgroup of NT threads (LDS pair scan, atomicMin in LDS for the stop, LDS broadcast) ...
+template <class X> struct ChainWgStop { int stop; unsigned state; X xstop; };
+template <int NT, class X>
+struct ChainWg {
+  static constexpr bool nan_inf_apart = false;
+  PfxPair* shp;           // one slot per wave
+  ChainWgStop<X>* s;      // (not used without a stop search)
+  __device__ __forceinline__ bool leader() const { return threadIdx.x == 0; }
+  __device__ __forceinline__ void reset(int cnt) const {
+    pfx_sync();
+    if (threadIdx.x == 0) s->stop = cnt;
+    pfx_sync();
+  }
+  template <int K>
+  __device__ __forceinline__ unsigned enter(unsigned R, const unsigned (&f)[K], unsigned tiebits) const {
+    PfxPair total;
+    const PfxPair ex = pfx_pair_scan<NT>(chain_lane_pair(f, tiebits), shp, total);
+    return R + ((R & 1u) ? ex.a1 : ex.a0);
+  }
+  __device__ __forceinline__ int first_of(int first, int cnt) const {
+    if (first < cnt) atomicMin(&s->stop, first);
+    pfx_sync();
+    return s->stop;
+  }
+  // the mantissa behind element stop - 1 (when stop > pos) and the addend at `stop` (when stop < cnt), in every thread
+  template <int K>
+  __device__ __forceinline__ void pick(const unsigned (&st)[K], const X (&xv)[K], int t0, int pos, int stop, int cnt,
+                                       unsigned& sv, X& xstop) const {
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      const int li = t0 + k;
+      if (li >= pos && li == stop - 1) s->state = st[k];
+      if (li == stop) s->xstop = xv[k];
+    }
+    pfx_sync();
+    sv = s->state;
+    xstop = s->xstop;
+  }
+};
+// ... or one wave (DPP scans, readlane broadcasts, no barrier).  NOTIE: when no lane holds a rounding tie a pair is
+// (s, s) and the scan is a plain integer prefix sum (needs CHAIN_BOUND_22).
+template <bool NOTIE>
+struct ChainWave {
+  static constexpr bool nan_inf_apart = true;
+  __device__ __forceinline__ bool leader() const { return (threadIdx.x & 63) == 0; }
+  __device__ __forceinline__ void reset(int) const {}
+  template <int K>
+  __device__ __forceinline__ unsigned enter(unsigned R, const unsigned (&f)[K], unsigned tiebits) const {
+    if (NOTIE && __ballot(tiebits != 0u) == 0ull) {
+      unsigned lane_sum = 0u;
+#pragma unroll
+      for (int k = 0; k < K; k++) lane_sum += f[k];
+      return R + (uws_wave_scan_u(lane_sum) - lane_sum);
+    }
+    const PfxPair ex = pfx_pair_dpp<0x138, 0xF>(pfx_pair_wave_scan(chain_lane_pair(f, tiebits)));   // exclusive: wave_shr:1
+    return R + ((R & 1u) ? ex.a1 : ex.a0);
+  }
+  __device__ __forceinline__ int first_of(int first, int) const { return uws_wave_min(first); }
+  template <int K, class X>
+  __device__ __forceinline__ void pick(const unsigned (&st)[K], const X (&xv)[K], int t0, int pos, int stop, int cnt,
+                                       unsigned& sv, X& xstop) const {
+    unsigned v = 0u;   // in the lane that holds it: the mantissa before the stop, the addend at the stop
+    X xs = X(0);
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      if (t0 + k == stop - 1) v = st[k];
+      if (t0 + k == stop) xs = xv[k];
+    }
+    if (stop > pos) sv = (unsigned)__builtin_amdgcn_readlane((int)v, (stop - 1) / K);
+    if (stop < cnt) xstop = chain_readlane(xs, stop / K);
+  }
+};
+
+// ---- sink: what is written -------------------------------------------------------------------------------------------------
+// put(k, li, v): the running sum behind the lane's k-th addend, element li of the chunk, inside a stretch;
+// committed(r): a stretch is done, r the sum behind it; put_stop(t0, li, r): element li was really added.
+struct ChainNoSink {   // only the total is wanted
+  static constexpr bool own_irregular = false;
+  __device__ __forceinline__ void put(int, int, float) {}
+  __device__ __forceinline__ void committed(float) {}
+  __device__ __forceinline__ void put_stop(int, int, float) {}
+};
+template <int K>
+struct ChainRegSink {   // into registers: the caller stores them (pfs_wave_fill: back into the LDS image)
+  static constexpr bool own_irregular = false;
+  float pv[K];
+  __device__ __forceinline__ void put(int k, int, float v) { pv[k] = v; }
+  __device__ __forceinline__ void committed(float) {}
+  __device__ __forceinline__ void put_stop(int t0, int li, float r) {
+#pragma unroll
+    for (int k = 0; k < K; k++)
+      if (t0 + k == li) pv[k] = r;
+  }
+};
+// the running sum and the running maximum of chunk [lo, ..) to memory; a sum outside the binades a step works in goes
+// to the general path, pfx_exact_range (with its serial head at the very start)
+struct PfxGlobalSink {
+  static constexpr bool own_irregular = true;
+  const float* __restrict__ w;
+  long long lo;
+  float* __restrict__ runmax;
+  float* __restrict__ prefix_opt;
+  float& carry;
+  int head_len;
+  __device__ __forceinline__ void put(int, int li, float v) {
+    runmax[lo + li] = fmaxf(carry, v);
+    if (prefix_opt) prefix_opt[lo + li] = v;
+  }
+  __device__ __forceinline__ void committed(float r) { carry = fmaxf(carry, r); }   // increments are non-negative: the last committed value is the largest
+  __device__ __forceinline__ void put_stop(int, int li, float nr) {
+    if (nr == nr) carry = fmaxf(carry, nr);
+    if (threadIdx.x == 0) {
+      runmax[lo + li] = carry;
+      if (prefix_opt) prefix_opt[lo + li] = nr;
+    }
+  }
+  __device__ __forceinline__ void irregular(float& r, int& pos, int cnt) {
+    const long long a = lo + pos;
+    const long long b = a == 0 ? min((long long)head_len, (long long)cnt) : lo + cnt;
+    pfx_exact_range<PFXW_THREADS>(w, a, b, runmax, prefix_opt, r, carry, head_len);
+    pos = (int)(b - lo);
+  }
+};
+
+// ---- the step ----------------------------------------------------------------------------------------------------------------
+// One stretch of chunk elements [pos, cnt) inside the binade of r (a positive normal sum, PFXM_RE_MIN <= re <= PFXM_RE_MAX;
+// pos, cnt and r uniform over the scope).  Every lane holds K consecutive addends xv from its element t0 on.  Classifies
+// them, composes and scans the pairs, rebuilds the mantissa behind each of the lane's addends (st) and returns the
+// lane's first element that needs a real addition — an addend the classifier calls bad, or the one that takes the
+// mantissa to 2^24 — or cnt.  STOP = false: the caller knows that the whole chunk stays in the binade (an accepted
+// chunk of the fill kernel): no masking, no search.
+//
+// What differs between the uses on purpose, and where it is selected:
+//   * ChainWave<true> (pfs_wave_fill): plain integer scan when no lane holds a tie;
+//   * STOP = false (pfx_chunk_fill_kernel), which also stores its values as float4s;
+//   * a sum outside [PFXM_RE_MIN, PFXM_RE_MAX] never reaches the step; chain_walk sends it to the sink's own handler
+//     (PfxGlobalSink: pfx_exact_range), or skips the addends that leave it unchanged and really adds the next one —
+//     zero addends; under a scope with nan_inf_apart (the waves) also finite addends of an infinite sum, and a NaN sum
+//     ends the chunk at once.
+template <bool STOP, class A, int K, class SCOPE>
+__device__ __forceinline__ int chain_step(const typename A::value_t (&xv)[K], int t0, int pos, int cnt, float r,
+                                          const SCOPE& sc, unsigned (&st)[K]) {
+  const unsigned rb = __float_as_uint(r), re = rb >> 23, R = (rb & 0x7FFFFFu) | 0x800000u;
+  unsigned f[K];
+  unsigned tiebits = 0u;
+  int first = cnt;
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    const int li = t0 + k;
+    bool bad, tie;
+    A::classify(xv[k], re, f[k], tie, bad);
+    if (STOP) {
+      if (li < pos || li >= cnt) { f[k] = 0u; tie = false; bad = false; }
+      if (bad) first = min(first, li);
+    }
+    tiebits |= tie ? (1u << k) : 0u;
+  }
+  unsigned state = sc.enter(R, f, tiebits);   // the exact mantissa before this lane's first element
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    state += f[k] + (((tiebits >> k) & 1u) ? ((state + f[k]) & 1u) : 0u);   // a tie goes to the even neighbour
+    st[k] = state;
+    const int li = t0 + k;
+    if (STOP && li >= pos && li < cnt && state >= (1u << 24)) first = min(first, li);
+  }
+  return first;
+}
+// Chunk elements [pos, cnt) carried through from the running sum r: stretches and real additions in turn.  Per turn:
+// the first element that needs a real addition (`stop`), found by a step or, for a sum no step works on, by skipping
+// the addends that leave it unchanged; the elements before it committed to the sink; that one addition.  Returns the
+// sum behind the chunk.
+template <class A, int K, class SCOPE, class SINK>
+__device__ __forceinline__ float chain_walk(const A& a, const typename A::value_t (&xv)[K], int t0, int pos, int cnt,
+                                            float r, const SCOPE& sc, SINK& sink) {
+  using X = typename A::value_t;
   while (pos < cnt) {
 #ifdef TDR_UW_TIMELINE
-    if ((threadIdx.x & 63) == 0 && kind < 2) g_uw_tl[10 + kind]++;
+    if (A::src_t::lds && a.kind < 2 && sc.leader()) g_uw_tl[10 + a.kind]++;
 #endif
     const unsigned rb = __float_as_uint(r);
     const unsigned re = rb >> 23;   // sign included
-    int first = cnt;
-    unsigned st[CHAIN_K] = {};
     const bool regular = re >= PFXM_RE_MIN && re <= PFXM_RE_MAX;
-    if (r != r) return r;   // NaN stays NaN
-    if (!regular) {
-      // zero / tiny / huge / inf running sum: zero addends change nothing (an infinite sum: finite ones), the next other
-      // one is really added
-      const bool isinf = (rb & 0x7FFFFFFFu) == 0x7F800000u;
+    if (SCOPE::nan_inf_apart && r != r) {   // NaN stays NaN
 #pragma unroll
-      for (int k = 0; k < CHAIN_K; k++) {
+      for (int k = 0; k < K; k++)
+        if (t0 + k >= pos && t0 + k < cnt) sink.put(k, t0 + k, r);
+      break;
+    }
+    if constexpr (SINK::own_irregular) {
+      if (!regular) {   // zero / tiny / huge / negative / inf / NaN running sum
+        sink.irregular(r, pos, cnt);
+        continue;
+      }
+    }
+    sc.reset(cnt);
+    int first = cnt;
+    unsigned st[K] = {};
+    if (!regular) {
+      const bool isinf = SCOPE::nan_inf_apart && (rb & 0x7FFFFFFFu) == 0x7F800000u;
+#pragma unroll
+      for (int k = 0; k < K; k++) {
         const int li = t0 + k;
-        const bool acts = isinf ? !(fabs(xv[k]) < INFINITY) : (xv[k] != 0.0);
+        const bool acts = isinf ? !chain_finite(xv[k]) : (xv[k] != X(0));
         if (li >= pos && li < cnt && acts) first = min(first, li);
       }
     } else {
-      const unsigned R = (rb & 0x7FFFFFu) | 0x800000u;
-      unsigned f[CHAIN_K];
-      unsigned tiebits = 0u;
-      PfxPair mine = {0u, 0u};
-#pragma unroll
-      for (int k = 0; k < CHAIN_K; k++) {
-        const int li = t0 + k;
-        bool bad, tie;
-        chain_classify(xv[k], re, f[k], tie, bad);
-        if (li < pos || li >= cnt) { f[k] = 0u; tie = false; bad = false; }
-        if (bad) first = min(first, li);
-        tiebits |= tie ? (1u << k) : 0u;
-        mine = pfx_compose(mine, pfx_element_pair(f[k], tie));
-      }
-      const PfxPair ex = pfx_pair_dpp<0x138, 0xF>(pfx_pair_wave_scan(mine));   // exclusive: wave_shr:1
-      unsigned state = R + ((R & 1u) ? ex.a1 : ex.a0);
-#pragma unroll
-      for (int k = 0; k < CHAIN_K; k++) {
-        state += f[k] + (((tiebits >> k) & 1u) ? ((state + f[k]) & 1u) : 0u);
-        st[k] = state;
-        const int li = t0 + k;
-        if (li >= pos && li < cnt && state >= (1u << 24)) first = min(first, li);
-      }
+      first = chain_step<true, A>(xv, t0, pos, cnt, r, sc, st);
     }
-    const int stop = uws_wave_min(first);   // first addend that is really added (cnt: none)
-    unsigned sv = 0u;   // in the lane that holds it: the mantissa before the stop, the addend at the stop
-    double xs = 0.0;
+    const int stop = sc.first_of(first, cnt);   // first addend that is really added (cnt: none)
 #pragma unroll
-    for (int k = 0; k < CHAIN_K; k++) {
-      if (t0 + k == stop - 1) sv = st[k];
-      if (t0 + k == stop) xs = xv[k];
+    for (int k = 0; k < K; k++)
+      if (t0 + k >= pos && t0 + k < stop) sink.put(k, t0 + k, regular ? chain_mant(re, st[k]) : r);
+    unsigned sv = 0u;
+    X xstop = X(0);
+    sc.pick(st, xv, t0, pos, stop, cnt, sv, xstop);
+    if (regular) {
+      if (stop > pos) r = chain_mant(re, sv);
+      sink.committed(r);
     }
-    if (regular && stop > pos) r = uws_mant(re, (unsigned)__builtin_amdgcn_readlane((int)sv, (stop - 1) / CHAIN_K));
     if (stop < cnt) {
-      const double x = uws_readlane_d(xs, stop / CHAIN_K);
-      r = (float)((double)r + x);   // one real addition, in the reference's types
+      r = chain_add(r, xstop);   // one real addition, in the reference's types
+      sink.put_stop(t0, stop, r);
       pos = stop + 1;
     } else {
       pos = cnt;
@@ -1338,27 +982,413 @@ __device__ __forceinline__ float uws_wave_walk(int kind, int lo, int cnt, float 
   }
   return r;
 }
+
+// ---- the heads ---------------------------------------------------------------------------------------------------------------
+// The first hn addends one by one on one wave: 64 at a time into the lanes, then every lane runs the same chain over
+// them.  KEEP (the running sum): every lane keeps the sum behind its own addend, which replaces the weight in the LDS image.
+template <bool KEEP, class A>
+__device__ __forceinline__ float chain_head_lanes(const A& a, int hn) {
+  using X = typename A::value_t;
+  extern __shared__ float uws_lraw[];
+  const int lane = threadIdx.x & 63;
+  float run = 0.f;
+  X nxt = a.load(min(lane, hn - 1), lane < hn);
+  for (int b = 0; b < hn; b += 64) {
+    const X cur = nxt;
+    nxt = a.load(min(b + 64 + lane, hn - 1), b + 64 + lane < hn);
+    float mine = 0.f;
+#pragma unroll
+    for (int j = 0; j < 64; j++) {
+      run = chain_add(run, chain_readlane(cur, j));
+      if (KEEP) mine = (lane == j) ? run : mine;
+    }
+    if (KEEP && b + lane < hn) uws_lraw[uws_idx(b + lane)] = mine;
+  }
+  return run;
+}
+// The first hn <= CHAIN_HEAD addends one by one by a single thread of a workgroup of NT, out of LDS, starting from r0:
+// the form of the two workgroup-level walkers (their timing is pinned to it).  Returns the sum in every thread.
+#ifndef CHAIN_HEAD
+#define CHAIN_HEAD 1024   // leading addends added one by one (<= PFXM_CHUNK)
+#endif
+template <int NT, class A>
+__device__ __forceinline__ float chain_head_serial(const A& a, int hn, float r0) {
+  __shared__ double head[CHAIN_HEAD];
+  __shared__ float s_head_r;
+  pfx_sync();
+  for (int t = threadIdx.x; t < hn; t += NT) head[t] = a.load(t, true);
+  pfx_sync();
+  if (threadIdx.x == 0) {
+    float run = r0;
+    if (a.kind == CHAIN_SUM) {   // float addends: the float form (chain_add)
+      for (int t = 0; t < hn; t++) run = chain_add(run, (float)head[t]);
+    } else {
+      for (int t = 0; t < hn; t++) run = chain_add(run, head[t]);
+    }
+    s_head_r = run;
+  }
+  pfx_sync();
+  return s_head_r;
+}
+
+// ==== the multi-workgroup chains ==============================================================================================
+//   1. *_sum_kernel      — per chunk of PFXM_CHUNK addends: the sum in double
+//   2. *_summary_kernel  — per chunk: binade predicted from the double sum of everything before it; (D0, D1) in that
+//                          binade, or "irregular" (NaN / inf / negative / addend above the binade)
+//   3. *_walk_kernel     — ONE workgroup walks the chunks in order with the exact running sum: a chunk whose prediction
+//                          holds (same binade, R + D_p stays below 2^24) is a single integer add; any other chunk (the
+//                          ~log2(n) binade crossings, irregular addends, the head) is carried through on the spot
+//   4. pfx_chunk_fill_kernel (running sum only) — per accepted chunk: the same scan again, now with the exact starting
+//                          mantissa, writes every element's running sum / running maximum
+// pfx_*: the running sum, NT x K = 256 x 16 in the grid kernels; chain_*: the statistics chains, 512 x 8.
+template <int NT, int K, class A>
+__device__ __forceinline__ void chain_sum_body(const A& a, int64_t n, PfxChunk* __restrict__ ch) {
+  __shared__ double shd[NT / 64];
+  const long long lo = (long long)blockIdx.x * PFXM_CHUNK;
+  const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
+  typename A::value_t xv[K];
+  a.load_items(lo, cnt, threadIdx.x * K, xv);
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < K; k++) acc += (double)xv[k];
+  const double t = chain_wg_sum<NT>(acc, shd);
+  if (threadIdx.x == 0) ch[blockIdx.x].sum = t;
+}
+template <int NT, int K, class A>
+__device__ __forceinline__ void chain_summary_body(const A& a, int64_t n, PfxChunk* __restrict__ ch, int c_first) {
+  __shared__ double shd[NT / 64];
+  __shared__ PfxPair shp[NT / 64];
+  __shared__ int s_bad;
+  const int c = blockIdx.x + c_first;   // (the chunks before c_first are not walked, see prefix_multi / tdr_chain_total)
+  const long long lo = (long long)c * PFXM_CHUNK;
+  const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
+  // predicted running sum before the chunk: the double sums of the chunks before it, in chunk order per thread
+  double acc = 0.0;
+  for (int j = threadIdx.x; j < c; j += NT) acc += ch[j].sum;
+  if (threadIdx.x == 0) s_bad = 0;
+  const double before = chain_wg_sum<NT>(acc, shd);
+  const float r_pred = (float)before, r_end = (float)(before + ch[c].sum);
+  const unsigned pb = __float_as_uint(r_pred), eb = __float_as_uint(r_end);
+  const int re = (pb >> 23) & 0xFF;
+  // a chunk that is predicted to start and end in one binade of a positive normal sum; everything else is irregular
+  const bool plausible = (pb >> 31) == 0 && re >= PFXM_RE_MIN && re <= PFXM_RE_MAX && (int)((eb >> 23) & 0xFF) == re && (eb >> 31) == 0;
+  if (!plausible) {   // uniform across the workgroup
+    if (threadIdx.x == 0) { ch[c].re = -1; ch[c].d0 = 0u; ch[c].d1 = 0u; }
+    return;
+  }
+  typename A::value_t xv[K];
+  a.load_items(lo, cnt, threadIdx.x * K, xv);
+  PfxPair mine = {0u, 0u};
+  bool anybad = false;
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    unsigned f; bool tie, bad;
+    A::classify(xv[k], (unsigned)re, f, tie, bad);
+    anybad |= bad;
+    mine = pfx_compose(mine, pfx_element_pair(f, tie));
+  }
+  if (anybad) s_bad = 1;   // benign race: every writer stores 1; ordered by the barrier inside the scan
+  PfxPair total;
+  (void)pfx_pair_scan<NT>(mine, shp, total);
+  if (threadIdx.x == 0) {
+    const bool ok = s_bad == 0 && total.a0 < (1u << 24) && total.a1 < (1u << 24);
+    ch[c].re = ok ? re : -1;
+    ch[c].d0 = total.a0;
+    ch[c].d1 = total.a1;
+  }
+}
+// The walk over the chunk list [c_first, nch) by one workgroup of PFXW_THREADS: the headers staged PFXW_BLOCK at a time;
+// a chunk whose prediction holds is one integer add, any other goes to slow(c), which carries r (and carry) through it.
+// FILL: note r / carry in front of every accepted chunk and mark it, for pfx_chunk_fill_kernel.  (Chunk 0 starts at
+// zero or behind a serial head and is never taken as predicted.)
+#define PFXW_BLOCK 512   // chunk summaries / headers staged in LDS at a time
+template <bool FILL, class CH, class SLOW>
+__device__ __forceinline__ void chain_walk_chunks(CH* __restrict__ ch, int nch, int c_first, float& r, float& carry, SLOW slow) {
+  __shared__ int sm_re[PFXW_BLOCK];
+  __shared__ unsigned sm_d0[PFXW_BLOCK], sm_d1[PFXW_BLOCK];
+  __shared__ int sm_acc[FILL ? PFXW_BLOCK : 1];
+  __shared__ float sm_r0[FILL ? PFXW_BLOCK : 1], sm_c0[FILL ? PFXW_BLOCK : 1];
+  for (int cb = 0; cb < nch; cb += PFXW_BLOCK) {
+    pfx_sync();
+    for (int t = threadIdx.x; t < PFXW_BLOCK && cb + t < nch; t += PFXW_THREADS) {
+      const PfxChunk x = ch[cb + t];
+      sm_re[t] = x.re; sm_d0[t] = x.d0; sm_d1[t] = x.d1;
+      if constexpr (FILL) sm_acc[t] = 0;
+    }
+    pfx_sync();
+    const int ce = min(nch, cb + PFXW_BLOCK);
+    for (int c = max(cb, c_first); c < ce; c++) {
+      const unsigned rb = __float_as_uint(r);
+      const int re = (int)(rb >> 23);                   // sign bit included: a negative sum never matches
+      const unsigned R = (rb & 0x7FFFFFu) | 0x800000u;
+      const unsigned D = (R & 1u) ? sm_d1[c - cb] : sm_d0[c - cb];
+      // sm_re is in [PFXM_RE_MIN, PFXM_RE_MAX] or -1; the waves run through this loop unsynchronised and all store the same words
+      if (c > 0 && sm_re[c - cb] == re && R + D < (1u << 24)) {
+        if constexpr (FILL) { sm_r0[c - cb] = r; sm_c0[c - cb] = carry; sm_acc[c - cb] = 1; }
+        r = chain_mant((unsigned)re, R + D);
+        carry = fmaxf(carry, r);
+      } else {
+        slow(c);
+      }
+#ifdef TDR_PFX_TIMING   // diagnostic build: time stamp (100 MHz) after every chunk in the header's dead `sum` slot
+      if constexpr (FILL)
+        if (threadIdx.x == 0) *reinterpret_cast<long long*>(&ch[c].sum) = (long long)wall_clock64();
+#endif
+    }
+    if constexpr (FILL) {
+      pfx_sync();
+      for (int t = threadIdx.x; t < PFXW_BLOCK && cb + t < nch; t += PFXW_THREADS) {   // for pfx_chunk_fill_kernel
+        PfxChunk* o = ch + cb + t;
+        o->r0 = sm_r0[t];
+        o->carry0 = sm_c0[t];
+        o->accepted = sm_acc[t];
+      }
+    }
+  }
+}
+
+// ---- the running sum ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PFXM_THREADS) void pfx_chunk_sum_kernel(const float* __restrict__ w, int64_t n,
+                                                                     PfxChunk* __restrict__ ch) {
+  chain_sum_body<PFXM_THREADS, PFXM_K>(PfxRunSum{{w}, CHAIN_RUNSUM, 0.f}, n, ch);
+}
+__global__ __launch_bounds__(PFXM_THREADS) void pfx_chunk_summary_kernel(const float* __restrict__ w, int64_t n,
+                                                                         PfxChunk* __restrict__ ch, int c_first) {
+  chain_summary_body<PFXM_THREADS, PFXM_K>(PfxRunSum{{w}, CHAIN_RUNSUM, 0.f}, n, ch, c_first);
+}
+#define PFXW_HEAD 64   // leading elements the walk adds one by one (tunable: tdr_config_tuning("prefix_head", n))
+static int g_pfx_head = PFXW_HEAD;
+extern "C" int tdr_config_prefix_head(int n) {   // < 0: query only
+  if (n >= 0) g_pfx_head = n < 1 ? 1 : (n > PFX_HEAD ? PFX_HEAD : n);
+  return g_pfx_head;
+}
+// A chunk the walk cannot take as one integer add (it holds a binade crossing or an irregular weight, or was
+// mispredicted), carried through in order by the walking workgroup
+__device__ __forceinline__ void pfx_walk_chunk(const float* __restrict__ w, long long lo, int cnt,
+                                               float* __restrict__ runmax, float* __restrict__ prefix_opt,
+                                               float& r, float& carry, int head_len) {
+  __shared__ PfxPair shp[PFXW_THREADS / 64];
+  __shared__ ChainWgStop<float> stp;
+  const PfxRunSum a{{w}, CHAIN_RUNSUM, 0.f};
+  const int t0 = threadIdx.x * PFXW_K;
+  float wv[PFXW_K];
+  a.load_items(lo, cnt, t0, wv);
+  const ChainWg<PFXW_THREADS, float> sc{shp, &stp};
+  PfxGlobalSink sink{w, lo, runmax, prefix_opt, carry, head_len};
+  r = chain_walk(a, wv, t0, 0, cnt, r, sc, sink);
+}
+__global__ __launch_bounds__(PFXW_THREADS) void pfx_walk_kernel(const float* __restrict__ w, int64_t n,
+                                                               PfxChunk* __restrict__ ch, int nch,
+                                                               float* __restrict__ runmax,
+                                                               float* __restrict__ prefix_opt, int head_len,
+                                                               int c_first, const float* __restrict__ tail) {
+  // workgroup-uniform; chunks [0, c_first) were done by pfx_small_kernel, which left the sum and the maximum behind them
+  float r = c_first > 0 ? tail[0] : 0.f, carry = c_first > 0 ? tail[1] : -INFINITY;
+  chain_walk_chunks<true>(ch, nch, c_first, r, carry, [&](int c) {
+    const long long lo = (long long)c * PFXM_CHUNK;
+    const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
+    pfx_walk_chunk(w, lo, cnt, runmax, prefix_opt, r, carry, head_len);
+  });
+}
+__global__ __launch_bounds__(PFXM_THREADS) void pfx_chunk_fill_kernel(const float* __restrict__ w, int64_t n,
+                                                                      const PfxChunk* __restrict__ ch,
+                                                                      float* __restrict__ runmax,
+                                                                      float* __restrict__ prefix_opt) {
+  __shared__ PfxPair shp[PFXM_THREADS / 64];
+  const int c = blockIdx.x;
+  const PfxChunk hdr = ch[c];
+  if (!hdr.accepted) return;   // written by the walk
+  const long long lo = (long long)c * PFXM_CHUNK;
+  const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
+  const PfxRunSum a{{w}, CHAIN_RUNSUM, 0.f};
+  const int t0 = threadIdx.x * PFXM_K;
+  float wv[PFXM_K];
+  a.load_items(lo, cnt, t0, wv);
+  const ChainWg<PFXM_THREADS, float> sc{shp, nullptr};
+  unsigned st[PFXM_K];
+  (void)chain_step<false, PfxRunSum>(wv, t0, 0, cnt, hdr.r0, sc, st);
+  float val[PFXM_K];
+#pragma unroll
+  for (int k = 0; k < PFXM_K; k++) val[k] = chain_mant(__float_as_uint(hdr.r0) >> 23, st[k]);
+  const float carry = hdr.carry0;
+  if (t0 + PFXM_K <= cnt && ((lo & 3) == 0)) {
+    float4* o = reinterpret_cast<float4*>(runmax + lo + t0);
+#pragma unroll
+    for (int k = 0; k < PFXM_K / 4; k++)
+      o[k] = make_float4(fmaxf(carry, val[4 * k]), fmaxf(carry, val[4 * k + 1]), fmaxf(carry, val[4 * k + 2]),
+                         fmaxf(carry, val[4 * k + 3]));
+    if (prefix_opt) {
+      float4* q = reinterpret_cast<float4*>(prefix_opt + lo + t0);
+#pragma unroll
+      for (int k = 0; k < PFXM_K / 4; k++) q[k] = make_float4(val[4 * k], val[4 * k + 1], val[4 * k + 2], val[4 * k + 3]);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < PFXM_K; k++)
+      if (t0 + k < cnt) {
+        runmax[lo + t0 + k] = fmaxf(carry, val[k]);
+        if (prefix_opt) prefix_opt[lo + t0 + k] = val[k];
+      }
+  }
+}
+
+// ---- totals of the statistics chains ---------------------------------------------------------------------------------------------
+// ParticleFilter::update's statistics (CHAIN_SUM, CHAIN_BOTTOM) are serial chains too, and only their FINAL values are
+// used.  Both are carried with the addend as a double made on the fly from (raw, mean).  Chunks as above: double sum ->
+// predicted binade + parity summary -> one walking workgroup; no fill pass.
+struct ChainSrc {
+  const float* raw;    // raw weights
+  const float* mean;   // device scalar (kind 1)
+  int kind;            // CHAIN_SUM / CHAIN_BOTTOM
+};
+__device__ __forceinline__ ChainStat chain_stat(const ChainSrc& s) { return {{s.raw}, s.kind, s.kind ? *s.mean : 0.f}; }
+__global__ __launch_bounds__(PFXW_THREADS) void chain_sum_kernel(ChainSrc s, int64_t n, PfxChunk* __restrict__ ch) {
+  chain_sum_body<PFXW_THREADS, CHAIN_K>(chain_stat(s), n, ch);
+}
+__global__ __launch_bounds__(PFXW_THREADS) void chain_summary_kernel(ChainSrc s, int64_t n, PfxChunk* __restrict__ ch,
+                                                                    int c_first) {
+  chain_summary_body<PFXW_THREADS, CHAIN_K>(chain_stat(s), n, ch, c_first);
+}
+// one chunk on the spot by the whole workgroup, from its element pos on: no outputs, the total only
+template <class A>
+__device__ __forceinline__ void chain_walk_chunk(const A& a, long long lo, int cnt, float& r, int pos) {
+  __shared__ PfxPair shp[PFXW_THREADS / 64];
+  __shared__ ChainWgStop<double> stp;
+  const int t0 = threadIdx.x * CHAIN_K;
+  double xv[CHAIN_K];
+  a.load_items(lo, cnt, t0, xv);
+  const ChainWg<PFXW_THREADS, double> sc{shp, &stp};
+  ChainNoSink sink;
+  r = chain_walk(a, xv, t0, pos, cnt, r, sc, sink);
+}
+__global__ __launch_bounds__(PFXW_THREADS) void chain_walk_kernel(ChainSrc s, int64_t n, const PfxChunk* __restrict__ ch,
+                                                                 int nch, float* __restrict__ total_out, int c_first,
+                                                                 const float* __restrict__ r_first) {
+  const ChainStat a = chain_stat(s);
+  // head: the sum of unnormalised weights crosses a binade every time it doubles — about ten times within the first
+  // thousand addends — so those are added one by one
+  // (c_first > 0: chunks [0, c_first) were summed by chain_head_kernel, which left the sum behind them in *r_first)
+  const int hn = c_first > 0 ? 0 : (int)min((long long)CHAIN_HEAD, (long long)n);
+  float r = chain_head_serial<PFXW_THREADS>(a, hn, c_first > 0 ? *r_first : 0.f), carry = 0.f;   // workgroup-uniform
+  chain_walk_chunks<false>(ch, nch, c_first, r, carry, [&](int c) {
+    const long long lo = (long long)c * PFXM_CHUNK;
+    chain_walk_chunk(a, lo, (int)min((long long)PFXM_CHUNK, (long long)n - lo), r, c == 0 ? hn : 0);
+  });
+  if (threadIdx.x == 0) *total_out = r;
+}
+static int g_pfx_small = 1;   // 0 = without the one-launch kernel (A/B and debugging)
+extern "C" int tdr_config_prefix_small(int on) {   // < 0: query only
+  if (on >= 0) g_pfx_small = on ? 1 : 0;
+  return g_pfx_small;
+}
+#define CHAIN_HEAD_N 32768
+// whole chunks at the start that the one-workgroup machinery takes (0: none; tdr_config_prefix_small(0) switches it off
+// for the running sum AND the statistics chains: the chunk walk from the first addend on, for A/B and debugging)
+static int chain_head_chunks(int64_t n) { return (g_pfx_small && n >= CHAIN_HEAD_N) ? CHAIN_HEAD_N / PFXM_CHUNK : 0; }
+static int chain_head_launch(const float* raw, const float* mean_dev, int kind, int n_head, float* r_out, hipStream_t st);
+// raw: [n] raw weights; kind 0: total = serial float sum of the non-NaN weights; kind 1: total = serial
+// float-accumulated sum of pow(w - *mean_dev, 2) over the non-NaN weights below *mean_dev.  workspace: chunk headers,
+// tdr_prefix_workspace_bytes(n).  total_out: one device float.
+int tdr_chain_total(const float* raw, const float* mean_dev, int kind, int64_t n, float* total_out, void* workspace,
+                    hipStream_t st) {
+  const int64_t nch64 = cdiv(n, (int64_t)PFXM_CHUNK);
+  if (nch64 > (1 << 24)) return fail(TDR_ERR_ARG, "chain_total: n too large");
+  const int nch = (int)nch64;
+  PfxChunk* ch = reinterpret_cast<PfxChunk*>(workspace);
+  ChainSrc s{raw, mean_dev, kind};
+  // The first 32 768 addends — where the sum crosses most of its binades — go through the one-workgroup machinery of
+  // uw_small_kernel (chain_head_kernel, below); the chunk walk starts behind them.
+  const int c_first = chain_head_chunks(n);
+  hipLaunchKernelGGL(chain_sum_kernel, dim3(nch), dim3(PFXW_THREADS), 0, st, s, n, ch);
+  if (nch > c_first)
+    hipLaunchKernelGGL(chain_summary_kernel, dim3(nch - c_first), dim3(PFXW_THREADS), 0, st, s, n, ch, c_first);
+  float* r_first = reinterpret_cast<float*>(&ch[0].r0);   // (a header slot the chains do not use)
+  if (c_first > 0) {
+    const int rc = chain_head_launch(raw, mean_dev, kind, c_first * PFXM_CHUNK, r_first, st);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(chain_walk_kernel, dim3(1), dim3(PFXW_THREADS), 0, st, s, n, (const PfxChunk*)ch, nch, total_out,
+                     c_first, (const float*)r_first);
+  return TDR_OK;
+}
+
+// ==== ParticleFilter::update's statistics for small particle sets, in ONE launch ==========================================
+// src/particle_filter.cpp:107-147 for n <= TDR_UW_SMALL_MAX_N — the reference's own operating point (20 000 particles,
+// src/top_down_render.cpp:53).  One workgroup; the raw weights are staged into LDS once (n floats, at most 128 KB) and
+// every pass — the two exact serial chains, the counts, fill / normalise / argmax — runs out of LDS; the weights are
+// written to memory once, at the end.  Same results as the multi-workgroup path of tdr_filter.hip, bit for bit in
+// `sum`, `mean`, `bottom_stddev` (tests/test_gpu_parity.py::test_update_weights_serial_chains_bit_exact).
+//
+// The chains on the whole workgroup (tdr_config_uw_waves(0)): head one by one, then chunk by chunk with
+// chain_walk_chunk (no prediction pass: at most 8 chunks).  (One stretch over the whole array instead of chunks
+// re-classifies every remaining addend at each binade crossing: 80 us against 48 at 20 000 weights.)
+__device__ __forceinline__ float uws_chain_total(int kind, int n, float mean) {
+  const UwsWgAdd a{{}, kind, mean};
+  const int hn = min(CHAIN_HEAD, n);
+  float r = chain_head_serial<PFXW_THREADS>(a, hn, 0.f);   // workgroup-uniform
+  UW_STAMP(kind ? 5 : 2);
+  const int nch = (n + PFXM_CHUNK - 1) / PFXM_CHUNK;
+  for (int c = 0; c < nch; c++) {
+    const int lo = c * PFXM_CHUNK;
+    const int cnt = min((int)PFXM_CHUNK, n - lo);
+    if (c == 0 && hn >= cnt) continue;
+    chain_walk_chunk(a, lo, cnt, r, c == 0 ? hn : 0);
+  }
+  return r;
+}
+// ---- the same chains, wave by wave (default) --------------------------------------------------------------------------
+// The weights are cut into wave-chunks of 512 (one wave, 8 consecutive addends a lane).  The pass before the chain (the
+// count of valid weights / of weights below the mean) leaves the double sum of every wave-chunk's addends behind; from the
+// sums before a chunk every wave predicts the binade the chain is in when it enters and leaves it.  Then, side by side:
+//   * wave 0 adds the first wave-chunk one by one (the sum starts at zero and doubles every few addends);
+//   * the other waves summarise their chunks: a chunk predicted to stay in one binade as its parity pair (D0, D1) there;
+//     a chunk predicted to cross into the next binade as the parity pairs of every LANE (8 addends) in both binades.
+// One barrier later wave 0 walks the chunk list with the exact running sum, with register-level moves only — no workgroup
+// barrier inside the serial part: a one-binade chunk whose prediction holds is one integer add; in a crossing chunk a
+// scan of the lane pairs of the first binade finds the lane the sum crosses in, that lane's 8 addends are really added,
+// and a scan of the lane pairs of the second binade carries the sum to the chunk's end.  Whatever fits neither (a wrong
+// prediction, irregular addends, two crossings in one chunk) is carried through element by element by uws_wave_walk.
+// The bits are the serial chain's whatever was predicted, as in the multi-workgroup path.
+#define UWS_THREADS 1024
+#define UWS_DUAL_SLOTS 8        // crossing chunks summarised lane by lane (the sum doubles log2(n / 512) times behind the head)
+#define UWS_DUAL_FLAG 0x100
+struct UwsShared {
+  double csum[64];                       // double sum of every wave-chunk's addends
+  int code[64];                          // -1: carried through; binade; binade | UWS_DUAL_FLAG | slot << 16
+  unsigned d0[64], d1[64];               // parity pair of a one-binade chunk
+  uint4 dual[UWS_DUAL_SLOTS][64];        // crossing chunks: scans of the lane pairs in the binade entered (x, y) / the next (z, w)
+  double shd[UWS_THREADS / 64];
+  float total;
+};
+// wave-chunk [lo, lo + cnt) carried through by the calling wave from its element `pos` on, entered with the running sum r
+// (wave-uniform): chain_walk on one wave, every chain with double addends as chain_walk_chunk has them
+template <class A>
+__device__ __forceinline__ float uws_wave_walk(const A& a, int lo, int cnt, float r, int pos) {
+  const auto ad = a.as_double();
+  const int t0 = (threadIdx.x & 63) * CHAIN_K;
+  double xv[CHAIN_K];
+  ad.load_items(lo, cnt, t0, xv);
+  ChainNoSink sink;
+  return chain_walk(ad, xv, t0, pos, cnt, r, ChainWave<false>{}, sink);
+}
 // a chunk summarised lane by lane — the inclusive scans of the lanes' parity pairs in the binade predicted at its entry
 // (x, y) and in the next one (z, w) — entered with r; pos: the element of the chunk the returned sum stands before (cnt: the
 // chunk is done, else uws_wave_walk takes over there)
-__device__ __forceinline__ float uws_wave_dual(int kind, int lo, int cnt, float mean, float r, const uint4* pq, int& pos) {
+template <class A>
+__device__ __forceinline__ float uws_wave_dual(const A& a, int lo, int cnt, float r, const uint4* pq, int& pos) {
   const int lane = threadIdx.x & 63, t0 = lane * CHAIN_K;
   const unsigned rb = __float_as_uint(r), re = rb >> 23, R = (rb & 0x7FFFFFu) | 0x800000u;
   const uint4 v = pq[lane];
   const unsigned after = R + ((R & 1u) ? v.y : v.x);   // mantissa behind this lane's addends, while below 2^24
   const unsigned long long cross = __ballot(after >= (1u << 24));
   pos = cnt;
-  if (cross == 0ull) return uws_mant(re, (unsigned)__builtin_amdgcn_readlane((int)after, 63));
+  if (cross == 0ull) return chain_mant(re, (unsigned)__builtin_amdgcn_readlane((int)after, 63));
   const int L = __ffsll((long long)cross) - 1;   // the lane the sum leaves the binade in: its addends are really added
-  float rl = uws_mant(re, L > 0 ? (unsigned)__builtin_amdgcn_readlane((int)after, L - 1) : R);   // exact before lane L
-  UwsX x[CHAIN_K];
+  float rl = chain_mant(re, L > 0 ? (unsigned)__builtin_amdgcn_readlane((int)after, L - 1) : R);   // exact before lane L
+  typename A::value_t x[CHAIN_K];
+  a.load_items(lo, cnt, t0, x);
 #pragma unroll
-  for (int k = 0; k < CHAIN_K; k++) x[k] = uws_load_x(kind, lo + t0 + k, t0 + k < cnt, mean);
-#pragma unroll
-  for (int k = 0; k < CHAIN_K; k++) {
-    if (kind != 1) rl += x[k].f;   // float + float: the same sum as through double
-    else rl = (float)((double)rl + x[k].d);
-  }
+  for (int k = 0; k < CHAIN_K; k++) rl = chain_add(rl, x[k]);
   const float r2 = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(rl), L));
   const unsigned rb2 = __float_as_uint(r2), R2 = (rb2 & 0x7FFFFFu) | 0x800000u;
   const int next = (L + 1) * CHAIN_K;
@@ -1372,61 +1402,19 @@ __device__ __forceinline__ float uws_wave_dual(int kind, int lo, int cnt, float 
   const unsigned q63 = (unsigned)__builtin_amdgcn_readlane((int)(((R2 + qL) & 1u) ? v.w : v.z), 63);
   if (q63 >= PFXM_SAT || R2 + (q63 - qL) >= (1u << 24)) return r2;
   pos = cnt;
-  return uws_mant(re + 1u, R2 + (q63 - qL));
-}
-// the first hn addends one by one: 64 at a time into the lanes, then every lane runs the same chain over them
-__device__ __forceinline__ float uws_head(int kind, int hn, float mean) {
-  const int lane = threadIdx.x & 63;
-  float run = 0.f;
-  if (kind == 0) {
-    // float + float: (float)((double)a + (double)b) == a + b for every pair of floats (53 >= 2 * 24 + 2 bits)
-    float nxt = (float)uws_addend_if(0, min(lane, hn - 1), lane < hn, 0.f);
-    for (int b = 0; b < hn; b += 64) {
-      const int cur = (int)__float_as_uint(nxt);
-      nxt = (float)uws_addend_if(0, min(b + 64 + lane, hn - 1), b + 64 + lane < hn, 0.f);
-#pragma unroll
-      for (int j = 0; j < 64; j++) run += __uint_as_float((unsigned)__builtin_amdgcn_readlane(cur, j));
-    }
-  } else {
-    double nxt = uws_addend_if(1, min(lane, hn - 1), lane < hn, mean);
-    for (int b = 0; b < hn; b += 64) {
-      const double cur = nxt;
-      nxt = uws_addend_if(1, min(b + 64 + lane, hn - 1), b + 64 + lane < hn, mean);
-#pragma unroll
-      for (int j = 0; j < 64; j++) run = (float)((double)run + uws_readlane_d(cur, j));
-    }
-  }
-  return run;
-}
-// the running sum of the resample: the same head, and every lane keeps the running sum behind its own addend, which
-// replaces the weight in the staged array
-__device__ __forceinline__ float pfs_head(int hn) {
-  extern __shared__ float uws_lraw[];
-  const int lane = threadIdx.x & 63;
-  float run = 0.f;
-  float nxt = uws_addend_f(2, min(lane, hn - 1), lane < hn);
-  for (int b = 0; b < hn; b += 64) {
-    const int cur = (int)__float_as_uint(nxt);
-    nxt = uws_addend_f(2, min(b + 64 + lane, hn - 1), b + 64 + lane < hn);
-    float mine = 0.f;
-#pragma unroll
-    for (int j = 0; j < 64; j++) {
-      run += __uint_as_float((unsigned)__builtin_amdgcn_readlane(cur, j));
-      mine = (lane == j) ? run : mine;
-    }
-    if (b + lane < hn) uws_lraw[uws_idx(b + lane)] = mine;
-  }
-  return run;
+  return chain_mant(re + 1u, R2 + (q63 - qL));
 }
 // sh.csum holds the chunks' double sums and a barrier has passed since they were written; rin (kind 2): the running sum
 // in front of every wave-chunk
-__device__ __forceinline__ float uws_chain_total_waves(int kind, int n, float mean, UwsShared& sh, float* rin = nullptr) {
+template <class A>
+__device__ __forceinline__ float uws_chain_total_waves(const A& a, int n, UwsShared& sh, float* rin = nullptr) {
+  const int kind = a.kind;
   constexpr int NW = UWS_THREADS / 64;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), t0 = lane * CHAIN_K;
   const int nwc = (n + UWS_WC - 1) / UWS_WC;   // <= 64
   float r = 0.f;
   if (wave == 0) {
-    r = kind == 2 ? pfs_head(min(UWS_WC, n)) : uws_head(kind, min(UWS_WC, n), mean);
+    r = kind == CHAIN_RUNSUM ? chain_head_lanes<true>(a, min(UWS_WC, n)) : chain_head_lanes<false>(a, min(UWS_WC, n));
   } else {
     // the running double sum before / after each chunk -> what is predicted for it (lane c: chunk c)
     int my_code;
@@ -1448,22 +1436,21 @@ __device__ __forceinline__ float uws_chain_total_waves(int kind, int n, float me
       if (code >= 0) {
         const unsigned re = (unsigned)(code & 0xFF);
         const bool dual = (code & UWS_DUAL_FLAG) != 0;
-        UwsX x[CHAIN_K];   // (all eight reads in flight before the first use)
-#pragma unroll
-        for (int k = 0; k < CHAIN_K; k++) x[k] = uws_load_x(kind, lo + t0 + k, t0 + k < cnt, mean);
+        typename A::value_t x[CHAIN_K];   // (all eight reads in flight before the first use)
+        a.load_items(lo, cnt, t0, x);
         // without a rounding tie in the chunk a lane's pair is (s, s), s the plain sum of its increments
         bool anytie = false;
         unsigned f; bool tie, bad;
 #pragma unroll
         for (int k = 0; k < CHAIN_K; k++) {
-          uws_classify_x(kind, x[k], re, f, tie, bad);
+          A::classify(x[k], re, f, tie, bad);
           anybad |= bad; anytie |= tie;
-          P.a0 += f;   // (f < 2^22: no overflow in a lane, none below 2^31 in a wave)
+          P.a0 += f;   // (CHAIN_BOUND_22: no overflow in a lane, none below 2^31 in a wave)
         }
         if (dual) {
 #pragma unroll
           for (int k = 0; k < CHAIN_K; k++) {
-            uws_classify_x(kind, x[k], re + 1u, f, tie, bad);
+            A::classify(x[k], re + 1u, f, tie, bad);
             anybad |= bad; anytie |= tie;
             Q.a0 += f;
           }
@@ -1472,17 +1459,21 @@ __device__ __forceinline__ float uws_chain_total_waves(int kind, int n, float me
           P.a0 = P.a1 = uws_wave_scan_u(P.a0);
           if (dual) Q.a0 = Q.a1 = uws_wave_scan_u(Q.a0);
         } else {
+          // (rare.  The binade is made opaque here so that this branch classifies again instead of keeping the f and tie
+          // of all sixteen classifications above alive across the ballot: 16 VGPRs, and uw_small_kernel<true> has none to spare)
+          unsigned re_t = re;
+          asm volatile("" : "+s"(re_t));
           P = PfxPair{0u, 0u}; Q = PfxPair{0u, 0u};
 #pragma unroll
           for (int k = 0; k < CHAIN_K; k++) {
-            uws_classify_x(kind, x[k], re, f, tie, bad);
+            A::classify(x[k], re_t, f, tie, bad);
             P = pfx_compose(P, pfx_element_pair(f, tie));
           }
           P = pfx_pair_wave_scan(P);
           if (dual) {
 #pragma unroll
             for (int k = 0; k < CHAIN_K; k++) {
-              uws_classify_x(kind, x[k], re + 1u, f, tie, bad);
+              A::classify(x[k], re_t + 1u, f, tie, bad);
               Q = pfx_compose(Q, pfx_element_pair(f, tie));
             }
             Q = pfx_pair_wave_scan(Q);
@@ -1524,11 +1515,11 @@ __device__ __forceinline__ float uws_chain_total_waves(int kind, int n, float me
         }
         const unsigned long long cross = __ballot(in_run && after >= (1u << 24));
         const int c1 = cross ? __ffsll((long long)cross) - 1 : cend;   // chunks [c, c1) are taken
-        if (kind == 2) {
+        if (kind == CHAIN_RUNSUM) {
           const unsigned prev = (unsigned)__builtin_amdgcn_update_dpp(0, (int)after, 0x138, 0xF, 0xF, false);   // wave_shr:1
-          if (lane >= c && lane < c1) v_rin = lane == c ? r : uws_mant((unsigned)re, prev);
+          if (lane >= c && lane < c1) v_rin = lane == c ? r : chain_mant((unsigned)re, prev);
         }
-        if (c1 > c) r = uws_mant((unsigned)re, (unsigned)__builtin_amdgcn_readlane((int)after, c1 - 1));
+        if (c1 > c) r = chain_mant((unsigned)re, (unsigned)__builtin_amdgcn_readlane((int)after, c1 - 1));
 #ifdef TDR_UW_TIMELINE
         if (threadIdx.x == 0) g_uw_tl[12] += c1 - c;
 #endif
@@ -1538,20 +1529,20 @@ __device__ __forceinline__ float uws_chain_total_waves(int kind, int n, float me
       }
       const int lo = c * UWS_WC, cnt = min(UWS_WC, n - lo);
       const int code = __builtin_amdgcn_readlane(v_code, c);
-      if (kind == 2) v_rin = (lane == c) ? r : v_rin;
+      if (kind == CHAIN_RUNSUM) v_rin = (lane == c) ? r : v_rin;
       int pos = 0;
       const int re_now = (int)(__float_as_uint(r) >> 23);
       if (!overflow && code >= 0 && re_now <= PFXM_RE_MAX && (code & 0x1FF) == (re_now | UWS_DUAL_FLAG)) {
-        r = uws_wave_dual(kind, lo, cnt, mean, r, sh.dual[code >> 16], pos);
+        r = uws_wave_dual(a, lo, cnt, r, sh.dual[code >> 16], pos);
         UW_COUNT(13);
       }
       if (pos < cnt) {
         UW_COUNT(14);
-        r = uws_wave_walk(kind, lo, cnt, mean, r, pos);
+        r = uws_wave_walk(a, lo, cnt, r, pos);
       }
       c++;
     }
-    if (kind == 2) rin[lane] = v_rin;
+    if (kind == CHAIN_RUNSUM) rin[lane] = v_rin;
     if (lane == 0) sh.total = r;
   }
   pfx_sync();
@@ -1625,7 +1616,8 @@ __device__ __forceinline__ void uw_small_body(const float* __restrict__ raw, con
       const long long count = (long long)uws_sum_d<nt>((double)cnt, shd);   // (its barriers also publish the staged weights)
       if (kind == 0) valid_sum = uws_readlane_d(uws_wave_scan_d(lane < nwc ? ush.csum[lane] : 0.0), 63);
       UW_STAMP(kind ? 4 : 1);
-      const float total = uws_chain_total_waves(kind, n, mean, ush);   // serial float chain, exact
+      const float total = kind == 0 ? uws_chain_total_waves(UwsAddF{{}, CHAIN_SUM, 0.f}, n, ush)   // serial float chains, exact
+                                    : uws_chain_total_waves(UwsAddD{{}, CHAIN_BOTTOM, mean}, n, ush);
       UW_STAMP(kind ? 6 : 3);
       if (kind == 0) {
         sum = total; num_valid = count;
@@ -1650,7 +1642,7 @@ __device__ __forceinline__ void uw_small_body(const float* __restrict__ raw, con
     }
     num_valid = (long long)uws_sum_d<nt>(cnt, shd);   // (its barriers also publish the staged weights)
     UW_STAMP(1);
-    sum = uws_chain_total(0, n, 0.f);   // serial float chain, exact
+    sum = uws_chain_total(CHAIN_SUM, n, 0.f);   // serial float chain, exact
     UW_STAMP(3);
     mean = sum / (float)num_valid;  // :117 (0/0 -> NaN like the reference)
     // :118-126  bottom_stddev (serial float chain with double addends, exact) and the count below the mean
@@ -1661,7 +1653,7 @@ __device__ __forceinline__ void uw_small_body(const float* __restrict__ raw, con
     }
     num_under = (long long)uws_sum_d<nt>(cu, shd);
     UW_STAMP(4);
-    bsum = uws_chain_total(1, n, mean);
+    bsum = uws_chain_total(CHAIN_BOTTOM, n, mean);
     UW_STAMP(6);
   }
   const float bottom = sqrtf(bsum / (float)num_under);
@@ -1795,104 +1787,20 @@ struct PfsShared {
   float cmax[64];   // largest running sum inside it (NaN skipped)
   int irregular;    // a negative or NaN weight exists: the running sum is not its own running maximum
 };
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float pfs_max_dpp(float v) {
-  return fmaxf(v, __uint_as_float((unsigned)__builtin_amdgcn_update_dpp((int)0xFF800000u, (int)__float_as_uint(v), CTRL,
-                                                                        ROW_MASK, 0xF, false)));
-}
-__device__ __forceinline__ float pfs_wave_scan_max(float v) {   // inclusive maximum over the lanes before and this one
-  v = pfs_max_dpp<0x111, 0xF>(v);
-  v = pfs_max_dpp<0x112, 0xF>(v);
-  v = pfs_max_dpp<0x114, 0xF>(v);
-  v = pfs_max_dpp<0x118, 0xF>(v);
-  v = pfs_max_dpp<0x142, 0xA>(v);
-  v = pfs_max_dpp<0x143, 0xC>(v);
-  return v;
-}
 // wave-chunk [lo, lo + cnt) from its exact starting sum r: every addend's running sum, in place of the weight
 __device__ __forceinline__ void pfs_wave_fill(int lo, int cnt, float r) {
   extern __shared__ float uws_lraw[];
+  const UwsAddF a{{}, CHAIN_RUNSUM, 0.f};
   const int t0 = (threadIdx.x & 63) * CHAIN_K;
-  float x[CHAIN_K], pv[CHAIN_K];
+  float x[CHAIN_K];
+  a.load_items(lo, cnt, t0, x);
+  ChainRegSink<CHAIN_K> sink;
 #pragma unroll
-  for (int k = 0; k < CHAIN_K; k++) { x[k] = uws_addend_f(2, lo + t0 + k, t0 + k < cnt); pv[k] = 0.f; }
-  int pos = 0;
-  while (pos < cnt) {
-    const unsigned rb = __float_as_uint(r);
-    const unsigned re = rb >> 23;   // sign included
-    if (r != r) {                   // NaN stays NaN
-#pragma unroll
-      for (int k = 0; k < CHAIN_K; k++)
-        if (t0 + k >= pos) pv[k] = r;
-      break;
-    }
-    int first = cnt;
-    unsigned st[CHAIN_K] = {};
-    const bool regular = re >= PFXM_RE_MIN && re <= PFXM_RE_MAX;
-    if (!regular) {
-      const bool isinf = (rb & 0x7FFFFFFFu) == 0x7F800000u;
-#pragma unroll
-      for (int k = 0; k < CHAIN_K; k++) {
-        const int li = t0 + k;
-        const bool acts = isinf ? !(fabsf(x[k]) < INFINITY) : (x[k] != 0.f);
-        if (li >= pos && li < cnt && acts) first = min(first, li);
-      }
-    } else {
-      const unsigned R = (rb & 0x7FFFFFu) | 0x800000u;
-      unsigned f[CHAIN_K];
-      unsigned tiebits = 0u, lane_sum = 0u;
-#pragma unroll
-      for (int k = 0; k < CHAIN_K; k++) {
-        const int li = t0 + k;
-        bool bad, tie;
-        uws_classify_f(x[k], re, f[k], tie, bad);
-        if (li < pos || li >= cnt) { f[k] = 0u; tie = false; bad = false; }
-        if (bad) first = min(first, li);
-        tiebits |= tie ? (1u << k) : 0u;
-        lane_sum += f[k];
-      }
-      unsigned state;
-      if (__ballot(tiebits != 0u) == 0ull) {   // no rounding tie: plain sums
-        state = R + (uws_wave_scan_u(lane_sum) - lane_sum);
-      } else {
-        PfxPair mine = {0u, 0u};
-#pragma unroll
-        for (int k = 0; k < CHAIN_K; k++) mine = pfx_compose(mine, pfx_element_pair(f[k], ((tiebits >> k) & 1u) != 0u));
-        const PfxPair ex = pfx_pair_dpp<0x138, 0xF>(pfx_pair_wave_scan(mine));   // exclusive: wave_shr:1
-        state = R + ((R & 1u) ? ex.a1 : ex.a0);
-      }
-#pragma unroll
-      for (int k = 0; k < CHAIN_K; k++) {
-        state += f[k] + (((tiebits >> k) & 1u) ? ((state + f[k]) & 1u) : 0u);
-        st[k] = state;
-        const int li = t0 + k;
-        if (li >= pos && li < cnt && state >= (1u << 24)) first = min(first, li);
-      }
-    }
-    const int stop = uws_wave_min(first);   // first addend that is really added (cnt: none)
-    unsigned sv = 0u;
-    float xs = 0.f;
-#pragma unroll
-    for (int k = 0; k < CHAIN_K; k++) {
-      const int li = t0 + k;
-      if (li >= pos && li < stop) pv[k] = regular ? uws_mant(re, st[k]) : r;
-      if (li == stop - 1) sv = st[k];
-      if (li == stop) xs = x[k];
-    }
-    if (regular && stop > pos) r = uws_mant(re, (unsigned)__builtin_amdgcn_readlane((int)sv, (stop - 1) / CHAIN_K));
-    if (stop < cnt) {
-      r += __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(xs), stop / CHAIN_K));   // one real addition
-#pragma unroll
-      for (int k = 0; k < CHAIN_K; k++)
-        if (t0 + k == stop) pv[k] = r;
-      pos = stop + 1;
-    } else {
-      pos = cnt;
-    }
-  }
+  for (int k = 0; k < CHAIN_K; k++) sink.pv[k] = 0.f;
+  (void)chain_walk(a, x, t0, 0, cnt, r, ChainWave<true>{}, sink);
 #pragma unroll
   for (int k = 0; k < CHAIN_K; k++)
-    if (t0 + k < cnt) uws_lraw[uws_idx(lo + t0 + k)] = pv[k];
+    if (t0 + k < cnt) uws_lraw[uws_idx(lo + t0 + k)] = sink.pv[k];
 }
 // the one-workgroup running sum / running maximum: the body of pfx_small_kernel and of pfx_small_batch_kernel
 __device__ __forceinline__ void pfx_small_body(const float* __restrict__ w, int n, float* __restrict__ runmax,
@@ -1925,7 +1833,7 @@ __device__ __forceinline__ void pfx_small_body(const float* __restrict__ w, int 
   }
   if (__ballot(irr) != 0ull && lane == 0) atomicOr(&sh.irregular, 1);
   pfx_sync();
-  const float total = uws_chain_total_waves(2, n, 0.f, sh.u, sh.rin);   // (ends in a barrier)
+  const float total = uws_chain_total_waves(UwsAddF{{}, CHAIN_RUNSUM, 0.f}, n, sh.u, sh.rin);   // (ends in a barrier)
   // every chunk again from its exact starting sum (the first one was filled by the head)
   for (int c = 1 + wave; c < nwc; c += NW) pfs_wave_fill(c * UWS_WC, min(UWS_WC, n - c * UWS_WC), sh.rin[c]);
   pfx_sync();
@@ -2029,7 +1937,9 @@ __global__ __launch_bounds__(UWS_THREADS) void chain_head_kernel(const float* __
     if (lane == 63) ush.csum[c] = acc;
   }
   pfx_sync();
-  const float r = uws_chain_total_waves(KIND, n, mean, ush);
+  float r;
+  if constexpr (KIND == CHAIN_SUM) r = uws_chain_total_waves(UwsAddF{{}, CHAIN_SUM, 0.f}, n, ush);
+  else r = uws_chain_total_waves(UwsAddD{{}, CHAIN_BOTTOM, mean}, n, ush);
   if (tid == 0) *r_out = r;
 }
 static int chain_head_launch(const float* raw, const float* mean_dev, int kind, int n_head, float* r_out, hipStream_t st) {
