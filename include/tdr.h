@@ -503,7 +503,7 @@ int tdr_config_compact(int on);
  * agrees with it to rounding (<= 1e-6 relative).
  * mode 0 = never, 1 = when the filter holds enough particles per heading bin for the padding to pay (default: 64 x the
  * polar image's rows), 2 = whenever the shapes allow (ring groups and ring count multiples of 4, a map with narrow
- * compact records and class planes); < 0 only returns the mode.  Env TDR_SHIFT_UNIFORM sets the initial mode.
+ * compact records and class planes); < 0 only returns the mode.
  * The span: a launch with a tdr_score_ctx TUNES it while the filter runs — from the 31st call of a shape on, 2, 8, 16, 24
  * and 40 cells are timed over two scoring calls each (HIP events on the caller's stream, polled, never waited for), the fastest is kept and the trial is
  * repeated every 4000 calls.  Results never depend on it.  tdr_config_shift_uniform_span(cells >= 0) fixes
@@ -522,17 +522,17 @@ int tdr_config_ray_split(int k);
  * The Cartesian scoring has a second kernel that reads the scan side of a sample as a scalar descriptor and gives an empty
  * scan bin one 4-byte gather from the map's known mask instead of the record gather, decode and FMAs
  * (csrc/tdr_score_cart.hip); same partial sums, bit for bit.  It is used whenever the map has narrow compact records;
- * 0 forces the general kernel (A/B measurements, tests), 1 restores the default, < 0 only queries.  Env TDR_CART_SKIP. */
+ * 0 forces the general kernel (A/B measurements, tests), 1 restores the default, < 0 only queries. */
 int tdr_config_cart_skip(int on);
 /* The 40-rotation search of a particle without a heading (src/state_particle.cpp:195-206) runs on the matrix cores
  * (v_mfma_f32_16x16x32_f16; every record size: 4 / 8 floats through pre-split half records or split on the fly, 12 / 16
  * floats in two groups of 8 slots); 0 forces the vector-unit search (A/B measurements, tests), 1 restores the default,
- * < 0 only queries.  Only the choice among rotations whose costs tie to rounding can differ.  Env TDR_INIT_MFMA. */
+ * < 0 only queries.  Only the choice among rotations whose costs tie to rounding can differ. */
 int tdr_config_init_mfma(int on);
 /* The weight statistics of at most 32 768 particles (src/particle_filter.cpp:107-147) evaluate their two serial float
  * chains wave by wave: predicted wave-chunks in parallel, the rest carried through by one wave without workgroup barriers
  * (csrc/tdr_prefix.hip); 0 forces the chunk-by-chunk evaluation on the whole workgroup (A/B measurements, tests), 1
- * restores the default, < 0 only queries.  Same bits either way.  Env TDR_UW_WAVES. */
+ * restores the default, < 0 only queries.  Same bits either way. */
 int tdr_config_uw_waves(int on);
 /* diagnostics: scoring launches of this process that took the shift-uniform kernel */
 int64_t tdr_shift_uniform_launches(void);

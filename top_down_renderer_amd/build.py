@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 SRC = [os.path.join(PKG, "csrc", f) for f in
-       ("tdr_core.hip", "tdr_map.hip", "tdr_raster.hip", "tdr_score.hip", "tdr_score_su.hip", "tdr_score_ray.hip", "tdr_score_cart.hip", "tdr_filter.hip", "tdr_rng.hip", "tdr_prefix.hip",
+       ("tdr_core.hip", "tdr_map.hip", "tdr_raster.hip", "tdr_score.hip", "tdr_score_init.hip", "tdr_score_su.hip", "tdr_score_ray.hip", "tdr_score_cart.hip", "tdr_filter.hip", "tdr_rng.hip", "tdr_prefix.hip",
         "tdr_geo.hip", "tdr_cmap.hip", "tdr_active.hip", "tdr_poly.hip", "tdr_batch.hip", "tdr_batch_loop.hip", "tdr_init.hip", "tdr_map_incr.hip", "tdr_host.cpp", "tdr_comm.cpp", "tdr_gmm.cpp", "tdr_png.cpp",
         "tdr_svg.cpp")]
 # every header: a changed one rebuilds every translation unit (no per-file dependency tracking)
@@ -24,10 +24,10 @@ STAMP = os.path.join(PKG, "libtdr_hip.toolchain.txt")
 # -ffp-contract=off: index arithmetic must round like the reference's non-FMA x86-64 build (see csrc/tdr_common.h)
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I", os.path.join(ROOT, "include")]
 LDFLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-ldl", "-lz"]   # zlib: the PNG files of the raster cache
-# per-file flags.  tdr_score.hip: matrix-core accumulators in VGPRs — with AGPR accumulators the register allocator rotates
+# per-file flags.  tdr_score_init.hip: matrix-core accumulators in VGPRs — with AGPR accumulators the register allocator rotates
 # the six accumulator tiles of the init-search loop through ~36 v_accvgpr moves per step (there is no register pressure:
 # 112 VGPRs at 4 waves per SIMD)
-FILE_FLAGS = {"tdr_score.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+FILE_FLAGS = {"tdr_score_init.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
               # wave-uniform branch trees stay plain scalar branches (see the file's header comment)
               "tdr_score_su.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions"],
               "tdr_score_cart.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions"]}

@@ -9,7 +9,7 @@
 //   K2 score_polar_kernel          top_down_map_polar.cpp:28-52 + state_particle.cpp:132-143 (lane = particle)       tdr_score.hip
 //      score_cart_kernel           top_down_map.cpp:429-459 + state_particle.cpp:112-155
 //      score_finalize_kernel       state_particle.cpp:117-120,136-139,154,161-176,212
-//      score_init(_mfma)_kernel    state_particle.cpp:195-206
+//      score_init(_mfma)_kernel    state_particle.cpp:195-206                                                        tdr_score_init.hip
 //   K3 propagate_kernel            state_particle.cpp:57-78                                                          tdr_filter.hip
 //   K4 update_weights / uw_pass*   particle_filter.cpp:107-147
 //   K5 prefix kernels              particle_filter.cpp:175-183 (the serial float32 running sum, bit-exact)            tdr_prefix.hip
@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -64,6 +65,29 @@ int tdr_fail(int code, const char* fmt, ...);
 int tdr_libm_fma();
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Run-time flags -> template arguments, the one way every launch does it:
+//     with_flags([&](auto KS, auto US) { launch(kernel<decltype(KS)::value, decltype(US)::value>); return TDR_OK; }, ks, us);
+// calls f(std::bool_constant<ks>{}, std::bool_constant<us>{}).  Every combination of the flags is instantiated: a
+// combination that has no kernel is excluded with `if constexpr` inside f.
+template <class F>
+static inline int with_flags(F&& f) { return f(); }
+template <class F, class... Rest>
+static inline int with_flags(F&& f, bool b, Rest... rest) {
+  auto next = [&](auto B) { return with_flags([&](auto... bs) { return f(B, bs...); }, rest...); };
+  return b ? next(std::true_type{}) : next(std::false_type{});
+}
+// ... and the record size rf (4, 8, 12 or 16 floats) -> f(std::integral_constant<int, rf / 4>{})
+template <class F>
+static inline int with_nv4(int rf, const char* who, F&& f) {
+  switch (rf / 4) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});   // 8-11 classes
+    case 4: return f(std::integral_constant<int, 4>{});   // 12-15 classes (TDR_MAX_CLASSES)
+    default: return fail(TDR_ERR_ARG, "%s: unsupported record size %d", who, rf);
+  }
+}
 
 // tdr_prefix.hip: final value of a serial float32 chain over the raw weights (kind 0: sum of the non-NaN weights;
 // kind 1: float-accumulated squared deviations of the weights below *mean_dev), see there

@@ -1,4 +1,5 @@
-// tdr_score_dev.h — device helpers shared by the scoring kernels (tdr_score.hip, tdr_score_su.hip).
+// tdr_score_dev.h — device helpers shared by the scoring kernels (tdr_score.hip, tdr_score_init.hip, tdr_score_su.hip,
+// tdr_score_ray.hip, tdr_score_cart.hip) and by the files that build what they read (tdr_cmap.hip, tdr_map_incr.hip).
 #ifndef TDR_SCORE_DEV_H_
 #define TDR_SCORE_DEV_H_
 #include "tdr_common.h"
@@ -96,6 +97,34 @@ __device__ __forceinline__ unsigned plane_offset(int ri, int ci, int pkcol, int 
 // 256 — below 2^24 the total stays below 2^32, the normalisation sums fit 32 bits and the class sums 64.
 __device__ __forceinline__ bool int_form_off(const int32_t* flags) {
   return flags[0] != 0 || (uint32_t)flags[1] >= (1u << 24);
+}
+
+// ---- the gates of a particle: finalize kernels and the init search (tdr_score.hip, tdr_score_init.hip) ----------------------
+// Gates of state_particle.cpp:163-176.  scale_lo / scale_hi = pow(10, scale_log_min/max) evaluated on the host
+// (glibc pow, like the reference).
+struct GateArgs {
+  int force_on_map, scale_unknown;
+  float width, height;  // map size * resolution (state_particle.cpp:11,46-47)
+  double scale_lo, scale_hi;
+};
+static inline GateArgs make_gate(const tdr_filter_params* fp, const tdr_map_desc* map) {
+  GateArgs g;
+  g.force_on_map = fp->force_on_map;
+  g.scale_unknown = fp->fixed_scale < 0;
+  g.width = (float)map->cols * map->resolution;
+  g.height = (float)map->rows * map->resolution;
+  g.scale_lo = std::pow(10, fp->scale_log_min);
+  g.scale_hi = std::pow(10, fp->scale_log_max);
+  return g;
+}
+__device__ __forceinline__ bool particle_gated(const GateArgs& g, float cx, float cy, float scale) {
+  if (g.force_on_map) {
+    if (cx < 0 || cy < 0 || cx > g.width || cy > g.height) return true;  // :163-168
+  }
+  if (g.scale_unknown) {
+    if ((double)scale < g.scale_lo || (double)scale > g.scale_hi) return true;  // :169-176
+  }
+  return false;
 }
 
 // one compact record -> the RF operands the dense record would have delivered, bit for bit (ldict: the dictionary in LDS)

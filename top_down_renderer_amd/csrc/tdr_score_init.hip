@@ -1,0 +1,991 @@
+// tdr_score_init.hip — the 40-rotation init search of state_particle.cpp:195-206: the vector kernel, the three matrix-core
+// kernels (on the fly, wide records, pre-split half records) and the host function that picks among them
+// (tdr_score_init.h).  Built with -amdgpu-mfma-vgpr-form (build.py): the only file that issues MFMAs.
+#include "tdr_common.h"
+#include "tdr_score_dev.h"   // rot_shift_dev, the coordinate rounding, the gates
+#include "tdr_score_init.h"
+
+// The 40-rotation initialisation search of state_particle.cpp:195-206 in ONE pass over the window: the candidate
+// rotations are the same for every particle, so for rotation t the scan row paired with window row i — (i + s_t) mod nb
+// — is the same for all lanes, and a map record gathered once is multiplied against all candidates' scan records
+// (the reference also gathers once and scores 40 times).  One workgroup = one batch of 64 particles; its 4 waves
+// split the candidates (INIT_TW each), gather the same records (the repeats hit L1), read the candidates' scan records
+// through the scalar cache (they are wave-uniform) and keep INIT_TW x rf accumulators per lane.  Sums run in float over the whole window, which is only used to pick the best rotation:
+// the weight itself is then produced by the regular scoring pass at that rotation.
+#ifndef INIT_TW
+#define INIT_TW 6          // candidate rotations per wave
+#endif
+#ifndef INIT_WAVES
+#define INIT_WAVES 8       // waves per workgroup, all on the same 64 particles (A/B on MI355X, 250k particles:
+#endif                     // 4x11 401 ms, 6x8 630 ms, 8x6 285 ms, 12x4 422 ms, 16x3 447 ms; scalar-cache scan reads 773 ms)
+#define INIT_MAXROT (INIT_WAVES * INIT_TW)
+struct InitArgs {
+  const float* rec;
+  int rows, cols;
+  float resolution;
+  const float* tab;
+  const float* utab;
+  const float* scan_pk;
+  int nb, nr;
+  float res;
+  const float* st;     // read-only here: results go to res_theta / res_flag (keeps every other load scalarisable)
+  int64_t cap, n;
+  const int32_t* order;
+  tdr_filter_params fp;
+  GateArgs gate;
+  int64_t P;
+  int ncls;
+  const int* nrot;
+  const int* shift;    // [nrot] device arrays (filled by init_rot_kernel)
+  const float* theta;
+  const int* only_if;  // optional: the kernel runs only when this device word is non-zero (fallback after the MFMA pass)
+  float* res_theta;  // [n] chosen rotation
+  float* res_flag;   // [n] 0 = untouched, 1 = initialised, 2 = initialised but every rotation scored NaN
+                     //     (weight 1/(FLT_MAX + reg), state_particle.cpp:193,212)
+};
+
+template <int NV4, bool KSLOT, bool USCALE>
+__global__ __launch_bounds__(64 * INIT_WAVES) void score_init_kernel(InitArgs a) {
+  constexpr int RF = 4 * NV4;
+  constexpr int U = 1;
+#if TDR_INIT_SCAN_LDS
+  extern __shared__ float4 ring[];  // [NV4 planes][2*nb rows]
+  const int nb2 = 2 * a.nb;
+#endif
+  __shared__ float x_cost[INIT_WAVES][64];
+  __shared__ int x_rot[INIT_WAVES][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform, and the compiler knows it
+  if (a.only_if && *a.only_if == 0) return;               // (uniform) the MFMA pass already produced the results
+  const int64_t slot = (int64_t)blockIdx.x * 64 + lane;   // all four waves work on the same 64 particles
+  const bool valid = slot < a.n;
+  const int64_t p = a.order ? (int64_t)a.order[valid ? slot : 0] : (valid ? slot : 0);
+  const float scale = a.st[TDR_ST_SCALE * a.cap + p];
+  const float cx = a.st[TDR_ST_DX * a.cap + p] * scale + a.st[TDR_ST_INIT_X * a.cap + p];
+  const float cy = a.st[TDR_ST_DY * a.cap + p] * scale + a.st[TDR_ST_INIT_Y * a.cap + p];
+  const bool want = valid && a.st[TDR_ST_HAVE_INIT * a.cap + p] == 0.f && !particle_gated(a.gate, cx, cy, scale);
+  // every wave of the workgroup looks at the same 64 particles, so this per-wave vote is the same in all of them
+  // (and, unlike __syncthreads_or, involves no LDS atomic that would stop the compiler from using scalar loads)
+  if (__ballot(want) == 0) return;  // nothing to initialise in this batch
+  const float off0 = cy / a.resolution, off1 = cx / a.resolution;
+  const int rowstride = (a.cols + 2) * (RF * 4);
+  const int kbase = (a.cols + 3) * (RF * 4);
+  const float rmaxf = (float)a.rows, cmaxf = (float)a.cols;
+  const char* __restrict__ recb = reinterpret_cast<const char*>(a.rec);
+  const float2* __restrict__ tab2 = reinterpret_cast<const float2*>(USCALE ? a.utab : a.tab);
+  const float4* __restrict__ scan4 = reinterpret_cast<const float4*>(a.scan_pk);
+  const int nrot = *a.nrot;
+  int sh[INIT_TW];
+#pragma unroll
+  for (int r = 0; r < INIT_TW; r++) {
+    const int t = wave * INIT_TW + r;
+    sh[r] = t < nrot ? a.shift[t] : 0;
+  }
+  float acc[INIT_TW][RF];
+#pragma unroll
+  for (int r = 0; r < INIT_TW; r++)
+#pragma unroll
+    for (int k = 0; k < RF; k++) acc[r][k] = 0.f;
+  float known = 0.f;
+
+  auto cell_offset = [&](float2 t) -> unsigned {
+    float p0, p1;
+    if constexpr (USCALE) { p0 = t.x; p1 = t.y; }
+    else { p0 = (t.x * scale) * a.res; p1 = (t.y * scale) * a.res; }
+    p0 = p0 + off0;
+    p1 = p1 + off1;
+    p0 = __builtin_amdgcn_fmed3f(p0, -1.f, rmaxf);
+    p1 = __builtin_amdgcn_fmed3f(p1, -1.f, cmaxf);
+    const int ri = round_half_away_clamped(p0), ci = round_half_away_clamped(p1);
+    const bool inb = (unsigned)ri < (unsigned)a.rows && (unsigned)ci < (unsigned)a.cols;
+    return inb ? (unsigned)(__mul24(ri, rowstride) + (ci * (RF * 4) + kbase)) : 0u;
+  };
+
+  for (int j = 0; j < a.nr; j++) {
+    const float2* trow = tab2 + (int64_t)j * a.nb;
+    const float4* srow = scan4 + (int64_t)j * a.nb * NV4;  // ring j of the packed scan
+#if TDR_INIT_SCAN_LDS
+    __syncthreads();
+    for (int t = threadIdx.x; t < a.nb * NV4; t += 64 * INIT_WAVES) {
+      const float4 v = srow[t];
+      const int row = t / NV4, pl = t - row * NV4;
+      ring[pl * nb2 + row] = v;
+      ring[pl * nb2 + row + a.nb] = v;
+    }
+    __syncthreads();
+#endif
+    int i = 0;
+    for (; i + U <= a.nb; i += U) {
+      unsigned boff[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) boff[u] = cell_offset(trow[i + u]);
+      float4 m[U][NV4];
+#pragma unroll
+      for (int u = 0; u < U; u++)
+#pragma unroll
+        for (int v = 0; v < NV4; v++) m[u][v] = *reinterpret_cast<const float4*>(recb + boff[u] + 16 * v);
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        if (!KSLOT) known += m[u][NV4 - 1].w;
+#pragma unroll
+        for (int r = 0; r < INIT_TW; r++) {
+#pragma unroll
+          for (int v = 0; v < NV4; v++) {
+#if TDR_INIT_SCAN_LDS
+            const float4 sv = ring[v * nb2 + sh[r] + i + u];  // same address in every lane: LDS broadcast
+#else
+            int row = sh[r] + i + u;                    // wave-uniform: the record comes through the scalar cache
+            row -= row >= a.nb ? a.nb : 0;
+            const float4 sv = srow[row * NV4 + v];
+#endif
+            acc[r][4 * v + 0] = __builtin_fmaf(sv.x, m[u][v].x, acc[r][4 * v + 0]);
+            acc[r][4 * v + 1] = __builtin_fmaf(sv.y, m[u][v].y, acc[r][4 * v + 1]);
+            acc[r][4 * v + 2] = __builtin_fmaf(sv.z, m[u][v].z, acc[r][4 * v + 2]);
+            acc[r][4 * v + 3] = __builtin_fmaf(sv.w, m[u][v].w, acc[r][4 * v + 3]);
+          }
+        }
+      }
+    }
+    for (; i < a.nb; i++) {
+      const unsigned bo = cell_offset(trow[i]);
+      float4 m[NV4];
+#pragma unroll
+      for (int v = 0; v < NV4; v++) m[v] = *reinterpret_cast<const float4*>(recb + bo + 16 * v);
+      if (!KSLOT) known += m[NV4 - 1].w;
+#pragma unroll
+      for (int r = 0; r < INIT_TW; r++)
+#pragma unroll
+        for (int v = 0; v < NV4; v++) {
+#if TDR_INIT_SCAN_LDS
+          const float4 sv = ring[v * nb2 + sh[r] + i];
+#else
+          int row = sh[r] + i;
+          row -= row >= a.nb ? a.nb : 0;
+          const float4 sv = srow[row * NV4 + v];
+#endif
+          acc[r][4 * v + 0] = __builtin_fmaf(sv.x, m[v].x, acc[r][4 * v + 0]);
+          acc[r][4 * v + 1] = __builtin_fmaf(sv.y, m[v].y, acc[r][4 * v + 1]);
+          acc[r][4 * v + 2] = __builtin_fmaf(sv.z, m[v].z, acc[r][4 * v + 2]);
+          acc[r][4 * v + 3] = __builtin_fmaf(sv.w, m[v].w, acc[r][4 * v + 3]);
+        }
+    }
+  }
+  // cost of each candidate (state_particle.cpp:117-120,136-139,154), best of this wave's candidates in order
+  const float kn = KSLOT ? acc[0][RF - 2] : known;
+  const bool unknown = (kn / (float)a.P) < 0.5;
+  float cw[RF];
+#pragma unroll
+  for (int k = 0; k < RF; k++) cw[k] = k < 16 ? a.fp.class_weights[k < 16 ? k : 0] : 0.f;
+  float best = 3.402823466e+38f;
+  int best_t = -1;
+#pragma unroll
+  for (int r = 0; r < INIT_TW; r++) {
+    const int t = wave * INIT_TW + r;
+    float cost = 0.f;
+#pragma unroll
+    for (int k = 0; k < RF - 1; k++)   // constant indices only: a dynamic index would push the arguments to scratch
+      if (k < a.ncls) cost = (float)((double)cost + (double)acc[r][k] * 0.01 * (double)cw[k]);
+    cost = cost / acc[r][RF - 1];
+    if (unknown) cost = __builtin_nanf("");
+    if (t < nrot && cost < best) { best = cost; best_t = t; }  // :200-203 (NaN never wins)
+  }
+  x_cost[wave][lane] = best;
+  x_rot[wave][lane] = best_t;
+  __syncthreads();
+  if (wave == 0 && want) {
+    float b = 3.402823466e+38f;
+    int bt = -1;
+    for (int wv = 0; wv < INIT_WAVES; wv++)   // waves hold the candidates in loop order: strict '<' keeps the first minimum
+      if (x_cost[wv][lane] < b) { b = x_cost[wv][lane]; bt = x_rot[wv][lane]; }
+    a.res_theta[p] = bt >= 0 ? a.theta[bt] : 0.f;  // :205 (best_theta stays 0 if nothing won)
+    a.res_flag[p] = bt < 0 ? 2.f : 1.f;
+  }
+}
+
+// The same search on the matrix cores (records of 8 floats, i.e. 4-6 classes).  For one particle the 40 candidate
+// costs are  cost[m] = sum_{i,j,c} scan_c[(i + s_m) mod nb, j] * (w_c d_c[cell(i,j)]):  a contraction over
+// k = (sample, class) of a matrix A[m][k] that is the same for every particle (shifted scan records, from LDS) with
+// the particle's gathered window B[k][n].  v_mfma_f32_16x16x32_f16: 16 rotations x 16 particles x (4 samples x 8
+// record slots) per instruction.  Lane l holds, as its B fragment, the 8 slots of the record of particle l&15 at
+// sample 4t + (l>>4) — exactly the record it gathered — and as its A fragment the packed scan record at row
+// (4t + (l>>4) + s_m), m = l&15 (+16, +32 for the second and third tile of candidates), one ds_read_b128 each.
+//   * scan counts are integers: exact in f16 up to 2048 (a larger count raises *inexact and score_init_kernel redoes
+//     the search on the vector units);
+//   * distances (times 0.01 w_c, in f32) are split hi + lo into two f16 (relative error <= 2^-20), two MFMAs;
+//   * the normalisation  sum scanΣ * known  is a third MFMA with only slot 7 of B set; the known count is a plain add.
+// Products are exact and accumulate in f32 like the vector version.  Only the choice of the rotation comes out of
+// here; the weight itself is computed by the regular scoring pass at that rotation.
+typedef _Float16 tdr_h8 __attribute__((ext_vector_type(8)));
+typedef __fp16 tdr_h2 __attribute__((ext_vector_type(2)));   // what v_cvt_pkrtz_f16_f32 returns
+typedef float tdr_f4 __attribute__((ext_vector_type(4)));
+#define INITM_TILES 3   // 48 candidate rows >= the 40 (41) rotations of the search
+static_assert(INITM_TILES * 16 >= INIT_MAXROT || INIT_MAXROT == 48, "rotation tiles");
+
+// UNITW: all class weights are equal — a common factor does not move the minimum, so the distances go in unweighted.
+// SEVEN: 7 classes — slot 6 of the record is a seventh distance (no spare slot), slot 7 still `known` / the scan's sum.
+template <bool USCALE, bool UNITW, bool SEVEN>
+__global__ __launch_bounds__(256) void score_init_mfma_kernel(InitArgs a, int* __restrict__ inexact) {
+  constexpr int RF = 8;
+  extern __shared__ uint4 ring16[];   // [2*nb] packed scan records as 8 x f16 (row r and r+nb hold scan row r) + 1 zero row
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 15, q = lane >> 4;
+  const int64_t slot = (int64_t)blockIdx.x * 64 + wave * 16 + col;
+  const bool valid = slot < a.n;
+  const int64_t p = a.order ? (int64_t)a.order[valid ? slot : 0] : (valid ? slot : 0);
+  const float scale = a.st[TDR_ST_SCALE * a.cap + p];
+  const float cx = a.st[TDR_ST_DX * a.cap + p] * scale + a.st[TDR_ST_INIT_X * a.cap + p];
+  const float cy = a.st[TDR_ST_DY * a.cap + p] * scale + a.st[TDR_ST_INIT_Y * a.cap + p];
+  const bool want = valid && a.st[TDR_ST_HAVE_INIT * a.cap + p] == 0.f && !particle_gated(a.gate, cx, cy, scale);
+  if (!__syncthreads_or(want)) return;   // nothing to initialise in this batch of 64 particles
+  const float off0 = cy / a.resolution, off1 = cx / a.resolution;
+  const int rowstride = (a.cols + 2) * (RF * 4);
+  const int kbase = (a.cols + 3) * (RF * 4);
+  const float rmaxf = (float)a.rows, cmaxf = (float)a.cols;
+  const char* __restrict__ recb = reinterpret_cast<const char*>(a.rec);
+  const float2* __restrict__ tab2 = reinterpret_cast<const float2*>(USCALE ? a.utab : a.tab);
+  const float4* __restrict__ scan4 = reinterpret_cast<const float4*>(a.scan_pk);
+  const int nrot = *a.nrot;
+  // byte offset of the lane's candidate row within the ring for every tile; candidates past nrot read the zero row
+  const int zero_row = 2 * a.nb;
+  int sh[INITM_TILES];
+#pragma unroll
+  for (int T = 0; T < INITM_TILES; T++) {
+    const int m = 16 * T + col;
+    sh[T] = m < nrot ? a.shift[m] : -1;
+  }
+  if (threadIdx.x == 0) ring16[zero_row] = make_uint4(0u, 0u, 0u, 0u);
+  float wc[7];
+#pragma unroll
+  for (int c = 0; c < 7; c++) wc[c] = c < a.ncls ? (float)(0.01 * (double)a.fp.class_weights[c]) : 0.f;
+  tdr_f4 accC[INITM_TILES], accN[INITM_TILES];
+#pragma unroll
+  for (int T = 0; T < INITM_TILES; T++) { accC[T] = (tdr_f4){0.f, 0.f, 0.f, 0.f}; accN[T] = (tdr_f4){0.f, 0.f, 0.f, 0.f}; }
+  float known = 0.f;
+  const int steps = (a.nb + 3) / 4;
+
+  for (int j = 0; j < a.nr; j++) {
+    const float2* trow = tab2 + (int64_t)j * a.nb;
+    const float4* srow = scan4 + (int64_t)j * a.nb * 2;
+    __syncthreads();
+    bool big = false;
+    for (int t = threadIdx.x; t < a.nb; t += 256) {
+      const float4 v0 = srow[2 * t], v1 = srow[2 * t + 1];
+      big |= v0.x > 2048.f || v0.y > 2048.f || v0.z > 2048.f || v0.w > 2048.f || v1.x > 2048.f || v1.y > 2048.f ||
+             v1.z > 2048.f || v1.w > 2048.f;
+      union { tdr_h2 h[4]; uint4 u; } pk;
+      pk.h[0] = __builtin_amdgcn_cvt_pkrtz(v0.x, v0.y);
+      pk.h[1] = __builtin_amdgcn_cvt_pkrtz(v0.z, v0.w);
+      pk.h[2] = __builtin_amdgcn_cvt_pkrtz(v1.x, v1.y);
+      pk.h[3] = __builtin_amdgcn_cvt_pkrtz(v1.z, v1.w);
+      ring16[t] = pk.u;
+      ring16[t + a.nb] = pk.u;
+    }
+    if (big) atomicOr(inexact, 1);
+    __syncthreads();
+    // software pipeline: the record of step t+1 (and the table entry of step t+2) are requested before the matrix
+    // work of step t, so every wave keeps two gathers in flight
+    auto tab_at = [&](int t) -> float2 { return trow[min(4 * t + q, a.nb - 1)]; };
+    auto rec_addr = [&](float2 tv) -> const char* {
+      float p0, p1;
+      if constexpr (USCALE) { p0 = tv.x; p1 = tv.y; }
+      else { p0 = (tv.x * scale) * a.res; p1 = (tv.y * scale) * a.res; }   // top_down_map_polar.cpp:28
+      p0 = __builtin_amdgcn_fmed3f(p0 + off0, -1.f, rmaxf);
+      p1 = __builtin_amdgcn_fmed3f(p1 + off1, -1.f, cmaxf);
+      const int ri = round_half_away_clamped(p0), ci = round_half_away_clamped(p1);   // :31
+      const bool inb = (unsigned)ri < (unsigned)a.rows && (unsigned)ci < (unsigned)a.cols;
+      return recb + (inb ? (unsigned)(__mul24(ri, rowstride) + (ci * (RF * 4) + kbase)) : 0u);
+    };
+    float2 tv_next = tab_at(1);
+    float4 n0, n1;
+    {
+      const char* r0 = rec_addr(tab_at(0));
+      n0 = *reinterpret_cast<const float4*>(r0);
+      n1 = *reinterpret_cast<const float4*>(r0 + 16);
+    }
+    for (int t = 0; t < steps; t++) {
+      const int i = 4 * t + q;
+      const bool in = i < a.nb;
+      const int ic = in ? i : a.nb - 1;
+      float4 m0 = n0, m1 = n1;
+      {
+        const char* r1 = rec_addr(tv_next);        // step t+1 (clamped to the ring: an in-range address)
+        tv_next = tab_at(t + 2);
+        n0 = *reinterpret_cast<const float4*>(r1);
+        n1 = *reinterpret_cast<const float4*>(r1 + 16);
+      }
+      if (!in) { m0 = make_float4(0.f, 0.f, 0.f, 0.f); m1 = m0; }
+      known += m1.w;
+      float v[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, SEVEN ? m1.z : 0.f, 0.f};
+      if constexpr (!UNITW) {
+#pragma unroll
+        for (int c = 0; c < 7; c++) v[c] *= wc[c];
+      }
+      union { tdr_h2 h[4]; tdr_h8 v8; } bh, bl, bn;
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        const tdr_h2 hi = __builtin_amdgcn_cvt_pkrtz(v[2 * c], v[2 * c + 1]);
+        bh.h[c] = hi;
+        bl.h[c] = __builtin_amdgcn_cvt_pkrtz(v[2 * c] - (float)hi[0], v[2 * c + 1] - (float)hi[1]);
+      }
+      const tdr_h2 zero2 = __builtin_amdgcn_cvt_pkrtz(0.f, 0.f);
+      if constexpr (SEVEN) {
+        const tdr_h2 hi = __builtin_amdgcn_cvt_pkrtz(v[6], 0.f);
+        bh.h[3] = hi;
+        bl.h[3] = __builtin_amdgcn_cvt_pkrtz(v[6] - (float)hi[0], 0.f);
+      } else {
+        bh.h[3] = zero2;
+        bl.h[3] = zero2;
+      }
+      bn.h[0] = zero2; bn.h[1] = zero2; bn.h[2] = zero2;
+      bn.h[3] = __builtin_amdgcn_cvt_pkrtz(0.f, m1.w);
+      union { uint4 u; tdr_h8 v8; } av[INITM_TILES];
+#pragma unroll
+      for (int T = 0; T < INITM_TILES; T++) av[T].u = ring16[sh[T] < 0 ? zero_row : ic + sh[T]];
+      // dependent MFMAs (same accumulator) are kept three instructions apart
+#pragma unroll
+      for (int T = 0; T < INITM_TILES; T++) accC[T] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[T].v8, bh.v8, accC[T], 0, 0, 0);
+#pragma unroll
+      for (int T = 0; T < INITM_TILES; T++) accN[T] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[T].v8, bn.v8, accN[T], 0, 0, 0);
+#pragma unroll
+      for (int T = 0; T < INITM_TILES; T++) accC[T] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[T].v8, bl.v8, accC[T], 0, 0, 0);
+    }
+  }
+  // this lane holds rows 4q..4q+3 of every tile for particle `col`; the four lanes of a particle share the samples
+  known += __shfl_xor(known, 16, 64);
+  known += __shfl_xor(known, 32, 64);
+  const bool unknown = (known / (float)a.P) < 0.5;   // state_particle.cpp:117-120
+  float best = 3.402823466e+38f;
+  int bm = -1;
+#pragma unroll
+  for (int T = 0; T < INITM_TILES; T++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int m = 16 * T + 4 * q + r;
+      float cost = accC[T][r] / accN[T][r];             // :154
+      if (unknown) cost = __builtin_nanf("");
+      if (m < nrot && cost < best) { best = cost; bm = m; }   // :200-203 (NaN never wins)
+    }
+#pragma unroll
+  for (int o = 16; o <= 32; o <<= 1) {   // first minimum in rotation order over the particle's four lanes
+    const float oc = __shfl_xor(best, o, 64);
+    const int om = __shfl_xor(bm, o, 64);
+    const bool take = om >= 0 && (bm < 0 || oc < best || (oc == best && om < bm));
+    if (take) { best = oc; bm = om; }
+  }
+  if (q == 0 && want) {
+    a.res_theta[p] = bm >= 0 ? a.theta[bm] : 0.f;  // :205 (best_theta stays 0 if nothing won)
+    a.res_flag[p] = bm < 0 ? 2.f : 1.f;
+  }
+}
+
+// The same for records of 12 and 16 floats (8-15 classes): a sample's record is two groups of 8 slots, each group its own
+// pair of fragments — B from the gathered record, A from a second LDS image of the scan row — so a step of 4 samples is
+// 2 x (hi + lo) products per tile instead of one, plus the normalisation product on the group that holds slot RF - 1.
+// Class weights are always folded in (no unit-weight form); slots past the class count meet a zero weight.
+template <int NV4, bool USCALE>
+__global__ __launch_bounds__(256) void score_init_mfma_wide_kernel(InitArgs a, int* __restrict__ inexact) {
+  constexpr int RF = 4 * NV4, NH = 2;
+  static_assert(NV4 == 3 || NV4 == 4, "records of 12 or 16 floats");
+  constexpr int HN = (RF - 1) / 8, KN = (RF - 1) % 8;   // group and slot of `known` / the scan's sum
+  extern __shared__ uint4 ring16[];   // [2*nb + 1 rows][NH groups]: 8 x f16 each; rows r and r+nb hold scan row r, the last is zero
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 15, q = lane >> 4;
+  const int64_t slot = (int64_t)blockIdx.x * 64 + wave * 16 + col;
+  const bool valid = slot < a.n;
+  const int64_t p = a.order ? (int64_t)a.order[valid ? slot : 0] : (valid ? slot : 0);
+  const float scale = a.st[TDR_ST_SCALE * a.cap + p];
+  const float cx = a.st[TDR_ST_DX * a.cap + p] * scale + a.st[TDR_ST_INIT_X * a.cap + p];
+  const float cy = a.st[TDR_ST_DY * a.cap + p] * scale + a.st[TDR_ST_INIT_Y * a.cap + p];
+  const bool want = valid && a.st[TDR_ST_HAVE_INIT * a.cap + p] == 0.f && !particle_gated(a.gate, cx, cy, scale);
+  if (!__syncthreads_or(want)) return;   // nothing to initialise in this batch of 64 particles
+  const float off0 = cy / a.resolution, off1 = cx / a.resolution;
+  const int rowstride = (a.cols + 2) * (RF * 4);
+  const int kbase = (a.cols + 3) * (RF * 4);
+  const float rmaxf = (float)a.rows, cmaxf = (float)a.cols;
+  const char* __restrict__ recb = reinterpret_cast<const char*>(a.rec);
+  const float2* __restrict__ tab2 = reinterpret_cast<const float2*>(USCALE ? a.utab : a.tab);
+  const float4* __restrict__ scan4 = reinterpret_cast<const float4*>(a.scan_pk);
+  const int nrot = *a.nrot;
+  const int zero_row = 2 * a.nb;
+  int sh[INITM_TILES];
+#pragma unroll
+  for (int T = 0; T < INITM_TILES; T++) {
+    const int m = 16 * T + col;
+    sh[T] = m < nrot ? a.shift[m] : -1;
+  }
+  if (threadIdx.x < NH) ring16[zero_row * NH + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+  float wc[16];
+#pragma unroll
+  for (int c = 0; c < 16; c++) wc[c] = (c < a.ncls && c < TDR_MAX_CLASSES) ? (float)(0.01 * (double)a.fp.class_weights[c < TDR_MAX_CLASSES ? c : 0]) : 0.f;
+  tdr_f4 accC[INITM_TILES], accN[INITM_TILES];
+#pragma unroll
+  for (int T = 0; T < INITM_TILES; T++) { accC[T] = (tdr_f4){0.f, 0.f, 0.f, 0.f}; accN[T] = (tdr_f4){0.f, 0.f, 0.f, 0.f}; }
+  float known = 0.f;
+  const int steps = (a.nb + 3) / 4;
+  const tdr_h2 zero2 = __builtin_amdgcn_cvt_pkrtz(0.f, 0.f);
+
+  for (int j = 0; j < a.nr; j++) {
+    const float2* trow = tab2 + (int64_t)j * a.nb;
+    const float4* srow = scan4 + (int64_t)j * a.nb * NV4;
+    __syncthreads();
+    bool big = false;
+    for (int t = threadIdx.x; t < a.nb; t += 256) {
+      float f[16];
+#pragma unroll
+      for (int v = 0; v < 4; v++) {
+        const float4 x = v < NV4 ? srow[NV4 * t + (v < NV4 ? v : 0)] : make_float4(0.f, 0.f, 0.f, 0.f);
+        f[4 * v] = x.x; f[4 * v + 1] = x.y; f[4 * v + 2] = x.z; f[4 * v + 3] = x.w;
+      }
+#pragma unroll
+      for (int k = 0; k < 16; k++) big |= f[k] > 2048.f;
+#pragma unroll
+      for (int h = 0; h < NH; h++) {
+        union { tdr_h2 h2[4]; uint4 u; } pk;
+#pragma unroll
+        for (int c = 0; c < 4; c++) pk.h2[c] = __builtin_amdgcn_cvt_pkrtz(f[8 * h + 2 * c], f[8 * h + 2 * c + 1]);
+        ring16[t * NH + h] = pk.u;
+        ring16[(t + a.nb) * NH + h] = pk.u;
+      }
+    }
+    if (big) atomicOr(inexact, 1);
+    __syncthreads();
+    auto tab_at = [&](int t) -> float2 { return trow[min(4 * t + q, a.nb - 1)]; };
+    auto rec_addr = [&](float2 tv) -> const char* {
+      float p0, p1;
+      if constexpr (USCALE) { p0 = tv.x; p1 = tv.y; }
+      else { p0 = (tv.x * scale) * a.res; p1 = (tv.y * scale) * a.res; }   // top_down_map_polar.cpp:28
+      p0 = __builtin_amdgcn_fmed3f(p0 + off0, -1.f, rmaxf);
+      p1 = __builtin_amdgcn_fmed3f(p1 + off1, -1.f, cmaxf);
+      const int ri = round_half_away_clamped(p0), ci = round_half_away_clamped(p1);   // :31
+      const bool inb = (unsigned)ri < (unsigned)a.rows && (unsigned)ci < (unsigned)a.cols;
+      return recb + (inb ? (unsigned)(__mul24(ri, rowstride) + (ci * (RF * 4) + kbase)) : 0u);
+    };
+    float2 tv_next = tab_at(1);
+    float4 nx[NV4];
+    {
+      const char* r0 = rec_addr(tab_at(0));
+#pragma unroll
+      for (int v = 0; v < NV4; v++) nx[v] = *reinterpret_cast<const float4*>(r0 + 16 * v);
+    }
+    for (int t = 0; t < steps; t++) {
+      const int i = 4 * t + q;
+      const bool in = i < a.nb;
+      const int ic = in ? i : a.nb - 1;
+      float v[16];
+#pragma unroll
+      for (int k = 0; k < 16; k++) v[k] = 0.f;
+#pragma unroll
+      for (int g = 0; g < NV4; g++) { v[4 * g] = nx[g].x; v[4 * g + 1] = nx[g].y; v[4 * g + 2] = nx[g].z; v[4 * g + 3] = nx[g].w; }
+      {
+        const char* r1 = rec_addr(tv_next);        // step t+1 (clamped to the ring: an in-range address)
+        tv_next = tab_at(t + 2);
+#pragma unroll
+        for (int g = 0; g < NV4; g++) nx[g] = *reinterpret_cast<const float4*>(r1 + 16 * g);
+      }
+      if (!in) {
+#pragma unroll
+        for (int k = 0; k < 16; k++) v[k] = 0.f;
+      }
+      const float kn = v[RF - 1];
+      known += kn;
+#pragma unroll
+      for (int k = 0; k < 16; k++) v[k] *= wc[k];   // (slots past the classes: weight 0)
+      union { tdr_h2 h[4]; tdr_h8 v8; } bh[NH], bl[NH], bn;
+#pragma unroll
+      for (int h = 0; h < NH; h++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+          const tdr_h2 hi = __builtin_amdgcn_cvt_pkrtz(v[8 * h + 2 * c], v[8 * h + 2 * c + 1]);
+          bh[h].h[c] = hi;
+          bl[h].h[c] = __builtin_amdgcn_cvt_pkrtz(v[8 * h + 2 * c] - (float)hi[0], v[8 * h + 2 * c + 1] - (float)hi[1]);
+        }
+#pragma unroll
+      for (int c = 0; c < 4; c++) bn.h[c] = zero2;
+      bn.h[KN / 2] = (KN & 1) ? __builtin_amdgcn_cvt_pkrtz(0.f, kn) : __builtin_amdgcn_cvt_pkrtz(kn, 0.f);
+      union { uint4 u; tdr_h8 v8; } av[INITM_TILES][NH];
+#pragma unroll
+      for (int T = 0; T < INITM_TILES; T++)
+#pragma unroll
+        for (int h = 0; h < NH; h++) av[T][h].u = ring16[(sh[T] < 0 ? zero_row : ic + sh[T]) * NH + h];
+      // dependent MFMAs (same accumulator) are kept three instructions apart
+#pragma unroll
+      for (int h = 0; h < NH; h++) {
+#pragma unroll
+        for (int T = 0; T < INITM_TILES; T++) accC[T] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[T][h].v8, bh[h].v8, accC[T], 0, 0, 0);
+        if (h == HN) {
+#pragma unroll
+          for (int T = 0; T < INITM_TILES; T++) accN[T] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[T][h].v8, bn.v8, accN[T], 0, 0, 0);
+        }
+#pragma unroll
+        for (int T = 0; T < INITM_TILES; T++) accC[T] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[T][h].v8, bl[h].v8, accC[T], 0, 0, 0);
+      }
+    }
+  }
+  known += __shfl_xor(known, 16, 64);
+  known += __shfl_xor(known, 32, 64);
+  const bool unknown = (known / (float)a.P) < 0.5;   // state_particle.cpp:117-120
+  float best = 3.402823466e+38f;
+  int bm = -1;
+#pragma unroll
+  for (int T = 0; T < INITM_TILES; T++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int m = 16 * T + 4 * q + r;
+      float cost = accC[T][r] / accN[T][r];             // :154
+      if (unknown) cost = __builtin_nanf("");
+      if (m < nrot && cost < best) { best = cost; bm = m; }   // :200-203 (NaN never wins)
+    }
+#pragma unroll
+  for (int o = 16; o <= 32; o <<= 1) {   // first minimum in rotation order over the particle's four lanes
+    const float oc = __shfl_xor(best, o, 64);
+    const int om = __shfl_xor(bm, o, 64);
+    const bool take = om >= 0 && (bm < 0 || oc < best || (oc == best && om < bm));
+    if (take) { best = oc; bm = om; }
+  }
+  if (q == 0 && want) {
+    a.res_theta[p] = bm >= 0 ? a.theta[bm] : 0.f;  // :205 (best_theta stays 0 if nothing won)
+    a.res_flag[p] = bm < 0 ? 2.f : 1.f;
+  }
+}
+
+// ---- the matrix-core search on pre-split half records ------------------------------------------------------------------
+// score_init_mfma_kernel spends most of its vector instructions turning a gathered f32 record into the f16 hi / lo
+// operands (weights, two conversions and a subtraction per pair, the zeroing of ragged lanes), per sample per particle.
+// That work depends on the cell alone.  half_records_kernel does it ONCE per cell into a 32-byte record
+//     H = {hi_0 .. hi_5, hi_6 | 0, 0}   L = {lo_0 .. lo_5, lo_6 | 0, unknown}      (f16; hi + lo = w_c * 0.01 * d_c)
+// laid out like the dense records (guarded row-major grid, guard cells = distance 0, unknown; one all-zero record behind
+// the grid for lanes without a sample), so that a lane's two 16-byte loads ARE the B fragments: H as it is, L with its
+// last half cleared.  The scan side is ONE LDS image per ring, {c_0 .. c_5, c_6 | 0, sum c}: its slot 7 meets a zero in H
+// and in the cleared L.  The normalisation  sum_samples (sum c) * known  is taken as  S - sum_samples (sum c) * unknown
+// with S the sum of the whole scan (the same for every candidate): the third product, {0 .. 0, unknown}, is issued only
+// in steps where some lane of the wave met an unknown cell — none, for a window inside the mapped area.
+// Same f16 operands as score_init_mfma_kernel, summed in another order (four rings of one direction per instruction).
+// The records carry the class weights, so they are rebuilt at every search (one pass over the map, ~0.35 ms for 4000^2
+// cells) into scratch memory the map's owner provides (tdr_map_desc.rec16).
+// RF: floats of the dense record read (4: up to 3 classes, 8: 4 to 7) — the half record is the same 32 bytes for both
+template <int RF>
+__global__ __launch_bounds__(256) void half_records_kernel(const float4* __restrict__ rec, int64_t ncells, int unitw,
+                                                           tdr_filter_params fp, int ncls, uint4* __restrict__ out) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= ncells) return;
+  float m[RF];
+#pragma unroll
+  for (int q = 0; q < RF / 4; q++) {
+    const float4 t = rec[(RF / 4) * c + q];
+    m[4 * q] = t.x; m[4 * q + 1] = t.y; m[4 * q + 2] = t.z; m[4 * q + 3] = t.w;
+  }
+  const float known = m[RF - 1];
+  float v[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) v[k] = (k < RF - 1 && k < 7 && k < ncls) ? m[k < RF ? k : 0] : 0.f;   // the distances
+  if (!unitw) {
+#pragma unroll
+    for (int k = 0; k < 7; k++) v[k] *= k < ncls ? (float)(0.01 * (double)fp.class_weights[k]) : 0.f;
+  }
+  union { tdr_h2 h[4]; uint4 u; } H, L;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const tdr_h2 hi = __builtin_amdgcn_cvt_pkrtz(v[2 * k], v[2 * k + 1]);   // v[7] == 0
+    H.h[k] = hi;
+    L.h[k] = __builtin_amdgcn_cvt_pkrtz(v[2 * k] - (float)hi[0], k == 3 ? 1.f - known : v[2 * k + 1] - (float)hi[1]);
+  }
+  out[2 * c] = H.u;
+  out[2 * c + 1] = L.u;
+  if (c == 0) {   // the record behind the grid: nothing at all (what lanes without a sample read)
+    out[2 * ncells] = make_uint4(0u, 0u, 0u, 0u);
+    out[2 * ncells + 1] = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+
+// Work of one MFMA (k = 4 samples x 8 slots): the SAME direction i on 4 consecutive range rings — four neighbouring cells
+// along a ray for each of the wave's 16 (neighbouring) particles, so that one gather instruction touches few cache
+// lines (the L1 looks up one line per clock: with four samples a quarter ring apart the counters showed 42 line
+// accesses per instruction and the L1, not the matrix or the vector units, setting the pace).  Rings are staged four at
+// a time (one LDS image per ring).
+// AHEAD: record loads in flight — those of step t + AHEAD are issued before the matrix work of step t.  The step loop is
+// unrolled AHEAD + 1 times so that the buffers rotate by name (no register copies); the step count is padded to a multiple
+// of that, the padding steps read the zero guard record.
+template <bool USCALE, int AHEAD>
+__global__ __launch_bounds__(256) void score_init_half_kernel(InitArgs a, const uint4* __restrict__ rec16,
+                                                              int* __restrict__ inexact, int img, int rfs) {
+  constexpr int R = AHEAD + 1;
+  // LDS: [4 rings][img] scan records {c0..c5, c6|0, sum c} as 8 x f16, row r and r + nb of an image hold scan row r; the
+  // img - 2 nb >= R rows behind them stay zero (padding steps; the exact count is chosen on the host so that the four
+  // images sit on the banks with the fewest conflicts, init_half_image_rows) — followed by the rings' sample-table rows,
+  // [4][nb + 2 R] float2
+  extern __shared__ uint4 ringh[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 15, q = lane >> 4;
+  // (an XCD-contiguous order of the workgroups and 1, 2 or 3 record loads in flight all run within 1 %: A/B on MI355X)
+  const int64_t slot = (int64_t)blockIdx.x * 64 + wave * 16 + col;
+  const bool valid = slot < a.n;
+  const int64_t p = a.order ? (int64_t)a.order[valid ? slot : 0] : (valid ? slot : 0);
+  const float scale = a.st[TDR_ST_SCALE * a.cap + p];
+  const float cx = a.st[TDR_ST_DX * a.cap + p] * scale + a.st[TDR_ST_INIT_X * a.cap + p];
+  const float cy = a.st[TDR_ST_DY * a.cap + p] * scale + a.st[TDR_ST_INIT_Y * a.cap + p];
+  const bool want = valid && a.st[TDR_ST_HAVE_INIT * a.cap + p] == 0.f && !particle_gated(a.gate, cx, cy, scale);
+  if (!__syncthreads_or(want)) return;   // nothing to initialise in this batch of 64 particles
+  typedef float tdr_v2f __attribute__((ext_vector_type(2)));
+  const tdr_v2f offv = {cy / a.resolution, cx / a.resolution};
+  const int rowstride = (a.cols + 2) * 32;
+  const int kbase = (a.cols + 3) * 32;
+  const float rmaxf = (float)a.rows, cmaxf = (float)a.cols;
+  const char* __restrict__ recb = reinterpret_cast<const char*>(rec16);
+  const float2* __restrict__ tab2 = reinterpret_cast<const float2*>(USCALE ? a.utab : a.tab);
+  const int nrot = *a.nrot;
+  const int nb = a.nb;
+  const int ntab = nb + 2 * R;    // entries per table row in LDS
+  float2* const ltab = reinterpret_cast<float2*>(ringh + 4 * img);
+  // LDS byte address of this lane's candidate row at direction 0, per tile (the lane's ring image); candidates past nrot
+  // read row 0 (their results are ignored)
+  int arow[INITM_TILES];
+#pragma unroll
+  for (int T = 0; T < INITM_TILES; T++) {
+    const int m = 16 * T + col;
+    arow[T] = (q * img + (m < nrot ? a.shift[m] : 0)) * 16;
+  }
+  const int npad = img - 2 * nb;
+  for (int t = threadIdx.x; t < 4 * npad; t += 256) ringh[(t / npad) * img + 2 * nb + t % npad] = make_uint4(0u, 0u, 0u, 0u);
+  tdr_f4 accC[INITM_TILES], accN[INITM_TILES];   // accN: the normalisation's deficit, sum (sum c) * unknown
+#pragma unroll
+  for (int T = 0; T < INITM_TILES; T++) { accC[T] = (tdr_f4){0.f, 0.f, 0.f, 0.f}; accN[T] = (tdr_f4){0.f, 0.f, 0.f, 0.f}; }
+  unsigned ucount = 0;   // 60 per unknown cell met
+  float ssum = 0.f;      // this thread's share of S, the sum of the whole scan
+  const int rounds = (nb + R - 1) / R;   // R directions each
+  const char* const ringb = reinterpret_cast<const char*>(ringh);
+  const float2* const ltq = ltab + q * ntab;
+  const unsigned none_off = (unsigned)(a.rows + 2) * (unsigned)(a.cols + 2) * 32u;   // the all-zero record behind the grid
+
+  // byte offset of the half record of table entry tv; a lane without a sample (ring >= nr, padding step) gets `none`
+  auto rec_off = [&](float2 tv, bool in) -> unsigned {
+    tdr_v2f pv = {tv.x, tv.y};
+    if constexpr (!USCALE) pv = (pv * scale) * a.res;   // top_down_map_polar.cpp:28
+    pv = pv + offv;                                      // :29-30
+    tdr_v2f qv = {__builtin_amdgcn_fmed3f(pv.x, -1.f, rmaxf), __builtin_amdgcn_fmed3f(pv.y, -1.f, cmaxf)};
+    qv = qv + 0.49999997f;                               // :31, see round_half_away_clamped
+    int ri, ci;
+    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ri) : "v"(qv.x));
+    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ci) : "v"(qv.y));
+    const unsigned off = (unsigned)(__mul24(ri, rowstride) + (ci * 32 + kbase));   // guard cells: distance 0, unknown
+    return in ? off : none_off;
+  };
+
+  for (int j0 = 0; j0 < a.nr; j0 += 4) {
+    __syncthreads();
+    bool big = false;
+    for (int t = threadIdx.x; t < 4 * nb; t += 256) {
+      const int kb = t / nb, r = t - kb * nb;
+      union { tdr_h2 h[4]; uint4 u; } pc;
+      pc.u = make_uint4(0u, 0u, 0u, 0u);
+      if (j0 + kb < a.nr) {
+        // packed scan record of rfs floats: the class counts first, the sum of the counts last
+        const float* srow = a.scan_pk + ((int64_t)(j0 + kb) * nb + r) * rfs;
+        float cnt[8];
+#pragma unroll
+        for (int k = 0; k < 7; k++) cnt[k] = k < a.ncls ? srow[k] : 0.f;
+        cnt[7] = srow[rfs - 1];
+#pragma unroll
+        for (int k = 0; k < 8; k++) big |= cnt[k] > 2048.f;
+#pragma unroll
+        for (int k = 0; k < 4; k++) pc.h[k] = __builtin_amdgcn_cvt_pkrtz(cnt[2 * k], cnt[2 * k + 1]);
+        ssum += cnt[7];
+      }
+      ringh[kb * img + r] = pc.u;
+      ringh[kb * img + r + nb] = pc.u;
+    }
+    for (int t = threadIdx.x; t < 4 * ntab; t += 256) {
+      const int kb = t / ntab, r = t - kb * ntab;
+      ltab[t] = tab2[(int64_t)min(j0 + kb, a.nr - 1) * nb + min(r, nb - 1)];
+    }
+    if (big) atomicOr(inexact, 1);
+    __syncthreads();
+    const bool ring_ok = j0 + q < a.nr;
+    // Software pipeline: the two record loads of step t + AHEAD are issued before the matrix work of step t (the table
+    // entry comes from LDS, so the address costs no trip to memory).  The scheduling barriers keep the compiler from
+    // sinking the loads next to their use, which would expose a full memory latency in every step.
+    uint4 h[R], l[R];
+#pragma unroll
+    for (int k = 0; k < AHEAD; k++) {
+      const char* r = recb + rec_off(ltq[k], ring_ok && k < nb);
+      h[k] = *reinterpret_cast<const uint4*>(r);
+      l[k] = *reinterpret_cast<const uint4*>(r + 16);
+    }
+    int ar[INITM_TILES];
+#pragma unroll
+    for (int T = 0; T < INITM_TILES; T++) ar[T] = arow[T];
+    int inext = AHEAD;   // direction of the loads issued next
+    for (int rd = 0; rd < rounds; rd++) {
+#pragma unroll
+      for (int u = 0; u < R; u++) {
+        {
+          const char* r = recb + rec_off(ltq[inext], ring_ok && inext < nb);
+          h[(u + AHEAD) % R] = *reinterpret_cast<const uint4*>(r);
+          l[(u + AHEAD) % R] = *reinterpret_cast<const uint4*>(r + 16);
+          inext++;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (rd * R + u < nb) {   // (uniform) not a padding step
+          union { uint4 u4; tdr_h8 v8; } bh, bl, bn;
+          bh.u4 = h[u];
+          bl.u4 = l[u];
+          bn.u4 = make_uint4(0u, 0u, 0u, bl.u4.w & 0xFFFF0000u);   // {0 .. 0, unknown}
+          bl.u4.w &= 0x0000FFFFu;
+          ucount += bn.u4.w >> 24;   // f16 1.0 = 0x3C00: its high byte, 60 per unknown cell
+          union { uint4 u4; tdr_h8 v8; } ac[INITM_TILES];
+#pragma unroll
+          for (int T = 0; T < INITM_TILES; T++) ac[T].u4 = *reinterpret_cast<const uint4*>(ringb + ar[T]);
+#pragma unroll
+          for (int T = 0; T < INITM_TILES; T++) accC[T] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ac[T].v8, bh.v8, accC[T], 0, 0, 0);
+          if (__builtin_amdgcn_ballot_w64(bn.u4.w != 0u) != 0) {   // (uniform) some lane met an unknown cell
+#pragma unroll
+            for (int T = 0; T < INITM_TILES; T++) accN[T] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ac[T].v8, bn.v8, accN[T], 0, 0, 0);
+          }
+#pragma unroll
+          for (int T = 0; T < INITM_TILES; T++) accC[T] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ac[T].v8, bl.v8, accC[T], 0, 0, 0);
+        }
+#pragma unroll
+        for (int T = 0; T < INITM_TILES; T++) ar[T] += 16;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  }
+  // S: every thread staged its share of every ring
+  __syncthreads();
+  float* const red = reinterpret_cast<float*>(ringh);
+  red[threadIdx.x] = ssum;
+  __syncthreads();
+  float stotal = 0.f;
+  for (int t = 0; t < 256; t++) stotal += red[t];   // same order in every lane
+  // samples this lane went through: nb directions on each of its rings j = q, q + 4, ...
+  const int my_rings = (a.nr - q + 3) / 4;
+  float known = (float)(my_rings * nb - (int)(ucount / 60u));
+  known += __shfl_xor(known, 16, 64);
+  known += __shfl_xor(known, 32, 64);
+  const bool unknown = (known / (float)a.P) < 0.5;   // state_particle.cpp:117-120
+  float best = 3.402823466e+38f;
+  int bm = -1;
+#pragma unroll
+  for (int T = 0; T < INITM_TILES; T++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int m = 16 * T + 4 * q + r;
+      float cost = accC[T][r] / (stotal - accN[T][r]);  // :154
+      if (unknown) cost = __builtin_nanf("");
+      if (m < nrot && cost < best) { best = cost; bm = m; }   // :200-203 (NaN never wins)
+    }
+#pragma unroll
+  for (int o = 16; o <= 32; o <<= 1) {   // first minimum in rotation order over the particle's four lanes
+    const float oc = __shfl_xor(best, o, 64);
+    const int om = __shfl_xor(bm, o, 64);
+    const bool take = om >= 0 && (bm < 0 || oc < best || (oc == best && om < bm));
+    if (take) { best = oc; bm = om; }
+  }
+  if (q == 0 && want) {
+    a.res_theta[p] = bm >= 0 ? a.theta[bm] : 0.f;  // :205 (best_theta stays 0 if nothing won)
+    a.res_flag[p] = bm < 0 ? 2.f : 1.f;
+  }
+}
+
+// candidate rotations of the search, generated exactly like the reference's loop (state_particle.cpp:197: float t,
+// double increment) together with their bin shifts (:124-128)
+__global__ void init_rot_kernel(int nb, int* __restrict__ shift, float* __restrict__ theta, int* __restrict__ nrot) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  nrot[1] = 0;   // the "scan counts too large for f16" flag of score_init_mfma_kernel
+  int k = 0;
+  for (float t = 0; t < 2 * M_PI; t += 2 * M_PI / 40) {
+    if (k >= INIT_MAXROT) break;
+    theta[k] = t;
+    shift[k] = rot_shift_dev(t, nb);
+    k++;
+  }
+  *nrot = k;
+}
+
+// state_.theta = best_theta; state_.have_init = true (state_particle.cpp:205-206)
+__global__ void init_apply_kernel(const float* __restrict__ res_theta, const float* __restrict__ res_flag, int64_t n,
+                                  float* __restrict__ st, int64_t cap) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < n && res_flag[p] != 0.f) {
+    st[TDR_ST_THETA * cap + p] = res_theta[p];
+    st[TDR_ST_HAVE_INIT * cap + p] = 1.f;
+  }
+}
+// particles whose init search found no valid rotation keep best_cost = FLT_MAX (:193) -> weight 1/(FLT_MAX + reg)
+__global__ void init_fixup_kernel(const float* __restrict__ res_flag, int64_t n, float regularization,
+                                  float* __restrict__ raw_w) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < n && res_flag[p] == 2.f) raw_w[p] = (float)(1. / (double)(3.402823466e+38f + regularization));
+}
+
+static int g_init_mfma = 1;   // 0 = vector-unit search only (A/B and debugging)
+static bool init_use_mfma() { return g_init_mfma != 0; }
+extern "C" int tdr_config_init_mfma(int on) {   // < 0: query only
+  if (on >= 0) g_init_mfma = on ? 1 : 0;
+  return g_init_mfma;
+}
+// bytes of the scratch behind tdr_map_desc.rec16 (0: this record size has no matrix-core search)
+extern "C" size_t tdr_map_rec16_bytes(int ncls, int rows, int cols) {
+  if (ncls < 1 || ncls > 7 || rows < 1 || cols < 1) return 0;
+  // the search addresses this grid with 32-bit byte offsets and a 24-bit row multiply: a map beyond that has no half
+  // records (0: the caller passes none and the search splits the dense records on the fly)
+  const uint64_t bytes = (uint64_t)(rows + 2) * (uint64_t)(cols + 2) * 32 + 32;   // + the all-zero record behind the grid
+  if (bytes > 0xFFFFFFFFull || (uint64_t)(cols + 2) * 32 >= (1u << 24)) return 0;
+  return (size_t)bytes;
+}
+// Rebuilding the half records is one pass over the whole map: it pays from a few thousand particles on (4000^2 cells:
+// 0.35 ms, the price of searching ~2000 particles with 256 x 256 windows on the fly).  Filters below the threshold
+// ignore the scratch — the filter's TOTAL particle count decides (n_total, the same on every rank), so that the ranks of
+// a sharded filter take the kernel the one-rank filter takes and choose the same rotations where candidates tie.
+// tdr_config_rec16_min_particles(INT64_MAX) turns the path off (A/B).
+static int64_t g_rec16_min = 8192;
+extern "C" int64_t tdr_config_rec16_min_particles(int64_t n) {   // < 0: query only
+  if (n >= 0) g_rec16_min = n;
+  return g_rec16_min;
+}
+// Rows per LDS scan image of score_init_half_kernel: 2 nb + R + c with the c in [0, 16) that gives the ds_read_b128 of
+// the candidates' rows the fewest bank conflicts.  A lane (candidate m, ring q) reads row q * img + i + shift_m; the LDS
+// serves the instruction in four groups of 16 lanes (MI355X_MICROARCH.md, LDS) and two lanes of a group collide when
+// their rows differ by a multiple of 16.  The shifts are multiples of nb / 40, so only a few residues occur and the
+// image stride decides how the rings' residues interleave (nb = 256: 3.7 LDS cycles per read at the worst stride, 2.0 at
+// the best).
+static int init_half_image_rows(int nb, int R) {
+  int sh[48] = {0};
+  int k = 0;
+  for (float t = 0; t < 2 * M_PI && k < 48; t += 2 * M_PI / 40) {   // as init_rot_kernel / rot_shift_dev
+    int s = (int)round((double)(t * (float)nb / 2) / M_PI);
+    s %= nb;
+    if (s < 0) s += nb;
+    sh[k++] = s;
+  }
+  static const int grp[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
+                                 {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
+                                 {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
+                                 {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
+  int best_c = 0;
+  long best = -1;
+  for (int c = 0; c < 16; c++) {
+    const int img = 2 * nb + R + c;
+    long tot = 0;
+    for (int T = 0; T < 3; T++)
+      for (int i = 0; i < 16; i++)   // the pattern repeats with i mod 16
+        for (int g = 0; g < 4; g++) {
+          int rows[16], worst = 1;
+          for (int l = 0; l < 16; l++) rows[l] = (grp[g][l] >> 4) * img + i + sh[16 * T + (grp[g][l] & 15)];
+          for (int x = 0; x < 16; x++) {
+            int distinct = 1;   // distinct rows on the bank quad of rows[x]
+            for (int y = 0; y < x; y++)
+              if ((rows[y] - rows[x]) % 16 == 0 && rows[y] != rows[x]) {
+                bool seen = false;
+                for (int z = 0; z < y; z++) seen |= rows[z] == rows[y];
+                if (!seen) distinct++;
+              }
+            if (distinct > worst) worst = distinct;
+          }
+          tot += worst;
+        }
+    if (best < 0 || tot < best) { best = tot; best_c = c; }
+  }
+  return 2 * nb + R + best_c;
+}
+// record loads the half-record search keeps in flight per wave (1..3): tdr_config_tuning("init_ahead")
+static int g_init_ahead = 1;
+extern "C" int tdr_config_init_ahead(int v) {   // < 1: query only
+  if (v >= 1) g_init_ahead = std::min(v, 3);
+  return g_init_ahead;
+}
+
+int tdr_score_init_search(const tdr_map_desc* map, const float* tab, const float* utab, const float* scan_pk, int nb,
+                          int nr, float res, const tdr_filter_params* fp, float* st, int64_t cap, int64_t n,
+                          int64_t n_total, const int32_t* order, float* res_flag, int64_t npad, hipStream_t s) {
+  const int rf = map->rec_floats;
+  float* res_theta = res_flag + npad;
+  InitArgs ia;
+  ia.rec = map->rec; ia.rows = map->rows; ia.cols = map->cols; ia.resolution = map->resolution;
+  ia.tab = tab; ia.utab = utab; ia.scan_pk = scan_pk; ia.nb = nb; ia.nr = nr; ia.res = res;
+  ia.st = st; ia.cap = cap; ia.n = n; ia.order = order; ia.fp = *fp; ia.gate = make_gate(fp, map);
+  ia.P = (int64_t)nb * nr; ia.ncls = map->ncls; ia.res_flag = res_flag; ia.res_theta = res_theta;
+  // rotation table lives behind the result arrays: [shift INIT_MAXROT][theta INIT_MAXROT][nrot]
+  int* d_shift = reinterpret_cast<int*>(res_theta + npad);
+  float* d_theta = reinterpret_cast<float*>(d_shift + INIT_MAXROT);
+  int* d_nrot = reinterpret_cast<int*>(d_theta + INIT_MAXROT);
+  hipLaunchKernelGGL(init_rot_kernel, dim3(1), dim3(64), 0, s, nb, d_shift, d_theta, d_nrot);
+  LAUNCH_CHECK("init_rot");
+  ia.shift = d_shift; ia.theta = d_theta; ia.nrot = d_nrot;
+  HIP_TRY(hipMemsetAsync(res_flag, 0, sizeof(float) * (size_t)n, s));
+  dim3 grid((unsigned)cdiv(n, 64)), block(64 * INIT_WAVES);
+  const size_t lds = TDR_INIT_SCAN_LDS ? (size_t)2 * nb * rf * 4 : 0;
+  const bool ks = tdr_has_kslot(map->ncls, rf), us = utab != nullptr;
+  ia.only_if = nullptr;
+  bool unitw = true;
+  for (int c = 1; c < map->ncls; c++) unitw &= fp->class_weights[c] == fp->class_weights[0];
+  unitw &= fp->class_weights[0] > 0.f;
+  int* d_inexact = d_nrot + 1;
+  const bool half_path = (rf == 4 || rf == 8) && map->ncls <= 7 && init_use_mfma() && map->rec16 &&
+                         tdr_map_rec16_bytes(map->ncls, map->rows, map->cols) != 0 && n_total >= g_rec16_min &&
+                         (size_t)4 * (2 * nb + 20) * 16 + (size_t)4 * (nb + 8) * 8 <= 64 * 1024;
+  if (half_path) {
+    // matrix-core pass on pre-split half records (weights folded in), built into the map owner's scratch first; the
+    // vector kernel below then runs only if a scan count did not fit f16
+    const int64_t ncells = (int64_t)(map->rows + 2) * (map->cols + 2);
+    const dim3 hgrid((unsigned)cdiv(ncells, 256)), hblock(256);
+    const float4* rec4 = reinterpret_cast<const float4*>(map->rec);
+    uint4* r16 = reinterpret_cast<uint4*>(map->rec16);
+    if (rf == 4) hipLaunchKernelGGL((half_records_kernel<4>), hgrid, hblock, 0, s, rec4, ncells, unitw ? 1 : 0, *fp, map->ncls, r16);
+    else hipLaunchKernelGGL((half_records_kernel<8>), hgrid, hblock, 0, s, rec4, ncells, unitw ? 1 : 0, *fp, map->ncls, r16);
+    LAUNCH_CHECK("half_records");
+    const int ahead = g_init_ahead;
+    const int R = ahead + 1;
+    const int img = init_half_image_rows(nb, R);
+    const size_t ldsh = (size_t)4 * img * 16 + (size_t)4 * (nb + 2 * R) * 8;
+    const uint4* r16c = r16;
+    with_flags([&](auto US) {
+      constexpr bool U = decltype(US)::value;
+      auto launch = [&](auto kfn) { hipLaunchKernelGGL(kfn, grid, dim3(256), ldsh, s, ia, r16c, d_inexact, img, rf); };
+      if (ahead == 1) launch(score_init_half_kernel<U, 1>);
+      else if (ahead == 2) launch(score_init_half_kernel<U, 2>);
+      else launch(score_init_half_kernel<U, 3>);
+      return TDR_OK;
+    }, us);
+    LAUNCH_CHECK("score_init_half");
+    ia.only_if = d_inexact;
+  } else if (rf == 8 && (ks || map->ncls == 7) && init_use_mfma()) {
+    // matrix-core pass splitting the f32 records per sample (small filters, maps without the scratch); the vector
+    // kernel below then runs only if a scan count did not fit f16
+    const size_t lds16 = ((size_t)2 * nb + 1) * 16;
+    with_flags([&](auto US, auto UW, auto SV) {
+      hipLaunchKernelGGL((score_init_mfma_kernel<decltype(US)::value, decltype(UW)::value, decltype(SV)::value>), grid,
+                         dim3(256), lds16, s, ia, d_inexact);
+      return TDR_OK;
+    }, us, unitw, !ks);
+    LAUNCH_CHECK("score_init_mfma");
+    ia.only_if = d_inexact;
+  } else if ((rf == 12 || rf == 16) && init_use_mfma()) {
+    // 8-15 classes: two groups of 8 slots per sample (score_init_mfma_wide_kernel)
+    const size_t lds16 = ((size_t)2 * nb + 1) * 2 * 16;
+    with_flags([&](auto US, auto R16) {
+      hipLaunchKernelGGL((score_init_mfma_wide_kernel<decltype(R16)::value ? 4 : 3, decltype(US)::value>), grid, dim3(256),
+                         lds16, s, ia, d_inexact);
+      return TDR_OK;
+    }, us, rf == 16);
+    LAUNCH_CHECK("score_init_mfma_wide");
+    ia.only_if = d_inexact;
+  }
+  if (int rc = with_nv4(rf, "score", [&](auto N) {
+        return with_flags([&](auto KS, auto US) {
+          hipLaunchKernelGGL((score_init_kernel<decltype(N)::value, decltype(KS)::value, decltype(US)::value>), grid, block,
+                             lds, s, ia);
+          return TDR_OK;
+        }, ks, us);
+      }))
+    return rc;
+  LAUNCH_CHECK("score_init");
+  hipLaunchKernelGGL(init_apply_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, (const float*)res_theta,
+                     (const float*)res_flag, n, st, cap);
+  LAUNCH_CHECK("init_apply");
+  return TDR_OK;
+}
+int tdr_score_init_fixup(const float* res_flag, int64_t n, float regularization, float* raw_w, hipStream_t s) {
+  hipLaunchKernelGGL(init_fixup_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, res_flag, n, regularization, raw_w);
+  LAUNCH_CHECK("init_fixup");
+  return TDR_OK;
+}
