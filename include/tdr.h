@@ -560,6 +560,9 @@ int tdr_profile_variants(int64_t out[16]);
  *                      partition of the FLOAT kernel's sums: its results move in the last bits)
  *   "su_group"         rings per workgroup of the shift-uniform kernel alone (a multiple of 4; integer sums: same bits)
  *   "init_ahead"       record loads in flight in the init search (1-3)
+ *   "batch_init_search"  0 (default): a filter that may hold a particle without a heading runs its standalone
+ *                      calls inside tdr_batch_step; 1: it joins the batch, its search one launch per pass kind
+ *                      for the whole batch (same bits)
  *   "prefix_head"      leading addends the long running sum's walk adds one by one
  *   "ray_block_major"  0: the ray-mapped kernel keeps its first row order (direction-major) also when the caller's context
  *                      holds the table's factors (same bits)
@@ -900,7 +903,11 @@ int64_t tdr_filter_adaptive_count(tdr_filter* f);
  * they are not sharded, draw from the device generator in parity mode
  * (a seeded filter whose generator is its own), have at most 32 768 particles, no particle still without a heading (the
  * 40-rotation search of the first update) and a scoring launch of the float form (small windows and filters, see
- * tdr_config_shift_uniform).  Every other filter runs its standalone calls inside the same tdr_batch_step, so a batch is
+ * tdr_config_shift_uniform).  With tdr_config_tuning("batch_init_search", 1) a filter that may still hold a particle
+ * without a heading — a cold start (init_pos_deg_theta = inf), or for ever a gated filter (force_on_map, fixed_scale < 0) —
+ * joins the batch too: its search takes the pass its standalone call takes (tdr_config_init_mfma) as part of the batch's
+ * scoring stage, one launch per pass kind for all such filters, the map's half records built once per set of class weights
+ * instead of once per filter.  Every other filter runs its standalone calls inside the same tdr_batch_step, so a batch is
  * always correct.  Each filter's own stream and generator streams are ordered against `stream` with events.
  * Refused with TDR_ERR_ARG before any device work (no filter changes): k < 1, a null array or filter, a filter twice,
  * filters on different maps, a map without samplePtsPolar, an input without a scan, a render whose shape is not the map's.

@@ -63,6 +63,11 @@ class ParticleFilterBatch {
       throw std::runtime_error(std::string("ParticleFilterBatch::step: ") + tdr_last_error());
     tdr_batch_last_stats(&batched_, &standalone_);
   }
+  // tdr_config_tuning("batch_init_search"), process-wide: with true a filter that may still hold a particle without a
+  // heading — a cold start (init_pos_deg_theta = inf), a gated filter (force_on_map, unknown scale) — joins the batch, its
+  // 40-rotation search part of the batch's scoring stage, same bits; false (the default): its standalone calls inside step()
+  static void setInitSearchInBatch(bool on) { tdr_config_tuning("batch_init_search", on ? 1 : 0); }
+  static bool initSearchInBatch() { return tdr_config_tuning("batch_init_search", -1) == 1; }
   // filters of the last step that took the batched path / their standalone calls
   int lastBatched() const { return batched_; }
   int lastStandalone() const { return standalone_; }

@@ -192,6 +192,17 @@ def step_batch(filters, scans, res, priors, n_targets=None, stream=None):
     return last_stats()
 
 
+def set_init_search_in_batch(on):
+    """tdr_config_tuning("batch_init_search"): with True a filter that may still hold a particle without a heading (a cold
+    start, a gated filter) joins the batch, its 40-rotation search part of the batch's scoring stage — same bits; False (the
+    default): it runs its standalone calls inside step_batch.  Process-wide.  Returns the value in force."""
+    return bool(_lib.load().tdr_config_tuning(b"batch_init_search", 1 if on else 0))
+
+
+def init_search_in_batch():
+    return bool(_lib.load().tdr_config_tuning(b"batch_init_search", -1))
+
+
 def last_stats():
     """(batched, standalone): how the filters of this thread's last step_batch were stepped."""
     L = _lib.load()

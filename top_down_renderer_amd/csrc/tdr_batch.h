@@ -52,10 +52,12 @@ int tdr_batch_resample(const TdrBatchEntry* tab, int k, int blocks_res, hipStrea
 int tdr_batch_update_weights(const TdrBatchEntry* tab, int k, int64_t n_max, hipStream_t s);
 int tdr_batch_prefix(const TdrBatchEntry* tab, int k, int64_t n_max, hipStream_t s);
 
-// tdr_score.hip: the float form of every filter's scoring launch (tdr_k_score_polar_ctx without an init search and
-// without the locality order), one grid.  build fills a host staging area of tdr_batch_score_stage_bytes(k) bytes (64-byte
-// aligned); the caller copies it to device memory; launch reads the grid sizes from the host copy and the tables from the
-// device copy.  A filter whose launch takes the integer form (tdr_score_polar_float_form == false) is refused.
+// tdr_score.hip: the float form of every filter's scoring launch (tdr_k_score_polar_ctx without the locality order), one
+// grid — with the 40-rotation search of the filters that ask for it (init_search) in front of it (tdr_score_init.h: one
+// launch per pass kind, same bits as the standalone search).  build fills a host staging area of
+// tdr_batch_score_stage_bytes(k, k_init) bytes (64-byte aligned); the caller copies it to device memory; launch reads the
+// grid sizes from the host copy and the tables from the device copy.  A filter whose launch takes the integer form
+// (tdr_score_polar_float_form == false) is refused.
 struct TdrBatchScoreIn {
   const float* scan_pk;   // packed scan (tdr_k_pack_scan)
   float res;
@@ -65,8 +67,9 @@ struct TdrBatchScoreIn {
   float uniform_scale;
   float* raw_w;
   float* ws;              // tdr_score_workspace_floats(ncls, nb, nr, n, n) floats
+  int init_search;        // the filter may hold a particle without a heading: its 40-rotation search runs first
 };
-size_t tdr_batch_score_stage_bytes(int k);
+size_t tdr_batch_score_stage_bytes(int k, int k_init);   // k_init: the filters with init_search set
 int tdr_batch_score_build(const tdr_map_desc* map, const float* tab, int nb, int nr, int k, const TdrBatchScoreIn* in,
                           void* host_stage);
 int tdr_batch_score_launch(const tdr_map_desc* map, const float* tab, int nb, int nr, int k, const void* host_stage,

@@ -83,6 +83,8 @@ struct tdr_map {
   DevBuf<float> cdict;
   DevBuf<uint8_t> cws;
   DevBuf<uint8_t> rec16;   // scratch of the 40-rotation search (tdr_map_desc.rec16), allocated by the first large search
+  hipEvent_t rec16_used = nullptr;   // recorded after every search that used rec16; the next one waits for it (map_rec16_*)
+  ~tdr_map() { if (rec16_used) (void)hipEventDestroy(rec16_used); }
   std::vector<float> maps_host;  // class_maps_ (column-major), kept for getClassesAtPoint / particle initialisation
   std::vector<uint8_t> mask_host;  // class_mask_ (column-major), kept for the map cache
   tdr_map_desc desc{};
@@ -1425,6 +1427,27 @@ int tdr_filter_get_last_dist(tdr_filter* f, float* out, int64_t n) {
   HTRY(hipMemcpy(out, f->last_dist.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
   return TDR_OK;
 }
+// The half records of the 40-rotation search live in ONE scratch per map and every search rebuilds them for its class
+// weights, so searches of the map's filters must not overlap in time — whichever streams they run on (the filters' own,
+// the batch's).  A search that may use the scratch runs between these two: wait for the last one, leave an event behind.
+static int map_rec16_alloc(tdr_map* m, int64_t n) {
+  if (m->desc.rec16 || n < tdr_config_rec16_min_particles(-1)) return TDR_OK;
+  const size_t b16 = tdr_map_rec16_bytes(m->desc.ncls, m->desc.rows, m->desc.cols);
+  if (b16) {
+    TTRY(m->rec16.resize(b16));
+    m->desc.rec16 = m->rec16.p;
+  }
+  return TDR_OK;
+}
+static int map_rec16_begin(tdr_map* m, hipStream_t s) {
+  if (m->rec16_used) HTRY(hipStreamWaitEvent(s, m->rec16_used, 0));
+  return TDR_OK;
+}
+static int map_rec16_end(tdr_map* m, hipStream_t s) {
+  if (!m->rec16_used) HTRY(hipEventCreateWithFlags(&m->rec16_used, hipEventDisableTiming));
+  HTRY(hipEventRecord(m->rec16_used, s));
+  return TDR_OK;
+}
 static int filter_score(tdr_filter* f, const float* scan_imgs, const tdr_renderer* renderer, float res) {
   tdr_map* m = f->map;
   if (m->nb < 1 || !m->tab.p) return failh(TDR_ERR_ARG, "filter_update: samplePtsPolar was never called");
@@ -1465,18 +1488,14 @@ static int filter_score(tdr_filter* f, const float* scan_imgs, const tdr_rendere
   }
   f->states_changed();   // (the init search writes headings)
   TTRY(f->ws.resize(tdr_score_workspace_floats(ncls, nb, nr, n, f->n)));
-  if (f->maybe_uninit && !m->desc.rec16 && f->n >= tdr_config_rec16_min_particles(-1)) {
-    // the search over this many particles pays for pre-split half records (filters on one map share the scratch: their
-    // searches must not overlap in time)
-    const size_t b16 = tdr_map_rec16_bytes(ncls, m->desc.rows, m->desc.cols);
-    if (b16) {
-      TTRY(m->rec16.resize(b16));
-      m->desc.rec16 = m->rec16.p;
-    }
-  }
+  // the search over this many particles pays for pre-split half records
+  if (f->maybe_uninit) TTRY(map_rec16_alloc(m, f->n));
+  const bool uses_rec16 = f->maybe_uninit && m->desc.rec16 && f->n >= tdr_config_rec16_min_particles(-1);
+  if (uses_rec16) TTRY(map_rec16_begin(m, f->stream));
   TTRY(tdr_score_ctx_set_polar_factors(f->score_ctx, m->fac.p, nb, nr));
   TTRY(tdr_k_score_polar_ctx(&m->desc, m->tab.p, pk, nb, nr, res, &f->fp, f->st.p, f->cap, n, f->n, perm, f->uniform_scale,
                              f->maybe_uninit ? 1 : 0, f->raw_w.p, f->ws.p, f->score_ctx, f->stream));
+  if (uses_rec16) TTRY(map_rec16_end(m, f->stream));
   if (renderer && !scan_imgs) TTRY(renderer_note_read(renderer, f->stream));
   // the search initialises every un-gated particle; only gated ones (state_particle.cpp:163-176) can stay un-initialised
   if (f->maybe_uninit && !(f->fp.force_on_map || f->fp.fixed_scale < 0)) f->maybe_uninit = false;
@@ -1741,7 +1760,9 @@ int tdr_batch_last_stats(int* batched, int* standalone) {
 
 static bool batch_eligible(const tdr_filter* f) {
   const tdr_map* m = f->map;
-  return !f->comm && rng_device_capable(f) && !f->maybe_uninit && f->n >= 1 && f->n <= 32768 &&
+  // (a filter that may hold a particle without a heading: only with tdr_config_tuning("batch_init_search"))
+  const bool uninit_ok = !f->maybe_uninit || tdr_config_tuning("batch_init_search", -1) == 1;
+  return !f->comm && rng_device_capable(f) && uninit_ok && f->n >= 1 && f->n <= 32768 &&
          tdr_score_polar_float_form(&m->desc, m->nb, m->nr, f->n, f->n);
 }
 
@@ -1784,9 +1805,19 @@ int tdr_batch_step(tdr_filter* const* filters, int k, const tdr_batch_input* in,
   if (kf == 0) return TDR_OK;
 
   BatchCtx& B = g_batch;
+  // the batched filters whose 40-rotation search is part of the scoring stage; the largest decides about the map's scratch
+  int k_init = 0;
+  bool uses_rec16 = false;
+  for (int j = 0; j < kf; j++) {
+    const tdr_filter* f = filters[fast[j]];
+    if (!f->maybe_uninit) continue;
+    k_init++;
+    TTRY(map_rec16_alloc(m, f->n));
+    uses_rec16 |= m->desc.rec16 && f->n >= tdr_config_rec16_min_particles(-1);
+  }
   // one staging area: [kf] TdrBatchEntry, then the scoring launch's tables (tdr_batch_score_stage_bytes)
   const size_t ent_bytes = (sizeof(TdrBatchEntry) * (size_t)kf + 63) / 64 * 64;
-  const size_t stage = ent_bytes + tdr_batch_score_stage_bytes(kf);
+  const size_t stage = ent_bytes + tdr_batch_score_stage_bytes(kf, k_init);
   if (!B.uploaded) HTRY(hipEventCreateWithFlags(&B.uploaded, hipEventDisableTiming));
   if (!B.done) HTRY(hipEventCreateWithFlags(&B.done, hipEventDisableTiming));
   HTRY(hipEventSynchronize(B.uploaded));   // (the previous call's copy has left the pinned buffer)
@@ -1860,7 +1891,8 @@ int tdr_batch_step(tdr_filter* const* filters, int k, const tdr_batch_input* in,
     e.blk_res = blocks_res;
     blocks_res += (int)((n_new + TDR_BATCH_THREADS - 1) / TDR_BATCH_THREADS);
     n_big = std::max(n_big, f->n);
-    sin[j] = TdrBatchScoreIn{pk, x.res, &f->fp, f->st.p, f->cap, f->n, f->uniform_scale, f->raw_w.p, f->ws.p};
+    sin[j] = TdrBatchScoreIn{pk, x.res, &f->fp, f->st.p, f->cap, f->n, f->uniform_scale, f->raw_w.p, f->ws.p,
+                             f->maybe_uninit ? 1 : 0};
   }
   if (rc == TDR_OK) rc = tdr_batch_score_build(&m->desc, m->tab.p, nb, nr, kf, sin.data(), B.host + ent_bytes);
   if (rc == TDR_OK && hipMemcpyAsync(B.dev.p, B.host, stage, hipMemcpyHostToDevice, s) != hipSuccess)
@@ -1868,7 +1900,9 @@ int tdr_batch_step(tdr_filter* const* filters, int k, const tdr_batch_input* in,
   if (rc == TDR_OK && hipEventRecord(B.uploaded, s) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: event record");
   // one launch per stage over the whole batch (the scoring launch: utab, score, finalize)
   if (rc == TDR_OK) rc = tdr_batch_propagate(tab_dev, kf, blocks_prop, s);
+  if (rc == TDR_OK && uses_rec16) rc = map_rec16_begin(m, s);
   if (rc == TDR_OK) rc = tdr_batch_score_launch(&m->desc, m->tab.p, nb, nr, kf, B.host + ent_bytes, B.dev.p + ent_bytes, s);
+  if (rc == TDR_OK && uses_rec16) rc = map_rec16_end(m, s);
   if (rc == TDR_OK) rc = tdr_batch_update_weights(tab_dev, kf, n_big, s);
   if (rc == TDR_OK) rc = tdr_batch_prefix(tab_dev, kf, n_big, s);
   if (rc == TDR_OK) rc = tdr_batch_resample(tab_dev, kf, blocks_res, s);
@@ -1880,6 +1914,8 @@ int tdr_batch_step(tdr_filter* const* filters, int k, const tdr_batch_input* in,
     tdr_filter* f = filters[fast[j]];
     f->have_ml = true;
     f->states_changed();
+    // the search initialises every un-gated particle; only gated ones can stay un-initialised (filter_score)
+    if (f->maybe_uninit && !(f->fp.force_on_map || f->fp.fixed_scale < 0)) f->maybe_uninit = false;
     std::swap(f->st.p, f->st_new.p);   // particle_filter.cpp:187
     f->n = tab[j].n_new;
     f->step++;

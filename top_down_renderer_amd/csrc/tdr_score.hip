@@ -747,6 +747,7 @@ static int g_score_group = 0;   // 0: from the shapes (score_group_rings)
 static int g_su_group = 0;      // 0: from the shapes (tdr_score_workspace)
 static int64_t score_wave_target() { return g_score_waves; }
 extern "C" int tdr_config_init_ahead(int);         // tdr_score_init.hip
+extern "C" int tdr_config_batch_init_search(int);
 extern "C" int tdr_config_prefix_head(int);        // tdr_prefix.hip
 extern "C" int tdr_config_ray_block_major(int);    // tdr_score_ray.hip
 extern "C" int tdr_config_ray_patch(int);
@@ -763,6 +764,7 @@ extern "C" int64_t tdr_config_tuning(const char* name, int64_t value) {   // val
   if (n == "score_waves") { if (value > 0) g_score_waves = value; return g_score_waves; }
   if (n == "score_group") { if (value >= 0) g_score_group = (int)value; return g_score_group; }
   if (n == "su_group") { if (value >= 0) g_su_group = (int)value; return g_su_group; }
+  if (n == "batch_init_search") return tdr_config_batch_init_search((int)std::max<int64_t>(value, -1));
   if (n == "init_ahead") return tdr_config_init_ahead((int)std::min<int64_t>(std::max<int64_t>(value, -1), 3));
   if (n == "prefix_head") return tdr_config_prefix_head((int)std::max<int64_t>(value, -1));
   if (n == "ray_borrow") return tdr_config_ray_borrow((int)std::max<int64_t>(value, -1));
@@ -1162,6 +1164,7 @@ static void launch_finalize_exact(FinalizeArgs& f, const tdr_map_desc* map, int6
 namespace {
 struct BatchScoreHdr {
   int32_t blocks, max_chunks, fin_blocks, n_uscale;
+  int32_t k_init;   // filters whose 40-rotation search runs in this launch (their tables: behind the scoring tables)
   size_t lds;
 };
 struct UtabEntry {
@@ -1188,7 +1191,9 @@ __global__ void utab_batch_kernel(const float* __restrict__ tab, int64_t n2, con
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e.out && k < n2) e.out[k] = (tab[k] * e.scale) * e.res;  // utab_kernel's expression
 }
-size_t tdr_batch_score_stage_bytes(int k) { return k < 1 ? 0 : batch_layout(k).total; }
+size_t tdr_batch_score_stage_bytes(int k, int k_init) {
+  return k < 1 ? 0 : batch_layout(k).total + tdr_batch_init_stage_bytes(k_init);
+}
 int tdr_batch_score_build(const tdr_map_desc* map, const float* tab, int nb, int nr, int k, const TdrBatchScoreIn* in,
                           void* host_stage) {
   if (!map || !tab || !in || !host_stage || k < 1 || nb < 1 || nr < 1) return fail(TDR_ERR_ARG, "batch_score: bad arguments");
@@ -1205,6 +1210,7 @@ int tdr_batch_score_build(const tdr_map_desc* map, const float* tab, int nb, int
   int32_t* fblk = reinterpret_cast<int32_t*>(base + Lo.fblk);
   UtabEntry* ut = reinterpret_cast<UtabEntry*>(base + Lo.utab);
   h = BatchScoreHdr{};
+  std::vector<TdrBatchInitIn> iin;
   for (int i = 0; i < k; i++) {
     const TdrBatchScoreIn& x = in[i];
     if (x.n < 1 || x.cap < x.n || !x.fp || x.fp->num_classes != map->ncls) return fail(TDR_ERR_ARG, "batch_score: filter %d", i);
@@ -1226,7 +1232,11 @@ int tdr_batch_score_build(const tdr_map_desc* map, const float* tab, int nb, int
     fargs[i] = f;
     fblk[i] = h.fin_blocks;
     h.fin_blocks += (int32_t)cdiv(x.n << f.tlog, 256);
+    // res_flag / res_theta and the rotation table where tdr_k_score_polar_ctx puts them
+    if (x.init_search) iin.push_back(TdrBatchInitIn{x.scan_pk, x.res, x.fp, x.st, x.cap, x.n, a.utab, x.ws + W.off_aux, a.npad, x.raw_w});
   }
+  h.k_init = (int32_t)iin.size();
+  if (h.k_init > 0) return tdr_batch_init_build(map, tab, nb, nr, h.k_init, iin.data(), base + Lo.total);
   return TDR_OK;
 }
 int tdr_batch_score_launch(const tdr_map_desc* map, const float* tab, int nb, int nr, int k, const void* host_stage,
@@ -1246,6 +1256,10 @@ int tdr_batch_score_launch(const tdr_map_desc* map, const float* tab, int nb, in
     hipLaunchKernelGGL(utab_batch_kernel, dim3((unsigned)cdiv(n2, 256), (unsigned)k), dim3(256), 0, s, tab, n2, ut);
     LAUNCH_CHECK("batch_utab");
   }
+  // state_particle.cpp:195-206 first, as in tdr_k_score_polar_ctx: the regular pass below then scores every particle at its
+  // (possibly just chosen) rotation
+  if (h.k_init > 0)
+    if (int rc = tdr_batch_init_launch(map, nb, nr, static_cast<const char*>(host_stage) + Lo.total, d + Lo.total, s)) return rc;
   const dim3 grid((unsigned)h.blocks, (unsigned)h.max_chunks);
   for (int us = 1; us >= 0; us--) {   // the filters with a uniform-scale table, then the others: one instantiation each
     if (us ? h.n_uscale == 0 : h.n_uscale == k) continue;
@@ -1259,6 +1273,7 @@ int tdr_batch_score_launch(const tdr_map_desc* map, const float* tab, int nb, in
   LAUNCH_CHECK("batch_score_polar");
   hipLaunchKernelGGL(score_finalize_batch_kernel, dim3((unsigned)h.fin_blocks), dim3(256), 0, s, fargs, fblk, k);
   LAUNCH_CHECK("batch_score_finalize");
+  if (h.k_init > 0) return tdr_batch_init_fixup(static_cast<const char*>(host_stage) + Lo.total, d + Lo.total, s);
   return TDR_OK;
 }
 extern "C" int tdr_k_score_polar(const tdr_map_desc* map, const float* tab, const float* scan_pk, int nb, int nr,

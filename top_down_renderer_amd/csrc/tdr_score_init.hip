@@ -1,6 +1,11 @@
 // tdr_score_init.hip — the 40-rotation init search of state_particle.cpp:195-206: the vector kernel, the three matrix-core
 // kernels (on the fly, wide records, pre-split half records) and the host function that picks among them
 // (tdr_score_init.h).  Built with -amdgpu-mfma-vgpr-form (build.py): the only file that issues MFMAs.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "tdr_batch.h"       // batch_find
 #include "tdr_common.h"
 #include "tdr_score_dev.h"   // rot_shift_dev, the coordinate rounding, the gates
 #include "tdr_score_init.h"
@@ -44,8 +49,12 @@ struct InitArgs {
                      //     (weight 1/(FLT_MAX + reg), state_particle.cpp:193,212)
 };
 
+// Each search kernel is a body (bx: the workgroup's index among its filter's batches of 64 particles) behind two wrappers:
+// the standalone kernel passes its kernel arguments and blockIdx.x, the batched one (tdr_batch_step) finds
+// its filter from blockIdx.x and reads that filter's InitArgs from a device table — the index is wave-uniform and the
+// entry is read before anything is stored, so its fields arrive through scalar loads as kernel arguments do.
 template <int NV4, bool KSLOT, bool USCALE>
-__global__ __launch_bounds__(64 * INIT_WAVES) void score_init_kernel(InitArgs a) {
+__device__ __forceinline__ void score_init_body(const InitArgs& a, int bx) {
   constexpr int RF = 4 * NV4;
   constexpr int U = 1;
 #if TDR_INIT_SCAN_LDS
@@ -57,7 +66,7 @@ __global__ __launch_bounds__(64 * INIT_WAVES) void score_init_kernel(InitArgs a)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform, and the compiler knows it
   if (a.only_if && *a.only_if == 0) return;               // (uniform) the MFMA pass already produced the results
-  const int64_t slot = (int64_t)blockIdx.x * 64 + lane;   // all four waves work on the same 64 particles
+  const int64_t slot = (int64_t)bx * 64 + lane;   // all four waves work on the same 64 particles
   const bool valid = slot < a.n;
   const int64_t p = a.order ? (int64_t)a.order[valid ? slot : 0] : (valid ? slot : 0);
   const float scale = a.st[TDR_ST_SCALE * a.cap + p];
@@ -201,6 +210,27 @@ __global__ __launch_bounds__(64 * INIT_WAVES) void score_init_kernel(InitArgs a)
     a.res_flag[p] = bt < 0 ? 2.f : 1.f;
   }
 }
+template <int NV4, bool KSLOT, bool USCALE>
+__global__ __launch_bounds__(64 * INIT_WAVES) void score_init_kernel(InitArgs a) {
+  score_init_body<NV4, KSLOT, USCALE>(a, (int)blockIdx.x);
+}
+// Batched wrappers: entry e of `args` owns the blocks [blk[e], blk[e + 1]) counted from blk[0] (the launch covers a run of
+// the batch's table, `blk` is the cumulative count over the whole table).  A filter whose USCALE differs from the
+// instantiation's is another launch over the same run.
+// (The entry's pointers are generic ones to the compiler, so the gathers through them are flat loads where the standalone
+// kernels issue global loads — as in score_polar_batch_kernel.)
+#define INIT_BATCH_FIND()                                                                    \
+  const int b = (int)blockIdx.x + blk[0];                                                    \
+  const int e = batch_find(k, b, [&](int i) { return blk[i]; });                             \
+  const InitArgs a = args[e];                                                                \
+  if ((a.utab != nullptr) != USCALE) return; /* (uniform) */                                 \
+  const int bx = b - blk[e]
+template <int NV4, bool KSLOT, bool USCALE>
+__global__ __launch_bounds__(64 * INIT_WAVES) void score_init_batch_kernel(const InitArgs* __restrict__ args,
+                                                                           const int32_t* __restrict__ blk, int k) {
+  INIT_BATCH_FIND();
+  score_init_body<NV4, KSLOT, USCALE>(a, bx);
+}
 
 // The same search on the matrix cores (records of 8 floats, i.e. 4-6 classes).  For one particle the 40 candidate
 // costs are  cost[m] = sum_{i,j,c} scan_c[(i + s_m) mod nb, j] * (w_c d_c[cell(i,j)]):  a contraction over
@@ -224,12 +254,12 @@ static_assert(INITM_TILES * 16 >= INIT_MAXROT || INIT_MAXROT == 48, "rotation ti
 // UNITW: all class weights are equal — a common factor does not move the minimum, so the distances go in unweighted.
 // SEVEN: 7 classes — slot 6 of the record is a seventh distance (no spare slot), slot 7 still `known` / the scan's sum.
 template <bool USCALE, bool UNITW, bool SEVEN>
-__global__ __launch_bounds__(256) void score_init_mfma_kernel(InitArgs a, int* __restrict__ inexact) {
+__device__ __forceinline__ void score_init_mfma_body(const InitArgs& a, int bx, int* __restrict__ inexact) {
   constexpr int RF = 8;
   extern __shared__ uint4 ring16[];   // [2*nb] packed scan records as 8 x f16 (row r and r+nb hold scan row r) + 1 zero row
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = lane & 15, q = lane >> 4;
-  const int64_t slot = (int64_t)blockIdx.x * 64 + wave * 16 + col;
+  const int64_t slot = (int64_t)bx * 64 + wave * 16 + col;
   const bool valid = slot < a.n;
   const int64_t p = a.order ? (int64_t)a.order[valid ? slot : 0] : (valid ? slot : 0);
   const float scale = a.st[TDR_ST_SCALE * a.cap + p];
@@ -377,20 +407,31 @@ __global__ __launch_bounds__(256) void score_init_mfma_kernel(InitArgs a, int* _
     a.res_flag[p] = bm < 0 ? 2.f : 1.f;
   }
 }
+template <bool USCALE, bool UNITW, bool SEVEN>
+__global__ __launch_bounds__(256) void score_init_mfma_kernel(InitArgs a, int* __restrict__ inexact) {
+  score_init_mfma_body<USCALE, UNITW, SEVEN>(a, (int)blockIdx.x, inexact);
+}
+// batched: a filter's "scan count does not fit f16" word is its own (behind its rotation count, as standalone)
+template <bool USCALE, bool UNITW, bool SEVEN>
+__global__ __launch_bounds__(256) void score_init_mfma_batch_kernel(const InitArgs* __restrict__ args,
+                                                                    const int32_t* __restrict__ blk, int k) {
+  INIT_BATCH_FIND();
+  score_init_mfma_body<USCALE, UNITW, SEVEN>(a, bx, const_cast<int*>(a.nrot) + 1);
+}
 
 // The same for records of 12 and 16 floats (8-15 classes): a sample's record is two groups of 8 slots, each group its own
 // pair of fragments — B from the gathered record, A from a second LDS image of the scan row — so a step of 4 samples is
 // 2 x (hi + lo) products per tile instead of one, plus the normalisation product on the group that holds slot RF - 1.
 // Class weights are always folded in (no unit-weight form); slots past the class count meet a zero weight.
 template <int NV4, bool USCALE>
-__global__ __launch_bounds__(256) void score_init_mfma_wide_kernel(InitArgs a, int* __restrict__ inexact) {
+__device__ __forceinline__ void score_init_mfma_wide_body(const InitArgs& a, int bx, int* __restrict__ inexact) {
   constexpr int RF = 4 * NV4, NH = 2;
   static_assert(NV4 == 3 || NV4 == 4, "records of 12 or 16 floats");
   constexpr int HN = (RF - 1) / 8, KN = (RF - 1) % 8;   // group and slot of `known` / the scan's sum
   extern __shared__ uint4 ring16[];   // [2*nb + 1 rows][NH groups]: 8 x f16 each; rows r and r+nb hold scan row r, the last is zero
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = lane & 15, q = lane >> 4;
-  const int64_t slot = (int64_t)blockIdx.x * 64 + wave * 16 + col;
+  const int64_t slot = (int64_t)bx * 64 + wave * 16 + col;
   const bool valid = slot < a.n;
   const int64_t p = a.order ? (int64_t)a.order[valid ? slot : 0] : (valid ? slot : 0);
   const float scale = a.st[TDR_ST_SCALE * a.cap + p];
@@ -547,6 +588,16 @@ __global__ __launch_bounds__(256) void score_init_mfma_wide_kernel(InitArgs a, i
     a.res_flag[p] = bm < 0 ? 2.f : 1.f;
   }
 }
+template <int NV4, bool USCALE>
+__global__ __launch_bounds__(256) void score_init_mfma_wide_kernel(InitArgs a, int* __restrict__ inexact) {
+  score_init_mfma_wide_body<NV4, USCALE>(a, (int)blockIdx.x, inexact);
+}
+template <int NV4, bool USCALE>
+__global__ __launch_bounds__(256) void score_init_mfma_wide_batch_kernel(const InitArgs* __restrict__ args,
+                                                                         const int32_t* __restrict__ blk, int k) {
+  INIT_BATCH_FIND();
+  score_init_mfma_wide_body<NV4, USCALE>(a, bx, const_cast<int*>(a.nrot) + 1);
+}
 
 // ---- the matrix-core search on pre-split half records ------------------------------------------------------------------
 // score_init_mfma_kernel spends most of its vector instructions turning a gathered f32 record into the f16 hi / lo
@@ -606,8 +657,8 @@ __global__ __launch_bounds__(256) void half_records_kernel(const float4* __restr
 // unrolled AHEAD + 1 times so that the buffers rotate by name (no register copies); the step count is padded to a multiple
 // of that, the padding steps read the zero guard record.
 template <bool USCALE, int AHEAD>
-__global__ __launch_bounds__(256) void score_init_half_kernel(InitArgs a, const uint4* __restrict__ rec16,
-                                                              int* __restrict__ inexact, int img, int rfs) {
+__device__ __forceinline__ void score_init_half_body(const InitArgs& a, int bx, const uint4* __restrict__ rec16,
+                                                     int* __restrict__ inexact, int img, int rfs) {
   constexpr int R = AHEAD + 1;
   // LDS: [4 rings][img] scan records {c0..c5, c6|0, sum c} as 8 x f16, row r and r + nb of an image hold scan row r; the
   // img - 2 nb >= R rows behind them stay zero (padding steps; the exact count is chosen on the host so that the four
@@ -617,7 +668,7 @@ __global__ __launch_bounds__(256) void score_init_half_kernel(InitArgs a, const 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = lane & 15, q = lane >> 4;
   // (an XCD-contiguous order of the workgroups and 1, 2 or 3 record loads in flight all run within 1 %: A/B on MI355X)
-  const int64_t slot = (int64_t)blockIdx.x * 64 + wave * 16 + col;
+  const int64_t slot = (int64_t)bx * 64 + wave * 16 + col;
   const bool valid = slot < a.n;
   const int64_t p = a.order ? (int64_t)a.order[valid ? slot : 0] : (valid ? slot : 0);
   const float scale = a.st[TDR_ST_SCALE * a.cap + p];
@@ -785,11 +836,25 @@ __global__ __launch_bounds__(256) void score_init_half_kernel(InitArgs a, const 
     a.res_flag[p] = bm < 0 ? 2.f : 1.f;
   }
 }
+template <bool USCALE, int AHEAD>
+__global__ __launch_bounds__(256) void score_init_half_kernel(InitArgs a, const uint4* __restrict__ rec16,
+                                                              int* __restrict__ inexact, int img, int rfs) {
+  score_init_half_body<USCALE, AHEAD>(a, (int)blockIdx.x, rec16, inexact, img, rfs);
+}
+// batched: the half records, the image stride and the scan record size belong to the map and the scan shape — the same
+// for every filter of the batch — and stay kernel arguments
+template <bool USCALE, int AHEAD>
+__global__ __launch_bounds__(256) void score_init_half_batch_kernel(const InitArgs* __restrict__ args,
+                                                                    const int32_t* __restrict__ blk, int k,
+                                                                    const uint4* __restrict__ rec16, int img, int rfs) {
+  INIT_BATCH_FIND();
+  score_init_half_body<USCALE, AHEAD>(a, bx, rec16, const_cast<int*>(a.nrot) + 1, img, rfs);
+}
 
 // candidate rotations of the search, generated exactly like the reference's loop (state_particle.cpp:197: float t,
 // double increment) together with their bin shifts (:124-128)
-__global__ void init_rot_kernel(int nb, int* __restrict__ shift, float* __restrict__ theta, int* __restrict__ nrot) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ __forceinline__ void init_rot_body(int nb, int* __restrict__ shift, float* __restrict__ theta,
+                                              int* __restrict__ nrot) {
   nrot[1] = 0;   // the "scan counts too large for f16" flag of score_init_mfma_kernel
   int k = 0;
   for (float t = 0; t < 2 * M_PI; t += 2 * M_PI / 40) {
@@ -800,21 +865,62 @@ __global__ void init_rot_kernel(int nb, int* __restrict__ shift, float* __restri
   }
   *nrot = k;
 }
+__global__ void init_rot_kernel(int nb, int* __restrict__ shift, float* __restrict__ theta, int* __restrict__ nrot) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  init_rot_body(nb, shift, theta, nrot);
+}
 
 // state_.theta = best_theta; state_.have_init = true (state_particle.cpp:205-206)
-__global__ void init_apply_kernel(const float* __restrict__ res_theta, const float* __restrict__ res_flag, int64_t n,
-                                  float* __restrict__ st, int64_t cap) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void init_apply_body(const float* __restrict__ res_theta, const float* __restrict__ res_flag,
+                                                int64_t n, float* __restrict__ st, int64_t cap, int64_t p) {
   if (p < n && res_flag[p] != 0.f) {
     st[TDR_ST_THETA * cap + p] = res_theta[p];
     st[TDR_ST_HAVE_INIT * cap + p] = 1.f;
   }
 }
+__global__ void init_apply_kernel(const float* __restrict__ res_theta, const float* __restrict__ res_flag, int64_t n,
+                                  float* __restrict__ st, int64_t cap) {
+  init_apply_body(res_theta, res_flag, n, st, cap, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
 // particles whose init search found no valid rotation keep best_cost = FLT_MAX (:193) -> weight 1/(FLT_MAX + reg)
+__device__ __forceinline__ void init_fixup_body(const float* __restrict__ res_flag, int64_t n, float regularization,
+                                                float* __restrict__ raw_w, int64_t p) {
+  if (p < n && res_flag[p] == 2.f) raw_w[p] = (float)(1. / (double)(3.402823466e+38f + regularization));
+}
 __global__ void init_fixup_kernel(const float* __restrict__ res_flag, int64_t n, float regularization,
                                   float* __restrict__ raw_w) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p < n && res_flag[p] == 2.f) raw_w[p] = (float)(1. / (double)(3.402823466e+38f + regularization));
+  init_fixup_body(res_flag, n, regularization, raw_w, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+// The small kernels of a batched search, over the same block table as the search kernels (64 particles per block).
+// prep: the rotation table of every filter, its f16 flag and its res_flag zeroed (standalone: init_rot_kernel + a memset
+// per filter); apply and fixup as above.  `fix` holds what InitArgs does not: the filters' raw weights.
+struct InitFixEntry { float* raw_w; float* st; };
+__global__ __launch_bounds__(64) void init_prep_batch_kernel(const InitArgs* __restrict__ args,
+                                                             const int32_t* __restrict__ blk, int k) {
+  const int b = (int)blockIdx.x + blk[0];
+  const int e = batch_find(k, b, [&](int i) { return blk[i]; });
+  const InitArgs a = args[e];
+  const int bx = b - blk[e];
+  const int64_t p = (int64_t)bx * 64 + threadIdx.x;
+  if (p < a.n) a.res_flag[p] = 0.f;
+  if (bx == 0 && threadIdx.x == 0)
+    init_rot_body(a.nb, const_cast<int*>(a.shift), const_cast<float*>(a.theta), const_cast<int*>(a.nrot));
+}
+__global__ __launch_bounds__(64) void init_apply_batch_kernel(const InitArgs* __restrict__ args,
+                                                              const InitFixEntry* __restrict__ fix,
+                                                              const int32_t* __restrict__ blk, int k) {
+  const int b = (int)blockIdx.x + blk[0];
+  const int e = batch_find(k, b, [&](int i) { return blk[i]; });
+  const InitArgs a = args[e];
+  init_apply_body(a.res_theta, a.res_flag, a.n, fix[e].st, a.cap, (int64_t)(b - blk[e]) * 64 + threadIdx.x);
+}
+__global__ __launch_bounds__(64) void init_fixup_batch_kernel(const InitArgs* __restrict__ args,
+                                                              const InitFixEntry* __restrict__ fix,
+                                                              const int32_t* __restrict__ blk, int k) {
+  const int b = (int)blockIdx.x + blk[0];
+  const int e = batch_find(k, b, [&](int i) { return blk[i]; });
+  const InitArgs a = args[e];
+  init_fixup_body(a.res_flag, a.n, a.fp.regularization, fix[e].raw_w, (int64_t)(b - blk[e]) * 64 + threadIdx.x);
 }
 
 static int g_init_mfma = 1;   // 0 = vector-unit search only (A/B and debugging)
@@ -894,50 +1000,95 @@ extern "C" int tdr_config_init_ahead(int v) {   // < 1: query only
   return g_init_ahead;
 }
 
-int tdr_score_init_search(const tdr_map_desc* map, const float* tab, const float* utab, const float* scan_pk, int nb,
-                          int nr, float res, const tdr_filter_params* fp, float* st, int64_t cap, int64_t n,
-                          int64_t n_total, const int32_t* order, float* res_flag, int64_t npad, hipStream_t s) {
+// ---- what the standalone and the batched search share on the host ------------------------------------------------------
+// The matrix-core pass of a search — ONE choice for both paths: the passes pick differently where candidates tie to
+// rounding (tdr.h, tdr_config_init_mfma), so a batched filter must take the pass its standalone call takes.
+int tdr_score_init_pass(const tdr_map_desc* map, int nb, int64_t n_total) {
   const int rf = map->rec_floats;
-  float* res_theta = res_flag + npad;
+  const bool ks = tdr_has_kslot(map->ncls, rf);
+  if (!init_use_mfma()) return TDR_INIT_PASS_VECTOR;
+  if ((rf == 4 || rf == 8) && map->ncls <= 7 && map->rec16 && tdr_map_rec16_bytes(map->ncls, map->rows, map->cols) != 0 &&
+      n_total >= g_rec16_min && (size_t)4 * (2 * nb + 20) * 16 + (size_t)4 * (nb + 8) * 8 <= 64 * 1024)
+    return TDR_INIT_PASS_HALF;
+  if (rf == 8 && (ks || map->ncls == 7)) return TDR_INIT_PASS_SPLIT;
+  if (rf == 12 || rf == 16) return TDR_INIT_PASS_WIDE;
+  return TDR_INIT_PASS_VECTOR;
+}
+// all class weights equal and positive: a common factor does not move the minimum (UNITW; the half records' `unitw`)
+static bool init_unit_weights(const tdr_filter_params* fp, int ncls) {
+  bool unitw = true;
+  for (int c = 1; c < ncls; c++) unitw &= fp->class_weights[c] == fp->class_weights[0];
+  return unitw && fp->class_weights[0] > 0.f;
+}
+// the arguments of one filter's search; its rotation table lives behind the result arrays:
+// [shift INIT_MAXROT][theta INIT_MAXROT][nrot][the "scan count does not fit f16" word]
+static InitArgs make_init_args(const tdr_map_desc* map, const float* tab, const float* utab, const float* scan_pk, int nb,
+                               int nr, float res, const tdr_filter_params* fp, const float* st, int64_t cap, int64_t n,
+                               const int32_t* order, float* res_flag, int64_t npad) {
   InitArgs ia;
+  float* res_theta = res_flag + npad;
   ia.rec = map->rec; ia.rows = map->rows; ia.cols = map->cols; ia.resolution = map->resolution;
   ia.tab = tab; ia.utab = utab; ia.scan_pk = scan_pk; ia.nb = nb; ia.nr = nr; ia.res = res;
   ia.st = st; ia.cap = cap; ia.n = n; ia.order = order; ia.fp = *fp; ia.gate = make_gate(fp, map);
   ia.P = (int64_t)nb * nr; ia.ncls = map->ncls; ia.res_flag = res_flag; ia.res_theta = res_theta;
-  // rotation table lives behind the result arrays: [shift INIT_MAXROT][theta INIT_MAXROT][nrot]
   int* d_shift = reinterpret_cast<int*>(res_theta + npad);
   float* d_theta = reinterpret_cast<float*>(d_shift + INIT_MAXROT);
-  int* d_nrot = reinterpret_cast<int*>(d_theta + INIT_MAXROT);
-  hipLaunchKernelGGL(init_rot_kernel, dim3(1), dim3(64), 0, s, nb, d_shift, d_theta, d_nrot);
+  ia.shift = d_shift; ia.theta = d_theta; ia.nrot = reinterpret_cast<int*>(d_theta + INIT_MAXROT);
+  ia.only_if = nullptr;
+  return ia;
+}
+// the pre-split half records of `map` for these class weights, into the map owner's scratch
+static int launch_half_records(const tdr_map_desc* map, const tdr_filter_params* fp, bool unitw, hipStream_t s) {
+  const int64_t ncells = (int64_t)(map->rows + 2) * (map->cols + 2);
+  const dim3 hgrid((unsigned)cdiv(ncells, 256)), hblock(256);
+  const float4* rec4 = reinterpret_cast<const float4*>(map->rec);
+  uint4* r16 = reinterpret_cast<uint4*>(map->rec16);
+  if (map->rec_floats == 4) hipLaunchKernelGGL((half_records_kernel<4>), hgrid, hblock, 0, s, rec4, ncells, unitw ? 1 : 0, *fp, map->ncls, r16);
+  else hipLaunchKernelGGL((half_records_kernel<8>), hgrid, hblock, 0, s, rec4, ncells, unitw ? 1 : 0, *fp, map->ncls, r16);
+  LAUNCH_CHECK("half_records");
+  return TDR_OK;
+}
+struct HalfShape { int ahead, img; size_t lds; };
+static HalfShape init_half_shape(int nb) {
+  HalfShape h;
+  h.ahead = g_init_ahead;
+  const int R = h.ahead + 1;
+  h.img = init_half_image_rows(nb, R);
+  h.lds = (size_t)4 * h.img * 16 + (size_t)4 * (nb + 2 * R) * 8;
+  return h;
+}
+// tdr_config_tuning("batch_init_search"): 1 = a filter that may hold a particle without a heading joins the batch of
+// tdr_batch_step, its search part of the batch's scoring stage (0, the default: it runs its standalone calls)
+static int g_batch_init_search = 0;
+extern "C" int tdr_config_batch_init_search(int v) {   // < 0: query only
+  if (v >= 0) g_batch_init_search = v ? 1 : 0;
+  return g_batch_init_search;
+}
+
+int tdr_score_init_search(const tdr_map_desc* map, const float* tab, const float* utab, const float* scan_pk, int nb,
+                          int nr, float res, const tdr_filter_params* fp, float* st, int64_t cap, int64_t n,
+                          int64_t n_total, const int32_t* order, float* res_flag, int64_t npad, hipStream_t s) {
+  const int rf = map->rec_floats;
+  InitArgs ia = make_init_args(map, tab, utab, scan_pk, nb, nr, res, fp, st, cap, n, order, res_flag, npad);
+  float* res_theta = ia.res_theta;
+  int* d_nrot = const_cast<int*>(ia.nrot);
+  hipLaunchKernelGGL(init_rot_kernel, dim3(1), dim3(64), 0, s, nb, const_cast<int*>(ia.shift), const_cast<float*>(ia.theta), d_nrot);
   LAUNCH_CHECK("init_rot");
-  ia.shift = d_shift; ia.theta = d_theta; ia.nrot = d_nrot;
   HIP_TRY(hipMemsetAsync(res_flag, 0, sizeof(float) * (size_t)n, s));
   dim3 grid((unsigned)cdiv(n, 64)), block(64 * INIT_WAVES);
   const size_t lds = TDR_INIT_SCAN_LDS ? (size_t)2 * nb * rf * 4 : 0;
   const bool ks = tdr_has_kslot(map->ncls, rf), us = utab != nullptr;
-  ia.only_if = nullptr;
-  bool unitw = true;
-  for (int c = 1; c < map->ncls; c++) unitw &= fp->class_weights[c] == fp->class_weights[0];
-  unitw &= fp->class_weights[0] > 0.f;
+  const bool unitw = init_unit_weights(fp, map->ncls);
   int* d_inexact = d_nrot + 1;
-  const bool half_path = (rf == 4 || rf == 8) && map->ncls <= 7 && init_use_mfma() && map->rec16 &&
-                         tdr_map_rec16_bytes(map->ncls, map->rows, map->cols) != 0 && n_total >= g_rec16_min &&
-                         (size_t)4 * (2 * nb + 20) * 16 + (size_t)4 * (nb + 8) * 8 <= 64 * 1024;
-  if (half_path) {
+  const int pass = tdr_score_init_pass(map, nb, n_total);
+  if (pass == TDR_INIT_PASS_HALF) {
     // matrix-core pass on pre-split half records (weights folded in), built into the map owner's scratch first; the
     // vector kernel below then runs only if a scan count did not fit f16
-    const int64_t ncells = (int64_t)(map->rows + 2) * (map->cols + 2);
-    const dim3 hgrid((unsigned)cdiv(ncells, 256)), hblock(256);
-    const float4* rec4 = reinterpret_cast<const float4*>(map->rec);
-    uint4* r16 = reinterpret_cast<uint4*>(map->rec16);
-    if (rf == 4) hipLaunchKernelGGL((half_records_kernel<4>), hgrid, hblock, 0, s, rec4, ncells, unitw ? 1 : 0, *fp, map->ncls, r16);
-    else hipLaunchKernelGGL((half_records_kernel<8>), hgrid, hblock, 0, s, rec4, ncells, unitw ? 1 : 0, *fp, map->ncls, r16);
-    LAUNCH_CHECK("half_records");
-    const int ahead = g_init_ahead;
-    const int R = ahead + 1;
-    const int img = init_half_image_rows(nb, R);
-    const size_t ldsh = (size_t)4 * img * 16 + (size_t)4 * (nb + 2 * R) * 8;
-    const uint4* r16c = r16;
+    if (int rc = launch_half_records(map, fp, unitw, s)) return rc;
+    const HalfShape hs = init_half_shape(nb);
+    const int ahead = hs.ahead, img = hs.img;
+    const size_t ldsh = hs.lds;
+    const uint4* r16c = reinterpret_cast<const uint4*>(map->rec16);
     with_flags([&](auto US) {
       constexpr bool U = decltype(US)::value;
       auto launch = [&](auto kfn) { hipLaunchKernelGGL(kfn, grid, dim3(256), ldsh, s, ia, r16c, d_inexact, img, rf); };
@@ -948,7 +1099,7 @@ int tdr_score_init_search(const tdr_map_desc* map, const float* tab, const float
     }, us);
     LAUNCH_CHECK("score_init_half");
     ia.only_if = d_inexact;
-  } else if (rf == 8 && (ks || map->ncls == 7) && init_use_mfma()) {
+  } else if (pass == TDR_INIT_PASS_SPLIT) {
     // matrix-core pass splitting the f32 records per sample (small filters, maps without the scratch); the vector
     // kernel below then runs only if a scan count did not fit f16
     const size_t lds16 = ((size_t)2 * nb + 1) * 16;
@@ -959,7 +1110,7 @@ int tdr_score_init_search(const tdr_map_desc* map, const float* tab, const float
     }, us, unitw, !ks);
     LAUNCH_CHECK("score_init_mfma");
     ia.only_if = d_inexact;
-  } else if ((rf == 12 || rf == 16) && init_use_mfma()) {
+  } else if (pass == TDR_INIT_PASS_WIDE) {
     // 8-15 classes: two groups of 8 slots per sample (score_init_mfma_wide_kernel)
     const size_t lds16 = ((size_t)2 * nb + 1) * 2 * 16;
     with_flags([&](auto US, auto R16) {
@@ -982,6 +1133,168 @@ int tdr_score_init_search(const tdr_map_desc* map, const float* tab, const float
   hipLaunchKernelGGL(init_apply_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, (const float*)res_theta,
                      (const float*)res_flag, n, st, cap);
   LAUNCH_CHECK("init_apply");
+  return TDR_OK;
+}
+// ---- the searches of a batch (tdr_batch_step with "batch_init_search") -------------------------------------------------
+// The filters are sorted into RUNS of one matrix-core pass each — and, for the half-record pass, one set of half records:
+// the records fold the class weights in unless all are equal and positive, so half-path filters are grouped by that flag
+// and, where it is not set, by the weight vector.  Per run: (the group's half_records_kernel,) one launch per scale mode
+// present.  Then one vector-kernel launch per scale mode over the whole table — every filter reads its OWN f16 flag, so a
+// filter whose scan holds a count above 2048 sends only itself through the vector kernel — and one apply.
+namespace {
+struct InitRun { int32_t first, count, pass, unitw, us_mask; };
+struct BatchInitHdr { int32_t k, blocks, nruns, us_mask; };
+struct BatchInitLayout { size_t runs, args, fix, blk, total; };
+BatchInitLayout batch_init_layout(int k) {
+  auto up = [](size_t x) { return (x + 63) / 64 * 64; };
+  BatchInitLayout L;
+  L.runs = up(sizeof(BatchInitHdr));
+  L.args = L.runs + up(sizeof(InitRun) * k);
+  L.fix = L.args + up(sizeof(InitArgs) * k);
+  L.blk = L.fix + up(sizeof(InitFixEntry) * k);
+  L.total = L.blk + up(sizeof(int32_t) * (k + 1));
+  return L;
+}
+}  // namespace
+size_t tdr_batch_init_stage_bytes(int k) { return k < 1 ? 0 : batch_init_layout(k).total; }
+int tdr_batch_init_build(const tdr_map_desc* map, const float* tab, int nb, int nr, int k, const TdrBatchInitIn* in,
+                         void* host_stage) {
+  if (!map || !tab || !in || !host_stage || k < 1) return fail(TDR_ERR_ARG, "batch_init: bad arguments");
+  const BatchInitLayout Lo = batch_init_layout(k);
+  char* base = static_cast<char*>(host_stage);
+  BatchInitHdr& h = *reinterpret_cast<BatchInitHdr*>(base);
+  InitRun* runs = reinterpret_cast<InitRun*>(base + Lo.runs);
+  InitArgs* args = reinterpret_cast<InitArgs*>(base + Lo.args);
+  InitFixEntry* fix = reinterpret_cast<InitFixEntry*>(base + Lo.fix);
+  int32_t* blk = reinterpret_cast<int32_t*>(base + Lo.blk);
+  // sort key of a filter: pass, unit-weight flag (the wide pass has no such form), half-record group
+  struct Key { int pass, unitw, group, idx; };
+  std::vector<Key> keys((size_t)k);
+  std::vector<int> group_owner;   // a filter of every half-record group with weights folded in
+  for (int i = 0; i < k; i++) {
+    const TdrBatchInitIn& x = in[i];
+    if (!x.fp || !x.st || !x.res_flag || !x.raw_w || x.n < 1 || x.cap < x.n) return fail(TDR_ERR_ARG, "batch_init: filter %d", i);
+    Key q{tdr_score_init_pass(map, nb, x.n), 0, 0, i};
+    if (q.pass == TDR_INIT_PASS_HALF || q.pass == TDR_INIT_PASS_SPLIT) q.unitw = init_unit_weights(x.fp, map->ncls) ? 1 : 0;
+    if (q.pass == TDR_INIT_PASS_HALF && !q.unitw) {
+      size_t g = 0;
+      for (; g < group_owner.size(); g++)
+        if (std::memcmp(in[group_owner[g]].fp->class_weights, x.fp->class_weights, sizeof(float) * (size_t)std::min(map->ncls, 7)) == 0) break;
+      if (g == group_owner.size()) group_owner.push_back(i);
+      q.group = (int)g;
+    }
+    keys[i] = q;
+  }
+  std::stable_sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) {
+    return a.pass != b.pass ? a.pass < b.pass : a.unitw != b.unitw ? a.unitw < b.unitw : a.group < b.group;
+  });
+  h = BatchInitHdr{k, 0, 0, 0};
+  for (int j = 0; j < k; j++) {
+    const Key& q = keys[j];
+    const TdrBatchInitIn& x = in[q.idx];
+    InitArgs a = make_init_args(map, tab, x.utab, x.scan_pk, nb, nr, x.res, x.fp, x.st, x.cap, x.n, nullptr, x.res_flag, x.npad);
+    if (q.pass != TDR_INIT_PASS_VECTOR) a.only_if = a.nrot + 1;   // the vector kernel: only what the matrix-core pass could not take
+    args[j] = a;
+    fix[j] = InitFixEntry{x.raw_w, x.st};
+    blk[j] = h.blocks;
+    h.blocks += (int32_t)cdiv(x.n, 64);
+    const int us_bit = x.utab ? 2 : 1;
+    h.us_mask |= us_bit;
+    const bool same = j > 0 && keys[j - 1].pass == q.pass && keys[j - 1].unitw == q.unitw && keys[j - 1].group == q.group;
+    if (!same) runs[h.nruns++] = InitRun{j, 0, q.pass, q.unitw, 0};
+    runs[h.nruns - 1].count++;
+    runs[h.nruns - 1].us_mask |= us_bit;
+  }
+  blk[k] = h.blocks;
+  return TDR_OK;
+}
+int tdr_batch_init_launch(const tdr_map_desc* map, int nb, int nr, const void* host_stage, const void* dev_stage,
+                          hipStream_t s) {
+  if (!map || !host_stage || !dev_stage) return fail(TDR_ERR_ARG, "batch_init: bad arguments");
+  const BatchInitHdr& h = *static_cast<const BatchInitHdr*>(host_stage);
+  const int k = h.k;
+  const BatchInitLayout Lo = batch_init_layout(k);
+  const char* hb = static_cast<const char*>(host_stage);
+  const char* d = static_cast<const char*>(dev_stage);
+  const InitRun* runs = reinterpret_cast<const InitRun*>(hb + Lo.runs);
+  const InitArgs* hargs = reinterpret_cast<const InitArgs*>(hb + Lo.args);
+  const int32_t* hblk = reinterpret_cast<const int32_t*>(hb + Lo.blk);
+  const InitArgs* args = reinterpret_cast<const InitArgs*>(d + Lo.args);
+  const InitFixEntry* fix = reinterpret_cast<const InitFixEntry*>(d + Lo.fix);
+  const int32_t* blk = reinterpret_cast<const int32_t*>(d + Lo.blk);
+  const int rf = map->rec_floats;
+  const bool ks = tdr_has_kslot(map->ncls, rf);
+  const dim3 all((unsigned)h.blocks);
+  hipLaunchKernelGGL(init_prep_batch_kernel, all, dim3(64), 0, s, args, blk, k);
+  LAUNCH_CHECK("batch_init_prep");
+  for (int r = 0; r < h.nruns; r++) {
+    const InitRun& R = runs[r];
+    if (R.pass == TDR_INIT_PASS_VECTOR) continue;
+    const dim3 grid((unsigned)(hblk[R.first + R.count] - hblk[R.first]));
+    const InitArgs* ra = args + R.first;
+    const int32_t* rb = blk + R.first;
+    if (R.pass == TDR_INIT_PASS_HALF)
+      if (int rc = launch_half_records(map, &hargs[R.first].fp, R.unitw != 0, s)) return rc;
+    for (int us = 1; us >= 0; us--) {   // the filters with a uniform-scale table, then the others: one instantiation each
+      if (!(R.us_mask & (us ? 2 : 1))) continue;
+      if (R.pass == TDR_INIT_PASS_HALF) {
+        const HalfShape hs = init_half_shape(nb);
+        const uint4* r16c = reinterpret_cast<const uint4*>(map->rec16);
+        with_flags([&](auto US) {
+          constexpr bool U = decltype(US)::value;
+          auto launch = [&](auto kfn) { hipLaunchKernelGGL(kfn, grid, dim3(256), hs.lds, s, ra, rb, R.count, r16c, hs.img, rf); };
+          if (hs.ahead == 1) launch(score_init_half_batch_kernel<U, 1>);
+          else if (hs.ahead == 2) launch(score_init_half_batch_kernel<U, 2>);
+          else launch(score_init_half_batch_kernel<U, 3>);
+          return TDR_OK;
+        }, us != 0);
+        LAUNCH_CHECK("batch_score_init_half");
+      } else if (R.pass == TDR_INIT_PASS_SPLIT) {
+        const size_t lds16 = ((size_t)2 * nb + 1) * 16;
+        with_flags([&](auto US, auto UW, auto SV) {
+          hipLaunchKernelGGL((score_init_mfma_batch_kernel<decltype(US)::value, decltype(UW)::value, decltype(SV)::value>), grid,
+                             dim3(256), lds16, s, ra, rb, R.count);
+          return TDR_OK;
+        }, us != 0, R.unitw != 0, !ks);
+        LAUNCH_CHECK("batch_score_init_mfma");
+      } else {
+        const size_t lds16 = ((size_t)2 * nb + 1) * 2 * 16;
+        with_flags([&](auto US, auto R16) {
+          hipLaunchKernelGGL((score_init_mfma_wide_batch_kernel<decltype(R16)::value ? 4 : 3, decltype(US)::value>), grid,
+                             dim3(256), lds16, s, ra, rb, R.count);
+          return TDR_OK;
+        }, us != 0, rf == 16);
+        LAUNCH_CHECK("batch_score_init_mfma_wide");
+      }
+    }
+  }
+  const size_t lds = TDR_INIT_SCAN_LDS ? (size_t)2 * nb * rf * 4 : 0;
+  for (int us = 1; us >= 0; us--) {
+    if (!(h.us_mask & (us ? 2 : 1))) continue;
+    if (int rc = with_nv4(rf, "batch_init", [&](auto N) {
+          return with_flags([&](auto KS, auto US) {
+            hipLaunchKernelGGL((score_init_batch_kernel<decltype(N)::value, decltype(KS)::value, decltype(US)::value>), all,
+                               dim3(64 * INIT_WAVES), lds, s, args, blk, k);
+            return TDR_OK;
+          }, ks, us != 0);
+        }))
+      return rc;
+    LAUNCH_CHECK("batch_score_init");
+  }
+  hipLaunchKernelGGL(init_apply_batch_kernel, all, dim3(64), 0, s, args, fix, blk, k);
+  LAUNCH_CHECK("batch_init_apply");
+  (void)nr;
+  return TDR_OK;
+}
+int tdr_batch_init_fixup(const void* host_stage, const void* dev_stage, hipStream_t s) {
+  if (!host_stage || !dev_stage) return fail(TDR_ERR_ARG, "batch_init: bad arguments");
+  const BatchInitHdr& h = *static_cast<const BatchInitHdr*>(host_stage);
+  const BatchInitLayout Lo = batch_init_layout(h.k);
+  const char* d = static_cast<const char*>(dev_stage);
+  hipLaunchKernelGGL(init_fixup_batch_kernel, dim3((unsigned)h.blocks), dim3(64), 0, s,
+                     reinterpret_cast<const InitArgs*>(d + Lo.args), reinterpret_cast<const InitFixEntry*>(d + Lo.fix),
+                     reinterpret_cast<const int32_t*>(d + Lo.blk), h.k);
+  LAUNCH_CHECK("batch_init_fixup");
   return TDR_OK;
 }
 int tdr_score_init_fixup(const float* res_flag, int64_t n, float regularization, float* raw_w, hipStream_t s) {
