@@ -325,6 +325,34 @@ size_t tdr_score_cart_workspace_floats(int ncls, int rows, int cols, int64_t n, 
 int tdr_k_score_cart(const tdr_map_desc* map, const float* scan_pk, int rows, int cols, float res,
                      const tdr_filter_params* fp, float* st, int64_t cap, int64_t n, int64_t n_total,
                      const int32_t* perm, float* raw_w, float* workspace, void* stream);
+/* The HEADING SEARCH of the Cartesian filter (csrc/tdr_score_cart_init.hip): what StateParticle::computeWeight does for a
+ * particle with have_init == 0 (src/state_particle.cpp:195-206), with the Cartesian cost above in place of
+ * getCostForRot(..., t).  DEFINITION:
+ *  - the candidates are the reference's float loop `for (float t = 0; t < 2*M_PI; t += 2*M_PI/40)` as written (float t,
+ *    double increment): the table the polar search uses;
+ *  - the cost of candidate t is the Cartesian cost of that particle with theta = t, exactly as tdr_k_score_cart defines it
+ *    (a window less than half known gives NaN);
+ *  - the first candidate whose cost is strictly smaller than all earlier ones wins; a NaN cost is never chosen;
+ *  - afterwards theta = the best t (0 when no candidate was finite) and have_init = 1;
+ *  - there are no gates, and particles that already have a heading are not touched: their states stay bit for bit.
+ * The search only CHOOSES headings: the weights are what a following tdr_k_score_cart gives at those headings (it scores
+ * every particle, as the polar path does after its search).
+ * It is composed of a list of the particles without a heading (one small launch; made again in the order of
+ * tdr_k_locality_order_pose when it spans several chunks, so that a chunk is a neighbourhood of the map), and per chunk of
+ * tdr_config_tuning("cart_init_chunk") listed particles: their candidate states, their order by pose
+ * (tdr_k_locality_order_pose at theta_radius = (rows + cols) / 16, what the filters pass as `perm`), ONE tdr_k_score_cart
+ * launch over them — the form tdr_config_shift_uniform / tdr_config_cart_skip select, the partial-sum split of n_total, so a
+ * candidate's weight is the bits the regular launch gives that particle at that heading and the result does not depend on
+ * the chunk size — and a selection.  Nothing is allocated.  The launcher WAITS for `stream` ONCE, to read the list's length: that many chunks are
+ * launched, and a call that finds no particle without a heading costs the list launch and no scoring launch.  A caller that
+ * knows every particle has a heading does not call it.  Arguments as tdr_k_score_cart (n_total <= 0 means n); errors
+ * (TDR_ERR_ARG before any device work): null map / scan / states / workspace, rows < 1, cols < 1, n < 0, n > cap.
+ * workspace: tdr_score_cart_init_workspace_floats floats — the list, one chunk's candidate states, raw weights and order,
+ * and tdr_score_cart_workspace_floats for one chunk's candidates — read with the cart_init_chunk in force at the call. */
+size_t tdr_score_cart_init_workspace_floats(int ncls, int rows, int cols, int64_t n, int64_t n_total);
+int tdr_k_score_cart_init(const tdr_map_desc* map, const float* scan_pk, int rows, int cols, float res,
+                          const tdr_filter_params* fp, float* st, int64_t cap, int64_t n, int64_t n_total,
+                          float* workspace, void* stream);
 
 /* ---- StateParticle::propagate for all particles (src/state_particle.cpp:57-78 via particle_filter.cpp:86-92) -- */
 /* z4: optional DEVICE array [n][4] of standard normals {theta, dx, dy, scale} in the reference's consumption
@@ -582,7 +610,9 @@ int tdr_profile_variants(int64_t out[16]);
  *   "init_device"      0: tdr_filter_initialize_particles keeps the serial host loop; 1 (default): a filter that owns its
  *                      generator in parity mode initialises on the device (tdr_k_init_particles — the same states)
  *   "init_window_words" words of the generator's stream per window of tdr_k_init_particles (a multiple of 2048, 2048 to
- *                      2^22; default 2^21; same states) */
+ *                      2^22; default 2^21; same states)
+ *   "cart_init_chunk"  particles without a heading whose candidates one scoring launch of tdr_k_score_cart_init covers
+ *                      (>= 1; default 4096: DESIGN.md 5.5; bounds its workspace; same results) */
 int64_t tdr_config_tuning(const char* name, int64_t value);
 /* Device self-test of the scoring kernels: a tiny fixed problem (160 x 160 map, 6 classes, 512 particles) scored by every
  * kernel the library has for it.  The integer-form kernels run generated, hand-scheduled assembly; their sums are exact, so
@@ -662,6 +692,11 @@ int tdr_map_patch_labels(tdr_map* m, const uint8_t* patch, int y0, int x0, int h
 int tdr_map_get_desc(const tdr_map* m, tdr_map_desc* out);
 int tdr_map_sample_pts_polar(tdr_map* m, int nb, int nr, float ang_res);                 /* top_down_map_polar.cpp:7-19 */
 int tdr_map_polar_shape(const tdr_map* m, int* nb, int* nr);   /* the shape of the last samplePtsPolar (0, 0 before) */
+/* The Cartesian window (rows = y, cols = x) a Cartesian filter scores against (tdr_filter_create_cart): the shape of the
+ * images TopDownMap::getLocalMap is asked for; Python's TopDownMap.setWindow.  rows, cols >= 1.  The shape stays with the
+ * handle across map updates.  tdr_map_window_shape: the last one set (0, 0 before). */
+int tdr_map_set_window(tdr_map* m, int rows, int cols);
+int tdr_map_window_shape(const tdr_map* m, int* rows, int* cols);
 int tdr_map_info(const tdr_map* m, int* ncls, int* rows, int* cols, float* resolution, int* have_map);
 int tdr_map_center(const tdr_map* m, int* center_x, int* center_y);                      /* mapCenter(), top_down_map.h:72 */
 /* getLocalMap (polar != 0: top_down_map_polar.cpp:21-53 with scale_or_rot = scale and the table of
@@ -819,6 +854,19 @@ int64_t tdr_filter_num_local(const tdr_filter* f);
  * seed != 0: every draw comes from std::mt19937(seed) in the reference's order, propagate's 4N normals included (host
  * code, ~35 ns per draw) — the mode the parity tests use.  tdr_filter_configure changes the mode afterwards. */
 int tdr_filter_create(tdr_map* map, int n_max, const tdr_filter_params* fp, uint32_t seed, tdr_filter** out);
+/* A filter whose scoring stage is the CARTESIAN one (tdr_k_score_cart: BASELINE config 4).  The map needs a window
+ * (tdr_map_set_window), else TDR_ERR_ARG.  It is an ordinary tdr_filter:
+ *  - tdr_filter_update / tdr_filter_compute_weights read HOST [ncls][rows*cols] column-major images of the window's shape,
+ *    or a renderer's last CARTESIAN render of that shape (tdr_renderer_render with polar == 0); they order the particles
+ *    with tdr_k_locality_order_pose at theta_radius = (rows + cols) / 16, run the heading search
+ *    (tdr_k_score_cart_init) while a particle may lack a heading — a cold start, init_pos_deg_theta = inf: the first
+ *    update — then tdr_k_score_cart, and continue through the same statistics, running sum, resample, max-likelihood and
+ *    pose-statistics stages as a polar filter;
+ *  - propagate, the random stream, particle initialisation, set_states / get_states, mean_cov, freeze-scale, GMM /
+ *    adaptive count and map updates work as on a polar filter; tdr_batch_pose accepts it (it does not score).
+ * Refused with TDR_ERR_ARG, the filter unchanged: tdr_filter_update_geo (there is no Cartesian geometric cost), a Cartesian
+ * filter in tdr_batch_step, and sharding (there is no tdr_filter_create_cart_sharded). */
+int tdr_filter_create_cart(tdr_map* map, int n_max, const tdr_filter_params* fp, uint32_t seed, tdr_filter** out);
 void tdr_filter_destroy(tdr_filter* f);
 /* parity_rng: propagate consumes host std::mt19937 normals in the reference's order; 0 = device RNG.
  * locality_every: > 0 processes particles in Morton order of their map position (default 1; results unchanged). */

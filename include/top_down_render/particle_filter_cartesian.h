@@ -1,0 +1,131 @@
+// ParticleFilterCartesian — a ParticleFilter over a Cartesian TopDownMap (tdr_filter_create_cart, include/tdr.h): the
+// particles are scored against the rotated rectangular window of TopDownMap::getLocalMap (BASELINE config 4) instead of
+// the polar table.  The reference has no such class: its StateParticle only reaches the polar overloads
+// (state_particle.h:61).  The method names and argument meanings are ParticleFilter's.
+//
+// A class of its own rather than a constructor overload of ParticleFilter: that class keeps a TopDownMapPolar* (map(),
+// which ParticleFilterBatch reads, and update()'s check against polarShape()), an overload taking the base class would make
+// `ParticleFilter(N, nullptr, ...)` ambiguous, and what a Cartesian filter refuses — the geometric cost, batches, sharding —
+// is simply absent here instead of failing at run time.
+#ifndef PARTICLE_FILTER_CARTESIAN_H_
+#define PARTICLE_FILTER_CARTESIAN_H_
+
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "top_down_render/scan_renderer.h"
+#include "top_down_render/state_particle.h"
+#include "top_down_render/top_down_map.h"
+
+class ParticleFilterCartesian {
+ public:
+  // map: a TopDownMap whose window is set (TopDownMap::setWindow); seed as ParticleFilter's
+  ParticleFilterCartesian(int N, TopDownMap* map, FilterParams& params, uint32_t seed = 0) : map_(map), params_(params) {
+    if (!map) throw std::invalid_argument("ParticleFilterCartesian: null map");
+    tdr_filter_params c = to_tdr_params(params_, map_->numClasses());
+    if (tdr_filter_create_cart(map_->handle(), N, &c, seed, &f_) != TDR_OK) fail("ParticleFilterCartesian");
+    if (map_->haveMap() && tdr_filter_initialize_particles(f_) != TDR_OK) {   // particle_filter.cpp:14-16
+      const std::string msg = std::string("initializeParticles: ") + tdr_last_error();
+      tdr_filter_destroy(f_);   // the destructor does not run for a constructor that throws
+      throw std::runtime_error(msg);
+    }
+  }
+  ~ParticleFilterCartesian() { tdr_filter_destroy(f_); }
+  ParticleFilterCartesian(const ParticleFilterCartesian&) = delete;
+  ParticleFilterCartesian& operator=(const ParticleFilterCartesian&) = delete;
+
+  void propagate(Eigen::Vector2f& trans, float omega) { check(tdr_filter_propagate(f_, trans[0], trans[1], omega), "propagate"); }
+  // top_down_scan: one image of the window's shape per class (ScanRenderer::renderSemanticTopDown's output).  The first
+  // update of a cold-started filter chooses every particle's heading among the reference's 40 candidates first.  Wrong
+  // sizes: nothing is scored, the reason is left in tdr_last_error() (like ParticleFilter::update).
+  void update(std::vector<Eigen::ArrayXXf>& top_down_scan, float res) {
+    std::vector<float> buf;
+    if (pack(top_down_scan, buf)) check(tdr_filter_update(f_, buf.data(), nullptr, res, target_count_), "update");
+  }
+  // ... against the renderer's last (Cartesian) render, without copying the images through the host
+  void update(const ScanRenderer& renderer, float res) {
+    check(tdr_filter_update(f_, nullptr, renderer.handle(), res, target_count_), "update");
+  }
+  // StateParticle::computeWeight for every particle: raw weights only (rawWeights), no statistics, no resampling
+  void computeWeight(std::vector<Eigen::ArrayXXf>& top_down_scan, float res) {
+    std::vector<float> buf;
+    if (pack(top_down_scan, buf)) check(tdr_filter_compute_weights(f_, buf.data(), nullptr, res), "computeWeight");
+  }
+  void computeWeight(const ScanRenderer& renderer, float res) {
+    check(tdr_filter_compute_weights(f_, nullptr, renderer.handle(), res), "computeWeight");
+  }
+  void computeCov(Eigen::Matrix4f& cov) { stat(1, nullptr, &cov); }
+  void maxLikelihood(Eigen::Vector4f& state) { stat(1, &state, nullptr); }
+  void computeMeanCov(Eigen::Matrix4f& cov) { stat(0, nullptr, &cov); }
+  void meanLikelihood(Eigen::Vector4f& state) { stat(0, &state, nullptr); }
+  void freezeScale() { check(tdr_filter_freeze_scale(f_), "freezeScale"); }
+  bool isScaleFrozen() { return tdr_filter_is_scale_frozen(f_) != 0; }
+  float scale() const { return tdr_filter_scale(f_); }
+  int numParticles() const { return (int)tdr_filter_num_particles(f_); }
+  void computeGMM() { check(tdr_filter_compute_gmm(f_), "computeGMM"); }
+  void setTargetCount(int n) { target_count_ = n; }
+  void configure(bool parity_rng, int locality_every) { check(tdr_filter_configure(f_, parity_rng, locality_every), "configure"); }
+  void updateMap(const uint8_t* label_img, int img_h, int img_w, const std::vector<int>& flatten_lut,
+                 const Eigen::Vector2i& map_center) {
+    std::vector<int32_t> lut(flatten_lut.begin(), flatten_lut.end());
+    check(tdr_filter_update_map_labels(f_, label_img, img_h, img_w, lut.data(), (int)lut.size(), map_->numClasses(),
+                                       map_->resolution(), map_center[0], map_center[1]), "updateMap");
+  }
+  tdr_filter* handle() const { return f_; }
+  TopDownMap* map() const { return map_; }
+  void setStates(const std::vector<State>& s) {
+    check(tdr_filter_set_states(f_, reinterpret_cast<const tdr_state*>(s.data()), (int64_t)s.size()), "setStates");
+  }
+  std::vector<State> states() {
+    std::vector<State> s((size_t)tdr_filter_num_local(f_));
+    if (!s.empty()) check(tdr_filter_get_states(f_, reinterpret_cast<tdr_state*>(s.data()), (int64_t)s.size()), "states");
+    return s;
+  }
+  std::vector<float> weights(int n) {
+    std::vector<float> w((size_t)n);
+    if (n > 0) check(tdr_filter_get_weights(f_, w.data(), n), "weights");
+    return w;
+  }
+  std::vector<float> rawWeights(int n) {
+    std::vector<float> w((size_t)n);
+    if (n > 0) check(tdr_filter_get_raw_weights(f_, w.data(), n), "rawWeights");
+    return w;
+  }
+  std::vector<int32_t> resampleIndices() {
+    std::vector<int32_t> idx((size_t)tdr_filter_num_local(f_));
+    if (!idx.empty()) check(tdr_filter_get_resample_indices(f_, idx.data(), (int64_t)idx.size()), "resampleIndices");
+    return idx;
+  }
+
+ private:
+  // the images as one [ncls][rows*cols] array; false (and the reason in tdr_last_error()) when they cannot be used
+  bool pack(const std::vector<Eigen::ArrayXXf>& scan, std::vector<float>& buf) {
+    if (scan.empty() || numParticles() == 0) return false;
+    const int ncls = map_->numClasses();
+    const Eigen::Vector2i shape = map_->windowShape();
+    if ((int)scan.size() < ncls) return tdr_set_error(TDR_ERR_ARG, "update: fewer scan images than map classes"), false;
+    const size_t P = (size_t)shape[0] * shape[1];
+    for (int c = 0; c < ncls; c++)
+      if (scan[c].rows() != shape[0] || scan[c].cols() != shape[1])
+        return tdr_set_error(TDR_ERR_ARG, "update: a scan image does not have the shape given to setWindow"), false;
+    buf.resize(P * ncls);
+    for (int c = 0; c < ncls; c++) std::memcpy(buf.data() + P * c, scan[c].data(), P * sizeof(float));
+    return true;
+  }
+  void stat(int about_max, Eigen::Vector4f* state, Eigen::Matrix4f* cov) {
+    float s[4], c[16];
+    check(tdr_filter_mean_cov(f_, about_max, s, c), "statistics");
+    if (state) for (int i = 0; i < 4; i++) (*state)[i] = s[i];
+    if (cov) for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) (*cov)(i, j) = c[4 * i + j];
+  }
+  void check(int rc, const char* what) { if (rc != TDR_OK) fail(what); }
+  [[noreturn]] void fail(const char* what) { throw std::runtime_error(std::string(what) + ": " + tdr_last_error()); }
+
+  int target_count_ = -1;
+  TopDownMap* map_;
+  FilterParams params_;
+  tdr_filter* f_ = nullptr;
+};
+
+#endif  // PARTICLE_FILTER_CARTESIAN_H_

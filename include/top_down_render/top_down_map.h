@@ -188,6 +188,16 @@ class TopDownMap {
     if (dists.size() < 1) return;
     local_geo_map(0, center, rot, res, (int)dists[0].rows(), (int)dists[0].cols(), dists);
   }
+  // Extension: the window shape (rows = y, cols = x) a Cartesian filter scores against (ParticleFilterCartesian,
+  // particle_filter_cartesian.h; BASELINE config 4) — the sizes getLocalMap reads off the caller's arrays, fixed for the filter.
+  void setWindow(int rows, int cols) {
+    if (tdr_map_set_window(m_, rows, cols) != TDR_OK) throw std::invalid_argument(std::string("setWindow: ") + tdr_last_error());
+  }
+  Eigen::Vector2i windowShape() const {   // (rows, cols) of the last setWindow; (0, 0) before
+    int rows = 0, cols = 0;
+    tdr_map_window_shape(m_, &rows, &cols);
+    return Eigen::Vector2i(rows, cols);
+  }
   void getClassesAtPoint(const Eigen::Vector2f& center, std::vector<int>& classes) {      // :172-175
     getClassesAtPoint(Eigen::Vector2i((int)(center[0] / params_.resolution), (int)(center[1] / params_.resolution)), classes);
   }

@@ -152,6 +152,9 @@ SIGNATURES = {
     "tdr_score_cart_workspace_floats": (C.c_size_t, [_i, _i, _i, _i64, _i64]),
     "tdr_k_score_cart": (_i, [C.POINTER(MapDescC), _vp, _i, _i, _f, C.POINTER(FilterParamsC), _vp, _i64, _i64, _i64,
                               _vp, _vp, _vp, _vp]),
+    "tdr_score_cart_init_workspace_floats": (C.c_size_t, [_i, _i, _i, _i64, _i64]),
+    "tdr_k_score_cart_init": (_i, [C.POINTER(MapDescC), _vp, _i, _i, _f, C.POINTER(FilterParamsC), _vp, _i64, _i64, _i64,
+                                   _vp, _vp]),
     "tdr_k_propagate": (_i, [_vp, _i64, _i64, _vp, _f, _f, _f, _i, _f, _f, _vp, _u64, _u64, _i64, _vp]),
     "tdr_rng_create": (_vp, [_u32]),
     "tdr_rng_destroy": (None, [_vp]),
@@ -212,6 +215,8 @@ SIGNATURES = {
     "tdr_filter_patch_map_labels": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i64)]),
     "tdr_map_sample_pts_polar": (_i, [_vp, _i, _i, _f]),
     "tdr_map_polar_shape": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "tdr_map_set_window": (_i, [_vp, _i, _i]),
+    "tdr_map_window_shape": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "tdr_map_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_f), C.POINTER(_i)]),
     "tdr_map_center": (_i, [_vp, _vp, _vp]),
     "tdr_map_local_map": (_i, [_vp, _i, _f, _f, _f, _f, _i, _i, _vp, _vp]),
@@ -228,6 +233,7 @@ SIGNATURES = {
     "tdr_renderer_render": (_i, [_vp, _i, _vp, _i, _i, _i64, _f, _f, _i, _i, _i, _vp]),
     "tdr_renderer_render_geo": (_i, [_vp, _i, _vp, _i, _i64, _i64, _f, _f, _i, _i, _vp]),
     "tdr_filter_create": (_i, [_vp, _i, C.POINTER(FilterParamsC), _u32, C.POINTER(_vp)]),
+    "tdr_filter_create_cart": (_i, [_vp, _i, C.POINTER(FilterParamsC), _u32, C.POINTER(_vp)]),
     "tdr_filter_destroy": (None, [_vp]),
     "tdr_filter_configure": (_i, [_vp, _i, _i]),
     "tdr_filter_initialize_particles": (_i, [_vp]),

@@ -45,6 +45,11 @@ class MapHandle:
         check(self.L.tdr_map_sample_pts_polar(self.h, nb, nr, C.c_float(ang_res)))
         self.shape = (nb, nr)
 
+    def set_window(self, rows, cols):
+        """The Cartesian window (tdr_map_set_window) a FilterHandle(..., cart=True) scores against."""
+        check(self.L.tdr_map_set_window(self.h, int(rows), int(cols)))
+        self.window = (int(rows), int(cols))
+
     def __del__(self):
         if getattr(self, "h", None):
             self.L.tdr_map_destroy(self.h)
@@ -68,6 +73,13 @@ class Renderer:
         check(self.L.tdr_renderer_render(self.h, 1, _ptr(pts), stride, ioff, pts.size // stride, C.c_float(res),
                                          C.c_float(ang_res), ncls, nb, nr, None))
 
+    def render_cart(self, pts, stride, ioff, res, ncls, rows, cols):
+        """ScanRenderer::renderSemanticTopDown: the Cartesian render a Cartesian filter reads."""
+        pts = np.ascontiguousarray(pts, np.float32)
+        self._shape = (ncls, rows, cols)
+        check(self.L.tdr_renderer_render(self.h, 0, _ptr(pts), stride, ioff, pts.size // stride, C.c_float(res),
+                                         C.c_float(1.0), ncls, rows, cols, None))
+
     def get_render(self):
         """(img, pk) of the last render: img (ncls, rows, cols) as renderSemanticTopDown fills it, pk (rows * cols, rf) the
         packed records the scoring reads (record t = row + rows * col)."""
@@ -87,14 +99,20 @@ class Renderer:
 
 
 class FilterHandle:
-    """tdr_filter on a MapHandle; seed != 0 is the reference-ordered generator (parity mode)."""
+    """tdr_filter on a MapHandle; seed != 0 is the reference-ordered generator (parity mode).  cart: the Cartesian filter
+    (tdr_filter_create_cart) over the map's window (MapHandle.set_window)."""
 
-    def __init__(self, map_handle, n_max, params, seed=0):
+    def __init__(self, map_handle, n_max, params, seed=0, cart=False):
         self.L = _lib.load()
         self.map = map_handle
+        self.cart = bool(cart)
         self.h = _vp()
         fp = params if isinstance(params, FilterParamsC) else params.to_c(map_handle.ncls)
-        check(self.L.tdr_filter_create(map_handle.h, int(n_max), C.byref(fp), int(seed), C.byref(self.h)))
+        create = self.L.tdr_filter_create_cart if cart else self.L.tdr_filter_create
+        check(create(map_handle.h, int(n_max), C.byref(fp), int(seed), C.byref(self.h)))
+
+    def initialize_particles(self):
+        check(self.L.tdr_filter_initialize_particles(self.h))
 
     def configure(self, parity_rng, locality_every=1):
         check(self.L.tdr_filter_configure(self.h, int(parity_rng), int(locality_every)))
@@ -148,8 +166,16 @@ class FilterHandle:
         if isinstance(scan, Renderer):
             check(self.L.tdr_filter_update(self.h, None, scan.h, C.c_float(res), int(n_target)))
         else:
-            imgs = _scan_images(scan, self.map)
+            imgs = _scan_images(scan, self.map, self.cart)
             check(self.L.tdr_filter_update(self.h, _ptr(imgs), None, C.c_float(res), int(n_target)))
+
+    def compute_weights(self, scan, res):
+        """StateParticle::computeWeight for every particle (tdr_filter_compute_weights); read them with raw_weights."""
+        if isinstance(scan, Renderer):
+            check(self.L.tdr_filter_compute_weights(self.h, None, scan.h, C.c_float(res)))
+        else:
+            imgs = _scan_images(scan, self.map, self.cart)
+            check(self.L.tdr_filter_compute_weights(self.h, _ptr(imgs), None, C.c_float(res)))
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -157,10 +183,11 @@ class FilterHandle:
             self.h = None
 
 
-def _scan_images(scan, map_handle):
-    """(ncls, nb, nr) images -> the column-major [ncls][nb*nr] layout tdr_filter_update reads; the shape is checked."""
+def _scan_images(scan, map_handle, cart=False):
+    """(ncls, nb, nr) images -> the column-major [ncls][nb*nr] layout tdr_filter_update reads; the shape is checked
+    (cart: against the map's window)."""
     a = np.asarray(scan, np.float32)
-    want = (map_handle.ncls,) + tuple(map_handle.shape)
+    want = (map_handle.ncls,) + tuple(map_handle.window if cart else map_handle.shape)
     if a.shape != want:
         raise ValueError(f"scan of shape {a.shape}, the map expects {want}")
     return np.ascontiguousarray(np.transpose(a, (0, 2, 1)))
@@ -183,7 +210,7 @@ def step_batch(filters, scans, res, priors, n_targets=None, stream=None):
         if isinstance(sc, Renderer):
             ins[i].renderer = sc.h
         else:
-            imgs = _scan_images(sc, f.map)
+            imgs = _scan_images(sc, f.map, f.cart)   # (a Cartesian filter: tdr_batch_step refuses it)
             keep.append(imgs)
             ins[i].scan_imgs = imgs.ctypes.data
         ins[i].res, ins[i].n_target = resv[i], nts[i]

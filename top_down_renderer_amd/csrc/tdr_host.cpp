@@ -93,6 +93,7 @@ struct tdr_map {
   tdr_map_desc geo_desc{};
   int nb = 0, nr = 0;
   float ang_res = 0;
+  int win_rows = 0, win_cols = 0;   // the Cartesian window (tdr_map_set_window); 0: none
   int center_x = 0, center_y = 0;
   bool have_map = false;
   // staging of the run-time map replacement (tdr_map_set_labels: aerial maps keep arriving, top_down_render.cpp:574-600),
@@ -122,6 +123,7 @@ struct tdr_renderer {
   DevBuf<uint8_t> geo_ws;  // sort keys / scratch of the geometric render
   int ncls = 0, rows = 0, cols = 0;  // shape of the last render
   bool have_scan = false;
+  bool polar = true;                 // ... and its kind (renderSemanticTopDown of ScanRendererPolar / ScanRenderer)
   // tdr_batch_render_polar renders on the caller's stream without a host wait: `rendered` marks the end of that render
   // (render_async), and every stream that has since read img / pk leaves an event in `readers` for the next batched
   // render to wait on (one per stream: a later record on the same stream covers the earlier reads)
@@ -147,6 +149,8 @@ struct tdr_filter {
   uint64_t seed = 0, step = 0;
   uint64_t prop_calls = 0;    // device RNG: every propagate call draws fresh noise (counter = calls so far)
   bool scale_frozen = false, maybe_uninit = true, parity_rng = true;
+  bool cart = false;          // tdr_filter_create_cart: the scoring stage is the Cartesian one (window = the map's)
+  DevBuf<float> init_ws;      // ... and the workspace of its heading search, allocated by the first update that runs it
   int locality_every = 1;
   float uniform_scale = 0.f;
   bool rng_owned = true;      // false after tdr_filter_share_rng: the generator belongs to the caller
@@ -520,6 +524,19 @@ int tdr_map_sample_pts_polar(tdr_map* m, int nb, int nr, float ang_res) {
 }
 
 // the (theta bins, range bins) given to samplePtsPolar last: the shape ParticleFilter::update's images must have
+int tdr_map_set_window(tdr_map* m, int rows, int cols) {
+  if (!m || rows < 1 || cols < 1) return failh(TDR_ERR_ARG, "map_set_window: bad arguments");
+  m->win_rows = rows;
+  m->win_cols = cols;
+  return TDR_OK;
+}
+int tdr_map_window_shape(const tdr_map* m, int* rows, int* cols) {
+  if (!m) return failh(TDR_ERR_ARG, "map_window_shape: null map");
+  if (rows) *rows = m->win_rows;
+  if (cols) *cols = m->win_cols;
+  return TDR_OK;
+}
+
 int tdr_map_polar_shape(const tdr_map* m, int* nb, int* nr) {
   if (!m || !nb || !nr) return failh(TDR_ERR_ARG, "map_polar_shape: bad arguments");
   *nb = m->nb;
@@ -1078,6 +1095,7 @@ int tdr_renderer_render(tdr_renderer* r, int polar, const float* pts, int stride
   r->ncls = ncls;
   r->rows = rows;
   r->cols = cols;
+  r->polar = polar != 0;
   r->have_scan = true;
   return TDR_OK;
 }
@@ -1158,6 +1176,14 @@ static int filter_create(tdr_map* map, int n_max, const tdr_filter_params* fp, u
 }
 int tdr_filter_create(tdr_map* map, int n_max, const tdr_filter_params* fp, uint32_t seed, tdr_filter** out) {
   return filter_create(map, n_max, fp, seed, nullptr, out);
+}
+// the Cartesian filter (BASELINE config 4): the same object, its scoring stage is filter_score's Cartesian branch
+int tdr_filter_create_cart(tdr_map* map, int n_max, const tdr_filter_params* fp, uint32_t seed, tdr_filter** out) {
+  if (map && (map->win_rows < 1 || map->win_cols < 1))
+    return failh(TDR_ERR_ARG, "filter_create_cart: the map has no window (tdr_map_set_window)");
+  TTRY(filter_create(map, n_max, fp, seed, nullptr, out));
+  (*out)->cart = true;
+  return TDR_OK;
 }
 // particles sharded over the ranks of `comm` (not owned; must outlive the filter)
 int tdr_filter_create_sharded(tdr_map* map, int n_max, const tdr_filter_params* fp, uint32_t seed, tdr_comm* comm,
@@ -1377,6 +1403,7 @@ int tdr_filter_update_geo(tdr_filter* f, const float* scan_imgs, const float* ge
   if (!f || !f->map || !f->map->have_map) return failh(TDR_ERR_ARG, "filter_update_geo: no map");
   if (!scan_imgs || !geo_imgs) return failh(TDR_ERR_ARG, "filter_update_geo: null images");
   if (f->comm) return failh(TDR_ERR_ARG, "filter_update_geo: not available on a sharded filter");
+  if (f->cart) return failh(TDR_ERR_ARG, "filter_update_geo: there is no Cartesian geometric cost");
   if (f->n == 0) return TDR_OK;
   tdr_map* m = f->map;
   if (m->nb < 1 || !m->tab.p) return failh(TDR_ERR_ARG, "filter_update_geo: samplePtsPolar was never called");
@@ -1450,9 +1477,11 @@ static int map_rec16_end(tdr_map* m, hipStream_t s) {
 }
 static int filter_score(tdr_filter* f, const float* scan_imgs, const tdr_renderer* renderer, float res) {
   tdr_map* m = f->map;
-  if (m->nb < 1 || !m->tab.p) return failh(TDR_ERR_ARG, "filter_update: samplePtsPolar was never called");
+  if (!f->cart && (m->nb < 1 || !m->tab.p)) return failh(TDR_ERR_ARG, "filter_update: samplePtsPolar was never called");
+  if (f->cart && (m->win_rows < 1 || m->win_cols < 1)) return failh(TDR_ERR_ARG, "filter_update: the map has no window");
   f->fp.num_classes = m->desc.ncls;
-  const int ncls = m->desc.ncls, nb = m->nb, nr = m->nr;
+  // (a Cartesian scan is packed like a polar one with nb = the window's rows, nr = its columns: tdr_k_score_cart)
+  const int ncls = m->desc.ncls, nb = f->cart ? m->win_rows : m->nb, nr = f->cart ? m->win_cols : m->nr;
   const size_t P = (size_t)nb * nr;
   const size_t pk_floats = P * tdr_rec_floats(ncls);
   const float* pk = nullptr;
@@ -1467,6 +1496,7 @@ static int filter_score(tdr_filter* f, const float* scan_imgs, const tdr_rendere
     if (renderer->ncls != ncls || renderer->rows != nb || renderer->cols != nr)
       return failh(TDR_ERR_ARG, "filter_update: render shape %dx%dx%d does not match the map's %dx%dx%d",
                    renderer->ncls, renderer->rows, renderer->cols, ncls, nb, nr);
+    if (f->cart && renderer->polar) return failh(TDR_ERR_ARG, "filter_update: a Cartesian filter needs a Cartesian render");
     pk = renderer->pk.p;
     TTRY(renderer_wait_render(renderer, f->stream));
   } else if (!(f->comm && f->rank != 0)) {
@@ -1481,6 +1511,26 @@ static int filter_score(tdr_filter* f, const float* scan_imgs, const tdr_rendere
   }
   const int64_t n = f->nl();   // this rank's particles
   const int32_t* perm = nullptr;
+  if (f->cart) {
+    // windows that rotate with the particle: the heading belongs in the order's key.  The search runs first (it only
+    // chooses headings), the regular launch then scores every particle, as the polar path does.
+    f->states_changed();
+    if (f->maybe_uninit) {
+      TTRY(f->init_ws.resize(tdr_score_cart_init_workspace_floats(ncls, nb, nr, n, f->n)));
+      TTRY(tdr_k_score_cart_init(&m->desc, pk, nb, nr, res, &f->fp, f->st.p, f->cap, n, f->n, f->init_ws.p, f->stream));
+      f->maybe_uninit = false;   // no gates: every particle has a heading now
+    }
+    if (f->locality_every > 0) {
+      TTRY(f->loc_tmp.resize(tdr_locality_pose_tmp_ints(n) + 2));
+      TTRY(tdr_k_locality_order_pose(f->st.p, f->cap, n, m->desc.rows, m->desc.cols, (float)(nb + nr) / 16.f, f->perm.p,
+                                     f->loc_tmp.p, f->stream));
+      perm = f->perm.p;
+    }
+    TTRY(f->ws.resize(tdr_score_cart_workspace_floats(ncls, nb, nr, n, f->n)));
+    TTRY(tdr_k_score_cart(&m->desc, pk, nb, nr, res, &f->fp, f->st.p, f->cap, n, f->n, perm, f->raw_w.p, f->ws.p, f->stream));
+    if (renderer && !scan_imgs) TTRY(renderer_note_read(renderer, f->stream));
+    return TDR_OK;
+  }
   if (f->locality_every > 0) {
     TTRY(f->loc_tmp.resize(tdr_locality_tmp_ints(n, m->desc.rows, m->desc.cols)));
     TTRY(tdr_k_locality_order(f->st.p, f->cap, n, m->desc.rows, m->desc.cols, f->perm.p, f->loc_tmp.p, f->stream));
@@ -1781,6 +1831,8 @@ int tdr_batch_step(tdr_filter* const* filters, int k, const tdr_batch_input* in,
   tdr_map* m = filters[0]->map;
   for (int i = 0; i < k; i++)
     if (filters[i]->map != m) return failh(TDR_ERR_ARG, "batch_step: filter %d is on another map than filter 0", i);
+  for (int i = 0; i < k; i++)
+    if (filters[i]->cart) return failh(TDR_ERR_ARG, "batch_step: filter %d is a Cartesian filter (batches are polar)", i);
   if (!m || !m->have_map) return failh(TDR_ERR_ARG, "batch_step: the filters' map holds no map");
   if (m->nb < 1 || !m->tab.p) return failh(TDR_ERR_ARG, "batch_step: samplePtsPolar was never called on the map");
   const int ncls = m->desc.ncls, nb = m->nb, nr = m->nr;
@@ -2056,6 +2108,7 @@ int tdr_batch_render_polar(tdr_renderer* const* r, int k, const tdr_batch_cloud*
     q->ncls = ncls;
     q->rows = nb;
     q->cols = nr;
+    q->polar = true;
     q->have_scan = true;
   }
   return TDR_OK;

@@ -758,6 +758,7 @@ extern "C" int tdr_config_su_wave_span(int);       // tdr_score_su.hip
 extern "C" int tdr_config_su_lds_pad(int);
 extern "C" int tdr_config_init_device(int);         // tdr_init.hip
 extern "C" int64_t tdr_config_init_window_words(int64_t);
+extern "C" int64_t tdr_config_cart_init_chunk(int64_t);   // tdr_score_cart_init.hip
 extern "C" int64_t tdr_config_tuning(const char* name, int64_t value) {   // value < 0: query only
   if (!name) return -1;
   const std::string n(name);
@@ -776,6 +777,7 @@ extern "C" int64_t tdr_config_tuning(const char* name, int64_t value) {   // val
   if (n == "su_wave_span") return tdr_config_su_wave_span((int)std::max<int64_t>(value, -1));
   if (n == "init_device") return tdr_config_init_device((int)std::max<int64_t>(value, -1));
   if (n == "init_window_words") return tdr_config_init_window_words(value > 0 ? value : -1);
+  if (n == "cart_init_chunk") return tdr_config_cart_init_chunk(value > 0 ? value : -1);
   return -1;
 }
 static void choose_chunks(int64_t n, int nr, int& rpc, int& nchunks, int target_mul = 1) {

@@ -213,6 +213,7 @@ class HipKernels:
             raise _lib.TdrError("no HIP device visible: the MI355X path cannot run (there is no CPU fallback)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self._ws = None
+        self._init_ws = None   # the Cartesian heading search (score_cart_init): freed with the kernels object
         self._pws = None
         self._rws = None
 
@@ -569,6 +570,16 @@ class HipKernels:
         check(self.lib.tdr_k_score_cart(C.byref(m.desc), _ptr(scan_pk), rows, cols, C.c_float(res), C.byref(fp),
                                         _ptr(st), st.shape[1], n, n_total, _ptr(perm), _ptr(raw_w), _ptr(self._ws),
                                         self.stream()))
+
+    def score_cart_init(self, m, scan_pk, rows, cols, res, fp, st, n, n_total=0):
+        """The heading search of the Cartesian filter (tdr_k_score_cart_init): particles of st whose have_init is 0 get
+        the best of the reference's 40 candidate headings and have_init = 1; the others are not touched.  Waits for the
+        stream once (the number of such particles decides how many scoring launches follow)."""
+        need = int(self.lib.tdr_score_cart_init_workspace_floats(m.ncls, rows, cols, n, n_total))
+        if self._init_ws is None or self._init_ws.numel() < need:
+            self._init_ws = self.empty((need,))
+        check(self.lib.tdr_k_score_cart_init(C.byref(m.desc), _ptr(scan_pk), rows, cols, C.c_float(res), C.byref(fp),
+                                             _ptr(st), st.shape[1], n, n_total, _ptr(self._init_ws), self.stream()))
 
     def propagate(self, st, n, last_dist, tx, ty, omega, scale_freeze, pos_cov, theta_cov, z4=None, seed=0, step=0,
                   index_base=0):

@@ -319,11 +319,13 @@ class ParticleFilter:
                     uniform_scale=self._uniform_scale, n_total=n, ctx=self.score_ctx)
         else:   # Cartesian window (BASELINE config 4; definition in include/tdr.h:tdr_k_score_cart)
             rows, cols = m.window_shape()
+            if self._maybe_uninit:   # the heading search (include/tdr.h:tdr_k_score_cart_init); it only chooses headings
+                k.score_cart_init(m.dev, scan_pk, rows, cols, float(res), self.fp_c, self.st, nl, n_total=n)
             k.score_cart(m.dev, scan_pk, rows, cols, float(res), self.fp_c, self.st, nl, self.raw_w,
                          perm=self.perm if self.locality_every else None, n_total=n)
         # the init search initialises every un-gated particle; only gated ones (state_particle.cpp:163-176) can stay
-        # un-initialised, and gates exist only with force_on_map or an unknown scale
-        if not (self.params_.force_on_map or self.params_.fixed_scale < 0):
+        # un-initialised, and gates exist only with force_on_map or an unknown scale (the Cartesian score has no gates)
+        if not getattr(m, "polar", True) or not (self.params_.force_on_map or self.params_.fixed_scale < 0):
             self._maybe_uninit = False
         self._n_raw = nl
 
