@@ -607,6 +607,16 @@ int tdr_profile_variants(int64_t out[16]);
  *                      share goes through the plain kernel instead — same bits)
  *   "su_lds_pad"       bytes of dynamic LDS added to a workgroup of score_polar_su_kernel: fewer workgroups fit a CU — an
  *                      occupancy sweep without touching the code object (0, the default; same bits)
+ *   "su_tail_groups"   K: how many of the LAST ring groups of score_polar_su_kernel's grid are cut into sector ranges, so that
+ *                      the workgroups dispatched last are short and the launch's run-down with them (default 4; a launch
+ *                      of fewer than two rounds of the chip's resident workgroups takes none — except under
+ *                      tdr_config_shift_uniform(2), where the knobs hold on every shape)
+ *   "su_tail_parts"    Q: into how many sector ranges each of them is cut — 1, 2, 4 or 8 (another value: the next lower of
+ *                      these).  K = 0 or Q = 1 is the launch without tail units.  Integer sums: same bits for every K, Q.
+ *                      A dense slot then has (groups - K) + K Q rows of partial sums, and tdr_score_workspace_floats GROWS
+ *                      with them (nothing is clamped: K up to every group, Q up to 8) — like "su_group", set both BEFORE
+ *                      the workspace of a call is sized (default 4).  Where tail units apply and the shapes allow, the ring
+ *                      groups are 16 rings instead of 8 ("su_group" = 0)
  *   "init_device"      0: tdr_filter_initialize_particles keeps the serial host loop; 1 (default): a filter that owns its
  *                      generator in parity mode initialises on the device (tdr_k_init_particles — the same states)
  *   "init_window_words" words of the generator's stream per window of tdr_k_init_particles (a multiple of 2048, 2048 to
@@ -614,6 +624,10 @@ int tdr_profile_variants(int64_t out[16]);
  *   "cart_init_chunk"  particles without a heading whose candidates one scoring launch of tdr_k_score_cart_init covers
  *                      (>= 1; default 4096: DESIGN.md 5.5; bounds its workspace; same results) */
 int64_t tdr_config_tuning(const char* name, int64_t value);
+/* The rows of score_polar_su_kernel's grid for nchunks ring groups with the last k cut into q sector ranges each (tests):
+ * returns the row count R = (nchunks - k') + k' q', k' = k clamped to [0, nchunks], q' = q rounded down to 1, 2, 4 or 8; for
+ * 0 <= row < R also the row's ring group and its sectors [s0, s1) of the 8.  row < 0: R alone. */
+int tdr_su_tail_plan(int nchunks, int k, int q, int row, int* group, int* s0, int* s1);
 /* Device self-test of the scoring kernels: a tiny fixed problem (160 x 160 map, 6 classes, 512 particles) scored by every
  * kernel the library has for it.  The integer-form kernels run generated, hand-scheduled assembly; their sums are exact, so
  * score_polar_su_kernel == score_polar_ray_kernel and score_cart_su_kernel == score_cart_skip_kernel == score_cart_ray_kernel

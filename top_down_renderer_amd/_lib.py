@@ -140,6 +140,7 @@ SIGNATURES = {
     "tdr_score_ctx_span": (C.c_float, [_vp]),
     "tdr_score_ctx_trial_calls": (_i64, [_vp]),
     "tdr_config_tuning": (_i64, [C.c_char_p, _i64]),
+    "tdr_su_tail_plan": (_i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "tdr_selftest_score": (_i, []),
     "tdr_profile_variants": (_i, [C.POINTER(_i64)]),
     "tdr_score_ctx_set_polar_factors": (_i, [_vp, _vp, _i, _i]),

@@ -50,13 +50,7 @@ struct ScoreArgs {
 #include "tdr_score_cart.h"  // CartArgs, the Cartesian kernel that skips empty scan bins (tdr_score_cart.hip)
 
 
-#ifdef TDR_SCORE_TIMELINE   // diagnostic build: start / end time stamp (100 MHz) of every workgroup
-#define TDR_TL_MAX (1 << 17)
-__device__ unsigned long long g_timeline[2 * TDR_TL_MAX];
-extern "C" int tdr_debug_read_timeline(unsigned long long* out, int n) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_timeline), sizeof(unsigned long long) * 2 * (size_t)n) == hipSuccess ? 0 : -1;
-}
-#endif
+TDR_TL_BUFFER(g_timeline, tdr_debug_read_timeline)   // (diagnostic build only: tdr_score_dev.h)
 // COMPACT: this instantiation reads the compact records (10-bit dictionary indices, decoded through LDS; bit-identical
 // operands) instead of the dense ones — a quarter of the bytes through L1 / L2 / HBM for six classes.  It is the one
 // that runs whenever the map has a compact form (A/B on MI355X, config 2, 100 k particles, ms per launch dense ->
@@ -79,10 +73,7 @@ __device__ __forceinline__ void score_polar_body(const ScoreArgs& a, const unsig
   static_assert(!WIDE || (COMPACT && NV4 == 2), "wide compact records: 8-float dense records only");
   constexpr int CW = WIDE ? 4 : CmapShape<RF, KSLOT>::CW, LC = WIDE ? 1 : CmapShape<RF, KSLOT>::LC;
   constexpr int NDICT = WIDE ? TDR_CMAP_WIDE_MAX_DICT : TDR_CMAP_MAX_DICT;
-#ifdef TDR_SCORE_TIMELINE
-  const unsigned tl_id = blockIdx.y * gridDim.x + blockIdx.x;
-  if (threadIdx.x == 0 && tl_id < TDR_TL_MAX) g_timeline[2 * tl_id] = wall_clock64();
-#endif
+  TDR_TL_BEGIN(g_timeline)
   extern __shared__ float4 ring[];  // [nb rows][rs]: a row's (ring, plane) records side by side, rs = group * NV4 | 1
   __shared__ float ldict[COMPACT ? NDICT : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -276,10 +267,7 @@ __device__ __forceinline__ void score_polar_body(const ScoreArgs& a, const unsig
     for (int k = 0; k < RF; k++) o[(int64_t)k * a.npad] = acc[k];
     o[(int64_t)RF * a.npad] = KSLOT ? acc[RF - 2] : known;
   }
-#ifdef TDR_SCORE_TIMELINE
-  __syncthreads();
-  if (threadIdx.x == 0 && tl_id < TDR_TL_MAX) g_timeline[2 * tl_id + 1] = wall_clock64();
-#endif
+  TDR_TL_END(g_timeline)
 }
 template <int NV4, int U, bool KSLOT, bool USCALE, bool COMPACT, bool WIDE = false>
 __global__ __launch_bounds__(256, COMPACT ? (WIDE ? 3 : 5) : 1) void score_polar_kernel(ScoreArgs a) {
@@ -756,6 +744,8 @@ extern "C" int tdr_config_cart_seg_rows(int);      // tdr_score_cart.hip
 extern "C" int tdr_config_mt_stretches(int);       // tdr_rng.hip
 extern "C" int tdr_config_su_wave_span(int);       // tdr_score_su.hip
 extern "C" int tdr_config_su_lds_pad(int);
+extern "C" int tdr_config_su_tail_groups(int);
+extern "C" int tdr_config_su_tail_parts(int);
 extern "C" int tdr_config_init_device(int);         // tdr_init.hip
 extern "C" int64_t tdr_config_init_window_words(int64_t);
 extern "C" int64_t tdr_config_cart_init_chunk(int64_t);   // tdr_score_cart_init.hip
@@ -774,6 +764,8 @@ extern "C" int64_t tdr_config_tuning(const char* name, int64_t value) {   // val
   if (n == "cart_seg_rows") return tdr_config_cart_seg_rows((int)std::max<int64_t>(value, -1));
   if (n == "mt_stretches") return tdr_config_mt_stretches((int)std::max<int64_t>(value, -1));
   if (n == "su_lds_pad") return tdr_config_su_lds_pad((int)std::max<int64_t>(value, -1));
+  if (n == "su_tail_groups") return tdr_config_su_tail_groups((int)std::min<int64_t>(std::max<int64_t>(value, -1), 1 << 20));
+  if (n == "su_tail_parts") return tdr_config_su_tail_parts((int)std::min<int64_t>(std::max<int64_t>(value, -1), 8));
   if (n == "su_wave_span") return tdr_config_su_wave_span((int)std::max<int64_t>(value, -1));
   if (n == "init_device") return tdr_config_init_device((int)std::max<int64_t>(value, -1));
   if (n == "init_window_words") return tdr_config_init_window_words(value > 0 ? value : -1);
@@ -819,6 +811,7 @@ extern "C" int tdr_cmap_words(int ncls);   // tdr_cmap.hip
 struct ScoreWs {
   int group, nchunks;
   int su_group, su_nchunks;   // the ring groups of the shift-uniform kernel (integer sums: any partition gives the same bits)
+  int su_tail_k, su_tail_q, su_rows;   // ... the last of them cut by sector: rows of partial sums per dense slot (su_tail_plan)
   int64_t npad, npad_part, off_aux, off_utab, off_su, total;
   bool su;
   SuWs suw;
@@ -842,13 +835,27 @@ static ScoreWs score_ws(int ncls, int nb, int nr, int64_t n, int64_t n_total) {
     // eight rings per group where that divides the image and still leaves thousands of workgroups: a sector's mask is
     // staged half as often (config 2: 3.50 against 3.56 ms; 16 rings: 3.69, the staged boxes grow)
     if (w.su && w.group == 4 && nr % 8 == 0 && cdiv(n_total, 256) * (nr / 8) >= 4096) w.su_group = 8;
+    // sixteen where the launch's last groups go as short rows (tail units, tdr_su_tail): the run-down that made long groups
+    // lose is gone, and mask stagings, descriptor streams and finalize rows halve again (config 2: 4.41 ms a step with 8-ring
+    // groups and tail units, 4.32 with 16; 32 rings: 5.8 — the staged boxes outgrow LDS).  By THIS launch's particle count:
+    // integer sums do not care, and a rank's shard must still fill the chip.
+    int k16 = 0, q16 = 1;
+    if (w.su && w.su_group == 8 && nr % 16 == 0 && cdiv(std::max<int64_t>(n, 1), 256) * (nr / 16) >= 4096)
+      tdr_su_tail(nr / 16, std::max<int64_t>(n, 1), &k16, &q16);
+    if (k16 > 0) w.su_group = 16;
     if (w.su && forced >= 4 && forced % 4 == 0) w.su_group = forced;
   }
   w.su_nchunks = (int)cdiv(nr, w.su_group);
+  tdr_su_tail(w.su_nchunks, std::max<int64_t>(n, 1), &w.su_tail_k, &w.su_tail_q);
+  {
+    int g, s0, s1;
+    w.su_rows = su_tail_plan(w.su_nchunks, w.su_tail_k, w.su_tail_q, -1, &g, &s0, &s1);
+  }
   w.npad_part = w.su ? su_npad(std::max<int64_t>(n, 1), nb) : w.npad;
   // partial sums: [chunks][rows][slots] — float form rf + 1 rows; integer form (tdr_score_su.hip) 2 ncls + 2 rows of
-  // words and room for the chunk rows of a scattered particle's window (tdr_score_ray.hip)
-  w.off_aux = w.su ? (int64_t)std::max(std::max(w.nchunks, w.su_nchunks), TDR_RAY_MAX_SPLIT) * std::max(rf + 1, 2 * ncls + 2) * w.npad_part
+  // words — su_rows of them for a dense slot, whatever the tail knobs make of the ring groups — and room for the chunk rows
+  // of a scattered particle's window (tdr_score_ray.hip)
+  w.off_aux = w.su ? (int64_t)std::max(std::max(w.nchunks, w.su_rows), TDR_RAY_MAX_SPLIT) * std::max(rf + 1, 2 * ncls + 2) * w.npad_part
                    : (int64_t)w.nchunks * (rf + 1) * w.npad_part;
   w.off_utab = w.off_aux + 3 * w.npad + 64;
   w.off_su = (w.off_utab + 2 * (int64_t)nb * nr + 63) / 64 * 64;
@@ -1328,6 +1335,7 @@ extern "C" int tdr_k_score_polar_ctx(const tdr_map_desc* map, const float* tab, 
     L.map = map; L.tab = a.utab ? a.utab : a.tab; L.uniform_scale = a.utab != nullptr; L.scan_pk = scan_pk;
     L.nb = nb; L.nr = nr; L.rf = rf; L.res = res; L.st = st; L.cap = cap; L.n = n; L.perm = perm;
     L.group = W.su_group; L.nchunks = W.su_nchunks; L.npad = W.npad_part; L.part = a.part;
+    L.tail_k = W.su_tail_k; L.tail_q = W.su_tail_q; L.rows = W.su_rows;
     L.fac = ctx && ctx->fac && ctx->fac_nb == nb && ctx->fac_nr == nr ? ctx->fac : nullptr;
     L.uscale = uniform_scale;
     L.wave_span = tdr_su_wave_span();
@@ -1355,7 +1363,7 @@ extern "C" int tdr_k_score_polar_ctx(const tdr_map_desc* map, const float* tab, 
       r.run_if = inexact;
       if ((rc = launch_score(r, map, rf, s, false))) return rc;
     }
-    launch_finalize_exact(f, map, W.npad_part, slots, counts, inexact, W.su_nchunks, L.ray_split, s);
+    launch_finalize_exact(f, map, W.npad_part, slots, counts, inexact, W.su_rows, L.ray_split, s);
     LAUNCH_CHECK("score_finalize_exact");
     launch_finalize(f, n, s);
   } else {

@@ -157,4 +157,31 @@ __device__ __forceinline__ void cmap_decode_wide(const uint32_t (&w)[4], const f
   if (KSLOT) m[RF - 2] = kf;
   m[RF - 1] = kf;
 }
+// -DTDR_SCORE_TIMELINE, a diagnostic build: start / end time stamp (wall_clock64, 100 MHz) of every workgroup of a scoring
+// kernel — one pair per workgroup, written by thread 0, the end behind a barrier so that it is the workgroup's and not the
+// first wave's — in a buffer of the kernel's own translation unit.  READER copies the first n pairs out and clears the
+// buffer: a workgroup that left without doing anything has no stamp (tools/su_timeline.py, tools/diag_score_timeline.py).
+// The normal build has none of it.
+#ifdef TDR_SCORE_TIMELINE
+#define TDR_TL_MAX (1 << 17)
+#define TDR_TL_BUFFER(BUF, READER)                                                                                       \
+  __device__ unsigned long long BUF[2 * TDR_TL_MAX];                                                                     \
+  extern "C" int READER(unsigned long long* out, int n) {                                                                \
+    void* dev = nullptr;                                                                                                 \
+    if (n < 0 || n > TDR_TL_MAX || hipDeviceSynchronize() != hipSuccess) return -1;                                      \
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(BUF), sizeof(unsigned long long) * 2 * (size_t)n) != hipSuccess) return -1;  \
+    if (hipGetSymbolAddress(&dev, HIP_SYMBOL(BUF)) != hipSuccess) return -1;                                             \
+    return hipMemset(dev, 0, sizeof(unsigned long long) * 2 * TDR_TL_MAX) == hipSuccess ? 0 : -1;                        \
+  }
+#define TDR_TL_BEGIN(BUF)                                                                                                \
+  const unsigned tl_id = blockIdx.y * gridDim.x + blockIdx.x;                                                            \
+  if (threadIdx.x == 0 && tl_id < TDR_TL_MAX) BUF[2 * tl_id] = wall_clock64();
+#define TDR_TL_END(BUF)                                                                                                  \
+  __syncthreads();                                                                                                       \
+  if (threadIdx.x == 0 && tl_id < TDR_TL_MAX) BUF[2 * tl_id + 1] = wall_clock64();
+#else
+#define TDR_TL_BUFFER(BUF, READER)
+#define TDR_TL_BEGIN(BUF)
+#define TDR_TL_END(BUF)
+#endif
 #endif  // TDR_SCORE_DEV_H_

@@ -482,6 +482,7 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
     o[(int64_t)(2 * a.ncls + 1) * a.npad] = known;
   }
 }
+TDR_TL_BUFFER(g_timeline_ray, tdr_debug_read_timeline_ray)   // (diagnostic build only: tdr_score_dev.h)
 template <int GQ, bool USCALE, bool BM = false, bool PATCH = false>
 __global__ __launch_bounds__(256) void score_polar_ray_kernel(RayArgs a) {
   extern __shared__ unsigned long long lacc[];
@@ -489,9 +490,14 @@ __global__ __launch_bounds__(256) void score_polar_ray_kernel(RayArgs a) {
   __shared__ uint4 lut[16];
   __shared__ float2 ldir[PATCH ? RAY_PATCH_MAX_NB : 1];
   if (int_form_off(a.inexact)) return;
+#ifdef TDR_SCORE_TIMELINE
+  if ((int64_t)blockIdx.x * 4 >= (int64_t)a.counts[1] * a.nsplit) return;   // no stamps for an idle workgroup (ray_body's own test)
+#endif
+  TDR_TL_BEGIN(g_timeline_ray)
   // with factors that ARE the table's (ray_prep_kernel's check; uniform over the launch) the offsets are multiplied out
   if (a.fac && a.inexact[2] == 0) ray_body<GQ, USCALE, true, BM, PATCH>(a, lacc, ldict, lut, ldir);
   else ray_body<GQ, USCALE, false, BM, PATCH>(a, lacc, ldict, lut, ldir);
+  TDR_TL_END(g_timeline_ray)   // (ray_body's waves return from IT: every thread of a live workgroup arrives here)
 }
 
 

@@ -19,6 +19,32 @@ struct SuWs {
 #define TDR_RAY_MAX_SPLIT 8       // waves a particle's window may be split over (tdr_ray_splits): chunk rows of `part`
 SuWs tdr_su_ws(int nb, int nr, int group, int64_t n);
 
+// The ROWS of the shift-uniform kernel's grid (grid.y) — the "plan".  A row is a workgroup's share of a window: a ring group
+// and a range of its TDR_SU_NSECT sectors of directions.  The first nchunks - k rows are whole ring groups; each of the LAST k
+// groups is cut into q rows of 8 / q sectors (q: 1, 2, 4 or 8, anything else rounds down to one of them; k is clamped to
+// nchunks).  The grid is handed out x-fastest, so the short rows are the workgroups dispatched last: the launch's run-down,
+// when nothing refills a compute unit, lasts a short row's lifetime instead of a whole group's.  Integer sums do not care how
+// a window is partitioned and a sector's mask is staged once either way: the rows change no bit of any weight.
+// Returns the row count R = (nchunks - k) + k q; for 0 <= row < R also the row's ring group and sectors [s0, s1).
+#define TDR_SU_NSECT 8
+__host__ __device__ static inline int su_tail_plan(int nchunks, int k, int q, int row, int* group, int* s0, int* s1) {
+  const int lq = q >= 8 ? 3 : (q >= 4 ? 2 : (q >= 2 ? 1 : 0));
+  const int kk = k < 0 ? 0 : (k > nchunks ? nchunks : k);
+  const int head = nchunks - kk, rows = head + (kk << lq);
+  if (row < 0 || row >= rows) return rows;
+  if (row < head) {
+    *group = row; *s0 = 0; *s1 = TDR_SU_NSECT;
+  } else {
+    const int t = row - head, part = t & ((1 << lq) - 1);
+    *group = head + (t >> lq);
+    *s0 = part << (3 - lq);
+    *s1 = (part + 1) << (3 - lq);
+  }
+  return rows;
+}
+// the split of a launch: tdr_config_tuning("su_tail_groups" / "su_tail_parts") and the rule of the shapes (tdr_score_su.hip)
+void tdr_su_tail(int nchunks, int64_t n, int* k, int* q);
+
 struct SuLaunch {
   const tdr_map_desc* map;   // with a narrow compact form
   const float* tab;          // [P][2]: (tab*scale)*res when uniform_scale, else the table itself
@@ -30,8 +56,10 @@ struct SuLaunch {
   int64_t cap, n;
   const int32_t* perm;       // caller's locality order (NULL = identity)
   int group, nchunks;
+  int tail_k = 0, tail_q = 1;   // the last tail_k ring groups go as tail_q rows each (su_tail_plan) ...
+  int rows = 0;              // ... which makes this many rows of the shift-uniform kernel's grid and of `part` per dense slot
   int64_t npad;              // slot capacity = stride of part (su_npad)
-  float* part;               // integer partial sums, [chunks][2 ncls + 2][npad] words (tdr_score_su.hip)
+  float* part;               // integer partial sums, [rows][2 ncls + 2][npad] words (tdr_score_su.hip)
   int ray_split;             // waves per scattered particle (tdr_ray_splits)
   const float* fac;          // the table's factors (tdr_polar_factors_host) or NULL
   float uscale;              // the caller's uniform scale (<= 0: none)

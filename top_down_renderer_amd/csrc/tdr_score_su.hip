@@ -48,7 +48,7 @@
 #define SU_CODE_FULL 0xFFu       // several classes present: packed scan record, classes with a zero count skipped
 #define SU_CODE_FULL_ALL 0xFEu   // a non-finite value is in play: every class multiplied like score_polar_kernel does
 #define SU_CODE_PAD 0xFDu        // no such ring: the last group of an image whose ring count is no multiple of the group
-#define SU_NSECT 8               // sectors of directions per known-mask staging (16: 2 % slower on config 2)
+#define SU_NSECT TDR_SU_NSECT    // 8 sectors of directions per known-mask staging (16: 2 % slower on config 2)
 #define SU_BOX_WORDS 4096        // LDS words of the staged known mask: 16 KB (config 2's dense share 2.97 ms at 12 KB, 2.81 at 16
                                  // and at 20 KB, 4.18 at 24 KB, where a sixth wave per SIMD no longer fits; a wave that
                                  // stages a box of its own — the far-apart waves of config 5 — has a quarter of it)
@@ -75,8 +75,9 @@ struct SuArgs {
   const int32_t* slots;    // padded (shift, Morton) order, -1 = padding; every 64-slot batch holds one shift
   const int32_t* nslots;   // device word: slots in use (a multiple of 64)
   int group, nchunks, ncls;
+  int tail_k, tail_q;      // grid.y = the rows of su_tail_plan(nchunks, tail_k, tail_q, ...)
   int64_t npad;            // stride of `part`
-  uint32_t* part;          // [nchunks][2 ncls + 2][npad]: class k's integer sum as {low, high} words, normalisation, known count
+  uint32_t* part;          // [rows][2 ncls + 2][npad]: class k's integer sum as {low, high} words, normalisation, known count
   uint32_t* stats;         // NULL, or (profiling) counters of the variants the wave-sectors ran: tdr_profile_variants
 };
 
@@ -370,10 +371,12 @@ struct SuLds {
   int box[4];
 };
 
-// lane = particle; every wave holds particles of ONE heading bin (see the file comment).  grid.y = group of a.group
-// consecutive range rings (score_group_rings: a multiple of 4, nr a multiple of 4), samples visited ray-major like
+// lane = particle; every wave holds particles of ONE heading bin (see the file comment).  grid.y = a row of su_tail_plan:
+// a group of a.group consecutive range rings (score_group_rings: a multiple of 4, nr a multiple of 4) and all of its sectors,
+// or — the rows dispatched last — a part of them; samples visited ray-major like
 // score_polar_kernel: direction i ascending, the group's rings in steps of 4 consecutive cells along the ray.  The
 // directions are walked in SU_NSECT sectors; for each the workgroup stages the known mask of the cells its windows can reach.
+TDR_TL_BUFFER(g_timeline_su, tdr_debug_read_timeline_su)   // (diagnostic build only: tdr_score_dev.h)
 template <int NV4, bool KSLOT, bool USCALE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void score_polar_su_kernel(SuArgs a) {
   constexpr int RF = 4 * NV4;
@@ -385,6 +388,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform
   const int64_t nsl = (int64_t)__builtin_amdgcn_readfirstlane(*a.nslots);
   if ((int64_t)blockIdx.x * 256 >= nsl) return;   // the whole workgroup is beyond the slots in use (uniform)
+  TDR_TL_BEGIN(g_timeline_su)
   const int64_t base = ((int64_t)blockIdx.x * 4 + wave) * 64;
   const bool active = base < nsl;                 // wave-uniform; an idle wave still keeps the barriers below
   const int32_t sp = active ? a.slots[base + lane] : -1;
@@ -397,7 +401,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
   const float off1 = cx / a.resolution;  // :30
   const int shift = __builtin_amdgcn_readfirstlane(rot_shift_dev(a.st[TDR_ST_THETA * a.cap + p], a.nb));
   const int nb = a.nb, G = a.group;
-  const int j0 = blockIdx.y * G, gn = min(a.nr - j0, G);
+  int rgroup = 0, sect0 = 0, sect1 = SU_NSECT;   // this row's ring group and sectors (wave-uniform: scalar arithmetic)
+  su_tail_plan(a.nchunks, a.tail_k, a.tail_q, (int)blockIdx.y, &rgroup, &sect0, &sect1);
+  const int j0 = rgroup * G, gn = min(a.nr - j0, G);
   const float rmaxf = (float)a.rows, cmaxf = (float)a.cols;
   const int ckcol = a.ctiles_r * 128 - 16 * CW;   // cmap_offset
   const int pkcol = a.pkcol;                      // plane_offset; its constant comes with the descriptor
@@ -409,9 +415,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
   };
   typedef const float __attribute__((address_space(4))) * tdr_const_f;
   typedef const uint32_t __attribute__((address_space(4))) * tdr_const_u;
-  const tdr_const_f tbase = (tdr_const_f)a.tab_su + (int64_t)blockIdx.y * nb * G * 2;
-  const tdr_const_u dbase = (tdr_const_u)a.desc + (int64_t)blockIdx.y * nb * G * 4;
-  const tdr_const_f bbase = (tdr_const_f)a.bbox + (int64_t)blockIdx.y * SU_NSECT * 4;
+  const tdr_const_f tbase = (tdr_const_f)a.tab_su + (int64_t)rgroup * nb * G * 2;
+  const tdr_const_u dbase = (tdr_const_u)a.desc + (int64_t)rgroup * nb * G * 4;
+  const tdr_const_f bbase = (tdr_const_f)a.bbox + (int64_t)rgroup * SU_NSECT * 4;
   const tdr_const_f scanc = (tdr_const_f)a.scan_pk;
   const uint32_t* __restrict__ crec = a.crec;
   const uint32_t* __restrict__ kmask = a.kmask;
@@ -791,7 +797,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     }
   };
 
-  for (int sect = 0; sect < SU_NSECT; sect++) {
+  for (int sect = sect0; sect < sect1; sect++) {
     const int i0 = (int)((int64_t)sect * nb / SU_NSECT), i1 = (int)((int64_t)(sect + 1) * nb / SU_NSECT);
     // cells this lane's samples of the sector can fall on: rounding is monotone, so the box of the offsets carries over
     float a0 = bbase[4 * sect], b0 = bbase[4 * sect + 1], a1 = bbase[4 * sect + 2], b1 = bbase[4 * sect + 3];
@@ -891,6 +897,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     o[(int64_t)(2 * a.ncls) * a.npad] = norm;
     o[(int64_t)(2 * a.ncls + 1) * a.npad] = known;
   }
+  TDR_TL_END(g_timeline_su)
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -990,6 +997,44 @@ bool tdr_su_shape_ok(int nb, int nr, int group, int64_t n_total) {
   // takes 0.23 ms (0.18 + 0.10, side by side) where the float kernel takes 0.11 (profiles/r04_bench_ref_integer_form_v1.json).
   if ((int64_t)nb * nr < 8192) return false;
   return n_total >= (int64_t)64 * nb;
+}
+// ---- tail units: the rows of the launch's last ring groups (su_tail_plan, tdr_score_su.h) ---------------------------------
+// Once the dispatcher has handed out the last workgroup nothing refills a compute unit: over the last workgroup's lifetime the
+// chip runs from six resident workgroups per CU down to none.  Measured on MI355X at config 2 (tools/su_timeline.py,
+// profiles/su_timeline_before_v1.txt): 11 200 live workgroups of 370 us each on 1 536 slots, a run-down of 164 us of a 2.87 ms
+// kernel, 0.085 ms of it lost against a full chip.  With the last K groups cut into Q rows the run-down lasts a short row's
+// lifetime; a sector's mask is staged once either way, so the bulk keeps the economy of its long groups — and 16-ring groups,
+// which lost to 8-ring ones on their run-down alone (3.69 against 3.50 ms), now win (tdr_score.hip: score_ws).
+// Defaults from the sweep K in {0, 1, 2, 3, 4, 8} x Q in {2, 4, 8} x groups of 8 / 16 / 32 rings: 16 rings,
+// K = 4, Q = 4 — the last 64 of config 2's 256 rings go as rows of 16 rings x 2 sectors: config 2 4.47 -> 4.32 ms a step,
+// config 3's shard 5.57 -> 5.40, config 5's 13.87 -> 13.62.
+static int g_su_tail_groups = 4, g_su_tail_parts = 4;
+extern "C" int tdr_config_su_tail_groups(int k) {   // < 0: query only
+  if (k >= 0) g_su_tail_groups = k;
+  return g_su_tail_groups;
+}
+extern "C" int tdr_config_su_tail_parts(int q) {    // < 0: query only; 1, 2, 4 or 8 (anything else: the next lower of them)
+  if (q >= 0) g_su_tail_parts = q >= 8 ? 8 : (q >= 4 ? 4 : (q >= 2 ? 2 : 1));
+  return g_su_tail_parts;
+}
+// The rule of the shapes: short rows pay where workgroups QUEUE — a launch of fewer than two rounds of the chip's resident
+// workgroups (256 CUs x 6) has no run-down worth shortening, and every row costs the finalize a pass over its partial sums.
+// Results never depend on it.  (tdr_config_shift_uniform(2), the tests' mode: whatever the knobs say, on any shape.)
+void tdr_su_tail(int nchunks, int64_t n, int* k, int* q) {
+  *k = std::min(g_su_tail_groups, nchunks);
+  *q = g_su_tail_parts;
+  if (g_su_mode != 2 && cdiv(std::max<int64_t>(n, 1), 256) * nchunks < 2 * 256 * 6) *k = 0;
+  if (*k == 0 || *q == 1) { *k = 0; *q = 1; }
+}
+extern "C" int tdr_su_tail_plan(int nchunks, int k, int q, int row, int* group, int* s0, int* s1) {   // tests
+  int g = 0, a = 0, b = 0;
+  const int rows = su_tail_plan(nchunks, k, q, row, &g, &a, &b);
+  if (row >= 0 && row < rows) {
+    if (group) *group = g;
+    if (s0) *s0 = a;
+    if (s1) *s1 = b;
+  }
+  return rows;
 }
 static size_t su_sort_tmp_bytes(int64_t n) {
   size_t bytes = 0;
@@ -1117,9 +1162,12 @@ int tdr_su_score(const SuLaunch& L, const SuWs& W, hipStream_t s) {
   u.scan_pk = L.scan_pk;
   u.nb = L.nb; u.nr = L.nr; u.res = L.res; u.st = L.st; u.cap = L.cap;
   u.slots = base + W.slots; u.nslots = nslots;
-  u.group = L.group; u.nchunks = L.nchunks; u.ncls = map->ncls; u.npad = L.npad; u.part = reinterpret_cast<uint32_t*>(L.part);
+  u.group = L.group; u.nchunks = L.nchunks; u.tail_k = L.tail_k; u.tail_q = L.tail_q; u.ncls = map->ncls; u.npad = L.npad; u.part = reinterpret_cast<uint32_t*>(L.part);
   u.stats = tdr_profile_stats_ptr();
-  const dim3 grid((unsigned)cdiv(L.npad, 256), (unsigned)L.nchunks), block(256);
+  int rg, r0, r1;
+  const int rows = su_tail_plan(L.nchunks, L.tail_k, L.tail_q, -1, &rg, &r0, &r1);
+  if (L.rows != rows) return fail(TDR_ERR_ARG, "score: %d rows of partial sums for a plan of %d", L.rows, rows);
+  const dim3 grid((unsigned)cdiv(L.npad, 256), (unsigned)rows), block(256);
   const bool ks = tdr_has_kslot(map->ncls, L.rf), us = L.uniform_scale;
 #define TDR_LAUNCH_SU(NV4)                                                                         \
   if (ks && us) hipLaunchKernelGGL((score_polar_su_kernel<NV4, true, true>), grid, block, g_su_lds_pad, s, u);  \
