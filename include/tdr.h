@@ -617,6 +617,9 @@ int tdr_profile_variants(int64_t out[16]);
  *                      with them (nothing is clamped: K up to every group, Q up to 8) — like "su_group", set both BEFORE
  *                      the workspace of a call is sized (default 4).  Where tail units apply and the shapes allow, the ring
  *                      groups are 16 rings instead of 8 ("su_group" = 0)
+ *   "su_order_bucket"  1 (default): the heading order of an integer-form launch (and the dense / scattered order of the
+ *                      Cartesian one) is a one-pass stable bucket sort wherever its table of one word per (512 positions,
+ *                      key) stays within 4 n + 65536 words; 0: always rocPRIM's stable sort (A/B) — the same slot list
  *   "init_device"      0: tdr_filter_initialize_particles keeps the serial host loop; 1 (default): a filter that owns its
  *                      generator in parity mode initialises on the device (tdr_k_init_particles — the same states)
  *   "init_window_words" words of the generator's stream per window of tdr_k_init_particles (a multiple of 2048, 2048 to
@@ -628,6 +631,18 @@ int64_t tdr_config_tuning(const char* name, int64_t value);
  * returns the row count R = (nchunks - k') + k' q', k' = k clamped to [0, nchunks], q' = q rounded down to 1, 2, 4 or 8; for
  * 0 <= row < R also the row's ring group and its sectors [s0, s1) of the 8.  row < 0: R alone. */
 int tdr_su_tail_plan(int nchunks, int k, int q, int row, int* group, int* s0, int* s1);
+/* The ordering passes of an integer-form launch on their own (tests, timing): the slot list of n particles (states st,
+ * capacity cap) over nb heading bins — per bin the particles whose 64 neighbours in the caller's order `perm` (NULL:
+ * identity) lie within `span` map cells (span <= 0: all of them), in that order, every bin padded to whole waves with -1;
+ * behind the bins the other particles (key nb; nb == 1: the Cartesian launch's two keys).  workspace: device memory of
+ * tdr_k_su_order_workspace_ints(n, nb) 4-byte words (never fewer for more particles).  slots_out: tdr_k_su_order_slots(n, nb)
+ * words, of which the first counts_out[2] are defined; keys_out: the n keys in the caller's order; counts_out: {padded slots
+ * of the bins, particles behind them, both}.  These are device pointers; nb <= 4095.  bucket_out (host memory, may be NULL):
+ * 1 when the bucket sort ordered the launch, 0 when rocPRIM's sort did ("su_order_bucket"). */
+size_t tdr_k_su_order_workspace_ints(int64_t n, int nb);
+int64_t tdr_k_su_order_slots(int64_t n, int nb);
+int tdr_k_su_order(const float* st, int64_t cap, int64_t n, const int32_t* perm, int nb, float span, int32_t* workspace,
+                   int32_t* slots_out, int32_t* keys_out, int32_t* counts_out, int* bucket_out, void* stream);
 /* Device self-test of the scoring kernels: a tiny fixed problem (160 x 160 map, 6 classes, 512 particles) scored by every
  * kernel the library has for it.  The integer-form kernels run generated, hand-scheduled assembly; their sums are exact, so
  * score_polar_su_kernel == score_polar_ray_kernel and score_cart_su_kernel == score_cart_skip_kernel == score_cart_ray_kernel

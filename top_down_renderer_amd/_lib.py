@@ -141,6 +141,9 @@ SIGNATURES = {
     "tdr_score_ctx_trial_calls": (_i64, [_vp]),
     "tdr_config_tuning": (_i64, [C.c_char_p, _i64]),
     "tdr_su_tail_plan": (_i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "tdr_k_su_order_workspace_ints": (C.c_size_t, [_i64, _i]),
+    "tdr_k_su_order_slots": (_i64, [_i64, _i]),
+    "tdr_k_su_order": (_i, [_vp, _i64, _i64, _vp, _i, _f, _vp, _vp, _vp, _vp, C.POINTER(_i), _vp]),
     "tdr_selftest_score": (_i, []),
     "tdr_profile_variants": (_i, [C.POINTER(_i64)]),
     "tdr_score_ctx_set_polar_factors": (_i, [_vp, _vp, _i, _i]),

@@ -746,6 +746,7 @@ extern "C" int tdr_config_su_wave_span(int);       // tdr_score_su.hip
 extern "C" int tdr_config_su_lds_pad(int);
 extern "C" int tdr_config_su_tail_groups(int);
 extern "C" int tdr_config_su_tail_parts(int);
+extern "C" int tdr_config_su_order_bucket(int);
 extern "C" int tdr_config_init_device(int);         // tdr_init.hip
 extern "C" int64_t tdr_config_init_window_words(int64_t);
 extern "C" int64_t tdr_config_cart_init_chunk(int64_t);   // tdr_score_cart_init.hip
@@ -766,6 +767,7 @@ extern "C" int64_t tdr_config_tuning(const char* name, int64_t value) {   // val
   if (n == "su_lds_pad") return tdr_config_su_lds_pad((int)std::max<int64_t>(value, -1));
   if (n == "su_tail_groups") return tdr_config_su_tail_groups((int)std::min<int64_t>(std::max<int64_t>(value, -1), 1 << 20));
   if (n == "su_tail_parts") return tdr_config_su_tail_parts((int)std::min<int64_t>(std::max<int64_t>(value, -1), 8));
+  if (n == "su_order_bucket") return tdr_config_su_order_bucket((int)std::max<int64_t>(value, -1));
   if (n == "su_wave_span") return tdr_config_su_wave_span((int)std::max<int64_t>(value, -1));
   if (n == "init_device") return tdr_config_init_device((int)std::max<int64_t>(value, -1));
   if (n == "init_window_words") return tdr_config_init_window_words(value > 0 ? value : -1);

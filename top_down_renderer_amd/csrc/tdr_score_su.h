@@ -12,6 +12,8 @@ bool tdr_su_shape_ok(int nb, int nr, int group, int64_t n_total);
 struct SuWs {
   int64_t tab_su, desc, bbox, keys_in, keys_out, vals_in, vals_out, ints, slots, sort_tmp, ray_tab, ray_desc, ray_multi, ray_rad, total;
   int64_t slots2, wave_tmp;   // the re-routing pass (su_wave_far_kernel ...): a second slot list, four ints per wave
+  int64_t seg_hist;           // the bucket sort's table [segments][nb + 1] (su_colscan_kernel); empty where the rule of shapes
+                              // leaves the order to rocPRIM
   // ints: [cnt nb + 1][start nb + 1][slot_start nb + 1][counts 3][n_multi][inexact][mass bound][table is not its factors]
   //       [the counts before the re-routing pass 3]  (int_form_off)
 };

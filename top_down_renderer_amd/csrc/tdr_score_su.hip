@@ -20,10 +20,15 @@
 // values (0 * inf = NaN must not be skipped) turn the skipping off bin by bin (descriptor code SU_CODE_FULL_ALL).
 //
 // Per launch (all on the caller's stream, nothing synchronises):
-//   su_key_kernel      heading bin of every particle (in the caller's locality order) + histogram of the bins
-//   rocPRIM            stable radix sort by bin: (shift, Morton) order
-//   su_offsets_kernel  bucket starts in the sorted list and in the padded slot list, number of slots in use
-//   su_scatter_kernel  slot -> particle (-1 = padding)
+//   su_key_kernel      heading bin of every particle (in the caller's locality order) + the histogram of the bins of every
+//                      segment of 512 consecutive positions: one row of a table [segment][bin]
+//   su_colscan_kernel  the table's columns -> their exclusive prefix over the segments, the column sums (particles per bin)
+//   su_offsets_kernel  bucket starts in the padded slot list, number of slots in use; the -1 of the padding slots, the zero
+//                      of the words later kernels add to
+//   su_rank_scatter_kernel  slot -> particle: a wave per segment, ranks among equal bins by ballots — the (shift, Morton)
+//                      order, i.e. a stable sort by bin, in one pass
+//   (where the table would be out of proportion — the rule at su_seg_table_words — and under tdr_config_tuning(
+//    "su_order_bucket", 0): two fills, su_key_kernel, su_offsets_kernel, rocPRIM's stable radix sort by bin, su_scatter_kernel)
 //   su_prep_kernel     per (direction, ring): sample offset and scan descriptor, group-major (a wave streams them in order)
 //   su_bbox_kernel     bounding box of the sample offsets of every (ring group, sector of directions)
 //   score_polar_su_kernel, then score_finalize_kernel over the slots
@@ -183,16 +188,20 @@ __global__ __launch_bounds__(256) void su_bbox_kernel(const float* __restrict__ 
 // particles sorted together keep that box small and share the cache lines of their record gathers.  Sparse ones share
 // nothing whatever the order and are bound by the memory system, not by instruction issue: they keep their locality order
 // and go through score_polar_kernel (tdr_score.hip), behind the dense ones in the same slot list.
-// Histogram of the nb + 1 keys: per workgroup in LDS first (a converged filter fills a few bins).
+// Histogram of the nb + 1 keys, per workgroup in LDS (a converged filter fills a few bins).  A workgroup takes `per_block`
+// consecutive positions (a multiple of 256).  With seg_hist the workgroup's positions are one SEGMENT of the bucket sort
+// (su_colscan_kernel) and its histogram is row blockIdx.x of seg_hist[segment][key]: every word of the row is written, nothing
+// is zero-filled beforehand.  Without it (the rocPRIM path) the histogram is added to cnt, which the caller has zeroed.
 __global__ __launch_bounds__(256) void su_key_kernel(const float* __restrict__ st, int64_t cap, int64_t n,
-                                                     const int32_t* __restrict__ perm, int nb, float span,
+                                                     const int32_t* __restrict__ perm, int nb, float span, int per_block,
                                                      uint32_t* __restrict__ keys, int32_t* __restrict__ vals,
-                                                     int* __restrict__ cnt) {
+                                                     int* __restrict__ cnt, int* __restrict__ seg_hist) {
   extern __shared__ int hist[];
   for (int k = threadIdx.x; k <= nb; k += 256) hist[k] = 0;
   __syncthreads();
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) {
+  for (int it = 0; it < per_block; it += 256) {
+    const int64_t t = (int64_t)blockIdx.x * per_block + it + threadIdx.x;
+    if (t >= n) break;
     const int32_t p = perm ? perm[t] : (int32_t)t;
     uint32_t key = (uint32_t)rot_shift_dev(st[TDR_ST_THETA * cap + p], nb);
     if (span > 0.f) {
@@ -212,15 +221,72 @@ __global__ __launch_bounds__(256) void su_key_kernel(const float* __restrict__ s
     atomicAdd(&hist[key], 1);
   }
   __syncthreads();
-  for (int k = threadIdx.x; k <= nb; k += 256)
-    if (hist[k]) atomicAdd(&cnt[k], hist[k]);
+  if (seg_hist) {
+    int* row = seg_hist + (int64_t)blockIdx.x * (nb + 1);
+    for (int k = threadIdx.x; k <= nb; k += 256) row[k] = hist[k];
+  } else {
+    for (int k = threadIdx.x; k <= nb; k += 256)
+      if (hist[k]) atomicAdd(&cnt[k], hist[k]);
+  }
+}
+
+// ---- the bucket sort: a stable sort by a key of at most 4096 values is one ranked scatter ---------------------------------
+// The positions t of the caller's order are cut into segments of SU_SEG consecutive ones; su_key_kernel leaves the table
+// seg_hist[segment][key].  Here the table's columns are turned, in place, into their exclusive prefix over the segments —
+// seg_hist[s][k] = particles of key k in the segments before s — and the column sums go to cnt[k].  A workgroup takes 64
+// keys (a lane each, so a row's words are read side by side), its 16 waves a sixteenth of the segments each: the serial part
+// of a workgroup is segments / 16 long whatever the key count.
+#define SU_SEG 512
+#define SU_COLSCAN_WAVES 16
+__global__ __launch_bounds__(64 * SU_COLSCAN_WAVES) void su_colscan_kernel(int* __restrict__ seg_hist, int segs, int nkeys,
+                                                                           int* __restrict__ cnt) {
+  __shared__ int wsum[SU_COLSCAN_WAVES][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int k = blockIdx.x * 64 + lane;
+  const bool live = k < nkeys;
+  const int per = (segs + SU_COLSCAN_WAVES - 1) / SU_COLSCAN_WAVES;
+  const int s0 = min(w * per, segs), s1 = min(s0 + per, segs);
+  int* col = seg_hist + (live ? k : 0);
+  int sum = 0;
+  if (live)
+    for (int sgm = s0; sgm < s1; sgm += 8) {   // eight loads in flight
+      int v[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) v[u] = sgm + u < s1 ? col[(int64_t)(sgm + u) * nkeys] : 0;
+#pragma unroll
+      for (int u = 0; u < 8; u++) sum += v[u];
+    }
+  wsum[w][lane] = sum;
+  __syncthreads();
+  int run = 0, tot = 0;
+#pragma unroll
+  for (int j = 0; j < SU_COLSCAN_WAVES; j++) {
+    const int v = wsum[j][lane];
+    run += j < w ? v : 0;
+    tot += v;
+  }
+  if (!live) return;
+  if (w == 0) cnt[k] = tot;
+  for (int sgm = s0; sgm < s1; sgm += 8) {   // eight loads in flight, then the serial sums
+    int v[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) v[u] = sgm + u < s1 ? col[(int64_t)(sgm + u) * nkeys] : 0;
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      if (sgm + u < s1) col[(int64_t)(sgm + u) * nkeys] = run;
+      run += v[u];
+    }
+  }
 }
 
 // One workgroup.  The particles of key k start at start[k] in the sorted list and take slots [slot_start[k], + count) of
 // the slot list, the count of a heading bin (k < nkeys - 1) rounded up to whole waves.
 // counts = {slots of the heading bins (a multiple of 64), sparse particles behind them, both together}
+// The bucket sort (pad_slots set) has no filled slot list and no zeroed words to start from: the up to 63 padding slots of a
+// heading bin get their -1 here, and the words behind counts (TDR_SU_TAIL_INTS, which later kernels add to) their zero.
 __global__ __launch_bounds__(256) void su_offsets_kernel(const int* __restrict__ cnt, int nkeys, int* __restrict__ start,
-                                                         int* __restrict__ slot_start, int* __restrict__ counts) {
+                                                         int* __restrict__ slot_start, int* __restrict__ counts,
+                                                         int32_t* __restrict__ pad_slots) {
   __shared__ int sa[256], sb[256];
   int carry_a = 0, carry_b = 0;
   for (int base = 0; base < nkeys; base += 256) {
@@ -241,6 +307,8 @@ __global__ __launch_bounds__(256) void su_offsets_kernel(const int* __restrict__
     if (k < nkeys) {
       start[k] = carry_a + sa[threadIdx.x] - c;
       slot_start[k] = carry_b + sb[threadIdx.x] - cp;
+      if (pad_slots)
+        for (int j = c; j < cp; j++) pad_slots[carry_b + sb[threadIdx.x] - cp + j] = -1;
     }
     carry_a += sa[255];
     carry_b += sb[255];
@@ -252,6 +320,7 @@ __global__ __launch_bounds__(256) void su_offsets_kernel(const int* __restrict__
     counts[1] = sparse;
     counts[2] = carry_b;
   }
+  if (pad_slots && threadIdx.x >= 3 && threadIdx.x < TDR_SU_TAIL_INTS) counts[threadIdx.x] = 0;
 }
 
 __global__ __launch_bounds__(256) void su_scatter_kernel(const uint32_t* __restrict__ keys, const int32_t* __restrict__ vals,
@@ -261,6 +330,61 @@ __global__ __launch_bounds__(256) void su_scatter_kernel(const uint32_t* __restr
   if (t >= n) return;
   const uint32_t k = keys[t];
   slots[slot_start[k] + ((int)t - start[k])] = vals[t];
+}
+
+// The bucket sort's scatter.  One wave per segment; it walks the segment 64 positions at a time, in order.  ctr[k] (LDS) is
+// the slot of the segment's next particle of key k: slot_start[k] + the key's particles in earlier segments (su_colscan_kernel)
+// to begin with.  The lanes that hold the same key find each other by a multi-split over the key's bits; a lane's slot is
+// ctr[key] + the equal-key lanes below it, and the last of them moves ctr[key] on.  Segments, 64-groups and lanes are all
+// visited in position order: the slot list is the one a stable sort gives.
+__global__ __launch_bounds__(64) void su_rank_scatter_kernel(const uint32_t* __restrict__ keys, const int32_t* __restrict__ vals,
+                                                             int64_t n, const int* __restrict__ seg_pre,
+                                                             const int* __restrict__ slot_start, int nkeys, int bits,
+                                                             int32_t* __restrict__ slots) {
+  extern __shared__ int ctr[];
+  const int lane = threadIdx.x;
+  const int64_t t0 = (int64_t)blockIdx.x * SU_SEG;
+  uint32_t key[SU_SEG / 64];
+  int32_t val[SU_SEG / 64];
+#pragma unroll
+  for (int it = 0; it < SU_SEG / 64; it++) {   // (all of the segment's loads in flight at once, the counters' below too)
+    const int64_t t = t0 + it * 64 + lane;
+    key[it] = t < n ? keys[t] : 0u;
+    val[it] = t < n ? vals[t] : 0;
+  }
+  const int* row = seg_pre + (int64_t)blockIdx.x * nkeys;
+  for (int k0 = lane; k0 < nkeys; k0 += 256) {
+    int a[4], b[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int k = k0 + 64 * u;
+      a[u] = k < nkeys ? slot_start[k] : 0;
+      b[u] = k < nkeys ? row[k] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (k0 + 64 * u < nkeys) ctr[k0 + 64 * u] = a[u] + b[u];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < SU_SEG / 64; it++) {
+    const bool live = t0 + it * 64 + lane < n;
+    uint64_t same = __ballot(live);
+    for (int b = 0; b < bits; b++) {
+      const bool one = (key[it] >> b) & 1u;
+      const uint64_t ones = __ballot(one);
+      same &= one ? ones : ~ones;
+    }
+    const int below = __popcll(same & (((uint64_t)1 << lane) - 1)), all = __popcll(same);
+    int at = 0;
+    if (live) {
+      at = ctr[key[it]];
+      slots[at + below] = val[it];
+    }
+    __syncthreads();   // (one wave: every lane has read its counter)
+    if (live && below == all - 1) ctr[key[it]] = at + all;
+    __syncthreads();
+  }
 }
 
 // ---- re-routing by the wave's own box ---------------------------------------------------------------------------------------
@@ -1036,6 +1160,28 @@ extern "C" int tdr_su_tail_plan(int nchunks, int k, int q, int row, int* group, 
   }
   return rows;
 }
+// The ordering passes' rule of shapes.  The bucket sort (su_colscan_kernel) keeps a table of one word per (segment of SU_SEG
+// positions, key): n (nb + 1) / 512 words, a quarter of the particle count at config 2's 256 bins and two words at the
+// Cartesian launch's two keys.  It is taken while the table stays in proportion to the particles — segments x keys <= 4 n +
+// 65536 — which holds for every n up to nb = 2047 and leaves to rocPRIM's sort the launches of more headings over many
+// particles: from n = 16 384 on at nb = 4095, from about 35 000 on at nb = 3000.  (The bound is a choice of proportion, not a
+// measured crossover: nobody has timed the bucket sort against the merge sort at such shapes.)  Same slot list either way: a
+// stable sort by key has one answer.  tdr_config_tuning("su_order_bucket", 0): always rocPRIM (A/B).
+static int g_su_order_bucket = 1;
+extern "C" int tdr_config_su_order_bucket(int v) {   // < 0: query only
+  if (v >= 0) g_su_order_bucket = v ? 1 : 0;
+  return g_su_order_bucket;
+}
+static int64_t su_seg_table_words(int nb, int64_t n) {   // 0: no bucket sort for this shape
+  const int64_t words = cdiv(std::max<int64_t>(n, 1), SU_SEG) * ((int64_t)nb + 1);
+  return words <= 4 * std::max<int64_t>(n, 1) + 65536 ? words : 0;
+}
+// words reserved for the table: never fewer for more particles, so that a workspace sized for n holds every launch of up to n
+static int64_t su_seg_table_reserve(int nb, int64_t n) {
+  const int64_t m = std::max<int64_t>(n, 1);
+  return std::min<int64_t>(cdiv(m, SU_SEG) * ((int64_t)nb + 1), 4 * m + 65536);
+}
+static bool su_order_is_bucket(int nb, int64_t n) { return g_su_order_bucket && su_seg_table_words(nb, n) > 0; }
 static size_t su_sort_tmp_bytes(int64_t n) {
   size_t bytes = 0;
   uint32_t* k = nullptr;
@@ -1067,6 +1213,7 @@ SuWs tdr_su_ws(int nb, int nr, int group, int64_t n) {
   w.ray_desc = take((T + 1) / 2);              // the list of bins that hold several classes
   w.ray_multi = take((int64_t)nb * nr);
   w.ray_rad = take(T / nb);                    // the rings' radii in ray order (a table given as factors)
+  w.seg_hist = take(su_seg_table_reserve(nb, n));   // the bucket sort's table (whatever su_order_bucket says at the time)
   w.total = o;
   return w;
 }
@@ -1086,21 +1233,42 @@ int tdr_su_order(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_t*
   int* counts = slot_start + nkeys;
   int32_t* slots = base + W.slots;
   const int64_t n = L.n;
-  HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)(3 * nkeys + TDR_SU_TAIL_INTS), s));
-  HIP_TRY(hipMemsetAsync(slots, 0xFF, sizeof(int32_t) * (size_t)L.npad, s));
-  hipLaunchKernelGGL(su_key_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), sizeof(int) * (size_t)nkeys, s, L.st, L.cap, n,
-                     L.perm, L.nb, L.span, keys_in, vals_in, cnt);
-  LAUNCH_CHECK("su_key");
-  hipLaunchKernelGGL(su_offsets_kernel, dim3(1), dim3(256), 0, s, (const int*)cnt, nkeys, start, slot_start, counts);
-  LAUNCH_CHECK("su_offsets");
-  unsigned bits = 1;
-  while ((1u << bits) < (unsigned)nkeys) bits++;
-  size_t tmp_bytes = su_sort_tmp_bytes(n);
-  HIP_TRY(rocprim::radix_sort_pairs(base + W.sort_tmp, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, bits,
-                                    s, false));
-  hipLaunchKernelGGL(su_scatter_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, (const uint32_t*)keys_out,
-                     (const int32_t*)vals_out, n, (const int*)start, (const int*)slot_start, slots);
-  LAUNCH_CHECK("su_scatter");
+  if (su_order_is_bucket(L.nb, n)) {
+    // key + segment histograms, column prefixes, offsets (+ padding, + the zeroed words behind counts), ranked scatter
+    int* seg_hist = base + W.seg_hist;
+    const int64_t segs = cdiv(n, SU_SEG);
+    hipLaunchKernelGGL(su_key_kernel, dim3((unsigned)segs), dim3(256), sizeof(int) * (size_t)nkeys, s, L.st, L.cap, n, L.perm,
+                       L.nb, L.span, SU_SEG, keys_in, vals_in, (int*)nullptr, seg_hist);
+    LAUNCH_CHECK("su_key");
+    hipLaunchKernelGGL(su_colscan_kernel, dim3((unsigned)cdiv(nkeys, 64)), dim3(64 * SU_COLSCAN_WAVES), 0, s, seg_hist,
+                       (int)segs, nkeys, cnt);
+    LAUNCH_CHECK("su_colscan");
+    hipLaunchKernelGGL(su_offsets_kernel, dim3(1), dim3(256), 0, s, (const int*)cnt, nkeys, start, slot_start, counts, slots);
+    LAUNCH_CHECK("su_offsets");
+    unsigned bits = 1;
+    while ((1u << bits) < (unsigned)nkeys) bits++;
+    hipLaunchKernelGGL(su_rank_scatter_kernel, dim3((unsigned)segs), dim3(64), sizeof(int) * (size_t)nkeys, s,
+                       (const uint32_t*)keys_in, (const int32_t*)vals_in, n, (const int*)seg_hist, (const int*)slot_start, nkeys,
+                       (int)bits, slots);
+    LAUNCH_CHECK("su_rank_scatter");
+  } else {
+    HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)(3 * nkeys + TDR_SU_TAIL_INTS), s));
+    HIP_TRY(hipMemsetAsync(slots, 0xFF, sizeof(int32_t) * (size_t)L.npad, s));
+    hipLaunchKernelGGL(su_key_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), sizeof(int) * (size_t)nkeys, s, L.st, L.cap, n,
+                       L.perm, L.nb, L.span, 256, keys_in, vals_in, cnt, (int*)nullptr);
+    LAUNCH_CHECK("su_key");
+    hipLaunchKernelGGL(su_offsets_kernel, dim3(1), dim3(256), 0, s, (const int*)cnt, nkeys, start, slot_start, counts,
+                       (int32_t*)nullptr);
+    LAUNCH_CHECK("su_offsets");
+    unsigned bits = 1;
+    while ((1u << bits) < (unsigned)nkeys) bits++;
+    size_t tmp_bytes = su_sort_tmp_bytes(n);
+    HIP_TRY(rocprim::radix_sort_pairs(base + W.sort_tmp, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, bits,
+                                      s, false));
+    hipLaunchKernelGGL(su_scatter_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, (const uint32_t*)keys_out,
+                       (const int32_t*)vals_out, n, (const int*)start, (const int*)slot_start, slots);
+    LAUNCH_CHECK("su_scatter");
+  }
   if (L.wave_span > 0.f && L.nb > 1) {   // waves whose own particles lie far apart: to the scattered share after all
     int32_t* slots2 = base + W.slots2;
     int32_t* keep = base + W.wave_tmp;
@@ -1119,6 +1287,33 @@ int tdr_su_order(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_t*
   }
   *slots_out = slots;
   *counts_out = counts;
+  return TDR_OK;
+}
+// The ordering passes on their own (tests, timing): tdr_k_su_order_workspace_ints(n, nb) words of workspace; slots_out
+// su_npad(n, nb) words — those behind counts_out[2] are whatever the workspace held or the passes left there —, keys_out the n
+// keys in the caller's order, counts_out 3; bucket_out (host, optional): 1 when the bucket sort ran, 0 for rocPRIM's path.
+extern "C" size_t tdr_k_su_order_workspace_ints(int64_t n, int nb) {
+  if (n < 1 || nb < 1 || nb > 4095) return 0;
+  return (size_t)tdr_su_ws(nb, 4, 4, n).total;
+}
+extern "C" int64_t tdr_k_su_order_slots(int64_t n, int nb) { return n < 1 || nb < 1 ? 0 : su_npad(n, nb); }
+extern "C" int tdr_k_su_order(const float* st, int64_t cap, int64_t n, const int32_t* perm, int nb, float span,
+                              int32_t* workspace, int32_t* slots_out, int32_t* keys_out, int32_t* counts_out, int* bucket_out,
+                              void* stream) {
+  if (!st || !workspace || !slots_out || !keys_out || !counts_out) return fail(TDR_ERR_ARG, "su_order: null pointer");
+  if (n < 1 || cap < n || nb < 1 || nb > 4095) return fail(TDR_ERR_ARG, "su_order: bad shape");
+  hipStream_t s = (hipStream_t)stream;
+  const SuWs W = tdr_su_ws(nb, 4, 4, n);
+  SuLaunch L{};
+  L.st = st; L.cap = cap; L.n = n; L.perm = perm; L.nb = nb; L.span = span; L.ws = workspace;
+  L.npad = su_npad(n, nb);
+  const int32_t* slots = nullptr;
+  const int32_t* counts = nullptr;
+  if (bucket_out) *bucket_out = su_order_is_bucket(nb, n) ? 1 : 0;
+  if (int rc = tdr_su_order(L, W, s, &slots, &counts)) return rc;
+  HIP_TRY(hipMemcpyAsync(slots_out, slots, sizeof(int32_t) * (size_t)L.npad, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(keys_out, workspace + W.keys_in, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(counts_out, counts, sizeof(int32_t) * 3, hipMemcpyDeviceToDevice, s));
   return TDR_OK;
 }
 int tdr_su_prepare(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_t** slots_out, const int32_t** counts_out) {

@@ -667,6 +667,24 @@ class HipKernels:
         check(self.lib.tdr_k_states_soa_to_aos(_ptr(st), st.shape[1], n, _ptr(raw), self.stream()))
         return raw.cpu().numpy().view(dtype).reshape(-1).copy()
 
+    def su_order(self, st, n, nb, span, perm=None, workspace=None):
+        """tdr_k_su_order (include/tdr.h): the ordering passes of an integer-form launch alone.  Returns int32 tensors
+        (slots, keys, counts) and whether the bucket sort ran; `workspace`: an int32 tensor of at least
+        tdr_k_su_order_workspace_ints(n, nb) words."""
+        need = int(self.lib.tdr_k_su_order_workspace_ints(n, nb))
+        if workspace is None:
+            workspace = self.empty((need,), torch.int32)
+        if workspace.numel() < need:
+            raise ValueError(f"su_order: workspace of {workspace.numel()} words, {need} needed")
+        slots = self.empty((int(self.lib.tdr_k_su_order_slots(n, nb)),), torch.int32)
+        keys = self.empty((n,), torch.int32)
+        counts = self.empty((3,), torch.int32)
+        bucket = C.c_int(-1)
+        check(self.lib.tdr_k_su_order(_ptr(st), st.shape[1], n, _ptr(perm) if perm is not None else None, nb,
+                                      C.c_float(span), _ptr(workspace), _ptr(slots), _ptr(keys), _ptr(counts), C.byref(bucket),
+                                      self.stream()))
+        return slots, keys, counts, bool(bucket.value)
+
     def tuning(self, name, value=-1):
         """tdr_config_tuning (include/tdr.h): value < 0 queries; returns the value in force, -1 for an unknown name."""
         return int(self.lib.tdr_config_tuning(name.encode(), value))
