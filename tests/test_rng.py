@@ -183,6 +183,49 @@ def test_committed_jump_polynomials_are_the_generators_output(tmp_path):
     assert open(g.OUT).read() == open(os.path.join(root, "top_down_renderer_amd", "csrc", "tdr_mt_jump.h")).read()
 
 
+def _gen_mt_jump():
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("gen_mt_jump", os.path.join(root, "tools", "gen_mt_jump.py"))
+    g = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(g)
+    return g, os.path.join(root, "top_down_renderer_amd", "csrc", "tdr_mt_jump.h")
+
+
+def _committed_jump_levels(g, path):
+    """MT_JUMP[level][chunk][20] as the committed header spells it: the constants the device uses."""
+    import re
+    text = open(path).read()
+    words = [int(w, 16) for w in re.findall(r"0x([0-9a-f]{8})u", text[text.index("MT_JUMP[MT_JUMP_LEVELS]"):])]
+    assert len(words) == g.LEVELS * g.NCHUNK * 20
+    return np.asarray(words, np.uint32).reshape(g.LEVELS, g.NCHUNK, 20)
+
+
+def test_every_committed_jump_level_against_numpys_own_mt19937():
+    """Every level m = 0 .. 9 of the committed polynomials, through the host restatement of the device's procedure
+    (tools/gen_mt_jump.py: apply_jump), against an independent block stepper: NumPy's MT19937 set to an arbitrary block
+    reaches, after 624 * STRIDE * 2^m raw words, the state the jump gives."""
+    g, path = _gen_mt_jump()
+    levels = _committed_jump_levels(g, path)
+    assert levels.shape[0] == 10
+    x = np.random.default_rng(20260101).integers(0, 2 ** 32, 624, dtype=np.uint64).astype(np.uint32)
+    bg = np.random.MT19937(0)
+    state = bg.state
+    state["state"]["key"], state["state"]["pos"] = x.copy(), 624       # a twist comes first
+    bg.state = state
+    blocks = 0
+    for m in range(levels.shape[0]):
+        target = g.STRIDE << m                                          # the counts nest: draw on from the last level
+        while blocks < target:
+            step = min(target - blocks, 4096)
+            bg.random_raw(624 * step)
+            blocks += step
+        assert bg.state["state"]["pos"] == 624
+        want = np.asarray(bg.state["state"]["key"], np.uint32)
+        assert np.array_equal(g.apply_jump(levels[m], x), want), f"level {m} does not jump {target} blocks"
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,freeze,burn", [(16_000, False, 3), (20_000, True, 700), (100_003, False, 12345), (1_000_003, False, 99)])
 def test_stretches_reached_by_jump_ahead_give_the_serial_stream(k, n, freeze, burn):
@@ -221,3 +264,56 @@ def test_stretches_reached_by_jump_ahead_give_the_serial_stream(k, n, freeze, bu
     assert np.array_equal(out[0][1], out[1][1])
     assert out[0][2] == out[1][2]
     print(f"n = {n}: one wave {ms[0]:.3f} ms, stretches {ms[1]:.3f} ms (whole call, incl. attempts / scan / normals)")
+
+
+def _stretches_and_rounds(n, freeze):
+    """The stretches a propagate call of n particles is cut into and the rounds of doubling that reach them, by the
+    formulas of csrc/tdr_rng.hip (mt_attempt_budget, mt_ws, tdr_mt_raw_stream; MT_JUMP_STRIDE = 128 blocks of 624 words)."""
+    import math
+    need = n * (2 if freeze else 3)
+    attempts = math.ceil(need / 0.7853981633974483 * 1.05 + 12.0 * math.sqrt(need + 1.0) + 64.0)
+    nblocks = (2 * attempts + 624) // 624 + 2
+    stretches = -(-nblocks // 128)
+    return stretches, (stretches - 1).bit_length()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,freeze,stretches,rounds", [(5_500_003, False, 554, 10),     # rounds 0 .. 9: every level
+                                                       (8_000_003, True, 537, 10),      # two normals per particle
+                                                       (10_500_003, False, 1057, 11)])  # > 1024: the one-wave fall-back
+def test_every_jump_level_and_the_fallback_give_the_hosts_stream(k, n, freeze, stretches, rounds):
+    """Calls long enough to use all ten jump levels, and one past the 1024 stretches the levels reach (the raw stream
+    falls back to one wave): the normals of the stretch mode are those of mt_stretches = 0, both are the host engine's,
+    the generator state afterwards is the same words and the uniform that follows the same float."""
+    import torch
+    L = k.lib
+    assert _stretches_and_rounds(n, freeze) == (stretches, rounds)      # a change of the budget keeps the case on its level
+    assert (stretches > 1024) == (rounds > 10)
+    seed, burn = 7000 + n % 1000, 211
+    host = C.c_void_p(L.tdr_rng_create(C.c_uint32(seed)))
+    for _ in range(burn):
+        L.tdr_rng_uniform_host(host)
+    words = np.zeros(640, np.uint32)
+    assert L.tdr_rng_get_state_host(host, words.ctypes.data_as(C.c_void_p)) == 0
+    z_host = _host_normals(L, host, n, freeze).view(np.uint32)
+    u_host = float(L.tdr_rng_uniform_host(host))
+    L.tdr_rng_destroy(host)
+    before = L.tdr_config_tuning(b"mt_stretches", -1)
+    states = {}
+    try:
+        for mode in (0, 1):
+            L.tdr_config_tuning(b"mt_stretches", mode)
+            state = k.to_device(words.view(np.int32))
+            z = k.zeros((n, 4))
+            k.rng_propagate_normals_dev(state, n, 0, n, freeze, z, n)
+            u = k.zeros((64,))
+            k.rng_uniform_dev(state, u)
+            torch.cuda.synchronize()
+            assert np.array_equal(z.cpu().numpy().view(np.uint32), z_host), mode
+            assert float(u[0].item()) == u_host, mode
+            states[mode] = state.cpu().numpy()[:626].copy()
+            del z
+    finally:
+        L.tdr_config_tuning(b"mt_stretches", before)
+    assert np.array_equal(states[0], states[1])
+    assert states[0][625] == 0                                          # the attempt budget sufficed

@@ -157,7 +157,8 @@ def build():
 
 
 def self_check(levels):
-    """Level 0 and level 1 against STRIDE / 2 STRIDE honest block steps from an arbitrary state."""
+    """Level 0 and level 1 against STRIDE / 2 STRIDE honest block steps from an arbitrary state; every further level by the
+    doubling identity — level m applied twice is level m + 1 — so that all of them stand on the honest steps."""
     x = twist(twist(seed_state(20241005)))
     want = x.copy()
     for _ in range(STRIDE):
@@ -166,6 +167,9 @@ def self_check(levels):
     for _ in range(STRIDE):
         want = twist(want)
     assert np.array_equal(apply_jump(levels[1], x), want), "level 1 does not jump 2 STRIDE blocks"
+    for m in range(len(levels) - 1):
+        twice = apply_jump(levels[m], apply_jump(levels[m], x))
+        assert np.array_equal(twice, apply_jump(levels[m + 1], x)), f"level {m} applied twice is not level {m + 1}"
 
 
 def header(levels):
