@@ -582,6 +582,9 @@ int tdr_profile_variants(int64_t out[16]);
 
 /* The library reads NOTHING from the process environment: behaviour switches are these calls (and the tdr_config_* calls
  * above), process-wide, meant for A/B measurements, tests and debugging — results never depend on them unless stated.
+ * One thread configures, while no other is inside the library.  The library itself never writes them: tdr_selftest_score
+ * runs its kernel variants without setting a switch — they are what they were after it, a fixed span included, and no other
+ * thread sees them move while it runs.
  * tdr_config_tuning(name, value): value < 0 queries; returns the value in force, -1 for an unknown name.
  *   "score_waves"      waves the float / Cartesian scoring kernels aim for (default 131072)
  *   "score_group"      rings per workgroup of the float and shift-uniform kernels, 0 = from the shapes (changes the
@@ -599,14 +602,10 @@ int tdr_profile_variants(int64_t out[16]);
  *                      4 directions x 16 rings per step, a lane's four descriptors of a unit in one load (same bits)
  *   "ray_borrow"       0: an empty scan bin of the ray-mapped kernel reads its known bit from the coarse mask plane; 1 (default):
  *                      from the class plane its nearest non-empty neighbour of four rings reads anyway (same bits)
- *   "su_wave_span"     map cells a wave's own 64 same-heading particles may spread over before the wave is re-routed from the
- *                      shift-uniform kernel to the ray-mapped kernel (0, the default: never — measured, it does not pay) — same bits either way
  *   "mt_stretches"     0: the reference's random stream is always generated by one wave; 1 (default): calls of more than 128
  *                      state blocks fill stretches side by side, reached by jump-ahead (csrc/tdr_rng.hip) — the same words
  *   "cart_seg_rows"    window rows per segment of score_cart_su_kernel (a multiple of 4; 0: the Cartesian integer form's dense
  *                      share goes through the plain kernel instead — same bits)
- *   "su_lds_pad"       bytes of dynamic LDS added to a workgroup of score_polar_su_kernel: fewer workgroups fit a CU — an
- *                      occupancy sweep without touching the code object (0, the default; same bits)
  *   "su_tail_groups"   K: how many of the LAST ring groups of score_polar_su_kernel's grid are cut into sector ranges, so that
  *                      the workgroups dispatched last are short and the launch's run-down with them (default 4; a launch
  *                      of fewer than two rounds of the chip's resident workgroups takes none — except under

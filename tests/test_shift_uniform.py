@@ -348,3 +348,54 @@ def test_span_tuned_while_running_never_changes_the_weights(tdr, oracle):
     finally:
         k.lib.tdr_config_shift_uniform(before)
         k.lib.tdr_config_shift_uniform_span(-2.0)
+
+
+def _switch_triple(lib):
+    return (int(lib.tdr_config_shift_uniform(-1)), float(lib.tdr_config_shift_uniform_span(-1.0)),
+            int(lib.tdr_config_tuning(b"cart_seg_rows", -1)))
+
+
+def test_selftest_leaves_the_switches_alone(tdr):
+    """tdr_selftest_score (160 x 160 map, 6 classes, 512 particles, 64 x 32 and 32 x 24 windows) runs its kernel variants
+    without writing a process-wide switch: a mode, a FIXED span and a segment length set before it are in force after it."""
+    _, k = tdr
+    lib = k.lib
+    mode0, seg0 = int(lib.tdr_config_shift_uniform(-1)), int(lib.tdr_config_tuning(b"cart_seg_rows", -1))
+    try:
+        lib.tdr_config_shift_uniform(2)
+        lib.tdr_config_shift_uniform_span(24.0)
+        lib.tdr_config_tuning(b"cart_seg_rows", 8)
+        assert lib.tdr_selftest_score() == 0, lib.tdr_last_error().decode()
+        assert _switch_triple(lib) == (2, 24.0, 8)
+    finally:
+        lib.tdr_config_shift_uniform(mode0)
+        lib.tdr_config_shift_uniform_span(-2.0)
+        lib.tdr_config_tuning(b"cart_seg_rows", seg0)
+
+
+def test_no_other_thread_sees_the_selftest_move_a_switch(tdr):
+    """A second thread polls the three switches the self-test's runs differ in (host-only calls; ctypes releases the GIL
+    during the self-test) and must see the initial triple only."""
+    import threading
+    _, k = tdr
+    lib = k.lib
+    first = _switch_triple(lib)
+    seen, stop, started = set(), threading.Event(), threading.Event()
+
+    def poll():
+        while True:
+            seen.add(_switch_triple(lib))
+            started.set()
+            if stop.is_set():
+                return
+
+    t = threading.Thread(target=poll)
+    t.start()
+    try:
+        assert started.wait(10.0)
+        rc = lib.tdr_selftest_score()
+    finally:
+        stop.set()
+        t.join()
+    assert rc == 0, lib.tdr_last_error().decode()
+    assert seen == {first}

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "tdr.h"
+#include "tdr_config.h"
 
 // tuning knobs (compile-time)
 #ifndef TDR_SCORE_U
@@ -89,6 +90,10 @@ static inline int with_nv4(int rf, const char* who, F&& f) {
   }
 }
 
+#define PFX_HEAD 2048      // tdr_prefix.hip: leading elements added one by one: the running sum crosses most of its binades here
+// tdr_init.hip: the windows of tdr_k_init_particles are whole tiles
+#define INI_TILE 2048                 // stream positions per workgroup of ini_flags_kernel (1024 per parity)
+#define INI_MAX_TILES 2048            // ini_tail_kernel holds the tiles' minima in LDS: W <= 2^22
 // tdr_prefix.hip: final value of a serial float32 chain over the raw weights (kind 0: sum of the non-NaN weights;
 // kind 1: float-accumulated squared deviations of the weights below *mean_dev), see there
 int tdr_chain_total(const float* raw, const float* mean_dev, int kind, int64_t n, float* total_out, void* workspace,

@@ -22,6 +22,7 @@
 
 #include "tdr.h"
 #include "tdr_batch.h"
+#include "tdr_config.h"
 
 bool tdr_score_polar_float_form(const tdr_map_desc* map, int nb, int nr, int64_t n, int64_t n_total);   // tdr_score.hip
 
@@ -1294,7 +1295,7 @@ int tdr_filter_initialize_particles(tdr_filter* f) {
       }
     if (!good) return TDR_OK;  // "No road in map at init location"
   }
-  if (rng_device_capable(f) && tdr_config_tuning("init_device", -1) != 0) return initialize_on_device(f);
+  if (rng_device_capable(f) && tdr_cfg().init_device != 0) return initialize_on_device(f);
   std::vector<tdr_state> states((size_t)f->n_max + 16);
   int64_t n = 0;
   TTRY(rng_to_host(f));
@@ -1458,7 +1459,7 @@ int tdr_filter_get_last_dist(tdr_filter* f, float* out, int64_t n) {
 // weights, so searches of the map's filters must not overlap in time — whichever streams they run on (the filters' own,
 // the batch's).  A search that may use the scratch runs between these two: wait for the last one, leave an event behind.
 static int map_rec16_alloc(tdr_map* m, int64_t n) {
-  if (m->desc.rec16 || n < tdr_config_rec16_min_particles(-1)) return TDR_OK;
+  if (m->desc.rec16 || n < tdr_cfg().rec16_min) return TDR_OK;
   const size_t b16 = tdr_map_rec16_bytes(m->desc.ncls, m->desc.rows, m->desc.cols);
   if (b16) {
     TTRY(m->rec16.resize(b16));
@@ -1540,7 +1541,7 @@ static int filter_score(tdr_filter* f, const float* scan_imgs, const tdr_rendere
   TTRY(f->ws.resize(tdr_score_workspace_floats(ncls, nb, nr, n, f->n)));
   // the search over this many particles pays for pre-split half records
   if (f->maybe_uninit) TTRY(map_rec16_alloc(m, f->n));
-  const bool uses_rec16 = f->maybe_uninit && m->desc.rec16 && f->n >= tdr_config_rec16_min_particles(-1);
+  const bool uses_rec16 = f->maybe_uninit && m->desc.rec16 && f->n >= tdr_cfg().rec16_min;
   if (uses_rec16) TTRY(map_rec16_begin(m, f->stream));
   TTRY(tdr_score_ctx_set_polar_factors(f->score_ctx, m->fac.p, nb, nr));
   TTRY(tdr_k_score_polar_ctx(&m->desc, m->tab.p, pk, nb, nr, res, &f->fp, f->st.p, f->cap, n, f->n, perm, f->uniform_scale,
@@ -1811,7 +1812,7 @@ int tdr_batch_last_stats(int* batched, int* standalone) {
 static bool batch_eligible(const tdr_filter* f) {
   const tdr_map* m = f->map;
   // (a filter that may hold a particle without a heading: only with tdr_config_tuning("batch_init_search"))
-  const bool uninit_ok = !f->maybe_uninit || tdr_config_tuning("batch_init_search", -1) == 1;
+  const bool uninit_ok = !f->maybe_uninit || tdr_cfg().batch_init_search == 1;
   return !f->comm && rng_device_capable(f) && uninit_ok && f->n >= 1 && f->n <= 32768 &&
          tdr_score_polar_float_form(&m->desc, m->nb, m->nr, f->n, f->n);
 }
@@ -1865,7 +1866,7 @@ int tdr_batch_step(tdr_filter* const* filters, int k, const tdr_batch_input* in,
     if (!f->maybe_uninit) continue;
     k_init++;
     TTRY(map_rec16_alloc(m, f->n));
-    uses_rec16 |= m->desc.rec16 && f->n >= tdr_config_rec16_min_particles(-1);
+    uses_rec16 |= m->desc.rec16 && f->n >= tdr_cfg().rec16_min;
   }
   // one staging area: [kf] TdrBatchEntry, then the scoring launch's tables (tdr_batch_score_stage_bytes)
   const size_t ent_bytes = (sizeof(TdrBatchEntry) * (size_t)kf + 63) / 64 * 64;
@@ -2221,24 +2222,17 @@ int tdr_batch_pose(tdr_filter* const* f, int k, tdr_pose_stats* out, void* strea
 //              (bit for bit: the sums are exact), and both against the float kernel score_polar_kernel (rounding: 3e-6)
 //   Cartesian  score_cart_su_kernel (generated loop)  ==  score_cart_skip_kernel<INT> (plain C++)  ==  score_cart_ray_kernel,
 //              and against the float kernel
-// Process-wide switches are set for the duration of the call and restored (one caller at a time, like the profile switch).
-namespace {
-struct SelftestRestore {
-  int mode;
-  float span;
-  bool span_fixed_before;
-  int64_t seg;
-  SelftestRestore() : mode(tdr_config_shift_uniform(-1)), span(tdr_config_shift_uniform_span(-1.f)), seg(tdr_config_tuning("cart_seg_rows", -1)) {}
-  ~SelftestRestore() {
-    tdr_config_shift_uniform(mode);
-    tdr_config_shift_uniform_span(-2.f);   // back to tuning (the default); a caller that had fixed a span sets it again
-    tdr_config_tuning("cart_seg_rows", seg);
-  }
-};
-}  // namespace
+// Each run's variant is a TdrConfigScope on this thread: the process-wide switches are never written.
 int tdr_selftest_score(void) {
   constexpr int NCLS = 6, SIZE = 160, NB = 64, NR = 32, CR = 32, CC = 24, N = 512;
-  SelftestRestore restore;
+  auto selftest_variant = [](int mode, float span, int seg_rows) {   // the configuration in force, with a run's choices
+    TdrConfig c = tdr_cfg();
+    c.su_mode = mode;
+    c.su_span = span;
+    c.su_span_fixed = true;
+    c.cart_seg_rows = seg_rows;
+    return c;
+  };
   // a label image: bands of classes, a road grid (class 1), an unlabelled hole
   std::vector<uint8_t> lab((size_t)SIZE * SIZE);
   for (int y = 0; y < SIZE; y++)
@@ -2315,8 +2309,7 @@ int tdr_selftest_score(void) {
   // ---- polar: float kernel, integer form (dense share), integer form with every particle ray-mapped
   const struct { int mode; float span; } polar_runs[3] = {{0, 16.f}, {2, 16.f}, {2, 1e-6f}};
   for (int r = 0; r < 3; r++) {
-    tdr_config_shift_uniform(polar_runs[r].mode);
-    tdr_config_shift_uniform_span(polar_runs[r].span);
+    TdrConfigScope variant(selftest_variant(polar_runs[r].mode, polar_runs[r].span, tdr_cfg().cart_seg_rows));
     TTRY(tdr_filter_compute_weights(f, scan_p.data(), nullptr, 1.f));
     got[r].resize(N);
     TTRY(tdr_filter_get_raw_weights(f, got[r].data(), N));
@@ -2343,9 +2336,7 @@ int tdr_selftest_score(void) {
     const struct { int mode; float span; int seg; } cart_runs[5] = {{0, 16.f, 32}, {2, 0.f, 0}, {2, 0.f, 8}, {2, 0.f, 32}, {2, 1e-6f, 32}};
     std::vector<float> c[5];
     for (int r = 0; r < 5; r++) {
-      tdr_config_shift_uniform(cart_runs[r].mode);
-      tdr_config_shift_uniform_span(cart_runs[r].span);
-      tdr_config_tuning("cart_seg_rows", cart_runs[r].seg);
+      TdrConfigScope variant(selftest_variant(cart_runs[r].mode, cart_runs[r].span, cart_runs[r].seg));
       TTRY(tdr_k_score_cart(&m->desc, pk.p, CR, CC, 0.75f, &fp, f->st.p, f->cap, N, N, nullptr, raw.p, ws.p, f->stream));
       c[r].resize(N);
       HTRY(hipMemcpyAsync(c[r].data(), raw.p, N * sizeof(float), hipMemcpyDeviceToHost, f->stream));

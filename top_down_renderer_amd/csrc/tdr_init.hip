@@ -31,22 +31,8 @@
 #include "tdr_mt_dev.h"
 
 #define INI_MT_N 624
-#define INI_TILE 2048                 // stream positions per workgroup of ini_flags_kernel (1024 per parity)
-#define INI_MAX_TILES 2048            // ini_tail_kernel holds the tiles' minima in LDS: W <= 2^22
 #define INI_INF 0x7fffffff
 #define INI_MAX_NS 16
-
-static int64_t g_init_window = 1 << 21;   // words per window (tdr_config_tuning("init_window_words"))
-static int g_init_device = 1;             // 0: tdr_filter_initialize_particles keeps the host loop (A/B, tests)
-extern "C" int64_t tdr_config_init_window_words(int64_t w) {   // < 0: query only
-  if (w >= 0) g_init_window = std::min<int64_t>(std::max<int64_t>(cdiv(std::max<int64_t>(w, 1), INI_TILE) * INI_TILE, INI_TILE),
-                                                (int64_t)INI_TILE * INI_MAX_TILES);
-  return g_init_window;
-}
-extern "C" int tdr_config_init_device(int on) {   // < 0: query only
-  if (on >= 0) g_init_device = on ? 1 : 0;
-  return g_init_device;
-}
 
 struct IniParams {
   const float* rec;
@@ -352,7 +338,7 @@ static IniWs ini_ws(int64_t W) {
   s.total = (o + 255) / 256 * 256;
   return s;
 }
-extern "C" size_t tdr_init_workspace_bytes(void) { return ini_ws(g_init_window).total; }
+extern "C" size_t tdr_init_workspace_bytes(void) { return ini_ws(tdr_cfg().init_window).total; }
 
 // particles the reference's loop keeps: max_num, or (max_num / 10) groups of the scale loop's length
 static int ini_scales(float* sv) {
@@ -380,7 +366,7 @@ extern "C" int tdr_k_init_particles(uint32_t* state, const tdr_map_desc* map, co
   if (lo < 0 || hi > n || lo > hi || (hi > lo && (!st || cap < hi - lo)))
     return fail(TDR_ERR_ARG, "init_particles: bad range [%lld, %lld) of %lld particles", (long long)lo, (long long)hi, (long long)n);
   hipStream_t s = (hipStream_t)stream;
-  const IniWs S = ini_ws(g_init_window);
+  const IniWs S = ini_ws(tdr_cfg().init_window);
   char* base = reinterpret_cast<char*>(workspace);
   uint32_t* raw = reinterpret_cast<uint32_t*>(base);
   int* locG = reinterpret_cast<int*>(base + S.off_locG);

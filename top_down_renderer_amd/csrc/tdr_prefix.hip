@@ -14,7 +14,7 @@
 //    n < 24 576 otherwise                 prefix_serial_kernel: one wave, lane 0 adds in index order           mode 0
 //    else                                 prefix_exact_kernel: one workgroup, the older tie-list algorithm     mode 1
 //    tdr_config_prefix_small(0): no pfx_small_kernel (and no chain_head_kernel): the chunk walks start at the first addend
-//    tdr_config_prefix_head(n): addends pfx_walk_kernel hands to the serial head of pfx_exact_range at the very start
+//    tdr_config_tuning("prefix_head", n): addends pfx_walk_kernel hands to the serial head of pfx_exact_range at the very start
 //  tdr_uw_small (the update's statistics, n <= 32 768)
 //    uw_small_kernel<true>: the chains wave by wave (default); <false>: chunk by chunk on the whole workgroup
 //    (tdr_config_uw_waves(0))
@@ -103,7 +103,6 @@ __global__ __launch_bounds__(64) void prefix_serial_kernel(const float* __restri
 #define PFX_K 8
 #define PFX_TILE (PFX_THREADS * PFX_K)
 #define PFX_TIE_CAP 2048   // ties resolved per pass; a (never observed) denser tile is simply cut at that tie
-#define PFX_HEAD 2048      // leading elements added one by one: the running sum crosses most of its binades here
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding global store
 // (~1 us each time); in the prefix kernels the threads exchange data through LDS alone — global memory is read-only
@@ -1156,12 +1155,6 @@ __global__ __launch_bounds__(PFXM_THREADS) void pfx_chunk_summary_kernel(const f
                                                                          PfxChunk* __restrict__ ch, int c_first) {
   chain_summary_body<PFXM_THREADS, PFXM_K>(PfxRunSum{{w}, CHAIN_RUNSUM, 0.f}, n, ch, c_first);
 }
-#define PFXW_HEAD 64   // leading elements the walk adds one by one (tunable: tdr_config_tuning("prefix_head", n))
-static int g_pfx_head = PFXW_HEAD;
-extern "C" int tdr_config_prefix_head(int n) {   // < 0: query only
-  if (n >= 0) g_pfx_head = n < 1 ? 1 : (n > PFX_HEAD ? PFX_HEAD : n);
-  return g_pfx_head;
-}
 // A chunk the walk cannot take as one integer add (it holds a binade crossing or an irregular weight, or was
 // mispredicted), carried through in order by the walking workgroup
 __device__ __forceinline__ void pfx_walk_chunk(const float* __restrict__ w, long long lo, int cnt,
@@ -1276,15 +1269,10 @@ __global__ __launch_bounds__(PFXW_THREADS) void chain_walk_kernel(ChainSrc s, in
   });
   if (threadIdx.x == 0) *total_out = r;
 }
-static int g_pfx_small = 1;   // 0 = without the one-launch kernel (A/B and debugging)
-extern "C" int tdr_config_prefix_small(int on) {   // < 0: query only
-  if (on >= 0) g_pfx_small = on ? 1 : 0;
-  return g_pfx_small;
-}
 #define CHAIN_HEAD_N 32768
 // whole chunks at the start that the one-workgroup machinery takes (0: none; tdr_config_prefix_small(0) switches it off
 // for the running sum AND the statistics chains: the chunk walk from the first addend on, for A/B and debugging)
-static int chain_head_chunks(int64_t n) { return (g_pfx_small && n >= CHAIN_HEAD_N) ? CHAIN_HEAD_N / PFXM_CHUNK : 0; }
+static int chain_head_chunks(int64_t n) { return (tdr_cfg().pfx_small && n >= CHAIN_HEAD_N) ? CHAIN_HEAD_N / PFXM_CHUNK : 0; }
 static int chain_head_launch(const float* raw, const float* mean_dev, int kind, int n_head, float* r_out, hipStream_t st);
 // raw: [n] raw weights; kind 0: total = serial float sum of the non-NaN weights; kind 1: total = serial
 // float-accumulated sum of pow(w - *mean_dev, 2) over the non-NaN weights below *mean_dev.  workspace: chunk headers,
@@ -1749,11 +1737,6 @@ __global__ __launch_bounds__(WAVES ? UWS_THREADS : PFXW_THREADS) void uw_small_b
   const TdrBatchEntry& e = tab[blockIdx.x];
   uw_small_body<WAVES>(e.raw_w, e.last_dist, (int)e.n, e.w_out, e.info_out);
 }
-static int g_uw_waves = 1;   // 0 = the chains chunk by chunk on the whole workgroup (A/B and debugging)
-extern "C" int tdr_config_uw_waves(int on) {   // < 0: query only
-  if (on >= 0) g_uw_waves = on ? 1 : 0;
-  return g_uw_waves;
-}
 int tdr_uw_small(const float* raw, const float* last_dist, int64_t n, float* w, float* info, hipStream_t st) {
   if (n < 1 || n > 32768) return fail(TDR_ERR_ARG, "uw_small: n out of range");
   const size_t lds = ((size_t)n + (size_t)(n >> 5) + 1 + UWS_PAD) * sizeof(float);
@@ -1768,7 +1751,7 @@ int tdr_uw_small(const float* raw, const float* last_dist, int64_t n, float* w, 
       return fail(TDR_ERR_HIP, "uw_small: cannot raise the dynamic LDS limit");
     if (dev < 64) attr_set[dev] = true;
   }
-  if (g_uw_waves)
+  if (tdr_cfg().uw_waves)
     hipLaunchKernelGGL(uw_small_kernel<true>, dim3(1), dim3(UWS_THREADS), lds, st, raw, last_dist, (int)n, w, info);
   else
     hipLaunchKernelGGL(uw_small_kernel<false>, dim3(1), dim3(PFXW_THREADS), lds, st, raw, last_dist, (int)n, w, info);
@@ -1986,7 +1969,7 @@ static int prefix_multi(const float* w, int64_t n, float* runmax_out, float* pre
     const int rc = pfx_small(w, (int64_t)c_first * PFXM_CHUNK, runmax_out, prefix_out, st, tail);
     if (rc) return rc;
   }
-  const int head_len = tdr_config_prefix_head(-1);
+  const int head_len = tdr_cfg().pfx_head;
   hipLaunchKernelGGL(pfx_walk_kernel, dim3(1), dim3(PFXW_THREADS), 0, st, w, n, ch, nch, runmax_out, prefix_out,
                      head_len, c_first, (const float*)tail);
   hipLaunchKernelGGL(pfx_chunk_fill_kernel, dim3(nch), dim3(PFXM_THREADS), 0, st, w, n, (const PfxChunk*)ch,
@@ -1995,7 +1978,7 @@ static int prefix_multi(const float* w, int64_t n, float* runmax_out, float* pre
 }
 extern "C" int tdr_k_prefix(const float* w, int64_t n, float* runmax_out, void* workspace, void* stream) {
   if (!w || !runmax_out || n < 1) return fail(TDR_ERR_ARG, "prefix: bad arguments");
-  if (g_pfx_small && n >= TDR_PFX_SMALL_MIN_N && n <= TDR_PFX_SMALL_MAX_N) {
+  if (tdr_cfg().pfx_small && n >= TDR_PFX_SMALL_MIN_N && n <= TDR_PFX_SMALL_MAX_N) {
     const int rc = pfx_small(w, n, runmax_out, nullptr, (hipStream_t)stream);
     if (rc) return rc;
   } else if (workspace && n >= TDR_PFX_MULTI_MIN_N) {
@@ -2040,7 +2023,7 @@ static int batch_lds_attr(const void* fn) {
 int tdr_batch_update_weights(const TdrBatchEntry* tab, int k, int64_t n_max, hipStream_t st) {
   if (!tab || k < 1 || n_max < 1 || n_max > 32768) return fail(TDR_ERR_ARG, "batch_update_weights: bad arguments");
   const size_t lds = ((size_t)n_max + (size_t)(n_max >> 5) + 1 + UWS_PAD) * sizeof(float);
-  if (g_uw_waves) {
+  if (tdr_cfg().uw_waves) {
     if (int rc = batch_lds_attr(reinterpret_cast<const void*>(uw_small_batch_kernel<true>))) return rc;
     hipLaunchKernelGGL(uw_small_batch_kernel<true>, dim3((unsigned)k), dim3(UWS_THREADS), lds, st, tab);
   } else {

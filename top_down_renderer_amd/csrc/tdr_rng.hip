@@ -230,18 +230,12 @@ __global__ __launch_bounds__(64) void mt_uniform_kernel(uint32_t* __restrict__ s
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-// 0: every call's raw stream on one wave (A/B, tests); 1 (default): long calls in stretches (tdr_config_tuning("mt_stretches"))
-static int g_mt_stretches = 1;
-extern "C" int tdr_config_mt_stretches(int on) {   // < 0: query only
-  if (on >= 0) g_mt_stretches = on ? 1 : 0;
-  return g_mt_stretches;
-}
 // The raw stream [nblocks][624] behind `state` (mt_fill_kernel's layout): one wave walks it, or — a long call — stretches of
 // MT_JUMP_STRIDE blocks side by side, their first blocks reached by jumping ahead in rounds of doubling (round m: the 2^m
 // stretch starts there are, each 2^m stretches further).  Also the windows of the particle initialisation (tdr_init.hip).
 int tdr_mt_raw_stream(const uint32_t* state, int64_t nblocks, uint32_t* raw, hipStream_t s) {
   const int64_t nstretch = cdiv(nblocks, (int64_t)MT_JUMP_STRIDE);
-  if (g_mt_stretches && nstretch > 1 && nstretch <= ((int64_t)1 << MT_JUMP_LEVELS)) {
+  if (tdr_cfg().mt_stretches && nstretch > 1 && nstretch <= ((int64_t)1 << MT_JUMP_LEVELS)) {
     for (int m = 0; ((int64_t)1 << m) < nstretch; m++) {
       const int64_t have = (int64_t)1 << m, jumps = std::min(have, nstretch - have);
       hipLaunchKernelGGL(mt_jump_kernel, dim3((unsigned)jumps), dim3(1024), 0, s, state, raw, m);

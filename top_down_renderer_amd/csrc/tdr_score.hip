@@ -725,58 +725,9 @@ static void launch_finalize(FinalizeArgs& f, int64_t nslots, hipStream_t s) {
 
 // the Cartesian kernel likes twice as many, shorter waves (A/B on MI355X, config 4: x1 183 ms, x2 179 ms, x4 177 ms)
 #define TDR_CART_WAVE_MUL 2
-// Tuning knobs of the scoring launches (tdr_config_tuning, include/tdr.h) — defaults here, no environment variables: the
-// library reads nothing from the process environment.
-// score_waves: many short waves beat few long ones (A/B on MI355X, config 2: 16k waves 21.8 ms, 128k 15.2 ms): workgroups
-// of one ring chunk run together, so the concurrently touched part of the map is a thin annulus that L2 can hold, and
-// the slow (scattered) batches no longer leave a long tail.
-static int64_t g_score_waves = 131072;
-static int g_score_group = 0;   // 0: from the shapes (score_group_rings)
-static int g_su_group = 0;      // 0: from the shapes (tdr_score_workspace)
-static int64_t score_wave_target() { return g_score_waves; }
-extern "C" int tdr_config_init_ahead(int);         // tdr_score_init.hip
-extern "C" int tdr_config_batch_init_search(int);
-extern "C" int tdr_config_prefix_head(int);        // tdr_prefix.hip
-extern "C" int tdr_config_ray_block_major(int);    // tdr_score_ray.hip
-extern "C" int tdr_config_ray_patch(int);
-extern "C" int tdr_config_ray_borrow(int);
-extern "C" int tdr_config_cart_seg_rows(int);      // tdr_score_cart.hip
-extern "C" int tdr_config_mt_stretches(int);       // tdr_rng.hip
-extern "C" int tdr_config_su_wave_span(int);       // tdr_score_su.hip
-extern "C" int tdr_config_su_lds_pad(int);
-extern "C" int tdr_config_su_tail_groups(int);
-extern "C" int tdr_config_su_tail_parts(int);
-extern "C" int tdr_config_su_order_bucket(int);
-extern "C" int tdr_config_init_device(int);         // tdr_init.hip
-extern "C" int64_t tdr_config_init_window_words(int64_t);
-extern "C" int64_t tdr_config_cart_init_chunk(int64_t);   // tdr_score_cart_init.hip
-extern "C" int64_t tdr_config_tuning(const char* name, int64_t value) {   // value < 0: query only
-  if (!name) return -1;
-  const std::string n(name);
-  if (n == "score_waves") { if (value > 0) g_score_waves = value; return g_score_waves; }
-  if (n == "score_group") { if (value >= 0) g_score_group = (int)value; return g_score_group; }
-  if (n == "su_group") { if (value >= 0) g_su_group = (int)value; return g_su_group; }
-  if (n == "batch_init_search") return tdr_config_batch_init_search((int)std::max<int64_t>(value, -1));
-  if (n == "init_ahead") return tdr_config_init_ahead((int)std::min<int64_t>(std::max<int64_t>(value, -1), 3));
-  if (n == "prefix_head") return tdr_config_prefix_head((int)std::max<int64_t>(value, -1));
-  if (n == "ray_borrow") return tdr_config_ray_borrow((int)std::max<int64_t>(value, -1));
-  if (n == "ray_patch") return tdr_config_ray_patch((int)std::max<int64_t>(value, -1));
-  if (n == "ray_block_major") return tdr_config_ray_block_major((int)std::max<int64_t>(value, -1));
-  if (n == "cart_seg_rows") return tdr_config_cart_seg_rows((int)std::max<int64_t>(value, -1));
-  if (n == "mt_stretches") return tdr_config_mt_stretches((int)std::max<int64_t>(value, -1));
-  if (n == "su_lds_pad") return tdr_config_su_lds_pad((int)std::max<int64_t>(value, -1));
-  if (n == "su_tail_groups") return tdr_config_su_tail_groups((int)std::min<int64_t>(std::max<int64_t>(value, -1), 1 << 20));
-  if (n == "su_tail_parts") return tdr_config_su_tail_parts((int)std::min<int64_t>(std::max<int64_t>(value, -1), 8));
-  if (n == "su_order_bucket") return tdr_config_su_order_bucket((int)std::max<int64_t>(value, -1));
-  if (n == "su_wave_span") return tdr_config_su_wave_span((int)std::max<int64_t>(value, -1));
-  if (n == "init_device") return tdr_config_init_device((int)std::max<int64_t>(value, -1));
-  if (n == "init_window_words") return tdr_config_init_window_words(value > 0 ? value : -1);
-  if (n == "cart_init_chunk") return tdr_config_cart_init_chunk(value > 0 ? value : -1);
-  return -1;
-}
 static void choose_chunks(int64_t n, int nr, int& rpc, int& nchunks, int target_mul = 1) {
   int64_t nbatches = cdiv(std::max<int64_t>(n, 1), 64);
-  int64_t want = std::max<int64_t>(1, cdiv(score_wave_target() * target_mul, nbatches));  // enough waves to fill the chip
+  int64_t want = std::max<int64_t>(1, cdiv(tdr_cfg().score_waves * target_mul, nbatches));  // enough waves to fill the chip
   nchunks = (int)std::min<int64_t>(nr, want);
   rpc = (int)cdiv(nr, nchunks);
   nchunks = (int)cdiv(nr, rpc);
@@ -795,7 +746,7 @@ __global__ void utab_kernel(const float* __restrict__ tab, int64_t n2, float sca
 // never the size of one launch or shard: the partition of a particle's score into partial sums is then the same in an
 // N-rank run as in the 1-rank run.  Aim: >= 2048 workgroups.  tdr_config_tuning("score_group", g) overrides (tuning).
 static int score_group_rings(int nb, int nr, int rf, int64_t n_total) {
-  const int forced = g_score_group;
+  const int forced = tdr_cfg().score_group;
   const int64_t ring_bytes = std::max<int64_t>((int64_t)nb * rf * 4, 1);
   int g = (int)std::min<int64_t>(8, (32 * 1024) / ring_bytes);
   const int64_t chunks_wanted = cdiv(2048, cdiv(std::max<int64_t>(n_total, 1), 256));
@@ -833,7 +784,7 @@ static ScoreWs score_ws(int ncls, int nb, int nr, int64_t n, int64_t n_total) {
   w.su = tdr_su_shape_ok(nb, nr, w.group, n_total) && tdr_cmap_words(ncls) != 0;
   w.su_group = w.group;
   {
-    const int forced = g_su_group;
+    const int forced = tdr_cfg().su_group;
     // eight rings per group where that divides the image and still leaves thousands of workgroups: a sector's mask is
     // staged half as often (config 2: 3.50 against 3.56 ms; 16 rings: 3.69, the staged boxes grow)
     if (w.su && w.group == 4 && nr % 8 == 0 && cdiv(n_total, 256) * (nr / 8) >= 4096) w.su_group = 8;
@@ -996,12 +947,6 @@ static int check_map_addressing(const tdr_map_desc* map, int rf, const char* who
   return TDR_OK;
 }
 
-// The compact records are used whenever the map has them; tdr_config_compact(0) forces the dense ones (A/B, tests).
-static int g_use_compact = 1;
-extern "C" int tdr_config_compact(int on) {   // < 0: query only
-  if (on >= 0) g_use_compact = on ? 1 : 0;
-  return g_use_compact;
-}
 extern "C" int tdr_cmap_words(int ncls);
 extern "C" size_t tdr_cmap_tile_words(int ncls, int rows, int cols);
 
@@ -1012,7 +957,7 @@ static int compact_lc(const tdr_map_desc* map) {   // a tile of compact records 
   return map->cwords == 1 ? 3 : (map->cwords == 2 ? 2 : 1);
 }
 static bool map_has_compact(const tdr_map_desc* map, int rf) {
-  if (!(g_use_compact && map->cwords > 0 && map->crec && map->dict && map->dict_n > 0 && rf <= 12 &&
+  if (!(tdr_cfg().use_compact && map->cwords > 0 && map->crec && map->dict && map->dict_n > 0 && rf <= 12 &&
         (map->cwords == tdr_cmap_words(map->ncls) || map_is_wide(map, rf))))
     return false;
   if (map->dict_n > (map_is_wide(map, rf) ? TDR_CMAP_WIDE_MAX_DICT : TDR_CMAP_MAX_DICT)) return false;
@@ -1105,7 +1050,7 @@ extern "C" void tdr_score_ctx_destroy(tdr_score_ctx* c) {
   delete c;
 }
 extern "C" float tdr_score_ctx_span(const tdr_score_ctx* c) {   // the span the context's tuner has settled on so far
-  return c ? c->tuner.best : tdr_config_shift_uniform_span(-1.f);
+  return c ? c->tuner.best : tdr_cfg().su_span;
 }
 extern "C" int64_t tdr_score_ctx_trial_calls(const tdr_score_ctx* c) {   // launches spent on trial spans so far
   return c ? c->tuner.trial_calls : 0;
@@ -1340,8 +1285,7 @@ extern "C" int tdr_k_score_polar_ctx(const tdr_map_desc* map, const float* tab, 
     L.tail_k = W.su_tail_k; L.tail_q = W.su_tail_q; L.rows = W.su_rows;
     L.fac = ctx && ctx->fac && ctx->fac_nb == nb && ctx->fac_nr == nr ? ctx->fac : nullptr;
     L.uscale = uniform_scale;
-    L.wave_span = tdr_su_wave_span();
-    L.ray_split = tdr_ray_splits(nb, nr, n, tdr_ray_block_major(L));
+    L.ray_split = tdr_ray_splits(nb, nr, n, tdr_cfg().ray_block_major && L.fac != nullptr);
     L.ws = reinterpret_cast<int32_t*>(workspace + W.off_su);
     TunerScope tuner_scope(ctx, s);   // (closes the tuner's measurement on every way out)
     L.span = tdr_su_span_begin(ctx ? &ctx->tuner : nullptr,
@@ -1529,7 +1473,7 @@ extern "C" int tdr_k_score_cart(const tdr_map_desc* map, const float* scan_pk, i
       // (which particles count as dense: four times the polar launch's span — a Cartesian window is a rotated rectangle of
       // rows x cols cells and neighbours a few dozen cells apart still share most of their lines; measured on config 4, ms per
       // step at 8 / 16 / 32 / 64 cells: 32.6 / 29.2 / 28.8 / 28.5, the float kernel 36.9)
-      if (int rc = tdr_cart_int_launch(a, map, rf, desc_ws, iws, 4.f * tdr_config_shift_uniform_span(-1.f), s, &io)) return rc;
+      if (int rc = tdr_cart_int_launch(a, map, rf, desc_ws, iws, 4.f * tdr_cfg().su_span, s, &io)) return rc;
       int_form = true;
     } else if (int rc = tdr_cart_skip_launch(a, map, rf, desc_ws, s)) return rc;
   } else {

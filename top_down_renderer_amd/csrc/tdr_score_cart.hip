@@ -606,16 +606,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void s
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static int g_cart_skip = 1;
-extern "C" int tdr_config_cart_skip(int on) {   // < 0: query only
-  if (on >= 0) g_cart_skip = on ? 1 : 0;
-  return g_cart_skip;
-}
 extern "C" int tdr_cmap_words(int ncls);
 extern "C" size_t tdr_cmap_tile_words(int ncls, int rows, int cols);
 
 bool tdr_cart_skip_ok(const tdr_map_desc* map, int rf) {
-  return g_cart_skip && rf <= 12 && map->cwords > 0 && map->cwords == tdr_cmap_words(map->ncls) && map->crec && map->dict &&
+  return tdr_cfg().cart_skip && rf <= 12 && map->cwords > 0 && map->cwords == tdr_cmap_words(map->ncls) && map->crec && map->dict &&
          map->dict_n > 0 && map->dict_n <= TDR_CMAP_MAX_DICT;
 }
 
@@ -923,12 +918,11 @@ __global__ __launch_bounds__(256) void score_cart_ray_kernel(CartRayArgs a) {
 // ---- host side of the integer form ---------------------------------------------------------------------------------------
 extern "C" size_t tdr_cmap_plane_offset_words(int ncls, int rows, int cols);
 extern "C" size_t tdr_cmap_plane_words(int ncls, int rows, int cols);
-extern "C" int tdr_config_shift_uniform(int mode);
 
 bool tdr_cart_int_ok(const tdr_map_desc* map, int rf, int rows, int cols, int64_t n_total) {
   // (mode 0 of tdr_config_shift_uniform switches the integer forms off altogether: A/B measurements, tests)
-  return tdr_config_shift_uniform(-1) != 0 && tdr_cart_skip_ok(map, rf) && tdr_ray_map_ok(map) && rows < 65536 && cols < 65536 &&
-         (tdr_config_shift_uniform(-1) == 2 || n_total >= 4096);
+  return tdr_cfg().su_mode != 0 && tdr_cart_skip_ok(map, rf) && tdr_ray_map_ok(map) && rows < 65536 && cols < 65536 &&
+         (tdr_cfg().su_mode == 2 || n_total >= 4096);
 }
 static inline int64_t cart_ray_desc_words(int rows, int cols) {
   return ((int64_t)rows * cart_ray_blocks(cols) * cart_ray_gq(cols) * 64 + 1) / 2 + 64;
@@ -948,15 +942,6 @@ int64_t tdr_cart_int_words(int rows, int cols, int64_t n) {
   return tdr_cart_desc_words(rows, cols) + cart_ray_desc_words(rows, cols) + (int64_t)rows * cols + 64 + cart_order_ws(n).total +
          cart_su_words(rows, cols);
 }
-// rows of a segment of score_cart_su_kernel (a multiple of 4; tdr_config_tuning("cart_seg_rows", n)): the smaller the
-// segment, the smaller the box of cells a wave stages and the likelier it holds no unknown cell; the larger, the fewer
-// box computations.  Measured on config 4 (ms per step): see DESIGN.md 5.5
-static int g_cart_seg_rows = 32;
-extern "C" int tdr_config_cart_seg_rows(int n) {   // < 0: query only; 0: the assembly loop off (A/B: the plain kernel)
-  if (n >= 0) g_cart_seg_rows = n - n % 4;
-  return g_cart_seg_rows;
-}
-
 int tdr_cart_int_launch(CartArgs a, const tdr_map_desc* map, int rf, uint32_t* desc_ws, int32_t* ws, float span, hipStream_t s,
                         CartIntOut* out) {
   const int64_t n = a.n;
@@ -996,7 +981,7 @@ int tdr_cart_int_launch(CartArgs a, const tdr_map_desc* map, int rf, uint32_t* d
   const int32_t* flags = ints + 4;
   // the dense share through score_cart_su_kernel (generated sample loop, staged mask) when the records are the two-dword
   // ones: its own descriptors, the lists of bins with several classes per column chunk
-  const bool su_kernel = rf == 8 && tdr_has_kslot(map->ncls, rf) && map->cwords == 2 && g_cart_seg_rows >= 4 && (a.rows & 3) == 0 &&
+  const bool su_kernel = rf == 8 && tdr_has_kslot(map->ncls, rf) && map->cwords == 2 && tdr_cfg().cart_seg_rows >= 4 && (a.rows & 3) == 0 &&
                          a.rows >= 8 && (int64_t)a.rows * a.cols * 16 < (int64_t)1 << 31;
   const int cpc_su = (a.cpc + CART_ASM_NCOL - 1) / CART_ASM_NCOL * CART_ASM_NCOL;
   const int nchunks_su = (int)cdiv(a.cols, cpc_su);   // <= a.nchunks: the partial sums' rows suffice
@@ -1055,7 +1040,7 @@ int tdr_cart_int_launch(CartArgs a, const tdr_map_desc* map, int rf, uint32_t* d
     out->nchunks_dense = a.nchunks;
     if (su_kernel) {
       CartSuArgs x;
-      x.full_list = full_list; x.full_cnt = full_cnt; x.list_cap = list_cap; x.seg_rows = g_cart_seg_rows;
+      x.full_list = full_list; x.full_cnt = full_cnt; x.list_cap = list_cap; x.seg_rows = tdr_cfg().cart_seg_rows;
       x.bdesc = bdesc; x.pbytes = plane_bytes; x.pbase0 = pbase - plane_bytes;
       x.stats = tdr_profile_stats_ptr();
       d.desc = desc_su;

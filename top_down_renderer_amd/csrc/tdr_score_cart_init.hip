@@ -45,8 +45,6 @@ const CartInitRot& cart_init_rot() {
   return r;
 }
 
-int64_t g_cart_init_chunk = 4096;   // listed particles per scoring launch (tdr_config_tuning("cart_init_chunk"))
-
 inline int64_t pad64(int64_t x) { return cdiv(x, 64) * 64; }
 
 struct CartInitWs {   // offsets in floats, every part 256-byte aligned
@@ -56,7 +54,7 @@ struct CartInitWs {   // offsets in floats, every part 256-byte aligned
 CartInitWs cart_init_ws(int ncls, int rows, int cols, int64_t n, int64_t n_total) {
   CartInitWs w;
   n = std::max<int64_t>(n, 1);
-  w.chunk = std::min<int64_t>(g_cart_init_chunk, n);
+  w.chunk = std::min<int64_t>(tdr_cfg().cart_init_chunk, n);
   w.ccap = pad64(w.chunk * cart_init_rot().nrot);
   w.list = 0;                                  // int32 [64 + n]: [0] = count, the list from [64]
   w.order = w.list + pad64(64 + n);            // int32 [n]: the particles by pose; its scratch lies in the chunk's part
@@ -132,11 +130,6 @@ __global__ __launch_bounds__(256) void cart_init_select_kernel(const float* __re
 }
 
 }  // namespace
-
-extern "C" int64_t tdr_config_cart_init_chunk(int64_t particles) {   // < 1: query only
-  if (particles >= 1) g_cart_init_chunk = std::min<int64_t>(particles, 1 << 24);
-  return g_cart_init_chunk;
-}
 
 extern "C" size_t tdr_score_cart_init_workspace_floats(int ncls, int rows, int cols, int64_t n, int64_t n_total) {
   return (size_t)cart_init_ws(ncls, rows, cols, n, n_total).total;

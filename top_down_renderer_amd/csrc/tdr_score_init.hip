@@ -923,12 +923,6 @@ __global__ __launch_bounds__(64) void init_fixup_batch_kernel(const InitArgs* __
   init_fixup_body(a.res_flag, a.n, a.fp.regularization, fix[e].raw_w, (int64_t)(b - blk[e]) * 64 + threadIdx.x);
 }
 
-static int g_init_mfma = 1;   // 0 = vector-unit search only (A/B and debugging)
-static bool init_use_mfma() { return g_init_mfma != 0; }
-extern "C" int tdr_config_init_mfma(int on) {   // < 0: query only
-  if (on >= 0) g_init_mfma = on ? 1 : 0;
-  return g_init_mfma;
-}
 // bytes of the scratch behind tdr_map_desc.rec16 (0: this record size has no matrix-core search)
 extern "C" size_t tdr_map_rec16_bytes(int ncls, int rows, int cols) {
   if (ncls < 1 || ncls > 7 || rows < 1 || cols < 1) return 0;
@@ -937,16 +931,6 @@ extern "C" size_t tdr_map_rec16_bytes(int ncls, int rows, int cols) {
   const uint64_t bytes = (uint64_t)(rows + 2) * (uint64_t)(cols + 2) * 32 + 32;   // + the all-zero record behind the grid
   if (bytes > 0xFFFFFFFFull || (uint64_t)(cols + 2) * 32 >= (1u << 24)) return 0;
   return (size_t)bytes;
-}
-// Rebuilding the half records is one pass over the whole map: it pays from a few thousand particles on (4000^2 cells:
-// 0.35 ms, the price of searching ~2000 particles with 256 x 256 windows on the fly).  Filters below the threshold
-// ignore the scratch — the filter's TOTAL particle count decides (n_total, the same on every rank), so that the ranks of
-// a sharded filter take the kernel the one-rank filter takes and choose the same rotations where candidates tie.
-// tdr_config_rec16_min_particles(INT64_MAX) turns the path off (A/B).
-static int64_t g_rec16_min = 8192;
-extern "C" int64_t tdr_config_rec16_min_particles(int64_t n) {   // < 0: query only
-  if (n >= 0) g_rec16_min = n;
-  return g_rec16_min;
 }
 // Rows per LDS scan image of score_init_half_kernel: 2 nb + R + c with the c in [0, 16) that gives the ds_read_b128 of
 // the candidates' rows the fewest bank conflicts.  A lane (candidate m, ring q) reads row q * img + i + shift_m; the LDS
@@ -993,12 +977,6 @@ static int init_half_image_rows(int nb, int R) {
   }
   return 2 * nb + R + best_c;
 }
-// record loads the half-record search keeps in flight per wave (1..3): tdr_config_tuning("init_ahead")
-static int g_init_ahead = 1;
-extern "C" int tdr_config_init_ahead(int v) {   // < 1: query only
-  if (v >= 1) g_init_ahead = std::min(v, 3);
-  return g_init_ahead;
-}
 
 // ---- what the standalone and the batched search share on the host ------------------------------------------------------
 // The matrix-core pass of a search — ONE choice for both paths: the passes pick differently where candidates tie to
@@ -1006,9 +984,9 @@ extern "C" int tdr_config_init_ahead(int v) {   // < 1: query only
 int tdr_score_init_pass(const tdr_map_desc* map, int nb, int64_t n_total) {
   const int rf = map->rec_floats;
   const bool ks = tdr_has_kslot(map->ncls, rf);
-  if (!init_use_mfma()) return TDR_INIT_PASS_VECTOR;
+  if (!tdr_cfg().init_mfma) return TDR_INIT_PASS_VECTOR;
   if ((rf == 4 || rf == 8) && map->ncls <= 7 && map->rec16 && tdr_map_rec16_bytes(map->ncls, map->rows, map->cols) != 0 &&
-      n_total >= g_rec16_min && (size_t)4 * (2 * nb + 20) * 16 + (size_t)4 * (nb + 8) * 8 <= 64 * 1024)
+      n_total >= tdr_cfg().rec16_min && (size_t)4 * (2 * nb + 20) * 16 + (size_t)4 * (nb + 8) * 8 <= 64 * 1024)
     return TDR_INIT_PASS_HALF;
   if (rf == 8 && (ks || map->ncls == 7)) return TDR_INIT_PASS_SPLIT;
   if (rf == 12 || rf == 16) return TDR_INIT_PASS_WIDE;
@@ -1051,18 +1029,11 @@ static int launch_half_records(const tdr_map_desc* map, const tdr_filter_params*
 struct HalfShape { int ahead, img; size_t lds; };
 static HalfShape init_half_shape(int nb) {
   HalfShape h;
-  h.ahead = g_init_ahead;
+  h.ahead = tdr_cfg().init_ahead;
   const int R = h.ahead + 1;
   h.img = init_half_image_rows(nb, R);
   h.lds = (size_t)4 * h.img * 16 + (size_t)4 * (nb + 2 * R) * 8;
   return h;
-}
-// tdr_config_tuning("batch_init_search"): 1 = a filter that may hold a particle without a heading joins the batch of
-// tdr_batch_step, its search part of the batch's scoring stage (0, the default: it runs its standalone calls)
-static int g_batch_init_search = 0;
-extern "C" int tdr_config_batch_init_search(int v) {   // < 0: query only
-  if (v >= 0) g_batch_init_search = v ? 1 : 0;
-  return g_batch_init_search;
 }
 
 int tdr_score_init_search(const tdr_map_desc* map, const float* tab, const float* utab, const float* scan_pk, int nb,

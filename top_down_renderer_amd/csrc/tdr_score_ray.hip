@@ -62,23 +62,8 @@
 #define RAY_PR 16             // rings of a patch
 #define RAY_PG 16             // scan rows of a unit (four steps of four directions)
 #define RAY_PATCH_MAX_NB 256
-static bool g_ray_borrow = true;   // empty bins borrow a neighbour's class plane for their known bit (ray_prep_kernel)
-extern "C" int tdr_config_ray_borrow(int on) {   // < 0: query only
-  if (on >= 0) g_ray_borrow = on != 0;
-  return g_ray_borrow ? 1 : 0;
-}
-static bool g_ray_patch = true;
-extern "C" int tdr_config_ray_patch(int on) {   // < 0: query only
-  if (on >= 0) g_ray_patch = on != 0;
-  return g_ray_patch ? 1 : 0;
-}
-static bool g_ray_bm = true;
-extern "C" int tdr_config_ray_block_major(int on) {   // < 0: query only
-  if (on >= 0) g_ray_bm = on != 0;
-  return g_ray_bm ? 1 : 0;
-}
-static inline bool ray_bm(const SuLaunch& L) { return g_ray_bm && L.fac != nullptr; }
-static inline bool ray_patch(const SuLaunch& L) { return ray_bm(L) && g_ray_patch && L.nb % RAY_PG == 0 && L.nb <= RAY_PATCH_MAX_NB; }
+static inline bool ray_bm(const SuLaunch& L) { return tdr_cfg().ray_block_major && L.fac != nullptr; }
+static inline bool ray_patch(const SuLaunch& L) { return ray_bm(L) && tdr_cfg().ray_patch && L.nb % RAY_PG == 0 && L.nb <= RAY_PATCH_MAX_NB; }
 static inline int ray_gq(int nr, bool bm) { return bm ? 1 : (nr <= 64 ? 1 : (nr <= 128 ? 2 : 4)); }
 static inline int ray_blocks(int nr, bool bm) { return (int)cdiv(nr, 64 * ray_gq(nr, bm)); }
 // (the first order pads to whole blocks of GQ steps: never less than the block-major order needs)
@@ -509,14 +494,8 @@ bool tdr_ray_map_ok(const tdr_map_desc* map) {
   return map->crec && map->dict && map->cwords == tdr_cmap_words(map->ncls) && map->dict_n > 0 &&
          map->dict_n <= TDR_CMAP_MAX_DICT && tdr_cmap_plane_words(map->ncls, map->rows, map->cols) != 0;
 }
-static int g_ray_split = 0;   // 0: chosen per launch
-extern "C" int tdr_config_ray_split(int k) {   // >= 1: force; 0: per launch (default); < 0: query only
-  if (k >= 0) g_ray_split = k > TDR_RAY_MAX_SPLIT ? TDR_RAY_MAX_SPLIT : k;
-  return g_ray_split;
-}
-bool tdr_ray_block_major(const SuLaunch& L) { return ray_bm(L); }
 int tdr_ray_splits(int nb, int nr, int64_t n, bool bm) {
-  if (g_ray_split > 0) return g_ray_split;
+  if (tdr_cfg().ray_split > 0) return tdr_cfg().ray_split;   // forced (tdr_config_ray_split)
   // waves per particle: a window is nb * blocks rows of up to four steps; small launches split it to fill the chip (the
   // sums are exact: any split gives the same bits)
   const int64_t rows = (int64_t)nb * ray_blocks(nr, bm);
@@ -541,7 +520,7 @@ int tdr_ray_prepare(const SuLaunch& L, const SuWs& W, hipStream_t s) {
                      reinterpret_cast<float*>(base + W.ray_tab), reinterpret_cast<uint16_t*>(base + W.ray_desc),
                      reinterpret_cast<uint32_t*>(base + W.ray_multi), ints + 3, ints + 4, L.fac,
                      L.uniform_scale ? L.uscale : 0.f, L.res, reinterpret_cast<float*>(base + W.ray_rad), bm ? 1 : 0,
-                     ray_patch(L) ? 1 : 0, g_ray_borrow ? 1 : 0);
+                     ray_patch(L) ? 1 : 0, tdr_cfg().ray_borrow ? 1 : 0);
   LAUNCH_CHECK("ray_prep");
   return TDR_OK;
 }

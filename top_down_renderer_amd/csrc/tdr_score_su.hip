@@ -387,107 +387,6 @@ __global__ __launch_bounds__(64) void su_rank_scatter_kernel(const uint32_t* __r
   }
 }
 
-// ---- re-routing by the wave's own box ---------------------------------------------------------------------------------------
-// su_key_kernel calls a particle dense when its 64 neighbours in the ALL-heading locality order lie close together.  The
-// shift-uniform kernel's waves, though, hold 64 neighbours of ONE heading bin: where the headings are many and the cloud is
-// wide (config 5: 8 clusters x 40 headings, 780 particles per cluster and heading over ~25 000 cells) those lie tens of cells
-// apart, the wave's windows do not fit its quarter of the mask staging area, and the wave takes the kernel's far path — one
-// gather per SAMPLE, a quarter of config 5's wave-sectors in round 4.  Such a wave is what the ray-mapped kernel is for: this
-// pass, behind the heading-bin order, moves every wave whose own particles spread over more than `wave_span` cells to the
-// scattered share (three small kernels; the sums are exact integers: whichever kernel scores a particle, the bits agree).
-__global__ __launch_bounds__(256) void su_wave_far_kernel(const float* __restrict__ st, int64_t cap, const int32_t* __restrict__ slots,
-                                                          const int32_t* __restrict__ counts, float wave_span,
-                                                          int32_t* __restrict__ keep, int32_t* __restrict__ moved) {
-  const int lane = threadIdx.x & 63;
-  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), base = w * 64;
-  if (base >= (int64_t)counts[0]) return;
-  const int32_t p = slots[base + lane];
-  float x0 = 3.0e38f, x1 = -3.0e38f, y0 = 3.0e38f, y1 = -3.0e38f;
-  if (p >= 0) {
-    const float sc = st[TDR_ST_SCALE * cap + p];
-    const float x = st[TDR_ST_DX * cap + p] * sc + st[TDR_ST_INIT_X * cap + p];
-    const float y = st[TDR_ST_DY * cap + p] * sc + st[TDR_ST_INIT_Y * cap + p];
-    x0 = x1 = x;
-    y0 = y1 = y;
-  }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    x0 = fminf(x0, __shfl_xor(x0, d)); x1 = fmaxf(x1, __shfl_xor(x1, d));
-    y0 = fminf(y0, __shfl_xor(y0, d)); y1 = fmaxf(y1, __shfl_xor(y1, d));
-  }
-  const int nvalid = __popcll(__ballot(p >= 0));
-  // (a NaN centre makes the comparison false: the wave stays — the kernel's own checks deal with it)
-  const bool far = (x1 - x0 > wave_span) || (y1 - y0 > wave_span);
-  if (lane == 0) {
-    keep[w] = far ? 0 : 1;
-    moved[w] = far ? nvalid : 0;
-  }
-}
-// One workgroup: exclusive sums of the kept waves (x 64 slots) and of the moved particles; the new counts
-__global__ __launch_bounds__(256) void su_compact_offsets_kernel(int32_t* __restrict__ keep, int32_t* __restrict__ moved,
-                                                                 int32_t* __restrict__ counts, int32_t* __restrict__ old_counts) {
-  __shared__ int sa[256], sb[256];
-  const int c0 = counts[0], c1 = counts[1], c2 = counts[2];
-  const int nw = c0 >> 6;
-  int carry_a = 0, carry_b = 0;
-  for (int base = 0; base < nw; base += 256) {
-    const int w = base + threadIdx.x;
-    const int a = w < nw ? keep[w] : 0, b = w < nw ? moved[w] : 0;
-    sa[threadIdx.x] = a;
-    sb[threadIdx.x] = b;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {   // Hillis-Steele inclusive scan
-      const int va = threadIdx.x >= d ? sa[threadIdx.x - d] : 0;
-      const int vb = threadIdx.x >= d ? sb[threadIdx.x - d] : 0;
-      __syncthreads();
-      sa[threadIdx.x] += va;
-      sb[threadIdx.x] += vb;
-      __syncthreads();
-    }
-    if (w < nw) {
-      // keep[w]: the wave's new first slot, or -1; moved[w]: the rank of its first particle among the moved ones
-      keep[w] = a ? (carry_a + sa[threadIdx.x] - a) * 64 : -1;
-      moved[w] = carry_b + sb[threadIdx.x] - b;
-    }
-    carry_a += sa[255];
-    carry_b += sb[255];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    old_counts[0] = c0; old_counts[1] = c1; old_counts[2] = c2;
-    counts[0] = carry_a * 64;
-    counts[1] = c1 + carry_b;
-    counts[2] = carry_a * 64 + c1 + carry_b;
-  }
-}
-// slot t of the old list -> its place in the new one: kept waves close ranks, then the old scattered share, then the moved
-__global__ __launch_bounds__(256) void su_compact_scatter_kernel(const int32_t* __restrict__ slots, const int32_t* __restrict__ keep,
-                                                                 const int32_t* __restrict__ moved,
-                                                                 const int32_t* __restrict__ counts,
-                                                                 const int32_t* __restrict__ old_counts, int32_t* __restrict__ out) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int oc0 = old_counts[0], oc1 = old_counts[1];
-  if (t >= (int64_t)oc0 + oc1) return;
-  const int32_t p = slots[t];
-  if (t >= oc0) {   // the old scattered share, in its order
-    out[(int64_t)counts[0] + (t - oc0)] = p;
-    return;
-  }
-  const int64_t w = t >> 6;   // (a wave of this kernel is a wave of the list: blocks of 256 slots)
-  const int32_t k = keep[w];
-  const uint64_t valid = __ballot(p >= 0);
-  if (k >= 0) {
-    out[(int64_t)k + (t & 63)] = p;
-  } else if (p >= 0) {
-    const int rank = __popcll(valid & (((uint64_t)1 << (t & 63)) - 1));
-    out[(int64_t)counts[0] + oc1 + moved[w] + rank] = p;
-  }
-}
-__global__ void su_copy_slots_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ counts, int32_t* __restrict__ dst) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < (int64_t)counts[2]) dst[t] = src[t];
-}
-
 // LDS of the scoring kernel, ONE object so that the dictionary sits at LDS address 0 (the assembly loop reads it there)
 struct SuLds {
   uint32_t dict[TDR_CMAP_MAX_DICT];   // integer dictionary
@@ -1025,25 +924,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-// 0 = never, 1 = when it pays (default), 2 = whenever the shapes allow (tests: small filters, heavy padding)
-static int g_su_mode = 1;
-extern "C" int tdr_config_shift_uniform(int mode) {   // < 0: query only
-  if (mode >= 0) g_su_mode = mode > 2 ? 2 : mode;
-  return g_su_mode;
-}
 extern "C" size_t tdr_cmap_tile_words(int ncls, int rows, int cols);   // tdr_cmap.hip
 extern "C" size_t tdr_cmap_plane_offset_words(int ncls, int rows, int cols);
 extern "C" size_t tdr_cmap_plane_words(int ncls, int rows, int cols);
-// map cells the 64 locality neighbours of a "dense" particle may span: fixed (the config call), or — the default — tuned
-// while running, starting from SU_SPAN_START
-#define SU_SPAN_START 16.f
-static bool g_su_span_fixed = false;
-static float g_su_span = SU_SPAN_START;
-extern "C" float tdr_config_shift_uniform_span(float cells) {   // >= 0: fix it (0: every particle counts as dense);
-  if (cells >= 0.f) { g_su_span = cells; g_su_span_fixed = true; }   // -1: query only; below -1.5: back to tuning
-  else if (cells < -1.5f) { g_su_span = SU_SPAN_START; g_su_span_fixed = false; }
-  return g_su_span;
-}
+// The span (TdrConfig::su_span): fixed by the config call, or — the default — tuned while running.
 // Which span is fastest depends on the particle set (how far the same-heading neighbours of a moderately dense particle
 // lie apart): measured on MI355X, config 2 wants 8 (7.00 against 7.29 ms at 24), config 5 wants 16 (15.9 against 17.7 at 8),
 // a cluster with a single heading wants 24 or more (4.6 against 6.9 ms at 8).
@@ -1061,9 +945,10 @@ constexpr int kSpanSkip = 30;         // calls of a new shape before the first t
 constexpr int kSpanRetune = 4000;     // launches between two trials
 }  // namespace
 float tdr_su_span_begin(SpanTuner* t, int64_t shape, hipStream_t s) {
-  if (g_su_span_fixed || !t) return g_su_span;
-  if (!t->e0 && (hipEventCreate(&t->e0) != hipSuccess || hipEventCreate(&t->e1) != hipSuccess)) return g_su_span;
-  if (shape != t->shape) { t->shape = shape; t->phase = -kSpanSkip; t->trial = 0; t->best_ms = 3.0e38f; t->pending = false; t->best = t->round_best = g_su_span; }
+  const TdrConfig& cfg = tdr_cfg();
+  if (cfg.su_span_fixed || !t) return cfg.su_span;
+  if (!t->e0 && (hipEventCreate(&t->e0) != hipSuccess || hipEventCreate(&t->e1) != hipSuccess)) return cfg.su_span;
+  if (shape != t->shape) { t->shape = shape; t->phase = -kSpanSkip; t->trial = 0; t->best_ms = 3.0e38f; t->pending = false; t->best = t->round_best = cfg.su_span; }
   if (t->pending) {   // the candidate timed by an earlier launch — if its events are not through yet, ask again next time
     if (hipEventQuery(t->e1) != hipSuccess) return t->best;
     float ms = 0.f;
@@ -1090,32 +975,17 @@ float tdr_su_span_begin(SpanTuner* t, int64_t shape, hipStream_t s) {
   return kSpanCand[t->phase];
 }
 void tdr_su_span_end(SpanTuner* t, hipStream_t s) {
-  if (g_su_span_fixed || !t || !t->open) return;
+  if (tdr_cfg().su_span_fixed || !t || !t->open) return;
   t->open = false;
   t->pending = hipEventRecord(t->e1, s) == hipSuccess;
-}
-// cells a wave's own 64 particles may spread over before the wave is re-routed to the ray-mapped kernel (0: never — the
-// default: MEASURED, AND IT DOES NOT PAY.  MI355X, ms per step at 0 / 24 / 32 / 40 / 56 cells: config 5 14.40 / 16.16 / 15.19 /
-// 14.87 / 14.31, config 2 4.67 / 6.58 / 5.69 / 5.67 / 5.34 — a particle on the shift-uniform kernel's far path costs ~68 ns, on
-// the ray-mapped kernel ~80 ns: the waves this moves are cheaper where they are.  DESIGN.md 5.1.)
-static float g_su_wave_span = 0.f;
-extern "C" int tdr_config_su_wave_span(int cells) {   // < 0: query only
-  if (cells >= 0) g_su_wave_span = (float)cells;
-  return (int)g_su_wave_span;
-}
-float tdr_su_wave_span() { return g_su_wave_span; }
-static int g_su_lds_pad = 0;   // EXPERIMENT: dynamic LDS bytes per workgroup (limits the waves per SIMD without touching the code)
-extern "C" int tdr_config_su_lds_pad(int bytes) {
-  if (bytes >= 0) g_su_lds_pad = bytes;
-  return g_su_lds_pad;
 }
 static std::atomic<int64_t> g_su_launches{0};   // diagnostics only
 extern "C" int64_t tdr_shift_uniform_launches(void) { return g_su_launches.load(); }
 // Padding costs up to 63 idle lanes per heading bin: the order pays once a bin holds a few waves on average.
 bool tdr_su_shape_ok(int nb, int nr, int group, int64_t n_total) {
-  if (g_su_mode == 0) return false;
+  if (tdr_cfg().su_mode == 0) return false;
   if (group % 4 != 0 || nb > 4095) return false;
-  if (g_su_mode == 2) return true;   // tests: small filters and small windows too
+  if (tdr_cfg().su_mode == 2) return true;   // tests: small filters and small windows too
   // A small window does not pay for the per-sector set-up of the shift-uniform kernel (bounding box, mask staging, three
   // barriers) nor for a wave per particle: at the reference node's own 100 x 25 bins and 20 000 particles the integer form
   // takes 0.23 ms (0.18 + 0.10, side by side) where the float kernel takes 0.11 (profiles/r04_bench_ref_integer_form_v1.json).
@@ -1129,25 +999,14 @@ bool tdr_su_shape_ok(int nb, int nr, int group, int64_t n_total) {
 // kernel, 0.085 ms of it lost against a full chip.  With the last K groups cut into Q rows the run-down lasts a short row's
 // lifetime; a sector's mask is staged once either way, so the bulk keeps the economy of its long groups — and 16-ring groups,
 // which lost to 8-ring ones on their run-down alone (3.69 against 3.50 ms), now win (tdr_score.hip: score_ws).
-// Defaults from the sweep K in {0, 1, 2, 3, 4, 8} x Q in {2, 4, 8} x groups of 8 / 16 / 32 rings: 16 rings,
-// K = 4, Q = 4 — the last 64 of config 2's 256 rings go as rows of 16 rings x 2 sectors: config 2 4.47 -> 4.32 ms a step,
-// config 3's shard 5.57 -> 5.40, config 5's 13.87 -> 13.62.
-static int g_su_tail_groups = 4, g_su_tail_parts = 4;
-extern "C" int tdr_config_su_tail_groups(int k) {   // < 0: query only
-  if (k >= 0) g_su_tail_groups = k;
-  return g_su_tail_groups;
-}
-extern "C" int tdr_config_su_tail_parts(int q) {    // < 0: query only; 1, 2, 4 or 8 (anything else: the next lower of them)
-  if (q >= 0) g_su_tail_parts = q >= 8 ? 8 : (q >= 4 ? 4 : (q >= 2 ? 2 : 1));
-  return g_su_tail_parts;
-}
+// K and Q: TdrConfig::su_tail_groups / su_tail_parts (tdr_config.h has the sweep behind the defaults).
 // The rule of the shapes: short rows pay where workgroups QUEUE — a launch of fewer than two rounds of the chip's resident
 // workgroups (256 CUs x 6) has no run-down worth shortening, and every row costs the finalize a pass over its partial sums.
 // Results never depend on it.  (tdr_config_shift_uniform(2), the tests' mode: whatever the knobs say, on any shape.)
 void tdr_su_tail(int nchunks, int64_t n, int* k, int* q) {
-  *k = std::min(g_su_tail_groups, nchunks);
-  *q = g_su_tail_parts;
-  if (g_su_mode != 2 && cdiv(std::max<int64_t>(n, 1), 256) * nchunks < 2 * 256 * 6) *k = 0;
+  *k = std::min(tdr_cfg().su_tail_groups, nchunks);
+  *q = tdr_cfg().su_tail_parts;
+  if (tdr_cfg().su_mode != 2 && cdiv(std::max<int64_t>(n, 1), 256) * nchunks < 2 * 256 * 6) *k = 0;
   if (*k == 0 || *q == 1) { *k = 0; *q = 1; }
 }
 extern "C" int tdr_su_tail_plan(int nchunks, int k, int q, int row, int* group, int* s0, int* s1) {   // tests
@@ -1167,11 +1026,6 @@ extern "C" int tdr_su_tail_plan(int nchunks, int k, int q, int row, int* group, 
 // particles: from n = 16 384 on at nb = 4095, from about 35 000 on at nb = 3000.  (The bound is a choice of proportion, not a
 // measured crossover: nobody has timed the bucket sort against the merge sort at such shapes.)  Same slot list either way: a
 // stable sort by key has one answer.  tdr_config_tuning("su_order_bucket", 0): always rocPRIM (A/B).
-static int g_su_order_bucket = 1;
-extern "C" int tdr_config_su_order_bucket(int v) {   // < 0: query only
-  if (v >= 0) g_su_order_bucket = v ? 1 : 0;
-  return g_su_order_bucket;
-}
 static int64_t su_seg_table_words(int nb, int64_t n) {   // 0: no bucket sort for this shape
   const int64_t words = cdiv(std::max<int64_t>(n, 1), SU_SEG) * ((int64_t)nb + 1);
   return words <= 4 * std::max<int64_t>(n, 1) + 65536 ? words : 0;
@@ -1181,7 +1035,7 @@ static int64_t su_seg_table_reserve(int nb, int64_t n) {
   const int64_t m = std::max<int64_t>(n, 1);
   return std::min<int64_t>(cdiv(m, SU_SEG) * ((int64_t)nb + 1), 4 * m + 65536);
 }
-static bool su_order_is_bucket(int nb, int64_t n) { return g_su_order_bucket && su_seg_table_words(nb, n) > 0; }
+static bool su_order_is_bucket(int nb, int64_t n) { return tdr_cfg().su_order_bucket && su_seg_table_words(nb, n) > 0; }
 static size_t su_sort_tmp_bytes(int64_t n) {
   size_t bytes = 0;
   uint32_t* k = nullptr;
@@ -1205,8 +1059,6 @@ SuWs tdr_su_ws(int nb, int nr, int group, int64_t n) {
   w.vals_out = take(n);
   w.ints = take(3 * ((int64_t)nb + 1) + TDR_SU_TAIL_INTS);   // [cnt][start][slot_start] nb + 1 each, [counts 3][n_multi][inexact][mass bound][table is not its factors]
   w.slots = take(su_npad(n, nb));
-  w.slots2 = take(su_npad(n, nb));
-  w.wave_tmp = take(2 * (su_npad(n, nb) / 64 + 1));
   w.sort_tmp = take((int64_t)((su_sort_tmp_bytes(n) + 3) / 4));
   const int64_t T = tdr_ray_padded_samples(nb, nr);
   w.ray_tab = take(2 * T);                     // tdr_score_ray.hip: sample offsets and 16-bit scan descriptors in ray order,
@@ -1268,22 +1120,6 @@ int tdr_su_order(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_t*
     hipLaunchKernelGGL(su_scatter_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, (const uint32_t*)keys_out,
                        (const int32_t*)vals_out, n, (const int*)start, (const int*)slot_start, slots);
     LAUNCH_CHECK("su_scatter");
-  }
-  if (L.wave_span > 0.f && L.nb > 1) {   // waves whose own particles lie far apart: to the scattered share after all
-    int32_t* slots2 = base + W.slots2;
-    int32_t* keep = base + W.wave_tmp;
-    int32_t* moved = keep + (L.npad / 64 + 1);
-    int32_t* old_counts = counts + 7;   // (ints: TDR_SU_TAIL_INTS)
-    const int64_t nwaves = L.npad / 64;
-    hipLaunchKernelGGL(su_wave_far_kernel, dim3((unsigned)cdiv(nwaves, 4)), dim3(256), 0, s, L.st, L.cap, (const int32_t*)slots,
-                       (const int32_t*)counts, L.wave_span, keep, moved);
-    hipLaunchKernelGGL(su_compact_offsets_kernel, dim3(1), dim3(256), 0, s, keep, moved, counts, old_counts);
-    hipLaunchKernelGGL(su_compact_scatter_kernel, dim3((unsigned)cdiv(L.npad, 256)), dim3(256), 0, s, (const int32_t*)slots,
-                       (const int32_t*)keep, (const int32_t*)moved, (const int32_t*)counts, (const int32_t*)old_counts, slots2);
-    // padding slots of kept waves travel with them; nothing reads behind counts[2]
-    hipLaunchKernelGGL(su_copy_slots_kernel, dim3((unsigned)cdiv(L.npad, 256)), dim3(256), 0, s, (const int32_t*)slots2,
-                       (const int32_t*)counts, slots);
-    LAUNCH_CHECK("su_reroute");
   }
   *slots_out = slots;
   *counts_out = counts;
@@ -1365,10 +1201,10 @@ int tdr_su_score(const SuLaunch& L, const SuWs& W, hipStream_t s) {
   const dim3 grid((unsigned)cdiv(L.npad, 256), (unsigned)rows), block(256);
   const bool ks = tdr_has_kslot(map->ncls, L.rf), us = L.uniform_scale;
 #define TDR_LAUNCH_SU(NV4)                                                                         \
-  if (ks && us) hipLaunchKernelGGL((score_polar_su_kernel<NV4, true, true>), grid, block, g_su_lds_pad, s, u);  \
-  else if (ks) hipLaunchKernelGGL((score_polar_su_kernel<NV4, true, false>), grid, block, g_su_lds_pad, s, u);  \
-  else if (us) hipLaunchKernelGGL((score_polar_su_kernel<NV4, false, true>), grid, block, g_su_lds_pad, s, u);  \
-  else hipLaunchKernelGGL((score_polar_su_kernel<NV4, false, false>), grid, block, g_su_lds_pad, s, u);
+  if (ks && us) hipLaunchKernelGGL((score_polar_su_kernel<NV4, true, true>), grid, block, 0, s, u);  \
+  else if (ks) hipLaunchKernelGGL((score_polar_su_kernel<NV4, true, false>), grid, block, 0, s, u);  \
+  else if (us) hipLaunchKernelGGL((score_polar_su_kernel<NV4, false, true>), grid, block, 0, s, u);  \
+  else hipLaunchKernelGGL((score_polar_su_kernel<NV4, false, false>), grid, block, 0, s, u);
   switch (L.rf / 4) {
     case 1: TDR_LAUNCH_SU(1) break;
     case 2: TDR_LAUNCH_SU(2) break;
