@@ -1032,6 +1032,69 @@ typedef struct tdr_pose_stats {
 } tdr_pose_stats;
 int tdr_batch_pose(tdr_filter* const* f, int k, tdr_pose_stats* out, void* stream);
 
+/* ---- the particle picture: the node's map_viz image on the device (src/particle_filter.cpp:373-423, call site
+ * src/top_down_render.cpp:430-449) ----------------------------------------------------------------
+ * A DEFINITION, parity unpinned (like N3): OpenCV's anti-aliased thick lines blend in particle order, which no parallel
+ * drawing reproduces.  Kept from the reference: where things are drawn, the colours, the primitives, the integer
+ * conversions, the order of the layers.  Replaced: the coverage rule of a thick anti-aliased line.
+ *   Images are BGR8 [H][W][3]; pixels are integers, x to the right, y down, origin top-left.
+ *   Segment A -> B (integer endpoints, half width 1 = the reference's thickness 2) covers pixel P, with u = B - A,
+ *     w = P - A, L = u.u, d = u.w:  L = 0 or d <= 0: |P - A|^2 <= 1;  d >= L: |P - B|^2 <= 1;  else (ux wy - uy wx)^2 <= L.
+ *   Arrow(p1, p2) (cv::arrowedLine, tipLength 0.3): the shaft p1 -> p2 and two tips q -> p2,
+ *     q = (lrint(p2.x + tip cos(ang +- pi/4)), lrint(p2.y + tip sin(ang +- pi/4))), tip = sqrt(|p1 - p2|^2) * 0.3,
+ *     ang = atan2(p1.y - p2.y, p1.x - p2.x); double arithmetic on the host's libm, lrint rounds half to even.
+ *   Disc(c): the 21 pixels with dx^2 + dy^2 <= 5 (a filled radius-2 cv::circle).
+ *   float -> int is x86's truncating conversion: INT_MIN for NaN and for values outside [-2^31, 2^31).
+ *   Layers, later over earlier:
+ *     1 the background;
+ *     2 particle arrows (0,0,255): float32 without contraction x = dx_m scale + init_x_px, y = dy_m scale + init_y_px,
+ *       pt = ((int)x, (int)((float)H - y)); inside = !(pt.x < 0 || pt.x > W || pt.y < 0 || pt.y > H) (the reference's >:
+ *       x = W is inside, its arrow clipped); an inside particle with a finite theta draws Arrow(-dir, dir) moved to pt,
+ *       dir = ((int)(cosf(theta) 5), (int)(-sinf(theta) 5)), cosf / sinf the host libm's (csrc/tdr_sincosf.h); a
+ *       non-finite theta draws nothing (the reference overflows an int there);
+ *     3 border dots (0,255,0): a particle that is not inside draws Disc(clamp(pt.x, 5, W - 5), clamp(pt.y, 5, H - 5)).
+ *       Dots lie OVER arrows here; in the reference the two overwrite each other in particle order;
+ *     4 mixture and best particle (255,0,0): per component of the last computeGMM, with particle_viz.h's arithmetic (its
+ *       closed-form eigen-decomposition, its stop at the first component that is not PSD), the closed polyline through
+ *       the 72 vertices (lrint(cx + a cos t cos phi - b sin t sin phi), lrint(cy + a cos t sin phi + b sin t cos phi)),
+ *       t = k (pi / 36), (a, b) = 2 ((int)sqrtf(l0), (int)sqrtf(l1)), phi = (double)atan2f(-vy, vx), evaluated in double
+ *       from left to right; then the component's heading arrow; after the first update the arrow of the max-likelihood
+ *       state (the dir rule at the pt of its mlState);
+ *     5 the caller's arrows (0,255,0): Arrow((x1, y1), (x2, y2)) per row of an int32 [m][4] list.
+ *   Everything is clipped to the image.  An overlay arrow with an endpoint coordinate beyond +-2^20, and a polyline edge
+ *   with such a vertex, is not drawn (32 images away; the coverage arithmetic stays inside 64 bits).
+ *   Published size: out_w = (int)((float)W s), out_h = (int)((float)H s) (:442-444).  Equal to the input size: the
+ *   composed image.  Otherwise a bilinear resample in fixed point, per axis (x shown):
+ *   fx = (float)((ox + 0.5) ((double)W / out_w) - 0.5), sx = floor(fx), fx -= sx; sx < 0: sx = 0, fx = 0; sx >= W - 1:
+ *   sx = W - 1, fx = 0; second tap min(sx + 1, W - 1); a1 = lrint(fx 2048) (float product), a0 = 2048 - a1; a channel is
+ *   (sum b_i a_j S[y_i][x_j] + 2^21) >> 22.  The project's rule, not cv::resize's.
+ *
+ * Layer 1.  A call needs four bit planes (arrows, dots, blue, caller's green) of tdr_viz_plane_words(H, W) uint32 each,
+ * consecutive, 16-byte aligned, cleared by the caller on the same stream; 11 <= H, W <= 32768.  No allocation, no sync.
+ * tdr_viz_arrow_host: the three segments {x1, y1, x2, y2} of Arrow(-(dx, dy), (dx, dy)).  tdr_viz_overlay_host: layers 4
+ * and 5 as segments {x1, y1, x2, y2, plane} (plane 2: blue, 3: caller's green) from the mixture (means [k][3] = x, y,
+ * theta; covs [k][3][3]), the best state {x, y, theta} (NULL: none) and the caller's arrows; at most
+ * TDR_VIZ_MAX_SEGS(k, m) of them.  Both are host functions of the definition. */
+#define TDR_VIZ_MAX_SEGS(k, m) (75 * (k) + 3 + 3 * (m))
+size_t tdr_viz_plane_words(int H, int W);
+int tdr_viz_arrow_host(int dx, int dy, int32_t segs[12]);
+int tdr_viz_overlay_host(const float* means, const float* covs, int k, const float* best, const int32_t* arrows, int m,
+                         int H, int32_t* segs, int capacity, int* n_out);
+int tdr_k_viz_particles(const float* st, int64_t cap, int64_t n, int H, int W, uint32_t* planes, void* stream);
+int tdr_k_viz_segments(const int32_t* segs, int m, int H, int W, uint32_t* planes, void* stream);
+int tdr_k_viz_compose(const uint8_t* background, int H, int W, const uint32_t* planes, int out_h, int out_w,
+                      uint8_t* out_bgr, void* stream);
+/* Layer 2.  tdr_filter_set_viz_background uploads the background (host BGR8 [H][W][3]; 11 <= H, W <= 32768) once; the
+ * node's changes only with the map.  tdr_filter_visualize draws the picture of the filter's current particles, the mixture
+ * of the last tdr_filter_compute_gmm and, after the first update, the max-likelihood state, with `m` caller's arrows
+ * (extra_arrows [m][4], may be NULL when m = 0), and reads the published image back into out_bgr_host (`capacity` bytes;
+ * 3 * out_h * out_w needed).  *out_h / *out_w are set whenever the published size is valid; out_bgr_host = NULL only asks for them.  Polar and Cartesian
+ * filters alike; the filter is not changed.  Refused with TDR_ERR_ARG, the output untouched: no background, a sharded
+ * filter, a published dimension of 0 or above 32768 (pub_scale too small or too large, NaN included), too little room. */
+int tdr_filter_set_viz_background(tdr_filter* f, const uint8_t* bgr_host, int H, int W);
+int tdr_filter_visualize(tdr_filter* f, float pub_scale, const int32_t* extra_arrows, int m, uint8_t* out_bgr_host,
+                         int64_t capacity, int* out_h, int* out_w);
+
 /* internal: lets tdr_host.cpp report through tdr_last_error() */
 int tdr_set_error(int code, const char* msg);
 

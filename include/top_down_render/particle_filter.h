@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "top_down_render/active_localizer.h"   // like the reference's header (particle_filter.h:5)
+#include "top_down_render/particle_viz_device.h"
 #include "top_down_render/scan_renderer.h"
 #include "top_down_render/state_particle.h"
 
@@ -221,6 +222,20 @@ class ParticleFilter {
 #endif
 
   // --- beyond the reference's surface -------------------------------------------------------------------------------
+  // The picture drawn on the device (include/tdr.h, "the particle picture"; a definition, parity unpinned): the background
+  // is uploaded once (it changes only with the map), renderViz returns the image the node publishes — particles, mixture,
+  // best particle, the caller's arrows (the node's ground-truth arrow, :434-439), resized by pub_scale (:442-444).  Not
+  // for a sharded filter.  The vector overload returns the bytes [out_h][out_w][3].
+  template <class MatT = cv::Mat>
+  void setVizBackground(const MatT& bgr) { tdr_viz::setBackground(f_, bgr); }
+  template <class MatT = cv::Mat>
+  void renderViz(MatT& out, float pub_scale, const std::vector<std::array<int, 4>>& arrows = {}) {
+    tdr_viz::render(f_, out, pub_scale, arrows);
+  }
+  void renderViz(std::vector<uint8_t>& out, int& out_h, int& out_w, float pub_scale,
+                 const std::vector<std::array<int, 4>>& arrows = {}) {
+    tdr_viz::render(f_, out, out_h, out_w, pub_scale, arrows);
+  }
   void setTargetCount(int n) { target_count_ = n; }  // explicit adaptive particle count; < 0 keeps N
   void configure(bool parity_rng, int locality_every) { check(tdr_filter_configure(f_, parity_rng, locality_every), "configure"); }
   void setStates(const std::vector<State>& s) {

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "top_down_render/particle_viz_device.h"
 #include "top_down_render/scan_renderer.h"
 #include "top_down_render/state_particle.h"
 #include "top_down_render/top_down_map.h"
@@ -71,6 +72,20 @@ class ParticleFilterCartesian {
     std::vector<int32_t> lut(flatten_lut.begin(), flatten_lut.end());
     check(tdr_filter_update_map_labels(f_, label_img, img_h, img_w, lut.data(), (int)lut.size(), map_->numClasses(),
                                        map_->resolution(), map_center[0], map_center[1]), "updateMap");
+  }
+  // The picture drawn on the device (include/tdr.h, "the particle picture"; a definition, parity unpinned): the background
+  // is uploaded once (it changes only with the map), renderViz returns the image the node publishes — particles, mixture,
+  // best particle, the caller's arrows (the node's ground-truth arrow, :434-439), resized by pub_scale (:442-444).  The
+  // vector overload returns the bytes [out_h][out_w][3].
+  template <class MatT = cv::Mat>
+  void setVizBackground(const MatT& bgr) { tdr_viz::setBackground(f_, bgr); }
+  template <class MatT = cv::Mat>
+  void renderViz(MatT& out, float pub_scale, const std::vector<std::array<int, 4>>& arrows = {}) {
+    tdr_viz::render(f_, out, pub_scale, arrows);
+  }
+  void renderViz(std::vector<uint8_t>& out, int& out_h, int& out_w, float pub_scale,
+                 const std::vector<std::array<int, 4>>& arrows = {}) {
+    tdr_viz::render(f_, out, out_h, out_w, pub_scale, arrows);
   }
   tdr_filter* handle() const { return f_; }
   TopDownMap* map() const { return map_; }

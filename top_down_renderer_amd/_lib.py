@@ -266,6 +266,14 @@ SIGNATURES = {
     "tdr_batch_render_polar": (_i, [_vp, _i, _vp, _f, _i, _i, _i, _vp]),
     "tdr_renderer_get_render": (_i, [_vp, _vp, _vp]),
     "tdr_batch_pose": (_i, [_vp, _i, _vp, _vp]),
+    "tdr_viz_plane_words": (C.c_size_t, [_i, _i]),
+    "tdr_viz_arrow_host": (_i, [_i, _i, _vp]),
+    "tdr_viz_overlay_host": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, C.POINTER(_i)]),
+    "tdr_k_viz_particles": (_i, [_vp, _i64, _i64, _i, _i, _vp, _vp]),
+    "tdr_k_viz_segments": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "tdr_k_viz_compose": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "tdr_filter_set_viz_background": (_i, [_vp, _vp, _i, _i]),
+    "tdr_filter_visualize": (_i, [_vp, _f, _vp, _i, _vp, _i64, C.POINTER(_i), C.POINTER(_i)]),
     "tdr_set_error": (_i, [_i, C.c_char_p]),
     "tdr_locality_tmp_ints": (C.c_size_t, [_i64, _i, _i]),
     "tdr_locality_pose_tmp_ints": (C.c_size_t, [_i64]),

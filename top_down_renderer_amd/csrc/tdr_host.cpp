@@ -184,6 +184,12 @@ struct tdr_filter {
   int64_t cap = 0;
   DevBuf<float> xchg_in, xchg_out, raw_glob, ld_glob, st_send, st_all, st_glob, pk_recv;
   DevBuf<float> geo_pk;   // packed geometric scan (tdr_filter_update_geo)
+  // the particle picture (tdr_filter_visualize): the background as uploaded, the four bit planes, the overlay segments
+  // and the published image
+  DevBuf<uint8_t> viz_bg, viz_out;
+  DevBuf<uint32_t> viz_planes;
+  DevBuf<int32_t> viz_segs;
+  int viz_h = 0, viz_w = 0;
   int64_t nl() const { return n / world; }
 };
 
@@ -1728,6 +1734,65 @@ int64_t tdr_filter_adaptive_count(tdr_filter* f) {
   const int k = (int)(f->gmm_means.size() / 3);
   if (k == 0) return f->n;
   return tdr_adaptive_count_host(f->gmm_covs.data(), k, f->n, f->n_max);
+}
+
+// ---- the particle picture (include/tdr.h, "the particle picture"; kernels in tdr_viz.hip) ---------------------------------
+int tdr_filter_set_viz_background(tdr_filter* f, const uint8_t* bgr_host, int H, int W) {
+  if (!f || !bgr_host) return failh(TDR_ERR_ARG, "filter_set_viz_background: null argument");
+  if (H < 11 || W < 11 || H > 32768 || W > 32768)
+    return failh(TDR_ERR_ARG, "filter_set_viz_background: a %d x %d image (11 .. 32768 a side)", H, W);
+  const size_t bytes = (size_t)3 * H * W;
+  TTRY(f->viz_bg.resize(bytes));
+  TTRY(f->viz_planes.resize(4 * tdr_viz_plane_words(H, W)));
+  HTRY(hipStreamSynchronize(f->stream));   // (an earlier picture may still read the old background)
+  HTRY(hipMemcpy(f->viz_bg.p, bgr_host, bytes, hipMemcpyHostToDevice));
+  f->viz_h = H;
+  f->viz_w = W;
+  return TDR_OK;
+}
+
+// (int)((float)dim * s) as the node computes it (src/top_down_render.cpp:442-444), x86's conversion
+static int viz_pub_dim(int dim, float s) {
+  const float v = (float)dim * s;
+  return (v >= -2147483648.f && v < 2147483648.f) ? (int)v : std::numeric_limits<int>::min();
+}
+
+int tdr_filter_visualize(tdr_filter* f, float pub_scale, const int32_t* extra_arrows, int m, uint8_t* out_bgr_host,
+                         int64_t capacity, int* out_h, int* out_w) {
+  if (!f || !out_h || !out_w || m < 0 || (m > 0 && !extra_arrows) || m > (1 << 20))
+    return failh(TDR_ERR_ARG, "filter_visualize: bad arguments");
+  if (f->comm) return failh(TDR_ERR_ARG, "filter_visualize: a sharded filter has no picture (draw from a one-GPU filter)");
+  if (f->viz_h < 1) return failh(TDR_ERR_ARG, "filter_visualize: no background (tdr_filter_set_viz_background)");
+  const int H = f->viz_h, W = f->viz_w;
+  const int oh = viz_pub_dim(H, pub_scale), ow = viz_pub_dim(W, pub_scale);
+  if (oh < 1 || ow < 1 || oh > 32768 || ow > 32768)
+    return failh(TDR_ERR_ARG, "filter_visualize: scale %g publishes %d x %d pixels (1 .. 32768 a side)", (double)pub_scale, oh, ow);
+  *out_h = oh;
+  *out_w = ow;
+  if (!out_bgr_host) return TDR_OK;
+  const size_t bytes = (size_t)3 * oh * ow;
+  if (capacity < 0 || (size_t)capacity < bytes)
+    return failh(TDR_ERR_ARG, "filter_visualize: the image needs %zu bytes, room for %lld", bytes, (long long)capacity);
+  // layers 4 and 5 on the host: a few hundred integers
+  float best[4];
+  if (f->have_ml) HTRY(hipMemcpy(best, f->ml_dev.p + 8, sizeof(best), hipMemcpyDeviceToHost));
+  const int k = (int)(f->gmm_means.size() / 3);
+  std::vector<int32_t> segs((size_t)5 * TDR_VIZ_MAX_SEGS(k, m));
+  int nseg = 0;
+  TTRY(tdr_viz_overlay_host(f->gmm_means.data(), f->gmm_covs.data(), k, f->have_ml ? best : nullptr, extra_arrows, m, H,
+                            segs.data(), TDR_VIZ_MAX_SEGS(k, m), &nseg));
+  TTRY(f->viz_segs.resize((size_t)5 * std::max(nseg, 1)));
+  TTRY(f->viz_out.resize(bytes));
+  const size_t pw = tdr_viz_plane_words(H, W);
+  hipStream_t s = f->stream;
+  if (nseg) HTRY(hipMemcpyAsync(f->viz_segs.p, segs.data(), (size_t)5 * nseg * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HTRY(hipMemsetAsync(f->viz_planes.p, 0, 4 * pw * sizeof(uint32_t), s));
+  TTRY(tdr_k_viz_particles(f->st.p, f->cap, f->n, H, W, f->viz_planes.p, s));
+  TTRY(tdr_k_viz_segments(f->viz_segs.p, nseg, H, W, f->viz_planes.p, s));
+  TTRY(tdr_k_viz_compose(f->viz_bg.p, H, W, f->viz_planes.p, oh, ow, f->viz_out.p, s));
+  HTRY(hipMemcpyAsync(out_bgr_host, f->viz_out.p, bytes, hipMemcpyDeviceToHost, s));
+  HTRY(hipStreamSynchronize(s));
+  return TDR_OK;
 }
 
 // ParticleFilter::updateMap(const cv::Mat& map, map_center) (particle_filter.cpp:320-341) for a class-index image

@@ -204,6 +204,31 @@ def png_read_color(path):
     return out
 
 
+def viz_arrow_host(dx, dy):
+    """Host: the three segments {x1, y1, x2, y2} of Arrow(-(dx, dy), (dx, dy)) (include/tdr.h, "the particle picture")."""
+    segs = np.zeros((3, 4), np.int32)
+    check(_lib.load().tdr_viz_arrow_host(int(dx), int(dy), segs.ctypes.data_as(C.c_void_p)))
+    return segs
+
+
+def viz_overlay_host(means, covs, best, arrows, H):
+    """Host: the overlay of the particle picture as int32 segments {x1, y1, x2, y2, plane}.  means (k, 3), covs (k, 3, 3):
+    the mixture; best: {x, y, theta} of the max-likelihood state or None; arrows: (m, 4) caller's arrows or None."""
+    means = np.ascontiguousarray(means, np.float32).reshape(-1, 3)
+    covs = np.ascontiguousarray(covs, np.float32).reshape(-1, 9)
+    arrows = np.zeros((0, 4), np.int32) if arrows is None else np.ascontiguousarray(arrows, np.int32).reshape(-1, 4)
+    best_p = None if best is None else np.ascontiguousarray(best, np.float32)[:3].copy()
+    k, m = len(means), len(arrows)
+    cap = 75 * k + 3 + 3 * m   # TDR_VIZ_MAX_SEGS
+    segs = np.zeros((cap, 5), np.int32)
+    n = C.c_int(0)
+    check(_lib.load().tdr_viz_overlay_host(
+        means.ctypes.data_as(C.c_void_p) if k else None, covs.ctypes.data_as(C.c_void_p) if k else None, k,
+        None if best_p is None else best_p.ctypes.data_as(C.c_void_p),
+        arrows.ctypes.data_as(C.c_void_p) if m else None, m, int(H), segs.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+    return segs[: n.value].copy()
+
+
 class HipKernels:
     name = "hip"
 
@@ -636,6 +661,28 @@ class HipKernels:
         check(self.lib.tdr_gmm_select_host(x.ctypes.data_as(C.c_void_p), len(x), int(num_particles), C.byref(k), max_k,
                                            means.ctypes.data_as(C.c_void_p), covs.ctypes.data_as(C.c_void_p)))
         return k.value, means[: k.value].copy(), covs[: k.value].reshape(-1, 3, 3).copy()
+
+    # ---- the particle picture (csrc/tdr_viz.hip) ---------------------------------------------------------------
+    def viz_planes(self, H, W):
+        """The four bit planes of an H x W picture, as one int32 tensor (cleared by viz_draw)."""
+        words = int(self.lib.tdr_viz_plane_words(H, W))
+        if words == 0:
+            raise _lib.TdrError(f"no picture of {H} x {W} pixels")
+        return self.zeros((4 * words,), torch.int32)
+
+    def viz_draw(self, st, n, background, planes, segs, out_h, out_w, out=None):
+        """background: (H, W, 3) uint8 device tensor; segs: (m, 5) int32 overlay segments (host array).  Clears the
+        planes, draws particles and overlay and composes the published (out_h, out_w, 3) uint8 device tensor."""
+        H, W = int(background.shape[0]), int(background.shape[1])
+        if out is None:
+            out = self.empty((out_h, out_w, 3), torch.uint8)
+        planes.zero_()
+        check(self.lib.tdr_k_viz_particles(_ptr(st), st.shape[1], n, H, W, _ptr(planes), self.stream()))
+        if len(segs):
+            segs_d = self.to_device(np.ascontiguousarray(segs, np.int32))
+            check(self.lib.tdr_k_viz_segments(_ptr(segs_d), len(segs), H, W, _ptr(planes), self.stream()))
+        check(self.lib.tdr_k_viz_compose(_ptr(background), H, W, _ptr(planes), out_h, out_w, _ptr(out), self.stream()))
+        return out
 
     def set_scale(self, st, n, scale_dev):
         check(self.lib.tdr_k_set_scale(_ptr(st), st.shape[1], n, _ptr(scale_dev), self.stream()))

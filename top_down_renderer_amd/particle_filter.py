@@ -137,6 +137,8 @@ class ParticleFilter:
         self._uniform_scale = 0.0
         self._ml_fields = None
         self._ml_buf = None
+        self._viz_bg = None       # the background and bit planes of renderViz
+        self._viz_planes = None
         self.num_gaussians_ = 1   # :7
         self.gmm_means_ = np.zeros((0, 3), np.float32)
         self.gmm_covs_ = np.zeros((0, 3, 3), np.float32)
@@ -479,6 +481,36 @@ class ParticleFilter:
 
     def numParticles(self):
         return self.num_particles_
+
+    # ---- the particle picture (include/tdr.h, "the particle picture"): visualize (:373-423) on the device -----------
+    def setVizBackground(self, bgr):
+        """bgr: (H, W, 3) uint8, the image the node draws on (its background changes only with the map)."""
+        bgr = np.ascontiguousarray(bgr, np.uint8)
+        if bgr.ndim != 3 or bgr.shape[2] != 3 or not (11 <= bgr.shape[0] <= 32768 and 11 <= bgr.shape[1] <= 32768):
+            raise ValueError("setVizBackground: a BGR image of 11 .. 32768 pixels a side")
+        self._viz_bg = self.k.to_device(bgr)
+        self._viz_planes = self.k.viz_planes(bgr.shape[0], bgr.shape[1])
+
+    def renderViz(self, pub_scale, arrows=None):
+        """The picture of the current particles, the mixture of the last computeGMM and the max-likelihood state, with the
+        caller's arrows ((m, 4) integer endpoints), published at pub_scale: an (out_h, out_w, 3) uint8 array."""
+        from .kernels import viz_overlay_host
+        if self.comm.active:
+            raise ValueError("renderViz: a sharded filter has no picture")
+        if self._viz_bg is None:
+            raise ValueError("renderViz: no background (setVizBackground)")
+        H, W = int(self._viz_bg.shape[0]), int(self._viz_bg.shape[1])
+        s = np.float32(pub_scale)
+        dims = []
+        for d in (H, W):   # (int)((float)dim * s), x86's conversion (src/top_down_render.cpp:442-444)
+            v = np.float32(d) * s
+            dims.append(int(v) if -2147483648.0 <= v < 2147483648.0 else -2 ** 31)
+        if not all(1 <= d <= 32768 for d in dims):
+            raise ValueError(f"renderViz: scale {pub_scale} publishes {dims[0]} x {dims[1]} pixels (1 .. 32768 a side)")
+        best = self.maxLikelihood() if self._ml_fields is not None else None
+        segs = viz_overlay_host(self.gmm_means_, self.gmm_covs_, best, arrows, H)
+        out = self.k.viz_draw(self.st, self.n_local, self._viz_bg, self._viz_planes, segs, dims[0], dims[1])
+        return out.cpu().numpy()
 
     def updateMapIncremental(self, label_img, map_center=(0, 0)):
         """updateMap(label_img, map_center) with the map rebuilt only where the image changed
