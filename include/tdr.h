@@ -969,6 +969,59 @@ int64_t tdr_adaptive_count_host(const float* covs, int k, int64_t last_count, in
 int tdr_filter_compute_gmm(tdr_filter* f);
 int tdr_filter_get_gmm(tdr_filter* f, int max_k, int* k_out, float* means, float* covs);
 int64_t tdr_filter_adaptive_count(tdr_filter* f);
+/* Hooks for tests and drivers (the node loop needs none of them).  num_gaussians_ (:7): the count the next computeGMM
+ * searches around — 1 at creation, then what the last one chose; the setter lets a test or a timing tool start a search
+ * anywhere.  step_count: the updates the filter has made (computeGMM, on the host or the device, leaves it alone). */
+int tdr_filter_num_gaussians(const tdr_filter* f);
+int tdr_filter_set_num_gaussians(tdr_filter* f, int num_gaussians);
+int64_t tdr_filter_step_count(const tdr_filter* f);
+
+/* ---- the same fit on the device (csrc/tdr_gmm.hip) ----
+ * tdr_gmm_fit_host statement for statement, every sum in the host's order, in double: the device's exp / log are the
+ * only operations that may round differently.  One workgroup per fit, m <= 1000, k <= TDR_GMM_MAX_K, k <= m.
+ * A fit's output `out` is tdr_gmm_out_doubles(k) = 21 k + 2 doubles: w[k], mu[k][4], cov[k][4][4], the mean
+ * log-likelihood, the E-steps made.  `workspace` holds the responsibilities: tdr_gmm_workspace_bytes(m, k). */
+typedef struct tdr_gmm_job {
+  const double* samples;   /* [m][4] device */
+  int32_t m, k, max_iter, pad;
+  double* out;             /* [21 k + 2] device */
+  double* workspace;       /* tdr_gmm_workspace_bytes(m, k) device, the job's own */
+} tdr_gmm_job;
+/* One filter's cluster-count decision (:276-297): cand[0] = the fit at k, cand[1] = at k + 1 or NULL, cand[2] = at k - 1 or
+ * NULL (each a tdr_gmm_job's out).  dir = 0; +1 if cand[1] and ll + 0.3 < ll_up; then -1 if cand[2] and ll - 0.3 < ll_down
+ * (the later test wins, as in tdr_gmm_select_host).  record: TDR_GMM_RECORD_DOUBLES doubles — the chosen count, its mean
+ * log-likelihood, then per cluster {mu[4], cov(0,0), cov(0,1), cov(1,0), cov(1,1)}. */
+typedef struct tdr_gmm_pick_job {
+  const double* cand[3];
+  int32_t k, pad;
+  double* record;
+} tdr_gmm_pick_job;
+#define TDR_GMM_RECORD_DOUBLES (2 + 8 * TDR_GMM_MAX_K)
+size_t tdr_gmm_workspace_bytes(int m, int k);
+int tdr_gmm_out_doubles(int k);
+/* ml3 [num][3] floats {x, y, theta} (tdr_k_sample_ml_states) -> samples_out [num][4] doubles {x, y, 50 cos theta,
+ * 50 sin theta}, bit for bit tdr_filter_compute_gmm's host conversion (float cosf / sinf, float product, widened).
+ * For theta = +-inf / NaN the kernel writes the NaN bit patterns an x86-64 glibc host produces (the negative default NaN
+ * for an infinity, the quieted argument for a NaN): on a host of another architecture the host call and the device call
+ * may then store different NaN bits for such a heading (both are NaN; finite headings do not depend on the host). */
+int tdr_k_gmm_samples(const float* ml3, int num, double* samples_out, void* stream);
+/* The device twin of tdr_gmm_fit_host: one job, passed to the kernel by value; an asynchronous launch like every tdr_k_*. */
+int tdr_k_gmm_fit(const double* samples, int m, int k, int max_iter, double* out, double* workspace, void* stream);
+/* n_jobs fits in one launch, one workgroup each; jobs_dev is a device array.  A job with bad sizes writes nothing. */
+int tdr_k_gmm_fit_jobs(const tdr_gmm_job* jobs_dev, int n_jobs, void* stream);
+int tdr_k_gmm_pick(const tdr_gmm_pick_job* jobs_dev, int n, void* stream);
+/* The fits tdr_gmm_select_host makes before it decides: cand[0] = k = clamp(min(n / 20 + 1, num_gaussians), 1,
+ * min(max_k, m)); cand[1] = k + 1 if k * 50 < n and k + 1 <= min(max_k, m), else 0; cand[2] = k - 1 if k > 1, else 0. */
+int tdr_gmm_candidates_host(int num_gaussians, int64_t num_particles, int m, int max_k, int cand[3]);
+/* tdr_filter_compute_gmm with the fit on the device: the same samples (a sharded filter gathers like there and every rank
+ * runs the same fit), the candidate fits and the pick on the filter's stream, one read-back of the record, the host's
+ * conversion to means / covs.  Stores where tdr_filter_compute_gmm stores, so get_gmm, adaptive_count and the particle
+ * picture see it.  Reads the particle states only; a filter with 0 particles is left untouched. */
+int tdr_filter_compute_gmm_device(tdr_filter* f);
+/* tdr_filter_compute_gmm_device of k filters (polar or Cartesian, on any maps): the samples, every candidate fit and
+ * the picks are ONE launch each on `stream`, with one table upload and one read-back.  Each filter ends bit for bit where
+ * its own call leaves it.  Refused before any filter changes: null entries, duplicates, sharded filters. */
+int tdr_batch_compute_gmm(tdr_filter* const* filters, int k, void* stream);
 
 /* ---- batched filters: many filters on one map stepped together (csrc/tdr_batch.hip) ------------------------------------
  * tdr_batch_step = for every filter k: tdr_filter_propagate(filters[k], in[k].tx, in[k].ty, in[k].omega) followed by

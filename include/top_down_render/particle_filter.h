@@ -110,6 +110,9 @@ class ParticleFilter {
   int64_t nextCount() { return next_count(); }
   // getGMM (:238-243) / computeGMM (:252-318)
   void computeGMM() { check(tdr_filter_compute_gmm(f_), "computeGMM"); }
+  // ... with the same deterministic fit run as HIP kernels on the filter's stream (csrc/tdr_gmm.hip): no host EM, one small
+  // read-back; getGMM / the adaptive count / the particle picture see the result like computeGMM's
+  void computeGMMDevice() { check(tdr_filter_compute_gmm_device(f_), "computeGMMDevice"); }
   void getGMM(std::vector<Eigen::Vector3f>& means, std::vector<Eigen::Matrix3f>& covs) {
     float m[3 * TDR_GMM_MAX_K], c[9 * TDR_GMM_MAX_K];
     int k = 0;

@@ -63,6 +63,19 @@ class ParticleFilterBatch {
       throw std::runtime_error(std::string("ParticleFilterBatch::step: ") + tdr_last_error());
     tdr_batch_last_stats(&batched_, &standalone_);
   }
+  // computeGMMDevice() of every filter through tdr_batch_compute_gmm: the samples, every candidate fit and the picks are
+  // one launch each, with one read-back for the batch.  The filters need not share a map.  Throws on a refused batch
+  // (a null or repeated filter, a sharded one) before any filter changes.
+  void computeGMM(const std::vector<ParticleFilter*>& filters, void* stream = nullptr) {
+    if (filters.empty()) return;
+    std::vector<tdr_filter*> handles(filters.size(), nullptr);
+    for (size_t i = 0; i < filters.size(); i++) {
+      if (!filters[i]) throw std::invalid_argument("ParticleFilterBatch::computeGMM: null filter");
+      handles[i] = filters[i]->handle();
+    }
+    if (tdr_batch_compute_gmm(handles.data(), (int)handles.size(), stream) != TDR_OK)
+      throw std::runtime_error(std::string("ParticleFilterBatch::computeGMM: ") + tdr_last_error());
+  }
   // tdr_config_tuning("batch_init_search"), process-wide: with true a filter that may still hold a particle without a
   // heading — a cold start (init_pos_deg_theta = inf), a gated filter (force_on_map, unknown scale) — joins the batch, its
   // 40-rotation search part of the batch's scoring stage, same bits; false (the default): its standalone calls inside step()

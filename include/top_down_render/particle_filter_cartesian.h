@@ -65,6 +65,7 @@ class ParticleFilterCartesian {
   float scale() const { return tdr_filter_scale(f_); }
   int numParticles() const { return (int)tdr_filter_num_particles(f_); }
   void computeGMM() { check(tdr_filter_compute_gmm(f_), "computeGMM"); }
+  void computeGMMDevice() { check(tdr_filter_compute_gmm_device(f_), "computeGMMDevice"); }   // the fit as HIP kernels
   void setTargetCount(int n) { target_count_ = n; }
   void configure(bool parity_rng, int locality_every) { check(tdr_filter_configure(f_, parity_rng, locality_every), "configure"); }
   void updateMap(const uint8_t* label_img, int img_h, int img_w, const std::vector<int>& flatten_lut,

@@ -31,6 +31,10 @@ class TopDownRenderCore {
     float target_uncertainty_m = 2.5f;  // top_down_render.h:80
     int theta_bins = 100, range_bins = 25;   // hard-coded 100 x 25 in the node (:115, 530, 534); a parameter here
     uint32_t seed = 0;                  // ParticleFilter's seed (0: device noise; see particle_filter.h)
+    // The adaptive particle count (src/particle_filter.cpp:151-157; the reference's gmmThread refits once a second): after
+    // the publishPoseEst of every gmm_every-th step the mixture is refitted on the device (computeGMMDevice) and every
+    // update resamples to the count of :151-157.  0: never — the particle count stays particle_count.
+    int gmm_every = 0;
   };
   struct PoseEst {                      // what publishPoseEst computed this step
     Eigen::Matrix4f cov;                // computeMeanCov (:333)
@@ -82,6 +86,7 @@ class TopDownRenderCore {
     renderer_->renderSemanticTopDown(cloud_ptr, current_range_scale_, ang_res, top_down_);    // :539
     updateFilter(top_down_, top_down_geo_, current_range_scale_, trans, yaw);                 // :559
     PoseEst e = publishPoseEst();                                                            // :560
+    if (countStepAndGmmDue()) filter_->computeGMMDevice();
     if (est) *est = e;
     return true;
   }
@@ -145,10 +150,14 @@ class TopDownRenderCore {
 
  private:
   friend class TopDownRenderCoreBatch;   // steps many cores at once (top_down_render_core_batch.h)
+  // counts the step AND says whether its mixture fit is due (Config::gmm_every): exactly one call per step
+  bool countStepAndGmmDue() { return cfg_.gmm_every > 0 && ++steps_ % cfg_.gmm_every == 0; }
   void finishInit(FilterParams& filter_params, const Eigen::VectorXi& flatten_lut) {
     map_->samplePtsPolar(Eigen::Vector2i(cfg_.theta_bins, cfg_.range_bins), (float)(2 * M_PI / cfg_.theta_bins));   // :115
     filter_ = new ParticleFilter(cfg_.particle_count, map_, filter_params, cfg_.seed);                              // :116
     renderer_ = new ScanRendererPolar(flatten_lut);                                                                 // :117
+    steps_ = 0;
+    if (cfg_.gmm_every > 0) filter_->setAdaptiveCount(true);
   }
 
   Config cfg_;
@@ -161,6 +170,7 @@ class TopDownRenderCore {
   float last_res_ = 0.f;
   bool is_converged_ = false;          // :83
   bool device_scan_ = false;
+  int64_t steps_ = 0;                  // steps taken (counted only with Config::gmm_every > 0)
 };
 
 #endif  // TOP_DOWN_RENDER_CORE_H_

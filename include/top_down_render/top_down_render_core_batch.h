@@ -7,6 +7,7 @@
 //      cache)
 //   4. every core's own publishPoseEst() — it reads the cache, so it makes no device call except in the step in which a
 //      filter's scale freezes
+//   5. one ParticleFilterBatch::computeGMM for the cores whose mixture fit is due (Config::gmm_every): tdr_batch_compute_gmm
 //
 // Every core ends where cores[i]->takeStep(...) with setDeviceScan(true) leaves it: filter states, weights and generator
 // position, PoseEst, currentRangeScale, lastRes, isConverged.  One difference: the host topDown() images are not filled
@@ -81,11 +82,14 @@ class TopDownRenderCoreBatch {
     if (tdr_batch_pose(handles.data(), (int)k, stats.data(), stream) != TDR_OK)
       throw std::runtime_error(std::string("TopDownRenderCoreBatch::takeStep: ") + tdr_last_error());
     if (ests) ests->resize(k);
+    std::vector<ParticleFilter*> due;
     for (size_t i = 0; i < k; i++) {
       cores[i]->last_res_ = res[i];
       TopDownRenderCore::PoseEst e = cores[i]->publishPoseEst();                           // :560
+      if (cores[i]->countStepAndGmmDue()) due.push_back(filters[i]);
       if (ests) (*ests)[i] = e;
     }
+    batch_.computeGMM(due, stream);   // one mixture fit for the cores whose step is due (Config::gmm_every)
     return true;
   }
   // filters of the last step that took the batched path / their standalone calls (ParticleFilterBatch)

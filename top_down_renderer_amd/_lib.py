@@ -37,6 +37,21 @@ class BatchInputC(C.Structure):
                 ("ty", C.c_float), ("omega", C.c_float), ("n_target", C.c_int64)]
 
 
+class GmmJobC(C.Structure):
+    """tdr_gmm_job (include/tdr.h): one device fit."""
+    _fields_ = [("samples", C.c_void_p), ("m", C.c_int32), ("k", C.c_int32), ("max_iter", C.c_int32), ("pad", C.c_int32),
+                ("out", C.c_void_p), ("workspace", C.c_void_p)]
+
+
+class GmmPickJobC(C.Structure):
+    """tdr_gmm_pick_job (include/tdr.h): one filter's cluster-count decision over its candidate fits."""
+    _fields_ = [("cand", C.c_void_p * 3), ("k", C.c_int32), ("pad", C.c_int32), ("record", C.c_void_p)]
+
+
+GMM_MAX_K = 32
+GMM_RECORD_DOUBLES = 2 + 8 * GMM_MAX_K
+
+
 class BatchCloudC(C.Structure):
     """tdr_batch_cloud: one renderer's cloud in a tdr_batch_render_polar."""
     _fields_ = [("pts", C.c_void_p), ("stride", C.c_int), ("ioff", C.c_int), ("n", C.c_int64), ("res", C.c_float)]
@@ -185,6 +200,18 @@ SIGNATURES = {
     "tdr_filter_compute_gmm": (_i, [_vp]),
     "tdr_filter_get_gmm": (_i, [_vp, _i, _vp, _vp, _vp]),
     "tdr_filter_adaptive_count": (_i64, [_vp]),
+    "tdr_filter_step_count": (_i64, [_vp]),
+    "tdr_filter_num_gaussians": (_i, [_vp]),
+    "tdr_filter_set_num_gaussians": (_i, [_vp, _i]),
+    "tdr_gmm_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "tdr_gmm_out_doubles": (_i, [_i]),
+    "tdr_k_gmm_samples": (_i, [_vp, _i, _vp, _vp]),
+    "tdr_k_gmm_fit": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "tdr_k_gmm_fit_jobs": (_i, [_vp, _i, _vp]),
+    "tdr_k_gmm_pick": (_i, [_vp, _i, _vp]),
+    "tdr_gmm_candidates_host": (_i, [_i, _i64, _i, _i, _vp]),
+    "tdr_filter_compute_gmm_device": (_i, [_vp]),
+    "tdr_batch_compute_gmm": (_i, [_vp, _i, _vp]),
     "tdr_k_save_ml_state": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "tdr_k_shard_pack2": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "tdr_k_shard_unpack2": (_i, [_vp, _i, _i64, _vp, _vp, _vp]),

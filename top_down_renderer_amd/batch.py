@@ -169,6 +169,32 @@ class FilterHandle:
             imgs = _scan_images(scan, self.map, self.cart)
             check(self.L.tdr_filter_update(self.h, _ptr(imgs), None, C.c_float(res), int(n_target)))
 
+    def compute_gmm(self, device=True):
+        """computeGMM on the current particles: the fit on the device (tdr_filter_compute_gmm_device) or the host."""
+        check((self.L.tdr_filter_compute_gmm_device if device else self.L.tdr_filter_compute_gmm)(self.h))
+
+    def get_gmm(self):
+        """(means (k, 3), covs (k, 3, 3)) of the last compute_gmm."""
+        k = C.c_int()
+        means, covs = np.zeros((_lib.GMM_MAX_K, 3), np.float32), np.zeros((_lib.GMM_MAX_K, 9), np.float32)
+        check(self.L.tdr_filter_get_gmm(self.h, _lib.GMM_MAX_K, C.byref(k), _ptr(means), _ptr(covs)))
+        return means[: k.value].copy(), covs[: k.value].reshape(-1, 3, 3).copy()
+
+    def step_count(self):
+        """The updates the filter has made (tdr_filter_step_count)."""
+        return int(self.L.tdr_filter_step_count(self.h))
+
+    def num_gaussians(self):
+        return int(self.L.tdr_filter_num_gaussians(self.h))
+
+    def set_num_gaussians(self, k):
+        """num_gaussians_ (:7): the count the next compute_gmm searches around."""
+        check(self.L.tdr_filter_set_num_gaussians(self.h, int(k)))
+
+    def adaptive_count(self):
+        """The particle count of :151-157 from the stored mixture (n_target of the next update)."""
+        return int(self.L.tdr_filter_adaptive_count(self.h))
+
     def compute_weights(self, scan, res):
         """StateParticle::computeWeight for every particle (tdr_filter_compute_weights); read them with raw_weights."""
         if isinstance(scan, Renderer):
@@ -236,6 +262,15 @@ def last_stats():
     a, b = C.c_int(), C.c_int()
     check(L.tdr_batch_last_stats(C.byref(a), C.byref(b)))
     return a.value, b.value
+
+
+def compute_gmm_batch(filters, stream=None):
+    """FilterHandle.compute_gmm(device=True) of every filter in one tdr_batch_compute_gmm: the samples, every candidate
+    fit and the picks are one launch each.  The filters may be polar or Cartesian and need not share a map."""
+    L = _lib.load()
+    k = len(filters)
+    arr = (_vp * max(k, 1))(*[f.h if f is not None else None for f in filters])
+    check(L.tdr_batch_compute_gmm(arr, k, _vp(stream) if stream else None))
 
 
 def render_batch(renderers, clouds, res, ang_res, ncls, nb, nr, stream=None):
@@ -331,11 +366,17 @@ class LoopBatch:
         for c, r in zip(self.cores, res):
             c.last_res_ = r
         render_batch(self.renderers, clouds, [float(r) for r in res], self.ang_res, self.ncls, self.nb, self.nr, stream)
+        if n_targets is None and any(c.cfg.gmm_every > 0 for c in self.cores):   # :151-157 from each robot's last fit
+            n_targets = [f.adaptive_count() if c.cfg.gmm_every > 0 else -1 for c, f in zip(self.cores, self.filters)]
         self.stats = step_batch(self.filters, self.renderers, [float(r) for r in res], priors, n_targets, stream)
         mean, cov, scale, n = pose_batch(self.filters, stream)
-        out = []
+        out, due = [], []
         for i, (c, f) in enumerate(zip(self.cores, self.filters)):
             c.filter_ = _PoseView(f, mean[i], cov[i], float(scale[i]), n[i])
             out.append(c.publishPoseEst())
             c.filter_ = None
+            if c.countStepAndGmmDue():
+                due.append(f)
+        if due:   # one mixture fit for the robots whose step is due (CoreConfig.gmm_every)
+            compute_gmm_batch(due, stream)
         return out

@@ -546,11 +546,7 @@ __global__ void sample_ml_states_kernel(const float* __restrict__ st, int64_t ca
                                         float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= num) return;
-  const int64_t p = min(n - 1, (int64_t)i * n / num);   // :265-266
-  const float sc = st[TDR_ST_SCALE * cap + p];
-  out[3 * i + 0] = st[TDR_ST_DX * cap + p] * sc + st[TDR_ST_INIT_X * cap + p];
-  out[3 * i + 1] = st[TDR_ST_DY * cap + p] * sc + st[TDR_ST_INIT_Y * cap + p];
-  out[3 * i + 2] = st[TDR_ST_THETA * cap + p];
+  sample_ml_state(st, cap, n, num, i, out + 3 * i);
 }
 extern "C" int tdr_k_sample_ml_states(const float* st, int64_t cap, int64_t n, int num, float* out, void* stream) {
   if (!st || !out || n < 1 || cap < n || num < 1) return fail(TDR_ERR_ARG, "sample_ml_states: bad arguments");

@@ -247,4 +247,16 @@ __device__ __forceinline__ void mc_final_body(int64_t n, const float* __restrict
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// computeGMM's i-th sample of num (src/particle_filter.cpp:262-266): mlState().head<3>() = {x, y, theta} of particle
+// min(n-1, i*n/num).  The standalone sampler (tdr_filter.hip) and the batched mixture fit (tdr_gmm.hip) both call it.
+__device__ __forceinline__ void sample_ml_state(const float* __restrict__ st, int64_t cap, int64_t n, int num, int i,
+                                                float out[3]) {
+  const int64_t p = min(n - 1, (int64_t)i * n / num);   // :265-266
+  const float sc = st[TDR_ST_SCALE * cap + p];
+  out[0] = st[TDR_ST_DX * cap + p] * sc + st[TDR_ST_INIT_X * cap + p];
+  out[1] = st[TDR_ST_DY * cap + p] * sc + st[TDR_ST_INIT_Y * cap + p];
+  out[2] = st[TDR_ST_THETA * cap + p];
+}
+
 #endif  // TDR_FILTER_DEV_H_

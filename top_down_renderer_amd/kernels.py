@@ -662,6 +662,66 @@ class HipKernels:
                                            means.ctypes.data_as(C.c_void_p), covs.ctypes.data_as(C.c_void_p)))
         return k.value, means[: k.value].copy(), covs[: k.value].reshape(-1, 3, 3).copy()
 
+    # ---- the mixture fit on the device (csrc/tdr_gmm.hip) -------------------------------------------------------
+    def gmm_samples(self, ml3, num):
+        """(num, 3) float {x, y, theta} -> (num, 4) double {x, y, 50 cos theta, 50 sin theta}, the host conversion's bits."""
+        out = self.empty((num, 4), torch.float64)
+        check(self.lib.tdr_k_gmm_samples(_ptr(ml3), num, _ptr(out), self.stream()))
+        return out
+
+    def gmm_fit(self, samples, k, max_iter=100):
+        """The device twin of tdr_gmm_fit_host.  samples: (m, 4) float64 device tensor.
+        Returns (w (k,), mu (k, 4), cov (k, 4, 4), ll, E-steps made) as NumPy / Python values."""
+        m = samples.shape[0]
+        out = self.zeros((int(self.lib.tdr_gmm_out_doubles(k)),), torch.float64)
+        ws = self.empty((max(1, int(self.lib.tdr_gmm_workspace_bytes(m, k)) // 8),), torch.float64)
+        check(self.lib.tdr_k_gmm_fit(_ptr(samples), m, k, max_iter, _ptr(out), _ptr(ws), self.stream()))
+        o = out.cpu().numpy()
+        return o[:k].copy(), o[k:5 * k].reshape(k, 4).copy(), o[5 * k:21 * k].reshape(k, 4, 4).copy(), float(o[21 * k]), \
+            int(o[21 * k + 1])
+
+    def gmm_candidates(self, num_gaussians, num_particles, m, max_k=_lib.GMM_MAX_K):
+        """[k, k + 1 or 0, k - 1 or 0]: the fits tdr_gmm_select_host makes before it decides."""
+        cand = (C.c_int * 3)()
+        check(self.lib.tdr_gmm_candidates_host(int(num_gaussians), int(num_particles), int(m), int(max_k), cand))
+        return list(cand)
+
+    def gmm_select_device(self, ml3, num, num_particles, num_gaussians):
+        """tdr_filter_compute_gmm_device's launches on torch buffers: ml3 (num, 3) float device tensor of the samples.
+        Returns (k, means (k, 3) float32, covs (k, 3, 3) float32) like gmm_select."""
+        import math
+        x = self.gmm_samples(ml3, num)
+        cand = self.gmm_candidates(num_gaussians, num_particles, num)
+        jobs, pick, keep = [], _lib.GmmPickJobC(), []
+        pick.k = cand[0]
+        for j, kc in enumerate(cand):
+            if not kc:
+                continue
+            out = self.zeros((21 * kc + 2,), torch.float64)
+            ws = self.empty((num * kc,), torch.float64)
+            keep += [out, ws]
+            jobs.append(_lib.GmmJobC(x.data_ptr(), num, kc, 100, 0, out.data_ptr(), ws.data_ptr()))
+            pick.cand[j] = out.data_ptr()
+        rec = self.zeros((_lib.GMM_RECORD_DOUBLES,), torch.float64)
+        pick.record = rec.data_ptr()
+        jobs_c = (_lib.GmmJobC * len(jobs))(*jobs)
+        jobs_d = self.to_device(np.frombuffer(bytes(jobs_c), np.uint8))
+        pick_d = self.to_device(np.frombuffer(bytes(pick), np.uint8))
+        check(self.lib.tdr_k_gmm_fit_jobs(_ptr(jobs_d), len(jobs), self.stream()))
+        check(self.lib.tdr_k_gmm_pick(_ptr(pick_d), 1, self.stream()))
+        r = rec.cpu().numpy()   # (the one read-back; it waits for the stream)
+        k = int(r[0])
+        if not 1 <= k <= _lib.GMM_MAX_K:
+            raise _lib.TdrError("gmm_select_device: the device fit left no mixture")
+        o = r[2:2 + 8 * k].reshape(k, 8)
+        means = np.zeros((k, 3), np.float32)
+        covs = np.zeros((k, 3, 3), np.float32)
+        means[:, 0], means[:, 1] = o[:, 0], o[:, 1]
+        means[:, 2] = [math.atan2(a, b) for a, b in zip(o[:, 3], o[:, 2])]   # (the host libm's, as tdr_gmm_select_host)
+        covs[:, :2, :2] = o[:, 4:8].reshape(k, 2, 2)
+        covs[:, 2, 2] = 1
+        return k, means, covs
+
     # ---- the particle picture (csrc/tdr_viz.hip) ---------------------------------------------------------------
     def viz_planes(self, H, W):
         """The four bit planes of an H x W picture, as one int32 tensor (cleared by viz_draw)."""

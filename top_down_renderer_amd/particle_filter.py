@@ -21,6 +21,7 @@ Deliberate, documented deviations from the reference
   * top_down_geo is accepted and ignored like in the reference, whose geometric score term is commented out
     (state_particle.cpp:145-152); use_geometric_cost=True switches that term on.
 """
+import ctypes as C
 import math
 from dataclasses import dataclass, field
 
@@ -424,19 +425,34 @@ class ParticleFilter:
         return self.k.mean_cov(st, n)[:4].cpu().numpy().copy()
 
     # ---- particle_filter.cpp:238-318: the mixture behind the adaptive particle count --------------------------------
-    def computeGMM(self):
+    def computeGMM(self, device=False):
         """computeGMM (:252-318) on the current particles, synchronously (the reference runs it in a detached thread
-        once per second).  cv::ml::EM is replaced by the deterministic fit of csrc/tdr_gmm.cpp (parity unpinned)."""
+        once per second).  cv::ml::EM is replaced by the deterministic fit of csrc/tdr_gmm.cpp (parity unpinned).
+        device=True: the same fit as HIP kernels on the filter's buffers (csrc/tdr_gmm.hip), one small read-back."""
         st, n, _ = self._global_states()
         if n < 1:
             return
         num = min(1000, n)   # :262
+        if device:
+            ml3 = self.k.sample_ml_states(st, n, num)
+            self.num_gaussians_, self.gmm_means_, self.gmm_covs_ = self.k.gmm_select_device(ml3, num, n, self.num_gaussians_)
+            return
         h = self.k.sample_ml_states(st, n, num).cpu().numpy()
         x = np.empty((num, 4), np.float64)
         x[:, 0], x[:, 1] = h[:, 0], h[:, 1]
         x[:, 2] = np.float32(50) * np.cos(h[:, 2])   # :269-270
         x[:, 3] = np.float32(50) * np.sin(h[:, 2])
         self.num_gaussians_, self.gmm_means_, self.gmm_covs_ = self.k.gmm_select(x, n, self.num_gaussians_)
+
+    def adaptiveCount(self):
+        """num_particles_ of :151-157 from the clusters of the last computeGMM (tdr_adaptive_count_host): the n_target of
+        the next update.  The current count while there is no mixture."""
+        k = len(self.gmm_means_)
+        if k == 0:
+            return self.num_particles_
+        covs = np.ascontiguousarray(self.gmm_covs_, np.float32)
+        return int(self.k.lib.tdr_adaptive_count_host(covs.ctypes.data_as(C.c_void_p), k, self.num_particles_,
+                                                      self.max_num_particles_))
 
     def getGMM(self):
         """(means [k][3] = x, y, theta; covs [k][3][3]) of the last computeGMM (:238-243)."""

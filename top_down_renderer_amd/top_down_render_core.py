@@ -28,6 +28,9 @@ class CoreConfig:                       # the node's parameters that reach the s
     theta_bins: int = 100               # hard-coded 100 x 25 in the node (:115, 530, 534); parameters here
     range_bins: int = 25
     seed: int = 0                       # ParticleFilter's seed
+    # the adaptive particle count (src/particle_filter.cpp:151-157): after the publishPoseEst of every gmm_every-th step
+    # the mixture is refitted on the device and every update resamples to the count of :151-157.  0: never
+    gmm_every: int = 0
 
 
 @dataclass
@@ -48,11 +51,13 @@ class TopDownRenderCore:
         self.last_res_ = np.float32(0)
         self.is_converged_ = False                                         # top_down_render.h:83
         self.map_ = self.filter_ = self.renderer_ = None
+        self.steps_ = 0                                                    # counted only with cfg.gmm_every > 0
 
     def initialize(self, map, filter_params, flatten_lut, **filter_kw):
         """:81, 115-117 with a TopDownMapPolar the host built."""
         c = self.cfg
         self.map_ = map
+        self.steps_ = 0
         self.ang_res = np.float32(2 * np.pi / c.theta_bins)
         map.samplePtsPolar((c.theta_bins, c.range_bins), self.ang_res)                                     # :115
         self.filter_ = ParticleFilter(c.particle_count, map, filter_params, seed=c.seed, kernels=self.k, **filter_kw)   # :116
@@ -67,11 +72,25 @@ class TopDownRenderCore:
         self.last_res_ = self.current_range_scale_
         self.renderer_.renderSemanticTopDown(cloud, float(self.current_range_scale_), self.ang_res)         # :539
         self.updateFilter(self.renderer_.last_scan(), None, float(self.current_range_scale_), trans, yaw)   # :559
-        return self.publishPoseEst()                                                                        # :560
+        e = self.publishPoseEst()                                                                           # :560
+        if self.countStepAndGmmDue():
+            self.filter_.computeGMM(device=True)
+        return e
+
+    def countStepAndGmmDue(self):
+        """Counts the step AND says whether its mixture fit is due (cfg.gmm_every): exactly one call per step."""
+        g = self.cfg.gmm_every
+        if g <= 0:
+            return False
+        self.steps_ += 1
+        return self.steps_ % g == 0
 
     def updateFilter(self, top_down, top_down_geo, res, trans, yaw):
         self.filter_.propagate(trans, yaw)                                                                  # :423
-        self.filter_.update(top_down, top_down_geo, res)                                                    # :425
+        if self.cfg.gmm_every > 0:   # :151-157 from the clusters of the last fit
+            self.filter_.update(top_down, top_down_geo, res, n_target=self.filter_.adaptiveCount())
+        else:
+            self.filter_.update(top_down, top_down_geo, res)                                                # :425
 
     def publishPoseEst(self):
         """publishPoseEst (:331-365) without the publishing."""
