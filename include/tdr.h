@@ -434,7 +434,7 @@ int tdr_rng_pipe_init_particles(tdr_rng_pipe* p, const tdr_map_desc* map, const 
  * the multi-workgroup reductions and the chunk headers of the exact chains).  The result is a pure function of
  * (raw_w, last_dist, n).  `sum`, `mean` and `bottom_stddev` are the reference's serial float32 accumulations bit for
  * bit at every n (csrc/tdr_prefix.hip: uw_small_kernel up to 32768 particles, tdr_chain_total above).  n is limited
- * to what the scratch holds (~7 million). */
+ * to what the scratch holds: 40 bytes per chunk of 4096 weights behind ~12 KB of reduction scratch, about 25 million. */
 #define TDR_UW_INFO_FLOATS 65536
 int tdr_k_update_weights(const float* raw_w, const float* last_dist, int64_t n, float* w_out, float* info_out,
                          void* stream);
@@ -512,6 +512,12 @@ int tdr_k_set_scale(float* st, int64_t cap, int64_t n, const float* scale_dev, v
 int tdr_k_save_ml_state(const float* info, const float* st, int64_t cap, int64_t src_shard, int64_t n, float* out12,
                         void* stream);   /* src_shard > 0: st is the all-gathered [rank][7][src_shard] buffer */
 int tdr_k_shift_init(float* st, int64_t cap, int64_t n, float dx, float dy, void* stream);      /* updateMap :325-334 */
+/* The three calls an unsharded update ends with, in one launch: idx_out as tdr_k_resample_dev (shift_dev != NULL) or
+ * tdr_k_resample (`shift`), dst[f][i - i_begin] = src[f][idx] as tdr_k_gather_states (both source layouts; dst is not src)
+ * and out12 as tdr_k_save_ml_state, taken from src — the set BEFORE the resample.  The same bits as the three calls. */
+int tdr_k_resample_gather(const float* runmax, int64_t n, int64_t n_new, const float* shift_dev, float shift,
+                          int64_t i_begin, int64_t i_end, int32_t* idx_out, const float* src, int64_t src_cap,
+                          int64_t src_shard, float* dst, int64_t dst_cap, const float* info, float* out12, void* stream);
 
 /* The scoring kernels read the compact records whenever the map has them (tdr_k_compact_map); tdr_config_compact(0)
  * forces the dense records (A/B measurements, tests), 1 restores the default, < 0 only queries.  Results never depend on

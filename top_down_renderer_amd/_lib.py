@@ -213,6 +213,7 @@ SIGNATURES = {
     "tdr_filter_compute_gmm_device": (_i, [_vp]),
     "tdr_batch_compute_gmm": (_i, [_vp, _i, _vp]),
     "tdr_k_save_ml_state": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "tdr_k_resample_gather": (_i, [_vp, _i64, _i64, _vp, _f, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "tdr_k_shard_pack2": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "tdr_k_shard_unpack2": (_i, [_vp, _i, _i64, _vp, _vp, _vp]),
     "tdr_k_unshard_states": (_i, [_vp, _i, _i64, _vp, _i64, _vp]),

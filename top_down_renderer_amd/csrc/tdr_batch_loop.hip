@@ -37,7 +37,7 @@ __global__ __launch_bounds__(1024) void batch_raster_kernel(const TdrBatchRaster
 // rasterises without keys (those take tdr_k_raster_polar per renderer) or refuses
 bool tdr_batch_raster_shape(int ncls, int rows, int cols, float ang_res, TdrBatchRasterShape* out) {
   RasterShape sh;
-  if (ncls < 1 || ncls > TDR_MAX_CLASSES || rows < 1 || cols < 1 || !raster_shape(ncls, rows, cols, &sh) || !sh.keyed)
+  if (ncls < 1 || ncls > TDR_MAX_CLASSES || rows < 1 || cols < 1 || !raster_shape(ncls, rows, cols, true, &sh) || !sh.keyed)
     return false;
   TdrBatchRasterShape a;
   a.ang_res = ang_res; a.ncls = ncls; a.rows = rows; a.cols = cols; a.rf = tdr_rec_floats(ncls); a.cpt = sh.cpt;

@@ -95,9 +95,22 @@ static inline int with_nv4(int rf, const char* who, F&& f) {
 #define INI_TILE 2048                 // stream positions per workgroup of ini_flags_kernel (1024 per parity)
 #define INI_MAX_TILES 2048            // ini_tail_kernel holds the tiles' minima in LDS: W <= 2^22
 // tdr_prefix.hip: final value of a serial float32 chain over the raw weights (kind 0: sum of the non-NaN weights;
-// kind 1: float-accumulated squared deviations of the weights below *mean_dev), see there
+// kind 1: float-accumulated squared deviations of the weights below *mean_dev), see there.  have_sums: the chunk headers in
+// `workspace` already hold the double sums of this chain's chunks (tdr_uw_chunk_pass1 / _pass2 left them there)
 int tdr_chain_total(const float* raw, const float* mean_dev, int kind, int64_t n, float* total_out, void* workspace,
-                    hipStream_t st);
+                    bool have_sums, hipStream_t st);
+// The serial float chains of particle_filter.cpp:108-126 (`sum`, `bottom_stddev`) evaluated exactly by tdr_chain_total land
+// here, and the mean between them.
+struct UwExact {
+  float sum, mean, bsum, pad;
+};
+// tdr_prefix.hip: the two counting passes of tdr_k_update_weights above 32 768 weights, one workgroup per chain chunk, each
+// also leaving the double sum of the NEXT chain's chunks in the headers (chain_sum_body: the pass reads the array anyway).
+// pass 1: cnt_valid[c] = the chunk's non-NaN weights, the `sum` chain's chunk sums.
+// pass 2: ex->mean = ex->sum / valid (:117), cnt_under[c] = the chunk's weights below it, the `bottom_stddev` chain's sums.
+int tdr_uw_chunk_pass1(const float* raw, int64_t n, void* workspace, int* cnt_valid, hipStream_t st);
+int tdr_uw_chunk_pass2(const float* raw, int64_t n, UwExact* ex, const int* cnt_valid, void* workspace, int* cnt_under,
+                       hipStream_t st);
 // tdr_prefix.hip: particle_filter.cpp:107-147 for n <= 32768 in one launch, both serial chains exact
 int tdr_uw_small(const float* raw, const float* last_dist, int64_t n, float* w, float* info, hipStream_t st);
 // tdr_rng.hip: the generator's raw stream of `nblocks` state blocks behind `state`, and the state behind *consumed words of it

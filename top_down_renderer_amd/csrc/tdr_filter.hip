@@ -214,50 +214,22 @@ __device__ double uw_total(const double* part) {
   __syncthreads();
   return result;
 }
-// pass 1: sum / count of the valid raw weights (:108-116)
-__global__ __launch_bounds__(256) void uw_pass1(const float* __restrict__ raw, int64_t n, UwScratch* s1) {
-  __shared__ double shd[4];
-  __shared__ long long shl[4];
-  int64_t lo, hi;
-  uw_chunk(n, lo, hi);
-  double s = 0;
+// passes 1 and 2 — the count of the valid weights (:108-116), the mean (:117) and the count of the weights below it
+// (:118-125) — run chunk by chunk beside the chains' chunk sums (tdr_uw_chunk_pass1 / _pass2, tdr_prefix.hip) and leave one
+// count per chain chunk.  Their totals, in every thread (integers: any order):
+__device__ long long uw_count_total(const int* __restrict__ cnt, int nch, long long* shl) {
   long long c = 0;
-  for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
-    const float v = raw[i];
-    if (!isnan(v)) { s += (double)v; c++; }
-  }
-  const double ts = block_sum_d(s, shd);
-  const long long tc = block_sum_ll(c, shl);
-  if (threadIdx.x == 0) { s1->a[blockIdx.x] = ts; s1->b[blockIdx.x] = (double)tc; }
-}
-// The serial float chains of :108-126 (`sum`, `bottom_stddev`) evaluated exactly by tdr_chain_total land here.
-struct UwExact {
-  float sum, mean, bsum, pad;
-};
-// pass 2: the mean (:117) from the exact `sum` chain; count of the weights below it (:118-125)
-__global__ __launch_bounds__(256) void uw_pass2(const float* __restrict__ raw, int64_t n, const UwScratch* s1,
-                                                UwScratch* s2, UwExact* ex) {
-  __shared__ long long shl[4];
-  const float mean = ex->sum / (float)(long long)uw_total(s1->b);
-  int64_t lo, hi;
-  uw_chunk(n, lo, hi);
-  long long cu = 0;
-  for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
-    const float v = raw[i];
-    if (!isnan(v) && v < mean) cu++;
-  }
-  const long long tc = block_sum_ll(cu, shl);
-  if (threadIdx.x == 0) {
-    s2->b[blockIdx.x] = (double)tc;
-    if (blockIdx.x == 0) ex->mean = mean;   // every workgroup computed the same value
-  }
+  for (int j = threadIdx.x; j < nch; j += blockDim.x) c += cnt[j];
+  return block_sum_ll(c, shl);
 }
 // pass 3: NaN fill / all-ones fallback (:129-134) and the first normalisation sum
 __global__ __launch_bounds__(256) void uw_pass3(const float* __restrict__ raw, int64_t n, const UwExact* ex,
-                                                const UwScratch* s2, UwScratch* s3, float* __restrict__ w) {
+                                                const int* __restrict__ cnt_under, int nch, UwScratch* s3,
+                                                float* __restrict__ w) {
   __shared__ double shd[4];
+  __shared__ long long shl[4];
   const float sum = ex->sum, mean = ex->mean;
-  const long long num_under = (long long)uw_total(s2->b);
+  const long long num_under = uw_count_total(cnt_under, nch, shl);
   const float bottom = sqrtf(ex->bsum / (float)num_under);   // :126
   const bool fallback = (sum == 0.f || num_under < 1);
   const float fill = mean - bottom;
@@ -292,6 +264,36 @@ __global__ __launch_bounds__(256) void uw_pass4(const float* __restrict__ last_d
   const double t = block_sum_d(acc, shd);
   if (threadIdx.x == 0) s4->a[blockIdx.x] = t;
 }
+// the statistics a caller reads (info[0..7]) from the workgroups' argmax candidates, the counts and the exact chains; by
+// one workgroup of 256 threads
+__device__ __forceinline__ void uw_write_info(const UwScratch* s5, const int* __restrict__ cnt_valid,
+                                              const int* __restrict__ cnt_under, int nch, const UwExact* ex, float* info) {
+  static_assert(UW_G == 256, "one candidate per thread");
+  __shared__ float sb[4];
+  __shared__ long long si[4];
+  __shared__ long long shl[4];
+  // first maximum over the workgroups' candidates (:145-147): largest value, smallest index among equals; a NaN never
+  // wins (one thread per candidate and a tree instead of a serial loop over LDS: 23 -> 5 us)
+  float best = (float)s5->a[threadIdx.x];
+  long long besti = (long long)s5->b[threadIdx.x];
+  if (best != best) { best = -INFINITY; besti = 0x7fffffffffffffffll; }
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_down(best, o, 64);
+    const long long oi = __shfl_down(besti, o, 64);
+    if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+  }
+  if ((threadIdx.x & 63) == 0) { sb[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = besti; }
+  const float sum = ex->sum, mean = ex->mean;
+  const long long nv = uw_count_total(cnt_valid, nch, shl), nu = uw_count_total(cnt_under, nch, shl);   // (barriers inside)
+  const float bottom = sqrtf(ex->bsum / (float)nu);
+  if (threadIdx.x != 0) return;
+  for (int k = 1; k < 4; k++)
+    if (sb[k] > best || (sb[k] == best && si[k] < besti)) { best = sb[k]; besti = si[k]; }
+  if (besti == 0x7fffffffffffffffll) besti = 0;
+  info[0] = __int_as_float((int)besti);
+  info[1] = sum; info[2] = mean; info[3] = bottom; info[4] = (sum == 0.f || nu < 1) ? 1.f : 0.f;
+  info[5] = (float)nv; info[6] = (float)nu; info[7] = 0.f;
+}
 // pass 5: final normalisation (:142) and per-workgroup first maximum (:145-147)
 __global__ __launch_bounds__(256) void uw_pass5(int64_t n, const UwScratch* s4, UwScratch* s5, float* __restrict__ w) {
   __shared__ float sb[4];
@@ -320,32 +322,12 @@ __global__ __launch_bounds__(256) void uw_pass5(int64_t n, const UwScratch* s4, 
     s5->b[blockIdx.x] = (double)besti;  // exact: indices < 2^53
   }
 }
-__global__ __launch_bounds__(256) void uw_pass6(int64_t n, const UwScratch* s1, const UwScratch* s2,
-                                                const UwScratch* s5, const UwExact* ex, float* info) {
-  static_assert(UW_G == 256, "one candidate per thread");
-  __shared__ float sb[4];
-  __shared__ long long si[4];
-  // first maximum over the workgroups' candidates (:145-147): largest value, smallest index among equals; a NaN never
-  // wins (one thread per candidate and a tree instead of a serial loop over LDS: 23 -> 5 us)
-  float best = (float)s5->a[threadIdx.x];
-  long long besti = (long long)s5->b[threadIdx.x];
-  if (best != best) { best = -INFINITY; besti = 0x7fffffffffffffffll; }
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_down(best, o, 64);
-    const long long oi = __shfl_down(besti, o, 64);
-    if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
-  }
-  if ((threadIdx.x & 63) == 0) { sb[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = besti; }
-  const float sum = ex->sum, mean = ex->mean;
-  const long long nv = (long long)uw_total(s1->b), nu = (long long)uw_total(s2->b);   // (barriers inside)
-  const float bottom = sqrtf(ex->bsum / (float)nu);
-  if (threadIdx.x != 0) return;
-  for (int k = 1; k < 4; k++)
-    if (sb[k] > best || (sb[k] == best && si[k] < besti)) { best = sb[k]; besti = si[k]; }
-  if (besti == 0x7fffffffffffffffll) besti = 0;
-  info[0] = __int_as_float((int)besti);
-  info[1] = sum; info[2] = mean; info[3] = bottom; info[4] = (sum == 0.f || nu < 1) ? 1.f : 0.f;
-  info[5] = (float)nv; info[6] = (float)nu; info[7] = 0.f;
+// pass 6: one workgroup.  (Folded into pass 5 — the workgroup that draws the last ticket behind a fence writes info — the two
+// took 14.5 us together instead of 6.0 + 6.8: the fold was measured and dropped, DESIGN.md 5.2,
+// profiles/fixed_cost_kernel_stats_ticket_fold_v1.csv.)
+__global__ __launch_bounds__(256) void uw_pass6(const UwScratch* s5, const int* __restrict__ cnt_valid,
+                                                const int* __restrict__ cnt_under, int nch, const UwExact* ex, float* info) {
+  uw_write_info(s5, cnt_valid, cnt_under, nch, ex, info);
 }
 
 #define TDR_UW_SINGLE_MAX_N 32768
@@ -360,28 +342,34 @@ extern "C" int tdr_k_update_weights(const float* raw_w, const float* last_dist, 
     LAUNCH_CHECK("update_weights");
     return TDR_OK;
   }
-  // scratch behind the 8 info floats: 5 x UwScratch, UwExact, then the chunk headers of the two exact chains
-  constexpr size_t kFixed = 8 * sizeof(float) + 64 + 5 * sizeof(UwScratch) + sizeof(UwExact) + 64;
-  static_assert(kFixed + 32 * 1024 <= TDR_UW_INFO_FLOATS * sizeof(float), "info scratch");
+  // scratch behind the 8 info floats: 3 x UwScratch, UwExact, the chunk headers of the two exact chains, then the two counts
+  // per chunk
+  constexpr size_t kFixed = 8 * sizeof(float) + 64 + 3 * sizeof(UwScratch) + sizeof(UwExact) + 64;
+  static_assert(kFixed + 40 * 1024 <= TDR_UW_INFO_FLOATS * sizeof(float), "info scratch");
   UwScratch* sc = reinterpret_cast<UwScratch*>(
       (reinterpret_cast<uintptr_t>(info_out + 8) + 63) & ~(uintptr_t)63);
-  UwExact* ex = reinterpret_cast<UwExact*>(sc + 5);
+  UwExact* ex = reinterpret_cast<UwExact*>(sc + 3);
   void* chain_ws = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(ex + 1) + 63) & ~(uintptr_t)63);
   const size_t chain_room = TDR_UW_INFO_FLOATS * sizeof(float) - kFixed;
-  if ((size_t)tdr_prefix_workspace_bytes(n) > chain_room)
+  const int64_t nch = tdr_prefix_workspace_bytes(n) / 32;   // chain chunks (32-byte headers)
+  if ((size_t)tdr_prefix_workspace_bytes(n) + (size_t)nch * 2 * sizeof(int) > chain_room)
     return fail(TDR_ERR_ARG, "update_weights: n = %lld needs more than TDR_UW_INFO_FLOATS of scratch", (long long)n);
-  hipLaunchKernelGGL(uw_pass1, dim3(UW_G), dim3(256), 0, s, raw_w, n, sc + 0);
-  int rc = tdr_chain_total(raw_w, nullptr, 0, n, &ex->sum, chain_ws, s);                     // `sum` (:108-116)
+  int* cnt_valid = reinterpret_cast<int*>(reinterpret_cast<char*>(chain_ws) + tdr_prefix_workspace_bytes(n));
+  int* cnt_under = cnt_valid + nch;
+  int rc = tdr_uw_chunk_pass1(raw_w, n, chain_ws, cnt_valid, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(uw_pass2, dim3(UW_G), dim3(256), 0, s, raw_w, n, (const UwScratch*)(sc + 0), sc + 1, ex);
-  rc = tdr_chain_total(raw_w, &ex->mean, 1, n, &ex->bsum, chain_ws, s);                      // `bottom_stddev` (:118-125)
+  rc = tdr_chain_total(raw_w, nullptr, 0, n, &ex->sum, chain_ws, true, s);                   // `sum` (:108-116)
   if (rc) return rc;
-  hipLaunchKernelGGL(uw_pass3, dim3(UW_G), dim3(256), 0, s, raw_w, n, (const UwExact*)ex, (const UwScratch*)(sc + 1),
-                     sc + 2, w_out);
-  hipLaunchKernelGGL(uw_pass4, dim3(UW_G), dim3(256), 0, s, last_dist, n, (const UwScratch*)(sc + 2), sc + 3, w_out);
-  hipLaunchKernelGGL(uw_pass5, dim3(UW_G), dim3(256), 0, s, n, (const UwScratch*)(sc + 3), sc + 4, w_out);
-  hipLaunchKernelGGL(uw_pass6, dim3(1), dim3(256), 0, s, n, (const UwScratch*)(sc + 0), (const UwScratch*)(sc + 1),
-                     (const UwScratch*)(sc + 4), (const UwExact*)ex, info_out);
+  rc = tdr_uw_chunk_pass2(raw_w, n, ex, cnt_valid, chain_ws, cnt_under, s);
+  if (rc) return rc;
+  rc = tdr_chain_total(raw_w, &ex->mean, 1, n, &ex->bsum, chain_ws, true, s);                // `bottom_stddev` (:118-125)
+  if (rc) return rc;
+  hipLaunchKernelGGL(uw_pass3, dim3(UW_G), dim3(256), 0, s, raw_w, n, (const UwExact*)ex, (const int*)cnt_under, (int)nch,
+                     sc + 0, w_out);
+  hipLaunchKernelGGL(uw_pass4, dim3(UW_G), dim3(256), 0, s, last_dist, n, (const UwScratch*)(sc + 0), sc + 1, w_out);
+  hipLaunchKernelGGL(uw_pass5, dim3(UW_G), dim3(256), 0, s, n, (const UwScratch*)(sc + 1), sc + 2, w_out);
+  hipLaunchKernelGGL(uw_pass6, dim3(1), dim3(256), 0, s, (const UwScratch*)(sc + 2), (const int*)cnt_valid,
+                     (const int*)cnt_under, (int)nch, (const UwExact*)ex, info_out);
   LAUNCH_CHECK("update_weights(multi)");
   return TDR_OK;
 }
@@ -423,12 +411,9 @@ extern "C" int tdr_k_resample_dev(const float* runmax, int64_t n, int64_t n_new,
   return TDR_OK;
 }
 
-__global__ void gather_states_kernel(const float* __restrict__ src, int64_t src_cap, int64_t src_shard,
-                                     const int32_t* __restrict__ idx, int64_t n_new, float* __restrict__ dst,
-                                     int64_t dst_cap) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_new) return;
-  const int64_t j = idx[i];
+// particle j of either source layout -> slot i of the planes dst
+__device__ __forceinline__ void gather_state(const float* __restrict__ src, int64_t src_cap, int64_t src_shard, int64_t j,
+                                             float* __restrict__ dst, int64_t dst_cap, int64_t i) {
   if (src_shard > 0) {  // all-gathered source: [rank][field][src_shard], global particle j = rank*src_shard + local
     const int64_t r = j / src_shard, l = j - r * src_shard;
 #pragma unroll
@@ -436,6 +421,13 @@ __global__ void gather_states_kernel(const float* __restrict__ src, int64_t src_
   } else {
     gather_particle(src, src_cap, j, dst, dst_cap, i);
   }
+}
+__global__ void gather_states_kernel(const float* __restrict__ src, int64_t src_cap, int64_t src_shard,
+                                     const int32_t* __restrict__ idx, int64_t n_new, float* __restrict__ dst,
+                                     int64_t dst_cap) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_new) return;
+  gather_state(src, src_cap, src_shard, idx[i], dst, dst_cap, i);
 }
 
 extern "C" int tdr_k_gather_states(const float* src, int64_t src_cap, int64_t src_shard, const int32_t* idx,
@@ -516,9 +508,8 @@ extern "C" int tdr_k_shift_init(float* st, int64_t cap, int64_t n, float dx, flo
 
 // max_likelihood_particle_ = particles_[argmax] (particle_filter.cpp:145-147) points at the PRE-resample particle:
 // keep its fields and its mlState (state_particle.cpp:98-102) on the device, so the update needs no host round trip.
-__global__ void save_ml_state_kernel(const float* __restrict__ info, const float* __restrict__ st, int64_t cap,
-                                     int64_t src_shard, int64_t n, float* __restrict__ out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ __forceinline__ void save_ml_state(const float* __restrict__ info, const float* __restrict__ st, int64_t cap,
+                                              int64_t src_shard, int64_t n, float* __restrict__ out) {
   const int64_t best = ml_index(info, n);
   float f[TDR_ST_FIELDS];
   if (src_shard > 0) {   // all-gathered source [rank][field][src_shard], `best` is a global particle index
@@ -531,6 +522,11 @@ __global__ void save_ml_state_kernel(const float* __restrict__ info, const float
   }
   ml_record(f, out);
 }
+__global__ void save_ml_state_kernel(const float* __restrict__ info, const float* __restrict__ st, int64_t cap,
+                                     int64_t src_shard, int64_t n, float* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  save_ml_state(info, st, cap, src_shard, n, out);
+}
 extern "C" int tdr_k_save_ml_state(const float* info, const float* st, int64_t cap, int64_t src_shard, int64_t n,
                                    float* out12, void* stream) {
   if (!info || !st || !out12 || n < 1 || src_shard < 0 || (src_shard == 0 && cap < n))
@@ -538,6 +534,42 @@ extern "C" int tdr_k_save_ml_state(const float* info, const float* st, int64_t c
   hipLaunchKernelGGL(save_ml_state_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, info, st, cap, src_shard, n,
                      out12);
   LAUNCH_CHECK("save_ml_state");
+  return TDR_OK;
+}
+
+// The step's tail in one launch (particle_filter.cpp:172-187 with :145-147): thread i searches its source index in the
+// running maximum (resample_pick, as resample_kernel / resample_dev_kernel), copies that particle's seven state rows
+// (gather_state, as gather_states_kernel) and, in block 0, one thread keeps the max-likelihood particle of the
+// PRE-resample set (save_ml_state).  src is only read and dst is another buffer, so the three do not depend on each other
+// beyond idx[i], which stays in a register.  shift_dev != NULL: the draw is on the device (tdr_k_resample_dev), else `shift`.
+__global__ __launch_bounds__(256) void resample_gather_kernel(const float* __restrict__ runmax, int64_t n, int64_t n_new,
+                                                              const float* __restrict__ shift_dev, float shift,
+                                                              int64_t i_begin, int64_t i_end, int32_t* __restrict__ idx,
+                                                              const float* __restrict__ src, int64_t src_cap,
+                                                              int64_t src_shard, float* __restrict__ dst, int64_t dst_cap,
+                                                              const float* __restrict__ info, float* __restrict__ out12) {
+  const int64_t i = i_begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < i_end) {
+    const int64_t j = resample_pick(runmax, n, n_new, i, shift_dev ? *shift_dev : shift);
+    idx[i - i_begin] = (int32_t)j;
+    gather_state(src, src_cap, src_shard, j, dst, dst_cap, i - i_begin);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) save_ml_state(info, src, src_cap, src_shard, n, out12);
+}
+extern "C" int tdr_k_resample_gather(const float* runmax, int64_t n, int64_t n_new, const float* shift_dev, float shift,
+                                     int64_t i_begin, int64_t i_end, int32_t* idx_out, const float* src, int64_t src_cap,
+                                     int64_t src_shard, float* dst, int64_t dst_cap, const float* info, float* out12,
+                                     void* stream) {
+  if (!runmax || !idx_out || !src || !dst || !info || !out12) return fail(TDR_ERR_ARG, "resample_gather: null pointer");
+  if (n < 1 || n_new < 1 || i_begin < 0 || i_end > n_new || i_begin > i_end)
+    return fail(TDR_ERR_ARG, "resample_gather: bad range");
+  if (src_shard < 0 || (src_shard == 0 && src_cap < n) || dst_cap < i_end - i_begin || dst == src)
+    return fail(TDR_ERR_ARG, "resample_gather: bad state buffers");
+  // (an empty range still saves the max-likelihood state: one block)
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, cdiv(i_end - i_begin, 256));
+  hipLaunchKernelGGL(resample_gather_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, runmax, n, n_new, shift_dev,
+                     shift, i_begin, i_end, idx_out, src, src_cap, src_shard, dst, dst_cap, info, out12);
+  LAUNCH_CHECK("resample_gather");
   return TDR_OK;
 }
 

@@ -1571,15 +1571,13 @@ static int filter_resample(tdr_filter* f, int64_t n_target) {
   TTRY(tdr_k_prefix(f->w.p, n, f->runmax.p, f->pfx_ws.p, f->stream));
   // :172-173 (every rank owns an identically seeded generator); each rank draws its own slice [i0, i0 + nl_new) of the new
   // set, idx holds GLOBAL source indices
-  if (rng_on_device(f)) {   // the stream is on the device: so is the draw
-    const float* shift_dev = nullptr;
-    TTRY(tdr_rng_pipe_uniform(f->pipe, &shift_dev, f->stream));
-    TTRY(tdr_k_resample_dev(f->runmax.p, n, n_new, shift_dev, i0, i0 + nl_new, f->idx.p, f->stream));
-  } else {
-    const float shift = tdr_rng_uniform_host(f->rng);
-    TTRY(tdr_k_resample(f->runmax.p, n, n_new, shift, i0, i0 + nl_new, f->idx.p, f->stream));
-  }
+  const float* shift_dev = nullptr;
+  float shift = 0.f;
+  if (rng_on_device(f)) TTRY(tdr_rng_pipe_uniform(f->pipe, &shift_dev, f->stream));   // the stream is on the device: so is the draw
+  else shift = tdr_rng_uniform_host(f->rng);
   if (f->comm) {
+    if (shift_dev) TTRY(tdr_k_resample_dev(f->runmax.p, n, n_new, shift_dev, i0, i0 + nl_new, f->idx.p, f->stream));
+    else TTRY(tdr_k_resample(f->runmax.p, n, n_new, shift, i0, i0 + nl_new, f->idx.p, f->stream));
     // the second all-gather: the pre-resample state planes, [rank][7][nl] (28 B x N)
     for (int k = 0; k < TDR_ST_FIELDS; k++)
       HTRY(hipMemcpyAsync(f->st_send.p + (size_t)k * nl, f->st.p + (size_t)k * f->cap, (size_t)nl * sizeof(float),
@@ -1588,10 +1586,10 @@ static int filter_resample(tdr_filter* f, int64_t n_target) {
     TTRY(tdr_k_gather_states(f->st_all.p, 0, nl, f->idx.p, nl_new, f->st_new.p, f->cap, f->stream));
     TTRY(tdr_k_save_ml_state(f->info.p, f->st_all.p, 0, nl, n, f->ml_dev.p, f->stream));
   } else {
-    TTRY(tdr_k_gather_states(f->st.p, f->cap, 0, f->idx.p, n_new, f->st_new.p, f->cap, f->stream));
-    // max_likelihood_particle_ = particles_[argmax] (:145-147): keep that particle's pre-resample state (on the device:
-    // the update returns without waiting for the GPU)
-    TTRY(tdr_k_save_ml_state(f->info.p, f->st.p, f->cap, 0, n, f->ml_dev.p, f->stream));
+    // index, state rows and max_likelihood_particle_ = particles_[argmax] (:145-147, that particle's pre-resample state,
+    // kept on the device: the update returns without waiting for the GPU) in one launch
+    TTRY(tdr_k_resample_gather(f->runmax.p, n, n_new, shift_dev, shift, 0, n_new, f->idx.p, f->st.p, f->cap, 0, f->st_new.p,
+                               f->cap, f->info.p, f->ml_dev.p, f->stream));
   }
   f->have_ml = true;
   f->states_changed();

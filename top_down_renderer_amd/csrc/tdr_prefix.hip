@@ -8,8 +8,9 @@
 //
 //  tdr_k_prefix (running sum + running maximum; tdr_k_prefix_mode forces a path)
 //    256 <= n <= 32 768                   pfx_small_kernel: one launch, one workgroup, weights in LDS          mode 3
-//    n >= 6144 with a workspace           prefix_multi: pfx_chunk_sum_kernel -> pfx_chunk_summary_kernel ->    mode 2
-//                                         [pfx_small_kernel over the first 32 768 weights when n >= 32 768] ->
+//    n >= 6144 with a workspace           prefix_multi: pfx_chunk_sum_kernel -> pfx_chunk_summary_kernel [when  mode 2
+//                                         n >= 32 768 instead: pfx_small_kernel, block 0 over the first 32 768
+//                                         weights, the other blocks the summaries of the chunks behind them] ->
 //                                         pfx_walk_kernel -> pfx_chunk_fill_kernel
 //    n < 24 576 otherwise                 prefix_serial_kernel: one wave, lane 0 adds in index order           mode 0
 //    else                                 prefix_exact_kernel: one workgroup, the older tie-list algorithm     mode 1
@@ -19,7 +20,12 @@
 //    uw_small_kernel<true>: the chains wave by wave (default); <false>: chunk by chunk on the whole workgroup
 //    (tdr_config_uw_waves(0))
 //  tdr_chain_total (one statistics chain, n > 32 768; called from tdr_filter.hip)
-//    chain_sum_kernel -> chain_summary_kernel -> [chain_head_kernel<kind> over the first 32 768 addends] -> chain_walk_kernel
+//    [chain_sum_kernel unless the caller's pass left the chunk sums] -> chain_head_kernel<kind> (block 0: the first
+//    32 768 addends; the other blocks: the summaries of the chunks behind them) -> chain_walk_kernel
+//    tdr_config_prefix_small(0): chain_summary_kernel over every chunk instead of chain_head_kernel
+//  tdr_uw_chunk_pass1 / _pass2 (tdr_k_update_weights, n > 32 768): uw_chunk_pass1_kernel / uw_chunk_pass2_kernel, one
+//    workgroup per chain chunk: the count of valid weights / of weights below the mean, and the chunk sums of the chain
+//    that follows (chain_sum_body)
 //  tdr_batch_update_weights / tdr_batch_prefix: uw_small_batch_kernel / pfx_small_batch_kernel, one workgroup per filter
 //
 // Order of the file: the one-wave serial kernel; the one-workgroup tie-list kernel; the parity-pair chain step and
@@ -1273,30 +1279,104 @@ __global__ __launch_bounds__(PFXW_THREADS) void chain_walk_kernel(ChainSrc s, in
 // whole chunks at the start that the one-workgroup machinery takes (0: none; tdr_config_prefix_small(0) switches it off
 // for the running sum AND the statistics chains: the chunk walk from the first addend on, for A/B and debugging)
 static int chain_head_chunks(int64_t n) { return (tdr_cfg().pfx_small && n >= CHAIN_HEAD_N) ? CHAIN_HEAD_N / PFXM_CHUNK : 0; }
-static int chain_head_launch(const float* raw, const float* mean_dev, int kind, int n_head, float* r_out, hipStream_t st);
+// the head and, in the same launch, the summaries of the chunks [c_first, nch) behind it (chain_head_kernel, below)
+static int chain_head_launch(const float* raw, const float* mean_dev, int kind, int n_head, float* r_out, int64_t n,
+                             PfxChunk* ch, int nch, hipStream_t st);
 // raw: [n] raw weights; kind 0: total = serial float sum of the non-NaN weights; kind 1: total = serial
 // float-accumulated sum of pow(w - *mean_dev, 2) over the non-NaN weights below *mean_dev.  workspace: chunk headers,
-// tdr_prefix_workspace_bytes(n).  total_out: one device float.
+// tdr_prefix_workspace_bytes(n).  total_out: one device float.  have_sums: the headers hold the chunks' double sums already.
 int tdr_chain_total(const float* raw, const float* mean_dev, int kind, int64_t n, float* total_out, void* workspace,
-                    hipStream_t st) {
+                    bool have_sums, hipStream_t st) {
   const int64_t nch64 = cdiv(n, (int64_t)PFXM_CHUNK);
   if (nch64 > (1 << 24)) return fail(TDR_ERR_ARG, "chain_total: n too large");
   const int nch = (int)nch64;
   PfxChunk* ch = reinterpret_cast<PfxChunk*>(workspace);
   ChainSrc s{raw, mean_dev, kind};
   // The first 32 768 addends — where the sum crosses most of its binades — go through the one-workgroup machinery of
-  // uw_small_kernel (chain_head_kernel, below); the chunk walk starts behind them.
+  // uw_small_kernel (chain_head_kernel, below); the chunk walk starts behind them.  Head and summaries need the chunk sums
+  // and nothing of each other: one launch, block 0 the head, the summaries in its shadow.
   const int c_first = chain_head_chunks(n);
-  hipLaunchKernelGGL(chain_sum_kernel, dim3(nch), dim3(PFXW_THREADS), 0, st, s, n, ch);
-  if (nch > c_first)
-    hipLaunchKernelGGL(chain_summary_kernel, dim3(nch - c_first), dim3(PFXW_THREADS), 0, st, s, n, ch, c_first);
+  if (!have_sums) hipLaunchKernelGGL(chain_sum_kernel, dim3(nch), dim3(PFXW_THREADS), 0, st, s, n, ch);
   float* r_first = reinterpret_cast<float*>(&ch[0].r0);   // (a header slot the chains do not use)
   if (c_first > 0) {
-    const int rc = chain_head_launch(raw, mean_dev, kind, c_first * PFXM_CHUNK, r_first, st);
+    const int rc = chain_head_launch(raw, mean_dev, kind, c_first * PFXM_CHUNK, r_first, n, ch, nch, st);
     if (rc) return rc;
+  } else if (nch > c_first) {
+    hipLaunchKernelGGL(chain_summary_kernel, dim3(nch - c_first), dim3(PFXW_THREADS), 0, st, s, n, ch, c_first);
   }
   hipLaunchKernelGGL(chain_walk_kernel, dim3(1), dim3(PFXW_THREADS), 0, st, s, n, (const PfxChunk*)ch, nch, total_out,
                      c_first, (const float*)r_first);
+  return TDR_OK;
+}
+
+// ---- the update's two counting passes above 32 768 weights, chunk by chunk -------------------------------------------------
+// particle_filter.cpp:108-116 counts the valid weights and :118-125 those below the mean; each pass reads the whole array
+// and is followed by a chain over the same array, so it leaves that chain's chunk sums behind (chain_sum_body: a chunk's
+// additions in chain_sum_kernel's order).  Counts are integers: exact in any partition, so the grid is the chains' chunks.
+template <int NT>
+__device__ __forceinline__ int uw_wg_sum_int(int v, int* sh) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  pfx_sync();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  pfx_sync();
+  int t = 0;
+  for (int k = 0; k < NT / 64; k++) t += sh[k];
+  return t;
+}
+// weights of chunk blockIdx.x that are not NaN and, with BELOW, below `mean`
+template <bool BELOW>
+__device__ __forceinline__ int uw_chunk_count(const float* __restrict__ raw, int64_t n, float mean, int* sh) {
+  const long long lo = (long long)blockIdx.x * PFXM_CHUNK;
+  const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
+  const ChainAddend<float, ChainGlobal, CHAIN_BOUND_22> plain{{raw}, CHAIN_RUNSUM, 0.f};   // the weights as they are
+  float v[CHAIN_K];
+  const int t0 = threadIdx.x * CHAIN_K;
+  plain.load_items(lo, cnt, t0, v);
+  int c = 0;
+#pragma unroll
+  for (int k = 0; k < CHAIN_K; k++) c += (t0 + k < cnt && v[k] == v[k] && (!BELOW || v[k] < mean)) ? 1 : 0;
+  return uw_wg_sum_int<PFXW_THREADS>(c, sh);
+}
+__global__ __launch_bounds__(PFXW_THREADS) void uw_chunk_pass1_kernel(const float* __restrict__ raw, int64_t n,
+                                                                     PfxChunk* __restrict__ ch, int* __restrict__ cnt_valid) {
+  __shared__ int shc[PFXW_THREADS / 64];
+  const int c = uw_chunk_count<false>(raw, n, 0.f, shc);
+  if (threadIdx.x == 0) cnt_valid[blockIdx.x] = c;
+  chain_sum_body<PFXW_THREADS, CHAIN_K>(ChainStat{{raw}, CHAIN_SUM, 0.f}, n, ch);
+}
+__global__ __launch_bounds__(PFXW_THREADS) void uw_chunk_pass2_kernel(const float* __restrict__ raw, int64_t n,
+                                                                     UwExact* __restrict__ ex,
+                                                                     const int* __restrict__ cnt_valid,
+                                                                     PfxChunk* __restrict__ ch, int* __restrict__ cnt_under) {
+  __shared__ int shc[PFXW_THREADS / 64];
+  __shared__ long long shv[PFXW_THREADS / 64];
+  // the valid weights of all chunks (every workgroup: the same integer), then the mean (:117) from the exact `sum` chain
+  long long nv = 0;
+  for (int j = threadIdx.x; j < (int)gridDim.x; j += PFXW_THREADS) nv += cnt_valid[j];
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) nv += __shfl_xor(nv, o, 64);
+  if ((threadIdx.x & 63) == 0) shv[threadIdx.x >> 6] = nv;
+  pfx_sync();
+  nv = 0;
+  for (int k = 0; k < PFXW_THREADS / 64; k++) nv += shv[k];
+  const float mean = ex->sum / (float)nv;
+  const int c = uw_chunk_count<true>(raw, n, mean, shc);
+  if (threadIdx.x == 0) {
+    cnt_under[blockIdx.x] = c;
+    if (blockIdx.x == 0) ex->mean = mean;   // every workgroup computed the same value
+  }
+  chain_sum_body<PFXW_THREADS, CHAIN_K>(ChainStat{{raw}, CHAIN_BOTTOM, mean}, n, ch);
+}
+int tdr_uw_chunk_pass1(const float* raw, int64_t n, void* workspace, int* cnt_valid, hipStream_t st) {
+  hipLaunchKernelGGL(uw_chunk_pass1_kernel, dim3((unsigned)cdiv(n, (int64_t)PFXM_CHUNK)), dim3(PFXW_THREADS), 0, st, raw, n,
+                     reinterpret_cast<PfxChunk*>(workspace), cnt_valid);
+  return TDR_OK;
+}
+int tdr_uw_chunk_pass2(const float* raw, int64_t n, UwExact* ex, const int* cnt_valid, void* workspace, int* cnt_under,
+                       hipStream_t st) {
+  hipLaunchKernelGGL(uw_chunk_pass2_kernel, dim3((unsigned)cdiv(n, (int64_t)PFXM_CHUNK)), dim3(PFXW_THREADS), 0, st, raw, n,
+                     ex, cnt_valid, reinterpret_cast<PfxChunk*>(workspace), cnt_under);
   return TDR_OK;
 }
 
@@ -1866,9 +1946,25 @@ __device__ __forceinline__ void pfx_small_body(const float* __restrict__ w, int 
       }
   }
 }
+// The summary blocks of the two head kernels (pfx_small_kernel, chain_head_kernel): the waves above the summary's thread
+// count return at once and the others run chain_summary_body, barriers included.  That is sound because the cut falls on
+// whole waves (asserted here) and a wave that has ended no longer counts at the workgroup's s_barrier on this hardware.
+// Such a block is launched with the head's 1024 threads and its dynamic LDS (up to 132 KB) without using either, so one
+// fits a CU: 17 blocks at 100 000 weights; the 481 of 2 million weights take two rounds over 256 CUs.
+static_assert(PFXM_THREADS % 64 == 0 && PFXW_THREADS % 64 == 0 && PFXM_THREADS <= UWS_THREADS && PFXW_THREADS <= UWS_THREADS,
+              "summary blocks: whole waves of the head's workgroup");
+// Block 0: the one-workgroup running sum over w[0, n).  Further blocks (prefix_multi only, where these n weights are the
+// head of n_all): block b summarises chunk c_first + b - 1 of the whole array (pfx_chunk_summary_kernel's body, on its
+// PFXM_THREADS threads) — it needs the chunk sums and nothing of the head, so it runs in the head's shadow.
 __global__ __launch_bounds__(UWS_THREADS) void pfx_small_kernel(const float* __restrict__ w, int n,
                                                                 float* __restrict__ runmax, float* __restrict__ prefix_opt,
-                                                                float* __restrict__ tail) {
+                                                                float* __restrict__ tail, int64_t n_all,
+                                                                PfxChunk* __restrict__ ch, int c_first) {
+  if (blockIdx.x > 0) {
+    if (threadIdx.x < PFXM_THREADS)
+      chain_summary_body<PFXM_THREADS, PFXM_K>(PfxRunSum{{w}, CHAIN_RUNSUM, 0.f}, n_all, ch, c_first - 1);
+    return;
+  }
   pfx_small_body(w, n, runmax, prefix_opt, tail);
 }
 // batched filters (tdr_batch_step): workgroup k = filter k of the table
@@ -1877,7 +1973,10 @@ __global__ __launch_bounds__(UWS_THREADS) void pfx_small_batch_kernel(const TdrB
   pfx_small_body(e.w_out, (int)e.n, e.runmax_out, nullptr, nullptr);
 }
 #define TDR_PFX_SMALL_MAX_N 32768
-static int pfx_small(const float* w, int64_t n, float* runmax, float* prefix_opt, hipStream_t st, float* tail = nullptr) {
+// tail, n_all, ch, nch: prefix_multi's head — the sum and the maximum behind the n weights go to tail, and the launch also
+// summarises the chunks [n / PFXM_CHUNK, nch) of the n_all weights
+static int pfx_small(const float* w, int64_t n, float* runmax, float* prefix_opt, hipStream_t st, float* tail = nullptr,
+                     int64_t n_all = 0, PfxChunk* ch = nullptr, int nch = 0) {
   if (n < 1 || n > TDR_PFX_SMALL_MAX_N) return fail(TDR_ERR_ARG, "pfx_small: n out of range");
   const size_t lds = ((size_t)n + (size_t)(n >> 5) + 1 + UWS_PAD) * sizeof(float);
   static bool attr_set[64] = {false};   // per device: the attribute lives with the device's copy of the code object
@@ -1889,19 +1988,29 @@ static int pfx_small(const float* w, int64_t n, float* runmax, float* prefix_opt
       return fail(TDR_ERR_HIP, "pfx_small: cannot raise the dynamic LDS limit");
     if (dev < 64) attr_set[dev] = true;
   }
-  hipLaunchKernelGGL(pfx_small_kernel, dim3(1), dim3(UWS_THREADS), lds, st, w, (int)n, runmax, prefix_opt, tail);
+  const int c_first = ch ? (int)(n / PFXM_CHUNK) : 0;
+  hipLaunchKernelGGL(pfx_small_kernel, dim3(1 + (ch ? (unsigned)std::max(0, nch - c_first) : 0u)), dim3(UWS_THREADS), lds,
+                     st, w, (int)n, runmax, prefix_opt, tail, n_all, ch, c_first);
   return TDR_OK;
 }
 
 // The head of a statistics chain over more than 32 768 weights: its first n_head addends (whole 4096-chunks, at most
 // 32 768) staged into LDS and summed by uws_chain_total_waves; the chunk walk of chain_walk_kernel starts behind them.
+// Further blocks: block b summarises chunk c_first + b - 1 of all n_all weights (chain_summary_kernel's body, on its
+// PFXW_THREADS threads): it needs the chunk sums and nothing of the head, so it runs in the head's shadow.
 template <int KIND>
 __global__ __launch_bounds__(UWS_THREADS) void chain_head_kernel(const float* __restrict__ raw, const float* __restrict__ mean_dev,
-                                                                 int n, float* __restrict__ r_out) {
+                                                                 int n, float* __restrict__ r_out, int64_t n_all,
+                                                                 PfxChunk* __restrict__ ch, int c_first) {
+  const float mean = KIND ? *mean_dev : 0.f;
+  if (blockIdx.x > 0) {
+    if (threadIdx.x < PFXW_THREADS)
+      chain_summary_body<PFXW_THREADS, CHAIN_K>(ChainStat{{raw}, KIND, mean}, n_all, ch, c_first - 1);
+    return;
+  }
   extern __shared__ float uws_lraw[];
   __shared__ UwsShared ush;
   const int tid = threadIdx.x, lane = tid & 63, nwc = (n + UWS_WC - 1) / UWS_WC;
-  const float mean = KIND ? *mean_dev : 0.f;
   for (int c = tid >> 6; c < nwc; c += UWS_THREADS / 64) {
     const int base = c * UWS_WC + lane;
     float v[CHAIN_K];
@@ -1925,7 +2034,8 @@ __global__ __launch_bounds__(UWS_THREADS) void chain_head_kernel(const float* __
   else r = uws_chain_total_waves(UwsAddD{{}, CHAIN_BOTTOM, mean}, n, ush);
   if (tid == 0) *r_out = r;
 }
-static int chain_head_launch(const float* raw, const float* mean_dev, int kind, int n_head, float* r_out, hipStream_t st) {
+static int chain_head_launch(const float* raw, const float* mean_dev, int kind, int n_head, float* r_out, int64_t n,
+                             PfxChunk* ch, int nch, hipStream_t st) {
   const size_t lds = ((size_t)n_head + (size_t)(n_head >> 5) + 1 + UWS_PAD) * sizeof(float);
   static bool attr_set[64] = {false};   // per device: the attribute lives with the device's copy of the code object
   int dev = 0;
@@ -1938,10 +2048,12 @@ static int chain_head_launch(const float* raw, const float* mean_dev, int kind, 
       return fail(TDR_ERR_HIP, "chain_head: cannot raise the dynamic LDS limit");
     if (dev < 64) attr_set[dev] = true;
   }
+  const int c_first = n_head / PFXM_CHUNK;
+  const dim3 grid(1 + (unsigned)std::max(0, nch - c_first));
   if (kind == 0)
-    hipLaunchKernelGGL(chain_head_kernel<0>, dim3(1), dim3(UWS_THREADS), lds, st, raw, mean_dev, n_head, r_out);
+    hipLaunchKernelGGL(chain_head_kernel<0>, grid, dim3(UWS_THREADS), lds, st, raw, mean_dev, n_head, r_out, n, ch, c_first);
   else
-    hipLaunchKernelGGL(chain_head_kernel<1>, dim3(1), dim3(UWS_THREADS), lds, st, raw, mean_dev, n_head, r_out);
+    hipLaunchKernelGGL(chain_head_kernel<1>, grid, dim3(UWS_THREADS), lds, st, raw, mean_dev, n_head, r_out, n, ch, c_first);
   return TDR_OK;
 }
 
@@ -1961,13 +2073,16 @@ static int prefix_multi(const float* w, int64_t n, float* runmax_out, float* pre
   PfxChunk* ch = reinterpret_cast<PfxChunk*>(workspace);
   // the first 32 768 weights through pfx_small_kernel, the chunk walk behind them (see tdr_chain_total)
   const int c_first = chain_head_chunks(n);
-  float* tail = reinterpret_cast<float*>(&ch[0].sum);   // (chunk 0's sum is not read once the summaries are made)
+  // (header slots the walk rewrites only after it has read them; chunk 0's sum is still read by the summaries, which now
+  // run beside the head)
+  float* tail = reinterpret_cast<float*>(&ch[0].r0);
+  static_assert(offsetof(PfxChunk, carry0) == offsetof(PfxChunk, r0) + sizeof(float), "tail: sum, maximum");
   hipLaunchKernelGGL(pfx_chunk_sum_kernel, dim3(nch), dim3(PFXM_THREADS), 0, st, w, n, ch);
-  if (nch > c_first)
-    hipLaunchKernelGGL(pfx_chunk_summary_kernel, dim3(nch - c_first), dim3(PFXM_THREADS), 0, st, w, n, ch, c_first);
-  if (c_first > 0) {
-    const int rc = pfx_small(w, (int64_t)c_first * PFXM_CHUNK, runmax_out, prefix_out, st, tail);
+  if (c_first > 0) {   // head and the summaries behind it in one launch
+    const int rc = pfx_small(w, (int64_t)c_first * PFXM_CHUNK, runmax_out, prefix_out, st, tail, n, ch, nch);
     if (rc) return rc;
+  } else if (nch > c_first) {
+    hipLaunchKernelGGL(pfx_chunk_summary_kernel, dim3(nch - c_first), dim3(PFXM_THREADS), 0, st, w, n, ch, c_first);
   }
   const int head_len = tdr_cfg().pfx_head;
   hipLaunchKernelGGL(pfx_walk_kernel, dim3(1), dim3(PFXW_THREADS), 0, st, w, n, ch, nch, runmax_out, prefix_out,

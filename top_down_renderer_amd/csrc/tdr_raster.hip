@@ -61,7 +61,7 @@ static int launch_raster(const float* pts, int stride, int ioff, int64_t n, floa
   if (stride < 3 || ioff < 0 || ioff >= stride) return fail(TDR_ERR_ARG, "raster: bad point stride / offset");
   if (!(res > 0.f) || (polar && !(ang_res > 0.f))) return fail(TDR_ERR_ARG, "raster: resolution must be > 0");
   RasterShape sh;
-  if (!raster_shape(ncls, rows, cols, &sh)) return fail(TDR_ERR_ARG, "raster: ncls*rows too large for one LDS tile (152 KB)");
+  if (!raster_shape(ncls, rows, cols, workspace && n > 0, &sh)) return fail(TDR_ERR_ARG, "raster: ncls*rows too large for one LDS tile (152 KB)");
   RasterArgs a;
   a.pts = pts; a.stride = stride; a.ioff = ioff; a.n = n; a.res = res; a.ang_res = ang_res; a.lut = lut;
   a.ncls = ncls; a.rows = rows; a.cols = cols; a.rf = tdr_rec_floats(ncls); a.polar = polar; a.img = img; a.pk = pk;

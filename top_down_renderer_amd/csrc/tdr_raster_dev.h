@@ -66,14 +66,41 @@ __device__ __forceinline__ uint32_t raster_key(const float* __restrict__ pts, in
 __device__ __forceinline__ void raster_tile_clear(unsigned int* cnt, int tile) {
   for (int t = threadIdx.x; t < tile; t += blockDim.x) cnt[t] = 0;
 }
+// one key against the tile: an integer LDS atomic (exact, order-free)
+__device__ __forceinline__ void raster_tile_count_key(unsigned int* cnt, uint32_t key, int col0, int ncol, int ncls,
+                                                      int rows) {
+  const int col = (int)(key >> 20) - col0;
+  if (key == RASTER_NO_BIN || col < 0 || col >= ncol) return;
+  atomicAdd(&cnt[(col * ncls + (int)((key >> 16) & 15u)) * rows + (int)(key & 0xFFFFu)], 1u);
+}
+// Every thread of every tile walks all n keys, so the walk is bound by load latency, not by bytes: the keys are read as
+// 16-byte vectors, RASTER_KEY_VECS of them in flight per thread, behind a scalar head up to the first 16-byte boundary
+// (the workspace need only be 4-byte aligned) and in front of a scalar tail.
+#define RASTER_KEY_VECS 4
 __device__ __forceinline__ void raster_tile_count_keys(unsigned int* cnt, const uint32_t* __restrict__ keys, int64_t n,
                                                        int col0, int ncol, int ncls, int rows) {
-  for (int64_t q = threadIdx.x; q < n; q += blockDim.x) {
-    const uint32_t key = keys[q];
-    const int col = (int)(key >> 20) - col0;
-    if (key == RASTER_NO_BIN || col < 0 || col >= ncol) continue;
-    atomicAdd(&cnt[(col * ncls + (int)((key >> 16) & 15u)) * rows + (int)(key & 0xFFFFu)], 1u);
+  const int64_t to16 = (int64_t)((4u - (unsigned)((reinterpret_cast<uintptr_t>(keys) >> 2) & 3u)) & 3u);
+  const int64_t head = to16 < n ? to16 : n;
+  const int64_t nv = (n - head) >> 2;
+  if ((int64_t)threadIdx.x < head) raster_tile_count_key(cnt, keys[threadIdx.x], col0, ncol, ncls, rows);
+  const uint4* __restrict__ kv = reinterpret_cast<const uint4*>(keys + head);
+  for (int64_t q = threadIdx.x; q < nv; q += (int64_t)RASTER_KEY_VECS * blockDim.x) {
+    uint4 v[RASTER_KEY_VECS];
+#pragma unroll
+    for (int u = 0; u < RASTER_KEY_VECS; u++) {
+      const int64_t qu = q + (int64_t)u * blockDim.x;
+      v[u] = qu < nv ? kv[qu] : make_uint4(RASTER_NO_BIN, RASTER_NO_BIN, RASTER_NO_BIN, RASTER_NO_BIN);
+    }
+#pragma unroll
+    for (int u = 0; u < RASTER_KEY_VECS; u++) {
+      raster_tile_count_key(cnt, v[u].x, col0, ncol, ncls, rows);
+      raster_tile_count_key(cnt, v[u].y, col0, ncol, ncls, rows);
+      raster_tile_count_key(cnt, v[u].z, col0, ncol, ncls, rows);
+      raster_tile_count_key(cnt, v[u].w, col0, ncol, ncls, rows);
+    }
   }
+  const int64_t tail = head + 4 * nv + threadIdx.x;   // at most three keys
+  if (tail < n) raster_tile_count_key(cnt, keys[tail], col0, ncol, ncls, rows);
 }
 // the tile written whole, zeros included: the class planes img[ncls][rows * cols] and the packed records pk[rows * cols][rf]
 // (either may be null)
@@ -113,17 +140,23 @@ struct RasterShape {
   size_t lds;    // bytes of a tile's counters
   bool keyed;    // the image's bins fit the 4-byte key
 };
-// false: one image column does not fit an LDS tile
-static inline bool raster_shape(int ncls, int rows, int cols, RasterShape* out) {
+// tiles the keyed form asks for: a workgroup per CU of an MI355X (256 CUs) — a constant, not queried from the device, so
+// that an image's tiles, like its bits, do not depend on the card; fewer CUs run the tiles in rounds
+#define RASTER_KEYED_TILES 256
+// false: one image column does not fit an LDS tile.  with_keys: the shape of the keyed form (a key workspace and
+// out->keyed) — a tile there costs one more walk over the 4-byte keys and no arithmetic, so the image is cut into a tile
+// per CU where it has the columns; without keys every tile computes every point's bin again, and 32 tiles stay enough.
+static inline bool raster_shape(int ncls, int rows, int cols, bool with_keys, RasterShape* out) {
   const int64_t per_col = (int64_t)ncls * rows * 4;
   if (per_col > RASTER_MAX_LDS) return false;
+  out->keyed = cols <= RASTER_KEY_MAX_COLS && rows <= RASTER_KEY_MAX_ROWS;
   int cpt = (int)std::max<int64_t>(1, (64 * 1024) / per_col);
   cpt = std::min(cpt, cols);
   // enough workgroups to spread over the chip when the image is small
-  while (cpt > 1 && cdiv(cols, cpt) < 32) cpt = (cpt + 1) / 2;
+  const int want = (with_keys && out->keyed) ? RASTER_KEYED_TILES : 32;
+  while (cpt > 1 && cdiv(cols, cpt) < want) cpt = (cpt + 1) / 2;
   out->cpt = cpt;
   out->lds = (size_t)cpt * per_col;
-  out->keyed = cols <= RASTER_KEY_MAX_COLS && rows <= RASTER_KEY_MAX_ROWS;
   return true;
 }
 // a tile of more than 64 KB (one column, cpt = 1) has to be allowed per kernel and device, once; attr_set: the kernel's own

@@ -660,14 +660,27 @@ __global__ __launch_bounds__(256) void score_finalize_exact_kernel(FinalizeArgs 
   unsigned long long tot[TDR_MAX_CLASSES], norm = 0, known = 0;
 #pragma unroll
   for (int k = 0; k < TDR_MAX_CLASSES; k++) tot[k] = 0;
-  for (int c = t; c < nch; c += 4) {
-    const uint32_t* o = a.ipart + (int64_t)c * rows * a.npad + slot;
+  // two chunk rows per step, every word of both loaded before the first is added: a lane has 2 x rows loads in flight
+  // instead of one row's (integers: the same total in any grouping); an odd row count reads its last row twice and adds it once
+  for (int c = t; c < nch; c += 8) {
+    const bool two = c + 4 < nch;
+    const uint32_t* o0 = a.ipart + (int64_t)c * rows * a.npad + slot;
+    const uint32_t* o1 = a.ipart + (int64_t)(two ? c + 4 : c) * rows * a.npad + slot;
+    uint32_t v0[2 * TDR_MAX_CLASSES], v1[2 * TDR_MAX_CLASSES];
+#pragma unroll
+    for (int k = 0; k < 2 * TDR_MAX_CLASSES; k++)
+      if (k < 2 * a.ncls) { v0[k] = o0[(int64_t)k * a.npad]; v1[k] = o1[(int64_t)k * a.npad]; }
+    const uint32_t n0 = o0[(int64_t)(2 * a.ncls) * a.npad], k0 = o0[(int64_t)(2 * a.ncls + 1) * a.npad];
+    const uint32_t n1 = o1[(int64_t)(2 * a.ncls) * a.npad], k1 = o1[(int64_t)(2 * a.ncls + 1) * a.npad];
 #pragma unroll
     for (int k = 0; k < TDR_MAX_CLASSES; k++)
-      if (k < a.ncls)
-        tot[k] += (unsigned long long)o[(int64_t)(2 * k) * a.npad] | ((unsigned long long)o[(int64_t)(2 * k + 1) * a.npad] << 32);
-    norm += o[(int64_t)(2 * a.ncls) * a.npad];
-    known += o[(int64_t)(2 * a.ncls + 1) * a.npad];
+      if (k < a.ncls) {
+        tot[k] += (unsigned long long)v0[2 * k] | ((unsigned long long)v0[2 * k + 1] << 32);
+        if (two) tot[k] += (unsigned long long)v1[2 * k] | ((unsigned long long)v1[2 * k + 1] << 32);
+      }
+    norm += n0;
+    known += k0;
+    if (two) { norm += n1; known += k1; }
   }
   if (t > 0) {
 #pragma unroll

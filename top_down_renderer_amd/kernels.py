@@ -639,6 +639,16 @@ class HipKernels:
         cap = st.shape[1] if (st.dim() == 2 and src_shard == 0) else 0
         check(self.lib.tdr_k_save_ml_state(_ptr(info), _ptr(st), cap, src_shard, n, _ptr(out12), self.stream()))
 
+    def resample_gather(self, runmax, n, n_new, shift, i_begin, i_end, idx, src, dst, info, out12, src_shard=0):
+        """resample (shift: a float, or the device word holding the draw), gather_states and save_ml_state in one launch:
+        idx, dst and out12 as those three leave them; src is the set BEFORE the resample, in either layout."""
+        on_dev = hasattr(shift, "data_ptr")   # a tensor, or the DevPtr a generator pipe hands out
+        src_cap = src.shape[1] if (src.dim() == 2 and src_shard == 0) else 0
+        check(self.lib.tdr_k_resample_gather(_ptr(runmax), n, n_new, _ptr(shift) if on_dev else None,
+                                             C.c_float(0.0 if on_dev else shift), i_begin, i_end, _ptr(idx), _ptr(src),
+                                             src_cap, src_shard, _ptr(dst), dst.shape[1], _ptr(info), _ptr(out12),
+                                             self.stream()))
+
     def mean_cov(self, st, n, about=None):
         """about: optional device tensor of 4 floats (computeCov about that mlState); None = about the mean."""
         out = self.empty((4800,))   # TDR_MEAN_COV_FLOATS: 24 results + reduction scratch
@@ -802,6 +812,7 @@ class HipKernels:
 
     # the same generator continued on the device (csrc/tdr_rng.hip): state = 640 uint32 words (include/tdr.h)
     device_rng = True
+    fused_resample = True   # resample_gather: the unsharded update's tail in one launch (tdr_k_resample_gather)
 
     def rng_state_to_device(self, rng):
         words = np.zeros(640, np.uint32)

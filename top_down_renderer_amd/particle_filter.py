@@ -371,19 +371,31 @@ class ParticleFilter:
         if shift is None and self._rng_on_device:
             # :172-173 (every rank owns an identically seeded generator): the stream is on the device, so is the draw
             self._shift_dev = self._pipe.uniform()
-            k.resample_dev(self.runmax, n, n_new, self._shift_dev, i0, i0 + nl_new, self.idx)
+        elif shift is None:
+            shift = k.rng_uniform(self.gen_)
+        # unsharded: index, seven state rows and the max-likelihood particle of the old set in one launch
+        # (tdr_k_resample_gather).  The sharded update keeps the three calls (the state all-gather lies between them), and
+        # so does a kernel interface that does not declare `fused_resample` (like `device_rng`: HipKernels declares both,
+        # the CPU stand-in of the distributed tests neither).
+        if not comm.active and getattr(k, "fused_resample", False):
+            if self._ml_buf is None:
+                self._ml_buf = k.zeros((12,))
+            k.resample_gather(self.runmax, n, n_new, self._shift_dev if shift is None else float(shift), i0, i0 + nl_new,
+                              self.idx, self.st, self.st_new, self.info, self._ml_buf)
+            self._ml_fields = self._ml_buf[:7]
         else:
             if shift is None:
-                shift = k.rng_uniform(self.gen_)
-            k.resample(self.runmax, n, n_new, float(shift), i0, i0 + nl_new, self.idx)
-        if comm.active:
-            if st_work is not None:
-                st_work.wait()
-            k.gather_states(sa, self.idx, nl_new, self.st_new, src_shard=nl)
-            self._save_ml_state(sa, nl)
-        else:
-            k.gather_states(self.st, self.idx, nl_new, self.st_new)
-            self._save_ml_state(None, nl)
+                k.resample_dev(self.runmax, n, n_new, self._shift_dev, i0, i0 + nl_new, self.idx)
+            else:
+                k.resample(self.runmax, n, n_new, float(shift), i0, i0 + nl_new, self.idx)
+            if comm.active:
+                if st_work is not None:
+                    st_work.wait()
+                k.gather_states(sa, self.idx, nl_new, self.st_new, src_shard=nl)
+                self._save_ml_state(sa, nl)
+            else:
+                k.gather_states(self.st, self.idx, nl_new, self.st_new)
+                self._save_ml_state(None, nl)
         self.st, self.st_new = self.st_new, self.st   # :187
         self.num_particles_ = n_new
         self.perm = None if n_new != n else self.perm
