@@ -648,6 +648,23 @@ size_t tdr_k_su_order_workspace_ints(int64_t n, int nb);
 int64_t tdr_k_su_order_slots(int64_t n, int nb);
 int tdr_k_su_order(const float* st, int64_t cap, int64_t n, const int32_t* perm, int nb, float span, int32_t* workspace,
                    int32_t* slots_out, int32_t* keys_out, int32_t* counts_out, int* bucket_out, void* stream);
+/* The ordering passes and the scan-side preparation of an integer-form scoring call on their own (tests, timing): what
+ * tdr_k_score_polar_ctx runs in front of its two integer kernels, with the same arguments, on a workspace of
+ * tdr_score_workspace_floats floats; `span` as in tdr_k_su_order.  The call must have an integer form (a map with compact
+ * records, shapes the shift-uniform kernel takes: tdr_config_shift_uniform).  layout (host, 16 words): {rings per group G of the
+ * shift-uniform layout, groups C, padded rings per direction of the preparation's grid, steps per block and blocks per
+ * direction of the ray-mapped layout, block-major order 0 | 1, patch order 0 | 1, padded samples T of the ray-mapped layout,
+ * bins C nb G of the shift-uniform layout, sectors S per group, words behind the counts, uniform scale 0 | 1, 0...}.  With
+ * workspace == NULL only `layout` is filled.  out (host array of 9 device pointers, NULL = not wanted): [0] the uniform-scale
+ * table, 2 nb nr floats (untouched without a uniform scale); [1] sample offsets [C][nb][G][2] and [2] scan descriptors
+ * [C][nb][G][4] of the shift-uniform layout; [3] boxes [C][S]{min, max, min, max}; [4] sample offsets, 2 T floats, [5]
+ * 16-bit descriptors, (T + 1) / 2 words, [6] radii, T / nb floats (written only with the context's factors), of the ray-mapped
+ * layout; [7] the list of bins with several classes, nb nr words of which the first n_list are defined, in any order; [8] the
+ * words behind the counts: {dense slots, scattered particles, both, n_list, inexact, mass bound, table is not its factors, 3
+ * spare}. */
+int tdr_k_score_prep(const tdr_map_desc* map, const float* tab, const float* scan_pk, int nb, int nr, float res,
+                     const float* st, int64_t cap, int64_t n, int64_t n_total, const int32_t* perm, float uniform_scale,
+                     float span, float* workspace, tdr_score_ctx* ctx, int64_t* layout, void* const* out, void* stream);
 /* Device self-test of the scoring kernels: a tiny fixed problem (160 x 160 map, 6 classes, 512 particles) scored by every
  * kernel the library has for it.  The integer-form kernels run generated, hand-scheduled assembly; their sums are exact, so
  * score_polar_su_kernel == score_polar_ray_kernel and score_cart_su_kernel == score_cart_skip_kernel == score_cart_ray_kernel

@@ -159,6 +159,8 @@ SIGNATURES = {
     "tdr_k_su_order_workspace_ints": (C.c_size_t, [_i64, _i]),
     "tdr_k_su_order_slots": (_i64, [_i64, _i]),
     "tdr_k_su_order": (_i, [_vp, _i64, _i64, _vp, _i, _f, _vp, _vp, _vp, _vp, C.POINTER(_i), _vp]),
+    "tdr_k_score_prep": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _i64, _i64, _i64, _vp, _f, _f, _vp, _vp, C.POINTER(_i64),
+                              C.POINTER(_vp), _vp]),
     "tdr_selftest_score": (_i, []),
     "tdr_profile_variants": (_i, [C.POINTER(_i64)]),
     "tdr_score_ctx_set_polar_factors": (_i, [_vp, _vp, _i, _i]),

@@ -26,7 +26,7 @@ struct TdrConfig {
   int su_tail_groups = 4, su_tail_parts = 4;
   int su_order_bucket = 1;   // 0: the heading order always through rocPRIM's sort (A/B; su_seg_table_words has the rule)
   int ray_split = 0;         // waves per scattered particle; 0: chosen per launch (tdr_ray_splits)
-  int ray_borrow = 1;        // empty bins borrow a neighbour's class plane for their known bit (ray_prep_kernel)
+  int ray_borrow = 1;        // empty bins borrow a neighbour's class plane for their known bit (score_prep_kernel)
   int ray_patch = 1;         // 0: the ray order also where the patch order applies (tdr_score_ray.hip; A/B, same bits)
   int ray_block_major = 1;   // 0: the first (direction-major) row order everywhere (tdr_score_ray.hip; A/B, same bits)
   int cart_skip = 1;         // 0: the general Cartesian kernel also where the skipping kernel applies (A/B, tests)

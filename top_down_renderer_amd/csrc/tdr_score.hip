@@ -282,6 +282,29 @@ __global__ __launch_bounds__(256, COMPACT ? (WIDE ? 3 : 5) : 1) void score_polar
 #endif
   score_polar_body<NV4, U, KSLOT, USCALE, COMPACT, WIDE>(a, bx, blockIdx.y);
 }
+// The float form BEHIND the integer kernels of a launch (a.run_if set): a bounded grid — at most what the chip holds resident
+// — whose workgroups walk the launch's workgroup ids (vx, vy), x fastest like the dispatcher.  The flag is read once: while the
+// integer form is on, which is every call of a scan and a map that have one, the grid leaves at once instead of starting one
+// workgroup per unit that reads the flag and returns.  Per id the body is score_polar_kernel's own (its LDS image staged anew,
+// a barrier between two ids): a particle's partial sums are per (slot, ring group) and do not depend on which workgroup forms
+// them — the bits of the plain launch.
+template <int NV4, int U, bool KSLOT, bool USCALE, bool COMPACT, bool WIDE = false>
+__global__ __launch_bounds__(256, COMPACT ? (WIDE ? 3 : 5) : 1) void score_polar_bounded_kernel(ScoreArgs a, unsigned nbx, unsigned nby) {
+  if (!int_form_off(a.run_if)) return;   // (uniform)
+  a.run_if = nullptr;
+  const uint64_t total = (uint64_t)nbx * nby;
+  for (uint64_t v = blockIdx.x; v < total; v += gridDim.x) {
+    const unsigned vy = (unsigned)(v / nbx), vx = (unsigned)(v - (uint64_t)vy * nbx);
+#if TDR_XCD_SWIZZLE
+    const unsigned per = (nbx + 7) / 8;
+    const unsigned bx = nbx % 8 != 0 ? vx : (vx % 8) * per + vx / 8;
+#else
+    const unsigned bx = vx;
+#endif
+    score_polar_body<NV4, U, KSLOT, USCALE, COMPACT, WIDE>(a, bx, vy);
+    __syncthreads();   // every wave is through with the LDS image before the next id's is staged
+  }
+}
 // batched filters (tdr_batch_step): filter e owns the blocks [blk[e], blk[e + 1]) of grid.x and grid.y rows
 // [0, its nchunks); its ScoreArgs are args[e].  Filters whose USCALE differs from the instantiation's are another launch.
 template <int NV4, int U, bool KSLOT, bool USCALE, bool COMPACT, bool WIDE = false>
@@ -634,6 +657,14 @@ __device__ __forceinline__ void score_finalize_body(const FinalizeArgs& a, const
 __global__ __launch_bounds__(256) void score_finalize_kernel(FinalizeArgs a) {
   score_finalize_body(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
+// ... behind the exact finalize (a.run_if set): a bounded grid that reads the flag once and walks the launch's threads
+// (`total`, whole workgroups) in strides of the grid
+__global__ __launch_bounds__(256) void score_finalize_bounded_kernel(FinalizeArgs a, int64_t total) {
+  if (!int_form_off(a.run_if)) return;   // (uniform)
+  a.run_if = nullptr;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x)
+    score_finalize_body(a, g);
+}
 __global__ __launch_bounds__(256) void score_finalize_batch_kernel(const FinalizeArgs* __restrict__ args,
                                                                    const int32_t* __restrict__ blk, int k) {
   const int e = batch_find(k, (int)blockIdx.x, [&](int i) { return blk[i]; });
@@ -731,9 +762,26 @@ static int finalize_tlog(int nchunks, int64_t nslots) {
   return tl;
 }
 // nslots: slots the launch covers (a.n / a.count still bound the active ones)
-static void launch_finalize(FinalizeArgs& f, int64_t nslots, hipStream_t s) {
+// Workgroups of a launch that runs only while the integer form is off (run_if): what the chip holds resident — `per_cu` of them
+// on each compute unit — and never more than a quarter of TdrConfig::score_waves (four waves a workgroup: tests make it small)
+static int64_t bounded_grid(int64_t units, int per_cu) {
+  static int cus = 0;   // (one kind of device per process)
+  if (cus <= 0) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
+    else return std::max<int64_t>(1, std::min<int64_t>(units, 256 * per_cu));
+  }
+  const int64_t cap = std::min<int64_t>((int64_t)cus * per_cu, std::max<int64_t>(1, tdr_cfg().score_waves / 4));
+  return std::max<int64_t>(1, std::min(units, cap));
+}
+// bounded (the polar call's float form behind its integer kernels; f.run_if set): the bounded grid
+static void launch_finalize(FinalizeArgs& f, int64_t nslots, hipStream_t s, bool bounded = false) {
   f.tlog = finalize_tlog(f.nchunks, nslots);
-  hipLaunchKernelGGL(score_finalize_kernel, dim3((unsigned)cdiv(nslots << f.tlog, 256)), dim3(256), 0, s, f);
+  const int64_t blocks = cdiv(nslots << f.tlog, 256);
+  if (bounded && f.run_if)
+    hipLaunchKernelGGL(score_finalize_bounded_kernel, dim3((unsigned)bounded_grid(blocks, 8)), dim3(256), 0, s, f, blocks * 256);
+  else
+    hipLaunchKernelGGL(score_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, s, f);
 }
 
 // the Cartesian kernel likes twice as many, shorter waves (A/B on MI355X, config 4: x1 183 ms, x2 179 ms, x4 177 ms)
@@ -992,7 +1040,8 @@ static size_t polar_lds_bytes(int nb, int group, int rf) { return (size_t)nb * (
 
 // The instantiation of score_polar_kernel (BATCH: score_polar_batch_kernel) for this map: f(kernel).  Compact records
 // exist up to 12-float records, wide ones for 8-float records only: no other combination is instantiated.
-template <bool BATCH, class F>
+// (KIND: 0 score_polar_kernel, 1 score_polar_batch_kernel, 2 score_polar_bounded_kernel)
+template <int KIND, class F>
 static int with_polar_kernel(const tdr_map_desc* map, int rf, bool us, const char* who, F&& f) {
   const bool cm = map_has_compact(map, rf);
   return with_nv4(rf, who, [&](auto N) {
@@ -1000,7 +1049,8 @@ static int with_polar_kernel(const tdr_map_desc* map, int rf, bool us, const cha
       constexpr int NV4 = decltype(N)::value;
       constexpr bool ks = decltype(KS)::value, usc = decltype(US)::value, c = decltype(CM)::value, w = decltype(WD)::value;
       if constexpr ((c && NV4 == 4) || (w && !(c && NV4 == 2))) return fail(TDR_ERR_ARG, "%s: no kernel for this record form", who);
-      else if constexpr (BATCH) return f(score_polar_batch_kernel<NV4, TDR_SCORE_U, ks, usc, c, w>);
+      else if constexpr (KIND == 1) return f(score_polar_batch_kernel<NV4, TDR_SCORE_U, ks, usc, c, w>);
+      else if constexpr (KIND == 2) return f(score_polar_bounded_kernel<NV4, TDR_SCORE_U, ks, usc, c, w>);
       else return f(score_polar_kernel<NV4, TDR_SCORE_U, ks, usc, c, w>);
     }, tdr_has_kslot(map->ncls, rf), us, cm, cm && map_is_wide(map, rf));
   });
@@ -1014,7 +1064,20 @@ static int launch_score(ScoreArgs a, const tdr_map_desc* map, int rf, hipStream_
   set_compact(a, map, rf);
   const dim3 grid((unsigned)cdiv(a.n, 256), (unsigned)a.nchunks), block(256);
   const size_t lds = polar_lds_bytes(a.nb, a.group, rf);
-  if (int rc = with_polar_kernel<false>(map, rf, a.utab != nullptr, "score", [&](auto kfn) {
+  if (a.run_if) {   // the float form behind the integer kernels: a bounded grid that leaves when the flag is clear
+    const bool cm = map_has_compact(map, rf);
+    const int per_cu = cm ? (map_is_wide(map, rf) ? 3 : 5) : 1;   // score_polar_bounded_kernel's launch bounds
+    const dim3 bgrid((unsigned)bounded_grid((int64_t)grid.x * grid.y, per_cu));
+    if (int rc = with_polar_kernel<2>(map, rf, a.utab != nullptr, "score", [&](auto kfn) {
+          allow_lds(kfn, lds);
+          hipLaunchKernelGGL(kfn, bgrid, block, lds, s, a, grid.x, grid.y);
+          return TDR_OK;
+        }))
+      return rc;
+    LAUNCH_CHECK("score_polar_bounded");
+    return TDR_OK;
+  }
+  if (int rc = with_polar_kernel<0>(map, rf, a.utab != nullptr, "score", [&](auto kfn) {
         allow_lds(kfn, lds);
         hipLaunchKernelGGL(kfn, grid, block, lds, s, a);
         return TDR_OK;
@@ -1232,7 +1295,7 @@ int tdr_batch_score_launch(const tdr_map_desc* map, const float* tab, int nb, in
   const dim3 grid((unsigned)h.blocks, (unsigned)h.max_chunks);
   for (int us = 1; us >= 0; us--) {   // the filters with a uniform-scale table, then the others: one instantiation each
     if (us ? h.n_uscale == 0 : h.n_uscale == k) continue;
-    if (int rc = with_polar_kernel<true>(map, rf, us != 0, "batch_score", [&](auto kfn) {
+    if (int rc = with_polar_kernel<1>(map, rf, us != 0, "batch_score", [&](auto kfn) {
           allow_lds(kfn, h.lds);
           hipLaunchKernelGGL(kfn, grid, dim3(256), h.lds, s, args, blk, k);
           return TDR_OK;
@@ -1244,6 +1307,53 @@ int tdr_batch_score_launch(const tdr_map_desc* map, const float* tab, int nb, in
   LAUNCH_CHECK("batch_score_finalize");
   if (h.k_init > 0) return tdr_batch_init_fixup(static_cast<const char*>(host_stage) + Lo.total, d + Lo.total, s);
   return TDR_OK;
+}
+// SuLaunch of an integer-form call with the ScoreArgs `a` (a.utab: where the uniform-scale table is or will be) on `workspace`;
+// the caller adds the span
+static SuLaunch make_su_launch(const tdr_map_desc* map, const ScoreArgs& a, int rf, float uniform_scale, const tdr_score_ctx* ctx,
+                               const ScoreWs& W, float* workspace) {
+  const int nb = a.nb, nr = a.nr;
+  SuLaunch L;
+  L.map = map; L.tab = a.utab ? a.utab : a.tab; L.uniform_scale = a.utab != nullptr; L.scan_pk = a.scan_pk;
+  L.tab_src = a.tab; L.utab_out = const_cast<float*>(a.utab);
+  L.nb = nb; L.nr = nr; L.rf = rf; L.res = a.res; L.st = a.st; L.cap = a.cap; L.n = a.n; L.perm = a.order;
+  L.group = W.su_group; L.nchunks = W.su_nchunks; L.npad = W.npad_part; L.part = a.part;
+  L.tail_k = W.su_tail_k; L.tail_q = W.su_tail_q; L.rows = W.su_rows;
+  L.fac = ctx && ctx->fac && ctx->fac_nb == nb && ctx->fac_nr == nr ? ctx->fac : nullptr;
+  L.uscale = uniform_scale;
+  L.ray_split = tdr_ray_splits(nb, nr, a.n, tdr_cfg().ray_block_major && L.fac != nullptr);
+  L.ws = workspace ? reinterpret_cast<int32_t*>(workspace + W.off_su) : nullptr;   // (NULL: tdr_k_score_prep asking for the shapes)
+  L.span = tdr_cfg().su_span;
+  return L;
+}
+// The ordering passes and the scan-side preparation of an integer-form call on their own (include/tdr.h)
+extern "C" int tdr_k_score_prep(const tdr_map_desc* map, const float* tab, const float* scan_pk, int nb, int nr, float res,
+                                const float* st, int64_t cap, int64_t n, int64_t n_total, const int32_t* perm,
+                                float uniform_scale, float span, float* workspace, tdr_score_ctx* ctx, int64_t* layout,
+                                void* const* out, void* stream) {
+  if (!map || !map->rec || !layout) return fail(TDR_ERR_ARG, "score_prep: null pointer");
+  if (n_total <= 0) n_total = n;
+  if (n < 1 || cap < n || nb < 1 || nr < 1) return fail(TDR_ERR_ARG, "score_prep: bad shape");
+  if (map->ncls < 1 || map->ncls > TDR_MAX_CLASSES) return fail(TDR_ERR_ARG, "score_prep: bad class count");
+  const int rf = tdr_rec_floats(map->ncls);
+  if (map->rec_floats != rf) return fail(TDR_ERR_ARG, "score_prep: map record size %d != %d", map->rec_floats, rf);
+  const ScoreWs W = score_ws(map->ncls, nb, nr, n, n_total);
+  if (!int_form_applies(W, map, rf)) return fail(TDR_ERR_ARG, "score_prep: the call has no integer form");
+  ScoreArgs a = make_score_args(map, tab, scan_pk, nb, nr, res, st, cap, n, perm, W);
+  a.part = workspace;
+  a.utab = uniform_scale > 0.f && workspace ? workspace + W.off_utab : nullptr;
+  SuLaunch L = make_su_launch(map, a, rf, uniform_scale, ctx, W, workspace);
+  L.uniform_scale = uniform_scale > 0.f;
+  L.span = span;
+  hipStream_t s = (hipStream_t)stream;
+  if (!workspace) {   // the shapes alone
+    return tdr_su_prep_copy_out(L, W.suw, s, layout, nullptr);
+  }
+  if (!tab || !scan_pk || !st || !out) return fail(TDR_ERR_ARG, "score_prep: null pointer");
+  const int32_t* slots = nullptr;
+  const int32_t* counts = nullptr;
+  if (int rc = tdr_su_prepare(L, W.suw, s, &slots, &counts)) return rc;
+  return tdr_su_prep_copy_out(L, W.suw, s, layout, out);
 }
 extern "C" int tdr_k_score_polar(const tdr_map_desc* map, const float* tab, const float* scan_pk, int nb, int nr,
                                  float res, const tdr_filter_params* fp, float* st, int64_t cap, int64_t n,
@@ -1274,8 +1384,15 @@ extern "C" int tdr_k_score_polar_ctx(const tdr_map_desc* map, const float* tab, 
   const ScoreWs W = score_ws(map->ncls, nb, nr, n, n_total);
   ScoreArgs a = make_score_args(map, tab, scan_pk, nb, nr, res, st, cap, n, perm, W);
   a.part = workspace;
-  int rc = fill_utab(a, workspace, W, uniform_scale, s);
-  if (rc) return rc;
+  // the uniform-scale table: a launch of its own for the float form and in front of the init search; an integer-form call
+  // leaves it to its preparation kernel (tdr_su_prepare), which writes the same words
+  const bool int_form = int_form_applies(W, map, rf);
+  int rc = TDR_OK;
+  if (int_form && !init_search) {
+    a.utab = uniform_scale > 0.f ? workspace + W.off_utab : nullptr;
+  } else if ((rc = fill_utab(a, workspace, W, uniform_scale, s))) {
+    return rc;
+  }
   float* res_flag = workspace + W.off_aux;   // npad floats; behind them res_theta (npad) and the search's rotation table
   // state_particle.cpp:195-206 first: it fixes theta / have_init of the un-initialised particles, the regular pass
   // below then scores every particle at its (possibly just chosen) rotation
@@ -1283,7 +1400,7 @@ extern "C" int tdr_k_score_polar_ctx(const tdr_map_desc* map, const float* tab, 
     if ((rc = tdr_score_init_search(map, a.tab, a.utab, scan_pk, nb, nr, res, fp, st, cap, n, n_total, perm, res_flag, a.npad, s)))
       return rc;
   FinalizeArgs f = make_finalize_args(map, fp, a.part, a.nchunks, a.npad, (int64_t)nb * nr, st, cap, n, perm, raw_w);
-  if (int_form_applies(W, map, rf)) {
+  if (int_form) {
     // The INTEGER form of the launch (tdr_score_su.h): dense particles by heading bin through the shift-uniform kernel,
     // scattered ones — behind the bins in the same slot list — one wave each through the ray-mapped kernel; both form exact
     // integer sums, so a particle's weight does not depend on which of the two scored it.  A scan or a map without
@@ -1291,20 +1408,11 @@ extern "C" int tdr_k_score_polar_ctx(const tdr_map_desc* map, const float* tab, 
     // the integer kernels then return at once and the float kernel below does the launch — nothing is decided on the host.
     const int32_t* slots = nullptr;
     const int32_t* counts = nullptr;   // device words {slots of the dense share, scattered particles behind them, both}
-    SuLaunch L;
-    L.map = map; L.tab = a.utab ? a.utab : a.tab; L.uniform_scale = a.utab != nullptr; L.scan_pk = scan_pk;
-    L.nb = nb; L.nr = nr; L.rf = rf; L.res = res; L.st = st; L.cap = cap; L.n = n; L.perm = perm;
-    L.group = W.su_group; L.nchunks = W.su_nchunks; L.npad = W.npad_part; L.part = a.part;
-    L.tail_k = W.su_tail_k; L.tail_q = W.su_tail_q; L.rows = W.su_rows;
-    L.fac = ctx && ctx->fac && ctx->fac_nb == nb && ctx->fac_nr == nr ? ctx->fac : nullptr;
-    L.uscale = uniform_scale;
-    L.ray_split = tdr_ray_splits(nb, nr, n, tdr_cfg().ray_block_major && L.fac != nullptr);
-    L.ws = reinterpret_cast<int32_t*>(workspace + W.off_su);
+    SuLaunch L = make_su_launch(map, a, rf, uniform_scale, ctx, W, workspace);
     TunerScope tuner_scope(ctx, s);   // (closes the tuner's measurement on every way out)
     L.span = tdr_su_span_begin(ctx ? &ctx->tuner : nullptr,
                                ((int64_t)n << 24) ^ ((int64_t)nb << 12) ^ nr ^ ((int64_t)map->rows << 40), s);
     if ((rc = tdr_su_prepare(L, W.suw, s, &slots, &counts))) return rc;
-    if ((rc = tdr_ray_prepare(L, W.suw, s))) return rc;
     const int32_t* inexact = counts + 4;
     {
       ScoreProfScope prof(s);
@@ -1324,7 +1432,7 @@ extern "C" int tdr_k_score_polar_ctx(const tdr_map_desc* map, const float* tab, 
     }
     launch_finalize_exact(f, map, W.npad_part, slots, counts, inexact, W.su_rows, L.ray_split, s);
     LAUNCH_CHECK("score_finalize_exact");
-    launch_finalize(f, n, s);
+    launch_finalize(f, n, s, true);
   } else {
     if ((rc = launch_score(a, map, rf, s))) return rc;
     launch_finalize(f, n, s);

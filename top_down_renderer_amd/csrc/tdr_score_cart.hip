@@ -652,7 +652,7 @@ static inline int cart_ray_blocks(int cols) { return (int)cdiv(cols, 64 * cart_r
 
 // One thread per (window row i, padded column j): the 16-bit descriptor code << 12 | count of bin (i, j) in ray order
 // [((i * blocks + b) * 64 + lane) * GQ + g], the list of bins with several classes or a count >= 4096 (as i << 16 | j), and
-// the two words of int_form_off (see ray_prep_kernel, tdr_score_ray.hip).
+// the two words of int_form_off (see score_prep_kernel, tdr_score_su.hip).
 __global__ __launch_bounds__(256) void cart_ray_prep_kernel(const float* __restrict__ scan_pk, int rows, int cols, int rf, int ncls,
                                                             int gq, int blocks, const uint32_t* __restrict__ dict_tail,
                                                             uint16_t* __restrict__ desc_ray, uint32_t* __restrict__ list,

@@ -92,7 +92,7 @@ __device__ __forceinline__ unsigned plane_offset(int ri, int ci, int pkcol, int 
   return (unsigned)off;
 }
 
-// The two device words that decide between the integer and the float form of a launch (ray_prep_kernel writes them):
+// The two device words that decide between the integer and the float form of a launch (score_prep_kernel writes them):
 // flags[0] != 0: a scan count or the dictionary has no integer form; flags[1]: an upper bound of (the scan's total count) /
 // 256 — below 2^24 the total stays below 2^32, the normalisation sums fit 32 bits and the class sums 64.
 __device__ __forceinline__ bool int_form_off(const int32_t* flags) {

@@ -30,7 +30,8 @@
 //   * a lane adds its products into its own 64-bit accumulators in LDS, one per class (ds_add_u64).
 // Bins that hold several classes, or a count beyond 12 bits, are "empty" to the loop and go through a list afterwards.
 //
-// Per launch: ray_prep_kernel (sample offsets and scan descriptors in ray order, the list, the `inexact` flag), then
+// Per launch: score_prep_kernel (tdr_score_su.hip: sample offsets and scan descriptors in ray order, the list, the `inexact`
+// flag — the same launch prepares the shift-uniform kernel's side), then
 // score_polar_ray_kernel over the sparse share of the slot list; score_finalize_exact_kernel (tdr_score.hip) turns the
 // integer sums into weights.
 #include "tdr_score_dev.h"
@@ -59,114 +60,11 @@
 //     what a wave has just fetched is the sector next to the one it fetches now.
 // Lane l = direction (l >> 4) of the step's four, ring (l & 15) of the block.  tdr_config_tuning("ray_patch", 0): the ray order
 // (A/B; same bits).
-#define RAY_PR 16             // rings of a patch
-#define RAY_PG 16             // scan rows of a unit (four steps of four directions)
-#define RAY_PATCH_MAX_NB 256
-static inline bool ray_bm(const SuLaunch& L) { return tdr_cfg().ray_block_major && L.fac != nullptr; }
-static inline bool ray_patch(const SuLaunch& L) { return ray_bm(L) && tdr_cfg().ray_patch && L.nb % RAY_PG == 0 && L.nb <= RAY_PATCH_MAX_NB; }
-static inline int ray_gq(int nr, bool bm) { return bm ? 1 : (nr <= 64 ? 1 : (nr <= 128 ? 2 : 4)); }
-static inline int ray_blocks(int nr, bool bm) { return (int)cdiv(nr, 64 * ray_gq(nr, bm)); }
 // (the first order pads to whole blocks of GQ steps: never less than the block-major order needs)
 int64_t tdr_ray_padded_samples(int nb, int nr) { return (int64_t)nb * ray_blocks(nr, false) * ray_gq(nr, false) * 64; }
 
-// One thread per (scan row, padded ring).  tab_ray[((i * blocks + b) * 64 + l) * GQ + g] = sample offset of (direction i,
-// ring j); desc_ray (16-bit) at the same index for scan row i, ring j: code << 12 | count — code 0: nothing for the loop
-// (an empty bin, or one that went on the list), c + 1: class c alone.  Rings beyond nr: an offset far outside the map (their
-// cell is the guard cell: unknown), descriptor 0.
-// `list`: bins holding several classes or a count >= 4096, as row << 16 | ring.
-// inexact[0] is raised when the scan has no integer form: a count that is negative, fractional, not finite or >= 2^24, or
-// a dictionary without one (tdr_cmap.hip); inexact[1] collects the bound on the total count (int_form_off).
-// fac (optional): the table's factors (tdr_polar_factors_host).  rad_ray[(b * 64 + l) * GQ + g] = ring j's radius (rings
-// beyond nr: 1e30 — one of a direction's two products then leaves the map whatever the direction); inexact[2] is raised
-// when an entry of `tab` is not the float product its factors give (with a uniform scale: that product, scaled like
-// utab_kernel scales the table) — the scoring kernel then reads tab_ray instead of multiplying the factors itself.
-__global__ __launch_bounds__(256) void ray_prep_kernel(const float* __restrict__ tab, const float* __restrict__ scan_pk, int nb,
-                                                       int nr, int rf, int ncls, int gq, int blocks,
-                                                       const uint32_t* __restrict__ dict_tail, float* __restrict__ tab_ray,
-                                                       uint16_t* __restrict__ desc_ray, uint32_t* __restrict__ list,
-                                                       int32_t* __restrict__ n_list, int32_t* __restrict__ inexact,
-                                                       const float* __restrict__ fac, float uscale, float res,
-                                                       float* __restrict__ rad_ray, int bm, int patch, int borrow) {
-  const int rpad = blocks * gq * 64;
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t == 0 && dict_tail[1] != 1u) atomicOr(inexact, 1);
-  const bool live = t < (int64_t)nb * rpad;
-  const int i = live ? (int)(t / rpad) : 0, j = live ? (int)(t - (int64_t)i * rpad) : 0;
-  const int64_t k = (int64_t)j * nb + i;
-  const bool real = live && j < nr;
-  uint32_t mass = 0;
-  if (real) {
-    const float sum = scan_pk[k * rf + rf - 1];
-    if (sum >= 1.f && sum < 16777216.f) mass = ((uint32_t)sum >> 8) + 1u;
-  }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) mass += __shfl_xor(mass, d, 64);
-  if ((threadIdx.x & 63) == 0 && mass) atomicAdd(reinterpret_cast<unsigned*>(inexact) + 1, mass);
-  if (!live) return;
-  const int g = j >> 6, l = j & 63, b = g / gq;
-  const int64_t at = bm ? ((int64_t)b * nb + i) * 64 + l : (((int64_t)i * blocks + b) * 64 + l) * gq + (g - b * gq);
-  // patch order (descriptors only; the offsets keep the block-major order): unit (ring block j / 16, scan-row group i / 16),
-  // lane (i & 3) * 16 + (j & 15), step (i & 15) >> 2 — a lane's four steps side by side
-  int64_t at_d = at;
-  if (patch) at_d = ((((int64_t)(j / RAY_PR) * (nb / RAY_PG) + i / RAY_PG) * 64 + (i & 3) * RAY_PR + (j % RAY_PR)) << 2) + ((i % RAY_PG) >> 2);
-  float tx = -1.0e30f, ty = -1.0e30f;
-  uint32_t d = 0;
-  if (fac && i == 0) rad_ray[((int64_t)b * 64 + l) * gq + (g - b * gq)] = real ? fac[2 * nb + j] : 1.0e30f;
-  if (real) {
-    tx = tab[2 * k];
-    ty = tab[2 * k + 1];
-    if (fac) {
-      float fx = fac[2 * i] * fac[2 * nb + j], fy = fac[2 * i + 1] * fac[2 * nb + j];
-      if (uscale > 0.f) {
-        fx = (fx * uscale) * res;
-        fy = (fy * uscale) * res;
-      }
-      if (__float_as_uint(fx) != __float_as_uint(tx) || __float_as_uint(fy) != __float_as_uint(ty)) atomicOr(inexact + 2, 1);
-    }
-    const float* r = scan_pk + k * rf;
-    int nz = 0, first = 0;
-    bool ok = true;
-    for (int c = 0; c < ncls; c++) {
-      const float v = r[c];
-      ok &= v >= 0.f && v < 16777216.f && v == floorf(v);
-      if (v != 0.f) {
-        if (!nz) first = c;
-        nz++;
-      }
-    }
-    const float sum = r[rf - 1];
-    ok &= sum >= 0.f && sum < 16777216.f && sum == floorf(sum);
-    if (!ok) atomicOr(inexact, 1);
-    else if (nz == 1 && r[first] < 4096.f) d = (uint32_t)r[first] | ((uint32_t)(first + 1) << 12);
-    else if (nz >= 1) list[atomicAdd(n_list, 1)] = ((uint32_t)i << 16) | (uint32_t)j;   // (any order: the sums are exact)
-  }
-  // An EMPTY bin (and one that went on the list) needs its cell's known bit and nothing else — and every class plane carries that
-  // bit (bit 15 of a cell).  Four consecutive lanes of a gather — four consecutive rings of one scan row, in every order above —
-  // are served together by the L1's address path, at a cost per distinct LINE among them: an empty bin between two bins of
-  // class c that reads the coarse mask plane is a line of its own, one that reads class c's plane with a count of zero rides
-  // along.  So an empty bin borrows the class of the nearest non-empty bin of its aligned group of four rings (none: code 0,
-  // the mask plane, one line for the four); the product with a zero count adds nothing (round 5).
-  {
-    const uint32_t own = d >> 12;
-    const int ql = threadIdx.x & 3;
-    uint32_t c4[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) c4[q] = __shfl(own, (threadIdx.x & 60) + q, 64);   // (threads of a group: the same scan row i, rings 4 q' .. 4 q' + 3)
-    if (borrow && own == 0) {
-      uint32_t pick = 0;
-#pragma unroll
-      for (int dist = 3; dist >= 1; dist--) {   // the nearest wins (written last)
-        if (ql + dist < 4 && c4[(ql + dist) & 3]) pick = c4[(ql + dist) & 3];
-        if (ql - dist >= 0 && c4[(ql - dist) & 3]) pick = c4[(ql - dist) & 3];
-      }
-      d = pick << 12;
-    }
-  }
-  tab_ray[2 * at] = tx;
-  tab_ray[2 * at + 1] = ty;
-  desc_ray[at_d] = (uint16_t)d;
-}
-
+// The layouts — tab_ray, rad_ray, desc_ray, the list, the `inexact` words — are written by score_prep_kernel
+// (tdr_score_su.hip), which describes them.
 struct RayArgs {
   const uint32_t* crec;     // compact map: tiles, known mask, class planes, coarse mask plane (byte offsets from here)
   unsigned planes_off;      // byte offset of class plane 0
@@ -200,7 +98,7 @@ struct RayArgs {
 
 // FAC: the sample offsets are multiplied out of the table's factors — a direction's pair (uniform over the wave: two scalar
 // loads) times the lane's own radii (registers) — instead of read from tab_ray: the same float products the table holds
-// (ray_prep_kernel checked that), and 16 bytes per lane and row less through the texture path.
+// (score_prep_kernel checked that), and 16 bytes per lane and row less through the texture path.
 // lacc [4 waves][ncls + 1][64 lanes]: a lane's sums per class (slot 0: no class); lut, per class code: {plane constant,
 // column shift, known-bit index, accumulator}
 // PATCH (with BM): the patch order (see the top of the file); ldir: the directions' pairs in LDS
@@ -479,7 +377,7 @@ __global__ __launch_bounds__(256) void score_polar_ray_kernel(RayArgs a) {
   if ((int64_t)blockIdx.x * 4 >= (int64_t)a.counts[1] * a.nsplit) return;   // no stamps for an idle workgroup (ray_body's own test)
 #endif
   TDR_TL_BEGIN(g_timeline_ray)
-  // with factors that ARE the table's (ray_prep_kernel's check; uniform over the launch) the offsets are multiplied out
+  // with factors that ARE the table's (score_prep_kernel's check; uniform over the launch) the offsets are multiplied out
   if (a.fac && a.inexact[2] == 0) ray_body<GQ, USCALE, true, BM, PATCH>(a, lacc, ldict, lut, ldir);
   else ray_body<GQ, USCALE, false, BM, PATCH>(a, lacc, ldict, lut, ldir);
   TDR_TL_END(g_timeline_ray)   // (ray_body's waves return from IT: every thread of a live workgroup arrives here)
@@ -507,22 +405,6 @@ int tdr_ray_splits(int nb, int nr, int64_t n, bool bm) {
   if (s == 2 && bm && rows >= 512) s = 4;
   if (s == 2 && !bm && rows >= 256) s = 8;
   return s;
-}
-
-int tdr_ray_prepare(const SuLaunch& L, const SuWs& W, hipStream_t s) {
-  int32_t* base = L.ws;
-  int* ints = base + W.ints + 3 * (L.nb + 1);   // [counts 3][n_list][inexact][mass bound]
-  const bool bm = ray_bm(L);
-  const int gq = ray_gq(L.nr, bm), blocks = ray_blocks(L.nr, bm);
-  const int64_t T = tdr_ray_padded_samples(L.nb, L.nr);
-  hipLaunchKernelGGL(ray_prep_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, s, L.tab, L.scan_pk, L.nb, L.nr, L.rf,
-                     L.map->ncls, gq, blocks, reinterpret_cast<const uint32_t*>(L.map->dict) + 2 * TDR_CMAP_MAX_DICT,
-                     reinterpret_cast<float*>(base + W.ray_tab), reinterpret_cast<uint16_t*>(base + W.ray_desc),
-                     reinterpret_cast<uint32_t*>(base + W.ray_multi), ints + 3, ints + 4, L.fac,
-                     L.uniform_scale ? L.uscale : 0.f, L.res, reinterpret_cast<float*>(base + W.ray_rad), bm ? 1 : 0,
-                     ray_patch(L) ? 1 : 0, tdr_cfg().ray_borrow ? 1 : 0);
-  LAUNCH_CHECK("ray_prep");
-  return TDR_OK;
 }
 
 int tdr_ray_score(const SuLaunch& L, const SuWs& W, hipStream_t s) {

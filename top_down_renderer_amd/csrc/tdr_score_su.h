@@ -50,6 +50,8 @@ struct SuLaunch {
   const tdr_map_desc* map;   // with a narrow compact form
   const float* tab;          // [P][2]: (tab*scale)*res when uniform_scale, else the table itself
   bool uniform_scale;
+  const float* tab_src = nullptr;   // the caller's table itself: what the preparation reads (score_prep_kernel) ...
+  float* utab_out = nullptr;        // ... and, with a uniform scale, where it writes (tab*scale)*res — `tab` above, filled by it
   const float* scan_pk;
   int nb, nr, rf;
   float res;
@@ -67,12 +69,21 @@ struct SuLaunch {
   int32_t* ws;               // tdr_su_ws(...).total words
   float span;                // map cells the 64 locality neighbours of a dense particle may span (tdr_su_span_begin)
 };
-// ordering passes + descriptors (everything but the scoring kernels).  slots_out: the slot list — the dense particles
-// by heading bin, every bin padded to whole waves (-1), then the sparse particles in the caller's order (su_key_kernel);
-// counts_out: device words {slots of the heading bins, sparse particles behind them, both together (what finalize walks)}
+// ordering passes + the scan-side preparation (everything but the scoring kernels).  slots_out: the slot list — the dense
+// particles by heading bin, every bin padded to whole waves (-1), then the sparse particles in the caller's order
+// (su_key_kernel); counts_out: device words {slots of the heading bins, sparse particles behind them, both together (what
+// finalize walks)}.  The preparation is ONE kernel (score_prep_kernel, tdr_score_su.hip) for both scoring kernels: the
+// uniform-scale table, the shift-uniform layout (offsets, descriptors, bounding boxes) and the ray-mapped layouts (offsets,
+// radii, 16-bit descriptors, the list, the `inexact` words, the mass bound).
 int tdr_su_prepare(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_t** slots_out, const int32_t** counts_out);
-// the ordering passes alone (L.st, cap, n, perm, nb, span, ws; nb == 1: no heading bins — the Cartesian score)
-int tdr_su_order(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_t** slots_out, const int32_t** counts_out);
+// the ordering passes alone (L.st, cap, n, perm, nb, span, ws; nb == 1: no heading bins — the Cartesian score).  box_init
+// (optional): box_count boxes {min, max, min, max} that su_offsets_kernel sets to {+FLT_MAX, -FLT_MAX, ...} for the
+// preparation to lower / raise.
+int tdr_su_order(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_t** slots_out, const int32_t** counts_out,
+                 float* box_init = nullptr, int box_count = 0);
+// tests (tdr_k_score_prep): the preparation's products out of L.ws — out[0..8] = utab, tab_su, desc, bbox, tab_ray, desc_ray,
+// rad_ray, list, the words behind the counts (device memory, NULL: not wanted) — and the shapes behind their sizes
+int tdr_su_prep_copy_out(const SuLaunch& L, const SuWs& W, hipStream_t s, int64_t layout[16], void* const out[9]);
 // The span for this launch.  With a fixed span (tdr_config_shift_uniform_span, TDR_SU_SPAN) that one; otherwise it is tuned
 // while the filter runs: a few candidates are timed over one launch each (events on `s` around the whole scoring call,
 // tdr_su_span_end closes the measurement), the fastest is kept, and the trial is repeated every few thousand launches
@@ -100,6 +111,14 @@ int tdr_su_score(const SuLaunch& L, const SuWs& W, hipStream_t s);
 bool tdr_ray_map_ok(const tdr_map_desc* map);
 int64_t tdr_ray_padded_samples(int nb, int nr);   // window samples with every direction padded to whole blocks of steps
 int tdr_ray_splits(int nb, int nr, int64_t n, bool block_major = false);
-int tdr_ray_prepare(const SuLaunch& L, const SuWs& W, hipStream_t s);
+// The ray-mapped kernel's layouts of a launch (tdr_score_ray.hip has the description): gq steps of 64 rings per block,
+// `blocks` blocks per direction; block-major / patch order.  The preparation (tdr_score_su.hip) writes them.
+#define RAY_PR 16             // rings of a patch
+#define RAY_PG 16             // scan rows of a unit (four steps of four directions)
+#define RAY_PATCH_MAX_NB 256
+static inline bool ray_bm(const SuLaunch& L) { return tdr_cfg().ray_block_major && L.fac != nullptr; }
+static inline bool ray_patch(const SuLaunch& L) { return ray_bm(L) && tdr_cfg().ray_patch && L.nb % RAY_PG == 0 && L.nb <= RAY_PATCH_MAX_NB; }
+static inline int ray_gq(int nr, bool bm) { return bm ? 1 : (nr <= 64 ? 1 : (nr <= 128 ? 2 : 4)); }
+static inline int ray_blocks(int nr, bool bm) { return (int)cdiv(nr, 64 * ray_gq(nr, bm)); }
 int tdr_ray_score(const SuLaunch& L, const SuWs& W, hipStream_t s);
 #endif  // TDR_SCORE_SU_H_

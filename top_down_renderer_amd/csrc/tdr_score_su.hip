@@ -29,9 +29,11 @@
 //                      order, i.e. a stable sort by bin, in one pass
 //   (where the table would be out of proportion — the rule at su_seg_table_words — and under tdr_config_tuning(
 //    "su_order_bucket", 0): two fills, su_key_kernel, su_offsets_kernel, rocPRIM's stable radix sort by bin, su_scatter_kernel)
-//   su_prep_kernel     per (direction, ring): sample offset and scan descriptor, group-major (a wave streams them in order)
-//   su_bbox_kernel     bounding box of the sample offsets of every (ring group, sector of directions)
-//   score_polar_su_kernel, then score_finalize_kernel over the slots
+//   score_prep_kernel  the scan side, for this kernel and for the ray-mapped one (tdr_score_ray.hip), one thread per
+//                      (direction, ring): the uniform-scale table; sample offset and scan descriptor, group-major (a wave
+//                      streams them in order); the bounding box of the sample offsets of every (ring group, sector of
+//                      directions), on the words su_offsets_kernel initialised; the ray-mapped layouts and the `inexact` words
+//   score_polar_ray_kernel, score_polar_su_kernel, then score_finalize_exact_kernel over the slots (tdr_score.hip)
 //
 // Compiled with -mllvm -structurizecfg-skip-uniform-regions (build.py): the per-sample dispatch on the descriptor is a
 // tree of wave-uniform branches; left to the structuriser each leaf is followed by copies of all accumulators (phi
@@ -70,7 +72,7 @@ struct SuArgs {
   int rows, cols;          // map
   float resolution;
   const float* tab_su;     // [nchunks][nb][group][2]: (tab*scale)*res (USCALE) or tab
-  const uint32_t* desc;    // [nchunks][nb][group][4]: scan descriptor of bin (row, ring), see su_prep_kernel
+  const uint32_t* desc;    // [nchunks][nb][group][4]: scan descriptor of bin (row, ring), see score_prep_kernel
   const float* bbox;       // [nchunks][SU_NSECT][4]: min / max of tab_su's two coordinates over the sector
   const float* scan_pk;    // [nr][nb][rf]: read for bins holding several classes
   int nb, nr;
@@ -86,7 +88,23 @@ struct SuArgs {
   uint32_t* stats;         // NULL, or (profiling) counters of the variants the wave-sectors ran: tdr_profile_variants
 };
 
-// Scan descriptor of a bin, four dwords:
+// The scan-side preparation of an integer-form launch: ONE kernel, one thread per (scan row / direction i, padded ring j), j
+// fastest in a wave; a workgroup is PREP_DIRS neighbouring directions over the same 64 rings.  rp, the padded ring count, is a multiple of 64 that covers the shift-uniform layout (nchunks x group rings) and the
+// ray-mapped one (blocks x gq x 64): a wave is 64 consecutive rings of ONE direction, four consecutive lanes are an aligned
+// group of four rings — what the shuffles below lean on.  A thread reads its table entry and its bin's scan record once and
+// writes, for both scoring kernels:
+//   utab (with a uniform scale)  (tab * scale) * res in the table's own order, two roundings (top_down_map_polar.cpp:28): the
+//                       float form behind the integer kernels and the ray-mapped kernel's list pass read it
+//   tab_su, desc        the shift-uniform layout [nchunks][nb][group]: sample offset and the four-dword scan descriptor
+//   bbox                bounding box of the sample offsets of every (ring group, sector of directions): a wave reduces the rings
+//                       of each group it holds, the workgroup's waves of one sector meet in LDS, then one atomic min / max
+//                       per workgroup, group, sector and box word, on the words su_offsets_kernel initialised ({+FLT_MAX,
+//                       -FLT_MAX, ...}; float minima / maxima: any order)
+//   tab_ray, rad_ray, desc_ray, list, n_list, inexact[0..2], the mass bound     the ray-mapped kernel's layouts and the
+//                       words that decide between the integer and the float form (tdr_score_ray.hip has the layouts)
+// Nothing is kept between calls: the table may change under the same pointer.
+//
+// Scan descriptor of a bin (shift-uniform layout), four dwords:
 //   [0] code: 0 = every class zero; c + 1 = class c alone is non-zero; SU_CODE_FULL = several classes;
 //       SU_CODE_FULL_ALL = a non-finite dictionary / scan value: no skipping in this bin
 //   [1] the bin's count summed over the classes, as an integer — for a single class: its count
@@ -97,90 +115,232 @@ struct SuArgs {
 //   [3] bit 31, on the first bin of a step (4 consecutive rings) only: one of the step's bins is SU_CODE_FULL / SU_CODE_FULL_ALL
 //   (the steps that read RECORDS — the C++ steps, for bins with several classes and their neighbours, and the far path —
 //    work the record constants of a single class out of its code: su_rec_const / single_class)
-__global__ __launch_bounds__(256) void su_prep_kernel(const float* __restrict__ tab, const float* __restrict__ scan_pk,
-                                                      int nb, int nr, int rf, int ncls, int ckconst, unsigned pbase,
-                                                      unsigned plane_bytes, int group, int nchunks,
-                                                      const float* __restrict__ dict, int dict_n, float* __restrict__ tab_su,
-                                                      uint32_t* __restrict__ desc) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// A ring the image does not have (j >= nr) inside the last group: SU_CODE_PAD and the offset of the direction's last real ring
+// (inside every box the real ones span); it stays out of the box.
+//
+// Ray-mapped layouts.  tab_ray[((i * blocks + b) * 64 + l) * GQ + g] = sample offset of (direction i, ring j); desc_ray
+// (16-bit) at the same index for scan row i, ring j: code << 12 | count — code 0: nothing for the loop (an empty bin, or one
+// that went on the list), c + 1: class c alone.  Rings beyond nr: an offset far outside the map (their cell is the guard
+// cell: unknown), descriptor 0.  `list`: bins holding several classes or a count >= 4096, as row << 16 | ring (any order:
+// the sums are exact).  inexact[0] is raised when the scan has no integer form: a count that is negative, fractional, not
+// finite or >= 2^24, or a dictionary without one (tdr_cmap.hip); inexact[1] collects the bound on the total count
+// (int_form_off).  fac (optional): the table's factors (tdr_polar_factors_host).  rad_ray[(b * 64 + l) * GQ + g] = ring j's
+// radius (rings beyond nr: 1e30 — one of a direction's two products then leaves the map whatever the direction); inexact[2]
+// is raised when an entry of the table is not the float product its factors give (with a uniform scale: that product, scaled
+// the same way) — the scoring kernel then reads tab_ray instead of multiplying the factors itself.
+struct PrepArgs {
+  const float* tab;        // the caller's table [nr][nb][2]
+  const float* scan_pk;    // [nr][nb][rf]
+  int nb, nr, rf, ncls, rp;
+  float uscale, res;       // uscale > 0: a uniform scale
+  float* utab;             // NULL without a uniform scale
+  // shift-uniform layout
+  int group, nchunks, ckconst;
+  unsigned pbase, plane_bytes;
+  const float* dict;
+  int dict_n;
+  float* tab_su;
+  uint32_t* desc;
+  float* bbox;
+  // ray-mapped layouts
+  int gq, blocks, bm, patch, borrow;
+  const uint32_t* dict_tail;
+  const float* fac;
+  float* tab_ray;
+  float* rad_ray;
+  uint16_t* desc_ray;
+  uint32_t* list;
+  int32_t* n_list;
+  int32_t* inexact;
+};
+// float minimum / maximum on a word that holds a float: the sign decides which integer order is the float order (a NaN is left
+// out, as fminf / fmaxf leave it out)
+__device__ __forceinline__ void atomic_min_float(float* at, float v) {
+  if (!(v == v)) return;
+  if (__float_as_int(v) >= 0) atomicMin(reinterpret_cast<int*>(at), __float_as_int(v));
+  else atomicMax(reinterpret_cast<unsigned*>(at), __float_as_uint(v));
+}
+__device__ __forceinline__ void atomic_max_float(float* at, float v) {
+  if (!(v == v)) return;
+  if (__float_as_int(v) >= 0) atomicMax(reinterpret_cast<int*>(at), __float_as_int(v));
+  else atomicMin(reinterpret_cast<unsigned*>(at), __float_as_uint(v));
+}
+#define PREP_DIRS 8   // directions of a workgroup: a wave each
+__device__ __forceinline__ void score_prep_body(const PrepArgs& a, const unsigned block) {
+  const int nb = a.nb, nr = a.nr, rf = a.rf, rp = a.rp;
+  __shared__ float red[PREP_DIRS][64][4];   // the waves' box candidates
+  __shared__ unsigned wg_mass, wg_listed, wg_list_base;
+  if (threadIdx.x == 0) { wg_mass = 0; wg_listed = 0; }
   bool bad = false;   // the dictionary is small: every workgroup checks it for itself
-  for (int k = threadIdx.x; k < dict_n; k += blockDim.x) bad |= !(fabsf(dict[k]) <= 3.402823466e+38f);
-  const bool dict_bad = __syncthreads_or(bad);
-  const int64_t total = (int64_t)nchunks * nb * group;
-  const bool live = t < total;
-  const int64_t tt = live ? t : 0;
-  const int jj = (int)(tt % group);
-  const int64_t q = tt / group;
-  const int i = (int)(q % nb), chunk = (int)(q / nb);
-  const int j = chunk * group + jj;
-  float tx = 0.f, ty = 0.f, val = 0.f;
-  uint32_t code = SU_CODE_PAD, ckc = (uint32_t)ckconst, sh = 0;
-  if (live && j >= nr) {   // no such ring: the offset of the direction's last real one (inside every box the real ones span)
-    const int64_t k = (int64_t)(nr - 1) * nb + i;
-    tx = tab[2 * k];
-    ty = tab[2 * k + 1];
+  for (int k = threadIdx.x; k < a.dict_n; k += blockDim.x) bad |= !(fabsf(a.dict[k]) <= 3.402823466e+38f);
+  const bool dict_bad = __syncthreads_or(bad);   // (also: the three words above are set)
+  if (block == 0 && threadIdx.x == 0 && a.dict_tail[1] != 1u) atomicOr(a.inexact, 1);
+  // a workgroup: PREP_DIRS neighbouring directions (a wave each) x the same 64 rings — neighbouring directions share the lines
+  // of the table and of the scan, and their boxes, the list and the mass bound meet in LDS: the words that many workgroups add
+  // to get one atomic per workgroup, not one per wave or bin (same-line atomics are what this kernel's time was)
+  const int segs = rp >> 6, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i_raw = (int)(block / segs) * PREP_DIRS + wave, j = (int)(block % segs) * 64 + lane;
+  const bool live = i_raw < nb;   // (a whole wave)
+  const int i = live ? i_raw : nb - 1;
+  const bool real = live && j < nr;
+  const int64_t k = (int64_t)(j < nr ? j : nr - 1) * nb + i;   // (no such ring: the direction's last real one)
+  // (one request per table entry, two or three per record: a wave's 64 rings of one direction lie nb entries apart, every
+  // load touches 64 lines)
+  const float2 te = *reinterpret_cast<const float2*>(a.tab + 2 * k);
+  float tx = te.x, ty = te.y;
+  if (a.utab) {
+    tx = (tx * a.uscale) * a.res;   // `ang_sample_pts_*scale*res` (top_down_map_polar.cpp:28)
+    ty = (ty * a.uscale) * a.res;
+    if (real) *reinterpret_cast<float2*>(a.utab + 2 * k) = make_float2(tx, ty);
   }
-  if (live && j < nr) {
-    code = 0;
-    const int64_t k = (int64_t)j * nb + i;
-    tx = tab[2 * k];
-    ty = tab[2 * k + 1];
-    const float* r = scan_pk + k * rf;
-    int nz = 0, first = 0;
-    bool finite = true;
-    for (int c = 0; c < ncls; c++) {
-      finite &= fabsf(r[c]) <= 3.402823466e+38f;
-      if (r[c] != 0.f) {
-        if (!nz) first = c;
-        nz++;
+  // the bin's record, once (rf is 4, 8 or 12: tdr_su_prepare)
+  float rec[12];
+#pragma unroll
+  for (int q = 0; q < 3; q++) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (real && 4 * q < rf) v = reinterpret_cast<const float4*>(a.scan_pk + k * rf)[q];
+    rec[4 * q] = v.x; rec[4 * q + 1] = v.y; rec[4 * q + 2] = v.z; rec[4 * q + 3] = v.w;
+  }
+  int nz = 0, first = 0;
+  bool finite = true, whole = true;
+  float vfirst = 0.f, sum = 0.f;
+  if (real) {
+#pragma unroll
+    for (int c = 0; c < 11; c++)
+      if (c < a.ncls) {
+        const float v = rec[c];
+        finite &= fabsf(v) <= 3.402823466e+38f;
+        whole &= v >= 0.f && v < 16777216.f && v == floorf(v);
+        if (v != 0.f) {
+          if (!nz) { first = c; vfirst = v; }
+          nz++;
+        }
       }
-    }
-    // (a non-finite or fractional count: the launch runs in its float form instead — ray_prep_kernel raises `inexact`)
-    if (dict_bad || !finite) { code = SU_CODE_FULL_ALL; val = r[rf - 1]; }
-    else if (nz == 1) { code = (uint32_t)first + 1u; val = r[first]; ckc = pbase + (uint32_t)first * plane_bytes; }
-    else if (nz > 1) { code = SU_CODE_FULL; val = r[rf - 1]; }
+    sum = rf == 4 ? rec[3] : (rf == 8 ? rec[7] : rec[11]);
+    whole &= sum >= 0.f && sum < 16777216.f && sum == floorf(sum);
+  }
+  // ---- the mass bound: a wave's sum
+  uint32_t mass = 0;
+  if (real && sum >= 1.f && sum < 16777216.f) mass = ((uint32_t)sum >> 8) + 1u;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) mass += __shfl_xor(mass, d, 64);
+  if (lane == 0 && mass) atomicAdd(&wg_mass, mass);
+  // ---- the shift-uniform layout
+  const int group = a.group;
+  const bool su_live = live && j < a.nchunks * group;
+  const int chunk = j / group, jj = j - chunk * group;
+  uint32_t code = SU_CODE_PAD, ckc = (uint32_t)a.ckconst;
+  float val = 0.f;
+  if (real) {
+    code = 0;
+    // (a non-finite or fractional count: the launch runs in its float form instead — `inexact` below)
+    if (dict_bad || !finite) { code = SU_CODE_FULL_ALL; val = sum; }
+    else if (nz == 1) { code = (uint32_t)first + 1u; val = vfirst; ckc = a.pbase + (uint32_t)first * a.plane_bytes; }
+    else if (nz > 1) { code = SU_CODE_FULL; val = sum; }
   }
   // steps are 4 consecutive bins (group is a multiple of 4, so they are 4 consecutive threads of a wave)
   uint32_t anyfull = code >= SU_CODE_FULL_ALL ? 1u : 0u;
   anyfull |= __shfl_xor(anyfull, 1);
   anyfull |= __shfl_xor(anyfull, 2);
-  if (!live) return;
-  tab_su[2 * t] = tx;
-  tab_su[2 * t + 1] = ty;
-  desc[4 * t] = code;
-  desc[4 * t + 1] = (uint32_t)val;
-  desc[4 * t + 2] = ckc;
-  desc[4 * t + 3] = sh | (((jj & 3) == 0 && anyfull) ? 0x80000000u : 0u);
-}
-
-// bounding box of the sample offsets of ring group blockIdx.x, sector blockIdx.y (directions [sect nb / NSECT, ...))
-__global__ __launch_bounds__(256) void su_bbox_kernel(const float* __restrict__ tab_su, int nb, int nr, int group,
-                                                      float* __restrict__ bbox) {
-  const int chunk = blockIdx.x, sect = blockIdx.y;
-  const int i0 = (int)((int64_t)sect * nb / SU_NSECT), i1 = (int)((int64_t)(sect + 1) * nb / SU_NSECT);
-  const int gn = min(nr - chunk * group, group);
-  float lo0 = 3.402823466e+38f, hi0 = -3.402823466e+38f, lo1 = lo0, hi1 = hi0;
-  const int cnt = (i1 - i0) * gn;
-  for (int t = threadIdx.x; t < cnt; t += 256) {
-    const int i = i0 + t / gn, jj = t % gn;
-    const float* e = tab_su + (((int64_t)chunk * nb + i) * group + jj) * 2;
-    lo0 = fminf(lo0, e[0]); hi0 = fmaxf(hi0, e[0]);
-    lo1 = fminf(lo1, e[1]); hi1 = fmaxf(hi1, e[1]);
+  if (su_live) {
+    const int64_t at = ((int64_t)chunk * nb + i) * group + jj;
+    *reinterpret_cast<float2*>(a.tab_su + 2 * at) = make_float2(tx, ty);
+    *reinterpret_cast<uint4*>(a.desc + 4 * at) = make_uint4(code, (uint32_t)val, ckc, ((jj & 3) == 0 && anyfull) ? 0x80000000u : 0u);
   }
-  __shared__ float red[4][256];
-  red[0][threadIdx.x] = lo0; red[1][threadIdx.x] = hi0; red[2][threadIdx.x] = lo1; red[3][threadIdx.x] = hi1;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) {
-      red[0][threadIdx.x] = fminf(red[0][threadIdx.x], red[0][threadIdx.x + d]);
-      red[1][threadIdx.x] = fmaxf(red[1][threadIdx.x], red[1][threadIdx.x + d]);
-      red[2][threadIdx.x] = fminf(red[2][threadIdx.x], red[2][threadIdx.x + d]);
-      red[3][threadIdx.x] = fmaxf(red[3][threadIdx.x], red[3][threadIdx.x + d]);
+  // the boxes: the real rings of a group that this wave holds are consecutive lanes — a segmented reduction towards the
+  // segment's first lane (minima and maxima: a lane may meet an operand twice); the waves' candidates meet in LDS below
+  // the sector s with s nb / SU_NSECT <= dir < (s + 1) nb / SU_NSECT
+  auto sector = [&](int dir) { return (int)((SU_NSECT * ((int64_t)dir + 1) - 1) / nb); };
+  {
+    const float big = 3.402823466e+38f;
+    float lo0 = real ? tx : big, hi0 = real ? tx : -big, lo1 = real ? ty : big, hi1 = real ? ty : -big;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const float o0 = __shfl_down(lo0, d, 64), o1 = __shfl_down(hi0, d, 64), o2 = __shfl_down(lo1, d, 64), o3 = __shfl_down(hi1, d, 64);
+      const int oc = __shfl_down(chunk, d, 64);
+      if (lane + d < 64 && oc == chunk) {
+        lo0 = fminf(lo0, o0); hi0 = fmaxf(hi0, o1);
+        lo1 = fminf(lo1, o2); hi1 = fmaxf(hi1, o3);
+      }
     }
-    __syncthreads();
+    red[wave][lane][0] = lo0; red[wave][lane][1] = hi0; red[wave][lane][2] = lo1; red[wave][lane][3] = hi1;
   }
-  if (threadIdx.x < 4) bbox[((int64_t)chunk * SU_NSECT + sect) * 4 + threadIdx.x] = red[threadIdx.x][0];
+  // ---- the ray-mapped layouts
+  const bool ray_live = live && j < a.blocks * a.gq * 64;
+  uint32_t d = 0;
+  bool listed = false;
+  unsigned list_rank = 0;
+  if (real) {
+    if (a.fac) {
+      float fx = a.fac[2 * i] * a.fac[2 * nb + j], fy = a.fac[2 * i + 1] * a.fac[2 * nb + j];
+      if (a.uscale > 0.f) {
+        fx = (fx * a.uscale) * a.res;
+        fy = (fy * a.uscale) * a.res;
+      }
+      if (__float_as_uint(fx) != __float_as_uint(tx) || __float_as_uint(fy) != __float_as_uint(ty)) atomicOr(a.inexact + 2, 1);
+    }
+    if (!whole) atomicOr(a.inexact, 1);
+    else if (nz == 1 && vfirst < 4096.f) d = (uint32_t)vfirst | ((uint32_t)(first + 1) << 12);
+    else if (nz >= 1) { listed = true; list_rank = atomicAdd(&wg_listed, 1u); }
+  }
+  // An EMPTY bin (and one that went on the list) needs its cell's known bit and nothing else — and every class plane carries that
+  // bit (bit 15 of a cell).  Four consecutive lanes of a gather — four consecutive rings of one scan row, in every order —
+  // are served together by the L1's address path, at a cost per distinct LINE among them: an empty bin between two bins of
+  // class c that reads the coarse mask plane is a line of its own, one that reads class c's plane with a count of zero rides
+  // along.  So an empty bin borrows the class of the nearest non-empty bin of its aligned group of four rings (none: code 0,
+  // the mask plane, one line for the four); the product with a zero count adds nothing (round 5).
+  {
+    const uint32_t own = d >> 12;
+    const int ql = lane & 3;
+    uint32_t c4[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) c4[q] = __shfl(own, (lane & 60) + q, 64);   // (threads of a group: the same scan row i, rings 4 q' .. 4 q' + 3)
+    if (a.borrow && own == 0) {
+      uint32_t pick = 0;
+#pragma unroll
+      for (int dist = 3; dist >= 1; dist--) {   // the nearest wins (written last)
+        if (ql + dist < 4 && c4[(ql + dist) & 3]) pick = c4[(ql + dist) & 3];
+        if (ql - dist >= 0 && c4[(ql - dist) & 3]) pick = c4[(ql - dist) & 3];
+      }
+      d = pick << 12;
+    }
+  }
+  // ---- what the workgroup adds to the launch's words: one atomic each
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (wg_mass) atomicAdd(reinterpret_cast<unsigned*>(a.inexact) + 1, wg_mass);
+    wg_list_base = wg_listed ? (unsigned)atomicAdd(a.n_list, (int)wg_listed) : 0u;
+  }
+  // the box of (ring group, sector): the first of the workgroup's directions in the sector gathers the others'
+  if (real && (lane == 0 || jj == 0)) {
+    const int sect = sector(i);
+    if (wave == 0 || sector(i - 1) != sect) {
+      float lo0 = red[wave][lane][0], hi0 = red[wave][lane][1], lo1 = red[wave][lane][2], hi1 = red[wave][lane][3];
+      for (int w = wave + 1; w < PREP_DIRS && i + (w - wave) < nb && sector(i + (w - wave)) == sect; w++) {
+        lo0 = fminf(lo0, red[w][lane][0]); hi0 = fmaxf(hi0, red[w][lane][1]);
+        lo1 = fminf(lo1, red[w][lane][2]); hi1 = fmaxf(hi1, red[w][lane][3]);
+      }
+      float* box = a.bbox + ((int64_t)chunk * SU_NSECT + sect) * 4;
+      atomic_min_float(box, lo0);
+      atomic_max_float(box + 1, hi0);
+      atomic_min_float(box + 2, lo1);
+      atomic_max_float(box + 3, hi1);
+    }
+  }
+  __syncthreads();
+  if (listed) a.list[wg_list_base + list_rank] = ((uint32_t)i << 16) | (uint32_t)j;   // (any order: the sums are exact)
+  if (!ray_live) return;
+  const int g = j >> 6, l = j & 63, b = g / a.gq, gq = a.gq;
+  const int64_t at = a.bm ? ((int64_t)b * nb + i) * 64 + l : (((int64_t)i * a.blocks + b) * 64 + l) * gq + (g - b * gq);
+  // patch order (descriptors only; the offsets keep the block-major order): unit (ring block j / 16, scan-row group i / 16),
+  // lane (i & 3) * 16 + (j & 15), step (i & 15) >> 2 — a lane's four steps side by side
+  int64_t at_d = at;
+  if (a.patch) at_d = ((((int64_t)(j / RAY_PR) * (nb / RAY_PG) + i / RAY_PG) * 64 + (i & 3) * RAY_PR + (j % RAY_PR)) << 2) + ((i % RAY_PG) >> 2);
+  if (a.fac && i == 0) a.rad_ray[((int64_t)b * 64 + l) * gq + (g - b * gq)] = real ? a.fac[2 * nb + j] : 1.0e30f;
+  *reinterpret_cast<float2*>(a.tab_ray + 2 * at) = real ? make_float2(tx, ty) : make_float2(-1.0e30f, -1.0e30f);
+  a.desc_ray[at_d] = (uint16_t)d;
 }
+__global__ __launch_bounds__(64 * PREP_DIRS) void score_prep_kernel(PrepArgs a) { score_prep_body(a, blockIdx.x); }
 
 // Sort key of every particle (in the caller's locality order): its heading bin when its neighbourhood is DENSE, nb when
 // it is SPARSE — the 64 particles around it in the locality (Morton) order are more than `span` map cells apart.  A
@@ -284,10 +444,13 @@ __global__ __launch_bounds__(64 * SU_COLSCAN_WAVES) void su_colscan_kernel(int* 
 // counts = {slots of the heading bins (a multiple of 64), sparse particles behind them, both together}
 // The bucket sort (pad_slots set) has no filled slot list and no zeroed words to start from: the up to 63 padding slots of a
 // heading bin get their -1 here, and the words behind counts (TDR_SU_TAIL_INTS, which later kernels add to) their zero.
+// box_init (either path, optional): box_count boxes of {min, max, min, max} get the values score_prep_kernel lowers / raises.
 __global__ __launch_bounds__(256) void su_offsets_kernel(const int* __restrict__ cnt, int nkeys, int* __restrict__ start,
                                                          int* __restrict__ slot_start, int* __restrict__ counts,
-                                                         int32_t* __restrict__ pad_slots) {
+                                                         int32_t* __restrict__ pad_slots, float* __restrict__ box_init,
+                                                         int box_count) {
   __shared__ int sa[256], sb[256];
+  for (int k = threadIdx.x; k < 4 * box_count; k += 256) box_init[k] = (k & 1) ? -3.402823466e+38f : 3.402823466e+38f;
   int carry_a = 0, carry_b = 0;
   for (int base = 0; base < nkeys; base += 256) {
     const int k = base + threadIdx.x;
@@ -541,7 +704,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 #pragma unroll
     for (int u = 0; u < 4; u++) {
       code[u] = D[4 * u];
-      // A ring the image does not have (SU_CODE_PAD) goes through the step like an EMPTY bin — su_prep gives it the offset of
+      // A ring the image does not have (SU_CODE_PAD) goes through the step like an EMPTY bin — score_prep_kernel gives it the offset of
       // the direction's last real ring, so its mask lookup stays inside the staged box — and is masked out of the known
       // count below.
       pad[u] = code[u] == SU_CODE_PAD ? 0u : 0xFFFFFFFFu;
@@ -813,7 +976,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
       int r = i + shift;
       r -= r >= nb ? nb : 0;
       for (int jj = 0; jj < gn; jj += 4) {
-        // (the flag sits on the step's first bin: su_prep_kernel)
+        // (the flag sits on the step's first bin: score_prep_kernel)
         if (dbase[((int64_t)r * G + jj) * 4 + 3] >> 31) cpp_step(i, r, jj, krow4, kconst);
         else cpp_step_plane(i, r, jj, krow4, kconst);
       }
@@ -1072,7 +1235,8 @@ SuWs tdr_su_ws(int nb, int nr, int group, int64_t n) {
 
 // The ordering passes alone: the slot list — dense particles by heading bin (one bin when L.nb == 1: the Cartesian score has
 // no heading bins), every bin padded to whole waves (-1), then the sparse particles in the caller's order — and the counts.
-int tdr_su_order(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_t** slots_out, const int32_t** counts_out) {
+int tdr_su_order(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_t** slots_out, const int32_t** counts_out,
+                 float* box_init, int box_count) {
   int32_t* base = L.ws;
   uint32_t* keys_in = reinterpret_cast<uint32_t*>(base + W.keys_in);
   uint32_t* keys_out = reinterpret_cast<uint32_t*>(base + W.keys_out);
@@ -1095,7 +1259,8 @@ int tdr_su_order(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_t*
     hipLaunchKernelGGL(su_colscan_kernel, dim3((unsigned)cdiv(nkeys, 64)), dim3(64 * SU_COLSCAN_WAVES), 0, s, seg_hist,
                        (int)segs, nkeys, cnt);
     LAUNCH_CHECK("su_colscan");
-    hipLaunchKernelGGL(su_offsets_kernel, dim3(1), dim3(256), 0, s, (const int*)cnt, nkeys, start, slot_start, counts, slots);
+    hipLaunchKernelGGL(su_offsets_kernel, dim3(1), dim3(256), 0, s, (const int*)cnt, nkeys, start, slot_start, counts, slots,
+                       box_init, box_count);
     LAUNCH_CHECK("su_offsets");
     unsigned bits = 1;
     while ((1u << bits) < (unsigned)nkeys) bits++;
@@ -1110,7 +1275,7 @@ int tdr_su_order(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_t*
                        L.perm, L.nb, L.span, 256, keys_in, vals_in, cnt, (int*)nullptr);
     LAUNCH_CHECK("su_key");
     hipLaunchKernelGGL(su_offsets_kernel, dim3(1), dim3(256), 0, s, (const int*)cnt, nkeys, start, slot_start, counts,
-                       (int32_t*)nullptr);
+                       (int32_t*)nullptr, box_init, box_count);
     LAUNCH_CHECK("su_offsets");
     unsigned bits = 1;
     while ((1u << bits) < (unsigned)nkeys) bits++;
@@ -1152,24 +1317,72 @@ extern "C" int tdr_k_su_order(const float* st, int64_t cap, int64_t n, const int
   HIP_TRY(hipMemcpyAsync(counts_out, counts, sizeof(int32_t) * 3, hipMemcpyDeviceToDevice, s));
   return TDR_OK;
 }
+// rings per direction of score_prep_kernel's grid: a multiple of 64 that covers both layouts
+static int prep_padded_rings(const SuLaunch& L) {
+  const bool bm = ray_bm(L);
+  const int ray = ray_blocks(L.nr, bm) * ray_gq(L.nr, bm) * 64;
+  return (int)(cdiv(std::max(L.nchunks * L.group, ray), 64) * 64);
+}
 int tdr_su_prepare(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_t** slots_out, const int32_t** counts_out) {
-  if (int rc = tdr_su_order(L, W, s, slots_out, counts_out)) return rc;
   int32_t* base = L.ws;
-  float* tab_su = reinterpret_cast<float*>(base + W.tab_su);
-  uint32_t* desc = reinterpret_cast<uint32_t*>(base + W.desc);
-  const int64_t ndesc = (int64_t)L.nchunks * L.nb * L.group;
+  float* bbox = reinterpret_cast<float*>(base + W.bbox);
+  if (L.rf != 4 && L.rf != 8 && L.rf != 12) return fail(TDR_ERR_ARG, "score_prep: no integer form for records of %d floats", L.rf);
+  if (int rc = tdr_su_order(L, W, s, slots_out, counts_out, bbox, L.nchunks * SU_NSECT)) return rc;
+  int* ints = base + W.ints + 3 * (L.nb + 1);   // [counts 3][n_list][inexact][mass bound][table is not its factors]
+  PrepArgs p;
+  p.tab = L.tab_src; p.scan_pk = L.scan_pk;
+  p.nb = L.nb; p.nr = L.nr; p.rf = L.rf; p.ncls = L.map->ncls; p.rp = prep_padded_rings(L);
+  p.uscale = L.uniform_scale ? L.uscale : 0.f; p.res = L.res;
+  p.utab = L.uniform_scale ? L.utab_out : nullptr;
   const int lc = L.map->cwords == 1 ? 3 : (L.map->cwords == 2 ? 2 : 1);
-  const int ckconst = ((L.map->rows >> lc) + 2) * 128 + 128;   // cmap_offset (tdr_score_dev.h)
+  p.group = L.group; p.nchunks = L.nchunks;
+  p.ckconst = ((L.map->rows >> lc) + 2) * 128 + 128;   // cmap_offset (tdr_score_dev.h)
   // plane_offset's constant for class 0's plane, as a byte offset from crec (tdr_score_ray.hip uses the same)
-  const unsigned plane_bytes = (unsigned)(tdr_cmap_plane_words(L.map->ncls, L.map->rows, L.map->cols) * 4);
-  const unsigned pbase = (unsigned)(tdr_cmap_plane_offset_words(L.map->ncls, L.map->rows, L.map->cols) * 4) +
-                         (unsigned)(plane_trows(L.map->rows) * 128) + 128u;
-  hipLaunchKernelGGL(su_prep_kernel, dim3((unsigned)cdiv(ndesc, 256)), dim3(256), 0, s, L.tab, L.scan_pk, L.nb, L.nr, L.rf,
-                     L.map->ncls, ckconst, pbase, plane_bytes, L.group, L.nchunks, L.map->dict, L.map->dict_n, tab_su, desc);
-  LAUNCH_CHECK("su_prep");
-  hipLaunchKernelGGL(su_bbox_kernel, dim3((unsigned)L.nchunks, SU_NSECT), dim3(256), 0, s, (const float*)tab_su, L.nb, L.nr,
-                     L.group, reinterpret_cast<float*>(base + W.bbox));
-  LAUNCH_CHECK("su_bbox");
+  p.plane_bytes = (unsigned)(tdr_cmap_plane_words(L.map->ncls, L.map->rows, L.map->cols) * 4);
+  p.pbase = (unsigned)(tdr_cmap_plane_offset_words(L.map->ncls, L.map->rows, L.map->cols) * 4) +
+            (unsigned)(plane_trows(L.map->rows) * 128) + 128u;
+  p.dict = L.map->dict; p.dict_n = L.map->dict_n;
+  p.tab_su = reinterpret_cast<float*>(base + W.tab_su);
+  p.desc = reinterpret_cast<uint32_t*>(base + W.desc);
+  p.bbox = bbox;
+  const bool bm = ray_bm(L);
+  p.gq = ray_gq(L.nr, bm); p.blocks = ray_blocks(L.nr, bm); p.bm = bm ? 1 : 0; p.patch = ray_patch(L) ? 1 : 0;
+  p.borrow = tdr_cfg().ray_borrow ? 1 : 0;
+  p.dict_tail = reinterpret_cast<const uint32_t*>(L.map->dict) + 2 * TDR_CMAP_MAX_DICT;
+  p.fac = L.fac;
+  p.tab_ray = reinterpret_cast<float*>(base + W.ray_tab);
+  p.rad_ray = reinterpret_cast<float*>(base + W.ray_rad);
+  p.desc_ray = reinterpret_cast<uint16_t*>(base + W.ray_desc);
+  p.list = reinterpret_cast<uint32_t*>(base + W.ray_multi);
+  p.n_list = ints + 3; p.inexact = ints + 4;
+  hipLaunchKernelGGL(score_prep_kernel, dim3((unsigned)(cdiv(L.nb, PREP_DIRS) * (p.rp / 64))), dim3(64 * PREP_DIRS), 0, s, p);
+  LAUNCH_CHECK("score_prep");
+  return TDR_OK;
+}
+// The preparation's products, copied out of a launch's workspace (tdr_k_score_prep, tdr_score.hip): what each holds is
+// described at score_prep_kernel; layout: the shapes behind their sizes.
+int tdr_su_prep_copy_out(const SuLaunch& L, const SuWs& W, hipStream_t s, int64_t layout[16], void* const out[9]) {
+  const bool bm = ray_bm(L);
+  const int64_t nbins = (int64_t)L.nchunks * L.nb * L.group, T = tdr_ray_padded_samples(L.nb, L.nr);
+  if (layout) {
+    const int64_t v[16] = {L.group, L.nchunks, prep_padded_rings(L), ray_gq(L.nr, bm), ray_blocks(L.nr, bm), bm ? 1 : 0,
+                           ray_patch(L) ? 1 : 0, T, nbins, SU_NSECT, TDR_SU_TAIL_INTS, L.uniform_scale ? 1 : 0, 0, 0, 0, 0};
+    for (int k = 0; k < 16; k++) layout[k] = v[k];
+  }
+  if (!out || !L.ws) return TDR_OK;
+  const int32_t* base = L.ws;
+  const struct { const void* src; size_t bytes; } parts[9] = {
+      {L.uniform_scale ? L.utab_out : nullptr, sizeof(float) * 2 * (size_t)L.nb * L.nr},
+      {base + W.tab_su, sizeof(float) * 2 * (size_t)nbins},
+      {base + W.desc, sizeof(uint32_t) * 4 * (size_t)nbins},
+      {base + W.bbox, sizeof(float) * 4 * (size_t)L.nchunks * SU_NSECT},
+      {base + W.ray_tab, sizeof(float) * 2 * (size_t)T},
+      {base + W.ray_desc, sizeof(uint32_t) * (size_t)((T + 1) / 2)},
+      {base + W.ray_rad, sizeof(float) * (size_t)(T / L.nb)},
+      {base + W.ray_multi, sizeof(uint32_t) * (size_t)L.nb * L.nr},
+      {base + W.ints + 3 * (L.nb + 1), sizeof(int32_t) * TDR_SU_TAIL_INTS}};
+  for (int k = 0; k < 9; k++)
+    if (out[k] && parts[k].src) HIP_TRY(hipMemcpyAsync(out[k], parts[k].src, parts[k].bytes, hipMemcpyDeviceToDevice, s));
   return TDR_OK;
 }
 

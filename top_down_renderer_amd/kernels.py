@@ -802,6 +802,30 @@ class HipKernels:
                                       self.stream()))
         return slots, keys, counts, bool(bucket.value)
 
+    def score_prep(self, m, scan_pk, res, st, n, perm=None, uniform_scale=0.0, n_total=0, ctx=None, span=0.0, workspace=None):
+        """tdr_k_score_prep (include/tdr.h): the ordering passes and the scan-side preparation of an integer-form scoring call
+        alone.  Returns (layout, products): the 16 layout words and a dict of tensors — utab, tab_su, desc, bbox, tab_ray,
+        desc_ray (int16 view), rad_ray, list, tail.  `workspace`: a float tensor of tdr_score_workspace_floats floats."""
+        if ctx is not None:
+            check(self.lib.tdr_score_ctx_set_polar_factors(ctx.handle, _ptr(getattr(m, "fac", None)), m.nb, m.nr))
+        h = ctx.handle if ctx is not None else C.c_void_p(0)
+        lay = (C.c_int64 * 16)()
+        head = (C.byref(m.desc), _ptr(m.tab), _ptr(scan_pk), m.nb, m.nr, C.c_float(res), _ptr(st), st.shape[1], n, n_total,
+                _ptr(perm), C.c_float(uniform_scale), C.c_float(span))
+        check(self.lib.tdr_k_score_prep(*head, None, h, lay, None, self.stream()))
+        group, nchunks, _, _, _, _, _, T, nbins, nsect, tail = [int(v) for v in lay[:11]]
+        ws = workspace if workspace is not None else self._workspace(m.ncls, m.nb, m.nr, n, n_total)
+        prod = {"utab": self.zeros((m.nr * m.nb, 2)), "tab_su": self.zeros((nbins, 2)),
+                "desc": self.zeros((nbins, 4), torch.int32), "bbox": self.zeros((nchunks, nsect, 4)),
+                "tab_ray": self.zeros((T, 2)), "desc_ray": self.zeros(((T + 1) // 2,), torch.int32),
+                "rad_ray": self.zeros((T // m.nb,)), "list": self.zeros((m.nb * m.nr,), torch.int32),
+                "tail": self.zeros((tail,), torch.int32)}
+        out = (C.c_void_p * 9)(*[_ptr(prod[k]) for k in ("utab", "tab_su", "desc", "bbox", "tab_ray", "desc_ray", "rad_ray",
+                                                           "list", "tail")])
+        check(self.lib.tdr_k_score_prep(*head, _ptr(ws), h, lay, out, self.stream()))
+        prod["desc_ray"] = prod["desc_ray"].view(torch.int16)
+        return [int(v) for v in lay], prod
+
     def tuning(self, name, value=-1):
         """tdr_config_tuning (include/tdr.h): value < 0 queries; returns the value in force, -1 for an unknown name."""
         return int(self.lib.tdr_config_tuning(name.encode(), value))
