@@ -121,7 +121,10 @@ def _model(lib, m, tab, scan, lay, uscale, res, fac):
     listed = real & ~loop & (nz[K] >= 1)
     out["list"] = np.sort(((I[listed].astype(np.uint32) << 16) | J[listed].astype(np.uint32)))
     tk = total[(np.arange(nr)[:, None] * nb + np.arange(nb)[None, :]).ravel()]
-    out["mass"] = int(((tk[(tk >= 1) & (tk < 16777216)].astype(np.uint32) >> 8) + 1).sum())
+    # the mass bound: the word holds the sum modulo 2^32 (one bin adds at most 65 536: 65 536 such bins make it 0 again), and the
+    # addition that carries the sum to 2^24 or past it raises inexact[0] — a bound of 2^24 or more never passes for a low one
+    mass = int(((tk[(tk >= 1) & (tk < 16777216)].astype(np.int64) >> 8) + 1).sum())
+    out["mass"], out["mass_off"] = mass & 0xFFFFFFFF, int(mass >= (1 << 24))
     return out
 
 
@@ -172,13 +175,41 @@ def test_every_product_against_a_model(tdr, oracle, restore, shape):
                 assert tail[2] == tail[0] + tail[1] and tail[0] % 64 == 0 and 0 < tail[2] and tail[1] <= s.n
                 assert tail[3] == len(want["list"]) and tail[3] >= 3
                 assert np.array_equal(np.sort(got["list"][:tail[3]].view(np.uint32)), want["list"])
-                assert tail[4] == 0 and tail[5] == want["mass"] and want["mass"] < (1 << 24)
+                assert tail[4] == want["mass_off"] == 0 and tail[5] == want["mass"] and want["mass"] < (1 << 24)
                 assert tail[6] == want["not_factors"] == (1 if facs == "other" else 0)
     finally:
         dev.fac = fac_own
         k.lib.tdr_score_ctx_set_polar_factors(ctx.handle, None, 0, 0)
         restore()
     assert (1, 1, 1 if nb % 16 == 0 else 0) in seen_orders and any(o[1] == 0 for o in seen_orders)
+
+
+@pytest.mark.parametrize("shape,full,extra,bound", (((32, 24), 255, 65534 * 256, (1 << 24) - 1), ((32, 24), 256, 0, 1 << 24),
+                                                    ((32, 24), 256, 1, (1 << 24) + 1), ((256, 256), 65536, 0, 1 << 32)),
+                         ids=("2p24_minus_1", "2p24", "2p24_plus_1", "2p32_wraps"))
+def test_the_mass_bound_and_its_flag_against_the_model(tdr, oracle, restore, shape, full, extra, bound):
+    """Bins of 2^24 - 1 add 65 536 each to the bound: below 2^24 the word is the bound and inexact[0] stays down; from 2^24 on
+    inexact[0] is up, also where the word itself has wrapped to 0 (65 536 such bins) — int_form_off never sees a low bound."""
+    pkg, k = tdr
+    nb, nr = shape
+    s = Setup(tdr, oracle, nb, nr)
+    bins = np.random.default_rng(8).permutation(nb * nr)
+    scan = np.zeros_like(s.scan)
+    scan[0, bins[:full]] = (1 << 24) - 1
+    if extra:
+        scan[1, bins[full]] = extra
+    try:
+        k.lib.tdr_config_shift_uniform(2)
+        lay, got = k.score_prep(s.m.dev, s.m.scan_handle(scan), float(s.cfg.res), s.f.st, s.n, perm=s.perm, uniform_scale=0.0,
+                                n_total=N_TOTAL, ctx=None, span=4.0)
+        k.synchronize()
+        tail = got["tail"].cpu().numpy()
+        want = _model(k.lib, s.m.dev, s.m.dev.tab.cpu().numpy().reshape(-1, 2), scan, lay, 0.0, float(s.cfg.res), None)
+        assert want["mass"] == bound & 0xFFFFFFFF and want["mass_off"] == int(bound >= 1 << 24)
+        assert int(tail[5]) & 0xFFFFFFFF == want["mass"] and tail[4] == want["mass_off"]
+        assert tail[3] == len(want["list"]) == full + (1 if extra >= 4096 else 0)   # (a single class below 4096: the descriptor)
+    finally:
+        restore()
 
 
 def _oracle_weights(oracle, s, scan, ang_res=None):

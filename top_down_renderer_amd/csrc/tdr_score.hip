@@ -679,6 +679,16 @@ __global__ __launch_bounds__(256) void score_finalize_batch_kernel(const Finaliz
 // order, state_particle.cpp:136-138), then the reference's own arithmetic (:136-139, 154, 212).
 // A workgroup = 64 slots x 4 shares of a slot's chunk rows (a large filter has 25 rows of 18 words per slot: one lane per
 // slot walked them one after the other with a quarter of the waves); the shares meet in LDS — integers: any grouping.
+// A 64-bit total as a double that rounds to float exactly as the total itself does: up to 53 bits the total; past that
+// (double)total would be a rounding of its own, and the float made from it a number rounded TWICE (a total just above the
+// middle of two floats lands ON the middle and goes down) — so the 53 leading bits, the last of them set when any bit below
+// it is (rounding to odd: a float keeps 24 of them, whether the rest lies below, on or above the middle stays visible).
+__device__ __forceinline__ double u64_to_double_sticky(unsigned long long v) {
+  const int drop = 11 - __clzll(v);   // bits past the 53rd
+  if (drop <= 0) return (double)v;
+  const unsigned long long kept = (v >> drop) | ((v & ((1ull << drop) - 1ull)) != 0ull ? 1ull : 0ull);
+  return ldexp((double)kept, drop);
+}
 __global__ __launch_bounds__(256) void score_finalize_exact_kernel(FinalizeArgs a) {
   __shared__ unsigned long long red[3][TDR_MAX_CLASSES + 2][64];
   if (int_form_off(a.inexact)) return;
@@ -747,7 +757,7 @@ __global__ __launch_bounds__(256) void score_finalize_exact_kernel(FinalizeArgs 
 #pragma unroll
     for (int k = 0; k < TDR_MAX_CLASSES; k++)
       if (k < a.ncls) {
-        const float dot = (float)ldexp((double)tot[k], -q);
+        const float dot = (float)ldexp(u64_to_double_sticky(tot[k]), -q);   // ONE rounding
         cost = (float)((double)cost + (double)dot * 0.01 * (double)a.fp.class_weights[k]);  // :136-139
       }
     cost = cost / (float)norm;  // :154

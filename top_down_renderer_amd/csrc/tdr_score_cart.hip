@@ -671,7 +671,9 @@ __global__ __launch_bounds__(256) void cart_ray_prep_kernel(const float* __restr
   }
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) mass += __shfl_xor(mass, d, 64);
-  if ((threadIdx.x & 63) == 0 && mass) atomicAdd(reinterpret_cast<unsigned*>(flags) + 1, mass);
+  // (the word wraps at 2^32: the addition that carries it to 2^24 or past it raises flags[0] too — score_prep_body)
+  if ((threadIdx.x & 63) == 0 && mass && (uint64_t)atomicAdd(reinterpret_cast<unsigned*>(flags) + 1, mass) + mass >= (1u << 24))
+    atomicOr(flags, 1);
   if (!live) return;
   uint32_t d = 0;
   if (real) {

@@ -93,8 +93,10 @@ __device__ __forceinline__ unsigned plane_offset(int ri, int ci, int pkcol, int 
 }
 
 // The two device words that decide between the integer and the float form of a launch (score_prep_kernel writes them):
-// flags[0] != 0: a scan count or the dictionary has no integer form; flags[1]: an upper bound of (the scan's total count) /
-// 256 — below 2^24 the total stays below 2^32, the normalisation sums fit 32 bits and the class sums 64.
+// flags[0] != 0: a scan count or the dictionary has no integer form, or flags[1] passed 2^24 on its way; flags[1]: an upper
+// bound of (the scan's total count) / 256, modulo 2^32 — below 2^24 the total stays below 2^32, the normalisation sums fit
+// 32 bits and the class sums 64.  (The word alone can read low: 65 536 bins of 2^24 - 1 make it 2^32 = 0; the prep kernels
+// raise flags[0] with the addition that carries it to 2^24.)
 __device__ __forceinline__ bool int_form_off(const int32_t* flags) {
   return flags[0] != 0 || (uint32_t)flags[1] >= (1u << 24);
 }

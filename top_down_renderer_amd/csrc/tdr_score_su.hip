@@ -123,8 +123,8 @@ struct SuArgs {
 // that went on the list), c + 1: class c alone.  Rings beyond nr: an offset far outside the map (their cell is the guard
 // cell: unknown), descriptor 0.  `list`: bins holding several classes or a count >= 4096, as row << 16 | ring (any order:
 // the sums are exact).  inexact[0] is raised when the scan has no integer form: a count that is negative, fractional, not
-// finite or >= 2^24, or a dictionary without one (tdr_cmap.hip); inexact[1] collects the bound on the total count
-// (int_form_off).  fac (optional): the table's factors (tdr_polar_factors_host).  rad_ray[(b * 64 + l) * GQ + g] = ring j's
+// finite or >= 2^24, or a dictionary without one (tdr_cmap.hip), or a bound on the total count that reached 2^24; inexact[1]
+// collects that bound modulo 2^32 (int_form_off).  fac (optional): the table's factors (tdr_polar_factors_host).  rad_ray[(b * 64 + l) * GQ + g] = ring j's
 // radius (rings beyond nr: 1e30 — one of a direction's two products then leaves the map whatever the direction); inexact[2]
 // is raised when an entry of the table is not the float product its factors give (with a uniform scale: that product, scaled
 // the same way) — the scoring kernel then reads tab_ray instead of multiplying the factors itself.
@@ -308,7 +308,10 @@ __device__ __forceinline__ void score_prep_body(const PrepArgs& a, const unsigne
   // ---- what the workgroup adds to the launch's words: one atomic each
   __syncthreads();
   if (threadIdx.x == 0) {
-    if (wg_mass) atomicAdd(reinterpret_cast<unsigned*>(a.inexact) + 1, wg_mass);
+    // the bound must never read low: the word wraps at 2^32 (65 536 bins of 2^24 - 1 add up to exactly that), so the addition
+    // that carries it to 2^24 or past it raises inexact[0] as well — the word starts at 0 and one addition is at most
+    // 512 x 65 536 = 2^25, so the first such addition sees a word below 2^24 and cannot have wrapped it
+    if (wg_mass && (uint64_t)atomicAdd(reinterpret_cast<unsigned*>(a.inexact) + 1, wg_mass) + wg_mass >= (1u << 24)) atomicOr(a.inexact, 1);
     wg_list_base = wg_listed ? (unsigned)atomicAdd(a.n_list, (int)wg_listed) : 0u;
   }
   // the box of (ring group, sector): the first of the workgroup's directions in the sector gathers the others'
