@@ -706,7 +706,7 @@ int tdr_k_locality_order_pose(const float* st, int64_t cap, int64_t n, int map_r
                               int32_t* perm_out, int32_t* keys_tmp, void* stream);
 
 /* =================================================================================================================
- * Handle layer: C++ host code (csrc/tdr_host.cpp) that owns the device memory and sequences the kernels above the way
+ * Handle layer: C++ host code (csrc/tdr_host_*.cpp) that owns the device memory and sequences the kernels above the way
  * the reference's classes sequence their loops.  HOST pointers in and out; one handle per reference object; one caller
  * thread per handle.  This is what the headers under include/top_down_render/ (the reference's class surface) are
  * written against.
@@ -1171,7 +1171,7 @@ int tdr_filter_set_viz_background(tdr_filter* f, const uint8_t* bgr_host, int H,
 int tdr_filter_visualize(tdr_filter* f, float pub_scale, const int32_t* extra_arrows, int m, uint8_t* out_bgr_host,
                          int64_t capacity, int* out_h, int* out_w);
 
-/* internal: lets tdr_host.cpp report through tdr_last_error() */
+/* internal: lets the handle layer (csrc/tdr_host_*.cpp) report through tdr_last_error() */
 int tdr_set_error(int code, const char* msg);
 
 #ifdef __cplusplus

@@ -1,4 +1,4 @@
-"""Cartesian filters through the C handle (tdr_filter_create_cart, csrc/tdr_host.cpp) and through the Python
+"""Cartesian filters through the C handle (tdr_filter_create_cart, csrc/tdr_host_filter.cpp) and through the Python
 ParticleFilter: both sequence the heading search (tdr_k_score_cart_init) and tdr_k_score_cart into the same step, so they
 end with the same bytes; a cold start initialises every heading, checked against the CPU oracle under the rules of
 tests/cart_ref.py; what a Cartesian filter refuses is refused without changing it; and a scan rendered from a known pose

@@ -1,6 +1,7 @@
 """Map ingest: the .eig cache format, and label image -> per-class truncated distance maps.
 CPU: format + oracle restatement properties.  GPU: the device ingest (exact EDT) against the oracle, bit for bit."""
 import os
+import subprocess
 import tempfile
 
 import numpy as np
@@ -35,6 +36,26 @@ def test_eig_format_round_trip_and_layout():
     got, mask = eig_io.load_cached_maps(os.path.join(d, "cache"), 3)
     assert np.array_equal(got, maps) and mask.shape == (6, 5)
     assert open(os.path.join(d, "cache", "cached_data.txt")).read().split("\n")[:3] == ["/some/map.png", "3", "1"]
+
+
+def test_eig_reader_under_host_sanitizers(tmp_path):
+    """csrc/tdr_eig.cpp on its own (it needs no HIP runtime) under AddressSanitizer and UndefinedBehaviorSanitizer:
+    tests/cpp/eig_roundtrip.cpp round-trips a float and a uint8_t matrix bit for bit and feeds read_eig the damaged
+    files (empty, header only, a byte short, a byte long, 0 / -1 / 2^24 rows, the other scalar type), each of which must
+    be refused with the caller's vector untouched.  A stand-alone child process: the sanitizers never meet the shared
+    library or Python."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "eig_roundtrip")
+    # (the runtimes linked statically: the program then starts whatever else the environment preloads into it)
+    subprocess.run(["g++", "-std=c++17", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-static-libasan", "-static-libubsan",
+                    "-I", os.path.join(root, "include"), "-I", os.path.join(root, "top_down_renderer_amd", "csrc"),
+                    os.path.join(root, "tests", "cpp", "eig_roundtrip.cpp"),
+                    os.path.join(root, "top_down_renderer_amd", "csrc", "tdr_eig.cpp"), "-o", exe], check=True)
+    work = tmp_path / "files"
+    work.mkdir()
+    r = subprocess.run([exe, str(work)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "ok" and r.stderr == "", (r.returncode, r.stdout, r.stderr)
 
 
 def test_oracle_ingest_matches_generator_convention():

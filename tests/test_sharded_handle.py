@@ -1,4 +1,4 @@
-"""The C++ handle layer's sharded filter (tdr_filter_create_sharded, csrc/tdr_host.cpp + csrc/tdr_comm.cpp): particles
+"""The C++ handle layer's sharded filter (tdr_filter_create_sharded, csrc/tdr_host_filter.cpp + csrc/tdr_comm.cpp): particles
 partitioned over the ranks of a tdr_comm, scan broadcast from rank 0, one all-gather of {raw weight, last_dist}, one
 all-gather of the state planes.  Must equal the unsharded handle bit for bit.
 

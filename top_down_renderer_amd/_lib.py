@@ -236,7 +236,7 @@ SIGNATURES = {
     "tdr_profile_enable": (_i, [_i]),
     "tdr_profile_score_ms": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "tdr_profile_shares": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
-    # handle layer (csrc/tdr_host.cpp)
+    # handle layer (csrc/tdr_host_*.cpp)
     "tdr_map_create": (_i, [C.POINTER(_vp)]),
     "tdr_map_destroy": (None, [_vp]),
     "tdr_map_set": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _i]),

@@ -1,5 +1,5 @@
 // tdr_batch.h — the device tables of a batched filter step (tdr_batch_step, include/tdr.h): one entry per filter of the
-// batch, built by the handle layer (tdr_host.cpp) and read by the batched kernels — propagate and resample
+// batch, built by the handle layer (tdr_host_batch.cpp) and read by the batched kernels — propagate and resample
 // (tdr_batch.hip), statistics and running sum (tdr_prefix.hip: one workgroup per filter), scoring (tdr_score.hip).  A
 // workgroup finds its filter from its block index: entry k owns the blocks [blk_prop, next entry's blk_prop) of the
 // propagate launch and [blk_res, next entry's blk_res) of the resample launch, and workgroup k of the statistics and

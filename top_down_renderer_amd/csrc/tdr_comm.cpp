@@ -1,6 +1,6 @@
 // tdr_comm.cpp — the exchange steps of a particle filter sharded over several GPUs (include/tdr.h, "tdr_comm_*").
 //
-// One process per GPU, particles partitioned contiguously by rank.  A sharded tdr_filter (tdr_host.cpp) needs
+// One process per GPU, particles partitioned contiguously by rank.  A sharded tdr_filter (tdr_host_filter.cpp) needs
 // exactly two collectives per update — the all-gather of {raw weight, last_dist} of every shard and the all-gather of
 // the state planes the resampler reads — plus the broadcast of the rasterised scan from rank 0.  This file provides them
 // behind one small interface with two transports:
@@ -18,8 +18,6 @@
 #include <mutex>
 
 #include "tdr.h"
-
-extern "C" int tdr_set_error(int code, const char* msg);
 
 namespace {
 int failc(int code, const char* fmt, const char* a = "", const char* b = "") {

@@ -32,6 +32,7 @@
 
 #include "tdr.h"
 #include "tdr_config.h"
+#include "tdr_internal.h"   // the cross-file prototypes no subsystem header holds
 
 // tuning knobs (compile-time)
 #ifndef TDR_SCORE_U
@@ -116,8 +117,6 @@ int tdr_uw_small(const float* raw, const float* last_dist, int64_t n, float* w, 
 // tdr_rng.hip: the generator's raw stream of `nblocks` state blocks behind `state`, and the state behind *consumed words of it
 int tdr_mt_raw_stream(const uint32_t* state, int64_t nblocks, uint32_t* raw, hipStream_t s);
 int tdr_mt_advance(const uint32_t* raw, int64_t nblocks, const uint32_t* consumed, uint32_t* state, hipStream_t s);
-// tdr_score.hip: whether tdr_k_score_polar_ctx scores a filter of these shapes with the float kernel (not the integer form)
-bool tdr_score_polar_float_form(const tdr_map_desc* map, int nb, int nr, int64_t n, int64_t n_total);
 // a record with a spare slot (ncls + 2 <= rf) carries `known` twice: slot rf-2 pairs with a constant 1 of the scan record
 __host__ __device__ inline bool tdr_has_kslot(int ncls, int rf) { return ncls + 2 <= rf; }
 // diagnostics: 16 device counters while tdr_profile_enable(1) is in force, else NULL (tdr_score.hip, tdr_profile_variants)

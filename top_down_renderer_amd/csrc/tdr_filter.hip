@@ -589,7 +589,7 @@ extern "C" int tdr_k_sample_ml_states(const float* st, int64_t cap, int64_t n, i
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Sharded filter (one rank per GPU, tdr_host.cpp): the buffers the two all-gathers move.
+// Sharded filter (one rank per GPU, tdr_host_filter.cpp): the buffers the two all-gathers move.
 //   pack2   : {a[nl], b[nl]} -> one contiguous send buffer [2][nl]
 //   unpack2 : the gathered [world][2][nl] -> a_glob[world*nl], b_glob[world*nl] in global particle order
 //   unshard : the gathered state planes [world][7][nl] -> a plain SoA [7][cap] (pose statistics run on that)

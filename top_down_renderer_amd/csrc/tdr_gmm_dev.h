@@ -1,5 +1,5 @@
 // tdr_gmm_dev.h — the device table of a batched mixture fit's sampling launch (tdr_batch_compute_gmm, include/tdr.h): one
-// entry per filter, built by the handle layer (tdr_host.cpp), read by gmm_batch_samples_kernel (tdr_gmm.hip).  The fit and
+// entry per filter, built by the handle layer (tdr_host_gmm.cpp), read by gmm_batch_samples_kernel (tdr_gmm.hip).  The fit and
 // pick launches read the public tdr_gmm_job / tdr_gmm_pick_job tables.  Internal to libtdr_hip.so.
 #ifndef TDR_GMM_DEV_H_
 #define TDR_GMM_DEV_H_

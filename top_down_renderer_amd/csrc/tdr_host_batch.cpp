@@ -1,0 +1,397 @@
+// tdr_host_batch.cpp — the batched calls on many filters of one map: tdr_batch_step (csrc/tdr_batch.hip) and the two ends
+// of a batched node loop, tdr_batch_render_polar and tdr_batch_pose (csrc/tdr_batch_loop.hip).  Their per-thread
+// staging contexts live here and nowhere else.
+#include "tdr_host.h"
+
+// ---- batched filters (tdr_batch_step): many filters on one map, one launch per stage -------------------------------------
+// Each filter keeps what is its own: its generator pipe draws its normals and its uniform (per-filter mt19937 streams) and
+// its scan is packed into its own buffer.  The stages of the step are then one launch each over a table of the filters:
+// propagate and resample (csrc/tdr_batch.hip), the float scoring launch (tdr_score.hip), the statistics and the running
+// sum (tdr_prefix.hip).  The locality order is left out: it never changes results (tdr.h).
+namespace {
+thread_local int g_batch_stats[2] = {0, 0};   // filters of this thread's last batch: batched, standalone
+struct BatchCtx {   // per thread: the tables, staged in pinned host memory and copied to the device, reused from call to call
+  char* host = nullptr;
+  DevBuf<char> dev;
+  size_t cap = 0;
+  hipEvent_t uploaded = nullptr;   // the last call's copy has read `host`
+  hipEvent_t done = nullptr;       // the last call's kernels have read `dev`
+  ~BatchCtx() {
+    if (uploaded) { (void)hipEventSynchronize(uploaded); (void)hipEventDestroy(uploaded); }
+    if (done) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+    if (host) (void)hipHostFree(host);
+  }
+};
+thread_local BatchCtx g_batch;
+}  // namespace
+
+extern "C" {
+int tdr_batch_last_stats(int* batched, int* standalone) {
+  if (batched) *batched = g_batch_stats[0];
+  if (standalone) *standalone = g_batch_stats[1];
+  return TDR_OK;
+}
+
+static bool batch_eligible(const tdr_filter* f) {
+  const tdr_map* m = f->map;
+  // (a filter that may hold a particle without a heading: only with tdr_config_tuning("batch_init_search"))
+  const bool uninit_ok = !f->maybe_uninit || tdr_cfg().batch_init_search == 1;
+  return !f->comm && rng_device_capable(f) && uninit_ok && f->n >= 1 && f->n <= 32768 &&
+         tdr_score_polar_float_form(&m->desc, m->nb, m->nr, f->n, f->n);
+}
+
+int tdr_batch_step(tdr_filter* const* filters, int k, const tdr_batch_input* in, void* stream) {
+  g_batch_stats[0] = g_batch_stats[1] = 0;
+  if (k < 1) return failh(TDR_ERR_ARG, "batch_step: k = %d, at least one filter is needed", k);
+  if (!filters || !in) return failh(TDR_ERR_ARG, "batch_step: null %s array", !filters ? "filter" : "input");
+  for (int i = 0; i < k; i++)
+    if (!filters[i]) return failh(TDR_ERR_ARG, "batch_step: filter %d is null", i);
+  {
+    std::vector<const tdr_filter*> seen(filters, filters + k);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+      return failh(TDR_ERR_ARG, "batch_step: a filter appears twice in the batch");
+  }
+  tdr_map* m = filters[0]->map;
+  for (int i = 0; i < k; i++)
+    if (filters[i]->map != m) return failh(TDR_ERR_ARG, "batch_step: filter %d is on another map than filter 0", i);
+  for (int i = 0; i < k; i++)
+    if (filters[i]->cart) return failh(TDR_ERR_ARG, "batch_step: filter %d is a Cartesian filter (batches are polar)", i);
+  if (!m || !m->have_map) return failh(TDR_ERR_ARG, "batch_step: the filters' map holds no map");
+  if (m->nb < 1 || !m->tab.p) return failh(TDR_ERR_ARG, "batch_step: samplePtsPolar was never called on the map");
+  const int ncls = m->desc.ncls, nb = m->nb, nr = m->nr;
+  for (int i = 0; i < k; i++) {
+    const tdr_renderer* r = in[i].renderer;
+    if (!in[i].scan_imgs && !r) return failh(TDR_ERR_ARG, "batch_step: input %d has no scan", i);
+    if (!in[i].scan_imgs && !r->have_scan) return failh(TDR_ERR_ARG, "batch_step: input %d: the renderer has no render", i);
+    if (!in[i].scan_imgs && (r->ncls != ncls || r->rows != nb || r->cols != nr))
+      return failh(TDR_ERR_ARG, "batch_step: input %d: render shape %dx%dx%d does not match the map's %dx%dx%d", i, r->ncls,
+                   r->rows, r->cols, ncls, nb, nr);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> fast;
+  for (int i = 0; i < k; i++) {
+    tdr_filter* f = filters[i];
+    if (batch_eligible(f)) { fast.push_back(i); continue; }
+    TTRY(tdr_filter_propagate(f, in[i].tx, in[i].ty, in[i].omega));
+    TTRY(tdr_filter_update(f, in[i].scan_imgs, in[i].renderer, in[i].res, in[i].n_target));
+    g_batch_stats[1]++;
+  }
+  const int kf = (int)fast.size();
+  if (kf == 0) return TDR_OK;
+
+  BatchCtx& B = g_batch;
+  // the batched filters whose 40-rotation search is part of the scoring stage; the largest decides about the map's scratch
+  int k_init = 0;
+  bool uses_rec16 = false;
+  for (int j = 0; j < kf; j++) {
+    const tdr_filter* f = filters[fast[j]];
+    if (!f->maybe_uninit) continue;
+    k_init++;
+    TTRY(map_rec16_alloc(m, f->n));
+    uses_rec16 |= m->desc.rec16 && f->n >= tdr_cfg().rec16_min;
+  }
+  // one staging area: [kf] TdrBatchEntry, then the scoring launch's tables (tdr_batch_score_stage_bytes)
+  const size_t ent_bytes = (sizeof(TdrBatchEntry) * (size_t)kf + 63) / 64 * 64;
+  const size_t stage = ent_bytes + tdr_batch_score_stage_bytes(kf, k_init);
+  if (!B.uploaded) HTRY(hipEventCreateWithFlags(&B.uploaded, hipEventDisableTiming));
+  if (!B.done) HTRY(hipEventCreateWithFlags(&B.done, hipEventDisableTiming));
+  HTRY(hipEventSynchronize(B.uploaded));   // (the previous call's copy has left the pinned buffer)
+  if (B.cap < stage) {
+    HTRY(hipEventSynchronize(B.done));     // (and its kernels the device buffer that is replaced)
+    if (B.host) HTRY(hipHostFree(B.host));
+    B.host = nullptr;
+    B.cap = 0;
+    HTRY(hipHostMalloc((void**)&B.host, stage));
+    B.cap = stage;
+  }
+  TTRY(B.dev.resize(stage));
+  TdrBatchEntry* const tab = reinterpret_cast<TdrBatchEntry*>(B.host);
+  TdrBatchEntry* const tab_dev = reinterpret_cast<TdrBatchEntry*>(B.dev.p);
+
+  // the batch stream continues after the batched renders it reads, everything already queued on the filters' own
+  // streams, and after the previous batch's kernels have read the device tables this call overwrites
+  for (int j = 0; j < kf; j++)
+    if (!in[fast[j]].scan_imgs) TTRY(renderer_wait_render(in[fast[j]].renderer, s));
+  std::vector<hipEvent_t> evs((size_t)kf, nullptr);
+  auto destroy_events = [&]() { for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e); };
+  int rc = TDR_OK;
+  if (hipStreamWaitEvent(s, B.done, 0) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: stream wait");
+  for (int j = 0; j < kf && rc == TDR_OK; j++) {
+    tdr_filter* f = filters[fast[j]];
+    rc = rng_to_device(f);
+    if (rc == TDR_OK && hipEventCreateWithFlags(&evs[j], hipEventDisableTiming) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: event");
+    if (rc == TDR_OK && hipEventRecord(evs[j], f->stream) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: event record");
+    if (rc == TDR_OK && hipStreamWaitEvent(s, evs[j], 0) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: stream wait");
+  }
+  if (rc != TDR_OK) { destroy_events(); return rc; }
+
+  // per filter: its generator's normals and uniform (the pipe orders its own side stream against `s`; the draws keep the
+  // standalone order), its scan packed into its own buffer, and its table entries
+  const size_t P = (size_t)nb * nr, pk_floats = P * tdr_rec_floats(ncls);
+  std::vector<TdrBatchScoreIn> sin((size_t)kf);
+  int blocks_prop = 0, blocks_res = 0;
+  int64_t n_big = 1;
+  for (int j = 0; j < kf && rc == TDR_OK; j++) {
+    tdr_filter* f = filters[fast[j]];
+    const tdr_batch_input& x = in[fast[j]];
+    TdrBatchEntry& e = tab[j];
+    e = TdrBatchEntry{};
+    f->states_changed();
+    f->fp.num_classes = ncls;
+    rc = tdr_rng_pipe_normals(f->pipe, f->n, 0, f->n, f->scale_frozen ? 1 : 0, &e.z4, s);
+    f->prop_calls++;
+    if (rc == TDR_OK) rc = tdr_rng_pipe_uniform(f->pipe, &e.shift, s);
+    if (rc == TDR_OK) rc = f->ml_dev.resize(12);
+    const float* pk = nullptr;
+    if (rc == TDR_OK && x.scan_imgs) {
+      rc = f->scan_img.resize(P * ncls);
+      if (rc == TDR_OK) rc = f->scan_pk.resize(pk_floats);
+      if (rc == TDR_OK && hipMemcpyAsync(f->scan_img.p, x.scan_imgs, P * ncls * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)
+        rc = failh(TDR_ERR_HIP, "batch_step: scan upload");
+      if (rc == TDR_OK) rc = tdr_k_pack_scan(f->scan_img.p, ncls, nb, nr, f->scan_pk.p, s);
+      pk = f->scan_pk.p;
+    } else {
+      pk = x.renderer->pk.p;
+    }
+    if (rc == TDR_OK) rc = f->ws.resize(tdr_score_workspace_floats(ncls, nb, nr, f->n, f->n));
+    int64_t n_new = f->n;
+    if (x.n_target >= 0) n_new = std::max<int64_t>(1, std::min<int64_t>(x.n_target, f->n_max));
+    e.st = f->st.p; e.st_new = f->st_new.p; e.last_dist = f->last_dist.p; e.cap = f->cap; e.n = f->n; e.n_new = n_new;
+    e.tx = x.tx; e.ty = x.ty; e.omega = x.omega; e.pos_cov = f->fp.pos_cov; e.theta_cov = f->fp.theta_cov;
+    e.scale_freeze = f->scale_frozen ? 1 : 0;
+    e.raw_w = f->raw_w.p; e.w_out = f->w.p; e.info_out = f->info.p; e.runmax_out = f->runmax.p;
+    e.runmax = f->runmax.p; e.info = f->info.p; e.idx = f->idx.p; e.ml = f->ml_dev.p;
+    e.blk_prop = blocks_prop;
+    blocks_prop += (int)((f->n + TDR_BATCH_THREADS - 1) / TDR_BATCH_THREADS);
+    e.blk_res = blocks_res;
+    blocks_res += (int)((n_new + TDR_BATCH_THREADS - 1) / TDR_BATCH_THREADS);
+    n_big = std::max(n_big, f->n);
+    sin[j] = TdrBatchScoreIn{pk, x.res, &f->fp, f->st.p, f->cap, f->n, f->uniform_scale, f->raw_w.p, f->ws.p,
+                             f->maybe_uninit ? 1 : 0};
+  }
+  if (rc == TDR_OK) rc = tdr_batch_score_build(&m->desc, m->tab.p, nb, nr, kf, sin.data(), B.host + ent_bytes);
+  if (rc == TDR_OK && hipMemcpyAsync(B.dev.p, B.host, stage, hipMemcpyHostToDevice, s) != hipSuccess)
+    rc = failh(TDR_ERR_HIP, "batch_step: table upload");
+  if (rc == TDR_OK && hipEventRecord(B.uploaded, s) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: event record");
+  // one launch per stage over the whole batch (the scoring launch: utab, score, finalize)
+  if (rc == TDR_OK) rc = tdr_batch_propagate(tab_dev, kf, blocks_prop, s);
+  if (rc == TDR_OK && uses_rec16) rc = map_rec16_begin(m, s);
+  if (rc == TDR_OK) rc = tdr_batch_score_launch(&m->desc, m->tab.p, nb, nr, kf, B.host + ent_bytes, B.dev.p + ent_bytes, s);
+  if (rc == TDR_OK && uses_rec16) rc = map_rec16_end(m, s);
+  if (rc == TDR_OK) rc = tdr_batch_update_weights(tab_dev, kf, n_big, s);
+  if (rc == TDR_OK) rc = tdr_batch_prefix(tab_dev, kf, n_big, s);
+  if (rc == TDR_OK) rc = tdr_batch_resample(tab_dev, kf, blocks_res, s);
+  if (rc == TDR_OK && hipEventRecord(B.done, s) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: event record");
+  for (int j = 0; j < kf && rc == TDR_OK; j++)
+    if (!in[fast[j]].scan_imgs) rc = renderer_note_read(in[fast[j]].renderer, s);
+  if (rc != TDR_OK) { destroy_events(); return rc; }
+  for (int j = 0; j < kf; j++) {
+    tdr_filter* f = filters[fast[j]];
+    f->have_ml = true;
+    f->states_changed();
+    // the search initialises every un-gated particle; only gated ones can stay un-initialised (filter_score)
+    if (f->maybe_uninit && !(f->fp.force_on_map || f->fp.fixed_scale < 0)) f->maybe_uninit = false;
+    std::swap(f->st.p, f->st_new.p);   // particle_filter.cpp:187
+    f->n = tab[j].n_new;
+    f->step++;
+  }
+  // the filters' own streams continue after the batch
+  for (int j = 0; j < kf && rc == TDR_OK; j++)
+    if (hipStreamWaitEvent(filters[fast[j]]->stream, B.done, 0) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_step: stream wait");
+  destroy_events();
+  g_batch_stats[0] = kf;
+  return rc;
+}
+}  // extern "C"
+
+// ---- the two ends of a batched node loop: tdr_batch_render_polar, tdr_batch_pose (csrc/tdr_batch_loop.hip) ---------------
+namespace {
+thread_local StageCtx g_render_stage, g_pose_stage;
+}  // namespace
+
+extern "C" {
+int tdr_batch_render_polar(tdr_renderer* const* r, int k, const tdr_batch_cloud* clouds, float ang_res, int ncls, int nb,
+                           int nr, void* stream) {
+  if (k < 1) return failh(TDR_ERR_ARG, "batch_render: k = %d, at least one renderer is needed", k);
+  if (!r || !clouds) return failh(TDR_ERR_ARG, "batch_render: null %s array", !r ? "renderer" : "cloud");
+  for (int i = 0; i < k; i++)
+    if (!r[i]) return failh(TDR_ERR_ARG, "batch_render: renderer %d is null", i);
+  {
+    std::vector<const tdr_renderer*> seen(r, r + k);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+      return failh(TDR_ERR_ARG, "batch_render: a renderer appears twice in the batch");
+  }
+  for (int i = 0; i < k; i++) {
+    const tdr_batch_cloud& c = clouds[i];
+    if (c.n < 0 || (c.n > 0 && !c.pts)) return failh(TDR_ERR_ARG, "batch_render: cloud %d: null points", i);
+    if (c.stride < 3 || c.ioff < 0 || c.ioff >= c.stride)
+      return failh(TDR_ERR_ARG, "batch_render: cloud %d: bad point stride / offset %d / %d", i, c.stride, c.ioff);
+    if (!(c.res > 0.f)) return failh(TDR_ERR_ARG, "batch_render: cloud %d: resolution must be > 0", i);
+  }
+  if (!(ang_res > 0.f)) return failh(TDR_ERR_ARG, "batch_render: angular resolution must be > 0");
+  if (ncls < 1 || ncls > TDR_MAX_CLASSES || nb < 1 || nr < 1)
+    return failh(TDR_ERR_ARG, "batch_render: bad image shape %dx%dx%d", ncls, nb, nr);
+  if ((int64_t)ncls * nb * 4 > 152 * 1024) return failh(TDR_ERR_ARG, "batch_render: ncls*rows too large for one LDS tile (152 KB)");
+  TdrBatchRasterShape shape{};
+  const bool keyed = tdr_batch_raster_shape(ncls, nb, nr, ang_res, &shape);
+  hipStream_t s = (hipStream_t)stream;
+
+  // one staging area: [k] entries, then every cloud's points (64-byte aligned); on the device, the keys follow
+  const size_t ent_bytes = align64(sizeof(TdrBatchRasterEntry) * (size_t)k);
+  std::vector<size_t> pts_off((size_t)k), key_off((size_t)k);
+  size_t stage = ent_bytes;
+  for (int i = 0; i < k; i++) {
+    pts_off[i] = stage;
+    stage += align64((size_t)clouds[i].n * clouds[i].stride * sizeof(float));
+  }
+  size_t dev_bytes = stage;
+  for (int i = 0; i < k; i++) {
+    key_off[i] = dev_bytes;
+    dev_bytes += align64((size_t)clouds[i].n * sizeof(uint32_t));
+  }
+  StageCtx& B = g_render_stage;
+  TTRY(B.reserve(stage, std::max<size_t>(dev_bytes, 64), s));
+  const size_t P = (size_t)nb * nr, rf = (size_t)tdr_rec_floats(ncls);
+  for (int i = 0; i < k; i++) {
+    tdr_renderer* q = r[i];
+    TTRY(q->img.resize(P * ncls));
+    TTRY(q->pk.resize(P * rf));
+    // img / pk are rewritten: after their readers and the renderer's previous batched render
+    for (size_t j = 0; j < q->n_readers; j++) HTRY(hipStreamWaitEvent(s, q->readers[j].second, 0));
+    TTRY(renderer_wait_render(q, s));
+    if (!q->rendered) HTRY(hipEventCreateWithFlags(&q->rendered, hipEventDisableTiming));
+  }
+  TdrBatchRasterEntry* tab = reinterpret_cast<TdrBatchRasterEntry*>(B.host);
+  int blocks_keys = 0;
+  for (int i = 0; i < k; i++) {
+    const tdr_batch_cloud& c = clouds[i];
+    if (c.n > 0) std::memcpy(B.host + pts_off[i], c.pts, (size_t)c.n * c.stride * sizeof(float));
+    TdrBatchRasterEntry& e = tab[i];
+    e = TdrBatchRasterEntry{};
+    e.pts = reinterpret_cast<const float*>(B.dev.p + pts_off[i]);
+    e.lut = r[i]->lut.p;
+    e.keys = reinterpret_cast<uint32_t*>(B.dev.p + key_off[i]);
+    e.img = r[i]->img.p;
+    e.pk = r[i]->pk.p;
+    e.n = c.n;
+    e.res = c.res;
+    e.stride = c.stride;
+    e.ioff = c.ioff;
+    e.blk_keys = blocks_keys;
+    blocks_keys += (int)((c.n + 255) / 256);
+  }
+  HTRY(hipMemcpyAsync(B.dev.p, B.host, stage, hipMemcpyHostToDevice, s));
+  HTRY(hipEventRecord(B.uploaded, s));
+  if (keyed) {
+    TTRY(tdr_batch_raster(reinterpret_cast<const TdrBatchRasterEntry*>(B.dev.p), k, blocks_keys, shape, s));
+  } else {   // shapes the standalone raster scores without keys: its own launch per renderer
+    for (int i = 0; i < k; i++)
+      TTRY(tdr_k_raster_polar(tab[i].pts, clouds[i].stride, clouds[i].ioff, clouds[i].n, clouds[i].res, ang_res, r[i]->lut.p,
+                              ncls, nb, nr, r[i]->img.p, r[i]->pk.p, tab[i].keys, s));
+  }
+  HTRY(hipEventRecord(B.done, s));
+  for (int i = 0; i < k; i++) {
+    tdr_renderer* q = r[i];
+    HTRY(hipEventRecord(q->rendered, s));
+    q->render_async = true;
+    q->n_readers = 0;
+    q->ncls = ncls;
+    q->rows = nb;
+    q->cols = nr;
+    q->polar = true;
+    q->have_scan = true;
+  }
+  return TDR_OK;
+}
+
+int tdr_batch_pose(tdr_filter* const* f, int k, tdr_pose_stats* out, void* stream) {
+  if (k < 1) return failh(TDR_ERR_ARG, "batch_pose: k = %d, at least one filter is needed", k);
+  if (!f || !out) return failh(TDR_ERR_ARG, "batch_pose: null %s array", !f ? "filter" : "output");
+  for (int i = 0; i < k; i++)
+    if (!f[i]) return failh(TDR_ERR_ARG, "batch_pose: filter %d is null", i);
+  {
+    std::vector<const tdr_filter*> seen(f, f + k);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+      return failh(TDR_ERR_ARG, "batch_pose: a filter appears twice in the batch");
+  }
+  for (int i = 0; i < k; i++)
+    if (f[i]->map != f[0]->map) return failh(TDR_ERR_ARG, "batch_pose: filter %d is on another map than filter 0", i);
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> small, big;
+  for (int i = 0; i < k; i++) {
+    tdr_filter* g = f[i];
+    tdr_pose_stats& o = out[i];
+    o = tdr_pose_stats{};
+    o.n = g->n;
+    if (g->comm) {   // the all-gather inside is collective: the standalone calls
+      TTRY(tdr_filter_mean_cov(g, 0, o.mean, o.cov));
+      o.scale = tdr_filter_scale(g);
+      continue;
+    }
+    if (g->n < 1) { o.scale = tdr_filter_scale(g); continue; }   // (zeros, no device work)
+    (g->n <= TDR_BATCH_MC_SINGLE_MAX_N ? small : big).push_back(i);
+  }
+  const int ks = (int)small.size(), kb = (int)big.size(), kd = ks + kb;
+  if (kd == 0) return TDR_OK;
+  // staging: [kd] entries (small ones first), then the [kd] result records the kernels write and the copy brings back
+  const size_t ent_bytes = align64(sizeof(TdrBatchPoseEntry) * (size_t)kd);
+  const size_t res_bytes = sizeof(float) * TDR_BATCH_POSE_FLOATS * (size_t)kd;
+  StageCtx& B = g_pose_stage;
+  TTRY(B.reserve(ent_bytes + res_bytes, ent_bytes + res_bytes, s));
+  // after every filter's last step, on whichever stream it ran (tdr_batch_step leaves the filters' streams after it)
+  {
+    std::vector<hipStream_t> streams;
+    for (int i : small) streams.push_back(f[i]->stream);
+    for (int i : big) streams.push_back(f[i]->stream);
+    std::sort(streams.begin(), streams.end());
+    streams.erase(std::unique(streams.begin(), streams.end()), streams.end());
+    for (hipStream_t fs : streams) {
+      if (fs == s) continue;
+      hipEvent_t e = nullptr;
+      HTRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      int rc = TDR_OK;
+      if (hipEventRecord(e, fs) != hipSuccess || hipStreamWaitEvent(s, e, 0) != hipSuccess) rc = failh(TDR_ERR_HIP, "batch_pose: stream order");
+      (void)hipEventDestroy(e);
+      if (rc != TDR_OK) return rc;
+    }
+  }
+  TdrBatchPoseEntry* tab = reinterpret_cast<TdrBatchPoseEntry*>(B.host);
+  float* res_dev = reinterpret_cast<float*>(B.dev.p + ent_bytes);
+  float* res_host = reinterpret_cast<float*>(B.host + ent_bytes);
+  std::vector<int> order(small);
+  order.insert(order.end(), big.begin(), big.end());
+  for (int j = 0; j < kd; j++) {
+    tdr_filter* g = f[order[j]];
+    tab[j] = TdrBatchPoseEntry{g->st.p, g->cap, g->n, res_dev + (size_t)TDR_BATCH_POSE_FLOATS * j, g->stats.p + 24};
+  }
+  const TdrBatchPoseEntry* tab_dev = reinterpret_cast<const TdrBatchPoseEntry*>(B.dev.p);
+  HTRY(hipMemcpyAsync(B.dev.p, B.host, ent_bytes, hipMemcpyHostToDevice, s));
+  TTRY(tdr_batch_pose_launch(tab_dev, ks, tab_dev + ks, kb, s));
+  HTRY(hipMemcpyAsync(res_host, res_dev, res_bytes, hipMemcpyDeviceToHost, s));
+  HTRY(hipEventRecord(B.done, s));
+  HTRY(hipEventRecord(B.uploaded, s));
+  HTRY(hipEventSynchronize(B.done));   // the one wait of the call
+  for (int j = 0; j < kd; j++) {
+    tdr_filter* g = f[order[j]];
+    const float* rec = res_host + (size_t)TDR_BATCH_POSE_FLOATS * j;
+    tdr_pose_stats& o = out[order[j]];
+    std::memcpy(g->mean_cov_host, rec, sizeof(g->mean_cov_host));   // the cache tdr_filter_mean_cov(f, 0, ...) reads
+    g->mean_cov_valid = true;
+    std::memcpy(o.mean, rec, sizeof(o.mean));
+    std::memcpy(o.cov, rec + 4, sizeof(o.cov));
+    if (g->fp.fixed_scale > 0) {           // tdr_filter_scale
+      o.scale = g->fp.fixed_scale;
+    } else if (g->scale_frozen) {
+      o.scale = rec[24];
+      g->scale_host = rec[24];
+      g->scale_valid = true;
+    } else {
+      o.scale = -1.f;
+    }
+  }
+  return TDR_OK;
+}
+}  // extern "C"

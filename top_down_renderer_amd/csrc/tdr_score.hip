@@ -831,7 +831,6 @@ static int score_group_rings(int nb, int nr, int rf, int64_t n_total) {
 // best_theta npad][list npad + 64: rotation table of the init search][uniform-scale table 2*nb*nr][shift-uniform order,
 // tdr_score_su.h].  npad_part = the slot count of the shift-uniform order where the shapes allow it (its partial sums are
 // slot-indexed and the slots include the padding), else npad.
-extern "C" int tdr_cmap_words(int ncls);   // tdr_cmap.hip
 struct ScoreWs {
   int group, nchunks;
   int su_group, su_nchunks;   // the ring groups of the shift-uniform kernel (integer sums: any partition gives the same bits)
@@ -1017,9 +1016,6 @@ static int check_map_addressing(const tdr_map_desc* map, int rf, const char* who
                 map->rows, map->cols, rf);
   return TDR_OK;
 }
-
-extern "C" int tdr_cmap_words(int ncls);
-extern "C" size_t tdr_cmap_tile_words(int ncls, int rows, int cols);
 
 static bool map_is_wide(const tdr_map_desc* map, int rf) {   // tdr_cmap.hip: 16-bit fields
   return rf == 8 && map->cwords == 4 && map->dict_n > TDR_CMAP_MAX_DICT;

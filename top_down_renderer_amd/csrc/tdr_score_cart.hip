@@ -606,8 +606,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void s
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-extern "C" int tdr_cmap_words(int ncls);
-extern "C" size_t tdr_cmap_tile_words(int ncls, int rows, int cols);
 
 bool tdr_cart_skip_ok(const tdr_map_desc* map, int rf) {
   return tdr_cfg().cart_skip && rf <= 12 && map->cwords > 0 && map->cwords == tdr_cmap_words(map->ncls) && map->crec && map->dict &&
@@ -918,8 +916,6 @@ __global__ __launch_bounds__(256) void score_cart_ray_kernel(CartRayArgs a) {
 }
 
 // ---- host side of the integer form ---------------------------------------------------------------------------------------
-extern "C" size_t tdr_cmap_plane_offset_words(int ncls, int rows, int cols);
-extern "C" size_t tdr_cmap_plane_words(int ncls, int rows, int cols);
 
 bool tdr_cart_int_ok(const tdr_map_desc* map, int rf, int rows, int cols, int64_t n_total) {
   // (mode 0 of tdr_config_shift_uniform switches the integer forms off altogether: A/B measurements, tests)

@@ -149,7 +149,7 @@ extern "C" int tdr_k_score_cart_init(const tdr_map_desc* map, const float* scan_
   const CartInitWs w = cart_init_ws(map->ncls, rows, cols, n, n_total);
   int32_t* count = reinterpret_cast<int32_t*>(workspace + w.list);
   int32_t* list = count + 64;
-  const float theta_radius = (float)(rows + cols) / 16.f;   // the filters' (csrc/tdr_host.cpp, particle_filter.py)
+  const float theta_radius = (float)(rows + cols) / 16.f;   // the filters' (csrc/tdr_host_filter.cpp, particle_filter.py)
   hipLaunchKernelGGL(cart_init_list_kernel, dim3(1), dim3(1024), 0, s, (const float*)(st + TDR_ST_HAVE_INIT * cap),
                      (const int32_t*)nullptr, n, list, count);
   LAUNCH_CHECK("cart_init_list");

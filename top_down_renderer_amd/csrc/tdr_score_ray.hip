@@ -385,8 +385,6 @@ __global__ __launch_bounds__(256) void score_polar_ray_kernel(RayArgs a) {
 
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-extern "C" size_t tdr_cmap_plane_offset_words(int ncls, int rows, int cols);
-extern "C" size_t tdr_cmap_plane_words(int ncls, int rows, int cols);
 
 bool tdr_ray_map_ok(const tdr_map_desc* map) {
   return map->crec && map->dict && map->cwords == tdr_cmap_words(map->ncls) && map->dict_n > 0 &&

@@ -1090,9 +1090,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-extern "C" size_t tdr_cmap_tile_words(int ncls, int rows, int cols);   // tdr_cmap.hip
-extern "C" size_t tdr_cmap_plane_offset_words(int ncls, int rows, int cols);
-extern "C" size_t tdr_cmap_plane_words(int ncls, int rows, int cols);
 // The span (TdrConfig::su_span): fixed by the config call, or — the default — tuned while running.
 // Which span is fastest depends on the particle set (how far the same-heading neighbours of a moderately dense particle
 // lie apart): measured on MI355X, config 2 wants 8 (7.00 against 7.29 ms at 24), config 5 wants 16 (15.9 against 17.7 at 8),

@@ -33,8 +33,7 @@
 #include <vector>
 
 #include "tdr.h"
-
-extern "C" int tdr_set_error(int code, const char* msg);   // tdr_core.hip
+#include "tdr_internal.h"
 
 namespace {
 
@@ -829,7 +828,7 @@ int parse_file(const char* path, Out& out) {
 
 }  // namespace
 
-// internal (tdr_host.cpp): the parsed map
+// internal (tdr_host_map_load.cpp): the parsed map
 int tdr_svg_parse_internal(const char* path, float* w, float* h, std::vector<uint32_t>& keys, std::vector<int64_t>& offs,
                            std::vector<float>& verts) {
   try {
