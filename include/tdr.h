@@ -1171,6 +1171,115 @@ int tdr_filter_set_viz_background(tdr_filter* f, const uint8_t* bgr_host, int H,
 int tdr_filter_visualize(tdr_filter* f, float pub_scale, const int32_t* extra_arrows, int m, uint8_t* out_bgr_host,
                          int64_t capacity, int* out_h, int* out_w);
 
+/* The batched particle picture: the three stages over a device array of jobs, one launch each for all of them (a job is
+ * one picture; blockIdx.y is the job, and a block beyond its job's extent leaves at once).  A job's planes are its own,
+ * cleared by the caller.  segs is the job's own list of n_segs segments; best (device {x, y, theta} of the
+ * max-likelihood state, or NULL) adds that state's heading arrow as three further segments computed in the launch, so
+ * that the host needs no read-back to build the overlay: pass the rest of layer 4 and layer 5 in segs
+ * (tdr_viz_overlay_host with best = NULL).  The arrow is the tabulated Arrow(-dir, dir) moved to pt, which equals
+ * Arrow(pt - dir, pt + dir): the tips' lrint arguments lie at least 0.04 from a half for every dir, and |pt| <= 2^20.
+ * max_n / max_segs / max_out_pixels: the largest n / n_segs / out_h * out_w of the k jobs (they size the grid; a job
+ * beyond them is drawn in part only).  k >= 1; no allocation, no sync. */
+typedef struct tdr_viz_job {
+  const float* st;           /* [7][cap] device states */
+  int64_t cap, n;
+  int32_t H, W;              /* the background's size */
+  uint32_t* planes;          /* 4 * tdr_viz_plane_words(H, W), 16-byte aligned */
+  const uint8_t* background; /* [H][W][3] device */
+  const int32_t* segs;       /* [n_segs][5] device */
+  const float* best;         /* device {x, y, theta}, or NULL */
+  int32_t n_segs, pad;
+  int32_t out_h, out_w;
+  uint8_t* out;              /* [out_h][out_w][3] device */
+} tdr_viz_job;
+int tdr_k_viz_particles_jobs(const tdr_viz_job* jobs_dev, int k, int64_t max_n, void* stream);
+int tdr_k_viz_segments_jobs(const tdr_viz_job* jobs_dev, int k, int max_segs, void* stream);
+int tdr_k_viz_compose_jobs(const tdr_viz_job* jobs_dev, int k, int64_t max_out_pixels, void* stream);
+/* tdr_batch_visualize: for every i the bytes, *out_h and *out_w of tdr_filter_visualize(f[i], pub_scale, req[i]...).
+ * Each filter over its own background (sizes may differ).  The overlays are built on the host and uploaded once; the
+ * planes (one arena owned by the calling thread) are cleared with one memset; particles, segments and compose are one
+ * launch each on `stream`, which first waits for every filter's own stream; each picture is then copied straight into
+ * its request's image and the call waits once, at the end.  Filters with 0 particles, polar and Cartesian filters alike; no filter is changed.  A request with
+ * out_bgr_host = NULL only gets its size.  Refused with TDR_ERR_ARG before any device work, every output (images and
+ * sizes) untouched: k < 1, a null array or entry, a filter twice, a sharded filter, a filter without a background, an
+ * invalid published size, bad arrows, too little room in any request.
+ * Out of scope: sharded filters, one shared device background for several filters, one "fleet" image of all robots. */
+typedef struct tdr_viz_request {
+  const int32_t* extra_arrows;   /* [m][4], may be NULL when m = 0 */
+  int32_t m, pad;
+  uint8_t* out_bgr_host;
+  int64_t capacity;              /* bytes at out_bgr_host */
+  int32_t out_h, out_w;          /* set by the call */
+} tdr_viz_request;
+int tdr_batch_visualize(tdr_filter* const* f, int k, float pub_scale, tdr_viz_request* req, void* stream);
+
+/* ---- the scan picture: the node's two scan images and its map background on the device (src/top_down_render.cpp:246-305,
+ * :584) ---------------------------------------------------------------------------------------------------
+ * All images are BGR8.  `imgs` is the render layout [ncls][rows*cols], column-major: element (i, j) at i + j*rows.
+ *   Scan picture (TopDownRender::visualize, :275-305).  The reference builds map_mat(cols, rows) and writes .at(idy, idx)
+ *     from cls(idx, idy): the picture is [cols][rows][3] (height = cols, width = rows) and its pixel p = y*rows + x reads
+ *     imgs[c][p], the same linear index.  Per pixel, the reference's comparisons as written: best = -inf, worst = +inf,
+ *     best_cls = 255; for c = 0 .. ncls-1 in order, v = imgs[c][p]: if (v >= best) { best = v; best_cls = c; }
+ *     if (v < worst) worst = v.  A NaN takes part in nothing.  label = 255 when best == worst (all classes equal, all zero
+ *     included; always when ncls = 1, or when one class is not NaN); label = 255 when best_cls is still 255 (every value
+ *     NaN: the reference indexes out of bounds there); otherwise label = unflatten[best_cls] & 255 (the reference stores
+ *     the int into a uint8_t).  Ties go to the LAST class at the maximum (the >=).  The pixel is lut_bgr[label], lut_bgr
+ *     the caller's table of 256 BGR triplets: semantics_manager's ind2Color(Mat, Mat) is not in the reference tree, so
+ *     the table's contents are the caller's.  Parity unpinned.
+ *   Analog picture (visualizeAnalog, :266-273).  One float layer in the same transposed view: a = (float)(255.0 /
+ *     (double)scale), t = v * a in float32 without contraction, grey = lrintf(t) (half to even) clamped to [0, 255], and 0
+ *     when t is NaN, infinite or outside [-2^31, 2^31) (the project's x86-conversion rule: what cvRound + saturate_cast
+ *     give there).  The pixel is (g, g, g).  scale finite and > 0.  A DEFINITION: OpenCV is absent, parity unpinned.
+ *   Label picture (aerialMapCallback, :584).  out[p] = lut_bgr[labels[p]] for a uint8 [H][W] label image.
+ * Layer 1 (csrc/tdr_scan_viz.hip): device images, host tables (they travel in the kernel arguments), no allocation, no
+ * sync.  out_bgr: 3 * npix bytes.  The _jobs forms run k pictures in one launch over a device array of jobs that share
+ * the tables; max_npix is the largest npix of the jobs (it sizes the grid; every job is drawn whole whatever it is).
+ * Refused with TDR_ERR_ARG before any launch: null pointers, ncls outside 1..TDR_MAX_CLASSES, npix < 1, a scale that is
+ * not finite and > 0, k < 1.  A job with bad sizes (ncls above the n_unflatten entries of the table included) writes
+ * nothing. */
+typedef struct tdr_scan_picture_job {
+  const float* imgs;   /* [ncls][npix] device (the analog form: one layer [npix]) */
+  int32_t ncls, pad;
+  int64_t npix;
+  uint8_t* out_bgr;    /* [npix][3] device */
+} tdr_scan_picture_job;
+typedef struct tdr_label_picture_job {
+  const uint8_t* labels;   /* [npix] device */
+  int64_t npix;
+  uint8_t* out_bgr;        /* [npix][3] device */
+} tdr_label_picture_job;
+int tdr_k_scan_picture(const float* imgs, int ncls, int64_t npix, const int32_t* unflatten_host,
+                       const uint8_t* lut_bgr_host, uint8_t* out_bgr, void* stream);
+int tdr_k_analog_picture(const float* img, int64_t npix, float scale, uint8_t* out_bgr, void* stream);
+int tdr_k_label_picture(const uint8_t* labels, int64_t npix, const uint8_t* lut_bgr_host, uint8_t* out_bgr, void* stream);
+int tdr_k_scan_picture_jobs(const tdr_scan_picture_job* jobs_dev, int k, int64_t max_npix, const int32_t* unflatten_host,
+                            int n_unflatten, const uint8_t* lut_bgr_host, void* stream);
+int tdr_k_analog_picture_jobs(const tdr_scan_picture_job* jobs_dev, int k, int64_t max_npix, float scale, void* stream);
+int tdr_k_label_picture_jobs(const tdr_label_picture_job* jobs_dev, int k, int64_t max_npix, const uint8_t* lut_bgr_host,
+                             void* stream);
+/* Layer 2.  tdr_renderer_visualize draws the scan picture of the renderer's last semantic render (polar or Cartesian,
+ * tdr_renderer_render or tdr_batch_render_polar) from the device images and reads it back: out_bgr_host [cols][rows][3],
+ * `capacity` bytes; *out_h = cols and *out_w = rows are set whenever the renderer has a render; out_bgr_host = NULL only
+ * asks for them (and needs no tables).  unflatten: the renderer's ncls entries.  tdr_renderer_visualize_analog: layer `cls` of the same render.
+ * Refused with TDR_ERR_ARG, the output untouched: no render, too little room, cls outside the render, a bad scale.
+ * tdr_scan_picture_host: the scan picture of images the caller holds on the host (the geometric render's two layers,
+ * the node's std::vector<Eigen::ArrayXXf>): an upload, one launch, a read-back.
+ * tdr_filter_set_viz_background_labels leaves the filter where tdr_filter_set_viz_background leaves it given the
+ * host-coloured image of the same labels (uint8 [H][W]): one byte a cell is uploaded and coloured on the device; the
+ * same size limits.
+ * tdr_batch_scan_pictures: the k scan pictures into out_bgr_host [k][cols][rows][3] with one launch, one device-to-host
+ * copy and one wait.  Refused before any device work: k < 1, a null array or entry, a renderer twice, a renderer
+ * without a render, renders of different shapes. */
+int tdr_renderer_visualize(const tdr_renderer* r, const int32_t* unflatten, const uint8_t* lut_bgr, uint8_t* out_bgr_host,
+                           int64_t capacity, int* out_h, int* out_w);
+int tdr_renderer_visualize_analog(const tdr_renderer* r, int cls, float scale, uint8_t* out_bgr_host, int64_t capacity,
+                                  int* out_h, int* out_w);
+int tdr_scan_picture_host(const float* imgs_host, int ncls, int rows, int cols, const int32_t* unflatten,
+                          const uint8_t* lut_bgr, uint8_t* out_bgr_host);
+int tdr_filter_set_viz_background_labels(tdr_filter* f, const uint8_t* labels_host, int H, int W, const uint8_t* lut_bgr);
+int tdr_batch_scan_pictures(const tdr_renderer* const* r, int k, const int32_t* unflatten, const uint8_t* lut_bgr,
+                            uint8_t* out_bgr_host, void* stream);
+
 /* internal: lets the handle layer (csrc/tdr_host_*.cpp) report through tdr_last_error() */
 int tdr_set_error(int code, const char* msg);
 

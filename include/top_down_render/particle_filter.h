@@ -25,6 +25,7 @@
 
 #include "top_down_render/active_localizer.h"   // like the reference's header (particle_filter.h:5)
 #include "top_down_render/particle_viz_device.h"
+#include "top_down_render/scan_viz_device.h"
 #include "top_down_render/scan_renderer.h"
 #include "top_down_render/state_particle.h"
 
@@ -231,6 +232,9 @@ class ParticleFilter {
   // for a sharded filter.  The vector overload returns the bytes [out_h][out_w][3].
   template <class MatT = cv::Mat>
   void setVizBackground(const MatT& bgr) { tdr_viz::setBackground(f_, bgr); }
+  // ... from the label image the node colours (aerialMapCallback, :584): one byte a cell goes up, lut colours it on the device
+  template <class MatT = cv::Mat>
+  void setVizBackground(const MatT& labels, const SemanticColorLut& lut) { tdr_viz::setBackgroundLabels(f_, labels, lut); }
   template <class MatT = cv::Mat>
   void renderViz(MatT& out, float pub_scale, const std::vector<std::array<int, 4>>& arrows = {}) {
     tdr_viz::render(f_, out, pub_scale, arrows);

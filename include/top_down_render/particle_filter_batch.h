@@ -76,6 +76,19 @@ class ParticleFilterBatch {
     if (tdr_batch_compute_gmm(handles.data(), (int)handles.size(), stream) != TDR_OK)
       throw std::runtime_error(std::string("ParticleFilterBatch::computeGMM: ") + tdr_last_error());
   }
+  // renderViz(out, h, w, pub_scale, arrows[k]) of every filter through tdr_batch_visualize: one launch per stage, one
+  // read-back and one wait for the batch, each filter over its own background.  arrows: empty, or one list per filter.
+  // Throws on a refused batch (a null or repeated filter, a sharded one, one without a background) before any device work.
+  void renderViz(const std::vector<ParticleFilter*>& filters, float pub_scale,
+                 const std::vector<std::vector<std::array<int, 4>>>& arrows, std::vector<tdr_viz::Image>& outs,
+                 void* stream = nullptr) {
+    std::vector<tdr_filter*> handles(filters.size(), nullptr);
+    for (size_t i = 0; i < filters.size(); i++) {
+      if (!filters[i]) throw std::invalid_argument("ParticleFilterBatch::renderViz: null filter");
+      handles[i] = filters[i]->handle();
+    }
+    tdr_viz::renderBatch(handles, pub_scale, arrows, outs, stream);
+  }
   // tdr_config_tuning("batch_init_search"), process-wide: with true a filter that may still hold a particle without a
   // heading — a cold start (init_pos_deg_theta = inf), a gated filter (force_on_map, unknown scale) — joins the batch, its
   // 40-rotation search part of the batch's scoring stage, same bits; false (the default): its standalone calls inside step()

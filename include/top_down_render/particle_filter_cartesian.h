@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "top_down_render/particle_viz_device.h"
+#include "top_down_render/scan_viz_device.h"
 #include "top_down_render/scan_renderer.h"
 #include "top_down_render/state_particle.h"
 #include "top_down_render/top_down_map.h"
@@ -80,6 +81,9 @@ class ParticleFilterCartesian {
   // vector overload returns the bytes [out_h][out_w][3].
   template <class MatT = cv::Mat>
   void setVizBackground(const MatT& bgr) { tdr_viz::setBackground(f_, bgr); }
+  // ... from the label image the node colours (aerialMapCallback, :584): one byte a cell goes up, lut colours it on the device
+  template <class MatT = cv::Mat>
+  void setVizBackground(const MatT& labels, const SemanticColorLut& lut) { tdr_viz::setBackgroundLabels(f_, labels, lut); }
   template <class MatT = cv::Mat>
   void renderViz(MatT& out, float pub_scale, const std::vector<std::array<int, 4>>& arrows = {}) {
     tdr_viz::render(f_, out, pub_scale, arrows);

@@ -11,6 +11,7 @@
 
 #include "tdr.h"
 #include "top_down_render/tdr_compat.h"
+#include "top_down_render/scan_viz_device.h"
 
 typedef pcl::PointXYZI PointType;
 
@@ -35,6 +36,33 @@ class ScanRenderer {
   // cloud.  (Commented out at the reference's call site, src/top_down_render.cpp:540; part of the class surface.)
   void renderGeometricTopDown(const pcl::PointCloud<PointType>::ConstPtr& cloud, float res, std::vector<Eigen::ArrayXXf>& imgs) {
     render_geo(0, cloud, res, 1.f, imgs);
+  }
+  // --- beyond the reference's surface: the pictures of the last semantic render, drawn from the device images
+  // (include/tdr.h, "the scan picture").  renderViz is TopDownRender::visualize (src/top_down_render.cpp:275-305) without
+  // the download of the class images: img becomes [cols][rows] BGR.  renderVizAnalog is visualizeAnalog (:266-273) of one
+  // class layer.  Throw when the renderer has no render.
+  template <class MatT = cv::Mat>
+  void renderViz(const std::vector<int>& unflatten_lut, const SemanticColorLut& lut, MatT& img) const {
+    int h = 0, w = 0;
+    tdr_viz::rendererPictureSize(r_, h, w);
+    tdr_viz::rendererPicture(r_, unflatten_lut, lut, tdr_viz::pictureTarget(img, h, w, "renderViz"), h, w);
+  }
+  void renderViz(const std::vector<int>& unflatten_lut, const SemanticColorLut& lut, std::vector<uint8_t>& out, int& out_h,
+                 int& out_w) const {
+    tdr_viz::rendererPictureSize(r_, out_h, out_w);
+    out.resize((size_t)3 * out_h * out_w);
+    tdr_viz::rendererPicture(r_, unflatten_lut, lut, out.data(), out_h, out_w);
+  }
+  template <class MatT = cv::Mat>
+  void renderVizAnalog(int cls, float scale, MatT& img) const {
+    int h = 0, w = 0;
+    tdr_viz::rendererAnalogSize(r_, cls, scale, h, w);
+    tdr_viz::rendererAnalog(r_, cls, scale, tdr_viz::pictureTarget(img, h, w, "renderVizAnalog"), h, w);
+  }
+  void renderVizAnalog(int cls, float scale, std::vector<uint8_t>& out, int& out_h, int& out_w) const {
+    tdr_viz::rendererAnalogSize(r_, cls, scale, out_h, out_w);
+    out.resize((size_t)3 * out_h * out_w);
+    tdr_viz::rendererAnalog(r_, cls, scale, out.data(), out_h, out_w);
   }
   const tdr_renderer* handle() const { return r_; }  // device-resident last render, for ParticleFilter::update
   tdr_renderer* handle() { return r_; }              // ... and the target of a batched render (tdr_batch_render_polar)

@@ -11,7 +11,8 @@
 //
 // Every core ends where cores[i]->takeStep(...) with setDeviceScan(true) leaves it: filter states, weights and generator
 // position, PoseEst, currentRangeScale, lastRes, isConverged.  One difference: the host topDown() images are not filled
-// (the renders stay on the device; ScanRenderer::handle + tdr_renderer_get_render reads them).
+// (the renders stay on the device; ScanRenderer::handle + tdr_renderer_get_render reads them, and renderPictures draws the
+// robots' scan pictures and particle pictures from the device data in two batched calls).
 #pragma once
 
 #include <stdexcept>
@@ -91,6 +92,40 @@ class TopDownRenderCoreBatch {
     }
     batch_.computeGMM(due, stream);   // one mixture fit for the cores whose step is due (Config::gmm_every)
     return true;
+  }
+  // The two per-scan pictures of every core after a takeStep (publishSemanticTopDown, :246-254, and the particle picture,
+  // :430-449): tdr_batch_scan_pictures over the cores' renderers and ParticleFilterBatch::renderViz over their filters
+  // (each over its own background, ParticleFilter::setVizBackground).  scan_pictures[i] is [range_bins][theta_bins] BGR.
+  // arrows: empty, or one list per core.  Throws on a refused call; takeStep itself does not draw.
+  void renderPictures(const std::vector<TopDownRenderCore*>& cores, const std::vector<int>& unflatten_lut,
+                      const SemanticColorLut& lut, float pub_scale, const std::vector<std::vector<std::array<int, 4>>>& arrows,
+                      std::vector<tdr_viz::Image>& scan_pictures, std::vector<tdr_viz::Image>& particle_pictures,
+                      void* stream = nullptr) {
+    const size_t k = cores.size();
+    if (k < 1) throw std::invalid_argument("TopDownRenderCoreBatch::renderPictures: no core");
+    std::vector<const tdr_renderer*> rs(k);
+    std::vector<ParticleFilter*> filters(k);
+    for (size_t i = 0; i < k; i++) {
+      if (!cores[i] || !cores[i]->filter_ || !cores[i]->renderer_)
+        throw std::invalid_argument("TopDownRenderCoreBatch::renderPictures: core " + std::to_string(i) + " is null or not initialised");
+      rs[i] = static_cast<const ScanRenderer*>(cores[i]->renderer_)->handle();
+      filters[i] = cores[i]->filter_;
+    }
+    int h = 0, w = 0;
+    tdr_viz::rendererPictureSize(rs[0], h, w);   // (the batch call refuses renders of different shapes)
+    const std::vector<int32_t> unf = tdr_viz::unflattenTable(unflatten_lut, cores[0]->map_->numClasses(), "renderPictures");
+    const std::array<uint8_t, 768> table = tdr_viz::colourTable(lut);
+    const size_t pic = (size_t)3 * h * w;
+    std::vector<uint8_t> all(pic * k);
+    if (tdr_batch_scan_pictures(rs.data(), (int)k, unf.data(), table.data(), all.data(), stream) != TDR_OK)
+      throw std::runtime_error(std::string("TopDownRenderCoreBatch::renderPictures: ") + tdr_last_error());
+    scan_pictures.resize(k);
+    for (size_t i = 0; i < k; i++) {
+      scan_pictures[i].h = h;
+      scan_pictures[i].w = w;
+      scan_pictures[i].bgr.assign(all.begin() + pic * i, all.begin() + pic * (i + 1));
+    }
+    batch_.renderViz(filters, pub_scale, arrows, particle_pictures, stream);
   }
   // filters of the last step that took the batched path / their standalone calls (ParticleFilterBatch)
   int lastBatched() const { return batch_.lastBatched(); }

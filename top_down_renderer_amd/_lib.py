@@ -57,6 +57,29 @@ class BatchCloudC(C.Structure):
     _fields_ = [("pts", C.c_void_p), ("stride", C.c_int), ("ioff", C.c_int), ("n", C.c_int64), ("res", C.c_float)]
 
 
+class VizJobC(C.Structure):
+    """tdr_viz_job: one picture of a batched particle-picture launch."""
+    _fields_ = [("st", C.c_void_p), ("cap", C.c_int64), ("n", C.c_int64), ("H", C.c_int32), ("W", C.c_int32),
+                ("planes", C.c_void_p), ("background", C.c_void_p), ("segs", C.c_void_p), ("best", C.c_void_p),
+                ("n_segs", C.c_int32), ("pad", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32), ("out", C.c_void_p)]
+
+
+class VizRequestC(C.Structure):
+    """tdr_viz_request: one filter's share of a tdr_batch_visualize."""
+    _fields_ = [("extra_arrows", C.c_void_p), ("m", C.c_int32), ("pad", C.c_int32), ("out_bgr_host", C.c_void_p),
+                ("capacity", C.c_int64), ("out_h", C.c_int32), ("out_w", C.c_int32)]
+
+
+class ScanPictureJobC(C.Structure):
+    """tdr_scan_picture_job: one picture of a batched scan / analog picture launch."""
+    _fields_ = [("imgs", C.c_void_p), ("ncls", C.c_int32), ("pad", C.c_int32), ("npix", C.c_int64), ("out_bgr", C.c_void_p)]
+
+
+class LabelPictureJobC(C.Structure):
+    """tdr_label_picture_job: one picture of a batched label picture launch."""
+    _fields_ = [("labels", C.c_void_p), ("npix", C.c_int64), ("out_bgr", C.c_void_p)]
+
+
 class PoseStatsC(C.Structure):
     """tdr_pose_stats: one filter's result of a tdr_batch_pose."""
     _fields_ = [("mean", C.c_float * 4), ("cov", C.c_float * 16), ("scale", C.c_float), ("n", C.c_int64)]
@@ -304,6 +327,21 @@ SIGNATURES = {
     "tdr_k_viz_compose": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "tdr_filter_set_viz_background": (_i, [_vp, _vp, _i, _i]),
     "tdr_filter_visualize": (_i, [_vp, _f, _vp, _i, _vp, _i64, C.POINTER(_i), C.POINTER(_i)]),
+    "tdr_k_viz_particles_jobs": (_i, [_vp, _i, _i64, _vp]),
+    "tdr_k_viz_segments_jobs": (_i, [_vp, _i, _i, _vp]),
+    "tdr_k_viz_compose_jobs": (_i, [_vp, _i, _i64, _vp]),
+    "tdr_batch_visualize": (_i, [_vp, _i, _f, _vp, _vp]),
+    "tdr_k_scan_picture": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp]),
+    "tdr_k_analog_picture": (_i, [_vp, _i64, _f, _vp, _vp]),
+    "tdr_k_label_picture": (_i, [_vp, _i64, _vp, _vp, _vp]),
+    "tdr_k_scan_picture_jobs": (_i, [_vp, _i, _i64, _vp, _i, _vp, _vp]),
+    "tdr_k_analog_picture_jobs": (_i, [_vp, _i, _i64, _f, _vp]),
+    "tdr_k_label_picture_jobs": (_i, [_vp, _i, _i64, _vp, _vp]),
+    "tdr_renderer_visualize": (_i, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i), C.POINTER(_i)]),
+    "tdr_renderer_visualize_analog": (_i, [_vp, _i, _f, _vp, _i64, C.POINTER(_i), C.POINTER(_i)]),
+    "tdr_scan_picture_host": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "tdr_filter_set_viz_background_labels": (_i, [_vp, _vp, _i, _i, _vp]),
+    "tdr_batch_scan_pictures": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "tdr_set_error": (_i, [_i, C.c_char_p]),
     "tdr_locality_tmp_ints": (C.c_size_t, [_i64, _i, _i]),
     "tdr_locality_pose_tmp_ints": (C.c_size_t, [_i64]),

@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BatchCloudC, BatchInputC, FilterParamsC, PoseStatsC, check
+from ._lib import BatchCloudC, BatchInputC, FilterParamsC, PoseStatsC, VizRequestC, check
 
 _vp = C.c_void_p
 STATE_DTYPE = np.dtype([("init_x_px", "<f4"), ("init_y_px", "<f4"), ("dx_m", "<f4"), ("dy_m", "<f4"), ("theta", "<f4"),
@@ -92,10 +92,36 @@ class Renderer:
         check(self.L.tdr_renderer_get_render(self.h, _ptr(img), _ptr(pk)))
         return np.ascontiguousarray(np.transpose(img, (0, 2, 1))), pk
 
+    def picture(self, unflatten, lut_bgr):
+        """The scan picture of the last render (tdr_renderer_visualize): a (cols, rows, 3) uint8 BGR array."""
+        unf, lut = _picture_tables(unflatten, lut_bgr, self._shape[0] if self._shape else 0)
+        oh, ow = C.c_int(), C.c_int()
+        check(self.L.tdr_renderer_visualize(self.h, _ptr(unf), _ptr(lut), None, 0, C.byref(oh), C.byref(ow)))
+        out = np.zeros((oh.value, ow.value, 3), np.uint8)
+        check(self.L.tdr_renderer_visualize(self.h, _ptr(unf), _ptr(lut), _ptr(out), out.size, C.byref(oh), C.byref(ow)))
+        return out
+
+    def picture_analog(self, cls, scale):
+        """visualizeAnalog of class layer `cls` of the last render (tdr_renderer_visualize_analog)."""
+        oh, ow = C.c_int(), C.c_int()
+        check(self.L.tdr_renderer_visualize_analog(self.h, int(cls), C.c_float(scale), None, 0, C.byref(oh), C.byref(ow)))
+        out = np.zeros((oh.value, ow.value, 3), np.uint8)
+        check(self.L.tdr_renderer_visualize_analog(self.h, int(cls), C.c_float(scale), _ptr(out), out.size, C.byref(oh),
+                                                   C.byref(ow)))
+        return out
+
     def __del__(self):
         if getattr(self, "h", None):
             self.L.tdr_renderer_destroy(self.h)
             self.h = None
+
+
+def _picture_tables(unflatten, lut_bgr, ncls):
+    unf = np.ascontiguousarray(unflatten, np.int32).ravel()
+    lut = np.ascontiguousarray(lut_bgr, np.uint8).ravel()
+    if unf.size < ncls or lut.size != 768:
+        raise ValueError(f"pictures: unflatten needs {ncls} entries (has {unf.size}), the colour table 256 BGR triplets")
+    return unf, lut
 
 
 class FilterHandle:
@@ -179,6 +205,31 @@ class FilterHandle:
         means, covs = np.zeros((_lib.GMM_MAX_K, 3), np.float32), np.zeros((_lib.GMM_MAX_K, 9), np.float32)
         check(self.L.tdr_filter_get_gmm(self.h, _lib.GMM_MAX_K, C.byref(k), _ptr(means), _ptr(covs)))
         return means[: k.value].copy(), covs[: k.value].reshape(-1, 3, 3).copy()
+
+    def set_viz_background(self, bgr=None, labels=None, lut=None):
+        """The picture's background: bgr (H, W, 3) uint8, or labels (H, W) uint8 coloured on the device through lut
+        (256 BGR triplets; tdr_filter_set_viz_background_labels)."""
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, np.uint8)
+            lut = np.ascontiguousarray(lut, np.uint8).ravel()
+            if labels.ndim != 2 or lut.size != 768:
+                raise ValueError("set_viz_background: labels (H, W) and 256 BGR triplets")
+            check(self.L.tdr_filter_set_viz_background_labels(self.h, _ptr(labels), labels.shape[0], labels.shape[1], _ptr(lut)))
+            return
+        bgr = np.ascontiguousarray(bgr, np.uint8)
+        if bgr.ndim != 3 or bgr.shape[2] != 3:
+            raise ValueError("set_viz_background: a (H, W, 3) BGR image")
+        check(self.L.tdr_filter_set_viz_background(self.h, _ptr(bgr), bgr.shape[0], bgr.shape[1]))
+
+    def visualize(self, pub_scale, arrows=None):
+        """The particle picture (tdr_filter_visualize): an (out_h, out_w, 3) uint8 array."""
+        arr = None if arrows is None or len(arrows) == 0 else np.ascontiguousarray(arrows, np.int32).reshape(-1, 4)
+        m, ap = (0, None) if arr is None else (len(arr), _ptr(arr))
+        oh, ow = C.c_int(), C.c_int()
+        check(self.L.tdr_filter_visualize(self.h, C.c_float(pub_scale), ap, m, None, 0, C.byref(oh), C.byref(ow)))
+        out = np.zeros((oh.value, ow.value, 3), np.uint8)
+        check(self.L.tdr_filter_visualize(self.h, C.c_float(pub_scale), ap, m, _ptr(out), out.size, C.byref(oh), C.byref(ow)))
+        return out
 
     def step_count(self):
         """The updates the filter has made (tdr_filter_step_count)."""
@@ -307,6 +358,44 @@ def pose_batch(filters, stream=None):
     return mean, cov, np.array([o.scale for o in out[:k]], np.float32), np.array([o.n for o in out[:k]], np.int64)
 
 
+def scan_pictures_batch(renderers, unflatten, lut_bgr, stream=None):
+    """Renderer.picture of every renderer in one tdr_batch_scan_pictures (one launch, one copy, one wait): a
+    (k, cols, rows, 3) uint8 array.  The renders must share one shape."""
+    L = _lib.load()
+    k = len(renderers)
+    shape = renderers[0]._shape if k and renderers[0]._shape else (0, 0, 0)
+    unf, lut = _picture_tables(unflatten, lut_bgr, shape[0])
+    arr = (_vp * max(k, 1))(*[r.h for r in renderers])
+    out = np.zeros((k, shape[2], shape[1], 3), np.uint8)
+    check(L.tdr_batch_scan_pictures(arr, k, _ptr(unf), _ptr(lut), _ptr(out) if out.size else None,
+                                    _vp(stream) if stream else None))
+    return out
+
+
+def visualize_batch(filters, pub_scale, arrows=None, stream=None):
+    """FilterHandle.visualize of every filter in one tdr_batch_visualize: a list of (out_h, out_w, 3) uint8 arrays.
+    arrows: None, or per filter None / an (m, 4) integer list."""
+    L = _lib.load()
+    k = len(filters)
+    arrows = [None] * k if arrows is None else list(arrows)
+    if len(arrows) != k:
+        raise ValueError("visualize_batch: one arrow list (or None) per filter")
+    arr = (_vp * max(k, 1))(*[f.h for f in filters])
+    req = (VizRequestC * max(k, 1))()
+    keep = []
+    for i, a in enumerate(arrows):
+        if a is not None and len(a):
+            a = np.ascontiguousarray(a, np.int32).reshape(-1, 4)
+            keep.append(a)
+            req[i].extra_arrows, req[i].m = a.ctypes.data, len(a)
+    check(L.tdr_batch_visualize(arr, k, C.c_float(pub_scale), req, _vp(stream) if stream else None))   # the sizes
+    outs = [np.zeros((req[i].out_h, req[i].out_w, 3), np.uint8) for i in range(k)]
+    for i, o in enumerate(outs):
+        req[i].out_bgr_host, req[i].capacity = o.ctypes.data, o.size
+    check(L.tdr_batch_visualize(arr, k, C.c_float(pub_scale), req, _vp(stream) if stream else None))
+    return outs
+
+
 class _PoseView:
     """What TopDownRenderCore.publishPoseEst asks of its filter, answered from one robot's share of a pose_batch; a
     freezeScale goes to the filter, and the scale is read from it again afterwards (the freeze changes it)."""
@@ -380,3 +469,12 @@ class LoopBatch:
         if due:   # one mixture fit for the robots whose step is due (CoreConfig.gmm_every)
             compute_gmm_batch(due, stream)
         return out
+
+    def scan_pictures(self, unflatten, lut_bgr, stream=None):
+        """The robots' scan pictures after a take_step (publishSemanticTopDown of each): (k, nr, nb, 3) uint8."""
+        return scan_pictures_batch(self.renderers, unflatten, lut_bgr, stream)
+
+    def particle_pictures(self, pub_scale, arrows=None, stream=None):
+        """The robots' particle pictures after a take_step, each over its filter's own background
+        (FilterHandle.set_viz_background): a list of (out_h, out_w, 3) uint8 arrays."""
+        return visualize_batch(self.filters, pub_scale, arrows, stream)

@@ -158,6 +158,7 @@ struct tdr_renderer {
   bool render_async = false;
   mutable std::vector<std::pair<hipStream_t, hipEvent_t>> readers;
   mutable size_t n_readers = 0;
+  mutable DevBuf<uint8_t> viz_out;   // the scan picture of the last tdr_renderer_visualize(_analog), before its read-back
   ~tdr_renderer() {
     if (rendered) { (void)hipEventSynchronize(rendered); (void)hipEventDestroy(rendered); }
     for (auto& e : readers) { (void)hipEventSynchronize(e.second); (void)hipEventDestroy(e.second); }
@@ -238,5 +239,6 @@ int rng_to_device(tdr_filter* f);
 int rng_to_host(tdr_filter* f);
 bool rng_device_capable(const tdr_filter* f);
 int filter_global_states(tdr_filter* f, const float** st, int64_t* cap);
+int viz_pub_dim(int dim, float s);   // a published dimension of the particle picture; invalid outside 1 .. 32768
 }  // namespace tdrh
 #endif  // TDR_HOST_H_

@@ -1,6 +1,7 @@
 // tdr_host_batch.cpp — the batched calls on many filters of one map: tdr_batch_step (csrc/tdr_batch.hip) and the two ends
-// of a batched node loop, tdr_batch_render_polar and tdr_batch_pose (csrc/tdr_batch_loop.hip).  Their per-thread
-// staging contexts live here and nowhere else.
+// of a batched node loop, tdr_batch_render_polar and tdr_batch_pose (csrc/tdr_batch_loop.hip), and its pictures,
+// tdr_batch_scan_pictures (csrc/tdr_scan_viz.hip) and tdr_batch_visualize (csrc/tdr_viz.hip).  Their per-thread staging
+// contexts live here and nowhere else.
 #include "tdr_host.h"
 
 // ---- batched filters (tdr_batch_step): many filters on one map, one launch per stage -------------------------------------
@@ -392,6 +393,189 @@ int tdr_batch_pose(tdr_filter* const* f, int k, tdr_pose_stats* out, void* strea
       o.scale = -1.f;
     }
   }
+  return TDR_OK;
+}
+}  // extern "C"
+
+// ---- the pictures of a batched node loop: tdr_batch_scan_pictures, tdr_batch_visualize ------------------------------------
+namespace {
+thread_local StageCtx g_scan_pic_stage, g_viz_stage;
+
+// `s` continues after everything queued on the filters' own streams (tdr_batch_step leaves them after the batch)
+int order_after_filters(tdr_filter* const* f, const std::vector<int>& which, hipStream_t s, const char* who) {
+  std::vector<hipStream_t> streams;
+  for (int i : which) streams.push_back(f[i]->stream);
+  std::sort(streams.begin(), streams.end());
+  streams.erase(std::unique(streams.begin(), streams.end()), streams.end());
+  for (hipStream_t fs : streams) {
+    if (fs == s) continue;
+    hipEvent_t e = nullptr;
+    HTRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    int rc = TDR_OK;
+    if (hipEventRecord(e, fs) != hipSuccess || hipStreamWaitEvent(s, e, 0) != hipSuccess) rc = failh(TDR_ERR_HIP, "%s: stream order", who);
+    (void)hipEventDestroy(e);
+    if (rc != TDR_OK) return rc;
+  }
+  return TDR_OK;
+}
+}  // namespace
+
+extern "C" {
+int tdr_batch_scan_pictures(const tdr_renderer* const* r, int k, const int32_t* unflatten, const uint8_t* lut_bgr,
+                            uint8_t* out_bgr_host, void* stream) {
+  if (k < 1) return failh(TDR_ERR_ARG, "batch_scan_pictures: k = %d, at least one renderer is needed", k);
+  if (k > 65535) return failh(TDR_ERR_ARG, "batch_scan_pictures: k = %d, at most 65535 renderers", k);
+  if (!r || !unflatten || !lut_bgr || !out_bgr_host) return failh(TDR_ERR_ARG, "batch_scan_pictures: null argument");
+  for (int i = 0; i < k; i++)
+    if (!r[i]) return failh(TDR_ERR_ARG, "batch_scan_pictures: renderer %d is null", i);
+  {
+    std::vector<const tdr_renderer*> seen(r, r + k);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+      return failh(TDR_ERR_ARG, "batch_scan_pictures: a renderer appears twice in the batch");
+  }
+  for (int i = 0; i < k; i++)
+    if (!r[i]->have_scan) return failh(TDR_ERR_ARG, "batch_scan_pictures: renderer %d has no render", i);
+  const int ncls = r[0]->ncls, rows = r[0]->rows, cols = r[0]->cols;
+  for (int i = 1; i < k; i++)
+    if (r[i]->ncls != ncls || r[i]->rows != rows || r[i]->cols != cols)
+      return failh(TDR_ERR_ARG, "batch_scan_pictures: renderer %d holds a %dx%dx%d render, renderer 0 a %dx%dx%d one", i,
+                   r[i]->ncls, r[i]->rows, r[i]->cols, ncls, rows, cols);
+  if (ncls > TDR_MAX_CLASSES) return failh(TDR_ERR_ARG, "batch_scan_pictures: %d classes (at most %d)", ncls, TDR_MAX_CLASSES);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t P = (size_t)rows * cols, pic = 3 * P;
+  // staging: [k] jobs; on the device the k pictures follow, consecutive like the caller's array
+  const size_t job_bytes = align64(sizeof(tdr_scan_picture_job) * (size_t)k);
+  StageCtx& B = g_scan_pic_stage;
+  TTRY(B.reserve(job_bytes, job_bytes + pic * k, s));
+  tdr_scan_picture_job* tab = reinterpret_cast<tdr_scan_picture_job*>(B.host);
+  uint8_t* out_dev = reinterpret_cast<uint8_t*>(B.dev.p + job_bytes);
+  for (int i = 0; i < k; i++) {
+    TTRY(renderer_wait_render(r[i], s));
+    tab[i] = tdr_scan_picture_job{r[i]->img.p, ncls, 0, (int64_t)P, out_dev + pic * i};
+  }
+  HTRY(hipMemcpyAsync(B.dev.p, B.host, job_bytes, hipMemcpyHostToDevice, s));
+  HTRY(hipEventRecord(B.uploaded, s));
+  TTRY(tdr_k_scan_picture_jobs(reinterpret_cast<const tdr_scan_picture_job*>(B.dev.p), k, (int64_t)P, unflatten, ncls, lut_bgr, s));
+  for (int i = 0; i < k; i++) TTRY(renderer_note_read(r[i], s));
+  HTRY(hipMemcpyAsync(out_bgr_host, out_dev, pic * k, hipMemcpyDeviceToHost, s));
+  HTRY(hipEventRecord(B.done, s));
+  HTRY(hipEventSynchronize(B.done));   // the one wait of the call
+  return TDR_OK;
+}
+
+int tdr_batch_visualize(tdr_filter* const* f, int k, float pub_scale, tdr_viz_request* req, void* stream) {
+  if (k < 1) return failh(TDR_ERR_ARG, "batch_visualize: k = %d, at least one filter is needed", k);
+  if (k > 65535) return failh(TDR_ERR_ARG, "batch_visualize: k = %d, at most 65535 filters", k);
+  if (!f || !req) return failh(TDR_ERR_ARG, "batch_visualize: null %s array", !f ? "filter" : "request");
+  for (int i = 0; i < k; i++)
+    if (!f[i]) return failh(TDR_ERR_ARG, "batch_visualize: filter %d is null", i);
+  {
+    std::vector<const tdr_filter*> seen(f, f + k);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+      return failh(TDR_ERR_ARG, "batch_visualize: a filter appears twice in the batch");
+  }
+  std::vector<int> oh((size_t)k), ow((size_t)k);
+  for (int i = 0; i < k; i++) {
+    const tdr_filter* g = f[i];
+    const tdr_viz_request& q = req[i];
+    if (g->comm) return failh(TDR_ERR_ARG, "batch_visualize: filter %d is sharded and has no picture (draw from a one-GPU filter)", i);
+    if (g->viz_h < 1) return failh(TDR_ERR_ARG, "batch_visualize: filter %d has no background (tdr_filter_set_viz_background)", i);
+    if (q.m < 0 || (q.m > 0 && !q.extra_arrows) || q.m > (1 << 20))
+      return failh(TDR_ERR_ARG, "batch_visualize: request %d: bad arrows", i);
+    oh[i] = viz_pub_dim(g->viz_h, pub_scale);
+    ow[i] = viz_pub_dim(g->viz_w, pub_scale);
+    if (oh[i] < 1 || ow[i] < 1 || oh[i] > 32768 || ow[i] > 32768)
+      return failh(TDR_ERR_ARG, "batch_visualize: filter %d: scale %g publishes %d x %d pixels (1 .. 32768 a side)", i,
+                   (double)pub_scale, oh[i], ow[i]);
+    const size_t bytes = (size_t)3 * oh[i] * ow[i];
+    if (q.out_bgr_host && (q.capacity < 0 || (size_t)q.capacity < bytes))
+      return failh(TDR_ERR_ARG, "batch_visualize: request %d: the image needs %zu bytes, room for %lld", i, bytes,
+                   (long long)q.capacity);
+  }
+  // layers 4 (without the max-likelihood arrow, which the segments launch adds from the device state) and 5 on the host
+  std::vector<int> drawn;
+  std::vector<std::vector<int32_t>> segs((size_t)k);
+  std::vector<int> nseg((size_t)k, 0);
+  for (int i = 0; i < k; i++) {
+    if (!req[i].out_bgr_host) continue;
+    const tdr_filter* g = f[i];
+    const int kk = (int)(g->gmm_means.size() / 3), cap = TDR_VIZ_MAX_SEGS(kk, req[i].m);
+    segs[i].resize((size_t)5 * cap);
+    TTRY(tdr_viz_overlay_host(g->gmm_means.data(), g->gmm_covs.data(), kk, nullptr, req[i].extra_arrows, req[i].m, g->viz_h,
+                              segs[i].data(), cap, &nseg[i]));
+    drawn.push_back(i);
+  }
+  for (int i = 0; i < k; i++) {
+    req[i].out_h = oh[i];
+    req[i].out_w = ow[i];
+  }
+  const int kd = (int)drawn.size();
+  if (kd == 0) return TDR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  // staging, host and device alike: [kd] jobs, every filter's segments; on the device every picture and the planes follow
+  const size_t job_bytes = align64(sizeof(tdr_viz_job) * (size_t)kd);
+  std::vector<size_t> seg_off((size_t)kd), out_off((size_t)kd), pl_off((size_t)kd);
+  size_t up_bytes = job_bytes;
+  for (int j = 0; j < kd; j++) {
+    seg_off[j] = up_bytes;
+    up_bytes += align64((size_t)5 * nseg[drawn[j]] * sizeof(int32_t));
+  }
+  size_t pic_end = up_bytes;
+  for (int j = 0; j < kd; j++) {
+    out_off[j] = pic_end;
+    pic_end += align64((size_t)3 * oh[drawn[j]] * ow[drawn[j]]);
+  }
+  size_t dev_bytes = pic_end;
+  for (int j = 0; j < kd; j++) {
+    pl_off[j] = dev_bytes;
+    dev_bytes += align64(4 * tdr_viz_plane_words(f[drawn[j]]->viz_h, f[drawn[j]]->viz_w) * sizeof(uint32_t));
+  }
+  StageCtx& B = g_viz_stage;
+  TTRY(B.reserve(up_bytes, dev_bytes, s));
+  TTRY(order_after_filters(f, drawn, s, "batch_visualize"));
+  tdr_viz_job* tab = reinterpret_cast<tdr_viz_job*>(B.host);
+  int64_t max_n = 0, max_out = 0;
+  int max_segs = 0;
+  for (int j = 0; j < kd; j++) {
+    const int i = drawn[j];
+    const tdr_filter* g = f[i];
+    if (nseg[i]) std::memcpy(B.host + seg_off[j], segs[i].data(), (size_t)5 * nseg[i] * sizeof(int32_t));
+    tdr_viz_job& e = tab[j];
+    e = tdr_viz_job{};
+    e.st = g->st.p;
+    e.cap = g->cap;
+    e.n = g->n;
+    e.H = g->viz_h;
+    e.W = g->viz_w;
+    e.planes = reinterpret_cast<uint32_t*>(B.dev.p + pl_off[j]);
+    e.background = g->viz_bg.p;
+    e.segs = reinterpret_cast<const int32_t*>(B.dev.p + seg_off[j]);
+    e.best = g->have_ml ? g->ml_dev.p + 8 : nullptr;
+    e.n_segs = nseg[i];
+    e.out_h = oh[i];
+    e.out_w = ow[i];
+    e.out = reinterpret_cast<uint8_t*>(B.dev.p + out_off[j]);
+    max_n = std::max(max_n, g->n);
+    max_segs = std::max(max_segs, nseg[i]);
+    max_out = std::max(max_out, (int64_t)oh[i] * ow[i]);
+  }
+  const tdr_viz_job* tab_dev = reinterpret_cast<const tdr_viz_job*>(B.dev.p);
+  HTRY(hipMemcpyAsync(B.dev.p, B.host, up_bytes, hipMemcpyHostToDevice, s));
+  HTRY(hipEventRecord(B.uploaded, s));
+  HTRY(hipMemsetAsync(B.dev.p + pic_end, 0, dev_bytes - pic_end, s));
+  TTRY(tdr_k_viz_particles_jobs(tab_dev, kd, max_n, s));
+  TTRY(tdr_k_viz_segments_jobs(tab_dev, kd, max_segs, s));
+  TTRY(tdr_k_viz_compose_jobs(tab_dev, kd, max_out, s));
+  // every picture straight into its request's image: a second copy on the host (one read-back into pinned staging, then
+  // k memcpys) costs more than the launches and waits the batch saves
+  for (int j = 0; j < kd; j++) {
+    const int i = drawn[j];
+    HTRY(hipMemcpyAsync(req[i].out_bgr_host, B.dev.p + out_off[j], (size_t)3 * oh[i] * ow[i], hipMemcpyDeviceToHost, s));
+  }
+  HTRY(hipEventRecord(B.done, s));
+  HTRY(hipEventSynchronize(B.done));   // the one wait of the call
   return TDR_OK;
 }
 }  // extern "C"

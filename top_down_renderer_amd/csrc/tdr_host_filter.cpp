@@ -613,11 +613,32 @@ int tdr_filter_set_viz_background(tdr_filter* f, const uint8_t* bgr_host, int H,
   return TDR_OK;
 }
 
+// ... from the label image the node colours (aerialMapCallback, :584): one byte a cell goes up, the colour table is
+// applied on the device (tdr_k_label_picture); viz_out is the labels' staging
+int tdr_filter_set_viz_background_labels(tdr_filter* f, const uint8_t* labels_host, int H, int W, const uint8_t* lut_bgr) {
+  if (!f || !labels_host || !lut_bgr) return failh(TDR_ERR_ARG, "filter_set_viz_background_labels: null argument");
+  if (H < 11 || W < 11 || H > 32768 || W > 32768)
+    return failh(TDR_ERR_ARG, "filter_set_viz_background_labels: a %d x %d image (11 .. 32768 a side)", H, W);
+  const size_t cells = (size_t)H * W;
+  TTRY(f->viz_bg.resize(3 * cells));
+  TTRY(f->viz_planes.resize(4 * tdr_viz_plane_words(H, W)));
+  HTRY(hipStreamSynchronize(f->stream));   // (an earlier picture may still read the old background, or write viz_out)
+  TTRY(f->viz_out.resize(cells));
+  HTRY(hipMemcpy(f->viz_out.p, labels_host, cells, hipMemcpyHostToDevice));
+  TTRY(tdr_k_label_picture(f->viz_out.p, (int64_t)cells, lut_bgr, f->viz_bg.p, f->stream));
+  HTRY(hipStreamSynchronize(f->stream));
+  f->viz_h = H;
+  f->viz_w = W;
+  return TDR_OK;
+}
+
 // (int)((float)dim * s) as the node computes it (src/top_down_render.cpp:442-444), x86's conversion
-static int viz_pub_dim(int dim, float s) {
+}  // extern "C"
+int tdrh::viz_pub_dim(int dim, float s) {
   const float v = (float)dim * s;
   return (v >= -2147483648.f && v < 2147483648.f) ? (int)v : std::numeric_limits<int>::min();
 }
+extern "C" {
 
 int tdr_filter_visualize(tdr_filter* f, float pub_scale, const int32_t* extra_arrows, int m, uint8_t* out_bgr_host,
                          int64_t capacity, int* out_h, int* out_w) {

@@ -1,5 +1,6 @@
 // tdr_host_renderer.cpp — ScanRenderer(Polar) behind tdr_renderer_*: create, the semantic and the geometric render,
-// the read-back of the last render; and the two event helpers that order other streams against a batched render.
+// the read-back of the last render and its pictures (include/tdr.h, "the scan picture"; kernels in tdr_scan_viz.hip); and
+// the two event helpers that order other streams against a batched render.
 #include "tdr_host.h"
 
 namespace tdrh {
@@ -23,6 +24,25 @@ int renderer_note_read(const tdr_renderer* r, hipStream_t s) {
   return TDR_OK;
 }
 }  // namespace tdrh
+
+// what tdr_renderer_visualize and tdr_renderer_visualize_analog share: the size, the room, the read-back.  `draw` launches
+// the picture of the render into r->viz_out on the null stream.
+template <class Draw>
+static int renderer_picture(const tdr_renderer* r, const char* who, uint8_t* out_bgr_host, int64_t capacity, int* out_h,
+                            int* out_w, Draw draw) {
+  *out_h = r->cols;
+  *out_w = r->rows;
+  if (!out_bgr_host) return TDR_OK;
+  const size_t P = (size_t)r->rows * r->cols, bytes = 3 * P;
+  if (capacity < 0 || (size_t)capacity < bytes)
+    return failh(TDR_ERR_ARG, "%s: the image needs %zu bytes, room for %lld", who, bytes, (long long)capacity);
+  TTRY(r->viz_out.resize(bytes));
+  TTRY(renderer_wait_render(r, nullptr));
+  TTRY(draw((int64_t)P));
+  TTRY(renderer_note_read(r, nullptr));
+  HTRY(hipMemcpy(out_bgr_host, r->viz_out.p, bytes, hipMemcpyDeviceToHost));
+  return TDR_OK;
+}
 
 extern "C" {
 
@@ -106,6 +126,47 @@ int tdr_renderer_get_render(const tdr_renderer* r, float* imgs_out, float* pk_ou
   if (r->render_async) HTRY(hipEventSynchronize(r->rendered));
   if (imgs_out) HTRY(hipMemcpy(imgs_out, r->img.p, P * r->ncls * sizeof(float), hipMemcpyDeviceToHost));
   if (pk_out) HTRY(hipMemcpy(pk_out, r->pk.p, P * tdr_rec_floats(r->ncls) * sizeof(float), hipMemcpyDeviceToHost));
+  return TDR_OK;
+}
+
+// ---- the scan picture ------------------------------------------------------------------------------------------------------
+int tdr_renderer_visualize(const tdr_renderer* r, const int32_t* unflatten, const uint8_t* lut_bgr, uint8_t* out_bgr_host,
+                           int64_t capacity, int* out_h, int* out_w) {
+  if (!r || !out_h || !out_w || (out_bgr_host && (!unflatten || !lut_bgr)))   // (a size query needs no tables)
+    return failh(TDR_ERR_ARG, "renderer_visualize: null argument");
+  if (!r->have_scan) return failh(TDR_ERR_ARG, "renderer_visualize: the renderer has no render");
+  if (r->ncls > TDR_MAX_CLASSES) return failh(TDR_ERR_ARG, "renderer_visualize: %d classes (at most %d)", r->ncls, TDR_MAX_CLASSES);
+  return renderer_picture(r, "renderer_visualize", out_bgr_host, capacity, out_h, out_w, [&](int64_t P) {
+    return tdr_k_scan_picture(r->img.p, r->ncls, P, unflatten, lut_bgr, r->viz_out.p, nullptr);
+  });
+}
+
+int tdr_renderer_visualize_analog(const tdr_renderer* r, int cls, float scale, uint8_t* out_bgr_host, int64_t capacity,
+                                  int* out_h, int* out_w) {
+  if (!r || !out_h || !out_w) return failh(TDR_ERR_ARG, "renderer_visualize_analog: null argument");
+  if (!r->have_scan) return failh(TDR_ERR_ARG, "renderer_visualize_analog: the renderer has no render");
+  if (cls < 0 || cls >= r->ncls) return failh(TDR_ERR_ARG, "renderer_visualize_analog: class %d of %d", cls, r->ncls);
+  if (!(scale > 0.f) || !(scale < std::numeric_limits<float>::infinity()))
+    return failh(TDR_ERR_ARG, "renderer_visualize_analog: scale %g (finite and > 0)", (double)scale);
+  return renderer_picture(r, "renderer_visualize_analog", out_bgr_host, capacity, out_h, out_w, [&](int64_t P) {
+    return tdr_k_analog_picture(r->img.p + (size_t)cls * P, P, scale, r->viz_out.p, nullptr);
+  });
+}
+
+int tdr_scan_picture_host(const float* imgs_host, int ncls, int rows, int cols, const int32_t* unflatten,
+                          const uint8_t* lut_bgr, uint8_t* out_bgr_host) {
+  if (!imgs_host || !unflatten || !lut_bgr || !out_bgr_host) return failh(TDR_ERR_ARG, "scan_picture_host: null argument");
+  if (ncls < 1 || ncls > TDR_MAX_CLASSES || rows < 1 || cols < 1)
+    return failh(TDR_ERR_ARG, "scan_picture_host: bad image shape %dx%dx%d", ncls, rows, cols);
+  if (tdr_device_count() < 1) return failh(TDR_ERR_HIP, "scan_picture_host: no HIP device (there is no CPU fallback)");
+  static thread_local DevBuf<float> img;      // kept between calls: the node draws two of these per scan
+  static thread_local DevBuf<uint8_t> out;
+  const size_t P = (size_t)rows * cols;
+  TTRY(img.resize(P * ncls));
+  TTRY(out.resize(3 * P));
+  HTRY(hipMemcpy(img.p, imgs_host, P * ncls * sizeof(float), hipMemcpyHostToDevice));
+  TTRY(tdr_k_scan_picture(img.p, ncls, (int64_t)P, unflatten, lut_bgr, out.p, nullptr));
+  HTRY(hipMemcpy(out_bgr_host, out.p, 3 * P, hipMemcpyDeviceToHost));
   return TDR_OK;
 }
 

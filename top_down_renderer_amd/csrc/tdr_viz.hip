@@ -88,16 +88,17 @@ const VizStamps& viz_stamps() {
   return tab;
 }
 
-inline int viz_row_words(int W) { return (W + 127) / 128 * 4; }   // whole 16-byte groups
+__host__ __device__ inline int viz_row_words(int W) { return (W + 127) / 128 * 4; }   // whole 16-byte groups
 
 // ---- particles -------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void viz_or_global(uint32_t* p, uint32_t bits) {
   if ((*p & bits) != bits) atomicOr(p, bits);
 }
 
-__global__ __launch_bounds__(256) void viz_particles_kernel(const float* __restrict__ st, int64_t cap, int64_t n, int H,
-                                                            int W, int rw, int64_t pw, uint32_t* planes, int fma,
-                                                            VizStamps tab) {
+// the body of the particles stage for workgroup `blk` of one picture (viz_particles_kernel, viz_particles_jobs_kernel)
+__device__ __forceinline__ void viz_particles_body(const float* __restrict__ st, int64_t cap, int64_t n, int H, int W,
+                                                   int rw, int64_t pw, uint32_t* planes, int fma, const VizStamps& tab,
+                                                   int64_t blk) {
   __shared__ uint32_t s_rows[(VIZ_DIRS * VIZ_ROWS + 1) / 2];
   __shared__ uint32_t s_tile[2][VIZ_TH * VIZ_TW];
   __shared__ int s_org[4];   // per plane: first row, first word of the tile
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(256) void viz_particles_kernel(const float* __restr
   for (int i = tid; i < 2 * VIZ_TH * VIZ_TW; i += 256) (&s_tile[0][0])[i] = 0;
   if (tid < 4) s_org[tid] = INT_MAX;
 
-  const int64_t p = (int64_t)blockIdx.x * 256 + tid;
+  const int64_t p = blk * 256 + tid;
   int kind = -1, cx = 0, cy = 0, di = 0;   // kind 0: arrow, 1: dot
   if (p < n) {
     const float sc = st[TDR_ST_SCALE * cap + p];
@@ -167,6 +168,11 @@ __global__ __launch_bounds__(256) void viz_particles_kernel(const float* __restr
     if (bits) viz_or_global(planes + (int64_t)k * pw + (int64_t)(s_org[2 * k] + t / VIZ_TW) * rw + s_org[2 * k + 1] + t % VIZ_TW, bits);
   }
 }
+__global__ __launch_bounds__(256) void viz_particles_kernel(const float* __restrict__ st, int64_t cap, int64_t n, int H,
+                                                            int W, int rw, int64_t pw, uint32_t* planes, int fma,
+                                                            VizStamps tab) {
+  viz_particles_body(st, cap, n, H, W, rw, pw, planes, fma, tab, blockIdx.x);
+}
 
 // ---- overlay segments ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int64_t viz_min64(int64_t a, int64_t b) { return a < b ? a : b; }
@@ -179,11 +185,8 @@ __device__ __forceinline__ int64_t viz_floordiv(int64_t a, int64_t b) {
 // One workgroup per segment {ax, ay, bx, by, plane}.  Along the segment's major axis one thread per coordinate t (one
 // beyond either end, for the round caps) tests the pixels within -2 .. +3 of the line's floor there: a covered pixel is
 // within 1 of the line at right angles, which is within sqrt(2) along the minor axis.
-__global__ __launch_bounds__(256) void viz_segments_kernel(const int32_t* __restrict__ segs, int H, int W, int rw,
-                                                           int64_t pw, uint32_t* planes) {
-  const int32_t* s = segs + 5 * (int64_t)blockIdx.x;
-  const int64_t ax = s[0], ay = s[1], bx = s[2], by = s[3];
-  const int plane = s[4];
+__device__ __forceinline__ void viz_segment_body(int64_t ax, int64_t ay, int64_t bx, int64_t by, int plane, int H, int W,
+                                                 int rw, int64_t pw, uint32_t* planes) {
   if (plane < 0 || plane > 3) return;
   if (ax < -VIZ_LIM || ax > VIZ_LIM || ay < -VIZ_LIM || ay > VIZ_LIM || bx < -VIZ_LIM || bx > VIZ_LIM || by < -VIZ_LIM ||
       by > VIZ_LIM)
@@ -202,6 +205,11 @@ __global__ __launch_bounds__(256) void viz_segments_kernel(const int32_t* __rest
       if (viz_covered(ax, ay, bx, by, px, py)) viz_or_global(pl + py * rw + (px >> 5), 1u << (px & 31));
     }
   }
+}
+__global__ __launch_bounds__(256) void viz_segments_kernel(const int32_t* __restrict__ segs, int H, int W, int rw,
+                                                           int64_t pw, uint32_t* planes) {
+  const int32_t* s = segs + 5 * (int64_t)blockIdx.x;
+  viz_segment_body(s[0], s[1], s[2], s[3], s[4], H, W, rw, pw, planes);
 }
 
 // ---- compose -----------------------------------------------------------------------------------------------------------
@@ -225,23 +233,26 @@ __device__ __forceinline__ uint32_t viz_pixel(const uint8_t* __restrict__ bg, co
 }
 
 // same size, any width: one thread per pixel
-__global__ __launch_bounds__(256) void viz_compose_copy_kernel(const uint8_t* __restrict__ bg, int H, int W, int rw,
-                                                               int64_t pw, const uint32_t* __restrict__ planes,
-                                                               uint8_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void viz_compose_copy_body(const uint8_t* __restrict__ bg, int H, int W, int rw, int64_t pw,
+                                                      const uint32_t* __restrict__ planes, uint8_t* __restrict__ out,
+                                                      int64_t i) {
   if (i >= (int64_t)H * W) return;
   const uint32_t c = viz_pixel(bg, planes, W, rw, pw, (int)(i / W), (int)(i % W));
   out[3 * i] = (uint8_t)c;
   out[3 * i + 1] = (uint8_t)(c >> 8);
   out[3 * i + 2] = (uint8_t)(c >> 16);
 }
+__global__ __launch_bounds__(256) void viz_compose_copy_kernel(const uint8_t* __restrict__ bg, int H, int W, int rw,
+                                                               int64_t pw, const uint32_t* __restrict__ planes,
+                                                               uint8_t* __restrict__ out) {
+  viz_compose_copy_body(bg, H, W, rw, pw, planes, out, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
 
 // same size, W a multiple of 16 and 16-byte aligned images: one thread per 16 pixels = three 16-byte loads and stores;
 // the eight threads of a 128-pixel group read the same 16 bytes of every plane
-__global__ __launch_bounds__(256) void viz_compose_copy16_kernel(const uint8_t* __restrict__ bg, int H, int W, int rw,
-                                                                 int64_t pw, const uint32_t* __restrict__ planes,
-                                                                 uint8_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void viz_compose_copy16_body(const uint8_t* __restrict__ bg, int H, int W, int rw, int64_t pw,
+                                                        const uint32_t* __restrict__ planes, uint8_t* __restrict__ out,
+                                                        int64_t i) {
   const int g = W / 16;
   if (i >= (int64_t)H * g) return;
   const int y = (int)(i / g), xb = (int)(i % g);
@@ -277,6 +288,11 @@ __global__ __launch_bounds__(256) void viz_compose_copy16_kernel(const uint8_t* 
   dst[1] = b;
   dst[2] = c;
 }
+__global__ __launch_bounds__(256) void viz_compose_copy16_kernel(const uint8_t* __restrict__ bg, int H, int W, int rw,
+                                                                 int64_t pw, const uint32_t* __restrict__ planes,
+                                                                 uint8_t* __restrict__ out) {
+  viz_compose_copy16_body(bg, H, W, rw, pw, planes, out, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
 
 // the taps of output coordinate o on an axis of n_in source and n_out output pixels: s0, s1 and the weight a1 of s1 (of 2048)
 __device__ __forceinline__ void viz_taps(int o, int n_in, int n_out, int& s0, int& s1, int& a1) {
@@ -290,10 +306,9 @@ __device__ __forceinline__ void viz_taps(int o, int n_in, int n_out, int& s0, in
   a1 = (int)rintf(f * 2048.f);
 }
 // another size: one thread per output pixel composes its four taps
-__global__ __launch_bounds__(256) void viz_compose_resize_kernel(const uint8_t* __restrict__ bg, int H, int W, int rw,
-                                                                 int64_t pw, const uint32_t* __restrict__ planes,
-                                                                 int out_h, int out_w, uint8_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void viz_compose_resize_body(const uint8_t* __restrict__ bg, int H, int W, int rw, int64_t pw,
+                                                        const uint32_t* __restrict__ planes, int out_h, int out_w,
+                                                        uint8_t* __restrict__ out, int64_t i) {
   if (i >= (int64_t)out_h * out_w) return;
   int x0, x1, ax1, y0, y1, ay1;
   viz_taps((int)(i % out_w), W, out_w, x0, x1, ax1);
@@ -306,6 +321,93 @@ __global__ __launch_bounds__(256) void viz_compose_resize_kernel(const uint8_t* 
     const uint32_t v = ay0 * (ax0 * ((c00 >> sh) & 0xFFu) + (uint32_t)ax1 * ((c01 >> sh) & 0xFFu)) +
                        (uint32_t)ay1 * (ax0 * ((c10 >> sh) & 0xFFu) + (uint32_t)ax1 * ((c11 >> sh) & 0xFFu));
     out[3 * i + ch] = (uint8_t)((v + (1u << 21)) >> 22);
+  }
+}
+__global__ __launch_bounds__(256) void viz_compose_resize_kernel(const uint8_t* __restrict__ bg, int H, int W, int rw,
+                                                                 int64_t pw, const uint32_t* __restrict__ planes,
+                                                                 int out_h, int out_w, uint8_t* __restrict__ out) {
+  viz_compose_resize_body(bg, H, W, rw, pw, planes, out_h, out_w, out, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// ---- the job-table forms: k pictures in one launch per stage (blockIdx.y = the job) --------------------------------------
+__device__ __forceinline__ bool viz_job_ok(const tdr_viz_job& j) {
+  return j.planes && j.H >= 11 && j.W >= 11 && j.H <= VIZ_MAX_DIM && j.W <= VIZ_MAX_DIM;
+}
+
+__global__ __launch_bounds__(256) void viz_particles_jobs_kernel(const tdr_viz_job* __restrict__ jobs, int fma,
+                                                                 VizStamps tab) {
+  const tdr_viz_job j = jobs[blockIdx.y];
+  if (!viz_job_ok(j) || !j.st || j.n > j.cap || (int64_t)blockIdx.x * 256 >= j.n) return;   // (the whole workgroup leaves)
+  const int rw = viz_row_words(j.W);
+  viz_particles_body(j.st, j.cap, j.n, j.H, j.W, rw, (int64_t)j.H * rw, j.planes, fma, tab, blockIdx.x);
+}
+
+// Arrow(-dir, dir) per dir as offsets from pt: the three segments' {x1, y1, x2, y2} (|offset| <= 10)
+struct VizArrowTab {
+  uint32_t w[(VIZ_DIRS * 12 + 3) / 4];   // int8 offs[VIZ_DIRS][12]
+};
+const VizArrowTab& viz_arrow_tab() {
+  static VizArrowTab tab;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    std::memset(&tab, 0, sizeof(tab));
+    for (int dx = -5; dx <= 5; dx++)
+      for (int dy = -5; dy <= 5; dy++) {
+        int64_t s[12];
+        viz_arrow(-dx, -dy, dx, dy, s);
+        for (int i = 0; i < 12; i++) {
+          const int e = ((dx + 5) * 11 + (dy + 5)) * 12 + i;
+          tab.w[e / 4] |= ((uint32_t)(s[i] & 0xFF)) << (8 * (e & 3));
+        }
+      }
+  });
+  return tab;
+}
+
+// Workgroup x of job y draws segment x of the job's list; the three after the list are the heading arrow of the job's
+// max-likelihood state, by the particle's rule (viz_particles_body) and tdr_viz_overlay_host's range checks.
+__global__ __launch_bounds__(256) void viz_segments_jobs_kernel(const tdr_viz_job* __restrict__ jobs, int fma,
+                                                                VizArrowTab tab) {
+  const tdr_viz_job j = jobs[blockIdx.y];
+  if (!viz_job_ok(j) || j.n_segs < 0) return;
+  const int rw = viz_row_words(j.W);
+  const int64_t pw = (int64_t)j.H * rw;
+  const int i = (int)blockIdx.x;
+  if (i < j.n_segs) {
+    if (!j.segs) return;
+    const int32_t* s = j.segs + 5 * (int64_t)i;
+    viz_segment_body(s[0], s[1], s[2], s[3], s[4], j.H, j.W, rw, pw, j.planes);
+    return;
+  }
+  const int t = i - j.n_segs;
+  if (t >= 3 || !j.best) return;
+  const float x = j.best[0], y = j.best[1], th = j.best[2];
+  if (!(fabsf(th) < INFINITY)) return;
+  const int64_t cx = viz_f2i(x), cy = viz_f2i((float)j.H - y);
+  const int dx = (int)(tdr_libm::cosf_v(th, fma) * 5.f), dy = (int)(-tdr_libm::sinf_v(th, fma) * 5.f);
+  auto in_range = [](int64_t v) { return v >= -VIZ_LIM && v <= VIZ_LIM; };
+  if (!in_range(cx - dx) || !in_range(cy - dy) || !in_range(cx + dx) || !in_range(cy + dy)) return;
+  int64_t q[4];
+  for (int c = 0; c < 4; c++) {
+    const int e = ((dx + 5) * 11 + (dy + 5)) * 12 + 4 * t + c;
+    q[c] = (int64_t)(int8_t)((tab.w[e >> 2] >> (8 * (e & 3))) & 0xFFu) + ((c & 1) ? cy : cx);
+  }
+  viz_segment_body(q[0], q[1], q[2], q[3], 2, j.H, j.W, rw, pw, j.planes);   // (it drops a segment beyond +-VIZ_LIM itself)
+}
+
+__global__ __launch_bounds__(256) void viz_compose_jobs_kernel(const tdr_viz_job* __restrict__ jobs) {
+  const tdr_viz_job j = jobs[blockIdx.y];
+  if (!viz_job_ok(j) || !j.background || !j.out || j.out_h < 1 || j.out_w < 1 || j.out_h > VIZ_MAX_DIM || j.out_w > VIZ_MAX_DIM)
+    return;
+  const int rw = viz_row_words(j.W);
+  const int64_t pw = (int64_t)j.H * rw, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j.out_h == j.H && j.out_w == j.W) {   // the choices of tdr_k_viz_compose
+    if (j.W % 16 == 0 && (((uintptr_t)j.background | (uintptr_t)j.out) & 15) == 0)
+      viz_compose_copy16_body(j.background, j.H, j.W, rw, pw, j.planes, j.out, i);
+    else
+      viz_compose_copy_body(j.background, j.H, j.W, rw, pw, j.planes, j.out, i);
+  } else {
+    viz_compose_resize_body(j.background, j.H, j.W, rw, pw, j.planes, j.out_h, j.out_w, j.out, i);
   }
 }
 
@@ -423,5 +525,38 @@ extern "C" int tdr_k_viz_compose(const uint8_t* background, int H, int W, const 
                        background, H, W, rw, pw, planes, out_h, out_w, out_bgr);
   }
   LAUNCH_CHECK("viz_compose");
+  return TDR_OK;
+}
+
+static int viz_jobs_args(const char* who, const tdr_viz_job* jobs, int k, int64_t extent) {
+  if (!jobs) return fail(TDR_ERR_ARG, "%s: null job array", who);
+  if (k < 1 || k > 65535) return fail(TDR_ERR_ARG, "%s: k = %d (1 .. 65535 jobs)", who, k);
+  if (extent < 0 || cdiv(extent, 256) > INT_MAX) return fail(TDR_ERR_ARG, "%s: bad extent %lld", who, (long long)extent);
+  return TDR_OK;
+}
+
+extern "C" int tdr_k_viz_particles_jobs(const tdr_viz_job* jobs_dev, int k, int64_t max_n, void* stream) {
+  if (int rc = viz_jobs_args("viz_particles_jobs", jobs_dev, k, max_n)) return rc;
+  if (max_n == 0) return TDR_OK;
+  hipLaunchKernelGGL(viz_particles_jobs_kernel, dim3((unsigned)cdiv(max_n, 256), (unsigned)k), dim3(256), 0,
+                     (hipStream_t)stream, jobs_dev, tdr_libm_fma(), viz_stamps());
+  LAUNCH_CHECK("viz_particles_jobs");
+  return TDR_OK;
+}
+
+extern "C" int tdr_k_viz_segments_jobs(const tdr_viz_job* jobs_dev, int k, int max_segs, void* stream) {
+  if (int rc = viz_jobs_args("viz_segments_jobs", jobs_dev, k, max_segs)) return rc;
+  hipLaunchKernelGGL(viz_segments_jobs_kernel, dim3((unsigned)max_segs + 3u, (unsigned)k), dim3(256), 0,
+                     (hipStream_t)stream, jobs_dev, tdr_libm_fma(), viz_arrow_tab());
+  LAUNCH_CHECK("viz_segments_jobs");
+  return TDR_OK;
+}
+
+extern "C" int tdr_k_viz_compose_jobs(const tdr_viz_job* jobs_dev, int k, int64_t max_out_pixels, void* stream) {
+  if (int rc = viz_jobs_args("viz_compose_jobs", jobs_dev, k, max_out_pixels)) return rc;
+  if (max_out_pixels == 0) return TDR_OK;
+  hipLaunchKernelGGL(viz_compose_jobs_kernel, dim3((unsigned)cdiv(max_out_pixels, 256), (unsigned)k), dim3(256), 0,
+                     (hipStream_t)stream, jobs_dev);
+  LAUNCH_CHECK("viz_compose_jobs");
   return TDR_OK;
 }

@@ -754,6 +754,42 @@ class HipKernels:
         check(self.lib.tdr_k_viz_compose(_ptr(background), H, W, _ptr(planes), out_h, out_w, _ptr(out), self.stream()))
         return out
 
+    # ---- the scan picture (csrc/tdr_scan_viz.hip) ----------------------------------------------------------------
+    @staticmethod
+    def _colour_table(lut_bgr):
+        lut = np.ascontiguousarray(lut_bgr, np.uint8)
+        if lut.size != 768:
+            raise ValueError("the colour table is 256 BGR triplets")
+        return lut
+
+    def scan_picture(self, imgs, ncls, rows, cols, unflatten, lut_bgr, out=None):
+        """imgs: device float32 [ncls][rows*cols] (the render layout) -> the (cols, rows, 3) uint8 device picture."""
+        unf = np.ascontiguousarray(unflatten, np.int32)
+        if unf.size < ncls:
+            raise ValueError(f"unflatten has {unf.size} entries, the render {ncls} classes")
+        lut = self._colour_table(lut_bgr)
+        if out is None:
+            out = self.empty((cols, rows, 3), torch.uint8)
+        check(self.lib.tdr_k_scan_picture(_ptr(imgs), int(ncls), int(rows) * int(cols), unf.ctypes.data_as(C.c_void_p),
+                                          lut.ctypes.data_as(C.c_void_p), _ptr(out), self.stream()))
+        return out
+
+    def analog_picture(self, img, rows, cols, scale, out=None):
+        """img: one device float32 layer [rows*cols] -> the (cols, rows, 3) grey device picture."""
+        if out is None:
+            out = self.empty((cols, rows, 3), torch.uint8)
+        check(self.lib.tdr_k_analog_picture(_ptr(img), int(rows) * int(cols), C.c_float(scale), _ptr(out), self.stream()))
+        return out
+
+    def label_picture(self, labels, lut_bgr, out=None):
+        """labels: (H, W) uint8 device tensor -> the (H, W, 3) uint8 device picture lut_bgr[labels]."""
+        lut = self._colour_table(lut_bgr)
+        H, W = int(labels.shape[0]), int(labels.shape[1])
+        if out is None:
+            out = self.empty((H, W, 3), torch.uint8)
+        check(self.lib.tdr_k_label_picture(_ptr(labels), H * W, lut.ctypes.data_as(C.c_void_p), _ptr(out), self.stream()))
+        return out
+
     def set_scale(self, st, n, scale_dev):
         check(self.lib.tdr_k_set_scale(_ptr(st), st.shape[1], n, _ptr(scale_dev), self.stream()))
 

@@ -511,8 +511,21 @@ class ParticleFilter:
         return self.num_particles_
 
     # ---- the particle picture (include/tdr.h, "the particle picture"): visualize (:373-423) on the device -----------
-    def setVizBackground(self, bgr):
-        """bgr: (H, W, 3) uint8, the image the node draws on (its background changes only with the map)."""
+    def setVizBackground(self, bgr=None, labels=None, lut=None):
+        """bgr: (H, W, 3) uint8, the image the node draws on (its background changes only with the map).  Or
+        labels=(H, W) uint8 with lut=256 BGR triplets: the label image goes up at one byte a cell and is coloured on
+        the device (aerialMapCallback's ind2Color)."""
+        if labels is not None:
+            if bgr is not None or lut is None:
+                raise ValueError("setVizBackground: either bgr, or labels with lut")
+            labels = np.ascontiguousarray(labels, np.uint8)
+            if labels.ndim != 2 or not (11 <= labels.shape[0] <= 32768 and 11 <= labels.shape[1] <= 32768):
+                raise ValueError("setVizBackground: a label image of 11 .. 32768 pixels a side")
+            self._viz_bg = self.k.label_picture(self.k.to_device(labels), lut)
+            self._viz_planes = self.k.viz_planes(labels.shape[0], labels.shape[1])
+            return
+        if bgr is None:
+            raise ValueError("setVizBackground: either bgr, or labels with lut")
         bgr = np.ascontiguousarray(bgr, np.uint8)
         if bgr.ndim != 3 or bgr.shape[2] != 3 or not (11 <= bgr.shape[0] <= 32768 and 11 <= bgr.shape[1] <= 32768):
             raise ValueError("setVizBackground: a BGR image of 11 .. 32768 pixels a side")

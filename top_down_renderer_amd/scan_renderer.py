@@ -44,6 +44,7 @@ class ScanRenderer:
         ncls, (rows, cols) = self._shape(imgs)
         img, pk = self.k.raster_cart(pts, n, stride, ioff, float(res), self.flatten_lut_, ncls, rows, cols)
         self._last = (img, pk)
+        self._last_shape = (ncls, rows, cols)
         self._fill(imgs, img, rows, cols)
 
     def _organised(self, cloud, width, height):
@@ -83,6 +84,27 @@ class ScanRenderer:
     def last_images(self):
         return self._last[0]
 
+    def _last_render(self, who):
+        if self._last is None:
+            raise ValueError(f"{who}: the renderer has no render")
+        return self._last[0], self._last_shape
+
+    def renderViz(self, unflatten_lut, lut_bgr):
+        """The scan picture of the last semantic render (TopDownRender::visualize, include/tdr.h "the scan picture"),
+        drawn from the device images: a (cols, rows, 3) uint8 BGR array.  lut_bgr: 256 BGR triplets."""
+        img, (ncls, rows, cols) = self._last_render("renderViz")
+        return self.k.scan_picture(img, ncls, rows, cols, unflatten_lut, lut_bgr).cpu().numpy()
+
+    def renderVizAnalog(self, cls, scale):
+        """visualizeAnalog of class layer `cls` of the last semantic render: a (cols, rows, 3) grey array."""
+        img, (ncls, rows, cols) = self._last_render("renderVizAnalog")
+        if not 0 <= int(cls) < ncls:
+            raise ValueError(f"renderVizAnalog: class {cls} of {ncls}")
+        if not (np.isfinite(scale) and scale > 0):
+            raise ValueError(f"renderVizAnalog: scale {scale} (finite and > 0)")
+        layer = img.reshape(ncls, rows * cols)[int(cls)]
+        return self.k.analog_picture(layer, rows, cols, float(scale)).cpu().numpy()
+
 
 class ScanRendererPolar(ScanRenderer):
     def renderSemanticTopDown(self, cloud, res, ang_res, imgs=None):
@@ -93,6 +115,7 @@ class ScanRendererPolar(ScanRenderer):
         ncls, (nb, nr) = self._shape(imgs)
         img, pk = self.k.raster_polar(pts, n, stride, ioff, float(res), float(ang_res), self.flatten_lut_, ncls, nb, nr)
         self._last = (img, pk)
+        self._last_shape = (ncls, nb, nr)
         self._fill(imgs, img, nb, nr)
 
     def renderGeometricTopDown(self, cloud, res, ang_res, imgs, width=None, height=None):
