@@ -949,6 +949,9 @@ int tdr_filter_get_weights(tdr_filter* f, float* out, int64_t n);
 int tdr_filter_compute_weights(tdr_filter* f, const float* scan_imgs, const tdr_renderer* renderer, float res);
 int tdr_filter_get_raw_weights(tdr_filter* f, float* out, int64_t n);
 int tdr_filter_get_last_dist(tdr_filter* f, float* out, int64_t n);
+/* scale_freeze == 0 gives every particle's scale a draw of its own, on a frozen or fixed-scale filter too: the filter then
+ * no longer treats the scales as one value (the uniform_scale shortcut of tdr_k_score_polar), and the next score reads
+ * each particle's own scale.  The frozen flag itself (tdr_filter_is_scale_frozen) is the caller's business and stays. */
 int tdr_filter_propagate_freeze(tdr_filter* f, float tx, float ty, float omega, int scale_freeze);
 int tdr_filter_init_one(tdr_filter* f);
 int tdr_filter_share_rng(tdr_filter* f, void* mt19937);

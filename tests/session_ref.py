@@ -1,0 +1,566 @@
+"""A long-lived C handle driven through a script of events with the CPU oracle in lock step (shared by
+tests/test_handle_session.py; not a test module).
+
+One `Session` owns what a node owns for hours — a MapHandle, a Renderer and a FilterHandle of
+top_down_renderer_amd/batch.py — and the oracle's mirror of it: the map, the polar table, the filter parameters, the frozen
+flag and an `oracle.Rng(seed)` that draws whenever the handle's generator draws (the draw counts depend on the particle
+count and the freeze flag alone).  Every call is checked stage by stage, each stage on inputs READ BACK from the device, so
+every comparison is as tight as the suite makes it elsewhere and a stale buffer or flag shows at the stage where it bites:
+
+  initialize   oracle.initialize_particles on the mirrored stream                      bytes equal
+  propagate    oracle.propagate(states read back, same stream)                         six fields, last_dist: bit for bit
+  score        oracle.compute_weights / compute_weights_cart on the states read back   1e-5 relative, NaN and zero pattern
+               a FRESH TWIN (new MapHandle, new FilterHandle, set_states(read-back))    raw weights and states: same bits
+  search       the rule of tests/test_gpu_fuzz.py (Cartesian: tests/cart_ref.py)        ties within 2e-5, no floor
+  statistics   oracle.update_weights(raw read back, last_dist read back)               rtol 3e-6, the argmax
+  resample     oracle.resample_prefix(weights read back, n_new, mirrored uniform)      indices equal
+  gather       oracle.gather_states(scored states, indices)                            bit for bit, count, step count
+  pose         tests/pose_ref.py on the states read back, and the fresh twin           pose_ref's bounds; twin: same bits
+
+After every call that changes the particle set the pose is read twice (fresh, then cached).  Calls that must not change the
+set are followed by a comparison of the states and the step count; the generator's position shows in the next propagate or
+resample, which is bit for bit (there is no accessor that looks at the stream without drawing from it).
+
+With handle=False the same script runs on the oracle alone (no GPU): the states are then the oracle's own, and `records`
+holds what tests/test_handle_session.py asserts about the script itself."""
+import math
+from dataclasses import dataclass, field
+
+import numpy as np
+
+import cart_ref
+import pose_ref as P
+
+F32 = np.float32
+FIELDS = ("init_x_px", "init_y_px", "dx_m", "dy_m", "theta", "scale")
+WEIGHT_RTOL = 1e-5      # BASELINE.json north_star
+TIE_RTOL = 2e-5         # tests/test_gpu_fuzz.py:161
+STATS_RTOL = 3e-6       # tests/test_gpu_fuzz.py:96
+
+
+@dataclass
+class MapSpec:
+    """What a map is made from — enough to make the same map again on a fresh handle, and the oracle's copy of it."""
+    maps: np.ndarray            # (ncls, rows, cols) distance maps (of the label image when there is one)
+    mask: np.ndarray
+    resolution: float
+    center: tuple = (0, 0)
+    img: np.ndarray = None      # the class-index image (cv::Mat layout) when the map was set from labels
+    lut: np.ndarray = None
+    pts: np.ndarray = None      # the cloud scans of this map are rendered from
+    geo_const: bool = False     # geo_maps_ are the constant 1 of the dynamic-map path
+
+    @property
+    def ncls(self):
+        return self.maps.shape[0]
+
+    def handle(self, batch):
+        if self.img is not None:
+            return batch.MapHandle.from_labels(self.img, self.lut, self.ncls, self.resolution, self.center)
+        return batch.MapHandle(self.maps, self.mask, self.resolution, self.center)
+
+
+def labels_spec(np_oracle, img, lut, ncls, resolution, center, pts):
+    maps, mask = np_oracle.load_compressed_raster_map(img, lut, ncls, resolution)
+    return MapSpec(maps, mask, resolution, tuple(center), np.ascontiguousarray(img, np.uint8), np.asarray(lut, np.int32), pts,
+                   geo_const=True)
+
+
+def images(flat, rows, cols):
+    """[ncls][rows*cols] column-major images (the oracle's raster) -> (ncls, rows, cols) arrays."""
+    return np.ascontiguousarray(flat.reshape(len(flat), cols, rows).transpose(0, 2, 1))
+
+
+def bits_equal(a, b, names=FIELDS + ("have_init",)):
+    return [f for f in names if a[f].tobytes() != b[f].tobytes()]
+
+
+def assert_weights(w, ref, what):
+    """1e-5 relative, the same NaN pattern, the same zero pattern."""
+    assert np.array_equal(np.isnan(w), np.isnan(ref)), (what, int(np.isnan(w).sum()), int(np.isnan(ref).sum()))
+    ok = ~np.isnan(ref)
+    assert np.array_equal(w[ok] == 0, ref[ok] == 0), (what, "zero pattern")
+    err = np.abs(w[ok] - ref[ok]) / np.maximum(np.abs(ref[ok]), 1e-30)
+    assert err.max(initial=0.0) <= WEIGHT_RTOL, f"{what}: max rel err {err.max():.3e}"
+
+
+class _PoseRef:
+    """tests/pose_ref.py's exact reference of one particle set (what pose_ref.check_cov asks of a Ref)."""
+
+    def __init__(self, st):
+        self.st, self.n = st, len(st)
+        self.mean, self.geo, self.tot = P.mean_ref(st)
+
+    def cov(self, about):
+        return P.cov_ref(self.st, about)
+
+
+@dataclass
+class Session:
+    oracle: object
+    spec: MapSpec
+    n_max: int
+    seed: int
+    params: dict
+    cart: bool = False
+    handle: bool = True
+    shape: tuple = (36, 12)               # polar (nb, nr) or the Cartesian window (rows, cols)
+    map_handle: object = None             # shared with another Session (script D), else made here
+    renderer: object = None
+    name: str = "f"
+    records: list = field(default_factory=list)
+
+    def __post_init__(self):
+        o = self.oracle
+        self.rng = o.Rng(self.seed)
+        self.side = o.Rng(self.seed + 7777)    # oracle-alone runs: the draws of a step whose noise is the device's own
+        self.frozen = self.params.get("fixed_scale", 1.0) > 0
+        self.parity = True
+        self.st = np.zeros(0, o.STATE_DTYPE)
+        self.ld = np.zeros(self.n_max, F32)
+        self.ml = None
+        self.steps = 0
+        self.label = "start"
+        self._set_oracle_map(self.spec)
+        self.f = None
+        if self.handle:
+            from top_down_renderer_amd import batch, synth
+            from top_down_renderer_amd.particle_filter import FilterParams
+            self.batch = batch
+            self.fp_py = FilterParams(**self.params)
+            if self.map_handle is None:
+                self.map_handle = self.spec.handle(batch)
+            self._shape_map(self.map_handle)
+            if self.renderer is None:
+                self.renderer = batch.Renderer(synth.make_lut(6))
+            self.f = batch.FilterHandle(self.map_handle, self.n_max, self._fp_c(), seed=self.seed,
+                                        cart=self.cart)
+
+    # ---- the oracle's side ------------------------------------------------------------------------------------------
+    def _set_oracle_map(self, spec):
+        o = self.oracle
+        self.spec = spec
+        self.om = o.OracleMap(spec.maps, spec.mask, spec.resolution)
+        cw = list(self.params.get("class_weights") or [1.0] * spec.ncls)[: spec.ncls]
+        kw = dict(self.params, class_weights=cw)
+        self.fpo = o.make_params(spec.ncls, **kw)
+        self._set_shape(self.shape)
+
+    def _set_shape(self, shape):
+        self.shape = tuple(shape)
+        if not self.cart:
+            nb, nr = self.shape
+            self.ang_res = F32(2 * np.pi / nb)
+            self.tab = self.oracle.polar_table(nb, nr, self.ang_res, self.spec.resolution)
+
+    def _fp_c(self):
+        """The filter's parameters for the current map: a map of fewer classes uses the first of the class weights."""
+        from top_down_renderer_amd.particle_filter import FilterParams
+        cw = list(self.params.get("class_weights") or [])[: self.spec.ncls]
+        return FilterParams(**dict(self.params, class_weights=cw)).to_c(self.spec.ncls)
+
+    def _shape_map(self, mh):
+        if self.cart:
+            mh.set_window(*self.shape)
+        else:
+            mh.sample_pts_polar(self.shape[0], self.shape[1], F32(2 * np.pi / self.shape[0]))
+
+    def scan_flat(self, res, zero=False):
+        o, s = self.oracle, self.spec
+        lut = self._lut()
+        if self.cart:
+            flat = o.raster_cart(s.pts, res, lut, s.ncls, *self.shape)
+        else:
+            flat = o.raster_polar(s.pts, res, self.ang_res, lut, s.ncls, *self.shape)
+        return np.zeros_like(flat) if zero else flat
+
+    def _lut(self):
+        from top_down_renderer_amd import synth
+        return synth.make_lut(6)     # one renderer, one table: clouds of a 4-class map hold no raw id 4 or 5
+
+    def _oracle_score(self, st_in, flat, res, geo=None):
+        """(raw weights, the states after scoring: the search's headings written) on the oracle."""
+        o = self.oracle
+        st = st_in.copy()
+        with np.errstate(all="ignore"):
+            if self.cart:
+                un = st["have_init"] == 0
+                if un.any():
+                    sub = np.ascontiguousarray(st[un])
+                    w40 = cart_ref.oracle_candidate_weights(o, self.om, *self.shape, flat, res, self.fpo, sub)
+                    best = np.where(np.isnan(w40), -1.0, w40)
+                    j = best.argmax(1)                      # the first maximum, NaN never chosen; none finite: 0
+                    none = ~(best.max(1) > 0)
+                    th = cart_ref.candidates()[j]
+                    th[none] = 0
+                    st["theta"][un] = th
+                    st["have_init"] = 1
+                raw = o.compute_weights_cart(self.om, *self.shape, flat, res, self.fpo, st)
+            elif geo is not None:
+                raw = o.compute_weights_geo(self.om, self._geo_map(), self.tab, *self.shape, flat, geo, res, self.fpo, st)
+            else:
+                raw = o.compute_weights(self.om, self.tab, *self.shape, flat, res, self.fpo, st)
+        return raw, st
+
+    def _geo_map(self):
+        o, s = self.oracle, self.spec
+        if s.geo_const:
+            one = np.ones((2,) + s.mask.shape, F32)
+            return o.OracleMap(one, np.zeros(s.mask.shape, np.uint8), s.resolution)
+        return o.geo_maps_from_class_maps(s.maps, s.mask, s.resolution)
+
+    def geo_scan(self, res):
+        pts = np.ascontiguousarray(self.spec.pts[:, :4])
+        return self.oracle.raster_geo_polar(pts, len(pts), 1, res, self.ang_res, *self.shape)
+
+    def _rescore(self, scored_dev, flat, res, geo):
+        """The oracle's weights at the headings the device holds (everything else the oracle's)."""
+        st2 = scored_dev.copy()
+        st2["have_init"] = np.where(scored_dev["have_init"] != 0, 1, 0)
+        raw2, _ = self._oracle_score(st2, flat, res, geo)
+        return raw2
+
+    # ---- checks -----------------------------------------------------------------------------------------------------
+    def _what(self, stage):
+        return f"[{self.name}] {stage} after '{self.label}' (step {self.steps}, n = {len(self.st)})"
+
+    def _check_score(self, before, raw_g, scored_g, flat, res, geo, stage):
+        """raw_g, scored_g: the device's raw weights and its states after scoring `before`."""
+        what = self._what(stage)
+        raw_o, st_o = self._oracle_score(before, flat, res, geo)
+        bad = bits_equal(scored_g, before, ("init_x_px", "init_y_px", "dx_m", "dy_m", "scale"))
+        assert not bad, (what, "scoring moved", bad)
+        had = before["have_init"] != 0
+        assert scored_g["theta"][had].tobytes() == before["theta"][had].tobytes(), (what, "a particle with a heading lost it")
+        assert np.array_equal(scored_g["have_init"], st_o["have_init"]), (what, "have_init")
+        same = scored_g["theta"] == st_o["theta"]      # (no floor on how many agree: every mismatch must be a tie, below)
+        assert_weights(raw_g[same], raw_o[same], what)
+        diff = np.nonzero(~same)[0]
+        if len(diff):
+            raw2 = self._rescore(scored_g, flat, res, geo)
+            assert_weights(raw_g[diff], raw2[diff], what + " at the device's rotation")
+            tie = np.abs(raw2[diff] - raw_o[diff]) / np.maximum(np.abs(raw_o[diff]), 1e-30)
+            assert np.nanmax(tie, initial=0.0) <= TIE_RTOL, f"{what}: chosen rotation is not a near-tie: {np.nanmax(tie):.2e}"
+            if self.cart:
+                th = cart_ref.candidates()
+                assert np.isin(scored_g["theta"][diff], th).all(), (what, "a heading that is no candidate")
+        return raw_o, st_o
+
+    def _twin(self):
+        """A fresh map and filter from the same inputs: nothing an earlier call left behind."""
+        mh = self.spec.handle(self.batch)
+        self._shape_map(mh)
+        return self.batch.FilterHandle(mh, self.n_max, self._fp_c(), seed=self.seed + 1, cart=self.cart)
+
+    def _scan_arg(self, flat, res, source):
+        """What update / compute_weights is handed: host images, or the renderer after rendering the cloud at `res`."""
+        s = self.spec
+        if source == "renderer":
+            r = self.renderer
+            if self.cart:
+                r.render_cart(s.pts, 4, 3, res, s.ncls, *self.shape)
+            else:
+                r.render_polar(s.pts, 4, 3, res, self.ang_res, s.ncls, *self.shape)
+            img, _ = r.get_render()
+            assert np.array_equal(img, images(flat, *self.shape)), self._what("render")
+            return r
+        return images(flat, *self.shape)
+
+    def pose(self, stage="pose"):
+        """The pose read twice (fresh, cached), against pose_ref on the states read back and against a fresh twin."""
+        if not self.handle:
+            return
+        f, what, st = self.f, self._what(stage), self.st
+        n = len(st)
+        assert f.num_particles() == n, what
+        assert f.is_scale_frozen() == self.frozen, (what, "is_scale_frozen")
+        fixed = self.params.get("fixed_scale", 1.0)
+        want_scale = F32(fixed) if fixed > 0 else (st["scale"][0] if self.frozen and n > 0 else F32(-1))
+        assert F32(f.scale()) == want_scale, (what, "scale()", f.scale(), want_scale)
+        if n == 0:
+            return
+        m0, c0 = f.mean_cov(False)       # fresh
+        m1, c1 = f.mean_cov(False)       # cached
+        assert m0.tobytes() == m1.tobytes() and c0.tobytes() == c1.tobytes(), (what, "the cached pose differs")
+        tw = self.batch.FilterHandle(self.map_handle, n, self._fp_c(), seed=1, cart=self.cart)
+        tw.set_states(st)
+        mt, ct = tw.mean_cov(False)
+        assert m0.tobytes() == mt.tobytes() and c0.tobytes() == ct.tobytes(), (what, "a fresh filter's pose differs", m0, mt)
+        ref = _PoseRef(st)
+        idx = [0, 1, 3]
+        err = np.abs(m0[idx].astype(np.float64) - ref.mean[idx].astype(np.float64)) / P.ulp(ref.mean[idx])
+        assert err.max() <= P.MEAN_ULPS, f"{what}: mean x / y / scale {m0[idx]} vs {ref.mean[idx]}: {err} ulp"
+        # pose_ref's heading bound holds for every resultant the double sums resolve: its inputs are each within 2 ulp
+        # RELATIVE, so the angle moves by a few 1e-7 whatever the resultant's length (a cold start's is ~ 1 / sqrt(n))
+        if math.hypot(ref.tot[4], ref.tot[5]) >= 1e-6 * n:
+            dh = abs((float(m0[2]) - float(ref.mean[2]) + math.pi) % (2 * math.pi) - math.pi)
+            assert dh <= P.HEADING_TOL, f"{what}: mean heading {m0[2]!r} vs {ref.mean[2]!r}: {dh:.3e} rad"
+        out = np.zeros(24, F32)
+        out[:4], out[4:20] = m0, c0.reshape(-1)
+        P.check_cov(out, ref, m0)
+        if self.ml is not None:
+            ms, cm = f.mean_cov(True)
+            assert ms.tobytes() == self.ml.tobytes(), (what, "maxLikelihood state", ms, self.ml)
+            out[:4], out[4:20] = ms, cm.reshape(-1)
+            P.check_cov(out, ref, ms)
+            m2, c2 = f.mean_cov(False)   # ... and the cache survived the other question
+            assert m0.tobytes() == m2.tobytes() and c0.tobytes() == c2.tobytes(), (what, "cache after computeCov")
+        self.unchanged(stage + " reads")
+
+    def unchanged(self, stage):
+        """The states and the step count stand where the driver last saw them."""
+        if not self.handle:
+            return
+        got = self.f.states()
+        assert got.tobytes() == self.st.tobytes(), (self._what(stage), "the particle set moved", bits_equal(got, self.st))
+        assert self.f.step_count() == self.steps, self._what(stage)
+
+    # ---- events -----------------------------------------------------------------------------------------------------
+    def initialize(self, label="initialize"):
+        o = self.oracle
+        self.label = label
+        if self.params.get("fixed_scale", 1.0) >= 0:
+            self.frozen = True
+        want = o.initialize_particles(self.om, self.fpo, self.n_max, self.rng)
+        if self.handle:
+            self.f.initialize_particles()
+            got = self.f.states()
+            assert got.tobytes() == want.tobytes(), (self._what("initialize"), bits_equal(got, want), len(got), len(want))
+        self.st = want
+        self.pose()
+
+    def set_states(self, st, label="set_states"):
+        self.label = label
+        st = np.ascontiguousarray(st, self.oracle.STATE_DTYPE)
+        if self.params.get("fixed_scale", 1.0) > 0:
+            self.frozen = True
+        if self.handle:
+            self.f.set_states(st)
+            got = self.f.states()
+            assert got.tobytes() == st.tobytes(), self._what("set_states")
+        self.st = st.copy()
+        self.pose()
+
+    def freeze(self, label="freeze_scale"):
+        self.label = label
+        if self.frozen or len(self.st) < 1:
+            if self.handle:
+                self.f.freeze_scale()
+                self.unchanged("freeze_scale of a frozen filter")
+            return
+        ref = self.st.copy()
+        self.oracle.freeze_scale(ref)
+        if self.handle:
+            before = self.st
+            geo = _PoseRef(before).geo
+            self.f.freeze_scale()
+            got = self.f.states()
+            assert not bits_equal(got, before, ("init_x_px", "init_y_px", "dx_m", "dy_m", "theta", "have_init"))
+            assert len(np.unique(got["scale"])) == 1, self._what("freeze_scale")
+            s = got["scale"][0]
+            assert abs(float(s) - float(geo)) <= P.GEO_ULPS * float(P.ulp(geo)), (self._what("freeze_scale"), s, geo)
+            # (the oracle's serial float32 chain of logs drifts past that at thousands of particles — pose_ref's
+            # float_chain_drift — so the exact reference above is the check; the oracle's value is not compared)
+            ref = got
+        self.frozen = True
+        self.st = ref
+        self.pose()
+
+    def configure(self, parity, locality=1, label=None):
+        self.label = label or f"configure(parity_rng={parity}, locality_every={locality})"
+        self.parity = bool(parity)
+        if self.handle:
+            self.f.configure(parity, locality)
+            self.unchanged("configure")
+
+    def window(self, shape, label=None):
+        """tdr_map_sample_pts_polar / tdr_map_set_window to another shape on the live map."""
+        self.label = label or f"window {shape}"
+        self._set_shape(shape)
+        if self.handle:
+            self._shape_map(self.map_handle)
+            self.unchanged("window")
+
+    def propagate(self, tx, ty, omega, freeze=None, label=None):
+        o = self.oracle
+        if label:
+            self.label = label
+        n = len(self.st)
+        if n == 0:
+            return
+        flag = self.frozen if freeze is None else bool(freeze)
+        before = self.st
+        ref = before.copy()
+        last = o.propagate(ref, tx, ty, omega, flag, self.fpo, self.rng if self.parity else self.side)
+        if self.handle:
+            if freeze is None:
+                self.f.propagate(tx, ty, omega)
+            else:
+                self.f.propagate_freeze(tx, ty, omega, flag)
+            got, ld = self.f.states(), self.f.last_dist(n)
+            what = self._what("propagate")
+            if self.parity:
+                bad = bits_equal(got, ref)
+                assert not bad, (what, bad)
+                assert ld.tobytes() == last.tobytes(), (what, "last_dist")
+            else:   # the device's own noise: what the noise does not touch stays, the rest is finite and has moved
+                assert not bits_equal(got, before, ("init_x_px", "init_y_px", "have_init") + (("scale",) if flag else ()))
+                assert all(np.isfinite(got[k]).all() for k in FIELDS) and np.isfinite(ld).all(), what
+                assert (got["dx_m"] != before["dx_m"]).mean() > 0.99 and (got["theta"] != before["theta"]).mean() > 0.99
+                if not flag:
+                    assert (got["scale"] != before["scale"]).mean() > 0.99, (what, "the scales did not move")
+            ref, last = got, ld
+            tail = self.f.last_dist(self.n_max)[n:]
+            assert tail.tobytes() == self.ld[n:].tobytes(), (what, "last_dist behind n was written")
+        self.ld[:n] = last
+        self.st = ref
+        self.pose("pose after propagate")
+
+    def compute_weights(self, res, source="host", zero=False, label=None):
+        """tdr_filter_compute_weights: the score stage alone (the search may write headings; nothing else moves)."""
+        if label:
+            self.label = label
+        n = len(self.st)
+        flat = self.scan_flat(res, zero)
+        before = self.st
+        if self.handle:
+            self.f.compute_weights(self._scan_arg(flat, res, source), res)
+            raw, scored = self.f.raw_weights(n), self.f.states()
+            tw = self._twin()
+            tw.set_states(before)
+            tw.compute_weights(images(flat, *self.shape), res)
+            what = self._what("compute_weights")
+            assert np.array_equal(raw, tw.raw_weights(n), equal_nan=True), (what, "a fresh twin's raw weights differ")
+            assert scored.tobytes() == tw.states().tobytes(), (what, "a fresh twin's states differ")
+            self._check_score(before, raw, scored, flat, res, None, "compute_weights")
+            assert self.f.step_count() == self.steps and self.f.num_particles() == n, what
+            moved = scored.tobytes() != before.tobytes()
+            self.st = scored
+            if moved:
+                self.pose("pose after compute_weights")
+            else:
+                self.unchanged("compute_weights")
+        else:
+            raw, self.st = self._oracle_score(before, flat, res)
+        return raw
+
+    def update(self, res, n_target=-1, source="host", zero=False, geo=False, degenerate=False, label=None):
+        """tdr_filter_update (geo: tdr_filter_update_geo) stage by stage."""
+        o = self.oracle
+        if label:
+            self.label = label
+        n = len(self.st)
+        if n == 0:
+            return
+        n_new = n if n_target < 0 else max(1, min(int(n_target), self.n_max))
+        flat = self.scan_flat(res, zero)
+        geo_flat = self.geo_scan(res) if geo else None
+        before = self.st
+        ld = self.ld[:n].copy()
+        search = float((before["have_init"] == 0).mean())
+        if self.handle:
+            f, what = self.f, self._what("update")
+            assert f.last_dist(n).tobytes() == ld.tobytes(), (what, "last_dist moved since the propagate")
+            if geo:
+                f.update_geo(images(flat, *self.shape), images(geo_flat, *self.shape), res, n_target)
+            else:
+                f.update(self._scan_arg(flat, res, source), res, n_target)
+            raw = f.raw_weights(n)
+            w = f._floats(f.L.tdr_filter_get_weights, n)
+            idx, after = f.resample_indices(), f.states()
+            assert f.num_particles() == n_new == len(after), (what, f.num_particles(), n_new)
+            assert f.step_count() == self.steps + 1, (what, "step_count")
+            # -- score: a fresh twin on the states read back; its states after scoring are the scored states
+            tw = self._twin()
+            tw.set_states(before)
+            if geo:
+                tw.update_geo(images(flat, *self.shape), images(geo_flat, *self.shape), res, n_target)
+                _, scored = self._oracle_score(before, flat, res, geo_flat)
+                assert scored["theta"].tobytes() == before["theta"].tobytes(), "script: update_geo on a step with a search"
+            else:
+                tw.compute_weights(images(flat, *self.shape), res)
+                scored = tw.states()
+            assert np.array_equal(raw, tw.raw_weights(n), equal_nan=True), (what, "a fresh twin's raw weights differ")
+            self._check_score(before, raw, scored, flat, res, geo_flat, "score")
+            # -- statistics on the raw weights and last_dist read back
+            with np.errstate(all="ignore"):
+                w_o, best_o, _ = o.update_weights(raw, ld)
+            assert np.allclose(w, w_o, rtol=STATS_RTOL, atol=0) or np.isnan(raw).all(), (what, "weights")
+            # -- resample on the weights read back, the mirrored uniform
+            u = self.rng.uniform()
+            idx_o = o.resample_prefix(w, n_new, u)
+            assert np.array_equal(idx, idx_o), (what, "resample indices", int((idx != idx_o).sum()))
+            # -- gather
+            want = o.gather_states(scored, idx_o)
+            bad = bits_equal(after, want)
+            assert not bad, (what, "gather", bad)
+            if True:
+                # the argmax (all-NaN raw weights included: every weight is then 1 / n): maxLikelihood is that particle's state before the resample.  The oracle's first maximum, or
+                # a particle whose oracle weight ties with it within the bound the weights themselves are held to (a
+                # zero scan leaves every weight at 1 / n to rounding, and the device's maximum is over its own roundings)
+                ms, _ = f.mean_cov(True)
+                tied = np.nonzero(w_o >= w_o[best_o] * (1 - STATS_RTOL))[0]
+                x, y, th, sc = P.ml_states(scored[tied])
+                cand = np.stack([x, y, th, sc], axis=1).astype(F32)
+                hit = np.nonzero((cand.view(np.uint32) == ms.view(np.uint32)).all(1))[0]
+                assert len(hit), (what, "maxLikelihood is no particle that ties with the oracle's argmax", ms, cand[0], len(tied))
+                assert len(tied) > 1 or tied[0] == best_o
+                self.ml = cand[hit[0]]
+            self.st = after
+        else:
+            raw, scored = self._oracle_score(before, flat, res, geo_flat)
+            with np.errstate(all="ignore"):
+                w, _, _ = o.update_weights(raw, ld)
+            idx = o.resample_prefix(w, n_new, self.rng.uniform())
+            self.st = o.gather_states(scored, idx)
+        self.steps += 1
+        good = float((np.isfinite(raw) & (raw != 0)).mean())
+        self.records.append(dict(label=self.label, n=n, n_new=n_new, good=good, distinct=len(np.unique(idx)), search=search,
+                                 degenerate=degenerate, source=source, geo=geo, res=res, shape=self.shape,
+                                 ncls=self.spec.ncls, parity=self.parity))
+        self.pose("pose after update")
+
+    def step(self, motion, res, n_target=-1, **kw):
+        self.propagate(*motion)
+        self.update(res, n_target, **kw)
+
+    def new_map(self, spec, how, label=None, patch=None):
+        """The map replaced through one of the four entry points (how: "maps", "labels", "incremental", "patch"); the
+        particles shift by the centre's move.  Returns the changed-cell count of the incremental calls."""
+        self.label = label or f"map via {how}"
+        dx, dy = spec.center[0] - self.spec.center[0], spec.center[1] - self.spec.center[1]
+        ref = self.st.copy()
+        self.oracle.shift_init(ref, dx, dy)
+        changed = None
+        if self.handle:
+            f = self.f
+            if how == "maps":
+                f.update_map(spec.maps, spec.mask, spec.resolution, spec.center)
+            elif how == "labels":
+                f.update_map_labels(spec.img, spec.lut, spec.ncls, spec.resolution, spec.center)
+            elif how == "incremental":
+                changed = f.update_map_labels_incremental(spec.img, spec.lut, spec.ncls, spec.resolution, spec.center)
+            else:
+                y0, x0, h, w = patch
+                changed = f.patch_map_labels(spec.img[y0:y0 + h, x0:x0 + w], y0, x0, spec.center)
+            assert self.map_handle.center() == tuple(spec.center)
+            got = f.states()
+            assert not bits_equal(got, ref), (self._what("map update"), bits_equal(got, ref))
+            ref = got
+        self.st = ref
+        self._set_oracle_map(spec)
+        self.pose("pose after the map update")
+        return changed
+
+    def reads(self, label="reads"):
+        """Calls that must not change the set: the getters, the pose, the mixture fit."""
+        self.label = label
+        if not self.handle:
+            return
+        f, n = self.f, len(self.st)
+        f.raw_weights(n), f.weights(), f.resample_indices(), f.last_dist(n)
+        f.compute_gmm(device=True)
+        f.get_gmm()
+        f.compute_gmm(device=False)
+        f.adaptive_count()
+        self.unchanged("getters and compute_gmm")

@@ -35,11 +35,29 @@ class MapHandle:
         self.h = _vp()
         check(self.L.tdr_map_create(C.byref(self.h)))
         ncls, rows, cols = class_maps.shape
-        maps_cm = np.ascontiguousarray(np.transpose(class_maps, (0, 2, 1)), np.float32)
-        mask_cm = np.ascontiguousarray(np.asarray(class_mask).T, np.uint8)
+        maps_cm, mask_cm = _maps_cm(class_maps, class_mask)
         check(self.L.tdr_map_set(self.h, _ptr(maps_cm), _ptr(mask_cm), ncls, rows, cols, C.c_float(resolution),
                                  int(center[0]), int(center[1])))
         self.ncls = ncls
+
+    @classmethod
+    def from_labels(cls, label_img, flatten_lut, ncls, resolution=1.0, center=(0, 0)):
+        """A map set from a class-index image (tdr_map_set_labels; cv::Mat layout, row 0 = top)."""
+        self = cls.__new__(cls)
+        self.L = _lib.load()
+        self.h = _vp()
+        check(self.L.tdr_map_create(C.byref(self.h)))
+        img, lut = _label_args(label_img, flatten_lut)
+        check(self.L.tdr_map_set_labels(self.h, _ptr(img), img.shape[0], img.shape[1], _ptr(lut), len(lut), int(ncls),
+                                        C.c_float(resolution), int(center[0]), int(center[1])))
+        self.ncls = int(ncls)
+        return self
+
+    def center(self):
+        """mapCenter() (tdr_map_center): (center_x, center_y)."""
+        cx, cy = C.c_int(), C.c_int()
+        check(self.L.tdr_map_center(self.h, C.byref(cx), C.byref(cy)))
+        return cx.value, cy.value
 
     def sample_pts_polar(self, nb, nr, ang_res):
         check(self.L.tdr_map_sample_pts_polar(self.h, nb, nr, C.c_float(ang_res)))
@@ -54,6 +72,19 @@ class MapHandle:
         if getattr(self, "h", None):
             self.L.tdr_map_destroy(self.h)
             self.h = None
+
+
+def _maps_cm(class_maps, class_mask):
+    """(ncls, rows, cols) distance maps and the (rows, cols) mask in the column-major layout tdr_map_set reads."""
+    return (np.ascontiguousarray(np.transpose(class_maps, (0, 2, 1)), np.float32),
+            np.ascontiguousarray(np.asarray(class_mask).T, np.uint8))
+
+
+def _label_args(label_img, flatten_lut):
+    img = np.ascontiguousarray(label_img, np.uint8)
+    if img.ndim != 2:
+        raise ValueError("a label image is (H, W) uint8")
+    return img, np.ascontiguousarray(flatten_lut, np.int32).ravel()
 
 
 class Renderer:
@@ -187,6 +218,57 @@ class FilterHandle:
 
     def propagate(self, tx, ty, omega):
         check(self.L.tdr_filter_propagate(self.h, C.c_float(tx), C.c_float(ty), C.c_float(omega)))
+
+    def propagate_freeze(self, tx, ty, omega, scale_freeze):
+        """StateParticle::propagate with the caller's scale_freeze flag (tdr_filter_propagate_freeze)."""
+        check(self.L.tdr_filter_propagate_freeze(self.h, C.c_float(tx), C.c_float(ty), C.c_float(omega), int(bool(scale_freeze))))
+
+    def last_dist(self, n=None):
+        """lastDist() of the first n particles (tdr_filter_get_last_dist): what the last propagate left."""
+        return self._floats(self.L.tdr_filter_get_last_dist, self.num_particles() if n is None else int(n))
+
+    def update_geo(self, scan, geo, res, n_target=-1):
+        """update with the geometric images entering the score (tdr_filter_update_geo): scan (ncls, nb, nr), geo (2, nb, nr)."""
+        imgs = _scan_images(scan, self.map, self.cart)
+        g = np.asarray(geo, np.float32)
+        if g.shape != (2,) + imgs.shape[:0:-1]:
+            raise ValueError(f"geometric images of shape {g.shape}, the map expects {(2,) + imgs.shape[:0:-1]}")
+        g = np.ascontiguousarray(np.transpose(g, (0, 2, 1)))
+        check(self.L.tdr_filter_update_geo(self.h, _ptr(imgs), _ptr(g), C.c_float(res), int(n_target)))
+
+    # updateMap of a live filter: the map is replaced, the particles shift by the centre's move (or are initialised)
+    def update_map(self, class_maps, class_mask, resolution, center):
+        """tdr_filter_update_map: the new map in distance-map form."""
+        ncls, rows, cols = class_maps.shape
+        maps_cm, mask_cm = _maps_cm(class_maps, class_mask)
+        check(self.L.tdr_filter_update_map(self.h, _ptr(maps_cm), _ptr(mask_cm), ncls, rows, cols, C.c_float(resolution),
+                                           int(center[0]), int(center[1])))
+        self.map.ncls = ncls
+
+    def update_map_labels(self, label_img, flatten_lut, ncls, resolution, center):
+        """tdr_filter_update_map_labels: the new map as a class-index image (cv::Mat layout)."""
+        img, lut = _label_args(label_img, flatten_lut)
+        check(self.L.tdr_filter_update_map_labels(self.h, _ptr(img), img.shape[0], img.shape[1], _ptr(lut), len(lut),
+                                                  int(ncls), C.c_float(resolution), int(center[0]), int(center[1])))
+        self.map.ncls = int(ncls)
+
+    def update_map_labels_incremental(self, label_img, flatten_lut, ncls, resolution, center):
+        """tdr_filter_update_map_labels_incremental; returns the changed cells (-1: the full path was taken)."""
+        img, lut = _label_args(label_img, flatten_lut)
+        changed = C.c_int64(0)
+        check(self.L.tdr_filter_update_map_labels_incremental(self.h, _ptr(img), img.shape[0], img.shape[1], _ptr(lut),
+                                                              len(lut), int(ncls), C.c_float(resolution), int(center[0]),
+                                                              int(center[1]), C.byref(changed)))
+        self.map.ncls = int(ncls)
+        return changed.value
+
+    def patch_map_labels(self, patch, y0, x0, center):
+        """tdr_filter_patch_map_labels: the rectangle at image pixel (y0, x0) of the last label image overwritten."""
+        patch = np.ascontiguousarray(patch, np.uint8)
+        changed = C.c_int64(0)
+        check(self.L.tdr_filter_patch_map_labels(self.h, _ptr(patch), int(y0), int(x0), patch.shape[0], patch.shape[1],
+                                                 int(center[0]), int(center[1]), C.byref(changed)))
+        return changed.value
 
     def update(self, scan, res, n_target=-1):
         if isinstance(scan, Renderer):

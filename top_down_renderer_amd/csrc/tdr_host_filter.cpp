@@ -224,6 +224,8 @@ int tdr_filter_initialize_particles(tdr_filter* f) {
 static int filter_propagate(tdr_filter* f, float tx, float ty, float omega, bool scale_freeze) {
   if (f->n == 0) return TDR_OK;
   f->states_changed();
+  // every particle's scale takes a draw of its own: the promise behind uniform_scale (tdr_k_score_polar) ends here
+  if (!scale_freeze) f->uniform_scale = 0.f;
   const int64_t nl = f->nl();
   const float* z = nullptr;
   if (rng_device_capable(f)) {
