@@ -8,6 +8,8 @@ is a DEFINITION of this repository, include/tdr.h)."""
 import numpy as np
 import pytest
 
+from variant_scenes import counted
+
 pytestmark = pytest.mark.gpu
 ALL_RAY = 1e-6
 
@@ -68,6 +70,11 @@ def test_generated_loop_equals_plain_kernel_ray_kernel_and_oracle(tdr, oracle, n
         # a second cloud hugging the map's corner: waves whose boxes reach the guard ring (the clamping variant)
         st["init_x_px"][700:1100] = rng.normal(6.0, 3.0, 400).astype(np.float32)
         st["init_y_px"][700:1100] = rng.normal(8.0, 3.0, 400).astype(np.float32)
+        # a third cloud at the corner of an unlabelled hole well inside the map: boxes that hold unknown cells and need no
+        # clamp (the variant between the two; the cloud around the pose sees known cells only — the counters showed it)
+        ys, xs = np.nonzero(class_mask[100:500, 100:500])
+        st["init_x_px"][1100:1300] = rng.normal(100.0 + xs[0], 3.0, 200).astype(np.float32)
+        st["init_y_px"][1100:1300] = rng.normal(100.0 + ys[0], 3.0, 200).astype(np.float32)
     elif particles == "known":
         # every cell labelled: distance maps of a label image without holes (the mask is all zero)
         lab = sc.lab.copy()
@@ -88,7 +95,18 @@ def test_generated_loop_equals_plain_kernel_ray_kernel_and_oracle(tdr, oracle, n
     plain = _run(pkg, k, m, st, scan, cfg.res, 0, 0.0)             # every particle dense, the plain kernel
     ray = _run(pkg, k, m, st, scan, cfg.res, 32, ALL_RAY)          # every particle through the ray-mapped kernel
     for seg in (32, 8, 4, 64):
-        got = _run(pkg, k, m, st, scan, cfg.res, seg, 0.0)         # every particle dense, the generated loop
+        dense = lambda: _run(pkg, k, m, st, scan, cfg.res, seg, 0.0)   # every particle dense, the generated loop
+        if seg == 32:   # what the row of CASES promises, from the kernel's own counters (tdr_profile_variants: [8..10] all known /
+            got, v = counted(k, dense)           # inside / general, [11] the plain steps)
+            print(f"{particles}: variant counters {v}")
+            if particles == "known":
+                assert v[8] > 0 and v[10] == 0 and v[11] == 0, v
+            elif particles == "large":
+                assert v[11] > 0, v
+            else:
+                assert v[8] > 0 and v[9] > 0 and v[10] > 0, v
+        else:
+            got = dense()
         assert np.array_equal(got, plain, equal_nan=True), f"segment of {seg} rows: {int((got != plain).sum())} weights differ"
     mixed = _run(pkg, k, m, st, scan, cfg.res, 32, 6.0)
     assert np.array_equal(plain, ray, equal_nan=True)

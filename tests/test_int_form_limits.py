@@ -14,7 +14,8 @@ a filter of 10^6) and Cartesian (plain kernel, generated loop, mixed, ray-mapped
   * "integer" cases: the weights are the exact reference's, bit for bit;
   * "float" cases (the device must notice that the scan or the map has no integer form): the bits of the float kernel;
   * always: within 1e-5 of the oracle with its NaN and zero pattern (BASELINE.json north_star) — the float kernel too.
-The float kernel's distance from the exact reference is printed, not bounded (DESIGN.md 3 records it).
+The float kernel's distance from the exact reference is printed, not bounded (DESIGN.md 3 records it); so are the loop
+variants the dense kernels ran (tdr_profile_variants) — tests/test_loop_variants.py is where each variant is demanded.
 None of these inputs indexes memory with a count: a failure here is a wrong number."""
 import numpy as np
 import pytest
@@ -22,6 +23,7 @@ import pytest
 import int_form_cases as T
 from test_cart_su import _run
 from test_shift_uniform import ALL_RAY, _score_both, tdr  # noqa: F401
+from variant_scenes import counted
 
 pytestmark = pytest.mark.gpu
 
@@ -70,8 +72,12 @@ def test_polar_launch_at_the_limits(tdr, oracle, name):
     tail = m.dev.dict.cpu().numpy()[2048:2050].view(np.uint32)      # the dictionary as integers: q, "has an integer form"
     assert int(tail[1]) == (0 if name == "dictionary_at_2p32" else 1) and (int(tail[0]) == 23 or not tail[1])
     m.samplePtsPolar((nb, nr), case["ang_res"])
-    runs = [_score_both(pkg, k, m, case["scan"], case["res"], case["states"], case["params"], span=span,
-                        ctx=k.score_ctx_create() if span == 3.0 else None) for span in (0.0, 3.0, ALL_RAY)]
+    runs = []
+    for span in (0.0, 3.0, ALL_RAY):
+        r, v = counted(k, lambda: _score_both(pkg, k, m, case["scan"], case["res"], case["states"], case["params"], span=span,
+                                              ctx=k.score_ctx_create() if span == 3.0 else None))
+        print(f"{name} polar, span {span:g}: variant counters {v}")     # which loops of the dense kernel the case reached
+        runs.append(r)
     floats = [r[0][0] for r in runs]
     assert all(np.array_equal(floats[0], f, equal_nan=True) for f in floats[1:])
     _check(case, floats[0], [r[1][0] for r in runs], exact, ref)
@@ -85,8 +91,11 @@ def test_cartesian_launch_at_the_limits(tdr, oracle, name):
     m = pkg.TopDownMap(pkg.Params(resolution=1.0), case["maps"], case["mask"], kernels=k)
     m.setWindow(rows, cols)
     st, scan, res = case["states"], case["scan"], case["res"]
-    ints = [_run(pkg, k, m, st, scan, res, 32, 0.0),        # every particle dense, the generated loop
+    dense, v_dense = counted(k, lambda: _run(pkg, k, m, st, scan, res, 32, 0.0))     # every particle dense, the generated loop
+    mixed, v_mixed = counted(k, lambda: _run(pkg, k, m, st, scan, res, 32, 3.0))
+    print(f"{name} cart: variant counters, every particle dense {v_dense}, mixed launch {v_mixed}")
+    ints = [dense,
             _run(pkg, k, m, st, scan, res, 0, 0.0),         # ... the plain kernel
-            _run(pkg, k, m, st, scan, res, 32, 3.0),        # mixed
+            mixed,
             _run(pkg, k, m, st, scan, res, 32, ALL_RAY)]    # every particle through the ray-mapped kernel
     _check(case, _run(pkg, k, m, st, scan, res, 32, 0.0, mode=0), ints, exact, ref)

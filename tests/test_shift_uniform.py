@@ -9,6 +9,8 @@ path whatever the padding costs."""
 import numpy as np
 import pytest
 
+from variant_scenes import counted
+
 pytestmark = pytest.mark.gpu
 
 N_TOTAL = 1_000_000
@@ -151,11 +153,24 @@ def test_shift_uniform_on_a_fully_known_map(tdr, oracle, holes):
     scan = oracle.raster_polar(sc.pts, cfg.res, cfg.ang_res, sc.lut, cfg.ncls, cfg.nb, cfg.nr)
     ref = oracle.compute_weights(oracle.OracleMap(maps, mask, 1.0), oracle.polar_table(cfg.nb, cfg.nr, cfg.ang_res),
                                  cfg.nb, cfg.nr, scan, cfg.res, oracle.make_params(cfg.ncls, **params), st.copy())
-    (raw0, _), (raw2, _) = _score_both(pkg, k, m, scan, cfg.res, st, params)
+    # (tdr_profile_variants: [0..2] the workgroup's box all known / inside / general, [3..5] the wave's own, [6] the far path)
+    ((raw0, _), (raw2, _)), v = counted(k, lambda: _score_both(pkg, k, m, scan, cfg.res, st, params))
+    print(f"holes {holes}: variant counters {v}")
+    assert v[0] + v[3] > 0, v                         # the loop the test is about ran
     _assert_float_form_agrees(raw0, raw2)
     _assert_weights(raw2, ref)
     (_, _), (raw4, _) = _score_both(pkg, k, m, scan, cfg.res, st, params, span=ALL_RAY)
     assert np.array_equal(raw2, raw4, equal_nan=True)
+    if holes == "none":
+        # the particles whose windows stay inside the map (24 rings of one cell, two cells of margin), scored alone: no
+        # sector of theirs is general or far — and their weights are those they had among the others
+        keep = np.flatnonzero((np.minimum(st["init_x_px"], st["init_y_px"]) >= 26) &
+                              (np.maximum(st["init_x_px"], st["init_y_px"]) <= 420 - 27))
+        assert len(st) - 64 <= len(keep) < len(st)
+        ((_, _), (raw5, _)), v = counted(k, lambda: _score_both(pkg, k, m, scan, cfg.res, st[keep], params))
+        print(f"holes {holes}, windows inside: variant counters {v}")
+        assert v[0] + v[3] > 0 and v[2] == 0 and v[5] == 0 and v[6] == 0, v
+        assert np.array_equal(raw5, raw2[keep], equal_nan=True)
 
 
 @pytest.mark.parametrize("kind", ["empty", "dense", "fractional", "one bin"])
