@@ -583,7 +583,11 @@ int tdr_profile_shares(double* dense_ms, double* scattered_ms, int64_t* scattere
 /* With tdr_profile_enable(2) — never inside a timed region: an atomic per wave-sector slows the kernels — the dense kernels count which loop variant each wave-sector (polar) / wave-segment (Cartesian) ran; reads
  * and resets the 16 counters (synchronises): [0..2] score_polar_su_kernel with the workgroup's staged box — every cell known /
  * every cell inside the map / general; [3..5] the same with the wave's own box; [6] its far path; [8..10]
- * score_cart_su_kernel — all known / inside / general; [11] its plain steps (a box that did not fit). */
+ * score_cart_su_kernel — all known / inside / general; [11] its plain steps (a box that did not fit).
+ * The 40-rotation init search counts the 64-particle batches whose results each of its passes wrote (one atomic per
+ * workgroup; a batch with nothing to initialise counts nothing): [12] the matrix-core pass on half records, [13] the one
+ * that splits the records on the fly, [14] the one on wide records, [15] the vector kernel — alone, or redoing a search whose
+ * scan counts did not fit f16 (then the matrix-core pass has counted the same batches too). */
 int tdr_profile_variants(int64_t out[16]);
 
 /* The library reads NOTHING from the process environment: behaviour switches are these calls (and the tdr_config_* calls

@@ -138,6 +138,12 @@ def test_random_init_search_against_oracle(env, oracle, seed, ncls, pile):
     m.samplePtsPolar((nb, nr), cfg.ang_res)
     f = pkg.ParticleFilter(len(st), m, pkg.FilterParams(**params), seed=seed, kernels=k, init_particles=False)
     f.set_states(st)
+    # the same choice held to the exactly summed COST (the first 160 particles): the first candidate of its shift class,
+    # within 2e-5 of the minimum; gated particles untouched; theta 0 where no candidate can win
+    import init_exact_ref as X
+    nx = min(len(st), 160)
+    exact = X.Search(oracle, maps, mask, cfg.map_resolution, tab, nb, nr, scan_o, cfg.res, fpo, st[:nx])
+
     def search_and_check():
         # score only: read the states back before the resample shuffles them
         f.set_states(st)
@@ -159,6 +165,8 @@ def test_random_init_search_against_oracle(env, oracle, seed, ncls, pile):
             _assert_weights(raw_g[diff], raw2[diff], 1e-5)
             tie = np.abs(raw2[diff] - raw_o[diff]) / np.maximum(np.abs(raw_o[diff]), 1e-30)
             assert np.nanmax(tie, initial=0.0) <= 2e-5, f"chosen rotation is not a near-tie: {np.nanmax(tie):.2e}"
+        X.check_choice(exact, st["theta"][:nx], got["theta"][:nx], got["have_init"][:nx], raw_g[:nx], raw_o[:nx],
+                       st["have_init"][:nx])
 
     search_and_check()
     # The same search on pre-split half records (score_init_half_kernel through tdr_map_desc.rec16; by default only

@@ -1121,6 +1121,11 @@ def test_init_search_c1(tdr, oracle):
         tie = np.abs(ref2[differ] - ref[differ]) / np.maximum(np.abs(ref[differ]), 1e-30)
         assert np.nanmax(tie, initial=0.0) <= 2e-5, f"chosen rotation is not a near-tie: {np.nanmax(tie):.2e}"
     assert pre["have_init"].all()
+    # ... and on the COST, exactly summed: the first candidate of its shift class, within 2e-5 of the minimum
+    import init_exact_ref as X
+    exact = X.Search(oracle, sc.class_maps, sc.class_mask, 1.0, tab, cfg.nb, cfg.nr, scan, cfg.res,
+                     oracle.make_params(cfg.ncls), st)
+    X.check_choice(exact, st["theta"], pre["theta"], pre["have_init"], f.raw_weights(), ref, st["have_init"])
 
 
 @pytest.mark.parametrize("ncls", [8, 11, 12, 15])
@@ -1171,6 +1176,15 @@ def test_init_search_on_the_matrix_cores_for_wide_records(tdr, oracle, ncls):
             tie = np.abs(ref2[~same] - ref[~same]) / np.maximum(np.abs(ref[~same]), 1e-30)
             assert np.nanmax(tie, initial=0.0) <= 2e-5, f"mfma={on}: chosen rotation is not a near-tie: {np.nanmax(tie):.2e}"
     assert (got[0][1]["theta"] != got[1][1]["theta"]).mean() < 0.02
+    # ... and on the COST, exactly summed (the first 160 particles, the four at the edges among them): the first candidate
+    # of its shift class, within 2e-5 of the minimum
+    import init_exact_ref as X
+    nx = 160
+    exact = X.Search(oracle, sc.class_maps, sc.class_mask, 1.0, tab, cfg.nb, cfg.nr, scan, cfg.res, fpo, st[:nx])
+    for on in (0, 1):
+        raw, sts = got[on]
+        X.check_choice(exact, st["theta"][:nx], sts["theta"][:nx], sts["have_init"][:nx], raw[:nx], ref[:nx],
+                       st["have_init"][:nx])
 
 
 def test_freeze_scale_and_shift_init(tdr, oracle, g):

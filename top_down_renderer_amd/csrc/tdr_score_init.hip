@@ -47,7 +47,28 @@ struct InitArgs {
   float* res_theta;  // [n] chosen rotation
   float* res_flag;   // [n] 0 = untouched, 1 = initialised, 2 = initialised but every rotation scored NaN
                      //     (weight 1/(FLT_MAX + reg), state_particle.cpp:193,212)
+  uint32_t* stats;   // NULL, or (tdr_profile_enable(2)) the 16 counters of tdr_profile_variants: every workgroup that
+                     // writes results adds one to its pass's slot — [12] half records, [13] on the fly, [14] wide, [15] vector
 };
+// one atomic per workgroup, where its results are written (a workgroup that left early wrote none and counts nothing)
+__device__ __forceinline__ void init_count_pass(const InitArgs& a, int slot) {
+  if (a.stats && threadIdx.x == 0) atomicAdd(a.stats + slot, 1u);
+}
+// The matrix-core passes take the weighted distances 0.01 w_c d_c as f16 pairs hi + lo.  lo is exact only while it stays a
+// normal f16 (>= 2^-14; below that its step is 2^-24 whatever its size), so every 0.01 w_c is first multiplied by ONE
+// power of two that brings the largest of them into [1, 2): exact, the same factor on every candidate's cost — the minimum
+// does not move — and with the map's distances (at most 50) far from f16's range at the other end.  An operand
+// v = w_c' d_c >= 2^-4 then has hi + lo within 2^-20 of it (relative).
+__device__ __forceinline__ float init_weight_pow2(const tdr_filter_params& fp, int ncls) {
+  float mx = 0.f;
+#pragma unroll
+  for (int c = 0; c < TDR_MAX_CLASSES; c++)
+    if (c < ncls) mx = fmaxf(mx, fabsf((float)(0.01 * (double)fp.class_weights[c])));
+  if (!(mx > 0.f) || !(mx <= 3.402823466e+38f)) return 1.f;
+  int e;
+  (void)frexpf(mx, &e);   // mx = f * 2^e, f in [0.5, 1)
+  return ldexpf(1.f, min(max(1 - e, -100), 100));
+}
 
 // Each search kernel is a body (bx: the workgroup's index among its filter's batches of 64 particles) behind two wrappers:
 // the standalone kernel passes its kernel arguments and blockIdx.x, the batched one (tdr_batch_step) finds
@@ -209,6 +230,7 @@ __device__ __forceinline__ void score_init_body(const InitArgs& a, int bx) {
     a.res_theta[p] = bt >= 0 ? a.theta[bt] : 0.f;  // :205 (best_theta stays 0 if nothing won)
     a.res_flag[p] = bt < 0 ? 2.f : 1.f;
   }
+  init_count_pass(a, 15);
 }
 template <int NV4, bool KSLOT, bool USCALE>
 __global__ __launch_bounds__(64 * INIT_WAVES) void score_init_kernel(InitArgs a) {
@@ -241,7 +263,8 @@ __global__ __launch_bounds__(64 * INIT_WAVES) void score_init_batch_kernel(const
 // (4t + (l>>4) + s_m), m = l&15 (+16, +32 for the second and third tile of candidates), one ds_read_b128 each.
 //   * scan counts are integers: exact in f16 up to 2048 (a larger count raises *inexact and score_init_kernel redoes
 //     the search on the vector units);
-//   * distances (times 0.01 w_c, in f32) are split hi + lo into two f16 (relative error <= 2^-20), two MFMAs;
+//   * distances (times 0.01 w_c, in f32, times the one power of two of init_weight_pow2) are split hi + lo into two f16
+//     (relative error <= 2^-20 from 2^-4 up, see there), two MFMAs;
 //   * the normalisation  sum scanΣ * known  is a third MFMA with only slot 7 of B set; the known count is a plain add.
 // Products are exact and accumulate in f32 like the vector version.  Only the choice of the rotation comes out of
 // here; the weight itself is computed by the regular scoring pass at that rotation.
@@ -287,6 +310,11 @@ __device__ __forceinline__ void score_init_mfma_body(const InitArgs& a, int bx, 
   float wc[7];
 #pragma unroll
   for (int c = 0; c < 7; c++) wc[c] = c < a.ncls ? (float)(0.01 * (double)a.fp.class_weights[c]) : 0.f;
+  if constexpr (!UNITW) {
+    const float w2 = init_weight_pow2(a.fp, a.ncls);
+#pragma unroll
+    for (int c = 0; c < 7; c++) wc[c] *= w2;
+  }
   tdr_f4 accC[INITM_TILES], accN[INITM_TILES];
 #pragma unroll
   for (int T = 0; T < INITM_TILES; T++) { accC[T] = (tdr_f4){0.f, 0.f, 0.f, 0.f}; accN[T] = (tdr_f4){0.f, 0.f, 0.f, 0.f}; }
@@ -406,6 +434,7 @@ __device__ __forceinline__ void score_init_mfma_body(const InitArgs& a, int bx, 
     a.res_theta[p] = bm >= 0 ? a.theta[bm] : 0.f;  // :205 (best_theta stays 0 if nothing won)
     a.res_flag[p] = bm < 0 ? 2.f : 1.f;
   }
+  init_count_pass(a, 13);
 }
 template <bool USCALE, bool UNITW, bool SEVEN>
 __global__ __launch_bounds__(256) void score_init_mfma_kernel(InitArgs a, int* __restrict__ inexact) {
@@ -458,6 +487,11 @@ __device__ __forceinline__ void score_init_mfma_wide_body(const InitArgs& a, int
   float wc[16];
 #pragma unroll
   for (int c = 0; c < 16; c++) wc[c] = (c < a.ncls && c < TDR_MAX_CLASSES) ? (float)(0.01 * (double)a.fp.class_weights[c < TDR_MAX_CLASSES ? c : 0]) : 0.f;
+  {
+    const float w2 = init_weight_pow2(a.fp, a.ncls);
+#pragma unroll
+    for (int c = 0; c < 16; c++) wc[c] *= w2;
+  }
   tdr_f4 accC[INITM_TILES], accN[INITM_TILES];
 #pragma unroll
   for (int T = 0; T < INITM_TILES; T++) { accC[T] = (tdr_f4){0.f, 0.f, 0.f, 0.f}; accN[T] = (tdr_f4){0.f, 0.f, 0.f, 0.f}; }
@@ -587,6 +621,7 @@ __device__ __forceinline__ void score_init_mfma_wide_body(const InitArgs& a, int
     a.res_theta[p] = bm >= 0 ? a.theta[bm] : 0.f;  // :205 (best_theta stays 0 if nothing won)
     a.res_flag[p] = bm < 0 ? 2.f : 1.f;
   }
+  init_count_pass(a, 14);
 }
 template <int NV4, bool USCALE>
 __global__ __launch_bounds__(256) void score_init_mfma_wide_kernel(InitArgs a, int* __restrict__ inexact) {
@@ -603,7 +638,8 @@ __global__ __launch_bounds__(256) void score_init_mfma_wide_batch_kernel(const I
 // score_init_mfma_kernel spends most of its vector instructions turning a gathered f32 record into the f16 hi / lo
 // operands (weights, two conversions and a subtraction per pair, the zeroing of ragged lanes), per sample per particle.
 // That work depends on the cell alone.  half_records_kernel does it ONCE per cell into a 32-byte record
-//     H = {hi_0 .. hi_5, hi_6 | 0, 0}   L = {lo_0 .. lo_5, lo_6 | 0, unknown}      (f16; hi + lo = w_c * 0.01 * d_c)
+//     H = {hi_0 .. hi_5, hi_6 | 0, 0}   L = {lo_0 .. lo_5, lo_6 | 0, unknown}      (f16; hi + lo = 2^k * w_c * 0.01 * d_c,
+//                                                                                   2^k: init_weight_pow2; d_c with unitw)
 // laid out like the dense records (guarded row-major grid, guard cells = distance 0, unknown; one all-zero record behind
 // the grid for lanes without a sample), so that a lane's two 16-byte loads ARE the B fragments: H as it is, L with its
 // last half cleared.  The scan side is ONE LDS image per ring, {c_0 .. c_5, c_6 | 0, sum c}: its slot 7 meets a zero in H
@@ -630,8 +666,9 @@ __global__ __launch_bounds__(256) void half_records_kernel(const float4* __restr
 #pragma unroll
   for (int k = 0; k < 8; k++) v[k] = (k < RF - 1 && k < 7 && k < ncls) ? m[k < RF ? k : 0] : 0.f;   // the distances
   if (!unitw) {
+    const float w2 = init_weight_pow2(fp, ncls);
 #pragma unroll
-    for (int k = 0; k < 7; k++) v[k] *= k < ncls ? (float)(0.01 * (double)fp.class_weights[k]) : 0.f;
+    for (int k = 0; k < 7; k++) v[k] *= k < ncls ? (float)(0.01 * (double)fp.class_weights[k]) * w2 : 0.f;
   }
   union { tdr_h2 h[4]; uint4 u; } H, L;
 #pragma unroll
@@ -835,6 +872,7 @@ __device__ __forceinline__ void score_init_half_body(const InitArgs& a, int bx, 
     a.res_theta[p] = bm >= 0 ? a.theta[bm] : 0.f;  // :205 (best_theta stays 0 if nothing won)
     a.res_flag[p] = bm < 0 ? 2.f : 1.f;
   }
+  init_count_pass(a, 12);
 }
 template <bool USCALE, int AHEAD>
 __global__ __launch_bounds__(256) void score_init_half_kernel(InitArgs a, const uint4* __restrict__ rec16,
@@ -1013,6 +1051,7 @@ static InitArgs make_init_args(const tdr_map_desc* map, const float* tab, const 
   float* d_theta = reinterpret_cast<float*>(d_shift + INIT_MAXROT);
   ia.shift = d_shift; ia.theta = d_theta; ia.nrot = reinterpret_cast<int*>(d_theta + INIT_MAXROT);
   ia.only_if = nullptr;
+  ia.stats = tdr_profile_stats_ptr();
   return ia;
 }
 // the pre-split half records of `map` for these class weights, into the map owner's scratch
