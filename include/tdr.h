@@ -1210,7 +1210,8 @@ int tdr_k_viz_compose_jobs(const tdr_viz_job* jobs_dev, int k, int64_t max_out_p
  * out_bgr_host = NULL only gets its size.  Refused with TDR_ERR_ARG before any device work, every output (images and
  * sizes) untouched: k < 1, a null array or entry, a filter twice, a sharded filter, a filter without a background, an
  * invalid published size, bad arrows, too little room in any request.
- * Out of scope: sharded filters, one shared device background for several filters, one "fleet" image of all robots. */
+ * Out of scope: sharded filters.  One shared device background for several filters and one image of all robots are the
+ * fleet picture below; this call keeps one picture and one background per filter. */
 typedef struct tdr_viz_request {
   const int32_t* extra_arrows;   /* [m][4], may be NULL when m = 0 */
   int32_t m, pad;
@@ -1219,6 +1220,66 @@ typedef struct tdr_viz_request {
   int32_t out_h, out_w;          /* set by the call */
 } tdr_viz_request;
 int tdr_batch_visualize(tdr_filter* const* f, int k, float pub_scale, tdr_viz_request* req, void* stream);
+
+/* ---- the fleet picture: k robots in one image over one background held by their map ----------------------
+ * A DEFINITION like the particle picture, parity unpinned for the same reason (what OpenCV would draw anti-aliased and in
+ * particle order is replaced by the coverage rule); the reference shows several robots only as separate displays
+ * (survey_mult.rviz).  It draws k filters (1 <= k <= TDR_FLEET_MAX) that share one map over one H x W BGR8 background,
+ * 11 <= H, W <= 32768, held by the map handle.  Every primitive, integer conversion, clipping rule and range limit is
+ * the particle picture's, unchanged: Arrow, Disc, the segment coverage rule, the mixture polyline, the max-likelihood
+ * arrow, the +-2^20 limit, the published size and the fixed-point bilinear resample.  New are the colours and the
+ * composition over robots:
+ *   Palette: uint8 [k][3][3], for robot i the BGR of its particle arrows, of its border dots and of its estimate.  The
+ *     estimate is layer 4 of the particle picture: the mixture's ellipses, their heading arrows and, after the first
+ *     update, the max-likelihood arrow.
+ *   Per robot three bit planes (arrows, dots, estimate) drawn exactly as planes 0 - 2 of its particle picture; one further
+ *     plane for the caller's arrows, one int32 [m][4] list for the whole image.
+ *   A pixel takes the first of these that applies:
+ *     1 the caller's arrows, (0,255,0);
+ *     2 the estimate colour of the HIGHEST-INDEXED robot whose estimate plane covers the pixel;
+ *     3 the dot colour of the highest-indexed robot whose dot plane covers it;
+ *     4 the arrow colour of the highest-indexed robot whose arrow plane covers it;
+ *     5 the background.
+ *   The order is layer-major: every robot's dots lie over every robot's arrows and every estimate over every dot,
+ *   whatever the indices.  "Highest index wins" makes the image a function of the planes alone: it does not depend on
+ *   launch order or on atomics.  With k = 1 and the palette {(0,0,255), (0,255,0), (255,0,0)} the image is
+ *   tdr_filter_visualize's, byte for byte.
+ * Layer 1.  tdr_k_viz_particles_jobs and tdr_k_viz_segments_jobs draw the whole fleet: one job per robot with its own
+ * planes 0 - 2, all jobs with the same H and W.  A segment of plane 3 in robot i's list goes to the words that follow
+ * robot i's plane 2, so the caller's arrows travel in ONE robot's list and the plane behind that robot's three is the
+ * image's green plane (tdr_batch_visualize_fleet: the last robot's).  tdr_k_viz_compose_fleet composes the published
+ * image in one launch: the forms of tdr_k_viz_compose (per-pixel copy; 16 pixels a thread with 16-byte loads and stores
+ * when W % 16 == 0 and both images are 16-byte aligned; the four-tap resample composing each tap on the fly).  It reads
+ * jobs_dev[i].planes (a job whose H, W differ from the call's, or without planes, draws nothing); palette_host travels in
+ * the kernel arguments; background and out_bgr are device images, green_plane tdr_viz_plane_words(H, W) device words.  No
+ * allocation, no sync; refused with TDR_ERR_ARG before the launch: null pointers, k outside 1..TDR_FLEET_MAX, H, W or
+ * the published size out of range. */
+#define TDR_FLEET_MAX 64
+int tdr_k_viz_compose_fleet(const tdr_viz_job* jobs_dev, int k, const uint8_t* palette_host, const uint8_t* background,
+                            int H, int W, const uint32_t* green_plane, int out_h, int out_w, uint8_t* out_bgr,
+                            void* stream);
+/* Layer 2.  tdr_map_set_viz_background stores ONE device copy of the background (host BGR8 [H][W][3]) on the map;
+ * tdr_map_set_viz_background_labels uploads one byte a cell (uint8 [H][W]) and colours it on the device with lut_bgr (256
+ * BGR triplets, tdr_k_label_picture).  Both return after the copy is complete; the background stays until either is
+ * called again, and no map update (tdr_map_set*, tdr_filter_update_map*, the incremental updates) touches it, exactly as
+ * a filter's own background.  The filters' own backgrounds are another matter: tdr_filter_visualize and
+ * tdr_batch_visualize still refuse a filter without its own, whatever its map holds.
+ * tdr_batch_visualize_fleet draws the fleet picture of f[0..k-1] over their map's background: `stream` first waits for
+ * every filter's own stream; the overlays are built on the host (the max-likelihood arrows in the segments launch, from
+ * the device states) and uploaded once; the planes (3k + 1 of them in one arena owned by the calling thread) are cleared
+ * with one memset; particles, segments and compose are one launch each; one device-to-host copy into out_bgr_host
+ * (`capacity` bytes, 3 * out_h * out_w needed) and one wait.  *out_h / *out_w are set whenever the call is not refused;
+ * out_bgr_host = NULL only asks for them.  Polar and Cartesian filters alike, filters with 0 particles too; no filter is
+ * changed.  Refused with TDR_ERR_ARG before any device work, the image and the sizes untouched: k < 1 or
+ * k > TDR_FLEET_MAX, a null array or entry, a filter twice, a sharded filter, filters on different maps, a map without a
+ * background, a null palette, bad arrows, an invalid published size (NaN scale included), too little room.
+ * Out of scope: sharded filters, anti-aliasing, several maps or background sizes in one image, more than TDR_FLEET_MAX
+ * robots, an arrow list per robot. */
+int tdr_map_set_viz_background(tdr_map* m, const uint8_t* bgr_host, int H, int W);
+int tdr_map_set_viz_background_labels(tdr_map* m, const uint8_t* labels_host, int H, int W, const uint8_t* lut_bgr);
+int tdr_batch_visualize_fleet(tdr_filter* const* f, int k, float pub_scale, const uint8_t* palette,
+                              const int32_t* extra_arrows, int m, uint8_t* out_bgr_host, int64_t capacity, int* out_h,
+                              int* out_w, void* stream);
 
 /* ---- the scan picture: the node's two scan images and its map background on the device (src/top_down_render.cpp:246-305,
  * :584) ---------------------------------------------------------------------------------------------------

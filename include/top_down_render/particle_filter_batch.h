@@ -89,6 +89,29 @@ class ParticleFilterBatch {
     }
     tdr_viz::renderBatch(handles, pub_scale, arrows, outs, stream);
   }
+  // The fleet picture (include/tdr.h): every filter's cloud in ONE image over the background their map holds
+  // (TopDownMap::setVizBackground), palette[i] the colours of filter i, arrows one list for the image; one launch per stage,
+  // one read-back and one wait.  Throws on a refused call (filters on different maps, a map without a background, more
+  // than TDR_FLEET_MAX filters, a null, repeated or sharded filter) before any device work.
+  void renderFleet(const std::vector<ParticleFilter*>& filters, float pub_scale,
+                   const std::vector<tdr_viz::FleetColours>& palette, const std::vector<std::array<int, 4>>& arrows,
+                   tdr_viz::Image& out, void* stream = nullptr) {
+    std::vector<tdr_filter*> handles(filters.size(), nullptr);
+    for (size_t i = 0; i < filters.size(); i++) {
+      if (!filters[i]) throw std::invalid_argument("ParticleFilterBatch::renderFleet: null filter");
+      handles[i] = filters[i]->handle();
+    }
+    tdr_viz::renderFleet(handles, pub_scale, palette, arrows, out, stream);
+  }
+  void renderFleet(const std::vector<ParticleFilter*>& filters, float pub_scale,
+                   const std::vector<tdr_viz::FleetColours>& palette, const std::vector<std::array<int, 4>>& arrows,
+                   std::vector<uint8_t>& out, int& out_h, int& out_w, void* stream = nullptr) {
+    tdr_viz::Image img;
+    renderFleet(filters, pub_scale, palette, arrows, img, stream);
+    out.swap(img.bgr);
+    out_h = img.h;
+    out_w = img.w;
+  }
   // tdr_config_tuning("batch_init_search"), process-wide: with true a filter that may still hold a particle without a
   // heading — a cold start (init_pos_deg_theta = inf), a gated filter (force_on_map, unknown scale) — joins the batch, its
   // 40-rotation search part of the batch's scoring stage, same bits; false (the default): its standalone calls inside step()

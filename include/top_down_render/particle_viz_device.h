@@ -20,18 +20,22 @@ namespace tdr_viz {
 
 // bgr: an 8-bit image of three channels (B, G, R), the one the node draws on.  (Templates on the image type, like the
 // members that call them: they are compiled only where a host uses them.)
-template <class MatT>
-void setBackground(tdr_filter* f, const MatT& bgr) {
+// The owner is a filter (its own background, the particle picture's) or a map (one background for every filter on it, the
+// fleet picture's).
+inline int setBackgroundBytes(tdr_filter* f, const uint8_t* bgr, int h, int w) { return tdr_filter_set_viz_background(f, bgr, h, w); }
+inline int setBackgroundBytes(tdr_map* m, const uint8_t* bgr, int h, int w) { return tdr_map_set_viz_background(m, bgr, h, w); }
+template <class HandleT, class MatT>
+void setBackground(HandleT* owner, const MatT& bgr) {
   if (bgr.empty() || bgr.channels() != 3 || bgr.elemSize() != 3)
     throw std::invalid_argument("setVizBackground: an 8-bit image of three channels is needed");
   if (bgr.isContinuous()) {
-    if (tdr_filter_set_viz_background(f, bgr.template ptr<uint8_t>(), bgr.rows, bgr.cols) != TDR_OK) fail("setVizBackground");
+    if (setBackgroundBytes(owner, bgr.template ptr<uint8_t>(), bgr.rows, bgr.cols) != TDR_OK) fail("setVizBackground");
     return;
   }
   std::vector<uint8_t> packed((size_t)bgr.rows * bgr.cols * 3);
   for (int r = 0; r < bgr.rows; r++)
     std::memcpy(packed.data() + (size_t)r * bgr.cols * 3, bgr.template ptr<uint8_t>(r), (size_t)bgr.cols * 3);
-  if (tdr_filter_set_viz_background(f, packed.data(), bgr.rows, bgr.cols) != TDR_OK) fail("setVizBackground");
+  if (setBackgroundBytes(owner, packed.data(), bgr.rows, bgr.cols) != TDR_OK) fail("setVizBackground");
 }
 
 // the published image as bytes [out_h][out_w][3]

@@ -121,20 +121,26 @@ inline void rendererAnalog(const tdr_renderer* r, int cls, float scale, uint8_t*
 
 // the particle picture's background from the label image the node colours (aerialMapCallback, :584): labels is an 8-bit
 // image of one channel
-template <class MatT>
-void setBackgroundLabels(tdr_filter* f, const MatT& labels, const SemanticColorLut& lut) {
+inline int setBackgroundLabelBytes(tdr_filter* f, const uint8_t* labels, int h, int w, const uint8_t* table) {
+  return tdr_filter_set_viz_background_labels(f, labels, h, w, table);
+}
+inline int setBackgroundLabelBytes(tdr_map* m, const uint8_t* labels, int h, int w, const uint8_t* table) {
+  return tdr_map_set_viz_background_labels(m, labels, h, w, table);
+}
+template <class HandleT, class MatT>
+void setBackgroundLabels(HandleT* owner, const MatT& labels, const SemanticColorLut& lut) {
   if (labels.empty() || labels.channels() != 1 || labels.elemSize() != 1)
     throw std::invalid_argument("setVizBackground: an 8-bit label image of one channel is needed");
   const std::array<uint8_t, 768> table = colourTable(lut);
   if (labels.isContinuous()) {
-    if (tdr_filter_set_viz_background_labels(f, labels.template ptr<uint8_t>(), labels.rows, labels.cols, table.data()) != TDR_OK)
+    if (setBackgroundLabelBytes(owner, labels.template ptr<uint8_t>(), labels.rows, labels.cols, table.data()) != TDR_OK)
       fail("setVizBackground");
     return;
   }
   std::vector<uint8_t> packed((size_t)labels.rows * labels.cols);
   for (int r = 0; r < labels.rows; r++)
     std::memcpy(packed.data() + (size_t)r * labels.cols, labels.template ptr<uint8_t>(r), (size_t)labels.cols);
-  if (tdr_filter_set_viz_background_labels(f, packed.data(), labels.rows, labels.cols, table.data()) != TDR_OK)
+  if (setBackgroundLabelBytes(owner, packed.data(), labels.rows, labels.cols, table.data()) != TDR_OK)
     fail("setVizBackground");
 }
 
@@ -162,6 +168,29 @@ inline void renderBatch(const std::vector<tdr_filter*>& filters, float pub_scale
     req[i].capacity = (int64_t)outs[i].bgr.size();
   }
   if (tdr_batch_visualize(filters.data(), (int)k, pub_scale, req.data(), stream) != TDR_OK) fail("renderViz");
+}
+
+// One robot's colours in the fleet picture (include/tdr.h): BGR of its particle arrows, its border dots, its estimate
+// (mixture and max-likelihood arrow).  classic() is what renderViz draws one robot with.
+struct FleetColours {
+  std::array<uint8_t, 3> arrows, dots, estimate;
+  static FleetColours classic() { return FleetColours{{0, 0, 255}, {0, 255, 0}, {255, 0, 0}}; }
+};
+// the fleet picture of filters on one map, over the background the map holds, in one tdr_batch_visualize_fleet
+inline void renderFleet(const std::vector<tdr_filter*>& filters, float pub_scale, const std::vector<FleetColours>& palette,
+                        const std::vector<std::array<int, 4>>& arrows, Image& out, void* stream) {
+  static_assert(sizeof(std::array<int, 4>) == 4 * sizeof(int32_t), "arrows are int32 [m][4]");
+  static_assert(sizeof(FleetColours) == 9, "the palette is uint8 [k][3][3]");
+  if (palette.size() != filters.size()) throw std::invalid_argument("renderFleet: one FleetColours per filter");
+  const int32_t* a = arrows.empty() ? nullptr : reinterpret_cast<const int32_t*>(arrows.data());
+  const uint8_t* pal = palette.empty() ? nullptr : reinterpret_cast<const uint8_t*>(palette.data());
+  if (tdr_batch_visualize_fleet(filters.data(), (int)filters.size(), pub_scale, pal, a, (int)arrows.size(), nullptr, 0, &out.h,
+                                &out.w, stream) != TDR_OK)
+    fail("renderFleet");
+  out.bgr.resize((size_t)3 * out.h * out.w);
+  if (tdr_batch_visualize_fleet(filters.data(), (int)filters.size(), pub_scale, pal, a, (int)arrows.size(), out.bgr.data(),
+                                (int64_t)out.bgr.size(), &out.h, &out.w, stream) != TDR_OK)
+    fail("renderFleet");
 }
 
 }  // namespace tdr_viz

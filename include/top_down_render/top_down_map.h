@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "tdr.h"
+#include "top_down_render/scan_viz_device.h"
 #include "top_down_render/tdr_compat.h"
 
 class TopDownMap {
@@ -219,6 +220,15 @@ class TopDownMap {
     return have != 0;
   }
   tdr_map* handle() const { return m_; }
+  // The fleet picture's background (include/tdr.h, "the fleet picture"): ONE device copy for every filter on this map,
+  // which ParticleFilterBatch::renderFleet draws all of them over.  Kept until it is set again; updateMap leaves it
+  // alone.  bgr: an 8-bit image of three channels; or the label image the node colours (aerialMapCallback, :584), one
+  // byte a cell, coloured on the device through lut.  The filters' own backgrounds (ParticleFilter::setVizBackground)
+  // are separate.
+  template <class MatT = cv::Mat>
+  void setVizBackground(const MatT& bgr) { tdr_viz::setBackground(m_, bgr); }
+  template <class MatT = cv::Mat>
+  void setVizBackground(const MatT& labels, const SemanticColorLut& lut) { tdr_viz::setBackgroundLabels(m_, labels, lut); }
 
  protected:
   void local_map(int polar, const Eigen::Vector2f& center, float scale_or_rot, float res, int rows, int cols,

@@ -127,10 +127,34 @@ class TopDownRenderCoreBatch {
     }
     batch_.renderViz(filters, pub_scale, arrows, particle_pictures, stream);
   }
+  // Every core's cloud after a takeStep in ONE image over the background the cores' map holds
+  // (TopDownMap::setVizBackground): ParticleFilterBatch::renderFleet over the cores' filters.  palette: one per core;
+  // arrows: one list for the image.  Throws on a refused call.
+  void renderFleetPicture(const std::vector<TopDownRenderCore*>& cores, float pub_scale,
+                          const std::vector<tdr_viz::FleetColours>& palette, const std::vector<std::array<int, 4>>& arrows,
+                          tdr_viz::Image& out, void* stream = nullptr) {
+    batch_.renderFleet(coreFilters(cores, "renderFleetPicture"), pub_scale, palette, arrows, out, stream);
+  }
+  void renderFleetPicture(const std::vector<TopDownRenderCore*>& cores, float pub_scale,
+                          const std::vector<tdr_viz::FleetColours>& palette, const std::vector<std::array<int, 4>>& arrows,
+                          std::vector<uint8_t>& out, int& out_h, int& out_w, void* stream = nullptr) {
+    batch_.renderFleet(coreFilters(cores, "renderFleetPicture"), pub_scale, palette, arrows, out, out_h, out_w, stream);
+  }
   // filters of the last step that took the batched path / their standalone calls (ParticleFilterBatch)
   int lastBatched() const { return batch_.lastBatched(); }
   int lastStandalone() const { return batch_.lastStandalone(); }
 
  private:
+  static std::vector<ParticleFilter*> coreFilters(const std::vector<TopDownRenderCore*>& cores, const char* who) {
+    if (cores.empty()) throw std::invalid_argument(std::string("TopDownRenderCoreBatch::") + who + ": no core");
+    std::vector<ParticleFilter*> filters(cores.size());
+    for (size_t i = 0; i < cores.size(); i++) {
+      if (!cores[i] || !cores[i]->filter_)
+        throw std::invalid_argument(std::string("TopDownRenderCoreBatch::") + who + ": core " + std::to_string(i) +
+                                    " is null or not initialised");
+      filters[i] = cores[i]->filter_;
+    }
+    return filters;
+  }
   ParticleFilterBatch batch_;
 };

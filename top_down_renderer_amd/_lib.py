@@ -333,6 +333,10 @@ SIGNATURES = {
     "tdr_k_viz_segments_jobs": (_i, [_vp, _i, _i, _vp]),
     "tdr_k_viz_compose_jobs": (_i, [_vp, _i, _i64, _vp]),
     "tdr_batch_visualize": (_i, [_vp, _i, _f, _vp, _vp]),
+    "tdr_k_viz_compose_fleet": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "tdr_map_set_viz_background": (_i, [_vp, _vp, _i, _i]),
+    "tdr_map_set_viz_background_labels": (_i, [_vp, _vp, _i, _i, _vp]),
+    "tdr_batch_visualize_fleet": (_i, [_vp, _i, _f, _vp, _vp, _i, _vp, _i64, C.POINTER(_i), C.POINTER(_i), _vp]),
     "tdr_k_scan_picture": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp]),
     "tdr_k_analog_picture": (_i, [_vp, _i64, _f, _vp, _vp]),
     "tdr_k_label_picture": (_i, [_vp, _i64, _vp, _vp, _vp]),

@@ -68,6 +68,21 @@ class MapHandle:
         check(self.L.tdr_map_set_window(self.h, int(rows), int(cols)))
         self.window = (int(rows), int(cols))
 
+    def set_viz_background(self, bgr=None, labels=None, lut=None):
+        """The fleet picture's background, one device copy for every filter on this map: bgr (H, W, 3) uint8, or labels
+        (H, W) uint8 coloured on the device through lut (256 BGR triplets).  It stays until it is set again."""
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, np.uint8)
+            lut = np.ascontiguousarray(lut, np.uint8).ravel()
+            if labels.ndim != 2 or lut.size != 768:
+                raise ValueError("set_viz_background: labels (H, W) and 256 BGR triplets")
+            check(self.L.tdr_map_set_viz_background_labels(self.h, _ptr(labels), labels.shape[0], labels.shape[1], _ptr(lut)))
+            return
+        bgr = np.ascontiguousarray(bgr, np.uint8)
+        if bgr.ndim != 3 or bgr.shape[2] != 3:
+            raise ValueError("set_viz_background: a (H, W, 3) BGR image")
+        check(self.L.tdr_map_set_viz_background(self.h, _ptr(bgr), bgr.shape[0], bgr.shape[1]))
+
     def __del__(self):
         if getattr(self, "h", None):
             self.L.tdr_map_destroy(self.h)
@@ -478,6 +493,30 @@ def visualize_batch(filters, pub_scale, arrows=None, stream=None):
     return outs
 
 
+CLASSIC_PALETTE = ((0, 0, 255), (0, 255, 0), (255, 0, 0))   # one robot's colours in tdr_filter_visualize: arrows, dots, estimate
+
+
+def visualize_fleet(filters, pub_scale, palette, arrows=None, stream=None):
+    """The fleet picture (tdr_batch_visualize_fleet): every filter's cloud in ONE (out_h, out_w, 3) uint8 image over the
+    background their map holds (MapHandle.set_viz_background).  palette: (k, 3, 3) uint8, per robot the BGR of its
+    arrows, its border dots and its estimate; arrows: None or one (m, 4) integer list for the image."""
+    L = _lib.load()
+    k = len(filters)
+    pal = np.ascontiguousarray(palette, np.uint8)
+    if pal.size != 9 * k:
+        raise ValueError("visualize_fleet: the palette is (k, 3, 3) BGR bytes")
+    arr = None if arrows is None or len(arrows) == 0 else np.ascontiguousarray(arrows, np.int32).reshape(-1, 4)
+    m, ap = (0, None) if arr is None else (len(arr), _ptr(arr))
+    hs = (_vp * max(k, 1))(*[f.h for f in filters])
+    st = _vp(stream) if stream else None
+    oh, ow = C.c_int(), C.c_int()
+    check(L.tdr_batch_visualize_fleet(hs, k, C.c_float(pub_scale), _ptr(pal), ap, m, None, 0, C.byref(oh), C.byref(ow), st))
+    out = np.zeros((oh.value, ow.value, 3), np.uint8)
+    check(L.tdr_batch_visualize_fleet(hs, k, C.c_float(pub_scale), _ptr(pal), ap, m, _ptr(out), out.size, C.byref(oh),
+                                      C.byref(ow), st))
+    return out
+
+
 class _PoseView:
     """What TopDownRenderCore.publishPoseEst asks of its filter, answered from one robot's share of a pose_batch; a
     freezeScale goes to the filter, and the scale is read from it again afterwards (the freeze changes it)."""
@@ -560,3 +599,8 @@ class LoopBatch:
         """The robots' particle pictures after a take_step, each over its filter's own background
         (FilterHandle.set_viz_background): a list of (out_h, out_w, 3) uint8 arrays."""
         return visualize_batch(self.filters, pub_scale, arrows, stream)
+
+    def fleet_picture(self, pub_scale, palette, arrows=None, stream=None):
+        """All robots after a take_step in one image over the map's background (MapHandle.set_viz_background):
+        visualize_fleet of the loop's filters."""
+        return visualize_fleet(self.filters, pub_scale, palette, arrows, stream)

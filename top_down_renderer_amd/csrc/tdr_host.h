@@ -141,6 +141,10 @@ struct tdr_map {
   std::vector<int32_t> inc_tiles;
   std::vector<float> inc_hstage;
   std::vector<uint8_t> inc_hmstage;
+  // the fleet picture's background (tdr_map_set_viz_background*): one device copy for every filter on this map; no map
+  // update touches it
+  DevBuf<uint8_t> viz_bg;
+  int viz_h = 0, viz_w = 0;
 };
 
 struct tdr_renderer {

@@ -578,4 +578,107 @@ int tdr_batch_visualize(tdr_filter* const* f, int k, float pub_scale, tdr_viz_re
   HTRY(hipEventSynchronize(B.done));   // the one wait of the call
   return TDR_OK;
 }
+
+// the fleet picture (include/tdr.h): k robots on one map in one image over the map's background
+int tdr_batch_visualize_fleet(tdr_filter* const* f, int k, float pub_scale, const uint8_t* palette,
+                              const int32_t* extra_arrows, int m, uint8_t* out_bgr_host, int64_t capacity, int* out_h,
+                              int* out_w, void* stream) {
+  if (k < 1 || k > TDR_FLEET_MAX) return failh(TDR_ERR_ARG, "batch_visualize_fleet: k = %d (1 .. %d filters)", k, TDR_FLEET_MAX);
+  if (!f) return failh(TDR_ERR_ARG, "batch_visualize_fleet: null filter array");
+  if (!out_h || !out_w) return failh(TDR_ERR_ARG, "batch_visualize_fleet: null size pointers");
+  for (int i = 0; i < k; i++)
+    if (!f[i]) return failh(TDR_ERR_ARG, "batch_visualize_fleet: filter %d is null", i);
+  {
+    std::vector<const tdr_filter*> seen(f, f + k);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+      return failh(TDR_ERR_ARG, "batch_visualize_fleet: a filter appears twice in the fleet");
+  }
+  for (int i = 0; i < k; i++) {
+    if (f[i]->comm) return failh(TDR_ERR_ARG, "batch_visualize_fleet: filter %d is sharded and has no picture (draw from a one-GPU filter)", i);
+    if (f[i]->map != f[0]->map) return failh(TDR_ERR_ARG, "batch_visualize_fleet: filter %d is on another map than filter 0", i);
+  }
+  const tdr_map* map = f[0]->map;
+  if (!map || map->viz_h < 1) return failh(TDR_ERR_ARG, "batch_visualize_fleet: the map has no background (tdr_map_set_viz_background)");
+  if (!palette) return failh(TDR_ERR_ARG, "batch_visualize_fleet: null palette");
+  if (m < 0 || (m > 0 && !extra_arrows) || m > (1 << 20)) return failh(TDR_ERR_ARG, "batch_visualize_fleet: bad arrows");
+  const int H = map->viz_h, W = map->viz_w;
+  const int oh = viz_pub_dim(H, pub_scale), ow = viz_pub_dim(W, pub_scale);
+  if (oh < 1 || ow < 1 || oh > 32768 || ow > 32768)
+    return failh(TDR_ERR_ARG, "batch_visualize_fleet: scale %g publishes %d x %d pixels (1 .. 32768 a side)", (double)pub_scale, oh, ow);
+  const size_t bytes = (size_t)3 * oh * ow;
+  if (out_bgr_host && (capacity < 0 || (size_t)capacity < bytes))
+    return failh(TDR_ERR_ARG, "batch_visualize_fleet: the image needs %zu bytes, room for %lld", bytes, (long long)capacity);
+  // every robot's estimate (without the max-likelihood arrow, which the segments launch adds from the device state) on
+  // the host; the caller's arrows go into the last robot's list: its plane 3 is the image's green plane (below)
+  std::vector<std::vector<int32_t>> segs((size_t)k);
+  std::vector<int> nseg((size_t)k, 0);
+  if (out_bgr_host)
+    for (int i = 0; i < k; i++) {
+      const tdr_filter* g = f[i];
+      const int mi = i == k - 1 ? m : 0;
+      const int kk = (int)(g->gmm_means.size() / 3), cap = TDR_VIZ_MAX_SEGS(kk, mi);
+      segs[i].resize((size_t)5 * cap);
+      TTRY(tdr_viz_overlay_host(g->gmm_means.data(), g->gmm_covs.data(), kk, nullptr, extra_arrows, mi, H, segs[i].data(),
+                                cap, &nseg[i]));
+    }
+  *out_h = oh;
+  *out_w = ow;
+  if (!out_bgr_host) return TDR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  // staging, host and device alike: [k] jobs, every robot's segments; on the device the picture and the planes follow:
+  // robot i's planes 0 - 2 at 3 i plane sizes, the green plane behind the last robot's
+  const size_t job_bytes = align64(sizeof(tdr_viz_job) * (size_t)k);
+  std::vector<size_t> seg_off((size_t)k);
+  size_t up_bytes = job_bytes;
+  for (int i = 0; i < k; i++) {
+    seg_off[i] = up_bytes;
+    up_bytes += align64((size_t)5 * nseg[i] * sizeof(int32_t));
+  }
+  const size_t pic_end = up_bytes + align64(bytes);
+  const size_t pw = tdr_viz_plane_words(H, W);
+  const size_t dev_bytes = pic_end + ((size_t)3 * k + 1) * pw * sizeof(uint32_t);
+  StageCtx& B = g_viz_stage;
+  TTRY(B.reserve(up_bytes, dev_bytes, s));
+  std::vector<int> all((size_t)k);
+  for (int i = 0; i < k; i++) all[i] = i;
+  TTRY(order_after_filters(f, all, s, "batch_visualize_fleet"));
+  tdr_viz_job* tab = reinterpret_cast<tdr_viz_job*>(B.host);
+  uint32_t* planes = reinterpret_cast<uint32_t*>(B.dev.p + pic_end);
+  uint8_t* out_dev = reinterpret_cast<uint8_t*>(B.dev.p + up_bytes);
+  int64_t max_n = 0;
+  int max_segs = 0;
+  for (int i = 0; i < k; i++) {
+    const tdr_filter* g = f[i];
+    if (nseg[i]) std::memcpy(B.host + seg_off[i], segs[i].data(), (size_t)5 * nseg[i] * sizeof(int32_t));
+    tdr_viz_job& e = tab[i];
+    e = tdr_viz_job{};
+    e.st = g->st.p;
+    e.cap = g->cap;
+    e.n = g->n;
+    e.H = H;
+    e.W = W;
+    e.planes = planes + (size_t)3 * i * pw;
+    e.background = map->viz_bg.p;
+    e.segs = reinterpret_cast<const int32_t*>(B.dev.p + seg_off[i]);
+    e.best = g->have_ml ? g->ml_dev.p + 8 : nullptr;
+    e.n_segs = nseg[i];
+    e.out_h = oh;
+    e.out_w = ow;
+    e.out = out_dev;
+    max_n = std::max(max_n, g->n);
+    max_segs = std::max(max_segs, nseg[i]);
+  }
+  const tdr_viz_job* tab_dev = reinterpret_cast<const tdr_viz_job*>(B.dev.p);
+  HTRY(hipMemcpyAsync(B.dev.p, B.host, up_bytes, hipMemcpyHostToDevice, s));
+  HTRY(hipEventRecord(B.uploaded, s));
+  HTRY(hipMemsetAsync(planes, 0, dev_bytes - pic_end, s));
+  TTRY(tdr_k_viz_particles_jobs(tab_dev, k, max_n, s));
+  TTRY(tdr_k_viz_segments_jobs(tab_dev, k, max_segs, s));
+  TTRY(tdr_k_viz_compose_fleet(tab_dev, k, palette, map->viz_bg.p, H, W, planes + (size_t)3 * k * pw, oh, ow, out_dev, s));
+  HTRY(hipMemcpyAsync(out_bgr_host, out_dev, bytes, hipMemcpyDeviceToHost, s));
+  HTRY(hipEventRecord(B.done, s));
+  HTRY(hipEventSynchronize(B.done));   // the one wait of the call
+  return TDR_OK;
+}
 }  // extern "C"

@@ -436,4 +436,36 @@ int tdr_map_classes_at_point(const tdr_map* m, int px, int py, uint32_t* class_b
   return TDR_OK;
 }
 
+// ---- the fleet picture's background (include/tdr.h, "the fleet picture"): one device copy for every filter on the map ------
+int tdr_map_set_viz_background(tdr_map* m, const uint8_t* bgr_host, int H, int W) {
+  if (!m || !bgr_host) return failh(TDR_ERR_ARG, "map_set_viz_background: null argument");
+  if (H < 11 || W < 11 || H > 32768 || W > 32768)
+    return failh(TDR_ERR_ARG, "map_set_viz_background: a %d x %d image (11 .. 32768 a side)", H, W);
+  const size_t bytes = (size_t)3 * H * W;
+  HTRY(hipDeviceSynchronize());   // (a picture on any stream may still read the old background)
+  TTRY(m->viz_bg.resize(bytes));
+  HTRY(hipMemcpy(m->viz_bg.p, bgr_host, bytes, hipMemcpyHostToDevice));
+  m->viz_h = H;
+  m->viz_w = W;
+  return TDR_OK;
+}
+
+// ... from a label image: one byte a cell goes up, the colour table is applied on the device (tdr_k_label_picture)
+int tdr_map_set_viz_background_labels(tdr_map* m, const uint8_t* labels_host, int H, int W, const uint8_t* lut_bgr) {
+  if (!m || !labels_host || !lut_bgr) return failh(TDR_ERR_ARG, "map_set_viz_background_labels: null argument");
+  if (H < 11 || W < 11 || H > 32768 || W > 32768)
+    return failh(TDR_ERR_ARG, "map_set_viz_background_labels: a %d x %d image (11 .. 32768 a side)", H, W);
+  const size_t cells = (size_t)H * W;
+  DevBuf<uint8_t> labels;   // staging of this call only
+  HTRY(hipDeviceSynchronize());
+  TTRY(m->viz_bg.resize(3 * cells));
+  TTRY(labels.resize(cells));
+  HTRY(hipMemcpy(labels.p, labels_host, cells, hipMemcpyHostToDevice));
+  TTRY(tdr_k_label_picture(labels.p, (int64_t)cells, lut_bgr, m->viz_bg.p, nullptr));
+  HTRY(hipStreamSynchronize(nullptr));
+  m->viz_h = H;
+  m->viz_w = W;
+  return TDR_OK;
+}
+
 }  // extern "C"

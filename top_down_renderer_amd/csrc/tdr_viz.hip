@@ -5,6 +5,8 @@
 //     viz_segments_kernel    one workgroup per overlay segment ORs its pixels into plane 2 or 3
 //     viz_compose_*_kernel   background + planes -> published image (same size: copy with overlay; else the four taps of
 //                            the fixed-point bilinear resample are composed on the fly)
+//     viz_fleet_*_kernel     the fleet picture: the planes 0 - 2 of k robots and one green plane over one
+//                            background, layer-major with the highest index winning, in the same three forms
 // Every pixel set is integer arithmetic (viz_covered), so a primitive's pixels do not depend on who draws it; the
 // double-precision parts of the definition (arrow tips, ellipse vertices) run on the host (tdr_viz_arrow_host,
 // tdr_viz_overlay_host) and reach the device as integers.
@@ -411,6 +413,139 @@ __global__ __launch_bounds__(256) void viz_compose_jobs_kernel(const tdr_viz_job
   }
 }
 
+// ---- the fleet picture: k robots' planes 0 - 2 and one green plane over one background (include/tdr.h) ------------------
+// Layer-major, the highest index wins: green, then per layer estimate / dots / arrows the robots from k - 1 down.  The
+// image is a function of the planes alone.  A workgroup stages what every pixel needs of the k jobs in LDS: the plane
+// pointers (a job of another size, or without planes, gets none and draws nothing) and the colours as b | g << 8 | r << 16.
+struct VizPalette {
+  uint32_t w[TDR_FLEET_MAX * 9 / 4];   // uint8 [TDR_FLEET_MAX][3][3]
+};
+struct VizFleet {
+  const uint32_t* planes[TDR_FLEET_MAX];
+  uint32_t col[TDR_FLEET_MAX * 3];
+};
+__device__ __forceinline__ void viz_fleet_stage(const tdr_viz_job* __restrict__ jobs, int k, const VizPalette& pal, int H,
+                                                int W, VizFleet& s) {
+  for (int i = threadIdx.x; i < k; i += 256) {
+    const uint32_t* p = jobs[i].planes;
+    s.planes[i] = (jobs[i].H == H && jobs[i].W == W) ? p : nullptr;
+  }
+  for (int i = threadIdx.x; i < 3 * k; i += 256) {
+    uint32_t c = 0;
+    for (int ch = 0; ch < 3; ch++) {
+      const int byte = 3 * i + ch;
+      c |= ((pal.w[byte >> 2] >> (8 * (byte & 3))) & 0xFFu) << (8 * ch);
+    }
+    s.col[i] = c;
+  }
+  __syncthreads();
+}
+
+// one pixel: the colour of the first layer that covers it, else the background's
+__device__ __forceinline__ uint32_t viz_fleet_pixel(const VizFleet& s, int k, const uint8_t* __restrict__ bg,
+                                                    const uint32_t* __restrict__ green, int W, int rw, int64_t pw, int y,
+                                                    int x) {
+  const int64_t o = (int64_t)y * rw + (x >> 5);
+  const int sh = x & 31;
+  if ((green[o] >> sh) & 1u) return 0x00FF00u;
+  for (int l = 2; l >= 0; l--)
+    for (int r = k - 1; r >= 0; r--) {
+      const uint32_t* p = s.planes[r];
+      if (p && ((p[l * pw + o] >> sh) & 1u)) return s.col[3 * r + l];
+    }
+  const uint8_t* b = bg + ((int64_t)y * W + x) * 3;
+  return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16);
+}
+
+__global__ __launch_bounds__(256) void viz_fleet_copy_kernel(const tdr_viz_job* __restrict__ jobs, int k, VizPalette pal,
+                                                             const uint8_t* __restrict__ bg, int H, int W, int rw,
+                                                             int64_t pw, const uint32_t* __restrict__ green,
+                                                             uint8_t* __restrict__ out) {
+  __shared__ VizFleet s;
+  viz_fleet_stage(jobs, k, pal, H, W, s);
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)H * W) return;
+  const uint32_t c = viz_fleet_pixel(s, k, bg, green, W, rw, pw, (int)(i / W), (int)(i % W));
+  out[3 * i] = (uint8_t)c;
+  out[3 * i + 1] = (uint8_t)(c >> 8);
+  out[3 * i + 2] = (uint8_t)(c >> 16);
+}
+
+// the pixels of mask m (bit px = pixel px of the group) of a 16-pixel group's twelve words take colour col
+__device__ __forceinline__ void viz_paint16(uint32_t w[12], uint32_t m, uint32_t col) {
+#pragma unroll
+  for (int px = 0; px < 16; px++) {
+    if (!((m >> px) & 1u)) continue;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+      const int byte = 3 * px + ch;
+      w[byte >> 2] = (w[byte >> 2] & ~(0xFFu << (8 * (byte & 3)))) | (((col >> (8 * ch)) & 0xFFu) << (8 * (byte & 3)));
+    }
+  }
+}
+
+// same size, W a multiple of 16, 16-byte aligned images: one thread per 16 pixels = three 16-byte loads and stores of the
+// image and, per plane, the half word of the group's 16 pixels.  `undecided` holds the pixels no layer has claimed yet;
+// the walk over layers and robots ends when it is empty.
+__global__ __launch_bounds__(256) void viz_fleet_copy16_kernel(const tdr_viz_job* __restrict__ jobs, int k, VizPalette pal,
+                                                               const uint8_t* __restrict__ bg, int H, int W, int rw,
+                                                               int64_t pw, const uint32_t* __restrict__ green,
+                                                               uint8_t* __restrict__ out) {
+  __shared__ VizFleet s;
+  viz_fleet_stage(jobs, k, pal, H, W, s);
+  const int g = W / 16;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)H * g) return;
+  const int y = (int)(i / g), xb = (int)(i % g);
+  const int64_t o = (int64_t)y * rw + (xb >> 1);
+  const int sh = 16 * (xb & 1);
+  const uint4* src = reinterpret_cast<const uint4*>(bg + ((int64_t)y * W + (int64_t)xb * 16) * 3);
+  uint4* dst = reinterpret_cast<uint4*>(out + ((int64_t)y * W + (int64_t)xb * 16) * 3);
+  const uint4 a = src[0], b = src[1], c = src[2];
+  uint32_t w[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+  uint32_t undecided = 0xFFFFu;
+  uint32_t m = (green[o] >> sh) & undecided;
+  if (m) {
+    viz_paint16(w, m, 0x00FF00u);
+    undecided &= ~m;
+  }
+  for (int l = 2; l >= 0 && undecided; l--)
+    for (int r = k - 1; r >= 0 && undecided; r--) {
+      const uint32_t* p = s.planes[r];
+      if (!p) continue;
+      m = (p[l * pw + o] >> sh) & undecided;
+      if (!m) continue;
+      viz_paint16(w, m, s.col[3 * r + l]);
+      undecided &= ~m;
+    }
+  dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+  dst[2] = make_uint4(w[8], w[9], w[10], w[11]);
+}
+
+// another size: one thread per output pixel composes its four taps (viz_compose_resize_body's arithmetic)
+__global__ __launch_bounds__(256) void viz_fleet_resize_kernel(const tdr_viz_job* __restrict__ jobs, int k, VizPalette pal,
+                                                               const uint8_t* __restrict__ bg, int H, int W, int rw,
+                                                               int64_t pw, const uint32_t* __restrict__ green, int out_h,
+                                                               int out_w, uint8_t* __restrict__ out) {
+  __shared__ VizFleet s;
+  viz_fleet_stage(jobs, k, pal, H, W, s);
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)out_h * out_w) return;
+  int x0, x1, ax1, y0, y1, ay1;
+  viz_taps((int)(i % out_w), W, out_w, x0, x1, ax1);
+  viz_taps((int)(i / out_w), H, out_h, y0, y1, ay1);
+  const uint32_t ax0 = 2048u - ax1, ay0 = 2048u - ay1;
+  const uint32_t c00 = viz_fleet_pixel(s, k, bg, green, W, rw, pw, y0, x0), c01 = viz_fleet_pixel(s, k, bg, green, W, rw, pw, y0, x1);
+  const uint32_t c10 = viz_fleet_pixel(s, k, bg, green, W, rw, pw, y1, x0), c11 = viz_fleet_pixel(s, k, bg, green, W, rw, pw, y1, x1);
+  for (int ch = 0; ch < 3; ch++) {
+    const int sh = 8 * ch;
+    const uint32_t v = ay0 * (ax0 * ((c00 >> sh) & 0xFFu) + (uint32_t)ax1 * ((c01 >> sh) & 0xFFu)) +
+                       (uint32_t)ay1 * (ax0 * ((c10 >> sh) & 0xFFu) + (uint32_t)ax1 * ((c11 >> sh) & 0xFFu));
+    out[3 * i + ch] = (uint8_t)((v + (1u << 21)) >> 22);
+  }
+}
+
 bool viz_dims_ok(int H, int W) { return H >= 11 && W >= 11 && H <= VIZ_MAX_DIM && W <= VIZ_MAX_DIM; }
 
 }  // namespace
@@ -558,5 +693,34 @@ extern "C" int tdr_k_viz_compose_jobs(const tdr_viz_job* jobs_dev, int k, int64_
   hipLaunchKernelGGL(viz_compose_jobs_kernel, dim3((unsigned)cdiv(max_out_pixels, 256), (unsigned)k), dim3(256), 0,
                      (hipStream_t)stream, jobs_dev);
   LAUNCH_CHECK("viz_compose_jobs");
+  return TDR_OK;
+}
+
+extern "C" int tdr_k_viz_compose_fleet(const tdr_viz_job* jobs_dev, int k, const uint8_t* palette_host,
+                                       const uint8_t* background, int H, int W, const uint32_t* green_plane, int out_h,
+                                       int out_w, uint8_t* out_bgr, void* stream) {
+  if (!jobs_dev || !palette_host || !background || !green_plane || !out_bgr)
+    return fail(TDR_ERR_ARG, "viz_compose_fleet: null argument");
+  if (k < 1 || k > TDR_FLEET_MAX) return fail(TDR_ERR_ARG, "viz_compose_fleet: k = %d (1 .. %d robots)", k, TDR_FLEET_MAX);
+  if (!viz_dims_ok(H, W) || out_h < 1 || out_w < 1 || out_h > VIZ_MAX_DIM || out_w > VIZ_MAX_DIM)
+    return fail(TDR_ERR_ARG, "viz_compose_fleet: a %d x %d image published as %d x %d", H, W, out_h, out_w);
+  VizPalette pal;
+  std::memset(&pal, 0, sizeof(pal));
+  std::memcpy(&pal, palette_host, (size_t)9 * k);
+  const int rw = viz_row_words(W);
+  const int64_t pw = (int64_t)tdr_viz_plane_words(H, W);
+  hipStream_t s = (hipStream_t)stream;
+  if (out_h == H && out_w == W) {   // the choices of tdr_k_viz_compose
+    if (W % 16 == 0 && (((uintptr_t)background | (uintptr_t)out_bgr) & 15) == 0)
+      hipLaunchKernelGGL(viz_fleet_copy16_kernel, dim3((unsigned)cdiv((int64_t)H * (W / 16), 256)), dim3(256), 0, s,
+                         jobs_dev, k, pal, background, H, W, rw, pw, green_plane, out_bgr);
+    else
+      hipLaunchKernelGGL(viz_fleet_copy_kernel, dim3((unsigned)cdiv((int64_t)H * W, 256)), dim3(256), 0, s, jobs_dev, k,
+                         pal, background, H, W, rw, pw, green_plane, out_bgr);
+  } else {
+    hipLaunchKernelGGL(viz_fleet_resize_kernel, dim3((unsigned)cdiv((int64_t)out_h * out_w, 256)), dim3(256), 0, s,
+                       jobs_dev, k, pal, background, H, W, rw, pw, green_plane, out_h, out_w, out_bgr);
+  }
+  LAUNCH_CHECK("viz_compose_fleet");
   return TDR_OK;
 }

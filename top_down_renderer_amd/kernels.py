@@ -754,6 +754,48 @@ class HipKernels:
         check(self.lib.tdr_k_viz_compose(_ptr(background), H, W, _ptr(planes), out_h, out_w, _ptr(out), self.stream()))
         return out
 
+    # ---- the fleet picture (include/tdr.h, "the fleet picture") ------------------------------------------------------
+    def viz_compose_fleet(self, jobs, k, palette, background, green_plane, out_h, out_w, out=None):
+        """tdr_k_viz_compose_fleet: jobs is a device uint8 tensor holding k tdr_viz_job records (their planes 0 - 2
+        drawn), palette (k, 3, 3) uint8 on the host, background (H, W, 3) uint8 and green_plane int32 device tensors.
+        Returns the published (out_h, out_w, 3) uint8 device tensor."""
+        H, W = int(background.shape[0]), int(background.shape[1])
+        pal = np.ascontiguousarray(palette, np.uint8)
+        if pal.size != 9 * k:
+            raise ValueError("viz_compose_fleet: the palette is (k, 3, 3) BGR bytes")
+        if out is None:
+            out = self.empty((out_h, out_w, 3), torch.uint8)
+        check(self.lib.tdr_k_viz_compose_fleet(_ptr(jobs), int(k), pal.ctypes.data_as(C.c_void_p), _ptr(background), H, W,
+                                               _ptr(green_plane), int(out_h), int(out_w), _ptr(out), self.stream()))
+        return out
+
+    def viz_draw_fleet(self, robots, background, palette, arrows, out_h, out_w):
+        """The fleet picture's three launches on torch buffers.  robots: per robot (st, n, segs, best) — st a (7, cap)
+        float device tensor, segs its estimate as (m, 5) int32 host segments (viz_overlay_host with best = None and no
+        arrows), best a device float tensor {x, y, theta} or None; arrows: the caller's (m, 4) list or None."""
+        H, W = int(background.shape[0]), int(background.shape[1])
+        k = len(robots)
+        words = int(self.lib.tdr_viz_plane_words(H, W))
+        planes = self.zeros(((3 * k + 1) * words,), torch.int32)   # robot i's three at 3 i, the green plane last
+        green = viz_overlay_host(np.zeros((0, 3)), np.zeros((0, 9)), None, arrows, H)
+        jobs, keep, max_n, max_segs = (_lib.VizJobC * k)(), [], 0, 0
+        for i, (st, n, segs, best) in enumerate(robots):
+            segs = np.ascontiguousarray(segs, np.int32).reshape(-1, 5)
+            if i == k - 1:   # (its plane 3 is the green plane)
+                segs = np.concatenate([segs, green])
+            segs_d = self.to_device(segs if len(segs) else np.zeros((1, 5), np.int32))
+            keep.append(segs_d)
+            j = jobs[i]
+            j.st, j.cap, j.n, j.H, j.W = st.data_ptr(), st.shape[1], int(n), H, W
+            j.planes = planes.data_ptr() + 4 * 3 * i * words
+            j.background, j.segs, j.n_segs = background.data_ptr(), segs_d.data_ptr(), len(segs)
+            j.best = best.data_ptr() if best is not None else None
+            max_n, max_segs = max(max_n, int(n)), max(max_segs, len(segs))
+        jobs_d = self.to_device(np.frombuffer(jobs, np.uint8))
+        check(self.lib.tdr_k_viz_particles_jobs(_ptr(jobs_d), k, max_n, self.stream()))
+        check(self.lib.tdr_k_viz_segments_jobs(_ptr(jobs_d), k, max_segs, self.stream()))
+        return self.viz_compose_fleet(jobs_d, k, palette, background, planes[3 * k * words:], out_h, out_w)
+
     # ---- the scan picture (csrc/tdr_scan_viz.hip) ----------------------------------------------------------------
     @staticmethod
     def _colour_table(lut_bgr):
