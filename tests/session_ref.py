@@ -446,18 +446,15 @@ class Session:
 
     def update(self, res, n_target=-1, source="host", zero=False, geo=False, degenerate=False, label=None):
         """tdr_filter_update (geo: tdr_filter_update_geo) stage by stage."""
-        o = self.oracle
         if label:
             self.label = label
         n = len(self.st)
         if n == 0:
             return
-        n_new = n if n_target < 0 else max(1, min(int(n_target), self.n_max))
         flat = self.scan_flat(res, zero)
         geo_flat = self.geo_scan(res) if geo else None
         before = self.st
         ld = self.ld[:n].copy()
-        search = float((before["have_init"] == 0).mean())
         if self.handle:
             f, what = self.f, self._what("update")
             assert f.last_dist(n).tobytes() == ld.tobytes(), (what, "last_dist moved since the propagate")
@@ -465,6 +462,19 @@ class Session:
                 f.update_geo(images(flat, *self.shape), images(geo_flat, *self.shape), res, n_target)
             else:
                 f.update(self._scan_arg(flat, res, source), res, n_target)
+        self.check_update(before, ld, flat, res, n_target, geo_flat=geo_flat, source=source, degenerate=degenerate)
+
+    def check_update(self, before, ld, flat, res, n_target=-1, geo_flat=None, source="host", degenerate=False, stage="update"):
+        """The stages of an update the handle has ALREADY made (by tdr_filter_update, or inside a tdr_batch_step), from the
+        score on: `before` are the states that were scored (read back, or — where no call can read them — the oracle's
+        propagated ones), `ld` their last_dist, `flat` the scan.  With handle=False the oracle makes the step itself."""
+        o = self.oracle
+        geo = geo_flat is not None
+        n = len(before)
+        n_new = n if n_target < 0 else max(1, min(int(n_target), self.n_max))
+        search = float((before["have_init"] == 0).mean())
+        if self.handle:
+            f, what = self.f, self._what(stage)
             raw = f.raw_weights(n)
             w = f._floats(f.L.tdr_filter_get_weights, n)
             idx, after = f.resample_indices(), f.states()
