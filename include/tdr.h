@@ -1348,6 +1348,97 @@ int tdr_filter_set_viz_background_labels(tdr_filter* f, const uint8_t* labels_ho
 int tdr_batch_scan_pictures(const tdr_renderer* const* r, int k, const int32_t* unflatten, const uint8_t* lut_bgr,
                             uint8_t* out_bgr_host, void* stream);
 
+/* ---- map fusion: localised scans vote into the label map on the device (csrc/tdr_fuse.hip, csrc/tdr_host_fuse.cpp;
+ * DESIGN.md 5.14) -------------------------------------------------------------------------------------------------------
+ * A DEFINITION (the reference has only the embryo, src/refine_map.cpp, an offline tool whose relabelling rule is switched
+ * off): parity unpinned.  A robot that localises against a stale aerial map sees the truth in every scan; the filter knows
+ * where the scan belongs on the map.  Fusion accumulates the scans' class counts over the map's cells and relabels a cell
+ * by its most-voted class; the result goes through tdr_map_patch_labels, so the map, its host copies and its compact form
+ * stay coherent.
+ *   State.  One uint32 plane per class over the map's cells, votes [ncls][rows][cols] (cell (yi, xi) at yi * cols + xi),
+ *     and a dirty bitmap: one bit per TDR_MAP_INCR_TILE^2-cell tile (tile t = ty * ceil(cols / TILE) + tx is bit t & 31 of
+ *     word t >> 5; tdr_map_incr_tiles(rows, cols) tiles).
+ *   One scan is a render [ncls][rows*cols] (column-major floats, the renderer's layout) with a pose {cx, cy, theta, scale}
+ *     and `res`, the quantities StateParticle::computeWeight passes on (cx, cy in the units tdr_k_local_map_* takes).
+ *     Polar render (nb x nr, the shape of the map's table): with s = the circular shift getCostForRot computes from theta
+ *     (state_particle.cpp:124-128), bin (i, j) of class c with count n adds n to plane c at the cell tdr_k_local_map_polar
+ *     addresses for sample k = ((i - s) mod nb) + nb * j at `scale`, `res` — the pairing of scan row and window row of
+ *     state_particle.cpp:136-142.  Cartesian render (rows x cols): sample (i, j) votes into the cell tdr_k_local_map_cart
+ *     addresses at rot = theta and res * scale, shift 0 (the window of tdr_k_score_cart).  The cell is computed by the
+ *     device function the gather itself uses (csrc/tdr_local_cell.h), libm-exact sinf / cosf and rounding included: the
+ *     vote step is the transpose of getLocalMap + getCostForRot.
+ *   Counts.  A bin value v votes n = (uint32)v when 1 <= v < 2^31, otherwise 0 (NaN, negatives, fractions below 1).
+ *     Samples outside the map are dropped and counted.  Known / unknown cells are treated alike.  The adds are device-scope
+ *     integer atomics: the planes do not depend on the order of scans or bins.  A cell's count is exact below 2^32 and
+ *     WRAPS beyond.
+ *   Labels.  Per cell: total = the sum of its votes, w = the class with the most (the lowest index on a tie).  The cell has a
+ *     verdict iff total >= min_votes and v_w * share_den >= total * share_num (64-bit integers; share_den <= 2^24 keeps both
+ *     products exact).  Its fused label is class_label[w] with a verdict, the BASE label otherwise: the fused image is a
+ *     function of (votes, base) alone, not of history.  class_label [ncls] is the caller's class -> raw label table, the
+ *     inverse of its flatten_lut.  The label of cell (yi, xi) lives at the image pixel loadCompressedRasterMap samples for
+ *     it (top_down_map.cpp:137-138; csrc/tdr_ingest_dev.h), a one-to-one mapping for resolution >= 1 only: maps of a
+ *     resolution below 1 are refused.
+ * Layer 1: device pointers, no allocation, no sync.  tdr_k_fuse_votes_jobs: k scans in one launch over a DEVICE array of
+ * jobs (the K scans of K robots); max_bins = the largest rows * cols of the jobs (it sizes the grid).  map: ncls / rows /
+ * cols / resolution are read; tab / nb / nr: the map's polar table (tdr_polar_table_host layout) or NULL / 0 / 0; a polar
+ * job of another shape votes nothing.  counters: DEVICE uint64 [2], votes added and votes dropped are ADDED to them.
+ * tdr_k_fuse_votes: one scan, through the same launch.  tdr_k_fuse_labels: one workgroup per listed tile (tiles: DEVICE
+ * int32 [n_tiles]); `current` is updated in place, out5: DEVICE int32 [5] = {pixels that differed from `current`, then the
+ * min y, min x, max y, max x of those pixels}, combined by integer atomics: initialise to {0, INT_MAX, INT_MAX, -1, -1}.
+ * class_label_host travels in the kernel arguments.  tdr_k_fuse_decay: v >>= shift on every plane (shift >= 32 zeroes);
+ * tiles that held votes become dirty. */
+typedef struct tdr_fuse_job {
+  const float* scan;   /* [ncls][rows*cols] device */
+  int32_t rows, cols;  /* polar: nb, nr */
+  int32_t polar, pad;
+  float cx, cy, theta, scale, res, pad2;
+} tdr_fuse_job;
+int tdr_k_fuse_votes_jobs(const tdr_map_desc* map, const float* tab, int nb, int nr, const tdr_fuse_job* jobs_dev, int k,
+                          int64_t max_bins, uint32_t* votes, uint32_t* dirty, uint64_t* counters, void* stream);
+int tdr_k_fuse_votes(const tdr_map_desc* map, const float* tab, int nb, int nr, const float* scan, int polar, int rows,
+                     int cols, float cx, float cy, float theta, float scale, float res, uint32_t* votes, uint32_t* dirty,
+                     uint64_t* counters, void* stream);
+int tdr_k_fuse_labels(const uint32_t* votes, int ncls, int rows, int cols, int img_h, int img_w, float resolution,
+                      const uint8_t* class_label_host, uint32_t min_votes, uint32_t share_num, uint32_t share_den,
+                      const uint8_t* base, uint8_t* current, const int32_t* tiles, int n_tiles, int32_t* out5, void* stream);
+int tdr_k_fuse_decay(uint32_t* votes, int ncls, int rows, int cols, int shift, uint32_t* dirty, void* stream);
+/* Layer 2: the fuser of one map.  tdr_fuser_create needs a map last set from a label image (tdr_map_set_labels or an
+ * incremental update); base and `current` are copies of the map's own device image.  Refused: no such map, resolution < 1,
+ * share_den == 0 or > 2^24, share_num > share_den, min_votes == 0, flatten_lut[class_label[c]] != c for a class c.
+ *   tdr_fuser_add: the renderer's last render, read on the device (ordered against a batched render by the renderer's
+ *     events like tdr_filter_update).  tdr_fuser_add_batch: k renders in one launch, poses [k][5] = {cx, cy, theta, scale,
+ *     res}.  tdr_fuser_add_images: HOST images [ncls][rows*cols].  votes_added / votes_dropped (may be NULL): this call's.
+ *     Refused before any device work: no render, a class count other than the map's, a polar render whose shape is not the
+ *     map's table shape, a renderer twice, a non-finite pose, scale <= 0, res <= 0.
+ *   tdr_fuser_apply: the label pass over the dirty tiles (the bitmap is cleared); if pixels changed, their bounding
+ *     rectangle alone is read back and sent through tdr_map_patch_labels with the map's own centre, then through
+ *     tdr_filter_patch_map_labels for each of the k listed filters of that map (k = 0: the map alone), which leaves them
+ *     scoring against the new map on their next update.  *changed_cells: the cells whose class changed.
+ *   tdr_fuser_decay: tdr_k_fuse_decay.  tdr_fuser_reset: zeroes the votes; tiles that held votes become dirty.
+ *   tdr_fuser_rebase: takes the map's present label image as the new base after someone else replaced the map.  The votes
+ *     are kept (*kept = 1) only if shape, resolution, class count and centre are unchanged, cleared otherwise.  add and
+ *     apply are refused while the map's shape differs from the fuser's.
+ *   tdr_fuser_get_votes: HOST uint32 [ncls][rows][cols].  tdr_fuser_get_labels: the fused image, HOST uint8 [img_h][img_w].
+ *   tdr_fuser_stats: out9 = {scans added, votes added, votes dropped, applies that changed the map, then the shapes the
+ *     two read-backs have: ncls, rows, cols, img_h, img_w}. */
+typedef struct tdr_fuser tdr_fuser;
+int tdr_fuser_create(tdr_map* m, const uint8_t* class_label, uint32_t min_votes, uint32_t share_num, uint32_t share_den,
+                     tdr_fuser** out);
+void tdr_fuser_destroy(tdr_fuser* f);
+int tdr_fuser_add(tdr_fuser* f, const tdr_renderer* r, float cx, float cy, float theta, float scale, float res,
+                  uint64_t* votes_added, uint64_t* votes_dropped);
+int tdr_fuser_add_batch(tdr_fuser* f, const tdr_renderer* const* r, int k, const float* poses, uint64_t* votes_added,
+                        uint64_t* votes_dropped);
+int tdr_fuser_add_images(tdr_fuser* f, const float* imgs_host, int polar, int rows, int cols, float cx, float cy,
+                         float theta, float scale, float res, uint64_t* votes_added, uint64_t* votes_dropped);
+int tdr_fuser_apply(tdr_fuser* f, tdr_filter* const* filters, int k, int64_t* changed_cells);
+int tdr_fuser_decay(tdr_fuser* f, int shift);
+int tdr_fuser_reset(tdr_fuser* f);
+int tdr_fuser_rebase(tdr_fuser* f, int* kept);
+int tdr_fuser_get_votes(const tdr_fuser* f, uint32_t* votes_out);
+int tdr_fuser_get_labels(const tdr_fuser* f, uint8_t* labels_out);
+int tdr_fuser_stats(const tdr_fuser* f, uint64_t* out9);
+
 /* internal: lets the handle layer (csrc/tdr_host_*.cpp) report through tdr_last_error() */
 int tdr_set_error(int code, const char* msg);
 

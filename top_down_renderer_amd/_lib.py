@@ -80,6 +80,13 @@ class LabelPictureJobC(C.Structure):
     _fields_ = [("labels", C.c_void_p), ("npix", C.c_int64), ("out_bgr", C.c_void_p)]
 
 
+class FuseJobC(C.Structure):
+    """tdr_fuse_job: one scan of a batched vote launch."""
+    _fields_ = [("scan", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("polar", C.c_int32), ("pad", C.c_int32),
+                ("cx", C.c_float), ("cy", C.c_float), ("theta", C.c_float), ("scale", C.c_float), ("res", C.c_float),
+                ("pad2", C.c_float)]
+
+
 class PoseStatsC(C.Structure):
     """tdr_pose_stats: one filter's result of a tdr_batch_pose."""
     _fields_ = [("mean", C.c_float * 4), ("cov", C.c_float * 16), ("scale", C.c_float), ("n", C.c_int64)]
@@ -348,6 +355,23 @@ SIGNATURES = {
     "tdr_scan_picture_host": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "tdr_filter_set_viz_background_labels": (_i, [_vp, _vp, _i, _i, _vp]),
     "tdr_batch_scan_pictures": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    # map fusion (csrc/tdr_fuse.hip, csrc/tdr_host_fuse.cpp)
+    "tdr_k_fuse_votes_jobs": (_i, [_vp, _vp, _i, _i, _vp, _i, _i64, _vp, _vp, _vp, _vp]),
+    "tdr_k_fuse_votes": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    "tdr_k_fuse_labels": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _i, _vp, _vp]),
+    "tdr_k_fuse_decay": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "tdr_fuser_create": (_i, [_vp, _vp, _u32, _u32, _u32, C.POINTER(_vp)]),
+    "tdr_fuser_destroy": (None, [_vp]),
+    "tdr_fuser_add": (_i, [_vp, _vp, _f, _f, _f, _f, _f, C.POINTER(_u64), C.POINTER(_u64)]),
+    "tdr_fuser_add_batch": (_i, [_vp, _vp, _i, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "tdr_fuser_add_images": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _f, _f, _f, C.POINTER(_u64), C.POINTER(_u64)]),
+    "tdr_fuser_apply": (_i, [_vp, _vp, _i, C.POINTER(_i64)]),
+    "tdr_fuser_decay": (_i, [_vp, _i]),
+    "tdr_fuser_reset": (_i, [_vp]),
+    "tdr_fuser_rebase": (_i, [_vp, C.POINTER(_i)]),
+    "tdr_fuser_get_votes": (_i, [_vp, _vp]),
+    "tdr_fuser_get_labels": (_i, [_vp, _vp]),
+    "tdr_fuser_stats": (_i, [_vp, _vp]),
     "tdr_set_error": (_i, [_i, C.c_char_p]),
     "tdr_locality_tmp_ints": (C.c_size_t, [_i64, _i, _i]),
     "tdr_locality_pose_tmp_ints": (C.c_size_t, [_i64]),

@@ -45,6 +45,7 @@ struct ScoreArgs {
 };
 
 #include "tdr_score_dev.h"   // rot_shift_dev, the coordinate rounding, compact-record geometry / load / decode, the gates
+#include "tdr_local_cell.h"  // linspaced_dev, the cell of one window sample (shared with tdr_fuse.hip)
 #include "tdr_score_init.h"  // the 40-rotation init search (tdr_score_init.hip)
 #include "tdr_score_su.h"    // the shift-uniform kernel's host interface (tdr_score_su.hip)
 #include "tdr_score_cart.h"  // CartArgs, the Cartesian kernel that skips empty scan bins (tdr_score_cart.hip)
@@ -322,11 +323,7 @@ __global__ __launch_bounds__(256, COMPACT ? (WIDE ? 3 : 5) : 1) void score_polar
 // with shift 0 (src/state_particle.cpp:132-143) (definition recorded in include/tdr.h:tdr_k_score_cart and DESIGN.md).
 // Same mapping as the polar kernel (lane = particle); the rotation now lives in the sampling, so the scan record of
 // sample (i,j) is the same for every lane and comes through the scalar cache instead of LDS.
-__device__ __forceinline__ float linspaced_dev(int i, int size1, float low, float high, float step) {
-  // Eigen LinSpaced<float>, |high| == |low| here, so never the flipped branch of linspaced_op_impl
-  return (i == size1) ? high : (low + (float)i * step);
-}
-
+// (linspaced_dev: tdr_local_cell.h)
 template <int NV4, int U, bool KSLOT, bool COMPACT, bool WIDE = false>
 __global__ __launch_bounds__(256) void score_cart_kernel(CartArgs a) {
   constexpr int RF = 4 * NV4;
@@ -474,28 +471,11 @@ __global__ void local_map_kernel(LocalMapArgs a) {
   const int64_t P = (int64_t)a.rows * a.cols;
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= P) return;
-  const float off0 = a.cy / a.resolution, off1 = a.cx / a.resolution;
-  float p0, p1;
-  if constexpr (POLAR) {
-    p0 = (a.tab[2 * k] * a.scale_or_rot) * a.res + off0;      // top_down_map_polar.cpp:28-30
-    p1 = (a.tab[2 * k + 1] * a.scale_or_rot) * a.res + off1;
-  } else {
-    const int i = (int)(k % a.rows), j = (int)(k / a.rows);
-    const float resq = a.res / a.resolution;                    // top_down_map.cpp:434
-    const float c = tdr_libm::cosf_v(a.scale_or_rot, a.libm_fma), s = tdr_libm::sinf_v(a.scale_or_rot, a.libm_fma);   // :381-385
-    const float lo_r = (float)((double)(-resq * (float)(a.rows - 1)) / 2.), hi_r = (float)((double)(resq * (float)(a.rows - 1)) / 2.);
-    const float lo_c = (float)((double)(-resq * (float)(a.cols - 1)) / 2.), hi_c = (float)((double)(resq * (float)(a.cols - 1)) / 2.);
-    const float step_r = a.rows == 1 ? 0.f : (hi_r - lo_r) / (float)(a.rows - 1);
-    const float step_c = a.cols == 1 ? 0.f : (hi_c - lo_c) / (float)(a.cols - 1);
-    const float yi = linspaced_dev(i, a.rows == 1 ? 1 : a.rows - 1, lo_r, hi_r, step_r);
-    const float xj = linspaced_dev(j, a.cols == 1 ? 1 : a.cols - 1, lo_c, hi_c, step_c);
-    p0 = (c * yi + (-s) * xj) + off0;                           // samplePts :383-388
-    p1 = (s * yi + c * xj) + off1;
-  }
-  p0 = __builtin_amdgcn_fmed3f(p0, -1.f, (float)a.map_rows);
-  p1 = __builtin_amdgcn_fmed3f(p1, -1.f, (float)a.map_cols);
-  const int ri = round_half_away_clamped(p0), ci = round_half_away_clamped(p1);
-  const bool inb = (unsigned)ri < (unsigned)a.map_rows && (unsigned)ci < (unsigned)a.map_cols;
+  LocalCellArgs g;   // the cell of sample k: tdr_local_cell.h, shared with the vote scatter (tdr_fuse.hip)
+  g.map_rows = a.map_rows; g.map_cols = a.map_cols; g.resolution = a.resolution; g.tab = a.tab; g.rows = a.rows;
+  g.cols = a.cols; g.cx = a.cx; g.cy = a.cy; g.scale_or_rot = a.scale_or_rot; g.res = a.res; g.libm_fma = a.libm_fma;
+  int ri, ci;
+  const bool inb = local_map_cell<POLAR>(g, k, ri, ci);
   const float* r = a.rec + ((int64_t)(ri + 1) * (a.map_cols + 2) + (ci + 1)) * a.rf;   // guard ring: always valid
   for (int c = 0; c < a.ncls; c++) a.dists[(int64_t)c * P + k] = inb ? r[c] : 0.f;
   a.mask[k] = inb ? (uint8_t)(r[a.rf - 1] == 0.f ? 1 : 0) : (uint8_t)1;

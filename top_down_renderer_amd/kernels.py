@@ -542,6 +542,47 @@ class HipKernels:
                                                 C.c_float(scale_or_rot), C.c_float(res), _ptr(d), _ptr(k), self.stream()))
         return d, k
 
+    # ---- map fusion (include/tdr.h, "map fusion") -------------------------------------------------------------------
+    def fuse_state(self, m):
+        """(votes (ncls, rows, cols) int32 holding uint32 bits, dirty bitmap words, counters (2,) int64), all zero."""
+        words = (int(self.lib.tdr_map_incr_tiles(m.rows, m.cols)) + 31) // 32
+        return (self.zeros((m.ncls, m.rows, m.cols), torch.int32), self.zeros((words,), torch.int32),
+                self.zeros((2,), torch.int64))
+
+    def fuse_votes(self, m, scans, polar, poses, votes, dirty, counters):
+        """One launch (tdr_k_fuse_votes_jobs) for the scans of a list: scans[k] a contiguous device tensor (ncls, cols, rows),
+        which is the render layout [ncls][rows*cols] column-major; polar[k] its kind, poses[k] = (cx, cy, theta, scale, res).
+        A single scan goes through tdr_k_fuse_votes."""
+        tab = m.tab if m.nb > 0 else None
+        args = (C.byref(m.desc), _ptr(tab) if tab is not None else None, m.nb if tab is not None else 0,
+                m.nr if tab is not None else 0)
+        if len(scans) == 1:
+            s, (cx, cy, th, sc, res) = scans[0], poses[0]
+            check(self.lib.tdr_k_fuse_votes(*args, _ptr(s), int(bool(polar[0])), s.shape[2], s.shape[1], C.c_float(cx),
+                                            C.c_float(cy), C.c_float(th), C.c_float(sc), C.c_float(res), _ptr(votes),
+                                            _ptr(dirty), _ptr(counters), self.stream()))
+            return
+        jobs = (_lib.FuseJobC * len(scans))()
+        for j, s, pl, (cx, cy, th, sc, res) in zip(jobs, scans, polar, poses):
+            j.scan, j.rows, j.cols, j.polar = s.data_ptr(), s.shape[2], s.shape[1], int(bool(pl))
+            j.cx, j.cy, j.theta, j.scale, j.res = cx, cy, th, sc, res
+        jobs_d = self.to_device(np.frombuffer(bytearray(jobs), np.uint8))
+        check(self.lib.tdr_k_fuse_votes_jobs(*args, _ptr(jobs_d), len(scans), max(s.shape[1] * s.shape[2] for s in scans),
+                                             _ptr(votes), _ptr(dirty), _ptr(counters), self.stream()))
+        self.synchronize()   # (jobs_d is this call's)
+
+    def fuse_labels(self, votes, img_shape, resolution, class_label, min_votes, share, base, current, tiles):
+        """tdr_k_fuse_labels over the listed tiles (an int32 device tensor): `current` (img_h, img_w) uint8 is updated in
+        place; returns (changed pixels, y min, x min, y max, x max)."""
+        ncls, rows, cols = votes.shape
+        out = self.to_device(np.asarray([0, 2 ** 31 - 1, 2 ** 31 - 1, -1, -1], np.int32))
+        cl = np.ascontiguousarray(class_label, np.uint8)
+        check(self.lib.tdr_k_fuse_labels(_ptr(votes), ncls, rows, cols, int(img_shape[0]), int(img_shape[1]),
+                                         C.c_float(resolution), cl.ctypes.data_as(C.c_void_p), int(min_votes), int(share[0]),
+                                         int(share[1]), _ptr(base), _ptr(current), _ptr(tiles), int(tiles.numel()), _ptr(out),
+                                         self.stream()))
+        return tuple(int(x) for x in out.cpu().numpy())
+
     def pack_scan(self, img, ncls, nb, nr):
         pk = self.empty((nr * nb * self.lib.tdr_rec_floats(ncls),))
         check(self.lib.tdr_k_pack_scan(_ptr(img), ncls, nb, nr, _ptr(pk), self.stream()))
