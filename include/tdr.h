@@ -589,6 +589,14 @@ int tdr_profile_shares(double* dense_ms, double* scattered_ms, int64_t* scattere
  * that splits the records on the fly, [14] the one on wide records, [15] the vector kernel — alone, or redoing a search whose
  * scan counts did not fit f16 (then the matrix-core pass has counted the same batches too). */
 int tdr_profile_variants(int64_t out[16]);
+/* With tdr_profile_enable(2), likewise outside timed regions: how the ray-mapped kernel's gate count ended, for the launches
+ * that walk compact bin lists (a context with the table's factors, a direction count that is a multiple of 16 and <= 256).
+ * Reads and resets four counters (synchronises): [0] scattered particles whose count was settled by the non-empty bins alone
+ * (at least half the samples known, or too few even with every empty bin's cell known); [1] particles whose waves stopped
+ * walking the empty bins once the shared count reached half the samples; [2] particles whose empty bins were walked to the
+ * end (always, where a particle's waves do not share a workgroup or the window has 2^24 samples or more); [3] blocks of up
+ * to 256 empty bins walked, over all waves. */
+int tdr_profile_ray_gate(int64_t out[4]);
 
 /* The library reads NOTHING from the process environment: behaviour switches are these calls (and the tdr_config_* calls
  * above), process-wide, meant for A/B measurements, tests and debugging — results never depend on them unless stated.

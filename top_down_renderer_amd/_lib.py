@@ -195,6 +195,7 @@ SIGNATURES = {
     # out[16]: [0..11] the dense kernels' loop variants, [12..15] the init search's passes — half records, on the fly,
     # wide, vector kernel: 64-particle batches whose results the pass wrote (include/tdr.h)
     "tdr_profile_variants": (_i, [C.POINTER(_i64)]),
+    "tdr_profile_ray_gate": (_i, [C.POINTER(_i64)]),
     "tdr_score_ctx_set_polar_factors": (_i, [_vp, _vp, _i, _i]),
     "tdr_polar_factors_host": (_i, [_i, _i, _f, _f, _vp]),
     "tdr_k_score_polar_ctx": (_i, [C.POINTER(MapDescC), _vp, _vp, _i, _i, _f, C.POINTER(FilterParamsC), _vp, _i64, _i64,

@@ -121,4 +121,6 @@ int tdr_mt_advance(const uint32_t* raw, int64_t nblocks, const uint32_t* consume
 __host__ __device__ inline bool tdr_has_kslot(int ncls, int rf) { return ncls + 2 <= rf; }
 // diagnostics: 16 device counters while tdr_profile_enable(1) is in force, else NULL (tdr_score.hip, tdr_profile_variants)
 uint32_t* tdr_profile_stats_ptr();
+// likewise the four counters of tdr_profile_ray_gate (tdr_score_ray.hip)
+uint32_t* tdr_profile_gate_ptr();
 #endif  // TDR_COMMON_H_

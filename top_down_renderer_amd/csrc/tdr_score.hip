@@ -949,6 +949,27 @@ extern "C" int tdr_profile_variants(int64_t out[16]) {   // reads and resets (sy
   for (int k = 0; k < 16; k++) out[k] = h[k];
   return TDR_OK;
 }
+// ... and how the ray-mapped kernel's gate count ended for each scattered particle (tdr_profile_ray_gate in tdr.h)
+static uint32_t* g_gate_stats = nullptr;
+uint32_t* tdr_profile_gate_ptr() {
+  if (!g_prof_on || !g_prof_variants) return nullptr;
+  if (!g_gate_stats) {
+    if (hipMalloc((void**)&g_gate_stats, 4 * sizeof(uint32_t)) != hipSuccess) { g_gate_stats = nullptr; return nullptr; }
+    (void)hipMemset(g_gate_stats, 0, 4 * sizeof(uint32_t));
+  }
+  return g_gate_stats;
+}
+extern "C" int tdr_profile_ray_gate(int64_t out[4]) {   // reads and resets (synchronises)
+  if (!out) return fail(TDR_ERR_ARG, "profile_ray_gate: null pointer");
+  for (int k = 0; k < 4; k++) out[k] = 0;
+  if (!g_gate_stats) return TDR_OK;
+  uint32_t h[4];
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h, g_gate_stats, sizeof(h), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemset(g_gate_stats, 0, sizeof(h)));
+  for (int k = 0; k < 4; k++) out[k] = h[k];
+  return TDR_OK;
+}
 extern "C" int tdr_profile_enable(int on) {
   g_prof_on = on != 0;
   g_prof_variants = on == 2;

@@ -60,6 +60,12 @@
 //     what a wave has just fetched is the sector next to the one it fetches now.
 // Lane l = direction (l >> 4) of the step's four, ring (l & 15) of the block.  tdr_config_tuning("ray_patch", 0): the ray order
 // (A/B; same bits).
+// COMPACT lists (round 6; the patch order with the table's factors): the wave walks lists of a sector's non-empty bins, 64 to
+// a gather, and the empty bins only as far as the gate needs them — see above ray_body.  They take the place of the patch
+// walk above wherever the factors are the table's; the patch walk itself is left for a table that is not its factors'
+// products (it reads the offsets from the table, and desc_ray as before).  Measured on config 2 (13 868
+// scattered particles, HIP events around the kernel): 1.02 -> 0.93 ms; 1 488 -> 1 041 vector-memory instructions per
+// particle; the L1 address path 0.84 -> 0.69 busy, at 35 -> 42 cycles per gather.
 // (the first order pads to whole blocks of GQ steps: never less than the block-major order needs)
 int64_t tdr_ray_padded_samples(int nb, int nr) { return (int64_t)nb * ray_blocks(nr, false) * ray_gq(nr, false) * 64; }
 
@@ -94,6 +100,9 @@ struct RayArgs {
   int nsplit;               // waves per particle: each takes a contiguous share of the directions and writes one chunk row
   int64_t npad;
   uint32_t* part;           // [>= nsplit][2 ncls + 2][npad], like score_polar_su_kernel
+  const uint32_t* clist;    // COMPACT: the sectors' bin lists and their table (score_prep_kernel)
+  const int32_t* ctab;
+  uint32_t* gate_ctr;       // NULL, or (profiling) the four counters of tdr_profile_ray_gate
 };
 
 // FAC: the sample offsets are multiplied out of the table's factors — a direction's pair (uniform over the wave: two scalar
@@ -102,16 +111,62 @@ struct RayArgs {
 // lacc [4 waves][ncls + 1][64 lanes]: a lane's sums per class (slot 0: no class); lut, per class code: {plane constant,
 // column shift, known-bit index, accumulator}
 // PATCH (with BM): the patch order (see the top of the file); ldir: the directions' pairs in LDS
+// COMPACT: the entries of gathers 0 .. N - 1 of a step that starts at entry e0 (a multiple of 256) of a stream — one 16-byte
+// load per lane and block of four gathers (score_prep_kernel stores the blocks lane-major and fills the last one with
+// RAY_CL_NONE: no class, no count, and a radius that leaves the map).
+template <int N>
+__device__ __forceinline__ void ray_list_load(const uint4* __restrict__ lst, int e0, int lane, uint32_t (&w)[N]) {
+  uint4 q[(N + 3) / 4];
+#pragma unroll
+  for (int b = 0; b < (N + 3) / 4; b++) q[b] = lst[((e0 >> 8) + b) * 64 + lane];
+#pragma unroll
+  for (int u = 0; u < N; u++) {
+    const uint4 qq = q[u >> 2];
+    w[u] = (u & 3) == 0 ? qq.x : ((u & 3) == 1 ? qq.y : ((u & 3) == 2 ? qq.z : qq.w));
+  }
+}
+// COMPACT (= PATCH with FAC; round 6).  An empty scan bin adds nothing to a cost and nothing to the normalisation: the loop
+// gathers its cell only to count the cell's known bit, and the known count has ONE consumer — the gate of
+// state_particle.cpp:117-120, which for P < 2^24 asks whether 2 known >= P (score_finalize_exact_kernel: a correctly rounded
+// quotient of two exact floats is below one half exactly when it is).  So score_prep_kernel packs each sector's bins into
+// lists: A, the single-class bins with a count below 2^12, unit by unit and class by class; B, the bins the loop sees as
+// empty.  An entry carries its position in the sector — scan row & 15, ring & 63, as byte offsets into the two LDS tables
+// below — and, A, the descriptor.
+//   Phase 1: a wave walks the A lists of its sectors, 64 entries per gather; a lane's direction pair and radius come out of
+//     LDS by the entry's position.  Products, normalisation and the A bins' known bits are exact.
+//   Phase 2, the gate count: the waves of a particle add their phase-1 counts and their B entries into LDS words and meet at
+//     one barrier.  A total of at least P / 2 settles the particle; so does a total that stays below P / 2 even if every B
+//     cell were known (it will be NaN).  Otherwise the waves walk their B lists on the mask plane in blocks of up to 256
+//     entries, add each block's known bits to the shared word and stop when it has reached P / 2 or the lists end.
+// INVARIANT: every unit added to a known count is the known bit of a distinct real sample, so the sum of the waves' counts in
+// `part` never exceeds the true count; a wave leaves its B lists unfinished only after the shared total — all of it counted
+// by waves that write it out — reached P / 2.  So the written sum is >= P / 2 exactly when the true count is, and the gate
+// falls as it did.  Where a particle's waves do not share a workgroup (a split that does not divide 4) or P >= 2^24 the B
+// lists are walked to the end: the exact count.
 template <int GQ, bool USCALE, bool FAC, bool BM, bool PATCH>
-__device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* lacc, uint32_t* ldict, uint4* lut, float2* ldir) {
+__device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* lacc, uint32_t* ldict, uint4* lut, float2* ldir,
+                                         uint32_t (*lgate)[4]) {
   static_assert(!BM || GQ == 1, "block-major: one step per row");
   static_assert(!PATCH || BM, "the patch order is a block-major order");
+  constexpr bool COMPACT = PATCH && FAC;
   const int nsparse = a.counts[1];
   if ((int64_t)blockIdx.x * 4 >= (int64_t)nsparse * a.nsplit) return;   // whole workgroup idle (uniform)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   for (int t = threadIdx.x; t < a.dict_n; t += 256) ldict[t] = a.dict_int[t];
-  if constexpr (PATCH && FAC)
-    for (int t = threadIdx.x; t < a.nb; t += 256) ldir[t] = reinterpret_cast<const float2*>(a.fac)[t];
+  // COMPACT: the rings' radii behind the accumulators, 65 per segment of 64 rings (a ring the image does not have, and
+  // RAY_CL_NONE's slot 64: the cell leaves the map); ldir: the directions' pairs twice over, so that (scan row - shift + nb)
+  // needs no wrap
+  float* const lrad = reinterpret_cast<float*>(lacc + (size_t)4 * (a.ncls + 1) * 64);
+  // the gate count is shared where a particle's waves are waves of one workgroup and the gate is the integer comparison
+  const bool gate_shared = COMPACT && 4 % a.nsplit == 0 && (int64_t)a.nb * a.nr < (1 << 24);
+  if constexpr (COMPACT) {
+    for (int t = threadIdx.x; t < 2 * a.nb + RAY_PG; t += 256) ldir[t] = reinterpret_cast<const float2*>(a.fac)[t % a.nb];
+    for (int t = threadIdx.x; t < a.blocks * 65; t += 256) {
+      const int sg = t / 65, rr = t - sg * 65, jr = sg * 64 + rr;
+      lrad[t] = rr < 64 && jr < a.nr ? a.fac[2 * a.nb + jr] : 1.0e30f;
+    }
+    if (threadIdx.x < 16) lgate[threadIdx.x >> 2][threadIdx.x & 3] = 0;   // per particle: {phase-1 count, B entries, B count, waves done}
+  }
   const unsigned pconst = (unsigned)(a.pkcol + 16) + 128u;   // plane_offset's constant without the plane's own offset
   if (threadIdx.x < 16) {
     const int code = threadIdx.x;
@@ -131,7 +186,10 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
   const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
   const int64_t q = gw / a.nsplit;
   const int part_id = (int)(gw - q * a.nsplit);
-  if (q >= nsparse) return;   // (wave-uniform; no barrier below)
+  if (q >= nsparse) {   // (wave-uniform; the only barrier below is the gate's)
+    if (COMPACT && gate_shared && a.nsplit > 1) __syncthreads();
+    return;
+  }
   const int64_t slot = (int64_t)a.counts[0] + q;
   const int64_t p = a.slots[slot];
   const float scale = a.st[TDR_ST_SCALE * a.cap + p];
@@ -250,7 +308,66 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
 #pragma unroll
     for (int s = 0; s < N * GQ; s++) consume(v[s], shb[s], cnt[s], acc_at[s]);
   };
-  if constexpr (PATCH) {
+  uint32_t nb_mine = 0;   // COMPACT: B entries of this wave's sectors
+  if constexpr (COMPACT) {
+    // phase 1: the A lists of this wave's sectors
+    const int ngroups = a.nb / RAY_PG, sectors_all = a.blocks * ngroups;
+    const int sper = (sectors_all + a.nsplit - 1) / a.nsplit;
+    const int s0 = part_id * sper, s1 = min(sectors_all, s0 + sper);
+    int seg = s0 / ngroups, pg = s0 - seg * ngroups;
+    // (a sector's counts are read one sector ahead: nothing waits for them)
+    int4 tn = s0 < s1 ? *reinterpret_cast<const int4*>(a.ctab + (int64_t)s0 * 16 + 12) : make_int4(0, 0, 0, 0);
+    for (int sc = s0; sc < s1; sc++) {
+      const int n_a = tn.x + tn.y;
+      nb_mine += (uint32_t)(tn.z + tn.w);
+      tn = *reinterpret_cast<const int4*>(a.ctab + (int64_t)min(sc + 1, s1 - 1) * 16 + 12);
+      const uint4* __restrict__ lst = reinterpret_cast<const uint4*>(a.clist + (int64_t)sc * RAY_CL_WORDS);
+      const int dbase = (pg * RAY_PG - shift + a.nb) * 8, rbase = seg * 65 * 4;   // byte offsets into ldir, lrad
+      const unsigned pbase_a = a.planes_off + pconst - a.plane_bytes;                // class code c + 1: plane c
+      auto step_a = [&](auto cnt_c, int e0) {
+        constexpr int N = decltype(cnt_c)::value;
+        uint32_t w[N], v[N];
+        ray_list_load<N>(lst, e0, lane, w);
+#pragma unroll
+        for (int u = 0; u < N; u++) {
+          const float2 dv = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(ldir) + dbase + (w[u] >> 25));
+          const float rad = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(lrad) + rbase + ((w[u] >> 16) & 0x1FFu));
+          int ri, ci;
+          cell_fac((tdr_v2f){dv.x, dv.y}, rad, ri, ci);
+          // an A entry has ONE class: its plane, cells as they are, `known` in bit 15 — nothing out of the class table
+          const unsigned off = plane_offset(ri, ci, a.pkcol, (int)(pbase_a + ((w[u] >> 12) & 0xFu) * a.plane_bytes));
+          v[u] = *reinterpret_cast<const uint16_t*>(crecb + off);
+        }
+#pragma unroll
+        for (int u = 0; u < N; u++) {
+          const uint32_t kbit = v[u] >> 15, cnt = w[u] & 0xFFFu;
+          known += kbit;
+          norm = __umul24(cnt, kbit) + norm;                  // state_particle.cpp:141-142
+          const uint32_t D = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(ldict) + (v[u] & 0xFFCu));
+          unsigned long long* const acc = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(my) + ((w[u] >> 3) & 0x1E00u));
+          __hip_atomic_fetch_add(acc, (unsigned long long)cnt * D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+      };
+      // up to 16 gathers (the last one may be part of one) in one or two steps of up to 8 in flight together; a step starts at
+      // a block of 256 entries, and neither is left with a single gather to wait for alone
+      int e = 0, left = (n_a + 63) >> 6;
+      if (left > 12) { step_a(std::integral_constant<int, 8>{}, 0); e = 512; left -= 8; }
+      else if (left > 8) { step_a(std::integral_constant<int, 4>{}, 0); e = 256; left -= 4; }
+      switch (left) {
+        case 8: step_a(std::integral_constant<int, 8>{}, e); break;
+        case 7: step_a(std::integral_constant<int, 7>{}, e); break;
+        case 6: step_a(std::integral_constant<int, 6>{}, e); break;
+        case 5: step_a(std::integral_constant<int, 5>{}, e); break;
+        case 4: step_a(std::integral_constant<int, 4>{}, e); break;
+        case 3: step_a(std::integral_constant<int, 3>{}, e); break;
+        case 2: step_a(std::integral_constant<int, 2>{}, e); break;
+        case 1: step_a(std::integral_constant<int, 1>{}, e); break;
+        default: break;
+      }
+      pg++;
+      if (pg == ngroups) { pg = 0; seg++; }
+    }
+  } else if constexpr (PATCH) {
     // the patch order (top of the file): a wave takes a contiguous share of the SECTORS (segment of 64 rings, group of 16 scan
     // rows); a sector = the segment's four ring blocks = four units of four steps; two units' gathers are in flight together
     const int ngroups = a.nb / RAY_PG, sectors_all = a.blocks * ngroups;
@@ -258,30 +375,15 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
     const int s0 = part_id * sper, s1 = min(sectors_all, s0 + sper);
     const int pl_d = lane >> 4, pl_r = lane & (RAY_PR - 1);
     const uint2* __restrict__ descq = reinterpret_cast<const uint2*>(a.desc_ray);
-    float rad4[4] = {0.f, 0.f, 0.f, 0.f};
-    int cur_seg = -1;
     int seg = s0 / ngroups, pg = s0 - seg * ngroups;
     for (int sc = s0; sc < s1; sc++) {
-      if (seg != cur_seg) {   // (wave-uniform) the lane's radii of the segment's four ring blocks
-        cur_seg = seg;
-#pragma unroll
-        for (int qq = 0; qq < 4; qq++) {
-          const int j = (seg * 4 + qq) * RAY_PR + pl_r;
-          rad4[qq] = j < a.nr ? a.fac[2 * a.nb + j] : 1.0e30f;   // (a ring the image does not have: its cell leaves the map)
-        }
-      }
       // the window directions of the sector's four steps: scan row 16 pg + 4 k + (lane >> 4) meets direction (row - shift) mod nb
       int wi[4];
-      tdr_v2f wdir[4];
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         int i = pg * RAY_PG + 4 * k + pl_d - shift;
         i += i < 0 ? a.nb : 0;
         wi[k] = i;
-        if constexpr (FAC) {
-          const float2 dv = ldir[i];
-          wdir[k] = (tdr_v2f){dv.x, dv.y};
-        }
       }
 #pragma unroll
       for (int h = 0; h < 2; h++) {
@@ -294,9 +396,7 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
 #pragma unroll
           for (int k = 0; k < 4; k++) {
             int ri, ci;
-            if constexpr (FAC) {
-              cell_fac(wdir[k], rad4[2 * h + u], ri, ci);
-            } else {   // (the table is not its factors' products: its own entries, in its own order)
+            {   // (the table is not its factors' products: its own entries, in its own order)
               const int j = min((seg * 4 + 2 * h + u) * RAY_PR + pl_r, a.nr - 1);
               const int64_t kk = (int64_t)j * a.nb + wi[k];
               if ((seg * 4 + 2 * h + u) * RAY_PR + pl_r < a.nr) cell(a.tab[2 * kk], a.tab[2 * kk + 1], ri, ci);
@@ -344,6 +444,90 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
       norm += (uint32_t)a.scan_pk[bin * a.rf + a.rf - 1] & (0u - kbit);
     }
   }
+  // phase 2 (COMPACT): the gate count — see the invariant above ray_body
+  if constexpr (COMPACT) {
+#pragma unroll
+    for (int dlt = 32; dlt > 0; dlt >>= 1) known += __shfl_xor(known, dlt, 64);   // (every lane: the wave's phase-1 count)
+    const uint32_t P = (uint32_t)((int64_t)a.nb * a.nr);   // (read only where gate_shared: below 2^24)
+    uint32_t* const g = lgate[gate_shared ? wave - part_id : 0];   // the particle's words (gate_shared: part_id = wave mod nsplit)
+    uint32_t tot_a = known, nb_all = nb_mine;
+    if (gate_shared && a.nsplit > 1) {
+      if (lane == 0) {
+        atomicAdd(&g[0], known);
+        atomicAdd(&g[1], nb_mine);
+      }
+      __syncthreads();   // the one barrier: every wave of the workgroup, idle ones included, arrives once
+      tot_a = *reinterpret_cast<volatile uint32_t*>(&g[0]);   // (no wave adds to these two words behind the barrier)
+      nb_all = *reinterpret_cast<volatile uint32_t*>(&g[1]);
+    }
+    const bool settled = gate_shared && (2 * tot_a >= P || 2 * (tot_a + nb_all) < P);
+    uint32_t known_b = 0, blocks_b = 0;
+    bool early = false;
+    if (!settled) {
+      const int ngroups = a.nb / RAY_PG, sectors_all = a.blocks * ngroups;
+      const int sper = (sectors_all + a.nsplit - 1) / a.nsplit;
+      const int s0 = part_id * sper, s1 = min(sectors_all, s0 + sper);
+      int seg = s0 / ngroups, pg = s0 - seg * ngroups;
+      const uint4 em = lut[0];   // the coarse mask plane: a B entry needs its cell's known bit and nothing else
+      for (int sc = s0; sc < s1 && !early; sc++) {
+        const int32_t* __restrict__ tb = a.ctab + (int64_t)sc * 16;
+        const int n_a = tb[12] + tb[13], n_b = tb[14] + tb[15];
+        const uint4* __restrict__ lst = reinterpret_cast<const uint4*>(a.clist + (int64_t)sc * RAY_CL_WORDS + ((n_a + 255) >> 8) * 256);
+        const int dbase = (pg * RAY_PG - shift + a.nb) * 8, rbase = seg * 65 * 4;
+        auto step_b = [&](auto cnt_c, int e0) {   // known cells among N x 64 entries (wave-uniform)
+          constexpr int N = decltype(cnt_c)::value;
+          uint32_t w[N], v[N], shb[N];
+          ray_list_load<N>(lst, e0, lane, w);
+#pragma unroll
+          for (int u = 0; u < N; u++) {
+            const float2 dv = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(ldir) + dbase + (w[u] >> 25));
+            const float rad = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(lrad) + rbase + ((w[u] >> 16) & 0x1FFu));
+            int ri, ci;
+            cell_fac((tdr_v2f){dv.x, dv.y}, rad, ri, ci);
+            const unsigned off = plane_offset(ri >> (int)em.y, ci >> (int)em.y, a.pkcol, (int)em.x);
+            shb[u] = (((uint32_t)ri & 3u) << 2) | ((uint32_t)ci & 3u);
+            v[u] = *reinterpret_cast<const uint16_t*>(crecb + off);
+          }
+          uint32_t c = 0;
+#pragma unroll
+          for (int u = 0; u < N; u++) c += (uint32_t)__popcll(__ballot((v[u] >> shb[u]) & 1u));
+          return c;
+        };
+        for (int e = 0; e < n_b && !early; e += 256) {
+          const int left = (n_b - e + 63) >> 6;
+          uint32_t c = 0;
+          if (left >= 4) c = step_b(std::integral_constant<int, 4>{}, e);
+          else if (left == 3) c = step_b(std::integral_constant<int, 3>{}, e);
+          else if (left == 2) c = step_b(std::integral_constant<int, 2>{}, e);
+          else c = step_b(std::integral_constant<int, 1>{}, e);
+          known_b += c;
+          blocks_b++;
+          if (gate_shared) {
+            uint32_t tot_b = known_b;
+            if (a.nsplit > 1) {   // the particle's running count: this block's bits in, the total so far out
+              uint32_t old = 0;
+              if (lane == 0) old = atomicAdd(&g[2], c);
+              tot_b = (uint32_t)__builtin_amdgcn_readfirstlane((int)old) + c;
+            }
+            early = 2 * (tot_a + tot_b) >= P && (e + 256 < n_b || sc + 1 < s1);
+          }
+        }
+        pg++;
+        if (pg == ngroups) { pg = 0; seg++; }
+      }
+      known += known_b;
+    }
+    if (a.gate_ctr && lane == 0) {   // (profiling) the particle's outcome, by the last of its waves to arrive here
+      if (blocks_b) atomicAdd(&a.gate_ctr[3], blocks_b);
+      if (!gate_shared) {
+        if (part_id == 0) atomicAdd(&a.gate_ctr[2], 1u);
+      } else {
+        const uint32_t mine = 1u + (settled ? 0u : 0x100u) + (early ? 0x10000u : 0u);
+        const uint32_t all = atomicAdd(&g[3], mine) + mine;
+        if ((all & 0xFFu) == (uint32_t)a.nsplit) atomicAdd(&a.gate_ctr[(all >> 16) ? 1 : ((all & 0xFF00u) ? 2 : 0)], 1u);
+      }
+    }
+  }
   // lanes -> one sum per class (the rings a block pads a direction with fell on the guard cell — unknown — and counted nothing)
   uint32_t* o = a.part + (int64_t)part_id * (2 * a.ncls + 2) * a.npad + slot;
   for (int c = 0; c < a.ncls; c++) {
@@ -357,7 +541,7 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
   }
 #pragma unroll
   for (int dlt = 32; dlt > 0; dlt >>= 1) {
-    known += __shfl_xor(known, dlt, 64);
+    if constexpr (!COMPACT) known += __shfl_xor(known, dlt, 64);   // (COMPACT: phase 2 left the wave's count in every lane)
     norm += __shfl_xor(norm, dlt, 64);
   }
   if (lane == 0) {
@@ -371,15 +555,16 @@ __global__ __launch_bounds__(256) void score_polar_ray_kernel(RayArgs a) {
   extern __shared__ unsigned long long lacc[];
   __shared__ uint32_t ldict[TDR_CMAP_MAX_DICT];
   __shared__ uint4 lut[16];
-  __shared__ float2 ldir[PATCH ? RAY_PATCH_MAX_NB : 1];
+  __shared__ float2 ldir[PATCH ? 2 * RAY_PATCH_MAX_NB + RAY_PG : 1];
+  __shared__ uint32_t lgate[4][4];
   if (int_form_off(a.inexact)) return;
 #ifdef TDR_SCORE_TIMELINE
   if ((int64_t)blockIdx.x * 4 >= (int64_t)a.counts[1] * a.nsplit) return;   // no stamps for an idle workgroup (ray_body's own test)
 #endif
   TDR_TL_BEGIN(g_timeline_ray)
   // with factors that ARE the table's (score_prep_kernel's check; uniform over the launch) the offsets are multiplied out
-  if (a.fac && a.inexact[2] == 0) ray_body<GQ, USCALE, true, BM, PATCH>(a, lacc, ldict, lut, ldir);
-  else ray_body<GQ, USCALE, false, BM, PATCH>(a, lacc, ldict, lut, ldir);
+  if (a.fac && a.inexact[2] == 0) ray_body<GQ, USCALE, true, BM, PATCH>(a, lacc, ldict, lut, ldir, lgate);
+  else ray_body<GQ, USCALE, false, BM, PATCH>(a, lacc, ldict, lut, ldir, lgate);
   TDR_TL_END(g_timeline_ray)   // (ray_body's waves return from IT: every thread of a live workgroup arrives here)
 }
 
@@ -436,8 +621,12 @@ int tdr_ray_score(const SuLaunch& L, const SuWs& W, hipStream_t s) {
   r.nsplit = L.ray_split;
   r.npad = L.npad;
   r.part = reinterpret_cast<uint32_t*>(L.part);
+  r.clist = reinterpret_cast<const uint32_t*>(base + W.ray_clist);
+  r.ctab = base + W.ray_ctab;
+  r.gate_ctr = ray_patch(L) ? tdr_profile_gate_ptr() : nullptr;
   const dim3 grid((unsigned)cdiv(L.n * r.nsplit, 4)), block(256);
-  const size_t lds = (size_t)4 * (map->ncls + 1) * 64 * sizeof(unsigned long long);
+  // the lanes' accumulators; behind them, in the patch order, the rings' radii
+  const size_t lds = (size_t)4 * (map->ncls + 1) * 64 * sizeof(unsigned long long) + (ray_patch(L) ? (size_t)r.blocks * 65 * sizeof(float) : 0);
 #define TDR_LAUNCH_RAY(GQ)                                                                            \
   if (L.uniform_scale) hipLaunchKernelGGL((score_polar_ray_kernel<GQ, true>), grid, block, lds, s, r); \
   else hipLaunchKernelGGL((score_polar_ray_kernel<GQ, false>), grid, block, lds, s, r);

@@ -13,6 +13,7 @@ struct SuWs {
   int64_t tab_su, desc, bbox, keys_in, keys_out, vals_in, vals_out, ints, slots, sort_tmp, ray_tab, ray_desc, ray_multi, ray_rad, total;
   int64_t seg_hist;           // the bucket sort's table [segments][nb + 1] (su_colscan_kernel); empty where the rule of shapes
                               // leaves the order to rocPRIM
+  int64_t ray_clist, ray_ctab;   // the compact bin lists of the patch order's sectors and their table (score_prep_kernel)
   // ints: [cnt nb + 1][start nb + 1][slot_start nb + 1][counts 3][n_multi][inexact][mass bound][table is not its factors]
   //       [3 spare]  (int_form_off)
 };
@@ -116,6 +117,11 @@ int tdr_ray_splits(int nb, int nr, int64_t n, bool block_major = false);
 #define RAY_PR 16             // rings of a patch
 #define RAY_PG 16             // scan rows of a unit (four steps of four directions)
 #define RAY_PATCH_MAX_NB 256
+// words of a sector's compact lists: its 1 024 bins in two streams of whole 256-entry blocks (at most five blocks)
+#define RAY_CL_WORDS 1280
+// no entry: scan row 0 and "ring 64" — the slot behind a segment's radii, whose radius leaves the map: the guard cell,
+// unknown — of class 0's plane (an A entry always names a plane), with a count of zero
+#define RAY_CL_NONE 0x01001000u
 static inline bool ray_bm(const SuLaunch& L) { return tdr_cfg().ray_block_major && L.fac != nullptr; }
 static inline bool ray_patch(const SuLaunch& L) { return ray_bm(L) && tdr_cfg().ray_patch && L.nb % RAY_PG == 0 && L.nb <= RAY_PATCH_MAX_NB; }
 static inline int ray_gq(int nr, bool bm) { return bm ? 1 : (nr <= 64 ? 1 : (nr <= 128 ? 2 : 4)); }

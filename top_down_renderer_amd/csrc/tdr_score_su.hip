@@ -102,6 +102,7 @@ struct SuArgs {
 //                       -FLT_MAX, ...}; float minima / maxima: any order)
 //   tab_ray, rad_ray, desc_ray, list, n_list, inexact[0..2], the mass bound     the ray-mapped kernel's layouts and the
 //                       words that decide between the integer and the float form (tdr_score_ray.hip has the layouts)
+//   clist, ctab         (patch order only) the sectors' compact bin lists and their table: described where the kernel writes them
 // Nothing is kept between calls: the table may change under the same pointer.
 //
 // Scan descriptor of a bin (shift-uniform layout), four dwords:
@@ -152,6 +153,8 @@ struct PrepArgs {
   uint32_t* list;
   int32_t* n_list;
   int32_t* inexact;
+  uint32_t* clist;         // the compact lists of the patch order's sectors (NULL: none), and their table
+  int32_t* ctab;
 };
 // float minimum / maximum on a word that holds a float: the sign decides which integer order is the float order (a NaN is left
 // out, as fminf / fmaxf leave it out)
@@ -165,12 +168,20 @@ __device__ __forceinline__ void atomic_max_float(float* at, float v) {
   if (__float_as_int(v) >= 0) atomicMax(reinterpret_cast<int*>(at), __float_as_int(v));
   else atomicMin(reinterpret_cast<unsigned*>(at), __float_as_uint(v));
 }
-#define PREP_DIRS 8   // directions of a workgroup: a wave each
+// directions of a workgroup, a wave each: 8, or — a launch that writes the compact lists — the 16 scan rows of a unit, so
+// that a workgroup holds one whole SECTOR (16 scan rows x 64 rings = four units) and ranks its bins in LDS
+#define PREP_DIRS_COMPACT RAY_PG
+#define PREP_KEYS 80   // compact lists: keys unit * 16 + class code (A), 64 + unit (B)
+template <int PREP_DIRS>
 __device__ __forceinline__ void score_prep_body(const PrepArgs& a, const unsigned block) {
   const int nb = a.nb, nr = a.nr, rf = a.rf, rp = a.rp;
   __shared__ float red[PREP_DIRS][64][4];   // the waves' box candidates
   __shared__ unsigned wg_mass, wg_listed, wg_list_base;
+  // compact lists: a scan row's entries per key (then: the entries of the rows before it), the sector's, and where a key's run starts
+  __shared__ unsigned crow[PREP_DIRS == PREP_DIRS_COMPACT ? PREP_DIRS : 1][PREP_KEYS], ckeys[PREP_KEYS], cbase[PREP_KEYS];
   if (threadIdx.x == 0) { wg_mass = 0; wg_listed = 0; }
+  if constexpr (PREP_DIRS == PREP_DIRS_COMPACT)
+    for (int t = threadIdx.x; t < PREP_DIRS * PREP_KEYS; t += 64 * PREP_DIRS) (&crow[0][0])[t] = 0;
   bool bad = false;   // the dictionary is small: every workgroup checks it for itself
   for (int k = threadIdx.x; k < a.dict_n; k += blockDim.x) bad |= !(fabsf(a.dict[k]) <= 3.402823466e+38f);
   const bool dict_bad = __syncthreads_or(bad);   // (also: the three words above are set)
@@ -283,6 +294,29 @@ __device__ __forceinline__ void score_prep_body(const PrepArgs& a, const unsigne
     else if (nz == 1 && vfirst < 4096.f) d = (uint32_t)vfirst | ((uint32_t)(first + 1) << 12);
     else if (nz >= 1) { listed = true; list_rank = atomicAdd(&wg_listed, 1u); }
   }
+  // ---- the compact lists (tdr_score_ray.hip: the patch order with the table's factors).  The workgroup is ONE sector: its
+  // four units' A lists — the single-class bins the loop multiplies, unit by unit and class by class inside a unit — then the
+  // four B lists: the bins the loop sees as empty (those on `list` too: it counts their cell's known bit).  An entry is
+  // (scan row & 15) << 28 | (ring & 63) << 18 | descriptor — bits 25-31 the byte offset of the row's direction pair, bits 16-24
+  // that of the ring's radius in the kernel's LDS tables: two shifts decode it.  Rings the image
+  // does not have are in neither list.  Inside a class run the entries keep the order scan row, ring: four neighbouring lanes
+  // of a gather are then, as far as the scan allows, neighbouring rings of one scan row — the cells one line holds.  No
+  // atomics: a wave is a scan row, its ranks are ballots; the rows meet in LDS.
+  const bool compact = PREP_DIRS == PREP_DIRS_COMPACT && a.clist != nullptr && j < a.blocks * 64;   // (a whole workgroup)
+  unsigned ckey = 0, crank = 0;
+  if (compact) {
+    const unsigned unit = (unsigned)lane >> 4, code = d >> 12;
+    const unsigned long long umask = 0xFFFFull << (16 * unit), below = (1ull << lane) - 1ull;
+    ckey = code ? unit * 16u + code : 64u + unit;
+    for (unsigned c = 0; c <= (unsigned)a.ncls; c++) {
+      const unsigned long long same = __ballot(real && code == c) & umask;
+      if (real && code == c) {
+        crank = (unsigned)__popcll(same & below);
+        if ((same >> lane) == 1ull) crow[wave][ckey] = crank + 1u;   // (the key's last lane of the row)
+      }
+    }
+  }
+  const uint32_t centry = (((uint32_t)i & (RAY_PG - 1)) << 28) | (((uint32_t)j & 63u) << 18) | d;
   // An EMPTY bin (and one that went on the list) needs its cell's known bit and nothing else — and every class plane carries that
   // bit (bit 15 of a cell).  Four consecutive lanes of a gather — four consecutive rings of one scan row, in every order —
   // are served together by the L1's address path, at a cost per distinct LINE among them: an empty bin between two bins of
@@ -314,6 +348,23 @@ __device__ __forceinline__ void score_prep_body(const PrepArgs& a, const unsigne
     if (wg_mass && (uint64_t)atomicAdd(reinterpret_cast<unsigned*>(a.inexact) + 1, wg_mass) + wg_mass >= (1u << 24)) atomicOr(a.inexact, 1);
     wg_list_base = wg_listed ? (unsigned)atomicAdd(a.n_list, (int)wg_listed) : 0u;
   }
+  if (compact) {   // (80 keys: 16 rows, then up to 80 additions each — nothing next to the loads above)
+    if (threadIdx.x < PREP_KEYS) {
+      unsigned run = 0;
+      for (int w = 0; w < PREP_DIRS; w++) {
+        const unsigned c = crow[w][threadIdx.x];
+        crow[w][threadIdx.x] = run;
+        run += c;
+      }
+      ckeys[threadIdx.x] = run;
+    }
+    __syncthreads();
+    if (threadIdx.x < PREP_KEYS) {
+      unsigned at = 0;
+      for (int q = 0; q < (int)threadIdx.x; q++) at += ckeys[q];
+      cbase[threadIdx.x] = at;
+    }
+  }
   // the box of (ring group, sector): the first of the workgroup's directions in the sector gathers the others'
   if (real && (lane == 0 || jj == 0)) {
     const int sect = sector(i);
@@ -332,6 +383,34 @@ __device__ __forceinline__ void score_prep_body(const PrepArgs& a, const unsigne
   }
   __syncthreads();
   if (listed) a.list[wg_list_base + list_rank] = ((uint32_t)i << 16) | (uint32_t)j;   // (any order: the sums are exact)
+  if (compact) {
+    // sector = (segment of 64 rings, group of 16 scan rows), numbered as the ray-mapped kernel walks them; its lists have a
+    // fixed place (no launch-wide counter): RAY_CL_WORDS words, the A stream from the front in blocks of 256 entries, the B
+    // stream from the first block behind it.  A block is stored lane-major — entry r of a stream at (r >> 8) * 256 + (r & 63) * 4
+    // + ((r >> 6) & 3) — so that ONE 16-byte load per lane brings a wave the entries of four gathers; what a stream's last
+    // block has left is filled with RAY_CL_NONE (the kernel reads whole gathers and tests nothing).  The table, 16 words:
+    // per unit {its first A entry, A entries, its first B entry, B entries} (positions in the two streams)
+    const int64_t sector = (int64_t)(j >> 6) * (nb / RAY_PG) + i / RAY_PG;
+    const unsigned n_a = cbase[64];
+    if (threadIdx.x < 512) {
+      const unsigned stream = threadIdx.x >> 8, t = threadIdx.x & 255u;
+      const unsigned n = stream ? cbase[67] + ckeys[67] - n_a : n_a, blk = (stream ? (n_a + 255u) >> 8 : 0u) + (n >> 8);
+      if (t >= (n & 255u) && (n & 255u)) a.clist[sector * RAY_CL_WORDS + blk * 256u + (t & 63u) * 4u + (t >> 6)] = RAY_CL_NONE;
+    }
+    if (real) {
+      unsigned r = cbase[ckey] + crow[wave][ckey] + crank, blk0 = 0;
+      if (ckey >= 64u) { r -= n_a; blk0 = (n_a + 255u) >> 8; }
+      a.clist[sector * RAY_CL_WORDS + (blk0 + (r >> 8)) * 256u + (r & 63u) * 4u + ((r >> 6) & 3u)] = centry;
+    }
+    if (threadIdx.x < 4) {
+      const unsigned u = threadIdx.x;
+      int32_t* t = a.ctab + sector * 16 + 4 * u;
+      t[0] = (int32_t)cbase[16 * u];
+      t[1] = (int32_t)(cbase[16 * u + 16] - cbase[16 * u]);
+      t[2] = (int32_t)(cbase[64 + u] - n_a);
+      t[3] = (int32_t)ckeys[64 + u];
+    }
+  }
   if (!ray_live) return;
   const int g = j >> 6, l = j & 63, b = g / a.gq, gq = a.gq;
   const int64_t at = a.bm ? ((int64_t)b * nb + i) * 64 + l : (((int64_t)i * a.blocks + b) * 64 + l) * gq + (g - b * gq);
@@ -343,7 +422,8 @@ __device__ __forceinline__ void score_prep_body(const PrepArgs& a, const unsigne
   *reinterpret_cast<float2*>(a.tab_ray + 2 * at) = real ? make_float2(tx, ty) : make_float2(-1.0e30f, -1.0e30f);
   a.desc_ray[at_d] = (uint16_t)d;
 }
-__global__ __launch_bounds__(64 * PREP_DIRS) void score_prep_kernel(PrepArgs a) { score_prep_body(a, blockIdx.x); }
+template <int PREP_DIRS>
+__global__ __launch_bounds__(64 * PREP_DIRS) void score_prep_kernel(PrepArgs a) { score_prep_body<PREP_DIRS>(a, blockIdx.x); }
 
 // Sort key of every particle (in the caller's locality order): its heading bin when its neighbourhood is DENSE, nb when
 // it is SPARSE — the 64 particles around it in the locality (Morton) order are more than `span` map cells apart.  A
@@ -1229,6 +1309,11 @@ SuWs tdr_su_ws(int nb, int nr, int group, int64_t n) {
   w.ray_multi = take((int64_t)nb * nr);
   w.ray_rad = take(T / nb);                    // the rings' radii in ray order (a table given as factors)
   w.seg_hist = take(su_seg_table_reserve(nb, n));   // the bucket sort's table (whatever su_order_bucket says at the time)
+  // the patch order's compact lists: RAY_CL_WORDS words and a table of 16 per sector (16 scan rows x 64 rings)
+  const bool patch_shape = nb % RAY_PG == 0 && nb <= RAY_PATCH_MAX_NB;
+  const int64_t sectors = patch_shape ? (int64_t)(nb / RAY_PG) * ray_blocks(nr, true) : 0;
+  w.ray_clist = take(sectors * RAY_CL_WORDS);
+  w.ray_ctab = take(sectors * 16);
   w.total = o;
   return w;
 }
@@ -1355,7 +1440,15 @@ int tdr_su_prepare(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_
   p.desc_ray = reinterpret_cast<uint16_t*>(base + W.ray_desc);
   p.list = reinterpret_cast<uint32_t*>(base + W.ray_multi);
   p.n_list = ints + 3; p.inexact = ints + 4;
-  hipLaunchKernelGGL(score_prep_kernel, dim3((unsigned)(cdiv(L.nb, PREP_DIRS) * (p.rp / 64))), dim3(64 * PREP_DIRS), 0, s, p);
+  p.clist = nullptr; p.ctab = nullptr;
+  if (p.patch) {   // the compact lists: a workgroup per sector (the direction count is a multiple of 16)
+    p.clist = reinterpret_cast<uint32_t*>(base + W.ray_clist);
+    p.ctab = base + W.ray_ctab;
+    hipLaunchKernelGGL(score_prep_kernel<PREP_DIRS_COMPACT>, dim3((unsigned)(L.nb / PREP_DIRS_COMPACT * (p.rp / 64))),
+                       dim3(64 * PREP_DIRS_COMPACT), 0, s, p);
+  } else {
+    hipLaunchKernelGGL(score_prep_kernel<8>, dim3((unsigned)(cdiv(L.nb, 8) * (p.rp / 64))), dim3(64 * 8), 0, s, p);
+  }
   LAUNCH_CHECK("score_prep");
   return TDR_OK;
 }
