@@ -597,6 +597,12 @@ int tdr_profile_variants(int64_t out[16]);
  * end (always, where a particle's waves do not share a workgroup or the window has 2^24 samples or more); [3] blocks of up
  * to 256 empty bins walked, over all waves. */
 int tdr_profile_ray_gate(int64_t out[4]);
+/* With tdr_profile_enable(2), likewise outside timed regions: what became of the scan bins that hold several classes in
+ * score_polar_su_kernel's assembly path (one atomic per wave and counter).  Reads and resets two counters (synchronises):
+ * [0] four-ring steps the assembly loop handed to the C++ step ("su_full_list" = 0: every step with such a bin; 1: only
+ * steps where a non-finite value is in play); [1] bins the list pass behind the loop scored — with every particle dense,
+ * (dense waves) x (bins of the scan with several classes).  (The 16 counters of tdr_profile_variants are all in use.) */
+int tdr_profile_su_list(int64_t out[2]);
 
 /* The library reads NOTHING from the process environment: behaviour switches are these calls (and the tdr_config_* calls
  * above), process-wide, meant for A/B measurements, tests and debugging — results never depend on them unless stated.
@@ -642,7 +648,12 @@ int tdr_profile_ray_gate(int64_t out[4]);
  *   "init_window_words" words of the generator's stream per window of tdr_k_init_particles (a multiple of 2048, 2048 to
  *                      2^22; default 2^21; same states)
  *   "cart_init_chunk"  particles without a heading whose candidates one scoring launch of tdr_k_score_cart_init covers
- *                      (>= 1; default 4096: DESIGN.md 5.5; bounds its workspace; same results) */
+ *                      (>= 1; default 4096: DESIGN.md 5.5; bounds its workspace; same results)
+ * One more name, not a part of the list above (tests/test_config_table.py replays that list as it was recorded):
+ * "su_full_list" — 1 (default): scan bins that hold several classes are empty to score_polar_su_kernel's assembly loop and
+ * are added behind it, sector by sector, from a list (a mask word per ring group and scan row that the preparation writes),
+ * each class from its plane; 0: the loop hands every four-ring step that holds such a bin to the C++ step (A/B, tests).
+ * Integer sums: same bits.  Ring groups of 4, 8 or 16 rings. */
 int64_t tdr_config_tuning(const char* name, int64_t value);
 /* The rows of score_polar_su_kernel's grid for nchunks ring groups with the last k cut into q sector ranges each (tests):
  * returns the row count R = (nchunks - k') + k' q', k' = k clamped to [0, nchunks], q' = q rounded down to 1, 2, 4 or 8; for
@@ -677,6 +688,13 @@ int tdr_k_su_order(const float* st, int64_t cap, int64_t n, const int32_t* perm,
 int tdr_k_score_prep(const tdr_map_desc* map, const float* tab, const float* scan_pk, int nb, int nr, float res,
                      const float* st, int64_t cap, int64_t n, int64_t n_total, const int32_t* perm, float uniform_scale,
                      float span, float* workspace, tdr_score_ctx* ctx, int64_t* layout, void* const* out, void* stream);
+/* The preparation's mask of the scan bins that hold several classes (tests): after tdr_k_score_prep or a scoring call of
+ * these shapes on `workspace` (with "su_full_list" on and ring groups of 4, 8 or 16 rings; otherwise the words are whatever
+ * the workspace held), *words = 2 C nb words to `out` (device memory), [C][2 nb]: bit jj of word (group c, scan row i) — and
+ * of word nb + i, the rows are stored twice over — says bin (i, ring c G + jj) holds several classes.  workspace or out
+ * NULL: *words alone. */
+int tdr_k_score_prep_full_mask(const tdr_map_desc* map, int nb, int nr, int64_t n, int64_t n_total, const float* workspace,
+                               uint32_t* out, int64_t* words, void* stream);
 /* Device self-test of the scoring kernels: a tiny fixed problem (160 x 160 map, 6 classes, 512 particles) scored by every
  * kernel the library has for it.  The integer-form kernels run generated, hand-scheduled assembly; their sums are exact, so
  * score_polar_su_kernel == score_polar_ray_kernel and score_cart_su_kernel == score_cart_skip_kernel == score_cart_ray_kernel

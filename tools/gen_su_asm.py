@@ -19,6 +19,10 @@ Register plan (fixed registers, all named in the statement's clobber list):
                         step's scalars into the other set before it works on its own)
   s65 / s66 byte offsets of the step in the offset / descriptor streams, s67 steps left - 1,
             s68 steps until the scan rows wrap - 1;  s69..s71 the same offsets / count for the step behind it
+Flagged steps (one of the four bins holds several classes: bit 31 of the first descriptor's last dword): each of the two
+bodies exists a second time, on the same register sets, for them.  There a bin with several classes takes the empty-bin
+path (run_sector's list pass adds it behind the loop); the text is left — the step handed to the C++ step — only without
+the list pass (bit 31 of the %[wrapl] operand clear) or for a bin in which a non-finite value is in play.
 Arithmetic: EXACT.  A scan count is an integer and a dictionary value an integer multiple of 2^-q (tdr_cmap.hip), so a
 class's product sum is accumulated as a 64-bit integer — v_mad_u64_u32, one instruction at the cost of the v_fmac_f32 it
 replaces (tools/valu_cost.hip) — and does not depend on the order of the additions: every kernel, launch and shard gives
@@ -61,6 +65,11 @@ def loop_text(uscale, clamp, mask=True):
     # step k is worked on, so their scalar-cache latency hides behind it
     step(a, uscale, clamp, mask, T=40, D=48, TN=72, DN=80, tag="e", nxt="o")
     step(a, uscale, clamp, mask, T=72, D=80, TN=40, DN=48, tag="o", nxt="e")
+    a("s_branch .Lsu_out%=")
+    # the same two bodies for a FLAGGED step (one of its bins holds several classes): such a bin is empty to them — no gather,
+    # no count, its known bit counted — and run_sector adds it from the sector's list behind the loop (tdr_score_su.hip)
+    step(a, uscale, clamp, mask, T=40, D=48, TN=72, DN=80, tag="e", nxt="o", flagged=True)
+    step(a, uscale, clamp, mask, T=72, D=80, TN=40, DN=48, tag="o", nxt="e", flagged=True)
     a(".Lsu_out%=:")
     a("s_waitcnt lgkmcnt(0)")                        # (a request for the step behind the last one may still be in flight)
     if not mask:
@@ -75,17 +84,39 @@ def loop_text(uscale, clamp, mask=True):
     return [x for x in L if PAD or x != "s_nop 0"]
 
 
-def step(a, uscale, clamp, mask, T, D, TN, DN, tag, nxt):
-    a(f".Lsu_step{tag}%=:")
-    a(f"s_bitcmp1_b32 s{D + 3}, 31")                 # a bin with several classes in this step: hand it to the C++ step
-    a("s_cbranch_scc1 .Lsu_out%=")
+SU_CODE_FULL, SU_CODE_FULL_ALL = 0xFF, 0xFE          # tdr_score_su.hip
+
+
+def step(a, uscale, clamp, mask, T, D, TN, DN, tag, nxt, flagged=False):
+    if flagged:
+        # Entered from the plain copy of the same parity, with the same register sets.  Without the list (bit 31 of %[wrapl] clear) and
+        # for a bin where a non-finite value is in play (SU_CODE_FULL_ALL: every class multiplied) the step is still handed
+        # to the C++ step — before anything of it is done.
+        tag += "f"
+        a(f".Lsu_step{tag}%=:")
+        a("s_bitcmp0_b32 %[wrapl], 31")
+        a("s_cbranch_scc1 .Lsu_out%=")
+        for u in range(4):
+            a(f"s_cmp_eq_u32 s{D + 4 * u}, {SU_CODE_FULL_ALL:#x}")
+            a("s_cbranch_scc1 .Lsu_out%=")
+    else:
+        a(f".Lsu_step{tag}%=:")
+        a(f"s_bitcmp1_b32 s{D + 3}, 31")             # a bin with several classes in this step: the flagged copy of the body
+        a(f"s_cbranch_scc1 .Lsu_step{tag}f%=")
+
+    def skip_if_empty(code, label):                  # an empty bin — to a flagged step: one with several classes too
+        a(f"s_cmp_eq_u32 s{code}, 0")
+        a(f"s_cbranch_scc1 {label}")
+        if flagged:
+            a(f"s_cmp_eq_u32 s{code}, {SU_CODE_FULL:#x}")
+            a(f"s_cbranch_scc1 {label}")
     # the step behind this one: T at byte s69, D at byte s70 (the scan rows wrap: (i + shift) mod nb)
     a("s_add_u32 s69, s65, 32")
     a("s_add_u32 s70, s66, 64")
     a("s_sub_u32 s71, s68, 1")
     a(f"s_cbranch_scc0 .Lsu_nw{tag}%=")
     a("s_mov_b32 s70, 0")
-    a("s_mov_b32 s71, %[wrapm1]")
+    a("s_and_b32 s71, %[wrapl], 0x7fffffff")         # (steps of the scan rows - 1; bit 31 says the list pass is on)
     a(f".Lsu_nw{tag}%=:")
     a(f"s_load_dwordx8 s[{TN}:{TN + 7}], %[tb], s69")
     a(f"s_load_dwordx16 s[{DN}:{DN + 15}], %[db], s70")
@@ -141,8 +172,7 @@ def step(a, uscale, clamp, mask, T, D, TN, DN, tag, nxt):
     # few cells apart — and the lines a gather touches are what bounds the kernel.)
     for u in range(4):
         code, ckc = D + 4 * u, D + 2 + 4 * u
-        a(f"s_cmp_eq_u32 s{code}, 0")
-        a(f"s_cbranch_scc1 .Lsu_a{u}{tag}%=")
+        skip_if_empty(code, f".Lsu_a{u}{tag}%=")
         if not mask:
             coords([u])
         a(f"v_ashrrev_i32 v{20 + u}, 3, v{9 + 2 * u}")
@@ -177,8 +207,7 @@ def step(a, uscale, clamp, mask, T, D, TN, DN, tag, nxt):
     # (every cell the sector can reach known: four more known samples per step, counted at the exit)
     for u in range(4):
         code, val = D + 4 * u, D + 1 + 4 * u
-        a(f"s_cmp_eq_u32 s{code}, 0")
-        a(f"s_cbranch_scc1 .Lsu_b{u}{tag}%=")
+        skip_if_empty(code, f".Lsu_b{u}{tag}%=")
         if mask:
             a(f"v_and_b32 v20, s{val}, v{16 + u}")                               # the bin's count x known (:141-142)
         a(f"v_and_b32 v21, 0xffc, v{24 + u}")                                    # the class's dictionary index * 4
@@ -207,7 +236,10 @@ def step(a, uscale, clamp, mask, T, D, TN, DN, tag, nxt):
     a("s_sub_u32 s67, s67, 1")
     if tag == "e":
         a("s_cbranch_scc1 .Lsu_out%=")               # (falls through into the other copy)
-    else:
+    elif tag == "ef":
+        a("s_cbranch_scc1 .Lsu_out%=")
+        a(f"s_branch .Lsu_step{nxt}%=")
+    else:                                            # ("of" is the text's last body: it falls through to the exit)
         a(f"s_cbranch_scc0 .Lsu_step{nxt}%=")
 
 

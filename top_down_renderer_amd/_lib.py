@@ -196,6 +196,9 @@ SIGNATURES = {
     # wide, vector kernel: 64-particle batches whose results the pass wrote (include/tdr.h)
     "tdr_profile_variants": (_i, [C.POINTER(_i64)]),
     "tdr_profile_ray_gate": (_i, [C.POINTER(_i64)]),
+    # out[2]: steps the dense polar kernel's assembly loop handed back, bins its list pass scored (include/tdr.h)
+    "tdr_profile_su_list": (_i, [C.POINTER(_i64)]),
+    "tdr_k_score_prep_full_mask": (_i, [_vp, _i, _i, _i64, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
     "tdr_score_ctx_set_polar_factors": (_i, [_vp, _vp, _i, _i]),
     "tdr_polar_factors_host": (_i, [_i, _i, _f, _f, _vp]),
     "tdr_k_score_polar_ctx": (_i, [C.POINTER(MapDescC), _vp, _vp, _i, _i, _f, C.POINTER(FilterParamsC), _vp, _i64, _i64,

@@ -123,4 +123,6 @@ __host__ __device__ inline bool tdr_has_kslot(int ncls, int rf) { return ncls + 
 uint32_t* tdr_profile_stats_ptr();
 // likewise the four counters of tdr_profile_ray_gate (tdr_score_ray.hip)
 uint32_t* tdr_profile_gate_ptr();
+// likewise the two counters of tdr_profile_su_list (tdr_score_su.hip)
+uint32_t* tdr_profile_su_list_ptr();
 #endif  // TDR_COMMON_H_

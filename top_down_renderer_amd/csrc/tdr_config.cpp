@@ -46,7 +46,8 @@ const Knob kKnobs[] = {
        return c.su_tail_parts;
      }},
     {"su_order_bucket", [](TdrConfig& c, int64_t v) { return set_flag(c.su_order_bucket, v); }},
-    {"init_device", [](TdrConfig& c, int64_t v) { return set_flag(c.init_device, v); }},
+    {"su_full_list", [](TdrConfig& c, int64_t v) { return set_flag(c.su_full_list, v); }},
+    {"init_device",[](TdrConfig& c, int64_t v) { return set_flag(c.init_device, v); }},
     {"init_window_words", [](TdrConfig& c, int64_t v) {   // < 1: query only; whole tiles, 1 .. INI_MAX_TILES of them
        if (v > 0) c.init_window = std::min<int64_t>((v + INI_TILE - 1) / INI_TILE * INI_TILE, (int64_t)INI_TILE * INI_MAX_TILES);
        return c.init_window;

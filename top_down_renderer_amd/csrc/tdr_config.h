@@ -25,6 +25,7 @@ struct TdrConfig {
   // 5's 13.87 -> 13.62.
   int su_tail_groups = 4, su_tail_parts = 4;
   int su_order_bucket = 1;   // 0: the heading order always through rocPRIM's sort (A/B; su_seg_table_words has the rule)
+  int su_full_list = 1;      // 0: the assembly loop hands a step with a several-class bin to the C++ step (A/B, tests; same bits)
   int ray_split = 0;         // waves per scattered particle; 0: chosen per launch (tdr_ray_splits)
   int ray_borrow = 1;        // empty bins borrow a neighbour's class plane for their known bit (score_prep_kernel)
   int ray_patch = 1;         // 0: the ray order also where the patch order applies (tdr_score_ray.hip; A/B, same bits)

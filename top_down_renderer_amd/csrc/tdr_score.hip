@@ -959,6 +959,27 @@ uint32_t* tdr_profile_gate_ptr() {
   }
   return g_gate_stats;
 }
+// ... and what became of the shift-uniform kernel's bins with several classes (tdr_profile_su_list in tdr.h)
+static uint32_t* g_su_list_stats = nullptr;
+uint32_t* tdr_profile_su_list_ptr() {
+  if (!g_prof_on || !g_prof_variants) return nullptr;
+  if (!g_su_list_stats) {
+    if (hipMalloc((void**)&g_su_list_stats, 2 * sizeof(uint32_t)) != hipSuccess) { g_su_list_stats = nullptr; return nullptr; }
+    (void)hipMemset(g_su_list_stats, 0, 2 * sizeof(uint32_t));
+  }
+  return g_su_list_stats;
+}
+extern "C" int tdr_profile_su_list(int64_t out[2]) {   // reads and resets (synchronises)
+  if (!out) return fail(TDR_ERR_ARG, "profile_su_list: null pointer");
+  out[0] = out[1] = 0;
+  if (!g_su_list_stats) return TDR_OK;
+  uint32_t h[2];
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h, g_su_list_stats, sizeof(h), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemset(g_su_list_stats, 0, sizeof(h)));
+  out[0] = h[0]; out[1] = h[1];
+  return TDR_OK;
+}
 extern "C" int tdr_profile_ray_gate(int64_t out[4]) {   // reads and resets (synchronises)
   if (!out) return fail(TDR_ERR_ARG, "profile_ray_gate: null pointer");
   for (int k = 0; k < 4; k++) out[k] = 0;
@@ -1361,6 +1382,20 @@ extern "C" int tdr_k_score_prep(const tdr_map_desc* map, const float* tab, const
   const int32_t* counts = nullptr;
   if (int rc = tdr_su_prepare(L, W.suw, s, &slots, &counts)) return rc;
   return tdr_su_prep_copy_out(L, W.suw, s, layout, out);
+}
+// The preparation's mask of the bins with several classes (include/tdr.h), out of the workspace a call of these shapes used
+extern "C" int tdr_k_score_prep_full_mask(const tdr_map_desc* map, int nb, int nr, int64_t n, int64_t n_total,
+                                          const float* workspace, uint32_t* out, int64_t* words, void* stream) {
+  if (!map || !words) return fail(TDR_ERR_ARG, "score_prep_full_mask: null pointer");
+  if (n_total <= 0) n_total = n;
+  if (n < 1 || nb < 1 || nr < 1 || map->ncls < 1 || map->ncls > TDR_MAX_CLASSES) return fail(TDR_ERR_ARG, "score_prep_full_mask: bad shape");
+  const ScoreWs W = score_ws(map->ncls, nb, nr, n, n_total);
+  if (!int_form_applies(W, map, tdr_rec_floats(map->ncls))) return fail(TDR_ERR_ARG, "score_prep_full_mask: the call has no integer form");
+  *words = (int64_t)W.su_nchunks * 2 * nb;
+  if (!workspace || !out) return TDR_OK;
+  HIP_TRY(hipMemcpyAsync(out, reinterpret_cast<const int32_t*>(workspace + W.off_su) + W.suw.full_mask, sizeof(uint32_t) * (size_t)*words,
+                         hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return TDR_OK;
 }
 extern "C" int tdr_k_score_polar(const tdr_map_desc* map, const float* tab, const float* scan_pk, int nb, int nr,
                                  float res, const tdr_filter_params* fp, float* st, int64_t cap, int64_t n,

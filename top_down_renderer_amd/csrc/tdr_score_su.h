@@ -14,6 +14,8 @@ struct SuWs {
   int64_t seg_hist;           // the bucket sort's table [segments][nb + 1] (su_colscan_kernel); empty where the rule of shapes
                               // leaves the order to rocPRIM
   int64_t ray_clist, ray_ctab;   // the compact bin lists of the patch order's sectors and their table (score_prep_kernel)
+  int64_t full_mask;          // [groups][2 nb] words: which bins of a (ring group, scan row) hold several classes — what the
+                              // shift-uniform kernel's list pass walks (written while tdr_su_full_list(L) holds)
   // ints: [cnt nb + 1][start nb + 1][slot_start nb + 1][counts 3][n_multi][inexact][mass bound][table is not its factors]
   //       [3 spare]  (int_form_off)
 };
@@ -70,6 +72,12 @@ struct SuLaunch {
   int32_t* ws;               // tdr_su_ws(...).total words
   float span;                // map cells the 64 locality neighbours of a dense particle may span (tdr_su_span_begin)
 };
+// Whether the launch's bins with several classes go to the shift-uniform kernel's list pass (tdr_config_tuning(
+// "su_full_list"), default 1) instead of being handed from its assembly loop to the C++ step one four-ring step at a time:
+// the ring groups the assembly loop takes, whose mask words a wave of the preparation can cut out of one ballot.  Same bits.
+static inline bool tdr_su_full_list(const SuLaunch& L) {
+  return tdr_cfg().su_full_list && (L.group == 4 || L.group == 8 || L.group == 16);
+}
 // ordering passes + the scan-side preparation (everything but the scoring kernels).  slots_out: the slot list — the dense
 // particles by heading bin, every bin padded to whole waves (-1), then the sparse particles in the caller's order
 // (su_key_kernel); counts_out: device words {slots of the heading bins, sparse particles behind them, both together (what

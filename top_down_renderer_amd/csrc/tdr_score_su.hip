@@ -86,6 +86,10 @@ struct SuArgs {
   int64_t npad;            // stride of `part`
   uint32_t* part;          // [rows][2 ncls + 2][npad]: class k's integer sum as {low, high} words, normalisation, known count
   uint32_t* stats;         // NULL, or (profiling) counters of the variants the wave-sectors ran: tdr_profile_variants
+  const uint32_t* full_mask;   // [nchunks][2 nb]: the bins with several classes (score_prep_kernel), NULL: no list pass — the
+                               // assembly loop hands their steps to the C++ step (tdr_config_tuning("su_full_list", 0))
+  unsigned pbase, plane_bytes; // class c's plane: plane_offset's constant pbase + c * plane_bytes (the list pass)
+  uint32_t* list_stats;    // NULL, or (profiling) {steps handed back to the C++ step, bins the list pass scored}: tdr_profile_su_list
 };
 
 // The scan-side preparation of an integer-form launch: ONE kernel, one thread per (scan row / direction i, padded ring j), j
@@ -155,6 +159,8 @@ struct PrepArgs {
   int32_t* inexact;
   uint32_t* clist;         // the compact lists of the patch order's sectors (NULL: none), and their table
   int32_t* ctab;
+  uint32_t* full_mask;     // NULL, or [nchunks][2 nb]: bit jj of word (group, scan row i) — and of word nb + i, so that a sector's
+                           // rows need no wrap — says bin (i, ring group * G + jj) is SU_CODE_FULL (G divides 64, G <= 32)
 };
 // float minimum / maximum on a word that holds a float: the sign decides which integer order is the float order (a NaN is left
 // out, as fminf / fmaxf leave it out)
@@ -257,6 +263,17 @@ __device__ __forceinline__ void score_prep_body(const PrepArgs& a, const unsigne
     const int64_t at = ((int64_t)chunk * nb + i) * group + jj;
     *reinterpret_cast<float2*>(a.tab_su + 2 * at) = make_float2(tx, ty);
     *reinterpret_cast<uint4*>(a.desc + 4 * at) = make_uint4(code, (uint32_t)val, ckc, ((jj & 3) == 0 && anyfull) ? 0x80000000u : 0u);
+  }
+  // the bins with several classes, a word per (ring group, scan row): the wave's 64 rings are whole groups, a group's first
+  // lane cuts its slice out of the ballot (the shift-uniform kernel's list pass walks these words)
+  if (a.full_mask) {   // (uniform)
+    const unsigned long long fullb = __ballot(su_live && code == SU_CODE_FULL);
+    if (su_live && jj == 0) {
+      const uint32_t wv = (uint32_t)(fullb >> lane) & (group >= 32 ? 0xFFFFFFFFu : (1u << group) - 1u);
+      uint32_t* row = a.full_mask + (int64_t)chunk * 2 * nb + i;
+      row[0] = wv;
+      row[nb] = wv;
+    }
   }
   // the boxes: the real rings of a group that this wave holds are consecutive lanes — a segmented reduction towards the
   // segment's first lane (minima and maxima: a lane may meet an operand twice); the waves' candidates meet in LDS below
@@ -720,6 +737,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
   for (int k = 0; k < ND; k++) acc[k] = 0;
   uint32_t norm = 0;
   uint32_t known = 0;
+  uint32_t n_hand = 0, n_listed = 0;   // (profiling, wave-uniform) steps the assembly loop handed back, bins the list pass scored
 
   // per-class accumulate of a bin that holds class cd - 1 only: a switch over a wave-uniform value
   auto single_class = [&](uint32_t cd, uint32_t v, uint32_t ww) {
@@ -775,8 +793,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
   };
 
   // One step with the known mask staged in LDS: the 4 samples (i, j0 + jj .. jj + 3), paired with scan row r.  Known bits
-  // come from word ri * krow4 + (ci >> 5) * 4 + kconst of the staged mask.
-  auto cpp_step = [&](int i, int r, int jj, int krow4, int kconst) {
+  // come from word ri * krow4 + (ci >> 5) * 4 + kconst of the staged mask.  listed: the caller's list pass adds the bins
+  // with several classes (SU_CODE_FULL) — they are empty bins here.
+  auto cpp_step = [&](int i, int r, int jj, int krow4, int kconst, bool listed) {
     const tdr_const_f T = tbase + ((int64_t)i * G + jj) * 2;
     const tdr_const_u D = dbase + ((int64_t)r * G + jj) * 4;
     uint32_t val[4];
@@ -791,7 +810,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
       // the direction's last real ring, so its mask lookup stays inside the staged box — and is masked out of the known
       // count below.
       pad[u] = code[u] == SU_CODE_PAD ? 0u : 0xFFFFFFFFu;
-      code[u] = code[u] == SU_CODE_PAD ? 0u : code[u];
+      code[u] = code[u] == SU_CODE_PAD || (listed && code[u] == SU_CODE_FULL) ? 0u : code[u];
       val[u] = D[4 * u + 1];
       const uint32_t ckc = su_rec_const(code[u]);
       int ri, ci;
@@ -994,8 +1013,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     if constexpr (ASM_LOOP) {
       if (gn == G && lds_base == 0 && (G == 4 || G == 8 || G == 16)) {
         // the steps of the sector as one stream: step k reads T at byte k * 32 from its start and D at byte k * 64 from the
-        // start of scan row (i0 + shift) mod nb, wrapping to row 0; the loop hands a step that holds a bin with several
-        // classes back (nleft >= 0 on exit), cpp_step does that one, and the loop goes on behind it
+        // start of scan row (i0 + shift) mod nb, wrapping to row 0; the loop hands a step back (nleft >= 0 on exit), cpp_step
+        // does that one, and the loop goes on behind it.  Handed back: without the list pass below every step that holds a
+        // bin with several classes; with it only a step with a bin where a non-finite value is in play (SU_CODE_FULL_ALL,
+        // which an integer-form launch never meets) — the others run in the loop's second copy of its bodies, in which a
+        // bin with several classes is an empty bin
         const int spd = G / 4;                                // steps per direction
         int r0 = i0 + shift;
         r0 -= r0 >= nb ? nb : 0;
@@ -1012,6 +1034,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
         const float cmax_s = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(cmaxf)));
         const tdr_v2f scale2 = {scale, scale};
         const uint64_t res2 = (uint64_t)__float_as_uint(a.res) * 0x100000001ull;   // {res, res} in an SGPR pair
+        // the loop's operand for wrapm1 carries, in bit 31, whether bins with several classes are empty to the loop and listed
+        // below (an operand of its own would be one more scalar register held across the loop)
+        const bool flist = a.full_mask != nullptr;
+        const uint32_t wrapl = __builtin_amdgcn_readfirstlane(wrapm1 | (flist ? 0x80000000u : 0u));
         while (nleft != 0xFFFFFFFFu) {
 #define SU_ASM_OPERANDS                                                                                               \
           /* the accumulators (64-bit) are TIED to v[32:43]: the loop reaches them by VGPR-relative indexing */                \
@@ -1021,7 +1047,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
             [nleft] "+v"(nleft), [wleft] "+v"(wleft)                                                                   \
           : [offv] "v"(offv), [krow4] "v"(krow4), [pkcol] "v"(pkcol), [tb] "s"(tbase), [db] "s"(dbase),              \
             [rmax] "s"(rmax_s), [cmax] "s"(cmax_s), [half] "s"(half2), [kconst] "s"(kconst_s), [crec] "s"(crec),           \
-            [wrapm1] "s"(wrapm1), [scale2] "v"(scale2), [res2] "s"(res2)                                               \
+            [wrapl] "s"(wrapl), [scale2] "v"(scale2), [res2] "s"(res2)                                                 \
           : SU_ASM_CLOBBERS
           if (allknown) {   // wave-uniform
             if constexpr (USCALE) asm volatile(SU_ASM_US_ALLKNOWN SU_ASM_OPERANDS);
@@ -1044,13 +1070,58 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
           const int i = i0 + (k >> lsp), jj = (k & (spd - 1)) * 4;
           int r = i + shift;
           r -= r >= nb ? nb : 0;
-          cpp_step(i, r, jj, krow4, kconst);
+          cpp_step(i, r, jj, krow4, kconst, flist);
+          n_hand++;
           toff += 32u;
           doff += 64u;
           if (wleft == 0) { doff = 0; wleft = wrapm1; } else wleft--;
           nleft--;   // 0 -> 0xFFFFFFFF: the sector is done
           toff = __builtin_amdgcn_readfirstlane(toff); doff = __builtin_amdgcn_readfirstlane(doff);
           nleft = __builtin_amdgcn_readfirstlane(nleft); wleft = __builtin_amdgcn_readfirstlane(wleft);
+        }
+        // The sector's bins with several classes — empty to the loop above, which has counted their known bits.  The mask
+        // words of scan rows r0 .. r0 + (i1 - i0) - 1 (stored twice over: no wrap) name them; each is scored from the class
+        // planes like the loop's single-class bins, one 2-byte gather per class present.  ~1 % of a LiDAR scan's bins; the
+        // sums are exact integers, so adding them here instead of in ray order changes no bit.
+        if (flist) {   // (uniform)
+          const tdr_const_u fm = (tdr_const_u)a.full_mask + ((int64_t)rgroup * 2 * nb + r0);
+          for (int k = 0; k < i1 - i0; k++) {
+            uint32_t wv = fm[k];   // (scalar load: wave-uniform)
+            if (wv == 0) continue;
+            const int i = i0 + k;
+            int r = r0 + k;
+            r -= r >= nb ? nb : 0;
+            do {
+              const int jj = __builtin_ctz(wv);
+              wv &= wv - 1u;
+              n_listed++;
+              const tdr_const_f T = tbase + ((int64_t)i * G + jj) * 2;
+              const uint32_t total = dbase[((int64_t)r * G + jj) * 4 + 1];
+              int ri, ci;
+              cell(T[0], T[1], ri, ci);
+              int kmsk = -1;   // 0 / -1: the cell's known bit
+              if (!allknown) {
+                int wa;
+                asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(wa) : "v"(ri), "v"(krow4), "s"(kconst_s));
+                const int cw5 = ci >> 5;
+                unsigned la;
+                asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(la) : "v"(cw5), "v"(wa));
+                const uint32_t bits = lds_word(la);
+                asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(kmsk) : "v"(bits), "v"(ci));
+              }
+              norm += (uint32_t)kmsk & total;   // the bin's count x known (state_particle.cpp:141-142)
+              const tdr_const_f S = scanc + ((int64_t)(j0 + jj) * nb + r) * RF;
+#pragma unroll
+              for (int c = 0; c < ND; c++) {
+                const float sc = c < a.ncls ? S[c] : 0.f;
+                if (sc != 0.f) {   // wave-uniform
+                  const uint32_t pc = map_ushort(plane_offset(ri, ci, pkcol, (int)(a.pbase + (uint32_t)c * a.plane_bytes)));
+                  const uint32_t m = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds.dict) + (pc & 0xFFCu));
+                  acc[c] += (uint64_t)(uint32_t)sc * (uint64_t)m;
+                }
+              }
+            } while (wv != 0);
+          }
         }
         return;
       }
@@ -1060,7 +1131,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
       r -= r >= nb ? nb : 0;
       for (int jj = 0; jj < gn; jj += 4) {
         // (the flag sits on the step's first bin: score_prep_kernel)
-        if (dbase[((int64_t)r * G + jj) * 4 + 3] >> 31) cpp_step(i, r, jj, krow4, kconst);
+        if (dbase[((int64_t)r * G + jj) * 4 + 3] >> 31) cpp_step(i, r, jj, krow4, kconst, false);
         else cpp_step_plane(i, r, jj, krow4, kconst);
       }
     }
@@ -1165,6 +1236,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
       }
     o[(int64_t)(2 * a.ncls) * a.npad] = norm;
     o[(int64_t)(2 * a.ncls + 1) * a.npad] = known;
+    if (a.list_stats && lane == 0) {   // (profiling: one atomic per wave and counter)
+      if (n_hand) atomicAdd(&a.list_stats[0], n_hand);
+      if (n_listed) atomicAdd(&a.list_stats[1], n_listed);
+    }
   }
   TDR_TL_END(g_timeline_su)
 }
@@ -1314,6 +1389,7 @@ SuWs tdr_su_ws(int nb, int nr, int group, int64_t n) {
   const int64_t sectors = patch_shape ? (int64_t)(nb / RAY_PG) * ray_blocks(nr, true) : 0;
   w.ray_clist = take(sectors * RAY_CL_WORDS);
   w.ray_ctab = take(sectors * 16);
+  w.full_mask = take(nchunks * 2 * nb);   // the bins with several classes, a word per (ring group, scan row), rows twice over
   w.total = o;
   return w;
 }
@@ -1441,6 +1517,7 @@ int tdr_su_prepare(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_
   p.list = reinterpret_cast<uint32_t*>(base + W.ray_multi);
   p.n_list = ints + 3; p.inexact = ints + 4;
   p.clist = nullptr; p.ctab = nullptr;
+  p.full_mask = tdr_su_full_list(L) ? reinterpret_cast<uint32_t*>(base + W.full_mask) : nullptr;
   if (p.patch) {   // the compact lists: a workgroup per sector (the direction count is a multiple of 16)
     p.clist = reinterpret_cast<uint32_t*>(base + W.ray_clist);
     p.ctab = base + W.ray_ctab;
@@ -1501,6 +1578,10 @@ int tdr_su_score(const SuLaunch& L, const SuWs& W, hipStream_t s) {
   u.slots = base + W.slots; u.nslots = nslots;
   u.group = L.group; u.nchunks = L.nchunks; u.tail_k = L.tail_k; u.tail_q = L.tail_q; u.ncls = map->ncls; u.npad = L.npad; u.part = reinterpret_cast<uint32_t*>(L.part);
   u.stats = tdr_profile_stats_ptr();
+  u.full_mask = tdr_su_full_list(L) ? reinterpret_cast<const uint32_t*>(base + W.full_mask) : nullptr;
+  u.plane_bytes = (unsigned)(tdr_cmap_plane_words(map->ncls, map->rows, map->cols) * 4);   // (as tdr_su_prepare has them)
+  u.pbase = (unsigned)(tdr_cmap_plane_offset_words(map->ncls, map->rows, map->cols) * 4) + (unsigned)(plane_trows(map->rows) * 128) + 128u;
+  u.list_stats = tdr_profile_su_list_ptr();
   int rg, r0, r1;
   const int rows = su_tail_plan(L.nchunks, L.tail_k, L.tail_q, -1, &rg, &r0, &r1);
   if (L.rows != rows) return fail(TDR_ERR_ARG, "score: %d rows of partial sums for a plan of %d", L.rows, rows);
