@@ -1465,6 +1465,74 @@ int tdr_fuser_get_votes(const tdr_fuser* f, uint32_t* votes_out);
 int tdr_fuser_get_labels(const tdr_fuser* f, uint8_t* labels_out);
 int tdr_fuser_stats(const tdr_fuser* f, uint64_t* out9);
 
+/* ---- KLD-sampling count: the pose bins the particle set occupies choose the next count (csrc/tdr_kld.hip,
+ * csrc/tdr_host_kld.cpp) --------------------------------------------------------------------------------
+ * A DEFINITION (the reference chooses its count from the mixture's ellipse areas, particle_filter.cpp:151-157; this is the
+ * rule of KLD-sampling, Fox 2001, AMCL's kld_err / kld_z, applied to the bins the CURRENT set occupies): count the distinct
+ * pose-space bins among all n particles, and keep as many particles as that many bins need.  It feeds n_target of
+ * tdr_filter_update like tdr_filter_adaptive_count; nothing on the per-scan path changes.
+ *   The key of particle p (float32, no contraction):
+ *     centre  s = st[SCALE], cx = st[DX] * s + st[INIT_X], cy = st[DY] * s + st[INIT_Y] (the scorer's centre, map pixels);
+ *     ix = (int)floorf(med3(cx / bin_xy_px, -524288.f, 524287.f)), iy likewise from cy (IEEE division; floor, not
+ *       truncation: -0.5 px lies in bin -1; everything beyond +-2^19 bins shares the outermost bin);
+ *     it = the scorer's circular shift of theta (state_particle.cpp:124-128) with theta_bins in place of the scan's direction
+ *       count when have_init != 0, and it = theta_bins otherwise: a particle without a heading occupies a bin of its own per
+ *       position.  theta is expected finite (the conversion of a non-finite or astronomically large quotient saturates);
+ *     is = bits(s) >> (23 - scale_bits): exponent and the top scale_bits mantissa bits (2^scale_bits bins per octave), an
+ *       exact integer operation; a fixed or frozen scale gives one value for all particles;
+ *     key = (uint64)(ix + 524288) << 43 | (uint64)(iy + 524288) << 23 | (uint64)it << 14 | is   (20 + 20 + 9 + 14 bits:
+ *       bit 63 is clear, so the all-ones word TDR_KLD_NO_KEY is no key).
+ *     A particle with a non-finite cx, cy or s, or with s <= 0, has no key: it is not counted in k but in `skipped`.  Gated
+ *     particles (off the map, scale out of range) are counted like any other: the key depends on the state alone.
+ *   k = the number of distinct keys among particles [0, n).
+ *   tdr_kld_bound_host, in double, in this order: k < 2 gives 0; otherwise a = 2.0 / (9.0 * (k - 1)),
+ *     t = 1.0 - a + sqrt(a) * z, n_kld = ceil(((k - 1) / (2.0 * epsilon)) * (t * t * t)), saturated at 2^62.
+ *   tdr_kld_target_host = min(max(n_kld, n_min, 3 * last_count / 4 + 10), max_count): the shrink limit and the cap of
+ *     particle_filter.cpp:157, a drop-in for tdr_adaptive_count_host.
+ * Layer 1 (device pointers, asynchronous, no allocation).  The kernel: one thread per particle; equal keys are merged among
+ * the 64 lanes of a wave; each distinct key of a wave is inserted once into an open-addressing table of 64-bit words in
+ * global memory (compare-and-swap, linear probing, empty = all ones), and an insertion counts exactly when its swap found
+ * the empty word: integer atomics only, the two words do not depend on order.  workspace: tdr_kld_workspace_bytes(n) bytes
+ * (a power of two of slots, at least 2 n).  tdr_k_kld_count fills the table and zeroes out2 on the stream in front of the
+ * kernel; out2: DEVICE {k, skipped}.  tdr_k_kld_count_jobs: grid.y = the job, a DEVICE array of jobs; the CALLER has filled
+ * every table with all-ones bytes and zeroed every out2 (one fill over adjoining slices).  table_slots: a power of two,
+ * >= 2 n, >= 64.  tdr_k_kld_keys: the keys alone, TDR_KLD_NO_KEY where there is none (tests and tools). */
+#define TDR_KLD_NO_KEY 0xFFFFFFFFFFFFFFFFull
+typedef struct tdr_kld_params {
+  float   bin_xy_px;      /* > 0, finite: bin edge in map pixels (the units of the particle centre) */
+  int32_t theta_bins;     /* T, 1..511: heading bins over one turn */
+  int32_t scale_bits;     /* b, 0..6: mantissa bits of the scale that enter the key (2^b bins per octave) */
+  double  epsilon, z;     /* Fox's bound: epsilon > 0, z >= 0 (0.05 and 2.326 are the usual defaults) */
+  int64_t n_min;          /* >= 1 */
+} tdr_kld_params;
+typedef struct tdr_kld_job {
+  const float* st;        /* [TDR_ST_FIELDS][cap] device */
+  int64_t cap, n;
+  uint64_t* table;        /* [table_slots] device, the job's own, all ones */
+  int64_t table_slots;
+  int64_t* out2;          /* {k, skipped} device, the job's own, zero */
+} tdr_kld_job;
+size_t tdr_kld_workspace_bytes(int64_t n);
+int tdr_k_kld_keys(const float* st, int64_t cap, int64_t n, const tdr_kld_params* p, uint64_t* keys_out, void* stream);
+int tdr_k_kld_count(const float* st, int64_t cap, int64_t n, const tdr_kld_params* p, void* workspace, int64_t* out2,
+                    void* stream);
+int tdr_k_kld_count_jobs(const tdr_kld_job* jobs_dev, int n_jobs, const tdr_kld_params* p, void* stream);
+int64_t tdr_kld_bound_host(int64_t k, double epsilon, double z);
+int64_t tdr_kld_target_host(int64_t n_kld, int64_t last_count, int64_t n_min, int64_t max_count);
+/* Handle layer.  tdr_filter_kld_count: the fill, the kernel and one 16-byte read-back on the filter's stream; the table is
+ * the handle's, allocated on first use for n_max.  It READS the states: states, raw and normalised weights, the cached
+ * statistics and their validity, the generator's position, tdr_filter_step_count and the stored mixture stay as they were.
+ * *target_out = tdr_kld_target_host(bound(k), the filter's count, n_min, its n_max); a filter without particles gives k = 0.
+ * Outputs may be NULL.  tdr_batch_kld_count: k filters (polar or Cartesian, on any maps) with one job upload, one fill
+ * over the filters' table slices, one launch, one read-back; each filter's numbers equal its own call's.
+ * Refused with TDR_ERR_ARG, nothing written, no filter changed: a null filter or parameter pointer, a filter twice, k < 1,
+ * bin_xy_px not finite or <= 0, theta_bins outside 1..511, scale_bits outside 0..6, epsilon <= 0 or not finite, z < 0 or
+ * not finite, n_min < 1, and SHARDED filters: the distinct count of a sharded set is a global quantity, and combining the
+ * ranks' key sets is not built. */
+int tdr_filter_kld_count(tdr_filter* f, const tdr_kld_params* p, int64_t* k_out, int64_t* skipped_out, int64_t* target_out);
+int tdr_batch_kld_count(tdr_filter* const* filters, int k, const tdr_kld_params* p, int64_t* k_out, int64_t* skipped_out,
+                        int64_t* target_out, void* stream);
+
 /* internal: lets the handle layer (csrc/tdr_host_*.cpp) report through tdr_last_error() */
 int tdr_set_error(int code, const char* msg);
 

@@ -128,6 +128,14 @@ class ParticleFilter {
     }
   }
   void setAdaptiveCount(bool on) { adaptive_ = on; }   // :151-157 from the clusters of the last computeGMM
+  // KLD-sampling count (extension; include/tdr.h): the particle count the pose bins of the CURRENT set ask for, counted on
+  // the device over all particles (tdr_filter_kld_count) — what setTargetCount() takes.  *k: the occupied bins.  The filter
+  // is read, not changed.  Throws on bad parameters and on a sharded filter (the distinct count is a global quantity).
+  int64_t kldCount(const KldParams& p, int64_t* k = nullptr) {
+    int64_t target = 0;
+    check(tdr_filter_kld_count(f_, &p, k, nullptr, &target), "kldCount");
+    return target;
+  }
   void computeCov(Eigen::Matrix4f& cov) { stat(1, nullptr, &cov); }                        // :226-236
   void maxLikelihood(Eigen::Vector4f& state) { stat(1, &state, nullptr); }                 // :222-224
   void computeMeanCov(Eigen::Matrix4f& cov) { stat(0, nullptr, &cov); }                    // :205-220

@@ -76,6 +76,23 @@ class ParticleFilterBatch {
     if (tdr_batch_compute_gmm(handles.data(), (int)handles.size(), stream) != TDR_OK)
       throw std::runtime_error(std::string("ParticleFilterBatch::computeGMM: ") + tdr_last_error());
   }
+  // kldCount(p) of every filter through tdr_batch_kld_count: one job upload, one fill, one launch and one read-back for
+  // the batch; targets[i] (and bins[i], when asked for) are what filters[i]->kldCount(p, &k) returns.  The filters need not
+  // share a map.  Throws on a refused batch (bad parameters, a null or repeated filter, a sharded one); no filter changes.
+  void kldCount(const std::vector<ParticleFilter*>& filters, const KldParams& p, std::vector<int64_t>& targets,
+                std::vector<int64_t>* bins = nullptr, void* stream = nullptr) {
+    targets.assign(filters.size(), 0);
+    if (bins) bins->assign(filters.size(), 0);
+    if (filters.empty()) return;
+    std::vector<tdr_filter*> handles(filters.size(), nullptr);
+    for (size_t i = 0; i < filters.size(); i++) {
+      if (!filters[i]) throw std::invalid_argument("ParticleFilterBatch::kldCount: null filter");
+      handles[i] = filters[i]->handle();
+    }
+    if (tdr_batch_kld_count(handles.data(), (int)handles.size(), &p, bins ? bins->data() : nullptr, nullptr, targets.data(),
+                            stream) != TDR_OK)
+      throw std::runtime_error(std::string("ParticleFilterBatch::kldCount: ") + tdr_last_error());
+  }
   // renderViz(out, h, w, pub_scale, arrows[k]) of every filter through tdr_batch_visualize: one launch per stage, one
   // read-back and one wait for the batch, each filter over its own background.  arrows: empty, or one list per filter.
   // Throws on a refused batch (a null or repeated filter, a sharded one, one without a background) before any device work.

@@ -68,6 +68,12 @@ class ParticleFilterCartesian {
   void computeGMM() { check(tdr_filter_compute_gmm(f_), "computeGMM"); }
   void computeGMMDevice() { check(tdr_filter_compute_gmm_device(f_), "computeGMMDevice"); }   // the fit as HIP kernels
   void setTargetCount(int n) { target_count_ = n; }
+  // KLD-sampling count (ParticleFilter::kldCount): the count the pose bins of the current set ask for; *k: the bins
+  int64_t kldCount(const KldParams& p, int64_t* k = nullptr) {
+    int64_t target = 0;
+    check(tdr_filter_kld_count(f_, &p, k, nullptr, &target), "kldCount");
+    return target;
+  }
   void configure(bool parity_rng, int locality_every) { check(tdr_filter_configure(f_, parity_rng, locality_every), "configure"); }
   void updateMap(const uint8_t* label_img, int img_h, int img_w, const std::vector<int>& flatten_lut,
                  const Eigen::Vector2i& map_center) {

@@ -48,6 +48,16 @@ typedef struct FilterParams {
   std::vector<float> class_weights;
 } FilterParams;
 
+// KLD-sampling count (extension; include/tdr.h, "KLD-sampling count"): the pose bins and Fox's bound, with AMCL's usual
+// kld_err / kld_z.  ParticleFilter::kldCount, TopDownRenderCore::Config::kld.
+struct KldParams : tdr_kld_params {
+  KldParams() : tdr_kld_params{4.f, 36, 3, 0.05, 2.326, 100} {}
+};
+inline bool sameKldParams(const tdr_kld_params& a, const tdr_kld_params& b) {
+  return a.bin_xy_px == b.bin_xy_px && a.theta_bins == b.theta_bins && a.scale_bits == b.scale_bits &&
+         a.epsilon == b.epsilon && a.z == b.z && a.n_min == b.n_min;
+}
+
 inline tdr_filter_params to_tdr_params(const FilterParams& p, int num_classes) {
   tdr_filter_params c{};
   c.pos_cov = p.pos_cov; c.theta_cov = p.theta_cov; c.regularization = p.regularization;

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <stdexcept>
 
 #include "top_down_render/particle_filter.h"
 #include "top_down_render/scan_renderer_polar.h"
@@ -35,6 +36,12 @@ class TopDownRenderCore {
     // the publishPoseEst of every gmm_every-th step the mixture is refitted on the device (computeGMMDevice) and every
     // update resamples to the count of :151-157.  0: never — the particle count stays particle_count.
     int gmm_every = 0;
+    // KLD-sampling count (extension; include/tdr.h): after the publishPoseEst of every kld_every-th step the pose bins of
+    // the particle set are counted on the device (ParticleFilter::kldCount) and the following updates resample to the
+    // count they ask for.  0: never — no call, no allocation.  Together with gmm_every > 0 it is refused at initialize:
+    // two rules for one number.
+    int kld_every = 0;
+    KldParams kld;
   };
   struct PoseEst {                      // what publishPoseEst computed this step
     Eigen::Matrix4f cov;                // computeMeanCov (:333)
@@ -87,6 +94,7 @@ class TopDownRenderCore {
     updateFilter(top_down_, top_down_geo_, current_range_scale_, trans, yaw);                 // :559
     PoseEst e = publishPoseEst();                                                            // :560
     if (countStepAndGmmDue()) filter_->computeGMMDevice();
+    if (countStepAndKldDue()) filter_->setTargetCount((int)filter_->kldCount(cfg_.kld));
     if (est) *est = e;
     return true;
   }
@@ -152,7 +160,11 @@ class TopDownRenderCore {
   friend class TopDownRenderCoreBatch;   // steps many cores at once (top_down_render_core_batch.h)
   // counts the step AND says whether its mixture fit is due (Config::gmm_every): exactly one call per step
   bool countStepAndGmmDue() { return cfg_.gmm_every > 0 && ++steps_ % cfg_.gmm_every == 0; }
+  // ... the same for the KLD-sampling count (Config::kld_every; never both, finishInit)
+  bool countStepAndKldDue() { return cfg_.kld_every > 0 && ++steps_ % cfg_.kld_every == 0; }
   void finishInit(FilterParams& filter_params, const Eigen::VectorXi& flatten_lut) {
+    if (cfg_.kld_every > 0 && cfg_.gmm_every > 0)
+      throw std::invalid_argument("TopDownRenderCore: kld_every and gmm_every are two rules for one particle count; set one of them");
     map_->samplePtsPolar(Eigen::Vector2i(cfg_.theta_bins, cfg_.range_bins), (float)(2 * M_PI / cfg_.theta_bins));   // :115
     filter_ = new ParticleFilter(cfg_.particle_count, map_, filter_params, cfg_.seed);                              // :116
     renderer_ = new ScanRendererPolar(flatten_lut);                                                                 // :117
@@ -170,7 +182,7 @@ class TopDownRenderCore {
   float last_res_ = 0.f;
   bool is_converged_ = false;          // :83
   bool device_scan_ = false;
-  int64_t steps_ = 0;                  // steps taken (counted only with Config::gmm_every > 0)
+  int64_t steps_ = 0;                  // steps taken (counted only with Config::gmm_every or kld_every > 0)
 };
 
 #endif  // TOP_DOWN_RENDER_CORE_H_

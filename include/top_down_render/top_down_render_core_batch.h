@@ -7,7 +7,8 @@
 //      cache)
 //   4. every core's own publishPoseEst() — it reads the cache, so it makes no device call except in the step in which a
 //      filter's scale freezes
-//   5. one ParticleFilterBatch::computeGMM for the cores whose mixture fit is due (Config::gmm_every): tdr_batch_compute_gmm
+//   5. one ParticleFilterBatch::computeGMM for the cores whose mixture fit is due (Config::gmm_every): tdr_batch_compute_gmm;
+//      one ParticleFilterBatch::kldCount for those whose KLD-sampling count is due (Config::kld_every): tdr_batch_kld_count
 //
 // Every core ends where cores[i]->takeStep(...) with setDeviceScan(true) leaves it: filter states, weights and generator
 // position, PoseEst, currentRangeScale, lastRes, isConverged.  One difference: the host topDown() images are not filled
@@ -84,13 +85,28 @@ class TopDownRenderCoreBatch {
       throw std::runtime_error(std::string("TopDownRenderCoreBatch::takeStep: ") + tdr_last_error());
     if (ests) ests->resize(k);
     std::vector<ParticleFilter*> due;
+    std::vector<size_t> kld_due;
     for (size_t i = 0; i < k; i++) {
       cores[i]->last_res_ = res[i];
       TopDownRenderCore::PoseEst e = cores[i]->publishPoseEst();                           // :560
       if (cores[i]->countStepAndGmmDue()) due.push_back(filters[i]);
+      if (cores[i]->countStepAndKldDue()) kld_due.push_back(i);
       if (ests) (*ests)[i] = e;
     }
     batch_.computeGMM(due, stream);   // one mixture fit for the cores whose step is due (Config::gmm_every)
+    // ... and one bin count for those whose KLD-sampling count is due (Config::kld_every): cores with equal parameters
+    // share a tdr_batch_kld_count
+    while (!kld_due.empty()) {
+      const KldParams& p = cores[kld_due[0]]->cfg_.kld;
+      std::vector<size_t> same, rest;
+      for (size_t i : kld_due) (sameKldParams(p, cores[i]->cfg_.kld) ? same : rest).push_back(i);
+      std::vector<ParticleFilter*> fs;
+      for (size_t i : same) fs.push_back(filters[i]);
+      std::vector<int64_t> targets;
+      batch_.kldCount(fs, p, targets, nullptr, stream);
+      for (size_t j = 0; j < same.size(); j++) filters[same[j]]->setTargetCount((int)targets[j]);
+      kld_due.swap(rest);
+    }
     return true;
   }
   // The two per-scan pictures of every core after a takeStep (publishSemanticTopDown, :246-254, and the particle picture,

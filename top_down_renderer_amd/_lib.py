@@ -87,6 +87,21 @@ class FuseJobC(C.Structure):
                 ("pad2", C.c_float)]
 
 
+class KldParamsC(C.Structure):
+    """tdr_kld_params (include/tdr.h, "KLD-sampling count")."""
+    _fields_ = [("bin_xy_px", C.c_float), ("theta_bins", C.c_int32), ("scale_bits", C.c_int32), ("epsilon", C.c_double),
+                ("z", C.c_double), ("n_min", C.c_int64)]
+
+
+class KldJobC(C.Structure):
+    """tdr_kld_job: one filter of a batched count."""
+    _fields_ = [("st", C.c_void_p), ("cap", C.c_int64), ("n", C.c_int64), ("table", C.c_void_p), ("table_slots", C.c_int64),
+                ("out2", C.c_void_p)]
+
+
+KLD_NO_KEY = 0xFFFFFFFFFFFFFFFF
+
+
 class PoseStatsC(C.Structure):
     """tdr_pose_stats: one filter's result of a tdr_batch_pose."""
     _fields_ = [("mean", C.c_float * 4), ("cov", C.c_float * 16), ("scale", C.c_float), ("n", C.c_int64)]
@@ -376,6 +391,15 @@ SIGNATURES = {
     "tdr_fuser_get_votes": (_i, [_vp, _vp]),
     "tdr_fuser_get_labels": (_i, [_vp, _vp]),
     "tdr_fuser_stats": (_i, [_vp, _vp]),
+    # KLD-sampling count (csrc/tdr_kld.hip, csrc/tdr_host_kld.cpp)
+    "tdr_kld_workspace_bytes": (C.c_size_t, [_i64]),
+    "tdr_k_kld_keys": (_i, [_vp, _i64, _i64, C.POINTER(KldParamsC), _vp, _vp]),
+    "tdr_k_kld_count": (_i, [_vp, _i64, _i64, C.POINTER(KldParamsC), _vp, _vp, _vp]),
+    "tdr_k_kld_count_jobs": (_i, [_vp, _i, C.POINTER(KldParamsC), _vp]),
+    "tdr_kld_bound_host": (_i64, [_i64, C.c_double, C.c_double]),
+    "tdr_kld_target_host": (_i64, [_i64, _i64, _i64, _i64]),
+    "tdr_filter_kld_count": (_i, [_vp, C.POINTER(KldParamsC), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "tdr_batch_kld_count": (_i, [_vp, _i, C.POINTER(KldParamsC), _vp, _vp, _vp, _vp]),
     "tdr_set_error": (_i, [_i, C.c_char_p]),
     "tdr_locality_tmp_ints": (C.c_size_t, [_i64, _i, _i]),
     "tdr_locality_pose_tmp_ints": (C.c_size_t, [_i64]),

@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import BatchCloudC, BatchInputC, FilterParamsC, PoseStatsC, VizRequestC, check
+from .particle_filter import kld_params_c
 
 _vp = C.c_void_p
 STATE_DTYPE = np.dtype([("init_x_px", "<f4"), ("init_y_px", "<f4"), ("dx_m", "<f4"), ("dy_m", "<f4"), ("theta", "<f4"),
@@ -303,6 +304,14 @@ class FilterHandle:
         check(self.L.tdr_filter_get_gmm(self.h, _lib.GMM_MAX_K, C.byref(k), _ptr(means), _ptr(covs)))
         return means[: k.value].copy(), covs[: k.value].reshape(-1, 3, 3).copy()
 
+    def kld_count(self, params):
+        """(k, skipped, target) of tdr_filter_kld_count: the pose bins the particles occupy, the particles without a key, the
+        n_target of the next update.  params: KldParams or KldParamsC.  The filter is read, not changed."""
+        p = params if isinstance(params, _lib.KldParamsC) else params.to_c()
+        k, sk, t = C.c_int64(), C.c_int64(), C.c_int64()
+        check(self.L.tdr_filter_kld_count(self.h, C.byref(p), C.byref(k), C.byref(sk), C.byref(t)))
+        return k.value, sk.value, t.value
+
     def set_viz_background(self, bgr=None, labels=None, lut=None):
         """The picture's background: bgr (H, W, 3) uint8, or labels (H, W) uint8 coloured on the device through lut
         (256 BGR triplets; tdr_filter_set_viz_background_labels)."""
@@ -419,6 +428,18 @@ def compute_gmm_batch(filters, stream=None):
     k = len(filters)
     arr = (_vp * max(k, 1))(*[f.h if f is not None else None for f in filters])
     check(L.tdr_batch_compute_gmm(arr, k, _vp(stream) if stream else None))
+
+
+def kld_count(filters, params, stream=None):
+    """FilterHandle.kld_count of every filter in one tdr_batch_kld_count (one job upload, one fill, one launch, one
+    read-back): (k[n], skipped[n], target[n]) int64 arrays.  The filters may be polar or Cartesian and need not share a map."""
+    L = _lib.load()
+    n = len(filters)
+    p = params if isinstance(params, _lib.KldParamsC) else params.to_c()
+    arr = (_vp * max(n, 1))(*[f.h if f is not None else None for f in filters])
+    k, sk, t = (np.zeros(max(n, 1), np.int64) for _ in range(3))
+    check(L.tdr_batch_kld_count(arr, n, C.byref(p), _ptr(k), _ptr(sk), _ptr(t), _vp(stream) if stream else None))
+    return k[:n], sk[:n], t[:n]
 
 
 def render_batch(renderers, clouds, res, ang_res, ncls, nb, nr, stream=None):
@@ -566,6 +587,8 @@ class LoopBatch:
             raise ValueError("LoopBatch: one renderer per filter")
         cfgs = list(cfgs) if isinstance(cfgs, (list, tuple)) else [cfgs or CoreConfig()] * k
         self.filters, self.renderers = list(filters), list(renderers)
+        for c in cfgs:
+            c.check()
         self.cores = [TopDownRenderCore(c) for c in cfgs]
         self.ang_res, self.ncls, self.nb, self.nr = float(ang_res), int(ncls), int(nb), int(nr)
         self.stats = (0, 0)
@@ -578,17 +601,25 @@ class LoopBatch:
         render_batch(self.renderers, clouds, [float(r) for r in res], self.ang_res, self.ncls, self.nb, self.nr, stream)
         if n_targets is None and any(c.cfg.gmm_every > 0 for c in self.cores):   # :151-157 from each robot's last fit
             n_targets = [f.adaptive_count() if c.cfg.gmm_every > 0 else -1 for c, f in zip(self.cores, self.filters)]
+        if n_targets is None and any(c.kld_target_ is not None for c in self.cores):   # ... or from its last bin count
+            n_targets = [-1 if c.kld_target_ is None else c.kld_target_ for c in self.cores]
         self.stats = step_batch(self.filters, self.renderers, [float(r) for r in res], priors, n_targets, stream)
         mean, cov, scale, n = pose_batch(self.filters, stream)
-        out, due = [], []
+        out, due, kld_due = [], [], {}
         for i, (c, f) in enumerate(zip(self.cores, self.filters)):
             c.filter_ = _PoseView(f, mean[i], cov[i], float(scale[i]), n[i])
             out.append(c.publishPoseEst())
             c.filter_ = None
             if c.countStepAndGmmDue():
                 due.append(f)
+            if c.countStepAndKldDue():   # (cores with equal parameters share a launch)
+                kld_due.setdefault(bytes(kld_params_c(c.cfg.kld)), []).append(i)
         if due:   # one mixture fit for the robots whose step is due (CoreConfig.gmm_every)
             compute_gmm_batch(due, stream)
+        for ids in kld_due.values():   # one bin count for the robots whose step is due (CoreConfig.kld_every)
+            _, _, target = kld_count([self.filters[i] for i in ids], self.cores[ids[0]].cfg.kld, stream)
+            for i, t in zip(ids, target):
+                self.cores[i].kld_target_ = int(t)
         return out
 
     def scan_pictures(self, unflatten, lut_bgr, stream=None):

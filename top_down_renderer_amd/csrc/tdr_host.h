@@ -190,6 +190,7 @@ struct tdr_filter {
   DevBuf<double> gmm_dev;     // the device fit: samples [num][4], the candidate fits' outputs and workspaces (gmm_plan)
   int num_gaussians = 1;      // particle_filter.cpp:7
   std::vector<float> gmm_means, gmm_covs;
+  DevBuf<uint64_t> kld_ws;    // tdr_filter_kld_count: the key table for n_max and the two output words, allocated by the first call
   DevBuf<float> ml_dev;  // fields + mlState of the max-likelihood particle of the last update (tdr_k_save_ml_state)
   bool have_ml = false;
   // meanLikelihood + computeMeanCov of the CURRENT particle set, as last read back: publishPoseEst asks for both in a row

@@ -773,6 +773,48 @@ class HipKernels:
         covs[:, 2, 2] = 1
         return k, means, covs
 
+    # ---- KLD-sampling count (csrc/tdr_kld.hip; include/tdr.h, "KLD-sampling count") ---------------------------------
+    def kld_keys(self, st, n, params):
+        """The pose-bin keys of particles [0, n) of st (7, cap): NumPy uint64 (n,), KLD_NO_KEY where there is none."""
+        out = self.empty((max(1, n),), torch.int64)
+        check(self.lib.tdr_k_kld_keys(_ptr(st), st.shape[1], n, C.byref(params), _ptr(out), self.stream()))
+        return out[:n].cpu().numpy().view(np.uint64).copy()
+
+    def kld_workspace(self, n):
+        """A key table for up to n particles (int64 device tensor; kld_count clears it)."""
+        return self.empty((int(self.lib.tdr_kld_workspace_bytes(n)) // 8,), torch.int64)
+
+    def kld_count(self, st, n, params, workspace=None):
+        """(k, skipped): the distinct keys among particles [0, n) and the particles without a key.  One read-back."""
+        if workspace is None:
+            workspace = self.kld_workspace(n)
+        if workspace.numel() * 8 < int(self.lib.tdr_kld_workspace_bytes(n)):
+            raise ValueError("kld_count: the workspace is smaller than tdr_kld_workspace_bytes(n)")
+        out = self.empty((2,), torch.int64)
+        check(self.lib.tdr_k_kld_count(_ptr(st), st.shape[1], n, C.byref(params), _ptr(workspace), _ptr(out), self.stream()))
+        k, skipped = out.cpu().tolist()
+        return int(k), int(skipped)
+
+    def kld_count_jobs(self, sts, ns, params):
+        """kld_count of several state tensors in one launch (the job table of tdr_k_kld_count_jobs): [(k, skipped)]."""
+        slots = [int(self.lib.tdr_kld_workspace_bytes(n)) // 8 if n >= 1 else 0 for n in ns]
+        tables = self.empty((max(1, sum(slots)),), torch.int64)
+        tables.fill_(-1)
+        out = self.zeros((len(sts), 2), torch.int64)
+        jobs, at = [], 0
+        for i, (st, n) in enumerate(zip(sts, ns)):
+            jobs.append(_lib.KldJobC(st.data_ptr(), st.shape[1], n, tables.data_ptr() + 8 * at, slots[i],
+                                     out.data_ptr() + 16 * i))
+            at += slots[i]
+        jobs_d = self.to_device(np.frombuffer(bytes((_lib.KldJobC * len(jobs))(*jobs)), np.uint8).copy())
+        check(self.lib.tdr_k_kld_count_jobs(_ptr(jobs_d), len(jobs), C.byref(params), self.stream()))
+        return [(int(a), int(b)) for a, b in out.cpu().tolist()]
+
+    def kld_target(self, k, params, last_count, max_count):
+        """The next update's count from k occupied bins (tdr_kld_bound_host, tdr_kld_target_host)."""
+        n_kld = self.lib.tdr_kld_bound_host(int(k), C.c_double(params.epsilon), C.c_double(params.z))
+        return int(self.lib.tdr_kld_target_host(n_kld, int(last_count), int(params.n_min), int(max_count)))
+
     # ---- the particle picture (csrc/tdr_viz.hip) ---------------------------------------------------------------
     def viz_planes(self, H, W):
         """The four bit planes of an H x W picture, as one int32 tensor (cleared by viz_draw)."""

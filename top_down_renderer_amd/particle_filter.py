@@ -28,7 +28,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from ._lib import FilterParamsC
+from ._lib import FilterParamsC, KldParamsC
 from .synth import STATE_DTYPE
 
 
@@ -66,6 +66,31 @@ class FilterParams:
         for i in range(16):
             c.class_weights[i] = float(cw[i]) if i < ncls else 0.0
         return c
+
+
+@dataclass
+class KldParams:
+    """tdr_kld_params (include/tdr.h, "KLD-sampling count"): the pose bins and Fox's bound."""
+    bin_xy_px: float = 4.0      # bin edge in map pixels
+    theta_bins: int = 36        # heading bins over one turn, 1..511
+    scale_bits: int = 3         # 2^scale_bits scale bins per octave, 0..6
+    epsilon: float = 0.05       # AMCL's kld_err
+    z: float = 2.326            # AMCL's kld_z
+    n_min: int = 100
+
+    def to_c(self):
+        return KldParamsC(float(self.bin_xy_px), int(self.theta_bins), int(self.scale_bits), float(self.epsilon),
+                          float(self.z), int(self.n_min))
+
+
+def kld_params_c(params):
+    """A KldParams or KldParamsC as a checked KldParamsC: what the handle layer refuses raises here."""
+    p = params if isinstance(params, KldParamsC) else params.to_c()
+    if not (math.isfinite(p.bin_xy_px) and p.bin_xy_px > 0 and 1 <= p.theta_bins <= 511 and 0 <= p.scale_bits <= 6
+            and math.isfinite(p.epsilon) and p.epsilon > 0 and math.isfinite(p.z) and p.z >= 0 and p.n_min >= 1):
+        raise ValueError("KLD parameters: bin_xy_px finite and > 0, theta_bins 1..511, scale_bits 0..6, epsilon finite "
+                         "and > 0, z finite and >= 0, n_min >= 1")
+    return p
 
 
 class _Comm:
@@ -143,6 +168,8 @@ class ParticleFilter:
         self.num_gaussians_ = 1   # :7
         self.gmm_means_ = np.zeros((0, 3), np.float32)
         self.gmm_covs_ = np.zeros((0, 3, 3), np.float32)
+        self._kld_ws = None       # the key table of kldCount, allocated by its first call
+        self.last_kld_ = (0, 0)
         self._alloc()
         if map.haveMap():
             self.fp_c = params.to_c(map.numClasses())
@@ -469,6 +496,25 @@ class ParticleFilter:
     def getGMM(self):
         """(means [k][3] = x, y, theta; covs [k][3][3]) of the last computeGMM (:238-243)."""
         return self.gmm_means_.copy(), self.gmm_covs_.copy()
+
+    # ---- KLD-sampling count (include/tdr.h, "KLD-sampling count"): the other rule for the same number ---------------
+    def kldCount(self, params):
+        """The particle count the pose bins of the current set ask for (tdr_kld_target_host over the device count of
+        csrc/tdr_kld.hip): the n_target of the next update.  params: KldParams.  Reads the states only; (k, skipped)
+        of the call stay in last_kld_.  A sharded filter raises: the distinct count of a sharded set is a global quantity
+        and combining the ranks' key sets is not built."""
+        if self.comm.active:
+            raise ValueError("kldCount is not available on a sharded filter (the distinct count is a global quantity)")
+        params = kld_params_c(params)
+        n = self.num_particles_
+        if n >= 1:
+            if self._kld_ws is None:
+                self._kld_ws = self.k.kld_workspace(self.max_num_particles_)
+            k, skipped = self.k.kld_count(self.st, n, params, self._kld_ws)
+        else:
+            k, skipped = 0, 0
+        self.last_kld_ = (k, skipped)
+        return self.k.kld_target(k, params, n, self.max_num_particles_)
 
     def computeMeanCov(self):
         if self.num_particles_ < 1:

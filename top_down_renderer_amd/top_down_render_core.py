@@ -15,7 +15,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .particle_filter import ParticleFilter
+from .particle_filter import KldParams, ParticleFilter, kld_params_c
 from .scan_renderer import ScanRendererPolar
 
 
@@ -31,6 +31,17 @@ class CoreConfig:                       # the node's parameters that reach the s
     # the adaptive particle count (src/particle_filter.cpp:151-157): after the publishPoseEst of every gmm_every-th step
     # the mixture is refitted on the device and every update resamples to the count of :151-157.  0: never
     gmm_every: int = 0
+    # KLD-sampling count (include/tdr.h, "KLD-sampling count"): after the publishPoseEst of every kld_every-th step the pose
+    # bins of the particle set are counted on the device and the following updates resample to the count they ask for.
+    # 0: never.  Together with gmm_every > 0 it is refused: two rules for one number
+    kld_every: int = 0
+    kld: KldParams = field(default_factory=KldParams)
+
+    def check(self):
+        if self.kld_every > 0 and self.gmm_every > 0:
+            raise ValueError("CoreConfig: kld_every and gmm_every are two rules for one particle count; set one of them")
+        if self.kld_every > 0:
+            kld_params_c(self.kld)
 
 
 @dataclass
@@ -51,13 +62,16 @@ class TopDownRenderCore:
         self.last_res_ = np.float32(0)
         self.is_converged_ = False                                         # top_down_render.h:83
         self.map_ = self.filter_ = self.renderer_ = None
-        self.steps_ = 0                                                    # counted only with cfg.gmm_every > 0
+        self.steps_ = 0                                                    # counted only with cfg.gmm_every / kld_every > 0
+        self.kld_target_ = None                                            # the count the last kldCount asked for
 
     def initialize(self, map, filter_params, flatten_lut, **filter_kw):
         """:81, 115-117 with a TopDownMapPolar the host built."""
         c = self.cfg
+        c.check()
         self.map_ = map
         self.steps_ = 0
+        self.kld_target_ = None
         self.ang_res = np.float32(2 * np.pi / c.theta_bins)
         map.samplePtsPolar((c.theta_bins, c.range_bins), self.ang_res)                                     # :115
         self.filter_ = ParticleFilter(c.particle_count, map, filter_params, seed=c.seed, kernels=self.k, **filter_kw)   # :116
@@ -75,6 +89,8 @@ class TopDownRenderCore:
         e = self.publishPoseEst()                                                                           # :560
         if self.countStepAndGmmDue():
             self.filter_.computeGMM(device=True)
+        if self.countStepAndKldDue():
+            self.kld_target_ = self.filter_.kldCount(self.cfg.kld)
         return e
 
     def countStepAndGmmDue(self):
@@ -85,10 +101,20 @@ class TopDownRenderCore:
         self.steps_ += 1
         return self.steps_ % g == 0
 
+    def countStepAndKldDue(self):
+        """The same for the KLD-sampling count (cfg.kld_every; never both, CoreConfig.check)."""
+        g = self.cfg.kld_every
+        if g <= 0:
+            return False
+        self.steps_ += 1
+        return self.steps_ % g == 0
+
     def updateFilter(self, top_down, top_down_geo, res, trans, yaw):
         self.filter_.propagate(trans, yaw)                                                                  # :423
         if self.cfg.gmm_every > 0:   # :151-157 from the clusters of the last fit
             self.filter_.update(top_down, top_down_geo, res, n_target=self.filter_.adaptiveCount())
+        elif self.cfg.kld_every > 0 and self.kld_target_ is not None:   # the count the bins of the last kldCount asked for
+            self.filter_.update(top_down, top_down_geo, res, n_target=self.kld_target_)
         else:
             self.filter_.update(top_down, top_down_geo, res)                                                # :425
 
