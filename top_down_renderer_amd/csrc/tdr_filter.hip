@@ -169,6 +169,9 @@ extern "C" int tdr_init_particles_host(void* rng, const float* class_maps, int n
 // taken in double with a fixed order, the reference's two serial float chains (`sum`, `bottom_stddev`) exactly, so the
 // result depends only on (raw_w, last_dist, n) — identical on every rank that holds the all-gathered weights.  Up to
 // 32768 particles everything is one launch of one workgroup (uw_small_kernel, tdr_prefix.hip); above, the passes below.
+// Behind the chains every step is one correctly rounded float operation, so the weights are one of the few arrays the
+// rounding of the two double sums allows: tests/test_uw_exact.py holds every path to them bit for bit (the statement
+// itself: tests/uw_exact_ref.py).
 __device__ long long block_sum_ll(long long v, long long* sh) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

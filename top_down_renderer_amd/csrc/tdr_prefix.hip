@@ -30,7 +30,9 @@
 //
 // Order of the file: the one-wave serial kernel; the one-workgroup tie-list kernel; the parity-pair chain step and
 // what it is made of (written once, used by every kernel behind it); the multi-workgroup kernels; the one-workgroup
-// kernels; dispatch.  tests/test_gpu_parity.py compares every path with the CPU chains bit for bit.
+// kernels; dispatch.  tests/test_gpu_parity.py compares every path with the CPU chains bit for bit; what the update does
+// behind its chains (fill or fallback, the two normalisations, the blend, the first maximum) is held to an exact
+// statement, on both one-workgroup kernels and the multi-workgroup passes, in tests/test_uw_exact.py.
 //
 // ---- one wave, serially --------------------------------------------------------------------------------------------------
 // prefix_serial_kernel: lane 0 performs the additions in index order (weights staged through LDS).  Simple, ~10 ns per
@@ -1733,8 +1735,11 @@ __device__ __forceinline__ void uw_small_body(const float* __restrict__ raw, con
   if constexpr (WAVES) {
     // :130-135 without a pass of its own: the filled weights sum to the valid ones plus `fill` for every NaN (all ones in
     // the fallback); the fill itself happens where the weight is read next.  The last travel distances are requested
-    // sixteen per thread at a time, ahead of the divisions.
-    fs1 = (float)(fallback ? (double)n : valid_sum + (double)(n - num_valid) * (double)fill);
+    // sixteen per thread at a time, ahead of the divisions.  With no NaN there is nothing to fill and `fill` stays out of
+    // the sum: it is inf or NaN when `bottom_stddev` or `sum` overflows, and 0 * inf would turn every weight into NaN
+    // where the reference, which sums the weights as filled, keeps them finite (tests/test_uw_exact.py).
+    const double fill_sum = num_valid == n ? 0.0 : (double)(n - num_valid) * (double)fill;
+    fs1 = (float)(fallback ? (double)n : valid_sum + fill_sum);
     UW_STAMP(7);
     for (int i0 = tid; i0 < n; i0 += 16 * nt) {
       float ld[16];
