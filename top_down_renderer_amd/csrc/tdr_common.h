@@ -38,9 +38,6 @@
 #ifndef TDR_SCORE_U
 #define TDR_SCORE_U 4          // samples whose loads are kept in flight together in the scoring loop
 #endif
-#ifndef TDR_INIT_SCAN_LDS
-#define TDR_INIT_SCAN_LDS 1   // init search: candidates' scan records via LDS broadcast (1) or the scalar cache (0)
-#endif
 #ifndef TDR_XCD_SWIZZLE
 #define TDR_XCD_SWIZZLE 0
 #endif

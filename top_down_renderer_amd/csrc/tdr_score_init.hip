@@ -13,16 +13,15 @@
 // The 40-rotation initialisation search of state_particle.cpp:195-206 in ONE pass over the window: the candidate
 // rotations are the same for every particle, so for rotation t the scan row paired with window row i — (i + s_t) mod nb
 // — is the same for all lanes, and a map record gathered once is multiplied against all candidates' scan records
-// (the reference also gathers once and scores 40 times).  One workgroup = one batch of 64 particles; its 4 waves
-// split the candidates (INIT_TW each), gather the same records (the repeats hit L1), read the candidates' scan records
-// through the scalar cache (they are wave-uniform) and keep INIT_TW x rf accumulators per lane.  Sums run in float over the whole window, which is only used to pick the best rotation:
-// the weight itself is then produced by the regular scoring pass at that rotation.
-#ifndef INIT_TW
+// (the reference also gathers once and scores 40 times).  One workgroup = one batch of 64 particles; its INIT_WAVES waves
+// split the candidates (INIT_TW each), gather the same records (the repeats hit L1) and keep INIT_TW x rf accumulators
+// per lane.  A ring of the packed scan is staged in LDS twice over (rows r and r + nb hold scan row r), so the record of
+// candidate t at window row i sits at row i + s_t without a wrap, the same address in every lane: an LDS broadcast.
+// Sums run in float over the whole window, which is only used to pick the best rotation: the weight itself is then
+// produced by the regular scoring pass at that rotation.
 #define INIT_TW 6          // candidate rotations per wave
-#endif
-#ifndef INIT_WAVES
 #define INIT_WAVES 8       // waves per workgroup, all on the same 64 particles (A/B on MI355X, 250k particles:
-#endif                     // 4x11 401 ms, 6x8 630 ms, 8x6 285 ms, 12x4 422 ms, 16x3 447 ms; scalar-cache scan reads 773 ms)
+                           // 4x11 401 ms, 6x8 630 ms, 8x6 285 ms, 12x4 422 ms, 16x3 447 ms; scalar-cache scan reads 773 ms)
 #define INIT_MAXROT (INIT_WAVES * INIT_TW)
 struct InitArgs {
   const float* rec;
@@ -70,37 +69,119 @@ __device__ __forceinline__ float init_weight_pow2(const tdr_filter_params& fp, i
   return ldexpf(1.f, min(max(1 - e, -100), 100));
 }
 
+// ---- what the kernel bodies share ---------------------------------------------------------------------------------------
+typedef _Float16 tdr_h8 __attribute__((ext_vector_type(8)));
+typedef __fp16 tdr_h2 __attribute__((ext_vector_type(2)));   // what v_cvt_pkrtz_f16_f32 returns
+typedef float tdr_f4 __attribute__((ext_vector_type(4)));
+typedef float tdr_f2 __attribute__((ext_vector_type(2)));
+#define INITM_TILES 3   // matrix-core kernels: 48 candidate rows >= the 40 (41) rotations of the search
+static_assert(INITM_TILES * 16 >= INIT_MAXROT || INIT_MAXROT == 48, "rotation tiles");
+
+// The particle of a lane: slot `slot` of the filter's order (a slot past the end reads particle 0 and wants nothing).
+struct InitLane {
+  int64_t p;
+  float scale, cx, cy;
+  bool valid, want;   // want: no heading yet and not gated — the search writes this particle's result
+};
+__device__ __forceinline__ InitLane init_lane(const InitArgs& a, int64_t slot) {
+  InitLane l;
+  l.valid = slot < a.n;
+  l.p = a.order ? (int64_t)a.order[l.valid ? slot : 0] : (l.valid ? slot : 0);
+  l.scale = a.st[TDR_ST_SCALE * a.cap + l.p];
+  l.cx = a.st[TDR_ST_DX * a.cap + l.p] * l.scale + a.st[TDR_ST_INIT_X * a.cap + l.p];
+  l.cy = a.st[TDR_ST_DY * a.cap + l.p] * l.scale + a.st[TDR_ST_INIT_Y * a.cap + l.p];
+  l.want = l.valid && a.st[TDR_ST_HAVE_INIT * a.cap + l.p] == 0.f && !particle_gated(a.gate, l.cx, l.cy, l.scale);
+  return l;
+}
+// Byte offset of the dense record (RB bytes) that sample-table entry t reads for a particle of scale `scale` centred at
+// (off0, off1) cells: top_down_map_polar.cpp:28-31, the one place where the search and the scoring kernels must agree on
+// the cell.  The grid is guarded by one ring of cells; a sample outside it reads the record at offset 0.
+template <bool USCALE, int RB>
+__device__ __forceinline__ unsigned init_cell_offset(const InitArgs& a, float scale, float off0, float off1, float2 t) {
+  float p0, p1;
+  if constexpr (USCALE) { p0 = t.x; p1 = t.y; }
+  else { p0 = (t.x * scale) * a.res; p1 = (t.y * scale) * a.res; }   // :28
+  auto cell = [](float v, float vmax) { return round_half_away_clamped(__builtin_amdgcn_fmed3f(v, -1.f, vmax)); };   // :31
+  const int ri = cell(p0 + off0, (float)a.rows), ci = cell(p1 + off1, (float)a.cols);
+  const bool inb = (unsigned)ri < (unsigned)a.rows && (unsigned)ci < (unsigned)a.cols;
+  return inb ? (unsigned)(__mul24(ri, (a.cols + 2) * RB) + (ci * RB + (a.cols + 3) * RB)) : 0u;
+}
+// res_theta / res_flag of particle p: candidate bt won, or none did (bt < 0)
+__device__ __forceinline__ void init_write_choice(const InitArgs& a, int64_t p, int bt) {
+  a.res_theta[p] = bt >= 0 ? a.theta[bt] : 0.f;  // state_particle.cpp:205 (best_theta stays 0 if nothing won)
+  a.res_flag[p] = bt < 0 ? 2.f : 1.f;
+}
+// The end of a matrix-core body.  Lane (col, q) holds rows 4q..4q+3 of every tile for particle `col` — candidate
+// 16 T + 4 q + r has the cost accC[T][r] / div(T, r) — and `known` is its share of the particle's known samples (the four
+// lanes of a particle share the samples).  Picks the first strict minimum in rotation order, writes it and counts the
+// workgroup in slot `stat` of the pass counters.
+template <class Div>
+__device__ __forceinline__ void init_pick_write(const InitArgs& a, const InitLane& l, int q, int nrot, float known,
+                                                const tdr_f4 (&accC)[INITM_TILES], Div div, int stat) {
+  known += __shfl_xor(known, 16, 64);
+  known += __shfl_xor(known, 32, 64);
+  const bool unknown = (known / (float)a.P) < 0.5;   // state_particle.cpp:117-120
+  float best = 3.402823466e+38f;
+  int bm = -1;
+#pragma unroll
+  for (int T = 0; T < INITM_TILES; T++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int m = 16 * T + 4 * q + r;
+      float cost = accC[T][r] / div(T, r);              // :154
+      if (unknown) cost = __builtin_nanf("");
+      if (m < nrot && cost < best) { best = cost; bm = m; }   // :200-203 (NaN never wins)
+    }
+#pragma unroll
+  for (int o = 16; o <= 32; o <<= 1) {   // first minimum in rotation order over the particle's four lanes
+    const float oc = __shfl_xor(best, o, 64);
+    const int om = __shfl_xor(bm, o, 64);
+    const bool take = om >= 0 && (bm < 0 || oc < best || (oc == best && om < bm));
+    if (take) { best = oc; bm = om; }
+  }
+  if (q == 0 && l.want) init_write_choice(a, l.p, bm);
+  init_count_pass(a, stat);
+}
+// the filter's "scan count does not fit f16" word: behind its rotation count (the layout: make_init_args)
+__device__ __forceinline__ int* init_inexact_word(const InitArgs& a) { return const_cast<int*>(a.nrot) + 1; }
+// x, y as f16 pairs hi + lo (see init_weight_pow2)
+__device__ __forceinline__ void init_split_pair(float x, float y, tdr_h2& hi, tdr_h2& lo) {
+  hi = __builtin_amdgcn_cvt_pkrtz(x, y);
+  lo = __builtin_amdgcn_cvt_pkrtz(x - (float)hi[0], y - (float)hi[1]);
+}
+// 8 scan counts as one LDS row of 8 x f16; `big` is raised by a count f16 does not hold exactly (above 2048)
+__device__ __forceinline__ uint4 init_pack_scan8(const float* f, bool& big) {
+  union { tdr_h2 h[4]; uint4 u; } pk;
+#pragma unroll
+  for (int k = 0; k < 8; k++) big |= f[k] > 2048.f;
+#pragma unroll
+  for (int c = 0; c < 4; c++) pk.h[c] = __builtin_amdgcn_cvt_pkrtz(f[2 * c], f[2 * c + 1]);
+  return pk.u;
+}
+
 // Each search kernel is a body (bx: the workgroup's index among its filter's batches of 64 particles) behind two wrappers:
 // the standalone kernel passes its kernel arguments and blockIdx.x, the batched one (tdr_batch_step) finds
 // its filter from blockIdx.x and reads that filter's InitArgs from a device table — the index is wave-uniform and the
 // entry is read before anything is stored, so its fields arrive through scalar loads as kernel arguments do.
+// Records of 16 floats: one workgroup per CU fits, two waves per SIMD, whatever the schedule — the kernels say so, and the
+// scheduler spends the registers on LDS reads in flight (15 per row; aiming at a third wave it kept one or two: +9 % time).
+// Only NV4 == 4 is constrained: 1 to 8 waves is what the other forms have anyway.
+#define INIT_WAVES_PER_SIMD(NV4) __attribute__((amdgpu_waves_per_eu(NV4 == 4 ? 2 : 1, NV4 == 4 ? 2 : 8)))
 template <int NV4, bool KSLOT, bool USCALE>
 __device__ __forceinline__ void score_init_body(const InitArgs& a, int bx) {
   constexpr int RF = 4 * NV4;
-  constexpr int U = 1;
-#if TDR_INIT_SCAN_LDS
   extern __shared__ float4 ring[];  // [NV4 planes][2*nb rows]
   const int nb2 = 2 * a.nb;
-#endif
   __shared__ float x_cost[INIT_WAVES][64];
   __shared__ int x_rot[INIT_WAVES][64];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform, and the compiler knows it
   if (a.only_if && *a.only_if == 0) return;               // (uniform) the MFMA pass already produced the results
-  const int64_t slot = (int64_t)bx * 64 + lane;   // all four waves work on the same 64 particles
-  const bool valid = slot < a.n;
-  const int64_t p = a.order ? (int64_t)a.order[valid ? slot : 0] : (valid ? slot : 0);
-  const float scale = a.st[TDR_ST_SCALE * a.cap + p];
-  const float cx = a.st[TDR_ST_DX * a.cap + p] * scale + a.st[TDR_ST_INIT_X * a.cap + p];
-  const float cy = a.st[TDR_ST_DY * a.cap + p] * scale + a.st[TDR_ST_INIT_Y * a.cap + p];
-  const bool want = valid && a.st[TDR_ST_HAVE_INIT * a.cap + p] == 0.f && !particle_gated(a.gate, cx, cy, scale);
+  const InitLane l = init_lane(a, (int64_t)bx * 64 + lane);   // all waves work on the same 64 particles
   // every wave of the workgroup looks at the same 64 particles, so this per-wave vote is the same in all of them
   // (and, unlike __syncthreads_or, involves no LDS atomic that would stop the compiler from using scalar loads)
-  if (__ballot(want) == 0) return;  // nothing to initialise in this batch
-  const float off0 = cy / a.resolution, off1 = cx / a.resolution;
-  const int rowstride = (a.cols + 2) * (RF * 4);
-  const int kbase = (a.cols + 3) * (RF * 4);
-  const float rmaxf = (float)a.rows, cmaxf = (float)a.cols;
+  if (__ballot(l.want) == 0) return;  // nothing to initialise in this batch
+  const float off0 = l.cy / a.resolution, off1 = l.cx / a.resolution;
   const char* __restrict__ recb = reinterpret_cast<const char*>(a.rec);
   const float2* __restrict__ tab2 = reinterpret_cast<const float2*>(USCALE ? a.utab : a.tab);
   const float4* __restrict__ scan4 = reinterpret_cast<const float4*>(a.scan_pk);
@@ -111,30 +192,16 @@ __device__ __forceinline__ void score_init_body(const InitArgs& a, int bx) {
     const int t = wave * INIT_TW + r;
     sh[r] = t < nrot ? a.shift[t] : 0;
   }
-  float acc[INIT_TW][RF];
+  tdr_f2 acc[INIT_TW][RF / 2];   // slot pairs: the packed FMA's operands by construction
 #pragma unroll
   for (int r = 0; r < INIT_TW; r++)
 #pragma unroll
-    for (int k = 0; k < RF; k++) acc[r][k] = 0.f;
+    for (int k = 0; k < RF / 2; k++) acc[r][k] = (tdr_f2){0.f, 0.f};
   float known = 0.f;
-
-  auto cell_offset = [&](float2 t) -> unsigned {
-    float p0, p1;
-    if constexpr (USCALE) { p0 = t.x; p1 = t.y; }
-    else { p0 = (t.x * scale) * a.res; p1 = (t.y * scale) * a.res; }
-    p0 = p0 + off0;
-    p1 = p1 + off1;
-    p0 = __builtin_amdgcn_fmed3f(p0, -1.f, rmaxf);
-    p1 = __builtin_amdgcn_fmed3f(p1, -1.f, cmaxf);
-    const int ri = round_half_away_clamped(p0), ci = round_half_away_clamped(p1);
-    const bool inb = (unsigned)ri < (unsigned)a.rows && (unsigned)ci < (unsigned)a.cols;
-    return inb ? (unsigned)(__mul24(ri, rowstride) + (ci * (RF * 4) + kbase)) : 0u;
-  };
 
   for (int j = 0; j < a.nr; j++) {
     const float2* trow = tab2 + (int64_t)j * a.nb;
     const float4* srow = scan4 + (int64_t)j * a.nb * NV4;  // ring j of the packed scan
-#if TDR_INIT_SCAN_LDS
     __syncthreads();
     for (int t = threadIdx.x; t < a.nb * NV4; t += 64 * INIT_WAVES) {
       const float4 v = srow[t];
@@ -143,65 +210,25 @@ __device__ __forceinline__ void score_init_body(const InitArgs& a, int bx) {
       ring[pl * nb2 + row + a.nb] = v;
     }
     __syncthreads();
-#endif
-    int i = 0;
-    for (; i + U <= a.nb; i += U) {
-      unsigned boff[U];
+    for (int i = 0; i < a.nb; i++) {
+      const unsigned boff = init_cell_offset<USCALE, RF * 4>(a, l.scale, off0, off1, trow[i]);
+      float4 m[NV4];
 #pragma unroll
-      for (int u = 0; u < U; u++) boff[u] = cell_offset(trow[i + u]);
-      float4 m[U][NV4];
+      for (int v = 0; v < NV4; v++) m[v] = *reinterpret_cast<const float4*>(recb + boff + 16 * v);
+      if (!KSLOT) known += m[NV4 - 1].w;
 #pragma unroll
-      for (int u = 0; u < U; u++)
+      for (int r = 0; r < INIT_TW; r++) {
 #pragma unroll
-        for (int v = 0; v < NV4; v++) m[u][v] = *reinterpret_cast<const float4*>(recb + boff[u] + 16 * v);
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        if (!KSLOT) known += m[u][NV4 - 1].w;
-#pragma unroll
-        for (int r = 0; r < INIT_TW; r++) {
-#pragma unroll
-          for (int v = 0; v < NV4; v++) {
-#if TDR_INIT_SCAN_LDS
-            const float4 sv = ring[v * nb2 + sh[r] + i + u];  // same address in every lane: LDS broadcast
-#else
-            int row = sh[r] + i + u;                    // wave-uniform: the record comes through the scalar cache
-            row -= row >= a.nb ? a.nb : 0;
-            const float4 sv = srow[row * NV4 + v];
-#endif
-            acc[r][4 * v + 0] = __builtin_fmaf(sv.x, m[u][v].x, acc[r][4 * v + 0]);
-            acc[r][4 * v + 1] = __builtin_fmaf(sv.y, m[u][v].y, acc[r][4 * v + 1]);
-            acc[r][4 * v + 2] = __builtin_fmaf(sv.z, m[u][v].z, acc[r][4 * v + 2]);
-            acc[r][4 * v + 3] = __builtin_fmaf(sv.w, m[u][v].w, acc[r][4 * v + 3]);
-          }
+        for (int v = 0; v < NV4; v++) {
+          const float4 sv = ring[v * nb2 + sh[r] + i];  // same address in every lane: LDS broadcast
+          acc[r][2 * v] = __builtin_elementwise_fma((tdr_f2){sv.x, sv.y}, (tdr_f2){m[v].x, m[v].y}, acc[r][2 * v]);
+          acc[r][2 * v + 1] = __builtin_elementwise_fma((tdr_f2){sv.z, sv.w}, (tdr_f2){m[v].z, m[v].w}, acc[r][2 * v + 1]);
         }
       }
     }
-    for (; i < a.nb; i++) {
-      const unsigned bo = cell_offset(trow[i]);
-      float4 m[NV4];
-#pragma unroll
-      for (int v = 0; v < NV4; v++) m[v] = *reinterpret_cast<const float4*>(recb + bo + 16 * v);
-      if (!KSLOT) known += m[NV4 - 1].w;
-#pragma unroll
-      for (int r = 0; r < INIT_TW; r++)
-#pragma unroll
-        for (int v = 0; v < NV4; v++) {
-#if TDR_INIT_SCAN_LDS
-          const float4 sv = ring[v * nb2 + sh[r] + i];
-#else
-          int row = sh[r] + i;
-          row -= row >= a.nb ? a.nb : 0;
-          const float4 sv = srow[row * NV4 + v];
-#endif
-          acc[r][4 * v + 0] = __builtin_fmaf(sv.x, m[v].x, acc[r][4 * v + 0]);
-          acc[r][4 * v + 1] = __builtin_fmaf(sv.y, m[v].y, acc[r][4 * v + 1]);
-          acc[r][4 * v + 2] = __builtin_fmaf(sv.z, m[v].z, acc[r][4 * v + 2]);
-          acc[r][4 * v + 3] = __builtin_fmaf(sv.w, m[v].w, acc[r][4 * v + 3]);
-        }
-    }
   }
   // cost of each candidate (state_particle.cpp:117-120,136-139,154), best of this wave's candidates in order
-  const float kn = KSLOT ? acc[0][RF - 2] : known;
+  const float kn = KSLOT ? acc[0][RF / 2 - 1][0] : known;
   const bool unknown = (kn / (float)a.P) < 0.5;
   float cw[RF];
 #pragma unroll
@@ -214,26 +241,26 @@ __device__ __forceinline__ void score_init_body(const InitArgs& a, int bx) {
     float cost = 0.f;
 #pragma unroll
     for (int k = 0; k < RF - 1; k++)   // constant indices only: a dynamic index would push the arguments to scratch
-      if (k < a.ncls) cost = (float)((double)cost + (double)acc[r][k] * 0.01 * (double)cw[k]);
-    cost = cost / acc[r][RF - 1];
+      if (k < a.ncls) cost = (float)((double)cost + (double)acc[r][k / 2][k % 2] * 0.01 * (double)cw[k]);
+    cost = cost / acc[r][RF / 2 - 1][1];
     if (unknown) cost = __builtin_nanf("");
     if (t < nrot && cost < best) { best = cost; best_t = t; }  // :200-203 (NaN never wins)
   }
   x_cost[wave][lane] = best;
   x_rot[wave][lane] = best_t;
   __syncthreads();
-  if (wave == 0 && want) {
+  if (wave == 0 && l.want) {
     float b = 3.402823466e+38f;
     int bt = -1;
     for (int wv = 0; wv < INIT_WAVES; wv++)   // waves hold the candidates in loop order: strict '<' keeps the first minimum
       if (x_cost[wv][lane] < b) { b = x_cost[wv][lane]; bt = x_rot[wv][lane]; }
-    a.res_theta[p] = bt >= 0 ? a.theta[bt] : 0.f;  // :205 (best_theta stays 0 if nothing won)
-    a.res_flag[p] = bt < 0 ? 2.f : 1.f;
+    init_write_choice(a, l.p, bt);
   }
   init_count_pass(a, 15);
 }
 template <int NV4, bool KSLOT, bool USCALE>
-__global__ __launch_bounds__(64 * INIT_WAVES) void score_init_kernel(InitArgs a) {
+__global__ __launch_bounds__(64 * INIT_WAVES) INIT_WAVES_PER_SIMD(NV4)
+void score_init_kernel(InitArgs a) {
   score_init_body<NV4, KSLOT, USCALE>(a, (int)blockIdx.x);
 }
 // Batched wrappers: entry e of `args` owns the blocks [blk[e], blk[e + 1]) counted from blk[0] (the launch covers a run of
@@ -248,8 +275,8 @@ __global__ __launch_bounds__(64 * INIT_WAVES) void score_init_kernel(InitArgs a)
   if ((a.utab != nullptr) != USCALE) return; /* (uniform) */                                 \
   const int bx = b - blk[e]
 template <int NV4, bool KSLOT, bool USCALE>
-__global__ __launch_bounds__(64 * INIT_WAVES) void score_init_batch_kernel(const InitArgs* __restrict__ args,
-                                                                           const int32_t* __restrict__ blk, int k) {
+__global__ __launch_bounds__(64 * INIT_WAVES) INIT_WAVES_PER_SIMD(NV4)
+void score_init_batch_kernel(const InitArgs* __restrict__ args, const int32_t* __restrict__ blk, int k) {
   INIT_BATCH_FIND();
   score_init_body<NV4, KSLOT, USCALE>(a, bx);
 }
@@ -261,39 +288,25 @@ __global__ __launch_bounds__(64 * INIT_WAVES) void score_init_batch_kernel(const
 // record slots) per instruction.  Lane l holds, as its B fragment, the 8 slots of the record of particle l&15 at
 // sample 4t + (l>>4) — exactly the record it gathered — and as its A fragment the packed scan record at row
 // (4t + (l>>4) + s_m), m = l&15 (+16, +32 for the second and third tile of candidates), one ds_read_b128 each.
-//   * scan counts are integers: exact in f16 up to 2048 (a larger count raises *inexact and score_init_kernel redoes
-//     the search on the vector units);
+//   * scan counts are integers: exact in f16 up to 2048 (a larger count raises the filter's "does not fit f16" word,
+//     a.nrot[1], and score_init_kernel redoes the search on the vector units);
 //   * distances (times 0.01 w_c, in f32, times the one power of two of init_weight_pow2) are split hi + lo into two f16
 //     (relative error <= 2^-20 from 2^-4 up, see there), two MFMAs;
 //   * the normalisation  sum scanΣ * known  is a third MFMA with only slot 7 of B set; the known count is a plain add.
 // Products are exact and accumulate in f32 like the vector version.  Only the choice of the rotation comes out of
 // here; the weight itself is computed by the regular scoring pass at that rotation.
-typedef _Float16 tdr_h8 __attribute__((ext_vector_type(8)));
-typedef __fp16 tdr_h2 __attribute__((ext_vector_type(2)));   // what v_cvt_pkrtz_f16_f32 returns
-typedef float tdr_f4 __attribute__((ext_vector_type(4)));
-#define INITM_TILES 3   // 48 candidate rows >= the 40 (41) rotations of the search
-static_assert(INITM_TILES * 16 >= INIT_MAXROT || INIT_MAXROT == 48, "rotation tiles");
-
+//
 // UNITW: all class weights are equal — a common factor does not move the minimum, so the distances go in unweighted.
 // SEVEN: 7 classes — slot 6 of the record is a seventh distance (no spare slot), slot 7 still `known` / the scan's sum.
 template <bool USCALE, bool UNITW, bool SEVEN>
-__device__ __forceinline__ void score_init_mfma_body(const InitArgs& a, int bx, int* __restrict__ inexact) {
+__device__ __forceinline__ void score_init_mfma_body(const InitArgs& a, int bx) {
   constexpr int RF = 8;
   extern __shared__ uint4 ring16[];   // [2*nb] packed scan records as 8 x f16 (row r and r+nb hold scan row r) + 1 zero row
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = lane & 15, q = lane >> 4;
-  const int64_t slot = (int64_t)bx * 64 + wave * 16 + col;
-  const bool valid = slot < a.n;
-  const int64_t p = a.order ? (int64_t)a.order[valid ? slot : 0] : (valid ? slot : 0);
-  const float scale = a.st[TDR_ST_SCALE * a.cap + p];
-  const float cx = a.st[TDR_ST_DX * a.cap + p] * scale + a.st[TDR_ST_INIT_X * a.cap + p];
-  const float cy = a.st[TDR_ST_DY * a.cap + p] * scale + a.st[TDR_ST_INIT_Y * a.cap + p];
-  const bool want = valid && a.st[TDR_ST_HAVE_INIT * a.cap + p] == 0.f && !particle_gated(a.gate, cx, cy, scale);
-  if (!__syncthreads_or(want)) return;   // nothing to initialise in this batch of 64 particles
-  const float off0 = cy / a.resolution, off1 = cx / a.resolution;
-  const int rowstride = (a.cols + 2) * (RF * 4);
-  const int kbase = (a.cols + 3) * (RF * 4);
-  const float rmaxf = (float)a.rows, cmaxf = (float)a.cols;
+  const InitLane l = init_lane(a, (int64_t)bx * 64 + wave * 16 + col);
+  if (!__syncthreads_or(l.want)) return;   // nothing to initialise in this batch of 64 particles
+  const float off0 = l.cy / a.resolution, off1 = l.cx / a.resolution;
   const char* __restrict__ recb = reinterpret_cast<const char*>(a.rec);
   const float2* __restrict__ tab2 = reinterpret_cast<const float2*>(USCALE ? a.utab : a.tab);
   const float4* __restrict__ scan4 = reinterpret_cast<const float4*>(a.scan_pk);
@@ -328,31 +341,17 @@ __device__ __forceinline__ void score_init_mfma_body(const InitArgs& a, int bx, 
     bool big = false;
     for (int t = threadIdx.x; t < a.nb; t += 256) {
       const float4 v0 = srow[2 * t], v1 = srow[2 * t + 1];
-      big |= v0.x > 2048.f || v0.y > 2048.f || v0.z > 2048.f || v0.w > 2048.f || v1.x > 2048.f || v1.y > 2048.f ||
-             v1.z > 2048.f || v1.w > 2048.f;
-      union { tdr_h2 h[4]; uint4 u; } pk;
-      pk.h[0] = __builtin_amdgcn_cvt_pkrtz(v0.x, v0.y);
-      pk.h[1] = __builtin_amdgcn_cvt_pkrtz(v0.z, v0.w);
-      pk.h[2] = __builtin_amdgcn_cvt_pkrtz(v1.x, v1.y);
-      pk.h[3] = __builtin_amdgcn_cvt_pkrtz(v1.z, v1.w);
-      ring16[t] = pk.u;
-      ring16[t + a.nb] = pk.u;
+      const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+      const uint4 pk = init_pack_scan8(f, big);
+      ring16[t] = pk;
+      ring16[t + a.nb] = pk;
     }
-    if (big) atomicOr(inexact, 1);
+    if (big) atomicOr(init_inexact_word(a), 1);
     __syncthreads();
     // software pipeline: the record of step t+1 (and the table entry of step t+2) are requested before the matrix
     // work of step t, so every wave keeps two gathers in flight
     auto tab_at = [&](int t) -> float2 { return trow[min(4 * t + q, a.nb - 1)]; };
-    auto rec_addr = [&](float2 tv) -> const char* {
-      float p0, p1;
-      if constexpr (USCALE) { p0 = tv.x; p1 = tv.y; }
-      else { p0 = (tv.x * scale) * a.res; p1 = (tv.y * scale) * a.res; }   // top_down_map_polar.cpp:28
-      p0 = __builtin_amdgcn_fmed3f(p0 + off0, -1.f, rmaxf);
-      p1 = __builtin_amdgcn_fmed3f(p1 + off1, -1.f, cmaxf);
-      const int ri = round_half_away_clamped(p0), ci = round_half_away_clamped(p1);   // :31
-      const bool inb = (unsigned)ri < (unsigned)a.rows && (unsigned)ci < (unsigned)a.cols;
-      return recb + (inb ? (unsigned)(__mul24(ri, rowstride) + (ci * (RF * 4) + kbase)) : 0u);
-    };
+    auto rec_addr = [&](float2 tv) { return recb + init_cell_offset<USCALE, RF * 4>(a, l.scale, off0, off1, tv); };
     float2 tv_next = tab_at(1);
     float4 n0, n1;
     {
@@ -380,17 +379,9 @@ __device__ __forceinline__ void score_init_mfma_body(const InitArgs& a, int bx, 
       }
       union { tdr_h2 h[4]; tdr_h8 v8; } bh, bl, bn;
 #pragma unroll
-      for (int c = 0; c < 3; c++) {
-        const tdr_h2 hi = __builtin_amdgcn_cvt_pkrtz(v[2 * c], v[2 * c + 1]);
-        bh.h[c] = hi;
-        bl.h[c] = __builtin_amdgcn_cvt_pkrtz(v[2 * c] - (float)hi[0], v[2 * c + 1] - (float)hi[1]);
-      }
+      for (int c = 0; c < (SEVEN ? 4 : 3); c++) init_split_pair(v[2 * c], v[2 * c + 1], bh.h[c], bl.h[c]);   // v[7] == 0
       const tdr_h2 zero2 = __builtin_amdgcn_cvt_pkrtz(0.f, 0.f);
-      if constexpr (SEVEN) {
-        const tdr_h2 hi = __builtin_amdgcn_cvt_pkrtz(v[6], 0.f);
-        bh.h[3] = hi;
-        bl.h[3] = __builtin_amdgcn_cvt_pkrtz(v[6] - (float)hi[0], 0.f);
-      } else {
+      if constexpr (!SEVEN) {
         bh.h[3] = zero2;
         bl.h[3] = zero2;
       }
@@ -408,44 +399,17 @@ __device__ __forceinline__ void score_init_mfma_body(const InitArgs& a, int bx, 
       for (int T = 0; T < INITM_TILES; T++) accC[T] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[T].v8, bl.v8, accC[T], 0, 0, 0);
     }
   }
-  // this lane holds rows 4q..4q+3 of every tile for particle `col`; the four lanes of a particle share the samples
-  known += __shfl_xor(known, 16, 64);
-  known += __shfl_xor(known, 32, 64);
-  const bool unknown = (known / (float)a.P) < 0.5;   // state_particle.cpp:117-120
-  float best = 3.402823466e+38f;
-  int bm = -1;
-#pragma unroll
-  for (int T = 0; T < INITM_TILES; T++)
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int m = 16 * T + 4 * q + r;
-      float cost = accC[T][r] / accN[T][r];             // :154
-      if (unknown) cost = __builtin_nanf("");
-      if (m < nrot && cost < best) { best = cost; bm = m; }   // :200-203 (NaN never wins)
-    }
-#pragma unroll
-  for (int o = 16; o <= 32; o <<= 1) {   // first minimum in rotation order over the particle's four lanes
-    const float oc = __shfl_xor(best, o, 64);
-    const int om = __shfl_xor(bm, o, 64);
-    const bool take = om >= 0 && (bm < 0 || oc < best || (oc == best && om < bm));
-    if (take) { best = oc; bm = om; }
-  }
-  if (q == 0 && want) {
-    a.res_theta[p] = bm >= 0 ? a.theta[bm] : 0.f;  // :205 (best_theta stays 0 if nothing won)
-    a.res_flag[p] = bm < 0 ? 2.f : 1.f;
-  }
-  init_count_pass(a, 13);
+  init_pick_write(a, l, q, nrot, known, accC, [&](int T, int r) { return accN[T][r]; }, 13);
 }
 template <bool USCALE, bool UNITW, bool SEVEN>
-__global__ __launch_bounds__(256) void score_init_mfma_kernel(InitArgs a, int* __restrict__ inexact) {
-  score_init_mfma_body<USCALE, UNITW, SEVEN>(a, (int)blockIdx.x, inexact);
+__global__ __launch_bounds__(256) void score_init_mfma_kernel(InitArgs a) {
+  score_init_mfma_body<USCALE, UNITW, SEVEN>(a, (int)blockIdx.x);
 }
-// batched: a filter's "scan count does not fit f16" word is its own (behind its rotation count, as standalone)
 template <bool USCALE, bool UNITW, bool SEVEN>
 __global__ __launch_bounds__(256) void score_init_mfma_batch_kernel(const InitArgs* __restrict__ args,
                                                                     const int32_t* __restrict__ blk, int k) {
   INIT_BATCH_FIND();
-  score_init_mfma_body<USCALE, UNITW, SEVEN>(a, bx, const_cast<int*>(a.nrot) + 1);
+  score_init_mfma_body<USCALE, UNITW, SEVEN>(a, bx);
 }
 
 // The same for records of 12 and 16 floats (8-15 classes): a sample's record is two groups of 8 slots, each group its own
@@ -453,25 +417,16 @@ __global__ __launch_bounds__(256) void score_init_mfma_batch_kernel(const InitAr
 // 2 x (hi + lo) products per tile instead of one, plus the normalisation product on the group that holds slot RF - 1.
 // Class weights are always folded in (no unit-weight form); slots past the class count meet a zero weight.
 template <int NV4, bool USCALE>
-__device__ __forceinline__ void score_init_mfma_wide_body(const InitArgs& a, int bx, int* __restrict__ inexact) {
+__device__ __forceinline__ void score_init_mfma_wide_body(const InitArgs& a, int bx) {
   constexpr int RF = 4 * NV4, NH = 2;
   static_assert(NV4 == 3 || NV4 == 4, "records of 12 or 16 floats");
   constexpr int HN = (RF - 1) / 8, KN = (RF - 1) % 8;   // group and slot of `known` / the scan's sum
   extern __shared__ uint4 ring16[];   // [2*nb + 1 rows][NH groups]: 8 x f16 each; rows r and r+nb hold scan row r, the last is zero
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = lane & 15, q = lane >> 4;
-  const int64_t slot = (int64_t)bx * 64 + wave * 16 + col;
-  const bool valid = slot < a.n;
-  const int64_t p = a.order ? (int64_t)a.order[valid ? slot : 0] : (valid ? slot : 0);
-  const float scale = a.st[TDR_ST_SCALE * a.cap + p];
-  const float cx = a.st[TDR_ST_DX * a.cap + p] * scale + a.st[TDR_ST_INIT_X * a.cap + p];
-  const float cy = a.st[TDR_ST_DY * a.cap + p] * scale + a.st[TDR_ST_INIT_Y * a.cap + p];
-  const bool want = valid && a.st[TDR_ST_HAVE_INIT * a.cap + p] == 0.f && !particle_gated(a.gate, cx, cy, scale);
-  if (!__syncthreads_or(want)) return;   // nothing to initialise in this batch of 64 particles
-  const float off0 = cy / a.resolution, off1 = cx / a.resolution;
-  const int rowstride = (a.cols + 2) * (RF * 4);
-  const int kbase = (a.cols + 3) * (RF * 4);
-  const float rmaxf = (float)a.rows, cmaxf = (float)a.cols;
+  const InitLane l = init_lane(a, (int64_t)bx * 64 + wave * 16 + col);
+  if (!__syncthreads_or(l.want)) return;   // nothing to initialise in this batch of 64 particles
+  const float off0 = l.cy / a.resolution, off1 = l.cx / a.resolution;
   const char* __restrict__ recb = reinterpret_cast<const char*>(a.rec);
   const float2* __restrict__ tab2 = reinterpret_cast<const float2*>(USCALE ? a.utab : a.tab);
   const float4* __restrict__ scan4 = reinterpret_cast<const float4*>(a.scan_pk);
@@ -512,29 +467,16 @@ __device__ __forceinline__ void score_init_mfma_wide_body(const InitArgs& a, int
         f[4 * v] = x.x; f[4 * v + 1] = x.y; f[4 * v + 2] = x.z; f[4 * v + 3] = x.w;
       }
 #pragma unroll
-      for (int k = 0; k < 16; k++) big |= f[k] > 2048.f;
-#pragma unroll
       for (int h = 0; h < NH; h++) {
-        union { tdr_h2 h2[4]; uint4 u; } pk;
-#pragma unroll
-        for (int c = 0; c < 4; c++) pk.h2[c] = __builtin_amdgcn_cvt_pkrtz(f[8 * h + 2 * c], f[8 * h + 2 * c + 1]);
-        ring16[t * NH + h] = pk.u;
-        ring16[(t + a.nb) * NH + h] = pk.u;
+        const uint4 pk = init_pack_scan8(f + 8 * h, big);
+        ring16[t * NH + h] = pk;
+        ring16[(t + a.nb) * NH + h] = pk;
       }
     }
-    if (big) atomicOr(inexact, 1);
+    if (big) atomicOr(init_inexact_word(a), 1);
     __syncthreads();
     auto tab_at = [&](int t) -> float2 { return trow[min(4 * t + q, a.nb - 1)]; };
-    auto rec_addr = [&](float2 tv) -> const char* {
-      float p0, p1;
-      if constexpr (USCALE) { p0 = tv.x; p1 = tv.y; }
-      else { p0 = (tv.x * scale) * a.res; p1 = (tv.y * scale) * a.res; }   // top_down_map_polar.cpp:28
-      p0 = __builtin_amdgcn_fmed3f(p0 + off0, -1.f, rmaxf);
-      p1 = __builtin_amdgcn_fmed3f(p1 + off1, -1.f, cmaxf);
-      const int ri = round_half_away_clamped(p0), ci = round_half_away_clamped(p1);   // :31
-      const bool inb = (unsigned)ri < (unsigned)a.rows && (unsigned)ci < (unsigned)a.cols;
-      return recb + (inb ? (unsigned)(__mul24(ri, rowstride) + (ci * (RF * 4) + kbase)) : 0u);
-    };
+    auto rec_addr = [&](float2 tv) { return recb + init_cell_offset<USCALE, RF * 4>(a, l.scale, off0, off1, tv); };
     float2 tv_next = tab_at(1);
     float4 nx[NV4];
     {
@@ -569,11 +511,7 @@ __device__ __forceinline__ void score_init_mfma_wide_body(const InitArgs& a, int
 #pragma unroll
       for (int h = 0; h < NH; h++)
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
-          const tdr_h2 hi = __builtin_amdgcn_cvt_pkrtz(v[8 * h + 2 * c], v[8 * h + 2 * c + 1]);
-          bh[h].h[c] = hi;
-          bl[h].h[c] = __builtin_amdgcn_cvt_pkrtz(v[8 * h + 2 * c] - (float)hi[0], v[8 * h + 2 * c + 1] - (float)hi[1]);
-        }
+        for (int c = 0; c < 4; c++) init_split_pair(v[8 * h + 2 * c], v[8 * h + 2 * c + 1], bh[h].h[c], bl[h].h[c]);
 #pragma unroll
       for (int c = 0; c < 4; c++) bn.h[c] = zero2;
       bn.h[KN / 2] = (KN & 1) ? __builtin_amdgcn_cvt_pkrtz(0.f, kn) : __builtin_amdgcn_cvt_pkrtz(kn, 0.f);
@@ -596,42 +534,17 @@ __device__ __forceinline__ void score_init_mfma_wide_body(const InitArgs& a, int
       }
     }
   }
-  known += __shfl_xor(known, 16, 64);
-  known += __shfl_xor(known, 32, 64);
-  const bool unknown = (known / (float)a.P) < 0.5;   // state_particle.cpp:117-120
-  float best = 3.402823466e+38f;
-  int bm = -1;
-#pragma unroll
-  for (int T = 0; T < INITM_TILES; T++)
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int m = 16 * T + 4 * q + r;
-      float cost = accC[T][r] / accN[T][r];             // :154
-      if (unknown) cost = __builtin_nanf("");
-      if (m < nrot && cost < best) { best = cost; bm = m; }   // :200-203 (NaN never wins)
-    }
-#pragma unroll
-  for (int o = 16; o <= 32; o <<= 1) {   // first minimum in rotation order over the particle's four lanes
-    const float oc = __shfl_xor(best, o, 64);
-    const int om = __shfl_xor(bm, o, 64);
-    const bool take = om >= 0 && (bm < 0 || oc < best || (oc == best && om < bm));
-    if (take) { best = oc; bm = om; }
-  }
-  if (q == 0 && want) {
-    a.res_theta[p] = bm >= 0 ? a.theta[bm] : 0.f;  // :205 (best_theta stays 0 if nothing won)
-    a.res_flag[p] = bm < 0 ? 2.f : 1.f;
-  }
-  init_count_pass(a, 14);
+  init_pick_write(a, l, q, nrot, known, accC, [&](int T, int r) { return accN[T][r]; }, 14);
 }
 template <int NV4, bool USCALE>
-__global__ __launch_bounds__(256) void score_init_mfma_wide_kernel(InitArgs a, int* __restrict__ inexact) {
-  score_init_mfma_wide_body<NV4, USCALE>(a, (int)blockIdx.x, inexact);
+__global__ __launch_bounds__(256) void score_init_mfma_wide_kernel(InitArgs a) {
+  score_init_mfma_wide_body<NV4, USCALE>(a, (int)blockIdx.x);
 }
 template <int NV4, bool USCALE>
 __global__ __launch_bounds__(256) void score_init_mfma_wide_batch_kernel(const InitArgs* __restrict__ args,
                                                                          const int32_t* __restrict__ blk, int k) {
   INIT_BATCH_FIND();
-  score_init_mfma_wide_body<NV4, USCALE>(a, bx, const_cast<int*>(a.nrot) + 1);
+  score_init_mfma_wide_body<NV4, USCALE>(a, bx);
 }
 
 // ---- the matrix-core search on pre-split half records ------------------------------------------------------------------
@@ -672,11 +585,9 @@ __global__ __launch_bounds__(256) void half_records_kernel(const float4* __restr
   }
   union { tdr_h2 h[4]; uint4 u; } H, L;
 #pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const tdr_h2 hi = __builtin_amdgcn_cvt_pkrtz(v[2 * k], v[2 * k + 1]);   // v[7] == 0
-    H.h[k] = hi;
-    L.h[k] = __builtin_amdgcn_cvt_pkrtz(v[2 * k] - (float)hi[0], k == 3 ? 1.f - known : v[2 * k + 1] - (float)hi[1]);
-  }
+  for (int k = 0; k < 3; k++) init_split_pair(v[2 * k], v[2 * k + 1], H.h[k], L.h[k]);
+  H.h[3] = __builtin_amdgcn_cvt_pkrtz(v[6], 0.f);   // slot 7: nothing in H, `unknown` in L
+  L.h[3] = __builtin_amdgcn_cvt_pkrtz(v[6] - (float)H.h[3][0], 1.f - known);
   out[2 * c] = H.u;
   out[2 * c + 1] = L.u;
   if (c == 0) {   // the record behind the grid: nothing at all (what lanes without a sample read)
@@ -694,8 +605,8 @@ __global__ __launch_bounds__(256) void half_records_kernel(const float4* __restr
 // unrolled AHEAD + 1 times so that the buffers rotate by name (no register copies); the step count is padded to a multiple
 // of that, the padding steps read the zero guard record.
 template <bool USCALE, int AHEAD>
-__device__ __forceinline__ void score_init_half_body(const InitArgs& a, int bx, const uint4* __restrict__ rec16,
-                                                     int* __restrict__ inexact, int img, int rfs) {
+__device__ __forceinline__ void score_init_half_body(const InitArgs& a, int bx, const uint4* __restrict__ rec16, int img,
+                                                     int rfs) {
   constexpr int R = AHEAD + 1;
   // LDS: [4 rings][img] scan records {c0..c5, c6|0, sum c} as 8 x f16, row r and r + nb of an image hold scan row r; the
   // img - 2 nb >= R rows behind them stay zero (padding steps; the exact count is chosen on the host so that the four
@@ -705,16 +616,10 @@ __device__ __forceinline__ void score_init_half_body(const InitArgs& a, int bx, 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = lane & 15, q = lane >> 4;
   // (an XCD-contiguous order of the workgroups and 1, 2 or 3 record loads in flight all run within 1 %: A/B on MI355X)
-  const int64_t slot = (int64_t)bx * 64 + wave * 16 + col;
-  const bool valid = slot < a.n;
-  const int64_t p = a.order ? (int64_t)a.order[valid ? slot : 0] : (valid ? slot : 0);
-  const float scale = a.st[TDR_ST_SCALE * a.cap + p];
-  const float cx = a.st[TDR_ST_DX * a.cap + p] * scale + a.st[TDR_ST_INIT_X * a.cap + p];
-  const float cy = a.st[TDR_ST_DY * a.cap + p] * scale + a.st[TDR_ST_INIT_Y * a.cap + p];
-  const bool want = valid && a.st[TDR_ST_HAVE_INIT * a.cap + p] == 0.f && !particle_gated(a.gate, cx, cy, scale);
-  if (!__syncthreads_or(want)) return;   // nothing to initialise in this batch of 64 particles
+  const InitLane l = init_lane(a, (int64_t)bx * 64 + wave * 16 + col);
+  if (!__syncthreads_or(l.want)) return;   // nothing to initialise in this batch of 64 particles
   typedef float tdr_v2f __attribute__((ext_vector_type(2)));
-  const tdr_v2f offv = {cy / a.resolution, cx / a.resolution};
+  const tdr_v2f offv = {l.cy / a.resolution, l.cx / a.resolution};
   const int rowstride = (a.cols + 2) * 32;
   const int kbase = (a.cols + 3) * 32;
   const float rmaxf = (float)a.rows, cmaxf = (float)a.cols;
@@ -745,9 +650,10 @@ __device__ __forceinline__ void score_init_half_body(const InitArgs& a, int bx, 
   const unsigned none_off = (unsigned)(a.rows + 2) * (unsigned)(a.cols + 2) * 32u;   // the all-zero record behind the grid
 
   // byte offset of the half record of table entry tv; a lane without a sample (ring >= nr, padding step) gets `none`
+  // (not init_cell_offset: packed arithmetic, a floor conversion and no in-bounds select — tuned as it stands)
   auto rec_off = [&](float2 tv, bool in) -> unsigned {
     tdr_v2f pv = {tv.x, tv.y};
-    if constexpr (!USCALE) pv = (pv * scale) * a.res;   // top_down_map_polar.cpp:28
+    if constexpr (!USCALE) pv = (pv * l.scale) * a.res;   // top_down_map_polar.cpp:28
     pv = pv + offv;                                      // :29-30
     tdr_v2f qv = {__builtin_amdgcn_fmed3f(pv.x, -1.f, rmaxf), __builtin_amdgcn_fmed3f(pv.y, -1.f, cmaxf)};
     qv = qv + 0.49999997f;                               // :31, see round_half_away_clamped
@@ -763,8 +669,7 @@ __device__ __forceinline__ void score_init_half_body(const InitArgs& a, int bx, 
     bool big = false;
     for (int t = threadIdx.x; t < 4 * nb; t += 256) {
       const int kb = t / nb, r = t - kb * nb;
-      union { tdr_h2 h[4]; uint4 u; } pc;
-      pc.u = make_uint4(0u, 0u, 0u, 0u);
+      uint4 pc = make_uint4(0u, 0u, 0u, 0u);
       if (j0 + kb < a.nr) {
         // packed scan record of rfs floats: the class counts first, the sum of the counts last
         const float* srow = a.scan_pk + ((int64_t)(j0 + kb) * nb + r) * rfs;
@@ -772,20 +677,17 @@ __device__ __forceinline__ void score_init_half_body(const InitArgs& a, int bx, 
 #pragma unroll
         for (int k = 0; k < 7; k++) cnt[k] = k < a.ncls ? srow[k] : 0.f;
         cnt[7] = srow[rfs - 1];
-#pragma unroll
-        for (int k = 0; k < 8; k++) big |= cnt[k] > 2048.f;
-#pragma unroll
-        for (int k = 0; k < 4; k++) pc.h[k] = __builtin_amdgcn_cvt_pkrtz(cnt[2 * k], cnt[2 * k + 1]);
+        pc = init_pack_scan8(cnt, big);
         ssum += cnt[7];
       }
-      ringh[kb * img + r] = pc.u;
-      ringh[kb * img + r + nb] = pc.u;
+      ringh[kb * img + r] = pc;
+      ringh[kb * img + r + nb] = pc;
     }
     for (int t = threadIdx.x; t < 4 * ntab; t += 256) {
       const int kb = t / ntab, r = t - kb * ntab;
       ltab[t] = tab2[(int64_t)min(j0 + kb, a.nr - 1) * nb + min(r, nb - 1)];
     }
-    if (big) atomicOr(inexact, 1);
+    if (big) atomicOr(init_inexact_word(a), 1);
     __syncthreads();
     const bool ring_ok = j0 + q < a.nr;
     // Software pipeline: the two record loads of step t + AHEAD are issued before the matrix work of step t (the table
@@ -846,38 +748,13 @@ __device__ __forceinline__ void score_init_half_body(const InitArgs& a, int bx, 
   for (int t = 0; t < 256; t++) stotal += red[t];   // same order in every lane
   // samples this lane went through: nb directions on each of its rings j = q, q + 4, ...
   const int my_rings = (a.nr - q + 3) / 4;
-  float known = (float)(my_rings * nb - (int)(ucount / 60u));
-  known += __shfl_xor(known, 16, 64);
-  known += __shfl_xor(known, 32, 64);
-  const bool unknown = (known / (float)a.P) < 0.5;   // state_particle.cpp:117-120
-  float best = 3.402823466e+38f;
-  int bm = -1;
-#pragma unroll
-  for (int T = 0; T < INITM_TILES; T++)
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int m = 16 * T + 4 * q + r;
-      float cost = accC[T][r] / (stotal - accN[T][r]);  // :154
-      if (unknown) cost = __builtin_nanf("");
-      if (m < nrot && cost < best) { best = cost; bm = m; }   // :200-203 (NaN never wins)
-    }
-#pragma unroll
-  for (int o = 16; o <= 32; o <<= 1) {   // first minimum in rotation order over the particle's four lanes
-    const float oc = __shfl_xor(best, o, 64);
-    const int om = __shfl_xor(bm, o, 64);
-    const bool take = om >= 0 && (bm < 0 || oc < best || (oc == best && om < bm));
-    if (take) { best = oc; bm = om; }
-  }
-  if (q == 0 && want) {
-    a.res_theta[p] = bm >= 0 ? a.theta[bm] : 0.f;  // :205 (best_theta stays 0 if nothing won)
-    a.res_flag[p] = bm < 0 ? 2.f : 1.f;
-  }
-  init_count_pass(a, 12);
+  const float known = (float)(my_rings * nb - (int)(ucount / 60u));
+  init_pick_write(a, l, q, nrot, known, accC, [&](int T, int r) { return stotal - accN[T][r]; }, 12);
 }
 template <bool USCALE, int AHEAD>
-__global__ __launch_bounds__(256) void score_init_half_kernel(InitArgs a, const uint4* __restrict__ rec16,
-                                                              int* __restrict__ inexact, int img, int rfs) {
-  score_init_half_body<USCALE, AHEAD>(a, (int)blockIdx.x, rec16, inexact, img, rfs);
+__global__ __launch_bounds__(256) void score_init_half_kernel(InitArgs a, const uint4* __restrict__ rec16, int img,
+                                                              int rfs) {
+  score_init_half_body<USCALE, AHEAD>(a, (int)blockIdx.x, rec16, img, rfs);
 }
 // batched: the half records, the image stride and the scan record size belong to the map and the scan shape — the same
 // for every filter of the batch — and stay kernel arguments
@@ -886,7 +763,7 @@ __global__ __launch_bounds__(256) void score_init_half_batch_kernel(const InitAr
                                                                     const int32_t* __restrict__ blk, int k,
                                                                     const uint4* __restrict__ rec16, int img, int rfs) {
   INIT_BATCH_FIND();
-  score_init_half_body<USCALE, AHEAD>(a, bx, rec16, const_cast<int*>(a.nrot) + 1, img, rfs);
+  score_init_half_body<USCALE, AHEAD>(a, bx, rec16, img, rfs);
 }
 
 // candidate rotations of the search, generated exactly like the reference's loop (state_particle.cpp:197: float t,
@@ -1017,14 +894,21 @@ static int init_half_image_rows(int nb, int R) {
 }
 
 // ---- what the standalone and the batched search share on the host ------------------------------------------------------
+// dynamic LDS of each pass, in bytes (the layouts: at the bodies' `extern __shared__` arrays)
+static size_t init_lds_vector(int nb, int rf) { return (size_t)2 * nb * rf * 4; }
+static size_t init_lds_split(int nb) { return ((size_t)2 * nb + 1) * 16; }
+static size_t init_lds_wide(int nb) { return ((size_t)2 * nb + 1) * 2 * 16; }
+static size_t init_lds_half(int img, int nb, int R) { return (size_t)4 * img * 16 + (size_t)4 * (nb + 2 * R) * 8; }
 // The matrix-core pass of a search — ONE choice for both paths: the passes pick differently where candidates tie to
 // rounding (tdr.h, tdr_config_init_mfma), so a batched filter must take the pass its standalone call takes.
 int tdr_score_init_pass(const tdr_map_desc* map, int nb, int64_t n_total) {
   const int rf = map->rec_floats;
   const bool ks = tdr_has_kslot(map->ncls, rf);
   if (!tdr_cfg().init_mfma) return TDR_INIT_PASS_VECTOR;
+  // (with the most loads in flight, AHEAD = 3, and c = 15 init_half_image_rows gives at most 2 nb + 19 rows; the check keeps
+  // the 2 nb + 20 it has always asked for)
   if ((rf == 4 || rf == 8) && map->ncls <= 7 && map->rec16 && tdr_map_rec16_bytes(map->ncls, map->rows, map->cols) != 0 &&
-      n_total >= tdr_cfg().rec16_min && (size_t)4 * (2 * nb + 20) * 16 + (size_t)4 * (nb + 8) * 8 <= 64 * 1024)
+      n_total >= tdr_cfg().rec16_min && init_lds_half(2 * nb + 20, nb, 4) <= 64 * 1024)
     return TDR_INIT_PASS_HALF;
   if (rf == 8 && (ks || map->ncls == 7)) return TDR_INIT_PASS_SPLIT;
   if (rf == 12 || rf == 16) return TDR_INIT_PASS_WIDE;
@@ -1065,82 +949,99 @@ static int launch_half_records(const tdr_map_desc* map, const tdr_filter_params*
   LAUNCH_CHECK("half_records");
   return TDR_OK;
 }
-struct HalfShape { int ahead, img; size_t lds; };
-static HalfShape init_half_shape(int nb) {
-  HalfShape h;
-  h.ahead = tdr_cfg().init_ahead;
-  const int R = h.ahead + 1;
-  h.img = init_half_image_rows(nb, R);
-  h.lds = (size_t)4 * h.img * 16 + (size_t)4 * (nb + 2 * R) * 8;
-  return h;
+// Where a search kernel runs: on one filter — the standalone kernels, `one` going by value — or on a run of a batch's table,
+// entries args[0, count) with the cumulative block counts blk (the batched kernels, see INIT_BATCH_FIND).  The two kernels
+// of an instantiation take the same arguments behind these.
+struct InitTarget {
+  const InitArgs* one;
+  const InitArgs* args;
+  const int32_t* blk;
+  int count;
+  dim3 grid;
+};
+template <class KOne, class KBatch, class... Tail>
+static void init_launch(const InitTarget& t, KOne one, KBatch batched, unsigned threads, size_t lds, hipStream_t s,
+                        Tail... tail) {
+  if (t.one) hipLaunchKernelGGL(one, t.grid, dim3(threads), lds, s, *t.one, tail...);
+  else hipLaunchKernelGGL(batched, t.grid, dim3(threads), lds, s, t.args, t.blk, t.count, tail...);
+}
+// The matrix-core pass `pass` (tdr_score_init_pass) on the filters of `t` whose scale mode is `us`; unitw: all their class
+// weights are equal (init_unit_weights; the wide pass has no such form).  The vector kernel behind it then runs only for
+// a filter whose scan held a count that did not fit f16.
+static int launch_init_mfma(int pass, const tdr_map_desc* map, int nb, bool us, bool unitw, const InitTarget& t,
+                            hipStream_t s) {
+  const int rf = map->rec_floats;
+  if (pass == TDR_INIT_PASS_HALF) {
+    // pre-split half records (weights folded in), which launch_half_records built into the map owner's scratch
+    const int ahead = tdr_cfg().init_ahead, img = init_half_image_rows(nb, ahead + 1);
+    const size_t lds = init_lds_half(img, nb, ahead + 1);
+    const uint4* r16 = reinterpret_cast<const uint4*>(map->rec16);
+    with_flags([&](auto US) {
+      constexpr bool U = decltype(US)::value;
+      if (ahead == 1) init_launch(t, score_init_half_kernel<U, 1>, score_init_half_batch_kernel<U, 1>, 256, lds, s, r16, img, rf);
+      else if (ahead == 2) init_launch(t, score_init_half_kernel<U, 2>, score_init_half_batch_kernel<U, 2>, 256, lds, s, r16, img, rf);
+      else init_launch(t, score_init_half_kernel<U, 3>, score_init_half_batch_kernel<U, 3>, 256, lds, s, r16, img, rf);
+      return TDR_OK;
+    }, us);
+    LAUNCH_CHECK(t.one ? "score_init_half" : "batch_score_init_half");
+  } else if (pass == TDR_INIT_PASS_SPLIT) {
+    // the f32 records split per sample (small filters, maps without the scratch)
+    with_flags([&](auto US, auto UW, auto SV) {
+      constexpr bool U = decltype(US)::value, W = decltype(UW)::value, V = decltype(SV)::value;
+      init_launch(t, score_init_mfma_kernel<U, W, V>, score_init_mfma_batch_kernel<U, W, V>, 256, init_lds_split(nb), s);
+      return TDR_OK;
+    }, us, unitw, !tdr_has_kslot(map->ncls, rf));
+    LAUNCH_CHECK(t.one ? "score_init_mfma" : "batch_score_init_mfma");
+  } else {
+    // 8-15 classes: two groups of 8 slots per sample
+    with_flags([&](auto US, auto R16) {
+      constexpr bool U = decltype(US)::value;
+      constexpr int NV4 = decltype(R16)::value ? 4 : 3;
+      init_launch(t, score_init_mfma_wide_kernel<NV4, U>, score_init_mfma_wide_batch_kernel<NV4, U>, 256, init_lds_wide(nb), s);
+      return TDR_OK;
+    }, us, rf == 16);
+    LAUNCH_CHECK(t.one ? "score_init_mfma_wide" : "batch_score_init_mfma_wide");
+  }
+  return TDR_OK;
+}
+// the vector kernel, likewise
+static int launch_init_vector(const tdr_map_desc* map, int nb, bool us, const InitTarget& t, hipStream_t s) {
+  const int rf = map->rec_floats;
+  if (int rc = with_nv4(rf, t.one ? "score" : "batch_init", [&](auto N) {
+        return with_flags([&](auto KS, auto US) {
+          constexpr int NV4 = decltype(N)::value;
+          constexpr bool K = decltype(KS)::value, U = decltype(US)::value;
+          init_launch(t, score_init_kernel<NV4, K, U>, score_init_batch_kernel<NV4, K, U>, 64 * INIT_WAVES,
+                      init_lds_vector(nb, rf), s);
+          return TDR_OK;
+        }, tdr_has_kslot(map->ncls, rf), us);
+      }))
+    return rc;
+  LAUNCH_CHECK(t.one ? "score_init" : "batch_score_init");
+  return TDR_OK;
 }
 
 int tdr_score_init_search(const tdr_map_desc* map, const float* tab, const float* utab, const float* scan_pk, int nb,
                           int nr, float res, const tdr_filter_params* fp, float* st, int64_t cap, int64_t n,
                           int64_t n_total, const int32_t* order, float* res_flag, int64_t npad, hipStream_t s) {
-  const int rf = map->rec_floats;
   InitArgs ia = make_init_args(map, tab, utab, scan_pk, nb, nr, res, fp, st, cap, n, order, res_flag, npad);
-  float* res_theta = ia.res_theta;
-  int* d_nrot = const_cast<int*>(ia.nrot);
-  hipLaunchKernelGGL(init_rot_kernel, dim3(1), dim3(64), 0, s, nb, const_cast<int*>(ia.shift), const_cast<float*>(ia.theta), d_nrot);
+  hipLaunchKernelGGL(init_rot_kernel, dim3(1), dim3(64), 0, s, nb, const_cast<int*>(ia.shift), const_cast<float*>(ia.theta),
+                     const_cast<int*>(ia.nrot));
   LAUNCH_CHECK("init_rot");
   HIP_TRY(hipMemsetAsync(res_flag, 0, sizeof(float) * (size_t)n, s));
-  dim3 grid((unsigned)cdiv(n, 64)), block(64 * INIT_WAVES);
-  const size_t lds = TDR_INIT_SCAN_LDS ? (size_t)2 * nb * rf * 4 : 0;
-  const bool ks = tdr_has_kslot(map->ncls, rf), us = utab != nullptr;
-  const bool unitw = init_unit_weights(fp, map->ncls);
-  int* d_inexact = d_nrot + 1;
+  const InitTarget t{&ia, nullptr, nullptr, 0, dim3((unsigned)cdiv(n, 64))};
+  const bool us = utab != nullptr, unitw = init_unit_weights(fp, map->ncls);
   const int pass = tdr_score_init_pass(map, nb, n_total);
-  if (pass == TDR_INIT_PASS_HALF) {
-    // matrix-core pass on pre-split half records (weights folded in), built into the map owner's scratch first; the
-    // vector kernel below then runs only if a scan count did not fit f16
+  if (pass == TDR_INIT_PASS_HALF)
     if (int rc = launch_half_records(map, fp, unitw, s)) return rc;
-    const HalfShape hs = init_half_shape(nb);
-    const int ahead = hs.ahead, img = hs.img;
-    const size_t ldsh = hs.lds;
-    const uint4* r16c = reinterpret_cast<const uint4*>(map->rec16);
-    with_flags([&](auto US) {
-      constexpr bool U = decltype(US)::value;
-      auto launch = [&](auto kfn) { hipLaunchKernelGGL(kfn, grid, dim3(256), ldsh, s, ia, r16c, d_inexact, img, rf); };
-      if (ahead == 1) launch(score_init_half_kernel<U, 1>);
-      else if (ahead == 2) launch(score_init_half_kernel<U, 2>);
-      else launch(score_init_half_kernel<U, 3>);
-      return TDR_OK;
-    }, us);
-    LAUNCH_CHECK("score_init_half");
-    ia.only_if = d_inexact;
-  } else if (pass == TDR_INIT_PASS_SPLIT) {
-    // matrix-core pass splitting the f32 records per sample (small filters, maps without the scratch); the vector
-    // kernel below then runs only if a scan count did not fit f16
-    const size_t lds16 = ((size_t)2 * nb + 1) * 16;
-    with_flags([&](auto US, auto UW, auto SV) {
-      hipLaunchKernelGGL((score_init_mfma_kernel<decltype(US)::value, decltype(UW)::value, decltype(SV)::value>), grid,
-                         dim3(256), lds16, s, ia, d_inexact);
-      return TDR_OK;
-    }, us, unitw, !ks);
-    LAUNCH_CHECK("score_init_mfma");
-    ia.only_if = d_inexact;
-  } else if (pass == TDR_INIT_PASS_WIDE) {
-    // 8-15 classes: two groups of 8 slots per sample (score_init_mfma_wide_kernel)
-    const size_t lds16 = ((size_t)2 * nb + 1) * 2 * 16;
-    with_flags([&](auto US, auto R16) {
-      hipLaunchKernelGGL((score_init_mfma_wide_kernel<decltype(R16)::value ? 4 : 3, decltype(US)::value>), grid, dim3(256),
-                         lds16, s, ia, d_inexact);
-      return TDR_OK;
-    }, us, rf == 16);
-    LAUNCH_CHECK("score_init_mfma_wide");
-    ia.only_if = d_inexact;
+  if (pass != TDR_INIT_PASS_VECTOR) {
+    if (int rc = launch_init_mfma(pass, map, nb, us, unitw, t, s)) return rc;
+    // the vector kernel: only what the matrix-core pass could not take.  (t.one points at ia and is read at the launch, so
+    // the launch below sees this; a target that held the arguments by value would have to be rebuilt here.)
+    ia.only_if = ia.nrot + 1;
   }
-  if (int rc = with_nv4(rf, "score", [&](auto N) {
-        return with_flags([&](auto KS, auto US) {
-          hipLaunchKernelGGL((score_init_kernel<decltype(N)::value, decltype(KS)::value, decltype(US)::value>), grid, block,
-                             lds, s, ia);
-          return TDR_OK;
-        }, ks, us);
-      }))
-    return rc;
-  LAUNCH_CHECK("score_init");
-  hipLaunchKernelGGL(init_apply_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, (const float*)res_theta,
+  if (int rc = launch_init_vector(map, nb, us, t, s)) return rc;
+  hipLaunchKernelGGL(init_apply_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, (const float*)ia.res_theta,
                      (const float*)res_flag, n, st, cap);
   LAUNCH_CHECK("init_apply");
   return TDR_OK;
@@ -1232,65 +1133,24 @@ int tdr_batch_init_launch(const tdr_map_desc* map, int nb, int nr, const void* h
   const InitArgs* args = reinterpret_cast<const InitArgs*>(d + Lo.args);
   const InitFixEntry* fix = reinterpret_cast<const InitFixEntry*>(d + Lo.fix);
   const int32_t* blk = reinterpret_cast<const int32_t*>(d + Lo.blk);
-  const int rf = map->rec_floats;
-  const bool ks = tdr_has_kslot(map->ncls, rf);
   const dim3 all((unsigned)h.blocks);
   hipLaunchKernelGGL(init_prep_batch_kernel, all, dim3(64), 0, s, args, blk, k);
   LAUNCH_CHECK("batch_init_prep");
   for (int r = 0; r < h.nruns; r++) {
     const InitRun& R = runs[r];
     if (R.pass == TDR_INIT_PASS_VECTOR) continue;
-    const dim3 grid((unsigned)(hblk[R.first + R.count] - hblk[R.first]));
-    const InitArgs* ra = args + R.first;
-    const int32_t* rb = blk + R.first;
+    const InitTarget t{nullptr, args + R.first, blk + R.first, R.count,
+                       dim3((unsigned)(hblk[R.first + R.count] - hblk[R.first]))};
     if (R.pass == TDR_INIT_PASS_HALF)
       if (int rc = launch_half_records(map, &hargs[R.first].fp, R.unitw != 0, s)) return rc;
-    for (int us = 1; us >= 0; us--) {   // the filters with a uniform-scale table, then the others: one instantiation each
-      if (!(R.us_mask & (us ? 2 : 1))) continue;
-      if (R.pass == TDR_INIT_PASS_HALF) {
-        const HalfShape hs = init_half_shape(nb);
-        const uint4* r16c = reinterpret_cast<const uint4*>(map->rec16);
-        with_flags([&](auto US) {
-          constexpr bool U = decltype(US)::value;
-          auto launch = [&](auto kfn) { hipLaunchKernelGGL(kfn, grid, dim3(256), hs.lds, s, ra, rb, R.count, r16c, hs.img, rf); };
-          if (hs.ahead == 1) launch(score_init_half_batch_kernel<U, 1>);
-          else if (hs.ahead == 2) launch(score_init_half_batch_kernel<U, 2>);
-          else launch(score_init_half_batch_kernel<U, 3>);
-          return TDR_OK;
-        }, us != 0);
-        LAUNCH_CHECK("batch_score_init_half");
-      } else if (R.pass == TDR_INIT_PASS_SPLIT) {
-        const size_t lds16 = ((size_t)2 * nb + 1) * 16;
-        with_flags([&](auto US, auto UW, auto SV) {
-          hipLaunchKernelGGL((score_init_mfma_batch_kernel<decltype(US)::value, decltype(UW)::value, decltype(SV)::value>), grid,
-                             dim3(256), lds16, s, ra, rb, R.count);
-          return TDR_OK;
-        }, us != 0, R.unitw != 0, !ks);
-        LAUNCH_CHECK("batch_score_init_mfma");
-      } else {
-        const size_t lds16 = ((size_t)2 * nb + 1) * 2 * 16;
-        with_flags([&](auto US, auto R16) {
-          hipLaunchKernelGGL((score_init_mfma_wide_batch_kernel<decltype(R16)::value ? 4 : 3, decltype(US)::value>), grid,
-                             dim3(256), lds16, s, ra, rb, R.count);
-          return TDR_OK;
-        }, us != 0, rf == 16);
-        LAUNCH_CHECK("batch_score_init_mfma_wide");
-      }
-    }
+    for (int us = 1; us >= 0; us--)   // the filters with a uniform-scale table, then the others: one instantiation each
+      if (R.us_mask & (us ? 2 : 1))
+        if (int rc = launch_init_mfma(R.pass, map, nb, us != 0, R.unitw != 0, t, s)) return rc;
   }
-  const size_t lds = TDR_INIT_SCAN_LDS ? (size_t)2 * nb * rf * 4 : 0;
-  for (int us = 1; us >= 0; us--) {
-    if (!(h.us_mask & (us ? 2 : 1))) continue;
-    if (int rc = with_nv4(rf, "batch_init", [&](auto N) {
-          return with_flags([&](auto KS, auto US) {
-            hipLaunchKernelGGL((score_init_batch_kernel<decltype(N)::value, decltype(KS)::value, decltype(US)::value>), all,
-                               dim3(64 * INIT_WAVES), lds, s, args, blk, k);
-            return TDR_OK;
-          }, ks, us != 0);
-        }))
-      return rc;
-    LAUNCH_CHECK("batch_score_init");
-  }
+  const InitTarget t{nullptr, args, blk, k, all};
+  for (int us = 1; us >= 0; us--)
+    if (h.us_mask & (us ? 2 : 1))
+      if (int rc = launch_init_vector(map, nb, us != 0, t, s)) return rc;
   hipLaunchKernelGGL(init_apply_batch_kernel, all, dim3(64), 0, s, args, fix, blk, k);
   LAUNCH_CHECK("batch_init_apply");
   (void)nr;
