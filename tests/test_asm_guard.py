@@ -89,10 +89,11 @@ def test_the_cartesian_guard_sees_a_violation(bad, why):
 
 def test_no_inline_assembly_load_or_wait_outside_the_generated_texts():
     """Rounds 3-4 issued loads through separate inline-assembly statements with hand-counted s_waitcnt (the compiler moved a
-    copy between a load and its wait twice).  The pattern must not come back: in the two kernels' sources, no asm statement
-    other than the generated loops' may contain a load or a wait."""
+    copy between a load and its wait twice).  The pattern must not come back: in the sources of the integer form's kernels
+    and in the headers that hold the asm statements they share, no asm statement other than the generated loops' may contain
+    a load or a wait."""
     import re
-    for f in ("tdr_score_su.hip", "tdr_score_cart.hip"):
+    for f in ("tdr_score_su.hip", "tdr_score_cart.hip", "tdr_score_ray.hip", "tdr_score_dev.h", "tdr_score_int_dev.h"):
         src = open(os.path.join(ROOT, "top_down_renderer_amd", "csrc", f)).read()
         for m in re.finditer(r'asm\s*(?:volatile)?\s*\(\s*"([^"]*)"', src):
             text = m.group(1)

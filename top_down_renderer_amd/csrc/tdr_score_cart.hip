@@ -18,7 +18,7 @@
 #include <type_traits>
 
 #include "tdr_score_cart.h"
-#include "tdr_score_dev.h"
+#include "tdr_score_int_dev.h"
 #include "tdr_score_su.h"   // the ordering passes (tdr_su_order) and the ray order's helpers
 #include "tdr_sincosf.h"
 
@@ -137,7 +137,6 @@ __global__ __launch_bounds__(256) void score_cart_skip_kernel(CartArgs a) {
   // cos(rot), sin(rot) of top_down_map.cpp:381-385 = the host libm's cosf / sinf, bit for bit (tdr_sincosf.h)
   const float c = tdr_libm::cosf_v(theta, a.libm_fma), s = tdr_libm::sinf_v(theta, a.libm_fma);
   const float ns = -s;
-  typedef float tdr_v2f __attribute__((ext_vector_type(2)));
   const tdr_v2f cs = {c, s}, offv = {off0, off1};
   const float lo_r = (float)((double)(-resq * (float)(a.rows - 1)) / 2.), hi_r = (float)((double)(resq * (float)(a.rows - 1)) / 2.);
   const float lo_c = (float)((double)(-resq * (float)(a.cols - 1)) / 2.), hi_c = (float)((double)(resq * (float)(a.cols - 1)) / 2.);
@@ -155,17 +154,7 @@ __global__ __launch_bounds__(256) void score_cart_skip_kernel(CartArgs a) {
   const tdr_const_f scanc = (tdr_const_f)a.scan_pk;
   const tdr_const_u descc = (tdr_const_u)a.desc;
 
-  auto field = [&](const uint32_t (&w)[CW], int k) -> uint32_t {   // distance k of a compact record (cmap_decode, one field)
-    const uint32_t ww = w[k / 3];
-    const int sh = 10 * (k % 3);
-    const uint32_t boff = sh ? ((ww >> sh) & 0xFFCu) : (ww & 0xFFCu);
-    return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(ldict) + boff);
-  };
-  auto field1 = [&](uint32_t ww, int k) -> uint32_t {   // ... when the sample loaded only the dword class k lives in
-    const int sh = 10 * (k % 3);
-    const uint32_t boff = sh ? ((ww >> sh) & 0xFFCu) : (ww & 0xFFCu);
-    return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(ldict) + boff);
-  };
+  auto field = [&](const uint32_t (&w)[CW], int k) { return int_record_field(ldict, w[k / 3], k); };   // distance k of a record
   typedef typename std::conditional<INT, unsigned long long, float>::type acc_t;
   acc_t acc[ND];
 #pragma unroll
@@ -182,7 +171,7 @@ __global__ __launch_bounds__(256) void score_cart_skip_kernel(CartArgs a) {
   case K + 1:                                                                                       \
     if constexpr (K < ND) {                                                                         \
       /* (a plane's cell: the dictionary index * 4 in bits 2..11, whatever the class) */            \
-      const uint32_t m = field1(ww, planes ? 0 : (K < ND ? K : 0));                                 \
+      const uint32_t m = int_record_field(ldict, ww, planes ? 0 : K);                               \
       if constexpr (INT) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(acc[K < ND ? K : 0]) : "s"(v), "v"(m) : "vcc"); \
       else asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(acc[K < ND ? K : 0]) : "s"(v), "v"(m));      \
     }                                                                                               \
@@ -195,14 +184,8 @@ __global__ __launch_bounds__(256) void score_cart_skip_kernel(CartArgs a) {
   };
   // rotm * pts (:383-385) for window sample (row value yi, column terms AB = {-s * xj, c * xj}), centre added (:387-388),
   // rounded (:437) — the float operations of score_cart_kernel
-  auto cell = [&](tdr_v2f cyi, tdr_v2f AB, int& ri, int& ci) {
-    tdr_v2f pv = cyi + AB;         // p0 = c * yi + (-s * xj), p1 = s * yi + c * xj
-    pv = pv + offv;
-    tdr_v2f qv = {__builtin_amdgcn_fmed3f(pv.x, -1.f, rmaxf), __builtin_amdgcn_fmed3f(pv.y, -1.f, cmaxf)};
-    qv = qv + 0.49999997f;         // see round_half_away_clamped
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ri) : "v"(qv.x));
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ci) : "v"(qv.y));
-  };
+  // (p0 = c * yi + (-s * xj), p1 = s * yi + c * xj)
+  auto cell = [&](tdr_v2f cyi, tdr_v2f AB, int& ri, int& ci) { int_cell((cyi + AB) + offv, rmaxf, cmaxf, ri, ci); };
   auto column_terms = [&](int j) -> tdr_v2f {
     const float xj = cart_linspaced(j, c1, lo_c, hi_c, step_c);
     return (tdr_v2f){ns * xj, c * xj};
@@ -221,18 +204,10 @@ __global__ __launch_bounds__(256) void score_cart_skip_kernel(CartArgs a) {
       cis[u] = ci;
       if (D[4 * u] == 0) {   // wave-uniform
         offs[u] = kmask_offset(ri, ci, mrow, mconst);
-      } else if (planes && D[4 * u] < CART_CODE_FULL_ALL) {   // one class: the 2-byte cell of its plane (plane_offset), read
-        int t1, t2;                                           // as the low half of a dword at a 2-byte aligned address
-        const int cq = ci >> 3;
-        asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(t1) : "v"(cq), "v"(pkcol), "s"(D[4 * u + 2]));
-        asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(t2) : "v"(ci), "v"(t1));
-        asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(offs[u]) : "v"(ri), "v"(t2));
+      } else if (planes && D[4 * u] < CART_CODE_FULL_ALL) {   // one class: the 2-byte cell of its plane, read as the low
+        offs[u] = plane_offset_sconst(ri, ci, pkcol, D[4 * u + 2]);   // half of a dword at a 2-byte aligned address
       } else {
-        int t1, t2;
-        const int cq = ci >> 2;
-        asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(t1) : "v"(cq), "v"(ckcol), "s"(D[4 * u + 2]));
-        asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(t2) : "v"(ci), "n"(CW == 1 ? 2 : (CW == 2 ? 3 : 4)), "v"(t1));
-        asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(offs[u]) : "v"(ri), "n"(CW == 1 ? 4 : (CW == 2 ? 5 : 6)), "v"(t2));
+        offs[u] = cmap_offset_sconst<CW>(ri, ci, ckcol, D[4 * u + 2]);
       }
       // a plain load: the compiler tracks the destination and places the waits (all NS requests are issued before the first
       // value is used below).  (Rounds 3-4 issued these through inline assembly with hand-counted s_waitcnt; a register
@@ -243,9 +218,7 @@ __global__ __launch_bounds__(256) void score_cart_skip_kernel(CartArgs a) {
     for (int u = 0; u < NS; u++) {
       const uint32_t cd = D[4 * u];
       if (cd == 0) {   // wave-uniform
-        int kmsk;      // 0 / -1: the cell's known bit
-        asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(kmsk) : "v"(w[u]), "v"(cis[u]));
-        known -= (uint32_t)kmsk;
+        known -= (uint32_t)staged_mask_bit(w[u], cis[u]);   // 0 / -1: the cell's known bit
       } else {
         // bit 0 of every dword of a compact record, bit 15 of a plane's cell (tdr_cmap.hip)
         const uint32_t kb = (planes && cd < CART_CODE_FULL_ALL) ? (w[u] >> 15) & 1u : w[u] & 1u;
@@ -297,18 +270,8 @@ __global__ __launch_bounds__(256) void score_cart_skip_kernel(CartArgs a) {
     }
   }
   if constexpr (INT) {
-    if (real) {   // [chunk][2 ncls + 2][npad] words, like score_polar_su_kernel
-      const int ncls = a.ncls;
-      uint32_t* o = reinterpret_cast<uint32_t*>(a.part) + (int64_t)blockIdx.y * (2 * ncls + 2) * a.npad + slot;
-#pragma unroll
-      for (int k = 0; k < ND; k++)
-        if (k < ncls) {
-          o[(int64_t)(2 * k) * a.npad] = (uint32_t)acc[k];
-          o[(int64_t)(2 * k + 1) * a.npad] = (uint32_t)((unsigned long long)acc[k] >> 32);
-        }
-      o[(int64_t)(2 * ncls) * a.npad] = inorm;
-      o[(int64_t)(2 * ncls + 1) * a.npad] = known;
-    }
+    if (real)
+      int_write_sums(reinterpret_cast<uint32_t*>(a.part) + (int64_t)blockIdx.y * (2 * a.ncls + 2) * a.npad + slot, a.npad, a.ncls, acc, inorm, known);
   } else if (slot < a.npad) {
     float* o = a.part + (int64_t)blockIdx.y * (RF + 1) * a.npad + slot;
 #pragma unroll
@@ -377,7 +340,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void s
   const float resq = (a.res * scale) / a.resolution;
   const float c = tdr_libm::cosf_v(theta, a.libm_fma), sn = tdr_libm::sinf_v(theta, a.libm_fma);
   const float ns = -sn;
-  typedef float tdr_v2f __attribute__((ext_vector_type(2)));
   const tdr_v2f cs = {c, sn}, offv = {off0, off1};
   const float lo_r = (float)((double)(-resq * (float)(a.rows - 1)) / 2.), hi_r = (float)((double)(resq * (float)(a.rows - 1)) / 2.);
   const float lo_c = (float)((double)(-resq * (float)(a.cols - 1)) / 2.), hi_c = (float)((double)(resq * (float)(a.cols - 1)) / 2.);
@@ -408,26 +370,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void s
   for (int k = 0; k < ND; k++) acc[k] = 0;
   uint32_t inorm = 0, known = 0;
 
-  auto cell = [&](tdr_v2f cyi, tdr_v2f AB, int& ri, int& ci) {
-    tdr_v2f pv = cyi + AB;         // p0 = c * yi + (-s * xj), p1 = s * yi + c * xj
-    pv = pv + offv;
-    tdr_v2f qv = {__builtin_amdgcn_fmed3f(pv.x, -1.f, rmaxf), __builtin_amdgcn_fmed3f(pv.y, -1.f, cmaxf)};
-    qv = qv + 0.49999997f;         // see round_half_away_clamped
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ri) : "v"(qv.x));
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ci) : "v"(qv.y));
-  };
+  // (p0 = c * yi + (-s * xj), p1 = s * yi + c * xj)
+  auto cell = [&](tdr_v2f cyi, tdr_v2f AB, int& ri, int& ci) { int_cell((cyi + AB) + offv, rmaxf, cmaxf, ri, ci); };
   auto column_terms = [&](int j) -> tdr_v2f {
     const float xj = cart_linspaced(j, c1, lo_c, hi_c, step_c);
     return (tdr_v2f){ns * xj, c * xj};
-  };
-  auto add_class = [&](uint32_t cd, uint32_t v, uint32_t m) {   // acc[cd - 1] += v * m: a switch over a wave-uniform value
-    switch (cd) {
-#define CART_SU_CASE(K) \
-  case K + 1: asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(acc[K]) : "s"(v), "v"(m) : "vcc"); break;
-      CART_SU_CASE(0) CART_SU_CASE(1) CART_SU_CASE(2) CART_SU_CASE(3) CART_SU_CASE(4) CART_SU_CASE(5)
-#undef CART_SU_CASE
-      default: break;
-    }
   };
   // NS samples of one window column in plain C++ (rows of cyi[], descriptors D): one compiler-tracked gather each — the
   // mask word of an empty bin, the plane cell of a bin with one class — all requested before the first is used
@@ -443,13 +390,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void s
       if (D[4 * u] == 0) {   // wave-uniform
         w[u] = *reinterpret_cast<const uint32_t*>(crecb + kmask_offset(ri, ci, mrow, mconst));
       } else {
-        int t1, t2;
-        unsigned off;
-        const int cq = ci >> 3;
-        asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(t1) : "v"(cq), "v"(pkcol), "s"(D[4 * u + 2]));
-        asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(t2) : "v"(ci), "v"(t1));
-        asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(off) : "v"(ri), "v"(t2));
-        w[u] = *reinterpret_cast<const uint16_t*>(crecb + off);
+        w[u] = *reinterpret_cast<const uint16_t*>(crecb + plane_offset_sconst(ri, ci, pkcol, D[4 * u + 2]));
       }
     }
 #pragma unroll
@@ -462,7 +403,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void s
         known += kb;
         const uint32_t v = D[4 * u + 1];
         inorm += (0u - kb) & v;                  // the bin's count x known (state_particle.cpp:141-142)
-        add_class(cd, v, *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds.dict) + (w[u] & 0xFFCu)));
+        int_add_class(acc, cd, v, int_dict_at(lds.dict, w[u]));
       }
     }
   };
@@ -581,28 +522,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void s
 #pragma unroll
       for (int k = 0; k < ND; k++) {
         const float sk = S[k];
-        if (sk != 0.f) {   // wave-uniform
-          const uint32_t ww = wr[k / 3];
-          const int sh = 10 * (k % 3);
-          const uint32_t boff = sh ? ((ww >> sh) & 0xFFCu) : (ww & 0xFFCu);
-          acc[k] += (unsigned long long)(uint32_t)sk *
-                    *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds.dict) + boff);
-        }
+        if (sk != 0.f) acc[k] += (unsigned long long)(uint32_t)sk * int_record_field(lds.dict, wr[k / 3], k);   // wave-uniform
       }
     }
   }
-  if (real) {   // [chunk][2 ncls + 2][npad] words, like score_polar_su_kernel
-    const int ncls = a.ncls;
-    uint32_t* o = reinterpret_cast<uint32_t*>(a.part) + (int64_t)blockIdx.y * (2 * ncls + 2) * a.npad + slot;
-#pragma unroll
-    for (int k = 0; k < ND; k++)
-      if (k < ncls) {
-        o[(int64_t)(2 * k) * a.npad] = (uint32_t)acc[k];
-        o[(int64_t)(2 * k + 1) * a.npad] = (uint32_t)(acc[k] >> 32);
-      }
-    o[(int64_t)(2 * ncls) * a.npad] = inorm;
-    o[(int64_t)(2 * ncls + 1) * a.npad] = known;
-  }
+  if (real)
+    int_write_sums(reinterpret_cast<uint32_t*>(a.part) + (int64_t)blockIdx.y * (2 * a.ncls + 2) * a.npad + slot, a.npad, a.ncls, acc, inorm, known);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -642,7 +567,8 @@ int tdr_cart_skip_launch(CartArgs a, const tdr_map_desc* map, int rf, uint32_t* 
 // The integer form of a Cartesian launch: score_cart_skip_kernel<.., INT> for the dense particles, score_cart_ray_kernel for
 // the scattered ones — one WAVE per particle, lanes = 64 consecutive window columns of one window row, i.e. 64 cells along a
 // line of the map (the rotation lives in the sampling, src/top_down_map.cpp:367-389): the mapping, the data (class planes,
-// coarse mask plane, integer dictionary) and the loop of score_polar_ray_kernel (tdr_score_ray.hip).  The sample offsets are
+// coarse mask plane, integer dictionary) and the loop of score_polar_ray_kernel (tdr_score_ray.hip; the text the two share is
+// in tdr_score_int_dev.h: ray_prologue, ray_list_pass, ray_write_sums; the two halves of a sample stand in both kernels).  The sample offsets are
 // not a table here but three float operations per coordinate from the particle's rotation, computed per lane exactly like
 // the lane = particle kernels compute them; the scan descriptors are not rotated (shift 0).
 static inline int cart_ray_gq(int cols) { return cols <= 64 ? 1 : (cols <= 128 ? 2 : 4); }
@@ -729,22 +655,7 @@ __global__ __launch_bounds__(256) void score_cart_ray_kernel(CartRayArgs a) {
   const int nsparse = a.counts[1];
   if ((int64_t)blockIdx.x * 4 >= (int64_t)nsparse * a.nsplit) return;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int t = threadIdx.x; t < a.dict_n; t += 256) ldict[t] = a.dict_int[t];
-  const unsigned pconst = (unsigned)(a.pkcol + 16) + 128u;
-  if (threadIdx.x < 16) {
-    const int code = threadIdx.x;
-    uint4 e;
-    if (code >= 1 && code <= a.ncls) {
-      e.x = a.planes_off + (unsigned)(code - 1) * a.plane_bytes + pconst;
-      e.y = 0; e.z = 15; e.w = (unsigned)code * 512u;
-    } else {
-      e.x = a.cmask_off + pconst;
-      e.y = 2; e.z = 0; e.w = 0;
-    }
-    lut[code] = e;
-  }
-  unsigned long long* const my = lacc + (size_t)wave * (a.ncls + 1) * 64 + lane;
-  for (int c = 0; c <= a.ncls; c++) my[c * 64] = 0;
+  unsigned long long* const my = ray_prologue(a, lacc, ldict, lut, wave, lane);
   __syncthreads();
   const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
   const int64_t q = gw / a.nsplit;
@@ -762,7 +673,6 @@ __global__ __launch_bounds__(256) void score_cart_ray_kernel(CartRayArgs a) {
   const float resq = (a.res * scale) / a.resolution;
   const float c = tdr_libm::cosf_v(theta, a.libm_fma), s = tdr_libm::sinf_v(theta, a.libm_fma);
   const float ns = -s;
-  typedef float tdr_v2f __attribute__((ext_vector_type(2)));
   const tdr_v2f cs = {c, s}, offv = {off0, off1};
   const float lo_r = (float)((double)(-resq * (float)(a.rows - 1)) / 2.), hi_r = (float)((double)(resq * (float)(a.rows - 1)) / 2.);
   const float lo_c = (float)((double)(-resq * (float)(a.cols - 1)) / 2.), hi_c = (float)((double)(resq * (float)(a.cols - 1)) / 2.);
@@ -771,15 +681,11 @@ __global__ __launch_bounds__(256) void score_cart_ray_kernel(CartRayArgs a) {
   const int r1 = a.rows == 1 ? 1 : a.rows - 1, c1 = a.cols == 1 ? 1 : a.cols - 1;
   const float rmaxf = (float)a.map_rows, cmaxf = (float)a.map_cols;
   const char* __restrict__ crecb = reinterpret_cast<const char*>(a.crec);
+  // cell of a sample from its row term and its column term
+  auto cell_tab = [&](tdr_v2f cyi, tdr_v2f AB, int& ri, int& ci) { int_cell((cyi + AB) + offv, rmaxf, cmaxf, ri, ci); };
   auto cell = [&](tdr_v2f cyi, int j, int& ri, int& ci) {
     const float xj = cart_linspaced(j, c1, lo_c, hi_c, step_c);
-    const tdr_v2f AB = {ns * xj, c * xj};
-    tdr_v2f pv = cyi + AB;
-    pv = pv + offv;
-    tdr_v2f qv = {__builtin_amdgcn_fmed3f(pv.x, -1.f, rmaxf), __builtin_amdgcn_fmed3f(pv.y, -1.f, cmaxf)};
-    qv = qv + 0.49999997f;
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ri) : "v"(qv.x));
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ci) : "v"(qv.y));
+    cell_tab(cyi, (tdr_v2f){ns * xj, c * xj}, ri, ci);
   };
   auto row_term = [&](int i) -> tdr_v2f { return cs * cart_linspaced(i, r1, lo_r, hi_r, step_r); };
   // The column terms {-sin * x_j, cos * x_j} of the lane's columns: a lane meets the same GQ * blocks columns in every
@@ -797,14 +703,6 @@ __global__ __launch_bounds__(256) void score_cart_ray_kernel(CartRayArgs a) {
     const float xj = cart_linspaced(j, c1, lo_c, hi_c, step_c);
     ABt[k] = (tab && j < a.cols) ? (tdr_v2f){ns * xj, c * xj} : (tdr_v2f){1.0e30f, 1.0e30f};
   }
-  auto cell_tab = [&](tdr_v2f cyi, tdr_v2f AB, int& ri, int& ci) {
-    tdr_v2f pv = cyi + AB;
-    pv = pv + offv;
-    tdr_v2f qv = {__builtin_amdgcn_fmed3f(pv.x, -1.f, rmaxf), __builtin_amdgcn_fmed3f(pv.y, -1.f, cmaxf)};
-    qv = qv + 0.49999997f;
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ri) : "v"(qv.x));
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ci) : "v"(qv.y));
-  };
 
   // rows of steps: m = window row * blocks + block; this wave's share
   const int rows_all = a.rows * a.blocks, per = (rows_all + a.nsplit - 1) / a.nsplit;
@@ -854,8 +752,7 @@ __global__ __launch_bounds__(256) void score_cart_ray_kernel(CartRayArgs a) {
       kbit &= ok[sidx];
       known += kbit;
       norm = __umul24(cnt[sidx], kbit) + norm;
-      const uint32_t D = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(ldict) + (v[sidx] & 0xFFCu));
-      const unsigned long long prod = (unsigned long long)cnt[sidx] * D;
+      const unsigned long long prod = (unsigned long long)cnt[sidx] * int_dict_at(ldict, v[sidx]);
       unsigned long long* const acc = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(my) + acc_at[sidx]);
       __hip_atomic_fetch_add(acc, prod, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
@@ -871,48 +768,13 @@ __global__ __launch_bounds__(256) void score_cart_ray_kernel(CartRayArgs a) {
     for (; m + U <= m1; m += U) rows_step(std::integral_constant<int, U>{}, std::false_type{}, m);
     for (; m < m1; m++) rows_step(std::integral_constant<int, 1>{}, std::false_type{}, m);
   }
-  {   // the list: bins with several classes (or one large count)
-    const int nm = *a.n_list, mper = (nm + a.nsplit - 1) / a.nsplit;
-    const int e1 = min(nm, (part_id + 1) * mper);
-    for (int e = part_id * mper + lane; e < e1; e += 64) {
-      const uint32_t w = a.list[e];
-      const int i = (int)(w >> 16), j = (int)(w & 0xFFFFu);
-      const int64_t bin = (int64_t)j * a.rows + i;
-      int ri, ci;
-      cell(row_term(i), j, ri, ci);
-      const unsigned cell_off = plane_offset(ri, ci, a.pkcol, (int)(a.planes_off + pconst));
-      uint32_t kbit = 0;
-      for (int cl = 0; cl < a.ncls; cl++) {
-        const float sv = a.scan_pk[bin * a.rf + cl];
-        if (sv != 0.f) {
-          const uint32_t vv = *reinterpret_cast<const uint16_t*>(crecb + cell_off + (unsigned)cl * a.plane_bytes);
-          kbit = vv >> 15;
-          __hip_atomic_fetch_add(&my[(cl + 1) * 64], (unsigned long long)(uint32_t)sv * ldict[(vv & 0xFFCu) >> 2],
-                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-      }
-      norm += (uint32_t)a.scan_pk[bin * a.rf + a.rf - 1] & (0u - kbit);
-    }
-  }
-  uint32_t* o = a.part + (int64_t)part_id * (2 * a.ncls + 2) * a.npad + slot;
-  for (int cl = 0; cl < a.ncls; cl++) {
-    unsigned long long sum = __hip_atomic_load(&my[(cl + 1) * 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#pragma unroll
-    for (int dlt = 32; dlt > 0; dlt >>= 1) sum += __shfl_xor(sum, dlt, 64);
-    if (lane == 0) {
-      o[(int64_t)(2 * cl) * a.npad] = (uint32_t)sum;
-      o[(int64_t)(2 * cl + 1) * a.npad] = (uint32_t)(sum >> 32);
-    }
-  }
-#pragma unroll
-  for (int dlt = 32; dlt > 0; dlt >>= 1) {
-    known += __shfl_xor(known, dlt, 64);
-    norm += __shfl_xor(norm, dlt, 64);
-  }
-  if (lane == 0) {
-    o[(int64_t)(2 * a.ncls) * a.npad] = norm;
-    o[(int64_t)(2 * a.ncls + 1) * a.npad] = known;
-  }
+  // the list: bins with several classes, or one large count (scan_pk is [cols][rows][rf])
+  ray_list_pass(a, part_id, lane, crecb, ldict, my, norm, [&](uint32_t w, int& ri, int& ci) -> int64_t {
+    const int i = (int)(w >> 16), j = (int)(w & 0xFFFFu);
+    cell(row_term(i), j, ri, ci);
+    return (int64_t)j * a.rows + i;
+  });
+  ray_write_sums<false>(a.part + (int64_t)part_id * (2 * a.ncls + 2) * a.npad + slot, a.npad, a.ncls, lane, my, known, norm);
 }
 
 // ---- host side of the integer form ---------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 // tdr_score_dev.h — device helpers shared by the scoring kernels (tdr_score.hip, tdr_score_init.hip, tdr_score_su.hip,
 // tdr_score_ray.hip, tdr_score_cart.hip) and by the files that build what they read (tdr_cmap.hip, tdr_map_incr.hip).
+// What only the kernels of the integer form share is in tdr_score_int_dev.h, on top of this file.
 #ifndef TDR_SCORE_DEV_H_
 #define TDR_SCORE_DEV_H_
 #include "tdr_common.h"

@@ -34,7 +34,7 @@
 // flag — the same launch prepares the shift-uniform kernel's side), then
 // score_polar_ray_kernel over the sparse share of the slot list; score_finalize_exact_kernel (tdr_score.hip) turns the
 // integer sums into weights.
-#include "tdr_score_dev.h"
+#include "tdr_score_int_dev.h"
 #include "tdr_score_su.h"
 
 // ray order: a direction's rings in BLOCKS of GQ steps of 64 rings (GQ = 1, 2 or 4: ray_gq); "row" m = direction * blocks
@@ -109,7 +109,8 @@ struct RayArgs {
 // loads) times the lane's own radii (registers) — instead of read from tab_ray: the same float products the table holds
 // (score_prep_kernel checked that), and 16 bytes per lane and row less through the texture path.
 // lacc [4 waves][ncls + 1][64 lanes]: a lane's sums per class (slot 0: no class); lut, per class code: {plane constant,
-// column shift, known-bit index, accumulator}
+// column shift, known-bit index, accumulator}.  The prologue that fills them, the list pass and the epilogue are
+// score_cart_ray_kernel's too: ray_prologue, ray_list_pass, ray_write_sums (tdr_score_int_dev.h).
 // PATCH (with BM): the patch order (see the top of the file); ldir: the directions' pairs in LDS
 // COMPACT: the entries of gathers 0 .. N - 1 of a step that starts at entry e0 (a multiple of 256) of a stream — one 16-byte
 // load per lane and block of four gathers (score_prep_kernel stores the blocks lane-major and fills the last one with
@@ -152,7 +153,7 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
   const int nsparse = a.counts[1];
   if ((int64_t)blockIdx.x * 4 >= (int64_t)nsparse * a.nsplit) return;   // whole workgroup idle (uniform)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int t = threadIdx.x; t < a.dict_n; t += 256) ldict[t] = a.dict_int[t];
+  unsigned long long* const my = ray_prologue(a, lacc, ldict, lut, wave, lane);
   // COMPACT: the rings' radii behind the accumulators, 65 per segment of 64 rings (a ring the image does not have, and
   // RAY_CL_NONE's slot 64: the cell leaves the map); ldir: the directions' pairs twice over, so that (scan row - shift + nb)
   // needs no wrap
@@ -168,20 +169,6 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
     if (threadIdx.x < 16) lgate[threadIdx.x >> 2][threadIdx.x & 3] = 0;   // per particle: {phase-1 count, B entries, B count, waves done}
   }
   const unsigned pconst = (unsigned)(a.pkcol + 16) + 128u;   // plane_offset's constant without the plane's own offset
-  if (threadIdx.x < 16) {
-    const int code = threadIdx.x;
-    uint4 e;
-    if (code >= 1 && code <= a.ncls) {   // class code - 1 alone: its plane, cells as they are, `known` in bit 15
-      e.x = a.planes_off + (unsigned)(code - 1) * a.plane_bytes + pconst;
-      e.y = 0; e.z = 15; e.w = (unsigned)code * 512u;
-    } else {                             // nothing to multiply: the coarse mask plane (4 x 4 map cells per cell)
-      e.x = a.cmask_off + pconst;
-      e.y = 2; e.z = 0; e.w = 0;
-    }
-    lut[code] = e;
-  }
-  unsigned long long* const my = lacc + (size_t)wave * (a.ncls + 1) * 64 + lane;
-  for (int c = 0; c <= a.ncls; c++) my[c * 64] = 0;
   __syncthreads();
   const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
   const int64_t q = gw / a.nsplit;
@@ -201,25 +188,16 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
   const int shift = rot_shift_dev(a.st[TDR_ST_THETA * a.cap + p], a.nb);
   const float rmaxf = (float)a.rows, cmaxf = (float)a.cols;
   const char* __restrict__ crecb = reinterpret_cast<const char*>(a.crec);
-  typedef float tdr_v2f __attribute__((ext_vector_type(2)));
   const tdr_v2f offv = {off0, off1};
   auto cell = [&](float tx, float ty, int& ri, int& ci) {
     tdr_v2f pv = {tx, ty};
     if constexpr (!USCALE) pv = (pv * scale) * a.res;  // top_down_map_polar.cpp:28
-    pv = pv + offv;                                     // :29-30
-    tdr_v2f qv = {__builtin_amdgcn_fmed3f(pv.x, -1.f, rmaxf), __builtin_amdgcn_fmed3f(pv.y, -1.f, cmaxf)};
-    qv = qv + 0.49999997f;                              // round_half_away_clamped
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ri) : "v"(qv.x));
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ci) : "v"(qv.y));
+    int_cell(pv + offv, rmaxf, cmaxf, ri, ci);          // :29-31
   };
   auto cell_fac = [&](tdr_v2f dir, float rad, int& ri, int& ci) {
     tdr_v2f pv = dir * rad;                             // top_down_map_polar.cpp:17-18
     pv = (pv * fscale) * a.res;                         // :28
-    pv = pv + offv;
-    tdr_v2f qv = {__builtin_amdgcn_fmed3f(pv.x, -1.f, rmaxf), __builtin_amdgcn_fmed3f(pv.y, -1.f, cmaxf)};
-    qv = qv + 0.49999997f;
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ri) : "v"(qv.x));
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ci) : "v"(qv.y));
+    int_cell(pv + offv, rmaxf, cmaxf, ri, ci);
   };
 
   // this wave's share of the window: rows m = direction * blocks + block; a window row meets scan row (m + shift * blocks)
@@ -240,6 +218,11 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
   const bool one_block = a.blocks == 1;
   rad_t rad0 = {};
   if constexpr (FAC) rad0 = radv[lane];   // (block 0's; the only block of a window of up to 256 rings)
+  // The two halves of a sample stand here and, to the letter, in score_cart_ray_kernel.  As shared forced-inline functions
+  // (called directly or through these lambdas, a struct or four scalars per sample, the map pointer with or without
+  // restrict) the table-order kernels <2 | 4, *, false, false> were scheduled and allocated differently (<4>: 75 -> 78
+  // registers) and 100 000 uniform particles without a caller context took 8.54 ms against 8.32
+  // (profiles/int_form_shared_timing_v1.txt, "first form").
   // one sample, first half: everything that depends on the bin's class out of the table, the cell's address, the gather
   auto issue = [&](uint32_t d, int ri, int ci, uint32_t& v, uint32_t& shb, uint32_t& cnt, uint32_t& acc_at) {
     cnt = d & 0xFFFu;
@@ -258,8 +241,7 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
     asm("v_bfe_u32 %0, %1, %2, 1" : "=v"(kbit) : "v"(v), "v"(shb));
     known += kbit;
     norm = __umul24(cnt, kbit) + norm;                  // state_particle.cpp:141-142
-    const uint32_t D = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(ldict) + (v & 0xFFCu));
-    const unsigned long long prod = (unsigned long long)cnt * D;   // :136-139, as integers (0 for an empty bin)
+    const unsigned long long prod = (unsigned long long)cnt * int_dict_at(ldict, v);   // :136-139, as integers (0 for an empty bin)
     unsigned long long* const acc = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(my) + acc_at);
     __hip_atomic_fetch_add(acc, prod, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ds_add_u64; the lane's own slot
   };
@@ -343,7 +325,7 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
           const uint32_t kbit = v[u] >> 15, cnt = w[u] & 0xFFFu;
           known += kbit;
           norm = __umul24(cnt, kbit) + norm;                  // state_particle.cpp:141-142
-          const uint32_t D = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(ldict) + (v[u] & 0xFFCu));
+          const uint32_t D = int_dict_at(ldict, v[u]);
           unsigned long long* const acc = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(my) + ((w[u] >> 3) & 0x1E00u));
           __hip_atomic_fetch_add(acc, (unsigned long long)cnt * D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
@@ -417,33 +399,15 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
     for (; m < m1; m++) rows_step(std::integral_constant<int, 1>{}, m);
   }
 
-  // the list: bins that hold several classes (or one large count).  The loop above saw them as empty bins — their cell's
-  // known bit is counted — ; here every class present meets its plane, and the bin's count enters the normalisation.
-  {
-    const int nm = *a.n_list, mper = (nm + a.nsplit - 1) / a.nsplit;
-    const int e1 = min(nm, (part_id + 1) * mper);
-    for (int e = part_id * mper + lane; e < e1; e += 64) {
-      const uint32_t w = a.list[e];
-      const int r = (int)(w >> 16), j = (int)(w & 0xFFFFu);
-      int i = r - shift;   // the window row that meets scan row r
-      i += i < 0 ? a.nb : 0;
-      const int64_t k = (int64_t)j * a.nb + i, bin = (int64_t)j * a.nb + r;
-      int ri, ci;
-      cell(a.tab[2 * k], a.tab[2 * k + 1], ri, ci);
-      const unsigned cell_off = plane_offset(ri, ci, a.pkcol, (int)(a.planes_off + pconst));
-      uint32_t kbit = 0;
-      for (int c = 0; c < a.ncls; c++) {
-        const float s = a.scan_pk[bin * a.rf + c];
-        if (s != 0.f) {
-          const uint32_t vv = *reinterpret_cast<const uint16_t*>(crecb + cell_off + (unsigned)c * a.plane_bytes);
-          kbit = vv >> 15;
-          __hip_atomic_fetch_add(&my[(c + 1) * 64], (unsigned long long)(uint32_t)s * ldict[(vv & 0xFFCu) >> 2],
-                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-      }
-      norm += (uint32_t)a.scan_pk[bin * a.rf + a.rf - 1] & (0u - kbit);
-    }
-  }
+  // the list: bins that hold several classes, or one large count (ray_list_pass)
+  ray_list_pass(a, part_id, lane, crecb, ldict, my, norm, [&](uint32_t w, int& ri, int& ci) -> int64_t {
+    const int r = (int)(w >> 16), j = (int)(w & 0xFFFFu);
+    int i = r - shift;   // the window row that meets scan row r
+    i += i < 0 ? a.nb : 0;
+    const int64_t k = (int64_t)j * a.nb + i;
+    cell(a.tab[2 * k], a.tab[2 * k + 1], ri, ci);
+    return (int64_t)j * a.nb + r;
+  });
   // phase 2 (COMPACT): the gate count — see the invariant above ray_body
   if constexpr (COMPACT) {
 #pragma unroll
@@ -528,26 +492,9 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
       }
     }
   }
-  // lanes -> one sum per class (the rings a block pads a direction with fell on the guard cell — unknown — and counted nothing)
-  uint32_t* o = a.part + (int64_t)part_id * (2 * a.ncls + 2) * a.npad + slot;
-  for (int c = 0; c < a.ncls; c++) {
-    unsigned long long s = __hip_atomic_load(&my[(c + 1) * 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#pragma unroll
-    for (int dlt = 32; dlt > 0; dlt >>= 1) s += __shfl_xor(s, dlt, 64);
-    if (lane == 0) {
-      o[(int64_t)(2 * c) * a.npad] = (uint32_t)s;
-      o[(int64_t)(2 * c + 1) * a.npad] = (uint32_t)(s >> 32);
-    }
-  }
-#pragma unroll
-  for (int dlt = 32; dlt > 0; dlt >>= 1) {
-    if constexpr (!COMPACT) known += __shfl_xor(known, dlt, 64);   // (COMPACT: phase 2 left the wave's count in every lane)
-    norm += __shfl_xor(norm, dlt, 64);
-  }
-  if (lane == 0) {
-    o[(int64_t)(2 * a.ncls) * a.npad] = norm;
-    o[(int64_t)(2 * a.ncls + 1) * a.npad] = known;
-  }
+  // (the rings a block pads a direction with fell on the guard cell — unknown — and counted nothing; COMPACT: phase 2 left
+  // the wave's known count in every lane)
+  ray_write_sums<COMPACT>(a.part + (int64_t)part_id * (2 * a.ncls + 2) * a.npad + slot, a.npad, a.ncls, lane, my, known, norm);
 }
 TDR_TL_BUFFER(g_timeline_ray, tdr_debug_read_timeline_ray)   // (diagnostic build only: tdr_score_dev.h)
 template <int GQ, bool USCALE, bool BM = false, bool PATCH = false>

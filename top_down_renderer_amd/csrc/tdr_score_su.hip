@@ -48,7 +48,7 @@
 
 #include <atomic>
 
-#include "tdr_score_dev.h"
+#include "tdr_score_int_dev.h"
 #include "tdr_score_su.h"
 #include "tdr_score_su_asm.h"
 
@@ -710,7 +710,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
   const unsigned lds_base = (unsigned)(uintptr_t)&lds;                // LDS byte address of the dictionary ...
   const unsigned lbits_lds = (unsigned)(uintptr_t)&lds.bits[0];      // ... and of the staged mask
 
-  typedef float tdr_v2f __attribute__((ext_vector_type(2)));
   const tdr_v2f offv = {off0, off1};
   // plain, compiler-tracked loads: a word of the staged mask at an LDS byte address, bytes of the compact map at a byte offset
   typedef const uint32_t __attribute__((address_space(3))) * tdr_lds_u;
@@ -719,17 +718,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
   auto map_dword = [&](unsigned off) -> uint32_t { return *reinterpret_cast<const uint32_t*>(crecb + off); };
   auto map_ushort = [&](unsigned off) -> uint32_t { return *reinterpret_cast<const uint16_t*>(crecb + off); };
   const bool weird = !(fabsf(off0) <= 1e9f) || !(fabsf(off1) <= 1e9f) || (!USCALE && !(fabsf(scale * a.res) <= 1e9f));
-  auto field = [&](const uint32_t (&w)[CW], int k) -> uint32_t {   // distance k of a compact record (cmap_decode, one field)
-    const uint32_t ww = w[k / 3];
-    const int sh = 10 * (k % 3);
-    const uint32_t boff = sh ? ((ww >> sh) & 0xFFCu) : (ww & 0xFFCu);
-    return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds.dict) + boff);
-  };
-  auto field1 = [&](uint32_t ww, int k) -> uint32_t {   // ... when the sample loaded only the dword class k lives in
-    const int sh = 10 * (k % 3);
-    const uint32_t boff = sh ? ((ww >> sh) & 0xFFCu) : (ww & 0xFFCu);
-    return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds.dict) + boff);
-  };
+  auto field = [&](const uint32_t (&w)[CW], int k) { return int_record_field(lds.dict, w[k / 3], k); };   // distance k of a record
 
   // integer sums (see the file comment: exact, so independent of the order and of the kernel that forms them)
   uint64_t acc[ND];
@@ -739,29 +728,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
   uint32_t known = 0;
   uint32_t n_hand = 0, n_listed = 0;   // (profiling, wave-uniform) steps the assembly loop handed back, bins the list pass scored
 
-  // per-class accumulate of a bin that holds class cd - 1 only: a switch over a wave-uniform value
-  auto single_class = [&](uint32_t cd, uint32_t v, uint32_t ww) {
+  // A bin that holds class cd - 1 only (cd is wave-uniform): int_add_class with the value looked up from the dword the class
+  // lives in (cpp_step) or from the 2-byte cell of the class's plane.
+  auto single_class = [&](uint32_t cd, uint32_t v, uint32_t ww) { int_add_class(acc, cd, v, int_record_field(lds.dict, ww, (int)cd - 1)); };
+  auto single_class_plane = [&](uint32_t cd, uint32_t v, uint32_t cell) { int_add_class(acc, cd, v, int_dict_at(lds.dict, cell)); };
+  // far_steps keeps the switch it had, the lookup inside every case with the field's shift a constant: with the lookup in
+  // front of the switch score_polar_su_kernel<3, true, true> spills 8 bytes more (292 against 284; the kernel is pinned at
+  // 80 registers)
+  auto single_class_far = [&](uint32_t cd, uint32_t v, uint32_t ww) {
     switch (cd) {
 #define SU_CASE(K)                                                                                 \
   case K + 1:                                                                                      \
     if constexpr (K < ND) {                                                                        \
-      const uint32_t m = field1(ww, K < ND ? K : 0);                                               \
-      asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(acc[K < ND ? K : 0]) : "s"(v), "v"(m) : "vcc"); \
-    }                                                                                              \
-    break;
-      SU_CASE(0) SU_CASE(1) SU_CASE(2) SU_CASE(3) SU_CASE(4) SU_CASE(5)
-      SU_CASE(6) SU_CASE(7) SU_CASE(8) SU_CASE(9) SU_CASE(10)
-#undef SU_CASE
-      default: break;
-    }
-  };
-  // ... when the sample loaded the 2-byte cell of the class's plane (dictionary index * 4 in bits 2..11)
-  auto single_class_plane = [&](uint32_t cd, uint32_t v, uint32_t cell) {
-    const uint32_t m = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds.dict) + (cell & 0xFFCu));
-    switch (cd) {
-#define SU_CASE(K)                                                                                 \
-  case K + 1:                                                                                      \
-    if constexpr (K < ND) {                                                                        \
+      const uint32_t m = int_record_field(lds.dict, ww, K < ND ? K : 0);                           \
       asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(acc[K < ND ? K : 0]) : "s"(v), "v"(m) : "vcc"); \
     }                                                                                              \
     break;
@@ -785,11 +764,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
   auto cell = [&](float tx, float ty, int& ri, int& ci) {
     tdr_v2f pv = {tx, ty};
     if constexpr (!USCALE) pv = (pv * scale) * a.res;  // top_down_map_polar.cpp:28
-    pv = pv + offv;                                     // :29-30
-    tdr_v2f qv = {__builtin_amdgcn_fmed3f(pv.x, -1.f, rmaxf), __builtin_amdgcn_fmed3f(pv.y, -1.f, cmaxf)};
-    qv = qv + 0.49999997f;                              // round_half_away_clamped
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ri) : "v"(qv.x));
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ci) : "v"(qv.y));
+    int_cell(pv + offv, rmaxf, cmaxf, ri, ci);          // :29-31
   };
 
   // One step with the known mask staged in LDS: the 4 samples (i, j0 + jj .. jj + 3), paired with scan row r.  Known bits
@@ -816,28 +791,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
       int ri, ci;
       cell(T[2 * u], T[2 * u + 1], ri, ci);
       cis[u] = ci;
-      int wa;
-      asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(wa) : "v"(ri), "v"(krow4), "s"(kconst));
-      const int cw5 = ci >> 5;
-      unsigned la;
-      asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(la) : "v"(cw5), "v"(wa));
-      bits[u] = lds_word(la);
+      bits[u] = lds_word(staged_mask_addr(ri, ci, krow4, kconst));
       w[u] = 0;
       offs[u] = 0;
       if (code[u] != 0) {   // wave-uniform: only a non-empty bin needs its record — one dword of it
-        int t1, t2;
-        const int cq = ci >> 2;
-        asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(t1) : "v"(cq), "v"(ckcol), "s"(ckc));
-        asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(t2) : "v"(ci), "n"(CW == 1 ? 2 : (CW == 2 ? 3 : 4)), "v"(t1));
-        asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(offs[u]) : "v"(ri), "n"(CW == 1 ? 4 : (CW == 2 ? 5 : 6)), "v"(t2));
+        offs[u] = cmap_offset_sconst<CW>(ri, ci, ckcol, ckc);
         w[u] = map_dword(offs[u]);
       }
     }
 #pragma unroll
     for (int u = 0; u < 4; u++) {
       const uint32_t cd = code[u];
-      int kmsk;   // 0 / -1: the cell's known bit
-      asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(kmsk) : "v"(bits[u]), "v"(cis[u]));
+      const int kmsk = staged_mask_bit(bits[u], cis[u]);   // 0 / -1: the cell's known bit
       known -= (uint32_t)kmsk & pad[u];
       if (cd != 0) {   // wave-uniform
         if (cd < SU_CODE_FULL_ALL) {
@@ -875,27 +840,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
       int ri, ci;
       cell(T[2 * u], T[2 * u + 1], ri, ci);
       cis[u] = ci;
-      int wa;
-      asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(wa) : "v"(ri), "v"(krow4), "s"(kconst));
-      const int cw5 = ci >> 5;
-      unsigned la;
-      asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(la) : "v"(cw5), "v"(wa));
-      bits[u] = lds_word(la);
+      bits[u] = lds_word(staged_mask_addr(ri, ci, krow4, kconst));
       w[u] = 0;
       if (code[u] != 0) {   // wave-uniform
-        int t1, t2;
-        unsigned off;
-        const int cq = ci >> 3;
-        asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(t1) : "v"(cq), "v"(pkcol), "s"(pkc));
-        asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(t2) : "v"(ci), "v"(t1));
-        asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(off) : "v"(ri), "v"(t2));
-        w[u] = map_ushort(off);
+        w[u] = map_ushort(plane_offset_sconst(ri, ci, pkcol, pkc));
       }
     }
 #pragma unroll
     for (int u = 0; u < 4; u++) {
-      int kmsk;   // 0 / -1: the cell's known bit
-      asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(kmsk) : "v"(bits[u]), "v"(cis[u]));
+      const int kmsk = staged_mask_bit(bits[u], cis[u]);   // 0 / -1: the cell's known bit
       known -= (uint32_t)kmsk & pad[u];
       if (code[u] != 0) {   // wave-uniform
         norm += (uint32_t)kmsk & val[u];   // the bin's count x known (state_particle.cpp:141-142)
@@ -933,12 +886,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
           off = kmask_offset(ri, ci, mtrb, mconst);
           cbits[sidx / 6] |= (uint32_t)(ci & 31) << (5 * (sidx % 6));
         } else {               // a single class: the dword it lives in; several classes: dword 0
-          const uint32_t ckc = su_rec_const(D[4 * u]);
-          int t1, t2;
-          const int cq = ci >> 2;
-          asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(t1) : "v"(cq), "v"(ckcol), "s"(ckc));
-          asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(t2) : "v"(ci), "n"(CW == 1 ? 2 : (CW == 2 ? 3 : 4)), "v"(t1));
-          asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(off) : "v"(ri), "n"(CW == 1 ? 4 : (CW == 2 ? 5 : 6)), "v"(t2));
+          off = cmap_offset_sconst<CW>(ri, ci, ckcol, su_rec_const(D[4 * u]));
         }
         w[4 * d + u] = map_dword(off);   // (all 4 NS requests are issued before the first value is used below)
       }
@@ -963,7 +911,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
           const uint32_t v = D[4 * u + 1];
           if (cd < SU_CODE_FULL_ALL) {
             norm += (0u - kb) & v;
-            single_class(cd, v, ww);
+            single_class_far(cd, v, ww);
           } else {
             // the other dwords of the record: its offset again (rare: ~1 % of the bins hold several classes)
             // (behind a barrier the optimiser cannot see through: it would keep the coordinates of all 4 NS samples
@@ -1101,13 +1049,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
               cell(T[0], T[1], ri, ci);
               int kmsk = -1;   // 0 / -1: the cell's known bit
               if (!allknown) {
-                int wa;
-                asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(wa) : "v"(ri), "v"(krow4), "s"(kconst_s));
-                const int cw5 = ci >> 5;
-                unsigned la;
-                asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(la) : "v"(cw5), "v"(wa));
-                const uint32_t bits = lds_word(la);
-                asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(kmsk) : "v"(bits), "v"(ci));
+                kmsk = staged_mask_bit(lds_word(staged_mask_addr(ri, ci, krow4, kconst_s)), ci);
               }
               norm += (uint32_t)kmsk & total;   // the bin's count x known (state_particle.cpp:141-142)
               const tdr_const_f S = scanc + ((int64_t)(j0 + jj) * nb + r) * RF;
@@ -1116,8 +1058,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
                 const float sc = c < a.ncls ? S[c] : 0.f;
                 if (sc != 0.f) {   // wave-uniform
                   const uint32_t pc = map_ushort(plane_offset(ri, ci, pkcol, (int)(a.pbase + (uint32_t)c * a.plane_bytes)));
-                  const uint32_t m = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds.dict) + (pc & 0xFFCu));
-                  acc[c] += (uint64_t)(uint32_t)sc * (uint64_t)m;
+                  acc[c] += (uint64_t)(uint32_t)sc * (uint64_t)int_dict_at(lds.dict, pc);
                 }
               }
             } while (wv != 0);
@@ -1189,6 +1130,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
         // 8 clusters x 40 headings, more than half of the sectors).  A wave's own 64 particles still lie together: a box
         // per wave in a quarter of the staging area each (rl .. ch: the wave's own bounds after the shuffles above;
         // nothing here crosses waves, so no workgroup barrier: a wave's LDS operations execute in order).
+        // score_cart_su_kernel has the same box per segment, in its own text.  One function behind both (bounds and wave
+        // reduction, staging with the Cartesian loop) took this kernel's scratch away but config 5's step measured 12.76 ms
+        // against 12.68 at a spread of 0.07; the bounds function alone made three instantiations spill more
+        // (profiles/int_form_shared_timing_v1.txt "first form", profiles/int_form_shared_kernels_v1.txt).
         const int wrl = __builtin_amdgcn_readfirstlane(rl), wrh = __builtin_amdgcn_readfirstlane(rh);
         const int wcl = __builtin_amdgcn_readfirstlane(cl), wch = __builtin_amdgcn_readfirstlane(ch);
         const int wl = (wcl >> 5) + 1, wh = (wch >> 5) + 1;
@@ -1227,15 +1172,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
   }
   if (active) {
     const int64_t slot = base + lane;
-    uint32_t* o = a.part + (int64_t)blockIdx.y * (2 * a.ncls + 2) * a.npad + slot;
-#pragma unroll
-    for (int k = 0; k < ND; k++)
-      if (k < a.ncls) {
-        o[(int64_t)(2 * k) * a.npad] = (uint32_t)acc[k];
-        o[(int64_t)(2 * k + 1) * a.npad] = (uint32_t)(acc[k] >> 32);
-      }
-    o[(int64_t)(2 * a.ncls) * a.npad] = norm;
-    o[(int64_t)(2 * a.ncls + 1) * a.npad] = known;
+    int_write_sums(a.part + (int64_t)blockIdx.y * (2 * a.ncls + 2) * a.npad + slot, a.npad, a.ncls, acc, norm, known);
     if (a.list_stats && lane == 0) {   // (profiling: one atomic per wave and counter)
       if (n_hand) atomicAdd(&a.list_stats[0], n_hand);
       if (n_listed) atomicAdd(&a.list_stats[1], n_listed);
