@@ -1533,6 +1533,107 @@ int tdr_filter_kld_count(tdr_filter* f, const tdr_kld_params* p, int64_t* k_out,
 int tdr_batch_kld_count(tdr_filter* const* filters, int k, const tdr_kld_params* p, int64_t* k_out, int64_t* skipped_out,
                         int64_t* target_out, void* stream);
 
+/* ---- recovery injection: fresh on-road particles for a filter that sits on the wrong place (csrc/tdr_recover.hip,
+ * csrc/tdr_host_recover.cpp, csrc/tdr_philox.h) -------------------------------------------------------------
+ * A DEFINITION (the reference has no recovery; this is the random-particle injection of augmented MCL, AMCL's
+ * recovery_alpha_slow / recovery_alpha_fast, drawn from the map's road cells).  It is a call of its own after
+ * tdr_filter_update, like tdr_filter_kld_count: without the call nothing on any existing path changes, the position of
+ * the reference's std::mt19937 stream included.
+ *   The random source is Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; 10
+ *     rounds): philox(counter[4], key[2]) -> 4 words, tdr_philox4x32_host.  A slot's words depend on (seed, draw, slot,
+ *     purpose) alone, so an injection is a pure function of its inputs: no grid shape, wave order or rank enters.
+ *   The road list of a map: the cell indices r * cols + c, ascending, of every cell whose class-1 slot holds a value < 1.f
+ *     (the on-road test of particle initialisation on the device records: unknown cells hold 0 and count as road, as in
+ *     the reference).  A lane draws a cell from it in O(1); a per-lane rejection loop would diverge and has a long tail
+ *     where road is rare.
+ *   Slot i = slot_begin + local (the GLOBAL index, < 2^31), key = {seed lo, seed hi}:
+ *     a = philox({i, draw lo, draw hi, 0}, key).  The slot is injected iff (a[0] >> 8) < threshold24, an integer compare;
+ *       threshold24 = tdr_inject_threshold_host(p) = floor(p * 2^24) in double, clamped to [0, 2^24] (a NaN gives 0):
+ *       0 injects nothing, 2^24 every slot.
+ *     cell = road[((uint64)a[1] * n_road) >> 32], r = cell / cols, c = cell % cols.
+ *     ux = (a[2] >> 24) * 2^-8, uy = (a[3] >> 24) * 2^-8: eight bits, so (float)c + ux is exact below 2^15 cells a side
+ *       and never rounds up into the next cell.
+ *     init_x_px = ((float)c + ux) * resolution, init_y_px = ((float)r + uy) * resolution (float32, no contraction),
+ *       dx_m = dy_m = 0: x goes with the column, y with the row, as in the StateParticle constructor
+ *       (state_particle.cpp:3-49).  At a power-of-two resolution >= 1 the products are exact and the constructor's own
+ *       on-road test ((int)((float)(int)x / resolution) per axis) lands on the drawn cell for every injected particle; at
+ *       any other resolution the particle is by definition "on the cell it was drawn from", whatever that test rounds to.
+ *     scale keeps the value the resample left in the slot: the scale belongs to the sensor-to-map relation that the whole
+ *       posterior shares; no transcendental function enters, and a fixed or frozen filter stays uniform.
+ *     heading_mode 1: b = philox({i, draw lo, draw hi, 1}, key),
+ *       theta = (float)(b[0] >> 8) * 0x1p-24f * 6.2831855f - 3.1415927f, every operation rounded to float32, have_init = 1.
+ *     heading_mode 0: theta = 0, have_init = 0: a fresh constructor particle without a heading; the next update's
+ *       40-rotation search gives it one.
+ *     A slot that is not injected is not written; the padding behind n and the other planes are untouched.
+ *   The tracker (host, double): tdr_recovery_track_host(state, w_avg, params): a non-finite or non-positive w_avg leaves
+ *     the state alone and returns 0; otherwise each average that is zero is set to w_avg, else w += alpha * (w_avg - w)
+ *     (w_slow with alpha_slow first, then w_fast with alpha_fast); p = min(p_max, max(0, 1 - w_fast / w_slow)).
+ *     tdr_recovery_reset_host zeroes both averages (AMCL's rule after an injection).  w_avg is info[2] of the update, the
+ *     reference's mean over the valid raw weights 1 / (cost + regularization), comparable from scan to scan.
+ * Layer 1 (device pointers, asynchronous, no allocation).  tdr_k_map_road_cells: counts per workgroup, a running sum, a
+ * write; cells_out holds rows * cols words, *count_dev (DEVICE) the length, workspace tdr_map_road_workspace_bytes(rows,
+ * cols) bytes; ncls < 2 is refused as tdr_k_init_particles refuses it, and so are more than 2^31 cells.  tdr_k_inject: one
+ * thread per slot, one 4-byte load from the list per injected lane, vector stores to injected slots only;
+ * *injected_dev (DEVICE, may be NULL) is INCREMENTED by the number of injected slots with one 64-bit integer atomic per wave
+ * that injected something: the caller zeroes it.  tdr_k_inject_jobs: grid.y = the job, a DEVICE array of jobs (filters on any
+ * maps: a job carries its map's column count and resolution); the caller has checked what tdr_k_inject checks. */
+typedef struct tdr_inject_job {
+  float* st;              /* [TDR_ST_FIELDS][cap] device */
+  int64_t cap, n, slot_begin;
+  const uint32_t* road;   /* [n_road] device */
+  int64_t n_road;         /* >= 1 */
+  int32_t cols;           /* of the job's map ... */
+  float resolution;       /* ... and its resolution */
+  uint64_t seed, draw;
+  uint32_t threshold24;   /* 0 .. 2^24 */
+  int32_t heading_mode;   /* 0 .. 1 */
+  int64_t* injected;      /* device, the job's own, or NULL */
+} tdr_inject_job;
+typedef struct tdr_recovery_state {
+  double w_slow, w_fast;
+} tdr_recovery_state;
+typedef struct tdr_recovery_params {
+  double alpha_slow, alpha_fast;   /* in (0, 1]; alpha_slow << alpha_fast (AMCL: 0.001 and 0.1) */
+  double p_max;                    /* in [0, 1] */
+  int32_t heading_mode;            /* 0 .. 1 */
+  uint64_t seed;
+} tdr_recovery_params;
+void tdr_philox4x32_host(const uint32_t c[4], const uint32_t k[2], uint32_t out[4]);
+uint32_t tdr_inject_threshold_host(double p);
+double tdr_recovery_track_host(tdr_recovery_state* s, double w_avg, const tdr_recovery_params* p);
+void tdr_recovery_reset_host(tdr_recovery_state* s);
+size_t tdr_map_road_workspace_bytes(int rows, int cols);
+int tdr_k_map_road_cells(const tdr_map_desc* map, uint32_t* cells_out, int64_t* count_dev, void* workspace, void* stream);
+int tdr_k_inject(float* st, int64_t cap, int64_t n, int64_t slot_begin, const tdr_map_desc* map, const uint32_t* road,
+                 int64_t n_road, uint64_t seed, uint64_t draw, uint32_t threshold24, int heading_mode, int64_t* injected_dev,
+                 void* stream);
+int tdr_k_inject_jobs(const tdr_inject_job* jobs_dev, int n_jobs, void* stream);
+/* Handle layer.  tdr_map_road_cells: the map's road list (DEVICE, the map's own) and its length, built on first use and
+ * kept until an entry point writes the map's records (tdr_map_set*, the incremental and patch updates, every loader,
+ * tdr_fuser_apply through the patch path): the map counts those writes and the list remembers the count it was built at.
+ * A map without records, with fewer than two classes or without a road cell: TDR_ERR_ARG.
+ * tdr_filter_get_weight_stats: the first 8 floats of the last update's info (tdr_k_update_weights); TDR_ERR_ARG before the
+ * first update.  tdr_filter_inject: draw = tdr_filter_step_count, the road list of the filter's map, the kernel on the
+ * filter's stream; injected_out == NULL: no read-back and no wait.  With heading_mode 0 and p > 0 the filter's next update
+ * runs the 40-rotation search.  tdr_filter_recovery_step: reads the statistics (one 32-byte read-back), tracks, and when
+ * p > 0 injects with the parameters' heading_mode and seed and resets the averages; *p_out, *injected_out may be NULL.
+ * tdr_batch_inject: k filters (polar or Cartesian, on any maps), p[k] and seeds[k] one each, with one job upload, one
+ * launch, one read-back (injected_out may be NULL: none); each filter ends byte for byte where its own call leaves it.
+ * None of them changes raw or normalised weights, the cached weight statistics, the generator's position, the stored
+ * mixture or tdr_filter_step_count.  Refused with TDR_ERR_ARG, nothing written: null pointers, p outside [0, 1] or not
+ * finite, alphas outside (0, 1], p_max outside [0, 1], heading_mode outside 0..1, a filter without particles or whose map
+ * has no road cell, k < 1, a filter twice in a batch, and SHARDED filters (slot_begin makes a rank's slice well defined at
+ * layer 1; the handle path for it is not built). */
+int tdr_map_road_cells(tdr_map* m, const uint32_t** cells_dev, int64_t* n_road);
+/* ... read back: *n_road is set; out_host == NULL only asks for it, else capacity >= *n_road words (TDR_ERR_ARG otherwise) */
+int tdr_map_read_road_cells(tdr_map* m, uint32_t* out_host, int64_t capacity, int64_t* n_road);
+int tdr_filter_get_weight_stats(tdr_filter* f, float out8[8]);
+int tdr_filter_inject(tdr_filter* f, double p, int heading_mode, uint64_t seed, int64_t* injected_out);
+int tdr_filter_recovery_step(tdr_filter* f, tdr_recovery_state* s, const tdr_recovery_params* rp, double* p_out,
+                             int64_t* injected_out);
+int tdr_batch_inject(tdr_filter* const* filters, int k, const double* p, int heading_mode, const uint64_t* seeds,
+                     int64_t* injected_out, void* stream);
+
 /* internal: lets the handle layer (csrc/tdr_host_*.cpp) report through tdr_last_error() */
 int tdr_set_error(int code, const char* msg);
 

@@ -93,6 +93,24 @@ class ParticleFilterBatch {
                             stream) != TDR_OK)
       throw std::runtime_error(std::string("ParticleFilterBatch::kldCount: ") + tdr_last_error());
   }
+  // inject(p[i], heading_mode, seeds[i]) of every filter through tdr_batch_inject: one job upload, one launch and one
+  // read-back for the batch; each filter ends byte for byte where its own call leaves it.  The filters need not share a
+  // map.  injected: the slots replaced per filter, or nullptr (no read-back, no wait).  Throws on a refused batch.
+  void inject(const std::vector<ParticleFilter*>& filters, const std::vector<double>& p, int heading_mode,
+              const std::vector<uint64_t>& seeds, std::vector<int64_t>* injected = nullptr, void* stream = nullptr) {
+    if (injected) injected->assign(filters.size(), 0);
+    if (p.size() != filters.size() || seeds.size() != filters.size())
+      throw std::invalid_argument("ParticleFilterBatch::inject: one probability and one seed per filter");
+    if (filters.empty()) return;
+    std::vector<tdr_filter*> handles(filters.size(), nullptr);
+    for (size_t i = 0; i < filters.size(); i++) {
+      if (!filters[i]) throw std::invalid_argument("ParticleFilterBatch::inject: null filter");
+      handles[i] = filters[i]->handle();
+    }
+    if (tdr_batch_inject(handles.data(), (int)handles.size(), p.data(), heading_mode, seeds.data(),
+                         injected ? injected->data() : nullptr, stream) != TDR_OK)
+      throw std::runtime_error(std::string("ParticleFilterBatch::inject: ") + tdr_last_error());
+  }
   // renderViz(out, h, w, pub_scale, arrows[k]) of every filter through tdr_batch_visualize: one launch per stage, one
   // read-back and one wait for the batch, each filter over its own background.  arrows: empty, or one list per filter.
   // Throws on a refused batch (a null or repeated filter, a sharded one, one without a background) before any device work.

@@ -74,6 +74,27 @@ class ParticleFilterCartesian {
     check(tdr_filter_kld_count(f_, &p, k, nullptr, &target), "kldCount");
     return target;
   }
+  // Recovery injection (extension; include/tdr.h, "recovery injection"): every slot whose Philox word falls below
+  // floor(p * 2^24) becomes a fresh particle on a road cell of the map (tdr_filter_inject); draw = the update count.
+  // heading_mode 0: no heading, the next update's 40-rotation search gives one; 1: a uniform heading.  Returns the
+  // injected slots (count = false: no read-back and no wait, returns -1).  Weights, their statistics, the generator and
+  // the step count stay as they were.  Throws on bad arguments, an empty or sharded filter and a map without road.
+  int64_t inject(double p, int heading_mode = 0, uint64_t seed = 0, bool count = true) {
+    int64_t injected = -1;
+    check(tdr_filter_inject(f_, p, heading_mode, seed, count ? &injected : nullptr), "inject");
+    return injected;
+  }
+  // ... driven by the slow / fast averages of the last update's mean raw weight (tdr_filter_recovery_step): returns the
+  // probability the tracker gave; *injected: the slots replaced
+  double recoveryStep(tdr_recovery_state& state, const RecoveryParams& rp, int64_t* injected = nullptr) {
+    double p = 0.;
+    int64_t n = 0;
+    check(tdr_filter_recovery_step(f_, &state, &rp, &p, &n), "recoveryStep");
+    if (injected) *injected = n;
+    return p;
+  }
+  // {argmax bits, sum, mean, bottom_stddev, fallback, num_valid, num_under, 0} of the last update (particle_filter.cpp:107-147)
+  void weightStats(float out8[8]) { check(tdr_filter_get_weight_stats(f_, out8), "weightStats"); }
   void configure(bool parity_rng, int locality_every) { check(tdr_filter_configure(f_, parity_rng, locality_every), "configure"); }
   void updateMap(const uint8_t* label_img, int img_h, int img_w, const std::vector<int>& flatten_lut,
                  const Eigen::Vector2i& map_center) {

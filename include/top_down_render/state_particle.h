@@ -53,6 +53,12 @@ typedef struct FilterParams {
 struct KldParams : tdr_kld_params {
   KldParams() : tdr_kld_params{4.f, 36, 3, 0.05, 2.326, 100} {}
 };
+// Recovery injection (extension; include/tdr.h, "recovery injection"): the slow / fast averages of the updates' mean raw
+// weight with AMCL's usual recovery_alpha_slow / recovery_alpha_fast, at most half the slots a step, particles without a
+// heading.  ParticleFilter::recoveryStep, TopDownRenderCore::Config::recovery.
+struct RecoveryParams : tdr_recovery_params {
+  RecoveryParams() : tdr_recovery_params{0.001, 0.1, 0.5, 0, 0} {}
+};
 inline bool sameKldParams(const tdr_kld_params& a, const tdr_kld_params& b) {
   return a.bin_xy_px == b.bin_xy_px && a.theta_bins == b.theta_bins && a.scale_bits == b.scale_bits &&
          a.epsilon == b.epsilon && a.z == b.z && a.n_min == b.n_min;

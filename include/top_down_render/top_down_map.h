@@ -220,6 +220,16 @@ class TopDownMap {
     return have != 0;
   }
   tdr_map* handle() const { return m_; }
+  // The road list (extension; include/tdr.h, "recovery injection"): the ascending cell indices r * cols + c of the cells the
+  // on-road test of particle initialisation accepts, read back from the device (the map keeps its device copy until its
+  // records are written again).  Throws on a map without records, with fewer than two classes or without a road cell.
+  std::vector<uint32_t> roadCells() {
+    int64_t n = 0;
+    if (tdr_map_read_road_cells(m_, nullptr, 0, &n) != TDR_OK) throw std::invalid_argument(std::string("roadCells: ") + tdr_last_error());
+    std::vector<uint32_t> out((size_t)n);
+    if (tdr_map_read_road_cells(m_, out.data(), n, &n) != TDR_OK) throw std::runtime_error(std::string("roadCells: ") + tdr_last_error());
+    return out;
+  }
   // The fleet picture's background (include/tdr.h, "the fleet picture"): ONE device copy for every filter on this map,
   // which ParticleFilterBatch::renderFleet draws all of them over.  Kept until it is set again; updateMap leaves it
   // alone.  bgr: an 8-bit image of three channels; or the label image the node colours (aerialMapCallback, :584), one

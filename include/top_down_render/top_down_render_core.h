@@ -42,6 +42,12 @@ class TopDownRenderCore {
     // two rules for one number.
     int kld_every = 0;
     KldParams kld;
+    // Recovery injection (extension; include/tdr.h): after the publishPoseEst of every recovery_every-th step the slow /
+    // fast averages take the update's mean raw weight and, when the fast one has dropped below the slow one, fresh on-road
+    // particles replace that share of the slots (ParticleFilter::recoveryStep; the step's estimate is the un-injected
+    // set's).  0: never — no call, no allocation, every byte of the loop as without the field.
+    int recovery_every = 0;
+    RecoveryParams recovery;
   };
   struct PoseEst {                      // what publishPoseEst computed this step
     Eigen::Matrix4f cov;                // computeMeanCov (:333)
@@ -95,6 +101,7 @@ class TopDownRenderCore {
     PoseEst e = publishPoseEst();                                                            // :560
     if (countStepAndGmmDue()) filter_->computeGMMDevice();
     if (countStepAndKldDue()) filter_->setTargetCount((int)filter_->kldCount(cfg_.kld));
+    if (countStepAndRecoveryDue()) last_recovery_p_ = filter_->recoveryStep(recovery_state_, cfg_.recovery, &last_recovery_injected_);
     if (est) *est = e;
     return true;
   }
@@ -152,6 +159,10 @@ class TopDownRenderCore {
   float currentRangeScale() const { return current_range_scale_; }
   float lastRes() const { return last_res_; }              // the res the last takeStep rendered and scored with
   bool isConverged() const { return is_converged_; }
+  // the probability and the replaced slots of the last recovery step (Config::recovery_every), and the tracker's averages
+  double lastRecoveryP() const { return last_recovery_p_; }
+  int64_t lastRecoveryInjected() const { return last_recovery_injected_; }
+  const tdr_recovery_state& recoveryState() const { return recovery_state_; }
   std::vector<Eigen::ArrayXXf>& topDown() { return top_down_; }
   // Extension: score the renderer's device images directly (ParticleFilter::update(const ScanRenderer&, float))
   void setDeviceScan(bool on) { device_scan_ = on; }
@@ -162,6 +173,8 @@ class TopDownRenderCore {
   bool countStepAndGmmDue() { return cfg_.gmm_every > 0 && ++steps_ % cfg_.gmm_every == 0; }
   // ... the same for the KLD-sampling count (Config::kld_every; never both, finishInit)
   bool countStepAndKldDue() { return cfg_.kld_every > 0 && ++steps_ % cfg_.kld_every == 0; }
+  // ... and for the recovery injection (Config::recovery_every), on a counter of its own
+  bool countStepAndRecoveryDue() { return cfg_.recovery_every > 0 && ++recovery_steps_ % cfg_.recovery_every == 0; }
   void finishInit(FilterParams& filter_params, const Eigen::VectorXi& flatten_lut) {
     if (cfg_.kld_every > 0 && cfg_.gmm_every > 0)
       throw std::invalid_argument("TopDownRenderCore: kld_every and gmm_every are two rules for one particle count; set one of them");
@@ -169,6 +182,8 @@ class TopDownRenderCore {
     filter_ = new ParticleFilter(cfg_.particle_count, map_, filter_params, cfg_.seed);                              // :116
     renderer_ = new ScanRendererPolar(flatten_lut);                                                                 // :117
     steps_ = 0;
+    recovery_steps_ = 0;
+    recovery_state_ = tdr_recovery_state{0., 0.};
     if (cfg_.gmm_every > 0) filter_->setAdaptiveCount(true);
   }
 
@@ -183,6 +198,10 @@ class TopDownRenderCore {
   bool is_converged_ = false;          // :83
   bool device_scan_ = false;
   int64_t steps_ = 0;                  // steps taken (counted only with Config::gmm_every or kld_every > 0)
+  int64_t recovery_steps_ = 0;         // ... (only with Config::recovery_every > 0)
+  tdr_recovery_state recovery_state_{0., 0.};
+  double last_recovery_p_ = 0.;
+  int64_t last_recovery_injected_ = 0;
 };
 
 #endif  // TOP_DOWN_RENDER_CORE_H_

@@ -9,6 +9,8 @@
 //      filter's scale freezes
 //   5. one ParticleFilterBatch::computeGMM for the cores whose mixture fit is due (Config::gmm_every): tdr_batch_compute_gmm;
 //      one ParticleFilterBatch::kldCount for those whose KLD-sampling count is due (Config::kld_every): tdr_batch_kld_count
+//   6. the recovery trackers of the cores whose recovery step is due (Config::recovery_every), one small read-back each,
+//      and one ParticleFilterBatch::inject per heading mode for those whose tracker asks for an injection: tdr_batch_inject
 //
 // Every core ends where cores[i]->takeStep(...) with setDeviceScan(true) leaves it: filter states, weights and generator
 // position, PoseEst, currentRangeScale, lastRes, isConverged.  One difference: the host topDown() images are not filled
@@ -106,6 +108,36 @@ class TopDownRenderCoreBatch {
       batch_.kldCount(fs, p, targets, nullptr, stream);
       for (size_t j = 0; j < same.size(); j++) filters[same[j]]->setTargetCount((int)targets[j]);
       kld_due.swap(rest);
+    }
+    // recovery: what ParticleFilter::recoveryStep does, the injections of one heading mode sharing a launch
+    for (int mode = 0; mode < 2; mode++) {
+      std::vector<ParticleFilter*> fs;
+      std::vector<TopDownRenderCore*> cs;
+      std::vector<double> ps;
+      std::vector<uint64_t> seeds;
+      for (size_t i = 0; i < k; i++) {
+        TopDownRenderCore* c = cores[i];
+        if (c->cfg_.recovery_every <= 0 || c->cfg_.recovery.heading_mode != mode) continue;
+        if (!c->countStepAndRecoveryDue()) continue;
+        float st8[8];
+        filters[i]->weightStats(st8);
+        tdr_recovery_state next = c->recovery_state_;
+        const double p = tdr_recovery_track_host(&next, (double)st8[2], &c->cfg_.recovery);
+        c->last_recovery_p_ = p;
+        c->last_recovery_injected_ = 0;
+        if (p > 0.) {
+          fs.push_back(filters[i]);
+          cs.push_back(c);
+          ps.push_back(p);
+          seeds.push_back(c->cfg_.recovery.seed);
+          tdr_recovery_reset_host(&next);
+        }
+        c->recovery_state_ = next;
+      }
+      if (fs.empty()) continue;
+      std::vector<int64_t> injected;
+      batch_.inject(fs, ps, mode, seeds, &injected, stream);
+      for (size_t j = 0; j < cs.size(); j++) cs[j]->last_recovery_injected_ = injected[j];
     }
     return true;
   }

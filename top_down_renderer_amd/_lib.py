@@ -102,6 +102,24 @@ class KldJobC(C.Structure):
 KLD_NO_KEY = 0xFFFFFFFFFFFFFFFF
 
 
+class InjectJobC(C.Structure):
+    """tdr_inject_job (include/tdr.h, "recovery injection"): one filter of a batched injection."""
+    _fields_ = [("st", C.c_void_p), ("cap", C.c_int64), ("n", C.c_int64), ("slot_begin", C.c_int64), ("road", C.c_void_p),
+                ("n_road", C.c_int64), ("cols", C.c_int32), ("resolution", C.c_float), ("seed", C.c_uint64),
+                ("draw", C.c_uint64), ("threshold24", C.c_uint32), ("heading_mode", C.c_int32), ("injected", C.c_void_p)]
+
+
+class RecoveryStateC(C.Structure):
+    """tdr_recovery_state: the slow and the fast average of the updates' mean raw weight."""
+    _fields_ = [("w_slow", C.c_double), ("w_fast", C.c_double)]
+
+
+class RecoveryParamsC(C.Structure):
+    """tdr_recovery_params."""
+    _fields_ = [("alpha_slow", C.c_double), ("alpha_fast", C.c_double), ("p_max", C.c_double), ("heading_mode", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
 class PoseStatsC(C.Structure):
     """tdr_pose_stats: one filter's result of a tdr_batch_pose."""
     _fields_ = [("mean", C.c_float * 4), ("cov", C.c_float * 16), ("scale", C.c_float), ("n", C.c_int64)]
@@ -400,6 +418,22 @@ SIGNATURES = {
     "tdr_kld_target_host": (_i64, [_i64, _i64, _i64, _i64]),
     "tdr_filter_kld_count": (_i, [_vp, C.POINTER(KldParamsC), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "tdr_batch_kld_count": (_i, [_vp, _i, C.POINTER(KldParamsC), _vp, _vp, _vp, _vp]),
+    # recovery injection (csrc/tdr_recover.hip, csrc/tdr_host_recover.cpp)
+    "tdr_philox4x32_host": (None, [_vp, _vp, _vp]),
+    "tdr_inject_threshold_host": (_u32, [C.c_double]),
+    "tdr_recovery_track_host": (C.c_double, [C.POINTER(RecoveryStateC), C.c_double, C.POINTER(RecoveryParamsC)]),
+    "tdr_recovery_reset_host": (None, [C.POINTER(RecoveryStateC)]),
+    "tdr_map_road_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "tdr_k_map_road_cells": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "tdr_k_inject": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _u64, _u64, _u32, _i, _vp, _vp]),
+    "tdr_k_inject_jobs": (_i, [_vp, _i, _vp]),
+    "tdr_map_road_cells": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "tdr_map_read_road_cells": (_i, [_vp, _vp, _i64, C.POINTER(_i64)]),
+    "tdr_filter_get_weight_stats": (_i, [_vp, _vp]),
+    "tdr_filter_inject": (_i, [_vp, C.c_double, _i, _u64, C.POINTER(_i64)]),
+    "tdr_filter_recovery_step": (_i, [_vp, C.POINTER(RecoveryStateC), C.POINTER(RecoveryParamsC), C.POINTER(C.c_double),
+                                      C.POINTER(_i64)]),
+    "tdr_batch_inject": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
     "tdr_set_error": (_i, [_i, C.c_char_p]),
     "tdr_locality_tmp_ints": (C.c_size_t, [_i64, _i, _i]),
     "tdr_locality_pose_tmp_ints": (C.c_size_t, [_i64]),

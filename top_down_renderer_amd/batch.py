@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import BatchCloudC, BatchInputC, FilterParamsC, PoseStatsC, VizRequestC, check
-from .particle_filter import kld_params_c
+from .particle_filter import kld_params_c, recovery_params_c
 
 _vp = C.c_void_p
 STATE_DTYPE = np.dtype([("init_x_px", "<f4"), ("init_y_px", "<f4"), ("dx_m", "<f4"), ("dy_m", "<f4"), ("theta", "<f4"),
@@ -59,6 +59,14 @@ class MapHandle:
         cx, cy = C.c_int(), C.c_int()
         check(self.L.tdr_map_center(self.h, C.byref(cx), C.byref(cy)))
         return cx.value, cy.value
+
+    def road_cells(self):
+        """The map's road list (tdr_map_road_cells) read back: ascending cell indices r * cols + c, uint32."""
+        n = C.c_int64(0)
+        check(self.L.tdr_map_read_road_cells(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint32)
+        check(self.L.tdr_map_read_road_cells(self.h, _ptr(out), n.value, C.byref(n)))
+        return out
 
     def sample_pts_polar(self, nb, nr, ang_res):
         check(self.L.tdr_map_sample_pts_polar(self.h, nb, nr, C.c_float(ang_res)))
@@ -312,6 +320,28 @@ class FilterHandle:
         check(self.L.tdr_filter_kld_count(self.h, C.byref(p), C.byref(k), C.byref(sk), C.byref(t)))
         return k.value, sk.value, t.value
 
+    def weight_stats(self):
+        """The first 8 floats of the last update's info (tdr_filter_get_weight_stats): {argmax bits, sum, mean,
+        bottom_stddev, fallback, num_valid, num_under, 0}."""
+        out = np.zeros(8, np.float32)
+        check(self.L.tdr_filter_get_weight_stats(self.h, _ptr(out)))
+        return out
+
+    def inject(self, p, heading_mode=0, seed=0, count=True):
+        """tdr_filter_inject: fresh on-road particles in the slots whose Philox word falls below floor(p * 2^24).  Returns
+        the number of injected slots, or None with count=False (no read-back, no wait)."""
+        n = C.c_int64(0)
+        check(self.L.tdr_filter_inject(self.h, C.c_double(p), int(heading_mode), int(seed), C.byref(n) if count else None))
+        return n.value if count else None
+
+    def recovery_step(self, state, params):
+        """tdr_filter_recovery_step: state (a _lib.RecoveryStateC) tracks the last update's mean raw weight, and the filter
+        is injected when the tracker asks for it.  params: RecoveryParams or RecoveryParamsC.  Returns (p, injected)."""
+        rp = params if isinstance(params, _lib.RecoveryParamsC) else params.to_c()
+        p, n = C.c_double(0), C.c_int64(0)
+        check(self.L.tdr_filter_recovery_step(self.h, C.byref(state), C.byref(rp), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def set_viz_background(self, bgr=None, labels=None, lut=None):
         """The picture's background: bgr (H, W, 3) uint8, or labels (H, W) uint8 coloured on the device through lut
         (256 BGR triplets; tdr_filter_set_viz_background_labels)."""
@@ -440,6 +470,20 @@ def kld_count(filters, params, stream=None):
     k, sk, t = (np.zeros(max(n, 1), np.int64) for _ in range(3))
     check(L.tdr_batch_kld_count(arr, n, C.byref(p), _ptr(k), _ptr(sk), _ptr(t), _vp(stream) if stream else None))
     return k[:n], sk[:n], t[:n]
+
+
+def inject(filters, p, heading_mode=0, seeds=None, count=True, stream=None):
+    """FilterHandle.inject of every filter in one tdr_batch_inject (one job upload, one launch, one read-back): p and seeds
+    one per filter (a scalar serves all).  Returns the injected counts (int64 array), or None with count=False."""
+    L = _lib.load()
+    n = len(filters)
+    pv = np.ascontiguousarray(np.broadcast_to(np.asarray(p, np.float64), (n,)))
+    sv = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if seeds is None else seeds, np.uint64), (n,)))
+    arr = (_vp * max(n, 1))(*[f.h if f is not None else None for f in filters])
+    out = np.zeros(max(n, 1), np.int64)
+    check(L.tdr_batch_inject(arr, n, _ptr(pv) if n else None, int(heading_mode), _ptr(sv) if n else None,
+                             _ptr(out) if count else None, _vp(stream) if stream else None))
+    return out[:n] if count else None
 
 
 def render_batch(renderers, clouds, res, ang_res, ncls, nb, nr, stream=None):
@@ -620,6 +664,25 @@ class LoopBatch:
             _, _, target = kld_count([self.filters[i] for i in ids], self.cores[ids[0]].cfg.kld, stream)
             for i, t in zip(ids, target):
                 self.cores[i].kld_target_ = int(t)
+        # recovery (CoreConfig.recovery_every): each due robot's tracker takes its update's mean raw weight; the robots it
+        # asks an injection for share one launch per heading mode
+        inj = {}
+        for i, (c, f) in enumerate(zip(self.cores, self.filters)):
+            if not c.countStepAndRecoveryDue():
+                continue
+            rp = recovery_params_c(c.cfg.recovery)
+            nxt = _lib.RecoveryStateC(c.recovery_state_.w_slow, c.recovery_state_.w_fast)
+            p = float(self.filters[i].L.tdr_recovery_track_host(C.byref(nxt), C.c_double(float(f.weight_stats()[2])), C.byref(rp)))
+            c.last_recovery_ = (p, 0)
+            if p > 0.0:
+                inj.setdefault(rp.heading_mode, []).append((i, p, rp.seed))
+                f.L.tdr_recovery_reset_host(C.byref(nxt))
+            c.recovery_state_ = nxt
+        for mode, items in inj.items():
+            counts = inject([self.filters[i] for i, _, _ in items], [p for _, p, _ in items], mode,
+                            [s for _, _, s in items], stream=stream)
+            for (i, p, _), cnt in zip(items, counts):
+                self.cores[i].last_recovery_ = (p, int(cnt))
         return out
 
     def scan_pictures(self, unflatten, lut_bgr, stream=None):

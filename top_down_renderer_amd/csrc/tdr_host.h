@@ -145,6 +145,14 @@ struct tdr_map {
   // update touches it
   DevBuf<uint8_t> viz_bg;
   int viz_h = 0, viz_w = 0;
+  // the road list (tdr_map_road_cells, csrc/tdr_recover.hip), built on first use.  rec_writes counts the calls that wrote
+  // `rec` (rec_written: every entry point that does makes it); the list is current while road_at equals it.
+  DevBuf<uint32_t> road;
+  DevBuf<int64_t> road_count;   // the list's length, as the running sum leaves it on the device
+  DevBuf<uint8_t> road_ws;
+  int64_t road_n = 0;
+  uint64_t rec_writes = 0, road_at = ~(uint64_t)0;
+  void rec_written() { rec_writes++; }
 };
 
 struct tdr_renderer {
@@ -191,6 +199,7 @@ struct tdr_filter {
   int num_gaussians = 1;      // particle_filter.cpp:7
   std::vector<float> gmm_means, gmm_covs;
   DevBuf<uint64_t> kld_ws;    // tdr_filter_kld_count: the key table for n_max and the two output words, allocated by the first call
+  DevBuf<int64_t> inject_out;   // tdr_filter_inject: the count of injected slots, allocated by the first call
   DevBuf<float> ml_dev;  // fields + mlState of the max-likelihood particle of the last update (tdr_k_save_ml_state)
   bool have_ml = false;
   // meanLikelihood + computeMeanCov of the CURRENT particle set, as last read back: publishPoseEst asks for both in a row

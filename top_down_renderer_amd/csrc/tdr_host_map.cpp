@@ -96,6 +96,7 @@ int tdr_map_set(tdr_map* m, const float* class_maps, const uint8_t* class_mask, 
   if (ncls < 1 || ncls > TDR_MAX_CLASSES || rows < 1 || cols < 1 || !(resolution > 0))
     return failh(TDR_ERR_ARG, "map_set: bad shape / resolution");
   m->inc_valid = false;
+  m->rec_written();
   const size_t ncell = (size_t)rows * cols;
   DevBuf<float> d_maps;
   DevBuf<uint8_t> d_mask;
@@ -132,6 +133,7 @@ int tdr_map_set_labels(tdr_map* m, const uint8_t* label_img, int img_h, int img_
   TTRY(tdr_map_ingest_shape(img_h, img_w, resolution, &rows, &cols));
   if (ncls < 1 || ncls > TDR_MAX_CLASSES || rows < 1 || cols < 1) return failh(TDR_ERR_ARG, "map_set_labels: bad shape");
   m->inc_valid = false;
+  m->rec_written();
   DevBuf<uint8_t>&d_img = m->ing_img, &d_ws = m->ing_ws, &d_mask = m->ing_mask;
   DevBuf<int32_t>& d_lut = m->ing_lut;
   DevBuf<float>& d_maps = m->ing_maps;
@@ -191,6 +193,7 @@ static int map_apply_incremental(tdr_map* m, int center_x, int center_y, int64_t
     m->inc_counts_ok = true;
   }
   m->inc_valid = false;   // until the update is through
+  m->rec_written();
   int n_tiles = 0, compact_ok = 0;
   TTRY(tdr_k_map_update_labels(m->ing_img.p, m->inc_img_h, m->inc_img_w, m->ing_lut.p, (int)m->inc_lut.size(), &m->desc,
                                m->ing_ws.p, m->desc.cwords ? m->inc_counts.p : nullptr, max_cells, m->inc_ws.p,

@@ -150,6 +150,7 @@ static int map_set_from_rasters(tdr_map* m, const uint8_t* d_planes, int num_cla
   m->inc_valid = false;
   DevBuf<uint8_t> d_ws;
   TTRY(d_ws.resize(tdr_map_ingest_workspace_bytes(num_classes, rows, cols)));
+  m->rec_written();   // before the write: a failed ingest leaves no list marked current
   TTRY(m->rec.resize(tdr_map_rec_floats_total(num_classes, rows, cols)));
   TTRY(tdr_k_map_from_rasters(d_planes, num_classes, rows, cols, resolution, m->rec.p, d_ws.p, nullptr));
   return map_adopt_static(m, num_classes, rows, cols, resolution, center_x, center_y);
@@ -354,6 +355,7 @@ static int map_load_color(tdr_map* m, const uint8_t* bgr, int img_h, int img_w, 
   TTRY(d_img.resize(nbytes));
   TTRY(d_ws.resize(tdr_map_ingest_workspace_bytes(num_classes, rows, cols)));
   HTRY(hipMemcpy(d_img.p, bgr, nbytes, hipMemcpyHostToDevice));
+  m->rec_written();   // before the write, as in map_set_from_rasters
   TTRY(m->rec.resize(tdr_map_rec_floats_total(num_classes, rows, cols)));
   TTRY(tdr_k_map_from_color(d_img.p, img_h, img_w, fill_keys, flatten_lut, lut_size, num_classes, resolution, m->rec.p,
                             d_ws.p, nullptr));

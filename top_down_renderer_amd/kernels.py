@@ -120,6 +120,7 @@ class DeviceMap:
         self.counts = None             # the dictionary's occurrence counts (tdr_k_map_dict_counts), current if counts_ok
         self.counts_ok = False
         self.incr_ws = None
+        self.road = None               # the road list (HipKernels.road_cells), built on first use; a record write drops it
 
     def init_scratch(self, kernels):
         """Gives the descriptor the scratch the matrix-core init search writes its pre-split f16 records to."""
@@ -332,6 +333,7 @@ class HipKernels:
                                           C.byref(n_tiles), C.byref(changed), C.byref(compact_ok), self.stream()))
         if n_tiles.value < 0:
             return None
+        m.road = None   # the records changed
         if not compact_ok.value:
             m.counts_ok = False
             m.compact(self)
@@ -814,6 +816,41 @@ class HipKernels:
         """The next update's count from k occupied bins (tdr_kld_bound_host, tdr_kld_target_host)."""
         n_kld = self.lib.tdr_kld_bound_host(int(k), C.c_double(params.epsilon), C.c_double(params.z))
         return int(self.lib.tdr_kld_target_host(n_kld, int(last_count), int(params.n_min), int(max_count)))
+
+    # ---- recovery injection (csrc/tdr_recover.hip; include/tdr.h, "recovery injection") ------------------------------
+    def road_cells(self, dmap):
+        """The road list of a DeviceMap: the cell indices r * cols + c, ascending, of the cells whose class-1 slot is below
+        1 (int32 device tensor holding uint32 words).  One read-back (the length)."""
+        cells = self.empty((dmap.rows * dmap.cols,), torch.int32)
+        ws = self.empty((max(1, int(self.lib.tdr_map_road_workspace_bytes(dmap.rows, dmap.cols))),), torch.uint8)
+        count = self.zeros((1,), torch.int64)
+        check(self.lib.tdr_k_map_road_cells(C.byref(dmap.desc), _ptr(cells), _ptr(count), _ptr(ws), self.stream()))
+        return cells[: int(count.item())]
+
+    def inject(self, st, n, dmap, road, seed, draw, threshold24, heading_mode, slot_begin=0, count=True):
+        """tdr_k_inject on slots [0, n) of st (7, cap): every slot whose Philox word falls below threshold24 becomes a fresh
+        particle on a cell of `road` (road_cells).  Returns the number of injected slots (one read-back), or None with
+        count=False (no read-back, no wait)."""
+        out = self.zeros((1,), torch.int64) if count else None
+        check(self.lib.tdr_k_inject(_ptr(st), st.shape[1], n, slot_begin, C.byref(dmap.desc), _ptr(road), road.numel(),
+                                    int(seed), int(draw), int(threshold24), int(heading_mode), _ptr(out), self.stream()))
+        return int(out.item()) if count else None
+
+    def inject_jobs(self, sts, ns, dmaps, roads, seeds, draws, thresholds, heading_mode, slot_begins=None):
+        """inject of several state tensors in one launch (the job table of tdr_k_inject_jobs): the injected counts."""
+        out = self.zeros((len(sts),), torch.int64)
+        jobs = []
+        for i, (st, n, dm, road) in enumerate(zip(sts, ns, dmaps, roads)):
+            jobs.append(_lib.InjectJobC(st.data_ptr(), st.shape[1], n, 0 if slot_begins is None else slot_begins[i],
+                                        road.data_ptr(), road.numel(), dm.cols, dm.resolution, int(seeds[i]), int(draws[i]),
+                                        int(thresholds[i]), int(heading_mode), out.data_ptr() + 8 * i))
+        jobs_d = self.to_device(np.frombuffer(bytes((_lib.InjectJobC * len(jobs))(*jobs)), np.uint8).copy())
+        check(self.lib.tdr_k_inject_jobs(_ptr(jobs_d), len(jobs), self.stream()))
+        return [int(v) for v in out.cpu().tolist()]
+
+    def inject_threshold(self, p):
+        """tdr_inject_threshold_host: floor(p * 2^24), clamped to [0, 2^24]."""
+        return int(self.lib.tdr_inject_threshold_host(C.c_double(p)))
 
     # ---- the particle picture (csrc/tdr_viz.hip) ---------------------------------------------------------------
     def viz_planes(self, H, W):

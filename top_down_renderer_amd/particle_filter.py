@@ -28,6 +28,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
+from . import _lib
 from ._lib import FilterParamsC, KldParamsC
 from .synth import STATE_DTYPE
 
@@ -81,6 +82,28 @@ class KldParams:
     def to_c(self):
         return KldParamsC(float(self.bin_xy_px), int(self.theta_bins), int(self.scale_bits), float(self.epsilon),
                           float(self.z), int(self.n_min))
+
+
+@dataclass
+class RecoveryParams:
+    """tdr_recovery_params (include/tdr.h, "recovery injection"): the slow / fast averages and the injection."""
+    alpha_slow: float = 0.001   # AMCL's recovery_alpha_slow
+    alpha_fast: float = 0.1     # AMCL's recovery_alpha_fast
+    p_max: float = 0.5          # the largest share of the slots one step may replace
+    heading_mode: int = 0       # 0: no heading, the next update's 40-rotation search gives one; 1: uniform heading
+    seed: int = 0
+
+    def to_c(self):
+        return _lib.RecoveryParamsC(float(self.alpha_slow), float(self.alpha_fast), float(self.p_max), int(self.heading_mode),
+                                    int(self.seed))
+
+
+def recovery_params_c(params):
+    """A RecoveryParams or RecoveryParamsC as a checked RecoveryParamsC: what the handle layer refuses raises here."""
+    p = params if isinstance(params, _lib.RecoveryParamsC) else params.to_c()
+    if not (0.0 < p.alpha_slow <= 1.0 and 0.0 < p.alpha_fast <= 1.0 and 0.0 <= p.p_max <= 1.0 and p.heading_mode in (0, 1)):
+        raise ValueError("recovery parameters: alphas in (0, 1], p_max in [0, 1], heading_mode 0 or 1")
+    return p
 
 
 def kld_params_c(params):
@@ -515,6 +538,53 @@ class ParticleFilter:
             k, skipped = 0, 0
         self.last_kld_ = (k, skipped)
         return self.k.kld_target(k, params, n, self.max_num_particles_)
+
+    # ---- recovery injection (include/tdr.h, "recovery injection") ------------------------------------------------------
+    def weightStats(self):
+        """The first 8 floats of the last update's info: {argmax bits, sum, mean, bottom_stddev, fallback, num_valid,
+        num_under, 0} (tdr_k_update_weights).  One read-back."""
+        if self.step_ == 0:
+            raise ValueError("weightStats: no update yet")
+        return self.info[:8].cpu().numpy().copy()
+
+    def inject(self, p, heading_mode=0, seed=0, count=True):
+        """tdr_filter_inject's rule on this filter: every slot whose Philox word falls below floor(p * 2^24) becomes a
+        fresh particle on a road cell of the map; draw = the update count, so a call is a pure function of (states, map,
+        p, heading_mode, seed, step).  heading_mode 0: no heading, the next update's 40-rotation search gives one; 1: a
+        uniform heading.  Returns the number of injected slots (None with count=False: no read-back).  Weights, their
+        statistics, the generator and the step count stay as they were."""
+        if self.comm.active:
+            raise ValueError("inject is not available on a sharded filter (the handle path for a rank's slice is not built)")
+        p = float(p)
+        if not (math.isfinite(p) and 0.0 <= p <= 1.0):
+            raise ValueError("inject: p must lie in [0, 1]")
+        if heading_mode not in (0, 1):
+            raise ValueError("inject: heading_mode is 0 or 1")
+        if self.num_particles_ < 1:
+            raise ValueError("inject: the filter has no particles")
+        road = self.map_.roadCells()
+        th = self.k.inject_threshold(float(p))
+        out = self.k.inject(self.st, self.num_particles_, self.map_.dev, road, seed, self.step_, th, heading_mode, count=count)
+        if th > 0 and heading_mode == 0:
+            self._maybe_uninit = True
+        return out
+
+    def recoveryStep(self, state, params):
+        """tdr_filter_recovery_step: track the mean raw weight of the last update in state (a _lib.RecoveryStateC) with
+        params (RecoveryParams), inject with the probability the tracker gives and reset the averages when it is
+        positive.  Returns (p, injected)."""
+        params = recovery_params_c(params)
+        if self.comm.active or self.num_particles_ < 1:
+            raise ValueError("recoveryStep needs an unsharded filter with particles")
+        w_avg = float(self.weightStats()[2])
+        nxt = _lib.RecoveryStateC(state.w_slow, state.w_fast)
+        p = float(self.k.lib.tdr_recovery_track_host(C.byref(nxt), C.c_double(w_avg), C.byref(params)))
+        injected = 0
+        if p > 0.0:
+            injected = self.inject(p, params.heading_mode, params.seed)
+            self.k.lib.tdr_recovery_reset_host(C.byref(nxt))
+        state.w_slow, state.w_fast = nxt.w_slow, nxt.w_fast
+        return p, injected
 
     def computeMeanCov(self):
         if self.num_particles_ < 1:

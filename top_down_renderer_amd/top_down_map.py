@@ -273,6 +273,19 @@ class TopDownMap:
         if old is not None and getattr(old, "nb", 0):
             self.k.set_polar_table(self.dev, old.nb, old.nr, old.ang_res)
 
+    def roadCells(self):
+        """The map's road list on the device (include/tdr.h, "recovery injection"): the ascending cell indices
+        r * cols + c of the cells the on-road test of particle initialisation accepts.  Built on first use and kept until
+        the map's records are written again (every loader and updateMap make a new device map, the incremental update drops
+        the list).  A map with fewer than two classes or without a road cell raises."""
+        if self.dev is None:
+            raise ValueError("roadCells: no map")
+        if self.dev.road is None:
+            self.dev.road = self.k.road_cells(self.dev)
+        if self.dev.road.numel() < 1:
+            raise ValueError("roadCells: the map has no road cell")
+        return self.dev.road
+
     # top_down_map.cpp:159-175
     def getClassesAtPoint(self, center):
         cx, cy = center

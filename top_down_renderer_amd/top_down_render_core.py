@@ -15,7 +15,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .particle_filter import KldParams, ParticleFilter, kld_params_c
+from . import _lib
+from .particle_filter import KldParams, ParticleFilter, RecoveryParams, kld_params_c, recovery_params_c
 from .scan_renderer import ScanRendererPolar
 
 
@@ -36,8 +37,15 @@ class CoreConfig:                       # the node's parameters that reach the s
     # 0: never.  Together with gmm_every > 0 it is refused: two rules for one number
     kld_every: int = 0
     kld: KldParams = field(default_factory=KldParams)
+    # recovery injection (include/tdr.h, "recovery injection"): after the publishPoseEst of every recovery_every-th step the
+    # slow / fast averages take the update's mean raw weight and, when the fast one has dropped below the slow one, fresh
+    # on-road particles replace that share of the slots (the step's estimate is the un-injected set's).  0: never
+    recovery_every: int = 0
+    recovery: RecoveryParams = field(default_factory=RecoveryParams)
 
     def check(self):
+        if self.recovery_every > 0:
+            recovery_params_c(self.recovery)
         if self.kld_every > 0 and self.gmm_every > 0:
             raise ValueError("CoreConfig: kld_every and gmm_every are two rules for one particle count; set one of them")
         if self.kld_every > 0:
@@ -64,6 +72,9 @@ class TopDownRenderCore:
         self.map_ = self.filter_ = self.renderer_ = None
         self.steps_ = 0                                                    # counted only with cfg.gmm_every / kld_every > 0
         self.kld_target_ = None                                            # the count the last kldCount asked for
+        self.recovery_steps_ = 0                                           # counted only with cfg.recovery_every > 0
+        self.recovery_state_ = _lib.RecoveryStateC(0.0, 0.0)
+        self.last_recovery_ = (0.0, 0)                                     # (p, injected) of the last recovery step
 
     def initialize(self, map, filter_params, flatten_lut, **filter_kw):
         """:81, 115-117 with a TopDownMapPolar the host built."""
@@ -72,6 +83,8 @@ class TopDownRenderCore:
         self.map_ = map
         self.steps_ = 0
         self.kld_target_ = None
+        self.recovery_steps_ = 0
+        self.recovery_state_ = _lib.RecoveryStateC(0.0, 0.0)
         self.ang_res = np.float32(2 * np.pi / c.theta_bins)
         map.samplePtsPolar((c.theta_bins, c.range_bins), self.ang_res)                                     # :115
         self.filter_ = ParticleFilter(c.particle_count, map, filter_params, seed=c.seed, kernels=self.k, **filter_kw)   # :116
@@ -91,6 +104,8 @@ class TopDownRenderCore:
             self.filter_.computeGMM(device=True)
         if self.countStepAndKldDue():
             self.kld_target_ = self.filter_.kldCount(self.cfg.kld)
+        if self.countStepAndRecoveryDue():
+            self.last_recovery_ = self.filter_.recoveryStep(self.recovery_state_, self.cfg.recovery)
         return e
 
     def countStepAndGmmDue(self):
@@ -108,6 +123,14 @@ class TopDownRenderCore:
             return False
         self.steps_ += 1
         return self.steps_ % g == 0
+
+    def countStepAndRecoveryDue(self):
+        """The same for the recovery injection (cfg.recovery_every), on a counter of its own."""
+        g = self.cfg.recovery_every
+        if g <= 0:
+            return False
+        self.recovery_steps_ += 1
+        return self.recovery_steps_ % g == 0
 
     def updateFilter(self, top_down, top_down_geo, res, trans, yaw):
         self.filter_.propagate(trans, yaw)                                                                  # :423
