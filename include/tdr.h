@@ -434,7 +434,9 @@ int tdr_rng_pipe_init_particles(tdr_rng_pipe* p, const tdr_map_desc* map, const 
  * the multi-workgroup reductions and the chunk headers of the exact chains).  The result is a pure function of
  * (raw_w, last_dist, n).  `sum`, `mean` and `bottom_stddev` are the reference's serial float32 accumulations bit for
  * bit at every n (csrc/tdr_prefix.hip: uw_small_kernel up to 32768 particles, tdr_chain_total above).  n is limited
- * to what the scratch holds: 40 bytes per chunk of 4096 weights behind ~12 KB of reduction scratch, about 25 million. */
+ * to what the scratch holds: 40 bytes per chunk of 4096 weights behind ~12 KB of reduction scratch, about 25 million.
+ * (Up to about 3.7 million the scratch also holds 24 bytes per 512 weights and 32 KB of slots, with which the chains are
+ * summarised over the whole chip; beyond, one workgroup walks the 4096-chunks.) */
 #define TDR_UW_INFO_FLOATS 65536
 int tdr_k_update_weights(const float* raw_w, const float* last_dist, int64_t n, float* w_out, float* info_out,
                          void* stream);
@@ -445,8 +447,10 @@ int tdr_k_update_weights(const float* raw_w, const float* last_dist, int64_t n, 
  * reference's operating point — everything is one launch of one workgroup with the weights in LDS; above, with a
  * workspace, the chain is evaluated by many workgroups (per-chunk parity summaries, see csrc/tdr_prefix.hip); without
  * one, by one workgroup.  The bits written are the serial chain's either way.  tdr_config_prefix_small(0) takes the
- * one-launch kernel out of the choice (A/B measurements, tests), 1 restores the default, < 0 only queries; env
- * TDR_PFX_SMALL. */
+ * one-launch kernel and, above 32 768 weights, the wave-chunk path of this chain and of the statistics chains out of
+ * the choice (A/B measurements, tests), 1 restores the default, < 0 only queries; env TDR_PFX_SMALL.
+ * tdr_prefix_workspace_bytes: 32 bytes per 4096 weights; above 32 768 weights also 24 bytes per 512 weights, 4 per
+ * 4096 and about 32 KB. */
 int tdr_config_prefix_small(int on);
 int64_t tdr_prefix_workspace_bytes(int64_t n);
 int tdr_k_prefix(const float* w, int64_t n, float* runmax_out, void* workspace, void* stream);

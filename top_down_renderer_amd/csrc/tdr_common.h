@@ -94,9 +94,14 @@ static inline int with_nv4(int rf, const char* who, F&& f) {
 #define INI_MAX_TILES 2048            // ini_tail_kernel holds the tiles' minima in LDS: W <= 2^22
 // tdr_prefix.hip: final value of a serial float32 chain over the raw weights (kind 0: sum of the non-NaN weights;
 // kind 1: float-accumulated squared deviations of the weights below *mean_dev), see there.  have_sums: the chunk headers in
-// `workspace` already hold the double sums of this chain's chunks (tdr_uw_chunk_pass1 / _pass2 left them there)
+// `workspace` already hold the double sums of this chain's chunks (tdr_uw_chunk_pass1 / _pass2 left them there).
+// grid: the path above 32 768 addends that summarises wave-chunks of 512 over the whole chip; the caller asks tdr_chain_grid(n)
+// and needs tdr_chain_workspace_bytes(n, true) of workspace for it, else (n, false): the 4096-chunk walk.  One value of `grid`
+// for the passes and the chains of a call.
 int tdr_chain_total(const float* raw, const float* mean_dev, int kind, int64_t n, float* total_out, void* workspace,
-                    bool have_sums, hipStream_t st);
+                    bool have_sums, bool grid, hipStream_t st);
+int64_t tdr_chain_workspace_bytes(int64_t n, bool grid);
+bool tdr_chain_grid(int64_t n);
 // The serial float chains of particle_filter.cpp:108-126 (`sum`, `bottom_stddev`) evaluated exactly by tdr_chain_total land
 // here, and the mean between them.
 struct UwExact {
@@ -106,9 +111,9 @@ struct UwExact {
 // also leaving the double sum of the NEXT chain's chunks in the headers (chain_sum_body: the pass reads the array anyway).
 // pass 1: cnt_valid[c] = the chunk's non-NaN weights, the `sum` chain's chunk sums.
 // pass 2: ex->mean = ex->sum / valid (:117), cnt_under[c] = the chunk's weights below it, the `bottom_stddev` chain's sums.
-int tdr_uw_chunk_pass1(const float* raw, int64_t n, void* workspace, int* cnt_valid, hipStream_t st);
-int tdr_uw_chunk_pass2(const float* raw, int64_t n, UwExact* ex, const int* cnt_valid, void* workspace, int* cnt_under,
-                       hipStream_t st);
+int tdr_uw_chunk_pass1(const float* raw, int64_t n, void* workspace, bool grid, int* cnt_valid, hipStream_t st);
+int tdr_uw_chunk_pass2(const float* raw, int64_t n, UwExact* ex, const int* cnt_valid, void* workspace, bool grid,
+                       int* cnt_under, hipStream_t st);
 // tdr_prefix.hip: particle_filter.cpp:107-147 for n <= 32768 in one launch, both serial chains exact
 int tdr_uw_small(const float* raw, const float* last_dist, int64_t n, float* w, float* info, hipStream_t st);
 // tdr_rng.hip: the generator's raw stream of `nblocks` state blocks behind `state`, and the state behind *consumed words of it

@@ -354,18 +354,23 @@ extern "C" int tdr_k_update_weights(const float* raw_w, const float* last_dist, 
   UwExact* ex = reinterpret_cast<UwExact*>(sc + 3);
   void* chain_ws = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(ex + 1) + 63) & ~(uintptr_t)63);
   const size_t chain_room = TDR_UW_INFO_FLOATS * sizeof(float) - kFixed;
-  const int64_t nch = tdr_prefix_workspace_bytes(n) / 32;   // chain chunks (32-byte headers)
-  if ((size_t)tdr_prefix_workspace_bytes(n) + (size_t)nch * 2 * sizeof(int) > chain_room)
+  const int64_t nch = tdr_chain_workspace_bytes(n, false) / 32;   // chain chunks (32-byte headers)
+  const size_t counts = (size_t)nch * 2 * sizeof(int);
+  // the wave-chunk records of the chains' chip-wide path fit up to about 3.7 million weights; beyond, up to 25 million, the
+  // chunk headers alone do and the chains walk 4096-chunks
+  const bool grid = tdr_chain_grid(n) && (size_t)tdr_chain_workspace_bytes(n, true) + counts <= chain_room;
+  const size_t ws_bytes = (size_t)tdr_chain_workspace_bytes(n, grid);
+  if (ws_bytes + counts > chain_room)
     return fail(TDR_ERR_ARG, "update_weights: n = %lld needs more than TDR_UW_INFO_FLOATS of scratch", (long long)n);
-  int* cnt_valid = reinterpret_cast<int*>(reinterpret_cast<char*>(chain_ws) + tdr_prefix_workspace_bytes(n));
+  int* cnt_valid = reinterpret_cast<int*>(reinterpret_cast<char*>(chain_ws) + ws_bytes);
   int* cnt_under = cnt_valid + nch;
-  int rc = tdr_uw_chunk_pass1(raw_w, n, chain_ws, cnt_valid, s);
+  int rc = tdr_uw_chunk_pass1(raw_w, n, chain_ws, grid, cnt_valid, s);
   if (rc) return rc;
-  rc = tdr_chain_total(raw_w, nullptr, 0, n, &ex->sum, chain_ws, true, s);                   // `sum` (:108-116)
+  rc = tdr_chain_total(raw_w, nullptr, 0, n, &ex->sum, chain_ws, true, grid, s);             // `sum` (:108-116)
   if (rc) return rc;
-  rc = tdr_uw_chunk_pass2(raw_w, n, ex, cnt_valid, chain_ws, cnt_under, s);
+  rc = tdr_uw_chunk_pass2(raw_w, n, ex, cnt_valid, chain_ws, grid, cnt_under, s);
   if (rc) return rc;
-  rc = tdr_chain_total(raw_w, &ex->mean, 1, n, &ex->bsum, chain_ws, true, s);                // `bottom_stddev` (:118-125)
+  rc = tdr_chain_total(raw_w, &ex->mean, 1, n, &ex->bsum, chain_ws, true, grid, s);          // `bottom_stddev` (:118-125)
   if (rc) return rc;
   hipLaunchKernelGGL(uw_pass3, dim3(UW_G), dim3(256), 0, s, raw_w, n, (const UwExact*)ex, (const int*)cnt_under, (int)nch,
                      sc + 0, w_out);

@@ -8,29 +8,34 @@
 //
 //  tdr_k_prefix (running sum + running maximum; tdr_k_prefix_mode forces a path)
 //    256 <= n <= 32 768                   pfx_small_kernel: one launch, one workgroup, weights in LDS          mode 3
-//    n >= 6144 with a workspace           prefix_multi: pfx_chunk_sum_kernel -> pfx_chunk_summary_kernel [when  mode 2
-//                                         n >= 32 768 instead: pfx_small_kernel, block 0 over the first 32 768
-//                                         weights, the other blocks the summaries of the chunks behind them] ->
-//                                         pfx_walk_kernel -> pfx_chunk_fill_kernel
+//    n >= 6144 with a workspace           prefix_multi                                                         mode 2
+//      n > 32 768                         pfx_chunk_sum_kernel -> pfx_grid_summary_kernel (one wave per wave-chunk of
+//                                         512, over the chip) -> pfx_grid_walk_kernel (ONE wave walks the summaries) ->
+//                                         pfx_grid_fill_kernel (one wave per wave-chunk).  An input with a negative or NaN
+//                                         weight takes the 4096-chunk bodies of the line below inside these launches
+//      n <= 32 768, or tdr_config_prefix_small(0)
+//                                         pfx_chunk_sum_kernel -> pfx_chunk_summary_kernel -> pfx_walk_kernel (one
+//                                         workgroup walks 4096-chunks from the first addend on) -> pfx_chunk_fill_kernel
 //    n < 24 576 otherwise                 prefix_serial_kernel: one wave, lane 0 adds in index order           mode 0
 //    else                                 prefix_exact_kernel: one workgroup, the older tie-list algorithm     mode 1
-//    tdr_config_prefix_small(0): no pfx_small_kernel (and no chain_head_kernel): the chunk walks start at the first addend
 //    tdr_config_tuning("prefix_head", n): addends pfx_walk_kernel hands to the serial head of pfx_exact_range at the very start
 //  tdr_uw_small (the update's statistics, n <= 32 768)
 //    uw_small_kernel<true>: the chains wave by wave (default); <false>: chunk by chunk on the whole workgroup
 //    (tdr_config_uw_waves(0))
 //  tdr_chain_total (one statistics chain, n > 32 768; called from tdr_filter.hip)
-//    [chain_sum_kernel unless the caller's pass left the chunk sums] -> chain_head_kernel<kind> (block 0: the first
-//    32 768 addends; the other blocks: the summaries of the chunks behind them) -> chain_walk_kernel
-//    tdr_config_prefix_small(0): chain_summary_kernel over every chunk instead of chain_head_kernel
+//    [chain_sum_kernel unless the caller's pass left the sums] -> chain_grid_summary_kernel<kind> (one wave per
+//    wave-chunk, over the chip) -> chain_grid_walk_kernel<kind> (ONE wave)
+//    tdr_config_prefix_small(0), or a caller without room for the wave-chunk records (grid = false): chain_summary_kernel
+//    over every 4096-chunk -> chain_walk_kernel (one workgroup, from the first addend on)
 //  tdr_uw_chunk_pass1 / _pass2 (tdr_k_update_weights, n > 32 768): uw_chunk_pass1_kernel / uw_chunk_pass2_kernel, one
-//    workgroup per chain chunk: the count of valid weights / of weights below the mean, and the chunk sums of the chain
-//    that follows (chain_sum_body)
+//    workgroup per chain chunk: the count of valid weights / of weights below the mean, and the chunk and wave-chunk sums
+//    of the chain that follows (chain_sum_body)
 //  tdr_batch_update_weights / tdr_batch_prefix: uw_small_batch_kernel / pfx_small_batch_kernel, one workgroup per filter
 //
 // Order of the file: the one-wave serial kernel; the one-workgroup tie-list kernel; the parity-pair chain step and
-// what it is made of (written once, used by every kernel behind it); the multi-workgroup kernels; the one-workgroup
-// kernels; dispatch.  tests/test_gpu_parity.py compares every path with the CPU chains bit for bit; what the update does
+// what it is made of (written once, used by every kernel behind it); the multi-workgroup kernels at 4096-chunk grain;
+// the one-workgroup kernels; the chip-wide kernels at wave-chunk grain, which reuse the one-workgroup kernels' wave-level
+// pieces; dispatch.  tests/test_gpu_parity.py compares every path with the CPU chains bit for bit; what the update does
 // behind its chains (fill or fallback, the two normalisations, the blend, the first maximum) is held to an exact
 // statement, on both one-workgroup kernels and the multi-workgroup passes, in tests/test_uw_exact.py.
 //
@@ -468,6 +473,27 @@ struct PfxChunk {     // 32 bytes per chunk in the caller's workspace
   int accepted;       // 3: 1 = pfx_chunk_fill_kernel writes this chunk's outputs
 };
 static_assert(sizeof(PfxChunk) == 32, "PfxChunk");
+// Above 32 768 addends the workspace continues behind the chunk headers with one record per wave-chunk (UWS_WC addends),
+// a few control words and the dual slots of the crossing chunks ("the long chains at wave-chunk grain", below).
+struct WcRec {        // 24 bytes per wave-chunk
+  double sum;         // 1: double sum of the wave-chunk (any order of additions: it feeds predictions only)
+  int code;           // 2: -1: carried through; binade; binade | UWS_DUAL_FLAG | slot << 16
+  unsigned d0, d1;    // 2: parity pair of a one-binade chunk
+  float rin;          // 3: exact running sum in front of the chunk (the running sum's refill)
+};
+struct WcCtl {
+  int slots;          // 1: zeroed; 2: dual slots handed out
+  int irregular;      // 3: the running sum's input holds a negative or NaN weight: the 4096-chunk walk took it
+  int pad[2];
+};
+#define UWG_DUAL_SLOTS 32   // 1 KB each; a crossing chunk beyond them is carried through (uws_wave_walk)
+struct ChainGridWs {
+  PfxChunk* ch;       // [nch]
+  WcRec* wc;          // [nwc]
+  int* irr;           // [nch] 1: per chunk, a weight that is negative or NaN (running sum only)
+  WcCtl* ctl;
+  uint4* dual;        // [UWG_DUAL_SLOTS][64]
+};
 #ifndef PFXW_THREADS
 #define PFXW_THREADS 512   // the walking workgroup: PFXW_THREADS x PFXW_K = one chunk (two waves per SIMD: the dependent
 #endif                     // instruction chains of one wave hide behind the other's)
@@ -992,11 +1018,10 @@ __device__ __forceinline__ float chain_walk(const A& a, const typename A::value_
 
 // ---- the heads ---------------------------------------------------------------------------------------------------------------
 // The first hn addends one by one on one wave: 64 at a time into the lanes, then every lane runs the same chain over
-// them.  KEEP (the running sum): every lane keeps the sum behind its own addend, which replaces the weight in the LDS image.
-template <bool KEEP, class A>
-__device__ __forceinline__ float chain_head_lanes(const A& a, int hn) {
+// them.  KEEP (the running sum): every lane keeps the sum behind its own addend and hands it to keep(i, v).
+template <bool KEEP, class A, class PUT>
+__device__ __forceinline__ float chain_head_lanes(const A& a, int hn, PUT keep) {
   using X = typename A::value_t;
-  extern __shared__ float uws_lraw[];
   const int lane = threadIdx.x & 63;
   float run = 0.f;
   X nxt = a.load(min(lane, hn - 1), lane < hn);
@@ -1009,9 +1034,14 @@ __device__ __forceinline__ float chain_head_lanes(const A& a, int hn) {
       run = chain_add(run, chain_readlane(cur, j));
       if (KEEP) mine = (lane == j) ? run : mine;
     }
-    if (KEEP && b + lane < hn) uws_lraw[uws_idx(b + lane)] = mine;
+    if (KEEP && b + lane < hn) keep(b + lane, mine);
   }
   return run;
+}
+template <bool KEEP, class A>
+__device__ __forceinline__ float chain_head_lanes(const A& a, int hn) {   // out of the LDS image and back into it
+  extern __shared__ float uws_lraw[];
+  return chain_head_lanes<KEEP>(a, hn, [](int i, float v) { uws_lraw[uws_idx(i)] = v; });
 }
 // The first hn <= CHAIN_HEAD addends one by one by a single thread of a workgroup of NT, out of LDS, starting from r0:
 // the form of the two workgroup-level walkers (their timing is pinned to it).  Returns the sum in every thread.
@@ -1048,9 +1078,14 @@ __device__ __forceinline__ float chain_head_serial(const A& a, int hn, float r0)
 //   4. pfx_chunk_fill_kernel (running sum only) — per accepted chunk: the same scan again, now with the exact starting
 //                          mantissa, writes every element's running sum / running maximum
 // pfx_*: the running sum, NT x K = 256 x 16 in the grid kernels; chain_*: the statistics chains, 512 x 8.
-template <int NT, int K, class A>
-__device__ __forceinline__ void chain_sum_body(const A& a, int64_t n, PfxChunk* __restrict__ ch) {
+// ws.wc (n above 32 768, else null): a wave holds one wave-chunk, whose sum goes to its record; the dual-slot counter is
+// zeroed for the summaries of the launch behind this one.  FLAGS (the running sum): also ws.irr, does the chunk hold an
+// addend that is negative or NaN — then the running sum is not its own running maximum, see pfx_grid_walk_kernel.
+template <int NT, int K, bool FLAGS = false, class A>
+__device__ __forceinline__ void chain_sum_body(const A& a, int64_t n, const ChainGridWs& ws) {
+  static_assert(K == CHAIN_K && NT * K == PFXM_CHUNK, "one wave, one wave-chunk");
   __shared__ double shd[NT / 64];
+  __shared__ int shi[FLAGS ? NT / 64 : 1];
   const long long lo = (long long)blockIdx.x * PFXM_CHUNK;
   const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
   typename A::value_t xv[K];
@@ -1058,15 +1093,33 @@ __device__ __forceinline__ void chain_sum_body(const A& a, int64_t n, PfxChunk* 
   double acc = 0.0;
 #pragma unroll
   for (int k = 0; k < K; k++) acc += (double)xv[k];
+  if constexpr (FLAGS) {   // (addends behind the chunk's end are zeros; published by the barrier of the sum)
+    bool irr = false;
+#pragma unroll
+    for (int k = 0; k < K; k++) irr |= !(xv[k] >= 0);
+    const bool any = __ballot(irr) != 0ull;
+    if ((threadIdx.x & 63) == 0) shi[threadIdx.x >> 6] = any ? 1 : 0;
+  }
   const double t = chain_wg_sum<NT>(acc, shd);
-  if (threadIdx.x == 0) ch[blockIdx.x].sum = t;
+  if (threadIdx.x == 0) ws.ch[blockIdx.x].sum = t;
+  if (ws.wc) {
+    if constexpr (FLAGS) {
+      if (threadIdx.x == 0) {
+        int f = 0;
+        for (int k = 0; k < NT / 64; k++) f |= shi[k];
+        ws.irr[blockIdx.x] = f;
+      }
+    }
+    if (threadIdx.x < NT / 64 && threadIdx.x * UWS_WC < cnt) ws.wc[blockIdx.x * (NT / 64) + threadIdx.x].sum = shd[threadIdx.x];
+    if (blockIdx.x == 0 && threadIdx.x == 0) ws.ctl->slots = 0;
+  }
 }
 template <int NT, int K, class A>
-__device__ __forceinline__ void chain_summary_body(const A& a, int64_t n, PfxChunk* __restrict__ ch, int c_first) {
+__device__ __forceinline__ void chain_summary_body(const A& a, int64_t n, PfxChunk* __restrict__ ch) {
   __shared__ double shd[NT / 64];
   __shared__ PfxPair shp[NT / 64];
   __shared__ int s_bad;
-  const int c = blockIdx.x + c_first;   // (the chunks before c_first are not walked, see prefix_multi / tdr_chain_total)
+  const int c = blockIdx.x;
   const long long lo = (long long)c * PFXM_CHUNK;
   const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
   // predicted running sum before the chunk: the double sums of the chunks before it, in chunk order per thread
@@ -1104,13 +1157,13 @@ __device__ __forceinline__ void chain_summary_body(const A& a, int64_t n, PfxChu
     ch[c].d1 = total.a1;
   }
 }
-// The walk over the chunk list [c_first, nch) by one workgroup of PFXW_THREADS: the headers staged PFXW_BLOCK at a time;
+// The walk over the chunk list [0, nch) by one workgroup of PFXW_THREADS: the headers staged PFXW_BLOCK at a time;
 // a chunk whose prediction holds is one integer add, any other goes to slow(c), which carries r (and carry) through it.
 // FILL: note r / carry in front of every accepted chunk and mark it, for pfx_chunk_fill_kernel.  (Chunk 0 starts at
 // zero or behind a serial head and is never taken as predicted.)
 #define PFXW_BLOCK 512   // chunk summaries / headers staged in LDS at a time
 template <bool FILL, class CH, class SLOW>
-__device__ __forceinline__ void chain_walk_chunks(CH* __restrict__ ch, int nch, int c_first, float& r, float& carry, SLOW slow) {
+__device__ __forceinline__ void chain_walk_chunks(CH* __restrict__ ch, int nch, float& r, float& carry, SLOW slow) {
   __shared__ int sm_re[PFXW_BLOCK];
   __shared__ unsigned sm_d0[PFXW_BLOCK], sm_d1[PFXW_BLOCK];
   __shared__ int sm_acc[FILL ? PFXW_BLOCK : 1];
@@ -1124,7 +1177,7 @@ __device__ __forceinline__ void chain_walk_chunks(CH* __restrict__ ch, int nch, 
     }
     pfx_sync();
     const int ce = min(nch, cb + PFXW_BLOCK);
-    for (int c = max(cb, c_first); c < ce; c++) {
+    for (int c = cb; c < ce; c++) {
       const unsigned rb = __float_as_uint(r);
       const int re = (int)(rb >> 23);                   // sign bit included: a negative sum never matches
       const unsigned R = (rb & 0x7FFFFFu) | 0x800000u;
@@ -1155,13 +1208,12 @@ __device__ __forceinline__ void chain_walk_chunks(CH* __restrict__ ch, int nch, 
 }
 
 // ---- the running sum ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PFXM_THREADS) void pfx_chunk_sum_kernel(const float* __restrict__ w, int64_t n,
-                                                                     PfxChunk* __restrict__ ch) {
-  chain_sum_body<PFXM_THREADS, PFXM_K>(PfxRunSum{{w}, CHAIN_RUNSUM, 0.f}, n, ch);
+__global__ __launch_bounds__(PFXW_THREADS) void pfx_chunk_sum_kernel(const float* __restrict__ w, int64_t n, ChainGridWs ws) {
+  chain_sum_body<PFXW_THREADS, CHAIN_K, true>(ChainAddend<float, ChainGlobal, CHAIN_BOUND_22>{{w}, CHAIN_RUNSUM, 0.f}, n, ws);
 }
 __global__ __launch_bounds__(PFXM_THREADS) void pfx_chunk_summary_kernel(const float* __restrict__ w, int64_t n,
-                                                                         PfxChunk* __restrict__ ch, int c_first) {
-  chain_summary_body<PFXM_THREADS, PFXM_K>(PfxRunSum{{w}, CHAIN_RUNSUM, 0.f}, n, ch, c_first);
+                                                                         PfxChunk* __restrict__ ch) {
+  chain_summary_body<PFXM_THREADS, PFXM_K>(PfxRunSum{{w}, CHAIN_RUNSUM, 0.f}, n, ch);
 }
 // A chunk the walk cannot take as one integer add (it holds a binade crossing or an irregular weight, or was
 // mispredicted), carried through in order by the walking workgroup
@@ -1178,25 +1230,25 @@ __device__ __forceinline__ void pfx_walk_chunk(const float* __restrict__ w, long
   PfxGlobalSink sink{w, lo, runmax, prefix_opt, carry, head_len};
   r = chain_walk(a, wv, t0, 0, cnt, r, sc, sink);
 }
-__global__ __launch_bounds__(PFXW_THREADS) void pfx_walk_kernel(const float* __restrict__ w, int64_t n,
-                                                               PfxChunk* __restrict__ ch, int nch,
-                                                               float* __restrict__ runmax,
-                                                               float* __restrict__ prefix_opt, int head_len,
-                                                               int c_first, const float* __restrict__ tail) {
-  // workgroup-uniform; chunks [0, c_first) were done by pfx_small_kernel, which left the sum and the maximum behind them
-  float r = c_first > 0 ? tail[0] : 0.f, carry = c_first > 0 ? tail[1] : -INFINITY;
-  chain_walk_chunks<true>(ch, nch, c_first, r, carry, [&](int c) {
+__device__ __forceinline__ void pfx_walk_body(const float* __restrict__ w, int64_t n, PfxChunk* __restrict__ ch, int nch,
+                                              float* __restrict__ runmax, float* __restrict__ prefix_opt, int head_len) {
+  float r = 0.f, carry = -INFINITY;   // workgroup-uniform
+  chain_walk_chunks<true>(ch, nch, r, carry, [&](int c) {
     const long long lo = (long long)c * PFXM_CHUNK;
     const int cnt = (int)min((long long)PFXM_CHUNK, (long long)n - lo);
     pfx_walk_chunk(w, lo, cnt, runmax, prefix_opt, r, carry, head_len);
   });
 }
-__global__ __launch_bounds__(PFXM_THREADS) void pfx_chunk_fill_kernel(const float* __restrict__ w, int64_t n,
-                                                                      const PfxChunk* __restrict__ ch,
-                                                                      float* __restrict__ runmax,
-                                                                      float* __restrict__ prefix_opt) {
+__global__ __launch_bounds__(PFXW_THREADS) void pfx_walk_kernel(const float* __restrict__ w, int64_t n,
+                                                               PfxChunk* __restrict__ ch, int nch,
+                                                               float* __restrict__ runmax,
+                                                               float* __restrict__ prefix_opt, int head_len) {
+  pfx_walk_body(w, n, ch, nch, runmax, prefix_opt, head_len);
+}
+// (on PFXM_THREADS threads; c: the chunk)
+__device__ __forceinline__ void pfx_chunk_fill_body(const float* __restrict__ w, int64_t n, const PfxChunk* __restrict__ ch,
+                                                    int c, float* __restrict__ runmax, float* __restrict__ prefix_opt) {
   __shared__ PfxPair shp[PFXM_THREADS / 64];
-  const int c = blockIdx.x;
   const PfxChunk hdr = ch[c];
   if (!hdr.accepted) return;   // written by the walk
   const long long lo = (long long)c * PFXM_CHUNK;
@@ -1232,6 +1284,12 @@ __global__ __launch_bounds__(PFXM_THREADS) void pfx_chunk_fill_kernel(const floa
       }
   }
 }
+__global__ __launch_bounds__(PFXM_THREADS) void pfx_chunk_fill_kernel(const float* __restrict__ w, int64_t n,
+                                                                      const PfxChunk* __restrict__ ch,
+                                                                      float* __restrict__ runmax,
+                                                                      float* __restrict__ prefix_opt) {
+  pfx_chunk_fill_body(w, n, ch, blockIdx.x, runmax, prefix_opt);
+}
 
 // ---- totals of the statistics chains ---------------------------------------------------------------------------------------------
 // ParticleFilter::update's statistics (CHAIN_SUM, CHAIN_BOTTOM) are serial chains too, and only their FINAL values are
@@ -1243,12 +1301,11 @@ struct ChainSrc {
   int kind;            // CHAIN_SUM / CHAIN_BOTTOM
 };
 __device__ __forceinline__ ChainStat chain_stat(const ChainSrc& s) { return {{s.raw}, s.kind, s.kind ? *s.mean : 0.f}; }
-__global__ __launch_bounds__(PFXW_THREADS) void chain_sum_kernel(ChainSrc s, int64_t n, PfxChunk* __restrict__ ch) {
-  chain_sum_body<PFXW_THREADS, CHAIN_K>(chain_stat(s), n, ch);
+__global__ __launch_bounds__(PFXW_THREADS) void chain_sum_kernel(ChainSrc s, int64_t n, ChainGridWs ws) {
+  chain_sum_body<PFXW_THREADS, CHAIN_K>(chain_stat(s), n, ws);
 }
-__global__ __launch_bounds__(PFXW_THREADS) void chain_summary_kernel(ChainSrc s, int64_t n, PfxChunk* __restrict__ ch,
-                                                                    int c_first) {
-  chain_summary_body<PFXW_THREADS, CHAIN_K>(chain_stat(s), n, ch, c_first);
+__global__ __launch_bounds__(PFXW_THREADS) void chain_summary_kernel(ChainSrc s, int64_t n, PfxChunk* __restrict__ ch) {
+  chain_summary_body<PFXW_THREADS, CHAIN_K>(chain_stat(s), n, ch);
 }
 // one chunk on the spot by the whole workgroup, from its element pos on: no outputs, the total only
 template <class A>
@@ -1263,51 +1320,66 @@ __device__ __forceinline__ void chain_walk_chunk(const A& a, long long lo, int c
   r = chain_walk(a, xv, t0, pos, cnt, r, sc, sink);
 }
 __global__ __launch_bounds__(PFXW_THREADS) void chain_walk_kernel(ChainSrc s, int64_t n, const PfxChunk* __restrict__ ch,
-                                                                 int nch, float* __restrict__ total_out, int c_first,
-                                                                 const float* __restrict__ r_first) {
+                                                                 int nch, float* __restrict__ total_out) {
   const ChainStat a = chain_stat(s);
   // head: the sum of unnormalised weights crosses a binade every time it doubles — about ten times within the first
   // thousand addends — so those are added one by one
-  // (c_first > 0: chunks [0, c_first) were summed by chain_head_kernel, which left the sum behind them in *r_first)
-  const int hn = c_first > 0 ? 0 : (int)min((long long)CHAIN_HEAD, (long long)n);
-  float r = chain_head_serial<PFXW_THREADS>(a, hn, c_first > 0 ? *r_first : 0.f), carry = 0.f;   // workgroup-uniform
-  chain_walk_chunks<false>(ch, nch, c_first, r, carry, [&](int c) {
+  const int hn = (int)min((long long)CHAIN_HEAD, (long long)n);
+  float r = chain_head_serial<PFXW_THREADS>(a, hn, 0.f), carry = 0.f;   // workgroup-uniform
+  chain_walk_chunks<false>(ch, nch, r, carry, [&](int c) {
     const long long lo = (long long)c * PFXM_CHUNK;
     chain_walk_chunk(a, lo, (int)min((long long)PFXM_CHUNK, (long long)n - lo), r, c == 0 ? hn : 0);
   });
   if (threadIdx.x == 0) *total_out = r;
 }
-#define CHAIN_HEAD_N 32768
-// whole chunks at the start that the one-workgroup machinery takes (0: none; tdr_config_prefix_small(0) switches it off
-// for the running sum AND the statistics chains: the chunk walk from the first addend on, for A/B and debugging)
-static int chain_head_chunks(int64_t n) { return (tdr_cfg().pfx_small && n >= CHAIN_HEAD_N) ? CHAIN_HEAD_N / PFXM_CHUNK : 0; }
-// the head and, in the same launch, the summaries of the chunks [c_first, nch) behind it (chain_head_kernel, below)
-static int chain_head_launch(const float* raw, const float* mean_dev, int kind, int n_head, float* r_out, int64_t n,
-                             PfxChunk* ch, int nch, hipStream_t st);
+// The workspace of a chain over n addends.  grid: with the wave-chunk records, control words and dual slots of the path
+// above 32 768 addends behind the chunk headers.
+#define CHAIN_GRID_MIN_N 32769
+int64_t tdr_chain_workspace_bytes(int64_t n, bool grid) {
+  if (n < 1) return 0;
+  const int64_t nch = cdiv(n, (int64_t)PFXM_CHUNK), nwc = cdiv(n, (int64_t)UWS_WC);
+  int64_t b = (int64_t)sizeof(PfxChunk) * nch;
+  if (grid)
+    b += (int64_t)sizeof(WcRec) * nwc + (nwc & 1) * 8 + ((nch * (int64_t)sizeof(int) + 15) & ~(int64_t)15) + (int64_t)sizeof(WcCtl) +
+         (int64_t)UWG_DUAL_SLOTS * 64 * (int64_t)sizeof(uint4);
+  return b;
+}
+static ChainGridWs chain_grid_ws(void* workspace, int64_t n, bool grid) {
+  const int64_t nch = cdiv(n, (int64_t)PFXM_CHUNK), nwc = cdiv(n, (int64_t)UWS_WC);
+  ChainGridWs ws{reinterpret_cast<PfxChunk*>(workspace), nullptr, nullptr, nullptr, nullptr};
+  if (!grid) return ws;
+  char* p = reinterpret_cast<char*>(workspace) + sizeof(PfxChunk) * nch;   // (32-byte headers: every part stays 16-byte aligned)
+  ws.wc = reinterpret_cast<WcRec*>(p); p += sizeof(WcRec) * nwc + (nwc & 1) * 8;
+  ws.irr = reinterpret_cast<int*>(p); p += (nch * sizeof(int) + 15) & ~(size_t)15;
+  ws.ctl = reinterpret_cast<WcCtl*>(p); p += sizeof(WcCtl);
+  ws.dual = reinterpret_cast<uint4*>(p);
+  return ws;
+}
+// Does a chain over n addends take the wave-chunk path?  tdr_config_prefix_small(0) switches it off for the running sum
+// AND the statistics chains: the 4096-chunk walk from the first addend on, the independent second evaluation the tests
+// compare with.
+bool tdr_chain_grid(int64_t n) { return tdr_cfg().pfx_small && n >= CHAIN_GRID_MIN_N; }
+// summaries over the chip and the walking wave (chain_grid_summary_kernel / chain_grid_walk_kernel, below)
+static void chain_grid_total(const ChainSrc& s, int64_t n, float* total_out, const ChainGridWs& ws, hipStream_t st);
 // raw: [n] raw weights; kind 0: total = serial float sum of the non-NaN weights; kind 1: total = serial
-// float-accumulated sum of pow(w - *mean_dev, 2) over the non-NaN weights below *mean_dev.  workspace: chunk headers,
-// tdr_prefix_workspace_bytes(n).  total_out: one device float.  have_sums: the headers hold the chunks' double sums already.
+// float-accumulated sum of pow(w - *mean_dev, 2) over the non-NaN weights below *mean_dev.  workspace:
+// tdr_chain_workspace_bytes(n, grid); grid: the wave-chunk path (the caller asks tdr_chain_grid and has the room).
+// total_out: one device float.  have_sums: the workspace holds the chunks' (and wave-chunks') double sums already.
 int tdr_chain_total(const float* raw, const float* mean_dev, int kind, int64_t n, float* total_out, void* workspace,
-                    bool have_sums, hipStream_t st) {
+                    bool have_sums, bool grid, hipStream_t st) {
   const int64_t nch64 = cdiv(n, (int64_t)PFXM_CHUNK);
   if (nch64 > (1 << 24)) return fail(TDR_ERR_ARG, "chain_total: n too large");
+  if (grid && n < CHAIN_GRID_MIN_N) return fail(TDR_ERR_ARG, "chain_total: the wave-chunk path starts at 32 769 addends");
   const int nch = (int)nch64;
-  PfxChunk* ch = reinterpret_cast<PfxChunk*>(workspace);
+  const ChainGridWs ws = chain_grid_ws(workspace, n, grid);
   ChainSrc s{raw, mean_dev, kind};
-  // The first 32 768 addends — where the sum crosses most of its binades — go through the one-workgroup machinery of
-  // uw_small_kernel (chain_head_kernel, below); the chunk walk starts behind them.  Head and summaries need the chunk sums
-  // and nothing of each other: one launch, block 0 the head, the summaries in its shadow.
-  const int c_first = chain_head_chunks(n);
-  if (!have_sums) hipLaunchKernelGGL(chain_sum_kernel, dim3(nch), dim3(PFXW_THREADS), 0, st, s, n, ch);
-  float* r_first = reinterpret_cast<float*>(&ch[0].r0);   // (a header slot the chains do not use)
-  if (c_first > 0) {
-    const int rc = chain_head_launch(raw, mean_dev, kind, c_first * PFXM_CHUNK, r_first, n, ch, nch, st);
-    if (rc) return rc;
-  } else if (nch > c_first) {
-    hipLaunchKernelGGL(chain_summary_kernel, dim3(nch - c_first), dim3(PFXW_THREADS), 0, st, s, n, ch, c_first);
+  if (!have_sums) hipLaunchKernelGGL(chain_sum_kernel, dim3(nch), dim3(PFXW_THREADS), 0, st, s, n, ws);
+  if (grid) {
+    chain_grid_total(s, n, total_out, ws, st);
+    return TDR_OK;
   }
-  hipLaunchKernelGGL(chain_walk_kernel, dim3(1), dim3(PFXW_THREADS), 0, st, s, n, (const PfxChunk*)ch, nch, total_out,
-                     c_first, (const float*)r_first);
+  hipLaunchKernelGGL(chain_summary_kernel, dim3(nch), dim3(PFXW_THREADS), 0, st, s, n, ws.ch);
+  hipLaunchKernelGGL(chain_walk_kernel, dim3(1), dim3(PFXW_THREADS), 0, st, s, n, (const PfxChunk*)ws.ch, nch, total_out);
   return TDR_OK;
 }
 
@@ -1341,16 +1413,16 @@ __device__ __forceinline__ int uw_chunk_count(const float* __restrict__ raw, int
   return uw_wg_sum_int<PFXW_THREADS>(c, sh);
 }
 __global__ __launch_bounds__(PFXW_THREADS) void uw_chunk_pass1_kernel(const float* __restrict__ raw, int64_t n,
-                                                                     PfxChunk* __restrict__ ch, int* __restrict__ cnt_valid) {
+                                                                     ChainGridWs ws, int* __restrict__ cnt_valid) {
   __shared__ int shc[PFXW_THREADS / 64];
   const int c = uw_chunk_count<false>(raw, n, 0.f, shc);
   if (threadIdx.x == 0) cnt_valid[blockIdx.x] = c;
-  chain_sum_body<PFXW_THREADS, CHAIN_K>(ChainStat{{raw}, CHAIN_SUM, 0.f}, n, ch);
+  chain_sum_body<PFXW_THREADS, CHAIN_K>(ChainStat{{raw}, CHAIN_SUM, 0.f}, n, ws);
 }
 __global__ __launch_bounds__(PFXW_THREADS) void uw_chunk_pass2_kernel(const float* __restrict__ raw, int64_t n,
                                                                      UwExact* __restrict__ ex,
                                                                      const int* __restrict__ cnt_valid,
-                                                                     PfxChunk* __restrict__ ch, int* __restrict__ cnt_under) {
+                                                                     ChainGridWs ws, int* __restrict__ cnt_under) {
   __shared__ int shc[PFXW_THREADS / 64];
   __shared__ long long shv[PFXW_THREADS / 64];
   // the valid weights of all chunks (every workgroup: the same integer), then the mean (:117) from the exact `sum` chain
@@ -1368,17 +1440,17 @@ __global__ __launch_bounds__(PFXW_THREADS) void uw_chunk_pass2_kernel(const floa
     cnt_under[blockIdx.x] = c;
     if (blockIdx.x == 0) ex->mean = mean;   // every workgroup computed the same value
   }
-  chain_sum_body<PFXW_THREADS, CHAIN_K>(ChainStat{{raw}, CHAIN_BOTTOM, mean}, n, ch);
+  chain_sum_body<PFXW_THREADS, CHAIN_K>(ChainStat{{raw}, CHAIN_BOTTOM, mean}, n, ws);
 }
-int tdr_uw_chunk_pass1(const float* raw, int64_t n, void* workspace, int* cnt_valid, hipStream_t st) {
+int tdr_uw_chunk_pass1(const float* raw, int64_t n, void* workspace, bool grid, int* cnt_valid, hipStream_t st) {
   hipLaunchKernelGGL(uw_chunk_pass1_kernel, dim3((unsigned)cdiv(n, (int64_t)PFXM_CHUNK)), dim3(PFXW_THREADS), 0, st, raw, n,
-                     reinterpret_cast<PfxChunk*>(workspace), cnt_valid);
+                     chain_grid_ws(workspace, n, grid), cnt_valid);
   return TDR_OK;
 }
-int tdr_uw_chunk_pass2(const float* raw, int64_t n, UwExact* ex, const int* cnt_valid, void* workspace, int* cnt_under,
-                       hipStream_t st) {
+int tdr_uw_chunk_pass2(const float* raw, int64_t n, UwExact* ex, const int* cnt_valid, void* workspace, bool grid,
+                       int* cnt_under, hipStream_t st) {
   hipLaunchKernelGGL(uw_chunk_pass2_kernel, dim3((unsigned)cdiv(n, (int64_t)PFXM_CHUNK)), dim3(PFXW_THREADS), 0, st, raw, n,
-                     ex, cnt_valid, reinterpret_cast<PfxChunk*>(workspace), cnt_under);
+                     ex, cnt_valid, chain_grid_ws(workspace, n, grid), cnt_under);
   return TDR_OK;
 }
 
@@ -1432,8 +1504,9 @@ struct UwsShared {
 };
 // wave-chunk [lo, lo + cnt) carried through by the calling wave from its element `pos` on, entered with the running sum r
 // (wave-uniform): chain_walk on one wave, every chain with double addends as chain_walk_chunk has them
-template <class A>
-__device__ __forceinline__ float uws_wave_walk(const A& a, int lo, int cnt, float r, int pos) {
+// (I: int for the LDS image, long long for an array in memory)
+template <class A, class I>
+__device__ __forceinline__ float uws_wave_walk(const A& a, I lo, int cnt, float r, int pos) {
   const auto ad = a.as_double();
   const int t0 = (threadIdx.x & 63) * CHAIN_K;
   double xv[CHAIN_K];
@@ -1444,8 +1517,8 @@ __device__ __forceinline__ float uws_wave_walk(const A& a, int lo, int cnt, floa
 // a chunk summarised lane by lane — the inclusive scans of the lanes' parity pairs in the binade predicted at its entry
 // (x, y) and in the next one (z, w) — entered with r; pos: the element of the chunk the returned sum stands before (cnt: the
 // chunk is done, else uws_wave_walk takes over there)
-template <class A>
-__device__ __forceinline__ float uws_wave_dual(const A& a, int lo, int cnt, float r, const uint4* pq, int& pos) {
+template <class A, class I>
+__device__ __forceinline__ float uws_wave_dual(const A& a, I lo, int cnt, float r, const uint4* pq, int& pos) {
   const int lane = threadIdx.x & 63, t0 = lane * CHAIN_K;
   const unsigned rb = __float_as_uint(r), re = rb >> 23, R = (rb & 0x7FFFFFu) | 0x800000u;
   const uint4 v = pq[lane];
@@ -1474,13 +1547,141 @@ __device__ __forceinline__ float uws_wave_dual(const A& a, int lo, int cnt, floa
   pos = cnt;
   return chain_mant(re + 1u, R2 + (q63 - qL));
 }
+// What is predicted for a wave-chunk from the double sums before and behind it: its binade when it stays in one, its
+// binade and UWS_DUAL_FLAG when it crosses into the next one (the caller adds the slot), else -1.
+__device__ __forceinline__ int uws_predict(double before, double after, bool& dualc) {
+  const int re_b = (int)(__float_as_uint((float)before) >> 23), re_a = (int)(__float_as_uint((float)after) >> 23);   // sign included
+  const bool inr = re_b >= PFXM_RE_MIN && re_a <= PFXM_RE_MAX;
+  dualc = inr && re_a == re_b + 1;
+  return (inr && re_a == re_b) ? re_b : dualc ? (re_b | UWS_DUAL_FLAG) : -1;
+}
+// One wave summarises wave-chunk [lo, lo + cnt) as `code` (>= 0) predicts: P (lane 63: the chunk's parity pair in the
+// binade entered); with UWS_DUAL_FLAG the inclusive scans of the lanes' pairs in that binade and the next go to dual[lane].
+// Returns whether every addend could be classified (else the chunk is carried through).
+template <class A, class I>
+__device__ __forceinline__ bool uws_wave_summary(const A& a, I lo, int cnt, int code, uint4* dual_out, PfxPair& P) {
+  const int lane = threadIdx.x & 63, t0 = lane * CHAIN_K;
+  PfxPair Q = {0u, 0u};
+  bool anybad = false;
+  const unsigned re = (unsigned)(code & 0xFF);
+  const bool dual = (code & UWS_DUAL_FLAG) != 0;
+  typename A::value_t x[CHAIN_K];   // (all eight reads in flight before the first use)
+  a.load_items(lo, cnt, t0, x);
+  // without a rounding tie in the chunk a lane's pair is (s, s), s the plain sum of its increments
+  bool anytie = false;
+  unsigned f; bool tie, bad;
+#pragma unroll
+  for (int k = 0; k < CHAIN_K; k++) {
+    A::classify(x[k], re, f, tie, bad);
+    anybad |= bad; anytie |= tie;
+    P.a0 += f;   // (CHAIN_BOUND_22: no overflow in a lane, none below 2^31 in a wave)
+  }
+  if (dual) {
+#pragma unroll
+    for (int k = 0; k < CHAIN_K; k++) {
+      A::classify(x[k], re + 1u, f, tie, bad);
+      anybad |= bad; anytie |= tie;
+      Q.a0 += f;
+    }
+  }
+  if (__ballot(anytie) == 0ull) {
+    P.a0 = P.a1 = uws_wave_scan_u(P.a0);
+    if (dual) Q.a0 = Q.a1 = uws_wave_scan_u(Q.a0);
+  } else {
+    // (rare.  The binade is made opaque here so that this branch classifies again instead of keeping the f and tie
+    // of all sixteen classifications above alive across the ballot: 16 VGPRs, and uw_small_kernel<true> has none to spare)
+    unsigned re_t = re;
+    asm volatile("" : "+s"(re_t));
+    P = PfxPair{0u, 0u}; Q = PfxPair{0u, 0u};
+#pragma unroll
+    for (int k = 0; k < CHAIN_K; k++) {
+      A::classify(x[k], re_t, f, tie, bad);
+      P = pfx_compose(P, pfx_element_pair(f, tie));
+    }
+    P = pfx_pair_wave_scan(P);
+    if (dual) {
+#pragma unroll
+      for (int k = 0; k < CHAIN_K; k++) {
+        A::classify(x[k], re_t + 1u, f, tie, bad);
+        Q = pfx_compose(Q, pfx_element_pair(f, tie));
+      }
+      Q = pfx_pair_wave_scan(Q);
+    }
+  }
+  if (dual) dual_out[lane] = make_uint4(P.a0, P.a1, Q.a0, Q.a1);
+  return __ballot(anybad) == 0ull;
+}
+// what a summarised chunk is noted as for the walk: its code, or -1 where it has to be carried through
+__device__ __forceinline__ int uws_summary_code(int code, bool ok, const PfxPair& P) {
+  return (ok && ((code & UWS_DUAL_FLAG) || (P.a0 < (1u << 24) && P.a1 < (1u << 24)))) ? code : -1;
+}
+// The walk.  Lane l holds the summary of wave-chunk base + l (v_code -1 where there is none, and for chunk 0, which the
+// head takes); nl: lanes in use; n: addends in all.  The calling wave enters with the exact sum r in front of the first
+// summarised chunk and returns the sum behind the last; kind CHAIN_RUNSUM: v_rin, lane l: the sum in front of chunk base + l.
+// dual_of(code): the slot a dual chunk's scans were left in.
+template <class A, class I, class DUAL>
+__device__ __forceinline__ float uws_walk_summaries(const A& a, I n, int base, int nl, int v_code, unsigned v_d0,
+                                                    unsigned v_d1, DUAL dual_of, float r, float& v_rin) {
+  const int kind = a.kind;
+  const int lane = threadIdx.x & 63;
+  int c = base == 0 ? 1 : 0;
+  while (c < nl) {
+    const unsigned rb = __float_as_uint(r);
+    const int re = (int)(rb >> 23);
+    const unsigned R = (rb & 0x7FFFFFu) | 0x800000u;
+    bool overflow = false;   // chunk c was predicted to stay in this binade and does not
+    // the run of chunks from c on that were summarised in the binade the sum is in: one scan of their pairs (plain
+    // sums when none of them holds a rounding tie) carries the sum through all of them
+    const unsigned long long other = ~__ballot(lane < nl && v_code == re) & (~0ull << c);
+    const int cend = other ? __ffsll((long long)other) - 1 : 64;   // the run is [c, cend)
+    if (cend > c) {
+      const bool in_run = lane >= c && lane < cend;
+      unsigned after;   // lane l: mantissa behind chunk l, while below 2^24
+      if (__ballot(in_run && v_d0 != v_d1) == 0ull) {
+        after = R + uws_wave_scan_u(in_run ? v_d0 : 0u);
+      } else {
+        const PfxPair in = pfx_pair_wave_scan(in_run ? PfxPair{v_d0, v_d1} : PfxPair{0u, 0u});
+        after = R + ((R & 1u) ? in.a1 : in.a0);
+      }
+      const unsigned long long cross = __ballot(in_run && after >= (1u << 24));
+      const int c1 = cross ? __ffsll((long long)cross) - 1 : cend;   // chunks [c, c1) are taken
+      if (kind == CHAIN_RUNSUM) {
+        const unsigned prev = (unsigned)__builtin_amdgcn_update_dpp(0, (int)after, 0x138, 0xF, 0xF, false);   // wave_shr:1
+        if (lane >= c && lane < c1) v_rin = lane == c ? r : chain_mant((unsigned)re, prev);
+      }
+      if (c1 > c) r = chain_mant((unsigned)re, (unsigned)__builtin_amdgcn_readlane((int)after, c1 - 1));
+#ifdef TDR_UW_TIMELINE
+      if (threadIdx.x == 0) g_uw_tl[12] += c1 - c;
+#endif
+      c = c1;
+      if (c1 == cend) continue;
+      overflow = true;
+    }
+    const I lo = (I)(base + c) * UWS_WC;
+    const int cnt = (int)min((I)UWS_WC, n - lo);
+    const int code = __builtin_amdgcn_readlane(v_code, c);
+    if (kind == CHAIN_RUNSUM) v_rin = (lane == c) ? r : v_rin;
+    int pos = 0;
+    const int re_now = (int)(__float_as_uint(r) >> 23);
+    if (!overflow && code >= 0 && re_now <= PFXM_RE_MAX && (code & 0x1FF) == (re_now | UWS_DUAL_FLAG)) {
+      r = uws_wave_dual(a, lo, cnt, r, dual_of(code), pos);
+      UW_COUNT(13);
+    }
+    if (pos < cnt) {
+      UW_COUNT(14);
+      r = uws_wave_walk(a, lo, cnt, r, pos);
+    }
+    c++;
+  }
+  return r;
+}
 // sh.csum holds the chunks' double sums and a barrier has passed since they were written; rin (kind 2): the running sum
 // in front of every wave-chunk
 template <class A>
 __device__ __forceinline__ float uws_chain_total_waves(const A& a, int n, UwsShared& sh, float* rin = nullptr) {
   const int kind = a.kind;
   constexpr int NW = UWS_THREADS / 64;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), t0 = lane * CHAIN_K;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwc = (n + UWS_WC - 1) / UWS_WC;   // <= 64
   float r = 0.f;
   if (wave == 0) {
@@ -1491,69 +1692,20 @@ __device__ __forceinline__ float uws_chain_total_waves(const A& a, int n, UwsSha
     {
       const double own = lane < nwc ? sh.csum[lane] : 0.0;
       const double after = uws_wave_scan_d(own), before = after - own;
-      const int re_b = (int)(__float_as_uint((float)before) >> 23), re_a = (int)(__float_as_uint((float)after) >> 23);   // sign included
-      const bool inr = lane >= 1 && lane < nwc && re_b >= PFXM_RE_MIN && re_a <= PFXM_RE_MAX;
-      const bool dualc = inr && re_a == re_b + 1;
-      const unsigned long long dm = __ballot(dualc);
+      bool dualc;
+      const int pred = uws_predict(before, after, dualc);
+      const bool have = lane >= 1 && lane < nwc;
+      const unsigned long long dm = __ballot(have && dualc);
       const int slot = __popcll(dm & ((1ull << lane) - 1ull));
-      my_code = (inr && re_a == re_b) ? re_b : (dualc && slot < UWS_DUAL_SLOTS) ? (re_b | UWS_DUAL_FLAG | (slot << 16)) : -1;
+      my_code = !have ? -1 : !dualc ? pred : slot < UWS_DUAL_SLOTS ? (pred | (slot << 16)) : -1;
     }
     for (int c = wave; c < nwc; c += NW - 1) {   // chunks 1 .. nwc - 1 over waves 1 .. NW - 1
       const int code = __builtin_amdgcn_readlane(my_code, c);
       const int lo = c * UWS_WC, cnt = min(UWS_WC, n - lo);
-      PfxPair P = {0u, 0u}, Q = {0u, 0u};
-      bool anybad = false;
-      if (code >= 0) {
-        const unsigned re = (unsigned)(code & 0xFF);
-        const bool dual = (code & UWS_DUAL_FLAG) != 0;
-        typename A::value_t x[CHAIN_K];   // (all eight reads in flight before the first use)
-        a.load_items(lo, cnt, t0, x);
-        // without a rounding tie in the chunk a lane's pair is (s, s), s the plain sum of its increments
-        bool anytie = false;
-        unsigned f; bool tie, bad;
-#pragma unroll
-        for (int k = 0; k < CHAIN_K; k++) {
-          A::classify(x[k], re, f, tie, bad);
-          anybad |= bad; anytie |= tie;
-          P.a0 += f;   // (CHAIN_BOUND_22: no overflow in a lane, none below 2^31 in a wave)
-        }
-        if (dual) {
-#pragma unroll
-          for (int k = 0; k < CHAIN_K; k++) {
-            A::classify(x[k], re + 1u, f, tie, bad);
-            anybad |= bad; anytie |= tie;
-            Q.a0 += f;
-          }
-        }
-        if (__ballot(anytie) == 0ull) {
-          P.a0 = P.a1 = uws_wave_scan_u(P.a0);
-          if (dual) Q.a0 = Q.a1 = uws_wave_scan_u(Q.a0);
-        } else {
-          // (rare.  The binade is made opaque here so that this branch classifies again instead of keeping the f and tie
-          // of all sixteen classifications above alive across the ballot: 16 VGPRs, and uw_small_kernel<true> has none to spare)
-          unsigned re_t = re;
-          asm volatile("" : "+s"(re_t));
-          P = PfxPair{0u, 0u}; Q = PfxPair{0u, 0u};
-#pragma unroll
-          for (int k = 0; k < CHAIN_K; k++) {
-            A::classify(x[k], re_t, f, tie, bad);
-            P = pfx_compose(P, pfx_element_pair(f, tie));
-          }
-          P = pfx_pair_wave_scan(P);
-          if (dual) {
-#pragma unroll
-            for (int k = 0; k < CHAIN_K; k++) {
-              A::classify(x[k], re_t + 1u, f, tie, bad);
-              Q = pfx_compose(Q, pfx_element_pair(f, tie));
-            }
-            Q = pfx_pair_wave_scan(Q);
-          }
-        }
-        if (dual) sh.dual[code >> 16][lane] = make_uint4(P.a0, P.a1, Q.a0, Q.a1);
-      }
-      const bool ok = code >= 0 && __ballot(anybad) == 0ull;
+      PfxPair P = {0u, 0u};
+      const bool ok = code >= 0 && uws_wave_summary(a, lo, cnt, code, sh.dual[(code >> 16) & (UWS_DUAL_SLOTS - 1)], P);
       if (lane == 63) {
-        sh.code[c] = (ok && ((code & UWS_DUAL_FLAG) || (P.a0 < (1u << 24) && P.a1 < (1u << 24)))) ? code : -1;
+        sh.code[c] = uws_summary_code(code, ok, P);
         sh.d0[c] = P.a0; sh.d1[c] = P.a1;
       }
     }
@@ -1561,57 +1713,11 @@ __device__ __forceinline__ float uws_chain_total_waves(const A& a, int n, UwsSha
   pfx_sync();
   UW_STAMP(kind ? 5 : 2);
   if (wave == 0) {   // the walk
-    const int v_code = (lane >= 1 && lane < nwc) ? sh.code[lane] : -1;
-    const unsigned v_d0 = (lane >= 1 && lane < nwc) ? sh.d0[lane] : 0u, v_d1 = (lane >= 1 && lane < nwc) ? sh.d1[lane] : 0u;
+    const bool have = lane >= 1 && lane < nwc;
+    const int v_code = have ? sh.code[lane] : -1;
+    const unsigned v_d0 = have ? sh.d0[lane] : 0u, v_d1 = have ? sh.d1[lane] : 0u;
     float v_rin = 0.f;   // lane c: the running sum in front of chunk c
-    int c = 1;
-    while (c < nwc) {
-      const unsigned rb = __float_as_uint(r);
-      const int re = (int)(rb >> 23);
-      const unsigned R = (rb & 0x7FFFFFu) | 0x800000u;
-      bool overflow = false;   // chunk c was predicted to stay in this binade and does not
-      // the run of chunks from c on that were summarised in the binade the sum is in: one scan of their pairs (plain
-      // sums when none of them holds a rounding tie) carries the sum through all of them
-      const unsigned long long other = ~__ballot(lane < nwc && v_code == re) & (~0ull << c);
-      const int cend = other ? __ffsll((long long)other) - 1 : 64;   // the run is [c, cend)
-      if (cend > c) {
-        const bool in_run = lane >= c && lane < cend;
-        unsigned after;   // lane l: mantissa behind chunk l, while below 2^24
-        if (__ballot(in_run && v_d0 != v_d1) == 0ull) {
-          after = R + uws_wave_scan_u(in_run ? v_d0 : 0u);
-        } else {
-          const PfxPair in = pfx_pair_wave_scan(in_run ? PfxPair{v_d0, v_d1} : PfxPair{0u, 0u});
-          after = R + ((R & 1u) ? in.a1 : in.a0);
-        }
-        const unsigned long long cross = __ballot(in_run && after >= (1u << 24));
-        const int c1 = cross ? __ffsll((long long)cross) - 1 : cend;   // chunks [c, c1) are taken
-        if (kind == CHAIN_RUNSUM) {
-          const unsigned prev = (unsigned)__builtin_amdgcn_update_dpp(0, (int)after, 0x138, 0xF, 0xF, false);   // wave_shr:1
-          if (lane >= c && lane < c1) v_rin = lane == c ? r : chain_mant((unsigned)re, prev);
-        }
-        if (c1 > c) r = chain_mant((unsigned)re, (unsigned)__builtin_amdgcn_readlane((int)after, c1 - 1));
-#ifdef TDR_UW_TIMELINE
-        if (threadIdx.x == 0) g_uw_tl[12] += c1 - c;
-#endif
-        c = c1;
-        if (c1 == cend) continue;
-        overflow = true;
-      }
-      const int lo = c * UWS_WC, cnt = min(UWS_WC, n - lo);
-      const int code = __builtin_amdgcn_readlane(v_code, c);
-      if (kind == CHAIN_RUNSUM) v_rin = (lane == c) ? r : v_rin;
-      int pos = 0;
-      const int re_now = (int)(__float_as_uint(r) >> 23);
-      if (!overflow && code >= 0 && re_now <= PFXM_RE_MAX && (code & 0x1FF) == (re_now | UWS_DUAL_FLAG)) {
-        r = uws_wave_dual(a, lo, cnt, r, sh.dual[code >> 16], pos);
-        UW_COUNT(13);
-      }
-      if (pos < cnt) {
-        UW_COUNT(14);
-        r = uws_wave_walk(a, lo, cnt, r, pos);
-      }
-      c++;
-    }
+    r = uws_walk_summaries(a, n, 0, nwc, v_code, v_d0, v_d1, [&](int code) { return sh.dual[code >> 16]; }, r, v_rin);
     if (kind == CHAIN_RUNSUM) rin[lane] = v_rin;
     if (lane == 0) sh.total = r;
   }
@@ -1855,10 +1961,10 @@ struct PfsShared {
   float cmax[64];   // largest running sum inside it (NaN skipped)
   int irregular;    // a negative or NaN weight exists: the running sum is not its own running maximum
 };
-// wave-chunk [lo, lo + cnt) from its exact starting sum r: every addend's running sum, in place of the weight
-__device__ __forceinline__ void pfs_wave_fill(int lo, int cnt, float r) {
-  extern __shared__ float uws_lraw[];
-  const UwsAddF a{{}, CHAIN_RUNSUM, 0.f};
+// wave-chunk [lo, lo + cnt) from its exact starting sum r: the running sum behind each of the lane's addends (one scan, a
+// second one behind a crossing)
+template <class A, class I>
+__device__ __forceinline__ void chain_wave_fill(const A& a, I lo, int cnt, float r, float (&pv)[CHAIN_K]) {
   const int t0 = (threadIdx.x & 63) * CHAIN_K;
   float x[CHAIN_K];
   a.load_items(lo, cnt, t0, x);
@@ -1867,13 +1973,21 @@ __device__ __forceinline__ void pfs_wave_fill(int lo, int cnt, float r) {
   for (int k = 0; k < CHAIN_K; k++) sink.pv[k] = 0.f;
   (void)chain_walk(a, x, t0, 0, cnt, r, ChainWave<true>{}, sink);
 #pragma unroll
+  for (int k = 0; k < CHAIN_K; k++) pv[k] = sink.pv[k];
+}
+// ... out of the LDS image, in place of the weight
+__device__ __forceinline__ void pfs_wave_fill(int lo, int cnt, float r) {
+  extern __shared__ float uws_lraw[];
+  const int t0 = (threadIdx.x & 63) * CHAIN_K;
+  float pv[CHAIN_K];
+  chain_wave_fill(UwsAddF{{}, CHAIN_RUNSUM, 0.f}, lo, cnt, r, pv);
+#pragma unroll
   for (int k = 0; k < CHAIN_K; k++)
-    if (t0 + k < cnt) uws_lraw[uws_idx(lo + t0 + k)] = sink.pv[k];
+    if (t0 + k < cnt) uws_lraw[uws_idx(lo + t0 + k)] = pv[k];
 }
 // the one-workgroup running sum / running maximum: the body of pfx_small_kernel and of pfx_small_batch_kernel
 __device__ __forceinline__ void pfx_small_body(const float* __restrict__ w, int n, float* __restrict__ runmax,
-                                               float* __restrict__ prefix_opt,
-                                               float* __restrict__ tail) {   // tail (optional): sum, maximum
+                                               float* __restrict__ prefix_opt) {
   extern __shared__ float uws_lraw[];
   float* const lraw = uws_lraw;
   __shared__ PfsShared sh;
@@ -1901,12 +2015,11 @@ __device__ __forceinline__ void pfx_small_body(const float* __restrict__ w, int 
   }
   if (__ballot(irr) != 0ull && lane == 0) atomicOr(&sh.irregular, 1);
   pfx_sync();
-  const float total = uws_chain_total_waves(UwsAddF{{}, CHAIN_RUNSUM, 0.f}, n, sh.u, sh.rin);   // (ends in a barrier)
+  (void)uws_chain_total_waves(UwsAddF{{}, CHAIN_RUNSUM, 0.f}, n, sh.u, sh.rin);   // (ends in a barrier)
   // every chunk again from its exact starting sum (the first one was filled by the head)
   for (int c = 1 + wave; c < nwc; c += NW) pfs_wave_fill(c * UWS_WC, min(UWS_WC, n - c * UWS_WC), sh.rin[c]);
   pfx_sync();
   if (sh.irregular == 0) {   // the running sum never falls: it is its own running maximum
-    if (tail && tid == 0) { tail[0] = total; tail[1] = total; }
     for (int i = tid; i < n; i += nt) {
       const float v = lraw[uws_idx(i)];
       runmax[i] = v;
@@ -1928,7 +2041,6 @@ __device__ __forceinline__ void pfx_small_body(const float* __restrict__ w, int 
   }
   pfx_sync();
   const float before = pfs_wave_scan_max(lane < nwc ? sh.cmax[lane] : -INFINITY);   // lane c: maximum up to chunk c's end
-  if (tail && tid == 63) { tail[0] = total; tail[1] = before; }
   for (int c = wave; c < nwc; c += NW) {
     const int lo = c * UWS_WC, cnt = min(UWS_WC, n - lo);
     const float carry = c > 0 ? __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(before), c - 1)) : -INFINITY;
@@ -1951,37 +2063,17 @@ __device__ __forceinline__ void pfx_small_body(const float* __restrict__ w, int 
       }
   }
 }
-// The summary blocks of the two head kernels (pfx_small_kernel, chain_head_kernel): the waves above the summary's thread
-// count return at once and the others run chain_summary_body, barriers included.  That is sound because the cut falls on
-// whole waves (asserted here) and a wave that has ended no longer counts at the workgroup's s_barrier on this hardware.
-// Such a block is launched with the head's 1024 threads and its dynamic LDS (up to 132 KB) without using either, so one
-// fits a CU: 17 blocks at 100 000 weights; the 481 of 2 million weights take two rounds over 256 CUs.
-static_assert(PFXM_THREADS % 64 == 0 && PFXW_THREADS % 64 == 0 && PFXM_THREADS <= UWS_THREADS && PFXW_THREADS <= UWS_THREADS,
-              "summary blocks: whole waves of the head's workgroup");
-// Block 0: the one-workgroup running sum over w[0, n).  Further blocks (prefix_multi only, where these n weights are the
-// head of n_all): block b summarises chunk c_first + b - 1 of the whole array (pfx_chunk_summary_kernel's body, on its
-// PFXM_THREADS threads) — it needs the chunk sums and nothing of the head, so it runs in the head's shadow.
 __global__ __launch_bounds__(UWS_THREADS) void pfx_small_kernel(const float* __restrict__ w, int n,
-                                                                float* __restrict__ runmax, float* __restrict__ prefix_opt,
-                                                                float* __restrict__ tail, int64_t n_all,
-                                                                PfxChunk* __restrict__ ch, int c_first) {
-  if (blockIdx.x > 0) {
-    if (threadIdx.x < PFXM_THREADS)
-      chain_summary_body<PFXM_THREADS, PFXM_K>(PfxRunSum{{w}, CHAIN_RUNSUM, 0.f}, n_all, ch, c_first - 1);
-    return;
-  }
-  pfx_small_body(w, n, runmax, prefix_opt, tail);
+                                                                float* __restrict__ runmax, float* __restrict__ prefix_opt) {
+  pfx_small_body(w, n, runmax, prefix_opt);
 }
 // batched filters (tdr_batch_step): workgroup k = filter k of the table
 __global__ __launch_bounds__(UWS_THREADS) void pfx_small_batch_kernel(const TdrBatchEntry* __restrict__ tab) {
   const TdrBatchEntry& e = tab[blockIdx.x];
-  pfx_small_body(e.w_out, (int)e.n, e.runmax_out, nullptr, nullptr);
+  pfx_small_body(e.w_out, (int)e.n, e.runmax_out, nullptr);
 }
 #define TDR_PFX_SMALL_MAX_N 32768
-// tail, n_all, ch, nch: prefix_multi's head — the sum and the maximum behind the n weights go to tail, and the launch also
-// summarises the chunks [n / PFXM_CHUNK, nch) of the n_all weights
-static int pfx_small(const float* w, int64_t n, float* runmax, float* prefix_opt, hipStream_t st, float* tail = nullptr,
-                     int64_t n_all = 0, PfxChunk* ch = nullptr, int nch = 0) {
+static int pfx_small(const float* w, int64_t n, float* runmax, float* prefix_opt, hipStream_t st) {
   if (n < 1 || n > TDR_PFX_SMALL_MAX_N) return fail(TDR_ERR_ARG, "pfx_small: n out of range");
   const size_t lds = ((size_t)n + (size_t)(n >> 5) + 1 + UWS_PAD) * sizeof(float);
   static bool attr_set[64] = {false};   // per device: the attribute lives with the device's copy of the code object
@@ -1993,106 +2085,196 @@ static int pfx_small(const float* w, int64_t n, float* runmax, float* prefix_opt
       return fail(TDR_ERR_HIP, "pfx_small: cannot raise the dynamic LDS limit");
     if (dev < 64) attr_set[dev] = true;
   }
-  const int c_first = ch ? (int)(n / PFXM_CHUNK) : 0;
-  hipLaunchKernelGGL(pfx_small_kernel, dim3(1 + (ch ? (unsigned)std::max(0, nch - c_first) : 0u)), dim3(UWS_THREADS), lds,
-                     st, w, (int)n, runmax, prefix_opt, tail, n_all, ch, c_first);
+  hipLaunchKernelGGL(pfx_small_kernel, dim3(1), dim3(UWS_THREADS), lds, st, w, (int)n, runmax, prefix_opt);
   return TDR_OK;
 }
 
-// The head of a statistics chain over more than 32 768 weights: its first n_head addends (whole 4096-chunks, at most
-// 32 768) staged into LDS and summed by uws_chain_total_waves; the chunk walk of chain_walk_kernel starts behind them.
-// Further blocks: block b summarises chunk c_first + b - 1 of all n_all weights (chain_summary_kernel's body, on its
-// PFXW_THREADS threads): it needs the chunk sums and nothing of the head, so it runs in the head's shadow.
+// ==== the long chains at wave-chunk grain, over the chip (n > 32 768) =====================================================
+// uws_chain_total_waves' algorithm with the addends in memory instead of an LDS image, and the chip instead of one CU:
+//   1. the pass that reads every addend before the chain (uw_chunk_pass1 / _pass2, chain_sum_kernel, pfx_chunk_sum_kernel)
+//      leaves the double sum of every wave-chunk in its WcRec beside the 4096-chunks' sums, and zeroes the slot counter;
+//   2. chain_grid_summary_kernel, one wave per wave-chunk c >= 1: the double sum in front of the chunk (the 4096-chunk sums
+//      before it, then the wave-chunks of its own 4096-chunk) -> uws_predict -> uws_wave_summary.  A chunk predicted to
+//      cross draws a dual slot from the counter (UWG_DUAL_SLOTS; beyond them it is simply carried through);
+//   3. chain_grid_walk_kernel / pfx_grid_walk_kernel, ONE wave: the first wave-chunk one by one (chain_head_lanes), then
+//      uws_walk_summaries over the records, 64 at a time — the sum is all that passes from one 64 to the next, so a run of
+//      chunks in one binade simply goes on.  The running sum notes the exact sum in front of every wave-chunk (WcRec::rin);
+//   4. pfx_grid_fill_kernel (running sum only), one wave per wave-chunk: chain_wave_fill from rin, straight to the outputs.
+// The running maximum is the running sum itself while no weight is negative or NaN.  An input that holds one (irr[], left
+// by pass 1) takes the 4096-chunk path wholesale instead, inside the same three launches: the summary launch runs
+// chain_summary_body on its first nch workgroups, the walk launch pfx_walk_body, the fill launch pfx_chunk_fill_body.
+#define UWG_WAVES (PFXM_THREADS / 64)   // waves per workgroup of the summary and fill launches (whose workgroups may have to
+                                        // run the 4096-chunk bodies: PFXM_THREADS)
+using GridAddF = ChainAddend<float, ChainGlobal, CHAIN_BOUND_22>;   // CHAIN_SUM, CHAIN_RUNSUM
+using GridAddD = ChainAddend<double, ChainGlobal, CHAIN_BOUND_22>;  // CHAIN_BOTTOM
+// any flag among irr[0, nch)?  (wave-uniform)
+__device__ __forceinline__ bool pfx_grid_irregular(const int* __restrict__ irr, int nch) {
+  int f = 0;
+  for (int j = threadIdx.x & 63; j < nch; j += 64) f |= irr[j];
+  return __ballot(f != 0) != 0ull;
+}
+template <class A>
+__device__ __forceinline__ void chain_grid_summary(const A& a, int64_t n, const ChainGridWs& ws) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long nwc = ((long long)n + UWS_WC - 1) / UWS_WC;
+  const long long c = 1 + (long long)blockIdx.x * UWG_WAVES + wave;
+  if (c >= nwc) return;
+  constexpr int PER = PFXM_CHUNK / UWS_WC;   // wave-chunks per chunk
+  const int cc = (int)(c / PER);
+  double acc = 0.0;
+  for (int j = lane; j < cc; j += 64) acc += ws.ch[j].sum;
+  if (lane < (int)(c - (long long)cc * PER)) acc += ws.wc[(long long)cc * PER + lane].sum;
+  const double before = uws_readlane_d(uws_wave_scan_d(acc), 63);
+  bool dualc;
+  int code = uws_predict(before, before + ws.wc[c].sum, dualc);
+  if (dualc) {   // (wave-uniform)
+    int slot = 0;
+    if (lane == 0) slot = atomicAdd(&ws.ctl->slots, 1);
+    slot = __builtin_amdgcn_readfirstlane(slot);
+    code = slot < UWG_DUAL_SLOTS ? (code | (slot << 16)) : -1;
+  }
+  const long long lo = c * UWS_WC;
+  const int cnt = (int)min((long long)UWS_WC, (long long)n - lo);
+  PfxPair P = {0u, 0u};
+  const bool ok = code >= 0 && uws_wave_summary(a, lo, cnt, code, ws.dual + (size_t)(code >> 16) * 64, P);
+  if (lane == 63) {
+    WcRec* o = ws.wc + c;
+    o->code = uws_summary_code(code, ok, P);
+    o->d0 = P.a0; o->d1 = P.a1;
+  }
+}
+// the walking wave: returns the chain's total; kind CHAIN_RUNSUM: keep(i, v) takes the sums behind the first wave-chunk's addends
+template <class A, class PUT>
+__device__ __forceinline__ float chain_grid_walk(const A& a, int64_t n, const ChainGridWs& ws, PUT keep) {
+  const int lane = threadIdx.x & 63;
+  const long long nwc = ((long long)n + UWS_WC - 1) / UWS_WC;
+  const int hn = (int)min((long long)UWS_WC, (long long)n);
+  float r = a.kind == CHAIN_RUNSUM ? chain_head_lanes<true>(a, hn, keep) : chain_head_lanes<false>(a, hn, keep);
+  for (long long base = 0; base < nwc; base += 64) {
+    const int nl = (int)min(64ll, nwc - base);
+    const bool have = lane < nl && base + lane >= 1;
+    const WcRec* rec = ws.wc + base + lane;
+    const int v_code = have ? rec->code : -1;
+    const unsigned v_d0 = have ? rec->d0 : 0u, v_d1 = have ? rec->d1 : 0u;
+    float v_rin = 0.f;
+    r = uws_walk_summaries(a, (long long)n, (int)base, nl, v_code, v_d0, v_d1,
+                           [&](int code) { return ws.dual + (size_t)(code >> 16) * 64; }, r, v_rin);
+    if (a.kind == CHAIN_RUNSUM && have) ws.wc[base + lane].rin = v_rin;
+  }
+  return r;
+}
 template <int KIND>
-__global__ __launch_bounds__(UWS_THREADS) void chain_head_kernel(const float* __restrict__ raw, const float* __restrict__ mean_dev,
-                                                                 int n, float* __restrict__ r_out, int64_t n_all,
-                                                                 PfxChunk* __restrict__ ch, int c_first) {
-  const float mean = KIND ? *mean_dev : 0.f;
-  if (blockIdx.x > 0) {
-    if (threadIdx.x < PFXW_THREADS)
-      chain_summary_body<PFXW_THREADS, CHAIN_K>(ChainStat{{raw}, KIND, mean}, n_all, ch, c_first - 1);
+__global__ __launch_bounds__(PFXM_THREADS) void chain_grid_summary_kernel(const float* __restrict__ raw,
+                                                                          const float* __restrict__ mean_dev, int64_t n,
+                                                                          ChainGridWs ws) {
+  if constexpr (KIND == CHAIN_SUM) chain_grid_summary(GridAddF{{raw}, CHAIN_SUM, 0.f}, n, ws);
+  else chain_grid_summary(GridAddD{{raw}, CHAIN_BOTTOM, *mean_dev}, n, ws);
+}
+template <int KIND>
+__global__ __launch_bounds__(64) void chain_grid_walk_kernel(const float* __restrict__ raw, const float* __restrict__ mean_dev,
+                                                             int64_t n, ChainGridWs ws, float* __restrict__ total_out) {
+  float r;
+  if constexpr (KIND == CHAIN_SUM) r = chain_grid_walk(GridAddF{{raw}, CHAIN_SUM, 0.f}, n, ws, [](int, float) {});
+  else r = chain_grid_walk(GridAddD{{raw}, CHAIN_BOTTOM, *mean_dev}, n, ws, [](int, float) {});
+  if (threadIdx.x == 0) *total_out = r;
+}
+static unsigned chain_grid_blocks(int64_t n) { return (unsigned)cdiv(cdiv(n, (int64_t)UWS_WC), (int64_t)UWG_WAVES); }
+static void chain_grid_total(const ChainSrc& s, int64_t n, float* total_out, const ChainGridWs& ws, hipStream_t st) {
+  const dim3 grid(chain_grid_blocks(n));   // (chunk 0 has no summary: the last workgroup may have a wave to spare)
+  if (s.kind == CHAIN_SUM) {
+    hipLaunchKernelGGL(chain_grid_summary_kernel<CHAIN_SUM>, grid, dim3(PFXM_THREADS), 0, st, s.raw, s.mean, n, ws);
+    hipLaunchKernelGGL(chain_grid_walk_kernel<CHAIN_SUM>, dim3(1), dim3(64), 0, st, s.raw, s.mean, n, ws, total_out);
+  } else {
+    hipLaunchKernelGGL(chain_grid_summary_kernel<CHAIN_BOTTOM>, grid, dim3(PFXM_THREADS), 0, st, s.raw, s.mean, n, ws);
+    hipLaunchKernelGGL(chain_grid_walk_kernel<CHAIN_BOTTOM>, dim3(1), dim3(64), 0, st, s.raw, s.mean, n, ws, total_out);
+  }
+}
+// the running sum's three launches behind pfx_chunk_sum_kernel
+__global__ __launch_bounds__(PFXM_THREADS) void pfx_grid_summary_kernel(const float* __restrict__ w, int64_t n, ChainGridWs ws,
+                                                                        int nch) {
+  if (pfx_grid_irregular(ws.irr, nch)) {   // (the same answer in every wave of the launch)
+    if ((int)blockIdx.x < nch) chain_summary_body<PFXM_THREADS, PFXM_K>(PfxRunSum{{w}, CHAIN_RUNSUM, 0.f}, n, ws.ch);
     return;
   }
-  extern __shared__ float uws_lraw[];
-  __shared__ UwsShared ush;
-  const int tid = threadIdx.x, lane = tid & 63, nwc = (n + UWS_WC - 1) / UWS_WC;
-  for (int c = tid >> 6; c < nwc; c += UWS_THREADS / 64) {
-    const int base = c * UWS_WC + lane;
-    float v[CHAIN_K];
-#pragma unroll
-    for (int m = 0; m < CHAIN_K; m++) v[m] = base + 64 * m < n ? raw[base + 64 * m] : __uint_as_float(0x7FC00000u);
-    double acc = 0;
-#pragma unroll
-    for (int m = 0; m < CHAIN_K; m++) {
-      if (base + 64 * m < n) uws_lraw[uws_idx(base + 64 * m)] = v[m];
-      const bool take = KIND == 0 ? v[m] == v[m] : (v[m] == v[m] && v[m] < mean);
-      double x = (double)(KIND == 0 ? v[m] : v[m] - mean);
-      if (KIND) x = x * x;
-      acc += take ? x : 0.0;
+  chain_grid_summary(GridAddF{{w}, CHAIN_RUNSUM, 0.f}, n, ws);
+}
+__global__ __launch_bounds__(PFXW_THREADS) void pfx_grid_walk_kernel(const float* __restrict__ w, int64_t n, ChainGridWs ws,
+                                                                    int nch, float* __restrict__ runmax,
+                                                                    float* __restrict__ prefix_opt, int head_len) {
+  const bool irregular = pfx_grid_irregular(ws.irr, nch);
+  if (threadIdx.x == 0) ws.ctl->irregular = irregular ? 1 : 0;   // for the fill (the walk overwrites nothing it has read from)
+  if (irregular) {
+    pfx_walk_body(w, n, ws.ch, nch, runmax, prefix_opt, head_len);
+    return;
+  }
+  if (threadIdx.x >= 64) return;   // one wave walks
+  (void)chain_grid_walk(GridAddF{{w}, CHAIN_RUNSUM, 0.f}, n, ws, [&](int i, float v) {
+    runmax[i] = v;
+    if (prefix_opt) prefix_opt[i] = v;
+  });
+}
+__global__ __launch_bounds__(PFXM_THREADS) void pfx_grid_fill_kernel(const float* __restrict__ w, int64_t n, ChainGridWs ws,
+                                                                    int nch, float* __restrict__ runmax,
+                                                                    float* __restrict__ prefix_opt) {
+  if (ws.ctl->irregular) {
+    if ((int)blockIdx.x < nch) pfx_chunk_fill_body(w, n, ws.ch, (int)blockIdx.x, runmax, prefix_opt);
+    return;
+  }
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), t0 = lane * CHAIN_K;
+  const long long c = (long long)blockIdx.x * UWG_WAVES + wave;
+  const long long lo = c * UWS_WC;
+  if (c == 0 || lo >= (long long)n) return;   // (the first wave-chunk: written by the walking wave's head)
+  const int cnt = (int)min((long long)UWS_WC, (long long)n - lo);
+  float pv[CHAIN_K];
+  chain_wave_fill(GridAddF{{w}, CHAIN_RUNSUM, 0.f}, lo, cnt, ws.wc[c].rin, pv);
+  // no weight is negative or NaN: the running sum never falls and is its own running maximum
+  if (t0 + CHAIN_K <= cnt) {
+    float4* o = reinterpret_cast<float4*>(runmax + lo + t0);
+    o[0] = make_float4(pv[0], pv[1], pv[2], pv[3]);
+    o[1] = make_float4(pv[4], pv[5], pv[6], pv[7]);
+    if (prefix_opt) {
+      float4* q = reinterpret_cast<float4*>(prefix_opt + lo + t0);
+      q[0] = make_float4(pv[0], pv[1], pv[2], pv[3]);
+      q[1] = make_float4(pv[4], pv[5], pv[6], pv[7]);
     }
-    acc = uws_wave_scan_d(acc);
-    if (lane == 63) ush.csum[c] = acc;
+  } else {
+#pragma unroll
+    for (int k = 0; k < CHAIN_K; k++)
+      if (t0 + k < cnt) {
+        runmax[lo + t0 + k] = pv[k];
+        if (prefix_opt) prefix_opt[lo + t0 + k] = pv[k];
+      }
   }
-  pfx_sync();
-  float r;
-  if constexpr (KIND == CHAIN_SUM) r = uws_chain_total_waves(UwsAddF{{}, CHAIN_SUM, 0.f}, n, ush);
-  else r = uws_chain_total_waves(UwsAddD{{}, CHAIN_BOTTOM, mean}, n, ush);
-  if (tid == 0) *r_out = r;
 }
-static int chain_head_launch(const float* raw, const float* mean_dev, int kind, int n_head, float* r_out, int64_t n,
-                             PfxChunk* ch, int nch, hipStream_t st) {
-  const size_t lds = ((size_t)n_head + (size_t)(n_head >> 5) + 1 + UWS_PAD) * sizeof(float);
-  static bool attr_set[64] = {false};   // per device: the attribute lives with the device's copy of the code object
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
-  if (dev >= 64 || !attr_set[dev]) {   // more than the default 64 KB of dynamic LDS
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(chain_head_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            133 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(chain_head_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            133 * 1024) != hipSuccess)
-      return fail(TDR_ERR_HIP, "chain_head: cannot raise the dynamic LDS limit");
-    if (dev < 64) attr_set[dev] = true;
-  }
-  const int c_first = n_head / PFXM_CHUNK;
-  const dim3 grid(1 + (unsigned)std::max(0, nch - c_first));
-  if (kind == 0)
-    hipLaunchKernelGGL(chain_head_kernel<0>, grid, dim3(UWS_THREADS), lds, st, raw, mean_dev, n_head, r_out, n, ch, c_first);
-  else
-    hipLaunchKernelGGL(chain_head_kernel<1>, grid, dim3(UWS_THREADS), lds, st, raw, mean_dev, n_head, r_out, n, ch, c_first);
-  return TDR_OK;
-}
+static_assert(CHAIN_K == 8, "pfx_grid_fill_kernel: two float4 per lane");
 
 // Dispatch (tools/bench_prefix_modes.py on MI355X; us at n = 1k / 4k / 8k / 20k / 100k: one wave 16 / 43 / 84 / 208 /
 // 1036, one workgroup 60 / 129 / 156 / 235 / 417, multi-workgroup 38 / 59 / 53 / 74 / 101):
 #define TDR_PFX_MULTI_MIN_N 6144    // with a workspace: the multi-workgroup scan from here on, one wave below
 #define TDR_PFX_EXACT_MIN_N 24576   // without a workspace: one workgroup from here on, one wave below
 #define TDR_PFX_SMALL_MIN_N 256     // the one-launch kernel from here up to TDR_PFX_SMALL_MAX_N
-extern "C" int64_t tdr_prefix_workspace_bytes(int64_t n) {
-  return n < 1 ? 0 : (int64_t)sizeof(PfxChunk) * cdiv(n, (int64_t)PFXM_CHUNK);
-}
+// (the size does not depend on tdr_config_prefix_small: a workspace serves either path)
+extern "C" int64_t tdr_prefix_workspace_bytes(int64_t n) { return tdr_chain_workspace_bytes(n, n >= CHAIN_GRID_MIN_N); }
 static int prefix_multi(const float* w, int64_t n, float* runmax_out, float* prefix_out, void* workspace,
                         hipStream_t st) {
   const int64_t nch64 = cdiv(n, (int64_t)PFXM_CHUNK);
   if (nch64 > (1 << 24)) return fail(TDR_ERR_ARG, "prefix: n too large");
   const int nch = (int)nch64;
-  PfxChunk* ch = reinterpret_cast<PfxChunk*>(workspace);
-  // the first 32 768 weights through pfx_small_kernel, the chunk walk behind them (see tdr_chain_total)
-  const int c_first = chain_head_chunks(n);
-  // (header slots the walk rewrites only after it has read them; chunk 0's sum is still read by the summaries, which now
-  // run beside the head)
-  float* tail = reinterpret_cast<float*>(&ch[0].r0);
-  static_assert(offsetof(PfxChunk, carry0) == offsetof(PfxChunk, r0) + sizeof(float), "tail: sum, maximum");
-  hipLaunchKernelGGL(pfx_chunk_sum_kernel, dim3(nch), dim3(PFXM_THREADS), 0, st, w, n, ch);
-  if (c_first > 0) {   // head and the summaries behind it in one launch
-    const int rc = pfx_small(w, (int64_t)c_first * PFXM_CHUNK, runmax_out, prefix_out, st, tail, n, ch, nch);
-    if (rc) return rc;
-  } else if (nch > c_first) {
-    hipLaunchKernelGGL(pfx_chunk_summary_kernel, dim3(nch - c_first), dim3(PFXM_THREADS), 0, st, w, n, ch, c_first);
-  }
   const int head_len = tdr_cfg().pfx_head;
-  hipLaunchKernelGGL(pfx_walk_kernel, dim3(1), dim3(PFXW_THREADS), 0, st, w, n, ch, nch, runmax_out, prefix_out,
-                     head_len, c_first, (const float*)tail);
-  hipLaunchKernelGGL(pfx_chunk_fill_kernel, dim3(nch), dim3(PFXM_THREADS), 0, st, w, n, (const PfxChunk*)ch,
+  const bool grid = tdr_chain_grid(n);
+  const ChainGridWs ws = chain_grid_ws(workspace, n, grid);
+  hipLaunchKernelGGL(pfx_chunk_sum_kernel, dim3(nch), dim3(PFXW_THREADS), 0, st, w, n, ws);
+  if (grid) {
+    const dim3 blocks(std::max(chain_grid_blocks(n), (unsigned)nch));   // (nch: the 4096-chunk bodies of an irregular input)
+    hipLaunchKernelGGL(pfx_grid_summary_kernel, blocks, dim3(PFXM_THREADS), 0, st, w, n, ws, nch);
+    hipLaunchKernelGGL(pfx_grid_walk_kernel, dim3(1), dim3(PFXW_THREADS), 0, st, w, n, ws, nch, runmax_out, prefix_out,
+                       head_len);
+    hipLaunchKernelGGL(pfx_grid_fill_kernel, blocks, dim3(PFXM_THREADS), 0, st, w, n, ws, nch, runmax_out, prefix_out);
+    return TDR_OK;
+  }
+  hipLaunchKernelGGL(pfx_chunk_summary_kernel, dim3(nch), dim3(PFXM_THREADS), 0, st, w, n, ws.ch);
+  hipLaunchKernelGGL(pfx_walk_kernel, dim3(1), dim3(PFXW_THREADS), 0, st, w, n, ws.ch, nch, runmax_out, prefix_out, head_len);
+  hipLaunchKernelGGL(pfx_chunk_fill_kernel, dim3(nch), dim3(PFXM_THREADS), 0, st, w, n, (const PfxChunk*)ws.ch,
                      runmax_out, prefix_out);
   return TDR_OK;
 }
