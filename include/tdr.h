@@ -640,9 +640,10 @@ int tdr_profile_su_list(int64_t out[2]);
  *                      tdr_config_shift_uniform(2), where the knobs hold on every shape)
  *   "su_tail_parts"    Q: into how many sector ranges each of them is cut — 1, 2, 4 or 8 (another value: the next lower of
  *                      these).  K = 0 or Q = 1 is the launch without tail units.  Integer sums: same bits for every K, Q.
- *                      A dense slot then has (groups - K) + K Q rows of partial sums, and tdr_score_workspace_floats GROWS
- *                      with them (nothing is clamped: K up to every group, Q up to 8) — like "su_group", set both BEFORE
- *                      the workspace of a call is sized (default 4).  Where tail units apply and the shapes allow, the ring
+ *                      The grid then has (groups - K) + K Q rows; each adds its share of a slot's integer sums in place, into
+ *                      the one row of sums a slot has.  tdr_score_workspace_floats still GROWS with the rows (nothing is
+ *                      clamped: K up to every group, Q up to 8) — like "su_group", set both BEFORE the workspace of a call
+ *                      is sized (default 4).  Where tail units apply and the shapes allow, the ring
  *                      groups are 16 rings instead of 8 ("su_group" = 0)
  *   "su_order_bucket"  1 (default): the heading order of an integer-form launch (and the dense / scattered order of the
  *                      Cartesian one) is a one-pass stable bucket sort wherever its table of one word per (512 positions,

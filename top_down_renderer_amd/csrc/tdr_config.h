@@ -22,7 +22,8 @@ struct TdrConfig {
   // Tail units (tdr_su_tail): the last K ring groups of a launch go as Q short rows each.  Defaults from the sweep K in {0, 1,
   // 2, 3, 4, 8} x Q in {2, 4, 8} x groups of 8 / 16 / 32 rings: 16 rings, K = 4, Q = 4 — the last 64 of config
   // 2's 256 rings go as rows of 16 rings x 2 sectors: config 2 4.47 -> 4.32 ms a step, config 3's shard 5.57 -> 5.40, config
-  // 5's 13.87 -> 13.62.
+  // 5's 13.87 -> 13.62.  (That sweep priced every row with a pass of the finalize over its partial sums; the sums are added in
+  // place since — tdr_score_int_dev.h — and rows are free there: the sweep has not been redone)
   int su_tail_groups = 4, su_tail_parts = 4;
   int su_order_bucket = 1;   // 0: the heading order always through rocPRIM's sort (A/B; su_seg_table_words has the rule)
   int su_full_list = 1;      // 0: the assembly loop hands a step with a several-class bin to the C++ step (A/B, tests; same bits)

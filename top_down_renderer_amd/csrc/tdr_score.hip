@@ -531,12 +531,11 @@ struct FinalizeArgs {
   int only_uninit = 0;  // mode 1: slots whose particle already has a heading are left alone
   int tlog = 0;         // 2^tlog neighbouring lanes share a slot's chunks (launch_finalize)
   const int32_t* run_if = nullptr;   // optional device words: run only when the integer form is off (see ScoreArgs)
-  // the integer form (score_finalize_exact_kernel): `part` holds 64-bit integer sums
-  const uint32_t* ipart = nullptr;   // [chunks][2 ncls + 2][npad]
+  // the integer form (score_finalize_exact_kernel): the head of `part` holds the launch's integer sums
+  const uint32_t* ipart = nullptr;   // [2 ncls + 2][npad]: int_add_sums (tdr_score_int_dev.h)
   const uint32_t* dict_tail = nullptr;   // {q, ...}: a sum is a multiple of 2^-q
-  const int32_t* counts = nullptr;   // {slots of the dense share: nchunks chunk rows each; ...; all slots}: the others have ray_split rows
+  const int32_t* counts = nullptr;   // {slots of the dense share, scattered particles, all slots}
   const int32_t* inexact = nullptr;
-  int ray_split = 1;
 };
 
 // the body of score_finalize_kernel and of score_finalize_batch_kernel, for thread gid of the launch
@@ -652,13 +651,13 @@ __global__ __launch_bounds__(256) void score_finalize_batch_kernel(const Finaliz
   score_finalize_body(a, (int64_t)(blockIdx.x - (unsigned)blk[e]) * blockDim.x + threadIdx.x);
 }
 
-// The integer form of a launch (tdr_score_su.hip, tdr_score_ray.hip): a slot's chunk rows hold, per class, the 64-bit
-// integer sum of count x (distance 2^q) over the chunk's samples, and the normalisation and the known-cell count as
-// integers.  Integer sums are exact: whatever kernel, split or order produced the rows, their total is the same number, and
+// The integer form of a launch (tdr_score_su.hip, tdr_score_ray.hip): per slot and class ONE 64-bit integer sum of count x
+// (distance 2^q) over the window's samples, and the normalisation and the known-cell count as integers — every row of the
+// dense kernel and every wave of the ray-mapped one has added its share in place (int_add_sums, tdr_score_int_dev.h).
+// Integer sums are exact: whatever kernel, split or order produced the shares, their total is the same number, and
 // so is the weight.  dot_c = total 2^-q rounded to float once (the reference: a float sum of float products in Eigen's
-// order, state_particle.cpp:136-138), then the reference's own arithmetic (:136-139, 154, 212).
-// A workgroup = 64 slots x 4 shares of a slot's chunk rows (a large filter has 25 rows of 18 words per slot: one lane per
-// slot walked them one after the other with a quarter of the waves); the shares meet in LDS — integers: any grouping.
+// order, state_particle.cpp:136-138), then the reference's own arithmetic (:136-139, 154, 212).  One thread per slot: it reads
+// 2 ncls + 2 words.
 // A 64-bit total as a double that rounds to float exactly as the total itself does: up to 53 bits the total; past that
 // (double)total would be a rounding of its own, and the float made from it a number rounded TWICE (a total just above the
 // middle of two floats lands ON the middle and goes down) — so the 53 leading bits, the last of them set when any bit below
@@ -670,55 +669,15 @@ __device__ __forceinline__ double u64_to_double_sticky(unsigned long long v) {
   return ldexp((double)kept, drop);
 }
 __global__ __launch_bounds__(256) void score_finalize_exact_kernel(FinalizeArgs a) {
-  __shared__ unsigned long long red[3][TDR_MAX_CLASSES + 2][64];
   if (int_form_off(a.inexact)) return;
-  const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
-  const int64_t nslots = (int64_t)a.counts[2];
-  if ((int64_t)blockIdx.x * 64 >= nslots) return;   // (uniform)
-  const int64_t slot = min((int64_t)blockIdx.x * 64 + lane, nslots - 1);
-  const int rows = 2 * a.ncls + 2;
-  const int nch = slot < (int64_t)a.counts[0] ? a.nchunks : a.ray_split;
-  unsigned long long tot[TDR_MAX_CLASSES], norm = 0, known = 0;
+  const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (slot >= (int64_t)a.counts[2]) return;
+  const unsigned long long* const s64 = reinterpret_cast<const unsigned long long*>(a.ipart) + slot;
+  unsigned long long tot[TDR_MAX_CLASSES];
 #pragma unroll
-  for (int k = 0; k < TDR_MAX_CLASSES; k++) tot[k] = 0;
-  // two chunk rows per step, every word of both loaded before the first is added: a lane has 2 x rows loads in flight
-  // instead of one row's (integers: the same total in any grouping); an odd row count reads its last row twice and adds it once
-  for (int c = t; c < nch; c += 8) {
-    const bool two = c + 4 < nch;
-    const uint32_t* o0 = a.ipart + (int64_t)c * rows * a.npad + slot;
-    const uint32_t* o1 = a.ipart + (int64_t)(two ? c + 4 : c) * rows * a.npad + slot;
-    uint32_t v0[2 * TDR_MAX_CLASSES], v1[2 * TDR_MAX_CLASSES];
-#pragma unroll
-    for (int k = 0; k < 2 * TDR_MAX_CLASSES; k++)
-      if (k < 2 * a.ncls) { v0[k] = o0[(int64_t)k * a.npad]; v1[k] = o1[(int64_t)k * a.npad]; }
-    const uint32_t n0 = o0[(int64_t)(2 * a.ncls) * a.npad], k0 = o0[(int64_t)(2 * a.ncls + 1) * a.npad];
-    const uint32_t n1 = o1[(int64_t)(2 * a.ncls) * a.npad], k1 = o1[(int64_t)(2 * a.ncls + 1) * a.npad];
-#pragma unroll
-    for (int k = 0; k < TDR_MAX_CLASSES; k++)
-      if (k < a.ncls) {
-        tot[k] += (unsigned long long)v0[2 * k] | ((unsigned long long)v0[2 * k + 1] << 32);
-        if (two) tot[k] += (unsigned long long)v1[2 * k] | ((unsigned long long)v1[2 * k + 1] << 32);
-      }
-    norm += n0;
-    known += k0;
-    if (two) { norm += n1; known += k1; }
-  }
-  if (t > 0) {
-#pragma unroll
-    for (int k = 0; k < TDR_MAX_CLASSES; k++)
-      if (k < a.ncls) red[t - 1][k][lane] = tot[k];
-    red[t - 1][TDR_MAX_CLASSES][lane] = norm;
-    red[t - 1][TDR_MAX_CLASSES + 1][lane] = known;
-  }
-  __syncthreads();
-  if (t > 0 || (int64_t)blockIdx.x * 64 + lane >= nslots) return;
-  for (int u = 0; u < 3; u++) {
-#pragma unroll
-    for (int k = 0; k < TDR_MAX_CLASSES; k++)
-      if (k < a.ncls) tot[k] += red[u][k][lane];
-    norm += red[u][TDR_MAX_CLASSES][lane];
-    known += red[u][TDR_MAX_CLASSES + 1][lane];
-  }
+  for (int k = 0; k < TDR_MAX_CLASSES; k++) tot[k] = k < a.ncls ? s64[(int64_t)k * a.npad] : 0ull;
+  const unsigned long long norm = a.ipart[(int64_t)(2 * a.ncls) * a.npad + slot];
+  const unsigned long long known = a.ipart[(int64_t)(2 * a.ncls + 1) * a.npad + slot];
   const int64_t p = a.order[slot];
   if (p < 0) return;   // a padding slot of the shift-uniform order
   const float scale = a.st[TDR_ST_SCALE * a.cap + p];
@@ -855,9 +814,9 @@ static ScoreWs score_ws(int ncls, int nb, int nr, int64_t n, int64_t n_total) {
     w.su_rows = su_tail_plan(w.su_nchunks, w.su_tail_k, w.su_tail_q, -1, &g, &s0, &s1);
   }
   w.npad_part = w.su ? su_npad(std::max<int64_t>(n, 1), nb) : w.npad;
-  // partial sums: [chunks][rows][slots] — float form rf + 1 rows; integer form (tdr_score_su.hip) 2 ncls + 2 rows of
-  // words — su_rows of them for a dense slot, whatever the tail knobs make of the ring groups — and room for the chunk rows
-  // of a scattered particle's window (tdr_score_ray.hip)
+  // partial sums: [chunks][rows][slots] — the float form's rf + 1 rows per chunk.  The integer form (tdr_score_su.hip,
+  // tdr_score_ray.hip) needs ONE block of 2 ncls + 2 rows of words at the head, which every row and wave adds to
+  // (tdr_score_int_dev.h); the sizing still counts a block per row of the grid, as it did when each row wrote its own
   w.off_aux = w.su ? (int64_t)std::max(std::max(w.nchunks, w.su_rows), TDR_RAY_MAX_SPLIT) * std::max(rf + 1, 2 * ncls + 2) * w.npad_part
                    : (int64_t)w.nchunks * (rf + 1) * w.npad_part;
   w.off_utab = w.off_aux + 3 * w.npad + 64;
@@ -1203,17 +1162,14 @@ static FinalizeArgs make_finalize_args(const tdr_map_desc* map, const tdr_filter
   return f;
 }
 // score_finalize_exact_kernel over the integer sums an integer-form launch left at f.part (slot list, device words {dense
-// slots, scattered, both}, the int_form_off words, chunk rows of a dense / of a scattered slot); f then finalizes only what
-// the float kernel had to score
+// slots, scattered, both}, the int_form_off words); f then finalizes only what the float kernel had to score
 static void launch_finalize_exact(FinalizeArgs& f, const tdr_map_desc* map, int64_t npad, const int32_t* slots,
-                                  const int32_t* counts, const int32_t* inexact, int nchunks_dense, int ray_split,
-                                  hipStream_t s) {
+                                  const int32_t* counts, const int32_t* inexact, hipStream_t s) {
   FinalizeArgs fx = f;
   fx.npad = npad; fx.order = slots; fx.counts = counts; fx.inexact = inexact;
   fx.ipart = reinterpret_cast<const uint32_t*>(f.part);
   fx.dict_tail = reinterpret_cast<const uint32_t*>(map->dict) + 2 * TDR_CMAP_MAX_DICT;
-  fx.nchunks = nchunks_dense; fx.ray_split = ray_split;
-  hipLaunchKernelGGL(score_finalize_exact_kernel, dim3((unsigned)cdiv(npad, 64)), dim3(256), 0, s, fx);
+  hipLaunchKernelGGL(score_finalize_exact_kernel, dim3((unsigned)cdiv(npad, 256)), dim3(256), 0, s, fx);
   f.run_if = inexact;
 }
 
@@ -1373,6 +1329,7 @@ extern "C" int tdr_k_score_prep(const tdr_map_desc* map, const float* tab, const
   SuLaunch L = make_su_launch(map, a, rf, uniform_scale, ctx, W, workspace);
   L.uniform_scale = uniform_scale > 0.f;
   L.span = span;
+  L.part = nullptr;   // no scoring kernel behind this preparation: no sums to zero
   hipStream_t s = (hipStream_t)stream;
   if (!workspace) {   // the shapes alone
     return tdr_su_prep_copy_out(L, W.suw, s, layout, nullptr);
@@ -1429,6 +1386,8 @@ extern "C" int tdr_k_score_polar_ctx(const tdr_map_desc* map, const float* tab, 
   // the uniform-scale table: a launch of its own for the float form and in front of the init search; an integer-form call
   // leaves it to its preparation kernel (tdr_su_prepare), which writes the same words
   const bool int_form = int_form_applies(W, map, rf);
+  if (int_form && (reinterpret_cast<uintptr_t>(workspace) & 7) != 0)   // the 64-bit class sums at its head (int_add_sums)
+    return fail(TDR_ERR_ARG, "score: the workspace must be 8-byte aligned");
   int rc = TDR_OK;
   if (int_form && !init_search) {
     a.utab = uniform_scale > 0.f ? workspace + W.off_utab : nullptr;
@@ -1472,7 +1431,7 @@ extern "C" int tdr_k_score_polar_ctx(const tdr_map_desc* map, const float* tab, 
       r.run_if = inexact;
       if ((rc = launch_score(r, map, rf, s, false))) return rc;
     }
-    launch_finalize_exact(f, map, W.npad_part, slots, counts, inexact, W.su_rows, L.ray_split, s);
+    launch_finalize_exact(f, map, W.npad_part, slots, counts, inexact, s);
     LAUNCH_CHECK("score_finalize_exact");
     launch_finalize(f, n, s, true);
   } else {
@@ -1633,6 +1592,8 @@ extern "C" int tdr_k_score_cart(const tdr_map_desc* map, const float* scan_pk, i
       // the integer form: dense particles through the skipping kernel with integer accumulators, scattered ones one wave
       // each through score_cart_ray_kernel; the float skipping kernel behind them for what has no integer form
       int32_t* iws = reinterpret_cast<int32_t*>(desc_ws + tdr_cart_desc_words(rows, cols));
+      if ((reinterpret_cast<uintptr_t>(workspace) & 7) != 0)   // the 64-bit class sums at its head (int_add_sums)
+        return fail(TDR_ERR_ARG, "score_cart: the workspace must be 8-byte aligned");
       // (which particles count as dense: four times the polar launch's span — a Cartesian window is a rotated rectangle of
       // rows x cols cells and neighbours a few dozen cells apart still share most of their lines; measured on config 4, ms per
       // step at 8 / 16 / 32 / 64 cells: 32.6 / 29.2 / 28.8 / 28.5, the float kernel 36.9)
@@ -1656,7 +1617,7 @@ extern "C" int tdr_k_score_cart(const tdr_map_desc* map, const float* scan_pk, i
   FinalizeArgs f = make_finalize_args(map, fp, a.part, a.nchunks, a.npad, (int64_t)rows * cols, st, cap, n, perm, raw_w);
   f.gate.force_on_map = 0;   // the Cartesian definition has no gates (include/tdr.h)
   f.gate.scale_unknown = 0;
-  if (int_form) launch_finalize_exact(f, map, io.npad, io.slots, io.counts, io.flags, io.nchunks_dense, io.ray_split, s);
+  if (int_form) launch_finalize_exact(f, map, io.npad, io.slots, io.counts, io.flags, s);
   launch_finalize(f, n, s);
   LAUNCH_CHECK("score_finalize(cart)");
   return TDR_OK;

@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void score_cart_skip_kernel(CartArgs a) {
   }
   if constexpr (INT) {
     if (real)
-      int_write_sums(reinterpret_cast<uint32_t*>(a.part) + (int64_t)blockIdx.y * (2 * a.ncls + 2) * a.npad + slot, a.npad, a.ncls, acc, inorm, known);
+      int_add_sums(reinterpret_cast<uint32_t*>(a.part), a.npad, slot, a.ncls, acc, inorm, known);
   } else if (slot < a.npad) {
     float* o = a.part + (int64_t)blockIdx.y * (RF + 1) * a.npad + slot;
 #pragma unroll
@@ -527,7 +527,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void s
     }
   }
   if (real)
-    int_write_sums(reinterpret_cast<uint32_t*>(a.part) + (int64_t)blockIdx.y * (2 * a.ncls + 2) * a.npad + slot, a.npad, a.ncls, acc, inorm, known);
+    int_add_sums(reinterpret_cast<uint32_t*>(a.part), a.npad, slot, a.ncls, acc, inorm, known);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -568,7 +568,7 @@ int tdr_cart_skip_launch(CartArgs a, const tdr_map_desc* map, int rf, uint32_t* 
 // the scattered ones — one WAVE per particle, lanes = 64 consecutive window columns of one window row, i.e. 64 cells along a
 // line of the map (the rotation lives in the sampling, src/top_down_map.cpp:367-389): the mapping, the data (class planes,
 // coarse mask plane, integer dictionary) and the loop of score_polar_ray_kernel (tdr_score_ray.hip; the text the two share is
-// in tdr_score_int_dev.h: ray_prologue, ray_list_pass, ray_write_sums; the two halves of a sample stand in both kernels).  The sample offsets are
+// in tdr_score_int_dev.h: ray_prologue, ray_list_pass, ray_add_sums; the two halves of a sample stand in both kernels).  The sample offsets are
 // not a table here but three float operations per coordinate from the particle's rotation, computed per lane exactly like
 // the lane = particle kernels compute them; the scan descriptors are not rotated (shift 0).
 static inline int cart_ray_gq(int cols) { return cols <= 64 ? 1 : (cols <= 128 ? 2 : 4); }
@@ -576,13 +576,16 @@ static inline int cart_ray_blocks(int cols) { return (int)cdiv(cols, 64 * cart_r
 
 // One thread per (window row i, padded column j): the 16-bit descriptor code << 12 | count of bin (i, j) in ray order
 // [((i * blocks + b) * 64 + lane) * GQ + g], the list of bins with several classes or a count >= 4096 (as i << 16 | j), and
-// the two words of int_form_off (see score_prep_kernel, tdr_score_su.hip).
+// the two words of int_form_off (see score_prep_kernel, tdr_score_su.hip).  The launch in front of the scoring kernels: its
+// threads also zero the launch's sums (sums_words words at sums: int_zero_sums, tdr_score_int_dev.h).
 __global__ __launch_bounds__(256) void cart_ray_prep_kernel(const float* __restrict__ scan_pk, int rows, int cols, int rf, int ncls,
                                                             int gq, int blocks, const uint32_t* __restrict__ dict_tail,
                                                             uint16_t* __restrict__ desc_ray, uint32_t* __restrict__ list,
-                                                            int32_t* __restrict__ n_list, int32_t* __restrict__ flags) {
+                                                            int32_t* __restrict__ n_list, int32_t* __restrict__ flags,
+                                                            uint32_t* __restrict__ sums, int64_t sums_words) {
   const int cpad = blocks * gq * 64;
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int_zero_sums(sums, sums_words, t, (int64_t)gridDim.x * blockDim.x);
   if (t == 0 && dict_tail[1] != 1u) atomicOr(flags, 1);
   const bool live = t < (int64_t)rows * cpad;
   const int i = live ? (int)(t / cpad) : 0, j = live ? (int)(t - (int64_t)i * cpad) : 0;
@@ -774,7 +777,7 @@ __global__ __launch_bounds__(256) void score_cart_ray_kernel(CartRayArgs a) {
     cell(row_term(i), j, ri, ci);
     return (int64_t)j * a.rows + i;
   });
-  ray_write_sums<false>(a.part + (int64_t)part_id * (2 * a.ncls + 2) * a.npad + slot, a.npad, a.ncls, lane, my, known, norm);
+  ray_add_sums<false>(a.part, a.npad, slot, a.ncls, lane, my, known, norm);
 }
 
 // ---- host side of the integer form ---------------------------------------------------------------------------------------
@@ -836,7 +839,7 @@ int tdr_cart_int_launch(CartArgs a, const tdr_map_desc* map, int rf, uint32_t* d
   const int64_t T = (int64_t)a.rows * blocks * gq * 64;
   hipLaunchKernelGGL(cart_ray_prep_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, s, a.scan_pk, a.rows, a.cols, rf, map->ncls,
                      gq, blocks, reinterpret_cast<const uint32_t*>(map->dict) + 2 * TDR_CMAP_MAX_DICT, desc_ray, list, ints + 3,
-                     ints + 4);
+                     ints + 4, reinterpret_cast<uint32_t*>(a.part), (int64_t)(2 * map->ncls + 2) * L.npad);
   LAUNCH_CHECK("cart_ray_prep");
   const int32_t* flags = ints + 4;
   // the dense share through score_cart_su_kernel (generated sample loop, staged mask) when the records are the two-dword
@@ -844,7 +847,7 @@ int tdr_cart_int_launch(CartArgs a, const tdr_map_desc* map, int rf, uint32_t* d
   const bool su_kernel = rf == 8 && tdr_has_kslot(map->ncls, rf) && map->cwords == 2 && tdr_cfg().cart_seg_rows >= 4 && (a.rows & 3) == 0 &&
                          a.rows >= 8 && (int64_t)a.rows * a.cols * 16 < (int64_t)1 << 31;
   const int cpc_su = (a.cpc + CART_ASM_NCOL - 1) / CART_ASM_NCOL * CART_ASM_NCOL;
-  const int nchunks_su = (int)cdiv(a.cols, cpc_su);   // <= a.nchunks: the partial sums' rows suffice
+  const int nchunks_su = (int)cdiv(a.cols, cpc_su);
   uint32_t* desc_su = reinterpret_cast<uint32_t*>(ows + W.total);
   uint32_t* full_list = desc_su + tdr_cart_desc_words(a.rows, a.cols);
   int32_t* full_cnt = reinterpret_cast<int32_t*>(full_list + ((int64_t)a.rows * a.cols + 63) / 64 * 64);
@@ -887,7 +890,6 @@ int tdr_cart_int_launch(CartArgs a, const tdr_map_desc* map, int rf, uint32_t* d
     else if (gq == 2) hipLaunchKernelGGL((score_cart_ray_kernel<2>), grid, block, lds, s, r);
     else hipLaunchKernelGGL((score_cart_ray_kernel<4>), grid, block, lds, s, r);
     LAUNCH_CHECK("score_cart_ray");
-    out->ray_split = r.nsplit;
   }
   // dense particles: the skipping kernel with integer accumulators over the dense slots
   {
@@ -897,7 +899,6 @@ int tdr_cart_int_launch(CartArgs a, const tdr_map_desc* map, int rf, uint32_t* d
     d.flags = flags; d.run_if_int = 1;
     d.order = slots; d.count = counts; d.npad = npad_int;
     d.pkcol = plane_trows(map->rows) * 128 - 16;
-    out->nchunks_dense = a.nchunks;
     if (su_kernel) {
       CartSuArgs x;
       x.full_list = full_list; x.full_cnt = full_cnt; x.list_cap = list_cap; x.seg_rows = tdr_cfg().cart_seg_rows;
@@ -906,7 +907,6 @@ int tdr_cart_int_launch(CartArgs a, const tdr_map_desc* map, int rf, uint32_t* d
       d.desc = desc_su;
       d.cpc = cpc_su;
       d.nchunks = nchunks_su;
-      out->nchunks_dense = nchunks_su;
       hipLaunchKernelGGL(score_cart_su_kernel, dim3((unsigned)cdiv(npad_int, 256), (unsigned)nchunks_su), dim3(256), 0, s, d, x);
       LAUNCH_CHECK("score_cart_su");
     } else {

@@ -87,17 +87,41 @@ __device__ __forceinline__ void int_add_class(T (&acc)[ND], uint32_t cd, uint32_
   }
 }
 
-// ---- what a lane = particle kernel writes: [chunk][2 ncls + 2][npad] words, o at the particle's slot of its chunk ----------------
+// ---- a launch's sums: ONE block [2 ncls + 2][npad] of words for all its kernels, rows, waves and splits ------------------------
+// Rows 2 k and 2 k + 1 together are class k's 64-bit sums, one per slot (8-byte aligned: the block is, npad is a multiple of
+// 64); row 2 ncls the normalisation, row 2 ncls + 1 the known count, 32-bit words (their totals stay below 2^32:
+// score_prep_kernel's bound on the scan's mass, a window of fewer than 2^32 samples).  Whoever holds a share of a slot's
+// sums ADDS it — integers: the total is the same number in whatever order the shares arrive — with relaxed no-return
+// atomics of agent scope, a class sum with one 64-bit add (two 32-bit adds would lose the carry between the halves).  The
+// launch in front of the first scoring kernel zeroes the block (int_zero_sums); score_finalize_exact_kernel reads it.
+__device__ __forceinline__ void int_add_u64(unsigned long long* at, unsigned long long v) {
+  (void)__hip_atomic_fetch_add(at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void int_add_u32(uint32_t* at, uint32_t v) {
+  (void)__hip_atomic_fetch_add(at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// the zeroing, by every thread of a grid of `threads` threads of which this is thread `t` (words: a multiple of 4 — npad is
+// one of 64; 16-byte stores where the block is aligned for them)
+__device__ __forceinline__ void int_zero_sums(uint32_t* sums, int64_t words, int64_t t, int64_t threads) {
+  if (!sums) return;
+  if ((reinterpret_cast<uintptr_t>(sums) & 15) == 0) {
+    uint4* const s4 = reinterpret_cast<uint4*>(sums);
+    for (int64_t i = t; i < (words >> 2); i += threads) s4[i] = make_uint4(0u, 0u, 0u, 0u);
+  } else {
+    for (int64_t i = t; i < words; i += threads) sums[i] = 0u;
+  }
+}
+// what a lane = particle kernel adds: the lane's sums over its row's samples, at the particle's slot.  (A zero adds nothing
+// and is not sent: a row of few rings meets few classes.)
 template <class T, int ND>
-__device__ __forceinline__ void int_write_sums(uint32_t* o, int64_t npad, int ncls, const T (&acc)[ND], uint32_t norm, uint32_t known) {
+__device__ __forceinline__ void int_add_sums(uint32_t* sums, int64_t npad, int64_t slot, int ncls, const T (&acc)[ND], uint32_t norm,
+                                             uint32_t known) {
+  unsigned long long* const s64 = reinterpret_cast<unsigned long long*>(sums) + slot;
 #pragma unroll
   for (int k = 0; k < ND; k++)
-    if (k < ncls) {
-      o[(int64_t)(2 * k) * npad] = (uint32_t)acc[k];
-      o[(int64_t)(2 * k + 1) * npad] = (uint32_t)((unsigned long long)acc[k] >> 32);
-    }
-  o[(int64_t)(2 * ncls) * npad] = norm;
-  o[(int64_t)(2 * ncls + 1) * npad] = known;
+    if (k < ncls && (unsigned long long)acc[k] != 0ull) int_add_u64(s64 + (int64_t)k * npad, (unsigned long long)acc[k]);
+  if (norm) int_add_u32(sums + (int64_t)(2 * ncls) * npad + slot, norm);
+  if (known) int_add_u32(sums + (int64_t)(2 * ncls + 1) * npad + slot, known);
 }
 
 // ---- the ray-mapped kernels (one wave per particle): prologue, list pass, epilogue ---------------------------------------------
@@ -151,19 +175,19 @@ __device__ __forceinline__ void ray_list_pass(const Args& a, int part_id, int la
     norm += (uint32_t)a.scan_pk[bin * a.rf + a.rf - 1] & (0u - kbit);
   }
 }
-// Epilogue: lanes -> one sum per class, the words [part][2 ncls + 2][npad] (like the lane = particle kernels'), o at the
-// particle's slot of the wave's part.  KNOWN_FOLDED: every lane already holds the wave's known count.
+// Epilogue: lanes -> one sum per class, added to the launch's sums (int_add_sums has the block) at the particle's slot, by
+// lane 0, as it wrote them before (kept in this shape: with the class sums collected into lanes for one atomic instruction the
+// patch-order kernel took 82 registers for 79 and lost a wave per SIMD).  KNOWN_FOLDED: every lane already holds the wave's
+// known count.
 template <bool KNOWN_FOLDED>
-__device__ __forceinline__ void ray_write_sums(uint32_t* o, int64_t npad, int ncls, int lane, unsigned long long* my,
-                                               uint32_t& known, uint32_t& norm) {   // (by reference: by value the
-  for (int c = 0; c < ncls; c++) {                                                    // Cartesian kernel's loop takes 7 registers more)
+__device__ __forceinline__ void ray_add_sums(uint32_t* sums, int64_t npad, int64_t slot, int ncls, int lane, unsigned long long* my,
+                                             uint32_t& known, uint32_t& norm) {   // (by reference: by value the
+  unsigned long long* const s64 = reinterpret_cast<unsigned long long*>(sums) + slot;   // Cartesian kernel's loop takes 7 registers more)
+  for (int c = 0; c < ncls; c++) {
     unsigned long long s = __hip_atomic_load(&my[(c + 1) * 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #pragma unroll
     for (int dlt = 32; dlt > 0; dlt >>= 1) s += __shfl_xor(s, dlt, 64);
-    if (lane == 0) {
-      o[(int64_t)(2 * c) * npad] = (uint32_t)s;
-      o[(int64_t)(2 * c + 1) * npad] = (uint32_t)(s >> 32);
-    }
+    if (lane == 0 && s != 0ull) int_add_u64(s64 + (int64_t)c * npad, s);
   }
 #pragma unroll
   for (int dlt = 32; dlt > 0; dlt >>= 1) {
@@ -171,8 +195,8 @@ __device__ __forceinline__ void ray_write_sums(uint32_t* o, int64_t npad, int nc
     norm += __shfl_xor(norm, dlt, 64);
   }
   if (lane == 0) {
-    o[(int64_t)(2 * ncls) * npad] = norm;
-    o[(int64_t)(2 * ncls + 1) * npad] = known;
+    if (norm) int_add_u32(sums + (int64_t)(2 * ncls) * npad + slot, norm);
+    if (known) int_add_u32(sums + (int64_t)(2 * ncls + 1) * npad + slot, known);
   }
 }
 #endif  // TDR_SCORE_INT_DEV_H_

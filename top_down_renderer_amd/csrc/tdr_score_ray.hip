@@ -97,9 +97,9 @@ struct RayArgs {
   const int32_t* slots;     // the launch's slot list; the sparse share is slots [counts[0], counts[0] + counts[1])
   const int32_t* counts;
   const int32_t* inexact;
-  int nsplit;               // waves per particle: each takes a contiguous share of the directions and writes one chunk row
+  int nsplit;               // waves per particle: each takes a contiguous share of the directions and adds its sums to the slot's
   int64_t npad;
-  uint32_t* part;           // [>= nsplit][2 ncls + 2][npad], like score_polar_su_kernel
+  uint32_t* part;           // the launch's sums [2 ncls + 2][npad], score_polar_su_kernel's too (int_add_sums)
   const uint32_t* clist;    // COMPACT: the sectors' bin lists and their table (score_prep_kernel)
   const int32_t* ctab;
   uint32_t* gate_ctr;       // NULL, or (profiling) the four counters of tdr_profile_ray_gate
@@ -110,7 +110,7 @@ struct RayArgs {
 // (score_prep_kernel checked that), and 16 bytes per lane and row less through the texture path.
 // lacc [4 waves][ncls + 1][64 lanes]: a lane's sums per class (slot 0: no class); lut, per class code: {plane constant,
 // column shift, known-bit index, accumulator}.  The prologue that fills them, the list pass and the epilogue are
-// score_cart_ray_kernel's too: ray_prologue, ray_list_pass, ray_write_sums (tdr_score_int_dev.h).
+// score_cart_ray_kernel's too: ray_prologue, ray_list_pass, ray_add_sums (tdr_score_int_dev.h).
 // PATCH (with BM): the patch order (see the top of the file); ldir: the directions' pairs in LDS
 // COMPACT: the entries of gathers 0 .. N - 1 of a step that starts at entry e0 (a multiple of 256) of a stream — one 16-byte
 // load per lane and block of four gathers (score_prep_kernel stores the blocks lane-major and fills the last one with
@@ -139,9 +139,9 @@ __device__ __forceinline__ void ray_list_load(const uint4* __restrict__ lst, int
 //     one barrier.  A total of at least P / 2 settles the particle; so does a total that stays below P / 2 even if every B
 //     cell were known (it will be NaN).  Otherwise the waves walk their B lists on the mask plane in blocks of up to 256
 //     entries, add each block's known bits to the shared word and stop when it has reached P / 2 or the lists end.
-// INVARIANT: every unit added to a known count is the known bit of a distinct real sample, so the sum of the waves' counts in
-// `part` never exceeds the true count; a wave leaves its B lists unfinished only after the shared total — all of it counted
-// by waves that write it out — reached P / 2.  So the written sum is >= P / 2 exactly when the true count is, and the gate
+// INVARIANT: every unit added to a known count is the known bit of a distinct real sample, so the count the waves add up in
+// the launch's sums never exceeds the true one; a wave leaves its B lists unfinished only after the shared total — all of it counted
+// by waves that write it out — reached P / 2.  So the added-up count is >= P / 2 exactly when the true count is, and the gate
 // falls as it did.  Where a particle's waves do not share a workgroup (a split that does not divide 4) or P >= 2^24 the B
 // lists are walked to the end: the exact count.
 template <int GQ, bool USCALE, bool FAC, bool BM, bool PATCH>
@@ -494,7 +494,7 @@ __device__ __forceinline__ void ray_body(const RayArgs& a, unsigned long long* l
   }
   // (the rings a block pads a direction with fell on the guard cell — unknown — and counted nothing; COMPACT: phase 2 left
   // the wave's known count in every lane)
-  ray_write_sums<COMPACT>(a.part + (int64_t)part_id * (2 * a.ncls + 2) * a.npad + slot, a.npad, a.ncls, lane, my, known, norm);
+  ray_add_sums<COMPACT>(a.part, a.npad, slot, a.ncls, lane, my, known, norm);
 }
 TDR_TL_BUFFER(g_timeline_ray, tdr_debug_read_timeline_ray)   // (diagnostic build only: tdr_score_dev.h)
 template <int GQ, bool USCALE, bool BM = false, bool PATCH = false>

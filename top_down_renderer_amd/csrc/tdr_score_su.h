@@ -20,7 +20,7 @@ struct SuWs {
   //       [3 spare]  (int_form_off)
 };
 #define TDR_SU_TAIL_INTS 10       // the words of `ints` behind the three per-key tables
-#define TDR_RAY_MAX_SPLIT 8       // waves a particle's window may be split over (tdr_ray_splits): chunk rows of `part`
+#define TDR_RAY_MAX_SPLIT 8       // waves a particle's window may be split over (tdr_ray_splits)
 SuWs tdr_su_ws(int nb, int nr, int group, int64_t n);
 
 // The ROWS of the shift-uniform kernel's grid (grid.y) — the "plan".  A row is a workgroup's share of a window: a ring group
@@ -63,9 +63,10 @@ struct SuLaunch {
   const int32_t* perm;       // caller's locality order (NULL = identity)
   int group, nchunks;
   int tail_k = 0, tail_q = 1;   // the last tail_k ring groups go as tail_q rows each (su_tail_plan) ...
-  int rows = 0;              // ... which makes this many rows of the shift-uniform kernel's grid and of `part` per dense slot
-  int64_t npad;              // slot capacity = stride of part (su_npad)
-  float* part;               // integer partial sums, [rows][2 ncls + 2][npad] words (tdr_score_su.hip)
+  int rows = 0;              // ... which makes this many rows of the shift-uniform kernel's grid
+  int64_t npad;              // slot capacity = stride of the sums (su_npad)
+  float* part;               // the launch's integer sums, ONE block [2 ncls + 2][npad] of words that every row and wave adds to
+                             // (tdr_score_int_dev.h: int_add_sums); NULL: the preparation alone, nothing to zero
   int ray_split;             // waves per scattered particle (tdr_ray_splits)
   const float* fac;          // the table's factors (tdr_polar_factors_host) or NULL
   float uscale;              // the caller's uniform scale (<= 0: none)

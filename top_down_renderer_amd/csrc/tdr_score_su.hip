@@ -83,8 +83,8 @@ struct SuArgs {
   const int32_t* nslots;   // device word: slots in use (a multiple of 64)
   int group, nchunks, ncls;
   int tail_k, tail_q;      // grid.y = the rows of su_tail_plan(nchunks, tail_k, tail_q, ...)
-  int64_t npad;            // stride of `part`
-  uint32_t* part;          // [rows][2 ncls + 2][npad]: class k's integer sum as {low, high} words, normalisation, known count
+  int64_t npad;            // stride of the sums
+  uint32_t* part;          // the launch's sums [2 ncls + 2][npad]: every row adds its share (int_add_sums, tdr_score_int_dev.h)
   uint32_t* stats;         // NULL, or (profiling) counters of the variants the wave-sectors ran: tdr_profile_variants
   const uint32_t* full_mask;   // [nchunks][2 nb]: the bins with several classes (score_prep_kernel), NULL: no list pass — the
                                // assembly loop hands their steps to the C++ step (tdr_config_tuning("su_full_list", 0))
@@ -161,6 +161,8 @@ struct PrepArgs {
   int32_t* ctab;
   uint32_t* full_mask;     // NULL, or [nchunks][2 nb]: bit jj of word (group, scan row i) — and of word nb + i, so that a sector's
                            // rows need no wrap — says bin (i, ring group * G + jj) is SU_CODE_FULL (G divides 64, G <= 32)
+  uint32_t* sums;          // NULL (the preparation on its own), or the launch's integer sums: sums_words words, zeroed here
+  int64_t sums_words;
 };
 // float minimum / maximum on a word that holds a float: the sign decides which integer order is the float order (a NaN is left
 // out, as fminf / fmaxf leave it out)
@@ -440,7 +442,12 @@ __device__ __forceinline__ void score_prep_body(const PrepArgs& a, const unsigne
   a.desc_ray[at_d] = (uint16_t)d;
 }
 template <int PREP_DIRS>
-__global__ __launch_bounds__(64 * PREP_DIRS) void score_prep_kernel(PrepArgs a) { score_prep_body<PREP_DIRS>(a, blockIdx.x); }
+__global__ __launch_bounds__(64 * PREP_DIRS) void score_prep_kernel(PrepArgs a) {
+  // the launch in front of the scoring kernels: its threads zero the sums those add to, in every call (nothing is kept between
+  // calls) — stores that need no answer, in front of the loads below
+  int_zero_sums(a.sums, a.sums_words, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+  score_prep_body<PREP_DIRS>(a, blockIdx.x);
+}
 
 // Sort key of every particle (in the caller's locality order): its heading bin when its neighbourhood is DENSE, nb when
 // it is SPARSE — the 64 particles around it in the locality (Morton) order are more than `span` map cells apart.  A
@@ -1172,7 +1179,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
   }
   if (active) {
     const int64_t slot = base + lane;
-    int_write_sums(a.part + (int64_t)blockIdx.y * (2 * a.ncls + 2) * a.npad + slot, a.npad, a.ncls, acc, norm, known);
+    int_add_sums(a.part, a.npad, slot, a.ncls, acc, norm, known);
     if (a.list_stats && lane == 0) {   // (profiling: one atomic per wave and counter)
       if (n_hand) atomicAdd(&a.list_stats[0], n_hand);
       if (n_listed) atomicAdd(&a.list_stats[1], n_listed);
@@ -1256,7 +1263,7 @@ bool tdr_su_shape_ok(int nb, int nr, int group, int64_t n_total) {
 // which lost to 8-ring ones on their run-down alone (3.69 against 3.50 ms), now win (tdr_score.hip: score_ws).
 // K and Q: TdrConfig::su_tail_groups / su_tail_parts (tdr_config.h has the sweep behind the defaults).
 // The rule of the shapes: short rows pay where workgroups QUEUE — a launch of fewer than two rounds of the chip's resident
-// workgroups (256 CUs x 6) has no run-down worth shortening, and every row costs the finalize a pass over its partial sums.
+// workgroups (256 CUs x 6) has no run-down worth shortening.
 // Results never depend on it.  (tdr_config_shift_uniform(2), the tests' mode: whatever the knobs say, on any shape.)
 void tdr_su_tail(int nchunks, int64_t n, int* k, int* q) {
   *k = std::min(tdr_cfg().su_tail_groups, nchunks);
@@ -1455,6 +1462,8 @@ int tdr_su_prepare(const SuLaunch& L, const SuWs& W, hipStream_t s, const int32_
   p.n_list = ints + 3; p.inexact = ints + 4;
   p.clist = nullptr; p.ctab = nullptr;
   p.full_mask = tdr_su_full_list(L) ? reinterpret_cast<uint32_t*>(base + W.full_mask) : nullptr;
+  p.sums = reinterpret_cast<uint32_t*>(L.part);
+  p.sums_words = L.part ? (int64_t)(2 * L.map->ncls + 2) * L.npad : 0;
   if (p.patch) {   // the compact lists: a workgroup per sector (the direction count is a multiple of 16)
     p.clist = reinterpret_cast<uint32_t*>(base + W.ray_clist);
     p.ctab = base + W.ray_ctab;
@@ -1521,7 +1530,7 @@ int tdr_su_score(const SuLaunch& L, const SuWs& W, hipStream_t s) {
   u.list_stats = tdr_profile_su_list_ptr();
   int rg, r0, r1;
   const int rows = su_tail_plan(L.nchunks, L.tail_k, L.tail_q, -1, &rg, &r0, &r1);
-  if (L.rows != rows) return fail(TDR_ERR_ARG, "score: %d rows of partial sums for a plan of %d", L.rows, rows);
+  if (L.rows != rows) return fail(TDR_ERR_ARG, "score: a grid of %d rows for a plan of %d", L.rows, rows);
   const dim3 grid((unsigned)cdiv(L.npad, 256), (unsigned)rows), block(256);
   const bool ks = tdr_has_kslot(map->ncls, L.rf), us = L.uniform_scale;
 #define TDR_LAUNCH_SU(NV4)                                                                         \
