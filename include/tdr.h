@@ -658,7 +658,9 @@ int tdr_profile_su_list(int64_t out[2]);
  * "su_full_list" — 1 (default): scan bins that hold several classes are empty to score_polar_su_kernel's assembly loop and
  * are added behind it, sector by sector, from a list (a mask word per ring group and scan row that the preparation writes),
  * each class from its plane; 0: the loop hands every four-ring step that holds such a bin to the C++ step (A/B, tests).
- * Integer sums: same bits.  Ring groups of 4, 8 or 16 rings. */
+ * Integer sums: same bits.  Ring groups of 4, 8 or 16 rings.
+ * "inject_cand_chunk" — candidates one scoring launch of tdr_filter_inject_sensor covers, in whole slots (>= 1; default
+ * 65536; bounds the call's buffers; same results: "sensor resetting" below). */
 int64_t tdr_config_tuning(const char* name, int64_t value);
 /* The rows of score_polar_su_kernel's grid for nchunks ring groups with the last k cut into q sector ranges each (tests):
  * returns the row count R = (nchunks - k') + k' q', k' = k clamped to [0, nchunks], q' = q rounded down to 1, 2, 4 or 8; for
@@ -1638,6 +1640,73 @@ int tdr_filter_recovery_step(tdr_filter* f, tdr_recovery_state* s, const tdr_rec
                              int64_t* injected_out);
 int tdr_batch_inject(tdr_filter* const* filters, int k, const double* p, int heading_mode, const uint64_t* seeds,
                      int64_t* injected_out, void* stream);
+
+/* ---- sensor resetting: the injected slots take the best-scoring of C road candidates (csrc/tdr_recover_sensor.hip,
+ * csrc/tdr_host_recover.cpp) -----------------------------------------------------------------------------------
+ * A DEFINITION, like the recovery injection above, whose words, road list and formulas it uses.  Inputs: a filter and the
+ * scan of the step, res, p, candidates = C (1 .. 4096), heading_mode (0 .. 1), seed, draw = the filter's update count.
+ *   1. The injected slots are exactly those tdr_k_inject would inject: slot i iff
+ *      (philox({i, draw lo, draw hi, 0}, key)[0] >> 8) < threshold24.  The LIST is those slot indices, ascending.
+ *   2. Candidate j (0 <= j < C) of slot i, position: a_j = philox({i, draw lo, draw hi, 2j}, key); cell, sub-cell offsets,
+ *      init_x_px, init_y_px and dx_m = dy_m = 0 from a_j[1..3] exactly as the injection derives them from a[1..3]; a_j[0] is
+ *      unused for j >= 1; scale is the slot's current scale.
+ *   3. Its heading.  heading_mode 1: theta from philox({i, draw lo, draw hi, 2j + 1}, key)[0] by the injection's formula,
+ *      have_init = 1.  heading_mode 0: theta = 0, have_init = 0.  Candidate 0 is, word for word, the particle the plain
+ *      injection writes.
+ *   4. A candidate's weight is the raw weight tdr_filter_compute_weights gives a particle in that state in THIS filter: its
+ *      map and table, fp, uniform_scale, n_total = the filter's particle count; polar filters: tdr_k_score_polar with
+ *      init_search = (heading_mode == 0); Cartesian filters: tdr_k_score_cart_init (mode 0 only), then tdr_k_score_cart.
+ *      There is no geometric term.  In mode 0 the search sets the candidate's theta and have_init as for any particle.
+ *   5. The pick: key_j = w_j, or -1 where w_j is NaN; the smallest j whose key is the maximum.  A gated candidate (weight 0)
+ *      loses to any positive one; if all are NaN, candidate 0 wins.
+ *   6. The slot takes the seven state fields of the picked candidate as scoring left them.  Slots that are not on the list
+ *      and the padding behind n are not written.
+ *   7. Raw and normalised weights, the weight statistics, the generator, the stored mixture and the step count stay as they
+ *      are: tdr_filter_inject's contract.
+ *   With C = 1 and mode 1 the result is byte for byte tdr_filter_inject's; with C = 1 and mode 0 the slot holds what the
+ *   plain injection followed by the next update's search would hold.
+ * Layer 1 (device pointers, asynchronous, no allocation).
+ *   tdr_k_inject_list: the list of [0, n) (LOCAL indices; the words are those of slot_begin + local) to list_out (n words)
+ *     and its length to *count_dev (DEVICE): ballot counts per wave, counts per workgroup, a running sum, a write; workspace
+ *     of tdr_inject_list_workspace_bytes(n) bytes.  max_blocks: a bound on the grid (<= 0: the launcher's own; tests) — the
+ *     list is the same whatever the grid.  n == 0 or threshold24 == 0: the length alone.
+ *   tdr_k_inject_candidates: for list entries [first, first + m) the SoA states [TDR_ST_FIELDS][cand_cap] of their
+ *     candidates, candidate q = (e - first) * C + j: one 4-byte road load per candidate, vector stores.
+ *   tdr_k_inject_select: one wave per listed slot, the lanes stride over its C weights cand_w[(e - first) * C + j] and the
+ *     wave reduces lexicographically on (key, -j), so the result does not depend on the reduction order; the winner's seven
+ *     fields go to the slot; pick_out[e - first] = j (may be NULL); *written_dev (DEVICE, may be NULL) is INCREMENTED by the
+ *     number of listed slots of the call with one 64-bit integer atomic per workgroup: the caller zeroes it.
+ *   Refused with TDR_ERR_ARG before any device work: null pointers, n < 0 or n > cap, slots beyond 2^31, threshold24 above
+ *   2^24, first < 0, m < 0, first + m > n, C outside 1 .. 4096, heading_mode outside 0 .. 1, n_road < 1, m * C > cand_cap.
+ * Handle layer.  tdr_filter_inject_sensor: the scan as tdr_filter_compute_weights takes it (host images, or a renderer's
+ *   last render); scan_imgs == NULL && renderer == NULL: the packed scan the filter keeps from its last update or
+ *   compute_weights that was handed images (TDR_ERR_ARG before the first; a renderer's scan stays the renderer's and is not
+ *   kept).  The launcher runs the list and WAITS ONCE on the filter's stream for its length; an empty list costs the list
+ *   launch and nothing else.  It then walks the list in chunks of max(1, chunk / C) whole slots, chunk =
+ *   tdr_config_tuning("inject_cand_chunk") candidates (default 65536; not one of the names listed at tdr_config_tuning:
+ *   tests/test_config_table.py replays that list as it was recorded): the candidates, their order by pose (results do not
+ *   depend on it), the scoring launch(es) of the filter's kind with n_total = the filter's count, the selection.  (The
+ *   Cartesian search, mode 0, waits once more per chunk: tdr_k_score_cart_init reads its own list's length.)  Candidate
+ *   states, weights, order and the scorer's workspace are the filter's, allocated on first use and sized by the chunk.
+ *   injected_out == NULL: no read-back of the count.  After a call that wrote slots the cached pose statistics are dropped,
+ *   and with heading_mode 0 the next update runs the search again (a gated winner can stay without a heading).
+ *   tdr_filter_recovery_step_sensor: tdr_filter_recovery_step's tracker and reset rule with this injection.
+ *   Refused like tdr_filter_inject, in the same words (sharded filters included), and: candidates outside 1 .. 4096, a res
+ *   that is not finite or not positive, a scan of another shape, no scan.  A refused call writes nothing. */
+size_t tdr_inject_list_workspace_bytes(int64_t n);
+int tdr_k_inject_list(int64_t n, int64_t slot_begin, uint64_t seed, uint64_t draw, uint32_t threshold24, int32_t* list_out,
+                      int64_t* count_dev, void* workspace, int max_blocks, void* stream);
+int tdr_k_inject_candidates(const float* st, int64_t cap, int64_t n, int64_t slot_begin, const int32_t* list, int64_t first,
+                            int64_t m, int candidates, const tdr_map_desc* map, const uint32_t* road, int64_t n_road,
+                            uint64_t seed, uint64_t draw, int heading_mode, float* cand_st, int64_t cand_cap, void* stream);
+int tdr_k_inject_select(float* st, int64_t cap, int64_t n, const int32_t* list, int64_t first, int64_t m, int candidates,
+                        const float* cand_st, int64_t cand_cap, const float* cand_w, int32_t* pick_out, int64_t* written_dev,
+                        void* stream);
+int tdr_filter_inject_sensor(tdr_filter* f, const float* scan_imgs, const tdr_renderer* renderer, float res, double p,
+                             int candidates, int heading_mode, uint64_t seed, int64_t* injected_out);
+int tdr_filter_recovery_step_sensor(tdr_filter* f, tdr_recovery_state* s, const tdr_recovery_params* rp, int candidates,
+                                    const float* scan_imgs, const tdr_renderer* renderer, float res, double* p_out,
+                                    int64_t* injected_out);
 
 /* internal: lets the handle layer (csrc/tdr_host_*.cpp) report through tdr_last_error() */
 int tdr_set_error(int code, const char* msg);

@@ -155,6 +155,28 @@ class ParticleFilter {
     if (injected) *injected = n;
     return p;
   }
+  // Sensor resetting (extension; include/tdr.h, "sensor resetting"): the slots inject() would write take the best-scoring of
+  // `candidates` road candidates against the renderer's last render (tdr_filter_inject_sensor); renderer == nullptr: the
+  // scan the filter kept from its last update or computeWeight that was handed images.  Returns the written slots (count =
+  // false: no read-back of the count, returns -1).  Throws on what inject() throws on, on candidates outside 1 .. 4096, a
+  // res that is not finite and positive, and without a scan.
+  int64_t injectSensor(const ScanRenderer* renderer, float res, double p, int candidates, int heading_mode = 0,
+                       uint64_t seed = 0, bool count = true) {
+    int64_t injected = -1;
+    check(tdr_filter_inject_sensor(f_, nullptr, renderer ? renderer->handle() : nullptr, res, p, candidates, heading_mode, seed,
+                                   count ? &injected : nullptr), "injectSensor");
+    return injected;
+  }
+  // ... driven by the tracker of recoveryStep (tdr_filter_recovery_step_sensor)
+  double recoveryStepSensor(tdr_recovery_state& state, const RecoveryParams& rp, int candidates, const ScanRenderer* renderer,
+                            float res, int64_t* injected = nullptr) {
+    double p = 0.;
+    int64_t n = 0;
+    check(tdr_filter_recovery_step_sensor(f_, &state, &rp, candidates, nullptr, renderer ? renderer->handle() : nullptr, res, &p,
+                                          &n), "recoveryStepSensor");
+    if (injected) *injected = n;
+    return p;
+  }
   // {argmax bits, sum, mean, bottom_stddev, fallback, num_valid, num_under, 0} of the last update (particle_filter.cpp:107-147)
   void weightStats(float out8[8]) { check(tdr_filter_get_weight_stats(f_, out8), "weightStats"); }
   void computeCov(Eigen::Matrix4f& cov) { stat(1, nullptr, &cov); }                        // :226-236

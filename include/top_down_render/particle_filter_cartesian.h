@@ -93,6 +93,25 @@ class ParticleFilterCartesian {
     if (injected) *injected = n;
     return p;
   }
+  // Sensor resetting (ParticleFilter::injectSensor / recoveryStepSensor; include/tdr.h, "sensor resetting"): the injected
+  // slots take the best-scoring of `candidates` road candidates against the renderer's last Cartesian render (nullptr: the
+  // scan the filter kept); heading_mode 0 runs the heading search on the candidates
+  int64_t injectSensor(const ScanRenderer* renderer, float res, double p, int candidates, int heading_mode = 0,
+                       uint64_t seed = 0, bool count = true) {
+    int64_t injected = -1;
+    check(tdr_filter_inject_sensor(f_, nullptr, renderer ? renderer->handle() : nullptr, res, p, candidates, heading_mode, seed,
+                                   count ? &injected : nullptr), "injectSensor");
+    return injected;
+  }
+  double recoveryStepSensor(tdr_recovery_state& state, const RecoveryParams& rp, int candidates, const ScanRenderer* renderer,
+                            float res, int64_t* injected = nullptr) {
+    double p = 0.;
+    int64_t n = 0;
+    check(tdr_filter_recovery_step_sensor(f_, &state, &rp, candidates, nullptr, renderer ? renderer->handle() : nullptr, res, &p,
+                                          &n), "recoveryStepSensor");
+    if (injected) *injected = n;
+    return p;
+  }
   // {argmax bits, sum, mean, bottom_stddev, fallback, num_valid, num_under, 0} of the last update (particle_filter.cpp:107-147)
   void weightStats(float out8[8]) { check(tdr_filter_get_weight_stats(f_, out8), "weightStats"); }
   void configure(bool parity_rng, int locality_every) { check(tdr_filter_configure(f_, parity_rng, locality_every), "configure"); }

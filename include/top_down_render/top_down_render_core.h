@@ -48,6 +48,10 @@ class TopDownRenderCore {
     // set's).  0: never — no call, no allocation, every byte of the loop as without the field.
     int recovery_every = 0;
     RecoveryParams recovery;
+    // Sensor resetting (extension; include/tdr.h): above 1, a due recovery step gives every injected slot the best-scoring
+    // of this many road candidates (1 .. 4096) against the step's render at the step's res
+    // (ParticleFilter::recoveryStepSensor).  1: exactly the call above.  TopDownRenderCoreBatch refuses a core with more.
+    int recovery_candidates = 1;
   };
   struct PoseEst {                      // what publishPoseEst computed this step
     Eigen::Matrix4f cov;                // computeMeanCov (:333)
@@ -101,7 +105,13 @@ class TopDownRenderCore {
     PoseEst e = publishPoseEst();                                                            // :560
     if (countStepAndGmmDue()) filter_->computeGMMDevice();
     if (countStepAndKldDue()) filter_->setTargetCount((int)filter_->kldCount(cfg_.kld));
-    if (countStepAndRecoveryDue()) last_recovery_p_ = filter_->recoveryStep(recovery_state_, cfg_.recovery, &last_recovery_injected_);
+    if (countStepAndRecoveryDue()) {
+      if (cfg_.recovery_candidates > 1)   // sensor resetting: against the render and the res of this step
+        last_recovery_p_ = filter_->recoveryStepSensor(recovery_state_, cfg_.recovery, cfg_.recovery_candidates, renderer_,
+                                                       last_res_, &last_recovery_injected_);
+      else
+        last_recovery_p_ = filter_->recoveryStep(recovery_state_, cfg_.recovery, &last_recovery_injected_);
+    }
     if (est) *est = e;
     return true;
   }

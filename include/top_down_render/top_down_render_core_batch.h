@@ -46,6 +46,10 @@ class TopDownRenderCoreBatch {
                                     std::to_string(c->cfg_.theta_bins) + " x " + std::to_string(c->cfg_.range_bins) +
                                     " bins, core 0 " + std::to_string(cores[0]->cfg_.theta_bins) + " x " +
                                     std::to_string(cores[0]->cfg_.range_bins));
+      if (c->cfg_.recovery_every > 0 && c->cfg_.recovery_candidates > 1)
+        throw std::invalid_argument("TopDownRenderCoreBatch::takeStep: core " + std::to_string(i) + " has recovery_candidates = " +
+                                    std::to_string(c->cfg_.recovery_candidates) +
+                                    ": sensor resetting is not built for a batch (tdr_batch_inject is the plain injection)");
       if (c->map_ != cores[0]->map_)
         throw std::invalid_argument("TopDownRenderCoreBatch::takeStep: core " + std::to_string(i) + " is on another map than core 0");
     }

@@ -434,6 +434,14 @@ SIGNATURES = {
     "tdr_filter_recovery_step": (_i, [_vp, C.POINTER(RecoveryStateC), C.POINTER(RecoveryParamsC), C.POINTER(C.c_double),
                                       C.POINTER(_i64)]),
     "tdr_batch_inject": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
+    # sensor resetting (csrc/tdr_recover_sensor.hip, csrc/tdr_host_recover.cpp)
+    "tdr_inject_list_workspace_bytes": (C.c_size_t, [_i64]),
+    "tdr_k_inject_list": (_i, [_i64, _i64, _u64, _u64, _u32, _vp, _vp, _vp, _i, _vp]),
+    "tdr_k_inject_candidates": (_i, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _vp, _i64, _u64, _u64, _i, _vp, _i64, _vp]),
+    "tdr_k_inject_select": (_i, [_vp, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "tdr_filter_inject_sensor": (_i, [_vp, _vp, _vp, _f, C.c_double, _i, _i, _u64, C.POINTER(_i64)]),
+    "tdr_filter_recovery_step_sensor": (_i, [_vp, C.POINTER(RecoveryStateC), C.POINTER(RecoveryParamsC), _i, _vp, _vp, _f,
+                                             C.POINTER(C.c_double), C.POINTER(_i64)]),
     "tdr_set_error": (_i, [_i, C.c_char_p]),
     "tdr_locality_tmp_ints": (C.c_size_t, [_i64, _i, _i]),
     "tdr_locality_pose_tmp_ints": (C.c_size_t, [_i64]),

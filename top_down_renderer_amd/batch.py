@@ -342,6 +342,34 @@ class FilterHandle:
         check(self.L.tdr_filter_recovery_step(self.h, C.byref(state), C.byref(rp), C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def _scan_args(self, scan):
+        """(scan_imgs, renderer) of a scoring call: a Renderer, images (ncls, nb, nr), or None: the scan the filter kept."""
+        if scan is None:
+            return None, None, None
+        if isinstance(scan, Renderer):
+            return None, scan.h, None
+        imgs = _scan_images(scan, self.map, self.cart)
+        return _ptr(imgs), None, imgs
+
+    def inject_sensor(self, scan, res, p, candidates, heading_mode=0, seed=0, count=True):
+        """tdr_filter_inject_sensor: the slots inject() would write take the best-scoring of `candidates` road candidates
+        against `scan` (a Renderer, images, or None: the scan the filter kept).  Returns the number of written slots, or
+        None with count=False."""
+        n = C.c_int64(0)
+        imgs, rh, keep = self._scan_args(scan)
+        check(self.L.tdr_filter_inject_sensor(self.h, imgs, rh, C.c_float(res), C.c_double(p), int(candidates), int(heading_mode),
+                                              int(seed), C.byref(n) if count else None))
+        return n.value if count else None
+
+    def recovery_step_sensor(self, state, params, candidates, scan, res):
+        """tdr_filter_recovery_step_sensor: recovery_step with inject_sensor.  Returns (p, injected)."""
+        rp = params if isinstance(params, _lib.RecoveryParamsC) else params.to_c()
+        p, n = C.c_double(0), C.c_int64(0)
+        imgs, rh, keep = self._scan_args(scan)
+        check(self.L.tdr_filter_recovery_step_sensor(self.h, C.byref(state), C.byref(rp), int(candidates), imgs, rh, C.c_float(res),
+                                                     C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def set_viz_background(self, bgr=None, labels=None, lut=None):
         """The picture's background: bgr (H, W, 3) uint8, or labels (H, W) uint8 coloured on the device through lut
         (256 BGR triplets; tdr_filter_set_viz_background_labels)."""
@@ -631,8 +659,11 @@ class LoopBatch:
             raise ValueError("LoopBatch: one renderer per filter")
         cfgs = list(cfgs) if isinstance(cfgs, (list, tuple)) else [cfgs or CoreConfig()] * k
         self.filters, self.renderers = list(filters), list(renderers)
-        for c in cfgs:
+        for i, c in enumerate(cfgs):
             c.check()
+            if c.recovery_every > 0 and c.recovery_candidates > 1:
+                raise ValueError(f"LoopBatch: robot {i} has recovery_candidates = {c.recovery_candidates}: sensor resetting is "
+                                 "not built for a batch (tdr_batch_inject is the plain injection)")
         self.cores = [TopDownRenderCore(c) for c in cfgs]
         self.ang_res, self.ncls, self.nb, self.nr = float(ang_res), int(ncls), int(nb), int(nr)
         self.stats = (0, 0)

@@ -53,6 +53,7 @@ const Knob kKnobs[] = {
        return c.init_window;
      }},
     {"cart_init_chunk", [](TdrConfig& c, int64_t v) { if (v >= 1) c.cart_init_chunk = std::min<int64_t>(v, 1 << 24); return c.cart_init_chunk; }},
+    {"inject_cand_chunk", [](TdrConfig& c, int64_t v) { if (v >= 1) c.inject_cand_chunk = std::min<int64_t>(v, 1 << 24); return c.inject_cand_chunk; }},
 };
 }  // namespace
 

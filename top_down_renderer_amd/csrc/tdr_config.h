@@ -58,6 +58,8 @@ struct TdrConfig {
   int batch_init_search = 0;
   int init_device = 1;              // 0: tdr_filter_initialize_particles keeps the host loop (A/B, tests)
   int64_t init_window = 1 << 21;    // words of the generator's stream per window of tdr_k_init_particles
+  // ---- sensor-resetting recovery (tdr_host_recover.cpp)
+  int64_t inject_cand_chunk = 65536;   // candidates per scoring launch of tdr_filter_inject_sensor, in whole slots
   // ---- weight statistics, running sum, generator (tdr_prefix.hip, tdr_rng.hip)
   int pfx_small = 1;      // 0 = without the one-launch kernel (A/B and debugging)
   int pfx_head = 64;      // leading elements the long running sum's walk adds one by one

@@ -200,6 +200,13 @@ struct tdr_filter {
   std::vector<float> gmm_means, gmm_covs;
   DevBuf<uint64_t> kld_ws;    // tdr_filter_kld_count: the key table for n_max and the two output words, allocated by the first call
   DevBuf<int64_t> inject_out;   // tdr_filter_inject: the count of injected slots, allocated by the first call
+  // tdr_filter_inject_sensor (tdr_host_recover.cpp), allocated by the first call: the list of injected slots (n words),
+  // {its length, the written slots}, the list build's workspace, and ONE chunk's candidate states, weights, order, the
+  // order's scratch and the scorer's workspaces — sized by "inject_cand_chunk", not by the number of candidates
+  DevBuf<int32_t> sr_list, sr_perm, sr_tmp;
+  DevBuf<int64_t> sr_count;
+  DevBuf<uint8_t> sr_list_ws;
+  DevBuf<float> sr_cst, sr_craw, sr_ws, sr_init_ws;
   DevBuf<float> ml_dev;  // fields + mlState of the max-likelihood particle of the last update (tdr_k_save_ml_state)
   bool have_ml = false;
   // meanLikelihood + computeMeanCov of the CURRENT particle set, as last read back: publishPoseEst asks for both in a row

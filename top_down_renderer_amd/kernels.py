@@ -852,6 +852,30 @@ class HipKernels:
         """tdr_inject_threshold_host: floor(p * 2^24), clamped to [0, 2^24]."""
         return int(self.lib.tdr_inject_threshold_host(C.c_double(p)))
 
+    # ---- sensor resetting (csrc/tdr_recover_sensor.hip; include/tdr.h, "sensor resetting") -----------------------------
+    def inject_list(self, n, seed, draw, threshold24, slot_begin=0, max_blocks=0):
+        """tdr_k_inject_list: the ascending local indices of the slots of [0, n) that inject would write (int32 device
+        tensor).  One read-back (the length)."""
+        lst = self.empty((max(n, 1),), torch.int32)
+        ws = self.empty((max(8, int(self.lib.tdr_inject_list_workspace_bytes(n))),), torch.uint8)
+        count = self.zeros((1,), torch.int64)
+        check(self.lib.tdr_k_inject_list(n, slot_begin, int(seed), int(draw), int(threshold24), _ptr(lst), _ptr(count), _ptr(ws),
+                                         int(max_blocks), self.stream()))
+        return lst[: int(count.item())]
+
+    def inject_candidates(self, st, n, lst, first, m, candidates, dmap, road, seed, draw, heading_mode, cand_st, slot_begin=0):
+        """tdr_k_inject_candidates: the states of the `candidates` candidates of list entries [first, first + m) into
+        cand_st (7, cand_cap), candidate (e - first) * candidates + j."""
+        check(self.lib.tdr_k_inject_candidates(_ptr(st), st.shape[1], n, slot_begin, _ptr(lst), first, m, int(candidates),
+                                               C.byref(dmap.desc), _ptr(road), road.numel(), int(seed), int(draw), int(heading_mode),
+                                               _ptr(cand_st), cand_st.shape[1], self.stream()))
+
+    def inject_select(self, st, n, lst, first, m, candidates, cand_st, cand_w, pick=None, written=None):
+        """tdr_k_inject_select: every slot of list entries [first, first + m) takes the first of its candidates of the
+        largest weight (a NaN counts as -1); pick (int32, m) and written (int64, 1; incremented) are optional."""
+        check(self.lib.tdr_k_inject_select(_ptr(st), st.shape[1], n, _ptr(lst), first, m, int(candidates), _ptr(cand_st),
+                                           cand_st.shape[1], _ptr(cand_w), _ptr(pick), _ptr(written), self.stream()))
+
     # ---- the particle picture (csrc/tdr_viz.hip) ---------------------------------------------------------------
     def viz_planes(self, H, W):
         """The four bit planes of an H x W picture, as one int32 tensor (cleared by viz_draw)."""

@@ -586,6 +586,73 @@ class ParticleFilter:
         state.w_slow, state.w_fast = nxt.w_slow, nxt.w_fast
         return p, injected
 
+    # ---- sensor resetting (include/tdr.h, "sensor resetting") ------------------------------------------------------------
+    def injectSensor(self, top_down_scan, res, p, candidates, heading_mode=0, seed=0, count=True):
+        """tdr_filter_inject_sensor's rule and launches on this filter's torch buffers: the slots inject() would write take
+        the best-scoring of `candidates` road candidates against top_down_scan (as update takes it).  One read-back (the
+        list's length); candidates are scored in chunks of tuning("inject_cand_chunk") with n_total = this filter's count.
+        Returns the number of written slots (None with count=False)."""
+        if self.comm.active:
+            raise ValueError("injectSensor is not available on a sharded filter (the handle path for a rank's slice is not built)")
+        p, res, C_ = float(p), float(res), int(candidates)
+        if not (math.isfinite(p) and 0.0 <= p <= 1.0):
+            raise ValueError("injectSensor: p must lie in [0, 1]")
+        if heading_mode not in (0, 1):
+            raise ValueError("injectSensor: heading_mode is 0 or 1")
+        if not 1 <= C_ <= 4096:
+            raise ValueError("injectSensor: candidates must lie in 1 .. 4096")
+        if not (math.isfinite(res) and res > 0.0):
+            raise ValueError("injectSensor: res must be finite and positive")
+        if self.num_particles_ < 1:
+            raise ValueError("injectSensor: the filter has no particles")
+        k, m, n = self.k, self.map_, self.num_particles_
+        road = m.roadCells()
+        scan_pk = m.scan_handle(top_down_scan)
+        th = k.inject_threshold(p)
+        lst = k.inject_list(n, seed, self.step_, th)
+        listed = int(lst.numel())
+        if listed == 0:
+            return 0 if count else None
+        per = min(max(1, k.tuning("inject_cand_chunk") // C_), listed)
+        ccap = (per * C_ + 63) // 64 * 64
+        cst, craw, perm = k.empty((7, ccap)), k.empty((ccap,)), k.empty((ccap,), torch.int32)
+        polar = getattr(m, "polar", True)
+        for lo in range(0, listed, per):
+            ms = min(per, listed - lo)
+            nc = ms * C_
+            k.inject_candidates(self.st, n, lst, lo, ms, C_, m.dev, road, seed, self.step_, heading_mode, cst)
+            if polar:
+                k.locality_order(cst, nc, m.rows, m.cols, perm)
+                k.score(m.dev, scan_pk, res, self.fp_c, cst, nc, craw, perm=perm, init_search=heading_mode == 0,
+                        uniform_scale=self._uniform_scale, n_total=n)
+            else:
+                rows, cols = m.window_shape()
+                if heading_mode == 0:
+                    k.score_cart_init(m.dev, scan_pk, rows, cols, res, self.fp_c, cst, nc, n_total=n)
+                k.locality_order_pose(cst, nc, m.rows, m.cols, perm, theta_radius=(rows + cols) / 16.0)
+                k.score_cart(m.dev, scan_pk, rows, cols, res, self.fp_c, cst, nc, craw, perm=perm, n_total=n)
+            k.inject_select(self.st, n, lst, lo, ms, C_, cst, craw)
+        if heading_mode == 0:
+            self._maybe_uninit = True
+        return listed if count else None
+
+    def recoveryStepSensor(self, state, params, candidates, top_down_scan, res):
+        """tdr_filter_recovery_step_sensor: recoveryStep's tracker and reset rule with injectSensor.  Returns (p, injected)."""
+        params = recovery_params_c(params)
+        if self.comm.active or self.num_particles_ < 1:
+            raise ValueError("recoveryStepSensor needs an unsharded filter with particles")
+        if not 1 <= int(candidates) <= 4096:
+            raise ValueError("recoveryStepSensor: candidates must lie in 1 .. 4096")
+        w_avg = float(self.weightStats()[2])
+        nxt = _lib.RecoveryStateC(state.w_slow, state.w_fast)
+        p = float(self.k.lib.tdr_recovery_track_host(C.byref(nxt), C.c_double(w_avg), C.byref(params)))
+        injected = 0
+        if p > 0.0:
+            injected = self.injectSensor(top_down_scan, res, p, candidates, params.heading_mode, params.seed)
+            self.k.lib.tdr_recovery_reset_host(C.byref(nxt))
+        state.w_slow, state.w_fast = nxt.w_slow, nxt.w_fast
+        return p, injected
+
     def computeMeanCov(self):
         if self.num_particles_ < 1:
             return np.zeros((4, 4), np.float32)

@@ -42,10 +42,15 @@ class CoreConfig:                       # the node's parameters that reach the s
     # on-road particles replace that share of the slots (the step's estimate is the un-injected set's).  0: never
     recovery_every: int = 0
     recovery: RecoveryParams = field(default_factory=RecoveryParams)
+    # sensor resetting (include/tdr.h, "sensor resetting"): above 1, a due recovery step gives every injected slot the
+    # best-scoring of this many road candidates against the step's render at the step's res.  1: the plain injection
+    recovery_candidates: int = 1
 
     def check(self):
         if self.recovery_every > 0:
             recovery_params_c(self.recovery)
+            if not 1 <= int(self.recovery_candidates) <= 4096:
+                raise ValueError("CoreConfig: recovery_candidates must lie in 1 .. 4096")
         if self.kld_every > 0 and self.gmm_every > 0:
             raise ValueError("CoreConfig: kld_every and gmm_every are two rules for one particle count; set one of them")
         if self.kld_every > 0:
@@ -105,7 +110,12 @@ class TopDownRenderCore:
         if self.countStepAndKldDue():
             self.kld_target_ = self.filter_.kldCount(self.cfg.kld)
         if self.countStepAndRecoveryDue():
-            self.last_recovery_ = self.filter_.recoveryStep(self.recovery_state_, self.cfg.recovery)
+            if self.cfg.recovery_candidates > 1:
+                self.last_recovery_ = self.filter_.recoveryStepSensor(self.recovery_state_, self.cfg.recovery,
+                                                                      self.cfg.recovery_candidates, self.renderer_.last_scan(),
+                                                                      float(self.last_res_))
+            else:
+                self.last_recovery_ = self.filter_.recoveryStep(self.recovery_state_, self.cfg.recovery)
         return e
 
     def countStepAndGmmDue(self):
