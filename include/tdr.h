@@ -660,7 +660,8 @@ int tdr_profile_su_list(int64_t out[2]);
  * each class from its plane; 0: the loop hands every four-ring step that holds such a bin to the C++ step (A/B, tests).
  * Integer sums: same bits.  Ring groups of 4, 8 or 16 rings.
  * "inject_cand_chunk" — candidates one scoring launch of tdr_filter_inject_sensor covers, in whole slots (>= 1; default
- * 65536; bounds the call's buffers; same results: "sensor resetting" below). */
+ * 65536; bounds the call's buffers; same results: "sensor resetting" below); tdr_filter_grid_search walks its list in the
+ * same chunks, in whole lattice points ("pose-grid search" below). */
 int64_t tdr_config_tuning(const char* name, int64_t value);
 /* The rows of score_polar_su_kernel's grid for nchunks ring groups with the last k cut into q sector ranges each (tests):
  * returns the row count R = (nchunks - k') + k' q', k' = k clamped to [0, nchunks], q' = q rounded down to 1, 2, 4 or 8; for
@@ -1707,6 +1708,99 @@ int tdr_filter_inject_sensor(tdr_filter* f, const float* scan_imgs, const tdr_re
 int tdr_filter_recovery_step_sensor(tdr_filter* f, tdr_recovery_state* s, const tdr_recovery_params* rp, int candidates,
                                     const float* scan_imgs, const tdr_renderer* renderer, float res, double* p_out,
                                     int64_t* injected_out);
+
+/* ---- pose-grid search: one scan scored over a lattice of map cells, the peaks found on the device (csrc/tdr_grid.hip,
+ * csrc/tdr_host_grid.cpp) --------------------------------------------------------------------------------------
+ * A DEFINITION, like the recovery injection and sensor resetting above (the reference has nothing to match), and a call of
+ * its own: without the call every byte of every existing path stays what it is.  Inputs: a filter, the scan, res, a
+ * tdr_grid_spec, the radius R and the number K of peaks asked for.
+ *   1. Lattice point g = iy * nx + ix (0 <= ix < nx, 0 <= iy < ny) stands on map cell c = c0 + ix * step (column),
+ *      r = r0 + iy * step (row), in 64-bit integers.  It is LISTED iff 0 <= c < cols, 0 <= r < rows and, with road_only,
+ *      the cell is a road cell by the road list's own test (the class-1 slot of its record holds a value < 1.f).  The LIST
+ *      is the listed g, ascending.
+ *   2. Candidate (g, h), 0 <= h < H = n_headings: init_x_px = ((float)c + 0.5f) * resolution, init_y_px = ((float)r + 0.5f) *
+ *      resolution (float32, no contraction; x goes with the column, as in the injection), dx_m = dy_m = 0, scale =
+ *      spec.scale.  heading_mode 1: theta = theta0 + (float)h * dtheta (float32, no contraction), have_init = 1.
+ *      heading_mode 0: theta = 0, have_init = 0 (H is 1).
+ *   3. A candidate's weight is the raw weight tdr_filter_compute_weights gives a particle in that state in THIS filter:
+ *      item 4 of "sensor resetting" with init_search = (heading_mode == 0), n_total = the filter's count, no geometric term.
+ *      The polar launch is told the uniform scale that tdr_filter_set_states would note for a set whose scales are all
+ *      spec.scale (spec.scale for a filter with a fixed or frozen scale, none otherwise), so a second filter that is handed
+ *      the lattice states scores them the same way.
+ *   4. Per listed g: key_h = w_h, or -1 where w_h is NaN; the pick is the smallest h whose key is the maximum (the pick rule
+ *      of sensor resetting).  W[g] = the pick's weight; T[g] = the pick's theta as scoring left it, or NaN if its have_init
+ *      is 0 after scoring.  Unlisted points have W = T = NaN (0x7fc00000).  vol[h * nx * ny + g] = w_h (optional), NaN
+ *      for unlisted points.
+ *   5. Peaks, radius R (0 .. 16 lattice points, Chebyshev).  g is ELIGIBLE iff W[g] > 0 (NaN, 0 and negative values are not).
+ *      g is a peak iff it is eligible and every other lattice point g' of its (2R+1)^2 window inside the lattice is not
+ *      eligible, or has W[g'] < W[g], or has W[g'] == W[g] and g' > g.  With R = 0 every eligible point is a peak; a plateau
+ *      has exactly one.  The output: n_peaks, and the first min(K, n_peaks) peaks in the order (w descending, g ascending),
+ *      K in 0 .. 4096; cell = r * cols + c.  The order is total, so any selection method gives the same bytes.
+ * Layer 1 (device pointers, asynchronous, no allocation).
+ *   tdr_k_grid_list: the list to list_out (nx * ny words) and its length to *count_dev (DEVICE), by the count / running sum
+ *     / write of the road list; workspace of tdr_grid_list_workspace_bytes(nx, ny) bytes; max_blocks as in
+ *     tdr_k_inject_list.  The map's records are read with road_only alone.
+ *   tdr_k_grid_candidates: for entries [first, first + m) of a list of n_list entries the SoA states
+ *     [TDR_ST_FIELDS][cand_cap], candidate q = (e - first) * H + h: one lane per candidate, no loads but the list.
+ *   tdr_k_grid_reduce: for the same entries, the weights cand_w[(e - first) * H + h] and the states as scoring left them:
+ *     W, T and (vol != NULL) the vol column of every listed point of the window, into planes the caller pre-filled with NaN.
+ *     One wave per point and the (key, -h) butterfly of tdr_k_inject_select; H == 1: one lane per point.
+ *   tdr_k_grid_peaks: the peaks of the W plane: *n_peaks_dev (DEVICE; set, not incremented) and, with max_peaks > 0, the
+ *     first min(max_peaks, n_peaks) entries of peaks_out (DEVICE, max_peaks entries; the rest is not written); workspace of
+ *     tdr_grid_peaks_workspace_bytes(nx, ny) bytes (0 for a lattice outside its ranges or when the sort's scratch size
+ *     cannot be asked: no device).  A tile of 16 x 16 points with its halo in LDS, comparisons on the
+ *     integer bits of the positive floats, then a descending radix sort of the peaks' keys.
+ *   Refused with TDR_ERR_ARG before any device work: null pointers, a spec outside the ranges given at the struct, a map
+ *   without cells (with road_only: without records or class 1), n_list outside 0 .. nx * ny, first < 0, m < 0,
+ *   first + m > n_list, m * H > cand_cap, nms_radius outside 0 .. 16, max_peaks outside 0 .. 4096.
+ * Handle layer.  tdr_filter_grid_search: the scan as tdr_filter_inject_sensor takes it (images, a renderer, or NULL, NULL:
+ *   the packed scan the filter keeps).  The launcher runs the list and WAITS ONCE for its length, then walks it in chunks of
+ *   max(1, tdr_config_tuning("inject_cand_chunk") / H) whole points (candidates, the scoring launches of sensor resetting,
+ *   the reduction), then the peaks, then ONE read-back.  w_out, theta_out (nx * ny floats), vol_out (H * nx * ny floats),
+ *   peaks_out (max_peaks entries; NULL: no peaks are ordered), n_peaks_out, listed_out (the list's length) are HOST
+ *   pointers and may be NULL.  Buffers are the filter's, allocated on first use and sized by the chunk and the lattice.  The
+ *   filter's states, raw and normalised weights, weight statistics, generator, mixture, step count and pending heading
+ *   search stay as they are; handed images, the filter keeps the packed scan as tdr_filter_inject_sensor does.  Refused like
+ *   tdr_filter_inject_sensor (sharded filters and filters without particles included; a map without a road cell is NOT
+ *   refused: its road-only list is empty), and: a spec outside its ranges, nms_radius, max_peaks.  A refused call writes
+ *   nothing.
+ *   tdr_filter_inject_cells: tdr_filter_inject with the caller's cell list (HOST, n_cells words r * cols + c) in place of
+ *   the map's road list: the same slots, the same words, the same kernel.  n_cells in 1 .. 2^24 and at most the map's cell
+ *   count (tdr_k_inject's bound on a list); every cell < rows * cols, checked on the host; duplicates are allowed and weight
+ *   the draw.  This is what turns peaks into particles: with heading_mode 0 the next update's search gives them headings.
+ *   The call returns after the list was uploaded.  Refusals and what stays untouched: tdr_filter_inject's. */
+typedef struct tdr_grid_spec {
+  int32_t c0, r0;        /* map cell (column, row) of lattice point (0, 0); may be negative or beyond the map */
+  int32_t step;          /* cells between neighbouring lattice points, >= 1 */
+  int32_t nx, ny;        /* lattice points per row, rows; >= 1 each, nx * ny <= 2^24 */
+  int32_t road_only;     /* 0 .. 1 */
+  int32_t heading_mode;  /* 0: no heading, the 40-rotation search; 1: n_headings fixed headings per point */
+  int32_t n_headings;    /* H.  mode 1: 1 .. 4096; mode 0: must be 1 */
+  float theta0, dtheta;  /* mode 1, finite: theta_h = theta0 + (float)h * dtheta, float32, no contraction */
+  float scale;           /* every candidate's scale; finite, > 0 */
+} tdr_grid_spec;
+typedef struct tdr_grid_peak {
+  int32_t g;
+  uint32_t cell;
+  float w, theta;
+} tdr_grid_peak;
+size_t tdr_grid_list_workspace_bytes(int nx, int ny);
+int tdr_k_grid_list(const tdr_map_desc* map, const tdr_grid_spec* spec, int32_t* list_out, int64_t* count_dev, void* workspace,
+                    int max_blocks, void* stream);
+int tdr_k_grid_candidates(const tdr_map_desc* map, const tdr_grid_spec* spec, const int32_t* list, int64_t n_list,
+                          int64_t first, int64_t m, float* cand_st, int64_t cand_cap, void* stream);
+int tdr_k_grid_reduce(const tdr_grid_spec* spec, const int32_t* list, int64_t n_list, int64_t first, int64_t m,
+                      const float* cand_st, int64_t cand_cap, const float* cand_w, float* w_plane, float* theta_plane, float* vol,
+                      void* stream);
+size_t tdr_grid_peaks_workspace_bytes(int nx, int ny);
+int tdr_k_grid_peaks(const tdr_map_desc* map, const tdr_grid_spec* spec, const float* w_plane, const float* theta_plane,
+                     int nms_radius, int max_peaks, tdr_grid_peak* peaks_out, int64_t* n_peaks_dev, void* workspace,
+                     void* stream);
+int tdr_filter_grid_search(tdr_filter* f, const float* scan_imgs, const tdr_renderer* renderer, float res,
+                           const tdr_grid_spec* spec, float* w_out, float* theta_out, float* vol_out, int nms_radius,
+                           int max_peaks, tdr_grid_peak* peaks_out, int64_t* n_peaks_out, int64_t* listed_out);
+int tdr_filter_inject_cells(tdr_filter* f, const uint32_t* cells_host, int64_t n_cells, double p, int heading_mode,
+                            uint64_t seed, int64_t* injected_out);
 
 /* internal: lets the handle layer (csrc/tdr_host_*.cpp) report through tdr_last_error() */
 int tdr_set_error(int code, const char* msg);

@@ -179,6 +179,25 @@ class ParticleFilter {
   }
   // {argmax bits, sum, mean, bottom_stddev, fallback, num_valid, num_under, 0} of the last update (particle_filter.cpp:107-147)
   void weightStats(float out8[8]) { check(tdr_filter_get_weight_stats(f_, out8), "weightStats"); }
+  // Pose-grid search (extension; include/tdr.h, "pose-grid search"): the renderer's last render (nullptr: the scan the
+  // filter kept) scored over the lattice of `spec` as a particle of this filter would be scored, and the peaks of the
+  // weight plane within nms_radius lattice points, the best max_peaks of them in order (tdr_filter_grid_search).  The
+  // filter is read, not changed.  Throws on a spec outside its ranges, nms_radius outside 0 .. 16, max_peaks outside
+  // 0 .. 4096, a res that is not finite and positive, an empty or sharded filter, and without a scan.
+  GridSearchResult gridSearch(const ScanRenderer* renderer, float res, const tdr_grid_spec& spec, int nms_radius = 2,
+                              int max_peaks = 8, bool with_vol = false) {
+    GridSearchResult out;
+    check(gridSearchInto(f_, renderer ? renderer->handle() : nullptr, res, spec, nms_radius, max_peaks, with_vol, out), "gridSearch");
+    return out;
+  }
+  // ... and what turns its peaks into particles: inject() with the caller's cell list (r * cols + c; duplicates weight the
+  // draw) in place of the map's road list (tdr_filter_inject_cells)
+  int64_t injectCells(const std::vector<uint32_t>& cells, double p, int heading_mode = 0, uint64_t seed = 0, bool count = true) {
+    int64_t injected = -1;
+    check(tdr_filter_inject_cells(f_, cells.data(), (int64_t)cells.size(), p, heading_mode, seed, count ? &injected : nullptr),
+          "injectCells");
+    return injected;
+  }
   void computeCov(Eigen::Matrix4f& cov) { stat(1, nullptr, &cov); }                        // :226-236
   void maxLikelihood(Eigen::Vector4f& state) { stat(1, &state, nullptr); }                 // :222-224
   void computeMeanCov(Eigen::Matrix4f& cov) { stat(0, nullptr, &cov); }                    // :205-220

@@ -59,6 +59,42 @@ struct KldParams : tdr_kld_params {
 struct RecoveryParams : tdr_recovery_params {
   RecoveryParams() : tdr_recovery_params{0.001, 0.1, 0.5, 0, 0} {}
 };
+// Pose-grid search (extension; include/tdr.h, "pose-grid search"): a lattice of map cells without headings (the 40-rotation
+// search gives each point one), road cells only, at scale 1; and what ParticleFilter::gridSearch returns: the planes W and
+// T (ny rows of nx points; NaN where a point is not listed), vol (H planes, when asked for), the first peaks in the order
+// (w descending, g ascending), the number of peaks and of listed points.
+struct GridSpec : tdr_grid_spec {
+  GridSpec() : tdr_grid_spec{0, 0, 1, 1, 1, 1, 0, 1, 0.f, 0.f, 1.f} {}
+  GridSpec(int c0_, int r0_, int step_, int nx_, int ny_) : tdr_grid_spec{c0_, r0_, step_, nx_, ny_, 1, 0, 1, 0.f, 0.f, 1.f} {}
+};
+struct GridSearchResult {
+  int nx = 0, ny = 0, n_headings = 0;
+  std::vector<float> w, theta, vol;
+  std::vector<tdr_grid_peak> peaks;
+  int64_t n_peaks = 0, listed = 0;
+};
+// ParticleFilter::gridSearch and ParticleFilterCartesian::gridSearch: tdr_filter_grid_search into a GridSearchResult; the
+// return code is the caller's to report
+inline int gridSearchInto(tdr_filter* f, const tdr_renderer* renderer, float res, const tdr_grid_spec& spec, int nms_radius,
+                          int max_peaks, bool with_vol, GridSearchResult& out) {
+  const size_t G = spec.nx > 0 && spec.ny > 0 ? (size_t)spec.nx * (size_t)spec.ny : 0;
+  const size_t H = spec.n_headings > 0 ? (size_t)spec.n_headings : 0;
+  if (G <= ((size_t)1 << 24) && H <= 4096) {   // (a spec beyond its ranges is refused below, before anything is written)
+    out.w.resize(G);
+    out.theta.resize(G);
+    if (with_vol) out.vol.resize(G * H);
+  }
+  out.peaks.resize(max_peaks > 0 && max_peaks <= 4096 ? (size_t)max_peaks : 0);
+  const int rc = tdr_filter_grid_search(f, nullptr, renderer, res, &spec, out.w.data(), out.theta.data(),
+                                        with_vol ? out.vol.data() : nullptr, nms_radius, max_peaks, out.peaks.data(), &out.n_peaks,
+                                        &out.listed);
+  if (rc != TDR_OK) return rc;
+  out.nx = spec.nx;
+  out.ny = spec.ny;
+  out.n_headings = spec.n_headings;
+  out.peaks.resize((size_t)(out.n_peaks < (int64_t)out.peaks.size() ? out.n_peaks : (int64_t)out.peaks.size()));
+  return rc;
+}
 inline bool sameKldParams(const tdr_kld_params& a, const tdr_kld_params& b) {
   return a.bin_xy_px == b.bin_xy_px && a.theta_bins == b.theta_bins && a.scale_bits == b.scale_bits &&
          a.epsilon == b.epsilon && a.z == b.z && a.n_min == b.n_min;

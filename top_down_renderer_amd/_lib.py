@@ -3,6 +3,8 @@ device is present, the product path raises."""
 import ctypes as C
 import os
 
+import numpy as np
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("TDR_LIB_PATH") or os.path.join(_PKG, "libtdr_hip.so")   # override: tuning variants only
 
@@ -118,6 +120,27 @@ class RecoveryParamsC(C.Structure):
     """tdr_recovery_params."""
     _fields_ = [("alpha_slow", C.c_double), ("alpha_fast", C.c_double), ("p_max", C.c_double), ("heading_mode", C.c_int32),
                 ("seed", C.c_uint64)]
+
+
+class GridSpecC(C.Structure):
+    """tdr_grid_spec (include/tdr.h, "pose-grid search"): the lattice, its headings and the candidates' scale."""
+    _fields_ = [("c0", C.c_int32), ("r0", C.c_int32), ("step", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32),
+                ("road_only", C.c_int32), ("heading_mode", C.c_int32), ("n_headings", C.c_int32), ("theta0", C.c_float),
+                ("dtheta", C.c_float), ("scale", C.c_float)]
+
+
+class GridPeakC(C.Structure):
+    """tdr_grid_peak: lattice point, map cell r * cols + c, weight and heading of one peak."""
+    _fields_ = [("g", C.c_int32), ("cell", C.c_uint32), ("w", C.c_float), ("theta", C.c_float)]
+
+
+GRID_PEAK_DTYPE = np.dtype([("g", "<i4"), ("cell", "<u4"), ("w", "<f4"), ("theta", "<f4")])   # tdr_grid_peak
+
+
+def grid_spec(c0, r0, step, nx, ny, road_only=1, heading_mode=0, n_headings=1, theta0=0.0, dtheta=0.0, scale=1.0):
+    """A GridSpecC from plain numbers (include/tdr.h, "pose-grid search")."""
+    return GridSpecC(int(c0), int(r0), int(step), int(nx), int(ny), int(road_only), int(heading_mode), int(n_headings),
+                     float(theta0), float(dtheta), float(scale))
 
 
 class PoseStatsC(C.Structure):
@@ -442,6 +465,15 @@ SIGNATURES = {
     "tdr_filter_inject_sensor": (_i, [_vp, _vp, _vp, _f, C.c_double, _i, _i, _u64, C.POINTER(_i64)]),
     "tdr_filter_recovery_step_sensor": (_i, [_vp, C.POINTER(RecoveryStateC), C.POINTER(RecoveryParamsC), _i, _vp, _vp, _f,
                                              C.POINTER(C.c_double), C.POINTER(_i64)]),
+    # pose-grid search (csrc/tdr_grid.hip, csrc/tdr_host_grid.cpp)
+    "tdr_grid_list_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "tdr_k_grid_list": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "tdr_k_grid_candidates": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "tdr_k_grid_reduce": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "tdr_grid_peaks_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "tdr_k_grid_peaks": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "tdr_filter_grid_search": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "tdr_filter_inject_cells": (_i, [_vp, _vp, _i64, C.c_double, _i, _u64, C.POINTER(_i64)]),
     "tdr_set_error": (_i, [_i, C.c_char_p]),
     "tdr_locality_tmp_ints": (C.c_size_t, [_i64, _i, _i]),
     "tdr_locality_pose_tmp_ints": (C.c_size_t, [_i64]),

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import BatchCloudC, BatchInputC, FilterParamsC, PoseStatsC, VizRequestC, check
-from .particle_filter import kld_params_c, recovery_params_c
+from .particle_filter import GridResult, kld_params_c, recovery_params_c
 
 _vp = C.c_void_p
 STATE_DTYPE = np.dtype([("init_x_px", "<f4"), ("init_y_px", "<f4"), ("dx_m", "<f4"), ("dy_m", "<f4"), ("theta", "<f4"),
@@ -359,6 +359,33 @@ class FilterHandle:
         imgs, rh, keep = self._scan_args(scan)
         check(self.L.tdr_filter_inject_sensor(self.h, imgs, rh, C.c_float(res), C.c_double(p), int(candidates), int(heading_mode),
                                               int(seed), C.byref(n) if count else None))
+        return n.value if count else None
+
+    def grid_search(self, scan, res, spec, nms_radius=2, max_peaks=8, vol=False):
+        """tdr_filter_grid_search: `scan` (a Renderer, images, or None: the scan the filter kept) scored over the lattice of
+        spec (a _lib.GridSpecC) as a particle of this filter would be, and the peaks of the weight plane.  Returns a
+        particle_filter.GridResult; the filter is read, not changed."""
+        nx, ny, H = int(spec.nx), int(spec.ny), int(spec.n_headings)
+        G = max(nx, 0) * max(ny, 0)
+        nan = np.float32("nan")
+        w, t = np.full(G, nan, np.float32), np.full(G, nan, np.float32)
+        v = np.full(G * max(H, 0), nan, np.float32) if vol else None
+        peaks = np.zeros(max(int(max_peaks), 1), _lib.GRID_PEAK_DTYPE)
+        n_peaks, listed = C.c_int64(0), C.c_int64(0)
+        imgs, rh, keep = self._scan_args(scan)
+        check(self.L.tdr_filter_grid_search(self.h, imgs, rh, C.c_float(res), C.byref(spec), _ptr(w), _ptr(t),
+                                            _ptr(v) if vol else None, int(nms_radius), int(max_peaks), _ptr(peaks),
+                                            C.byref(n_peaks), C.byref(listed)))
+        return GridResult(w.reshape(ny, nx), t.reshape(ny, nx), v.reshape(H, ny, nx) if vol else None,
+                          peaks[: min(int(max_peaks), n_peaks.value)].copy(), n_peaks.value, listed.value)
+
+    def inject_cells(self, cells, p, heading_mode=0, seed=0, count=True):
+        """tdr_filter_inject_cells: inject() with the caller's cell list (r * cols + c, duplicates weight the draw) in place
+        of the map's road list.  Returns the number of injected slots, or None with count=False."""
+        cells = np.ascontiguousarray(cells, np.uint32).ravel()
+        n = C.c_int64(0)
+        check(self.L.tdr_filter_inject_cells(self.h, _ptr(cells), len(cells), C.c_double(p), int(heading_mode), int(seed),
+                                             C.byref(n) if count else None))
         return n.value if count else None
 
     def recovery_step_sensor(self, state, params, candidates, scan, res):

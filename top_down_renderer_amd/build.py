@@ -13,8 +13,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 SRC = [os.path.join(PKG, "csrc", f) for f in
        ("tdr_core.hip", "tdr_map.hip", "tdr_raster.hip", "tdr_score.hip", "tdr_score_init.hip", "tdr_score_su.hip", "tdr_score_ray.hip", "tdr_score_cart.hip", "tdr_score_cart_init.hip", "tdr_filter.hip", "tdr_rng.hip", "tdr_prefix.hip",
-        "tdr_geo.hip", "tdr_cmap.hip", "tdr_active.hip", "tdr_poly.hip", "tdr_batch.hip", "tdr_batch_loop.hip", "tdr_init.hip", "tdr_map_incr.hip", "tdr_viz.hip", "tdr_scan_viz.hip", "tdr_gmm.hip", "tdr_fuse.hip", "tdr_kld.hip", "tdr_recover.hip", "tdr_recover_sensor.hip", "tdr_eig.cpp", "tdr_host_map.cpp", "tdr_host_map_load.cpp", "tdr_host_renderer.cpp", "tdr_host_filter.cpp",
-        "tdr_host_batch.cpp", "tdr_host_gmm.cpp", "tdr_host_fuse.cpp", "tdr_host_kld.cpp", "tdr_host_recover.cpp", "tdr_host_selftest.cpp", "tdr_config.cpp", "tdr_comm.cpp", "tdr_gmm.cpp", "tdr_png.cpp",
+        "tdr_geo.hip", "tdr_cmap.hip", "tdr_active.hip", "tdr_poly.hip", "tdr_batch.hip", "tdr_batch_loop.hip", "tdr_init.hip", "tdr_map_incr.hip", "tdr_viz.hip", "tdr_scan_viz.hip", "tdr_gmm.hip", "tdr_fuse.hip", "tdr_kld.hip", "tdr_recover.hip", "tdr_recover_sensor.hip", "tdr_grid.hip", "tdr_eig.cpp", "tdr_host_map.cpp", "tdr_host_map_load.cpp", "tdr_host_renderer.cpp", "tdr_host_filter.cpp",
+        "tdr_host_batch.cpp", "tdr_host_gmm.cpp", "tdr_host_fuse.cpp", "tdr_host_kld.cpp", "tdr_host_recover.cpp", "tdr_host_grid.cpp", "tdr_host_selftest.cpp", "tdr_config.cpp", "tdr_comm.cpp", "tdr_gmm.cpp", "tdr_png.cpp",
         "tdr_svg.cpp")]
 # every header: a changed one rebuilds every translation unit (no per-file dependency tracking)
 HDR = [os.path.join(ROOT, "include", "tdr.h")] + sorted(glob.glob(os.path.join(PKG, "csrc", "*.h")))

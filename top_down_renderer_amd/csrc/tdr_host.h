@@ -207,6 +207,16 @@ struct tdr_filter {
   DevBuf<int64_t> sr_count;
   DevBuf<uint8_t> sr_list_ws;
   DevBuf<float> sr_cst, sr_craw, sr_ws, sr_init_ws;
+  // tdr_filter_grid_search (tdr_host_grid.cpp), allocated by the first call and sized by the lattice: the list of lattice
+  // points, {its length, the number of peaks}, the list build's workspace, the W, T and vol planes, the peaks and the
+  // workspace of the peak search.  A chunk's candidates, weights and scorer workspaces are the sr_* buffers above.
+  // gs_cells: the caller's cell list of tdr_filter_inject_cells.
+  DevBuf<int32_t> gs_list;
+  DevBuf<int64_t> gs_count;
+  DevBuf<uint8_t> gs_list_ws, gs_peaks_ws;
+  DevBuf<float> gs_w, gs_t, gs_vol;
+  DevBuf<tdr_grid_peak> gs_peaks;
+  DevBuf<uint32_t> gs_cells;
   DevBuf<float> ml_dev;  // fields + mlState of the max-likelihood particle of the last update (tdr_k_save_ml_state)
   bool have_ml = false;
   // meanLikelihood + computeMeanCov of the CURRENT particle set, as last read back: publishPoseEst asks for both in a row
@@ -261,5 +271,13 @@ int rng_to_host(tdr_filter* f);
 bool rng_device_capable(const tdr_filter* f);
 int filter_global_states(tdr_filter* f, const float** st, int64_t* cap);
 int viz_pub_dim(int dim, float s);   // a published dimension of the particle picture; invalid outside 1 .. 32768
+// tdr_host_recover.cpp: the checks and notes of an injection; the scan of a sensor-resetting call (checked without a
+// write, then taken: packed on the filter's stream) and the raw weights of nc candidate states in f->sr_cst (plane stride
+// ccap) as a particle of THIS filter would be scored, to f->sr_craw
+int inject_check_p(double p, int heading_mode, const char* who);
+void inject_note(tdr_filter* f, uint32_t threshold24, int heading_mode);
+int sensor_check_scan(tdr_filter* f, const float* scan_imgs, const tdr_renderer* renderer, const char* who);
+int sensor_take_scan(tdr_filter* f, const float* scan_imgs, const tdr_renderer* renderer, const float** pk);
+int sensor_score(tdr_filter* f, const float* pk, float res, int64_t nc, int64_t ccap, bool init_search, float uniform_scale);
 }  // namespace tdrh
 #endif  // TDR_HOST_H_

@@ -6,14 +6,22 @@
 // tdr_filter_recovery_step_sensor.
 #include "tdr_host.h"
 
-namespace {
-thread_local StageCtx g_inject_stage;
-
+namespace tdrh {   // called by tdr_host_grid.cpp too (prototypes in tdr_host.h)
 int inject_check_p(double p, int heading_mode, const char* who) {
   if (!std::isfinite(p) || p < 0. || p > 1.) return failh(TDR_ERR_ARG, "%s: p = %g (0 .. 1)", who, p);
   if (heading_mode < 0 || heading_mode > 1) return failh(TDR_ERR_ARG, "%s: heading_mode = %d (0 .. 1)", who, heading_mode);
   return TDR_OK;
 }
+void inject_note(tdr_filter* f, uint32_t threshold24, int heading_mode) {
+  if (threshold24 == 0) return;
+  f->states_changed();
+  if (heading_mode == 0) f->maybe_uninit = true;
+}
+}  // namespace tdrh
+
+namespace {
+thread_local StageCtx g_inject_stage;
+
 int recovery_check(const tdr_recovery_params* rp, const char* who) {
   if (!rp) return failh(TDR_ERR_ARG, "%s: null parameters", who);
   if (!(rp->alpha_slow > 0.) || !(rp->alpha_slow <= 1.)) return failh(TDR_ERR_ARG, "%s: alpha_slow = %g (0 < alpha <= 1)", who, rp->alpha_slow);
@@ -26,11 +34,6 @@ int inject_check_filter(tdr_filter* f, const char* who, const uint32_t** road, i
   if (f->n < 1) return failh(TDR_ERR_ARG, "%s: the filter has no particles", who);
   if (!f->map) return failh(TDR_ERR_ARG, "%s: the filter has no map", who);
   return tdr_map_road_cells(f->map, road, n_road);
-}
-void inject_note(tdr_filter* f, uint32_t threshold24, int heading_mode) {
-  if (threshold24 == 0) return;
-  f->states_changed();
-  if (heading_mode == 0) f->maybe_uninit = true;
 }
 // `s` continues after everything already queued on the filters' own streams
 int inject_wait_filters(tdr_filter* const* fl, int k, hipStream_t s) {
@@ -56,6 +59,9 @@ int sensor_check(int candidates, float res, const char* who) {
   if (!std::isfinite(res) || !(res > 0.f)) return failh(TDR_ERR_ARG, "%s: res = %g (finite, > 0)", who, (double)res);
   return TDR_OK;
 }
+}  // namespace
+
+namespace tdrh {   // called by tdr_host_grid.cpp too (prototypes in tdr_host.h)
 // The scan of the call as filter_score (tdr_host_filter.cpp) takes it, checked; nothing is written.  NULL, NULL: the packed
 // scan the filter keeps from the last scoring call that was handed images.
 int sensor_check_scan(tdr_filter* f, const float* scan_imgs, const tdr_renderer* renderer, const char* who) {
@@ -95,8 +101,9 @@ int sensor_take_scan(tdr_filter* f, const float* scan_imgs, const tdr_renderer* 
   return TDR_OK;
 }
 // The raw weights tdr_filter_compute_weights gives nc particles in the states cst (plane stride ccap) in THIS filter:
-// filter_score's launches (tdr_host_filter.cpp) with n_total = f->n; init_search: the 40-rotation search first.
-int sensor_score(tdr_filter* f, const float* pk, float res, int64_t nc, int64_t ccap, bool init_search) {
+// filter_score's launches (tdr_host_filter.cpp) with n_total = f->n; init_search: the 40-rotation search first;
+// uniform_scale: what set_states would note for the candidates (0: their scales differ), for the polar launch.
+int sensor_score(tdr_filter* f, const float* pk, float res, int64_t nc, int64_t ccap, bool init_search, float uniform_scale) {
   tdr_map* m = f->map;
   hipStream_t s = f->stream;
   const int ncls = m->desc.ncls, nb = f->cart ? m->win_rows : m->nb, nr = f->cart ? m->win_cols : m->nr;
@@ -120,10 +127,13 @@ int sensor_score(tdr_filter* f, const float* pk, float res, int64_t nc, int64_t 
   const bool uses_rec16 = init_search && m->desc.rec16 && f->n >= tdr_cfg().rec16_min;
   if (uses_rec16) TTRY(map_rec16_begin(m, s));
   TTRY(tdr_k_score_polar(&m->desc, m->tab.p, pk, nb, nr, res, &f->fp, f->sr_cst.p, ccap, nc, f->n, f->sr_perm.p,
-                         f->uniform_scale, init_search ? 1 : 0, f->sr_craw.p, f->sr_ws.p, s));
+                         uniform_scale, init_search ? 1 : 0, f->sr_craw.p, f->sr_ws.p, s));
   if (uses_rec16) TTRY(map_rec16_end(m, s));
   return TDR_OK;
 }
+}  // namespace tdrh
+
+namespace {
 // The launcher: the list and ONE wait for its length, then per chunk of whole slots the candidates, their scores in this
 // filter and the pick.  written_dev (may be NULL) is incremented by the written slots; *listed: the list's length.
 int sensor_inject(tdr_filter* f, const float* pk, float res, uint32_t th, int C, int heading_mode, uint64_t seed,
@@ -151,7 +161,7 @@ int sensor_inject(tdr_filter* f, const float* pk, float res, uint32_t th, int C,
     const int64_t mslots = std::min(per, listed - lo), nc = mslots * C;
     TTRY(tdr_k_inject_candidates(f->st.p, f->cap, n, 0, f->sr_list.p, lo, mslots, C, &f->map->desc, road, n_road, seed, f->step,
                                  heading_mode, f->sr_cst.p, ccap, s));
-    TTRY(sensor_score(f, pk, res, nc, ccap, heading_mode == 0));
+    TTRY(sensor_score(f, pk, res, nc, ccap, heading_mode == 0, f->uniform_scale));
     TTRY(tdr_k_inject_select(f->st.p, f->cap, n, f->sr_list.p, lo, mslots, C, f->sr_cst.p, ccap, f->sr_craw.p, nullptr,
                              written_dev, s));
   }

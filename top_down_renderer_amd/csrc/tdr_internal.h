@@ -24,6 +24,8 @@ int tdr_poly_grid(int width, int height, float resolution, int* rows, int* cols)
 int tdr_poly_fill(const float* verts, const int64_t* offs, const int32_t* cls, int64_t n_poly, int width, int height,
                   float resolution, int ncls, const uint32_t* excl_above, uint8_t* planes_cm, uint8_t* raster,
                   hipStream_t s);
+// tdr_grid.hip: the ranges of a tdr_grid_spec (include/tdr.h, "pose-grid search"); TDR_ERR_ARG with `who` in the message
+int tdr_grid_spec_check(const tdr_grid_spec* spec, const char* who);
 // tdr_svg.cpp
 int tdr_svg_parse_internal(const char* path, float* w, float* h, std::vector<uint32_t>& keys, std::vector<int64_t>& offs,
                            std::vector<float>& verts);

@@ -1,92 +1,31 @@
 // tdr_recover.hip — recovery injection (include/tdr.h, "recovery injection"): the road list of a map and
 // the kernel that overwrites a random share of a filter's slots with fresh on-road particles.
 //   road list: the cells whose class-1 slot is below 1 (ini_on_road's predicate, tdr_init.hip), in ascending cell index.
-//     road_count_kernel   one cell per lane, ballot + bit count per wave, the workgroup's count to the workspace;
-//     road_scan_kernel    ONE workgroup: the exclusive running sum of the workgroups' counts, 1024 at a turn, and the total;
-//     road_write_kernel   the predicate again; a road cell's place = its workgroup's offset + the waves before it + the
-//                         road lanes below it.  The order is the cell order whatever the grid does.
+//     the count / running sum / write of tdr_compact_dev.h behind the predicate RoadCell: the order is the cell order
+//     whatever the grid does.
 //   inject_kernel: lane = slot.  The Philox words of a slot depend on (seed, draw, slot, purpose) alone (tdr_philox.h), so
 //     the result does not depend on the grid, the wave order or the rank.  One 4-byte load from the road list per injected
 //     lane (scattered by nature), vector stores to the planes of injected slots only, ballot + bit count per wave and one
 //     64-bit integer atomic per wave that injected something.
 #include "tdr_common.h"
+#include "tdr_compact_dev.h"
 #include "tdr_philox.h"
 
 namespace {
 constexpr int REC_BLOCK = 256;
-constexpr int REC_WAVES = REC_BLOCK / 64;
-constexpr int REC_SCAN_BLOCK = 1024;
 constexpr int INJ_MAX_BLOCKS = 2048;    // grid.x: a workgroup strides over its job's slots beyond that
 constexpr int INJ_JOBS_BLOCKS_X = 256;  // ... and the grid.x of a job table, whose sizes the host does not see
 
-struct RoadArgs {
+struct RoadCell {   // the predicate of the road list (tdr_compact_dev.h)
   const float* rec;
   int rf, cols;
   int64_t ncell;
+  __device__ __forceinline__ bool operator()(int64_t i) const {
+    if (i >= ncell) return false;
+    const int64_t r = i / cols, c = i - r * cols;
+    return rec[((r + 1) * (cols + 2) + (c + 1)) * rf + 1] < 1.f;
+  }
 };
-__device__ __forceinline__ bool road_cell(const RoadArgs& a, int64_t i) {
-  const int64_t r = i / a.cols, c = i - r * a.cols;
-  return a.rec[((r + 1) * (a.cols + 2) + (c + 1)) * a.rf + 1] < 1.f;
-}
-
-__global__ __launch_bounds__(REC_BLOCK) void road_count_kernel(RoadArgs a, int64_t* __restrict__ block_count) {
-  __shared__ int sh[REC_WAVES];
-  const int64_t i = (int64_t)blockIdx.x * REC_BLOCK + threadIdx.x;
-  const bool on = i < a.ncell && road_cell(a, i);
-  const int cnt = __popcll(__ballot(on));
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int w = 0; w < REC_WAVES; w++) t += sh[w];
-    block_count[blockIdx.x] = t;
-  }
-}
-
-// counts [nb] -> exclusive offsets in place; *total = their sum
-__global__ __launch_bounds__(REC_SCAN_BLOCK) void road_scan_kernel(int64_t* __restrict__ v, int64_t nb, int64_t* __restrict__ total) {
-  __shared__ int64_t wsum[REC_SCAN_BLOCK / 64];
-  __shared__ int64_t carry_sh;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_sh = 0;
-  __syncthreads();
-  for (int64_t b0 = 0; b0 < nb; b0 += REC_SCAN_BLOCK) {
-    const int64_t b = b0 + threadIdx.x;
-    const int64_t x = b < nb ? v[b] : 0;
-    int64_t inc = x;   // inclusive sum inside the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)inc, off, 64);
-      const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)((uint64_t)inc >> 32), off, 64);
-      if (lane >= off) inc += (int64_t)((uint64_t)hi << 32 | lo);
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int64_t before = carry_sh;
-    for (int w = 0; w < wave; w++) before += wsum[w];
-    if (b < nb) v[b] = before + inc - x;
-    __syncthreads();
-    if (threadIdx.x == REC_SCAN_BLOCK - 1) carry_sh = before + inc;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = carry_sh;
-}
-
-__global__ __launch_bounds__(REC_BLOCK) void road_write_kernel(RoadArgs a, const int64_t* __restrict__ block_off,
-                                                               uint32_t* __restrict__ cells) {
-  __shared__ int sh[REC_WAVES];
-  const int64_t i = (int64_t)blockIdx.x * REC_BLOCK + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool on = i < a.ncell && road_cell(a, i);
-  const uint64_t m = __ballot(on);
-  if (lane == 0) sh[wave] = __popcll(m);
-  __syncthreads();
-  if (!on) return;
-  int64_t at = block_off[blockIdx.x];
-  for (int w = 0; w < wave; w++) at += sh[w];
-  at += __popcll(m & (((uint64_t)1 << lane) - 1));
-  cells[at] = (uint32_t)i;   // at < the count of road cells <= ncell: the caller's cells_out holds ncell words
-}
 
 struct InjectArgs {
   const tdr_inject_job* jobs;   // DEVICE, or NULL: `one`
@@ -151,16 +90,8 @@ extern "C" int tdr_k_map_road_cells(const tdr_map_desc* map, uint32_t* cells_out
   if (int rc = road_check(map, "map_road_cells")) return rc;
   if (!cells_out || !count_dev || !workspace) return fail(TDR_ERR_ARG, "map_road_cells: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  RoadArgs a{map->rec, map->rec_floats, map->cols, (int64_t)map->rows * map->cols};
-  const int64_t nb = cdiv(a.ncell, REC_BLOCK);
-  int64_t* blocks = reinterpret_cast<int64_t*>(workspace);
-  hipLaunchKernelGGL(road_count_kernel, dim3((unsigned)nb), dim3(REC_BLOCK), 0, s, a, blocks);
-  LAUNCH_CHECK("road_count");
-  hipLaunchKernelGGL(road_scan_kernel, dim3(1), dim3(REC_SCAN_BLOCK), 0, s, blocks, nb, count_dev);
-  LAUNCH_CHECK("road_scan");
-  hipLaunchKernelGGL(road_write_kernel, dim3((unsigned)nb), dim3(REC_BLOCK), 0, s, a, (const int64_t*)blocks, cells_out);
-  LAUNCH_CHECK("road_write");
-  return TDR_OK;
+  RoadCell a{map->rec, map->rec_floats, map->cols, (int64_t)map->rows * map->cols};
+  return tdrcmp::cmp_list("map_road_cells", a, a.ncell, cells_out, count_dev, workspace, 0, s);
 }
 
 extern "C" uint32_t tdr_inject_threshold_host(double p) {

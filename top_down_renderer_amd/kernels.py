@@ -876,6 +876,48 @@ class HipKernels:
         check(self.lib.tdr_k_inject_select(_ptr(st), st.shape[1], n, _ptr(lst), first, m, int(candidates), _ptr(cand_st),
                                            cand_st.shape[1], _ptr(cand_w), _ptr(pick), _ptr(written), self.stream()))
 
+    # ---- pose-grid search (csrc/tdr_grid.hip; include/tdr.h, "pose-grid search") -----------------------------------------
+    def grid_list(self, dmap, spec, max_blocks=0):
+        """tdr_k_grid_list: the ascending lattice points of spec (a _lib.GridSpecC) that stand on a cell (with road_only: a
+        road cell) of the DeviceMap (int32 device tensor).  One read-back (the length)."""
+        G = int(spec.nx) * int(spec.ny)
+        lst = self.empty((max(G, 1),), torch.int32)
+        ws = self.empty((max(8, int(self.lib.tdr_grid_list_workspace_bytes(int(spec.nx), int(spec.ny)))),), torch.uint8)
+        count = self.zeros((1,), torch.int64)
+        check(self.lib.tdr_k_grid_list(C.byref(dmap.desc), C.byref(spec), _ptr(lst), _ptr(count), _ptr(ws), int(max_blocks),
+                                       self.stream()))
+        return lst[: int(count.item())]
+
+    def grid_candidates(self, dmap, spec, lst, first, m, cand_st):
+        """tdr_k_grid_candidates: the states of the H candidates of list entries [first, first + m) into cand_st
+        (7, cand_cap), candidate (e - first) * H + h."""
+        check(self.lib.tdr_k_grid_candidates(C.byref(dmap.desc), C.byref(spec), _ptr(lst), lst.numel(), first, m, _ptr(cand_st),
+                                             cand_st.shape[1], self.stream()))
+
+    def grid_planes(self, spec, vol=False):
+        """The W and T planes (and the H-deep vol) of a lattice, filled with the NaN of unlisted points."""
+        G = int(spec.nx) * int(spec.ny)
+        nan = lambda n: self.to_device(np.full(n, 0x7FC00000, np.uint32).view(np.float32))
+        return nan(G), nan(G), (nan(G * int(spec.n_headings)) if vol else None)
+
+    def grid_reduce(self, spec, lst, first, m, cand_st, cand_w, w_plane, t_plane, vol=None):
+        """tdr_k_grid_reduce: W, T and the vol column of list entries [first, first + m) from their H weights and the states
+        as scoring left them."""
+        check(self.lib.tdr_k_grid_reduce(C.byref(spec), _ptr(lst), lst.numel(), first, m, _ptr(cand_st), cand_st.shape[1],
+                                         _ptr(cand_w), _ptr(w_plane), _ptr(t_plane), _ptr(vol), self.stream()))
+
+    def grid_peaks(self, dmap, spec, w_plane, t_plane, radius, max_peaks):
+        """tdr_k_grid_peaks: (the first min(max_peaks, n_peaks) peaks as a _lib.GRID_PEAK_DTYPE array, n_peaks).  One
+        read-back."""
+        ws = self.empty((max(8, int(self.lib.tdr_grid_peaks_workspace_bytes(int(spec.nx), int(spec.ny)))),), torch.uint8)
+        count = self.zeros((1,), torch.int64)
+        peaks = self.zeros((max(int(max_peaks), 1), 4), torch.int32)
+        check(self.lib.tdr_k_grid_peaks(C.byref(dmap.desc), C.byref(spec), _ptr(w_plane), _ptr(t_plane), int(radius), int(max_peaks),
+                                        _ptr(peaks), _ptr(count), _ptr(ws), self.stream()))
+        n = int(count.item())
+        out = peaks.cpu().numpy().view(_lib.GRID_PEAK_DTYPE).reshape(-1)
+        return out[: min(int(max_peaks), n)].copy(), n
+
     # ---- the particle picture (csrc/tdr_viz.hip) ---------------------------------------------------------------
     def viz_planes(self, H, W):
         """The four bit planes of an H x W picture, as one int32 tensor (cleared by viz_draw)."""

@@ -98,6 +98,19 @@ class RecoveryParams:
                                     int(self.seed))
 
 
+@dataclass
+class GridResult:
+    """What a pose-grid search gives (include/tdr.h, "pose-grid search"): the planes W and T (ny, nx), vol (H, ny, nx) or
+    None, the first peaks in the order (w descending, g ascending) as a _lib.GRID_PEAK_DTYPE array, the number of peaks
+    and of listed lattice points."""
+    w: np.ndarray
+    theta: np.ndarray
+    vol: object
+    peaks: np.ndarray
+    n_peaks: int
+    listed: int
+
+
 def recovery_params_c(params):
     """A RecoveryParams or RecoveryParamsC as a checked RecoveryParamsC: what the handle layer refuses raises here."""
     p = params if isinstance(params, _lib.RecoveryParamsC) else params.to_c()
@@ -652,6 +665,81 @@ class ParticleFilter:
             self.k.lib.tdr_recovery_reset_host(C.byref(nxt))
         state.w_slow, state.w_fast = nxt.w_slow, nxt.w_fast
         return p, injected
+
+    # ---- pose-grid search (include/tdr.h, "pose-grid search") -----------------------------------------------------------
+    def gridSearch(self, top_down_scan, res, spec, nms_radius=2, max_peaks=8, vol=False):
+        """tdr_filter_grid_search's rule and launches on this filter's torch buffers: top_down_scan (as update takes it) is
+        scored over the lattice of spec (a _lib.GridSpecC, see _lib.grid_spec) as a particle of this filter would be, and
+        the peaks of the weight plane are found on the device.  The filter is read, not changed.  Returns a GridResult."""
+        if self.comm.active:
+            raise ValueError("gridSearch is not available on a sharded filter (the handle path for a rank's slice is not built)")
+        res = float(res)
+        if not (math.isfinite(res) and res > 0.0):
+            raise ValueError("gridSearch: res must be finite and positive")
+        if self.num_particles_ < 1:
+            raise ValueError("gridSearch: the filter has no particles")
+        k, m, n = self.k, self.map_, self.num_particles_
+        H, mode = int(spec.n_headings), int(spec.heading_mode)
+        # what the handle layer refuses raises here, before the scan is packed
+        if not (spec.step >= 1 and spec.nx >= 1 and spec.ny >= 1 and spec.nx * spec.ny <= 1 << 24 and spec.road_only in (0, 1)
+                and mode in (0, 1) and (1 <= H <= 4096 if mode == 1 else H == 1)
+                and (mode == 0 or (math.isfinite(spec.theta0) and math.isfinite(spec.dtheta)))
+                and math.isfinite(spec.scale) and spec.scale > 0.0):
+            raise ValueError("gridSearch: a spec outside its ranges (include/tdr.h, tdr_grid_spec)")
+        if not 0 <= int(nms_radius) <= 16 or not 0 <= int(max_peaks) <= 4096:
+            raise ValueError("gridSearch: nms_radius lies in 0 .. 16, max_peaks in 0 .. 4096")
+        scan_pk = m.scan_handle(top_down_scan)
+        lst = k.grid_list(m.dev, spec)
+        listed = int(lst.numel())
+        w_plane, t_plane, vol_plane = k.grid_planes(spec, vol)
+        if listed:
+            per = min(max(1, k.tuning("inject_cand_chunk") // H), listed)
+            ccap = (per * H + 63) // 64 * 64
+            cst, craw, perm = k.empty((7, ccap)), k.empty((ccap,)), k.empty((ccap,), torch.int32)
+            polar = getattr(m, "polar", True)
+            uniform = float(spec.scale) if self.scale_frozen_ else 0.0      # what set_states notes for equal scales
+            for lo in range(0, listed, per):
+                ms = min(per, listed - lo)
+                nc = ms * H
+                k.grid_candidates(m.dev, spec, lst, lo, ms, cst)
+                if polar:
+                    k.locality_order(cst, nc, m.rows, m.cols, perm)
+                    k.score(m.dev, scan_pk, res, self.fp_c, cst, nc, craw, perm=perm, init_search=mode == 0,
+                            uniform_scale=uniform, n_total=n)
+                else:
+                    rows, cols = m.window_shape()
+                    if mode == 0:
+                        k.score_cart_init(m.dev, scan_pk, rows, cols, res, self.fp_c, cst, nc, n_total=n)
+                    k.locality_order_pose(cst, nc, m.rows, m.cols, perm, theta_radius=(rows + cols) / 16.0)
+                    k.score_cart(m.dev, scan_pk, rows, cols, res, self.fp_c, cst, nc, craw, perm=perm, n_total=n)
+                k.grid_reduce(spec, lst, lo, ms, cst, craw, w_plane, t_plane, vol_plane)
+        peaks, n_peaks = k.grid_peaks(m.dev, spec, w_plane, t_plane, nms_radius, max_peaks)
+        ny, nx = int(spec.ny), int(spec.nx)
+        return GridResult(w_plane.cpu().numpy().reshape(ny, nx), t_plane.cpu().numpy().reshape(ny, nx),
+                          vol_plane.cpu().numpy().reshape(H, ny, nx) if vol else None, peaks, n_peaks, listed)
+
+    def injectCells(self, cells, p, heading_mode=0, seed=0, count=True):
+        """tdr_filter_inject_cells: inject() with the caller's cell list (r * cols + c; duplicates weight the draw) in place
+        of the map's road list, which is what turns the peaks of gridSearch into particles."""
+        if self.comm.active:
+            raise ValueError("injectCells is not available on a sharded filter (the handle path for a rank's slice is not built)")
+        p = float(p)
+        if not (math.isfinite(p) and 0.0 <= p <= 1.0):
+            raise ValueError("injectCells: p must lie in [0, 1]")
+        if heading_mode not in (0, 1):
+            raise ValueError("injectCells: heading_mode is 0 or 1")
+        if self.num_particles_ < 1:
+            raise ValueError("injectCells: the filter has no particles")
+        cells = np.ascontiguousarray(cells, np.uint32).ravel()
+        ncell = self.map_.rows * self.map_.cols
+        if not 1 <= len(cells) <= min(1 << 24, ncell) or int(cells.max()) >= ncell:
+            raise ValueError("injectCells: 1 .. 2^24 cells (at most the map's count), each below rows * cols")
+        th = self.k.inject_threshold(p)
+        out = self.k.inject(self.st, self.num_particles_, self.map_.dev, self.k.to_device(cells.view(np.int32)), seed, self.step_,
+                            th, heading_mode, count=count)
+        if th > 0 and heading_mode == 0:
+            self._maybe_uninit = True
+        return out
 
     def computeMeanCov(self):
         if self.num_particles_ < 1:
